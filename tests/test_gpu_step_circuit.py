@@ -565,6 +565,37 @@ def test_bench_with_the_early_witness_phases_on_the_device(tmp_path):
     assert d["config"]["run_in_steps"] == 8 and d["config"]["tail_steps"] == 8 and "ON THE DEVICE" in d["config"]["stages"]
 
 
+def test_bench_dump_outputs_hold_the_last_proofs(tmp_path):
+    """bench.py --dump-outputs DIR: exactly --steps timed steps, and per chain the last proof vpbs_ivc_prove_pbs returned -- its bytes and the
+    same proof parsed (caps, openings, FRI words, public inputs) as exact 32-bit halves; the counter public input is the chain's step count"""
+    import subprocess
+    import sys
+    import __graft_entry__ as entry
+    from vpbs_amd import circuit_file
+    detail, out = str(tmp_path / "detail.json"), tmp_path / "dump"
+    r = subprocess.run([sys.executable, entry.ROOT + "/bench.py", "--steps", "4", "--warmup", "1", "--chains", "2", "--device-witness", "0",
+                        "--no-single-chain", "--no-step-micro", "--no-cpu-baseline", "--no-survey-size", "--no-step-circuit", "--no-batch128",
+                        "--no-whole-pbs", "--no-ivc", "--detail", detail, "--dump-outputs", str(out)], capture_output=True, text=True, timeout=1500)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+    line, d = _bench_line_and_detail(r.stdout, detail)
+    assert line["steps"] == d["steps"] == 4 and line["ms_per_step"] > 0
+    steps = d["dump_outputs"]["steps_per_chain"]
+    assert steps == 1 + 4 + 3 and not d["dump_outputs"]["sampled"]      # warm-up, timed steps, the host pipeline's tail of three
+    names = sorted(os.listdir(out))
+    assert names == sorted("chain%d_%s.npy" % (c, k) for c in range(2) for k in ("proof_bytes", "caps", "openings", "fri", "public_inputs"))
+    cd = circuit_file.load(circuit_file.find_cyclic_circuit(1024, 2, 4, 5, 728, 16)[0])
+    words = lambda a: a[..., 0].astype(np.uint64) | (a[..., 1].astype(np.uint64) << np.uint64(32))
+    for c in range(2):
+        blob = np.load(out / ("chain%d_proof_bytes.npy" % c))
+        assert blob.dtype == np.float32 and blob.size == d["chain_checks"]["proof_bytes"]
+        proof, pis = api.step_proof_from_bytes(blob.astype(np.uint8).tobytes(), [cd.n_constants + 80, 135, 20, 16], 16, cd.n_constants)
+        for k in ("caps", "openings", "fri"):
+            got = np.load(out / ("chain%d_%s.npy" % (c, k)))
+            assert got.dtype == np.float64 and (words(got) == proof[k]).all()
+        got_pis = words(np.load(out / ("chain%d_public_inputs.npy" % c)))
+        assert (got_pis == pis).all() and int(pis[2 * 1024]) == steps
+
+
 def test_bench_contract_with_two_ranks_sharing_the_gpu(tmp_path):
     """The driver's multi-GPU launch of bench.py (torch.distributed.run, one rank per GPU, replicas: independent chains per rank, no
     data-path collective) with both ranks on the one device of the test box (--device 0, gloo for the barriers): ONE JSON line from rank 0,

@@ -798,3 +798,31 @@ def test_every_compat_position_oracle_prover_vs_product_verifier(pos):
         # read with the prefix the first public input is taken for a length that the buffer does not have
         with pytest.raises(api.VpbsError):
             api.step_proof_from_bytes(blob, ncols, log_n, 1, compat=flipped("bytes_pi_len_prefix"))
+
+
+def test_bench_dump_outputs_are_exact_and_bounded(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: 64-bit words go out as exact (low, high) 32-bit halves in float64; over the budget every array keeps the
+    same seeded sample of its rows on every run, with the row indices beside it, and the files stay within the budget"""
+    import bench
+    words = np.array([0, 1, P - 1, P, (1 << 64) - 1, 0x123456789ABCDEF0], np.uint64)
+    h = bench.u64_halves(words)
+    assert h.dtype == np.float64 and h.shape == (6, 2)
+    assert [int(lo) + (int(hi) << 32) for lo, hi in h] == [int(w) for w in words]
+    small = {"a": bench.u64_halves(words), "b": np.arange(5, dtype=np.float32)}
+    info = bench.dump_outputs(str(tmp_path / "small"), small)
+    assert not info["sampled"] and sorted(os.listdir(tmp_path / "small")) == ["a.npy", "b.npy"]
+    assert (np.load(tmp_path / "small" / "a.npy") == small["a"]).all() and np.load(tmp_path / "small" / "b.npy").dtype == np.float32
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 4096)
+    big = {"x": np.arange(4000, dtype=np.float32), "y": np.arange(3000, dtype=np.float64).reshape(1500, 2)}
+    runs = []
+    for name in ("r1", "r2"):
+        info = bench.dump_outputs(str(tmp_path / name), big, rank=1, world=2)
+        files = sorted(os.listdir(tmp_path / name))
+        assert info["sampled"] and files == ["rank1_x.npy", "rank1_x_rows.npy", "rank1_y.npy", "rank1_y_rows.npy"]
+        arrays = {f: np.load(tmp_path / name / f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert sum(a.nbytes for a in arrays.values()) <= 4096
+        assert (arrays["rank1_x.npy"] == big["x"][arrays["rank1_x_rows.npy"].astype(np.int64)]).all()
+        assert (arrays["rank1_y.npy"] == big["y"][arrays["rank1_y_rows.npy"].astype(np.int64)]).all()
+        runs.append(arrays)
+    assert all((runs[0][f] == runs[1][f]).all() for f in runs[0])

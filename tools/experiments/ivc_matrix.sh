@@ -9,10 +9,8 @@ cd "$GRAFT_REPO_ROOT" 2>/dev/null || cd "$(dirname "$0")/../.."
 declare -A PRESET=(
   [cpu_share_now]="2:6:64:250 2:6:64:250 2:8:64:250 4:6:64:250 4:8:64:250 4:8:64:250 16:8:64:200 16:6:0:200"
   [few_cpus_repeat]="2:6:64:300 2:6:64:200 2:6:64:300 2:6:64:200 4:6:64:300 4:6:64:200 16:6:64:300 2:6:64:730"
-  [hw_queues_dw]="GPU_MAX_HW_QUEUES=8:16:6:64:200 GPU_MAX_HW_QUEUES=8:4:6:64:200 GPU_MAX_HW_QUEUES=16:16:6:64:200 GPU_MAX_HW_QUEUES=16:4:6:64:200 GPU_MAX_HW_QUEUES=24:16:6:64:200 GPU_MAX_HW_QUEUES=24:4:6:64:200 GPU_MAX_HW_QUEUES=16:16:6:0:200 GPU_MAX_HW_QUEUES=8:16:6:0:200"
-  [hw_queues_dw2]="GPU_MAX_HW_QUEUES=16:4:8:64:200 GPU_MAX_HW_QUEUES=16:4:10:64:200 GPU_MAX_HW_QUEUES=16:2:6:64:200 GPU_MAX_HW_QUEUES=16:2:8:64:200 GPU_MAX_HW_QUEUES=12:4:6:64:200 GPU_MAX_HW_QUEUES=16:16:8:64:200 GPU_MAX_HW_QUEUES=16:4:6:32:200"
+  [hw_queues_dw2]="4:8:64:200 4:10:64:200 2:6:64:200 2:8:64:200 16:8:64:200 4:6:32:200"
   [more_chains_few_cpus]="2:10:64:200 2:12:64:200 2:8:64:200 4:10:64:200 4:12:64:200 2:10:32:200"
-  [host8_queues]="GPU_MAX_HW_QUEUES=8:16:8:0:200 GPU_MAX_HW_QUEUES=12:16:8:0:200 GPU_MAX_HW_QUEUES=16:16:8:0:200 VPBS_LATE_THREADS=6:16:8:0:200"
   [host_chains_16cpus]="16:8:0:200 16:9:0:200 16:10:0:200 16:12:0:200"
   [auto_blocking_ab]="16:6:0:200 VPBS_BLOCKING_SYNC=0:16:6:0:200 16:1:0:300 VPBS_BLOCKING_SYNC=0:16:1:0:300 8:8:64:200"
   [blocking_at_8_cpus]="VPBS_BLOCKING_SYNC=0:8:8:64:200 VPBS_BLOCKING_SYNC=1:8:8:64:200 VPBS_BLOCKING_SYNC=0:10:8:64:200 VPBS_BLOCKING_SYNC=1:10:8:64:200"

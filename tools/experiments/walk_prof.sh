@@ -1,5 +1,4 @@
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-export GPU_MAX_HW_QUEUES=16
 F="--no-cpu-baseline --no-step-micro --no-single-chain --no-step-circuit --no-whole-pbs --no-survey-size --no-ivc --no-batch128"
 rm -rf gpurun_out/prof_walk
 rocprofv3 --kernel-trace --output-format csv -d gpurun_out/prof_walk -- python3 bench.py $F --device-witness 30 --device-late --chains 1 --steps 30 --warmup 4 --detail /dev/null > /dev/null 2> gpurun_out/prof_walk.err

@@ -15,7 +15,6 @@ rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d gpurun_out/prof
 [ "$1" = "quick" ] && exit 0
 bash tools/prof_chain.sh 1 chain1 | tail -2
 bash tools/prof_chain.sh 8 chain8 | tail -2
-export GPU_MAX_HW_QUEUES=8
 rm -rf gpurun_out/prof_n2048 gpurun_out/pmc2048_a
 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_n2048 -- python3 tools/prove_ivc.py 2048 728 17 24 > gpurun_out/prof_n2048_chain.json 2> gpurun_out/prof_n2048.err
 f=$(ls gpurun_out/prof_n2048/*/*kernel_stats.csv 2>/dev/null | head -1); [ -n "$f" ] && cp "$f" gpurun_out/prof_n2048_kernel_stats.csv
