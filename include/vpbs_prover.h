@@ -36,8 +36,9 @@ typedef enum {
     VPBS_ERR_DEVICE = -2,    /* HIP runtime error (no device, launch failure, ...) */
     VPBS_ERR_OOM = -3,       /* device allocation failed */
     VPBS_ERR_POW = -4,       /* forced proof-of-work nonce is not valid / search exhausted */
-    VPBS_ERR_PEER = -5       /* a sharded step proof: ANOTHER rank of the communicator failed (its own call returns its own error); every
+    VPBS_ERR_PEER = -5,      /* a sharded step proof: ANOTHER rank of the communicator failed (its own call returns its own error); every
                                 rank of the step returns an error, none hangs in a collective */
+    VPBS_ERR_WITNESS = -6    /* a checked step proof / IVC chain: the witness does not satisfy the circuit (the message names the violation) */
 } vpbs_status;
 
 #define VPBS_POW_ANY UINT64_MAX
@@ -473,6 +474,18 @@ void vpbs_witness_device_free(vpbs_witness_device* dev);
  * vpbs_prove_step is a polynomial and the proof will verify. */
 int vpbs_check_witness(const vpbs_circuit* circuit, const uint64_t* wires /* [n_wires][n] */, const uint64_t public_inputs_hash[4],
                        char* err, size_t err_len);
+/* The same check on the device, with the same verdict and the same message for every input (the constraints are evaluated with the host
+ * checker's arithmetic, so a non-canonical word is judged as vpbs_check_witness judges it).  create uploads the circuit's tables once (row ->
+ * gate, constants, copy pairs, gates; the rows grouped by gate so that a wave evaluates one gate kind); the circuit's arrays may be freed
+ * afterwards.  run: wires [n_wires][n] on the host (on_device = 0, staged through a device buffer of the checker) or in device memory
+ * (on_device = 1, e.g. gathered by vpbs_witness_device_wires; read on the context's stream after the work already queued there).  Returns 1 =
+ * satisfied, 0 = violated (err: vpbs_check_witness's message for the first violation -- lowest row, then lowest constraint; a copy pair only
+ * when no gate row is violated), < 0 = error (err / vpbs_last_error).  One run at a time per checker. */
+typedef struct vpbs_witness_checker vpbs_witness_checker;
+int vpbs_witness_checker_create(vpbs_ctx* ctx, const vpbs_circuit* circuit, vpbs_witness_checker** out, char* err, size_t err_len);
+void vpbs_witness_checker_free(vpbs_witness_checker* chk);
+int vpbs_witness_checker_run(vpbs_witness_checker* chk, const uint64_t* wires, int on_device, const uint64_t public_inputs_hash[4], char* err,
+                             size_t err_len);
 
 /* ---- one step proof minus the host-only stages (transcript order of Appendix A.3) ---- */
 /* Progress of a step proof, for a host that starts consuming the proof before it is complete (the IVC chain: the next step's in-circuit
@@ -570,6 +583,12 @@ int vpbs_step_sizes_get(const vpbs_ctx* ctx, const vpbs_step_inputs* in, vpbs_st
  * challenges_out (optional, may be NULL): betas[nc], gammas[nc], alphas[nc], zeta[2]. */
 int vpbs_prove_step(vpbs_ctx* ctx, const vpbs_step_inputs* in, uint64_t* caps_out, uint64_t* openings_out,
                     uint64_t* fri_out, vpbs_challenger_state* challenger_out, uint64_t* challenges_out);
+/* vpbs_prove_step with the witness checked on the device first: the check of the step's device wires (`chk`, made for this circuit on this
+ * context's device) is queued behind the wires commitment and its verdict arrives with the read-back of the wires cap -- no extra host round
+ * trip.  A satisfied witness gives the proof vpbs_prove_step gives; a violated one returns VPBS_ERR_WITNESS with vpbs_check_witness's message
+ * in vpbs_last_error, and the context stays usable. */
+int vpbs_prove_step_checked(vpbs_ctx* ctx, vpbs_witness_checker* chk, const vpbs_step_inputs* in, uint64_t* caps_out, uint64_t* openings_out,
+                            uint64_t* fri_out, vpbs_challenger_state* challenger_out, uint64_t* challenges_out);
 /* The same step proof with every commitment coset-sharded over comm->world ranks (one GPU each).  Every rank holds the
  * full input matrices and runs the identical transcript; a rank computes the LDE, leaf hashes and Merkle subtrees of its
  * own cosets only (1/world of the dominant work), caps are assembled with comm->allgather, the FRI rounds are computed
@@ -711,6 +730,13 @@ void vpbs_ivc_free(vpbs_ivc* ivc);
  * matrix of a step no longer crosses PCIe and a chain needs about one host CPU instead of five; the proofs are the same bytes.  A batch of
  * 64 costs 2 x 0.9 GB of device memory at the paper's parameters (1.78 M value slots per instance).  batch = 0 returns to the host pipeline. */
 int vpbs_ivc_set_device_witness(vpbs_ivc* ivc, unsigned ELL, unsigned LOGB, unsigned batch, int late_on_device);
+/* on != 0: every witness of the chain -- the base proof's dummy witness and every step's, in the host pipeline and in the device-witness
+ * pipeline alike -- is checked on the device before it is proven (vpbs_prove_step_checked); a violated one stops vpbs_ivc_prove_pbs with
+ * VPBS_ERR_WITNESS and err = "step k: <vpbs_check_witness's message>" ("base proof: ..." for the dummy witness).  Off by default.  A sharded
+ * chain (comm != NULL) refuses checking: VPBS_ERR_INVALID.  The call resets the counters of vpbs_ivc_witness_checks: out[0] witnesses checked,
+ * out[1] violations found since. */
+int vpbs_ivc_set_check_witness(vpbs_ivc* ivc, int on);
+int vpbs_ivc_witness_checks(const vpbs_ivc* ivc, uint64_t out[2]);
 /* late_on_device != 0: the late phase on the device as well -- once the previous proof exists its words go to the device object that holds
  * the step's early values, the late generators run there as a level schedule of their own (vpbs_witness_device_run_late: ~160 dependent
  * levels, one instance), and all the step's wires are gathered into the prover's matrix: the host generates no witness at all (it keeps

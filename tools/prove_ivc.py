@@ -351,6 +351,10 @@ def main():
     # the chain runs inside the library (vpbs_ivc_prove_pbs; with several GPUs every rank calls it with its communicator);
     # VPBS_IVC_DRIVER=python: the same loop spelled out here over the C ABI
     native_driver = os.environ.get("VPBS_IVC_DRIVER", "library") != "python"
+    # VPBS_IVC_CHECK_WITNESS=1: the library checks every witness on the device before proving it (library driver, one GPU)
+    check_witness = os.environ.get("VPBS_IVC_CHECK_WITNESS", "") not in ("", "0")
+    if check_witness and not (native_driver and world == 1):
+        raise SystemExit("VPBS_IVC_CHECK_WITNESS needs the library driver on one GPU (a sharded chain is not checked)")
     chains = []
     for ci in range(n_chains):   # every chain has its own context (stream, device memory), circuit commitments and witness plans
         ctx = vpbs_amd.Context(device, log_n_max=max(16, log_n))
@@ -367,6 +371,8 @@ def main():
             ivc = api.Ivc(ctx, cd, dd, N, K, K * ELL * K * N, comm)
             if int(os.environ.get("VPBS_IVC_DEVICE_WITNESS", "0")):   # early witness phases on the device, this many steps per batch
                 ivc.set_device_witness(ELL, LOGB, int(os.environ["VPBS_IVC_DEVICE_WITNESS"]), os.environ.get("VPBS_IVC_DEVICE_LATE", "") not in ("", "0"))
+            if check_witness:   # every witness of the chain checked on the device before it is proven (vpbs_ivc_set_check_witness)
+                ivc.set_check_witness(True)
             chains.append((ctx, ivc, cd))
         else:
             chains.append((ctx, Circuit(ctx, cyc_path, comm, dist_device), Circuit(ctx, dummy_path)))
@@ -433,6 +439,7 @@ def main():
         "other_chains": [{k: r[k] for k in ("seconds", "message", "decrypted")} for r in results[1:]],
         "before_the_clock": {"circuit_files_commit_plan_s": t_setup, "seeded_keygen_s": r0["keygen_s"]},
         "cpu_by_role": cpu_report,
+        "witness_checks": [dict(zip(("checked", "violations"), c.witness_checks())) for _, c, _ in chains] if check_witness else None,
         "checks": "final proof serialised, parsed back and verified by vpbs_verify_step (full check); its public inputs carry the test vector, "
                   "counter = number of steps, the circuit's own verifier data, the native accumulator and both native chain hashes"
                   + ("; the bootstrapped ciphertext decrypts to the message" if steps == total else "")}))

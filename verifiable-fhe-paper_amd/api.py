@@ -19,6 +19,14 @@ class VpbsError(RuntimeError):
     pass
 
 
+ERR_WITNESS = -6   # VPBS_ERR_WITNESS
+
+
+class WitnessError(VpbsError):
+    """a checked step proof refused a witness that does not satisfy the circuit; str() is vpbs_check_witness's message"""
+    status = ERR_WITNESS
+
+
 class ChallengerStateC(C.Structure):
     _fields_ = [("sponge", C.c_uint64 * 12), ("input", C.c_uint64 * 8), ("output", C.c_uint64 * 8),
                 ("input_len", C.c_uint32), ("output_len", C.c_uint32)]
@@ -259,6 +267,12 @@ SIGNATURES = {
     "vpbs_witness_device_has_late": (_i, [_vp]),
     "vpbs_witness_device_run_late": (_i, [C.c_void_p, C.c_uint, U64P]),
     "vpbs_ctx_device": (_i, [_vp]),
+    "vpbs_witness_checker_create": (_i, [_vp, C.POINTER(CircuitC), C.POINTER(_vp), C.c_char_p, _sz]),
+    "vpbs_witness_checker_free": (None, [_vp]),
+    "vpbs_witness_checker_run": (_i, [_vp, _vp, _i, U64P, C.c_char_p, _sz]),
+    "vpbs_prove_step_checked": (_i, [_vp, _vp, C.POINTER(StepInputsC), U64P, U64P, U64P, C.POINTER(ChallengerStateC), U64P]),
+    "vpbs_ivc_set_check_witness": (_i, [_vp, _i]),
+    "vpbs_ivc_witness_checks": (_i, [_vp, U64P]),
     "vpbs_ivc_prove_pbs": (C.c_long, [_vp, U64P, U64P, U64P, U64P, _ui, _ui, C.POINTER(C.c_uint8), _sz, C.POINTER(IvcTimingC), C.c_char_p, _sz]),
     "vpbs_verify_pbs": (_i, [C.POINTER(VerifyPbsInputsC), C.POINTER(C.c_uint8), _sz, C.c_char_p, _sz]),
     "vpbs_blind_rotate_step": (_i, [_vp, C.POINTER(TfheParamsC), _ui, _vp, _vp, _vp, _i, _i, _i, _vp, _i]),
@@ -687,6 +701,45 @@ class WitnessPlan:
             pass
 
 
+class WitnessChecker:
+    """vpbs_witness_checker: vpbs_check_witness on the device (same verdict, same message); the circuit's tables are uploaded once."""
+
+    def __init__(self, ctx, circuit):
+        self.ctx, self.circuit = ctx, circuit
+        h, err = C.c_void_p(), C.create_string_buffer(512)
+        rc = lib().vpbs_witness_checker_create(ctx.h, C.byref(circuit.c), C.byref(h), err, 512)
+        if rc:
+            raise VpbsError("vpbs_witness_checker_create: status %d: %s" % (rc, err.value.decode()))
+        self.h = h
+        ctx._batches.add(self)   # like a batch, a checker must not outlive its context: Context.close() frees the survivors
+
+    def check(self, wires, pi_hash):
+        """wires: a host matrix [n_wires][n] or a device pointer (int) to one -> (ok, message of the first violation)"""
+        h = _u64(pi_hash)
+        assert h.size == 4
+        err = C.create_string_buffer(512)
+        if isinstance(wires, int):
+            rc = lib().vpbs_witness_checker_run(self.h, wires, 1, _ptr(h), err, 512)
+        else:
+            w = _u64(wires)
+            assert w.shape == (self.circuit.n_wires, self.circuit.n)
+            rc = lib().vpbs_witness_checker_run(self.h, w.ctypes.data, 0, _ptr(h), err, 512)
+        if rc < 0:
+            raise VpbsError("vpbs_witness_checker_run: status %d: %s" % (rc, err.value.decode()))
+        return rc == 1, err.value.decode()
+
+    def free(self):
+        if self.h:
+            lib().vpbs_witness_checker_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
 class WitnessDevice:
     """vpbs_witness_device: the plan's schedule replayed on the device for a batch of PartialWitnesses (create once per circuit)."""
 
@@ -837,6 +890,19 @@ class Ivc:
         rc = lib().vpbs_ivc_set_device_witness(self.h, ELL, LOGB, batch, 1 if late_on_device else 0)
         if rc != 0:
             raise VpbsError("vpbs_ivc_set_device_witness: status %d: %s" % (rc, lib().vpbs_ivc_last_error(self.h).decode()))
+
+    def set_check_witness(self, on=True):
+        """vpbs_ivc_set_check_witness: every witness of later chains (base proof and steps) checked on the device before it is proven; a
+        violation stops prove_pbs with VpbsError "... step k: <message>".  Resets the counters of witness_checks()."""
+        rc = lib().vpbs_ivc_set_check_witness(self.h, 1 if on else 0)
+        if rc != 0:
+            raise VpbsError("vpbs_ivc_set_check_witness: status %d: %s" % (rc, lib().vpbs_ivc_last_error(self.h).decode()))
+
+    def witness_checks(self):
+        """-> (witnesses checked, violations found) since the last set_check_witness"""
+        out = np.zeros(2, np.uint64)
+        lib().vpbs_ivc_witness_checks(self.h, _ptr(out))
+        return int(out[0]), int(out[1])
 
     def on_step(self, fn):
         """vpbs_ivc_set_step_callback: fn(done) runs on the proving thread with done = 0 after the base proof and 1 .. steps after each
@@ -1233,6 +1299,22 @@ class Context:
         else:
             self._check(lib().vpbs_prove_step_sharded(self.h, C.byref(si), C.byref(comm), _ptr(caps), _ptr(openings), _ptr(fri),
                                                       C.byref(ch.c), _ptr(chal)))
+        return {"caps": caps, "openings": openings, "fri": fri, "challenger": ch, "challenges": chal}
+
+    def prove_step_checked(self, si, checker):
+        """vpbs_prove_step_checked: prove_step with the witness checked on the device first (checker: a WitnessChecker of the circuit on
+        this context's device).  A violated witness raises WitnessError with vpbs_check_witness's message; the context stays usable."""
+        sizes = StepSizesC()
+        self._check(lib().vpbs_step_sizes_get(self.h, C.byref(si), C.byref(sizes)))
+        caps = np.zeros((3, sizes.cap_words // 4, 4), np.uint64)
+        openings = np.zeros((sizes.openings_words // 2, 2), np.uint64)
+        fri = np.zeros(sizes.fri_words, np.uint64)
+        ch = ChallengerState()
+        chal = np.zeros(3 * si.num_challenges + 2, np.uint64)
+        rc = lib().vpbs_prove_step_checked(self.h, checker.h, C.byref(si), _ptr(caps), _ptr(openings), _ptr(fri), C.byref(ch.c), _ptr(chal))
+        if rc == ERR_WITNESS:
+            raise WitnessError(lib().vpbs_last_error(self.h).decode())
+        self._check(rc)
         return {"caps": caps, "openings": openings, "fri": fri, "challenger": ch, "challenges": chal}
 
     def step_proof_to_bytes(self, si, n_constants, proof):

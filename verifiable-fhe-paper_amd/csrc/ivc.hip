@@ -62,6 +62,11 @@ struct Side {   // one circuit on the context
     vpbs_batch* cs = nullptr;
     vpbs_witness_plan* plan = nullptr;
     const vpbs_comm* comm = nullptr;   // not null: every commitment and proof of this circuit is coset-sharded over comm->world GPUs
+    // the witness check (vpbs_ivc_set_check_witness): the circuit's tables are kept on the host so that a checker can be made later
+    std::vector<uint32_t> row_gate, copies;
+    std::vector<u64> constants;
+    vpbs_witness_checker* chk = nullptr;
+    u64* checks = nullptr;             // {witnesses checked, violations}, the chain's counters
 
     int init(vpbs_ctx* c, const vpbs_ivc_circuit& d, unsigned cap_height, const vpbs_comm* cm, std::string& err) {
         ctx = c;
@@ -70,6 +75,9 @@ struct Side {   // one circuit on the context
         log_n = k.log_n; n_wires = k.n_wires; n_routed = k.n_routed; n_const_cols = k.n_constants_cols; num_selectors = k.num_selectors;
         n = (size_t)1 << log_n;
         gates.assign(k.gates, k.gates + k.n_gates);
+        row_gate.assign(k.row_gate, k.row_gate + n);
+        copies.assign(k.copies, k.copies + 2 * k.n_copies);
+        constants.assign(k.constants, k.constants + (size_t)n_const_cols * n);
         if (d.pi_pos) pi_pos.assign(d.pi_pos, d.pi_pos + d.n_pi);
         n_pi = d.n_pi;
         n_preset = d.n_preset;
@@ -122,10 +130,31 @@ struct Side {   // one circuit on the context
         in.gates = gates.data(); in.n_gates = (unsigned)gates.size(); in.num_selectors = num_selectors;
     }
     int prove(const vpbs_step_inputs& in, u64* caps, u64* openings, u64* fri) const {
+        if (chk) {   // never sharded (vpbs_ivc_set_check_witness refuses a chain with a communicator)
+            const int rc = vpbs_prove_step_checked(ctx, chk, &in, caps, openings, fri, nullptr, nullptr);
+            if (rc == VPBS_OK || rc == VPBS_ERR_WITNESS) ++checks[0];
+            if (rc == VPBS_ERR_WITNESS) ++checks[1];
+            return rc;
+        }
         return comm ? vpbs_prove_step_sharded(ctx, &in, comm, caps, openings, fri, nullptr, nullptr)
                     : vpbs_prove_step(ctx, &in, caps, openings, fri, nullptr, nullptr);
     }
+    // a checker of this circuit on the context (on) or none (!on)
+    int set_check(bool on, u64* counters, std::string& err) {
+        if (chk) vpbs_witness_checker_free(chk);
+        chk = nullptr;
+        checks = counters;
+        if (!on) return VPBS_OK;
+        const vpbs_circuit k{log_n, n_wires, n_routed, gates.data(), (unsigned)gates.size(), num_selectors, row_gate.data(), constants.data(),
+                             n_const_cols, copies.data(), copies.size() / 2, nullptr, 0};
+        char e[256] = {0};
+        const int rc = vpbs_witness_checker_create(ctx, &k, &chk, e, sizeof e);
+        if (rc != VPBS_OK) err = std::string("witness checker: ") + e;
+        return rc;
+    }
     void release() {
+        if (chk) vpbs_witness_checker_free(chk);
+        chk = nullptr;
         if (plan) vpbs_witness_plan_free(plan);
         if (cs) vpbs_batch_free(cs);
         if (d_sigma) vpbs_device_free(ctx, d_sigma);
@@ -269,6 +298,7 @@ struct vpbs_ivc {
     vpbs_ctx* wctx[2] = {nullptr, nullptr};
     vpbs_witness_device* wdev[2] = {nullptr, nullptr};
     u64* dw_presets = nullptr;   // pinned [n_preset][dw_batch]
+    u64 checks[2] = {0, 0};      // vpbs_ivc_witness_checks
     size_t late_in_count = 0;
     void drop_device_witness() {
         for (int i = 0; i < 2; ++i) {
@@ -423,6 +453,31 @@ int vpbs_ivc_set_step_callback(vpbs_ivc* v, vpbs_ivc_step_fn fn, void* user) {
 }
 
 const char* vpbs_ivc_last_error(const vpbs_ivc* v) { return v ? v->err.c_str() : ""; }
+
+int vpbs_ivc_set_check_witness(vpbs_ivc* v, int on) {
+    if (!v) return VPBS_ERR_INVALID;
+    v->err.clear();
+    if (on && v->cyc.comm) {   // a rank that stopped after its collectives began would leave its peers waiting
+        v->err = "witness checking is not available for a sharded chain";
+        return VPBS_ERR_INVALID;
+    }
+    v->checks[0] = v->checks[1] = 0;
+    int rc = v->cyc.set_check(on != 0, v->checks, v->err);
+    if (rc == VPBS_OK) rc = v->dum.set_check(on != 0, v->checks, v->err);
+    if (rc != VPBS_OK) {
+        std::string keep;
+        (void)v->cyc.set_check(false, v->checks, keep);
+        (void)v->dum.set_check(false, v->checks, keep);
+    }
+    return rc;
+}
+
+int vpbs_ivc_witness_checks(const vpbs_ivc* v, uint64_t out[2]) {
+    if (!v || !out) return VPBS_ERR_INVALID;
+    out[0] = v->checks[0];
+    out[1] = v->checks[1];
+    return VPBS_OK;
+}
 
 int vpbs_ivc_verifier_data(const vpbs_ivc* v, uint64_t* cyclic_vk, uint64_t* dummy_vk) {
     if (!v) return VPBS_ERR_INVALID;

@@ -10,6 +10,7 @@
 #include <cstdlib>
 
 #include "host/plonky2_mirror.h"
+#include "witness_check.h"
 
 using vpbs::DeviceError;
 using vpbs::Timed;
@@ -828,7 +829,8 @@ void maybe_inject_fault(const vpbs_comm* comm, int stage) {
 }  // namespace
 
 static int prove_step_impl(vpbs_ctx* ctx, const vpbs_step_inputs* in, const vpbs_comm* comm, uint64_t* caps_out, uint64_t* openings_out,
-                           uint64_t* fri_out, vpbs_challenger_state* challenger_out, uint64_t* challenges_out);
+                           uint64_t* fri_out, vpbs_challenger_state* challenger_out, uint64_t* challenges_out,
+                           vpbs_witness_checker* chk = nullptr);
 
 // the sharded form: the same prover under a ShardSession, which sees to it that every rank leaves the step through all of its collectives
 static int prove_step_sharded_impl(vpbs_ctx* ctx, const vpbs_step_inputs* in, const vpbs_comm* comm, uint64_t* caps_out, uint64_t* openings_out,
@@ -857,8 +859,9 @@ static int prove_step_sharded_impl(vpbs_ctx* ctx, const vpbs_step_inputs* in, co
     return rc;
 }
 
+// chk (vpbs_prove_step_checked, never with a communicator): the witness check of the device wires rides on the wires commitment
 static int prove_step_impl(vpbs_ctx* ctx, const vpbs_step_inputs* in, const vpbs_comm* comm, uint64_t* caps_out, uint64_t* openings_out,
-                           uint64_t* fri_out, vpbs_challenger_state* challenger_out, uint64_t* challenges_out) {
+                           uint64_t* fri_out, vpbs_challenger_state* challenger_out, uint64_t* challenges_out, vpbs_witness_checker* chk) {
     if (!ctx || !in || !caps_out || !openings_out || !fri_out || !in->constants_sigmas) return VPBS_ERR_INVALID;
     if (comm && (comm->world == 0 || comm->rank >= comm->world || (comm->world > 1 && (!comm->allgather || !comm->allreduce_sum))))
         return VPBS_ERR_INVALID;
@@ -912,7 +915,14 @@ static int prove_step_impl(vpbs_ctx* ctx, const vpbs_step_inputs* in, const vpbs
         PolynomialBatch wires = PolynomialBatch::from_values(ctx, d_wires, in->n_wires, log_n, false, comm);
         HashOut pi_hash;  // hashed on the host while the device works on the wires commitment
         vpbs_hash_no_pad(in->public_inputs, in->n_public_inputs, pi_hash.data());
+        // the witness check: queued behind the commitment (the hash it needs was just computed beside it), its verdict arrives in pinned
+        // memory with the cap read-back below -- no synchronisation of its own
+        if (chk) vpbs::witness_check_enqueue(chk, s, d_wires, pi_hash.data());
         wires.merkle_cap(caps_out, comm);
+        if (chk) {
+            std::string violation;
+            if (!vpbs::witness_check_result(chk, violation)) throw DeviceError{VPBS_ERR_WITNESS, violation};
+        }
         Challenger challenger;
         challenger.observe_elements(in->circuit_digest, 4);
         challenger.observe_hash(pi_hash);
@@ -1014,6 +1024,15 @@ static int prove_step_impl(vpbs_ctx* ctx, const vpbs_step_inputs* in, const vpbs
 int vpbs_prove_step(vpbs_ctx* ctx, const vpbs_step_inputs* in, uint64_t* caps_out, uint64_t* openings_out, uint64_t* fri_out,
                     vpbs_challenger_state* challenger_out, uint64_t* challenges_out) {
     return prove_step_impl(ctx, in, nullptr, caps_out, openings_out, fri_out, challenger_out, challenges_out);
+}
+int vpbs_prove_step_checked(vpbs_ctx* ctx, vpbs_witness_checker* chk, const vpbs_step_inputs* in, uint64_t* caps_out, uint64_t* openings_out,
+                            uint64_t* fri_out, vpbs_challenger_state* challenger_out, uint64_t* challenges_out) {
+    if (!ctx || !in) return VPBS_ERR_INVALID;
+    if (!vpbs::witness_check_fits(chk, ctx, in->log_n, in->n_wires)) {
+        ctx->err = "vpbs_prove_step_checked: the checker was made for another circuit shape or device";
+        return VPBS_ERR_INVALID;
+    }
+    return prove_step_impl(ctx, in, nullptr, caps_out, openings_out, fri_out, challenger_out, challenges_out, chk);
 }
 int vpbs_prove_step_sharded(vpbs_ctx* ctx, const vpbs_step_inputs* in, const vpbs_comm* comm, uint64_t* caps_out, uint64_t* openings_out,
                             uint64_t* fri_out, vpbs_challenger_state* challenger_out, uint64_t* challenges_out) {
