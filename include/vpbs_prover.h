@@ -674,6 +674,31 @@ long vpbs_step_proof_from_bytes(const vpbs_verify_inputs* in, const uint8_t* byt
 int vpbs_verify_step(const vpbs_verify_inputs* in, const uint64_t* caps /* [3][cap] */, const uint64_t* openings,
                      const uint64_t* fri);
 
+/* ---- batch verifier of serialised step proofs on the device (csrc/verify_batch.hip) ----
+ * For proof i = bytes[offsets[i] .. offsets[i + 1]) (host memory, as vpbs_step_proof_to_bytes writes it), verdicts[i] = 1 exactly when
+ * vpbs_step_proof_from_bytes(circuit, ..., public_inputs_capacity = max_public_inputs) >= 0 and vpbs_verify_step accepts what it parsed,
+ * under the same compat table.  `circuit` is the struct vpbs_verify_step takes; its public_inputs / n_public_inputs are ignored (every proof
+ * carries its own) and gate_terms_zeta without gates is refused (one zeta per proof).  reasons[i] (may be NULL) names the first failing
+ * check in the host verifier's order: MALFORMED (parse) -> VANISHING -> POW -> FRI -> MERKLE; VPBS_VERIFY_OK for an accepted proof.
+ * create uploads the cap, the gates and the layout tables once (at most 4 challenges, max_batch <= 65535); run returns the number of
+ * accepted proofs, VPBS_ERR_INVALID for count > max_batch, offsets that decrease or null pointers, VPBS_ERR_DEVICE for a failed launch.
+ * run works on the context's stream and returns when the verdicts are in host memory; one run at a time per verifier.  For one proof the
+ * host verifier is faster: the device pays for the upload and a fixed chain of launches. */
+typedef enum {
+    VPBS_VERIFY_OK = 0,
+    VPBS_VERIFY_MALFORMED = 1,   /* vpbs_step_proof_from_bytes refuses the bytes */
+    VPBS_VERIFY_VANISHING = 2,   /* vanishing(zeta) != Z_H(zeta) t(zeta) (never with fri_only) */
+    VPBS_VERIFY_POW = 3,         /* PoW witness >= p, or its response lacks the leading zeros */
+    VPBS_VERIFY_FRI = 4,         /* a fold consistency check or the final polynomial of some query */
+    VPBS_VERIFY_MERKLE = 5       /* a Merkle path */
+} vpbs_verify_reason;
+typedef struct vpbs_proof_verifier vpbs_proof_verifier;
+int vpbs_proof_verifier_create(vpbs_ctx* ctx, const vpbs_verify_inputs* circuit, size_t max_batch, size_t max_public_inputs,
+                               vpbs_proof_verifier** out, char* err, size_t err_len);
+long vpbs_proof_verifier_run(vpbs_proof_verifier* v, const uint8_t* bytes, const size_t* offsets /* [count + 1] */, size_t count,
+                             uint8_t* verdicts /* [count] */, uint8_t* reasons /* [count] or NULL */);
+void vpbs_proof_verifier_free(vpbs_proof_verifier* v);
+
 /* ---- one verifiable PBS as one call: the IVC chain of verified_pbs (/root/reference/src/vtfhe/ivc_based_vpbs.rs:159-386) ----
  * The cyclic step circuit and its dummy circuit arrive as data (what CircuitBuilder::build leaves behind: vpbs_circuit + the PartialWitness
  * targets in the order verified_pbs sets them + the public-input targets).  vpbs_ivc_create commits their constants / sigmas, derives the

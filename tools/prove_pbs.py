@@ -5,7 +5,7 @@ verifiable-fhe-paper_amd/circuit_file.py: this tool imports no circuit builder; 
 accumulator, counter and hash chains between steps is done by this driver, which is what the in-circuit verifier enforces in the
 reference).  Pipeline: native accumulator chain on the device (vpbs_pbs_accumulator_chain) and native hash chains on the host -> the
 PartialWitness values of every step (the hash chains computed by a host thread beside the device) -> device witness generation in batches (vpbs_witness_device_*) -> gather -> step proofs on
-`provers` contexts -> every proof verified on the host (after the clock).  Keys, test vector and the LWE input are the seeded ones of
+`provers` contexts -> every proof verified on the host (after the clock; VPBS_PBS_VERIFY=device: on the device, one batch per rank).  Keys, test vector and the LWE input are the seeded ones of
 vpbs_keygen / vpbs_lwe_encrypt / vpbs_testv at the paper's noise levels (main.rs:40-52); the final accumulator -- a public input of the last
 proof -- decrypts to the encrypted message under the partial key (main.rs:58-64).
 usage: tools/prove_pbs.py [n_lwe=728] [batch=73] [provers=5]  ->  one JSON line
@@ -37,6 +37,7 @@ def main():
     batch = int(sys.argv[2]) if len(sys.argv) > 2 else 73
     provers = int(sys.argv[3]) if len(sys.argv) > 3 else 5
     steps = n_lwe + 2
+    device_verify = os.environ.get("VPBS_PBS_VERIFY", "host") == "device"
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
     device = int(os.environ.get("VPBS_PBS_DEVICE", os.environ.get("LOCAL_RANK", "0")))
     dist = None
@@ -184,7 +185,8 @@ def main():
                             free_obj.put(k)
                 si = pctx[j].make_step_inputs(b.log_n, d_wires[j].data_ptr(), None, None, css[j], digest, pis, on_device=True, shapes=(135, 20, 16),
                                               sigmas=int(d_sigma.data_ptr()), n_routed=80, n_constants=n_constants, gates=b.gates)
-                results[s] = (pctx[j].prove_step(si), pis)
+                # VPBS_PBS_VERIFY=device keeps the step inputs (and what they point at) to serialise the proof after the clock
+                results[s] = (pctx[j].prove_step(si), pis, si if device_verify else None)
         except Exception as e:
             fail(e)
 
@@ -223,12 +225,21 @@ def main():
     cs_cap = css[0].cap()
 
     def verify(s):
-        proof, pis = results[s]
+        proof, pis = results[s][:2]
         return api.verify_step(proof, cs_cap, [n_constants + 80, 135, 20, 16], digest, pis, b.log_n, check_permutation=True,
                                n_constants=n_constants, n_routed=80, gates=b.gates)
 
-    with ThreadPoolExecutor(max_workers=8) as pool:      # the host verifier releases the GIL: every proof of the chain is checked
-        verdicts = list(pool.map(verify, range(my_first, my_end)))
+    if device_verify:   # every proof of this rank in ONE batch of vpbs_proof_verifier (same verdict as the host verifier)
+        pv = api.ProofVerifier(main_ctx, cs_cap, [n_constants + 80, 135, 20, 16], digest, b.log_n, n_constants=n_constants, n_routed=80,
+                               gates=b.gates, max_batch=max(1, my_end - my_first), max_public_inputs=len(pi_pos))
+        blobs = [pctx[0].step_proof_to_bytes(results[s][2], n_constants, results[s][0]) for s in range(my_first, my_end)]
+        verdicts = [bool(v) for v in pv.verify(blobs)[0]]
+        pv.close()
+        verifier = "vpbs_proof_verifier on the device in one batch per rank (serialisation included)"
+    else:
+        with ThreadPoolExecutor(max_workers=8) as pool:      # the host verifier releases the GIL: every proof of the chain is checked
+            verdicts = list(pool.map(verify, range(my_first, my_end)))
+        verifier = "vpbs_verify_step on 8 host threads per rank"
     assert all(verdicts), [my_first + s for s, v in enumerate(verdicts) if not v][:5]
     checked = my_end - my_first
     t_verify = time.perf_counter() - t0
@@ -261,7 +272,7 @@ def main():
         "message": message, "decrypted": decrypted,
         "checks": "the bootstrapped ciphertext decrypts to the message; accumulator / counter / hash public inputs of all %d proofs equal "
                   "the native chains; all %d proofs verified by "
-                  "vpbs_verify_step on 8 host threads per rank in %.2f s (after the clock)" % (checked, checked, t_verify),
+                  "%s in %.2f s (after the clock)" % (checked, checked, verifier, t_verify),
         "proof_words_kB": proof_bytes / 1e3}))
     if dist:
         dist.barrier()

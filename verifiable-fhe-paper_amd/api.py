@@ -251,6 +251,9 @@ SIGNATURES = {
     "vpbs_witness_device_free": (None, [C.c_void_p]),
     "vpbs_check_witness": (_i, [C.POINTER(CircuitC), U64P, U64P, C.c_char_p, _sz]),
     "vpbs_verify_step": (_i, [C.POINTER(VerifyInputsC), U64P, U64P, U64P]),
+    "vpbs_proof_verifier_create": (_i, [_vp, C.POINTER(VerifyInputsC), _sz, _sz, C.POINTER(_vp), C.c_char_p, _sz]),
+    "vpbs_proof_verifier_run": (C.c_long, [_vp, C.POINTER(C.c_uint8), C.POINTER(_sz), _sz, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]),
+    "vpbs_proof_verifier_free": (None, [_vp]),
     "vpbs_ivc_create": (_i, [_vp, C.POINTER(IvcCircuitC), C.POINTER(IvcCircuitC), _ui, _ui, _sz, C.POINTER(CommC), C.POINTER(_vp), C.c_char_p, _sz]),
     "vpbs_ivc_free": (None, [_vp]),
     "vpbs_ivc_verifier_data": (_i, [_vp, U64P, U64P]),
@@ -850,6 +853,88 @@ def verify_step(proof, cs_cap, ncols, circuit_digest, public_inputs, log_n, num_
     if rc < 0:
         raise VpbsError("vpbs_verify_step: malformed arguments (%d)" % rc)
     return rc == 1
+
+
+VERIFY_OK, VERIFY_MALFORMED, VERIFY_VANISHING, VERIFY_POW, VERIFY_FRI, VERIFY_MERKLE = range(6)   # vpbs_proof_verifier reasons
+
+
+def pack_proofs(blobs):
+    """serialised proofs -> (one uint8 buffer, offsets [count + 1] as size_t): the input of vpbs_proof_verifier_run"""
+    lens = np.fromiter((len(b) for b in blobs), dtype=np.uint64, count=len(blobs))
+    offsets = np.zeros(len(blobs) + 1, np.uint64)
+    np.cumsum(lens, out=offsets[1:])
+    buf = np.frombuffer(b"".join(bytes(b) for b in blobs), dtype=np.uint8) if blobs else np.zeros(0, np.uint8)
+    return buf, offsets
+
+
+class ProofVerifier:
+    """vpbs_proof_verifier: vpbs_step_proof_from_bytes + vpbs_verify_step for a batch of serialised step proofs on the device, with the host's
+    verdict for every one of them.  The parameters mirror verify_step (each proof carries its own public inputs); max_public_inputs is the
+    parser's public_inputs_capacity.  Every proof slot on the device holds the proof's words and max_public_inputs more, max_batch slots:
+    size both to the proofs at hand (the defaults, 256 proofs of up to 8192 public inputs, take ~200 MB for a paper-size step proof)."""
+
+    def __init__(self, ctx, cs_cap, ncols, circuit_digest, log_n, num_challenges=2, check_permutation=True, n_constants=0, n_routed=0,
+                 quotient_degree_factor=8, gates=None, compat=None, rate_bits=3, cap_height=4, max_batch=256, max_public_inputs=1 << 13,
+                 gate_terms_zeta=None):
+        if check_permutation and n_routed == 0:
+            raise ValueError("ProofVerifier: the full check needs n_constants / n_routed (and the gates); check_permutation=False for "
+                             "transcript + FRI only")
+        self.ctx, self.max_batch = ctx, max_batch
+        v = VerifyInputsC()
+        v.log_n, v.rate_bits, v.cap_height = log_n, rate_bits, cap_height
+        v.n_constants_sigmas, v.n_wires, v.n_zs_partial_products, v.n_quotient = ncols
+        v.num_challenges = num_challenges
+        self._cap = _u64(cs_cap)
+        v.constants_sigmas_cap = _ptr(self._cap)
+        for i in range(4):
+            v.circuit_digest[i] = int(circuit_digest[i])
+        v.fri_only = 0 if check_permutation else 1
+        v.n_constants, v.n_routed, v.quotient_degree_factor = n_constants, n_routed, quotient_degree_factor
+        self._gt = _u64(gate_terms_zeta) if gate_terms_zeta is not None else None
+        v.gate_terms_zeta = _ptr(self._gt) if self._gt is not None else None
+        if gates is not None:
+            v.gates, v.n_gates, v.num_selectors = gates.arr, gates.n, gates.num_selectors
+        if compat is not None:
+            self._compat = compat
+            v.compat = C.pointer(compat)
+        h, err = C.c_void_p(), C.create_string_buffer(512)
+        rc = lib().vpbs_proof_verifier_create(ctx.h, C.byref(v), max_batch, max_public_inputs, C.byref(h), err, 512)
+        if rc:
+            raise VpbsError("vpbs_proof_verifier_create: status %d: %s" % (rc, err.value.decode()))
+        self.h = h
+        ctx._batches.add(self)   # must not outlive its context: Context.close() frees the survivors
+
+    def verify_packed(self, buf, offsets):
+        """buf: uint8 buffer, offsets: [count + 1] (pack_proofs) -> (verdicts, reasons), np.uint8 each"""
+        buf = np.ascontiguousarray(buf, dtype=np.uint8)
+        offs = np.ascontiguousarray(offsets, dtype=np.uint64)
+        count = offs.size - 1
+        verdicts, reasons = np.zeros(max(count, 0), np.uint8), np.zeros(max(count, 0), np.uint8)
+        u8p = C.POINTER(C.c_uint8)
+        data = buf.ctypes.data_as(u8p) if buf.size else (C.c_uint8 * 1)()
+        rc = lib().vpbs_proof_verifier_run(self.h, data, offs.ctypes.data_as(C.POINTER(C.c_size_t)), count, verdicts.ctypes.data_as(u8p),
+                                           reasons.ctypes.data_as(u8p))
+        if rc < 0:
+            raise VpbsError("vpbs_proof_verifier_run: status %d" % rc)
+        return verdicts, reasons
+
+    def verify(self, blobs):
+        """list of ProofWithPublicInputs byte strings -> (verdicts, reasons), np.uint8 each"""
+        return self.verify_packed(*pack_proofs(blobs))
+
+    def close(self):
+        if self.h:
+            lib().vpbs_proof_verifier_free(self.h)
+            self.h = None
+            self.ctx._batches.discard(self)
+
+    free = close
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class Ivc:
