@@ -795,6 +795,43 @@ typedef struct {
 } vpbs_verify_pbs_inputs;
 int vpbs_verify_pbs(const vpbs_verify_pbs_inputs* in, const uint8_t* proof_bytes, size_t len, char* why, size_t why_len);
 
+/* ---- batch verifier of whole vPBS proofs on the device (csrc/verify_pbs_batch.hip) ----
+ * vpbs_verify_pbs for many last proofs of IVC chains made under ONE key set.  For proof i = bytes[offsets[i] .. offsets[i + 1]) with
+ * ct[i], out_ct[i] and testv (shared, or testv[i] with testv_per_proof != 0), verdicts[i] equals vpbs_verify_pbs's verdict on the same
+ * inputs and the keys whose hash the object holds; reasons[i] (may be NULL) is its first failing check, in its order; where that is
+ * VPBS_PBS_PROOF, proof_reasons[i] (may be NULL) is the batch verifier's vpbs_verify_reason (VPBS_VERIFY_OK otherwise).  Words are
+ * compared raw, as the host does; a word of ct at or above p enters the LWE chain as its residue, as in vpbs_hash_chain.
+ * vpbs_pbs_key_hash: the key hash chain of vpbs_verify_pbs, hash_no_pad chained over [ggsw_len zeros, bsk_0 .. bsk_{n_lwe-1}, ksk] (host,
+ * n_lwe + 2 links: about 1.9 s at the paper's parameters, once per key set).  create: circuit / N / K / n_lwe / ggsw_len as in
+ * vpbs_verify_pbs_inputs (testv, ct, out_ct, bsk and ksk are not read); the proof stages are a vpbs_proof_verifier's with
+ * max_public_inputs = 2 K N + 13 + cap words.  run returns the number of accepted proofs, VPBS_ERR_INVALID for count > max_batch, null
+ * pointers or offsets that decrease, VPBS_ERR_DEVICE for a failed launch; it works on the context's stream (and one stream of its own for
+ * the LWE chain) and returns when the verdicts are in host memory; one run at a time per verifier. */
+typedef enum {
+    VPBS_PBS_OK = 0,
+    VPBS_PBS_MALFORMED = 1,        /* the bytes are not a proof of the circuit, or their public-input count is not 2 K N + 13 + cap words */
+    VPBS_PBS_TESTV_MASK = 2,       /* the mask polynomials of the claimed test vector are not zero */
+    VPBS_PBS_TESTV = 3,            /* the claimed test vector differs from testv */
+    VPBS_PBS_COUNTER = 4,          /* the counter is not n + 2 */
+    VPBS_PBS_OUT_CT = 5,           /* out_ct is not the proof's accumulator */
+    VPBS_PBS_PROOF = 6,            /* the proof does not verify (proof_reasons: which check) */
+    VPBS_PBS_VERIFIER_DATA = 7,    /* the proof carries another circuit's verifier data */
+    VPBS_PBS_KEY_HASH = 8,         /* the key hash chain does not match */
+    VPBS_PBS_LWE_HASH = 9          /* the LWE hash chain does not match */
+} vpbs_pbs_reason;
+/* exactly the `why` vpbs_verify_pbs writes for that check ("" for VPBS_PBS_OK); NULL for an unknown code */
+const char* vpbs_pbs_reason_text(int reason);
+int vpbs_pbs_key_hash(const uint64_t* bsk /* [n_lwe][ggsw_len] */, const uint64_t* ksk /* [ggsw_len] */, unsigned n_lwe, size_t ggsw_len,
+                      uint64_t out[4]);
+typedef struct vpbs_pbs_verifier vpbs_pbs_verifier;
+int vpbs_pbs_verifier_create(vpbs_ctx* ctx, const vpbs_verify_pbs_inputs* shape, const uint64_t key_hash[4], size_t max_batch,
+                             vpbs_pbs_verifier** out, char* err, size_t err_len);
+long vpbs_pbs_verifier_run(vpbs_pbs_verifier* v, const uint8_t* bytes, const size_t* offsets /* [count + 1] */, size_t count,
+                           const uint64_t* testv /* [N] or [count][N] */, int testv_per_proof, const uint64_t* ct /* [count][n_lwe + 1] */,
+                           const uint64_t* out_ct /* [count][K][N] */, uint8_t* verdicts /* [count] */, uint8_t* reasons /* [count] or NULL */,
+                           uint8_t* proof_reasons /* [count] or NULL */);
+void vpbs_pbs_verifier_free(vpbs_pbs_verifier* v);
+
 /* ---- kernel-level entry points (host buffers; used by parity tests and by callers outside the prover) ---- */
 int vpbs_k_poseidon_batch(vpbs_ctx* ctx, uint64_t* states /* [n][12] in place */, size_t n);
 int vpbs_k_hash_rows(vpbs_ctx* ctx, const uint64_t* rows /* [n][len] */, size_t n, unsigned len, uint64_t* out /* [n][4] */);

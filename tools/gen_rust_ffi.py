@@ -255,6 +255,8 @@ EXCERPT = [
     ("one verifiable PBS as verified_pbs / verify_pbs see it (ivc_based_vpbs.rs:159-386, :388-489)",
      ["vpbs_ivc_create", "vpbs_ivc_set_step_callback", "vpbs_ivc_set_device_witness", "vpbs_ivc_last_error", "vpbs_ivc_verifier_data", "vpbs_ivc_prove_pbs",
       "vpbs_ivc_free", "vpbs_verify_pbs"]),
+    ("many vPBS proofs of one key set verified in one device batch (verify_pbs's verdict and reason for each)",
+     ["vpbs_pbs_key_hash", "vpbs_pbs_reason_text", "vpbs_pbs_verifier_create", "vpbs_pbs_verifier_run", "vpbs_pbs_verifier_free"]),
     ("RCCL collectives of a sharded step (the library binds librccl.so itself)",
      ["vpbs_rccl_available", "vpbs_rccl_unique_id", "vpbs_comm_rccl_create", "vpbs_comm_rccl_destroy"]),
 ]

@@ -13,6 +13,9 @@ usage: tools/prove_ivc.py [N=1024] [n_lwe=728] [log_n=16] [steps=all]   ->  one 
   steps < n + 2 proves only a prefix of the chain (tests); verify_pbs's counter / hash checks are then made against that prefix.
   VPBS_IVC_CHAINS=c: c independent PBS (own keys, message, context, plans) side by side on the one GPU: a chain leaves the GPU idle while its
   host phases run, a second chain fills those gaps -- throughput, not latency.
+  VPBS_IVC_VERIFY=device: the chains share one key set (their ciphertexts differ) and the final proofs of all of them are checked in one
+  device batch (api.PbsVerifier: verify_pbs's verdict and reason for each, the key hash computed once on the host); the JSON line reports
+  the verdicts and the device verification time.  The default (host) checks each chain's proof on the host only.
 Several GPUs (BASELINE config 4): python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 tools/prove_ivc.py ...
   the chain is sequential, so the GPUs share every STEP: each step proof is coset-sharded over the ranks (vpbs_prove_step_sharded: a rank
   computes the LDEs, leaf hashes and Merkle subtrees of its cosets; cap hashes, quotient values and query records travel over the library's
@@ -245,13 +248,14 @@ def check_chain(ctx, d, vk, blob, keys, testv, delta, ct, N, n_lwe, log_n, steps
     return t_verify, decrypted
 
 
-def run_chain_native(ctx, ivc, d, N, n_lwe, log_n, steps, seed, message, start, dist=None):
-    """the same PBS through the library's own driver (vpbs_ivc_prove_pbs: the loop of run_chain in C++, csrc/ivc.hip) -> result dict"""
+def run_chain_native(ctx, ivc, d, N, n_lwe, log_n, steps, seed, message, start, dist=None, nonce=0, keep_statement=False):
+    """the same PBS through the library's own driver (vpbs_ivc_prove_pbs: the loop of run_chain in C++, csrc/ivc.hip) -> result dict;
+    keep_statement: it carries "statement" = (proof bytes, testv, ct, out_ct, keys) for a batch verification after the clock"""
     total, kn = n_lwe + 2, K * N
     t_keys = time.perf_counter()
     keys = ctx.keygen(N, K, ELL, LOGB, n_lwe, seed, 4.99027217501041e-8, 1.17021618159313e-5)
     testv, delta = api.testv(N, 2)
-    ct = api.lwe_encrypt(keys["params"], keys["s_lwe"], delta * message % P)
+    ct = api.lwe_encrypt(keys["params"], keys["s_lwe"], delta * message % P, nonce=nonce)
     t_keys = time.perf_counter() - t_keys
     vk, _ = ivc.verifier_data()
     ncols = [d.n_constants + 80, 135, 20, 16]
@@ -261,7 +265,11 @@ def run_chain_native(ctx, ivc, d, N, n_lwe, log_n, steps, seed, message, start, 
     if dist:
         dist.barrier()
     t_verify, decrypted = check_chain(ctx, d, vk, blob, keys, testv, delta, ct, N, n_lwe, log_n, steps, message)
-    return {"seconds": t["seconds"], "split": {"witness_late_phase_host": t["late_witness_ms"], "late_rows_to_device": t["late_rows_upload_ms"],
+    statement = None
+    if keep_statement:
+        acc_init = np.concatenate([np.zeros((K - 1) * N, np.uint64), testv]).reshape(K, N)
+        statement = (blob, testv, ct, ctx.pbs_accumulator_chain(acc_init, ct, keys["bsk"], keys["ksk"], K, ELL, LOGB)[-1], keys)
+    return {"statement": statement, "seconds": t["seconds"], "split": {"witness_late_phase_host": t["late_witness_ms"], "late_rows_to_device": t["late_rows_upload_ms"],
                                                "prove_step": t["prove_step_ms"], "base_proof_once": t["base_proof_ms"],
                                                "witness_early_phase_on_a_second_thread": t["early_witness_ms"],
                                                "late_stages_run_during_the_previous_proofs_fri_stage": t["late_ahead_ms"]},
@@ -355,6 +363,9 @@ def main():
     check_witness = os.environ.get("VPBS_IVC_CHECK_WITNESS", "") not in ("", "0")
     if check_witness and not (native_driver and world == 1):
         raise SystemExit("VPBS_IVC_CHECK_WITNESS needs the library driver on one GPU (a sharded chain is not checked)")
+    device_verify = os.environ.get("VPBS_IVC_VERIFY", "host") == "device"
+    if device_verify and not (native_driver and world == 1 and steps == total):
+        raise SystemExit("VPBS_IVC_VERIFY=device needs the library driver on one GPU and whole chains (verify_pbs checks counter = n + 2)")
     chains = []
     for ci in range(n_chains):   # every chain has its own context (stream, device memory), circuit commitments and witness plans
         ctx = vpbs_amd.Context(device, log_n_max=max(16, log_n))
@@ -387,7 +398,9 @@ def main():
             torch.cuda.set_device(device)
             ctx, cyc, dum = chains[ci]
             if native_driver:
-                results[ci] = run_chain_native(ctx, cyc, dum, N, n_lwe, log_n, steps, 0x5EED0728 + ci, (message + ci) % 2, start, dist)
+                # one key set for all chains when their proofs are verified in one batch (one vpbs_pbs_verifier holds one key hash)
+                results[ci] = run_chain_native(ctx, cyc, dum, N, n_lwe, log_n, steps, 0x5EED0728 + (0 if device_verify else ci), (message + ci) % 2,
+                                               start, dist, nonce=ci if device_verify else 0, keep_statement=device_verify)
             else:
                 results[ci] = run_chain(ctx, cyc, dum, N, n_lwe, log_n, steps, 0x5EED0728 + ci, (message + ci) % 2, start, dist)
         except BaseException as e:                           # noqa: BLE001
@@ -409,6 +422,25 @@ def main():
         raise errors[0]
     ctx, cyc, dum = chains[0]
     r0 = results[0]
+    device_pbs_verify = None
+    if device_verify:   # the final proofs of all chains in one device batch
+        blobs, testvs, cts, out_cts, keys = zip(*[r["statement"] for r in results])
+        t = time.perf_counter()
+        key_hash = api.pbs_key_hash(keys[0]["bsk"], keys[0]["ksk"])
+        t_key = time.perf_counter() - t
+        vk, _ = cyc.verifier_data()
+        pv = api.PbsVerifier(ctx, vk[4:].reshape(-1, 4), [dum.n_constants + 80, 135, 20, 16], vk[:4], log_n, dum.n_constants, 80, dum.gates, N,
+                             K, n_lwe, K * ELL * K * N, key_hash, max_batch=n_chains)
+        run_ms = []
+        for _ in range(3):   # the first run also allocates the pinned staging
+            t = time.perf_counter()
+            verdicts, reasons, _ = pv.verify(list(blobs), np.stack(testvs), np.stack(cts), np.stack([o.reshape(-1) for o in out_cts]))
+            run_ms.append(1e3 * (time.perf_counter() - t))
+        pv.close()
+        device_pbs_verify = {"what": "the final proofs of all %d chains in one vpbs_pbs_verifier_run (upload included)" % n_chains,
+                             "verdicts": verdicts.tolist(), "reasons": [api.pbs_reason_text(x) for x in reasons], "ms": sorted(run_ms)[1],
+                             "runs_ms": run_ms, "key_hash_on_the_host_once_ms": 1e3 * t_key}
+        assert verdicts.all(), device_pbs_verify
     seconds = max(r["seconds"] for r in results)
     desc = dum if native_driver else cyc.d
     n_pi = len(desc.pi_pos)
@@ -439,6 +471,7 @@ def main():
         "other_chains": [{k: r[k] for k in ("seconds", "message", "decrypted")} for r in results[1:]],
         "before_the_clock": {"circuit_files_commit_plan_s": t_setup, "seeded_keygen_s": r0["keygen_s"]},
         "cpu_by_role": cpu_report,
+        "device_pbs_verify": device_pbs_verify,
         "witness_checks": [dict(zip(("checked", "violations"), c.witness_checks())) for _, c, _ in chains] if check_witness else None,
         "checks": "final proof serialised, parsed back and verified by vpbs_verify_step (full check); its public inputs carry the test vector, "
                   "counter = number of steps, the circuit's own verifier data, the native accumulator and both native chain hashes"

@@ -1,7 +1,9 @@
 """verifier timing on a full-size (2^15) step proof produced on the GPU: vpbs_verify_step on the host (default), or with
 --device --batch B the device batch verifier (vpbs_proof_verifier_run, wall clock including the upload, plus device events) against the
 host verifier on 16 threads over the same B serialised proofs, five alternating repetitions each: the 2^15 synthetic proof (fri_only:
-its wires satisfy no gate), or with --paper proofs of the exported step circuit at N = 1024 under the full check"""
+its wires satisfy no gate), or with --paper proofs of the exported step circuit at N = 1024 under the full check.
+--pbs --batch B[,B2,..]: whole vPBS proofs at N = 1024, n = 728 (two chains proven, replicated to B) through api.PbsVerifier against 16
+host threads that parse, verify the proof, check the statement and hash the LWE chain (key hash precomputed); one JSON line per B"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch, vpbs_amd
@@ -9,7 +11,8 @@ from vpbs_amd import api, synth
 import bench
 args = sys.argv[1:]
 device_mode = "--device" in args
-batch = int(args[args.index("--batch") + 1]) if "--batch" in args else 1
+batches = [int(b) for b in args[args.index("--batch") + 1].split(",")] if "--batch" in args else [1]   # --pbs: several, one line each
+batch = batches[0]
 log_n = 15
 ctx = vpbs_amd.Context(0, log_n_max=16)
 gates = api.GateSet(bench.GATES)
@@ -103,3 +106,80 @@ if device_mode and "--paper" in args:
     device_against_host("full check: step circuit at N = 1024 (2^%d rows), 8 distinct proofs" % d.log_n,
                         [distinct[k % 8] for k in range(batch)], pv, host_one)
     pv.close()
+
+if "--pbs" in args:
+    # --pbs [--batch B]: whole vPBS proofs at the paper's parameters (N = 1024, n = 728): the last proofs of real IVC chains under one key set,
+    # replicated to B.  Device: api.PbsVerifier (wall clock of vpbs_pbs_verifier_run, upload included); host: 16 threads, each running
+    # step_proof_from_bytes, verify_step, the statement checks and the LWE chain with the key hash precomputed (what the device object holds)
+    import json
+    from concurrent.futures import ThreadPoolExecutor
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
+    import export_circuits
+    from vpbs_amd import circuit_file
+    N, K, ELL, LOGB, n_lwe, plog_n, chains = 1024, 2, 4, 5, 728, 16, 2
+    cyc, dum = (circuit_file.load(p) for p in export_circuits.ensure_cyclic_circuit(N, K, ELL, LOGB, n_lwe, plog_n))
+    ivc = api.Ivc(ctx, cyc, dum, N, K, K * ELL * K * N)
+    vk, _ = ivc.verifier_data()
+    pcap, pdigest, pncols = vk[4:].reshape(-1, 4), vk[:4], [cyc.n_constants + 80, 135, 20, 16]
+    keys = ctx.keygen(N, K, ELL, LOGB, n_lwe, 0x5EED, 4.99027217501041e-8, 1.17021618159313e-5)
+    testv, delta = api.testv(N, 2)
+    testv = np.asarray(testv, np.uint64)
+    acc_init = np.concatenate([np.zeros((K - 1, N), np.uint64), testv.reshape(1, N)])
+    made = []
+    t = time.perf_counter()
+    for c in range(chains):
+        ct = np.asarray(api.lwe_encrypt(keys["params"], keys["s_lwe"], delta * (c % 2) % api.P, nonce=c), np.uint64)
+        blob, _ = ivc.prove_pbs(testv, ct, keys["bsk"], keys["ksk"])
+        made.append((blob, ct, ctx.pbs_accumulator_chain(acc_init, ct, keys["bsk"], keys["ksk"], K, ELL, LOGB)[-1].reshape(-1)))
+    prove_s = time.perf_counter() - t
+    ivc.free()
+    t = time.perf_counter()
+    ok, why = api.verify_pbs(made[0][0], pcap, pncols, pdigest, plog_n, cyc.n_constants, 80, cyc.gates, N, K, testv, made[0][1], keys["bsk"],
+                             keys["ksk"], made[0][2])
+    one_host_call_ms = 1e3 * (time.perf_counter() - t)
+    assert ok, why
+    t = time.perf_counter()
+    key_hash = api.pbs_key_hash(keys["bsk"], keys["ksk"])
+    key_hash_ms = 1e3 * (time.perf_counter() - t)
+    kn, n_pi = K * N, 2 * K * N + 13 + 64
+    for batch in batches:
+        pv = api.PbsVerifier(ctx, pcap, pncols, pdigest, plog_n, cyc.n_constants, 80, cyc.gates, N, K, n_lwe, K * ELL * K * N, key_hash,
+                             max_batch=batch)
+        pick = [made[k % chains] for k in range(batch)]
+        blobs, cts, outs = [p[0] for p in pick], np.stack([p[1] for p in pick]), np.stack([p[2] for p in pick])
+
+        def host_one(k):
+            blob, ct, out_ct = pick[k]
+            p, pi = api.step_proof_from_bytes(blob, pncols, plog_n, cyc.n_constants, max_public_inputs=n_pi)
+            if pi.size != n_pi or pi[:kn - N].any() or not (pi[kn - N:kn] == testv).all() or int(pi[kn]) != n_lwe + 2 or \
+                    not (pi[kn + 1:2 * kn + 1] == out_ct).all():
+                return False
+            if not api.verify_step(p, pcap, pncols, pdigest, pi, plog_n, n_constants=cyc.n_constants, n_routed=80, gates=cyc.gates):
+                return False
+            if not (pi[-68:] == vk).all() or not (pi[2 * kn + 1:2 * kn + 5] == key_hash).all():
+                return False
+            lwe_items = np.concatenate([ct[n_lwe:], ct[:n_lwe], np.zeros(1, np.uint64)]).reshape(-1, 1)
+            return api.hash_chain(lwe_items, pi[2 * kn + 5:2 * kn + 9])[1]
+        pv.verify(blobs, testv, cts, outs)   # warm-up: first launches, pinned staging
+        dev_ms, host_ms = [], []
+        with ThreadPoolExecutor(max_workers=16) as pool:
+            for _ in range(5):
+                t = time.perf_counter()
+                v, r, _ = pv.verify(blobs, testv, cts, outs)
+                dev_ms.append((time.perf_counter() - t) * 1e3)
+                assert v.all(), r
+                t = time.perf_counter()
+                okh = list(pool.map(host_one, range(batch)))
+                host_ms.append((time.perf_counter() - t) * 1e3)
+                assert all(okh)
+        ctx.timing_enable(1)
+        pv.verify(blobs, testv, cts, outs)
+        kernels = ctx.timing_report()
+        ctx.timing_enable(0)
+        pv.close()
+        med = lambda x: sorted(x)[len(x) // 2]
+        print(json.dumps({"what": "whole vPBS proofs at N = 1024, n = 728 (%d chains proven, replicated): vpbs_pbs_verifier_run against 16 host "
+                                  "threads (parse, verify_step, statement, LWE chain; key hash precomputed on both sides)" % chains,
+                          "batch": batch, "bytes_per_proof": len(blobs[0]), "device_ms_per_run_wall": med(dev_ms), "host_16_threads_ms": med(host_ms),
+                          "speedup": med(host_ms) / med(dev_ms), "device_runs_ms": dev_ms, "host_runs_ms": host_ms, "device_kernels": kernels,
+                          "one_vpbs_verify_pbs_call_ms": one_host_call_ms, "key_hash_on_the_host_ms": key_hash_ms, "proving_s": prove_s}))

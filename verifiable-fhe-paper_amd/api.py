@@ -278,6 +278,12 @@ SIGNATURES = {
     "vpbs_ivc_witness_checks": (_i, [_vp, U64P]),
     "vpbs_ivc_prove_pbs": (C.c_long, [_vp, U64P, U64P, U64P, U64P, _ui, _ui, C.POINTER(C.c_uint8), _sz, C.POINTER(IvcTimingC), C.c_char_p, _sz]),
     "vpbs_verify_pbs": (_i, [C.POINTER(VerifyPbsInputsC), C.POINTER(C.c_uint8), _sz, C.c_char_p, _sz]),
+    "vpbs_pbs_key_hash": (_i, [U64P, U64P, _ui, _sz, U64P]),
+    "vpbs_pbs_reason_text": (C.c_char_p, [_i]),
+    "vpbs_pbs_verifier_create": (_i, [_vp, C.POINTER(VerifyPbsInputsC), U64P, _sz, C.POINTER(_vp), C.c_char_p, _sz]),
+    "vpbs_pbs_verifier_run": (C.c_long, [_vp, C.POINTER(C.c_uint8), C.POINTER(_sz), _sz, U64P, _i, U64P, U64P, C.POINTER(C.c_uint8),
+                                         C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]),
+    "vpbs_pbs_verifier_free": (None, [_vp]),
     "vpbs_blind_rotate_step": (_i, [_vp, C.POINTER(TfheParamsC), _ui, _vp, _vp, _vp, _i, _i, _i, _vp, _i]),
     "vpbs_pbs_accumulator_chain": (_i, [_vp, C.POINTER(TfheParamsC), _ui, U64P, U64P, U64P, U64P, U64P]),
     "vpbs_host_alloc": (_vp, [_sz]),
@@ -1059,6 +1065,104 @@ def verify_pbs(blob, cs_cap, ncols, circuit_digest, log_n, n_constants, n_routed
     if rc < 0:
         raise VpbsError("vpbs_verify_pbs: " + why.value.decode())
     return rc == 1, why.value.decode()
+
+
+(PBS_OK, PBS_MALFORMED, PBS_TESTV_MASK, PBS_TESTV, PBS_COUNTER, PBS_OUT_CT, PBS_PROOF, PBS_VERIFIER_DATA, PBS_KEY_HASH,
+ PBS_LWE_HASH) = range(10)   # vpbs_pbs_verifier reasons, in vpbs_verify_pbs's order
+
+
+def pbs_reason_text(reason):
+    """vpbs_pbs_reason_text: the `why` vpbs_verify_pbs writes when that check fails ("" for PBS_OK)"""
+    t = lib().vpbs_pbs_reason_text(int(reason))
+    if t is None:
+        raise ValueError("no vPBS verifier reason %r" % (reason,))
+    return t.decode()
+
+
+def pbs_key_hash(bsk, ksk):
+    """vpbs_pbs_key_hash: the key hash chain of verify_pbs over [zeros, bsk_0 .. bsk_{n-1}, ksk] (host) -> [4].  bsk: [n][ggsw_len]"""
+    ks = _u64(ksk).reshape(-1)
+    if ks.size == 0:
+        raise VpbsError("vpbs_pbs_key_hash: an empty ksk (ggsw_len = 0)")
+    bs = _u64(bsk).reshape(-1, ks.size) if bsk is not None and len(bsk) else np.zeros((0, ks.size), np.uint64)
+    out = np.zeros(4, np.uint64)
+    if lib().vpbs_pbs_key_hash(_ptr(bs) if bs.size else None, _ptr(ks), bs.shape[0], ks.size, _ptr(out)) != 0:
+        raise VpbsError("vpbs_pbs_key_hash: malformed arguments")
+    return out
+
+
+class PbsVerifier:
+    """vpbs_pbs_verifier: vpbs_verify_pbs for a batch of vPBS proofs (the serialised last proofs of IVC chains) on the device, all under the
+    key set whose hash is key_hash (pbs_key_hash).  The parameters mirror verify_pbs; every proof brings its own ct and out_ct."""
+
+    def __init__(self, ctx, cs_cap, ncols, circuit_digest, log_n, n_constants, n_routed, gates, N, K, n_lwe, ggsw_len, key_hash, max_batch=64,
+                 num_challenges=2, quotient_degree_factor=8, rate_bits=3, cap_height=4, compat=None):
+        self.ctx, self.max_batch, self.N, self.K, self.n_lwe = ctx, max_batch, N, K, n_lwe
+        v = VerifyInputsC()
+        v.log_n, v.rate_bits, v.cap_height = log_n, rate_bits, cap_height
+        v.n_constants_sigmas, v.n_wires, v.n_zs_partial_products, v.n_quotient = ncols
+        v.num_challenges = num_challenges
+        self._cap = _u64(cs_cap)
+        v.constants_sigmas_cap = _ptr(self._cap)
+        for i in range(4):
+            v.circuit_digest[i] = int(circuit_digest[i])
+        v.n_constants, v.n_routed, v.quotient_degree_factor = n_constants, n_routed, quotient_degree_factor
+        v.gates, v.n_gates, v.num_selectors = gates.arr, gates.n, gates.num_selectors
+        if compat is not None:
+            self._compat = compat
+            v.compat = C.pointer(compat)
+        p = VerifyPbsInputsC()
+        p.circuit = C.pointer(v)
+        p.N, p.K, p.n_lwe, p.ggsw_len = N, K, n_lwe, ggsw_len
+        kh = _u64(key_hash).reshape(-1)
+        h, err = C.c_void_p(), C.create_string_buffer(512)
+        rc = lib().vpbs_pbs_verifier_create(ctx.h, C.byref(p), _ptr(kh), max_batch, C.byref(h), err, 512)
+        if rc:
+            raise VpbsError("vpbs_pbs_verifier_create: status %d: %s" % (rc, err.value.decode()))
+        self.h = h
+        ctx._batches.add(self)   # must not outlive its context: Context.close() frees the survivors
+
+    def verify_packed(self, buf, offsets, testv, cts, out_cts):
+        """buf, offsets: pack_proofs; testv: [N] shared or [count][N]; cts: [count][n + 1]; out_cts: [count][K][N]
+        -> (verdicts, reasons, proof_reasons), np.uint8 each"""
+        buf = np.ascontiguousarray(buf, dtype=np.uint8)
+        offs = np.ascontiguousarray(offsets, dtype=np.uint64)
+        count = offs.size - 1
+        tv = _u64(testv)
+        per_proof = tv.ndim == 2
+        tv = tv.reshape(-1)
+        c = _u64(cts).reshape(-1)
+        o = _u64(out_cts).reshape(-1)
+        if c.size != count * (self.n_lwe + 1) or o.size != count * self.K * self.N or tv.size != (count if per_proof else 1) * self.N:
+            raise ValueError("PbsVerifier.verify: expected testv [N] or [%d][N], cts [%d][n + 1] and out_cts [%d][K][N]" % (count, count, count))
+        verdicts, reasons, sub = (np.zeros(max(count, 0), np.uint8) for _ in range(3))
+        u8p = C.POINTER(C.c_uint8)
+        data = buf.ctypes.data_as(u8p) if buf.size else (C.c_uint8 * 1)()
+        keep = np.zeros(1, np.uint64)   # a valid pointer for empty arrays
+        ptr = lambda a: _ptr(a) if a.size else _ptr(keep)
+        rc = lib().vpbs_pbs_verifier_run(self.h, data, offs.ctypes.data_as(C.POINTER(C.c_size_t)), count, ptr(tv), 1 if per_proof else 0,
+                                         ptr(c), ptr(o), verdicts.ctypes.data_as(u8p), reasons.ctypes.data_as(u8p), sub.ctypes.data_as(u8p))
+        if rc < 0:
+            raise VpbsError("vpbs_pbs_verifier_run: status %d" % rc)
+        return verdicts, reasons, sub
+
+    def verify(self, blobs, testv, cts, out_cts):
+        """list of serialised vPBS proofs -> (verdicts, reasons, proof_reasons), np.uint8 each"""
+        return self.verify_packed(*pack_proofs(blobs), testv, cts, out_cts)
+
+    def close(self):
+        if self.h:
+            lib().vpbs_pbs_verifier_free(self.h)
+            self.h = None
+            self.ctx._batches.discard(self)
+
+    free = close
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def verify_step_fri_only(proof, cs_cap, ncols, circuit_digest, public_inputs, log_n, num_challenges=2, rate_bits=3, cap_height=4):

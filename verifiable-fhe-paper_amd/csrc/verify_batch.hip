@@ -31,6 +31,7 @@
 #include "poseidon.h"
 #include "gates.h"
 #include "context.h"
+#include "verify_batch.h"
 
 namespace {
 using vpbs::DeviceError;
@@ -732,11 +733,11 @@ int vpbs_proof_verifier_create(vpbs_ctx* ctx, const vpbs_verify_inputs* in, size
     return VPBS_OK;
 }
 
-long vpbs_proof_verifier_run(vpbs_proof_verifier* v, const uint8_t* bytes, const size_t* offsets, size_t count, uint8_t* verdicts,
-                             uint8_t* reasons) {
-    if (!v || !offsets || !verdicts || count > v->max_batch) return VPBS_ERR_INVALID;
-    if (count == 0) return 0;
-    if (!bytes) return VPBS_ERR_INVALID;
+void vpbs_proof_verifier_free(vpbs_proof_verifier* v) { delete v; }
+}  // extern "C"
+
+int vpbs::proof_verifier_enqueue(vpbs_proof_verifier* v, const uint8_t* bytes, const size_t* offsets, size_t count, ProofBatchView* view) {
+    if (!v || !bytes || !offsets || count == 0 || count > v->max_batch) return VPBS_ERR_INVALID;
     for (size_t k = 0; k < count; ++k)
         if (offsets[k + 1] < offsets[k]) return VPBS_ERR_INVALID;
     vpbs_ctx* ctx = v->ctx;
@@ -744,66 +745,79 @@ long vpbs_proof_verifier_run(vpbs_proof_verifier* v, const uint8_t* bytes, const
     const size_t total = offsets[count] - offsets[0];
     const size_t head = 8 * (count + 1);
     const size_t need = head + ((total + 7) & ~(size_t)7) + 16;
+    VPBS_HIP(hipSetDevice(ctx->device));
+    if (v->h_stage_bytes < need) {
+        VPBS_HIP(vpbs::stream_sync(ctx->stream));
+        if (v->h_stage) (void)hipHostFree(v->h_stage);
+        v->h_stage = nullptr;
+        v->h_stage_bytes = 0;
+        VPBS_HIP(hipHostMalloc((void**)&v->h_stage, need, hipHostMallocDefault));
+        v->h_stage_bytes = need;
+    }
+    if (v->stage_bytes < need) {
+        if (v->d_stage) ctx->release(v->d_stage);
+        v->d_stage = nullptr;
+        v->stage_bytes = 0;
+        v->d_stage = static_cast<u64*>(ctx->alloc_bytes(need));
+        v->stage_bytes = need;
+    }
+    u64* h_offs = reinterpret_cast<u64*>(v->h_stage);
+    for (size_t k = 0; k <= count; ++k) h_offs[k] = offsets[k] - offsets[0];
+    std::memcpy(v->h_stage + head, bytes + offsets[0], total);
+    std::memset(v->h_stage + head + total, 0, need - head - total);
+    VPBS_HIP(hipMemcpyAsync(v->d_stage, v->h_stage, need, hipMemcpyHostToDevice, ctx->stream));
+    VPBS_HIP(hipMemsetAsync(v->d_flags, 0, count * sizeof(u32), ctx->stream));
+    const u64* d_offs = v->d_stage;
+    const u64* d_raw = v->d_stage + (count + 1);
+    hipStream_t s = ctx->stream;
+    const u32 n = (u32)count;
+    {
+        vpbs::Timed t(ctx, "vb_parse");
+        const u32 span = std::max(S.n_fixed + S.max_pi, S.n_lenb);
+        vb_parse<<<dim3((span + 255) / 256, n), 256, 0, s>>>(d_raw, d_offs, v->d_src, v->d_lenb_off, v->d_lenb_val, S, v->d_words, v->d_npi,
+                                                             v->d_flags);
+    }
+    {
+        vpbs::Timed t(ctx, "vb_transcript");
+        vb_transcript<<<n, 16, 0, s>>>(v->d_words, v->d_npi, S, v->d_chal, v->d_flags);
+    }
+    if (!S.fri_only) {
+        if (S.n_gates) {
+            vpbs::Timed t(ctx, "vb_gates");
+            vb_gates<<<dim3((n + 63) / 64, S.n_gates), 64, 0, s>>>(v->d_words, v->d_chal, v->d_gates, v->d_coset, S, n, v->d_gterms);
+        }
+        vpbs::Timed t(ctx, "vb_vanishing");
+        vb_vanishing<<<(n + 63) / 64, 64, 0, s>>>(v->d_words, v->d_chal, v->d_gterms, S, n, v->d_flags);
+    }
+    {
+        vpbs::Timed t(ctx, "vb_fri");
+        const u64 lanes = (u64)n * S.nq;
+        vb_fri<<<(unsigned)((lanes + 63) / 64), 64, 0, s>>>(v->d_words, v->d_chal, S, n, v->d_flags);
+    }
+    {
+        vpbs::Timed t(ctx, "vb_merkle");
+        const u64 lanes = (u64)n * S.nq * (4 + S.n_rounds);
+        vb_merkle<<<(unsigned)((lanes + 63) / 64), 64, 0, s>>>(v->d_words, v->d_chal, v->d_cs_cap, S, n, v->d_flags);
+    }
+    vb_result<<<(n + 255) / 256, 256, 0, s>>>(v->d_flags, n, v->d_out);
+    VPBS_HIP(hipGetLastError());
+    if (view) *view = ProofBatchView{v->d_words, v->d_npi, v->d_out + count, S.W, S.n_fixed, S.max_pi};
+    return VPBS_OK;
+}
+
+extern "C" {
+long vpbs_proof_verifier_run(vpbs_proof_verifier* v, const uint8_t* bytes, const size_t* offsets, size_t count, uint8_t* verdicts,
+                             uint8_t* reasons) {
+    if (!v || !offsets || !verdicts || count > v->max_batch) return VPBS_ERR_INVALID;
+    if (count == 0) return 0;
+    if (!bytes) return VPBS_ERR_INVALID;
+    vpbs_ctx* ctx = v->ctx;
     try {
-        VPBS_HIP(hipSetDevice(ctx->device));
-        if (v->h_stage_bytes < need) {
-            VPBS_HIP(vpbs::stream_sync(ctx->stream));
-            if (v->h_stage) (void)hipHostFree(v->h_stage);
-            v->h_stage = nullptr;
-            v->h_stage_bytes = 0;
-            VPBS_HIP(hipHostMalloc((void**)&v->h_stage, need, hipHostMallocDefault));
-            v->h_stage_bytes = need;
-        }
-        if (v->stage_bytes < need) {
-            if (v->d_stage) ctx->release(v->d_stage);
-            v->d_stage = nullptr;
-            v->stage_bytes = 0;
-            v->d_stage = static_cast<u64*>(ctx->alloc_bytes(need));
-            v->stage_bytes = need;
-        }
-        u64* h_offs = reinterpret_cast<u64*>(v->h_stage);
-        for (size_t k = 0; k <= count; ++k) h_offs[k] = offsets[k] - offsets[0];
-        std::memcpy(v->h_stage + head, bytes + offsets[0], total);
-        std::memset(v->h_stage + head + total, 0, need - head - total);
-        VPBS_HIP(hipMemcpyAsync(v->d_stage, v->h_stage, need, hipMemcpyHostToDevice, ctx->stream));
-        VPBS_HIP(hipMemsetAsync(v->d_flags, 0, count * sizeof(u32), ctx->stream));
-        const u64* d_offs = v->d_stage;
-        const u64* d_raw = v->d_stage + (count + 1);
-        hipStream_t s = ctx->stream;
-        const u32 n = (u32)count;
-        {
-            vpbs::Timed t(ctx, "vb_parse");
-            const u32 span = std::max(S.n_fixed + S.max_pi, S.n_lenb);
-            vb_parse<<<dim3((span + 255) / 256, n), 256, 0, s>>>(d_raw, d_offs, v->d_src, v->d_lenb_off, v->d_lenb_val, S, v->d_words, v->d_npi,
-                                                                 v->d_flags);
-        }
-        {
-            vpbs::Timed t(ctx, "vb_transcript");
-            vb_transcript<<<n, 16, 0, s>>>(v->d_words, v->d_npi, S, v->d_chal, v->d_flags);
-        }
-        if (!S.fri_only) {
-            if (S.n_gates) {
-                vpbs::Timed t(ctx, "vb_gates");
-                vb_gates<<<dim3((n + 63) / 64, S.n_gates), 64, 0, s>>>(v->d_words, v->d_chal, v->d_gates, v->d_coset, S, n, v->d_gterms);
-            }
-            vpbs::Timed t(ctx, "vb_vanishing");
-            vb_vanishing<<<(n + 63) / 64, 64, 0, s>>>(v->d_words, v->d_chal, v->d_gterms, S, n, v->d_flags);
-        }
-        {
-            vpbs::Timed t(ctx, "vb_fri");
-            const u64 lanes = (u64)n * S.nq;
-            vb_fri<<<(unsigned)((lanes + 63) / 64), 64, 0, s>>>(v->d_words, v->d_chal, S, n, v->d_flags);
-        }
-        {
-            vpbs::Timed t(ctx, "vb_merkle");
-            const u64 lanes = (u64)n * S.nq * (4 + S.n_rounds);
-            vb_merkle<<<(unsigned)((lanes + 63) / 64), 64, 0, s>>>(v->d_words, v->d_chal, v->d_cs_cap, S, n, v->d_flags);
-        }
-        vb_result<<<(n + 255) / 256, 256, 0, s>>>(v->d_flags, n, v->d_out);
-        VPBS_HIP(hipGetLastError());
+        const int rc = vpbs::proof_verifier_enqueue(v, bytes, offsets, count, nullptr);
+        if (rc) return rc;
         // the verdicts come back through the front of the staging buffer (its offsets have been uploaded by now: same stream)
-        VPBS_HIP(hipMemcpyAsync(v->h_stage, v->d_out, 2 * count, hipMemcpyDeviceToHost, s));
-        VPBS_HIP(vpbs::stream_sync(s));
+        VPBS_HIP(hipMemcpyAsync(v->h_stage, v->d_out, 2 * count, hipMemcpyDeviceToHost, ctx->stream));
+        VPBS_HIP(vpbs::stream_sync(ctx->stream));
     } catch (const DeviceError& e) {
         ctx->err = e.what;
         return VPBS_ERR_DEVICE;
@@ -816,6 +830,4 @@ long vpbs_proof_verifier_run(vpbs_proof_verifier* v, const uint8_t* bytes, const
     }
     return accepted;
 }
-
-void vpbs_proof_verifier_free(vpbs_proof_verifier* v) { delete v; }
 }  // extern "C"
