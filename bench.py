@@ -9,7 +9,11 @@ transcript, and the dependency of each proof on the one before.  A vPBS proof = 
 (/root/reference/src/main.rs:27, n + 2), so value = chained step proofs/s / 730.  --warmup chained steps run untimed, then exactly --steps
 are timed between barrier + synchronise (the clock is placed from the library's progress hook, vpbs_ivc_set_step_callback).
 
-`--workload step` (and the `step_micro` object of the default line) is the synthetic back-to-back step proof over seeded random columns
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, --dump-outputs, the line.  `--full` adds everything else
+the benchmark measures or checks: the secondary legs (one-chain latency, the synthetic step, whole chains in their own processes, the CPU
+baseline, ...), the per-kernel table of the step workload and the checks of every chain's last proof after the clock.
+
+`--workload step` (and the `step_micro` object of a --full line) is the synthetic back-to-back step proof over seeded random columns
 resident in HBM that rounds 1-2 reported as the headline: no witness generation, no chain dependency, boost clock -- the device-side
 prover alone; the full-size parity check against the CPU oracle is made on that instance.
 
@@ -903,13 +907,14 @@ def measure_ivc(args, rank, local_rank, world, distributed):
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda" if args.dist_backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    # after the clock: the last proof of every chain is the proof of a prefix of a vPBS -- parsed, fully verified (gate constraints at
+    # after the clock (--full): the last proof of every chain is the proof of a prefix of a vPBS -- parsed, fully verified (gate constraints at
     # zeta included), its public inputs checked against the native accumulator chain and both native hash chains
     verify_ms = []
-    for c in chains:
-        vk, _ = c["ivc"].verifier_data()
-        tv, _ = prove_ivc.check_chain(c["ctx"], c["d"], vk, c["blob"], c["keys"], c["testv"], c["delta"], c["ct"], N, n_lwe, log_n, steps, c["message"])
-        verify_ms.append(1e3 * tv)
+    if args.full:
+        for c in chains:
+            vk, _ = c["ivc"].verifier_data()
+            tv, _ = prove_ivc.check_chain(c["ctx"], c["d"], vk, c["blob"], c["keys"], c["testv"], c["delta"], c["ct"], N, n_lwe, log_n, steps, c["message"])
+            verify_ms.append(1e3 * tv)
     dumped = None
     if getattr(args, "dump_outputs", None):
         # what vpbs_ivc_prove_pbs hands its caller per chain: the serialised last proof of the chain (bytes), and that proof parsed back
@@ -980,10 +985,11 @@ def measure_ivc(args, rank, local_rank, world, distributed):
                                         "base_proof_once": t0s["base_proof_ms"],
                                         "late_stages_run_during_the_previous_proofs_fri_stage": t0s["late_ahead_ms"],
                                         "over": "chain 0, warm-up steps included"},
-            "chain_checks": {"last_proof_verify_ms": verify_ms, "proof_bytes": len(chains[0]["blob"]),
-                             "what": "after the clock, per chain: the last proof (step %d of the chain) serialised by the library, parsed back, fully "
-                                     "verified by vpbs_verify_step (gate constraints at zeta included); test vector, counter = %d, verifier data, the "
-                                     "native accumulator chain and both native hash chains match its public inputs" % (steps, steps)},
+            "chain_checks": {"last_proof_verify_ms": verify_ms, "proof_bytes": len(chains[0]["blob"]), "checked": bool(args.full),
+                             "what": ("after the clock, per chain: the last proof (step %d of the chain) serialised by the library, parsed back, fully "
+                                      "verified by vpbs_verify_step (gate constraints at zeta included); test vector, counter = %d, verifier data, the "
+                                      "native accumulator chain and both native hash chains match its public inputs" % (steps, steps)) if args.full else
+                                     "not checked in this run: with --full every chain's last proof is parsed back and verified after the clock"},
             "before_the_clock_s": {"circuit_files_commit_plans_keys": t_setup},
             "host": host_info(),
         }
@@ -1103,7 +1109,7 @@ def measure_step(args, rank, local_rank, world, distributed, log_n):
         ctx.timing_enable(0)
 
     batch_result = None
-    if world == 1 and n_chains == 1 and args.batch_chains > 1:
+    if args.full and world == 1 and n_chains == 1 and args.batch_chains > 1:
         extra = []
         for c in range(1, args.batch_chains):
             cx = shares_the_gpu(vpbs_amd.Context(local_rank, log_n_max=16))
@@ -1134,15 +1140,16 @@ def measure_step(args, rank, local_rank, world, distributed, log_n):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
-    # per-kernel breakdown of one extra (untimed) step proof on chain 0 alone, for the record
-    ctx = ctxs[0]
-    ctx.timing_enable(1)
-    proof0 = ctx.prove_step(sis[0], comm)
-    breakdown = {k: round(v["ms"], 4) for k, v in ctx.timing_report().items()}
-    gpu_proof = None
-    if rank == 0 and not sharded and world == 1:   # kept for the word-for-word comparison with the oracle's proof (cpu_baseline leg)
-        gpu_proof = (proof0, ctx.step_proof_to_bytes(sis[0], N_CONSTANTS, proof0), keep[0][1].cap().copy())
-    ctx.timing_enable(0)
+    # --full: per-kernel breakdown of one extra (untimed) step proof on chain 0 alone, for the record
+    breakdown, gpu_proof = None, None
+    if args.full:
+        ctx = ctxs[0]
+        ctx.timing_enable(1)
+        proof0 = ctx.prove_step(sis[0], comm)
+        breakdown = {k: round(v["ms"], 4) for k, v in ctx.timing_report().items()}
+        if rank == 0 and not sharded and world == 1:   # kept for the word-for-word comparison with the oracle's proof (cpu_baseline leg)
+            gpu_proof = (proof0, ctx.step_proof_to_bytes(sis[0], N_CONSTANTS, proof0), keep[0][1].cap().copy())
+        ctx.timing_enable(0)
 
     out = None
     if rank == 0:
@@ -1174,9 +1181,10 @@ def measure_step(args, rank, local_rank, world, distributed, log_n):
                        "chains_per_gpu": n_chains},
             "roofline": roofline_of(per_step_ms, leaf_hash_bytes_per_step(log_n) * scale, leaf_hash_perms_per_step(log_n) * scale, sclk_mhz,
                                     sclk_samples, dominant["count"], "the timed back-to-back synthetic steps"),
-            "kernel_ms_one_step": breakdown,
             "host": host_info(),
         }
+        if breakdown is not None:
+            out["kernel_ms_one_step"] = breakdown
         if batch_result is not None:
             out["batch"] = batch_result   # several independent synthetic chains in flight (extra contexts / streams)
         if dumped is not None:
@@ -1286,6 +1294,11 @@ def main():
                     help="with --device-witness: the late witness phase on the device too (the host generates no witness).  Automatic where this "
                          "rank has ONE CPU (measured with round 6's staged walk: 1 CPU 0.164 against 0.127 with the late phase on the host; 2 and 4 "
                          "CPUs equal, 0.173-0.175 / 0.185; from 12 CPUs on the host pipeline is faster); VPBS_BENCH_DEVICE_LATE=0 keeps it off")
+    ap.add_argument("--full", action="store_true", default=os.environ.get("VPBS_BENCH_FULL", "") not in ("", "0"),
+                    help="also run what the headline does not need (a plain run sets up, warms up, times --steps, writes --dump-outputs and "
+                         "prints its line): at N = 1 the secondary legs below (the --no-* options switch single ones off) and the CPU "
+                         "baseline with its full-size parity check; the per-kernel table and the batch of the step workload; the checks of every "
+                         "chain's last proof after the clock.  VPBS_BENCH_FULL=1 sets it")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-step-micro", action="store_true", help="ivc workload: skip the synthetic step legs (step_micro, its batch, the parity check at full size)")
     ap.add_argument("--no-single-chain", action="store_true", help="ivc workload: skip the one-chain latency measurement")
@@ -1296,7 +1309,7 @@ def main():
     ap.add_argument("--no-batch128", action="store_true", help="skip the BASELINE config 3 leg (128 independent proofs through a pool of contexts)")
     ap.add_argument("--step-chains", type=int, default=1, help="step workload: independent synthetic chains proven concurrently per GPU")
     ap.add_argument("--batch-chains", type=int, default=4,
-                    help="after the single-chain synthetic step, also time this many concurrent synthetic chains (1 GPU only)")
+                    help="--full: after the single-chain synthetic step, also time this many concurrent synthetic chains (1 GPU only)")
     ap.add_argument("--mode", choices=["replicas", "sharded", "sharded-replay"], default="replicas",
                     help="N > 1: 'replicas' = independent chains per GPU (weak scaling, default, no data-path collective); "
                          "'sharded' = ONE chain whose commitments are coset-sharded over the GPUs (strong scaling: per-step "
@@ -1358,7 +1371,7 @@ def main():
             dist.init_process_group(args.dist_backend, timeout=vpbs_amd.sharding.group_timeout())
     launch = launch_report(args, rank, local_rank, world, distributed)
     log_n = args.log_n
-    secondary = rank == 0 and world == 1 and log_n == LOG_N
+    secondary = args.full and rank == 0 and world == 1 and log_n == LOG_N
     # What a rank's share of the host CPUs carries (measured on one MI355X with the affinity mask as the share and 8 hardware queues,
     # tools/experiments/cpu_share.sh, vPBS proofs/s per GPU): with the early witness phases on the HOST 2 / 4 / 8 / 16 CPUs give 0.074 / 0.086 /
     # 0.144 / 0.163 (1 / 1 / 4 / 6 chains); with the early phases on the DEVICE in batches of 64 (the host keeps the late phase and one
@@ -1498,7 +1511,7 @@ def main():
             d = subprocess_json([sys.executable, os.path.join(ROOT, "tools", "prove_ivc.py"), "2048", "728", "17", "24"], env, 900)
             out["ivc_chain_n2048"] = {k: d[k] for k in ("what", "step_proofs", "seconds", "ms_per_step", "ms_per_step_split", "proof_bytes",
                                                         "verify_last_proof_ms", "host") if k in d} if "error" not in d else d
-        if world == 1 and not args.no_cpu_baseline and log_n == LOG_N:
+        if args.full and world == 1 and not args.no_cpu_baseline and log_n == LOG_N:
             parity, out["cpu_baseline"] = cpu_baseline(gpu_proof)
             out["parity_checked_full_size"] = parity is not None
             out["parity_full_size"] = parity

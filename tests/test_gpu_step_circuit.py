@@ -553,7 +553,7 @@ def test_bench_with_the_early_witness_phases_on_the_device(tmp_path):
     import sys
     import __graft_entry__ as entry
     detail = str(tmp_path / "detail.json")
-    r = subprocess.run([sys.executable, entry.ROOT + "/bench.py", "--steps", "10", "--warmup", "3", "--chains", "2", "--device-witness", "4",
+    r = subprocess.run([sys.executable, entry.ROOT + "/bench.py", "--steps", "10", "--warmup", "3", "--chains", "2", "--device-witness", "4", "--full",
                         "--no-single-chain", "--no-step-micro", "--no-cpu-baseline", "--no-survey-size", "--no-step-circuit", "--no-batch128",
                         "--no-whole-pbs", "--no-ivc", "--detail", detail], capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
@@ -561,6 +561,7 @@ def test_bench_with_the_early_witness_phases_on_the_device(tmp_path):
     assert line["steps"] == 10 and line["config"]["chains_per_gpu"] == 2 and line["config"]["witness"] == "device"
     assert d["steps"] == 10 and d["config"]["chains_per_gpu"] == 2 and d["config"]["early_witness_phase"].startswith("on the device, 4 steps")
     assert abs(d["value"] - 2 * 1e3 / d["ms_per_step"] / 730) < 1e-9 and d["chain_checks"]["proof_bytes"] == 192716
+    assert d["chain_checks"]["checked"] is True and len(d["chain_checks"]["last_proof_verify_ms"]) == 2
     # the window sits in the pipeline's steady state: two batches of run-in before the warm-up, two batches of tail after the clock
     assert d["config"]["run_in_steps"] == 8 and d["config"]["tail_steps"] == 8 and "ON THE DEVICE" in d["config"]["stages"]
 
@@ -596,6 +597,25 @@ def test_bench_dump_outputs_hold_the_last_proofs(tmp_path):
         assert (got_pis == pis).all() and int(pis[2 * 1024]) == steps
 
 
+def test_plain_bench_runs_the_headline_alone(tmp_path):
+    """bench.py without --full and without any --no-* option: set-up, warm-up, exactly --steps timed steps and the line -- no secondary leg,
+    no CPU baseline, and the chains' last proofs are not checked after the clock (all of that is --full)"""
+    import subprocess
+    import sys
+    import __graft_entry__ as entry
+    detail = str(tmp_path / "detail.json")
+    r = subprocess.run([sys.executable, entry.ROOT + "/bench.py", "--steps", "4", "--warmup", "1", "--chains", "2", "--device-witness", "0",
+                        "--detail", detail], capture_output=True, text=True, timeout=1500)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+    line, d = _bench_line_and_detail(r.stdout, detail)
+    assert line["steps"] == d["steps"] == 4 and line["warmup"] == d["warmup"] == 1 and line["ms_per_step"] > 0 and line["higher_is_better"] is True
+    assert abs(d["value"] - 2 * 1e3 / d["ms_per_step"] / 730) < 1e-9 and line["config"]["chains_per_gpu"] == 2
+    legs = ("ivc_single_chain", "step_micro", "survey_degree_2pow15", "batch_of_128", "step_circuit_pipeline", "whole_pbs", "ivc_chain",
+            "ivc_full_chains", "sustained", "ivc_chain_n2048", "cpu_baseline", "parity_checked_full_size")
+    assert [k for k in legs if k in d or k in line] == []
+    assert d["chain_checks"]["checked"] is False and d["chain_checks"]["last_proof_verify_ms"] == [] and d["chain_checks"]["proof_bytes"] == 192716
+
+
 def test_bench_contract_with_two_ranks_sharing_the_gpu(tmp_path):
     """The driver's multi-GPU launch of bench.py (torch.distributed.run, one rank per GPU, replicas: independent chains per rank, no
     data-path collective) with both ranks on the one device of the test box (--device 0, gloo for the barriers): ONE JSON line from rank 0,
@@ -607,7 +627,7 @@ def test_bench_contract_with_two_ranks_sharing_the_gpu(tmp_path):
     import __graft_entry__ as entry
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", "29533", entry.ROOT + "/bench.py", "--gpus", "2", "--steps", "12", "--warmup", "2", "--device", "0",
-                        "--dist-backend", "gloo", "--chains", "1", "--device-witness", "0", "--detail", str(tmp_path / "detail.json")],
+                        "--dist-backend", "gloo", "--chains", "1", "--device-witness", "0", "--full", "--detail", str(tmp_path / "detail.json")],
                        capture_output=True, text=True, timeout=1500, env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"))
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     line, d = _bench_line_and_detail(r.stdout, str(tmp_path / "detail.json"))
@@ -617,6 +637,7 @@ def test_bench_contract_with_two_ranks_sharing_the_gpu(tmp_path):
     assert d["config"]["chains_per_gpu"] == 1 and "vpbs_ivc_prove_pbs" in d["config"]["workload"]
     assert abs(d["value"] - 2 * 1e3 / d["ms_per_step"] / 730) < 1e-9 * d["value"] + 1e-12       # both ranks' chains over the MAX time
     assert d["roofline"]["bound"] == "hbm" and d["roofline"]["int_valu_issue"]["bound"] == "int-valu-issue" and d["chain_checks"]["proof_bytes"] == 192716
+    assert d["chain_checks"]["checked"] is True and len(d["chain_checks"]["last_proof_verify_ms"]) == 1                 # rank 0's one chain
     assert "cpu_baseline" not in d                                                              # N = 1 only
 
 

@@ -4,6 +4,7 @@
 # earlier calls left in gpurun_out/, then summarize_profiles.py + pmc_table.py for the three counter tables + the copies into profiles/).
 # Every bench run here writes its full result with --detail (stdout carries only the compact record).
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
+export VPBS_BENCH_FULL=1     # every bench.py run below (the scripts it calls included) with all it measures and checks: bench.py --full
 rm -rf gpurun_out/prof_stats gpurun_out/prof_fetch gpurun_out/prof_write
 python3 tools/kernel_sources.py > gpurun_out/pmc_sources.json          # the device code these counters belong to
 CMD="python3 bench.py --workload step --steps 10 --warmup 2 --no-cpu-baseline --no-survey-size --no-step-circuit --no-batch128 --no-whole-pbs --no-ivc --batch-chains 1"
