@@ -309,3 +309,108 @@ int orc_verify_fri(const u64* const* caps, const size_t* ncols, size_t n_oracles
     }
     return 1;
 }
+
+u64 orc_pow_grind(const orc_challenger* ch, unsigned pow_bits) {
+    const u64 block = 1u << 12;
+    for (u64 start = 0;; start += block) {
+        u64 best = UINT64_MAX;
+#pragma omp parallel for schedule(static) reduction(min : best)
+        for (u64 w = start; w < start + block; ++w)
+            if (pow_ok(ch, w, pow_bits) && w < best) best = w;
+        if (best != UINT64_MAX) return best;
+    }
+}
+
+unsigned orc_verify_fri_checks(const u64* const* caps, const size_t* ncols, size_t n_oracles, const orc_fri_batch_info* batches,
+                               const u64* const* openings, size_t n_batches, orc_challenger* ch, const orc_fri_params* params,
+                               unsigned degree_bits, const u64* proof) {
+    unsigned log_lde = degree_bits + params->rate_bits;
+    size_t lde = (size_t)1 << log_lde;
+    size_t cap_words = (size_t)4 << params->cap_height;
+    size_t final_len = (size_t)1 << final_poly_bits(params, degree_bits);
+    size_t total = orc_fri_proof_words(params, degree_bits, ncols, n_oracles);
+    const u64* final_words = proof + total - 1 - 2 * final_len;
+    u64 pow_witness = proof[total - 1];
+    unsigned failed = 0;
+
+    ext2 alpha = ch_get_ext(ch);
+    ext2 betas[16];
+    const u64* w = proof;
+    const u64* fri_caps[16];
+    for (unsigned r = 0; r < params->n_rounds; ++r) {
+        fri_caps[r] = w;
+        orc_challenger_observe(ch, w, cap_words);
+        w += cap_words;
+        betas[r] = ch_get_ext(ch);
+    }
+    orc_challenger_observe(ch, final_words, 2 * final_len);
+    orc_challenger_observe(ch, &pow_witness, 1);
+    u64 pow_response = orc_challenger_get(ch);
+    if (params->pow_bits && (pow_response >> (64 - params->pow_bits)) != 0) failed |= ORC_FRI_POW;
+
+    ext2 reduced[8];
+    for (size_t b = 0; b < n_batches; ++b) {
+        ext2 acc = ext_from_base(0);
+        for (size_t j = batches[b].n_polys; j-- > 0;)
+            acc = ext_add(ext_mul(acc, alpha), ext_make(openings[b][2 * j], openings[b][2 * j + 1]));
+        reduced[b] = acc;
+    }
+
+    for (unsigned q = 0; q < params->num_query_rounds; ++q) {
+        u64 x = orc_challenger_get(ch);
+        size_t x_index = (size_t)(x % lde);
+        const u64* leaf[8];
+        for (size_t o = 0; o < n_oracles; ++o) {
+            size_t nsib = log_lde - params->cap_height;
+            leaf[o] = w;
+            if (!orc_merkle_verify(w, ncols[o], x_index, caps[o], params->cap_height, w + ncols[o], nsib)) failed |= ORC_FRI_MERKLE;
+            w += ncols[o] + 4 * nsib;
+        }
+        u64 subgroup_x = gl_mul(GL_GENERATOR, gl_exp(gl_root_of_unity(log_lde), bitrev(x_index, log_lde)));
+        ext2 sum = ext_from_base(0);
+        for (size_t b = 0; b < n_batches; ++b) {
+            ext2 acc = ext_from_base(0), apow = ext_from_base(1);
+            for (size_t j = 0; j < batches[b].n_polys; ++j) {
+                u64 e = leaf[batches[b].oracle_index[j]][batches[b].poly_index[j]];
+                acc = ext_add(acc, ext_scalar_mul(apow, e));
+                apow = ext_mul(apow, alpha);
+            }
+            ext2 num = ext_sub(acc, reduced[b]);
+            ext2 den = ext_sub(ext_from_base(subgroup_x), ext_make(batches[b].point[0], batches[b].point[1]));
+            sum = ext_add(ext_mul(sum, apow), ext_mul(num, ext_inv(den)));
+        }
+        if (params->mul_final_by_x) sum = ext_scalar_mul(sum, subgroup_x);
+        ext2 old_eval = sum;
+        unsigned lg = log_lde;
+        for (unsigned r = 0; r < params->n_rounds; ++r) {
+            unsigned ab = params->arity_bits[r]; size_t arity = (size_t)1 << ab;
+            const u64* evals = w;
+            size_t coset_index = x_index >> ab, within = x_index & (arity - 1);
+            if (evals[2 * within] != old_eval.c[0] || evals[2 * within + 1] != old_eval.c[1]) failed |= ORC_FRI_CONSISTENCY;
+            u64 g = gl_root_of_unity(ab);
+            size_t rev_within = bitrev(within, ab);
+            u64 coset_start = gl_mul(subgroup_x, gl_exp(g, arity - rev_within));
+            ext2 xs[16], ys[16];
+            u64 y = 1;
+            for (size_t i = 0; i < arity; ++i) {
+                size_t src = bitrev(i, ab);
+                xs[i] = ext_from_base(gl_mul(coset_start, y));
+                ys[i] = ext_make(evals[2 * src], evals[2 * src + 1]);
+                y = gl_mul(y, g);
+            }
+            old_eval = interpolate_at(xs, ys, arity, betas[r]);
+            lg -= ab;
+            size_t nsib = lg - params->cap_height;
+            if (!orc_merkle_verify(evals, 2 * arity, coset_index, fri_caps[r], params->cap_height, evals + 2 * arity, nsib))
+                failed |= ORC_FRI_MERKLE;
+            w += 2 * arity + 4 * nsib;
+            for (unsigned k = 0; k < ab; ++k) subgroup_x = gl_sqr(subgroup_x);
+            x_index = coset_index;
+        }
+        ext2 acc = ext_from_base(0);
+        for (size_t i = final_len; i-- > 0;)
+            acc = ext_add(ext_scalar_mul(acc, subgroup_x), ext_make(final_words[2 * i], final_words[2 * i + 1]));
+        if (!ext_eq(acc, old_eval)) failed |= ORC_FRI_CONSISTENCY;
+    }
+    return failed;
+}

@@ -155,6 +155,17 @@ int orc_prove_openings(const orc_batch* const* oracles, size_t n_oracles, const 
 int orc_verify_fri(const u64* const* caps, const size_t* ncols, size_t n_oracles, const orc_fri_batch_info* batches,
                    const u64* const* openings, size_t n_batches, orc_challenger* ch, const orc_fri_params* params,
                    unsigned degree_bits, const u64* proof);
+/* the checks of orc_verify_fri without stopping at the first failure: every query, every Merkle path and every fold is checked,
+ * and the result is the set of checks that failed (0 = the proof verifies).  The challenger is left after the last query index. */
+#define ORC_FRI_POW 1u          /* the proof-of-work response has fewer than pow_bits leading zeros */
+#define ORC_FRI_CONSISTENCY 2u  /* a fold does not hold the previous round's value, or the final polynomial disagrees */
+#define ORC_FRI_MERKLE 4u       /* a leaf of an initial oracle or of a fold round does not climb to its cap */
+unsigned orc_verify_fri_checks(const u64* const* caps, const size_t* ncols, size_t n_oracles, const orc_fri_batch_info* batches,
+                               const u64* const* openings, size_t n_batches, orc_challenger* ch, const orc_fri_params* params,
+                               unsigned degree_bits, const u64* proof);
+/* fri_proof_of_work: the smallest nonce whose response, after the challenger in state `ch` observes it, has pow_bits leading
+ * zeros (scalar permutations, searched in parallel blocks; `ch` is not changed) */
+u64 orc_pow_grind(const orc_challenger* ch, unsigned pow_bits);
 
 /* ---- permutation argument: Z and partial products (plonk/prover.rs all_wires_permutation_partial_products,
  *      wires_permutation_partial_products_and_zs; plonk/permutation_argument.rs get_unique_coset_shifts) ----

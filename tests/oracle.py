@@ -123,6 +123,9 @@ def lib():
                                             C.POINTER(FriParams), ui, u64, U64P]),
             "orc_verify_fri": (C.c_int, [C.POINTER(U64P), C.POINTER(sz), sz, C.POINTER(FriBatchInfo), C.POINTER(U64P), sz,
                                         C.POINTER(Challenger), C.POINTER(FriParams), ui, U64P]),
+            "orc_verify_fri_checks": (ui, [C.POINTER(U64P), C.POINTER(sz), sz, C.POINTER(FriBatchInfo), C.POINTER(U64P), sz,
+                                           C.POINTER(Challenger), C.POINTER(FriParams), ui, U64P]),
+            "orc_pow_grind": (u64, [C.POINTER(Challenger), ui]),
             "orc_partial_products": (C.c_int, [U64P, U64P, sz, ui, U64P, U64P, sz, sz, U64P]),
             "orc_quotient_permutation": (C.c_int, [U64P, U64P, U64P, sz, ui, U64P, U64P, U64P, sz, sz, U64P, U64P]),
             "orc_check_vanishing_at_zeta": (C.c_int, [U64P, U64P, U64P, U64P, U64P, U64P, sz, ui, U64P, U64P, U64P, sz, sz, U64P, U64P]),
@@ -393,12 +396,32 @@ def prove_openings(oracles, batches, challenger, params, degree_bits, forced_pow
     return proof
 
 
-def verify_fri(caps, ncols, batches, openings, challenger, params, degree_bits, proof):
+def _verify_fri_args(caps, ncols, batches, openings, challenger, params, degree_bits, proof):
     caps = [u64arr(c) for c in caps]; openings = [u64arr(o) for o in openings]
     cap_ptrs = (U64P * len(caps))(*[ptr(c) for c in caps])
     open_ptrs = (U64P * len(openings))(*[ptr(o) for o in openings])
     nc = (C.c_size_t * len(ncols))(*ncols)
     infos, keep = make_batch_infos(batches)
     proof = u64arr(proof)
-    return bool(lib().orc_verify_fri(cap_ptrs, nc, len(caps), infos, open_ptrs, len(batches), C.byref(challenger.c),
-                                     C.byref(params), degree_bits, ptr(proof)))
+    return (cap_ptrs, nc, len(caps), infos, open_ptrs, len(batches), C.byref(challenger.c), C.byref(params), degree_bits, ptr(proof)), \
+        (caps, openings, keep, proof)
+
+
+def verify_fri(caps, ncols, batches, openings, challenger, params, degree_bits, proof):
+    args, keep = _verify_fri_args(caps, ncols, batches, openings, challenger, params, degree_bits, proof)
+    return bool(lib().orc_verify_fri(*args))
+
+
+FRI_POW, FRI_CONSISTENCY, FRI_MERKLE = 1, 2, 4   # orc_verify_fri_checks bits
+
+
+def verify_fri_checks(caps, ncols, batches, openings, challenger, params, degree_bits, proof):
+    """orc_verify_fri_checks: the set of failed FRI checks ({"pow", "fri", "merkle"}; empty = the proof verifies), every query checked"""
+    args, keep = _verify_fri_args(caps, ncols, batches, openings, challenger, params, degree_bits, proof)
+    bits = int(lib().orc_verify_fri_checks(*args))
+    return {name for bit, name in ((FRI_POW, "pow"), (FRI_CONSISTENCY, "fri"), (FRI_MERKLE, "merkle")) if bits & bit}
+
+
+def pow_grind(challenger, pow_bits=16):
+    """orc_pow_grind: the smallest PoW nonce for the challenger's current state (the state is not changed)"""
+    return int(lib().orc_pow_grind(C.byref(challenger.c), pow_bits))

@@ -396,17 +396,13 @@ def test_negacyclic_ntt_to_edge_values(ctx, log_N):
 
 
 # ---------- device witness: the wd_* kernels of witness_device.hip ----------
-def test_device_witness_with_edge_presets(ctx):
-    """test_device_witness_for_every_gate_type (tests/test_gpu_gates.py) with every free preset taken from E instead of at random -- the
-    largest legal value where a generator has a range (edge_operands.legal_preset) -- and E public inputs; the Poseidon row that hashes the
-    public inputs keeps its zero padding, which is circuit structure.  Two instances with different E walks in one batch: the device wires
-    (wd_preset / wd_const / wd_arith / wd_bits / wd_rowop / wd_poseidon / wd_misc / wd_walk / wd_column kernels) equal the host plan's
-    witness and satisfy every constraint"""
-    import torch
+def _edge_witness(ctx, spec, log_n):
+    """the demo circuit over `spec` with every free preset taken from E (edge_operands.legal_preset) and E public inputs; the Poseidon row
+    that hashes the public inputs keeps its zero padding, which is circuit structure.  Two instances with different E walks, run by the
+    device witness generator -> (gate set, circuit, plan, WitnessDevice, preset columns, pi hashes)"""
     import test_gates_cpu as tg
-    log_n = 7
     n = 1 << log_n
-    gs, ps = go.GateSet(ALL), api.GateSet(ALL)
+    gs, ps = go.GateSet(spec), api.GateSet(spec)
     constants, wires, _, _, desc = go.demo_circuit(random.Random(404), gs, log_n, [eo.E[k] for k in (3, 5, 9, 11)], describe=True)
     circ = api.Circuit(ps, log_n, desc["row_gate"], constants, desc["copies"])
     generated = set()
@@ -430,6 +426,18 @@ def test_device_witness_with_edge_presets(ctx):
     plan = circ.witness_plan(positions)
     dev = api.WitnessDevice(ctx, plan, max_batch=2)
     dev.run(np.ascontiguousarray(np.array(columns, dtype=np.uint64).T))
+    return gs, circ, plan, dev, columns, pi_hashes
+
+
+def test_device_witness_with_edge_presets(ctx):
+    """test_device_witness_for_every_gate_type (tests/test_gpu_gates.py) with every free preset taken from E instead of at random -- the
+    largest legal value where a generator has a range (edge_operands.legal_preset) -- and E public inputs.  Two instances with different E
+    walks in one batch: the device wires (wd_preset / wd_const / wd_arith / wd_bits / wd_rowop / wd_poseidon / wd_misc / wd_walk / wd_column
+    kernels) equal the host plan's witness and satisfy every constraint"""
+    import torch
+    log_n = 7
+    n = 1 << log_n
+    gs, circ, plan, dev, columns, pi_hashes = _edge_witness(ctx, ALL, log_n)
     d_w = torch.zeros((135, n), dtype=torch.int64, device="cuda")
     for i in range(2):
         dev.wires(i, d_w.data_ptr())
@@ -440,3 +448,43 @@ def test_device_witness_with_edge_presets(ctx):
         ok, msg = circ.check_witness(got, pi_hashes[i])
         assert ok, msg
     dev.free(); plan.free()
+
+
+WITNESS_SETS = [(ALL, 7), (SMALL_VARIANTS + ["noop", "public_input", "poseidon"], 6)]
+
+
+@pytest.mark.parametrize("spec,log_n", WITNESS_SETS, ids=["all14", "small_variants"])
+def test_device_checker_on_edge_witnesses(ctx, spec, log_n):
+    """the device witness checker (api.WitnessChecker) on the edge-valued witnesses above: it accepts them from host arrays and as the wires
+    WitnessDevice leaves in HBM; then one cell of every used row replaced by another E value: the device's (ok, message) is the host
+    checker's, exactly"""
+    import torch
+    n = 1 << log_n
+    gs, circ, plan, dev, columns, pi_hashes = _edge_witness(ctx, spec, log_n)
+    chk = api.WitnessChecker(ctx, circ)
+    d_w = torch.zeros((135, n), dtype=torch.int64, device="cuda")
+    noop = gs.by_kind("noop").index
+    changed = 0
+    for i in range(2):
+        host = plan.run(columns[i])
+        h = pi_hashes[i]
+        assert chk.check(host, h) == (True, "") == circ.check_witness(host, h)
+        dev.wires(i, d_w.data_ptr())
+        ctx.synchronize()
+        assert chk.check(d_w.data_ptr(), h) == (True, "")
+        if i == 0:
+            continue
+        for row in range(n):
+            if int(circ.row_gate[row]) == noop:
+                continue
+            for k in range(2):
+                col = (11 * row + 37 * k) % gs.gates[int(circ.row_gate[row])].num_wires
+                w = host.copy()
+                cur = int(w[col, row])
+                j = eo.E.index(cur) if cur in eo.E else row % len(eo.E)
+                w[col, row] = eo.E[(j + 1 + k) % len(eo.E)]
+                want = circ.check_witness(w, h)
+                assert chk.check(w, h) == want, (row, col, want)
+                changed += 1
+    assert changed >= 40, changed
+    chk.free(); dev.free(); plan.free()
