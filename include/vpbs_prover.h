@@ -775,6 +775,23 @@ const char* vpbs_ivc_last_error(const vpbs_ivc* ivc);
 int vpbs_ivc_verifier_data(const vpbs_ivc* ivc, uint64_t* cyclic_vk, uint64_t* dummy_vk);
 long vpbs_ivc_prove_pbs(vpbs_ivc* ivc, const uint64_t* testv, const uint64_t* ct, const uint64_t* bsk, const uint64_t* ksk, unsigned n_lwe,
                         unsigned steps, uint8_t* proof_out, size_t capacity, vpbs_ivc_timing* timing, char* err, size_t err_len);
+/* Checkpoints of a running chain: fn(user, done, bytes, len) is called on the proving thread after chained step `done` for every `done`
+ * that is a multiple of `every` and below the call's last step (the last proof is the return value).  `bytes` are exactly what
+ * vpbs_ivc_prove_pbs(..., steps = done, ...) returns for the same inputs -- their public inputs hold the whole state the next step reads
+ * (acc_init | counter | accumulator | key hash | LWE hash | verifier data), their proof words the next step's inner proof -- and are valid
+ * during the call only.  Host and device-witness pipelines alike, and vpbs_ivc_resume_pbs.  every = 0 or fn = NULL: off (the default). */
+typedef void (*vpbs_ivc_checkpoint_fn)(void* user, unsigned done, const uint8_t* bytes, size_t len);
+int vpbs_ivc_set_checkpoint(vpbs_ivc* ivc, unsigned every, vpbs_ivc_checkpoint_fn fn, void* user);
+/* Resume a chain from a checkpoint (the bytes of a prefix of k steps): proves steps k .. steps - 1 and returns the last proof's bytes, which
+ * are byte-identical to vpbs_ivc_prove_pbs(ivc, testv, ct, bsk, ksk, n_lwe, steps, ...).  steps = 0: the whole chain; steps == k returns the
+ * checkpoint; steps < k is VPBS_ERR_INVALID.  The checkpoint is checked by the prefix form of vpbs_verify_pbs against this object's own
+ * cyclic verifier data -- parse, test vector, counter, vpbs_verify_step, verifier data and the LWE chain before anything is queued, the key
+ * chain on a host thread of its own beside the first resumed steps -- so its accumulator needs no recomputing; a checkpoint that fails
+ * never yields a proof: VPBS_ERR_INVALID with err = "checkpoint: <why>".  The step hook sees done = k + 1 .. steps (no base proof),
+ * checkpoints fire as above, timing->steps counts the steps proven here and base_proof_ms is 0.  A sharded chain refuses: VPBS_ERR_INVALID. */
+long vpbs_ivc_resume_pbs(vpbs_ivc* ivc, const uint64_t* testv, const uint64_t* ct, const uint64_t* bsk, const uint64_t* ksk, unsigned n_lwe,
+                         const uint8_t* checkpoint, size_t len, unsigned steps, uint8_t* proof_out, size_t capacity, vpbs_ivc_timing* timing,
+                         char* err, size_t err_len);
 
 /* = verify_pbs (/root/reference/src/vtfhe/ivc_based_vpbs.rs:388-489): the statement of ONE verifiable PBS checked on the last proof of its IVC
  * chain, in the reference's order -- claimed test vector, counter = n + 2, output ciphertext = the proof's accumulator, cd.verify(proof)
@@ -794,6 +811,13 @@ typedef struct {
     const uint64_t* ksk;      /* [ggsw_len] */
 } vpbs_verify_pbs_inputs;
 int vpbs_verify_pbs(const vpbs_verify_pbs_inputs* in, const uint8_t* proof_bytes, size_t len, char* why, size_t why_len);
+/* The prefix form: the same checks, in the same order and with the same `why` texts, on the last proof of a chain of k = counter proofs,
+ * any k in 1 .. n + 2 -- what vpbs_ivc_prove_pbs(..., steps = k, ...) returns, i.e. a checkpoint of the chain.  The counter must be in
+ * 1 .. n + 2 ("the counter is not in 1 .. n + 2"); out_ct is optional (NULL: not compared); the key hash chain runs over the first k items
+ * of [dummy GGSW, bsk_0 .. bsk_{n-1}, ksk], the LWE chain over the first k of [ct[n], ct[0] .. ct[n-1], 0].  Returns 1 and *steps_done = k
+ * (steps_done may be NULL), 0 = rejected (why), < 0 = malformed arguments.  At k = n + 2 with out_ct given its verdict and why are
+ * vpbs_verify_pbs's.  The key chain costs about 1.84 s x k / (n + 2) on one host thread at the paper's parameters. */
+int vpbs_verify_pbs_prefix(const vpbs_verify_pbs_inputs* in, const uint8_t* bytes, size_t len, unsigned* steps_done, char* why, size_t why_len);
 
 /* ---- batch verifier of whole vPBS proofs on the device (csrc/verify_pbs_batch.hip) ----
  * vpbs_verify_pbs for many last proofs of IVC chains made under ONE key set.  For proof i = bytes[offsets[i] .. offsets[i + 1]) with

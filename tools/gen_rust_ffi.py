@@ -254,7 +254,7 @@ EXCERPT = [
       "vpbs_device_scatter", "vpbs_witness_device_create", "vpbs_witness_device_run", "vpbs_witness_device_wires", "vpbs_witness_device_read"]),
     ("one verifiable PBS as verified_pbs / verify_pbs see it (ivc_based_vpbs.rs:159-386, :388-489)",
      ["vpbs_ivc_create", "vpbs_ivc_set_step_callback", "vpbs_ivc_set_device_witness", "vpbs_ivc_last_error", "vpbs_ivc_verifier_data", "vpbs_ivc_prove_pbs",
-      "vpbs_ivc_free", "vpbs_verify_pbs"]),
+      "vpbs_ivc_set_checkpoint", "vpbs_ivc_resume_pbs", "vpbs_ivc_free", "vpbs_verify_pbs", "vpbs_verify_pbs_prefix"]),
     ("many vPBS proofs of one key set verified in one device batch (verify_pbs's verdict and reason for each)",
      ["vpbs_pbs_key_hash", "vpbs_pbs_reason_text", "vpbs_pbs_verifier_create", "vpbs_pbs_verifier_run", "vpbs_pbs_verifier_free"]),
     ("RCCL collectives of a sharded step (the library binds librccl.so itself)",

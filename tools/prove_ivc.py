@@ -16,11 +16,16 @@ usage: tools/prove_ivc.py [N=1024] [n_lwe=728] [log_n=16] [steps=all]   ->  one 
   VPBS_IVC_VERIFY=device: the chains share one key set (their ciphertexts differ) and the final proofs of all of them are checked in one
   device batch (api.PbsVerifier: verify_pbs's verdict and reason for each, the key hash computed once on the host); the JSON line reports
   the verdicts and the device verification time.  The default (host) checks each chain's proof on the host only.
+  VPBS_IVC_CHECKPOINT=dir:every: every `every` steps each chain's proof so far is written to dir/chain<c>_step<k>.bin (vpbs_ivc_set_checkpoint;
+  written to a temporary name and renamed, so a crash never leaves a torn file).  VPBS_IVC_RESUME=path: chain 0 resumes from that checkpoint
+  (vpbs_ivc_resume_pbs) instead of starting at step 0; the checks of the last proof are the same.  The JSON line reports resumed_from and
+  checkpoints_written.
 Several GPUs (BASELINE config 4): python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 tools/prove_ivc.py ...
   the chain is sequential, so the GPUs share every STEP: each step proof is coset-sharded over the ranks (vpbs_prove_step_sharded: a rank
   computes the LDEs, leaf hashes and Merkle subtrees of its cosets; cap hashes, quotient values and query records travel over the library's
   RCCL collectives), every rank generates the (identical) witness on its host and ends with the identical proof.  VPBS_PBS_BACKEND=gloo and
   VPBS_PBS_DEVICE=0 put all ranks on one GPU with the callback communicator (tests)."""
+import hashlib
 import json
 import os
 import sys
@@ -248,9 +253,26 @@ def check_chain(ctx, d, vk, blob, keys, testv, delta, ct, N, n_lwe, log_n, steps
     return t_verify, decrypted
 
 
-def run_chain_native(ctx, ivc, d, N, n_lwe, log_n, steps, seed, message, start, dist=None, nonce=0, keep_statement=False):
+def checkpoint_writer(directory, chain):
+    """on_checkpoint's fn for VPBS_IVC_CHECKPOINT: directory/chain<c>_step<k>.bin, written under a temporary name and renamed into place"""
+    written = []
+
+    def write(done, blob):
+        path = os.path.join(directory, "chain%d_step%d.bin" % (chain, done))
+        tmp = path + ".tmp"
+        with open(tmp, "wb") as f:
+            f.write(blob)
+            f.flush()
+            os.fsync(f.fileno())
+        os.replace(tmp, path)
+        written.append(path)
+    return write, written
+
+
+def run_chain_native(ctx, ivc, d, N, n_lwe, log_n, steps, seed, message, start, dist=None, nonce=0, keep_statement=False, resume=None):
     """the same PBS through the library's own driver (vpbs_ivc_prove_pbs: the loop of run_chain in C++, csrc/ivc.hip) -> result dict;
-    keep_statement: it carries "statement" = (proof bytes, testv, ct, out_ct, keys) for a batch verification after the clock"""
+    keep_statement: it carries "statement" = (proof bytes, testv, ct, out_ct, keys) for a batch verification after the clock;
+    resume: checkpoint bytes to go on from (vpbs_ivc_resume_pbs) instead of step 0"""
     total, kn = n_lwe + 2, K * N
     t_keys = time.perf_counter()
     keys = ctx.keygen(N, K, ELL, LOGB, n_lwe, seed, 4.99027217501041e-8, 1.17021618159313e-5)
@@ -261,7 +283,10 @@ def run_chain_native(ctx, ivc, d, N, n_lwe, log_n, steps, seed, message, start, 
     ncols = [d.n_constants + 80, 135, 20, 16]
     torch.cuda.synchronize()
     start.wait()
-    blob, t = ivc.prove_pbs(testv, ct, keys["bsk"], keys["ksk"], steps)
+    if resume is None:
+        blob, t = ivc.prove_pbs(testv, ct, keys["bsk"], keys["ksk"], steps)
+    else:
+        blob, t = ivc.resume_pbs(resume, testv, ct, keys["bsk"], keys["ksk"], steps)
     if dist:
         dist.barrier()
     t_verify, decrypted = check_chain(ctx, d, vk, blob, keys, testv, delta, ct, N, n_lwe, log_n, steps, message)
@@ -273,7 +298,8 @@ def run_chain_native(ctx, ivc, d, N, n_lwe, log_n, steps, seed, message, start, 
                                                "prove_step": t["prove_step_ms"], "base_proof_once": t["base_proof_ms"],
                                                "witness_early_phase_on_a_second_thread": t["early_witness_ms"],
                                                "late_stages_run_during_the_previous_proofs_fri_stage": t["late_ahead_ms"]},
-            "proof_bytes": len(blob), "verify_ms": 1e3 * t_verify, "message": message, "decrypted": decrypted, "keygen_s": t_keys}
+            "proof_bytes": len(blob), "verify_ms": 1e3 * t_verify, "message": message, "decrypted": decrypted, "keygen_s": t_keys,
+            "resumed_from": None if resume is None else steps - t["steps"], "proof_sha256": hashlib.sha256(blob).hexdigest()}
 
 
 class CpuByRole:
@@ -364,6 +390,14 @@ def main():
     if check_witness and not (native_driver and world == 1):
         raise SystemExit("VPBS_IVC_CHECK_WITNESS needs the library driver on one GPU (a sharded chain is not checked)")
     device_verify = os.environ.get("VPBS_IVC_VERIFY", "host") == "device"
+    # VPBS_IVC_CHECKPOINT=dir:every / VPBS_IVC_RESUME=path (library driver): checkpoints of every chain, chain 0 resumed from one
+    checkpoint_spec, resume_path = os.environ.get("VPBS_IVC_CHECKPOINT", ""), os.environ.get("VPBS_IVC_RESUME", "")
+    if (checkpoint_spec or resume_path) and not native_driver:
+        raise SystemExit("VPBS_IVC_CHECKPOINT / VPBS_IVC_RESUME need the library driver")
+    if resume_path and world > 1:
+        raise SystemExit("VPBS_IVC_RESUME: a sharded chain is not resumed")
+    resume_bytes = open(resume_path, "rb").read() if resume_path else None
+    writers = []
     if device_verify and not (native_driver and world == 1 and steps == total):
         raise SystemExit("VPBS_IVC_VERIFY=device needs the library driver on one GPU and whole chains (verify_pbs checks counter = n + 2)")
     chains = []
@@ -384,6 +418,12 @@ def main():
                 ivc.set_device_witness(ELL, LOGB, int(os.environ["VPBS_IVC_DEVICE_WITNESS"]), os.environ.get("VPBS_IVC_DEVICE_LATE", "") not in ("", "0"))
             if check_witness:   # every witness of the chain checked on the device before it is proven (vpbs_ivc_set_check_witness)
                 ivc.set_check_witness(True)
+            if checkpoint_spec:
+                directory, every = checkpoint_spec.rsplit(":", 1)
+                os.makedirs(directory, exist_ok=True)
+                write, written = checkpoint_writer(directory, ci)
+                ivc.on_checkpoint(int(every), write)
+                writers.append(written)
             chains.append((ctx, ivc, cd))
         else:
             chains.append((ctx, Circuit(ctx, cyc_path, comm, dist_device), Circuit(ctx, dummy_path)))
@@ -400,7 +440,8 @@ def main():
             if native_driver:
                 # one key set for all chains when their proofs are verified in one batch (one vpbs_pbs_verifier holds one key hash)
                 results[ci] = run_chain_native(ctx, cyc, dum, N, n_lwe, log_n, steps, 0x5EED0728 + (0 if device_verify else ci), (message + ci) % 2,
-                                               start, dist, nonce=ci if device_verify else 0, keep_statement=device_verify)
+                                               start, dist, nonce=ci if device_verify else 0, keep_statement=device_verify,
+                                               resume=resume_bytes if ci == 0 else None)
             else:
                 results[ci] = run_chain(ctx, cyc, dum, N, n_lwe, log_n, steps, 0x5EED0728 + ci, (message + ci) % 2, start, dist)
         except BaseException as e:                           # noqa: BLE001
@@ -468,6 +509,8 @@ def main():
         "vpbs_proofs_per_s": (n_chains / seconds) if steps == total else None, "ms_per_step": 1e3 * seconds / steps,
         "ms_per_step_split": r0["split"], "ms_per_step_split_other_chains": [r["split"] for r in results[1:]],
         "proof_bytes": r0["proof_bytes"], "verify_last_proof_ms": r0["verify_ms"], "message": r0["message"], "decrypted": r0["decrypted"],
+        "proof_sha256": r0.get("proof_sha256"), "resumed_from": r0.get("resumed_from"),
+        "checkpoints_written": [len(w) for w in writers] if checkpoint_spec else None,
         "other_chains": [{k: r[k] for k in ("seconds", "message", "decrypted")} for r in results[1:]],
         "before_the_clock": {"circuit_files_commit_plan_s": t_setup, "seeded_keygen_s": r0["keygen_s"]},
         "cpu_by_role": cpu_report,

@@ -151,6 +151,7 @@ ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, U64P, C.c_size_t, U64P)
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, U64P, C.c_size_t)
 ALLGATHER_DEV_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t)
 IVC_STEP_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_uint)
+IVC_CHECKPOINT_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_uint, C.POINTER(C.c_uint8), C.c_size_t)
 
 
 class CommC(C.Structure):
@@ -278,6 +279,10 @@ SIGNATURES = {
     "vpbs_ivc_witness_checks": (_i, [_vp, U64P]),
     "vpbs_ivc_prove_pbs": (C.c_long, [_vp, U64P, U64P, U64P, U64P, _ui, _ui, C.POINTER(C.c_uint8), _sz, C.POINTER(IvcTimingC), C.c_char_p, _sz]),
     "vpbs_verify_pbs": (_i, [C.POINTER(VerifyPbsInputsC), C.POINTER(C.c_uint8), _sz, C.c_char_p, _sz]),
+    "vpbs_verify_pbs_prefix": (_i, [C.POINTER(VerifyPbsInputsC), C.POINTER(C.c_uint8), _sz, C.POINTER(_ui), C.c_char_p, _sz]),
+    "vpbs_ivc_set_checkpoint": (_i, [_vp, _ui, IVC_CHECKPOINT_FN, _vp]),
+    "vpbs_ivc_resume_pbs": (C.c_long, [_vp, U64P, U64P, U64P, U64P, _ui, C.POINTER(C.c_uint8), _sz, _ui, C.POINTER(C.c_uint8), _sz,
+                                       C.POINTER(IvcTimingC), C.c_char_p, _sz]),
     "vpbs_pbs_key_hash": (_i, [U64P, U64P, _ui, _sz, U64P]),
     "vpbs_pbs_reason_text": (C.c_char_p, [_i]),
     "vpbs_pbs_verifier_create": (_i, [_vp, C.POINTER(VerifyPbsInputsC), U64P, _sz, C.POINTER(_vp), C.c_char_p, _sz]),
@@ -1013,6 +1018,32 @@ class Ivc:
         self._step_cb = IVC_STEP_FN(trampoline)
         lib().vpbs_ivc_set_step_callback(self.h, self._step_cb, None)
 
+    def on_checkpoint(self, every, fn):
+        """vpbs_ivc_set_checkpoint: fn(done, bytes) runs on the proving thread after every chained step `done` that is a multiple of `every`
+        and below the call's last step; bytes are what prove_pbs(..., steps=done) returns -- a checkpoint resume_pbs takes.  every = 0 or
+        fn = None turns it off.  An exception raised by fn is kept and re-raised by prove_pbs / resume_pbs."""
+        self._ckpt_error = None
+        if fn is None or not every:
+            self._ckpt_cb = None
+            lib().vpbs_ivc_set_checkpoint(self.h, 0, C.cast(None, IVC_CHECKPOINT_FN), None)
+            return
+
+        def trampoline(_user, done, data, n):
+            try:
+                if self._ckpt_error is None:
+                    fn(int(done), C.string_at(data, n))
+            except BaseException as e:   # noqa: BLE001 -- must not unwind through the C frames
+                self._ckpt_error = e
+        self._ckpt_cb = IVC_CHECKPOINT_FN(trampoline)
+        lib().vpbs_ivc_set_checkpoint(self.h, every, self._ckpt_cb, None)
+
+    def _raise_callback_errors(self):
+        for name in ("_step_error", "_ckpt_error"):
+            e = getattr(self, name, None)
+            if e is not None:
+                setattr(self, name, None)
+                raise e
+
     def prove_pbs(self, testv, ct, bsk, ksk, steps=0):
         """-> (ProofWithPublicInputs bytes of the LAST proof of the chain, timing dict)"""
         tv, c, ks = _u64(testv).reshape(-1), _u64(ct).reshape(-1), _u64(ksk).reshape(-1)
@@ -1020,11 +1051,25 @@ class Ivc:
         buf, t, err = (C.c_uint8 * self.max_bytes)(), IvcTimingC(), C.create_string_buffer(512)
         n = lib().vpbs_ivc_prove_pbs(self.h, _ptr(tv), _ptr(c), _ptr(bs) if bs is not None else None, _ptr(ks), c.size - 1, steps, buf,
                                      self.max_bytes, C.byref(t), err, 512)
-        if getattr(self, "_step_error", None) is not None:
-            e, self._step_error = self._step_error, None
-            raise e
+        self._raise_callback_errors()
         if n < 0:
             raise VpbsError("vpbs_ivc_prove_pbs: " + err.value.decode())
+        return bytes(buf[:n]), {f: getattr(t, f) for f, _ in IvcTimingC._fields_}
+
+    def resume_pbs(self, checkpoint, testv, ct, bsk, ksk, steps=0):
+        """vpbs_ivc_resume_pbs: the chain from a checkpoint (the bytes of a prefix of k steps) to `steps` (0: the whole chain) -> (the bytes
+        prove_pbs(testv, ct, bsk, ksk, steps) returns, timing dict of the steps proven here).  A checkpoint that does not verify against this
+        object's verifier data, these keys and this ciphertext raises VpbsError "... checkpoint: <why>"."""
+        tv, c, ks = _u64(testv).reshape(-1), _u64(ct).reshape(-1), _u64(ksk).reshape(-1)
+        bs = _u64(bsk).reshape(-1) if c.size > 1 else None
+        cp = bytes(checkpoint)
+        src = (C.c_uint8 * max(1, len(cp))).from_buffer_copy(cp or b"\0")
+        buf, t, err = (C.c_uint8 * self.max_bytes)(), IvcTimingC(), C.create_string_buffer(512)
+        n = lib().vpbs_ivc_resume_pbs(self.h, _ptr(tv), _ptr(c), _ptr(bs) if bs is not None else None, _ptr(ks), c.size - 1, src, len(cp),
+                                      steps, buf, self.max_bytes, C.byref(t), err, 512)
+        self._raise_callback_errors()
+        if n < 0:
+            raise VpbsError("vpbs_ivc_resume_pbs: " + err.value.decode())
         return bytes(buf[:n]), {f: getattr(t, f) for f, _ in IvcTimingC._fields_}
 
     def free(self):
@@ -1065,6 +1110,39 @@ def verify_pbs(blob, cs_cap, ncols, circuit_digest, log_n, n_constants, n_routed
     if rc < 0:
         raise VpbsError("vpbs_verify_pbs: " + why.value.decode())
     return rc == 1, why.value.decode()
+
+
+def verify_pbs_prefix(blob, cs_cap, ncols, circuit_digest, log_n, n_constants, n_routed, gates, N, K, testv, ct, bsk, ksk, out_ct=None,
+                      num_challenges=2, quotient_degree_factor=8, rate_bits=3, cap_height=4, compat=None):
+    """vpbs_verify_pbs_prefix: verify_pbs's checks on the last proof of a chain of k = counter proofs (a checkpoint), k in 1 .. n + 2, the hash
+    chains over the first k keys and masks; out_ct optional -> (accepted, k, reason of the first failing check).  Arguments as verify_pbs."""
+    v = VerifyInputsC()
+    v.log_n, v.rate_bits, v.cap_height = log_n, rate_bits, cap_height
+    v.n_constants_sigmas, v.n_wires, v.n_zs_partial_products, v.n_quotient = ncols
+    v.num_challenges = num_challenges
+    cap = _u64(cs_cap)
+    v.constants_sigmas_cap = _ptr(cap)
+    for i in range(4):
+        v.circuit_digest[i] = int(circuit_digest[i])
+    v.n_constants, v.n_routed, v.quotient_degree_factor = n_constants, n_routed, quotient_degree_factor
+    v.gates, v.n_gates, v.num_selectors = gates.arr, gates.n, gates.num_selectors
+    if compat is not None:
+        v.compat = C.pointer(compat)
+    p = VerifyPbsInputsC()
+    p.circuit = C.pointer(v)
+    ct_a, tv, ks = _u64(ct).reshape(-1), _u64(testv).reshape(-1), _u64(ksk).reshape(-1)
+    bs = _u64(bsk).reshape(-1) if bsk is not None and len(bsk) else None
+    oc = _u64(out_ct).reshape(-1) if out_ct is not None else None
+    p.N, p.K, p.n_lwe, p.ggsw_len = N, K, ct_a.size - 1, ks.size
+    p.testv, p.ct, p.ksk = _ptr(tv), _ptr(ct_a), _ptr(ks)
+    p.bsk = _ptr(bs) if bs is not None else None
+    p.out_ct = _ptr(oc) if oc is not None else None
+    buf = (C.c_uint8 * max(1, len(blob))).from_buffer_copy(bytes(blob) or b"\0")
+    why, done = C.create_string_buffer(256), C.c_uint(0)
+    rc = lib().vpbs_verify_pbs_prefix(C.byref(p), buf, len(blob), C.byref(done), why, 256)
+    if rc < 0:
+        raise VpbsError("vpbs_verify_pbs_prefix: " + why.value.decode())
+    return rc == 1, int(done.value), why.value.decode()
 
 
 (PBS_OK, PBS_MALFORMED, PBS_TESTV_MASK, PBS_TESTV, PBS_COUNTER, PBS_OUT_CT, PBS_PROOF, PBS_VERIFIER_DATA, PBS_KEY_HASH,

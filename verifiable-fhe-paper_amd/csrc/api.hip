@@ -1080,9 +1080,14 @@ int vpbs_blind_rotate_step(vpbs_ctx* c, const vpbs_tfhe_params* prm, unsigned ba
     });
 }
 
-int vpbs_pbs_accumulator_chain(vpbs_ctx* c, const vpbs_tfhe_params* prm, unsigned n_lwe, const uint64_t* acc_init, const uint64_t* lwe_ct,
-                               const uint64_t* bsk, const uint64_t* ksk, uint64_t* accs_out) {
-    if (!c || !prm || !acc_init || !lwe_ct || !bsk || !ksk || !accs_out || n_lwe == 0) return VPBS_ERR_INVALID;
+}  // extern "C"
+
+namespace vpbs {
+// The accumulator chain from step `start` on (vpbs_ivc_resume_pbs): acc_in is the accumulator step `start` reads (acc_init at start = 0, the
+// output of step start - 1 otherwise); first_step only at step 0, last_step at step n + 1; accs_out receives [n + 2 - start][K][N].
+int pbs_accumulator_chain_from(vpbs_ctx* c, const vpbs_tfhe_params* prm, unsigned n_lwe, unsigned start, const uint64_t* acc_in,
+                               const uint64_t* lwe_ct, const uint64_t* bsk, const uint64_t* ksk, uint64_t* accs_out) {
+    if (!c || !prm || !acc_in || !lwe_ct || !bsk || !ksk || !accs_out || n_lwe == 0 || start > n_lwe + 1) return VPBS_ERR_INVALID;
     return guarded(c, [&] {
         const unsigned log_n = prm->log_N, K = prm->K, ELL = prm->ELL, LOGB = prm->LOGB;
         VPBS_REQUIRE(log_n >= 1 && log_n <= 11 && K >= 1 && K <= 8 && LOGB >= 1 && LOGB <= 32, "unsupported TFHE parameters");
@@ -1099,10 +1104,10 @@ int vpbs_pbs_accumulator_chain(vpbs_ctx* c, const vpbs_tfhe_params* prm, unsigne
         for (unsigned x = 0; x < n_lwe; ++x) h_masks[1 + x] = lwe_ct[x];
         h_masks[n_lwe + 1] = 0;
         DevTemp masks(c, h_masks.data(), h_masks.size()), limbs(c, nullptr, (size_t)K * ELL * n);
-        VPBS_HIP(hipMemcpyAsync(accs.p, acc_init, sizeof(u64) * acc_words, hipMemcpyHostToDevice, c->stream));
+        VPBS_HIP(hipMemcpyAsync(accs.p + (size_t)start * acc_words, acc_in, sizeof(u64) * acc_words, hipMemcpyHostToDevice, c->stream));
         {
             vpbs::Timed t(c, "pbs_accumulator_chain");
-            for (unsigned step = 0; step < n_lwe + 2; ++step) {
+            for (unsigned step = start; step < n_lwe + 2; ++step) {
                 const bool first = step == 0, last = step == n_lwe + 1;
                 const u64* ggsw = first ? nullptr : (last ? kk.p : keys.p + (size_t)(step - 1) * ggsw_words);
                 vpbs::launch_blind_rotate_step(c->stream, accs.p + (size_t)step * acc_words, masks.p + step, ggsw, 0, tab, tab + n, ninv, log_n, K,
@@ -1110,9 +1115,18 @@ int vpbs_pbs_accumulator_chain(vpbs_ctx* c, const vpbs_tfhe_params* prm, unsigne
             }
         }
         VPBS_HIP(hipGetLastError());
-        VPBS_HIP(hipMemcpyAsync(accs_out, accs.p + acc_words, sizeof(u64) * (size_t)(n_lwe + 2) * acc_words, hipMemcpyDeviceToHost, c->stream));
+        VPBS_HIP(hipMemcpyAsync(accs_out, accs.p + (size_t)(start + 1) * acc_words, sizeof(u64) * (size_t)(n_lwe + 2 - start) * acc_words,
+                                 hipMemcpyDeviceToHost, c->stream));
         VPBS_HIP(vpbs::stream_sync(c->stream));
     });
+}
+}  // namespace vpbs
+
+extern "C" {
+
+int vpbs_pbs_accumulator_chain(vpbs_ctx* c, const vpbs_tfhe_params* prm, unsigned n_lwe, const uint64_t* acc_init, const uint64_t* lwe_ct,
+                               const uint64_t* bsk, const uint64_t* ksk, uint64_t* accs_out) {
+    return vpbs::pbs_accumulator_chain_from(c, prm, n_lwe, 0, acc_init, lwe_ct, bsk, ksk, accs_out);
 }
 
 // ---------------- memory helpers for hosts without the HIP runtime ----------------

@@ -35,6 +35,11 @@ int device_scatter(vpbs_ctx* c, uint64_t* d_dst, const uint64_t* d_positions, co
 // ... and the late witness phase on the device stage by stage (witness_device.hip): queued as the previous proof's sections become final
 unsigned witness_device_late_stages(const vpbs_witness_device* d);
 int witness_device_run_late_stage(vpbs_witness_device* d, unsigned instance, unsigned stage, const uint64_t* preset_val, int wait);
+// ... the accumulator chain from a later step (api.hip) and the two halves of vpbs_verify_pbs_prefix (verifier.hip), for vpbs_ivc_resume_pbs
+int pbs_accumulator_chain_from(vpbs_ctx* c, const vpbs_tfhe_params* prm, unsigned n_lwe, unsigned start, const uint64_t* acc_in,
+                               const uint64_t* lwe_ct, const uint64_t* bsk, const uint64_t* ksk, uint64_t* accs_out);
+int verify_pbs_prefix_without_keys(const vpbs_verify_pbs_inputs* in, const uint8_t* bytes, size_t len, unsigned* steps_done, char* why, size_t why_len);
+bool pbs_key_chain_prefix_matches(const vpbs_verify_pbs_inputs* in, unsigned k, const uint64_t claimed[4]);
 }
 
 namespace {
@@ -291,6 +296,19 @@ struct vpbs_ivc {
     vpbs_comm comm{};
     vpbs_ivc_step_fn step_fn = nullptr;
     void* step_user = nullptr;
+    vpbs_ivc_checkpoint_fn ckpt_fn = nullptr;   // vpbs_ivc_set_checkpoint
+    void* ckpt_user = nullptr;
+    unsigned ckpt_every = 0;
+    std::vector<uint8_t> ckpt_bytes;
+    // after chained step `done` of a call that ends at step `last`: the proof serialised exactly as a call with steps = done returns it
+    int checkpoint(const vpbs_step_inputs& in, const u64* caps, const u64* openings, const u64* fri, unsigned done, unsigned last) {
+        if (!ckpt_fn || !ckpt_every || done % ckpt_every != 0 || done >= last) return VPBS_OK;
+        if (ckpt_bytes.empty()) ckpt_bytes.resize(8 * (proof_words + n_pi) + (1 << 16));
+        const long n = vpbs_step_proof_to_bytes(ctx, &in, cyc.n_const_cols, caps, openings, fri, ckpt_bytes.data(), ckpt_bytes.size());
+        if (n <= 0) return VPBS_ERR_INVALID;
+        ckpt_fn(ckpt_user, done, ckpt_bytes.data(), (size_t)n);
+        return VPBS_OK;
+    }
     // early witness phases on the device (vpbs_ivc_set_device_witness): two early-only device objects, each on a context of its own (their
     // runs overlap with the prover's context and with each other's gathers), filled alternately with batches of `dw_batch` steps
     unsigned dw_batch = 0, ELL = 0, LOGB = 0;
@@ -527,8 +545,12 @@ int vpbs_ivc_set_device_witness(vpbs_ivc* v, unsigned ELL, unsigned LOGB, unsign
 // `dw_batch` consecutive steps run on the device at once (thread B), a stager thread gathers an instance's wires into the device matrix
 // the prover will read and fetches the early values the late phase needs (thread S), and the caller is left with the late phase (the
 // in-circuit verifier's rows), the scatter of its values and the proof.
+// from > 0 (vpbs_ivc_resume_pbs): no base proof; step `from` takes the checkpoint's proof words and public inputs, the native accumulator
+// chain starts at step `from` from the checkpoint's accumulator and the hash thread from its two hashes.  Progress below is counted in steps
+// of THIS call: local step j is chain step from + j.
 static long prove_pbs_device_witness(vpbs_ivc* v, const uint64_t* testv, const uint64_t* ct, const uint64_t* bsk, const uint64_t* ksk, unsigned n_lwe,
-                                     unsigned steps, uint8_t* proof_out, size_t capacity, vpbs_ivc_timing* timing, char* err, size_t err_len) {
+                                     unsigned from, const u64* from_proof, const u64* from_pis, unsigned steps, uint8_t* proof_out, size_t capacity,
+                                     vpbs_ivc_timing* timing, char* err, size_t err_len) {
     auto say = [&](const std::string& m) {
         if (err && err_len) {
             std::strncpy(err, m.c_str(), err_len - 1);
@@ -538,28 +560,34 @@ static long prove_pbs_device_witness(vpbs_ivc* v, const uint64_t* testv, const u
     Side &cyc = v->cyc, &dum = v->dum;
     vpbs_ctx* ctx = v->ctx;
     const size_t kn = v->kn, n_pi = v->n_pi, proof_words = v->proof_words, ggsw_len = v->ggsw_len, n_preset = cyc.n_preset;
-    const unsigned B = v->dw_batch, total = n_lwe + 2;
+    const unsigned B = v->dw_batch, total = n_lwe + 2, n_run = steps - from;
     const std::vector<u64> zero_ggsw(ggsw_len, 0);
     auto ggsw_of = [&](unsigned s) { return s == 0 ? zero_ggsw.data() : (s <= n_lwe ? bsk + (size_t)(s - 1) * ggsw_len : ksk); };
     auto mask_of = [&](unsigned s) { return s == 0 ? ct[n_lwe] : (s <= n_lwe ? ct[s - 1] : (u64)0); };
     const double t0 = now();
     // ---- the chain's public inputs, natively ----
-    std::vector<u64> acc_init(kn, 0), accs((size_t)total * kn);
+    // accs[j] = the accumulator after chain step from + j (step `from` reads acc_init, or the checkpoint's accumulator)
+    std::vector<u64> acc_init(kn, 0), accs((size_t)(total - from) * kn);
     std::memcpy(acc_init.data() + kn - v->N, testv, 8 * (size_t)v->N);
     unsigned log_N = 0;
     while ((1u << log_N) < v->N) ++log_N;
     const vpbs_tfhe_params tp{log_N, v->K, v->ELL, v->LOGB};
-    if (vpbs_pbs_accumulator_chain(ctx, &tp, n_lwe, acc_init.data(), ct, bsk, ksk, accs.data()) != 0) {
+    if (vpbs::pbs_accumulator_chain_from(ctx, &tp, n_lwe, from, from ? from_pis + kn + 1 : acc_init.data(), ct, bsk, ksk, accs.data()) != 0) {
         say(std::string("native accumulator chain: ") + vpbs_last_error(ctx));
         return VPBS_ERR_INVALID;
     }
-    // pis[s + 1] = public inputs of step s (pis[0]: of the base proof): acc_init | counter | accumulator | key hash | LWE hash | verifier data
-    std::vector<u64> pis((size_t)(steps + 1) * n_pi, 0);
-    for (unsigned s = 0; s <= steps; ++s) {
-        u64* q = pis.data() + (size_t)s * n_pi;
+    // pis[j + 1] = public inputs of step from + j (pis[0]: of the base proof, or the checkpoint's): acc_init | counter | accumulator | key
+    // hash | LWE hash | verifier data
+    std::vector<u64> pis((size_t)(n_run + 1) * n_pi, 0);
+    for (unsigned j = 0; j <= n_run; ++j) {
+        u64* q = pis.data() + (size_t)j * n_pi;
+        if (j == 0 && from) {
+            std::memcpy(q, from_pis, 8 * n_pi);
+            continue;
+        }
         std::memcpy(q, acc_init.data(), 8 * kn);
-        q[kn] = s;
-        if (s) std::memcpy(q + kn + 1, accs.data() + (size_t)(s - 1) * kn, 8 * kn);
+        q[kn] = from + j;
+        if (j) std::memcpy(q + kn + 1, accs.data() + (size_t)(j - 1) * kn, 8 * kn);
         std::memcpy(q + n_pi - cyc.vk.size(), cyc.vk.data(), 8 * cyc.vk.size());
     }
     std::mutex mu;
@@ -574,7 +602,7 @@ static long prove_pbs_device_witness(vpbs_ivc* v, const uint64_t* testv, const u
         }
         cv.notify_all();
     };
-    unsigned hashed = 0;        // steps whose chain hashes are in pis (guarded by mu)
+    unsigned hashed = 0;        // steps whose chain hashes are in pis (guarded by mu; these four count the steps of this call: local j)
     unsigned batches_run = 0;   // batches whose early phases are on the device
     unsigned staged = 0;        // steps gathered and read back
     unsigned consumed = 0;      // steps the caller has finished with (their device matrix is free again)
@@ -583,26 +611,28 @@ static long prove_pbs_device_witness(vpbs_ivc* v, const uint64_t* testv, const u
     std::thread hasher([&] {
         name_thread("vpbs-hash");
         std::vector<u64> in2(5);
-        u64 hb[4] = {0, 0, 0, 0}, hl[4] = {0, 0, 0, 0};
+        u64 hb[4], hl[4];   // the chains so far: zero before the base proof, the checkpoint's hashes on a resume
+        std::memcpy(hb, pis.data() + 2 * kn + 1, 32);
+        std::memcpy(hl, pis.data() + 2 * kn + 5, 32);
         // the key chain in segments of eight links: the chains of one process walk theirs side by side (vpbs_hash_chain_links)
         constexpr unsigned SEG = 8;
         const u64* items[SEG];
         u64 links[4 * SEG];
-        for (unsigned s0 = 0; s0 < steps && !failed; s0 += SEG) {
+        for (unsigned s0 = 0; s0 < n_run && !failed; s0 += SEG) {
             {   // three batches ahead of the chain, no further: the batcher needs two, and the chains' hashing is spread over their whole
                 // length instead of a burst of 1.9 s of CPU per chain at the start (which a timed window further on would not see)
                 std::unique_lock<std::mutex> lk(mu);
                 cv.wait(lk, [&] { return failed || s0 < consumed + 3 * B; });
                 if (failed) return;
             }
-            const unsigned cnt = std::min(SEG, steps - s0);
-            for (unsigned i = 0; i < cnt; ++i) items[i] = ggsw_of(s0 + i);
+            const unsigned cnt = std::min(SEG, n_run - s0);
+            for (unsigned i = 0; i < cnt; ++i) items[i] = ggsw_of(from + s0 + i);
             if (vpbs_hash_chain_links(hb, items, cnt, ggsw_len, links) != 0) return fail("hash chain of the bootstrapping key: malformed arguments");
             std::memcpy(hb, links + 4 * (cnt - 1), 32);
             for (unsigned i = 0; i < cnt; ++i) {
                 const unsigned s = s0 + i;
                 std::memcpy(in2.data(), hl, 32);
-                in2[4] = mask_of(s);
+                in2[4] = mask_of(from + s);
                 vpbs_hash_no_pad(in2.data(), 5, hl);
                 u64* q = pis.data() + (size_t)(s + 1) * n_pi + 2 * kn + 1;
                 std::memcpy(q, links + 4 * i, 32);
@@ -616,11 +646,11 @@ static long prove_pbs_device_witness(vpbs_ivc* v, const uint64_t* testv, const u
         }
     });
     // thread B: batch b = steps [b B, (b + 1) B) on device object b & 1, once their public inputs exist and the object's previous batch is consumed
-    const unsigned n_batches = (steps + B - 1) / B;
+    const unsigned n_batches = (n_run + B - 1) / B;
     std::thread batcher([&] {
         name_thread("vpbs-batcher");
         for (unsigned b = 0; b < n_batches && !failed; ++b) {
-            const unsigned first = b * B, cnt = std::min(B, steps - first);
+            const unsigned first = b * B, cnt = std::min(B, n_run - first);
             {
                 std::unique_lock<std::mutex> lk(mu);
                 // step s needs the public inputs of step s - 1: hashed >= first + cnt - 1; the object held batch b - 2
@@ -632,8 +662,8 @@ static long prove_pbs_device_witness(vpbs_ivc* v, const uint64_t* testv, const u
             auto row = [&](size_t r) { return m + r * cnt; };
             for (size_t r = 0; r < proof_words; ++r) std::memset(row(r), 0, 8 * cnt);
             for (unsigned i = 0; i < cnt; ++i) {
-                const unsigned s = first + i;
-                const u64* q = pis.data() + (size_t)s * n_pi;
+                const unsigned s = from + first + i;
+                const u64* q = pis.data() + (size_t)(first + i) * n_pi;
                 size_t r = proof_words;
                 for (size_t k = 0; k < n_pi; ++k) row(r++)[i] = q[k];
                 row(r++)[i] = s == 0 ? 0 : 1;
@@ -646,7 +676,7 @@ static long prove_pbs_device_witness(vpbs_ivc* v, const uint64_t* testv, const u
                 for (size_t k = 0; k < n_pi; ++k) row(r++)[i] = 0;
             }
             if (vpbs_witness_device_run(v->wdev[b & 1], m, cnt) != 0)
-                return fail("early witness phases of steps " + std::to_string(first) + ".. on the device: " + vpbs_last_error(v->wctx[b & 1]));
+                return fail("early witness phases of steps " + std::to_string(from + first) + ".. on the device: " + vpbs_last_error(v->wctx[b & 1]));
             t_early += now() - t;
             {
                 std::lock_guard<std::mutex> lk(mu);
@@ -668,23 +698,23 @@ static long prove_pbs_device_witness(vpbs_ivc* v, const uint64_t* testv, const u
     std::thread stager([&] {
         name_thread("vpbs-stager");
         if (v->dw_late) return;   // the caller runs the late phase on the device object itself and gathers afterwards
-        for (unsigned s = 0; s < steps && !failed; ++s) {
-            const unsigned b = s / B, k = s % vpbs_ivc::NBUF;
+        for (unsigned j = 0; j < n_run && !failed; ++j) {
+            const unsigned b = j / B, k = j % vpbs_ivc::NBUF;
             {
                 std::unique_lock<std::mutex> lk(mu);
-                cv.wait(lk, [&] { return failed || (batches_run > b && s < consumed + vpbs_ivc::NBUF); });
+                cv.wait(lk, [&] { return failed || (batches_run > b && j < consumed + vpbs_ivc::NBUF); });
                 if (failed) return;
             }
-            if (vpbs_witness_device_wires(v->wdev[b & 1], s % B, v->d_bufs[k]) != 0 ||
-                vpbs_witness_device_read_late_inputs(v->wdev[b & 1], s % B, late_in[k].data()) != 0)
-                return fail("gathering the early wires of step " + std::to_string(s) + ": " + vpbs_last_error(v->wctx[b & 1]));
+            if (vpbs_witness_device_wires(v->wdev[b & 1], j % B, v->d_bufs[k]) != 0 ||
+                vpbs_witness_device_read_late_inputs(v->wdev[b & 1], j % B, late_in[k].data()) != 0)
+                return fail("gathering the early wires of step " + std::to_string(from + j) + ": " + vpbs_last_error(v->wctx[b & 1]));
             vpbs_witness_state* st = nullptr;
             if (vpbs_witness_state_from_late_inputs(cyc.plan, late_in[k].data(), &st) != 0)
-                return fail("late witness phase of step " + std::to_string(s) + ": the early values read back from the device are malformed");
+                return fail("late witness phase of step " + std::to_string(from + j) + ": the early values read back from the device are malformed");
             {
                 std::lock_guard<std::mutex> lk(mu);
                 states.st[k] = st;
-                staged = s + 1;
+                staged = j + 1;
             }
             cv.notify_all();
         }
@@ -706,16 +736,22 @@ static long prove_pbs_device_witness(vpbs_ivc* v, const uint64_t* testv, const u
     char e[256] = {0};
     vpbs_step_inputs in;
     vpbs_step_sizes sz{};
-    if (vpbs_witness_plan_run(dum.plan, pis.data(), 0, v->base_wires, e, sizeof e) != 0) return stop(std::string("dummy witness: ") + e, VPBS_ERR_INVALID);
+    if (!from && vpbs_witness_plan_run(dum.plan, pis.data(), 0, v->base_wires, e, sizeof e) != 0)
+        return stop(std::string("dummy witness: ") + e, VPBS_ERR_INVALID);
     dum.step_inputs(in, v->base_wires, false, pis.data());
     if (vpbs_step_sizes_get(ctx, &in, &sz) != 0 || 3 * sz.cap_words + sz.openings_words + sz.fri_words != proof_words)
         return stop("the proof of this shape does not have the number of words the cyclic circuit expects", VPBS_ERR_INVALID);
     std::vector<u64> values(n_preset, 0);   // run_late reads the late presets only: the previous proof's words, at the front
     u64 *caps = values.data(), *openings = caps + 3 * sz.cap_words, *fri = openings + sz.openings_words;
-    int rc = dum.prove(in, caps, openings, fri);
-    if (rc != 0) return stop(std::string("base proof: ") + vpbs_last_error(ctx), rc);
-    const double t_base = now() - t0;
-    if (v->step_fn) v->step_fn(v->step_user, 0);
+    int rc = VPBS_OK;
+    if (from) {
+        std::memcpy(values.data(), from_proof, 8 * proof_words);   // the checkpoint's proof is the inner proof of step `from`
+    } else {
+        rc = dum.prove(in, caps, openings, fri);
+        if (rc != 0) return stop(std::string("base proof: ") + vpbs_last_error(ctx), rc);
+    }
+    const double t_base = from ? 0.0 : now() - t0;
+    if (v->step_fn && !from) v->step_fn(v->step_user, 0);
     double t_late = 0, t_rows = 0, t_prove = 0, t_wait_staged = 0, t_wait_hashed = 0;
     double c_late = 0, c_rows = 0, c_prove = 0;   // CPU time of THIS thread in the same sections (VPBS_TRACE_IVC)
     // late stages 1 and 2 of the next step while this step's FRI stage runs (LateAhead); here the prover writes the proof straight into
@@ -788,16 +824,16 @@ static long prove_pbs_device_witness(vpbs_ivc* v, const uint64_t* testv, const u
         }
         return stop(m, why);
     };
-    for (unsigned s = 0; s < steps; ++s) {
-        const unsigned k = s % vpbs_ivc::NBUF;
+    for (unsigned j = 0; j < n_run; ++j) {
+        const unsigned s = from + j, k = j % vpbs_ivc::NBUF;
         {
             const double tw = now();
             std::unique_lock<std::mutex> lk(mu);
-            const unsigned b = s / B;
-            cv.wait(lk, [&] { return failed || (v->dw_late ? batches_run > b : staged > s); });
+            const unsigned b = j / B;
+            cv.wait(lk, [&] { return failed || (v->dw_late ? batches_run > b : staged > j); });
             const double tw2 = now();
             t_wait_staged += tw2 - tw;
-            cv.wait(lk, [&] { return failed || hashed > s; });   // its own public inputs are complete
+            cv.wait(lk, [&] { return failed || hashed > j; });   // its own public inputs are complete
             t_wait_hashed += now() - tw2;
             if (failed) {
                 lk.unlock();
@@ -808,15 +844,15 @@ static long prove_pbs_device_witness(vpbs_ivc* v, const uint64_t* testv, const u
         double c0 = thread_cpu();
         if (v->dw_late) {
             // the late phase on the device object that holds the step's early values, then ALL its wires into the prover's matrix
-            vpbs_witness_device* dev = v->wdev[(s / B) & 1];
-            rc = vpbs_witness_device_run_late(dev, s % B, values.data());
+            vpbs_witness_device* dev = v->wdev[(j / B) & 1];
+            rc = vpbs_witness_device_run_late(dev, j % B, values.data());
             if (rc != 0)
                 return stop_step("late witness phase of step " + std::to_string(s) + " (the previous proof does not verify in circuit): " +
-                            vpbs_last_error(v->wctx[(s / B) & 1]), rc);
+                            vpbs_last_error(v->wctx[(j / B) & 1]), rc);
             t_late += now() - t;
             t = now();
-            rc = vpbs_witness_device_wires(dev, s % B, v->d_bufs[k]);
-            if (rc != 0) return stop_step(std::string("gathering the wires: ") + vpbs_last_error(v->wctx[(s / B) & 1]), rc);
+            rc = vpbs_witness_device_wires(dev, j % B, v->d_bufs[k]);
+            if (rc != 0) return stop_step(std::string("gathering the wires: ") + vpbs_last_error(v->wctx[(j / B) & 1]), rc);
             t_rows += now() - t;
         } else {
             vpbs_witness_state* st = next_state;
@@ -847,15 +883,15 @@ static long prove_pbs_device_witness(vpbs_ivc* v, const uint64_t* testv, const u
         }
         t = now();
         c0 = thread_cpu();
-        cyc.step_inputs(in, v->d_bufs[k], true, pis.data() + (size_t)(s + 1) * n_pi);
+        cyc.step_inputs(in, v->d_bufs[k], true, pis.data() + (size_t)(j + 1) * n_pi);
         if (v->staged && !v->dw_late && s + 1 < steps) {
-            hook.step = s;
+            hook.step = j;
             in.on_section = &Hook::section;
             in.on_section_user = &hook;
         }
         static const bool dev_ahead = !std::getenv("VPBS_DEVICE_LATE_AHEAD") || std::atoi(std::getenv("VPBS_DEVICE_LATE_AHEAD")) != 0;   // A-B switch
         if (v->staged && v->dw_late && dev_ahead && s + 1 < steps) {
-            dev_hook.step = s;
+            dev_hook.step = j;
             dev_hook.queued = 0;
             in.on_section = &DevHook::section;
             in.on_section_user = &dev_hook;
@@ -872,10 +908,11 @@ static long prove_pbs_device_witness(vpbs_ivc* v, const uint64_t* testv, const u
         c_prove += thread_cpu() - c0;
         {
             std::lock_guard<std::mutex> lk(mu);
-            consumed = s + 1;
+            consumed = j + 1;
         }
         cv.notify_all();
         if (v->step_fn) v->step_fn(v->step_user, s + 1);
+        if (v->checkpoint(in, caps, openings, fri, s + 1, steps) != 0) return stop("checkpoint after step " + std::to_string(s) + ": the proof does not serialise", VPBS_ERR_INVALID);
     }
     hasher.join();
     batcher.join();
@@ -884,8 +921,8 @@ static long prove_pbs_device_witness(vpbs_ivc* v, const uint64_t* testv, const u
     if (std::getenv("VPBS_TRACE_IVC"))
         std::fprintf(stderr, "[ivc device witness] per step: waited %.2f ms for the staged wires, %.2f ms for the hash chain; late %.2f, scatter %.2f, "
                      "prove %.2f, device batch run %.2f ms; CPU time of the proving thread: late %.2f, scatter %.2f, prove %.2f ms (blocking waits: %d)\n",
-                     1e3 * t_wait_staged / steps, 1e3 * t_wait_hashed / steps, 1e3 * t_late / steps,
-                     1e3 * t_rows / steps, 1e3 * t_prove / steps, 1e3 * t_early / steps, 1e3 * c_late / steps, 1e3 * c_rows / steps, 1e3 * c_prove / steps,
+                     1e3 * t_wait_staged / n_run, 1e3 * t_wait_hashed / n_run, 1e3 * t_late / n_run,
+                     1e3 * t_rows / n_run, 1e3 * t_prove / n_run, 1e3 * t_early / n_run, 1e3 * c_late / n_run, 1e3 * c_rows / n_run, 1e3 * c_prove / n_run,
                      vpbs_host_blocking_sync());
     const long n_bytes = vpbs_step_proof_to_bytes(ctx, &in, cyc.n_const_cols, caps, openings, fri, proof_out, capacity);
     if (n_bytes <= 0) {
@@ -894,36 +931,32 @@ static long prove_pbs_device_witness(vpbs_ivc* v, const uint64_t* testv, const u
     }
     if (timing) {
         timing->seconds = seconds;
-        timing->steps = steps;
+        timing->steps = n_run;
         timing->base_proof_ms = 1e3 * t_base;
-        timing->late_witness_ms = 1e3 * t_late / steps;
-        timing->late_rows_upload_ms = 1e3 * t_rows / steps;
-        timing->prove_step_ms = 1e3 * t_prove / steps;
-        timing->early_witness_ms = 1e3 * t_early / steps;
-        timing->late_ahead_ms = 1e3 * ahead.busy_s / steps;
+        timing->late_witness_ms = 1e3 * t_late / n_run;
+        timing->late_rows_upload_ms = 1e3 * t_rows / n_run;
+        timing->prove_step_ms = 1e3 * t_prove / n_run;
+        timing->early_witness_ms = 1e3 * t_early / n_run;
+        timing->late_ahead_ms = 1e3 * ahead.busy_s / n_run;
     }
     return n_bytes;
 }
 
-long vpbs_ivc_prove_pbs(vpbs_ivc* v, const uint64_t* testv, const uint64_t* ct, const uint64_t* bsk, const uint64_t* ksk, unsigned n_lwe,
-                        unsigned steps, uint8_t* proof_out, size_t capacity, vpbs_ivc_timing* timing, char* err, size_t err_len) {
+// The host pipeline (the default): early phase on thread E, upload on thread U, late phase + proof on the caller.  from > 0
+// (vpbs_ivc_resume_pbs): no base proof; step `from` takes the checkpoint's proof words and public inputs.
+static long prove_pbs_host(vpbs_ivc* v, const uint64_t* testv, const uint64_t* ct, const uint64_t* bsk, const uint64_t* ksk, unsigned n_lwe,
+                           unsigned from, const u64* from_proof, const u64* from_pis, unsigned steps, uint8_t* proof_out, size_t capacity,
+                           vpbs_ivc_timing* timing, char* err, size_t err_len) {
     auto say = [&](const std::string& m) {
         if (err && err_len) {
             std::strncpy(err, m.c_str(), err_len - 1);
             err[err_len - 1] = 0;
         }
     };
-    say("");
-    if (!v || !testv || !ct || !ksk || (n_lwe && !bsk) || !proof_out) {
-        say("malformed arguments");
-        return VPBS_ERR_INVALID;
-    }
-    const unsigned total = n_lwe + 2;
-    if (steps == 0 || steps > total) steps = total;
-    if (v->dw_batch) return prove_pbs_device_witness(v, testv, ct, bsk, ksk, n_lwe, steps, proof_out, capacity, timing, err, err_len);
     Side &cyc = v->cyc, &dum = v->dum;
     vpbs_ctx* ctx = v->ctx;
     const size_t kn = v->kn, n_pi = v->n_pi, proof_words = v->proof_words, ggsw_len = v->ggsw_len;
+    const unsigned n_run = steps - from;
     const std::vector<u64> zero_ggsw(ggsw_len, 0);
     auto ggsw_of = [&](unsigned s) { return s == 0 ? zero_ggsw.data() : (s <= n_lwe ? bsk + (size_t)(s - 1) * ggsw_len : ksk); };
     auto mask_of = [&](unsigned s) { return s == 0 ? ct[n_lwe] : (s <= n_lwe ? ct[s - 1] : (u64)0); };
@@ -972,9 +1005,9 @@ long vpbs_ivc_prove_pbs(vpbs_ivc* v, const uint64_t* testv, const uint64_t* ct, 
     };
     std::thread early([&] {
         name_thread("vpbs-early");
-        std::vector<u64> pis_prev(base_pis);
+        std::vector<u64> pis_prev = from ? std::vector<u64>(from_pis, from_pis + n_pi) : base_pis;
         char e2[256];
-        for (unsigned s = 0; s < steps && !failed; ++s) {
+        for (unsigned s = from; s < steps && !failed; ++s) {
             int b;
             {
                 std::unique_lock<std::mutex> lk(mu);
@@ -1012,7 +1045,7 @@ long vpbs_ivc_prove_pbs(vpbs_ivc* v, const uint64_t* testv, const uint64_t* ct, 
     });
     std::thread uploader([&] {
         name_thread("vpbs-upload");
-        for (unsigned s = 0; s < steps; ++s) {
+        for (unsigned s = from; s < steps; ++s) {
             Ready r;
             {
                 std::unique_lock<std::mutex> lk(mu);
@@ -1050,16 +1083,22 @@ long vpbs_ivc_prove_pbs(vpbs_ivc* v, const uint64_t* testv, const uint64_t* ct, 
     char e[256] = {0};
     vpbs_step_inputs in;
     vpbs_step_sizes sz{};
-    if (vpbs_witness_plan_run(dum.plan, base_pis.data(), 0, v->base_wires, e, sizeof e) != 0) return stop(std::string("dummy witness: ") + e, VPBS_ERR_INVALID);
+    if (!from && vpbs_witness_plan_run(dum.plan, base_pis.data(), 0, v->base_wires, e, sizeof e) != 0)
+        return stop(std::string("dummy witness: ") + e, VPBS_ERR_INVALID);
     dum.step_inputs(in, v->base_wires, false, base_pis.data());
     if (vpbs_step_sizes_get(ctx, &in, &sz) != 0 || 3 * sz.cap_words + sz.openings_words + sz.fri_words != proof_words)
         return stop("the proof of this shape does not have the number of words the cyclic circuit expects", VPBS_ERR_INVALID);
     std::vector<u64> proof(proof_words), pis;
     u64 *caps = proof.data(), *openings = caps + 3 * sz.cap_words, *fri = openings + sz.openings_words;   // the flat order of the proof targets
-    int rc = dum.prove(in, caps, openings, fri);
-    if (rc != 0) return stop(std::string("base proof: ") + vpbs_last_error(ctx), rc);
-    const double t_base = now() - t0;
-    if (v->step_fn) v->step_fn(v->step_user, 0);
+    int rc = VPBS_OK;
+    if (from) {
+        std::copy(from_proof, from_proof + proof_words, proof.begin());   // the checkpoint's proof is the inner proof of step `from`
+    } else {
+        rc = dum.prove(in, caps, openings, fri);
+        if (rc != 0) return stop(std::string("base proof: ") + vpbs_last_error(ctx), rc);
+    }
+    const double t_base = from ? 0.0 : now() - t0;
+    if (v->step_fn && !from) v->step_fn(v->step_user, 0);
     double t_late = 0, t_rows = 0, t_prove = 0;
     // the next step's late stages 1 and 2 run on a worker while this step's FRI stage is on the device (LateAhead): the prover reports its
     // sections (on_section, on this thread); the first report that finds the next step's early phase finished and uploaded takes it
@@ -1099,7 +1138,7 @@ long vpbs_ivc_prove_pbs(vpbs_ivc* v, const uint64_t* testv, const uint64_t* ct, 
         cyc.step_inputs(shape, nullptr, true, nullptr);
         (void)vpbs_prove_step_sharded_fail(ctx, &shape, cyc.comm, why);
     };
-    for (unsigned s = 0; s < steps; ++s) {
+    for (unsigned s = from; s < steps; ++s) {
         Ready r;
         if (have_next) {
             r = std::move(next);
@@ -1161,6 +1200,7 @@ long vpbs_ivc_prove_pbs(vpbs_ivc* v, const uint64_t* testv, const uint64_t* ct, 
         }
         cv.notify_all();
         if (v->step_fn) v->step_fn(v->step_user, s + 1);
+        if (v->checkpoint(in, caps, openings, fri, s + 1, steps) != 0) return stop("checkpoint after step " + std::to_string(s) + ": the proof does not serialise", VPBS_ERR_INVALID);
     }
     early.join();
     uploader.join();
@@ -1172,14 +1212,143 @@ long vpbs_ivc_prove_pbs(vpbs_ivc* v, const uint64_t* testv, const uint64_t* ct, 
     }
     if (timing) {
         timing->seconds = seconds;
-        timing->steps = steps;
+        timing->steps = n_run;
         timing->base_proof_ms = 1e3 * t_base;
-        timing->late_witness_ms = 1e3 * t_late / steps;
-        timing->late_rows_upload_ms = 1e3 * t_rows / steps;
-        timing->prove_step_ms = 1e3 * t_prove / steps;
-        timing->early_witness_ms = 1e3 * t_early / steps;
-        timing->late_ahead_ms = 1e3 * ahead.busy_s / steps;
+        timing->late_witness_ms = 1e3 * t_late / n_run;
+        timing->late_rows_upload_ms = 1e3 * t_rows / n_run;
+        timing->prove_step_ms = 1e3 * t_prove / n_run;
+        timing->early_witness_ms = 1e3 * t_early / n_run;
+        timing->late_ahead_ms = 1e3 * ahead.busy_s / n_run;
     }
+    return n_bytes;
+}
+
+long vpbs_ivc_prove_pbs(vpbs_ivc* v, const uint64_t* testv, const uint64_t* ct, const uint64_t* bsk, const uint64_t* ksk, unsigned n_lwe,
+                        unsigned steps, uint8_t* proof_out, size_t capacity, vpbs_ivc_timing* timing, char* err, size_t err_len) {
+    if (err && err_len) err[0] = 0;
+    if (!v || !testv || !ct || !ksk || (n_lwe && !bsk) || !proof_out) {
+        if (err && err_len) std::snprintf(err, err_len, "%s", "malformed arguments");
+        return VPBS_ERR_INVALID;
+    }
+    const unsigned total = n_lwe + 2;
+    if (steps == 0 || steps > total) steps = total;
+    if (v->dw_batch) return prove_pbs_device_witness(v, testv, ct, bsk, ksk, n_lwe, 0, nullptr, nullptr, steps, proof_out, capacity, timing, err, err_len);
+    return prove_pbs_host(v, testv, ct, bsk, ksk, n_lwe, 0, nullptr, nullptr, steps, proof_out, capacity, timing, err, err_len);
+}
+
+int vpbs_ivc_set_checkpoint(vpbs_ivc* v, unsigned every, vpbs_ivc_checkpoint_fn fn, void* user) {
+    if (!v) return VPBS_ERR_INVALID;
+    v->ckpt_every = fn ? every : 0;
+    v->ckpt_fn = every ? fn : nullptr;
+    v->ckpt_user = user;
+    return VPBS_OK;
+}
+
+// Resume: the checkpoint is the last proof of a prefix of k steps, and its public inputs are the whole state step k reads.  The prefix form
+// of verify_pbs against this object's own verifier data establishes that state (by the proof's soundness its accumulator is the right one
+// once its hash chains are those of these keys and this ciphertext), so the chain goes on at step k with the checkpoint's proof words as
+// step k's inner proof -- the same witnesses, hence the same proofs, as an uninterrupted chain.  The key chain (seconds) runs on a thread of
+// its own beside the first resumed steps; everything else is checked before anything is queued.
+long vpbs_ivc_resume_pbs(vpbs_ivc* v, const uint64_t* testv, const uint64_t* ct, const uint64_t* bsk, const uint64_t* ksk, unsigned n_lwe,
+                         const uint8_t* checkpoint, size_t len, unsigned steps, uint8_t* proof_out, size_t capacity, vpbs_ivc_timing* timing,
+                         char* err, size_t err_len) {
+    auto say = [&](const std::string& m) {
+        if (err && err_len) {
+            std::strncpy(err, m.c_str(), err_len - 1);
+            err[err_len - 1] = 0;
+        }
+    };
+    say("");
+    if (!v || !testv || !ct || !ksk || (n_lwe && !bsk) || !proof_out || !checkpoint) {
+        say("malformed arguments");
+        return VPBS_ERR_INVALID;
+    }
+    if (v->cyc.comm) {
+        say("resume is not available for a sharded chain");
+        return VPBS_ERR_INVALID;
+    }
+    const Side& cyc = v->cyc;
+    const size_t kn = v->kn, n_pi = v->n_pi, cap_words = cyc.cs_cap.size();
+    vpbs_compat compat;
+    vpbs_ctx_get_compat(v->ctx, &compat);
+    vpbs_verify_inputs vi{};   // the cyclic circuit as this object committed it: its own verifier data
+    vi.log_n = cyc.log_n;
+    vi.rate_bits = vpbs_ctx_rate_bits(v->ctx);
+    vi.cap_height = vpbs_ctx_cap_height(v->ctx);
+    vi.n_constants_sigmas = cyc.n_const_cols + cyc.n_routed;
+    vi.n_wires = cyc.n_wires;
+    vi.n_zs_partial_products = 20;
+    vi.n_quotient = 16;
+    vi.num_challenges = 2;
+    vi.constants_sigmas_cap = cyc.cs_cap.data();
+    for (int i = 0; i < 4; ++i) vi.circuit_digest[i] = cyc.vk[i];
+    vi.n_constants = cyc.n_const_cols;
+    vi.n_routed = cyc.n_routed;
+    vi.quotient_degree_factor = 8;
+    vi.gates = cyc.gates.data();
+    vi.n_gates = (unsigned)cyc.gates.size();
+    vi.num_selectors = cyc.num_selectors;
+    vi.compat = &compat;
+    const vpbs_verify_pbs_inputs pin{&vi, v->N, v->K, n_lwe, v->ggsw_len, testv, nullptr, ct, bsk, ksk};
+    const double t0 = now();
+    unsigned k = 0;
+    char why[256] = {0};
+    const int ok = vpbs::verify_pbs_prefix_without_keys(&pin, checkpoint, len, &k, why, sizeof why);
+    if (ok != 1) {
+        say(std::string("checkpoint: ") + why);
+        return VPBS_ERR_INVALID;
+    }
+    const unsigned total = n_lwe + 2;
+    if (steps == 0 || steps > total) steps = total;
+    if (steps < k) {
+        say("checkpoint: its counter " + std::to_string(k) + " is beyond the requested " + std::to_string(steps) + " steps");
+        return VPBS_ERR_INVALID;
+    }
+    // the proof words in target order (caps, openings, FRI) and the public inputs
+    vpbs_step_inputs shape;
+    vpbs_step_sizes sz{};
+    cyc.step_inputs(shape, nullptr, true, nullptr);
+    if (vpbs_step_sizes_get(v->ctx, &shape, &sz) != 0 || sz.cap_words != cap_words || 3 * sz.cap_words + sz.openings_words + sz.fri_words != v->proof_words) {
+        say("checkpoint: the proof shape of this object is not the one its circuit expects");
+        return VPBS_ERR_INVALID;
+    }
+    std::vector<u64> words(v->proof_words), pis(n_pi);
+    u64 *caps = words.data(), *openings = caps + 3 * sz.cap_words, *fri = openings + sz.openings_words;
+    if (vpbs_step_proof_from_bytes(&vi, checkpoint, len, caps, openings, fri, pis.data(), n_pi) != (long)n_pi) {
+        say("checkpoint: the bytes are not a proof of this circuit (shape, canonical field elements, number of public inputs)");
+        return VPBS_ERR_INVALID;
+    }
+    const double t_checks = now() - t0;
+    // the key hash chain over the first k keys, beside the first resumed steps
+    double t_keys = 0;
+    bool keys_ok = false;
+    std::thread key_chain([&] {
+        name_thread("vpbs-resume-keys");
+        const double t = now();
+        keys_ok = vpbs::pbs_key_chain_prefix_matches(&pin, k, pis.data() + 2 * kn + 1);
+        t_keys = now() - t;
+    });
+    long n_bytes;
+    if (steps == k) {   // nothing to prove: the validated checkpoint itself
+        n_bytes = len <= capacity ? (long)len : VPBS_ERR_INVALID;
+        if (n_bytes > 0) std::memcpy(proof_out, checkpoint, len);
+        else say("the output buffer is too small for the proof");
+        if (timing) *timing = vpbs_ivc_timing{};
+    } else if (v->dw_batch) {
+        n_bytes = prove_pbs_device_witness(v, testv, ct, bsk, ksk, n_lwe, k, words.data(), pis.data(), steps, proof_out, capacity, timing, err, err_len);
+    } else {
+        n_bytes = prove_pbs_host(v, testv, ct, bsk, ksk, n_lwe, k, words.data(), pis.data(), steps, proof_out, capacity, timing, err, err_len);
+    }
+    key_chain.join();
+    if (std::getenv("VPBS_TRACE_IVC"))
+        std::fprintf(stderr, "[ivc resume] from step %u: parse + checks %.2f ms, key hash chain over %u keys %.3f s (beside the proof)\n", k, 1e3 * t_checks,
+                     k, t_keys);
+    if (!keys_ok) {   // the proof made from a checkpoint of other keys is discarded
+        if (n_bytes > 0) std::memset(proof_out, 0, (size_t)n_bytes);
+        say("checkpoint: the key hash chain does not match");
+        return VPBS_ERR_INVALID;
+    }
+    if (n_bytes > 0 && timing) timing->seconds = now() - t0;
     return n_bytes;
 }
 }  // extern "C"

@@ -443,7 +443,25 @@ extern "C" long vpbs_step_proof_from_bytes(const vpbs_verify_inputs* in, const u
 // vector, the step counter, the output ciphertext, cd.verify(proof) (vpbs_verify_step, full check), check_cyclic_proof_verifier_data (the
 // proof's last public inputs are the circuit's own digest and constants/sigmas cap), verify_hash_output over the bootstrapping / key
 // switching keys and over the LWE masks.  The reference panics at the first failing check; here the verdict is returned and `why` names it.
-extern "C" int vpbs_verify_pbs(const vpbs_verify_pbs_inputs* in, const uint8_t* proof_bytes, size_t len, char* why, size_t why_len) {
+// The prefix form (vpbs_verify_pbs_prefix, vpbs_ivc_resume_pbs) makes the same checks on the last proof of a chain of k = counter proofs: the
+// hash chains run over the first k items of ggsw_of / mask_of (csrc/ivc.hip), out_ct is optional, and the key chain may be left to the caller.
+namespace {
+enum class PbsForm { whole, prefix, prefix_without_keys };
+
+// key hash chain over ggsw_of(0 .. k-1) = [zeros, bsk_0 .. bsk_{k-2}] (+ ksk at k = n + 2), linked without materialising the items
+bool key_chain_matches(const vpbs_verify_pbs_inputs* in, unsigned k, const uint64_t* claimed) {
+    const size_t g = in->ggsw_len;
+    const std::vector<uint64_t> zero(g, 0);
+    std::vector<const uint64_t*> items(k);
+    for (unsigned s = 0; s < k; ++s) items[s] = s == 0 ? zero.data() : (s <= in->n_lwe ? in->bsk + (size_t)(s - 1) * g : in->ksk);
+    std::vector<uint64_t> links(4 * (size_t)k);
+    const uint64_t h0[4] = {0, 0, 0, 0};
+    if (vpbs_hash_chain_links(h0, items.data(), k, g, links.data()) != 0) return false;
+    return std::memcmp(links.data() + 4 * ((size_t)k - 1), claimed, 32) == 0;
+}
+
+int verify_pbs_form(const vpbs_verify_pbs_inputs* in, const uint8_t* proof_bytes, size_t len, PbsForm form, unsigned* steps_done, char* why,
+                    size_t why_len) {
     auto say = [&](const char* m) {
         if (why && why_len) {
             std::strncpy(why, m, why_len - 1);
@@ -451,11 +469,13 @@ extern "C" int vpbs_verify_pbs(const vpbs_verify_pbs_inputs* in, const uint8_t* 
         }
     };
     say("");
+    const bool whole = form == PbsForm::whole;
     // out_ct is part of the statement (the reference asserts it, :440-442): a verdict without it would not bind the proof to the ciphertext
     // the caller holds.  ggsw_len strides the caller's bsk / ksk arrays: it must be a whole number of [K][N] GLWE rows (K * ELL * K * N)
-    if (!in || !in->circuit || !proof_bytes || !in->testv || !in->out_ct || !in->ct || !in->ksk || (in->n_lwe && !in->bsk) || in->N == 0 ||
+    if (!in || !in->circuit || !proof_bytes || !in->testv || (whole && !in->out_ct) || !in->ct || !in->ksk || (in->n_lwe && !in->bsk) || in->N == 0 ||
         in->K == 0 || in->ggsw_len == 0 || in->ggsw_len % ((size_t)in->K * in->K * in->N) != 0) {
-        say("malformed arguments (testv, out_ct, ct, ksk, bsk are all required; ggsw_len = K * ELL * K * N)");
+        say(whole ? "malformed arguments (testv, out_ct, ct, ksk, bsk are all required; ggsw_len = K * ELL * K * N)"
+                  : "malformed arguments (testv, ct, ksk, bsk are all required; ggsw_len = K * ELL * K * N)");
         return VPBS_ERR_INVALID;
     }
     const vpbs_verify_inputs& c = *in->circuit;
@@ -477,11 +497,17 @@ extern "C" int vpbs_verify_pbs(const vpbs_verify_pbs_inputs* in, const uint8_t* 
         say("claimed test vector differs from testv");
         return 0;
     }
-    if (pis[kn] != (uint64_t)in->n_lwe + 2) {   // :435-438
+    const uint64_t total = (uint64_t)in->n_lwe + 2;
+    if (whole && pis[kn] != total) {   // :435-438
         say("the counter is not n + 2");
         return 0;
     }
-    if (std::memcmp(pis.data() + kn + 1, in->out_ct, 8 * kn) != 0) {   // :440-442
+    if (!whole && (pis[kn] == 0 || pis[kn] > total)) {
+        say("the counter is not in 1 .. n + 2");
+        return 0;
+    }
+    const unsigned k = (unsigned)pis[kn];
+    if (in->out_ct && std::memcmp(pis.data() + kn + 1, in->out_ct, 8 * kn) != 0) {   // :440-442
         say("the output ciphertext is not the proof's accumulator");
         return 0;
     }
@@ -504,23 +530,35 @@ extern "C" int vpbs_verify_pbs(const vpbs_verify_pbs_inputs* in, const uint8_t* 
         say("the proof carries another circuit's verifier data");
         return 0;
     }
-    // verify_hash_output (:454-481): dummy GGSW, the n bootstrapping keys, the key-switching key / ct[n], the n masks, zero
-    const size_t steps = (size_t)in->n_lwe + 2, g = in->ggsw_len;
-    {
-        std::vector<uint64_t> items(steps * g, 0);
-        if (in->n_lwe) std::memcpy(items.data() + g, in->bsk, 8 * (size_t)in->n_lwe * g);
-        std::memcpy(items.data() + (steps - 1) * g, in->ksk, 8 * g);
-        if (vpbs_hash_chain(items.data(), steps, g, pis.data() + 2 * kn + 1, nullptr) != 1) {
-            say("the key hash chain does not match");
-            return 0;
-        }
+    // verify_hash_output (:454-481): dummy GGSW, the n bootstrapping keys, the key-switching key / ct[n], the n masks, zero -- the first k of them
+    if (form != PbsForm::prefix_without_keys && !key_chain_matches(in, k, pis.data() + 2 * kn + 1)) {
+        say("the key hash chain does not match");
+        return 0;
     }
-    std::vector<uint64_t> masks(steps, 0);
-    masks[0] = in->ct[in->n_lwe];
-    for (unsigned i = 0; i < in->n_lwe; ++i) masks[i + 1] = in->ct[i];
-    if (vpbs_hash_chain(masks.data(), steps, 1, pis.data() + 2 * kn + 5, nullptr) != 1) {
+    std::vector<uint64_t> masks(k, 0);
+    for (unsigned s = 0; s < k; ++s) masks[s] = s == 0 ? in->ct[in->n_lwe] : (s <= in->n_lwe ? in->ct[s - 1] : 0);
+    if (vpbs_hash_chain(masks.data(), k, 1, pis.data() + 2 * kn + 5, nullptr) != 1) {
         say("the LWE hash chain does not match");
         return 0;
     }
+    if (steps_done) *steps_done = k;
     return 1;
+}
+}  // namespace
+
+namespace vpbs {
+// vpbs_ivc_resume_pbs's two halves of the prefix form: every check but the key hash chain (a few ms), and that chain alone (seconds)
+int verify_pbs_prefix_without_keys(const vpbs_verify_pbs_inputs* in, const uint8_t* bytes, size_t len, unsigned* steps_done, char* why, size_t why_len) {
+    return verify_pbs_form(in, bytes, len, PbsForm::prefix_without_keys, steps_done, why, why_len);
+}
+bool pbs_key_chain_prefix_matches(const vpbs_verify_pbs_inputs* in, unsigned k, const uint64_t claimed[4]) { return key_chain_matches(in, k, claimed); }
+}  // namespace vpbs
+
+extern "C" int vpbs_verify_pbs(const vpbs_verify_pbs_inputs* in, const uint8_t* proof_bytes, size_t len, char* why, size_t why_len) {
+    return verify_pbs_form(in, proof_bytes, len, PbsForm::whole, nullptr, why, why_len);
+}
+
+extern "C" int vpbs_verify_pbs_prefix(const vpbs_verify_pbs_inputs* in, const uint8_t* bytes, size_t len, unsigned* steps_done, char* why,
+                                      size_t why_len) {
+    return verify_pbs_form(in, bytes, len, PbsForm::prefix, steps_done, why, why_len);
 }
