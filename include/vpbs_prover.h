@@ -933,6 +933,37 @@ int vpbs_testv(unsigned log_N, unsigned p, uint64_t* testv, uint64_t* delta);
 /* Glwe::decrypt (crypto/glwe.rs:60-63): m = body - sum_j a_j s_j over X^N + 1; s: [K-1][N], ct: [K][N] coefficient domain, host arrays */
 int vpbs_glwe_decrypt(vpbs_ctx* ctx, unsigned log_N, unsigned K, const uint64_t* s, const uint64_t* ct, uint64_t* m_out);
 
+/* ---- bootstrapping batches of ciphertexts under one resident key set (csrc/pbs_batch.hip) ----
+ * vpbs_bootstrapper_run is vpbs_pbs_accumulator_chain with acc_init = (0, .., 0, testv) for `count` LWE ciphertexts in ONE launch -- one
+ * workgroup per ciphertext walks all n_lwe + 2 steps with the accumulator in LDS -- followed by Glwe::partial_sample_extract(n_lwe)
+ * (/root/reference/src/vtfhe/crypto/glwe.rs:96-113), which turns each output back into an LWE ciphertext under the input key, so that
+ * lwe_out can be the cts of a later run.  Word for word what the per-step path computes (tests/test_gpu_pbs_batch.py).
+ *   create: the keys (vpbs_keygen's layout) are uploaded once, or adopted when keys_on_device != 0 (device pointers that must outlive the
+ *           object, e.g. straight from vpbs_keygen(.., keys_on_device = 1)).  n_lwe <= (K - 1) N.  A workgroup holds accumulator [K][N] +
+ *           outputs [K][N] + limbs [ELL][N] in LDS: shapes above 160 KiB are refused with VPBS_ERR_INVALID and a message (err, and
+ *           vpbs_last_error) that names the budget; nothing is launched.
+ *   run:    cts [count][n_lwe + 1]; testv [N] shared or (testv_per_ct) [count][N]; any of out_ct [count][K][N], lwe_out
+ *           [count][n_lwe + 1], accs_out [count][n_lwe + 2][K][N] (every intermediate accumulator) may be NULL, not all three; host
+ *           pointers, or device pointers when on_device != 0.  Works on the context's stream and returns `count` when the outputs are
+ *           where the caller asked for them; VPBS_ERR_INVALID for count > max_batch, null cts / testv or no output; VPBS_ERR_DEVICE for a
+ *           failed launch.  One run at a time per object.
+ * Words are canonical field elements.  A word at or above p is NOT reduced first: it goes through the same operations as in
+ * vpbs_pbs_accumulator_chain (the mod switch reads the raw word; a coefficient c is negated as p - c in 64 bits), so the outputs equal that
+ * call's in that case too.
+ * vpbs_lwe_extract: partial_sample_extract(n_lwe) of existing GLWEs [count][K][N] -> [count][n_lwe + 1]: with
+ * full = [a_0[0], -a_0[N-1], .., -a_0[1], a_1[0], -a_1[N-1], ..] over the K - 1 mask polynomials, full[0 .. n_lwe) || body[0]
+ * (negation in the field: 0 stays 0); host or device pointers.
+ * vpbs_lwe_decrypt: lwe::decrypt (crypto/lwe.rs:62-69): body - <s, mask>, canonical; host. */
+typedef struct vpbs_bootstrapper vpbs_bootstrapper;
+int vpbs_bootstrapper_create(vpbs_ctx* ctx, const vpbs_tfhe_params* params, unsigned n_lwe, const uint64_t* bsk, const uint64_t* ksk,
+                             int keys_on_device, size_t max_batch, vpbs_bootstrapper** out, char* err, size_t err_len);
+long vpbs_bootstrapper_run(vpbs_bootstrapper* b, const uint64_t* cts, size_t count, const uint64_t* testv, int testv_per_ct,
+                           uint64_t* out_ct, uint64_t* lwe_out, uint64_t* accs_out, int on_device);
+void vpbs_bootstrapper_free(vpbs_bootstrapper* b);
+int vpbs_lwe_extract(vpbs_ctx* ctx, unsigned log_N, unsigned K, unsigned n_lwe, const uint64_t* glwe, size_t count, uint64_t* lwe_out,
+                     int on_device);
+int vpbs_lwe_decrypt(const uint64_t* s_lwe, const uint64_t* ct, unsigned n_lwe, uint64_t* m_out);
+
 /* ---- memory helpers for hosts that do not link the HIP runtime themselves (a Rust or plain C++ caller) ----
  * pinned host memory (hipHostMalloc): witness matrices written there reach the device at PCIe speed (70.8 MB in 1.3 ms instead of ~15 ms
  * from pageable memory); device buffers for per-circuit data that is uploaded once (the sigma values of vpbs_step_inputs.sigmas_values with

@@ -304,6 +304,11 @@ SIGNATURES = {
     "vpbs_lwe_encrypt": (_i, [C.POINTER(KeygenParamsC), U64P, _u64, _u64, U64P]),
     "vpbs_testv": (_i, [_ui, _ui, U64P, U64P]),
     "vpbs_glwe_decrypt": (_i, [_vp, _ui, _ui, U64P, U64P, U64P]),
+    "vpbs_bootstrapper_create": (_i, [_vp, C.POINTER(TfheParamsC), _ui, _vp, _vp, _i, _sz, C.POINTER(_vp), C.c_char_p, _sz]),
+    "vpbs_bootstrapper_run": (C.c_long, [_vp, _vp, _sz, _vp, _i, _vp, _vp, _vp, _i]),
+    "vpbs_bootstrapper_free": (None, [_vp]),
+    "vpbs_lwe_extract": (_i, [_vp, _ui, _ui, _ui, _vp, _sz, _vp, _i]),
+    "vpbs_lwe_decrypt": (_i, [U64P, U64P, _ui, U64P]),
     "vpbs_k_poseidon_batch": (_i, [_vp, U64P, _sz]),
     "vpbs_k_hash_rows": (_i, [_vp, U64P, _sz, _ui, U64P]),
     "vpbs_k_intt": (_i, [_vp, U64P, _ui, _ui, U64P]),
@@ -1289,6 +1294,83 @@ def testv(N, p=2):
     return t, int(d[0])
 
 
+def lwe_decrypt(s_lwe, ct):
+    """vpbs_lwe_decrypt (host): lwe::decrypt (crypto/lwe.rs:62-69) = body - <s, mask>; ct [n + 1] -> int, or [count][n + 1] -> [count]"""
+    s, c = _u64(s_lwe).reshape(-1), _u64(ct)
+    if c.shape[-1] != s.size + 1:
+        raise ValueError("lwe_decrypt: ct must be [.., n + 1] for a key of n words")
+    rows = c.reshape(-1, s.size + 1)
+    out = np.zeros(rows.shape[0], np.uint64)
+    for i in range(rows.shape[0]):
+        if lib().vpbs_lwe_decrypt(_ptr(s), _ptr(np.ascontiguousarray(rows[i])), s.size, _ptr(out[i:i + 1])) != 0:
+            raise VpbsError("vpbs_lwe_decrypt: bad arguments")
+    return int(out[0]) if c.ndim == 1 else out
+
+
+class Bootstrapper:
+    """vpbs_bootstrapper: the whole PBS (accumulator chain of verified_pbs + partial_sample_extract) for batches of LWE ciphertexts in one
+    launch, under a key set that stays on the device.  bsk [n][K*ELL*K*N], ksk [K*ELL*K*N] (keygen's layout): host arrays, or device
+    pointers (integers) with keys_on_device=True, N and n_lwe given -- they must stay allocated while the object lives."""
+
+    def __init__(self, ctx, bsk, ksk, K, ELL, LOGB, max_batch=64, N=None, n_lwe=None, keys_on_device=False):
+        if keys_on_device:
+            if N is None or n_lwe is None:
+                raise ValueError("Bootstrapper: device keys need N and n_lwe")
+            pb, pk = C.c_void_p(int(bsk)), C.c_void_p(int(ksk))
+        else:
+            b, k = _u64(bsk), _u64(ksk).reshape(-1)
+            n_lwe, N = b.shape[0], k.size // (K * ELL * K)
+            if b.shape != (n_lwe, K * ELL * K * N) or k.size != K * ELL * K * N:
+                raise ValueError("Bootstrapper: expected bsk [n][K*ELL*K*N] and ksk [K*ELL*K*N]")
+            pb, pk = C.c_void_p(b.ctypes.data), C.c_void_p(k.ctypes.data)
+        self.ctx, self.N, self.K, self.ELL, self.LOGB, self.n_lwe, self.max_batch = ctx, N, K, ELL, LOGB, n_lwe, max_batch
+        prm = TfheParamsC(N.bit_length() - 1, K, ELL, LOGB)
+        h, err = C.c_void_p(), C.create_string_buffer(512)
+        rc = lib().vpbs_bootstrapper_create(ctx.h, C.byref(prm), n_lwe, pb, pk, 1 if keys_on_device else 0, max_batch, C.byref(h), err, 512)
+        if rc:
+            raise VpbsError("vpbs_bootstrapper_create: status %d: %s" % (rc, err.value.decode()))
+        self.h = h
+        ctx._batches.add(self)   # must not outlive its context: Context.close() frees the survivors
+
+    def run(self, cts, testv, accumulators=False):
+        """cts [count][n + 1]; testv [N] shared or [count][N] -> (out_ct [count][K][N], lwe_out [count][n + 1]) and, with accumulators=True,
+        every intermediate accumulator [count][n + 2][K][N] (Context.pbs_accumulator_chain for each ciphertext)"""
+        c, tv = _u64(cts), _u64(testv)
+        if c.ndim != 2 or c.shape[1] != self.n_lwe + 1 or tv.shape not in ((self.N,), (c.shape[0], self.N)):
+            raise ValueError("Bootstrapper.run: expected cts [count][%d] and testv [%d] or [count][%d]" % (self.n_lwe + 1, self.N, self.N))
+        count = c.shape[0]
+        out_ct, lwe_out = np.zeros((count, self.K, self.N), np.uint64), np.zeros((count, self.n_lwe + 1), np.uint64)
+        accs = np.zeros((count, self.n_lwe + 2, self.K, self.N), np.uint64) if accumulators else None
+        keep = np.zeros(1, np.uint64)   # a valid pointer for an empty batch
+        p = lambda a: (a if a.size else keep).ctypes.data
+        rc = lib().vpbs_bootstrapper_run(self.h, p(c), count, p(tv), 1 if tv.ndim == 2 else 0, p(out_ct), p(lwe_out),
+                                         p(accs) if accumulators else None, 0)
+        if rc != count:
+            raise VpbsError("vpbs_bootstrapper_run: status %d: %s" % (rc, lib().vpbs_last_error(self.ctx.h).decode()))
+        return (out_ct, lwe_out, accs) if accumulators else (out_ct, lwe_out)
+
+    def run_device(self, d_cts, count, d_testv, testv_per_ct=False, d_out_ct=None, d_lwe_out=None, d_accs=None):
+        """the same on device pointers (integers; None = output not wanted); returns when the outputs are in place"""
+        q = lambda x: C.c_void_p(int(x)) if x else None
+        rc = lib().vpbs_bootstrapper_run(self.h, q(d_cts), count, q(d_testv), 1 if testv_per_ct else 0, q(d_out_ct), q(d_lwe_out), q(d_accs), 1)
+        if rc != count:
+            raise VpbsError("vpbs_bootstrapper_run: status %d: %s" % (rc, lib().vpbs_last_error(self.ctx.h).decode()))
+
+    def close(self):
+        if self.h:
+            lib().vpbs_bootstrapper_free(self.h)
+            self.h = None
+            self.ctx._batches.discard(self)
+
+    free = close
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def fri_params(degree_bits, **over):
     p = FriParams()
     lib().vpbs_fri_params_standard(degree_bits, C.byref(p))
@@ -1661,6 +1743,35 @@ class Context:
         self._check(lib().vpbs_keygen(self.h, C.byref(prm), _ptr(s_lwe), _ptr(s_glwe), _ptr(s_to), bsk.ctypes.data if want_bsk else None,
                                       ksk.ctypes.data if want_ksk else None, 0))
         return {"params": prm, "s_lwe": s_lwe, "s_glwe": s_glwe, "s_to": s_to, "bsk": bsk, "ksk": ksk}
+
+    def keygen_device(self, N, K, ELL, LOGB, n_lwe, seed, sigma_glwe=0.0, sigma_lwe=0.0):
+        """vpbs_keygen with keys_on_device = 1: the same keys, bsk / ksk left in device memory -> dict(params, s_lwe, s_glwe, s_to host
+        arrays; d_bsk, d_ksk device pointers for Bootstrapper(keys_on_device=True), to be released with device_free)"""
+        prm = KeygenParamsC(N.bit_length() - 1, K, ELL, LOGB, n_lwe, seed, sigma_glwe, sigma_lwe)
+        s_lwe, s_glwe, s_to = np.zeros(n_lwe, np.uint64), np.zeros((K - 1, N), np.uint64), np.zeros((K, N), np.uint64)
+        g = K * ELL * K * N
+        d_bsk, d_ksk = C.c_void_p(), C.c_void_p()
+        self._check(lib().vpbs_device_alloc(self.h, n_lwe * g, C.byref(d_bsk)))
+        self._check(lib().vpbs_device_alloc(self.h, g, C.byref(d_ksk)))
+        self._check(lib().vpbs_keygen(self.h, C.byref(prm), _ptr(s_lwe), _ptr(s_glwe), _ptr(s_to), d_bsk, d_ksk, 1))
+        return {"params": prm, "s_lwe": s_lwe, "s_glwe": s_glwe, "s_to": s_to, "d_bsk": d_bsk.value, "d_ksk": d_ksk.value}
+
+    def device_free(self, d_ptr):
+        lib().vpbs_device_free(self.h, C.c_void_p(int(d_ptr)))
+
+    def lwe_extract(self, glwe, n_lwe, count=None, N=None, K=None, out_dev_ptr=None):
+        """vpbs_lwe_extract: Glwe::partial_sample_extract(n_lwe) of GLWEs [count][K][N] (or one [K][N]) -> [count][n_lwe + 1] (or [n_lwe + 1]).
+        With out_dev_ptr, glwe is a device pointer too (count, N, K given) and nothing is returned."""
+        if out_dev_ptr is not None:
+            self._check(lib().vpbs_lwe_extract(self.h, N.bit_length() - 1, K, n_lwe, C.c_void_p(int(glwe)), count, C.c_void_p(int(out_dev_ptr)), 1))
+            return None
+        g = _u64(glwe)
+        one = g.ndim == 2
+        g3 = g.reshape((1,) + g.shape) if one else g
+        cnt, K_, N_ = g3.shape
+        out = np.zeros((cnt, n_lwe + 1), np.uint64)
+        self._check(lib().vpbs_lwe_extract(self.h, N_.bit_length() - 1, K_, n_lwe, g3.ctypes.data, cnt, out.ctypes.data, 0))
+        return out[0] if one else out
 
     def timing_shader_clock(self):
         """-> (MHz sustained under the leaf-hash kernel while timing was on, launches sampled)"""
