@@ -964,6 +964,52 @@ int vpbs_lwe_extract(vpbs_ctx* ctx, unsigned log_N, unsigned K, unsigned n_lwe, 
                      int on_device);
 int vpbs_lwe_decrypt(const uint64_t* s_lwe, const uint64_t* ct, unsigned n_lwe, uint64_t* m_out);
 
+/* ---- proving the bootstraps of a batch under one resident key set (csrc/pbs_prove_batch.hip) ----
+ * One object owns a key set in device memory and turns a batch of LWE ciphertexts into their bootstrapped outputs AND their vPBS proofs.
+ *   create: `chains` vpbs_ivc objects, each on a context of its own, in the device-witness pipeline with `witness_batch` steps per batch
+ *           (early phases on the device, late phase on the host), ONE vpbs_bootstrapper and ONE key set shared by all of them.  Host keys
+ *           are uploaded once; device keys (keys_on_device != 0) are adopted -- they must outlive the object -- and downloaded once for the
+ *           key hash chain over [0^ggsw_len, bsk_0 .. bsk_{n-1}, ksk], which is walked once, here, with every link kept.
+ *           VPBS_ERR_INVALID with a message, and nothing launched, for null arguments, chains = 0 (or above 64) and witness_batch = 0.
+ *   run:    cts [count][n_lwe + 1]; testv [N] shared or (testv_per_ct) [count][N]; out_ct [count][K][N] and lwe_out [count][n_lwe + 1] (either
+ *           may be NULL) are complete before the first proof is started: one Bootstrapper launch per 256 ciphertexts.  Then `chains` worker
+ *           threads take ciphertext indices from a queue: per ciphertext the Bootstrapper leaves the chain's accumulators on the device
+ *           (18 ms, against seconds of proving; device memory is bounded by the chains in flight, (n + 2) K N words each), and the chain
+ *           is proven with its preset matrices assembled on the device from the resident keys, those accumulators and the hash links.
+ *           proof_fn(user, index, bytes, len, NULL) is called once per finished proof, never two calls at once, in completion order; the
+ *           bytes (what vpbs_ivc_prove_pbs returns for that ciphertext, byte for byte) are valid during the call.  A chain that fails
+ *           reports proof_fn(user, index, NULL, 0, message); the other chains go on.  steps: 0 = n_lwe + 2, fewer = a prefix (tests).
+ *           Returns the number of proofs delivered, or VPBS_ERR_INVALID (null cts / testv with count > 0, no proof_fn, steps > n_lwe + 2;
+ *           nothing launched) or the Bootstrapper's status.  One run at a time per object (a second caller waits).
+ *   key_hash: the end of the key hash chain -- what vpbs_pbs_verifier_create wants (vpbs_pbs_key_hash, without walking the chain again).
+ *   set_check_witness / witness_checks: vpbs_ivc_set_check_witness on every chain; the counters summed over the chains.
+ *   set_checkpoint: vpbs_ivc_set_checkpoint on every chain; fn also gets the ciphertext index, and shares proof_fn's serialisation.
+ *   last_run: figures of the last run.  seconds: the whole call; outputs_seconds: from the call until out_ct / lwe_out were complete (0 when
+ *           neither was asked for); proofs: delivered; prepare_chain_ms: per delivered chain, what the chain waited for its public inputs
+ *           (its turn on the Bootstrapper, the launch, the copy of the accumulators to the host, the LWE hash chain); chain: the
+ *           vpbs_ivc_timing of the delivered chains, every field their mean (steps: of one chain). */
+typedef struct vpbs_pbs_prover vpbs_pbs_prover;
+typedef void (*vpbs_pbs_proof_fn)(void* user, size_t index, const uint8_t* bytes, size_t len, const char* error);
+typedef void (*vpbs_pbs_checkpoint_fn)(void* user, size_t index, unsigned done, const uint8_t* bytes, size_t len);
+typedef struct {
+    double seconds, outputs_seconds;
+    size_t proofs;
+    double prepare_chain_ms;
+    vpbs_ivc_timing chain;
+} vpbs_pbs_run_stats;
+int vpbs_pbs_prover_create(int device_ordinal, const vpbs_ivc_circuit* cyclic, const vpbs_ivc_circuit* dummy, const vpbs_tfhe_params* params,
+                           unsigned n_lwe, const uint64_t* bsk, const uint64_t* ksk, int keys_on_device, unsigned chains, unsigned witness_batch,
+                           vpbs_pbs_prover** out, char* err, size_t err_len);
+long vpbs_pbs_prover_run(vpbs_pbs_prover* p, const uint64_t* cts, size_t count, const uint64_t* testv, int testv_per_ct, unsigned steps,
+                         uint64_t* out_ct, uint64_t* lwe_out, vpbs_pbs_proof_fn proof_fn, void* user, char* err, size_t err_len);
+int vpbs_pbs_prover_key_hash(const vpbs_pbs_prover* p, uint64_t out[4]);
+int vpbs_pbs_prover_verifier_data(const vpbs_pbs_prover* p, uint64_t* cyclic_vk, uint64_t* dummy_vk);
+int vpbs_pbs_prover_set_check_witness(vpbs_pbs_prover* p, int on);
+int vpbs_pbs_prover_witness_checks(const vpbs_pbs_prover* p, uint64_t out[2]);
+int vpbs_pbs_prover_set_checkpoint(vpbs_pbs_prover* p, unsigned every, vpbs_pbs_checkpoint_fn fn, void* user);
+int vpbs_pbs_prover_last_run(const vpbs_pbs_prover* p, vpbs_pbs_run_stats* out);
+void vpbs_pbs_prover_free(vpbs_pbs_prover* p);
+
 /* ---- memory helpers for hosts that do not link the HIP runtime themselves (a Rust or plain C++ caller) ----
  * pinned host memory (hipHostMalloc): witness matrices written there reach the device at PCIe speed (70.8 MB in 1.3 ms instead of ~15 ms
  * from pageable memory); device buffers for per-circuit data that is uploaded once (the sigma values of vpbs_step_inputs.sigmas_values with

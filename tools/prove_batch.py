@@ -1,0 +1,201 @@
+#!/usr/bin/env python3
+"""A batch of verifiable bootstraps under one key set: seeded keys, M seeded ciphertexts, ONE api.PbsProver.prove (the outputs of all of
+them from the Bootstrapper, then their IVC chains on C worker threads with the chains' public inputs produced once, on the device), then
+ALL proofs through api.PbsVerifier built from the prover's key_hash() and all lwe_out decrypted (api.lwe_decrypt, rounded as the
+reference's main.rs:59-64).  One JSON line.
+
+usage: tools/prove_batch.py [--count M] [--chains C] [--witness-batch B] [--steps K] [--n2048 | --n8] [--keys-on-device] [--baseline]
+  --steps K < n + 2 proves a prefix of every chain (tests); the proofs are then checked by api.verify_pbs_prefix on the host (verify_pbs
+    insists on counter = n + 2); the outputs are those of the whole bootstrap either way.
+  --n8: the N = 8, n = 6 miniature (degree 2^13); --n2048: N = 2048 (degree 2^17); default: the paper's N = 1024, n = 728 (degree 2^16).
+  --keys-on-device: the keys are generated into device memory and never exist on the host (not with --baseline, whose entry points want
+    host arrays).
+  --baseline: the same batch the way it was done before PbsProver existed, using only api of that time -- C threads, each with its own
+    Context + Ivc.set_device_witness(ELL, LOGB, B) + Ivc.prove_pbs on host keys, outputs from each chain's proof -- so that this file can be
+    copied into a build of an older commit and run there."""
+import argparse
+import json
+import os
+import resource
+import sys
+import threading
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tools")]
+import numpy as np  # noqa: E402
+import torch  # noqa: E402,F401  (the HIP runtime the library shares with it)
+
+import vpbs_amd  # noqa: E402
+from vpbs_amd import api, circuit_file  # noqa: E402
+
+K, ELL, LOGB = 2, 4, 5
+P = api.P
+SIGMA_GLWE, SIGMA_LWE = 4.99027217501041e-8, 1.17021618159313e-5
+SEED = 0x5EED0728
+
+
+def rounded(m, delta, p=2):
+    """main.rs:59-64: round(m_bar / delta) mod 2 p"""
+    return int(round(int(m) / delta)) % (2 * p)
+
+
+def cpu_seconds():
+    r = resource.getrusage(resource.RUSAGE_SELF)
+    return r.ru_utime + r.ru_stime
+
+
+def prove_new(args, N, n_lwe, cyc, dum, ctx, keys, cts, testv):
+    """-> (proofs, out_ct, lwe_out, key_hash, verifier data, seconds, seconds until out_ct was complete, extra); called inside the CPU clock"""
+    t_make = time.perf_counter()
+    if args.keys_on_device:
+        prover = api.PbsProver(0, cyc, dum, keys["d_bsk"], keys["d_ksk"], K, ELL, LOGB, chains=args.chains, witness_batch=args.witness_batch,
+                               keys_on_device=True, N=N, n_lwe=n_lwe)
+    else:
+        prover = api.PbsProver(0, cyc, dum, keys["bsk"], keys["ksk"], K, ELL, LOGB, chains=args.chains, witness_batch=args.witness_batch)
+    t_make = time.perf_counter() - t_make
+    first = []
+    t0, c0 = time.perf_counter(), cpu_seconds()
+    proofs, out_ct, lwe_out = prover.prove(cts, testv, steps=args.steps, on_proof=lambda i, b: first.append(time.perf_counter() - t0))
+    seconds, cpu = time.perf_counter() - t0, cpu_seconds() - c0
+    kh, (vk, _) = prover.key_hash(), prover.verifier_data()
+    run = prover.last_run()   # the library's own clock: when out_ct / lwe_out were complete, the chains' vpbs_ivc_timing
+    prover.close()
+    return proofs, out_ct, lwe_out, kh, vk, seconds, run["outputs_seconds"], {
+        "cpu_seconds_proving": cpu, "prover_create_s": t_make, "first_proof_after_s": min(first) if first else None, "prepare_chain_ms": run["prepare_chain_ms"],
+        "chain_timing_mean": run["chain"], "early_witness_ms_per_step": run["chain"]["early_witness_ms"]}
+
+
+def prove_baseline(args, N, n_lwe, log_n, cyc_path, dum_path, keys, cts, testv):
+    """the parent's way: C threads, each with a Context and an Ivc of its own on HOST keys; a chain's output is its proof's accumulator"""
+    kn = K * N
+    todo, lock = list(range(len(cts))), threading.Lock()
+    proofs, out_ct, done_at, errors, timings = [None] * len(cts), np.zeros((len(cts), K, N), np.uint64), [0.0] * len(cts), [], []
+    chains = []
+    for _ in range(args.chains):
+        c = vpbs_amd.Context(0, log_n_max=max(16, log_n))
+        if args.chains > 1 and "VPBS_WIDE_THRESHOLD" not in os.environ:
+            c.set_option("wide_threshold", 2048)
+        ivc = api.Ivc(c, circuit_file.load(cyc_path), circuit_file.load(dum_path), N, K, K * ELL * K * N)
+        if args.witness_batch:
+            ivc.set_device_witness(ELL, LOGB, args.witness_batch)
+        chains.append((c, ivc))
+    start = threading.Barrier(args.chains + 1)
+
+    def work(ci):
+        c, ivc = chains[ci]
+        try:
+            start.wait()
+            while True:
+                with lock:
+                    if not todo:
+                        return
+                    i = todo.pop(0)
+                blob, t = ivc.prove_pbs(testv, cts[i], keys["bsk"], keys["ksk"], args.steps)
+                timings.append(t)
+                proofs[i] = blob
+                done_at[i] = time.perf_counter()
+        except BaseException as e:   # noqa: BLE001
+            errors.append(e)
+    threads = [threading.Thread(target=work, args=(ci,)) for ci in range(args.chains)]
+    for th in threads:
+        th.start()
+    start.wait()
+    t0, c0 = time.perf_counter(), cpu_seconds()
+    for th in threads:
+        th.join()
+    seconds, cpu = time.perf_counter() - t0, cpu_seconds() - c0
+    if errors:
+        raise errors[0]
+    vk, _ = chains[0][1].verifier_data()
+    cyc = circuit_file.load(cyc_path)
+    ncols = [cyc.n_constants + 80, 135, 20, 16]
+    whole = args.steps in (0, n_lwe + 2)
+    for i, blob in enumerate(proofs):   # the only place the parent's batch gets its outputs from: the last proof's accumulator
+        if whole:
+            out_ct[i] = api.step_proof_from_bytes(blob, ncols, log_n, cyc.n_constants)[1][kn + 1:2 * kn + 1].reshape(K, N)
+    lwe_out = chains[0][0].lwe_extract(out_ct, n_lwe) if whole else None
+    t_key = time.perf_counter()
+    kh = api.pbs_key_hash(keys["bsk"], keys["ksk"])
+    t_key = time.perf_counter() - t_key
+    for c, ivc in chains:
+        ivc.free()
+        c.close()
+    mean = {f: sum(t[f] for t in timings) / len(timings) for f in timings[0]}
+    return proofs, out_ct, lwe_out, kh, vk, seconds, max(done_at) - t0, {"cpu_seconds_proving": cpu, "key_hash_on_the_host_s": t_key, "chain_timing_mean": mean,
+                                                                        "early_witness_ms_per_step": mean["early_witness_ms"]}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--count", type=int, default=16)
+    ap.add_argument("--chains", type=int, default=8)
+    ap.add_argument("--witness-batch", type=int, default=64)
+    ap.add_argument("--steps", type=int, default=0)
+    ap.add_argument("--n2048", action="store_true")
+    ap.add_argument("--n8", action="store_true")
+    ap.add_argument("--keys-on-device", action="store_true")
+    ap.add_argument("--baseline", action="store_true")
+    args = ap.parse_args()
+    if args.baseline and args.keys_on_device:
+        raise SystemExit("--baseline proves under host keys: it cannot run with --keys-on-device")
+    N, n_lwe, log_n = (8, 6, 13) if args.n8 else ((2048, 728, 17) if args.n2048 else (1024, 728, 16))
+    total = n_lwe + 2
+    if args.steps < 0 or args.steps > total:
+        raise SystemExit("--steps must be 0 .. %d" % total)
+    whole = args.steps in (0, total)
+    api.host_set_late_threads(api.late_threads_for(args.chains, api.host_cpu_budget()))
+    api.host_set_early_threads(api.early_threads_for(args.chains))
+    cyc_path, dum_path = circuit_file.find_cyclic_circuit(N, K, ELL, LOGB, n_lwe, log_n)
+    cyc, dum = circuit_file.load(cyc_path), circuit_file.load(dum_path)
+    ctx = vpbs_amd.Context(0, log_n_max=max(16, log_n))
+    keygen = ctx.keygen_device if args.keys_on_device else ctx.keygen
+    keys = keygen(N, K, ELL, LOGB, n_lwe, SEED, SIGMA_GLWE, SIGMA_LWE)
+    testv, delta = api.testv(N, 2)
+    msgs = [(3 * i + i // 2) % 2 for i in range(args.count)]
+    cts = np.stack([api.lwe_encrypt(keys["params"], keys["s_lwe"], delta * m % P, nonce=i) for i, m in enumerate(msgs)])
+    load0, cpu0 = os.getloadavg()[0], cpu_seconds()
+    if args.baseline:
+        proofs, out_ct, lwe_out, kh, vk, seconds, t_out, extra = prove_baseline(args, N, n_lwe, log_n, cyc_path, dum_path, keys, cts, testv)
+    else:
+        proofs, out_ct, lwe_out, kh, vk, seconds, t_out, extra = prove_new(args, N, n_lwe, cyc, dum, ctx, keys, cts, testv)
+    cpu = cpu_seconds() - cpu0
+    # ---- after the clock: every proof verified, every output decrypted ----
+    ncols = [cyc.n_constants + 80, 135, 20, 16]
+    cap = vk[4:].reshape(-1, 4)
+    t = time.perf_counter()
+    if whole:
+        pv = api.PbsVerifier(ctx, cap, ncols, vk[:4], log_n, cyc.n_constants, 80, cyc.gates, N, K, n_lwe, K * ELL * K * N, kh,
+                             max_batch=args.count)
+        verdicts, reasons, _ = pv.verify(proofs, testv, cts, out_ct.reshape(args.count, -1))
+        pv.close()
+        accepted = int(verdicts.sum())
+        why = sorted({api.pbs_reason_text(int(r)) for v, r in zip(verdicts, reasons) if not v})
+    else:   # prefixes: the host's prefix form, which wants host keys
+        hk = keys if not args.keys_on_device else ctx.keygen(N, K, ELL, LOGB, n_lwe, SEED, SIGMA_GLWE, SIGMA_LWE)
+        res = [api.verify_pbs_prefix(b, cap, ncols, vk[:4], log_n, cyc.n_constants, 80, cyc.gates, N, K, testv, cts[i], hk["bsk"], hk["ksk"])
+               for i, b in enumerate(proofs)]
+        accepted = sum(1 for r in res if r[0] and r[1] == args.steps)
+        why = sorted({str(r[-1]) for r in res if not r[0]})
+    t_verify = time.perf_counter() - t
+    decrypted = None
+    if lwe_out is not None:
+        decrypted = sum(1 for m, want in zip(api.lwe_decrypt(keys["s_lwe"], lwe_out), msgs) if rounded(m, delta) == want)
+    if args.keys_on_device:
+        ctx.device_free(keys["d_bsk"])
+        ctx.device_free(keys["d_ksk"])
+    ctx.close()
+    print(json.dumps(dict({
+        "what": "%d verifiable bootstraps under one key set at N=%d, n=%d (degree 2^%d), %s" % (
+            args.count, N, n_lwe, log_n, "the parent's way: one Ivc per thread on host keys" if args.baseline else "one PbsProver.prove"),
+        "count": args.count, "chains": args.chains, "witness_batch": args.witness_batch, "steps": args.steps or total,
+        "keys_on_device": args.keys_on_device, "baseline": args.baseline, "seconds": seconds,
+        "proofs_per_s": args.count / seconds if whole else None, "ms_per_step": 1e3 * seconds * args.chains / (args.count * (args.steps or total)),
+        "seconds_until_out_ct_complete": t_out, "accepted": accepted, "rejected_because": why, "decrypted_correct": decrypted,
+        "cpu_seconds_setup_and_proving": cpu, "cpu_seconds_per_proof": extra["cpu_seconds_proving"] / args.count, "verify_s": t_verify,
+        "host": {"cpus": len(os.sched_getaffinity(0)), "loadavg_before": load0, "loadavg_after": os.getloadavg()[0]}}, **extra)))
+    return 0 if accepted == args.count and (decrypted in (None, args.count)) else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())

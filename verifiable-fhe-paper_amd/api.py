@@ -134,6 +134,11 @@ class IvcTimingC(C.Structure):
                 ("late_ahead_ms", C.c_double)]
 
 
+class PbsRunStatsC(C.Structure):
+    _fields_ = [("seconds", C.c_double), ("outputs_seconds", C.c_double), ("proofs", C.c_size_t), ("prepare_chain_ms", C.c_double),
+                ("chain", IvcTimingC)]
+
+
 class TfheParamsC(C.Structure):
     _fields_ = [("log_N", C.c_uint), ("K", C.c_uint), ("ELL", C.c_uint), ("LOGB", C.c_uint)]
 
@@ -152,6 +157,8 @@ ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, U64P, C.c_size_t)
 ALLGATHER_DEV_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t)
 IVC_STEP_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_uint)
 IVC_CHECKPOINT_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_uint, C.POINTER(C.c_uint8), C.c_size_t)
+PBS_PROOF_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint8), C.c_size_t, C.c_char_p)
+PBS_CHECKPOINT_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_size_t, C.c_uint, C.POINTER(C.c_uint8), C.c_size_t)
 
 
 class CommC(C.Structure):
@@ -307,6 +314,16 @@ SIGNATURES = {
     "vpbs_bootstrapper_create": (_i, [_vp, C.POINTER(TfheParamsC), _ui, _vp, _vp, _i, _sz, C.POINTER(_vp), C.c_char_p, _sz]),
     "vpbs_bootstrapper_run": (C.c_long, [_vp, _vp, _sz, _vp, _i, _vp, _vp, _vp, _i]),
     "vpbs_bootstrapper_free": (None, [_vp]),
+    "vpbs_pbs_prover_create": (_i, [_i, C.POINTER(IvcCircuitC), C.POINTER(IvcCircuitC), C.POINTER(TfheParamsC), _ui, _vp, _vp, _i, _ui, _ui,
+                                    C.POINTER(_vp), C.c_char_p, _sz]),
+    "vpbs_pbs_prover_run": (C.c_long, [_vp, U64P, _sz, U64P, _i, _ui, U64P, U64P, PBS_PROOF_FN, _vp, C.c_char_p, _sz]),
+    "vpbs_pbs_prover_key_hash": (_i, [_vp, U64P]),
+    "vpbs_pbs_prover_verifier_data": (_i, [_vp, U64P, U64P]),
+    "vpbs_pbs_prover_set_check_witness": (_i, [_vp, _i]),
+    "vpbs_pbs_prover_witness_checks": (_i, [_vp, U64P]),
+    "vpbs_pbs_prover_set_checkpoint": (_i, [_vp, _ui, PBS_CHECKPOINT_FN, _vp]),
+    "vpbs_pbs_prover_last_run": (_i, [_vp, C.POINTER(PbsRunStatsC)]),
+    "vpbs_pbs_prover_free": (None, [_vp]),
     "vpbs_lwe_extract": (_i, [_vp, _ui, _ui, _ui, _vp, _sz, _vp, _i]),
     "vpbs_lwe_decrypt": (_i, [U64P, U64P, _ui, U64P]),
     "vpbs_k_poseidon_batch": (_i, [_vp, U64P, _sz]),
@@ -319,6 +336,14 @@ SIGNATURES = {
     "vpbs_timing_enable": (_i, [_vp, _i]),
     "vpbs_timing_report": (_i, [_vp, C.c_char_p, _sz]),
     "vpbs_timing_shader_clock": (_i, [_vp, C.POINTER(C.c_double), C.POINTER(_ui)]),
+}
+
+# test entries (csrc/test_entries.h): exported for the suite, not part of the C ABI
+INTERNAL_SIGNATURES = {
+    "vpbs_test_ivc_preset_matrix": (_i, [_sz, _sz, _sz, _sz, _ui, _ui, _ui, U64P, U64P, U64P, U64P, U64P, U64P, U64P, U64P]),
+    "vpbs_test_pbs_prover_preset_matrix": (_i, [_vp, U64P, U64P, _ui, _ui, U64P]),
+    "vpbs_test_pbs_prover_preset_words": (_sz, [_vp]),
+    "vpbs_test_pbs_prover_dummy_proof": (_i, [_vp, U64P]),
 }
 
 _lib = None
@@ -349,7 +374,7 @@ def lib():
             except Exception:
                 pass
         L = C.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in list(SIGNATURES.items()) + list(INTERNAL_SIGNATURES.items()):
             fn = getattr(L, name)
             fn.restype, fn.argtypes = res, args
         _lib = L
@@ -1361,6 +1386,193 @@ class Bootstrapper:
             lib().vpbs_bootstrapper_free(self.h)
             self.h = None
             self.ctx._batches.discard(self)
+
+    free = close
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def ivc_preset_matrix_for_tests(proof_words, n_lwe, first, pis, ct, bsk, ksk, cyclic_vk, dummy_vk, dummy_proof):
+    """vpbs_test_ivc_preset_matrix (host, a test entry): the early-phase preset matrix [n_preset][count] of chain steps [first, first + count) as the
+    device-witness pipeline's host loop builds it.  pis [count][n_pi]: the public inputs of the predecessors of those steps."""
+    q, c, ks = _u64(pis), _u64(ct).reshape(-1), _u64(ksk).reshape(-1)
+    bs = _u64(bsk).reshape(-1) if n_lwe else None
+    cv, dv, dp = _u64(cyclic_vk).reshape(-1), _u64(dummy_vk).reshape(-1), _u64(dummy_proof).reshape(-1)
+    count, n_pi = q.shape
+    out = np.zeros((2 * (proof_words + n_pi) + 1 + ks.size + 1 + 2 * cv.size, count), np.uint64)
+    rc = lib().vpbs_test_ivc_preset_matrix(proof_words, n_pi, ks.size, cv.size, n_lwe, first, count, _ptr(q), _ptr(c), _ptr(bs) if bs is not None else None,
+                                      _ptr(ks), _ptr(cv), _ptr(dv), _ptr(dp), _ptr(out))
+    if rc != 0:
+        raise VpbsError("vpbs_test_ivc_preset_matrix: status %d" % rc)
+    return out
+
+
+class PbsProveError(VpbsError):
+    """PbsProver.prove: some chains failed.  failures {index: message}; proofs (None at those indices), out_ct, lwe_out: what the others gave"""
+
+    def __init__(self, failures, proofs, out_ct, lwe_out):
+        super().__init__("vpbs_pbs_prover_run: " + "; ".join("ciphertext %d: %s" % f for f in sorted(failures.items())))
+        self.failures, self.proofs, self.out_ct, self.lwe_out = failures, proofs, out_ct, lwe_out
+
+
+class PbsProver:
+    """vpbs_pbs_prover: the bootstraps of a batch of LWE ciphertexts AND their vPBS proofs under one key set that stays on the device.
+    cyclic / dummy: circuit_file.CircuitDescription of the exported cyclic step circuit and its dummy circuit.  bsk [n][K*ELL*K*N], ksk
+    [K*ELL*K*N] (keygen's layout): host arrays, or device pointers (integers) with keys_on_device=True and n_lwe given -- they must stay
+    allocated while the object lives.  `chains` IVC chains run side by side, each in the device-witness pipeline with `witness_batch` steps
+    per batch."""
+
+    def __init__(self, device, cyclic, dummy, bsk, ksk, K, ELL, LOGB, chains=8, witness_batch=64, keys_on_device=False, N=None, n_lwe=None):
+        ggsw_words = lambda N: K * ELL * K * N
+        if keys_on_device:
+            if N is None or n_lwe is None:
+                raise ValueError("PbsProver: device keys need N and n_lwe")
+            pb, pk = C.c_void_p(int(bsk)), C.c_void_p(int(ksk))
+        else:
+            b, k = _u64(bsk), _u64(ksk).reshape(-1)
+            n_lwe, N = b.shape[0], k.size // (K * ELL * K)
+            if b.shape != (n_lwe, ggsw_words(N)) or k.size != ggsw_words(N):
+                raise ValueError("PbsProver: expected bsk [n][K*ELL*K*N] and ksk [K*ELL*K*N]")
+            pb, pk = C.c_void_p(b.ctypes.data), C.c_void_p(k.ctypes.data)
+        self.N, self.K, self.ELL, self.LOGB, self.n_lwe, self.chains = N, K, ELL, LOGB, n_lwe, chains
+        keep = []
+
+        def side(d, proof_words):
+            c = IvcCircuitC()
+            pre = np.ascontiguousarray(d.preset_flat, dtype=np.uint32)
+            pi = np.ascontiguousarray(d.pi_flat, dtype=np.uint32)
+            keep.extend([pre, pi, d])
+            c.circuit = C.pointer(d.circuit.c)
+            c.preset_pos, c.n_preset = pre.ctypes.data_as(U32P), pre.size
+            c.pi_pos, c.n_pi = pi.ctypes.data_as(U32P), pi.size
+            c.proof_words = proof_words
+            return c
+        cy, du = side(cyclic, cyclic.meta["proof_words"]), side(dummy, 0)
+        prm = TfheParamsC(N.bit_length() - 1, K, ELL, LOGB)
+        self.h, err = C.c_void_p(), C.create_string_buffer(512)
+        rc = lib().vpbs_pbs_prover_create(device, C.byref(cy), C.byref(du), C.byref(prm), n_lwe, pb, pk, 1 if keys_on_device else 0, chains,
+                                          witness_batch, C.byref(self.h), err, 512)
+        if rc:
+            self.h = None
+            raise VpbsError("vpbs_pbs_prover_create: status %d: %s" % (rc, err.value.decode()))
+        self.vk_words = 4 + (4 << 4)
+        self._proof_words = cyclic.meta["proof_words"]
+        self._ckpt_cb = self._ckpt_error = None
+
+    def key_hash(self):
+        """the end of the key hash chain walked at creation: what PbsVerifier takes (= pbs_key_hash(bsk, ksk))"""
+        out = np.zeros(4, np.uint64)
+        lib().vpbs_pbs_prover_key_hash(self.h, _ptr(out))
+        return out
+
+    def verifier_data(self):
+        """-> (cyclic circuit: digest [4] + cap, dummy circuit: the same)"""
+        a, b = np.zeros(self.vk_words, np.uint64), np.zeros(self.vk_words, np.uint64)
+        lib().vpbs_pbs_prover_verifier_data(self.h, _ptr(a), _ptr(b))
+        return a, b
+
+    def set_check_witness(self, on=True):
+        """every witness of later chains checked on the device before it is proven (Ivc.set_check_witness on every chain); resets the counters"""
+        rc = lib().vpbs_pbs_prover_set_check_witness(self.h, 1 if on else 0)
+        if rc != 0:
+            raise VpbsError("vpbs_pbs_prover_set_check_witness: status %d" % rc)
+
+    def witness_checks(self):
+        """-> (witnesses checked, violations found), summed over the chains, since the last set_check_witness"""
+        out = np.zeros(2, np.uint64)
+        lib().vpbs_pbs_prover_witness_checks(self.h, _ptr(out))
+        return int(out[0]), int(out[1])
+
+    def on_checkpoint(self, every, fn):
+        """fn(index, done, bytes) after every chained step `done` of ciphertext `index` that is a multiple of `every` and below the chain's
+        last step (Ivc.on_checkpoint with the ciphertext index); never two calls at once.  every = 0 or fn = None turns it off.  An
+        exception raised by fn is kept and re-raised by prove."""
+        self._ckpt_error = None
+        if fn is None or not every:
+            self._ckpt_cb = None
+            lib().vpbs_pbs_prover_set_checkpoint(self.h, 0, C.cast(None, PBS_CHECKPOINT_FN), None)
+            return
+
+        def trampoline(_user, index, done, data, n):
+            try:
+                if self._ckpt_error is None:
+                    fn(int(index), int(done), C.string_at(data, n))
+            except BaseException as e:   # noqa: BLE001 -- must not unwind through the C frames
+                self._ckpt_error = e
+        self._ckpt_cb = PBS_CHECKPOINT_FN(trampoline)
+        lib().vpbs_pbs_prover_set_checkpoint(self.h, every, self._ckpt_cb, None)
+
+    def prove(self, cts, testv, steps=0, on_proof=None):
+        """cts [count][n + 1]; testv [N] shared or [count][N] -> (proofs: list of bytes in the order of cts, out_ct [count][K][N], lwe_out
+        [count][n + 1]).  on_proof(index, bytes) is called as each proof completes (completion order, never two calls at once); an exception
+        it raises is re-raised here after the run has drained.  A chain that fails does not stop the others: after the run PbsProveError is
+        raised, naming the failed indices, with .failures {index: message} and .proofs (None at the failed indices), .out_ct, .lwe_out --
+        everything the chains that succeeded delivered."""
+        c, tv = _u64(cts), _u64(testv)
+        if c.ndim != 2 or c.shape[1] != self.n_lwe + 1 or tv.shape not in ((self.N,), (c.shape[0], self.N)):
+            raise ValueError("PbsProver.prove: expected cts [count][%d] and testv [%d] or [count][%d]" % (self.n_lwe + 1, self.N, self.N))
+        count = c.shape[0]
+        out_ct, lwe_out = np.zeros((count, self.K, self.N), np.uint64), np.zeros((count, self.n_lwe + 1), np.uint64)
+        proofs, failures, raised = [None] * count, [], []
+
+        def trampoline(_user, index, data, n, error):
+            try:
+                if not data:
+                    failures.append((int(index), (error or b"").decode()))
+                    return
+                proofs[index] = C.string_at(data, n)
+                if on_proof is not None and not raised:
+                    on_proof(int(index), proofs[index])
+            except BaseException as e:   # noqa: BLE001 -- must not unwind through the C frames
+                raised.append(e)
+        cb, err = PBS_PROOF_FN(trampoline), C.create_string_buffer(512)
+        keep = np.zeros(1, np.uint64)   # a valid pointer for an empty batch
+        p = lambda a: _ptr(a if a.size else keep)
+        n = lib().vpbs_pbs_prover_run(self.h, p(c), count, p(tv), 1 if tv.ndim == 2 else 0, steps, p(out_ct), p(lwe_out), cb, None, err, 512)
+        if raised:
+            raise raised[0]
+        e, self._ckpt_error = self._ckpt_error, None
+        if e is not None:
+            raise e
+        if n < 0:
+            raise VpbsError("vpbs_pbs_prover_run: status %d: %s" % (n, err.value.decode()))
+        if failures:
+            raise PbsProveError(dict(failures), proofs, out_ct, lwe_out)
+        return proofs, out_ct, lwe_out
+
+    def last_run(self):
+        """vpbs_pbs_prover_last_run -> dict: seconds, outputs_seconds (call until out_ct / lwe_out were complete), proofs, prepare_chain_ms
+        (per chain: waiting for its public inputs) and chain = the mean vpbs_ivc_timing of the delivered chains"""
+        st = PbsRunStatsC()
+        lib().vpbs_pbs_prover_last_run(self.h, C.byref(st))
+        return {"seconds": st.seconds, "outputs_seconds": st.outputs_seconds, "proofs": st.proofs, "prepare_chain_ms": st.prepare_chain_ms,
+                "chain": {f: getattr(st.chain, f) for f, _ in IvcTimingC._fields_}}
+
+    def dummy_proof_for_tests(self):
+        """vpbs_test_pbs_prover_dummy_proof: the dummy proof [proof_words] as the object's vpbs_ivc holds it on the host"""
+        out = np.zeros(self._proof_words, np.uint64)
+        if lib().vpbs_test_pbs_prover_dummy_proof(self.h, _ptr(out)) != 0:
+            raise VpbsError("vpbs_test_pbs_prover_dummy_proof failed")
+        return out
+
+    def preset_matrix(self, ct, testv, first, count):
+        """vpbs_test_pbs_prover_preset_matrix (a test entry): the early-phase preset matrix [n_preset][count] of steps [first, first + count) of the chain of
+        `ct`, assembled on the device by the kernels the chains use"""
+        c, tv = _u64(ct).reshape(-1), _u64(testv).reshape(-1)
+        out = np.zeros((lib().vpbs_test_pbs_prover_preset_words(self.h), count), np.uint64)
+        rc = lib().vpbs_test_pbs_prover_preset_matrix(self.h, _ptr(c), _ptr(tv), first, count, _ptr(out))
+        if rc != 0:
+            raise VpbsError("vpbs_test_pbs_prover_preset_matrix: status %d" % rc)
+        return out
+
+    def close(self):
+        if self.h:
+            lib().vpbs_pbs_prover_free(self.h)
+            self.h = None
 
     free = close
 

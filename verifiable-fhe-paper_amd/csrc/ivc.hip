@@ -27,6 +27,8 @@
 #include <vector>
 
 #include "../../include/vpbs_prover.h"
+#include "ivc_resident.h"
+#include "test_entries.h"
 
 // The one thing this driver takes from the library beside the public header: vpbs_device_scatter's copy + kernel QUEUED on the context's
 // stream without the wait (api.hip).  A host that writes its own loop over the C ABI calls vpbs_device_scatter and pays the wait.
@@ -539,6 +541,32 @@ int vpbs_ivc_set_device_witness(vpbs_ivc* v, unsigned ELL, unsigned LOGB, unsign
     return VPBS_OK;
 }
 
+// The early-phase preset matrix [n_preset][cnt] (instances innermost: what vpbs_witness_device_run takes) of chain steps
+// [first, first + cnt): previous proof (late: ignored by the early phase, zeros) | the predecessor's public inputs | condition | GGSW | mask |
+// own and dummy verifier data | the dummy proof | its public inputs (zeros).  pis: [cnt][n_pi], the public inputs of the predecessors of
+// those steps.  The host statement of the layout (tests reach it through vpbs_test_ivc_preset_matrix); csrc/pbs_prove_batch.hip assembles the same
+// matrix on the device.
+static void preset_matrix_host(u64* m, unsigned first, unsigned cnt, const u64* pis, size_t proof_words, size_t n_pi, size_t ggsw_len, unsigned n_lwe,
+                               const u64* ct, const u64* bsk, const u64* ksk, const u64* cyc_vk, const u64* dum_vk, size_t vk_words,
+                               const u64* dummy_proof) {
+    auto row = [&](size_t r) { return m + r * cnt; };
+    for (size_t r = 0; r < proof_words; ++r) std::memset(row(r), 0, 8 * cnt);
+    for (unsigned i = 0; i < cnt; ++i) {
+        const unsigned s = first + i;
+        const u64* q = pis + (size_t)i * n_pi;
+        size_t r = proof_words;
+        for (size_t k = 0; k < n_pi; ++k) row(r++)[i] = q[k];
+        row(r++)[i] = s == 0 ? 0 : 1;
+        const u64* g = s == 0 ? nullptr : (s <= n_lwe ? bsk + (size_t)(s - 1) * ggsw_len : ksk);
+        for (size_t k = 0; k < ggsw_len; ++k) row(r++)[i] = g ? g[k] : 0;
+        row(r++)[i] = s == 0 ? ct[n_lwe] : (s <= n_lwe ? ct[s - 1] : (u64)0);
+        for (size_t k = 0; k < vk_words; ++k) row(r++)[i] = cyc_vk[k];
+        for (size_t k = 0; k < vk_words; ++k) row(r++)[i] = dum_vk[k];
+        for (size_t k = 0; k < proof_words; ++k) row(r++)[i] = dummy_proof[k];
+        for (size_t k = 0; k < n_pi; ++k) row(r++)[i] = 0;
+    }
+}
+
 // The chain with the early witness phases on the device.  What a step's early phase needs of its predecessor are the predecessor's PUBLIC
 // INPUTS, and those are known without proving anything: the accumulators from the native chain (vpbs_pbs_accumulator_chain), the two chain
 // hashes from the native sponge (one host thread walks them ahead of the batches), counter and verifier data.  So the early phases of
@@ -548,9 +576,11 @@ int vpbs_ivc_set_device_witness(vpbs_ivc* v, unsigned ELL, unsigned LOGB, unsign
 // from > 0 (vpbs_ivc_resume_pbs): no base proof; step `from` takes the checkpoint's proof words and public inputs, the native accumulator
 // chain starts at step `from` from the checkpoint's accumulator and the hash thread from its two hashes.  Progress below is counted in steps
 // of THIS call: local step j is chain step from + j.
+// res != nullptr (vpbs::ivc_prove_pbs_resident, from = 0, bsk and ksk not read): the chain's public inputs exist already -- accumulators and
+// both hash chains are taken from `res`, and every batch's preset matrix is written on the device by res->fill.
 static long prove_pbs_device_witness(vpbs_ivc* v, const uint64_t* testv, const uint64_t* ct, const uint64_t* bsk, const uint64_t* ksk, unsigned n_lwe,
                                      unsigned from, const u64* from_proof, const u64* from_pis, unsigned steps, uint8_t* proof_out, size_t capacity,
-                                     vpbs_ivc_timing* timing, char* err, size_t err_len) {
+                                     vpbs_ivc_timing* timing, char* err, size_t err_len, const vpbs::IvcResidentChain* res = nullptr) {
     auto say = [&](const std::string& m) {
         if (err && err_len) {
             std::strncpy(err, m.c_str(), err_len - 1);
@@ -567,15 +597,16 @@ static long prove_pbs_device_witness(vpbs_ivc* v, const uint64_t* testv, const u
     const double t0 = now();
     // ---- the chain's public inputs, natively ----
     // accs[j] = the accumulator after chain step from + j (step `from` reads acc_init, or the checkpoint's accumulator)
-    std::vector<u64> acc_init(kn, 0), accs((size_t)(total - from) * kn);
+    std::vector<u64> acc_init(kn, 0), own_accs(res ? 0 : (size_t)(total - from) * kn);
     std::memcpy(acc_init.data() + kn - v->N, testv, 8 * (size_t)v->N);
     unsigned log_N = 0;
     while ((1u << log_N) < v->N) ++log_N;
     const vpbs_tfhe_params tp{log_N, v->K, v->ELL, v->LOGB};
-    if (vpbs::pbs_accumulator_chain_from(ctx, &tp, n_lwe, from, from ? from_pis + kn + 1 : acc_init.data(), ct, bsk, ksk, accs.data()) != 0) {
+    if (!res && vpbs::pbs_accumulator_chain_from(ctx, &tp, n_lwe, from, from ? from_pis + kn + 1 : acc_init.data(), ct, bsk, ksk, own_accs.data()) != 0) {
         say(std::string("native accumulator chain: ") + vpbs_last_error(ctx));
         return VPBS_ERR_INVALID;
     }
+    const u64* accs = res ? res->accs : own_accs.data();
     // pis[j + 1] = public inputs of step from + j (pis[0]: of the base proof, or the checkpoint's): acc_init | counter | accumulator | key
     // hash | LWE hash | verifier data
     std::vector<u64> pis((size_t)(n_run + 1) * n_pi, 0);
@@ -587,7 +618,7 @@ static long prove_pbs_device_witness(vpbs_ivc* v, const uint64_t* testv, const u
         }
         std::memcpy(q, acc_init.data(), 8 * kn);
         q[kn] = from + j;
-        if (j) std::memcpy(q + kn + 1, accs.data() + (size_t)(j - 1) * kn, 8 * kn);
+        if (j) std::memcpy(q + kn + 1, accs + (size_t)(j - 1) * kn, 8 * kn);
         std::memcpy(q + n_pi - cyc.vk.size(), cyc.vk.data(), 8 * cyc.vk.size());
     }
     std::mutex mu;
@@ -610,6 +641,19 @@ static long prove_pbs_device_witness(vpbs_ivc* v, const uint64_t* testv, const u
     // thread H: the two hash chains of verify_hash_output (:64-78), h_s = hash_no_pad(h_{s-1} || item_s), one permutation after the other
     std::thread hasher([&] {
         name_thread("vpbs-hash");
+        if (res) {   // both chains exist: nothing to wait for, nothing to hash
+            for (unsigned s = 0; s < n_run; ++s) {
+                u64* q = pis.data() + (size_t)(s + 1) * n_pi + 2 * kn + 1;
+                std::memcpy(q, res->key_links + 4 * (size_t)s, 32);
+                std::memcpy(q + 4, res->lwe_links + 4 * (size_t)s, 32);
+            }
+            {
+                std::lock_guard<std::mutex> lk(mu);
+                hashed = n_run;
+            }
+            cv.notify_all();
+            return;
+        }
         std::vector<u64> in2(5);
         u64 hb[4], hl[4];   // the chains so far: zero before the base proof, the checkpoint's hashes on a resume
         std::memcpy(hb, pis.data() + 2 * kn + 1, 32);
@@ -658,24 +702,24 @@ static long prove_pbs_device_witness(vpbs_ivc* v, const uint64_t* testv, const u
                 if (failed) return;
             }
             const double t = now();
-            u64* m = v->dw_presets;   // [n_preset][cnt]: previous proof (late: ignored) | its public inputs | condition | GGSW | mask | vks | dummy proof | its pis
-            auto row = [&](size_t r) { return m + r * cnt; };
-            for (size_t r = 0; r < proof_words; ++r) std::memset(row(r), 0, 8 * cnt);
-            for (unsigned i = 0; i < cnt; ++i) {
-                const unsigned s = from + first + i;
-                const u64* q = pis.data() + (size_t)(first + i) * n_pi;
-                size_t r = proof_words;
-                for (size_t k = 0; k < n_pi; ++k) row(r++)[i] = q[k];
-                row(r++)[i] = s == 0 ? 0 : 1;
-                const u64* g = ggsw_of(s);
-                for (size_t k = 0; k < ggsw_len; ++k) row(r++)[i] = g[k];
-                row(r++)[i] = mask_of(s);
-                for (u64 x : cyc.vk) row(r++)[i] = x;
-                for (u64 x : dum.vk) row(r++)[i] = x;
-                for (u64 x : v->dummy_proof) row(r++)[i] = x;
-                for (size_t k = 0; k < n_pi; ++k) row(r++)[i] = 0;
+            int run_rc;
+            if (res) {   // the matrix is assembled on the device, on the witness object's stream
+                struct Fill {
+                    const vpbs::IvcResidentChain* res;
+                    unsigned first, cnt;
+                    static int call(void* user, void* stream, uint64_t* d_matrix) {
+                        auto* f = static_cast<Fill*>(user);
+                        return f->res->fill(f->res->user, stream, f->first, f->cnt, d_matrix);
+                    }
+                } fill{res, first, cnt};
+                run_rc = vpbs::witness_device_run_filled(v->wdev[b & 1], cnt, &Fill::call, &fill);
+            } else {
+                u64* m = v->dw_presets;   // [n_preset][cnt]
+                preset_matrix_host(m, from + first, cnt, pis.data() + (size_t)first * n_pi, proof_words, n_pi, ggsw_len, n_lwe, ct, bsk, ksk,
+                                   cyc.vk.data(), dum.vk.data(), cyc.vk.size(), v->dummy_proof.data());
+                run_rc = vpbs_witness_device_run(v->wdev[b & 1], m, cnt);
             }
-            if (vpbs_witness_device_run(v->wdev[b & 1], m, cnt) != 0)
+            if (run_rc != 0)
                 return fail("early witness phases of steps " + std::to_string(from + first) + ".. on the device: " + vpbs_last_error(v->wctx[b & 1]));
             t_early += now() - t;
             {
@@ -1236,6 +1280,16 @@ long vpbs_ivc_prove_pbs(vpbs_ivc* v, const uint64_t* testv, const uint64_t* ct, 
     return prove_pbs_host(v, testv, ct, bsk, ksk, n_lwe, 0, nullptr, nullptr, steps, proof_out, capacity, timing, err, err_len);
 }
 
+int vpbs_test_ivc_preset_matrix(size_t proof_words, size_t n_pi, size_t ggsw_len, size_t vk_words, unsigned n_lwe, unsigned first, unsigned count,
+                                const uint64_t* pis, const uint64_t* ct, const uint64_t* bsk, const uint64_t* ksk, const uint64_t* cyclic_vk,
+                                const uint64_t* dummy_vk, const uint64_t* dummy_proof, uint64_t* out) {
+    if (!pis || !ct || !ksk || (n_lwe && !bsk) || !cyclic_vk || !dummy_vk || !dummy_proof || !out || count == 0 || first + count > n_lwe + 2 ||
+        first + count < first)
+        return VPBS_ERR_INVALID;
+    preset_matrix_host(out, first, count, pis, proof_words, n_pi, ggsw_len, n_lwe, ct, bsk, ksk, cyclic_vk, dummy_vk, vk_words, dummy_proof);
+    return VPBS_OK;
+}
+
 int vpbs_ivc_set_checkpoint(vpbs_ivc* v, unsigned every, vpbs_ivc_checkpoint_fn fn, void* user) {
     if (!v) return VPBS_ERR_INVALID;
     v->ckpt_every = fn ? every : 0;
@@ -1352,3 +1406,22 @@ long vpbs_ivc_resume_pbs(vpbs_ivc* v, const uint64_t* testv, const uint64_t* ct,
     return n_bytes;
 }
 }  // extern "C"
+
+namespace vpbs {
+void ivc_shape(const vpbs_ivc* v, IvcShape* out) {
+    *out = IvcShape{v->N, v->K, v->cyc.log_n, v->kn, v->n_pi, v->cyc.n_preset, v->proof_words, v->ggsw_len, v->cyc.vk.size(),
+                    v->cyc.vk.data(), v->dum.vk.data(), v->dummy_proof.data(), v->ctx};
+}
+long ivc_prove_pbs_resident(vpbs_ivc* v, const uint64_t* testv, const uint64_t* ct, unsigned n_lwe, const IvcResidentChain* chain, unsigned steps,
+                            uint8_t* proof_out, size_t capacity, vpbs_ivc_timing* timing, char* err, size_t err_len) {
+    if (err && err_len) err[0] = 0;
+    if (!v || !testv || !ct || !chain || !chain->accs || !chain->key_links || !chain->lwe_links || !chain->fill || !proof_out || !v->dw_batch ||
+        v->dw_late || v->cyc.comm) {
+        if (err && err_len) std::snprintf(err, err_len, "%s", "malformed arguments (a resident chain needs the device-witness pipeline with the late phase on the host)");
+        return VPBS_ERR_INVALID;
+    }
+    const unsigned total = n_lwe + 2;
+    if (steps == 0 || steps > total) steps = total;
+    return prove_pbs_device_witness(v, testv, ct, nullptr, nullptr, n_lwe, 0, nullptr, nullptr, steps, proof_out, capacity, timing, err, err_len, chain);
+}
+}  // namespace vpbs

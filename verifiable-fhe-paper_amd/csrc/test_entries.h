@@ -1,0 +1,21 @@
+// Entries that exist for the test suite only: exported from the library, bound by api.py (INTERNAL_SIGNATURES), but NOT part of the C ABI
+// of include/vpbs_prover.h and not in the Rust binding -- they may change or go without notice.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+
+#include "../../include/vpbs_prover.h"
+
+extern "C" {
+// The early-phase preset matrix of the device-witness pipeline as its host loop builds it (ivc.hip: preset_matrix_host): out
+// [n_preset][count] (instances innermost, what vpbs_witness_device_run takes) for chain steps [first, first + count); pis [count][n_pi]: the
+// public inputs of the PREDECESSORS of those steps.  Host only.  VPBS_ERR_INVALID for null pointers, count = 0 or first + count > n_lwe + 2.
+int vpbs_test_ivc_preset_matrix(size_t proof_words, size_t n_pi, size_t ggsw_len, size_t vk_words, unsigned n_lwe, unsigned first, unsigned count,
+                                const uint64_t* pis, const uint64_t* ct, const uint64_t* bsk, const uint64_t* ksk, const uint64_t* cyclic_vk,
+                                const uint64_t* dummy_vk, const uint64_t* dummy_proof, uint64_t* out);
+// The same matrix for the chain of one ciphertext, assembled on the device by the kernels of pbs_prove_batch.hip and copied to the host;
+// preset_words: n_preset; dummy_proof: the [proof_words] dummy proof the object's vpbs_ivc holds on the host (the yardstick's constant).
+int vpbs_test_pbs_prover_preset_matrix(vpbs_pbs_prover* p, const uint64_t* ct, const uint64_t* testv, unsigned first, unsigned count, uint64_t* out);
+size_t vpbs_test_pbs_prover_preset_words(const vpbs_pbs_prover* p);
+int vpbs_test_pbs_prover_dummy_proof(const vpbs_pbs_prover* p, uint64_t* out);
+}

@@ -571,15 +571,22 @@ void throw_on_flags(const vpbs_witness_device* d, const unsigned report[2]) {
     throw DeviceError{VPBS_ERR_INVALID, "device witness generation: " + m.substr(0, m.size() - 2)};
 }
 // presets -> (captured) level launches -> error flags, on the context's stream; returns after the stream has drained
+// (fill != nullptr: the preset matrix is written on the device by what fill queues on the stream, instead of coming from preset_val)
 void run_schedule(vpbs_witness_device* d, const Plan::DeviceSchedule& ds, const DevSched& k, hipGraphExec_t& graph, unsigned& graph_key, unsigned key,
-                  Launch L, const u64* preset_val, u64*& d_vals, bool walk = false) {
+                  Launch L, const u64* preset_val, u64*& d_vals, bool walk = false,
+                  int (*fill)(void* user, void* stream, uint64_t* d_matrix) = nullptr, void* fill_user = nullptr) {
     vpbs_ctx* ctx = d->ctx;
     hipStream_t s = ctx->stream;
     const size_t n_preset = d->plan->preset_slot.size();
     VPBS_HIP(hipMemsetAsync(d->err, 0, 4 * sizeof(unsigned), s));   // flags, first conflicting slot + 1, the walk's barrier counter, spare
     if (n_preset) {
         d_vals = ctx->alloc_words(n_preset * L.n);
-        VPBS_HIP(hipMemcpyAsync(d_vals, preset_val, sizeof(u64) * n_preset * L.n, hipMemcpyHostToDevice, s));
+        if (fill) {
+            const int rc = fill(fill_user, s, d_vals);
+            if (rc != VPBS_OK) throw DeviceError{rc, "device witness generation: the preset matrix could not be assembled on the device"};
+        } else {
+            VPBS_HIP(hipMemcpyAsync(d_vals, preset_val, sizeof(u64) * n_preset * L.n, hipMemcpyHostToDevice, s));
+        }
         for (u32 pass = 0; pass < (k.preset_compares ? 2u : 1u); ++pass)
             hipLaunchKernelGGL(wd_preset_kernel, dim3((unsigned)((n_preset * L.n + WT - 1) / WT)), dim3(WT), 0, s, d->val, d->err, k.preset_slot, d_vals,
                                (u32)n_preset, L, pass);
@@ -623,8 +630,7 @@ void run_schedule(vpbs_witness_device* d, const Plan::DeviceSchedule& ds, const 
 }  // namespace vpbs
 }  // extern "C++"
 
-int vpbs_witness_device_run(vpbs_witness_device* d, const uint64_t* preset_val, unsigned batch) {
-    if (!d || batch == 0 || batch > d->max_batch || (!d->plan->preset_slot.empty() && !preset_val)) return VPBS_ERR_INVALID;
+static int device_run(vpbs_witness_device* d, const uint64_t* preset_val, unsigned batch, int (*fill)(void*, void*, uint64_t*), void* fill_user) {
     vpbs_ctx* ctx = d->ctx;
     std::lock_guard<std::mutex> lock(d->mu);
     vpbs::u64* d_vals = nullptr;
@@ -635,7 +641,8 @@ int vpbs_witness_device_run(vpbs_witness_device* d, const uint64_t* preset_val, 
         d->one_instance = -1;
         std::fill(d->stages_queued.begin(), d->stages_queued.end(), 0u);   // a new batch: no instance has late stages in flight (a chain that gave up may have left some)
         VPBS_HIP(hipMemsetAsync(d->val, 0, sizeof(u64) * (d->plan->n_slots + 1) * batch, ctx->stream));
-        run_schedule(d, *d->ds, d->k, d->graph, d->graph_batch, batch, Launch{batch, batch, nullptr}, preset_val, d_vals);
+        run_schedule(d, *d->ds, d->k, d->graph, d->graph_batch, batch, Launch{batch, batch, nullptr}, preset_val, d_vals, false, fill,
+                     fill_user);
         return VPBS_OK;
     } catch (const vpbs::DeviceError& e) {
         if (d_vals) {
@@ -647,6 +654,11 @@ int vpbs_witness_device_run(vpbs_witness_device* d, const uint64_t* preset_val, 
     }
 }
 
+int vpbs_witness_device_run(vpbs_witness_device* d, const uint64_t* preset_val, unsigned batch) {
+    if (!d || batch == 0 || batch > d->max_batch || (!d->plan->preset_slot.empty() && !preset_val)) return VPBS_ERR_INVALID;
+    return device_run(d, preset_val, batch, nullptr, nullptr);
+}
+
 int vpbs_witness_device_has_late(const vpbs_witness_device* d) { return d && d->has_late ? 1 : 0; }
 
 }  // extern "C"
@@ -656,6 +668,11 @@ int vpbs_witness_device_has_late(const vpbs_witness_device* d) { return d && d->
 // the object's stream, and with wait = 0 the call returns at once (~20 us of enqueues).  Stages must be queued in order; the call for the LAST
 // stage (or any call with wait != 0) waits for everything queued and reports what the generators found.
 namespace vpbs {
+// vpbs_witness_device_run with the preset matrix assembled on the device (ivc_resident.h)
+int witness_device_run_filled(vpbs_witness_device* d, unsigned batch, int (*fill)(void* user, void* stream, uint64_t* d_matrix), void* user) {
+    if (!d || !fill || batch == 0 || batch > d->max_batch || d->plan->preset_slot.empty()) return VPBS_ERR_INVALID;
+    return device_run(d, nullptr, batch, fill, user);
+}
 unsigned witness_device_late_stages(const vpbs_witness_device* d) { return d && d->has_late ? (unsigned)d->k_stage.size() : 0; }
 int witness_device_run_late_stage(vpbs_witness_device* d, unsigned instance, unsigned stage, const uint64_t* preset_val, int wait) {
     if (!d || !d->has_late || d->k_stage.empty() || !preset_val || stage < 1 || stage > d->k_stage.size()) return VPBS_ERR_INVALID;
