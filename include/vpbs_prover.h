@@ -1010,6 +1010,63 @@ int vpbs_pbs_prover_set_checkpoint(vpbs_pbs_prover* p, unsigned every, vpbs_pbs_
 int vpbs_pbs_prover_last_run(const vpbs_pbs_prover* p, vpbs_pbs_run_stats* out);
 void vpbs_pbs_prover_free(vpbs_pbs_prover* p);
 
+/* ---- programs of lookup gates on resident keys (csrc/program.hip) ----
+ * A program is a netlist of bootstraps.  Wire w < n_inputs is program input w; wire n_inputs + g is the output of gate g; every wire is an
+ * LWE ciphertext of n_lwe + 1 words under the input key.  The input ciphertext of gate g is
+ *     c_g = gate_const[g] * (0, .., 0, 1) + sum over t in [gate_first[g], gate_first[g + 1]) of term_coef[t] * wire[term_src[t]]
+ * word by word in the Goldilocks field, canonical on output, the constant added to the body only; the gate's output wire is lwe_out of the
+ * bootstrap of c_g with test vector testvs[gate_lut[g]] -- exactly what vpbs_bootstrapper_run computes for that ciphertext and test vector.
+ * A gate with no terms is legal: its input is the trivial ciphertext of gate_const[g].  Unlike the Bootstrapper, which passes a word at or
+ * above p through unreduced (above), the combination REDUCES every wire word it reads: an input ciphertext with a word w >= p enters a
+ * gate as w - p, and wires_out shows program inputs as they were given.
+ * Levels: inputs are level 0, a gate is 1 + the highest level among its sources, a gate without terms is level 1.
+ *   create: validates and levelises the description (host arrays, not read after the call) and, with a context, uploads it once in two
+ *           orders: the caller's (for verify) and permuted so that the gates of one level are contiguous (for run); all indices the caller
+ *           sees stay in its own gate order.  An invalid description gives no object, launches nothing and returns VPBS_ERR_INVALID with
+ *           a message that names the gate: a term_src of gate g that is not below n_inputs + g (topological order), gate_lut >= n_luts,
+ *           term_coef or gate_const >= p, gate_first not monotone from 0 to n_terms.  ctx may be NULL: the object is then host-only --
+ *           validated and levelised for vpbs_program_levels; run, prove and verify refuse it.
+ *   levels: levels_out [n_gates] (may be NULL) in the caller's gate order; returns the number of levels (0 for a program without gates).
+ *   run:    inputs [n_inputs][n_lwe + 1], testvs [n_luts][N]; outputs wires_out [n_inputs + n_gates][n_lwe + 1], gate_cts_out
+ *           [n_gates][n_lwe + 1] (the c_g), out_cts [n_gates][K][N] (the output GLWEs), any of them NULL; host pointers, or device pointers
+ *           with on_device != 0.  The inputs are uploaded once; per level, and per chunk of the Bootstrapper's max_batch gates within a
+ *           level, the combine kernel, a gather of the chunk's test vectors and the Bootstrapper's kernel are queued on the Bootstrapper's
+ *           context's stream, lwe_out landing in the level's rows of the device wire table: no wire, gate input or output GLWE visits the
+ *           host between levels, levels are ordered by the stream alone, and the host waits once, at the end.  Returns the number of
+ *           levels, VPBS_ERR_INVALID (null or host-only program, null inputs / testvs with something to read, a Bootstrapper on another
+ *           device) or VPBS_ERR_DEVICE / VPBS_ERR_OOM; the object stays usable after a refusal.  One run at a time per Bootstrapper.
+ *   prove:  evaluates as run does, with the prover's own Bootstrapper and resident keys, then hands every c_g with testvs[gate_lut[g]] to
+ *           vpbs_pbs_prover_run: proof g is byte for byte what that call makes of (c_g, testvs[gate_lut[g]]) and reaches proof_fn with the
+ *           caller's gate index; failure semantics (a failing chain reports its index, the others go on) and `steps` are that call's.  Host
+ *           pointers; wires_out and out_cts may be NULL.  Returns the number of proofs delivered or a negative status.
+ *   verify: takes the CLAIMED output GLWEs of all gates (out_cts [n_gates][K][N]) and the proofs (bytes, offsets [n_gates + 1], gate order).
+ *           The wire table is rebuilt as inputs followed by the extraction (partial_sample_extract) of every claimed output, the inputs of
+ *           ALL gates are combined in one launch -- verification has no level order -- and vpbs_pbs_verifier_run checks the proofs, in
+ *           chunks of its max_batch, against the recomputed c_g, testvs[gate_lut[g]] and out_cts[g]: gate g gets exactly the verdict and
+ *           reasons that call gives proof g on those inputs.  Returns the number of accepted gates; the program is proven iff that is
+ *           n_gates.  Consequence: a forged out_cts[g] fails gate g on the output check (VPBS_PBS_OUT_CT) and every consumer of wire
+ *           n_inputs + g on its LWE hash check (VPBS_PBS_LWE_HASH), since the consumer's proof was made for another input.  Host pointers. */
+typedef struct {
+    unsigned n_inputs, n_gates, n_luts;
+    size_t n_terms;
+    const uint64_t* gate_first; /* [n_gates + 1]: terms of gate g are [gate_first[g], gate_first[g + 1]) */
+    const uint32_t* term_src;   /* [n_terms]: wire index */
+    const uint64_t* term_coef;  /* [n_terms] */
+    const uint64_t* gate_const; /* [n_gates] */
+    const uint32_t* gate_lut;   /* [n_gates] */
+} vpbs_program_desc;
+typedef struct vpbs_program vpbs_program;
+int vpbs_program_create(vpbs_ctx* ctx, const vpbs_program_desc* desc, vpbs_program** out, char* err, size_t err_len);
+long vpbs_program_levels(const vpbs_program* prog, unsigned* levels_out /* [n_gates] or NULL */);
+long vpbs_program_run(vpbs_program* prog, vpbs_bootstrapper* bootstrapper, const uint64_t* inputs, const uint64_t* testvs, uint64_t* wires_out,
+                      uint64_t* gate_cts_out, uint64_t* out_cts, int on_device);
+long vpbs_program_prove(vpbs_program* prog, vpbs_pbs_prover* pbs_prover, const uint64_t* inputs, const uint64_t* testvs, unsigned steps,
+                        uint64_t* wires_out, uint64_t* out_cts, vpbs_pbs_proof_fn proof_fn, void* user, char* err, size_t err_len);
+long vpbs_program_verify(vpbs_program* prog, vpbs_pbs_verifier* pbs_verifier, const uint64_t* inputs, const uint64_t* testvs,
+                         const uint64_t* out_cts, const uint8_t* proofs, const size_t* offsets /* [n_gates + 1] */, uint8_t* verdicts /* [n_gates] */,
+                         uint8_t* reasons /* [n_gates] or NULL */, uint8_t* proof_reasons /* [n_gates] or NULL */);
+void vpbs_program_free(vpbs_program* prog);
+
 /* ---- memory helpers for hosts that do not link the HIP runtime themselves (a Rust or plain C++ caller) ----
  * pinned host memory (hipHostMalloc): witness matrices written there reach the device at PCIe speed (70.8 MB in 1.3 ms instead of ~15 ms
  * from pageable memory); device buffers for per-circuit data that is uploaded once (the sigma values of vpbs_step_inputs.sigmas_values with

@@ -1,0 +1,233 @@
+#!/usr/bin/env python3
+"""A program of lookup gates on one resident key set: seeded keys, seeded input ciphertexts, a seeded layered random netlist (or a program
+file), evaluated twice -- by ONE api.Program.run (the resident leg: gate inputs formed on the device, one wait at the end) and the way a
+user had to before api.Program existed (the baseline leg: Bootstrapper.run per level, combinations formed on the host with numpy) -- and
+compared wire by wire.  One JSON line.
+
+usage: tools/run_program.py [--levels L] [--width W] [--fan-in F] [--program FILE.json] [--n8] [--prove] [--baseline] [--runs R] [--seed S]
+  netlist: W inputs, L layers of W gates; a gate reads F wires of the layer before it with coefficients in {1, p - 1}; gate 0 of every layer
+    is the identity of gate 0 of the layer before it (fan-in 1, coefficient 1), so that one output has a known message whatever F is.
+  --program: {"n_inputs", "n_luts", "gates": [{"terms": [[src, coef], ..], "const", "lut"}, ..]} instead; lut 0 is the test vector of the
+    identity on {0, 1}, lut 1 its negation, further luts are seeded random words.
+  --n8: the N = 8, n = 6 miniature of tools/prove_batch.py --n8; default: the paper's N = 1024, n = 728.
+  --prove: api.Program.prove on an api.PbsProver, api.Program.verify on an api.PbsVerifier made from the prover's key_hash(), and the
+    output wires with a known message decrypted.
+  --baseline: the baseline leg ALONE.  It needs nothing newer than api.Bootstrapper, so this file can be copied into a build of an older
+    commit and time that.
+  Time: wall seconds per run of a leg (after one warm-up run), per level = / levels; HIP-event milliseconds of the bootstrap launches per
+  level (the library's own timers).  Bytes: what each leg moves between host and device per run, computed from the shapes."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tools")]
+import numpy as np  # noqa: E402
+import torch  # noqa: E402,F401  (the HIP runtime the library shares with it)
+
+import vpbs_amd  # noqa: E402
+from vpbs_amd import api, circuit_file  # noqa: E402
+
+K, ELL, LOGB = 2, 4, 5
+P = api.P
+SIGMA_GLWE, SIGMA_LWE = 4.99027217501041e-8, 1.17021618159313e-5
+SEED = 0x5EED0728
+
+
+def rounded(m, delta, p=2):
+    """main.rs:59-64: round(m_bar / delta) mod 2 p"""
+    return int(round(int(m) / delta)) % (2 * p)
+
+
+def layered(rng, levels, width, fan_in):
+    """-> (n_inputs, gates as (terms, const, lut)): see the module text"""
+    gates = []
+    for lv in range(levels):
+        base = 0 if lv == 0 else width + (lv - 1) * width       # first wire of the layer before
+        for g in range(width):
+            if g == 0:
+                gates.append(([(base, 1)], 0, 0))
+                continue
+            srcs = rng.integers(0, width, size=fan_in)
+            coefs = rng.integers(0, 2, size=fan_in)
+            gates.append(([(base + int(s), 1 if c else P - 1) for s, c in zip(srcs, coefs)], 0, 0))
+    return width, gates
+
+
+def load_program(path):
+    d = json.load(open(path))
+    return d["n_inputs"], [([(int(s), int(c)) for s, c in g["terms"]], int(g.get("const", 0)), int(g.get("lut", 0))) for g in d["gates"]], d.get("n_luts", 1)
+
+
+def gate_levels(n_inputs, gates):
+    lv = []
+    for terms, _, _ in gates:
+        lv.append(1 + max([0] + [lv[s - n_inputs] for s, _ in terms if s >= n_inputs]))
+    return lv
+
+
+def known_messages(n_inputs, gates, msgs):
+    """the message of every wire that is an identity (one term, coefficient 1, no constant, lut 0) of a wire with a known message"""
+    known = list(msgs)
+    for terms, const, lut in gates:
+        ok = len(terms) == 1 and terms[0][1] == 1 and const == 0 and lut == 0
+        known.append(known[terms[0][0]] if ok else None)
+    return known
+
+
+def mulmod(a, c):
+    """a [rows][words] uint64 (canonical) times the field element c, word by word: c is 1 or p - 1 in the seeded netlists (exact in numpy);
+    anything else goes through Python integers"""
+    if c == 1:
+        return a
+    if c == P - 1:
+        return np.where(a == 0, a, np.uint64(P) - a)
+    return np.array([[int(v) * c % P for v in row] for row in a], np.uint64)
+
+
+def addmod(a, b):
+    s = a + b                                   # wraps at 2^64
+    wrapped = s < a
+    s = np.where(wrapped, s + np.uint64(0xFFFFFFFF), s)      # 2^64 = 2^32 - 1 mod p; cannot wrap again: a, b < p
+    return np.where(s >= np.uint64(P), s - np.uint64(P), s)
+
+
+def run_baseline(ctx, bs, n_inputs, gates, lv, inputs, testvs):
+    """Bootstrapper.run per level (in chunks of max_batch) on host combinations -> (wires, event ms of every level)"""
+    n_levels = max([0] + lv)
+    words = inputs.shape[1]
+    wires = np.zeros((n_inputs + len(gates), words), np.uint64)
+    wires[:n_inputs] = inputs % np.uint64(P)
+    event_ms = []
+    for level in range(1, n_levels + 1):
+        todo = [g for g in range(len(gates)) if lv[g] == level]
+        cts = np.zeros((len(todo), words), np.uint64)
+        cts[:, words - 1] = np.array([gates[g][1] for g in todo], np.uint64)
+        fan = max(len(gates[g][0]) for g in todo)
+        for t in range(fan):                    # term t of every gate of the level at once
+            rows = [k for k, g in enumerate(todo) if len(gates[g][0]) > t]
+            for c in sorted({gates[todo[k]][0][t][1] for k in rows}):
+                sel = [k for k in rows if gates[todo[k]][0][t][1] == c]
+                cts[sel] = addmod(cts[sel], mulmod(wires[[gates[todo[k]][0][t][0] for k in sel]], c))
+        tvs = testvs[[gates[g][2] for g in todo]]
+        for lo in range(0, len(todo), bs.max_batch):
+            _, lwe = bs.run(cts[lo:lo + bs.max_batch], tvs[lo:lo + bs.max_batch])
+            wires[[n_inputs + g for g in todo[lo:lo + bs.max_batch]]] = lwe
+        event_ms.append(ctx.timing_report().get("pbs_batch", {}).get("ms", 0.0))
+    wires[:n_inputs] = inputs                   # as given
+    return wires, event_ms
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--levels", type=int, default=3)
+    ap.add_argument("--width", type=int, default=8)
+    ap.add_argument("--fan-in", type=int, default=2)
+    ap.add_argument("--program")
+    ap.add_argument("--n8", action="store_true")
+    ap.add_argument("--prove", action="store_true")
+    ap.add_argument("--baseline", action="store_true")
+    ap.add_argument("--runs", type=int, default=1)
+    ap.add_argument("--max-batch", type=int, default=256)
+    ap.add_argument("--chains", type=int, default=0)
+    ap.add_argument("--witness-batch", type=int, default=0)
+    ap.add_argument("--seed", type=int, default=1)
+    args = ap.parse_args()
+    if args.baseline and args.prove:
+        raise SystemExit("--baseline evaluates only: it cannot run with --prove")
+    N, n_lwe, log_n = (8, 6, 13) if args.n8 else (1024, 728, 16)
+    rng = np.random.default_rng(args.seed)
+    if args.program:
+        n_inputs, gates, n_luts = load_program(args.program)
+    else:
+        (n_inputs, gates), n_luts = layered(rng, args.levels, args.width, args.fan_in), 1
+    n_gates, lv = len(gates), gate_levels(n_inputs, gates)
+    n_levels = max([0] + lv)
+    ctx = vpbs_amd.Context(0, log_n_max=max(16, log_n))
+    keys = ctx.keygen(N, K, ELL, LOGB, n_lwe, SEED, SIGMA_GLWE, SIGMA_LWE)
+    testv, delta = api.testv(N, 2)
+    testvs = np.stack([testv, np.where(testv == 0, testv, np.uint64(P) - testv)] + [rng.integers(0, P, size=N, dtype=np.uint64) for _ in range(2, n_luts)])
+    testvs = np.ascontiguousarray(testvs[:max(n_luts, 1)])
+    msgs = [int(m) for m in rng.integers(0, 2, size=n_inputs)]
+    inputs = np.stack([api.lwe_encrypt(keys["params"], keys["s_lwe"], delta * m % P, nonce=i) for i, m in enumerate(msgs)])
+    known = known_messages(n_inputs, gates, msgs)
+    bs = api.Bootstrapper(ctx, keys["bsk"], keys["ksk"], K, ELL, LOGB, max_batch=max(1, min(args.max_batch, max(n_gates, 1))))
+    words, kn = n_lwe + 1, K * N
+    per_level = [sum(1 for x in lv if x == level) for level in range(1, n_levels + 1)]
+    out = {"what": "a program of %d gates on %d levels over %d inputs at N=%d, n=%d" % (n_gates, n_levels, n_inputs, N, n_lwe), "gates": n_gates,
+           "levels": n_levels, "inputs": n_inputs, "fan_in": None if args.program else args.fan_in, "max_batch": bs.max_batch, "runs": args.runs}
+    ctx.timing_enable(1)
+
+    # ---- the baseline leg ----
+    run_baseline(ctx, bs, n_inputs, gates, lv, inputs, testvs)       # warm-up
+    base_s, base_wires, base_events = [], None, None
+    for _ in range(args.runs):
+        ctx.timing_report()
+        t = time.perf_counter()
+        base_wires, base_events = run_baseline(ctx, bs, n_inputs, gates, lv, inputs, testvs)
+        base_s.append(time.perf_counter() - t)
+    out["baseline"] = {"seconds": base_s, "seconds_per_level": statistics.median(base_s) / max(n_levels, 1), "pbs_event_ms_per_level": base_events,
+                       "h2d_bytes": 8 * sum(c * (words + N) for c in per_level), "d2h_bytes": 8 * sum(c * (kn + words) for c in per_level)}
+    ok = True
+    if not args.baseline:
+        # ---- the resident leg: wires only ----
+        prog = api.Program(ctx, n_inputs, gates, testvs.shape[0])
+        assert prog.levels()[0].tolist() == lv
+        prog.run(bs, inputs, testvs, gate_cts=False, out_cts=False)      # warm-up
+        res_s, wires, rep = [], None, {}
+        for _ in range(args.runs):
+            ctx.timing_report()
+            t = time.perf_counter()
+            wires = prog.run(bs, inputs, testvs, gate_cts=False, out_cts=False)[0]
+            res_s.append(time.perf_counter() - t)
+            rep = ctx.timing_report()
+        launches = max(rep.get("pbs_batch", {}).get("count", 0), 1)
+        out["resident"] = {"seconds": res_s, "seconds_per_level": statistics.median(res_s) / max(n_levels, 1),
+                           "pbs_event_ms_per_level": rep.get("pbs_batch", {}).get("ms", 0.0) / max(n_levels, 1),
+                           "pbs_launches": launches, "combine_event_ms_total": rep.get("lwe_combine", {}).get("ms", 0.0),
+                           "h2d_bytes": 8 * (n_inputs * words + testvs.shape[0] * N), "d2h_bytes": 8 * (n_inputs + n_gates) * words}
+        out["resident_over_baseline"] = statistics.median(res_s) / statistics.median(base_s)
+        out["all_equal"] = bool((wires == base_wires).all())
+        ok = out["all_equal"]
+        if args.prove:
+            cyc_path, dum_path = circuit_file.find_cyclic_circuit(N, K, ELL, LOGB, n_lwe, log_n)
+            cyc, dum = circuit_file.load(cyc_path), circuit_file.load(dum_path)
+            chains = args.chains or (2 if args.n8 else 8)
+            api.host_set_late_threads(api.late_threads_for(chains, api.host_cpu_budget()))
+            api.host_set_early_threads(api.early_threads_for(chains))
+            prover = api.PbsProver(0, cyc, dum, keys["bsk"], keys["ksk"], K, ELL, LOGB, chains=chains,
+                                   witness_batch=args.witness_batch or (3 if args.n8 else 64))
+            t = time.perf_counter()
+            proofs, p_wires, out_cts = prog.prove(prover, inputs, testvs)
+            out["prove_seconds"] = time.perf_counter() - t
+            kh, (vk, _) = prover.key_hash(), prover.verifier_data()
+            prover.close()
+            pv = api.PbsVerifier(ctx, vk[4:].reshape(-1, 4), [cyc.n_constants + 80, 135, 20, 16], vk[:4], log_n, cyc.n_constants, 80, cyc.gates, N, K,
+                                 n_lwe, K * ELL * K * N, kh, max_batch=max(1, min(n_gates, 64)))
+            t = time.perf_counter()
+            verdicts, reasons, _ = prog.verify(pv, inputs, testvs, out_cts, proofs)
+            out["verify_seconds"] = time.perf_counter() - t
+            pv.close()
+            out["verified"] = int(verdicts.sum())
+            out["proven"] = out["verified"] == n_gates
+            out["rejected_because"] = sorted({api.pbs_reason_text(int(r)) for v, r in zip(verdicts, reasons) if not v})
+            out["all_equal"] = bool(out["all_equal"] and (p_wires == base_wires).all())
+            ok = out["all_equal"] and out["proven"]
+        prog.close()
+    # ---- the output wires (the last level) whose message is known ----
+    outputs = [n_inputs + g for g in range(n_gates) if lv[g] == n_levels and known[n_inputs + g] is not None]
+    got = [rounded(api.lwe_decrypt(keys["s_lwe"], base_wires[w]), delta) for w in outputs]
+    out["decrypted_checked"] = len(outputs)
+    out["decrypted_correct"] = sum(1 for w, m in zip(outputs, got) if m == known[w])
+    ok = ok and out["decrypted_correct"] == out["decrypted_checked"]
+    bs.close()
+    ctx.close()
+    print(json.dumps(out))
+    return 0 if ok else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())

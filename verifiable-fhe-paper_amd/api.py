@@ -143,6 +143,11 @@ class TfheParamsC(C.Structure):
     _fields_ = [("log_N", C.c_uint), ("K", C.c_uint), ("ELL", C.c_uint), ("LOGB", C.c_uint)]
 
 
+class ProgramDescC(C.Structure):
+    _fields_ = [("n_inputs", C.c_uint), ("n_gates", C.c_uint), ("n_luts", C.c_uint), ("n_terms", C.c_size_t), ("gate_first", U64P),
+                ("term_src", C.POINTER(C.c_uint32)), ("term_coef", U64P), ("gate_const", U64P), ("gate_lut", C.POINTER(C.c_uint32))]
+
+
 class KeygenParamsC(C.Structure):
     _fields_ = [("log_N", C.c_uint), ("K", C.c_uint), ("ELL", C.c_uint), ("LOGB", C.c_uint), ("n_lwe", C.c_uint), ("seed", C.c_uint64),
                 ("sigma_glwe", C.c_double), ("sigma_lwe", C.c_double)]
@@ -324,6 +329,13 @@ SIGNATURES = {
     "vpbs_pbs_prover_set_checkpoint": (_i, [_vp, _ui, PBS_CHECKPOINT_FN, _vp]),
     "vpbs_pbs_prover_last_run": (_i, [_vp, C.POINTER(PbsRunStatsC)]),
     "vpbs_pbs_prover_free": (None, [_vp]),
+    "vpbs_program_create": (_i, [_vp, C.POINTER(ProgramDescC), C.POINTER(_vp), C.c_char_p, _sz]),
+    "vpbs_program_levels": (C.c_long, [_vp, C.POINTER(_ui)]),
+    "vpbs_program_run": (C.c_long, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i]),
+    "vpbs_program_prove": (C.c_long, [_vp, _vp, U64P, U64P, _ui, U64P, U64P, PBS_PROOF_FN, _vp, C.c_char_p, _sz]),
+    "vpbs_program_verify": (C.c_long, [_vp, _vp, U64P, U64P, U64P, C.POINTER(C.c_uint8), C.POINTER(_sz), C.POINTER(C.c_uint8),
+                                       C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]),
+    "vpbs_program_free": (None, [_vp]),
     "vpbs_lwe_extract": (_i, [_vp, _ui, _ui, _ui, _vp, _sz, _vp, _i]),
     "vpbs_lwe_decrypt": (_i, [U64P, U64P, _ui, U64P]),
     "vpbs_k_poseidon_batch": (_i, [_vp, U64P, _sz]),
@@ -1573,6 +1585,147 @@ class PbsProver:
         if self.h:
             lib().vpbs_pbs_prover_free(self.h)
             self.h = None
+
+    free = close
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Program:
+    """vpbs_program: a netlist of bootstraps on resident keys.  Wire w < n_inputs is input w, wire n_inputs + g the output of gate g; gate g
+    bootstraps const * (0, .., 0, 1) + sum coef * wire[src] with test vector testvs[lut].  gates: a list of (terms=[(src, coef), ..], const, lut)
+    in topological order, or the CSR arrays as a dict {gate_first, term_src, term_coef, gate_const, gate_lut}.  ctx=None gives a host-only
+    object (validated and levelised: levels()); an invalid description raises VpbsError with a message that names the gate."""
+
+    def __init__(self, ctx, n_inputs, gates, n_luts):
+        if isinstance(gates, dict):
+            first = np.ascontiguousarray(gates["gate_first"], dtype=np.uint64).reshape(-1)
+            src = np.ascontiguousarray(gates["term_src"], dtype=np.uint32).reshape(-1)
+            coef, const = _u64(gates["term_coef"]).reshape(-1), _u64(gates["gate_const"]).reshape(-1)
+            lut = np.ascontiguousarray(gates["gate_lut"], dtype=np.uint32).reshape(-1)
+        else:
+            gates = [tuple(g) for g in gates]
+            first = np.cumsum([0] + [len(g[0]) for g in gates]).astype(np.uint64)
+            src = np.array([t[0] for g in gates for t in g[0]], np.uint32)
+            coef = np.array([int(t[1]) for g in gates for t in g[0]], np.uint64)
+            const, lut = np.array([int(g[1]) for g in gates], np.uint64), np.array([g[2] for g in gates], np.uint32)
+        if src.size != coef.size or const.size != lut.size or first.size != const.size + 1:
+            raise ValueError("Program: expected gate_first [n_gates + 1], term_src / term_coef [n_terms], gate_const / gate_lut [n_gates]")
+        self.ctx, self.n_inputs, self.n_gates, self.n_luts = ctx, n_inputs, int(const.size), n_luts
+        self.gate_first, self.term_src, self.term_coef, self.gate_const, self.gate_lut = first, src, coef, const, lut
+        d = ProgramDescC(n_inputs, self.n_gates, n_luts, src.size, _ptr(first), src.ctypes.data_as(C.POINTER(C.c_uint32)), _ptr(coef), _ptr(const),
+                         lut.ctypes.data_as(C.POINTER(C.c_uint32)))
+        h, err = C.c_void_p(), C.create_string_buffer(512)
+        rc = lib().vpbs_program_create(ctx.h if ctx is not None else None, C.byref(d), C.byref(h), err, 512)
+        if rc:
+            self.h = None
+            raise VpbsError("vpbs_program_create: status %d: %s" % (rc, err.value.decode()))
+        self.h = h
+        if ctx is not None:
+            ctx._batches.add(self)   # must not outlive its context: Context.close() frees the survivors
+
+    def levels(self):
+        """-> (level of every gate in the caller's order, np.uint32 [n_gates]; number of levels)"""
+        out = np.zeros(max(self.n_gates, 1), np.uint32)
+        n = lib().vpbs_program_levels(self.h, out.ctypes.data_as(C.POINTER(C.c_uint)))
+        if n < 0:
+            raise VpbsError("vpbs_program_levels: status %d" % n)
+        return out[:self.n_gates], int(n)
+
+    def _host_args(self, who, n_lwe, N, inputs, testvs):
+        x, tv = _u64(inputs).reshape(-1, n_lwe + 1), _u64(testvs).reshape(-1, N)
+        if x.shape[0] != self.n_inputs or tv.shape[0] != self.n_luts:
+            raise ValueError("Program.%s: expected inputs [%d][%d] and testvs [%d][%d]" % (who, self.n_inputs, n_lwe + 1, self.n_luts, N))
+        return x, tv
+
+    def run(self, bootstrapper, inputs, testvs, gate_cts=True, out_cts=True):
+        """inputs [n_inputs][n + 1], testvs [n_luts][N] -> (wires [n_inputs + n_gates][n + 1], gate_cts [n_gates][n + 1], out_cts
+        [n_gates][K][N]), all in the caller's gate order; the number of levels is levels()[1].  gate_cts=False / out_cts=False: that
+        output is not downloaded (None in its place)."""
+        b = bootstrapper
+        x, tv = self._host_args("run", b.n_lwe, b.N, inputs, testvs)
+        wires = np.zeros((self.n_inputs + self.n_gates, b.n_lwe + 1), np.uint64)
+        cts = np.zeros((self.n_gates, b.n_lwe + 1), np.uint64) if gate_cts else None
+        out = np.zeros((self.n_gates, b.K, b.N), np.uint64) if out_cts else None
+        keep = np.zeros(1, np.uint64)   # a valid pointer for an empty array
+        p = lambda a: None if a is None else (a if a.size else keep).ctypes.data
+        rc = lib().vpbs_program_run(self.h, b.h, p(x), p(tv), p(wires), p(cts), p(out), 0)
+        if rc < 0:
+            raise VpbsError("vpbs_program_run: status %d: %s" % (rc, lib().vpbs_last_error(b.ctx.h).decode()))
+        return wires, cts, out
+
+    def run_device(self, bootstrapper, d_inputs, d_testvs, d_wires=None, d_gate_cts=None, d_out_cts=None):
+        """the same on device pointers (integers; None = output not wanted); returns the number of levels when the outputs are in place"""
+        q = lambda x: C.c_void_p(int(x)) if x else None
+        rc = lib().vpbs_program_run(self.h, bootstrapper.h, q(d_inputs), q(d_testvs), q(d_wires), q(d_gate_cts), q(d_out_cts), 1)
+        if rc < 0:
+            raise VpbsError("vpbs_program_run: status %d: %s" % (rc, lib().vpbs_last_error(bootstrapper.ctx.h).decode()))
+        return rc
+
+    def prove(self, pbs_prover, inputs, testvs, steps=0, on_proof=None):
+        """-> (proofs: list of bytes in the caller's gate order, wires, out_cts).  Proof g is PbsProver.prove(gate_cts[g], testvs[lut_g])[0];
+        on_proof(gate, bytes), failures (PbsProveError, with .out_ct = out_cts and .lwe_out = wires) and `steps` as in PbsProver.prove."""
+        pp = pbs_prover
+        x, tv = self._host_args("prove", pp.n_lwe, pp.N, inputs, testvs)
+        wires, out = np.zeros((self.n_inputs + self.n_gates, pp.n_lwe + 1), np.uint64), np.zeros((self.n_gates, pp.K, pp.N), np.uint64)
+        proofs, failures, raised = [None] * self.n_gates, [], []
+
+        def trampoline(_user, index, data, n, error):
+            try:
+                if not data:
+                    failures.append((int(index), (error or b"").decode()))
+                    return
+                proofs[index] = C.string_at(data, n)
+                if on_proof is not None and not raised:
+                    on_proof(int(index), proofs[index])
+            except BaseException as e:   # noqa: BLE001 -- must not unwind through the C frames
+                raised.append(e)
+        cb, err = PBS_PROOF_FN(trampoline), C.create_string_buffer(512)
+        keep = np.zeros(1, np.uint64)
+        p = lambda a: _ptr(a if a.size else keep)
+        n = lib().vpbs_program_prove(self.h, pp.h, p(x.reshape(-1)), p(tv.reshape(-1)), steps, p(wires.reshape(-1)), p(out.reshape(-1)), cb, None, err, 512)
+        if raised:
+            raise raised[0]
+        e, pp._ckpt_error = pp._ckpt_error, None
+        if e is not None:
+            raise e
+        if n < 0:
+            raise VpbsError("vpbs_program_prove: status %d: %s" % (n, err.value.decode()))
+        if failures:
+            raise PbsProveError(dict(failures), proofs, out, wires)
+        return proofs, wires, out
+
+    def verify(self, pbs_verifier, inputs, testvs, out_cts, proofs):
+        """out_cts [n_gates][K][N]: the claimed output GLWEs; proofs: list of bytes in gate order -> (verdicts, reasons, proof_reasons),
+        np.uint8 [n_gates] each.  The program is proven iff every verdict is 1."""
+        v = pbs_verifier
+        x, tv = self._host_args("verify", v.n_lwe, v.N, inputs, testvs)
+        o = _u64(out_cts).reshape(-1)
+        if o.size != self.n_gates * v.K * v.N or len(proofs) != self.n_gates:
+            raise ValueError("Program.verify: expected out_cts [%d][K][N] and %d proofs" % (self.n_gates, self.n_gates))
+        buf, offs = pack_proofs(proofs)
+        buf, offs = np.ascontiguousarray(buf, dtype=np.uint8), np.ascontiguousarray(offs, dtype=np.uint64)
+        verdicts, reasons, sub = (np.zeros(self.n_gates, np.uint8) for _ in range(3))
+        u8p = C.POINTER(C.c_uint8)
+        data = buf.ctypes.data_as(u8p) if buf.size else (C.c_uint8 * 1)()
+        keep = np.zeros(1, np.uint64)
+        p = lambda a: _ptr(a if a.size else keep)
+        rc = lib().vpbs_program_verify(self.h, v.h, p(x.reshape(-1)), p(tv.reshape(-1)), p(o), data, offs.ctypes.data_as(C.POINTER(C.c_size_t)),
+                                       verdicts.ctypes.data_as(u8p), reasons.ctypes.data_as(u8p), sub.ctypes.data_as(u8p))
+        if rc < 0:
+            raise VpbsError("vpbs_program_verify: status %d: %s" % (rc, lib().vpbs_last_error(v.ctx.h).decode()))
+        return verdicts, reasons, sub
+
+    def close(self):
+        if self.h:
+            lib().vpbs_program_free(self.h)
+            self.h = None
+            if self.ctx is not None:
+                self.ctx._batches.discard(self)
 
     free = close
 

@@ -17,6 +17,7 @@
 #include <cstring>
 
 #include "context.h"
+#include "program_internal.h"
 
 using vpbs::DeviceError;
 using vpbs::u64;
@@ -285,6 +286,48 @@ struct vpbs_bootstrapper {
     }
 };
 
+namespace vpbs {
+void bootstrapper_shape(const vpbs_bootstrapper* b, BootstrapperShape* out) { *out = BootstrapperShape{b->ctx, b->prm, b->n_lwe, b->max_batch}; }
+
+void bootstrapper_enqueue(vpbs_bootstrapper* b, const uint64_t* d_cts, size_t count, const uint64_t* d_testv, int testv_per_ct, uint64_t* d_out_ct,
+                          uint64_t* d_lwe_out, uint64_t* d_accs_out) {
+    vpbs_ctx* ctx = b->ctx;
+    const unsigned log_n = b->prm.log_N;
+    const size_t n = (size_t)1 << log_n;
+    PbsBatchArgs a{};
+    a.cts = d_cts;
+    a.testv = d_testv;
+    a.out_ct = d_out_ct;
+    a.lwe_out = d_lwe_out;
+    a.accs_out = d_accs_out;
+    a.testv_stride = testv_per_ct ? n : 0;
+    a.bsk = b->d_bsk;
+    a.ksk = b->d_ksk;
+    a.roots = ctx->ring_table(log_n);
+    a.ninv = gl::inv((u64)n);
+    a.log_n = log_n;
+    a.K = b->prm.K;
+    a.ELL = b->prm.ELL;
+    a.LOGB = b->prm.LOGB;
+    a.n_lwe = b->n_lwe;
+    {
+        vpbs::Timed t(ctx, "pbs_batch");
+        // Measured: 1024 threads are fastest while every ciphertext has a CU of its own; with more ciphertexts than CUs,
+        // two 512-thread workgroups per CU (where two fit the LDS) overlap each other's barriers and beat one of 1024.
+        const unsigned threads = b->threads ? b->threads : (count > b->cus && 2 * b->lds_bytes <= PBS_LDS_BUDGET ? 512u : 1024u);
+        if (threads == 256) launch_pbs_batch<256>(ctx->stream, a, count, b->lds_bytes);
+        else if (threads == 512) launch_pbs_batch<512>(ctx->stream, a, count, b->lds_bytes);
+        else launch_pbs_batch<1024>(ctx->stream, a, count, b->lds_bytes);
+    }
+    VPBS_HIP(hipGetLastError());
+}
+
+void lwe_extract_enqueue(void* stream, const uint64_t* d_glwe, unsigned log_N, unsigned K, unsigned n_lwe, size_t count, uint64_t* d_lwe_out) {
+    hipLaunchKernelGGL(lwe_extract_kernel, dim3((unsigned)count), dim3(256), 0, static_cast<hipStream_t>(stream), d_glwe, log_N, K, n_lwe, d_lwe_out);
+    VPBS_HIP(hipGetLastError());
+}
+}  // namespace vpbs
+
 extern "C" {
 int vpbs_bootstrapper_create(vpbs_ctx* ctx, const vpbs_tfhe_params* prm, unsigned n_lwe, const uint64_t* bsk, const uint64_t* ksk,
                              int keys_on_device, size_t max_batch, vpbs_bootstrapper** out, char* err, size_t err_len) {
@@ -367,41 +410,18 @@ long vpbs_bootstrapper_run(vpbs_bootstrapper* b, const uint64_t* cts, size_t cou
     int rc = VPBS_OK;
     try {
         VPBS_HIP(hipSetDevice(ctx->device));
-        PbsBatchArgs a{};
-        a.cts = cts;
-        a.testv = testv;
-        a.out_ct = out_ct;
-        a.lwe_out = lwe_out;
-        a.accs_out = accs_out;
+        const u64 *d_cts = cts, *d_testv = testv;
+        u64 *d_out_ct = out_ct, *d_lwe_out = lwe_out, *d_accs_out = accs_out;
         if (!on_device) {
             VPBS_HIP(hipMemcpyAsync(b->d_cts, cts, sizeof(u64) * count * ct_words, hipMemcpyHostToDevice, ctx->stream));
             VPBS_HIP(hipMemcpyAsync(b->d_testv, testv, sizeof(u64) * (testv_per_ct ? count : 1) * n, hipMemcpyHostToDevice, ctx->stream));
-            a.cts = b->d_cts;
-            a.testv = b->d_testv;
-            a.out_ct = out_ct ? b->d_out : nullptr;
-            a.lwe_out = lwe_out ? b->d_lwe : nullptr;
-            if (accs_out) a.accs_out = d_accs = ctx->alloc_words(count * (n_lwe + 2) * kn);
+            d_cts = b->d_cts;
+            d_testv = b->d_testv;
+            d_out_ct = out_ct ? b->d_out : nullptr;
+            d_lwe_out = lwe_out ? b->d_lwe : nullptr;
+            if (accs_out) d_accs_out = d_accs = ctx->alloc_words(count * (n_lwe + 2) * kn);
         }
-        a.testv_stride = testv_per_ct ? n : 0;
-        a.bsk = b->d_bsk;
-        a.ksk = b->d_ksk;
-        a.roots = ctx->ring_table(log_n);
-        a.ninv = gl::inv((u64)n);
-        a.log_n = log_n;
-        a.K = K;
-        a.ELL = b->prm.ELL;
-        a.LOGB = b->prm.LOGB;
-        a.n_lwe = n_lwe;
-        {
-            vpbs::Timed t(ctx, "pbs_batch");
-            // Measured: 1024 threads are fastest while every ciphertext has a CU of its own; with more ciphertexts than CUs,
-            // two 512-thread workgroups per CU (where two fit the LDS) overlap each other's barriers and beat one of 1024.
-            const unsigned threads = b->threads ? b->threads : (count > b->cus && 2 * b->lds_bytes <= PBS_LDS_BUDGET ? 512u : 1024u);
-            if (threads == 256) launch_pbs_batch<256>(ctx->stream, a, count, b->lds_bytes);
-            else if (threads == 512) launch_pbs_batch<512>(ctx->stream, a, count, b->lds_bytes);
-            else launch_pbs_batch<1024>(ctx->stream, a, count, b->lds_bytes);
-        }
-        VPBS_HIP(hipGetLastError());
+        bootstrapper_enqueue(b, d_cts, count, d_testv, testv_per_ct, d_out_ct, d_lwe_out, d_accs_out);
         if (!on_device) {
             if (out_ct) VPBS_HIP(hipMemcpyAsync(out_ct, b->d_out, sizeof(u64) * count * kn, hipMemcpyDeviceToHost, ctx->stream));
             if (lwe_out) VPBS_HIP(hipMemcpyAsync(lwe_out, b->d_lwe, sizeof(u64) * count * ct_words, hipMemcpyDeviceToHost, ctx->stream));

@@ -30,6 +30,7 @@
 
 #include "context.h"
 #include "ivc_resident.h"
+#include "program_internal.h"
 #include "test_entries.h"
 
 using vpbs::DeviceError;
@@ -245,6 +246,13 @@ struct vpbs_pbs_prover {
         if (w->p->ckpt_fn) w->p->ckpt_fn(w->p->ckpt_user, w->index, done, bytes, len);
     }
 };
+
+namespace vpbs {
+vpbs_bootstrapper* pbs_prover_bootstrapper(vpbs_pbs_prover* p, std::mutex** boot_mu) {
+    *boot_mu = &p->boot_mu;
+    return p->boot;
+}
+}  // namespace vpbs
 
 extern "C" {
 

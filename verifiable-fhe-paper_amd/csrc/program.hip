@@ -1,0 +1,415 @@
+// Programs of lookup gates on resident keys (vpbs_program, include/vpbs_prover.h): a netlist whose every gate is one bootstrap of a linear
+// combination of earlier wires.  The object validates and levelises the description on the host and keeps it on the device twice: in the
+// caller's gate order (verification combines all gates at once) and permuted level by level (evaluation walks the levels).
+//
+//   run     per level, per chunk of the Bootstrapper's max_batch gates, on the Bootstrapper's context's stream:
+//             lwe_combine_kernel   wire table -> the chunk's gate inputs  [gates][n_lwe + 1]
+//             gather_rows_kernel   testvs[gate_lut] -> the chunk's test vectors  [gates][N]
+//             pbs_batch_kernel     (vpbs::bootstrapper_enqueue) -> out_ct, and lwe_out straight into the level's rows of the wire table
+//           The wire table on the device is in the PERMUTED order, so a level's outputs are contiguous rows; gather_rows_kernel puts the
+//           outputs back into the caller's order at the end.  The levels are ordered by the stream; nothing waits inside a kernel for
+//           another workgroup; the host waits once.
+//   prove   run on the batch prover's Bootstrapper, then vpbs_pbs_prover_run on the gate inputs (caller's order) with per-gate test vectors.
+//   verify  upload inputs and claimed outputs, lwe_extract_kernel on all outputs, ONE lwe_combine_kernel over all gates in the caller's
+//           order, then vpbs_pbs_verifier_run in chunks.
+#include <algorithm>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "context.h"
+#include "program_internal.h"
+
+using vpbs::DeviceError;
+using vpbs::u64;
+using u32 = uint32_t;
+
+namespace vpbs {
+namespace {
+struct CombineArgs {
+    const u64* wires;      // [n_wires][words]
+    const u64* first;      // [n_gates + 1]
+    const u32* src;        // [n_terms]: rows of `wires`
+    const u64* coef;       // [n_terms]
+    const u64* cst;        // [n_gates]
+    u64* out;              // [count][words]: row 0 is gate `gate0`
+    unsigned gate0, words; // words = n_lwe + 1
+};
+
+// One workgroup per gate, lanes on consecutive words of the ciphertext: every term is one coalesced read of a wire row.  The term list, the
+// coefficients and the constant depend on blockIdx.x alone, so their loads are wave-uniform.  A wire word is reduced before it is used (an
+// input ciphertext may hold words at or above p; bootstrap outputs are canonical); products and sums are canonical in, canonical out.
+__global__ void __launch_bounds__(256) lwe_combine_kernel(CombineArgs a) {
+    const unsigned g = a.gate0 + blockIdx.x;
+    const u64 t0 = a.first[g], t1 = a.first[g + 1];
+    const u64 c = a.cst[g];
+    u64* out = a.out + (size_t)blockIdx.x * a.words;
+    for (unsigned j = threadIdx.x; j < a.words; j += 256) {
+        u64 s = j + 1 == a.words ? c : 0;
+        for (u64 t = t0; t < t1; ++t) s = gl::add(s, gl::mul(a.coef[t], gl::canon(a.wires[(size_t)a.src[t] * a.words + j])));
+        out[j] = s;
+    }
+}
+
+// dst row i = src row map[i] (map null: row i), rows of `words` words: the per-gate test vectors of a chunk, and the outputs put back into the
+// caller's gate order.  One workgroup per row.
+__global__ void __launch_bounds__(256) gather_rows_kernel(const u64* __restrict__ src, const u32* __restrict__ map, size_t words,
+                                                          u64* __restrict__ dst) {
+    const u64* s = src + (size_t)(map ? map[blockIdx.x] : blockIdx.x) * words;
+    u64* d = dst + (size_t)blockIdx.x * words;
+    for (size_t j = threadIdx.x; j < words; j += 256) d[j] = s[j];
+}
+
+void report(char* err, size_t err_len, const std::string& m) {
+    if (err && err_len) {
+        std::strncpy(err, m.c_str(), err_len - 1);
+        err[err_len - 1] = 0;
+    }
+}
+
+struct Csr {   // a description in one gate order
+    std::vector<u64> first, coef, cst;
+    std::vector<u32> src, lut;
+};
+struct DeviceCsr {
+    u64 *first = nullptr, *coef = nullptr, *cst = nullptr;
+    u32 *src = nullptr, *lut = nullptr;
+};
+}  // namespace
+}  // namespace vpbs
+
+struct vpbs_program {
+    vpbs_ctx* ctx = nullptr;   // null: host-only
+    unsigned n_inputs = 0, n_gates = 0, n_luts = 0, n_levels = 0;
+    size_t n_terms = 0;
+    vpbs::Csr given;                   // the caller's order (host copy: prove gathers test vectors by it)
+    std::vector<unsigned> level;       // [n_gates], caller's order
+    std::vector<u32> order;            // permuted position q -> caller's gate
+    std::vector<u32> level_first;      // [n_levels + 1] in permuted positions
+    vpbs::DeviceCsr d_given, d_perm;   // d_perm.src: rows of the permuted wire table
+    u32 *d_wire_pos = nullptr, *d_gate_pos = nullptr;   // caller's wire / gate -> row of the permuted wire table / permuted position
+    std::vector<void*> owned;
+
+    ~vpbs_program() {
+        if (!ctx) return;
+        (void)hipSetDevice(ctx->device);
+        (void)vpbs::stream_sync(ctx->stream);
+        for (void* p : owned) ctx->release(p);
+    }
+    template <class T>
+    T* upload(const std::vector<T>& v) {
+        T* d = static_cast<T*>(ctx->alloc_bytes(std::max<size_t>(8, v.size() * sizeof(T))));
+        owned.push_back(d);
+        if (!v.empty()) VPBS_HIP(hipMemcpyAsync(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
+        return d;
+    }
+    vpbs::DeviceCsr upload(const vpbs::Csr& c) {
+        vpbs::DeviceCsr d;
+        d.first = upload(c.first);
+        d.coef = upload(c.coef);
+        d.cst = upload(c.cst);
+        d.src = upload(c.src);
+        d.lut = upload(c.lut);
+        return d;
+    }
+};
+
+namespace vpbs {
+namespace {
+void launch_combine(hipStream_t s, const u64* d_wires, const DeviceCsr& d, unsigned gate0, unsigned count, unsigned words, u64* d_out) {
+    const CombineArgs a{d_wires, d.first, d.src, d.coef, d.cst, d_out, gate0, words};
+    hipLaunchKernelGGL(lwe_combine_kernel, dim3(count), dim3(256), 0, s, a);
+}
+void launch_gather(hipStream_t s, const u64* d_src, const u32* d_map, size_t words, unsigned rows, u64* d_dst) {
+    hipLaunchKernelGGL(gather_rows_kernel, dim3(rows), dim3(256), 0, s, d_src, d_map, words, d_dst);
+}
+
+// device memory of one call, from a context's pool; released after the stream has drained
+struct Scratch {
+    vpbs_ctx* ctx;
+    std::vector<void*> blocks;
+    explicit Scratch(vpbs_ctx* c) : ctx(c) {}
+    u64* words(size_t n) {
+        u64* d = ctx->alloc_words(std::max<size_t>(1, n));
+        blocks.push_back(d);
+        return d;
+    }
+    ~Scratch() {
+        if (blocks.empty()) return;
+        (void)vpbs::stream_sync(ctx->stream);
+        for (void* p : blocks) ctx->release(p);
+    }
+};
+
+// vpbs_program_run; `b`'s runs are serialised by the caller
+long program_run(vpbs_program* prog, vpbs_bootstrapper* b, const u64* inputs, const u64* testvs, u64* wires_out, u64* gate_cts_out, u64* out_cts,
+                 int on_device) {
+    if (!prog || !b || !prog->ctx) return VPBS_ERR_INVALID;
+    BootstrapperShape sh{};
+    bootstrapper_shape(b, &sh);
+    vpbs_ctx* ctx = sh.ctx;
+    const unsigned n_in = prog->n_inputs, n_gates = prog->n_gates, words = sh.n_lwe + 1;
+    const size_t n = (size_t)1 << sh.prm.log_N, kn = sh.prm.K * n, n_wires = (size_t)n_in + n_gates;
+    if (ctx->device != prog->ctx->device) return ctx->err = "the program and the Bootstrapper are on different devices", VPBS_ERR_INVALID;
+    if ((n_in && !inputs) || (n_gates && !testvs)) return ctx->err = "null inputs or testvs", VPBS_ERR_INVALID;
+    int rc = VPBS_OK;
+    try {
+        VPBS_HIP(hipSetDevice(ctx->device));
+        hipStream_t s = ctx->stream;
+        Scratch mem(ctx);
+        try {
+            // the wire table in permuted order: inputs, then the gates level by level
+            u64* d_wires = mem.words(n_wires * words);
+            u64* d_cts = mem.words((size_t)n_gates * words);
+            u64* d_out = out_cts ? mem.words((size_t)n_gates * kn) : nullptr;
+            const size_t chunk_max = std::min<size_t>(sh.max_batch, std::max(1u, n_gates));
+            u64* d_tv = mem.words(chunk_max * n);
+            const u64* d_testvs = testvs;
+            if (on_device) {
+                if (n_in) VPBS_HIP(hipMemcpyAsync(d_wires, inputs, 8 * (size_t)n_in * words, hipMemcpyDeviceToDevice, s));
+            } else {
+                if (n_in) VPBS_HIP(hipMemcpyAsync(d_wires, inputs, 8 * (size_t)n_in * words, hipMemcpyHostToDevice, s));
+                if (n_gates) {
+                    u64* d = mem.words((size_t)prog->n_luts * n);
+                    VPBS_HIP(hipMemcpyAsync(d, testvs, 8 * (size_t)prog->n_luts * n, hipMemcpyHostToDevice, s));
+                    d_testvs = d;
+                }
+            }
+            for (unsigned lv = 0; lv < prog->n_levels; ++lv) {
+                for (size_t q0 = prog->level_first[lv]; q0 < prog->level_first[lv + 1]; q0 += sh.max_batch) {
+                    const unsigned c = (unsigned)std::min<size_t>(sh.max_batch, prog->level_first[lv + 1] - q0);
+                    {
+                        vpbs::Timed t(ctx, "lwe_combine");
+                        launch_combine(s, d_wires, prog->d_perm, (unsigned)q0, c, words, d_cts + q0 * words);
+                    }
+                    launch_gather(s, d_testvs, prog->d_perm.lut + q0, n, c, d_tv);
+                    VPBS_HIP(hipGetLastError());
+                    bootstrapper_enqueue(b, d_cts + q0 * words, c, d_tv, 1, d_out ? d_out + q0 * kn : nullptr, d_wires + ((size_t)n_in + q0) * words,
+                                         nullptr);
+                }
+            }
+            // back into the caller's order, to where the caller wants it
+            auto deliver = [&](u64* dst, const u64* d_src, const u32* d_map, size_t row_words, size_t rows) {
+                if (!dst || rows == 0) return;
+                u64* d_dst = on_device ? dst : mem.words(rows * row_words);
+                launch_gather(s, d_src, d_map, row_words, (unsigned)rows, d_dst);
+                VPBS_HIP(hipGetLastError());
+                if (!on_device) VPBS_HIP(hipMemcpyAsync(dst, d_dst, 8 * rows * row_words, hipMemcpyDeviceToHost, s));
+            };
+            deliver(wires_out, d_wires, prog->d_wire_pos, words, n_wires);
+            deliver(gate_cts_out, d_cts, prog->d_gate_pos, words, n_gates);
+            deliver(out_cts, d_out, prog->d_gate_pos, kn, n_gates);
+            VPBS_HIP(vpbs::stream_sync(s));   // the one wait
+        } catch (const DeviceError&) {
+            (void)vpbs::stream_sync(s);
+            throw;
+        }
+    } catch (const DeviceError& e) {
+        ctx->err = e.what;
+        rc = e.status == VPBS_ERR_OOM ? VPBS_ERR_OOM : (e.status == VPBS_ERR_INVALID ? VPBS_ERR_INVALID : VPBS_ERR_DEVICE);
+    }
+    return rc == VPBS_OK ? (long)prog->n_levels : rc;
+}
+}  // namespace
+}  // namespace vpbs
+
+extern "C" {
+int vpbs_program_create(vpbs_ctx* ctx, const vpbs_program_desc* desc, vpbs_program** out, char* err, size_t err_len) {
+    using namespace vpbs;
+    if (out) *out = nullptr;
+    auto refuse = [&](const std::string& m) {
+        report(err, err_len, m);
+        if (ctx) ctx->err = m;
+        return VPBS_ERR_INVALID;
+    };
+    if (!desc || !out) return refuse("null argument");
+    const unsigned n_in = desc->n_inputs, n_gates = desc->n_gates;
+    const size_t T = desc->n_terms;
+    if (n_gates && (!desc->gate_first || !desc->gate_const || !desc->gate_lut)) return refuse("null argument");
+    if (T && (!desc->term_src || !desc->term_coef || !n_gates)) return refuse("null argument");
+    if ((u64)n_in + n_gates > 0x7fffffffull) return refuse("too many wires");
+    // ---- validity, gate by gate ----
+    if (n_gates && desc->gate_first[0] != 0) return refuse("gate 0: gate_first does not start at 0");
+    for (unsigned g = 0; g < n_gates; ++g) {
+        const std::string gate = "gate " + std::to_string(g) + ": ";
+        const u64 t0 = desc->gate_first[g], t1 = desc->gate_first[g + 1];
+        if (t1 < t0 || t1 > T) return refuse(gate + "gate_first is not monotone within [0, n_terms]");
+        if (desc->gate_lut[g] >= desc->n_luts) return refuse(gate + "gate_lut " + std::to_string(desc->gate_lut[g]) + " is not below n_luts");
+        if (desc->gate_const[g] >= gl::P) return refuse(gate + "gate_const is not below p");
+        for (u64 t = t0; t < t1; ++t) {
+            if (desc->term_src[t] >= (u64)n_in + g)
+                return refuse(gate + "term " + std::to_string(t - t0) + " reads wire " + std::to_string(desc->term_src[t]) +
+                              ", which is not below n_inputs + " + std::to_string(g) + " (topological order)");
+            if (desc->term_coef[t] >= gl::P) return refuse(gate + "term " + std::to_string(t - t0) + ": term_coef is not below p");
+        }
+    }
+    if (n_gates && desc->gate_first[n_gates] != T)
+        return refuse("gate " + std::to_string(n_gates - 1) + ": gate_first ends at " + std::to_string(desc->gate_first[n_gates]) + ", not at n_terms");
+    // ---- levels, and the order that makes them contiguous (stable: the caller's order within a level) ----
+    auto* p = new vpbs_program;
+    p->n_inputs = n_in;
+    p->n_gates = n_gates;
+    p->n_luts = desc->n_luts;
+    p->n_terms = T;
+    Csr& G = p->given;
+    G.first.assign(desc->gate_first, desc->gate_first + (n_gates ? n_gates + 1 : 0));
+    if (!n_gates) G.first.assign(1, 0);
+    G.src.assign(desc->term_src, desc->term_src + T);
+    G.coef.assign(desc->term_coef, desc->term_coef + T);
+    G.cst.assign(desc->gate_const, desc->gate_const + n_gates);
+    G.lut.assign(desc->gate_lut, desc->gate_lut + n_gates);
+    p->level.resize(n_gates);
+    for (unsigned g = 0; g < n_gates; ++g) {
+        unsigned lv = 0;
+        for (u64 t = G.first[g]; t < G.first[g + 1]; ++t)
+            if (G.src[t] >= n_in) lv = std::max(lv, p->level[G.src[t] - n_in]);
+        p->level[g] = lv + 1;
+        p->n_levels = std::max(p->n_levels, lv + 1);
+    }
+    p->level_first.assign(p->n_levels + 1, 0);
+    for (unsigned g = 0; g < n_gates; ++g) ++p->level_first[p->level[g]];
+    for (unsigned lv = 0; lv < p->n_levels; ++lv) p->level_first[lv + 1] += p->level_first[lv];
+    p->order.resize(n_gates);
+    std::vector<u32> gate_pos(n_gates), wire_pos((size_t)n_in + n_gates);
+    {
+        std::vector<u32> next(p->level_first.begin(), p->level_first.end());
+        for (unsigned g = 0; g < n_gates; ++g) {
+            const u32 q = next[p->level[g] - 1]++;
+            p->order[q] = g;
+            gate_pos[g] = q;
+        }
+    }
+    for (unsigned w = 0; w < n_in; ++w) wire_pos[w] = w;
+    for (unsigned g = 0; g < n_gates; ++g) wire_pos[n_in + g] = n_in + gate_pos[g];
+    if (ctx) {
+        Csr R;   // the permuted description; sources are rows of the permuted wire table
+        R.first.push_back(0);
+        for (unsigned q = 0; q < n_gates; ++q) {
+            const unsigned g = p->order[q];
+            for (u64 t = G.first[g]; t < G.first[g + 1]; ++t) {
+                R.src.push_back(wire_pos[G.src[t]]);
+                R.coef.push_back(G.coef[t]);
+            }
+            R.first.push_back(R.src.size());
+            R.cst.push_back(G.cst[g]);
+            R.lut.push_back(G.lut[g]);
+        }
+        p->ctx = ctx;
+        try {
+            VPBS_HIP(hipSetDevice(ctx->device));
+            p->d_given = p->upload(G);
+            p->d_perm = p->upload(R);
+            p->d_wire_pos = p->upload(wire_pos);
+            p->d_gate_pos = p->upload(gate_pos);
+            VPBS_HIP(vpbs::stream_sync(ctx->stream));   // the staging vectors go away
+        } catch (const DeviceError& e) {
+            (void)vpbs::stream_sync(ctx->stream);
+            report(err, err_len, e.what);
+            ctx->err = e.what;
+            delete p;
+            return e.status;
+        }
+    }
+    *out = p;
+    report(err, err_len, "");
+    return VPBS_OK;
+}
+
+void vpbs_program_free(vpbs_program* prog) { delete prog; }
+
+long vpbs_program_levels(const vpbs_program* prog, unsigned* levels_out) {
+    if (!prog) return VPBS_ERR_INVALID;
+    if (levels_out) std::copy(prog->level.begin(), prog->level.end(), levels_out);
+    return (long)prog->n_levels;
+}
+
+long vpbs_program_run(vpbs_program* prog, vpbs_bootstrapper* bootstrapper, const uint64_t* inputs, const uint64_t* testvs, uint64_t* wires_out,
+                      uint64_t* gate_cts_out, uint64_t* out_cts, int on_device) {
+    return vpbs::program_run(prog, bootstrapper, inputs, testvs, wires_out, gate_cts_out, out_cts, on_device);
+}
+
+long vpbs_program_prove(vpbs_program* prog, vpbs_pbs_prover* pbs_prover, const uint64_t* inputs, const uint64_t* testvs, unsigned steps,
+                        uint64_t* wires_out, uint64_t* out_cts, vpbs_pbs_proof_fn proof_fn, void* user, char* err, size_t err_len) {
+    using namespace vpbs;
+    auto refuse = [&](const std::string& m) {
+        report(err, err_len, m);
+        return (long)VPBS_ERR_INVALID;
+    };
+    report(err, err_len, "");
+    if (!prog || !pbs_prover) return refuse("null program or prover");
+    if (!prog->ctx) return refuse("a host-only program (made without a context) cannot be evaluated");
+    if (!proof_fn) return refuse("no proof_fn: the proofs have nowhere to go");
+    if ((prog->n_inputs && !inputs) || (prog->n_gates && !testvs)) return refuse("null inputs or testvs");
+    std::mutex* boot_mu = nullptr;
+    vpbs_bootstrapper* boot = pbs_prover_bootstrapper(pbs_prover, &boot_mu);
+    BootstrapperShape sh{};
+    bootstrapper_shape(boot, &sh);
+    if (steps > sh.n_lwe + 2) return refuse("steps exceeds n_lwe + 2 = " + std::to_string(sh.n_lwe + 2));
+    const size_t n = (size_t)1 << sh.prm.log_N, words = sh.n_lwe + 1;
+    std::vector<u64> gate_cts((size_t)prog->n_gates * words), tv((size_t)prog->n_gates * n);
+    {
+        std::lock_guard<std::mutex> lk(*boot_mu);
+        const long rc = program_run(prog, boot, inputs, testvs, wires_out, gate_cts.data(), out_cts, 0);
+        if (rc < 0) return report(err, err_len, std::string("evaluating the program: ") + vpbs_last_error(sh.ctx)), rc;
+    }
+    if (prog->n_gates == 0) return 0;
+    for (unsigned g = 0; g < prog->n_gates; ++g) std::memcpy(tv.data() + (size_t)g * n, testvs + (size_t)prog->given.lut[g] * n, 8 * n);
+    return vpbs_pbs_prover_run(pbs_prover, gate_cts.data(), prog->n_gates, tv.data(), 1, steps, nullptr, nullptr, proof_fn, user, err, err_len);
+}
+
+long vpbs_program_verify(vpbs_program* prog, vpbs_pbs_verifier* pbs_verifier, const uint64_t* inputs, const uint64_t* testvs,
+                         const uint64_t* out_cts, const uint8_t* proofs, const size_t* offsets, uint8_t* verdicts, uint8_t* reasons,
+                         uint8_t* proof_reasons) {
+    using namespace vpbs;
+    if (!prog || !pbs_verifier || !prog->ctx || !offsets || !verdicts) return VPBS_ERR_INVALID;
+    PbsVerifierShape sh{};
+    pbs_verifier_shape(pbs_verifier, &sh);
+    vpbs_ctx* ctx = sh.ctx;
+    const unsigned n_in = prog->n_inputs, n_gates = prog->n_gates, words = sh.n_lwe + 1;
+    const size_t n = sh.N, kn = (size_t)sh.K * n;
+    if (ctx->device != prog->ctx->device) return ctx->err = "the program and the verifier are on different devices", VPBS_ERR_INVALID;
+    if (n_gates == 0) return 0;
+    if ((n_in && !inputs) || !testvs || !out_cts || !proofs) return ctx->err = "null inputs, testvs, out_cts or proofs", VPBS_ERR_INVALID;
+    unsigned log_n = 0;
+    while (((size_t)1 << log_n) < n) ++log_n;
+    if (((size_t)1 << log_n) != n || sh.K < 2 || sh.n_lwe == 0 || sh.n_lwe > (sh.K - 1) * n)
+        return ctx->err = "the verifier's shape has no sample extraction (N a power of two, 1 <= n_lwe <= (K - 1) N)", VPBS_ERR_INVALID;
+    std::vector<u64> cts((size_t)n_gates * words), tv((size_t)n_gates * n);
+    try {
+        VPBS_HIP(hipSetDevice(ctx->device));
+        hipStream_t s = ctx->stream;
+        Scratch mem(ctx);
+        try {
+            u64* d_wires = mem.words(((size_t)n_in + n_gates) * words);   // the caller's order: inputs, then the extractions
+            u64* d_out = mem.words((size_t)n_gates * kn);
+            u64* d_cts = mem.words((size_t)n_gates * words);
+            if (n_in) VPBS_HIP(hipMemcpyAsync(d_wires, inputs, 8 * (size_t)n_in * words, hipMemcpyHostToDevice, s));
+            VPBS_HIP(hipMemcpyAsync(d_out, out_cts, 8 * (size_t)n_gates * kn, hipMemcpyHostToDevice, s));
+            lwe_extract_enqueue(s, d_out, log_n, sh.K, sh.n_lwe, n_gates, d_wires + (size_t)n_in * words);
+            {
+                vpbs::Timed t(ctx, "lwe_combine");
+                launch_combine(s, d_wires, prog->d_given, 0, n_gates, words, d_cts);   // all gates at once: no level order
+            }
+            VPBS_HIP(hipGetLastError());
+            VPBS_HIP(hipMemcpyAsync(cts.data(), d_cts, 8 * cts.size(), hipMemcpyDeviceToHost, s));
+            VPBS_HIP(vpbs::stream_sync(s));
+        } catch (const DeviceError&) {
+            (void)vpbs::stream_sync(s);
+            throw;
+        }
+    } catch (const DeviceError& e) {
+        ctx->err = e.what;
+        return e.status == VPBS_ERR_OOM ? VPBS_ERR_OOM : VPBS_ERR_DEVICE;
+    }
+    for (unsigned g = 0; g < n_gates; ++g) std::memcpy(tv.data() + (size_t)g * n, testvs + (size_t)prog->given.lut[g] * n, 8 * n);
+    long accepted = 0;
+    for (size_t g0 = 0; g0 < n_gates; g0 += sh.max_batch) {
+        const size_t c = std::min<size_t>(sh.max_batch, n_gates - g0);
+        const long rc = vpbs_pbs_verifier_run(pbs_verifier, proofs, offsets + g0, c, tv.data() + g0 * n, 1, cts.data() + g0 * words, out_cts + g0 * kn,
+                                              verdicts + g0, reasons ? reasons + g0 : nullptr, proof_reasons ? proof_reasons + g0 : nullptr);
+        if (rc < 0) return rc;
+        accepted += rc;
+    }
+    return accepted;
+}
+}  // extern "C"

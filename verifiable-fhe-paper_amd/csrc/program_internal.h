@@ -1,0 +1,37 @@
+// The seam between the program object (program.hip) and the three objects it drives: the Bootstrapper (pbs_batch.hip), the batch prover
+// (pbs_prove_batch.hip) and the batch verifier of whole vPBS proofs (verify_pbs_batch.hip).  A program queues one bootstrap launch per
+// level behind its own combine kernel and waits once, at the end: it needs the Bootstrapper's launch WITHOUT the wait vpbs_bootstrapper_run
+// ends with, and the shapes of objects whose structs are private to their files.  Library-internal, like ivc_resident.h.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+#include <mutex>
+
+#include "../../include/vpbs_prover.h"
+
+namespace vpbs {
+struct BootstrapperShape {
+    vpbs_ctx* ctx;
+    vpbs_tfhe_params prm;
+    unsigned n_lwe;
+    size_t max_batch;
+};
+void bootstrapper_shape(const vpbs_bootstrapper* b, BootstrapperShape* out);
+// pbs_batch_kernel for `count` <= max_batch ciphertexts on device pointers, queued on the context's stream: the launch of
+// vpbs_bootstrapper_run(.., on_device = 1) and nothing else -- no copy, no wait.  d_testv: [N], or [count][N] with testv_per_ct.  Any output
+// may be null.  Throws vpbs::DeviceError (context.h) for a failed launch; the caller holds the device (hipSetDevice).
+void bootstrapper_enqueue(vpbs_bootstrapper* b, const uint64_t* d_cts, size_t count, const uint64_t* d_testv, int testv_per_ct, uint64_t* d_out_ct,
+                          uint64_t* d_lwe_out, uint64_t* d_accs_out);
+// lwe_extract_kernel on device pointers, queued on `stream` (a hipStream_t): GLWEs [count][K][N] -> [count][n_lwe + 1]
+void lwe_extract_enqueue(void* stream, const uint64_t* d_glwe, unsigned log_N, unsigned K, unsigned n_lwe, size_t count, uint64_t* d_lwe_out);
+
+// the batch prover's own Bootstrapper and the mutex that serialises its runs (vpbs_pbs_prover::boot_mu)
+vpbs_bootstrapper* pbs_prover_bootstrapper(vpbs_pbs_prover* p, std::mutex** boot_mu);
+
+struct PbsVerifierShape {
+    vpbs_ctx* ctx;
+    unsigned N, K, n_lwe;
+    size_t max_batch;
+};
+void pbs_verifier_shape(const vpbs_pbs_verifier* v, PbsVerifierShape* out);
+}  // namespace vpbs

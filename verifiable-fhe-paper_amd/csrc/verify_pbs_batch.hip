@@ -27,6 +27,7 @@
 #include "poseidon.h"
 #include "context.h"
 #include "verify_batch.h"
+#include "program_internal.h"
 
 namespace {
 using vpbs::DeviceError;
@@ -154,6 +155,12 @@ struct vpbs_pbs_verifier {
         vpbs_proof_verifier_free(proofs);
     }
 };
+
+namespace vpbs {
+void pbs_verifier_shape(const vpbs_pbs_verifier* v, PbsVerifierShape* out) {
+    *out = PbsVerifierShape{v->ctx, v->P.N, v->P.kn / v->P.N, v->P.n_lwe, v->max_batch};
+}
+}  // namespace vpbs
 
 extern "C" {
 int vpbs_pbs_key_hash(const uint64_t* bsk, const uint64_t* ksk, unsigned n_lwe, size_t ggsw_len, uint64_t out[4]) {
