@@ -10,6 +10,7 @@
 #include <cstdlib>
 
 #include "host/plonky2_mirror.h"
+#include "proof_shape.h"
 #include "witness_check.h"
 
 using vpbs::DeviceError;
@@ -1066,75 +1067,47 @@ int vpbs_comm_allgather_checked(const vpbs_comm* comm, const uint64_t* local, si
     return local_status ? local_status : (peer ? VPBS_ERR_PEER : VPBS_OK);
 }
 
-// ProofWithPublicInputs::to_bytes (util/serialization): caps, OpeningSet, FriProof, then public inputs
+// ProofWithPublicInputs::to_bytes (util/serialization): caps, OpeningSet, FriProof in the order of walk_step_proof (proof_shape.h), then
+// the public inputs
 long vpbs_step_proof_to_bytes(const vpbs_ctx* ctx, const vpbs_step_inputs* in, unsigned n_constants, const uint64_t* caps,
                               const uint64_t* openings, const uint64_t* fri, uint8_t* out, size_t cap_bytes) {
     if (!ctx || !in || !caps || !openings || !fri || !out || !in->constants_sigmas) return VPBS_ERR_INVALID;
-    const plonky2::FriParams fp = plonky2::FriParams::standard(in->log_n, ctx->rate_bits, ctx->cap_height);
-    const size_t n_cs = in->constants_sigmas->ncols;
-    if (n_constants > n_cs) return VPBS_ERR_INVALID;
-    size_t pos = 0;
-    bool overflow = false;
-    auto put_words = [&](const uint64_t* w, size_t cnt) {
-        if (pos + 8 * cnt > cap_bytes) { overflow = true; return; }
-        std::memcpy(out + pos, w, 8 * cnt);  // little-endian host
-        pos += 8 * cnt;
-    };
-    auto put_u8 = [&](uint8_t b) {
-        if (pos + 1 > cap_bytes) { overflow = true; return; }
-        out[pos++] = b;
-    };
-    const size_t cap_words = (size_t)4 << ctx->cap_height;
-    put_words(caps, 3 * cap_words);  // wires_cap, plonk_zs_partial_products_cap, quotient_polys_cap
-    // OpeningSet field order: constants, plonk_sigmas, wires, plonk_zs, plonk_zs_next, partial_products, quotient_polys,
-    // lookup_zs (empty), lookup_zs_next (empty).  `openings` holds [cs | wires | zs_pp | quotient | zs_next].
-    const unsigned nc = in->num_challenges;
-    const uint64_t* cs = openings;
-    const uint64_t* wires = cs + 2 * n_cs;
-    const uint64_t* zs_pp = wires + 2 * (size_t)in->n_wires;
-    const uint64_t* quot = zs_pp + 2 * (size_t)in->n_zs_partial_products;
-    const uint64_t* zs_next = quot + 2 * (size_t)in->n_quotient;
-    put_words(cs, 2 * (size_t)n_constants);
-    put_words(cs + 2 * (size_t)n_constants, 2 * (n_cs - n_constants));
-    put_words(wires, 2 * (size_t)in->n_wires);
-    put_words(zs_pp, 2 * (size_t)nc);
-    put_words(zs_next, 2 * (size_t)nc);
-    put_words(zs_pp + 2 * (size_t)nc, 2 * (size_t)(in->n_zs_partial_products - nc));
-    put_words(quot, 2 * (size_t)in->n_quotient);
-    // FriProof
-    const uint64_t* w = fri;
-    const size_t n_rounds = fp.reduction_arity_bits.size();
-    put_words(w, n_rounds * cap_words);
-    w += n_rounds * cap_words;
-    const unsigned log_lde = fp.lde_bits();
-    const size_t oracle_cols[4] = {n_cs, in->n_wires, in->n_zs_partial_products, in->n_quotient};
-    for (unsigned q = 0; q < fp.config.num_query_rounds; ++q) {
-        for (size_t o = 0; o < 4; ++o) {
-            const unsigned nsib = log_lde - fp.config.cap_height;
-            put_words(w, oracle_cols[o]);
-            w += oracle_cols[o];
-            put_u8((uint8_t)nsib);
-            put_words(w, 4 * (size_t)nsib);
-            w += 4 * (size_t)nsib;
+    vpbs_verify_inputs vi{};
+    vi.log_n = in->log_n;
+    vi.rate_bits = ctx->rate_bits;
+    vi.cap_height = ctx->cap_height;
+    vi.n_constants_sigmas = in->constants_sigmas->ncols;
+    vi.n_wires = in->n_wires;
+    vi.n_zs_partial_products = in->n_zs_partial_products;
+    vi.n_quotient = in->n_quotient;
+    vi.num_challenges = in->num_challenges;
+    vi.n_constants = n_constants;
+    vpbs::ProofShape S;
+    if (!vpbs::make_proof_shape(vi, ctx->compat, vpbs::SHAPE_PARSE, S)) return VPBS_ERR_INVALID;
+    struct Writer {   // copies out (little-endian host)
+        const vpbs::ProofShape& S;
+        uint8_t* out;
+        size_t cap_bytes;
+        vpbs::ProofArrays<const uint64_t> from;
+        size_t pos = 0;
+        bool overflow = false;
+        void put(const void* p, size_t bytes) {
+            if (pos + bytes > cap_bytes) { overflow = true; return; }
+            std::memcpy(out + pos, p, bytes);
+            pos += bytes;
         }
-        unsigned lg = log_lde;
-        for (unsigned ab : fp.reduction_arity_bits) {
-            lg -= ab;
-            const unsigned nsib = lg - fp.config.cap_height;
-            put_words(w, (size_t)2 << ab);
-            w += (size_t)2 << ab;
-            put_u8((uint8_t)nsib);
-            put_words(w, 4 * (size_t)nsib);
-            w += 4 * (size_t)nsib;
+        void words(uint32_t src, size_t cnt, bool) { put(from.at(S, src), 8 * cnt); }
+        void length_byte(unsigned nsib) {
+            const uint8_t b = (uint8_t)nsib;
+            put(&b, 1);
         }
-    }
-    const size_t final_words = (size_t)2 << fp.final_poly_bits();
-    put_words(w, final_words + 1);  // final_poly, pow_witness
+    } wr{S, out, cap_bytes, {caps, openings, fri}};
+    vpbs::walk_step_proof(S, wr);
     // public inputs: write_usize(len) (compat.bytes_pi_len_prefix) + elements
     const uint64_t n_pi = in->n_public_inputs;
-    if (ctx->compat.bytes_pi_len_prefix) put_words(&n_pi, 1);
-    put_words(in->public_inputs, in->n_public_inputs);
-    return overflow ? (long)VPBS_ERR_INVALID : (long)pos;
+    if (S.pi_prefix) wr.put(&n_pi, 8);
+    wr.put(in->public_inputs, 8 * in->n_public_inputs);
+    return wr.overflow ? (long)VPBS_ERR_INVALID : (long)wr.pos;
 }
 
 }  // extern "C"

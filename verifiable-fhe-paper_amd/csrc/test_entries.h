@@ -18,4 +18,11 @@ int vpbs_test_ivc_preset_matrix(size_t proof_words, size_t n_pi, size_t ggsw_len
 int vpbs_test_pbs_prover_preset_matrix(vpbs_pbs_prover* p, const uint64_t* ct, const uint64_t* testv, unsigned first, unsigned count, uint64_t* out);
 size_t vpbs_test_pbs_prover_preset_words(const vpbs_pbs_prover* p);
 int vpbs_test_pbs_prover_dummy_proof(const vpbs_pbs_prover* p, uint64_t* out);
+// What walk_step_proof (proof_shape.h) yields for the shape `in` describes (log_n, rate_bits, cap_height, the column counts, num_challenges,
+// n_constants), as vpbs_proof_verifier_create records it (verify_batch.hip): src [*n_src] the byte offset of every word of the unified order
+// caps | openings | fri in a serialised proof, lenb_off / lenb_val [*n_lenb] the offset and value of every Merkle-path length byte.  Returns
+// the bytes up to and including the PoW witness.  Host only.  VPBS_ERR_INVALID for a null pointer, a shape vpbs_step_proof_from_bytes
+// refuses or a capacity below the count (the counts are still written).  Tests bind it themselves: it has no entry in api.py.
+long vpbs_test_proof_byte_tables(const vpbs_verify_inputs* in, size_t src_capacity, size_t lenb_capacity, uint32_t* src, uint32_t* lenb_off,
+                                 uint8_t* lenb_val, size_t* n_src, size_t* n_lenb);
 }

@@ -1,9 +1,10 @@
-// Host-side verifier of step proofs (no device work): mirrors plonky2 0.2.0 plonk/verifier.rs `verify_with_challenges`,
-// plonk/get_challenges.rs, fri/verifier.rs `verify_fri_proof` / `fri_verifier_query_round` / `fri_combine_initial` /
-// `compute_evaluation`, hash/merkle_proofs.rs `verify_merkle_proof_to_cap` and plonk/vanishing_poly.rs
-// `eval_vanishing_poly` (permutation part).  The reference calls it as `cd.verify(proof)` at
-// /root/reference/src/vtfhe/ivc_based_vpbs.rs:443-447.  Product code: written against gl.h /
-// poseidon.h, independent of the test oracle.
+// Host-side verifier of step proofs (no device work): plonky2 0.2.0 plonk/verifier.rs `verify_with_challenges`, plonk/get_challenges.rs,
+// fri/verifier.rs `verify_fri_proof` and hash/merkle_proofs.rs `verify_merkle_proof_to_cap`.  The reference calls it as `cd.verify(proof)` at
+// /root/reference/src/vtfhe/ivc_based_vpbs.rs:443-447.  What this file owns is the order of the checks: the serial
+// transcript, the vanishing identity right behind it, the proof of work before any query is looked at, and the Merkle paths collected and
+// climbed last (eight side by side where the CPU has AVX-512).  The proof's layout and the refusal rules come from proof_shape.h, the
+// vanishing identity and the arithmetic of a FRI query from verify_core.h -- the same code the device verifier (verify_batch.hip) runs.
+// Product code: written against gl.h / poseidon.h, independent of the test oracle.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -13,6 +14,8 @@
 #include "kernels.h"
 #include "poseidon.h"
 #include "host/poseidon_x8.h"
+#include "proof_shape.h"
+#include "verify_core.h"
 
 using gl::Ext;
 using gl::u64;
@@ -126,99 +129,15 @@ bool merkle_verify_all(std::vector<MerkleJob>& jobs) {
         if (!merkle_verify(j.leaf, j.leaf_len, j.idx, j.cap, j.siblings, j.n_sib)) return false;
     return true;
 }
-Ext ext_at(const u64* p, size_t i) { return Ext{p[2 * i], p[2 * i + 1]}; }
-size_t bitrev(size_t x, unsigned bits) {
-    size_t r = 0;
-    for (unsigned i = 0; i < bits; ++i) { r = (r << 1) | (x & 1); x >>= 1; }
-    return r;
-}
-// interpolate {(xs[i], ys[i])} and evaluate at t (arity <= 16)
-Ext interpolate(const u64* xs, const Ext* ys, size_t k, Ext t) {
-    Ext res = gl::ext(0);
-    for (size_t i = 0; i < k; ++i) {
-        Ext num = ys[i];
-        u64 den = 1;
-        for (size_t j = 0; j < k; ++j)
-            if (j != i) {
-                num = gl::mul(num, gl::sub(t, gl::ext(xs[j])));
-                den = gl::mul(den, gl::sub(xs[i], xs[j]));
-            }
-        res = gl::add(res, gl::mul(num, gl::inv(den)));
-    }
-    return res;
-}
-
-bool check_permutation_identity(const vpbs_verify_inputs* in, const u64* openings, const u64* betas, const u64* gammas,
-                                const u64* alphas, Ext zeta, const u64* gate_terms_zeta) {
-    const unsigned nc = in->num_challenges, n_routed = in->n_routed, deg = in->quotient_degree_factor;
-    const unsigned n_chunks = (n_routed + deg - 1) / deg, num_prods = n_chunks - 1;
-    const size_t n = (size_t)1 << in->log_n;
-    const u64* cs_z = openings;
-    const u64* wires_z = cs_z + 2 * (size_t)in->n_constants_sigmas;
-    const u64* zs_pp_z = wires_z + 2 * (size_t)in->n_wires;
-    const u64* quot_z = zs_pp_z + 2 * (size_t)in->n_zs_partial_products;
-    const u64* zs_next_z = quot_z + 2 * (size_t)in->n_quotient;
-    const u64* sig_z = cs_z + 2 * (size_t)in->n_constants;
-    const u64* pps_z = zs_pp_z + 2 * (size_t)nc;
-    Ext zeta_n = zeta;
-    for (unsigned i = 0; i < in->log_n; ++i) zeta_n = gl::mul(zeta_n, zeta_n);
-    const Ext one = gl::ext(1);
-    const Ext z_h = gl::sub(zeta_n, one);
-    const Ext l0 = gl::mul(z_h, gl::inv(gl::mul(gl::sub(zeta, one), (u64)n)));
-    std::vector<Ext> terms(nc + nc * n_chunks);
-    std::vector<u64> k_is(n_routed);
-    u64 k = 1;
-    for (unsigned j = 0; j < n_routed; ++j) { k_is[j] = k; k = gl::mul(k, gl::GENERATOR); }
-    for (unsigned c = 0; c < nc; ++c) {
-        terms[c] = gl::mul(l0, gl::sub(ext_at(zs_pp_z, c), one));
-        for (unsigned kk = 0; kk < n_chunks; ++kk) {
-            Ext num = one, den = one;
-            for (unsigned j = kk * deg; j < (kk + 1) * deg && j < n_routed; ++j) {
-                const Ext w = ext_at(wires_z, j), g = gl::ext(gammas[c]);
-                num = gl::mul(num, gl::add(gl::add(w, gl::mul(zeta, gl::mul(betas[c], k_is[j]))), g));
-                den = gl::mul(den, gl::add(gl::add(w, gl::mul(ext_at(sig_z, j), betas[c])), g));
-            }
-            const Ext prev = kk == 0 ? ext_at(zs_pp_z, c) : ext_at(pps_z, c * num_prods + kk - 1);
-            const Ext next = kk == num_prods ? ext_at(zs_next_z, c) : ext_at(pps_z, c * num_prods + kk);
-            terms[nc + c * n_chunks + kk] = gl::sub(gl::mul(prev, num), gl::mul(next, den));  // check_partial_products
-        }
-    }
-    const unsigned chunks_per = 1u << in->rate_bits;
-    for (unsigned a = 0; a < nc; ++a) {
-        Ext acc = gate_terms_zeta ? ext_at(gate_terms_zeta, a) : gl::ext(0);
-        for (size_t i = terms.size(); i-- > 0;) acc = gl::add(gl::mul(acc, alphas[a]), terms[i]);  // reduce_with_powers
-        Ext q = gl::ext(0);
-        for (unsigned m = chunks_per; m-- > 0;) q = gl::add(gl::mul(q, zeta_n), ext_at(quot_z, a * chunks_per + m));
-        if (!gl::eq(acc, gl::mul(z_h, q))) return false;
-    }
-    return true;
-}
 }  // namespace
 
 extern "C" int vpbs_verify_step(const vpbs_verify_inputs* in, const uint64_t* caps, const uint64_t* openings, const uint64_t* fri) {
     using namespace plonky2;
     if (!in || !caps || !openings || !fri || !in->constants_sigmas_cap || (in->n_public_inputs && !in->public_inputs)) return VPBS_ERR_INVALID;
-    if (in->rate_bits > 3 || in->cap_height > 8 || in->log_n == 0 || in->log_n + in->rate_bits > 24 || in->num_challenges == 0 ||
-        in->num_challenges > in->n_zs_partial_products)
-        return VPBS_ERR_INVALID;
-    if (!in->fri_only) {
-        const unsigned deg = in->quotient_degree_factor;
-        if (deg == 0 || in->n_routed == 0 || in->n_routed > in->n_wires || in->n_constants + in->n_routed > in->n_constants_sigmas ||
-            in->n_zs_partial_products != in->num_challenges * ((in->n_routed + deg - 1) / deg) ||
-            in->n_quotient != (in->num_challenges << in->rate_bits))
-            return VPBS_ERR_INVALID;
-    }
-    const FriParams fp = FriParams::standard(in->log_n, in->rate_bits, in->cap_height);
-    if (!fp.caps_fit()) return VPBS_ERR_INVALID;
-    vpbs_compat compat;   // the switch table of include/vpbs_prover.h (NULL = plonky2 0.2.0 as restated)
-    vpbs_compat_default(&compat);
-    if (in->compat) compat = *in->compat;
-    const unsigned nc = in->num_challenges, log_n = in->log_n;
-    const unsigned log_lde = log_n + in->rate_bits;
-    const size_t lde = (size_t)1 << log_lde, cap_words = (size_t)4 << in->cap_height;
-    const size_t ncols[4] = {in->n_constants_sigmas, in->n_wires, in->n_zs_partial_products, in->n_quotient};
-    size_t total_cols = 0;
-    for (size_t c : ncols) total_cols += c;
+    vpbs::ProofShape S;
+    if (!vpbs::make_proof_shape(*in, vpbs::compat_of(*in), vpbs::SHAPE_VERIFY, S)) return VPBS_ERR_INVALID;
+    const unsigned nc = S.nc;
+    const size_t cap_words = S.cap_words;
 
     // ---- transcript (plonk/get_challenges.rs) ----
     HashOut pi_hash;
@@ -227,121 +146,62 @@ extern "C" int vpbs_verify_step(const vpbs_verify_inputs* in, const uint64_t* ca
     ch.observe_elements(in->circuit_digest, 4);
     ch.observe_hash(pi_hash);
     ch.observe_cap(caps, cap_words / 4);
-    const std::vector<u64> betas = ch.get_n_challenges(nc), gammas = ch.get_n_challenges(nc);
+    const std::vector<u64> betas_gammas = ch.get_n_challenges(2 * (size_t)nc);   // betas [nc] | gammas [nc]
     ch.observe_cap(caps + cap_words, cap_words / 4);
     const std::vector<u64> alphas = ch.get_n_challenges(nc);
     ch.observe_cap(caps + 2 * cap_words, cap_words / 4);
     const Ext zeta = ch.get_extension_challenge();
-    ch.observe_elements(openings, 2 * (total_cols + nc));
-    if (!in->fri_only) {
+    ch.observe_elements(openings, S.n_open_words);
+    if (!S.fri_only) {
         // eval_vanishing_poly: the gate constraints at zeta come from the openings of the constants and the wires
         const u64* gate_terms = in->gate_terms_zeta;
         std::vector<u64> gt(2 * (size_t)nc);
-        if (in->gates && in->n_gates) {
-            if (in->num_selectors > in->n_constants) return VPBS_ERR_INVALID;
-            try {
-                vpbs::validate_gates(in->gates, in->n_gates, in->num_selectors, in->n_constants, in->n_wires);
-            } catch (const vpbs::DeviceError&) {
-                return VPBS_ERR_INVALID;
-            }
+        if (S.n_gates) {
             vpbs::gate_terms_at(in->gates, in->n_gates, in->num_selectors, openings, in->n_constants, openings + 2 * (size_t)in->n_constants_sigmas,
                                 in->n_wires, pi_hash.data(), alphas.data(), nc, gt.data());
             gate_terms = gt.data();
         }
-        if (!check_permutation_identity(in, openings, betas.data(), gammas.data(), alphas.data(), zeta, gate_terms)) return 0;
+        const vpbs::ZetaTerms zt = vpbs::zeta_terms(S, zeta);
+        for (unsigned a = 0; a < nc; ++a)
+            if (!vpbs::vanishing_holds(S, openings, a, alphas[a], betas_gammas.data(), zeta, zt,
+                                       [&] { return gate_terms ? vpbs::ext_at(gate_terms, a) : gl::ext(0); }))
+                return 0;
     }
 
     // ---- FRI challenges ----
     const Ext fri_alpha = ch.get_extension_challenge();
-    const size_t n_rounds = fp.reduction_arity_bits.size();
-    const size_t final_len = (size_t)1 << fp.final_poly_bits();
-    const size_t total = fri_proof_words(fp, {ncols[0], ncols[1], ncols[2], ncols[3]});
-    const u64* final_words = fri + total - 1 - 2 * final_len;
-    const u64 pow_witness = fri[total - 1];
-    const u64* w = fri;
-    std::vector<const u64*> fri_caps(n_rounds);
-    std::vector<Ext> fri_betas(n_rounds);
-    for (size_t r = 0; r < n_rounds; ++r) {
-        fri_caps[r] = w;
-        ch.observe_cap(w, cap_words / 4);
-        w += cap_words;
-        fri_betas[r] = ch.get_extension_challenge();
+    const u64* final_words = fri + S.fri_total - 1 - 2 * (size_t)S.final_len;
+    const u64 pow_witness = fri[S.fri_total - 1];
+    std::vector<u64> fri_betas(2 * (size_t)S.n_rounds);
+    for (size_t r = 0; r < S.n_rounds; ++r) {
+        ch.observe_cap(fri + r * cap_words, cap_words / 4);
+        const Ext beta = ch.get_extension_challenge();
+        fri_betas[2 * r] = beta.c0;
+        fri_betas[2 * r + 1] = beta.c1;
     }
-    ch.observe_elements(final_words, 2 * final_len);
+    ch.observe_elements(final_words, 2 * (size_t)S.final_len);
     if (pow_witness >= gl::P) return 0;
     ch.observe_element(pow_witness);
     const u64 pow_response = ch.get_challenge();
-    if (fp.config.proof_of_work_bits && (pow_response >> (64 - fp.config.proof_of_work_bits)) != 0) return 0;
+    if (S.pow_bits && (pow_response >> (64 - S.pow_bits)) != 0) return 0;
 
-    // ---- PrecomputedReducedOpenings: batch 0 = every polynomial at zeta, batch 1 = Z polynomials at g * zeta ----
-    const Ext zeta_next = gl::mul(zeta, gl::root_of_unity(log_n));
-    Ext reduced0 = gl::ext(0), reduced1 = gl::ext(0);
-    for (size_t j = total_cols; j-- > 0;) reduced0 = gl::add(gl::mul(reduced0, fri_alpha), ext_at(openings, j));
-    for (size_t j = nc; j-- > 0;) reduced1 = gl::add(gl::mul(reduced1, fri_alpha), ext_at(openings, total_cols + j));
+    // ---- query rounds: the arithmetic of each now, its Merkle paths (4 initial oracles, one per reduction round) collected for the end ----
+    Ext reduced0, reduced1;
+    vpbs::reduced_openings(S, openings, fri_alpha, reduced0, reduced1);
     const u64* oracle_caps[4] = {in->constants_sigmas_cap, caps, caps + cap_words, caps + 2 * cap_words};
-
     std::vector<MerkleJob> merkle_jobs;
-    merkle_jobs.reserve((size_t)fp.config.num_query_rounds * (4 + n_rounds));
-    for (unsigned q = 0; q < fp.config.num_query_rounds; ++q) {
-        size_t x_index = (size_t)(ch.get_challenge() % lde);
-        const u64* leaf[4];
-        const size_t nsib0 = log_lde - in->cap_height;
-        for (size_t o = 0; o < 4; ++o) {  // fri_verify_initial_proof
-            leaf[o] = w;
-            merkle_jobs.push_back({w, ncols[o], x_index, oracle_caps[o], w + ncols[o], nsib0});
-            w += ncols[o] + 4 * nsib0;
+    merkle_jobs.reserve((size_t)S.nq * (4 + S.n_rounds));
+    for (unsigned q = 0; q < S.nq; ++q) {
+        size_t x_index = (size_t)(ch.get_challenge() & (((u64)1 << S.log_lde) - 1));
+        const u64* qw = fri + S.o_queries + (size_t)q * S.query_words;
+        if (!vpbs::fri_query_holds(S, reduced0, reduced1, qw, final_words, (uint32_t)x_index, zeta, fri_alpha, fri_betas.data())) return 0;
+        for (size_t o = 0; o < 4; ++o)   // fri_verify_initial_proof
+            merkle_jobs.push_back({qw + S.off_o[o], S.ncols[o], x_index, oracle_caps[o], qw + S.off_o[o] + S.ncols[o], S.nsib0});
+        for (size_t r = 0; r < S.n_rounds; ++r) {
+            x_index >>= S.ab[r];
+            const u64* evals = qw + S.off_r[r];
+            merkle_jobs.push_back({evals, (size_t)2 << S.ab[r], x_index, fri + r * cap_words, evals + ((size_t)2 << S.ab[r]), S.nsib_r[r]});
         }
-        u64 subgroup_x = gl::mul(gl::GENERATOR, gl::pow(gl::root_of_unity(log_lde), bitrev(x_index, log_lde)));
-        // fri_combine_initial
-        Ext sum = gl::ext(0);
-        {
-            Ext acc = gl::ext(0), apow = gl::ext(1);
-            for (size_t o = 0; o < 4; ++o)
-                for (size_t p = 0; p < ncols[o]; ++p) {
-                    acc = gl::add(acc, gl::mul(apow, leaf[o][p]));
-                    apow = gl::mul(apow, fri_alpha);
-                }
-            sum = gl::mul(gl::sub(acc, reduced0), gl::inv(gl::sub(gl::ext(subgroup_x), zeta)));
-            acc = gl::ext(0);
-            apow = gl::ext(1);
-            for (size_t p = 0; p < nc; ++p) {
-                acc = gl::add(acc, gl::mul(apow, leaf[2][p]));
-                apow = gl::mul(apow, fri_alpha);
-            }
-            sum = gl::add(gl::mul(sum, apow), gl::mul(gl::sub(acc, reduced1), gl::inv(gl::sub(gl::ext(subgroup_x), zeta_next))));
-            // compat.fri_mul_final_by_x: the prover multiplied the final polynomial by X, so the combined value carries a factor subgroup_x
-            if (compat.fri_mul_final_by_x) sum = gl::mul(sum, subgroup_x);
-        }
-        Ext old_eval = sum;
-        unsigned lg = log_lde;
-        for (size_t r = 0; r < n_rounds; ++r) {
-            const unsigned ab = fp.reduction_arity_bits[r];
-            const size_t arity = (size_t)1 << ab;
-            const u64* evals = w;
-            const size_t coset_index = x_index >> ab, within = x_index & (arity - 1);
-            if (evals[2 * within] != old_eval.c0 || evals[2 * within + 1] != old_eval.c1) return 0;
-            // compute_evaluation
-            const u64 g = gl::root_of_unity(ab);
-            const u64 coset_start = gl::mul(subgroup_x, gl::pow(g, arity - bitrev(within, ab)));
-            u64 xs[16];
-            Ext ys[16];
-            u64 y = 1;
-            for (size_t i = 0; i < arity; ++i) {
-                xs[i] = gl::mul(coset_start, y);
-                ys[i] = ext_at(evals, bitrev(i, ab));
-                y = gl::mul(y, g);
-            }
-            old_eval = interpolate(xs, ys, arity, fri_betas[r]);
-            lg -= ab;
-            const size_t nsib = lg - in->cap_height;
-            merkle_jobs.push_back({evals, 2 * arity, coset_index, fri_caps[r], evals + 2 * arity, nsib});
-            w += 2 * arity + 4 * nsib;
-            for (unsigned k = 0; k < ab; ++k) subgroup_x = gl::mul(subgroup_x, subgroup_x);
-            x_index = coset_index;
-        }
-        Ext acc = gl::ext(0);
-        for (size_t i = final_len; i-- > 0;) acc = gl::add(gl::mul(acc, subgroup_x), ext_at(final_words, i));
-        if (!gl::eq(acc, old_eval)) return 0;
     }
     return merkle_verify_all(merkle_jobs) ? 1 : 0;
 }
@@ -350,91 +210,43 @@ extern "C" int vpbs_verify_step(const vpbs_verify_inputs* in, const uint64_t* ca
 // shape comes from `in` (column counts, n_constants, degree); a byte string of another shape is rejected, not guessed at.
 extern "C" long vpbs_step_proof_from_bytes(const vpbs_verify_inputs* in, const uint8_t* bytes, size_t len, uint64_t* caps, uint64_t* openings, uint64_t* fri,
                                 uint64_t* public_inputs_out, size_t public_inputs_capacity) {
-    if (!in || !bytes || !caps || !openings || !fri || in->n_constants > in->n_constants_sigmas || in->num_challenges > in->n_zs_partial_products)
-        return VPBS_ERR_INVALID;
-    using namespace plonky2;
-    if (in->rate_bits > 3 || in->cap_height > 8 || in->log_n == 0 || in->log_n + in->rate_bits > 24) return VPBS_ERR_INVALID;
-    const FriParams fp = FriParams::standard(in->log_n, in->rate_bits, in->cap_height);
-    if (!fp.caps_fit()) return VPBS_ERR_INVALID;
-    size_t pos = 0;
-    bool bad = false;
-    auto get_words = [&](uint64_t* w, size_t cnt) {
-        if (bad || pos + 8 * cnt > len) {
-            bad = true;
-            return;
+    if (!in || !bytes || !caps || !openings || !fri) return VPBS_ERR_INVALID;
+    vpbs::ProofShape S;
+    if (!vpbs::make_proof_shape(*in, vpbs::compat_of(*in), vpbs::SHAPE_PARSE, S)) return VPBS_ERR_INVALID;
+    struct Reader {   // copies in: bounds, canonical field elements, the expected length bytes
+        const vpbs::ProofShape& S;
+        const uint8_t* bytes;
+        size_t len;
+        vpbs::ProofArrays<uint64_t> to;
+        size_t pos = 0;
+        bool bad = false;
+        void get(uint64_t* w, size_t cnt, bool pow) {
+            if (bad || pos + 8 * cnt > len) {
+                bad = true;
+                return;
+            }
+            std::memcpy(w, bytes + pos, 8 * cnt);
+            for (size_t i = 0; i < cnt && !pow; ++i)
+                if (w[i] >= gl::P) bad = true;  // non-canonical field element
+            pos += 8 * cnt;
         }
-        std::memcpy(w, bytes + pos, 8 * cnt);
-        for (size_t i = 0; i < cnt; ++i)
-            if (w[i] >= gl::P) bad = true;  // non-canonical field element
-        pos += 8 * cnt;
-    };
-    auto expect_u8 = [&](unsigned v) {
-        if (bad || pos + 1 > len || bytes[pos] != (uint8_t)v) bad = true;
-        ++pos;
-    };
-    const size_t cap_words = (size_t)4 << in->cap_height;
-    const size_t n_cs = in->n_constants_sigmas, nc = in->num_challenges;
-    get_words(caps, 3 * cap_words);
-    uint64_t* cs = openings;
-    uint64_t* wires = cs + 2 * n_cs;
-    uint64_t* zs_pp = wires + 2 * (size_t)in->n_wires;
-    uint64_t* quot = zs_pp + 2 * (size_t)in->n_zs_partial_products;
-    uint64_t* zs_next = quot + 2 * (size_t)in->n_quotient;
-    get_words(cs, 2 * (size_t)in->n_constants);
-    get_words(cs + 2 * (size_t)in->n_constants, 2 * (n_cs - in->n_constants));
-    get_words(wires, 2 * (size_t)in->n_wires);
-    get_words(zs_pp, 2 * nc);
-    get_words(zs_next, 2 * nc);
-    get_words(zs_pp + 2 * nc, 2 * (size_t)(in->n_zs_partial_products - nc));
-    get_words(quot, 2 * (size_t)in->n_quotient);
-    uint64_t* w = fri;
-    const size_t n_rounds = fp.reduction_arity_bits.size();
-    get_words(w, n_rounds * cap_words);
-    w += n_rounds * cap_words;
-    const unsigned log_lde = fp.lde_bits();
-    const size_t oracle_cols[4] = {n_cs, in->n_wires, in->n_zs_partial_products, in->n_quotient};
-    for (unsigned q = 0; q < fp.config.num_query_rounds && !bad; ++q) {
-        for (size_t o = 0; o < 4; ++o) {
-            const unsigned nsib = log_lde - fp.config.cap_height;
-            get_words(w, oracle_cols[o]);
-            w += oracle_cols[o];
-            expect_u8(nsib);
-            get_words(w, 4 * (size_t)nsib);
-            w += 4 * (size_t)nsib;
+        void words(uint32_t dest, size_t cnt, bool pow) { get(to.at(S, dest), cnt, pow); }
+        void length_byte(unsigned nsib) {
+            if (bad || pos + 1 > len || bytes[pos] != (uint8_t)nsib) bad = true;
+            ++pos;
         }
-        unsigned lg = log_lde;
-        for (unsigned ab : fp.reduction_arity_bits) {
-            lg -= ab;
-            const unsigned nsib = lg - fp.config.cap_height;
-            get_words(w, (size_t)2 << ab);
-            w += (size_t)2 << ab;
-            expect_u8(nsib);
-            get_words(w, 4 * (size_t)nsib);
-            w += 4 * (size_t)nsib;
-        }
-    }
-    const size_t final_words = (size_t)2 << fp.final_poly_bits();
-    get_words(w, final_words);
-    if (!bad && pos + 8 <= len) {  // pow_witness: a plain u64, not a field element
-        std::memcpy(w + final_words, bytes + pos, 8);
-        pos += 8;
-    } else {
-        bad = true;
-    }
+    } rd{S, bytes, len, {caps, openings, fri}};
+    vpbs::walk_step_proof(S, rd);
     uint64_t n_pi = 0;
-    const bool pi_prefix = in->compat ? in->compat->bytes_pi_len_prefix != 0 : true;   // the switch table of include/vpbs_prover.h
-    if (!pi_prefix) {   // older layout: the public inputs run to the end of the buffer
-        if (!bad && (len - pos) % 8 == 0) n_pi = (len - pos) / 8;
-        else bad = true;
-    } else if (!bad && pos + 8 <= len) {
-        std::memcpy(&n_pi, bytes + pos, 8);
-        pos += 8;
+    if (!S.pi_prefix) {   // older layout: the public inputs run to the end of the buffer
+        if (!rd.bad && (len - rd.pos) % 8 == 0) n_pi = (len - rd.pos) / 8;
+        else rd.bad = true;
     } else {
-        bad = true;
+        rd.get(&n_pi, 1, true);
     }
-    if (bad || n_pi > public_inputs_capacity || (n_pi && !public_inputs_out)) return VPBS_ERR_INVALID;
-    get_words(public_inputs_out, (size_t)n_pi);
-    if (bad || pos != len) return VPBS_ERR_INVALID;
+    if (rd.bad || n_pi > public_inputs_capacity || (n_pi && !public_inputs_out)) return VPBS_ERR_INVALID;
+    rd.get(public_inputs_out, (size_t)n_pi, false);
+    if (rd.bad || rd.pos != len) return VPBS_ERR_INVALID;
     return (long)n_pi;
 }
 

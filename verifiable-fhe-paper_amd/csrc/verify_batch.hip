@@ -1,9 +1,12 @@
 // Batch verifier of serialised step proofs on the device: vpbs_step_proof_from_bytes + vpbs_verify_step (verifier.hip) for many
-// ProofWithPublicInputs byte strings at once, with the host's verdict for every one of them.
+// ProofWithPublicInputs byte strings at once, with the host's verdict for every one of them.  The two verifiers share what a verdict rests
+// on: the proof's shape, the refusal rules and the serialised order (proof_shape.h), the vanishing identity and the arithmetic of a FRI
+// query (verify_core.h).  This file owns how the work is spread over lanes: the gather, the 16-lane challenger, the per-gate evaluation,
+// the Merkle climbs and the flags.
 //
 // Layout (made once, at vpbs_proof_verifier_create, from the circuit's shape):
-//   src   [n_fixed]: for every word of a proof in the host verifier's arrays (caps [3][cap] | openings | fri, the order
-//                    vpbs_step_proof_from_bytes writes them), its byte offset in the serialised proof -- the parser's walk, replayed once;
+//   src   [n_fixed]: for every word of a proof in the unified order caps [3][cap] | openings | fri, its byte offset in the serialised
+//                    proof -- walk_step_proof, recorded once;
 //   lenb  [..]:      byte offset and expected value of every Merkle-path length byte;
 //   the constants/sigmas cap, the gates and the CosetTables of gates::coset_tables.
 // Per proof the device keeps its words (stride W: the fixed words, then max_public_inputs public inputs), a challenge block and a flag word.
@@ -31,7 +34,10 @@
 #include "poseidon.h"
 #include "gates.h"
 #include "context.h"
+#include "proof_shape.h"
+#include "test_entries.h"
 #include "verify_batch.h"
+#include "verify_core.h"
 
 namespace {
 using vpbs::DeviceError;
@@ -41,22 +47,12 @@ using u64 = uint64_t;
 
 constexpr u32 F_MALFORMED = 1, F_VANISHING = 2, F_POW = 4, F_FRI = 8, F_MERKLE = 16;
 constexpr unsigned NC_MAX = 4;        // challenges per proof the device path carries in registers
-constexpr unsigned ROUNDS_MAX = 8;    // FRI reduction rounds (log_n + rate_bits <= 24 with arity 16: at most 5)
 constexpr unsigned MAX_BATCH = 65535;
 
-// the shape every kernel reads (passed by value)
-struct Shape {
-    u32 W;                        // words per proof
-    u32 n_fixed;                  // words before the public inputs = o_pi
-    u32 o_open, o_fri, fri_total;
-    u32 fixed_len;                // bytes up to and including the PoW witness
+// the shape every kernel reads (passed by value): the proof's, and the slots the device keeps per proof
+struct Shape : vpbs::ProofShape {
+    u32 W;                        // words per proof: n_fixed, then max_pi public inputs
     u32 n_lenb, max_pi;
-    int pi_prefix, fri_only, mul_final_by_x;
-    u32 cap_words, cap_height, nc, n_open_words, total_cols;
-    u32 n_cs, n_wires, n_zs, n_quot, n_constants, n_routed, deg, num_selectors, n_gates;
-    u32 log_n, log_lde, rate_bits, pow_bits, nq, n_rounds, final_len;
-    u32 ab[ROUNDS_MAX], nsib_r[ROUNDS_MAX], off_r[ROUNDS_MAX];
-    u32 off_o[4], ncols[4], nsib0, query_words, o_queries;
     u32 CH;                       // words of a challenge block
     u64 digest[4];
 };
@@ -258,7 +254,7 @@ __global__ __launch_bounds__(64) void vb_gates(const u64* __restrict__ words, co
     const u64* open = words + (u64)i * S.W + S.o_open;
     const u64* ch = chal + (u64)i * S.CH;
     const vpbs_gate g = gate_list[gi];
-    const DevVars v{open + 2 * (u64)S.n_cs, open + 2 * (u64)S.num_selectors, S.n_wires, S.n_constants - S.num_selectors, ch};
+    const DevVars v{open + 2 * (u64)S.ncols[0], open + 2 * (u64)S.num_selectors, S.ncols[1], S.n_constants - S.num_selectors, ch};
     AlphaSink s;
     s.nc = S.nc;
 #pragma unroll
@@ -278,149 +274,44 @@ __global__ __launch_bounds__(64) void vb_gates(const u64* __restrict__ words, co
     }
 }
 
-// the vanishing identity at zeta (check_permutation_identity of verifier.hip): one lane per proof
-__device__ __forceinline__ Ext ext_at(const u64* p, u64 i) { return Ext{p[2 * i], p[2 * i + 1]}; }
-
+// the vanishing identity at zeta: one lane per proof, the gate terms of a challenge summed over the per-gate partials of vb_gates
 __global__ __launch_bounds__(64) void vb_vanishing(const u64* __restrict__ words, const u64* __restrict__ chal, const u64* __restrict__ gterms,
                                                    Shape S, u32 count, u32* __restrict__ flags) {
     const u32 i = blockIdx.x * 64 + threadIdx.x;
     if (i >= count) return;
     const u64* open = words + (u64)i * S.W + S.o_open;
     const u64* ch = chal + (u64)i * S.CH;
-    const unsigned nc = S.nc, n_routed = S.n_routed, deg = S.deg;
-    const unsigned n_chunks = (n_routed + deg - 1) / deg, num_prods = n_chunks - 1;
-    const u64* cs_z = open;
-    const u64* wires_z = cs_z + 2 * (u64)S.n_cs;
-    const u64* zs_pp_z = wires_z + 2 * (u64)S.n_wires;
-    const u64* quot_z = zs_pp_z + 2 * (u64)S.n_zs;
-    const u64* zs_next_z = quot_z + 2 * (u64)S.n_quot;
-    const u64* sig_z = cs_z + 2 * (u64)S.n_constants;
-    const u64* pps_z = zs_pp_z + 2 * (u64)nc;
-    const Ext zeta = ext_at(ch + ch_zeta(S), 0);
-    Ext zeta_n = zeta;
-    for (unsigned k = 0; k < S.log_n; ++k) zeta_n = gl::mul(zeta_n, zeta_n);
-    const Ext one = gl::ext(1);
-    const Ext z_h = gl::sub(zeta_n, one);
-    const Ext l0 = gl::mul(z_h, gl::inv(gl::mul(gl::sub(zeta, one), (u64)1 << S.log_n)));
-    const unsigned chunks_per = 1u << S.rate_bits;
+    const Ext zeta = vpbs::ext_at(ch + ch_zeta(S), 0);
+    const vpbs::ZetaTerms zt = vpbs::zeta_terms(S, zeta);
     bool ok = true;
-    for (unsigned a = 0; a < nc; ++a) {
-        const u64 alpha = ch[ch_alphas(S) + a];
-        // reduce_with_powers(terms, alpha) with the gate terms as the initial accumulator: gt alpha^T + sum_t alpha^t terms[t]
-        Ext sum = gl::ext(0);
-        u64 apow = 1;
-        for (unsigned c = 0; c < nc; ++c) {
-            sum = gl::add(sum, gl::mul(gl::mul(l0, gl::sub(ext_at(zs_pp_z, c), one)), apow));
-            apow = gl::mul(apow, alpha);
-        }
-        for (unsigned c = 0; c < nc; ++c) {
-            const u64 beta = ch[ch_betas(S) + c], gamma = ch[ch_gammas(S) + c];
-            const Ext g = gl::ext(gamma);
-            u64 k = 1;
-            for (unsigned kk = 0; kk < n_chunks; ++kk) {
-                Ext num = one, den = one;
-                for (unsigned j = kk * deg; j < (kk + 1) * deg && j < n_routed; ++j) {
-                    const Ext wj = ext_at(wires_z, j);
-                    num = gl::mul(num, gl::add(gl::add(wj, gl::mul(zeta, gl::mul(beta, k))), g));
-                    den = gl::mul(den, gl::add(gl::add(wj, gl::mul(ext_at(sig_z, j), beta)), g));
-                    k = gl::mul(k, gl::GENERATOR);
-                }
-                const Ext prev = kk == 0 ? ext_at(zs_pp_z, c) : ext_at(pps_z, c * num_prods + kk - 1);
-                const Ext next = kk == num_prods ? ext_at(zs_next_z, c) : ext_at(pps_z, c * num_prods + kk);
-                sum = gl::add(sum, gl::mul(gl::sub(gl::mul(prev, num), gl::mul(next, den)), apow));
-                apow = gl::mul(apow, alpha);
-            }
-        }
-        Ext gt = gl::ext(0);
-        if (S.n_gates) {
-            const u64* t = gterms + (u64)i * S.n_gates * 2 * nc;
-            for (unsigned g = 0; g < S.n_gates; ++g) gt = gl::add(gt, ext_at(t + (u64)g * 2 * nc, a));
-        }
-        const Ext acc = gl::add(sum, gl::mul(gt, apow));
-        Ext q = gl::ext(0);
-        for (unsigned m = chunks_per; m-- > 0;) q = gl::add(gl::mul(q, zeta_n), ext_at(quot_z, a * chunks_per + m));
-        if (!gl::eq(acc, gl::mul(z_h, q))) ok = false;
+    for (unsigned a = 0; a < S.nc; ++a) {
+        const auto gate_term = [&] {   // the sum over the per-gate partials of vb_gates: [proof][gate][challenge][2]
+            Ext gt = gl::ext(0);
+            const u64* t = gterms + (u64)i * S.n_gates * 2 * S.nc;
+            for (unsigned g = 0; g < S.n_gates; ++g) gt = gl::add(gt, vpbs::ext_at(t + (u64)g * 2 * S.nc, a));
+            return gt;
+        };
+        if (!vpbs::vanishing_holds(S, open, a, ch[ch_alphas(S) + a], ch + ch_betas(S), zeta, zt, gate_term)) ok = false;
     }
     if (!ok) atomicOr(&flags[i], F_VANISHING);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------------
 // FRI query rounds: one lane per (proof, query)
-__device__ __forceinline__ u32 bitrev_n(u32 x, unsigned bits) { return bits ? __builtin_bitreverse32(x) >> (32 - bits) : 0; }
-
 __global__ __launch_bounds__(64) void vb_fri(const u64* __restrict__ words, const u64* __restrict__ chal, Shape S, u32 count,
                                              u32* __restrict__ flags) {
     const u64 t = (u64)blockIdx.x * 64 + threadIdx.x;
     if (t >= (u64)count * S.nq) return;
     const u32 i = (u32)(t / S.nq), q = (u32)(t % S.nq);
     const u64* w = words + (u64)i * S.W;
-    const u64* open = w + S.o_open;
     const u64* ch = chal + (u64)i * S.CH;
-    const Ext zeta = ext_at(ch + ch_zeta(S), 0), fri_alpha = ext_at(ch + ch_fri_alpha(S), 0);
-    const Ext zeta_next = gl::mul(zeta, gl::root_of_unity(S.log_n));
-    Ext reduced0 = gl::ext(0), reduced1 = gl::ext(0);
-    for (u32 j = S.total_cols; j-- > 0;) reduced0 = gl::add(gl::mul(reduced0, fri_alpha), ext_at(open, j));
-    for (u32 j = S.nc; j-- > 0;) reduced1 = gl::add(gl::mul(reduced1, fri_alpha), ext_at(open, S.total_cols + j));
-    u32 x_index = (u32)ch[ch_xq(S) + q];
+    const Ext zeta = vpbs::ext_at(ch + ch_zeta(S), 0), fri_alpha = vpbs::ext_at(ch + ch_fri_alpha(S), 0);
+    Ext reduced0, reduced1;
+    vpbs::reduced_openings(S, w + S.o_open, fri_alpha, reduced0, reduced1);
     const u64* qw = w + S.o_fri + S.o_queries + (u64)q * S.query_words;
-    u64 subgroup_x = gl::mul(gl::GENERATOR, gl::pow(gl::root_of_unity(S.log_lde), bitrev_n(x_index, S.log_lde)));
-    Ext sum;
-    {
-        Ext acc = gl::ext(0), apow = gl::ext(1);
-        for (u32 o = 0; o < 4; ++o) {
-            const u64* leaf = qw + S.off_o[o];
-            for (u32 p = 0; p < S.ncols[o]; ++p) {
-                acc = gl::add(acc, gl::mul(apow, leaf[p]));
-                apow = gl::mul(apow, fri_alpha);
-            }
-        }
-        sum = gl::mul(gl::sub(acc, reduced0), gl::inv(gl::sub(gl::ext(subgroup_x), zeta)));
-        acc = gl::ext(0);
-        apow = gl::ext(1);
-        const u64* leaf2 = qw + S.off_o[2];
-        for (u32 p = 0; p < S.nc; ++p) {
-            acc = gl::add(acc, gl::mul(apow, leaf2[p]));
-            apow = gl::mul(apow, fri_alpha);
-        }
-        sum = gl::add(gl::mul(sum, apow), gl::mul(gl::sub(acc, reduced1), gl::inv(gl::sub(gl::ext(subgroup_x), zeta_next))));
-        if (S.mul_final_by_x) sum = gl::mul(sum, subgroup_x);
-    }
-    Ext old_eval = sum;
-    bool ok = true;
-    for (u32 r = 0; r < S.n_rounds; ++r) {
-        const unsigned ab = S.ab[r];
-        const u32 arity = 1u << ab;
-        const u64* evals = qw + S.off_r[r];
-        const u32 coset_index = x_index >> ab, within = x_index & (arity - 1);
-        if (evals[2 * within] != old_eval.c0 || evals[2 * within + 1] != old_eval.c1) ok = false;
-        // compute_evaluation: interpolate {(coset_start g^i, evals[bitrev(i)])} at beta
-        const u64 g = gl::root_of_unity(ab);
-        const u64 coset_start = gl::mul(subgroup_x, gl::pow(g, arity - bitrev_n(within, ab)));
-        const Ext beta = ext_at(ch + ch_fri_betas(S), r);
-        Ext res = gl::ext(0);
-        u64 xi = coset_start;
-        for (u32 a = 0; a < arity; ++a) {
-            Ext num = ext_at(evals, bitrev_n(a, ab));
-            u64 den = 1, xj = coset_start;
-            for (u32 b = 0; b < arity; ++b) {
-                if (b != a) {
-                    num = gl::mul(num, gl::sub(beta, gl::ext(xj)));
-                    den = gl::mul(den, gl::sub(xi, xj));
-                }
-                xj = gl::mul(xj, g);
-            }
-            res = gl::add(res, gl::mul(num, gl::inv(den)));
-            xi = gl::mul(xi, g);
-        }
-        old_eval = res;
-        for (unsigned k = 0; k < ab; ++k) subgroup_x = gl::mul(subgroup_x, subgroup_x);
-        x_index = coset_index;
-    }
     const u64* fin = w + S.o_fri + S.fri_total - 1 - 2 * S.final_len;
-    Ext acc = gl::ext(0);
-    for (u32 k = S.final_len; k-- > 0;) acc = gl::add(gl::mul(acc, subgroup_x), ext_at(fin, k));
-    if (!gl::eq(acc, old_eval)) ok = false;
-    if (!ok) atomicOr(&flags[i], F_FRI);
+    if (!vpbs::fri_query_holds(S, reduced0, reduced1, qw, fin, (u32)ch[ch_xq(S) + q], zeta, fri_alpha, ch + ch_fri_betas(S)))
+        atomicOr(&flags[i], F_FRI);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------------
@@ -511,6 +402,34 @@ void report(char* err, size_t err_len, const std::string& m) {
         err[err_len - 1] = 0;
     }
 }
+
+// walk_step_proof, recorded once: for every word of the unified order its byte offset in a serialised proof, and the offset and expected
+// value of every Merkle-path length byte
+struct ByteTables {
+    std::vector<u32> src, lenb_off;
+    std::vector<uint8_t> lenb_val;
+    size_t pos = 0, n_words = 0;
+    void words(u32 dest, size_t cnt, bool) {
+        for (size_t k = 0; k < cnt; ++k) src[dest + k] = (u32)(pos + 8 * k);
+        pos += 8 * cnt;
+        n_words += cnt;
+    }
+    void length_byte(unsigned nsib) {
+        lenb_off.push_back((u32)pos);
+        lenb_val.push_back((uint8_t)nsib);
+        ++pos;
+    }
+    const char* record(const vpbs::ProofShape& S) {   // -> NULL, or which self-check of the layout failed
+        src.assign(S.n_fixed, ~0u);
+        vpbs::walk_step_proof(S, *this);
+        plonky2::FriParams fp = plonky2::FriParams::standard(S.log_n, S.rate_bits, S.cap_height);
+        if (n_words != S.n_fixed || pos != S.fixed_len || S.fri_total != plonky2::fri_proof_words(fp, {S.ncols[0], S.ncols[1], S.ncols[2], S.ncols[3]}))
+            return "proof layout does not match the FRI proof size";
+        for (u32 s : src)
+            if (s == ~0u) return "proof layout leaves a word unset";
+        return nullptr;
+    }
+};
 }  // namespace
 
 struct vpbs_proof_verifier {
@@ -551,7 +470,6 @@ struct vpbs_proof_verifier {
 extern "C" {
 int vpbs_proof_verifier_create(vpbs_ctx* ctx, const vpbs_verify_inputs* in, size_t max_batch, size_t max_public_inputs,
                                vpbs_proof_verifier** out, char* err, size_t err_len) {
-    using namespace plonky2;
     if (out) *out = nullptr;
     auto refuse = [&](const char* m) {
         report(err, err_len, m);
@@ -560,143 +478,24 @@ int vpbs_proof_verifier_create(vpbs_ctx* ctx, const vpbs_verify_inputs* in, size
     if (!ctx || !in || !out || !in->constants_sigmas_cap) return refuse("null argument");
     if (max_batch == 0 || max_batch > MAX_BATCH) return refuse("max_batch must be 1 .. 65535");
     if (max_public_inputs > (1u << 24)) return refuse("max_public_inputs above 2^24");
-    // what vpbs_step_proof_from_bytes and vpbs_verify_step refuse
-    if (in->n_constants > in->n_constants_sigmas || in->num_challenges > in->n_zs_partial_products) return refuse("malformed circuit description");
-    if (in->rate_bits > 3 || in->cap_height > 8 || in->log_n == 0 || in->log_n + in->rate_bits > 24 || in->num_challenges == 0)
-        return refuse("malformed circuit description (log_n, rate_bits, cap_height, num_challenges)");
-    if (in->num_challenges > NC_MAX) return refuse("the device verifier carries at most 4 challenges");
-    const bool has_gates = in->gates && in->n_gates;
-    if (in->gate_terms_zeta && !has_gates) return refuse("gate_terms_zeta without gates: a batch of proofs has one zeta per proof");
-    if (!in->fri_only) {
-        const unsigned deg = in->quotient_degree_factor;
-        if (deg == 0 || in->n_routed == 0 || in->n_routed > in->n_wires || in->n_constants + in->n_routed > in->n_constants_sigmas ||
-            in->n_zs_partial_products != in->num_challenges * ((in->n_routed + deg - 1) / deg) ||
-            in->n_quotient != (in->num_challenges << in->rate_bits))
-            return refuse("malformed circuit description (permutation argument shape)");
-        if (has_gates) {
-            if (in->num_selectors > in->n_constants) return refuse("more selectors than constants columns");
-            try {
-                vpbs::validate_gates(in->gates, in->n_gates, in->num_selectors, in->n_constants, in->n_wires);
-            } catch (const DeviceError& e) {
-                return refuse(e.what.c_str());
-            }
-        }
-    }
-    const FriParams fp = FriParams::standard(in->log_n, in->rate_bits, in->cap_height);
-    if (!fp.caps_fit()) return refuse("cap taller than a Merkle tree of the proof");
-    if (fp.reduction_arity_bits.size() > ROUNDS_MAX) return refuse("too many FRI rounds");
-    vpbs_compat compat;
-    vpbs_compat_default(&compat);
-    if (in->compat) compat = *in->compat;
-
+    // what vpbs_step_proof_from_bytes and vpbs_verify_step refuse.  The device's own two limits go in as a callback and not in front of the
+    // call on purpose: a description that breaks several rules is then refused with the message this entry has always given first
     Shape S{};
-    const size_t cap_words = (size_t)4 << in->cap_height, nc = in->num_challenges;
-    const size_t ncols[4] = {in->n_constants_sigmas, in->n_wires, in->n_zs_partial_products, in->n_quotient};
-    const size_t total_cols = ncols[0] + ncols[1] + ncols[2] + ncols[3];
-    const size_t n_open_words = 2 * (total_cols + nc);
-    const size_t fri_total = fri_proof_words(fp, {ncols[0], ncols[1], ncols[2], ncols[3]});
-    const size_t o_open = 3 * cap_words, o_fri = o_open + n_open_words, n_fixed = o_fri + fri_total;
-    // the parser's walk (vpbs_step_proof_from_bytes), replayed once: destination word -> byte offset
-    std::vector<u32> src(n_fixed, ~0u), lenb_off;
-    std::vector<uint8_t> lenb_val;
-    size_t pos = 0;
-    auto get = [&](size_t dest, size_t cnt) {
-        for (size_t k = 0; k < cnt; ++k) src[dest + k] = (u32)(pos + 8 * k);
-        pos += 8 * cnt;
-    };
-    auto u8 = [&](unsigned v) {
-        lenb_off.push_back((u32)pos);
-        lenb_val.push_back((uint8_t)v);
-        ++pos;
-    };
-    get(0, 3 * cap_words);
-    const size_t cs = o_open, wires = cs + 2 * ncols[0], zs_pp = wires + 2 * ncols[1], quot = zs_pp + 2 * ncols[2], zs_next = quot + 2 * ncols[3];
-    get(cs, 2 * (size_t)in->n_constants);
-    get(cs + 2 * (size_t)in->n_constants, 2 * (ncols[0] - in->n_constants));
-    get(wires, 2 * ncols[1]);
-    get(zs_pp, 2 * nc);
-    get(zs_next, 2 * nc);
-    get(zs_pp + 2 * nc, 2 * (ncols[2] - nc));
-    get(quot, 2 * ncols[3]);
-    size_t w = o_fri;
-    const size_t n_rounds = fp.reduction_arity_bits.size();
-    get(w, n_rounds * cap_words);
-    w += n_rounds * cap_words;
-    S.o_queries = (u32)(w - o_fri);
-    const unsigned log_lde = fp.lde_bits();
-    for (unsigned q = 0; q < fp.config.num_query_rounds; ++q) {
-        const size_t qstart = w;
-        for (size_t o = 0; o < 4; ++o) {
-            const unsigned nsib = log_lde - fp.config.cap_height;
-            if (q == 0) S.off_o[o] = (u32)(w - qstart);
-            get(w, ncols[o]);
-            w += ncols[o];
-            u8(nsib);
-            get(w, 4 * (size_t)nsib);
-            w += 4 * (size_t)nsib;
-            S.nsib0 = nsib;
-        }
-        unsigned lg = log_lde;
-        for (size_t r = 0; r < n_rounds; ++r) {
-            const unsigned ab = fp.reduction_arity_bits[r];
-            lg -= ab;
-            const unsigned nsib = lg - fp.config.cap_height;
-            if (q == 0) {
-                S.off_r[r] = (u32)(w - qstart);
-                S.ab[r] = ab;
-                S.nsib_r[r] = nsib;
-            }
-            get(w, (size_t)2 << ab);
-            w += (size_t)2 << ab;
-            u8(nsib);
-            get(w, 4 * (size_t)nsib);
-            w += 4 * (size_t)nsib;
-        }
-        if (q == 0) S.query_words = (u32)(w - qstart);
-    }
-    const size_t final_words = (size_t)2 << fp.final_poly_bits();
-    get(w, final_words);
-    w += final_words;
-    get(w, 1);   // the PoW witness
-    ++w;
-    if (w != n_fixed || pos > 0xFFFFFFF0u) return refuse("proof layout does not match the FRI proof size");
-    for (u32 s : src)
-        if (s == ~0u) return refuse("proof layout leaves a word unset");
+    std::string why;
+    const bool fits = vpbs::make_proof_shape(*in, vpbs::compat_of(*in), vpbs::SHAPE_PARSE | vpbs::SHAPE_VERIFY, S, &why, [&]() -> const char* {
+        if (in->num_challenges > NC_MAX) return "the device verifier carries at most 4 challenges";
+        if (in->gate_terms_zeta && !(in->gates && in->n_gates)) return "gate_terms_zeta without gates: a batch of proofs has one zeta per proof";
+        return nullptr;
+    });
+    if (!fits) return refuse(why.c_str());
+    ByteTables tab;
+    if (const char* m = tab.record(S)) return refuse(m);
+    const size_t cap_words = S.cap_words, nc = S.nc;
 
-    S.n_fixed = (u32)n_fixed;
     S.max_pi = (u32)max_public_inputs;
-    S.W = (u32)((n_fixed + max_public_inputs + 1) & ~(size_t)1);
-    S.o_open = (u32)o_open;
-    S.o_fri = (u32)o_fri;
-    S.fri_total = (u32)fri_total;
-    S.fixed_len = (u32)pos;
-    S.n_lenb = (u32)lenb_off.size();
-    S.pi_prefix = compat.bytes_pi_len_prefix != 0;
-    S.fri_only = in->fri_only != 0;
-    S.mul_final_by_x = compat.fri_mul_final_by_x != 0;
-    S.cap_words = (u32)cap_words;
-    S.cap_height = in->cap_height;
-    S.nc = (u32)nc;
-    S.n_open_words = (u32)n_open_words;
-    S.total_cols = (u32)total_cols;
-    S.n_cs = (u32)ncols[0];
-    S.n_wires = (u32)ncols[1];
-    S.n_zs = (u32)ncols[2];
-    S.n_quot = (u32)ncols[3];
-    S.n_constants = in->n_constants;
-    S.n_routed = in->n_routed;
-    S.deg = in->quotient_degree_factor;
-    S.num_selectors = has_gates ? in->num_selectors : 0;
-    S.n_gates = (!in->fri_only && has_gates) ? in->n_gates : 0;
-    S.log_n = in->log_n;
-    S.log_lde = log_lde;
-    S.rate_bits = in->rate_bits;
-    S.pow_bits = fp.config.proof_of_work_bits;
-    S.nq = fp.config.num_query_rounds;
-    S.n_rounds = (u32)n_rounds;
-    S.final_len = (u32)(final_words / 2);
-    for (int o = 0; o < 4; ++o) S.ncols[o] = (u32)ncols[o];
-    S.CH = (u32)(8 + 3 * nc + 2 * n_rounds + S.nq);
+    S.W = (u32)((S.n_fixed + max_public_inputs + 1) & ~(size_t)1);
+    S.n_lenb = (u32)tab.lenb_off.size();
+    S.CH = (u32)(8 + 3 * nc + 2 * S.n_rounds + S.nq);
     for (int k = 0; k < 4; ++k) S.digest[k] = in->circuit_digest[k];
 
     auto* v = new vpbs_proof_verifier;
@@ -705,9 +504,9 @@ int vpbs_proof_verifier_create(vpbs_ctx* ctx, const vpbs_verify_inputs* in, size
     v->max_batch = max_batch;
     try {
         VPBS_HIP(hipSetDevice(ctx->device));
-        v->d_src = v->upload(src.data(), src.size());
-        v->d_lenb_off = v->upload(lenb_off.data(), lenb_off.size());
-        v->d_lenb_val = v->upload(lenb_val.data(), lenb_val.size());
+        v->d_src = v->upload(tab.src.data(), tab.src.size());
+        v->d_lenb_off = v->upload(tab.lenb_off.data(), tab.lenb_off.size());
+        v->d_lenb_val = v->upload(tab.lenb_val.data(), tab.lenb_val.size());
         v->d_cs_cap = v->upload(in->constants_sigmas_cap, cap_words);
         if (S.n_gates) {
             v->d_gates = v->upload(in->gates, in->n_gates);
@@ -831,3 +630,20 @@ long vpbs_proof_verifier_run(vpbs_proof_verifier* v, const uint8_t* bytes, const
     return accepted;
 }
 }  // extern "C"
+
+// test_entries.h: the byte tables of a shape, on the host
+extern "C" long vpbs_test_proof_byte_tables(const vpbs_verify_inputs* in, size_t src_capacity, size_t lenb_capacity, uint32_t* src, uint32_t* lenb_off,
+                                            uint8_t* lenb_val, size_t* n_src, size_t* n_lenb) {
+    vpbs::ProofShape S;
+    ByteTables tab;
+    if (!in || !src || !lenb_off || !lenb_val || !n_src || !n_lenb || !vpbs::make_proof_shape(*in, vpbs::compat_of(*in), vpbs::SHAPE_PARSE, S) ||
+        tab.record(S))
+        return VPBS_ERR_INVALID;
+    *n_src = tab.src.size();
+    *n_lenb = tab.lenb_off.size();
+    if (tab.src.size() > src_capacity || tab.lenb_off.size() > lenb_capacity) return VPBS_ERR_INVALID;
+    std::memcpy(src, tab.src.data(), 4 * tab.src.size());
+    std::memcpy(lenb_off, tab.lenb_off.data(), 4 * tab.lenb_off.size());
+    std::memcpy(lenb_val, tab.lenb_val.data(), tab.lenb_val.size());
+    return (long)tab.pos;
+}
