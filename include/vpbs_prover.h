@@ -964,6 +964,50 @@ int vpbs_lwe_extract(vpbs_ctx* ctx, unsigned log_N, unsigned K, unsigned n_lwe, 
                      int on_device);
 int vpbs_lwe_decrypt(const uint64_t* s_lwe, const uint64_t* ct, unsigned n_lwe, uint64_t* m_out);
 
+/* ---- the client side in batches: encrypt, lookup-table test vectors, decode with noise statistics (csrc/lwe_client.hip) ----
+ * A call that takes a ctx runs on the host when ctx is NULL (then every pointer is a host array and the device flags must be 0).  With a
+ * context the work goes on its stream and the call returns when the outputs are where the caller asked for them.  VPBS_ERR_INVALID refusals
+ * launch nothing and, with a context, leave a text in vpbs_last_error that names the first offending index.
+ *
+ * vpbs_lwe_encrypt_batch: row i of cts_out [count][n_lwe + 1] is word for word vpbs_lwe_encrypt(params, s_lwe, messages[i], nonce0 + i).
+ *   s_lwe [n_lwe] is a device pointer when key_on_device != 0; messages [count] and cts_out are device pointers when on_device != 0.
+ *   Refused: a message at or above p (found on the device when the messages live there; rows before it may have been written), nonce0 + count
+ *   above 2^24, null pointers, parameters vpbs_lwe_encrypt refuses.
+ *
+ * vpbs_lut_testv (host): vpbs_testv with block i of N / p coefficients holding table[i] * delta (in the field) instead of i * delta, then the
+ *   same left_shift(block / 2) with negated wrap-around; table[i] = i with delta = get_delta(2 p) IS vpbs_testv.  Refused: table[i] >= 2 p,
+ *   p not a power of two, p > N, null pointers.  Negacyclic consequence: the bootstrap of a message m in [0, p) yields table[m] * delta, and
+ *   of a message in [p, 2 p) the NEGATED entry, -table[m - p] * delta -- a table over all of [0, 2 p) must satisfy t[m + p] = -t[m].
+ *
+ * vpbs_lwe_decode_batch: cts [count][n_lwe + 1]; expected [count] or NULL; any of phase_out, msg_out, err_out [count] may be NULL.  In integers:
+ *   phase_i = what vpbs_lwe_decrypt returns for row i: body - <s, mask> with every word of the row and of the key reduced below p first
+ *   msg_i   = floor((phase_i + floor(delta / 2)) / delta) mod modulus             (a sum of up to 65 bits)
+ *   ref_i   = expected_i when expected is given, else msg_i
+ *   err_i   = (phase_i - ref_i * delta) mod p, centred into (-p/2, p/2], stored as a two's-complement word
+ *   failure:  expected given and msg_i != expected_i mod modulus
+ *   where: VPBS_DECODE_HOST all pointers host; VPBS_DECODE_DEVICE cts, expected and the three outputs device; VPBS_DECODE_OUTPUTS_TO_HOST cts and
+ *   expected device, the outputs host (8 bytes per ciphertext and output come back instead of the ciphertexts).  s_lwe by key_on_device.
+ *   stats (a HOST struct in every mode, may be NULL) is ADDED to, so a survey over many calls accumulates into one struct; 608 bytes per call
+ *   come back for it.  Refused: null s_lwe / cts, n_lwe, delta or modulus 0, more than 2^31 ciphertexts in one call.
+ *
+ * vpbs_noise_stats: exact integers over the err_i of the calls so far, independent of the order of summation and hence the same on host and
+ * device: count; failures; max_abs = max |err|; sum_abs = sum |err| (128 bits, little-endian words); sum_sq = sum err^2 (192 bits);
+ * sum_signed = sum err (128 bits, two's complement); hist[k] = how many |err| have bit length k (hist[0]: err = 0).  Zero it before first use. */
+typedef struct {
+    uint64_t count, failures, max_abs;
+    uint64_t sum_abs[2];
+    uint64_t sum_sq[3];
+    uint64_t sum_signed[2];
+    uint64_t hist[65];
+} vpbs_noise_stats;
+typedef enum { VPBS_DECODE_HOST = 0, VPBS_DECODE_DEVICE = 1, VPBS_DECODE_OUTPUTS_TO_HOST = 2 } vpbs_decode_where;
+int vpbs_lwe_encrypt_batch(vpbs_ctx* ctx, const vpbs_keygen_params* params, const uint64_t* s_lwe, int key_on_device, const uint64_t* messages,
+                           size_t count, uint64_t nonce0, uint64_t* cts_out, int on_device);
+int vpbs_lut_testv(unsigned log_N, unsigned p, const uint64_t* table, uint64_t delta, uint64_t* testv);
+int vpbs_lwe_decode_batch(vpbs_ctx* ctx, const uint64_t* s_lwe, int key_on_device, const uint64_t* cts, size_t count, unsigned n_lwe, uint64_t delta,
+                          uint64_t modulus, const uint64_t* expected /* [count] or NULL */, uint64_t* phase_out, uint64_t* msg_out,
+                          uint64_t* err_out, vpbs_noise_stats* stats /* accumulated into, may be NULL */, int on_device /* vpbs_decode_where */);
+
 /* ---- proving the bootstraps of a batch under one resident key set (csrc/pbs_prove_batch.hip) ----
  * One object owns a key set in device memory and turns a batch of LWE ciphertexts into their bootstrapped outputs AND their vPBS proofs.
  *   create: `chains` vpbs_ivc objects, each on a context of its own, in the device-witness pipeline with `witness_batch` steps per batch

@@ -1,9 +1,11 @@
 """ctypes binding of include/vpbs_prover.h (libvpbs_hip.so).  No compute happens in Python."""
 import ctypes as C
 import json
+import math
 import os
 import subprocess
 import weakref
+from fractions import Fraction
 
 import numpy as np
 
@@ -151,6 +153,11 @@ class ProgramDescC(C.Structure):
 class KeygenParamsC(C.Structure):
     _fields_ = [("log_N", C.c_uint), ("K", C.c_uint), ("ELL", C.c_uint), ("LOGB", C.c_uint), ("n_lwe", C.c_uint), ("seed", C.c_uint64),
                 ("sigma_glwe", C.c_double), ("sigma_lwe", C.c_double)]
+
+
+class NoiseStatsC(C.Structure):
+    _fields_ = [("count", C.c_uint64), ("failures", C.c_uint64), ("max_abs", C.c_uint64), ("sum_abs", C.c_uint64 * 2), ("sum_sq", C.c_uint64 * 3),
+                ("sum_signed", C.c_uint64 * 2), ("hist", C.c_uint64 * 65)]
 
 
 class StepSizesC(C.Structure):
@@ -338,6 +345,9 @@ SIGNATURES = {
     "vpbs_program_free": (None, [_vp]),
     "vpbs_lwe_extract": (_i, [_vp, _ui, _ui, _ui, _vp, _sz, _vp, _i]),
     "vpbs_lwe_decrypt": (_i, [U64P, U64P, _ui, U64P]),
+    "vpbs_lwe_encrypt_batch": (_i, [_vp, C.POINTER(KeygenParamsC), _vp, _i, _vp, _sz, _u64, _vp, _i]),
+    "vpbs_lut_testv": (_i, [_ui, _ui, U64P, _u64, U64P]),
+    "vpbs_lwe_decode_batch": (_i, [_vp, _vp, _i, _vp, _sz, _ui, _u64, _u64, _vp, _vp, _vp, _vp, C.POINTER(NoiseStatsC), _i]),
     "vpbs_k_poseidon_batch": (_i, [_vp, U64P, _sz]),
     "vpbs_k_hash_rows": (_i, [_vp, U64P, _sz, _ui, U64P]),
     "vpbs_k_intt": (_i, [_vp, U64P, _ui, _ui, U64P]),
@@ -1344,6 +1354,162 @@ def lwe_decrypt(s_lwe, ct):
     return int(out[0]) if c.ndim == 1 else out
 
 
+def lut_testv(N, p, table, delta=None):
+    """vpbs_lut_testv: the test vector of a lookup table over [0, p): block i holds table[i] * delta (entries below 2 p; delta defaults to
+    get_delta(2 p), with which the identity table gives testv(N, p)).  A message in [p, 2 p) bootstraps to the NEGATED entry -> (testv [N], delta)"""
+    t = _u64(table).reshape(-1)
+    if t.size != p:
+        raise ValueError("lut_testv: the table must have p = %d entries" % p)
+    if delta is None:
+        d = np.zeros(1, np.uint64)
+        if lib().vpbs_testv(N.bit_length() - 1, p, None, _ptr(d)) != 0:
+            raise VpbsError("vpbs_lut_testv: bad arguments")
+        delta = int(d[0])
+    out = np.zeros(N, np.uint64)
+    if lib().vpbs_lut_testv(N.bit_length() - 1, p, _ptr(t), int(delta), _ptr(out)) != 0:
+        raise VpbsError("vpbs_lut_testv: bad arguments (p a power of two, p <= N, entries below 2 p)")
+    return out, int(delta)
+
+
+class NoiseStats:
+    """vpbs_noise_stats: exact integer statistics of the decoding errors err_i that lwe_decode_batch calls have added so far."""
+
+    def __init__(self):
+        self.c = NoiseStatsC()
+
+    @staticmethod
+    def _words(w, signed=False):
+        v = sum(int(x) << (64 * i) for i, x in enumerate(w))
+        return v - (1 << (64 * len(w))) if signed and v >> (64 * len(w) - 1) else v
+
+    count = property(lambda self: int(self.c.count))
+    failures = property(lambda self: int(self.c.failures))
+    max_abs = property(lambda self: int(self.c.max_abs))
+    sum_abs = property(lambda self: self._words(self.c.sum_abs))
+    sum_sq = property(lambda self: self._words(self.c.sum_sq))
+    sum_signed = property(lambda self: self._words(self.c.sum_signed, signed=True))
+    hist = property(lambda self: [int(x) for x in self.c.hist])
+
+    def mean(self):
+        return float(Fraction(self.sum_signed, self.count)) if self.count else 0.0
+
+    def mean_abs(self):
+        return float(Fraction(self.sum_abs, self.count)) if self.count else 0.0
+
+    def std(self):
+        """sqrt(E[err^2] - E[err]^2), the variance formed in exact rationals before the one rounding to a float"""
+        if not self.count:
+            return 0.0
+        return math.sqrt(Fraction(self.count * self.sum_sq - self.sum_signed ** 2, self.count ** 2))
+
+    def as_dict(self):
+        return {"count": self.count, "failures": self.failures, "max_abs": self.max_abs, "sum_abs": self.sum_abs, "sum_sq": self.sum_sq,
+                "sum_signed": self.sum_signed, "hist": self.hist}
+
+
+def _is_dev(x):
+    return isinstance(x, (int, np.integer))
+
+
+def _lwe_encrypt_batch(ctx, params, s_lwe, messages, nonce0, out_dev_ptr, count):
+    h = ctx.h if ctx is not None else None
+    n = int(params.n_lwe)
+    key = None if _is_dev(s_lwe) else _u64(s_lwe).reshape(-1)
+    if key is not None and key.size != n:
+        raise ValueError("lwe_encrypt_batch: the key must have n_lwe = %d words" % n)
+    msgs = None if _is_dev(messages) else _u64(messages).reshape(-1)
+    if msgs is None and (count is None or out_dev_ptr is None):
+        raise ValueError("lwe_encrypt_batch: messages on the device need count and out_dev_ptr")
+    count = msgs.size if msgs is not None else int(count)
+    keep = np.zeros(1, np.uint64)   # a valid pointer for an empty batch
+    pkey = int(s_lwe) if key is None else key.ctypes.data
+    tmp, out = None, None
+    try:
+        if out_dev_ptr is None:
+            out = np.zeros((count, n + 1), np.uint64)
+            pm, po, on_device = (msgs if count else keep).ctypes.data, (out if count else keep).ctypes.data, 0
+        else:
+            if msgs is not None:
+                tmp = ctx.device_upload_new(msgs if count else keep)
+            pm, po, on_device = (tmp if msgs is not None else int(messages)), int(out_dev_ptr), 1
+        rc = lib().vpbs_lwe_encrypt_batch(h, C.byref(params), pkey, 1 if key is None else 0, pm, count, int(nonce0), po, on_device)
+    finally:
+        if tmp is not None:
+            ctx.device_free(tmp)
+    if rc:
+        if h:
+            text = lib().vpbs_last_error(h).decode()
+        else:   # no context to hold the text: name the first offending index here
+            bad = np.nonzero(msgs >= np.uint64(P))[0]
+            text = ("message %d is not below p" % bad[0] if bad.size else
+                    "nonce0 + count exceeds 2^24" if int(nonce0) + count > 1 << 24 else "bad arguments")
+        raise VpbsError("vpbs_lwe_encrypt_batch: status %d: %s" % (rc, text))
+    return out
+
+
+DECODE_OUTPUTS = ("phase", "msg", "err")
+
+
+def _lwe_decode_batch(ctx, s_lwe, cts, delta, modulus, expected, count, stats, want, n_lwe):
+    h = ctx.h if ctx is not None else None
+    key = None if _is_dev(s_lwe) else _u64(s_lwe).reshape(-1)
+    n = key.size if key is not None else n_lwe
+    if n is None:
+        raise ValueError("lwe_decode_batch: a key on the device needs n_lwe")
+    if any(w not in DECODE_OUTPUTS for w in want):
+        raise ValueError("lwe_decode_batch: want names any of %r" % (DECODE_OUTPUTS,))
+    rows = None if _is_dev(cts) else _u64(cts)
+    if rows is not None:
+        if rows.ndim != 2 or rows.shape[1] != n + 1 or (count is not None and count != rows.shape[0]):
+            raise ValueError("lwe_decode_batch: expected cts [count][%d]" % (n + 1))
+        count = rows.shape[0]
+    elif count is None:
+        raise ValueError("lwe_decode_batch: ciphertexts on the device need count")
+    if isinstance(want, dict) and rows is not None:
+        raise ValueError("lwe_decode_batch: device outputs need device ciphertexts")
+    exp = None if expected is None or _is_dev(expected) else _u64(expected).reshape(-1)
+    if exp is not None and exp.size != count:
+        raise ValueError("lwe_decode_batch: expected must have count = %d entries" % count)
+    keep = np.zeros(1, np.uint64)
+    host = lambda a: (a if a.size else keep).ctypes.data
+    tmp, outs = None, {}
+    try:
+        if rows is not None:
+            where, pc, pe = 0, host(rows), (None if expected is None else host(exp))
+        else:
+            where, pc = (1 if isinstance(want, dict) else 2), int(cts)
+            if exp is not None:
+                tmp = ctx.device_upload_new(exp if count else keep)
+            pe = None if expected is None else tmp if exp is not None else int(expected)
+        if where == 1:
+            po = [int(want[w]) if w in want else None for w in DECODE_OUTPUTS]
+        else:
+            outs = {w: np.zeros(count, np.uint64) for w in want}
+            po = [host(outs[w]) if w in outs else None for w in DECODE_OUTPUTS]
+        rc = lib().vpbs_lwe_decode_batch(h, int(s_lwe) if key is None else key.ctypes.data, 1 if key is None else 0, pc, count, n, int(delta),
+                                         int(modulus), pe, po[0], po[1], po[2], C.byref(stats.c) if stats is not None else None, where)
+    finally:
+        if tmp is not None:
+            ctx.device_free(tmp)
+    if rc:
+        raise VpbsError("vpbs_lwe_decode_batch: status %d: %s" % (rc, lib().vpbs_last_error(h).decode() if h else "bad arguments"))
+    if where == 1:
+        return None
+    if "err" in outs:
+        outs["err"] = outs["err"].view(np.int64)
+    return outs
+
+
+def lwe_encrypt_batch(params, s_lwe, messages, nonce0=0):
+    """vpbs_lwe_encrypt_batch on the host (null context): row i = lwe_encrypt(params, s_lwe, messages[i], nonce0 + i) -> cts [count][n + 1]"""
+    return _lwe_encrypt_batch(None, params, s_lwe, messages, nonce0, None, None)
+
+
+def lwe_decode_batch(s_lwe, cts, delta, modulus, expected=None, stats=None, want=("msg",)):
+    """vpbs_lwe_decode_batch on the host (null context); see Context.lwe_decode_batch"""
+    return _lwe_decode_batch(None, s_lwe, cts, delta, modulus, expected, None, stats, want, None)
+
+
 class Bootstrapper:
     """vpbs_bootstrapper: the whole PBS (accumulator chain of verified_pbs + partial_sample_extract) for batches of LWE ciphertexts in one
     launch, under a key set that stays on the device.  bsk [n][K*ELL*K*N], ksk [K*ELL*K*N] (keygen's layout): host arrays, or device
@@ -2123,6 +2289,28 @@ class Context:
 
     def device_free(self, d_ptr):
         lib().vpbs_device_free(self.h, C.c_void_p(int(d_ptr)))
+
+    def device_upload_new(self, host):
+        """a fresh device buffer holding the words of `host` -> device pointer (to be released with device_free)"""
+        a = _u64(host).reshape(-1)
+        d = C.c_void_p()
+        self._check(lib().vpbs_device_alloc(self.h, max(a.size, 1), C.byref(d)))
+        if a.size:
+            self._check(lib().vpbs_device_upload(self.h, d, _ptr(a), a.size))
+        return d.value
+
+    def lwe_encrypt_batch(self, params, s_lwe, messages, nonce0=0, out_dev_ptr=None, count=None):
+        """vpbs_lwe_encrypt_batch on the device: row i = lwe_encrypt(params, s_lwe, messages[i], nonce0 + i), word for word.  s_lwe and messages
+        are host arrays or device pointers (integers; messages on the device need count and out_dev_ptr).  Without out_dev_ptr the rows come
+        back, [count][n + 1]; with it they are left at that device pointer and nothing is returned."""
+        return _lwe_encrypt_batch(self, params, s_lwe, messages, nonce0, out_dev_ptr, count)
+
+    def lwe_decode_batch(self, s_lwe, cts_or_dev_ptr, delta, modulus, expected=None, count=None, stats=None, want=("msg",), n_lwe=None):
+        """vpbs_lwe_decode_batch on the device.  cts [count][n + 1] host array, or a device pointer with count (then expected may be a device
+        pointer too; a key on the device needs n_lwe).  want: names among "phase", "msg", "err" -> dict of host arrays [count] (err as int64);
+        or, for device ciphertexts, a dict name -> device pointer, filled in place (returns None).  stats: a NoiseStats that is ADDED to;
+        expected makes err relative to expected * delta and counts msg != expected mod modulus as a failure."""
+        return _lwe_decode_batch(self, s_lwe, cts_or_dev_ptr, delta, modulus, expected, count, stats, want, n_lwe)
 
     def lwe_extract(self, glwe, n_lwe, count=None, N=None, K=None, out_dev_ptr=None):
         """vpbs_lwe_extract: Glwe::partial_sample_extract(n_lwe) of GLWEs [count][K][N] (or one [K][N]) -> [count][n_lwe + 1] (or [n_lwe + 1]).

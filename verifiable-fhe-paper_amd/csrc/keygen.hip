@@ -15,39 +15,14 @@
 //                  support +-6 sigma, integer arithmetic only, hence identical on every host and device (a libm Box-Muller would not be).
 // The GLWE encryptions are generated directly in the NTT domain the circuit consumes:  ntt(a), ntt(a s + e + m) = ntt(a) . ntt(s) + ntt(e + m)
 // -- the same field elements as the reference's encrypt-then-ntt_forward order (exact arithmetic), one transform per polynomial instead of three.
-#include <cmath>
 #include <vector>
 
 #include "context.h"
 #include "kernels.h"
+#include "keygen_streams.h"   // mix64 / stream / draw / field / noise, sigma_to_int, params_ok: shared with csrc/lwe_client.hip
 
 namespace vpbs {
 namespace keygen {
-constexpr u64 G = 0x9E3779B97F4A7C15ull;
-enum Kind : u64 { S_TO = 1, S_GLWE = 2, BSK_MASK = 3, BSK_NOISE = 4, KSK_MASK = 5, KSK_NOISE = 6, LWE_MASK = 7, LWE_NOISE = 8 };
-
-GL_HD u64 mix64(u64 z) {
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-GL_HD u64 tag(u64 kind, u64 a, u64 b, u64 c) { return (kind << 56) | (a << 32) | (b << 16) | c; }
-GL_HD u64 stream(u64 seed, u64 t) { return mix64(seed + G * (t + 1)); }
-GL_HD u64 draw(u64 stream_key, u64 i) { return mix64(stream_key + G * (i + 1)); }
-GL_HD u64 field(u64 u) { return u >= gl::P ? u - gl::P : u; }
-GL_HD u64 noise(u64 stream_key, u64 i, u64 m_sigma) {
-    u64 s = 0;
-#pragma unroll
-    for (unsigned k = 0; k < 6; ++k) {
-        const u64 d = draw(stream_key, 6 * i + k);
-        s += (d & 0xFFFFFFFFull) + (d >> 32);
-    }
-    const long long t = (long long)s - (6ll << 32);                     // |t| <= 6 2^32
-    const __int128 prod = (__int128)t * (__int128)m_sigma;              // m_sigma < 2^62
-    const long long e = (long long)(prod >> 32);                        // arithmetic shift = floor
-    return e < 0 ? gl::P - (u64)(-e) : (u64)e;
-}
-
 // every coefficient of every GLWE of a batch of GGSW encryptions, coefficient domain, straight into the output buffer
 // out: [n_ggsw][K][ELL][K][N];  msg: [K][N] (the polynomial GLEV p encrypts before the bit / gadget scaling);  bits: [n_ggsw] or null (= 1)
 struct GgswJob {
@@ -96,10 +71,6 @@ __global__ void __launch_bounds__(256) pointwise_mac_kernel(size_t n, unsigned t
     out[i] = acc;
 }
 
-inline u64 sigma_to_int(double sigma) {
-    const double q = (double)gl::P;  // 18446744069414584320.0, as `F::ORDER as f64`
-    return (u64)std::floor(sigma * q + 0.5);
-}
 inline u64 binary_coeff(u64 seed, u64 kind, unsigned poly, size_t i) { return draw(stream(seed, tag(kind, poly, 0, 0)), i) & 1; }
 }  // namespace keygen
 }  // namespace vpbs
@@ -116,14 +87,7 @@ struct DevBuf {
         c->release(p);
     }
 };
-bool params_ok(const vpbs_keygen_params* k) {
-    if (!k || k->log_N < 1 || k->log_N > 11 || k->K < 2 || k->K > 8 || k->LOGB < 1 || k->LOGB > 32) return false;
-    const unsigned nl = (64 + k->LOGB - 1) / k->LOGB;
-    if (k->ELL < 1 || k->ELL > nl || k->ELL > 16) return false;
-    if (k->n_lwe < 1 || k->n_lwe > (k->K << k->log_N) || k->n_lwe >= (1u << 24)) return false;
-    if (!(k->sigma_glwe >= 0.0) || !(k->sigma_lwe >= 0.0) || k->sigma_glwe > 0.2 || k->sigma_lwe > 0.2) return false;
-    return true;
-}
+using vpbs::keygen::params_ok;
 // Glwe::partial_key(n): polynomial j carries the LWE key coefficients [j N, (j + 1) N) as its leading coefficients, the rest is zero
 void host_keys(const vpbs_keygen_params* k, std::vector<u64>& s_to, std::vector<u64>& s_glwe) {
     using namespace vpbs::keygen;
