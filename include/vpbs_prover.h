@@ -964,6 +964,32 @@ int vpbs_lwe_extract(vpbs_ctx* ctx, unsigned log_N, unsigned K, unsigned n_lwe, 
                      int on_device);
 int vpbs_lwe_decrypt(const uint64_t* s_lwe, const uint64_t* ct, unsigned n_lwe, uint64_t* m_out);
 
+/* ---- bootstrapping mixed batches under many resident key sets (csrc/pbs_keyring.hip) ----
+ * A key ring holds up to max_keys key sets of ONE shape in device memory and bootstraps a batch whose ciphertexts belong to different key
+ * sets in ONE launch: ciphertext i is bootstrapped under the key set of slot key_of[i], and row i of every output is word for word what
+ * vpbs_bootstrapper_run gives for that ciphertext on a Bootstrapper made with that key set (tests/test_gpu_keyring.py).  The workgroups
+ * of a launch are ordered by slot, so that the workgroups of one key set run side by side; the outputs are at the caller's positions.
+ *   create: the shape (as vpbs_bootstrapper_create, with the same refusals: shapes above the 160 KiB of LDS a workgroup may declare get
+ *           VPBS_ERR_INVALID and a message that names the budget), max_keys and max_batch (1 .. 65535 each).  No key set yet.
+ *   add:    bsk / ksk in vpbs_keygen's layout are uploaded once, or adopted when keys_on_device != 0 (device pointers that must outlive
+ *           the slot).  *slot is the lowest free slot number; VPBS_ERR_INVALID when all max_keys slots are taken.
+ *   remove: empties the slot and frees what add uploaded (adopted pointers stay the caller's); a later add reuses the number.
+ *   count:  how many slots hold a key set.
+ *   run:    as vpbs_bootstrapper_run, plus key_of [count], a HOST array in every mode.  key_of is checked before anything is queued: an
+ *           index at or above max_keys, or an empty slot, returns VPBS_ERR_INVALID with a message (vpbs_last_error) that names the
+ *           ciphertext and the slot; nothing is launched and no output word is written.  count == 0 is legal and returns 0; count >
+ *           max_batch is VPBS_ERR_INVALID.
+ * add, remove and run of one ring exclude each other (a second caller waits); they work on the context's stream and return when done. */
+typedef struct vpbs_keyring vpbs_keyring;
+int vpbs_keyring_create(vpbs_ctx* ctx, const vpbs_tfhe_params* params, unsigned n_lwe, size_t max_keys, size_t max_batch, vpbs_keyring** out,
+                        char* err, size_t err_len);
+int vpbs_keyring_add(vpbs_keyring* ring, const uint64_t* bsk, const uint64_t* ksk, int keys_on_device, unsigned* slot);
+int vpbs_keyring_remove(vpbs_keyring* ring, unsigned slot);
+size_t vpbs_keyring_count(vpbs_keyring* ring);
+long vpbs_keyring_run(vpbs_keyring* ring, const uint64_t* cts, size_t count, const uint32_t* key_of, const uint64_t* testv, int testv_per_ct,
+                      uint64_t* out_ct, uint64_t* lwe_out, uint64_t* accs_out, int on_device);
+void vpbs_keyring_free(vpbs_keyring* ring);
+
 /* ---- the client side in batches: encrypt, lookup-table test vectors, decode with noise statistics (csrc/lwe_client.hip) ----
  * A call that takes a ctx runs on the host when ctx is NULL (then every pointer is a host array and the device flags must be 0).  With a
  * context the work goes on its stream and the call returns when the outputs are where the caller asked for them.  VPBS_ERR_INVALID refusals

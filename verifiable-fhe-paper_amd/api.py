@@ -326,6 +326,12 @@ SIGNATURES = {
     "vpbs_bootstrapper_create": (_i, [_vp, C.POINTER(TfheParamsC), _ui, _vp, _vp, _i, _sz, C.POINTER(_vp), C.c_char_p, _sz]),
     "vpbs_bootstrapper_run": (C.c_long, [_vp, _vp, _sz, _vp, _i, _vp, _vp, _vp, _i]),
     "vpbs_bootstrapper_free": (None, [_vp]),
+    "vpbs_keyring_create": (_i, [_vp, C.POINTER(TfheParamsC), _ui, _sz, _sz, C.POINTER(_vp), C.c_char_p, _sz]),
+    "vpbs_keyring_add": (_i, [_vp, _vp, _vp, _i, C.POINTER(_ui)]),
+    "vpbs_keyring_remove": (_i, [_vp, _ui]),
+    "vpbs_keyring_count": (_sz, [_vp]),
+    "vpbs_keyring_run": (C.c_long, [_vp, _vp, _sz, _vp, _vp, _i, _vp, _vp, _vp, _i]),
+    "vpbs_keyring_free": (None, [_vp]),
     "vpbs_pbs_prover_create": (_i, [_i, C.POINTER(IvcCircuitC), C.POINTER(IvcCircuitC), C.POINTER(TfheParamsC), _ui, _vp, _vp, _i, _ui, _ui,
                                     C.POINTER(_vp), C.c_char_p, _sz]),
     "vpbs_pbs_prover_run": (C.c_long, [_vp, U64P, _sz, U64P, _i, _ui, U64P, U64P, PBS_PROOF_FN, _vp, C.c_char_p, _sz]),
@@ -1562,6 +1568,114 @@ class Bootstrapper:
     def close(self):
         if self.h:
             lib().vpbs_bootstrapper_free(self.h)
+            self.h = None
+            self.ctx._batches.discard(self)
+
+    free = close
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def keyring_key_of(key_of, count, max_keys):
+    """the key_of argument of KeyRing.run as the C ABI wants it: a contiguous uint32 array [count] of slots below max_keys.  Refused here,
+    before any device call: a non-integer dtype, a shape other than [count], a negative slot or one at or above max_keys."""
+    k = np.asarray(key_of)
+    if k.shape == (0,):   # an empty list has no dtype of its own
+        k = k.astype(np.uint32)
+    if k.dtype.kind not in "iu":
+        raise ValueError("KeyRing: key_of must hold integers, not %s" % k.dtype)
+    if k.shape != (count,):
+        raise ValueError("KeyRing: expected key_of [%d], one slot per ciphertext, got shape %s" % (count, k.shape))
+    for i, v in enumerate(k.tolist()):
+        if v < 0 or v >= max_keys:
+            raise ValueError("KeyRing: key_of[%d] = %d is not a slot of a ring of %d (max_keys)" % (i, v, max_keys))
+    return np.ascontiguousarray(k, dtype=np.uint32)
+
+
+def keyring_run_args(N, n_lwe, max_keys, cts, key_of, testv):
+    """shapes of a KeyRing.run call, checked without a device: cts [count][n + 1], key_of [count], testv [N] or [count][N]"""
+    c, tv = _u64(cts), _u64(testv)
+    if c.ndim != 2 or c.shape[1] != n_lwe + 1 or tv.shape not in ((N,), (c.shape[0], N)):
+        raise ValueError("KeyRing.run: expected cts [count][%d] and testv [%d] or [count][%d]" % (n_lwe + 1, N, N))
+    return c, keyring_key_of(key_of, c.shape[0], max_keys), tv
+
+
+class KeyRing:
+    """vpbs_keyring: up to max_keys key sets of one shape resident on the device, and the whole PBS of a MIXED batch -- ciphertext i under
+    the key set of slot key_of[i] -- in one launch.  Row i of every output is what Bootstrapper(key set key_of[i]).run gives for it."""
+
+    def __init__(self, ctx, K, ELL, LOGB, N, n_lwe, max_keys, max_batch=64):
+        self.ctx, self.N, self.K, self.ELL, self.LOGB, self.n_lwe = ctx, N, K, ELL, LOGB, n_lwe
+        self.max_keys, self.max_batch = max_keys, max_batch
+        prm = TfheParamsC(N.bit_length() - 1, K, ELL, LOGB)
+        h, err = C.c_void_p(), C.create_string_buffer(512)
+        rc = lib().vpbs_keyring_create(ctx.h, C.byref(prm), n_lwe, max_keys, max_batch, C.byref(h), err, 512)
+        if rc:
+            raise VpbsError("vpbs_keyring_create: status %d: %s" % (rc, err.value.decode()))
+        self.h = h
+        ctx._batches.add(self)   # must not outlive its context: Context.close() frees the survivors
+
+    def _fail(self, what, rc):
+        e = VpbsError("%s: status %d: %s" % (what, rc, lib().vpbs_last_error(self.ctx.h).decode()))
+        e.status = rc
+        return e
+
+    def add(self, bsk, ksk, keys_on_device=False):
+        """bsk [n][K*ELL*K*N], ksk [K*ELL*K*N] (keygen's layout) uploaded once, or device pointers (integers) adopted with
+        keys_on_device=True -- they must stay allocated until the slot is removed.  Returns the slot: the lowest free number."""
+        g = self.K * self.ELL * self.K * self.N
+        if keys_on_device:
+            pb, pk = C.c_void_p(int(bsk)), C.c_void_p(int(ksk))
+        else:
+            b, k = _u64(bsk), _u64(ksk).reshape(-1)
+            if b.shape != (self.n_lwe, g) or k.size != g:
+                raise ValueError("KeyRing.add: expected bsk [%d][%d] and ksk [%d]" % (self.n_lwe, g, g))
+            pb, pk = C.c_void_p(b.ctypes.data), C.c_void_p(k.ctypes.data)
+        slot = C.c_uint()
+        rc = lib().vpbs_keyring_add(self.h, pb, pk, 1 if keys_on_device else 0, C.byref(slot))
+        if rc:
+            raise self._fail("vpbs_keyring_add", rc)
+        return slot.value
+
+    def remove(self, slot):
+        rc = lib().vpbs_keyring_remove(self.h, int(slot))
+        if rc:
+            raise self._fail("vpbs_keyring_remove", rc)
+
+    def count(self):
+        return lib().vpbs_keyring_count(self.h)
+
+    def run(self, cts, key_of, testv, accumulators=False):
+        """cts [count][n + 1]; key_of [count] slots; testv [N] shared or [count][N] -> (out_ct [count][K][N], lwe_out [count][n + 1]) and,
+        with accumulators=True, every intermediate accumulator [count][n + 2][K][N]"""
+        c, ko, tv = keyring_run_args(self.N, self.n_lwe, self.max_keys, cts, key_of, testv)
+        count = c.shape[0]
+        out_ct, lwe_out = np.zeros((count, self.K, self.N), np.uint64), np.zeros((count, self.n_lwe + 1), np.uint64)
+        accs = np.zeros((count, self.n_lwe + 2, self.K, self.N), np.uint64) if accumulators else None
+        keep = np.zeros(1, np.uint64)   # a valid pointer for an empty batch
+        p = lambda a: (a if a.size else keep).ctypes.data
+        rc = lib().vpbs_keyring_run(self.h, p(c), count, p(ko), p(tv), 1 if tv.ndim == 2 else 0, p(out_ct), p(lwe_out),
+                                    p(accs) if accumulators else None, 0)
+        if rc != count:
+            raise self._fail("vpbs_keyring_run", rc)
+        return (out_ct, lwe_out, accs) if accumulators else (out_ct, lwe_out)
+
+    def run_device(self, d_cts, count, key_of, d_testv, testv_per_ct=False, d_out_ct=None, d_lwe_out=None, d_accs=None):
+        """the same on device pointers (integers; None = output not wanted); key_of stays a host array; returns when the outputs are in place"""
+        ko = keyring_key_of(key_of, count, self.max_keys)
+        q = lambda x: C.c_void_p(int(x)) if x else None
+        rc = lib().vpbs_keyring_run(self.h, q(d_cts), count, (ko if ko.size else np.zeros(1, np.uint32)).ctypes.data, q(d_testv),
+                                    1 if testv_per_ct else 0, q(d_out_ct), q(d_lwe_out), q(d_accs), 1)
+        if rc != count:
+            raise self._fail("vpbs_keyring_run", rc)
+
+    def close(self):
+        if self.h:
+            lib().vpbs_keyring_free(self.h)
             self.h = None
             self.ctx._batches.discard(self)
 
