@@ -1105,6 +1105,21 @@ void vpbs_pbs_prover_free(vpbs_pbs_prover* p);
  *           host between levels, levels are ordered by the stream alone, and the host waits once, at the end.  Returns the number of
  *           levels, VPBS_ERR_INVALID (null or host-only program, null inputs / testvs with something to read, a Bootstrapper on another
  *           device) or VPBS_ERR_DEVICE / VPBS_ERR_OOM; the object stays usable after a refusal.  One run at a time per Bootstrapper.
+ *   run_batch: ONE program for `instances` input sets, instance b under the key set of slot key_of[b] of a key ring (above): inputs
+ *           [instances][n_inputs][n_lwe + 1]; key_of [instances], a HOST array in every mode; testvs [n_luts][N], shared by all instances;
+ *           outputs wires_out [instances][n_inputs + n_gates][n_lwe + 1], gate_cts_out [instances][n_gates][n_lwe + 1], out_cts
+ *           [instances][n_gates][K][N], any of them NULL; host pointers, or device pointers with on_device != 0.  CONTRACT: for every
+ *           instance b, slice b of each output is word for word what vpbs_program_run gives for inputs[b] and testvs on a Bootstrapper
+ *           made with the key set in slot key_of[b] -- including the reduction of input words at or above p, and wires_out showing the
+ *           inputs as given.  Level l of ALL instances goes into key-ring launches of the ring's max_batch rows each (a chunk boundary may
+ *           fall inside an instance's gates), queued on the ring's context's stream; every wire stays in device memory and the host
+ *           waits once.  Returns the number of levels; instances == 0 is legal, and so is a program without gates (its wires are the
+ *           inputs; nothing is launched).  VPBS_ERR_INVALID with a message in vpbs_last_error (of the ring's context; for a null ring
+ *           of the program's), nothing queued and no output word written, for: a null or host-only program; a null ring; a ring on another
+ *           device than the program; null inputs, testvs or key_of with something to read; more than 2^31 - 1 rows (instances x
+ *           wires); a key_of[b] at or above max_keys or naming an empty slot -- the key ring's wording, naming the instance and the
+ *           slot.  VPBS_ERR_OOM or VPBS_ERR_DEVICE otherwise.  The program and the ring stay usable after a refusal.  The call holds the
+ *           ring's mutex from its checks to its one wait: add, remove and run of that ring wait for it.
  *   prove:  evaluates as run does, with the prover's own Bootstrapper and resident keys, then hands every c_g with testvs[gate_lut[g]] to
  *           vpbs_pbs_prover_run: proof g is byte for byte what that call makes of (c_g, testvs[gate_lut[g]]) and reaches proof_fn with the
  *           caller's gate index; failure semantics (a failing chain reports its index, the others go on) and `steps` are that call's.  Host
@@ -1130,6 +1145,12 @@ int vpbs_program_create(vpbs_ctx* ctx, const vpbs_program_desc* desc, vpbs_progr
 long vpbs_program_levels(const vpbs_program* prog, unsigned* levels_out /* [n_gates] or NULL */);
 long vpbs_program_run(vpbs_program* prog, vpbs_bootstrapper* bootstrapper, const uint64_t* inputs, const uint64_t* testvs, uint64_t* wires_out,
                       uint64_t* gate_cts_out, uint64_t* out_cts, int on_device);
+long vpbs_program_run_batch(vpbs_program* prog, vpbs_keyring* ring, const uint64_t* inputs /* [instances][n_inputs][n_lwe + 1] */,
+                            size_t instances, const uint32_t* key_of /* [instances], HOST array in every mode */,
+                            const uint64_t* testvs /* [n_luts][N], shared by all instances */,
+                            uint64_t* wires_out /* [instances][n_inputs + n_gates][n_lwe + 1] or NULL */,
+                            uint64_t* gate_cts_out /* [instances][n_gates][n_lwe + 1] or NULL */,
+                            uint64_t* out_cts /* [instances][n_gates][K][N] or NULL */, int on_device);
 long vpbs_program_prove(vpbs_program* prog, vpbs_pbs_prover* pbs_prover, const uint64_t* inputs, const uint64_t* testvs, unsigned steps,
                         uint64_t* wires_out, uint64_t* out_cts, vpbs_pbs_proof_fn proof_fn, void* user, char* err, size_t err_len);
 long vpbs_program_verify(vpbs_program* prog, vpbs_pbs_verifier* pbs_verifier, const uint64_t* inputs, const uint64_t* testvs,

@@ -5,6 +5,7 @@ user had to before api.Program existed (the baseline leg: Bootstrapper.run per l
 compared wire by wire.  One JSON line.
 
 usage: tools/run_program.py [--levels L] [--width W] [--fan-in F] [--program FILE.json] [--n8] [--prove] [--baseline] [--runs R] [--seed S]
+                            [--instances B --keys M]
   netlist: W inputs, L layers of W gates; a gate reads F wires of the layer before it with coefficients in {1, p - 1}; gate 0 of every layer
     is the identity of gate 0 of the layer before it (fan-in 1, coefficient 1), so that one output has a known message whatever F is.
   --program: {"n_inputs", "n_luts", "gates": [{"terms": [[src, coef], ..], "const", "lut"}, ..]} instead; lut 0 is the test vector of the
@@ -14,6 +15,12 @@ usage: tools/run_program.py [--levels L] [--width W] [--fan-in F] [--program FIL
     output wires with a known message decrypted.
   --baseline: the baseline leg ALONE.  It needs nothing newer than api.Bootstrapper, so this file can be copied into a build of an older
     commit and time that.
+  --instances B --keys M: the same program for B input sets under M seeded key sets left on the device, instance b under key set b mod M.
+    The batched leg is ONE api.Program.run_batch on an api.KeyRing (level l of all instances in launches of --max-batch rows); the baseline
+    leg is api.Program.run per instance on the api.Bootstrapper of that instance's key set, which is all --baseline runs here -- it uses
+    nothing newer than api.Program.run.  Every wire of both legs is compared; every program output (a wire of the last level) is decrypted
+    under its own key, and those with a known message are checked.  Prints wall seconds, the HIP-event time of the bootstrap launches and
+    the launches queued per leg, and the bytes of the combine and delivery kernels computed from the shapes.
   Time: wall seconds per run of a leg (after one warm-up run), per level = / levels; HIP-event milliseconds of the bootstrap launches per
   level (the library's own timers).  Bytes: what each leg moves between host and device per run, computed from the shapes."""
 import argparse
@@ -121,6 +128,103 @@ def run_baseline(ctx, bs, n_inputs, gates, lv, inputs, testvs):
     return wires, event_ms
 
 
+def main_batch(args):
+    """--instances B --keys M: see the module text"""
+    B, M = args.instances, max(1, args.keys)
+    N, n_lwe, log_n = (8, 6, 13) if args.n8 else (1024, 728, 16)
+    rng = np.random.default_rng(args.seed)
+    if args.program:
+        n_inputs, gates, n_luts = load_program(args.program)
+    else:
+        (n_inputs, gates), n_luts = layered(rng, args.levels, args.width, args.fan_in), 1
+    n_gates, lv = len(gates), gate_levels(n_inputs, gates)
+    n_levels = max([0] + lv)
+    ctx = vpbs_amd.Context(0, log_n_max=max(16, log_n))
+    keys = [ctx.keygen_device(N, K, ELL, LOGB, n_lwe, SEED + k, SIGMA_GLWE, SIGMA_LWE) for k in range(M)]
+    testv, delta = api.testv(N, 2)
+    testvs = np.stack([testv, np.where(testv == 0, testv, np.uint64(P) - testv)] + [rng.integers(0, P, size=N, dtype=np.uint64) for _ in range(2, n_luts)])
+    testvs = np.ascontiguousarray(testvs[:max(n_luts, 1)])
+    key_of = np.array([b % M for b in range(B)], np.uint32)
+    msgs = rng.integers(0, 2, size=(B, n_inputs))
+    words, kn = n_lwe + 1, K * N
+    inputs = np.zeros((B, n_inputs, words), np.uint64)
+    for b in range(B):
+        k = keys[key_of[b]]
+        for i in range(n_inputs):
+            inputs[b, i] = api.lwe_encrypt(k["params"], k["s_lwe"], delta * int(msgs[b, i]) % P, nonce=b * n_inputs + i)
+    max_batch = max(1, args.max_batch)
+    out = {"what": "a program of %d gates on %d levels over %d inputs at N=%d, n=%d, for %d instances under %d key sets" %
+                   (n_gates, n_levels, n_inputs, N, n_lwe, B, M), "gates": n_gates, "levels": n_levels, "inputs": n_inputs, "instances": B, "keys": M,
+           "fan_in": None if args.program else args.fan_in, "max_batch": max_batch, "runs": args.runs}
+    ctx.timing_enable(1)
+    prog = api.Program(ctx, n_inputs, gates, testvs.shape[0])
+
+    def leg(run, timer):
+        run()                                                            # warm-up
+        secs, launches, ms, wires, rep = [], [], [], None, {}
+        for _ in range(args.runs):
+            ctx.timing_report()
+            t = time.perf_counter()
+            wires = run()
+            secs.append(time.perf_counter() - t)
+            rep = ctx.timing_report()
+            launches.append(rep.get(timer, {}).get("count", 0))
+            ms.append(rep.get(timer, {}).get("ms", 0.0))
+        # every figure per run, in the order of "seconds"
+        return wires, rep, {"seconds": secs, "pbs_launches": launches[-1] if launches else 0, "pbs_launches_per_run": launches, "pbs_event_ms": ms,
+                            "pbs_event_ms_per_launch": [m / max(c, 1) for m, c in zip(ms, launches)],
+                            "wall_minus_launch_seconds": [s - m / 1e3 for s, m in zip(secs, ms)]}
+
+    # ---- the baseline leg: Program.run per instance on the Bootstrapper of its key set ----
+    bss = [api.Bootstrapper(ctx, k["d_bsk"], k["d_ksk"], K, ELL, LOGB, max_batch=max(1, min(max_batch, max(n_gates, 1))), N=N, n_lwe=n_lwe,
+                            keys_on_device=True) for k in keys]
+    per_instance = lambda: np.stack([prog.run(bss[key_of[b]], inputs[b], testvs, gate_cts=False, out_cts=False)[0] for b in range(B)]) \
+        if B else np.zeros((0, n_inputs + n_gates, words), np.uint64)
+    base_wires, _, out["baseline"] = leg(per_instance, "pbs_batch")
+    for bs in bss:
+        bs.close()
+    wires, ok = base_wires, True
+    if not args.baseline:
+        # ---- the batched leg: ONE Program.run_batch on a ring ----
+        ring = api.KeyRing(ctx, K, ELL, LOGB, N, n_lwe, max_keys=M, max_batch=max_batch)
+        for k in keys:
+            ring.add(k["d_bsk"], k["d_ksk"], keys_on_device=True)
+        wires, rep, out["batch"] = leg(lambda: prog.run_batch(ring, inputs, key_of, testvs, gate_cts=False, out_cts=False)[0], "pbs_keyring")
+        ring.close()
+        terms = sum(len(g[0]) for g in gates)
+        out["batch"].update({"combine_event_ms": rep.get("lwe_combine", {}).get("ms", 0.0), "combine_launches": rep.get("lwe_combine", {}).get("count", 0),
+                             "combine_bytes": 8 * words * B * (terms + n_gates),               # a read per term, a write per gate
+                             "deliver_event_ms": rep.get("program_deliver", {}).get("ms", 0.0),
+                             "deliver_bytes": 2 * 8 * words * B * (n_inputs + n_gates),        # every wire read and written once
+                             # inputs, test vectors, and the index array: identity | slot and lut of every gate row | input rows | wire rows
+                             "h2d_bytes": 8 * (B * n_inputs * words + testvs.shape[0] * N) +
+                                          4 * (max(1, min(max_batch, B * max([0] + [sum(1 for x in lv if x == level) for level in range(1, n_levels + 1)]))) + B * (2 * n_gates + n_inputs) + B * (n_inputs + n_gates)),
+                             "d2h_bytes": 8 * B * (n_inputs + n_gates) * words})
+        out["batch_over_baseline"] = statistics.median(out["batch"]["seconds"]) / statistics.median(out["baseline"]["seconds"])
+        out["all_equal"] = bool(wires.shape == base_wires.shape and (wires == base_wires).all())
+        ok = out["all_equal"]
+    prog.close()
+    # ---- every program output (the wires of the last level), under its own key ----
+    outputs = [n_inputs + g for g in range(n_gates) if lv[g] == n_levels]
+    checked = correct = decrypted = 0
+    for b in range(B):
+        known = known_messages(n_inputs, gates, [int(m) for m in msgs[b]])
+        for w in outputs:
+            m = rounded(api.lwe_decrypt(keys[key_of[b]]["s_lwe"], wires[b, w]), delta)
+            decrypted += 1
+            if known[w] is not None:
+                checked += 1
+                correct += m == known[w]
+    out["decrypted"], out["decrypted_checked"], out["decrypted_correct"] = decrypted, checked, int(correct)
+    ok = ok and correct == checked
+    for k in keys:
+        ctx.device_free(k["d_bsk"])
+        ctx.device_free(k["d_ksk"])
+    ctx.close()
+    print(json.dumps(out))
+    return 0 if ok else 1
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--levels", type=int, default=3)
@@ -135,9 +239,15 @@ def main():
     ap.add_argument("--chains", type=int, default=0)
     ap.add_argument("--witness-batch", type=int, default=0)
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--instances", type=int)
+    ap.add_argument("--keys", type=int, default=1)
     args = ap.parse_args()
     if args.baseline and args.prove:
         raise SystemExit("--baseline evaluates only: it cannot run with --prove")
+    if args.instances is not None:
+        if args.prove:
+            raise SystemExit("--instances evaluates only: proofs are bound to one key set")
+        return main_batch(args)
     N, n_lwe, log_n = (8, 6, 13) if args.n8 else (1024, 728, 16)
     rng = np.random.default_rng(args.seed)
     if args.program:

@@ -345,6 +345,7 @@ SIGNATURES = {
     "vpbs_program_create": (_i, [_vp, C.POINTER(ProgramDescC), C.POINTER(_vp), C.c_char_p, _sz]),
     "vpbs_program_levels": (C.c_long, [_vp, C.POINTER(_ui)]),
     "vpbs_program_run": (C.c_long, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i]),
+    "vpbs_program_run_batch": (C.c_long, [_vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _i]),
     "vpbs_program_prove": (C.c_long, [_vp, _vp, U64P, U64P, _ui, U64P, U64P, PBS_PROOF_FN, _vp, C.c_char_p, _sz]),
     "vpbs_program_verify": (C.c_long, [_vp, _vp, U64P, U64P, U64P, C.POINTER(C.c_uint8), C.POINTER(_sz), C.POINTER(C.c_uint8),
                                        C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]),
@@ -1604,6 +1605,17 @@ def keyring_run_args(N, n_lwe, max_keys, cts, key_of, testv):
     return c, keyring_key_of(key_of, c.shape[0], max_keys), tv
 
 
+def program_batch_args(n_inputs, n_lwe, N, n_luts, max_keys, inputs, key_of, testvs):
+    """shapes of a Program.run_batch call, checked without a device: inputs [instances][n_inputs][n + 1], key_of [instances] slots below
+    max_keys (any integer dtype; the offending index is named), testvs [n_luts][N] -> (inputs, key_of as uint32, testvs), contiguous"""
+    x, tv = _u64(inputs), _u64(testvs)
+    if x.ndim != 3 or x.shape[1:] != (n_inputs, n_lwe + 1):
+        raise ValueError("Program.run_batch: expected inputs [instances][%d][%d], got shape %s" % (n_inputs, n_lwe + 1, x.shape))
+    if tv.shape != (n_luts, N):
+        raise ValueError("Program.run_batch: expected testvs [%d][%d], got shape %s" % (n_luts, N, tv.shape))
+    return x, keyring_key_of(key_of, x.shape[0], max_keys), tv
+
+
 class KeyRing:
     """vpbs_keyring: up to max_keys key sets of one shape resident on the device, and the whole PBS of a MIXED batch -- ciphertext i under
     the key set of slot key_of[i] -- in one launch.  Row i of every output is what Bootstrapper(key set key_of[i]).run gives for it."""
@@ -1944,6 +1956,48 @@ class Program:
         rc = lib().vpbs_program_run(self.h, bootstrapper.h, q(d_inputs), q(d_testvs), q(d_wires), q(d_gate_cts), q(d_out_cts), 1)
         if rc < 0:
             raise VpbsError("vpbs_program_run: status %d: %s" % (rc, lib().vpbs_last_error(bootstrapper.ctx.h).decode()))
+        return rc
+
+    def _batch_fail(self, ring, rc):
+        e = VpbsError("vpbs_program_run_batch: status %d: %s" % (rc, lib().vpbs_last_error(ring.ctx.h).decode()))
+        e.status = rc
+        return e
+
+    def run_batch(self, ring, inputs, key_of, testvs, gate_cts=True, out_cts=True):
+        """ONE program for many input sets on a KeyRing: inputs [instances][n_inputs][n + 1], key_of [instances] slots, testvs [n_luts][N]
+        shared -> (wires [instances][n_inputs + n_gates][n + 1], gate_cts [instances][n_gates][n + 1], out_cts [instances][n_gates][K][N]);
+        slice b is run(Bootstrapper of the key set in slot key_of[b], inputs[b], testvs), word for word.  Level l of all instances goes
+        into launches of the ring's max_batch rows.  gate_cts=False / out_cts=False: that output is not downloaded (None in its place)."""
+        if self.ctx is None:
+            raise VpbsError("Program.run_batch: a host-only program (made without a context) cannot be evaluated")
+        if ring is None or not ring.h:
+            raise VpbsError("Program.run_batch: no ring (None, or a closed KeyRing)")
+        r = ring
+        x, ko, tv = program_batch_args(self.n_inputs, r.n_lwe, r.N, self.n_luts, r.max_keys, inputs, key_of, testvs)
+        count = x.shape[0]
+        wires = np.zeros((count, self.n_inputs + self.n_gates, r.n_lwe + 1), np.uint64)
+        cts = np.zeros((count, self.n_gates, r.n_lwe + 1), np.uint64) if gate_cts else None
+        out = np.zeros((count, self.n_gates, r.K, r.N), np.uint64) if out_cts else None
+        keep = np.zeros(1, np.uint64)   # a valid pointer for an empty array
+        p = lambda a: None if a is None else (a if a.size else keep).ctypes.data
+        rc = lib().vpbs_program_run_batch(self.h, r.h, p(x), count, p(ko), p(tv), p(wires), p(cts), p(out), 0)
+        if rc < 0:
+            raise self._batch_fail(r, rc)
+        return wires, cts, out
+
+    def run_batch_device(self, ring, d_inputs, instances, key_of, d_testvs, d_wires=None, d_gate_cts=None, d_out_cts=None):
+        """the same on device pointers (integers; None = output not wanted); key_of stays a host array; returns the number of levels when
+        the outputs are in place"""
+        if self.ctx is None:
+            raise VpbsError("Program.run_batch_device: a host-only program (made without a context) cannot be evaluated")
+        if ring is None or not ring.h:
+            raise VpbsError("Program.run_batch_device: no ring (None, or a closed KeyRing)")
+        ko = keyring_key_of(key_of, instances, ring.max_keys)
+        q = lambda x: C.c_void_p(int(x)) if x else None
+        rc = lib().vpbs_program_run_batch(self.h, ring.h, q(d_inputs), instances, (ko if ko.size else np.zeros(1, np.uint32)).ctypes.data,
+                                          q(d_testvs), q(d_wires), q(d_gate_cts), q(d_out_cts), 1)
+        if rc < 0:
+            raise self._batch_fail(ring, rc)
         return rc
 
     def prove(self, pbs_prover, inputs, testvs, steps=0, on_proof=None):

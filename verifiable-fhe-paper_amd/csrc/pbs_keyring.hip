@@ -17,6 +17,7 @@
 
 #include "context.h"
 #include "pbs_chain.h"
+#include "program_internal.h"
 
 using vpbs::DeviceError;
 using vpbs::u64;
@@ -252,6 +253,59 @@ struct vpbs_keyring {
     }
 };
 
+namespace vpbs {
+void keyring_shape(const vpbs_keyring* r, KeyringShape* out) { *out = KeyringShape{r->ctx, r->prm, r->n_lwe, r->max_keys, r->max_batch}; }
+
+std::mutex& keyring_mutex(vpbs_keyring* r) { return r->mu; }
+
+bool keyring_check_slots(const vpbs_keyring* r, const uint32_t* key_of, size_t count, const char* who, const char* what, std::string* msg) {
+    for (size_t i = 0; i < count; ++i) {
+        const uint32_t s = key_of[i];
+        if (s >= r->max_keys || !r->slots[s].used) {
+            *msg = std::string(who) + ": key_of[" + std::to_string(i) + "] = " + std::to_string(s) +
+                   (s >= r->max_keys ? ": slot out of range (max_keys " + std::to_string(r->max_keys) + ")" : ": slot " + std::to_string(s) + " is empty") +
+                   "; " + what + " " + std::to_string(i) + " has no key set, nothing was launched";
+            return false;
+        }
+    }
+    return true;
+}
+
+void keyring_enqueue(vpbs_keyring* r, const uint64_t* d_cts, size_t count, const uint64_t* d_testv, int testv_per_ct, const uint32_t* d_order,
+                     const uint32_t* d_key_of, uint64_t* d_out_ct, uint64_t* d_lwe_out, uint64_t* d_accs_out) {
+    vpbs_ctx* ctx = r->ctx;
+    const unsigned log_n = r->prm.log_N;
+    const size_t n = (size_t)1 << log_n;
+    PbsKeyringArgs a{};
+    a.cts = d_cts;
+    a.testv = d_testv;
+    a.testv_stride = testv_per_ct ? n : 0;
+    a.table = r->d_table;
+    a.order = d_order;
+    a.key_of = d_key_of;
+    a.roots = ctx->ring_table(log_n);
+    a.ninv = gl::inv((u64)n);
+    a.out_ct = d_out_ct;
+    a.lwe_out = d_lwe_out;
+    a.accs_out = d_accs_out;
+    a.log_n = log_n;
+    a.K = r->prm.K;
+    a.ELL = r->prm.ELL;
+    a.LOGB = r->prm.LOGB;
+    a.n_lwe = r->n_lwe;
+    {
+        vpbs::Timed t(ctx, "pbs_keyring");
+        // the Bootstrapper's rule: 1024 threads while every ciphertext has a CU of its own, two 512-thread workgroups
+        // per CU above that where two fit the LDS
+        const unsigned threads = r->threads ? r->threads : (count > r->cus && 2 * r->lds_bytes <= PBS_LDS_BUDGET ? 512u : 1024u);
+        if (threads == 256) launch_pbs_keyring<256>(ctx->stream, a, count, r->lds_bytes);
+        else if (threads == 512) launch_pbs_keyring<512>(ctx->stream, a, count, r->lds_bytes);
+        else launch_pbs_keyring<1024>(ctx->stream, a, count, r->lds_bytes);
+    }
+    VPBS_HIP(hipGetLastError());
+}
+}  // namespace vpbs
+
 extern "C" {
 int vpbs_keyring_create(vpbs_ctx* ctx, const vpbs_tfhe_params* prm, unsigned n_lwe, size_t max_keys, size_t max_batch, vpbs_keyring** out,
                         char* err, size_t err_len) {
@@ -400,15 +454,7 @@ long vpbs_keyring_run(vpbs_keyring* r, const uint64_t* cts, size_t count, const 
         return VPBS_ERR_INVALID;
     }
     // every index before anything is queued
-    for (size_t i = 0; i < count; ++i) {
-        const uint32_t s = key_of[i];
-        if (s >= r->max_keys || !r->slots[s].used) {
-            ctx->err = "vpbs_keyring_run: key_of[" + std::to_string(i) + "] = " + std::to_string(s) +
-                       (s >= r->max_keys ? ": slot out of range (max_keys " + std::to_string(r->max_keys) + ")" : ": slot " + std::to_string(s) + " is empty") +
-                       "; ciphertext " + std::to_string(i) + " has no key set, nothing was launched";
-            return VPBS_ERR_INVALID;
-        }
-    }
+    if (!keyring_check_slots(r, key_of, count, "vpbs_keyring_run", "ciphertext", &ctx->err)) return VPBS_ERR_INVALID;
     if (count == 0) return 0;
     const unsigned log_n = r->prm.log_N, K = r->prm.K, n_lwe = r->n_lwe;
     const size_t n = (size_t)1 << log_n, kn = K * n, ct_words = n_lwe + 1;
@@ -433,33 +479,7 @@ long vpbs_keyring_run(vpbs_keyring* r, const uint64_t* cts, size_t count, const 
             d_lwe_out = lwe_out ? r->d_lwe : nullptr;
             if (accs_out) d_accs_out = d_accs = ctx->alloc_words(count * (n_lwe + 2) * kn);
         }
-        PbsKeyringArgs a{};
-        a.cts = d_cts;
-        a.testv = d_testv;
-        a.testv_stride = testv_per_ct ? n : 0;
-        a.table = r->d_table;
-        a.order = r->d_index;
-        a.key_of = r->d_index + r->max_batch;
-        a.roots = ctx->ring_table(log_n);
-        a.ninv = gl::inv((u64)n);
-        a.out_ct = d_out_ct;
-        a.lwe_out = d_lwe_out;
-        a.accs_out = d_accs_out;
-        a.log_n = log_n;
-        a.K = K;
-        a.ELL = r->prm.ELL;
-        a.LOGB = r->prm.LOGB;
-        a.n_lwe = n_lwe;
-        {
-            vpbs::Timed t(ctx, "pbs_keyring");
-            // the Bootstrapper's rule: 1024 threads while every ciphertext has a CU of its own, two 512-thread workgroups
-            // per CU above that where two fit the LDS
-            const unsigned threads = r->threads ? r->threads : (count > r->cus && 2 * r->lds_bytes <= PBS_LDS_BUDGET ? 512u : 1024u);
-            if (threads == 256) launch_pbs_keyring<256>(ctx->stream, a, count, r->lds_bytes);
-            else if (threads == 512) launch_pbs_keyring<512>(ctx->stream, a, count, r->lds_bytes);
-            else launch_pbs_keyring<1024>(ctx->stream, a, count, r->lds_bytes);
-        }
-        VPBS_HIP(hipGetLastError());
+        keyring_enqueue(r, d_cts, count, d_testv, testv_per_ct, r->d_index, r->d_index + r->max_batch, d_out_ct, d_lwe_out, d_accs_out);
         if (!on_device) {
             if (out_ct) VPBS_HIP(hipMemcpyAsync(out_ct, r->d_out, sizeof(u64) * count * kn, hipMemcpyDeviceToHost, ctx->stream));
             if (lwe_out) VPBS_HIP(hipMemcpyAsync(lwe_out, r->d_lwe, sizeof(u64) * count * ct_words, hipMemcpyDeviceToHost, ctx->stream));

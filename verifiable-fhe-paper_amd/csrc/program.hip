@@ -9,11 +9,22 @@
 //           The wire table on the device is in the PERMUTED order, so a level's outputs are contiguous rows; gather_rows_kernel puts the
 //           outputs back into the caller's order at the end.  The levels are ordered by the stream; nothing waits inside a kernel for
 //           another workgroup; the host waits once.
+//   run_batch  one program, `instances` input sets, instance b under the key set of slot key_of[b] of a key ring: level l of ALL instances
+//           goes into key-ring launches of the ring's max_batch rows (vpbs::keyring_enqueue).  The wire table is level-major -- the
+//           block of inputs [instances][n_inputs], then per level a block [instances][gates of the level] -- with the instances in slot
+//           order (a stable sort of key_of on the host), so that a chunk of consecutive rows is grouped by key set and its lwe_out is a
+//           contiguous piece of the level's block:
+//             lwe_combine_batch_kernel   level-major wire table -> the chunk's gate inputs
+//             gather_rows_kernel         testvs[gate_lut of the row] -> the chunk's test vectors
+//             pbs_keyring_kernel         -> out_ct, and lwe_out straight into the level's block
+//           Every index array of every launch is uploaded once, before the first launch; gather_rows_kernel delivers the three outputs in
+//           the caller's instance and gate order; the host waits once.
 //   prove   run on the batch prover's Bootstrapper, then vpbs_pbs_prover_run on the gate inputs (caller's order) with per-gate test vectors.
 //   verify  upload inputs and claimed outputs, lwe_extract_kernel on all outputs, ONE lwe_combine_kernel over all gates in the caller's
 //           order, then vpbs_pbs_verifier_run in chunks.
 #include <algorithm>
 #include <cstring>
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -47,6 +58,39 @@ __global__ void __launch_bounds__(256) lwe_combine_kernel(CombineArgs a) {
     for (unsigned j = threadIdx.x; j < a.words; j += 256) {
         u64 s = j + 1 == a.words ? c : 0;
         for (u64 t = t0; t < t1; ++t) s = gl::add(s, gl::mul(a.coef[t], gl::canon(a.wires[(size_t)a.src[t] * a.words + j])));
+        out[j] = s;
+    }
+}
+
+struct CombineBatchArgs {
+    const u64* wires;       // the level-major table of a batched evaluation
+    const u64* first;       // [n_gates + 1], permuted order
+    const u32* loc;         // [n_terms][3]: the source wire's block (first row per instance), the block's width, the position in it
+    const u64* coef;        // [n_terms]
+    const u64* cst;         // [n_gates]
+    u64* out;               // [count][words]: row 0 is row `row0` of the level's block
+    size_t instances;
+    unsigned row0, gate0, width, words;   // gate0: the level's first permuted gate; width: gates of the level
+};
+
+// lwe_combine_kernel for the rows of one level of MANY instances: one workgroup per (instance, gate) row, lanes on consecutive words.  Row r
+// of the level's block is gate gate0 + r % width of the instance at sorted position r / width; the term list, the coefficients, the
+// constant and the source rows depend on blockIdx.x alone (wave-uniform), and a term is one coalesced read of a wire row.  The same
+// arithmetic in the same order: canonical on read, canonical products and sums, the constant in the body only.
+__global__ void __launch_bounds__(256) lwe_combine_batch_kernel(CombineBatchArgs a) {
+    const unsigned r = a.row0 + blockIdx.x;
+    const size_t inst = r / a.width;
+    const unsigned g = a.gate0 + r % a.width;
+    const u64 t0 = a.first[g], t1 = a.first[g + 1];
+    const u64 c = a.cst[g];
+    u64* out = a.out + (size_t)blockIdx.x * a.words;
+    for (unsigned j = threadIdx.x; j < a.words; j += 256) {
+        u64 s = j + 1 == a.words ? c : 0;
+        for (u64 t = t0; t < t1; ++t) {
+            const u32* l = a.loc + 3 * t;
+            const size_t row = a.instances * l[0] + inst * l[1] + l[2];
+            s = gl::add(s, gl::mul(a.coef[t], gl::canon(a.wires[row * a.words + j])));
+        }
         out[j] = s;
     }
 }
@@ -88,6 +132,7 @@ struct vpbs_program {
     std::vector<u32> level_first;      // [n_levels + 1] in permuted positions
     vpbs::DeviceCsr d_given, d_perm;   // d_perm.src: rows of the permuted wire table
     u32 *d_wire_pos = nullptr, *d_gate_pos = nullptr;   // caller's wire / gate -> row of the permuted wire table / permuted position
+    u32* d_term_loc = nullptr;         // [n_terms][3], permuted term order: where a batched evaluation finds the term's source (run_batch)
     std::vector<void*> owned;
 
     ~vpbs_program() {
@@ -210,6 +255,158 @@ long program_run(vpbs_program* prog, vpbs_bootstrapper* b, const u64* inputs, co
     }
     return rc == VPBS_OK ? (long)prog->n_levels : rc;
 }
+// vpbs_program_run_batch
+long program_run_batch(vpbs_program* prog, vpbs_keyring* ring, const u64* inputs, size_t instances, const u32* key_of, const u64* testvs,
+                       u64* wires_out, u64* gate_cts_out, u64* out_cts, int on_device) {
+    if (!ring) {   // no ring, no mutex: the message goes to the program's context alone
+        if (prog && prog->ctx) prog->ctx->err = "vpbs_program_run_batch: null ring";
+        return VPBS_ERR_INVALID;
+    }
+    std::lock_guard<std::mutex> lock(keyring_mutex(ring));   // from the checks to the one wait: add, remove and run of the ring wait
+    KeyringShape sh{};
+    keyring_shape(ring, &sh);
+    vpbs_ctx* ctx = sh.ctx;
+    auto refuse = [&](const std::string& m) {   // under the ring's mutex, as every writer of its context's message
+        ctx->err = m;
+        return (long)VPBS_ERR_INVALID;
+    };
+    if (!prog) return refuse("vpbs_program_run_batch: null program");
+    if (!prog->ctx) return refuse("vpbs_program_run_batch: a host-only program (made without a context) cannot be evaluated");
+    const unsigned n_in = prog->n_inputs, n_gates = prog->n_gates, words = sh.n_lwe + 1;
+    const size_t n = (size_t)1 << sh.prm.log_N, kn = sh.prm.K * n, n_wires = (size_t)n_in + n_gates, B = instances;
+    if (ctx->device != prog->ctx->device) return refuse("vpbs_program_run_batch: the program and the ring are on different devices");
+    if (B && ((n_in && !inputs) || (n_gates && !testvs) || !key_of)) return refuse("vpbs_program_run_batch: null inputs, testvs or key_of");
+    if (n_wires && B > 0x7fffffffull / n_wires) return refuse("vpbs_program_run_batch: instances x wires exceeds 2^31 - 1 rows");
+    std::string msg;
+    if (!keyring_check_slots(ring, key_of, B, "vpbs_program_run_batch", "instance", &msg)) return refuse(msg);
+    if (B == 0) return (long)prog->n_levels;
+    if (n_gates == 0) {   // the wires are the inputs: nothing to launch, no index to build
+        if (!wires_out || !n_in) return 0;
+        if (!on_device) return std::memcpy(wires_out, inputs, 8 * B * n_in * words), 0;
+        try {
+            VPBS_HIP(hipSetDevice(ctx->device));
+            VPBS_HIP(hipMemcpyAsync(wires_out, inputs, 8 * B * n_in * words, hipMemcpyDeviceToDevice, ctx->stream));
+            VPBS_HIP(vpbs::stream_sync(ctx->stream));
+        } catch (const DeviceError& e) {
+            ctx->err = e.what;
+            return e.status == VPBS_ERR_OOM ? VPBS_ERR_OOM : VPBS_ERR_DEVICE;
+        }
+        return 0;
+    }
+    const std::vector<u32>& lf = prog->level_first;
+    // ---- the instances in slot order (stable), and every index array of every launch ----
+    std::vector<u32> inst(B), pos_of(B), gate_pos(n_gates);
+    {
+        std::vector<size_t> start(sh.max_keys + 1, 0);
+        for (size_t b = 0; b < B; ++b) ++start[key_of[b] + 1];
+        for (size_t k = 0; k < sh.max_keys; ++k) start[k + 1] += start[k];
+        for (size_t b = 0; b < B; ++b) {
+            pos_of[b] = (u32)start[key_of[b]]++;
+            inst[pos_of[b]] = (u32)b;
+        }
+    }
+    for (unsigned q = 0; q < n_gates; ++q) gate_pos[prog->order[q]] = q;
+    size_t widest = 0;
+    for (unsigned lv = 0; lv < prog->n_levels; ++lv) widest = std::max<size_t>(widest, lf[lv + 1] - lf[lv]);
+    const size_t chunk_max = std::max<size_t>(1, std::min<size_t>(sh.max_batch, B * widest)), rows_g = B * n_gates, rows_w = B * n_wires;
+    const bool want_gates = gate_cts_out || out_cts;
+    // identity [chunk_max] | key_of of every gate row | gate_lut of every gate row | input rows | caller's wire rows | caller's gate rows
+    const size_t o_key = chunk_max, o_lut = o_key + rows_g, o_in = o_lut + rows_g, o_wire = o_in + B * n_in,
+                 o_gate = o_wire + (wires_out ? rows_w : 0), total = o_gate + (want_gates ? rows_g : 0);
+    std::vector<u32> idx(total);   // lives until the wait
+    for (size_t i = 0; i < chunk_max; ++i) idx[i] = (u32)i;
+    for (unsigned lv = 0; lv < prog->n_levels; ++lv) {
+        const size_t w = lf[lv + 1] - lf[lv], base = B * lf[lv];
+        for (size_t s = 0; s < B; ++s)
+            for (size_t j = 0; j < w; ++j) {
+                idx[o_key + base + s * w + j] = key_of[inst[s]];
+                idx[o_lut + base + s * w + j] = prog->given.lut[prog->order[lf[lv] + j]];
+            }
+    }
+    for (size_t s = 0; s < B; ++s)
+        for (unsigned w = 0; w < n_in; ++w) idx[o_in + s * n_in + w] = (u32)((size_t)inst[s] * n_in + w);
+    auto gate_row = [&](size_t b, unsigned g) {   // row of gate g of instance b among the gate rows of the level-major table
+        const unsigned lv = prog->level[g] - 1;
+        return B * lf[lv] + (size_t)pos_of[b] * (lf[lv + 1] - lf[lv]) + (gate_pos[g] - lf[lv]);
+    };
+    for (size_t b = 0; b < B; ++b) {
+        if (wires_out) {
+            for (unsigned w = 0; w < n_in; ++w) idx[o_wire + b * n_wires + w] = (u32)((size_t)pos_of[b] * n_in + w);
+            for (unsigned g = 0; g < n_gates; ++g) idx[o_wire + b * n_wires + n_in + g] = (u32)(B * n_in + gate_row(b, g));
+        }
+        if (want_gates)
+            for (unsigned g = 0; g < n_gates; ++g) idx[o_gate + b * n_gates + g] = (u32)gate_row(b, g);
+    }
+    int rc = VPBS_OK;
+    try {
+        VPBS_HIP(hipSetDevice(ctx->device));
+        hipStream_t s = ctx->stream;
+        Scratch mem(ctx);
+        try {
+            u32* d_idx = reinterpret_cast<u32*>(mem.words((total + 1) / 2));
+            VPBS_HIP(hipMemcpyAsync(d_idx, idx.data(), sizeof(u32) * total, hipMemcpyHostToDevice, s));   // once, before the first launch
+            u64* d_wires = mem.words(rows_w * words);
+            u64* d_cts = mem.words(rows_g * words);
+            u64* d_out = out_cts ? mem.words(rows_g * kn) : nullptr;
+            u64* d_tv = mem.words(chunk_max * n);
+            const u64 *d_testvs = testvs, *d_inputs = inputs;
+            if (!on_device) {
+                u64* d = mem.words((size_t)prog->n_luts * n);
+                VPBS_HIP(hipMemcpyAsync(d, testvs, 8 * (size_t)prog->n_luts * n, hipMemcpyHostToDevice, s));
+                d_testvs = d;
+                if (n_in) {
+                    d = mem.words(B * n_in * words);
+                    VPBS_HIP(hipMemcpyAsync(d, inputs, 8 * B * n_in * words, hipMemcpyHostToDevice, s));
+                    d_inputs = d;
+                }
+            }
+            if (n_in) {   // the block of inputs, the instances in slot order, as given
+                launch_gather(s, d_inputs, d_idx + o_in, words, (unsigned)(B * n_in), d_wires);
+                VPBS_HIP(hipGetLastError());
+            }
+            for (unsigned lv = 0; lv < prog->n_levels; ++lv) {
+                const size_t w = lf[lv + 1] - lf[lv], rows = B * w, base = B * lf[lv];
+                for (size_t r0 = 0; r0 < rows; r0 += sh.max_batch) {
+                    const unsigned c = (unsigned)std::min<size_t>(sh.max_batch, rows - r0);
+                    u64* cts = d_cts + (base + r0) * words;
+                    {
+                        vpbs::Timed t(ctx, "lwe_combine");
+                        const CombineBatchArgs a{d_wires, prog->d_perm.first, prog->d_term_loc, prog->d_perm.coef, prog->d_perm.cst, cts, B,
+                                                 (unsigned)r0, lf[lv], (unsigned)w, words};
+                        hipLaunchKernelGGL(lwe_combine_batch_kernel, dim3(c), dim3(256), 0, s, a);
+                    }
+                    launch_gather(s, d_testvs, d_idx + o_lut + base + r0, n, c, d_tv);
+                    VPBS_HIP(hipGetLastError());
+                    // the rows are in slot order already: the identity as `order`, the rows' own slots as `key_of`
+                    keyring_enqueue(ring, cts, c, d_tv, 1, d_idx, d_idx + o_key + base + r0, d_out ? d_out + (base + r0) * kn : nullptr,
+                                    d_wires + (B * n_in + base + r0) * words, nullptr);
+                }
+            }
+            // back into the caller's instance and gate order, to where the caller wants it
+            auto deliver = [&](u64* dst, const u64* d_src, const u32* d_map, size_t row_words, size_t rows) {
+                if (!dst || rows == 0) return;
+                u64* d_dst = on_device ? dst : mem.words(rows * row_words);
+                {
+                    vpbs::Timed t(ctx, "program_deliver");
+                    launch_gather(s, d_src, d_map, row_words, (unsigned)rows, d_dst);
+                }
+                VPBS_HIP(hipGetLastError());
+                if (!on_device) VPBS_HIP(hipMemcpyAsync(dst, d_dst, 8 * rows * row_words, hipMemcpyDeviceToHost, s));
+            };
+            deliver(wires_out, d_wires, d_idx + o_wire, words, rows_w);
+            deliver(gate_cts_out, d_cts, d_idx + o_gate, words, rows_g);
+            deliver(out_cts, d_out, d_idx + o_gate, kn, rows_g);
+            VPBS_HIP(vpbs::stream_sync(s));   // the one wait
+        } catch (const DeviceError&) {
+            (void)vpbs::stream_sync(s);
+            throw;
+        }
+    } catch (const DeviceError& e) {
+        ctx->err = e.what;
+        rc = e.status == VPBS_ERR_OOM ? VPBS_ERR_OOM : (e.status == VPBS_ERR_INVALID ? VPBS_ERR_INVALID : VPBS_ERR_DEVICE);
+    }
+    return rc == VPBS_OK ? (long)prog->n_levels : rc;
+}
 }  // namespace
 }  // namespace vpbs
 
@@ -283,12 +480,20 @@ int vpbs_program_create(vpbs_ctx* ctx, const vpbs_program_desc* desc, vpbs_progr
     for (unsigned g = 0; g < n_gates; ++g) wire_pos[n_in + g] = n_in + gate_pos[g];
     if (ctx) {
         Csr R;   // the permuted description; sources are rows of the permuted wire table
+        std::vector<u32> term_loc;   // per term of R: the source's block in a level-major table (first row per instance, width, position)
         R.first.push_back(0);
         for (unsigned q = 0; q < n_gates; ++q) {
             const unsigned g = p->order[q];
             for (u64 t = G.first[g]; t < G.first[g + 1]; ++t) {
-                R.src.push_back(wire_pos[G.src[t]]);
+                const u32 row = wire_pos[G.src[t]];
+                R.src.push_back(row);
                 R.coef.push_back(G.coef[t]);
+                if (row < n_in) {
+                    term_loc.insert(term_loc.end(), {0u, n_in, row});
+                } else {
+                    const unsigned lv = p->level[G.src[t] - n_in] - 1;
+                    term_loc.insert(term_loc.end(), {n_in + p->level_first[lv], p->level_first[lv + 1] - p->level_first[lv], row - n_in - p->level_first[lv]});
+                }
             }
             R.first.push_back(R.src.size());
             R.cst.push_back(G.cst[g]);
@@ -301,6 +506,7 @@ int vpbs_program_create(vpbs_ctx* ctx, const vpbs_program_desc* desc, vpbs_progr
             p->d_perm = p->upload(R);
             p->d_wire_pos = p->upload(wire_pos);
             p->d_gate_pos = p->upload(gate_pos);
+            p->d_term_loc = p->upload(term_loc);
             VPBS_HIP(vpbs::stream_sync(ctx->stream));   // the staging vectors go away
         } catch (const DeviceError& e) {
             (void)vpbs::stream_sync(ctx->stream);
@@ -326,6 +532,11 @@ long vpbs_program_levels(const vpbs_program* prog, unsigned* levels_out) {
 long vpbs_program_run(vpbs_program* prog, vpbs_bootstrapper* bootstrapper, const uint64_t* inputs, const uint64_t* testvs, uint64_t* wires_out,
                       uint64_t* gate_cts_out, uint64_t* out_cts, int on_device) {
     return vpbs::program_run(prog, bootstrapper, inputs, testvs, wires_out, gate_cts_out, out_cts, on_device);
+}
+
+long vpbs_program_run_batch(vpbs_program* prog, vpbs_keyring* ring, const uint64_t* inputs, size_t instances, const uint32_t* key_of,
+                            const uint64_t* testvs, uint64_t* wires_out, uint64_t* gate_cts_out, uint64_t* out_cts, int on_device) {
+    return vpbs::program_run_batch(prog, ring, inputs, instances, key_of, testvs, wires_out, gate_cts_out, out_cts, on_device);
 }
 
 long vpbs_program_prove(vpbs_program* prog, vpbs_pbs_prover* pbs_prover, const uint64_t* inputs, const uint64_t* testvs, unsigned steps,

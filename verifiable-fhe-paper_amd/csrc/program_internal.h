@@ -1,11 +1,12 @@
-// The seam between the program object (program.hip) and the three objects it drives: the Bootstrapper (pbs_batch.hip), the batch prover
-// (pbs_prove_batch.hip) and the batch verifier of whole vPBS proofs (verify_pbs_batch.hip).  A program queues one bootstrap launch per
+// The seam between the program object (program.hip) and the four objects it drives: the Bootstrapper (pbs_batch.hip), the key ring
+// (pbs_keyring.hip), the batch prover (pbs_prove_batch.hip) and the batch verifier of whole vPBS proofs (verify_pbs_batch.hip).  A program queues one bootstrap launch per
 // level behind its own combine kernel and waits once, at the end: it needs the Bootstrapper's launch WITHOUT the wait vpbs_bootstrapper_run
 // ends with, and the shapes of objects whose structs are private to their files.  Library-internal, like ivc_resident.h.
 #pragma once
 #include <cstddef>
 #include <cstdint>
 #include <mutex>
+#include <string>
 
 #include "../../include/vpbs_prover.h"
 
@@ -27,6 +28,28 @@ void lwe_extract_enqueue(void* stream, const uint64_t* d_glwe, unsigned log_N, u
 
 // the batch prover's own Bootstrapper and the mutex that serialises its runs (vpbs_pbs_prover::boot_mu)
 vpbs_bootstrapper* pbs_prover_bootstrapper(vpbs_pbs_prover* p, std::mutex** boot_mu);
+
+// ---- the key ring (pbs_keyring.hip), for vpbs_program_run_batch ----
+struct KeyringShape {
+    vpbs_ctx* ctx;
+    vpbs_tfhe_params prm;
+    unsigned n_lwe;
+    size_t max_keys, max_batch;
+};
+void keyring_shape(const vpbs_keyring* r, KeyringShape* out);
+// the mutex that add, remove and run of the ring take: a caller that queues several launches holds it from its check of the slots to its wait
+std::mutex& keyring_mutex(vpbs_keyring* r);
+// Host-side check of key_of [count] against the ring's slots (the caller holds the mutex): true when every entry names a slot that holds
+// a key set; else false, with vpbs_keyring_run's message in *msg -- `who` is the entry point, `what` the thing entry i stands for
+// ("ciphertext", "instance").
+bool keyring_check_slots(const vpbs_keyring* r, const uint32_t* key_of, size_t count, const char* who, const char* what, std::string* msg);
+// pbs_keyring_kernel for `count` <= max_batch ciphertexts on device pointers, queued on the ring's context's stream: the launch of
+// vpbs_keyring_run(.., on_device = 1) and nothing else -- no copy, no wait, no check.  d_order, d_key_of: [count] in device memory, as the
+// kernel reads them (workgroup w handles ciphertext d_order[w] under slot d_key_of[d_order[w]]); they must stay unchanged until the launch
+// has run.  d_testv: [N], or [count][N] with testv_per_ct.  Any output may be null.  Threads per ciphertext by the ring's rule.  Throws
+// vpbs::DeviceError for a failed launch; the caller holds the mutex and the device (hipSetDevice).
+void keyring_enqueue(vpbs_keyring* r, const uint64_t* d_cts, size_t count, const uint64_t* d_testv, int testv_per_ct, const uint32_t* d_order,
+                     const uint32_t* d_key_of, uint64_t* d_out_ct, uint64_t* d_lwe_out, uint64_t* d_accs_out);
 
 struct PbsVerifierShape {
     vpbs_ctx* ctx;
