@@ -2,7 +2,12 @@
 """Dynamic VALU-instruction count of the product Poseidon permutation on gfx950 (the number quoted in DESIGN.md / bench.py).
 
 Compiles a one-permutation-per-lane kernel to ISA, counts VALU instructions per loop body and multiplies by the trip
-counts (4 + 4 full rounds, 7 fused partial groups, 1 plain partial round).  Needs hipcc only (no GPU)."""
+counts (4 + 4 full rounds, 7 fused partial groups, 1 plain partial round).  Needs hipcc only (no GPU).
+
+Besides the plain sum (what bench.py's constant and the SQ_INSTS_VALU counter mean) the count is split by issue rate, as measured by
+tools/microbench_valu2.hip (profiles/r07_microbench_valu2.txt, one SIMD with 4 waves): FULL-rate instructions take ~2.5 cycles per wave64
+(v_mov_b32, v_add_u32, the two-operand logic and 32-bit shifts), everything else ~4.2-4.6 (v_mad_u64_u32, every carry add, v_cndmask, the
+three-operand and 64-bit forms) -- priced here at 4.4 and 2.5."""
 import os
 import re
 import subprocess
@@ -25,6 +30,16 @@ __global__ void __launch_bounds__(256) permute_batch_kernel(u64* states, size_t 
     for (int k = 0; k < 12; ++k) states[12 * i + k] = s[k];
 }
 '''
+
+
+FULL_RATE = re.compile(r"^\s+v_(mov_b32|add_u32|sub_u32|subrev_u32|xor_b32|and_b32|or_b32|not_b32|lshlrev_b32|lshrrev_b32|ashrrev_i32)(_e32)?\s")
+HALF_CYCLES, FULL_CYCLES = 4.4, 2.5
+
+
+def count(seg):
+    """(VALU instructions, full-rate ones among them)"""
+    valu = [x for x in seg if re.match(r"^\s+v_", x)]
+    return len(valu), sum(1 for x in valu if FULL_RATE.match(x))
 
 
 def main():
@@ -63,14 +78,18 @@ def main():
         m = re.match(r"^\s+s_cbranch_\w+\s+(\.LBB\d+_\d+)", l)
         if m and m.group(1) in labels and labels[m.group(1)] < i:
             seg = body[labels[m.group(1)]:i]
-            loops.append(sum(1 for x in seg if re.match(r"^\s+v_", x)))
-    total_static = sum(1 for x in body if re.match(r"^\s+v_", x))
-    print("static VALU instructions:", total_static, " loop bodies:", loops)
+            loops.append(count(seg))
+    total_static, total_full = count(body)
+    print("static VALU instructions:", total_static, " loop bodies:", [n for n, _ in loops])
     if len(loops) == 3:
-        full_a, group, full_b = loops
-        rest = total_static - sum(loops)   # first constant layer, the plain partial round, canonicalisation, load/store
+        (full_a, fa), (group, fg), (full_b, fb) = loops
+        rest = total_static - full_a - group - full_b   # first constant layer, the plain partial round, canonicalisation, load/store
         dyn = 4 * full_a + 7 * group + 4 * full_b + rest
         print("dynamic VALU instructions per permutation ~ %d  (4 x %d + 7 x %d + 4 x %d + %d)" % (dyn, full_a, group, full_b, rest))
+        full = 4 * fa + 7 * fg + 4 * fb + (total_full - fa - fg - fb)
+        half = dyn - full
+        print("by issue rate: %d half-rate + %d full-rate;  cycle-weighted ~ %d SIMD cycles per wave64 permutation (%.1f / %.1f cycles)"
+              % (half, full, round(half * HALF_CYCLES + full * FULL_CYCLES), HALF_CYCLES, FULL_CYCLES))
 
 
 if __name__ == "__main__":

@@ -89,11 +89,76 @@ KERNEL(k_lshl_add_u64, asm("v_lshl_add_u64 %0, %0, 1, %1" : "+v"(q[i]) : "v"(q[(
 KERNEL(k_cndmask, { asm("v_cndmask_b32_e64 %0, %0, %1, %2" : "+v"(a[i]) : "v"(b[i]), "s"((uint64_t)seed * 0x9E3779B97F4A7C15ull)); })
 KERNEL(k_lshlrev_b64, asm("v_lshlrev_b64 %0, 1, %0" : "+v"(q[i])))
 KERNEL(k_alignbit, asm("v_alignbit_b32 %0, %1, %0, 7" : "+v"(a[i]) : "v"(b[i])))
+// ---- the rows that price a Goldilocks product in cycles: moves, the vcc-selected cndmask, the 64-bit shift that makes {hi, 0} in one
+// instruction, a one-in-three mix of full-rate and half-rate instructions, and the two whole assemblies of the 128-bit product
+KERNEL(k_mov_b32, asm("v_mov_b32 %0, %1" : "+v"(a[i]) : "v"(b[i])))
+KERNEL(k_add_u32_mov, asm("v_add_u32 %0, 0, %1" : "+v"(a[i]) : "v"(b[i])))
+// vcc as the selector: its value does not matter for the rate, the statements only have to keep their order (volatile)
+KERNEL(k_cndmask_e32, asm volatile("v_cndmask_b32_e32 %0, %0, %1, vcc" : "+v"(a[i]) : "v"(b[i])))
+KERNEL(k_cndmask_e32_const, asm volatile("v_cndmask_b32_e32 %0, 0, %1, vcc" : "+v"(a[i]) : "v"(b[i])))
+// the carry adds as the product forms write them: the 32-bit encodings with vcc (the rows above are the 64-bit encodings with an SGPR pair)
+KERNEL(k_add_co_e32, asm volatile("v_add_co_u32_e32 %0, vcc, %1, %0" : "+v"(a[i]) : "v"(b[i]) : "vcc"))
+KERNEL(k_addc_co_e32, asm volatile("v_addc_co_u32_e32 %0, vcc, %1, %0, vcc" : "+v"(a[i]) : "v"(b[i]) : "vcc"))
+KERNEL(k_lshrrev_b64_32, asm("v_lshrrev_b64 %0, 32, %0" : "+v"(q[i])))
+// one v_add_u32 per two v_mad_u64_u32, every chain on its own registers and its own carry SGPR pairs (the add steps a multiplicand of its
+// chain: a fourth register array would put the kernel over the 64 VGPRs that 8 waves per SIMD leave)
+#define M_MIX3(i, S, S0, S1, T, T0, T1) M_MAD(i, S, S0, S1, T, T0, T1) asm("v_mad_u64_u32 %0, " T ", %1, %2, %0" : "+v"(q2[i]) : "v"(c[i]), "v"(b[i]) : T0, T1); asm("v_add_u32 %0, %1, %0" : "+v"(c[i]) : "v"(b[i]));
+__global__ void __launch_bounds__(1024) __attribute__((amdgpu_waves_per_eu(8, 8))) k_mix_mad2_add(uint32_t* out, Stamp* stamps, uint32_t seed) {
+    PROLOGUE _Pragma("unroll") for (int r = 0; r < REPS; ++r) { SP(0, M_MIX3) } EPILOGUE }
+// The assembly of a0 a1 x b0 b1 -> 128 bits as in csrc/gl.h, one dependent chain per wave: a block's four result words are the next block's
+// operands, the blocks alternate between two scratch sets (v40.. / v48..), so that nothing but the assembly itself is issued.  32 blocks
+// per loop iteration (+ 4 moves that hand the last result to the next iteration, the same for every form: 1.5 % of the old form).
+// X = a0, a1, b0, b1 of the block; R0..R7 its scratch set (P01 / P23 / P45 the aligned pairs); SG its carry SGPR pair.
+#define ASM_OLD(...) ASM_OLD_(__VA_ARGS__)
+#define ASM_OLD_(a0, a1, b0, b1, R0, R1, R2, R3, R4, R5, R6, P01, P23, P45, SG) \
+    "v_mad_u64_u32 " P01 ", vcc, " a0 ", " b0 ", 0\n\t" \
+    "v_mad_u64_u32 " P23 ", vcc, " a0 ", " b1 ", 0\n\t" \
+    "v_mad_u64_u32 " P23 ", " SG ", " a1 ", " b0 ", " P23 "\n\t" \
+    "v_mad_u64_u32 " P45 ", vcc, " a1 ", " b1 ", 0\n\t" \
+    "v_cndmask_b32_e64 " R6 ", 0, 1, " SG "\n\t" \
+    "v_add_co_u32_e32 " R1 ", vcc, " R1 ", " R2 "\n\t" \
+    "v_addc_co_u32_e32 " R4 ", vcc, " R4 ", " R3 ", vcc\n\t" \
+    "v_addc_co_u32_e32 " R5 ", vcc, " R5 ", " R6 ", vcc\n\t"
+// chained: P = a0 b0; E = {P.hi, 0}; M = a0 b1 + E; M = a1 b0 + M (carry c); F = {M.hi, c}; H = a1 b1 + F; lo = {P.lo, M.lo}
+#define ASM_CHAIN(...) ASM_CHAIN_(__VA_ARGS__)
+#define ASM_CHAIN_(MOVE, ZERO_E, a0, a1, b0, b1, R0, R1, R2, R3, R4, R5, R6, P01, P23, P45, SG) \
+    "v_mad_u64_u32 " P01 ", vcc, " a0 ", " b0 ", 0\n\t" \
+    ZERO_E(MOVE, R1, R2, R3, P01, P23) \
+    "v_mad_u64_u32 " P23 ", vcc, " a0 ", " b1 ", " P23 "\n\t" \
+    "v_mad_u64_u32 " P23 ", " SG ", " a1 ", " b0 ", " P23 "\n\t" \
+    MOVE(R4, R3) \
+    "v_cndmask_b32_e64 " R5 ", 0, 1, " SG "\n\t" \
+    "v_mad_u64_u32 " P45 ", vcc, " a1 ", " b1 ", " P45 "\n\t" \
+    MOVE(R1, R2)
+#define MOVE_MOV(d, s) "v_mov_b32 " d ", " s "\n\t"
+#define MOVE_ADD(d, s) "v_add_u32 " d ", 0, " s "\n\t"
+#define E_TWO_MOVES(MOVE, R1, R2, R3, P01, P23) MOVE(R2, R1) "v_mov_b32 " R3 ", 0\n\t"
+#define E_SHIFT(MOVE, R1, R2, R3, P01, P23) "v_lshrrev_b64 " P23 ", 32, " P01 "\n\t"
+#define SET_A "v40", "v41", "v42", "v43", "v44", "v45", "v46", "v[40:41]", "v[42:43]", "v[44:45]", "s[80:81]"
+#define SET_B "v48", "v49", "v50", "v51", "v52", "v53", "v54", "v[48:49]", "v[50:51]", "v[52:53]", "s[86:87]"
+#define PAIR_OLD(first) ASM_OLD(first, SET_A) ASM_OLD("v40", "v41", "v44", "v45", SET_B)
+#define PAIR_CHAIN(MOVE, ZERO_E, first) ASM_CHAIN(MOVE, ZERO_E, first, SET_A) ASM_CHAIN(MOVE, ZERO_E, "v40", "v41", "v44", "v45", SET_B)
+#define FROM_OPS "%0", "%1", "%2", "%3"
+#define FROM_B "v48", "v49", "v52", "v53"
+#define X2(a, b) a b
+#define X16(first, rest) X2(first, rest) X2(rest, rest) X2(rest, rest) X2(rest, rest) X2(rest, rest) X2(rest, rest) X2(rest, rest) X2(rest, rest)
+#define KERNEL_PRODUCT(name, FIRST, REST) \
+    __global__ void __launch_bounds__(1024) name(uint32_t* out, Stamp* stamps, uint32_t seed) { \
+        PROLOGUE \
+        asm volatile(X16(FIRST, REST) "v_mov_b32 %0, v48\n\tv_mov_b32 %1, v49\n\tv_mov_b32 %2, v52\n\tv_mov_b32 %3, v53" \
+                     : "+v"(a[0]), "+v"(b[0]), "+v"(c[0]), "+v"(d[0]) \
+                     : : "v40", "v41", "v42", "v43", "v44", "v45", "v46", "v48", "v49", "v50", "v51", "v52", "v53", "v54", "vcc", "s80", "s81", "s86", "s87"); \
+        EPILOGUE }
+KERNEL_PRODUCT(k_product_old, PAIR_OLD(FROM_OPS), PAIR_OLD(FROM_B))
+KERNEL_PRODUCT(k_product_chain_mov, PAIR_CHAIN(MOVE_MOV, E_TWO_MOVES, FROM_OPS), PAIR_CHAIN(MOVE_MOV, E_TWO_MOVES, FROM_B))
+KERNEL_PRODUCT(k_product_chain_add, PAIR_CHAIN(MOVE_ADD, E_TWO_MOVES, FROM_OPS), PAIR_CHAIN(MOVE_ADD, E_TWO_MOVES, FROM_B))
+KERNEL_PRODUCT(k_product_chain_shift, PAIR_CHAIN(MOVE_MOV, E_SHIFT, FROM_OPS), PAIR_CHAIN(MOVE_MOV, E_SHIFT, FROM_B))
 typedef void (*kern_t)(uint32_t*, Stamp*, uint32_t);
 struct Entry {
     const char* name;
     kern_t k;
     int instr_per_body;   // wave instructions per chain step
+    bool per_block;       // report cycles per chain step (a whole product assembly), not per instruction
 };
 
 int main() {
@@ -108,6 +173,11 @@ int main() {
         {"v_mad_u64_u32 (vgpr x sgpr)", k_mad_u64_u32_s, 1}, {"v_add_co_u32_e64", k_add_co_u32, 1}, {"add_u64 (add_co+addc)", k_add_u64, 2},
         {"v_lshl_add_u64", k_lshl_add_u64, 1}, {"v_cndmask_b32_e64", k_cndmask, 1}, {"v_lshlrev_b64", k_lshlrev_b64, 1},
         {"v_alignbit_b32", k_alignbit, 1}, {"mix: mad_u64_u32 + add_co", k_mix_poseidon, 2},
+        {"v_mov_b32", k_mov_b32, 1}, {"v_add_u32 dst, 0, src", k_add_u32_mov, 1}, {"v_cndmask_b32_e32 (vcc)", k_cndmask_e32, 1},
+        {"v_cndmask_b32_e32 0, x, vcc", k_cndmask_e32_const, 1}, {"v_add_co_u32_e32 (vcc)", k_add_co_e32, 1}, {"v_addc_co_u32_e32 (vcc)", k_addc_co_e32, 1}, {"v_lshrrev_b64 by 32", k_lshrrev_b64_32, 1},
+        {"mix: 2 mad_u64_u32 + add_u32", k_mix_mad2_add, 3},
+        {"product: old (8 half)", k_product_old, 1, true}, {"product: chained, v_mov (5+4)", k_product_chain_mov, 1, true},
+        {"product: chained, v_add (5+4)", k_product_chain_add, 1, true}, {"product: chained, shift (6+2)", k_product_chain_shift, 1, true},
     };
     const int ws[] = {1, 2, 4, 8};
     const size_t max_threads = (size_t)cus * 2048;
@@ -119,6 +189,7 @@ int main() {
     hipEvent_t ev0, ev1;
     CHECK(hipEventCreate(&ev0));
     CHECK(hipEventCreate(&ev1));
+    printf("rows named product: cycles of one SIMD per whole assembly of the 128-bit product (a block of dependent instructions)\n");
     printf("cycles of one SIMD per wave64 instruction: in-kernel span of the SIMD's waves / from the HIP-event time of the launch\n");
     printf("%-30s", "");
     for (int w : ws) printf("  w=%d per SIMD", w);

@@ -102,10 +102,17 @@ GL_HD u64 reduce128_nc(u64 lo, u64 hi) {
 // Hand-scheduled gfx950 forms (bit-identical residues are not required between forms; all results are congruent mod p
 // and every consumer accepts any u64 residue).  They use fixed scratch registers v80..v87 / s[80:87], declared as
 // clobbers, because a 64-bit inline-asm operand cannot name its halves and v_mad_u64_u32 needs aligned pairs.
-//   product: 4 v_mad_u64_u32 (the a1*b0 term is accumulated onto a0*b1 with its carry-out kept in an SGPR pair) + 3 adds
+//   product: 4 v_mad_u64_u32 CHAINED -- each partial product takes what the previous one leaves above its low word as its 64-bit addend:
+//            P = a0 b0;  E = {P.hi, 0};  M = a0 b1 + E;  M = a1 b0 + M (carry c);  F = {M.hi, c};  H = a1 b1 + F;  product = {P.lo, M.lo, H}
+//            a0 b1 + E cannot overflow: (2^32 - 1)^2 + 2^32 - 1 < 2^64;  a1 b1 + F cannot either: it is the top half of a product < 2^128.
+//            A result's high word always sits in an odd register and a pair starts at an even one, so the addend pairs are put together:
+//            E by one v_lshrrev_b64 by 32, F.lo and the low pair's M.lo by v_mov_b32 -- full-rate instructions (2.5 cycles per wave64 on a
+//            SIMD with 4 waves, where v_mad_u64_u32, the carry adds and v_cndmask_b32_e64 take 4.2-4.6).  6 half-rate + 2 full-rate: 25.8
+//            cycles measured, where adding the partial products afterwards (8 half-rate) took 32.2, two moves for E 26.2 and moves written
+//            as v_add_u32 dst, 0, src 30.4 (tools/microbench_valu2.hip, profiles/r07_microbench_valu2.txt).
 //   reduce : u = hi_lo * (2^32-1) + lo as ONE v_mad_u64_u32 with carry-out c; r = u - hi_hi with borrow b;
 //            r += (c - b) * (2^32 - 1)  -- neither correction can wrap a second time
-// 16 VALU + 2 SALU instead of the 26 VALU hipcc emits for the C form below.
+// 12 half-rate + 2 full-rate VALU + 1 SALU instead of the 26 VALU hipcc emits for the C form below.
 // Scratch registers of the single-product form.  A translation unit whose kernels need few registers of their own (the
 // NTT kernels) defines GL_ASM_SCRATCH_LOW before including this header: the scratch block then sits at v24..v31 instead
 // of v80..v87, so those kernels are not pushed from ~50 to 96 VGPRs (5 -> 8 waves per SIMD).
@@ -159,6 +166,7 @@ GL_HD u64 reduce128_nc(u64 lo, u64 hi) {
 // b needs u < R5 < 2^32, i.e. one product in 2^32: the borrow's correction (r -= 2^32 - 1, applied FIRST so that the carry's correction
 // cannot wrap) sits behind a wave-level branch that is practically never taken, and the common path pays only the carry's correction:
 // 6 VALU where computing both corrections as one signed addend took 8 VALU + 2 SALU (round 5).
+#define GL_MOV(DST, SRC) "v_mov_b32 " DST ", " SRC "\n\t"
 #define GL_REDUCE_TAIL(UNIQ)                                                          \
     "v_mad_u64_u32 " GL_P01 ", s[80:81], " GL_R4 ", -1, " GL_P01 "\n\t"                \
     "v_sub_co_u32_e32 " GL_R0 ", vcc, " GL_R0 ", " GL_R5 "\n\t"                         \
@@ -173,14 +181,14 @@ GL_HD u64 reduce128_nc(u64 lo, u64 hi) {
     "v_addc_co_u32_e64 %1, vcc, " GL_R1 ", 0, vcc"
 __device__ __forceinline__ u64 mul_nc(u64 a, u64 b) {
     u32 r0, r1;
-    asm("v_mad_u64_u32 " GL_P01 ", vcc, %2, %4, 0\n\t"
-        "v_mad_u64_u32 " GL_P23 ", vcc, %2, %5, 0\n\t"
-        "v_mad_u64_u32 " GL_P23 ", s[80:81], %3, %4, " GL_P23 "\n\t"
-        "v_mad_u64_u32 " GL_P45 ", vcc, %3, %5, 0\n\t"
-        "v_cndmask_b32_e64 " GL_R6 ", 0, 1, s[80:81]\n\t"
-        "v_add_co_u32_e32 " GL_R1 ", vcc, " GL_R1 ", " GL_R2 "\n\t"
-        "v_addc_co_u32_e32 " GL_R4 ", vcc, " GL_R4 ", " GL_R3 ", vcc\n\t"
-        "v_addc_co_u32_e32 " GL_R5 ", vcc, " GL_R5 ", " GL_R6 ", vcc\n\t"
+    asm("v_mad_u64_u32 " GL_P01 ", vcc, %2, %4, 0\n\t"                       // P = a0 b0
+        "v_lshrrev_b64 " GL_P23 ", 32, " GL_P01 "\n\t"                        // E = {P.hi, 0}
+        "v_mad_u64_u32 " GL_P23 ", vcc, %2, %5, " GL_P23 "\n\t"              // M = a0 b1 + E
+        "v_mad_u64_u32 " GL_P23 ", s[80:81], %3, %4, " GL_P23 "\n\t"         // M = a1 b0 + M, carry c
+        GL_MOV(GL_R4, GL_R3)                                                  // F = {M.hi, c}
+        "v_cndmask_b32_e64 " GL_R5 ", 0, 1, s[80:81]\n\t"
+        "v_mad_u64_u32 " GL_P45 ", vcc, %3, %5, " GL_P45 "\n\t"              // H = a1 b1 + F
+        GL_MOV(GL_R1, GL_R2)                                                  // low 64 bits = {P.lo, M.lo}
         GL_REDUCE_TAIL("%=")
         : "=&v"(r0), "=&v"(r1)
         : "v"((u32)a), "v"((u32)(a >> 32)), "v"((u32)b), "v"((u32)(b >> 32))
@@ -192,22 +200,23 @@ __device__ __forceinline__ u64 mul_nc(u64 a, u64 b) {
 // Poseidon).  r = a * b, q = c * d.
 __device__ __forceinline__ void mul2_nc(u64 a, u64 b, u64 c, u64 d, u64& r, u64& q) {
     u32 r0, r1, q0, q1;
+    // both products chained as in mul_nc (2 x (6 half-rate + 2 full-rate) for the assemblies)
     asm("v_mad_u64_u32 v[80:81], vcc, %4, %6, 0\n\t"
         "v_mad_u64_u32 v[88:89], vcc, %8, %10, 0\n\t"
-        "v_mad_u64_u32 v[82:83], vcc, %4, %7, 0\n\t"
-        "v_mad_u64_u32 v[90:91], vcc, %8, %11, 0\n\t"
+        "v_lshrrev_b64 v[82:83], 32, v[80:81]\n\t"
+        "v_lshrrev_b64 v[90:91], 32, v[88:89]\n\t"
+        "v_mad_u64_u32 v[82:83], vcc, %4, %7, v[82:83]\n\t"
+        "v_mad_u64_u32 v[90:91], vcc, %8, %11, v[90:91]\n\t"
         "v_mad_u64_u32 v[82:83], s[80:81], %5, %6, v[82:83]\n\t"
         "v_mad_u64_u32 v[90:91], s[86:87], %9, %10, v[90:91]\n\t"
-        "v_mad_u64_u32 v[84:85], vcc, %5, %7, 0\n\t"
-        "v_mad_u64_u32 v[92:93], vcc, %9, %11, 0\n\t"
-        "v_cndmask_b32_e64 v86, 0, 1, s[80:81]\n\t"
-        "v_cndmask_b32_e64 v94, 0, 1, s[86:87]\n\t"
-        "v_add_co_u32_e32 v81, vcc, v81, v82\n\t"
-        "v_addc_co_u32_e32 v84, vcc, v84, v83, vcc\n\t"
-        "v_addc_co_u32_e32 v85, vcc, v85, v86, vcc\n\t"
-        "v_add_co_u32_e32 v89, vcc, v89, v90\n\t"
-        "v_addc_co_u32_e32 v92, vcc, v92, v91, vcc\n\t"
-        "v_addc_co_u32_e32 v93, vcc, v93, v94, vcc\n\t"
+        GL_MOV("v84", "v83")
+        "v_cndmask_b32_e64 v85, 0, 1, s[80:81]\n\t"
+        GL_MOV("v92", "v91")
+        "v_cndmask_b32_e64 v93, 0, 1, s[86:87]\n\t"
+        "v_mad_u64_u32 v[84:85], vcc, %5, %7, v[84:85]\n\t"
+        "v_mad_u64_u32 v[92:93], vcc, %9, %11, v[92:93]\n\t"
+        GL_MOV("v81", "v82")
+        GL_MOV("v89", "v90")
         // both reductions (GL_REDUCE_TAIL): the two borrows share ONE practically-never-taken branch
         "v_mad_u64_u32 v[80:81], s[80:81], v84, -1, v[80:81]\n\t"
         "v_mad_u64_u32 v[88:89], s[86:87], v92, -1, v[88:89]\n\t"
@@ -242,27 +251,26 @@ __device__ __forceinline__ void mul2_nc(u64 a, u64 b, u64 c, u64 d, u64& r, u64&
 // lo + hi_lo 2^64 + (hi_hi + k 2^32) 2^96 is reduced as in mul_nc.  The subtrahend hi_hi + k 2^32 is below 2^33 instead of 2^32, and
 // the single correction (c - b)(2^32 - 1) still cannot wrap: c = 1 means u < 2^64 - 2^33 + 1, so u + 2^32 - 1 < 2^64; b = 1 without c
 // means the wrapped difference is at least 2^64 - 2^33, so taking 2^32 - 1 away stays positive.  Any u64 residues in, a residue out.
-// 29 VALU + 2 SALU against 2 x 16 + 8 for two products and a modular addition.
+// Both products are chained as in mul_nc; their low pairs {P.lo, M.lo} need no move here, the 128-bit addition reads the words where they lie.
+// 23 half-rate + 2 full-rate VALU + 1 SALU against 2 x 14 + 8 for two products and a modular addition.
 __device__ __forceinline__ u64 dot2_nc(u64 a, u64 b, u64 c, u64 d) {
     u32 r0, r1;
     asm("v_mad_u64_u32 " GL_P01 ", vcc, %2, %4, 0\n\t"
         "v_mad_u64_u32 " GL_Q01 ", vcc, %6, %8, 0\n\t"
-        "v_mad_u64_u32 " GL_P23 ", vcc, %2, %5, 0\n\t"
-        "v_mad_u64_u32 " GL_Q23 ", vcc, %6, %9, 0\n\t"
+        "v_lshrrev_b64 " GL_P23 ", 32, " GL_P01 "\n\t"
+        "v_lshrrev_b64 " GL_Q23 ", 32, " GL_Q01 "\n\t"
+        "v_mad_u64_u32 " GL_P23 ", vcc, %2, %5, " GL_P23 "\n\t"
+        "v_mad_u64_u32 " GL_Q23 ", vcc, %6, %9, " GL_Q23 "\n\t"
         "v_mad_u64_u32 " GL_P23 ", s[80:81], %3, %4, " GL_P23 "\n\t"
         "v_mad_u64_u32 " GL_Q23 ", s[86:87], %7, %8, " GL_Q23 "\n\t"
-        "v_mad_u64_u32 " GL_P45 ", vcc, %3, %5, 0\n\t"
-        "v_mad_u64_u32 " GL_Q45 ", vcc, %7, %9, 0\n\t"
-        "v_cndmask_b32_e64 " GL_R6 ", 0, 1, s[80:81]\n\t"
-        "v_cndmask_b32_e64 " GL_Q6 ", 0, 1, s[86:87]\n\t"
-        "v_add_co_u32_e32 " GL_R1 ", vcc, " GL_R1 ", " GL_R2 "\n\t"
-        "v_addc_co_u32_e32 " GL_R4 ", vcc, " GL_R4 ", " GL_R3 ", vcc\n\t"
-        "v_addc_co_u32_e32 " GL_R5 ", vcc, " GL_R5 ", " GL_R6 ", vcc\n\t"
-        "v_add_co_u32_e32 " GL_Q1 ", vcc, " GL_Q1 ", " GL_Q2 "\n\t"
-        "v_addc_co_u32_e32 " GL_Q4 ", vcc, " GL_Q4 ", " GL_Q3 ", vcc\n\t"
-        "v_addc_co_u32_e32 " GL_Q5 ", vcc, " GL_Q5 ", " GL_Q6 ", vcc\n\t"
+        GL_MOV(GL_R4, GL_R3)
+        "v_cndmask_b32_e64 " GL_R5 ", 0, 1, s[80:81]\n\t"
+        GL_MOV(GL_Q4, GL_Q3)
+        "v_cndmask_b32_e64 " GL_Q5 ", 0, 1, s[86:87]\n\t"
+        "v_mad_u64_u32 " GL_P45 ", vcc, %3, %5, " GL_P45 "\n\t"
+        "v_mad_u64_u32 " GL_Q45 ", vcc, %7, %9, " GL_Q45 "\n\t"
         "v_add_co_u32_e32 " GL_R0 ", vcc, " GL_R0 ", " GL_Q0 "\n\t"
-        "v_addc_co_u32_e32 " GL_R1 ", vcc, " GL_R1 ", " GL_Q1 ", vcc\n\t"
+        "v_addc_co_u32_e32 " GL_R1 ", vcc, " GL_R2 ", " GL_Q2 ", vcc\n\t"
         "v_addc_co_u32_e32 " GL_R4 ", vcc, " GL_R4 ", " GL_Q4 ", vcc\n\t"
         "v_addc_co_u32_e32 " GL_R5 ", vcc, " GL_R5 ", " GL_Q5 ", vcc\n\t"
         "v_addc_co_u32_e64 " GL_R6 ", vcc, 0, 0, vcc\n\t"
@@ -281,27 +289,27 @@ __device__ __forceinline__ u64 dot2_nc(u64 a, u64 b, u64 c, u64 d) {
         : "=&v"(r0), "=&v"(r1)
         : "v"((u32)a), "v"((u32)(a >> 32)), "v"((u32)b), "v"((u32)(b >> 32)), "v"((u32)c), "v"((u32)(c >> 32)), "v"((u32)d),
           "v"((u32)(d >> 32))
-        : GL_R0, GL_R1, GL_R2, GL_R3, GL_R4, GL_R5, GL_R6, GL_R7, GL_Q0, GL_Q1, GL_Q2, GL_Q3, GL_Q4, GL_Q5, GL_Q6, "vcc", "scc",
+        : GL_R0, GL_R1, GL_R2, GL_R3, GL_R4, GL_R5, GL_R6, GL_R7, GL_Q0, GL_Q1, GL_Q2, GL_Q3, GL_Q4, GL_Q5, "vcc", "scc",
           "s80", "s81", "s86", "s87");
     return ((u64)r1 << 32) | r0;
 }
-// a * b + c with one reduction (the product plus a 64-bit addend stays below 2^128).  Any residues in, a residue out; 16 VALU.
+// a * b + c with one reduction (the product plus a 64-bit addend stays below 2^128).  Any residues in, a residue out; 12 half-rate + 3 full-rate VALU.
 __device__ __forceinline__ u64 mad_nc(u64 a, u64 b, u64 c) {
     u32 r0, r1;
-    // c is the 64-bit addend of the first multiply-add (T = a0 b0 + c, carry kc); kc joins the high half as a carry-in: two adds where
-    // adding c to the assembled product took four (round 5).  (The fully chained form -- every partial product taking the previous one's
-    // high word as its addend, 6 instead of 8 VALU for the assembly -- needs the register pairs {T1, 0} and {U1, k}, and gfx950 wants VGPR
-    // pairs 64-bit aligned: a result's high word always sits in an odd register.)
-    asm("v_mad_u64_u32 " GL_P01 ", s[82:83], %2, %4, %6\n\t"
-        "v_mad_u64_u32 " GL_P23 ", vcc, %2, %5, 0\n\t"
-        "v_mad_u64_u32 " GL_P23 ", s[80:81], %3, %4, " GL_P23 "\n\t"
-        "v_mad_u64_u32 " GL_P45 ", vcc, %3, %5, 0\n\t"
-        "v_cndmask_b32_e64 " GL_R6 ", 0, 1, s[80:81]\n\t"
-        "v_add_co_u32_e32 " GL_R1 ", vcc, " GL_R1 ", " GL_R2 "\n\t"
-        "v_addc_co_u32_e32 " GL_R4 ", vcc, " GL_R4 ", " GL_R3 ", vcc\n\t"
-        "v_addc_co_u32_e32 " GL_R5 ", vcc, " GL_R5 ", " GL_R6 ", vcc\n\t"
-        "v_addc_co_u32_e64 " GL_R4 ", vcc, " GL_R4 ", 0, s[82:83]\n\t"
-        "v_addc_co_u32_e64 " GL_R5 ", vcc, " GL_R5 ", 0, vcc\n\t"
+    // c is the 64-bit addend of the first multiply-add (T = a0 b0 + c, carry kc), and the chain of mul_nc goes on from T: kc weighs 2^64,
+    // which is the high word of E = {T.hi, kc} -- a v_cndmask in the place of mul_nc's zero.  a0 b1 + E cannot overflow:
+    // E = floor(T / 2^32) <= floor(((2^32 - 1)^2 + 2^64 - 1) / 2^32) = 2^33 - 2, and (2^32 - 1)^2 + 2^33 - 2 = 2^64 - 1;  a1 b1 + F cannot
+    // either: it is the top half of a b + c < 2^128.  6 half-rate + 3 full-rate for the assembly where adding kc behind the partial
+    // products took 10 half-rate (round 5).
+    asm("v_mad_u64_u32 " GL_P01 ", s[82:83], %2, %4, %6\n\t"                 // T = a0 b0 + c, carry kc
+        GL_MOV(GL_R2, GL_R1)                                                  // E = {T.hi, kc}
+        "v_cndmask_b32_e64 " GL_R3 ", 0, 1, s[82:83]\n\t"
+        "v_mad_u64_u32 " GL_P23 ", vcc, %2, %5, " GL_P23 "\n\t"              // M = a0 b1 + E
+        "v_mad_u64_u32 " GL_P23 ", s[80:81], %3, %4, " GL_P23 "\n\t"         // M = a1 b0 + M, carry c
+        GL_MOV(GL_R4, GL_R3)                                                  // F = {M.hi, c}
+        "v_cndmask_b32_e64 " GL_R5 ", 0, 1, s[80:81]\n\t"
+        "v_mad_u64_u32 " GL_P45 ", vcc, %3, %5, " GL_P45 "\n\t"              // H = a1 b1 + F
+        GL_MOV(GL_R1, GL_R2)                                                  // low 64 bits = {T.lo, M.lo}
         GL_REDUCE_TAIL("%=")
         : "=&v"(r0), "=&v"(r1)
         : "v"((u32)a), "v"((u32)(a >> 32)), "v"((u32)b), "v"((u32)(b >> 32)), "v"(c)
