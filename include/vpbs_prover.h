@@ -1080,6 +1080,52 @@ int vpbs_pbs_prover_set_checkpoint(vpbs_pbs_prover* p, unsigned every, vpbs_pbs_
 int vpbs_pbs_prover_last_run(const vpbs_pbs_prover* p, vpbs_pbs_run_stats* out);
 void vpbs_pbs_prover_free(vpbs_pbs_prover* p);
 
+/* ---- proving mixed batches under many resident key sets (csrc/pbs_prove_ring.hip) ----
+ * One prover for all clients of a key ring: the object owns a vpbs_keyring of max_keys slots, `chains` chains of the device-witness
+ * pipeline and, per slot, the key hash chain of that slot's keys.  Ciphertext i of a run is bootstrapped AND proven under the key set of
+ * slot key_of[i]; its proof is byte for byte what a vpbs_pbs_prover made with that key set delivers for it.  The chains (the large
+ * allocations) are shared by all key sets, and every key set is resident once, in the ring.
+ *   create: the refusals of vpbs_pbs_prover_create (null arguments, chains = 0 or above 64, witness_batch = 0, the TFHE parameters) and those
+ *           of vpbs_keyring_create with its message passed through (a shape above the 160 KiB of LDS a workgroup may declare, n_lwe above
+ *           (K - 1) N, max_keys outside 1 .. 65535).  No key set yet.  The ring bootstraps 256 rows per launch.
+ *   add:    vpbs_keyring_add on the owned ring (upload, or adoption of device pointers that must outlive the slot), and the key hash chain
+ *           over [0^ggsw_len, bsk_0 .. bsk_{n-1}, ksk], walked once ON THE HOST (vpbs_hash_chain_links; concurrent adds share its lanes)
+ *           with all n_lwe + 2 links kept for the slot on the host and on the device.  Device-only keys are downloaded once for this; after
+ *           add the object holds no host copy of the keys.  *slot is the lowest free slot number.
+ *   remove: drops the slot's links and its ring entry; VPBS_ERR_INVALID for a slot that holds no key set.  A later add that gets the same
+ *           number starts from nothing.
+ *   key_hash: the end of the slot's key hash chain -- what vpbs_pbs_verifier_create wants for the proofs of that slot.  VPBS_ERR_INVALID
+ *           for a slot that was never filled or has been emptied.
+ *   keyring: the owned ring, for vpbs_keyring_run and vpbs_program_run_batch on the same resident keys (they take turns with the chains
+ *           under the ring's mutex).  The caller never frees it.  The key links live in the prover, so vpbs_keyring_add and
+ *           vpbs_keyring_remove called on this ring directly are REFUSED (VPBS_ERR_INVALID, a message that names vpbs_ring_prover_add;
+ *           the ring is unchanged).  context: the ring's context (vpbs_last_error of the calls on the ring; device memory for them).
+ *   run:    as vpbs_pbs_prover_run, plus key_of [count], a HOST array, checked against the ring's slots before anything is queued: an entry
+ *           at or above max_keys, or an empty slot, returns VPBS_ERR_INVALID with the ring's message (the ciphertext and the slot) in err,
+ *           calls proof_fn zero times and writes no output word.  All outputs come first, in key-ring launches of 256 rows; then the
+ *           workers take indices from a queue: per ciphertext a count-1 vpbs_keyring_run under its slot leaves the chain's accumulators on
+ *           the device, and the preset matrices are assembled from that slot's resident bsk, ksk and key links.  count == 0 returns 0.
+ *   verifier_data, set_check_witness, witness_checks, set_checkpoint, last_run: as on vpbs_pbs_prover.
+ * add, remove and run of one object exclude each other for the whole of a run: no slot changes under a chain that is being proven. */
+typedef struct vpbs_ring_prover vpbs_ring_prover;
+int vpbs_ring_prover_create(int device_ordinal, const vpbs_ivc_circuit* cyclic, const vpbs_ivc_circuit* dummy, const vpbs_tfhe_params* params,
+                            unsigned n_lwe, size_t max_keys, unsigned chains, unsigned witness_batch, vpbs_ring_prover** out, char* err,
+                            size_t err_len);
+int vpbs_ring_prover_add(vpbs_ring_prover* p, const uint64_t* bsk, const uint64_t* ksk, int keys_on_device, unsigned* slot, char* err,
+                         size_t err_len);
+int vpbs_ring_prover_remove(vpbs_ring_prover* p, unsigned slot, char* err, size_t err_len);
+int vpbs_ring_prover_key_hash(vpbs_ring_prover* p, unsigned slot, uint64_t out[4]);
+vpbs_keyring* vpbs_ring_prover_keyring(vpbs_ring_prover* p);
+vpbs_ctx* vpbs_ring_prover_context(vpbs_ring_prover* p);
+long vpbs_ring_prover_run(vpbs_ring_prover* p, const uint64_t* cts, size_t count, const uint32_t* key_of, const uint64_t* testv, int testv_per_ct,
+                          unsigned steps, uint64_t* out_ct, uint64_t* lwe_out, vpbs_pbs_proof_fn proof_fn, void* user, char* err, size_t err_len);
+int vpbs_ring_prover_verifier_data(const vpbs_ring_prover* p, uint64_t* cyclic_vk, uint64_t* dummy_vk);
+int vpbs_ring_prover_set_check_witness(vpbs_ring_prover* p, int on);
+int vpbs_ring_prover_witness_checks(const vpbs_ring_prover* p, uint64_t out[2]);
+int vpbs_ring_prover_set_checkpoint(vpbs_ring_prover* p, unsigned every, vpbs_pbs_checkpoint_fn fn, void* user);
+int vpbs_ring_prover_last_run(const vpbs_ring_prover* p, vpbs_pbs_run_stats* out);
+void vpbs_ring_prover_free(vpbs_ring_prover* p);
+
 /* ---- programs of lookup gates on resident keys (csrc/program.hip) ----
  * A program is a netlist of bootstraps.  Wire w < n_inputs is program input w; wire n_inputs + g is the output of gate g; every wire is an
  * LWE ciphertext of n_lwe + 1 words under the input key.  The input ciphertext of gate g is
@@ -1124,6 +1170,13 @@ void vpbs_pbs_prover_free(vpbs_pbs_prover* p);
  *           vpbs_pbs_prover_run: proof g is byte for byte what that call makes of (c_g, testvs[gate_lut[g]]) and reaches proof_fn with the
  *           caller's gate index; failure semantics (a failing chain reports its index, the others go on) and `steps` are that call's.  Host
  *           pointers; wires_out and out_cts may be NULL.  Returns the number of proofs delivered or a negative status.
+ *   prove_batch: run_batch on the ring of a ring prover (above), then every gate input of every instance to vpbs_ring_prover_run under
+ *           that instance's slot: proof_fn gets index b * n_gates + g, and that proof is byte for byte what vpbs_program_prove delivers for
+ *           gate g of inputs[b] on a vpbs_pbs_prover of the key set in slot key_of[b].  wires_out and out_cts (either may be NULL) carry the
+ *           leading instance axis, as in run_batch.  Host pointers.  The refusals are run_batch's (the message in err, prefixed), plus a
+ *           null ring prover, no proof_fn and steps > n_lwe + 2; nothing is queued and proof_fn is not called.  The call holds the ring
+ *           prover's mutex from the evaluation to the last proof.  Verification stays per client: vpbs_program_verify with a verifier
+ *           made from vpbs_ring_prover_key_hash(slot).  Returns the number of proofs delivered or a negative status.
  *   verify: takes the CLAIMED output GLWEs of all gates (out_cts [n_gates][K][N]) and the proofs (bytes, offsets [n_gates + 1], gate order).
  *           The wire table is rebuilt as inputs followed by the extraction (partial_sample_extract) of every claimed output, the inputs of
  *           ALL gates are combined in one launch -- verification has no level order -- and vpbs_pbs_verifier_run checks the proofs, in
@@ -1153,6 +1206,9 @@ long vpbs_program_run_batch(vpbs_program* prog, vpbs_keyring* ring, const uint64
                             uint64_t* out_cts /* [instances][n_gates][K][N] or NULL */, int on_device);
 long vpbs_program_prove(vpbs_program* prog, vpbs_pbs_prover* pbs_prover, const uint64_t* inputs, const uint64_t* testvs, unsigned steps,
                         uint64_t* wires_out, uint64_t* out_cts, vpbs_pbs_proof_fn proof_fn, void* user, char* err, size_t err_len);
+long vpbs_program_prove_batch(vpbs_program* prog, vpbs_ring_prover* ring_prover, const uint64_t* inputs /* [instances][n_inputs][n_lwe + 1] */,
+                              size_t instances, const uint32_t* key_of /* [instances], HOST array */, const uint64_t* testvs, unsigned steps,
+                              uint64_t* wires_out, uint64_t* out_cts, vpbs_pbs_proof_fn proof_fn, void* user, char* err, size_t err_len);
 long vpbs_program_verify(vpbs_program* prog, vpbs_pbs_verifier* pbs_verifier, const uint64_t* inputs, const uint64_t* testvs,
                          const uint64_t* out_cts, const uint8_t* proofs, const size_t* offsets /* [n_gates + 1] */, uint8_t* verdicts /* [n_gates] */,
                          uint8_t* reasons /* [n_gates] or NULL */, uint8_t* proof_reasons /* [n_gates] or NULL */);

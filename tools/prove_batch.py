@@ -5,6 +5,7 @@ ALL proofs through api.PbsVerifier built from the prover's key_hash() and all lw
 reference's main.rs:59-64).  One JSON line.
 
 usage: tools/prove_batch.py [--count M] [--chains C] [--witness-batch B] [--steps K] [--n2048 | --n8] [--keys-on-device] [--baseline]
+                            [--keys M [--baseline]]
   --steps K < n + 2 proves a prefix of every chain (tests); the proofs are then checked by api.verify_pbs_prefix on the host (verify_pbs
     insists on counter = n + 2); the outputs are those of the whole bootstrap either way.
   --n8: the N = 8, n = 6 miniature (degree 2^13); --n2048: N = 2048 (degree 2^17); default: the paper's N = 1024, n = 728 (degree 2^16).
@@ -12,7 +13,13 @@ usage: tools/prove_batch.py [--count M] [--chains C] [--witness-batch B] [--step
     host arrays).
   --baseline: the same batch the way it was done before PbsProver existed, using only api of that time -- C threads, each with its own
     Context + Ivc.set_device_witness(ELL, LOGB, B) + Ivc.prove_pbs on host keys, outputs from each chain's proof -- so that this file can be
-    copied into a build of an older commit and run there."""
+    copied into a build of an older commit and run there.
+  --keys M: the batch spread over M seeded key sets (ciphertext i under key set i mod M) on ONE api.RingProver: every proof is verified by
+    an api.PbsVerifier made from the key hash of its own slot, every output decrypted under its own key.  --keys M --baseline: the same
+    with M api.PbsProver objects, one after the other, each proving the ciphertexts of its key set (it needs nothing newer than
+    api.PbsProver, so this file can be copied into a build of an older commit).  Both print one JSON line with the wall time (seconds),
+    proofs, device_bytes_held_by_the_provers (hipMemGetInfo before the first create and after the last), seconds_until_out_ct_complete and
+    prepare_chain_ms."""
 import argparse
 import json
 import os
@@ -126,6 +133,91 @@ def prove_baseline(args, N, n_lwe, log_n, cyc_path, dum_path, keys, cts, testv):
                                                                         "early_witness_ms_per_step": mean["early_witness_ms"]}
 
 
+def device_bytes_free():
+    free, _ = torch.cuda.mem_get_info(0)   # hipMemGetInfo
+    return int(free)
+
+
+def main_keys(args, N, n_lwe, log_n):
+    """--keys M [--baseline]: see the module text"""
+    M, count = args.keys, args.count
+    cyc_path, dum_path = circuit_file.find_cyclic_circuit(N, K, ELL, LOGB, n_lwe, log_n)
+    cyc, dum = circuit_file.load(cyc_path), circuit_file.load(dum_path)
+    ctx = vpbs_amd.Context(0, log_n_max=max(16, log_n))
+    keys = [ctx.keygen(N, K, ELL, LOGB, n_lwe, SEED + k, SIGMA_GLWE, SIGMA_LWE) for k in range(M)]
+    testv, delta = api.testv(N, 2)
+    key_of = [i % M for i in range(count)]
+    msgs = [(3 * i + i // 2) % 2 for i in range(count)]
+    cts = np.stack([api.lwe_encrypt(keys[k]["params"], keys[k]["s_lwe"], delta * m % P, nonce=i) for i, (m, k) in enumerate(zip(msgs, key_of))])
+    mine = [[i for i in range(count) if key_of[i] == k] for k in range(M)]
+    proofs, out_ct, lwe_out = [None] * count, np.zeros((count, K, N), np.uint64), np.zeros((count, n_lwe + 1), np.uint64)
+    ctx.synchronize()
+    load0, free0 = os.getloadavg()[0], device_bytes_free()
+    t0 = time.perf_counter()
+    if args.baseline:
+        provers = [api.PbsProver(0, cyc, dum, keys[k]["bsk"], keys[k]["ksk"], K, ELL, LOGB, chains=args.chains, witness_batch=args.witness_batch)
+                   for k in range(M)]
+        held, t_made = free0 - device_bytes_free(), time.perf_counter()
+        t_out, prepare, n_proofs = 0.0, [], 0
+        for k, p in enumerate(provers):           # one after the other: the outputs of the last key set wait for the proofs of all before
+            if not mine[k]:
+                continue
+            t_k = time.perf_counter()
+            got, o, l = p.prove(cts[mine[k]], testv, steps=args.steps)
+            run = p.last_run()
+            for j, i in enumerate(mine[k]):
+                proofs[i], out_ct[i], lwe_out[i] = got[j], o[j], l[j]
+            t_out = t_k - t_made + run["outputs_seconds"]
+            prepare.append(run["prepare_chain_ms"] * run["proofs"])
+            n_proofs += run["proofs"]
+        hashes, vk = [p.key_hash() for p in provers], provers[0].verifier_data()[0]
+        for p in provers:
+            p.close()
+        prepare_ms = sum(prepare) / max(n_proofs, 1)
+    else:
+        rp = api.RingProver(0, cyc, dum, K, ELL, LOGB, N, n_lwe, max_keys=M, chains=args.chains, witness_batch=args.witness_batch)
+        for k in range(M):
+            assert rp.add(keys[k]["bsk"], keys[k]["ksk"]) == k
+        held, t_made = free0 - device_bytes_free(), time.perf_counter()
+        proofs, out_ct, lwe_out = rp.prove(cts, key_of, testv, steps=args.steps)
+        run = rp.last_run()
+        t_out, prepare_ms, n_proofs = run["outputs_seconds"], run["prepare_chain_ms"], run["proofs"]
+        hashes, vk = [rp.key_hash(k) for k in range(M)], rp.verifier_data()[0]
+        rp.close()
+    t_end = time.perf_counter()
+    # ---- after the clock: every proof under the key hash of its own slot, every output under its own key ----
+    total = n_lwe + 2
+    whole = args.steps in (0, total)
+    ncols, cap = [cyc.n_constants + 80, 135, 20, 16], vk[4:].reshape(-1, 4)
+    accepted, why = 0, set()
+    for k in range(M):
+        if not mine[k]:
+            continue
+        sel = [proofs[i] for i in mine[k]]
+        if whole:
+            pv = api.PbsVerifier(ctx, cap, ncols, vk[:4], log_n, cyc.n_constants, 80, cyc.gates, N, K, n_lwe, K * ELL * K * N, hashes[k], max_batch=len(sel))
+            verdicts, reasons, _ = pv.verify(sel, testv, cts[mine[k]], out_ct[mine[k]].reshape(len(sel), -1))
+            pv.close()
+            accepted += int(verdicts.sum())
+            why |= {api.pbs_reason_text(int(r)) for v, r in zip(verdicts, reasons) if not v}
+        else:
+            res = [api.verify_pbs_prefix(b, cap, ncols, vk[:4], log_n, cyc.n_constants, 80, cyc.gates, N, K, testv, cts[i], keys[k]["bsk"], keys[k]["ksk"])
+                   for i, b in zip(mine[k], sel)]
+            accepted += sum(1 for r in res if r[0] and r[1] == args.steps)
+            why |= {str(r[-1]) for r in res if not r[0]}
+    decrypted = sum(1 for i in range(count) if rounded(api.lwe_decrypt(keys[key_of[i]]["s_lwe"], lwe_out[i]), delta) == msgs[i])
+    ctx.close()
+    print(json.dumps({
+        "what": "%d verifiable bootstraps under %d key sets at N=%d, n=%d (degree 2^%d), %s" % (
+            count, M, N, n_lwe, log_n, "one PbsProver per key set, one after the other" if args.baseline else "one RingProver.prove"),
+        "count": count, "keys": M, "chains": args.chains, "witness_batch": args.witness_batch, "steps": args.steps or total, "baseline": args.baseline,
+        "seconds": t_end - t_made, "seconds_with_create_and_close": t_end - t0, "create_seconds": t_made - t0, "proofs": n_proofs,
+        "seconds_per_proof": (t_end - t_made) / max(n_proofs, 1), "device_bytes_held_by_the_provers": held,
+        "seconds_until_out_ct_complete": t_out, "prepare_chain_ms": prepare_ms, "accepted": accepted, "rejected_because": sorted(why),
+        "decrypted_correct": decrypted, "host": {"cpus": len(os.sched_getaffinity(0)), "loadavg_before": load0, "loadavg_after": os.getloadavg()[0]}}))
+    return 0 if accepted == count and decrypted == count and n_proofs == count else 1
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--count", type=int, default=16)
@@ -136,6 +228,7 @@ def main():
     ap.add_argument("--n8", action="store_true")
     ap.add_argument("--keys-on-device", action="store_true")
     ap.add_argument("--baseline", action="store_true")
+    ap.add_argument("--keys", type=int, default=0)
     args = ap.parse_args()
     if args.baseline and args.keys_on_device:
         raise SystemExit("--baseline proves under host keys: it cannot run with --keys-on-device")
@@ -146,6 +239,10 @@ def main():
     whole = args.steps in (0, total)
     api.host_set_late_threads(api.late_threads_for(args.chains, api.host_cpu_budget()))
     api.host_set_early_threads(api.early_threads_for(args.chains))
+    if args.keys:
+        if args.keys < 0 or args.keys_on_device:
+            raise SystemExit("--keys M proves under M >= 1 host key sets: it cannot run with --keys-on-device")
+        return main_keys(args, N, n_lwe, log_n)
     cyc_path, dum_path = circuit_file.find_cyclic_circuit(N, K, ELL, LOGB, n_lwe, log_n)
     cyc, dum = circuit_file.load(cyc_path), circuit_file.load(dum_path)
     ctx = vpbs_amd.Context(0, log_n_max=max(16, log_n))

@@ -11,7 +11,7 @@ usage: tools/run_program.py [--levels L] [--width W] [--fan-in F] [--program FIL
   --program: {"n_inputs", "n_luts", "gates": [{"terms": [[src, coef], ..], "const", "lut"}, ..]} instead; lut 0 is the test vector of the
     identity on {0, 1}, lut 1 its negation, further luts are seeded random words.
   --n8: the N = 8, n = 6 miniature of tools/prove_batch.py --n8; default: the paper's N = 1024, n = 728.
-  --prove: api.Program.prove on an api.PbsProver, api.Program.verify on an api.PbsVerifier made from the prover's key_hash(), and the
+  --prove (without --instances): api.Program.prove on an api.PbsProver, api.Program.verify on an api.PbsVerifier made from the prover's key_hash(), and the
     output wires with a known message decrypted.
   --baseline: the baseline leg ALONE.  It needs nothing newer than api.Bootstrapper, so this file can be copied into a build of an older
     commit and time that.
@@ -21,6 +21,9 @@ usage: tools/run_program.py [--levels L] [--width W] [--fan-in F] [--program FIL
     nothing newer than api.Program.run.  Every wire of both legs is compared; every program output (a wire of the last level) is decrypted
     under its own key, and those with a known message are checked.  Prints wall seconds, the HIP-event time of the bootstrap launches and
     the launches queued per leg, and the bytes of the combine and delivery kernels computed from the shapes.
+    With --prove the batched leg is followed by ONE api.Program.prove_batch on an api.RingProver that holds the M key sets (host copies
+    from the same seeds): its wires must be the batched leg's, every instance is verified by api.Program.verify on an api.PbsVerifier made
+    from the ring prover's key_hash of that instance's slot, and the decrypted outputs are the proven ones.
   Time: wall seconds per run of a leg (after one warm-up run), per level = / levels; HIP-event milliseconds of the bootstrap launches per
   level (the library's own timers).  Bytes: what each leg moves between host and device per run, computed from the shapes."""
 import argparse
@@ -128,6 +131,40 @@ def run_baseline(ctx, bs, n_inputs, gates, lv, inputs, testvs):
     return wires, event_ms
 
 
+def prove_batch(args, ctx, prog, N, n_lwe, log_n, M, inputs, key_of, testvs, batch_wires, out):
+    """--instances B --keys M --prove: Program.prove_batch on a RingProver, Program.verify per instance -> (the proven wires, all accepted)"""
+    cyc_path, dum_path = circuit_file.find_cyclic_circuit(N, K, ELL, LOGB, n_lwe, log_n)
+    cyc, dum = circuit_file.load(cyc_path), circuit_file.load(dum_path)
+    chains = args.chains or (2 if args.n8 else 8)
+    api.host_set_late_threads(api.late_threads_for(chains, api.host_cpu_budget()))
+    api.host_set_early_threads(api.early_threads_for(chains))
+    rp = api.RingProver(0, cyc, dum, K, ELL, LOGB, N, n_lwe, max_keys=M, chains=chains, witness_batch=args.witness_batch or (3 if args.n8 else 64))
+    for k in range(M):
+        hk = ctx.keygen(N, K, ELL, LOGB, n_lwe, SEED + k, SIGMA_GLWE, SIGMA_LWE)
+        assert rp.add(hk["bsk"], hk["ksk"]) == k
+    t = time.perf_counter()
+    proofs, wires, out_cts = prog.prove_batch(rp, inputs, key_of, testvs)
+    out["prove_seconds"] = time.perf_counter() - t
+    hashes, (vk, _) = [rp.key_hash(k) for k in range(M)], rp.verifier_data()
+    rp.close()
+    n_gates = prog.n_gates
+    verified, why = 0, set()
+    t = time.perf_counter()
+    for k in range(M):
+        pv = api.PbsVerifier(ctx, vk[4:].reshape(-1, 4), [cyc.n_constants + 80, 135, 20, 16], vk[:4], log_n, cyc.n_constants, 80, cyc.gates, N, K, n_lwe,
+                             K * ELL * K * N, hashes[k], max_batch=max(1, min(n_gates, 64)))
+        for b in [b for b in range(len(key_of)) if key_of[b] == k]:
+            verdicts, reasons, _ = prog.verify(pv, inputs[b], testvs, out_cts[b], proofs[b])
+            verified += int(verdicts.sum())
+            why |= {api.pbs_reason_text(int(r)) for v, r in zip(verdicts, reasons) if not v}
+        pv.close()
+    out["verify_seconds"] = time.perf_counter() - t
+    out["verified"], out["rejected_because"] = verified, sorted(why)
+    out["proven"] = verified == len(key_of) * n_gates
+    out["proven_wires_equal"] = bool((wires == batch_wires).all())
+    return wires, out["proven"] and out["proven_wires_equal"]
+
+
 def main_batch(args):
     """--instances B --keys M: see the module text"""
     B, M = args.instances, max(1, args.keys)
@@ -191,6 +228,9 @@ def main_batch(args):
             ring.add(k["d_bsk"], k["d_ksk"], keys_on_device=True)
         wires, rep, out["batch"] = leg(lambda: prog.run_batch(ring, inputs, key_of, testvs, gate_cts=False, out_cts=False)[0], "pbs_keyring")
         ring.close()
+        if args.prove:
+            out["all_batch_equal"] = bool(wires.shape == base_wires.shape and (wires == base_wires).all())
+            wires, proven = prove_batch(args, ctx, prog, N, n_lwe, log_n, M, inputs, key_of, testvs, wires, out)
         terms = sum(len(g[0]) for g in gates)
         out["batch"].update({"combine_event_ms": rep.get("lwe_combine", {}).get("ms", 0.0), "combine_launches": rep.get("lwe_combine", {}).get("count", 0),
                              "combine_bytes": 8 * words * B * (terms + n_gates),               # a read per term, a write per gate
@@ -202,7 +242,7 @@ def main_batch(args):
                              "d2h_bytes": 8 * B * (n_inputs + n_gates) * words})
         out["batch_over_baseline"] = statistics.median(out["batch"]["seconds"]) / statistics.median(out["baseline"]["seconds"])
         out["all_equal"] = bool(wires.shape == base_wires.shape and (wires == base_wires).all())
-        ok = out["all_equal"]
+        ok = out["all_equal"] and (not args.prove or proven)
     prog.close()
     # ---- every program output (the wires of the last level), under its own key ----
     outputs = [n_inputs + g for g in range(n_gates) if lv[g] == n_levels]
@@ -245,8 +285,6 @@ def main():
     if args.baseline and args.prove:
         raise SystemExit("--baseline evaluates only: it cannot run with --prove")
     if args.instances is not None:
-        if args.prove:
-            raise SystemExit("--instances evaluates only: proofs are bound to one key set")
         return main_batch(args)
     N, n_lwe, log_n = (8, 6, 13) if args.n8 else (1024, 728, 16)
     rng = np.random.default_rng(args.seed)

@@ -342,11 +342,26 @@ SIGNATURES = {
     "vpbs_pbs_prover_set_checkpoint": (_i, [_vp, _ui, PBS_CHECKPOINT_FN, _vp]),
     "vpbs_pbs_prover_last_run": (_i, [_vp, C.POINTER(PbsRunStatsC)]),
     "vpbs_pbs_prover_free": (None, [_vp]),
+    "vpbs_ring_prover_create": (_i, [_i, C.POINTER(IvcCircuitC), C.POINTER(IvcCircuitC), C.POINTER(TfheParamsC), _ui, _sz, _ui, _ui, C.POINTER(_vp),
+                                     C.c_char_p, _sz]),
+    "vpbs_ring_prover_add": (_i, [_vp, _vp, _vp, _i, C.POINTER(_ui), C.c_char_p, _sz]),
+    "vpbs_ring_prover_remove": (_i, [_vp, _ui, C.c_char_p, _sz]),
+    "vpbs_ring_prover_key_hash": (_i, [_vp, _ui, U64P]),
+    "vpbs_ring_prover_keyring": (_vp, [_vp]),
+    "vpbs_ring_prover_context": (_vp, [_vp]),
+    "vpbs_ring_prover_run": (C.c_long, [_vp, U64P, _sz, _vp, U64P, _i, _ui, U64P, U64P, PBS_PROOF_FN, _vp, C.c_char_p, _sz]),
+    "vpbs_ring_prover_verifier_data": (_i, [_vp, U64P, U64P]),
+    "vpbs_ring_prover_set_check_witness": (_i, [_vp, _i]),
+    "vpbs_ring_prover_witness_checks": (_i, [_vp, U64P]),
+    "vpbs_ring_prover_set_checkpoint": (_i, [_vp, _ui, PBS_CHECKPOINT_FN, _vp]),
+    "vpbs_ring_prover_last_run": (_i, [_vp, C.POINTER(PbsRunStatsC)]),
+    "vpbs_ring_prover_free": (None, [_vp]),
     "vpbs_program_create": (_i, [_vp, C.POINTER(ProgramDescC), C.POINTER(_vp), C.c_char_p, _sz]),
     "vpbs_program_levels": (C.c_long, [_vp, C.POINTER(_ui)]),
     "vpbs_program_run": (C.c_long, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i]),
     "vpbs_program_run_batch": (C.c_long, [_vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _i]),
     "vpbs_program_prove": (C.c_long, [_vp, _vp, U64P, U64P, _ui, U64P, U64P, PBS_PROOF_FN, _vp, C.c_char_p, _sz]),
+    "vpbs_program_prove_batch": (C.c_long, [_vp, _vp, U64P, _sz, _vp, U64P, _ui, U64P, U64P, PBS_PROOF_FN, _vp, C.c_char_p, _sz]),
     "vpbs_program_verify": (C.c_long, [_vp, _vp, U64P, U64P, U64P, C.POINTER(C.c_uint8), C.POINTER(_sz), C.POINTER(C.c_uint8),
                                        C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]),
     "vpbs_program_free": (None, [_vp]),
@@ -1887,6 +1902,193 @@ class PbsProver:
             pass
 
 
+def ring_prove_args(N, n_lwe, max_keys, cts, key_of, testv, steps=0):
+    """shapes of a RingProver.prove call, checked without a device: cts [count][n + 1], key_of [count] slots below max_keys (any integer
+    dtype; the offending index is named), testv [N] or [count][N], steps 0 .. n + 2 -> (cts, key_of as uint32, testv), contiguous"""
+    c, tv = _u64(cts), _u64(testv)
+    if c.ndim != 2 or c.shape[1] != n_lwe + 1 or tv.shape not in ((N,), (c.shape[0], N)):
+        raise ValueError("RingProver.prove: expected cts [count][%d] and testv [%d] or [count][%d]" % (n_lwe + 1, N, N))
+    if int(steps) != steps or steps < 0 or steps > n_lwe + 2:
+        raise ValueError("RingProver.prove: steps must be 0 .. n_lwe + 2 = %d, got %r" % (n_lwe + 2, steps))
+    return c, keyring_key_of(key_of, c.shape[0], max_keys), tv
+
+
+class _RingContext:
+    """the context of a RingProver's ring, as far as KeyRing and Program.run_batch need one: the handle (for vpbs_last_error)"""
+
+    def __init__(self, h):
+        self.h, self._batches = h, set()
+
+
+class RingProver(PbsProver):
+    """vpbs_ring_prover: ONE prover for all clients of a key ring.  The object owns a KeyRing of max_keys slots, `chains` IVC chains in the
+    device-witness pipeline and the key hash chain of every slot; prove() bootstraps and proves ciphertext i under the key set of slot
+    key_of[i], and its proof is byte for byte what a PbsProver of that key set gives.  cyclic / dummy, chains, witness_batch: as PbsProver.
+    .keyring is a KeyRing view of the owned ring (KeyRing.run and Program.run_batch evaluate on the same resident keys; it is not closed
+    by the caller, and its add / remove are refused: key sets come and go through this object, which keeps their key links)."""
+
+    def __init__(self, device, cyclic, dummy, K, ELL, LOGB, N, n_lwe, max_keys, chains=8, witness_batch=64):
+        self.N, self.K, self.ELL, self.LOGB, self.n_lwe, self.chains, self.max_keys = N, K, ELL, LOGB, n_lwe, chains, max_keys
+        keep = []
+
+        def side(d, proof_words):
+            c = IvcCircuitC()
+            pre = np.ascontiguousarray(d.preset_flat, dtype=np.uint32)
+            pi = np.ascontiguousarray(d.pi_flat, dtype=np.uint32)
+            keep.extend([pre, pi, d])
+            c.circuit = C.pointer(d.circuit.c)
+            c.preset_pos, c.n_preset = pre.ctypes.data_as(U32P), pre.size
+            c.pi_pos, c.n_pi = pi.ctypes.data_as(U32P), pi.size
+            c.proof_words = proof_words
+            return c
+        cy, du = side(cyclic, cyclic.meta["proof_words"]), side(dummy, 0)
+        prm = TfheParamsC(N.bit_length() - 1, K, ELL, LOGB)
+        self.h, err = C.c_void_p(), C.create_string_buffer(512)
+        rc = lib().vpbs_ring_prover_create(device, C.byref(cy), C.byref(du), C.byref(prm), n_lwe, max_keys, chains, witness_batch,
+                                           C.byref(self.h), err, 512)
+        if rc:
+            self.h = None
+            e = VpbsError("vpbs_ring_prover_create: status %d: %s" % (rc, err.value.decode()))
+            e.status = rc
+            raise e
+        self.vk_words = 4 + (4 << 4)
+        self._proof_words = cyclic.meta["proof_words"]
+        self._ckpt_cb = self._ckpt_error = None
+        ring = KeyRing.__new__(KeyRing)   # a view: the handle is the prover's, and goes with it
+        ring.ctx = _RingContext(C.c_void_p(lib().vpbs_ring_prover_context(self.h)))
+        ring.N, ring.K, ring.ELL, ring.LOGB, ring.n_lwe, ring.max_keys, ring.max_batch = N, K, ELL, LOGB, n_lwe, max_keys, 256
+        ring.h = C.c_void_p(lib().vpbs_ring_prover_keyring(self.h))
+        ring.close = ring.free = lambda: None
+        self.keyring = ring
+
+    def _fail(self, what, rc, err):
+        e = VpbsError("%s: status %d: %s" % (what, rc, err.value.decode()))
+        e.status = rc
+        return e
+
+    def add(self, bsk, ksk, keys_on_device=False):
+        """KeyRing.add on the owned ring, and the key hash chain of the key set walked once, on the host.  Returns the slot."""
+        g = self.K * self.ELL * self.K * self.N
+        if keys_on_device:
+            pb, pk = C.c_void_p(int(bsk)), C.c_void_p(int(ksk))
+        else:
+            b, k = _u64(bsk), _u64(ksk).reshape(-1)
+            if b.shape != (self.n_lwe, g) or k.size != g:
+                raise ValueError("RingProver.add: expected bsk [%d][%d] and ksk [%d]" % (self.n_lwe, g, g))
+            pb, pk = C.c_void_p(b.ctypes.data), C.c_void_p(k.ctypes.data)
+        slot, err = C.c_uint(), C.create_string_buffer(512)
+        rc = lib().vpbs_ring_prover_add(self.h, pb, pk, 1 if keys_on_device else 0, C.byref(slot), err, 512)
+        if rc:
+            raise self._fail("vpbs_ring_prover_add", rc, err)
+        return slot.value
+
+    def remove(self, slot):
+        err = C.create_string_buffer(512)
+        rc = lib().vpbs_ring_prover_remove(self.h, int(slot), err, 512)
+        if rc:
+            raise self._fail("vpbs_ring_prover_remove", rc, err)
+
+    def key_hash(self, slot):
+        """the end of the slot's key hash chain: what the PbsVerifier of that client takes (= pbs_key_hash(bsk, ksk))"""
+        out = np.zeros(4, np.uint64)
+        rc = lib().vpbs_ring_prover_key_hash(self.h, int(slot), _ptr(out))
+        if rc:
+            e = VpbsError("vpbs_ring_prover_key_hash: status %d: slot %d holds no key set" % (rc, slot))
+            e.status = rc
+            raise e
+        return out
+
+    def verifier_data(self):
+        a, b = np.zeros(self.vk_words, np.uint64), np.zeros(self.vk_words, np.uint64)
+        lib().vpbs_ring_prover_verifier_data(self.h, _ptr(a), _ptr(b))
+        return a, b
+
+    def set_check_witness(self, on=True):
+        rc = lib().vpbs_ring_prover_set_check_witness(self.h, 1 if on else 0)
+        if rc != 0:
+            raise VpbsError("vpbs_ring_prover_set_check_witness: status %d" % rc)
+
+    def witness_checks(self):
+        out = np.zeros(2, np.uint64)
+        lib().vpbs_ring_prover_witness_checks(self.h, _ptr(out))
+        return int(out[0]), int(out[1])
+
+    def on_checkpoint(self, every, fn):
+        """as PbsProver.on_checkpoint"""
+        self._ckpt_error = None
+        if fn is None or not every:
+            self._ckpt_cb = None
+            lib().vpbs_ring_prover_set_checkpoint(self.h, 0, C.cast(None, PBS_CHECKPOINT_FN), None)
+            return
+
+        def trampoline(_user, index, done, data, n):
+            try:
+                if self._ckpt_error is None:
+                    fn(int(index), int(done), C.string_at(data, n))
+            except BaseException as e:   # noqa: BLE001 -- must not unwind through the C frames
+                self._ckpt_error = e
+        self._ckpt_cb = PBS_CHECKPOINT_FN(trampoline)
+        lib().vpbs_ring_prover_set_checkpoint(self.h, every, self._ckpt_cb, None)
+
+    def prove(self, cts, key_of, testv, steps=0, on_proof=None, out_ct=None, lwe_out=None):
+        """cts [count][n + 1]; key_of [count] slots; testv [N] shared or [count][N] -> (proofs: list of bytes in the order of cts, out_ct
+        [count][K][N], lwe_out [count][n + 1]); on_proof, failures (PbsProveError) and `steps` as in PbsProver.prove.  A key_of entry that
+        names an empty slot raises VpbsError (.status = VPBS_ERR_INVALID) with the ring's message before anything runs.  out_ct / lwe_out:
+        arrays to write into instead of fresh ones."""
+        c, ko, tv = ring_prove_args(self.N, self.n_lwe, self.max_keys, cts, key_of, testv, steps)
+        count = c.shape[0]
+        out_ct = np.zeros((count, self.K, self.N), np.uint64) if out_ct is None else out_ct
+        lwe_out = np.zeros((count, self.n_lwe + 1), np.uint64) if lwe_out is None else lwe_out
+        if out_ct.shape != (count, self.K, self.N) or lwe_out.shape != (count, self.n_lwe + 1):
+            raise ValueError("RingProver.prove: expected out_ct [count][K][N] and lwe_out [count][n + 1]")
+        proofs, failures, raised = [None] * count, [], []
+
+        def trampoline(_user, index, data, n, error):
+            try:
+                if not data:
+                    failures.append((int(index), (error or b"").decode()))
+                    return
+                proofs[index] = C.string_at(data, n)
+                if on_proof is not None and not raised:
+                    on_proof(int(index), proofs[index])
+            except BaseException as e:   # noqa: BLE001 -- must not unwind through the C frames
+                raised.append(e)
+        cb, err = PBS_PROOF_FN(trampoline), C.create_string_buffer(512)
+        keep = np.zeros(1, np.uint64)   # a valid pointer for an empty batch
+        p = lambda a: _ptr(a if a.size else keep)
+        n = lib().vpbs_ring_prover_run(self.h, p(c), count, (ko if ko.size else np.zeros(1, np.uint32)).ctypes.data, p(tv), 1 if tv.ndim == 2 else 0,
+                                       steps, p(out_ct), p(lwe_out), cb, None, err, 512)
+        if raised:
+            raise raised[0]
+        e, self._ckpt_error = self._ckpt_error, None
+        if e is not None:
+            raise e
+        if n < 0:
+            raise self._fail("vpbs_ring_prover_run", n, err)
+        if failures:
+            raise PbsProveError(dict(failures), proofs, out_ct, lwe_out)
+        return proofs, out_ct, lwe_out
+
+    def last_run(self):
+        st = PbsRunStatsC()
+        lib().vpbs_ring_prover_last_run(self.h, C.byref(st))
+        return {"seconds": st.seconds, "outputs_seconds": st.outputs_seconds, "proofs": st.proofs, "prepare_chain_ms": st.prepare_chain_ms,
+                "chain": {f: getattr(st.chain, f) for f, _ in IvcTimingC._fields_}}
+
+    def dummy_proof_for_tests(self):
+        raise NotImplementedError("a test entry of PbsProver")
+
+    preset_matrix = dummy_proof_for_tests
+
+    def close(self):
+        if self.h:
+            self.keyring.h = None
+            lib().vpbs_ring_prover_free(self.h)
+            self.h = None
+
+    free = close
+
+
 class Program:
     """vpbs_program: a netlist of bootstraps on resident keys.  Wire w < n_inputs is input w, wire n_inputs + g the output of gate g; gate g
     bootstraps const * (0, .., 0, 1) + sum coef * wire[src] with test vector testvs[lut].  gates: a list of (terms=[(src, coef), ..], const, lut)
@@ -2032,6 +2234,50 @@ class Program:
         if failures:
             raise PbsProveError(dict(failures), proofs, out, wires)
         return proofs, wires, out
+
+    def prove_batch(self, ring_prover, inputs, key_of, testvs, steps=0, on_proof=None):
+        """ONE program for many input sets, evaluated AND proven on a RingProver: inputs [instances][n_inputs][n + 1], key_of [instances]
+        slots, testvs [n_luts][N] -> (proofs[b][g]: bytes, wires [instances][n_inputs + n_gates][n + 1], out_cts
+        [instances][n_gates][K][N]).  wires and out_cts are run_batch's on the prover's ring; proof (b, g) is byte for byte
+        prove(PbsProver of the key set in slot key_of[b], inputs[b], testvs)[0][g].  on_proof((b, g), bytes); failures: PbsProveError with
+        .failures keyed by b * n_gates + g.  A client verifies its instance with verify() and a PbsVerifier made from key_hash(slot)."""
+        if self.ctx is None:
+            raise VpbsError("Program.prove_batch: a host-only program (made without a context) cannot be evaluated")
+        rp = ring_prover
+        if rp is None or not rp.h:
+            raise VpbsError("Program.prove_batch: no ring prover (None, or a closed RingProver)")
+        x, ko, tv = program_batch_args(self.n_inputs, rp.n_lwe, rp.N, self.n_luts, rp.max_keys, inputs, key_of, testvs)
+        B, G = x.shape[0], self.n_gates
+        wires, out = np.zeros((B, self.n_inputs + G, rp.n_lwe + 1), np.uint64), np.zeros((B, G, rp.K, rp.N), np.uint64)
+        flat, failures, raised = [None] * (B * G), [], []
+
+        def trampoline(_user, index, data, n, error):
+            try:
+                if not data:
+                    failures.append((int(index), (error or b"").decode()))
+                    return
+                flat[index] = C.string_at(data, n)
+                if on_proof is not None and not raised:
+                    on_proof(divmod(int(index), G), flat[index])
+            except BaseException as e:   # noqa: BLE001 -- must not unwind through the C frames
+                raised.append(e)
+        cb, err = PBS_PROOF_FN(trampoline), C.create_string_buffer(512)
+        keep = np.zeros(1, np.uint64)
+        p = lambda a: _ptr(a if a.size else keep)
+        n = lib().vpbs_program_prove_batch(self.h, rp.h, p(x.reshape(-1)), B, (ko if ko.size else np.zeros(1, np.uint32)).ctypes.data, p(tv.reshape(-1)),
+                                           steps, p(wires.reshape(-1)), p(out.reshape(-1)), cb, None, err, 512)
+        if raised:
+            raise raised[0]
+        e, rp._ckpt_error = rp._ckpt_error, None
+        if e is not None:
+            raise e
+        if n < 0:
+            e = VpbsError("vpbs_program_prove_batch: status %d: %s" % (n, err.value.decode()))
+            e.status = n
+            raise e
+        if failures:
+            raise PbsProveError(dict(failures), flat, out, wires)
+        return [flat[b * G:(b + 1) * G] for b in range(B)], wires, out
 
     def verify(self, pbs_verifier, inputs, testvs, out_cts, proofs):
         """out_cts [n_gates][K][N]: the claimed output GLWEs; proofs: list of bytes in gate order -> (verdicts, reasons, proof_reasons),

@@ -224,9 +224,11 @@ struct vpbs_keyring {
     unsigned n_lwe = 0, threads = 0, cus = 256;   // threads: 0 = chosen per run
     size_t max_keys = 0, max_batch = 0, lds_bytes = 0, ggsw_words = 0;
     std::mutex mu;   // add, remove and run: one at a time
+    bool has_owner = false;   // the ring of a vpbs_ring_prover: key sets come and go through the prover alone (keyring_set_owned)
     struct Slot {
         bool used = false;
         u64 *own_bsk = nullptr, *own_ksk = nullptr;   // what add uploaded (null for adopted pointers)
+        const u64 *bsk = nullptr, *ksk = nullptr;     // what the device table holds for the slot
     };
     std::vector<Slot> slots;
     size_t used = 0;
@@ -373,10 +375,39 @@ int vpbs_keyring_create(vpbs_ctx* ctx, const vpbs_tfhe_params* prm, unsigned n_l
 void vpbs_keyring_free(vpbs_keyring* r) { delete r; }
 
 int vpbs_keyring_add(vpbs_keyring* r, const uint64_t* bsk, const uint64_t* ksk, int keys_on_device, unsigned* slot_out) {
-    using namespace vpbs;
+    return vpbs::keyring_add(r, bsk, ksk, keys_on_device, slot_out, false);
+}
+
+int vpbs_keyring_remove(vpbs_keyring* r, unsigned slot) { return vpbs::keyring_remove(r, slot, false); }
+}  // extern "C"
+
+namespace vpbs {
+namespace {
+// a ring that a ring prover owns takes key sets from its owner alone: the prover keeps the key hash chain of every slot it filled
+bool refuse_owned(vpbs_keyring* r, bool owner, const char* who) {
+    if (!r->has_owner || owner) return false;
+    r->ctx->err = std::string(who) + ": the ring belongs to a vpbs_ring_prover, which keeps the key hash chain of every slot: add and remove "
+                  "key sets through vpbs_ring_prover_add / vpbs_ring_prover_remove";
+    return true;
+}
+}  // namespace
+
+void keyring_set_owned(vpbs_keyring* r) {
+    std::lock_guard<std::mutex> lock(r->mu);
+    r->has_owner = true;
+}
+
+void keyring_slot_keys(const vpbs_keyring* r, unsigned slot, const uint64_t** d_bsk, const uint64_t** d_ksk) {
+    const bool used = slot < r->max_keys && r->slots[slot].used;
+    *d_bsk = used ? r->slots[slot].bsk : nullptr;
+    *d_ksk = used ? r->slots[slot].ksk : nullptr;
+}
+
+int keyring_add(vpbs_keyring* r, const uint64_t* bsk, const uint64_t* ksk, int keys_on_device, unsigned* slot_out, bool owner) {
     if (!r || !bsk || !ksk || !slot_out) return VPBS_ERR_INVALID;
     std::lock_guard<std::mutex> lock(r->mu);
     vpbs_ctx* ctx = r->ctx;
+    if (refuse_owned(r, owner, "vpbs_keyring_add")) return VPBS_ERR_INVALID;
     size_t s = 0;
     while (s < r->max_keys && r->slots[s].used) ++s;
     if (s == r->max_keys) {
@@ -395,6 +426,8 @@ int vpbs_keyring_add(vpbs_keyring* r, const uint64_t* bsk, const uint64_t* ksk, 
             VPBS_HIP(hipMemcpyAsync(fresh.own_ksk, ksk, sizeof(u64) * r->ggsw_words, hipMemcpyHostToDevice, ctx->stream));
             entry = KeySlot{fresh.own_bsk, fresh.own_ksk};
         }
+        fresh.bsk = entry.bsk;
+        fresh.ksk = entry.ksk;
         VPBS_HIP(hipMemcpyAsync(r->d_table + s, &entry, sizeof entry, hipMemcpyHostToDevice, ctx->stream));
         VPBS_HIP(vpbs::stream_sync(ctx->stream));   // the caller's key arrays, and `entry`, may go away
     } catch (const DeviceError& e) {
@@ -410,11 +443,11 @@ int vpbs_keyring_add(vpbs_keyring* r, const uint64_t* bsk, const uint64_t* ksk, 
     return VPBS_OK;
 }
 
-int vpbs_keyring_remove(vpbs_keyring* r, unsigned slot) {
-    using namespace vpbs;
+int keyring_remove(vpbs_keyring* r, unsigned slot, bool owner) {
     if (!r) return VPBS_ERR_INVALID;
     std::lock_guard<std::mutex> lock(r->mu);
     vpbs_ctx* ctx = r->ctx;
+    if (refuse_owned(r, owner, "vpbs_keyring_remove")) return VPBS_ERR_INVALID;
     if (slot >= r->max_keys || !r->slots[slot].used) {
         ctx->err = "vpbs_keyring_remove: slot " + std::to_string(slot) + " holds no key set";
         return VPBS_ERR_INVALID;
@@ -436,7 +469,9 @@ int vpbs_keyring_remove(vpbs_keyring* r, unsigned slot) {
     --r->used;
     return rc;
 }
+}  // namespace vpbs
 
+extern "C" {
 size_t vpbs_keyring_count(vpbs_keyring* r) {
     if (!r) return 0;
     std::lock_guard<std::mutex> lock(r->mu);

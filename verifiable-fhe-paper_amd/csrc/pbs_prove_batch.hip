@@ -1,255 +1,36 @@
 // Proving the bootstraps of a batch under ONE resident key set (vpbs_pbs_prover, include/vpbs_prover.h): a vpbs_bootstrapper and C chains of
 // the device-witness pipeline (vpbs_ivc, csrc/ivc.hip) share the keys in device memory and the key hash chain, which is walked once when
-// the object is made.  Per ciphertext a worker thread lets the Bootstrapper leave every intermediate accumulator of the chain on the device
-// (they ARE the `current accumulator` public inputs of the n + 2 step proofs), walks the LWE hash chain on the host (one permutation per
-// link) and proves the chain through vpbs::ivc_prove_pbs_resident: the early-phase preset matrix of every batch of steps is assembled on the
-// device by the kernels below, straight from the resident sources --
-//
-//   preset rows of step s                     source
-//   previous proof's words                    zeros (late presets: the early phase ignores them)
-//   acc_init | counter                        (0, .., 0, testv) | s
-//   accumulator                               Bootstrapper accs[s - 1]                 (zeros for s = 0)     TRANSPOSED [cnt][K N] -> [K N][cnt]
-//   key hash | LWE hash                       resident key link s - 1 | the chain's LWE link s - 1  (zeros for s = 0)
-//   verifier data, condition                  constant | s != 0
-//   GGSW                                      zeros, resident bsk[s - 1], resident ksk                      TRANSPOSED [cnt][ggsw] -> [ggsw][cnt]
-//   mask                                      ct[n], ct[s - 1], 0
-//   own / dummy verifier data, dummy proof    constants of the object
-//   the dummy proof's public inputs           zeros
-//
-// -- so neither the 16 384 words of bsk[s] per step nor anything else of the matrix is stored by a host thread or crosses PCIe.
-#include <algorithm>
-#include <chrono>
-#include <condition_variable>
-#include <cstring>
+// the object is made.  The chains, their queue and the kernels that assemble the preset matrices on the device are the worker pool of
+// pbs_prove_pool.h; this file is the pool's key source with ONE key set: every chain is proven under the same resident bsk, ksk and key
+// links, and a chain's accumulators come from a count-1 run of the object's Bootstrapper.
 #include <memory>
-#include <mutex>
-#include <pthread.h>
-#include <string>
-#include <thread>
-#include <vector>
 
-#include "context.h"
-#include "ivc_resident.h"
+#include "pbs_prove_pool.h"
 #include "program_internal.h"
 #include "test_entries.h"
 
 using vpbs::DeviceError;
 using vpbs::u64;
 
-namespace vpbs {
-namespace {
-struct PresetArgs {
-    u64* m;                 // [n_preset][cnt], instances innermost
-    const u64* testv;       // [N]
-    const u64* accs;        // [n_lwe + 2][K N]
-    const u64* key_links;   // [n_lwe + 2][4]
-    const u64* lwe_links;   // [n_lwe + 2][4]
-    const u64* ct;          // [n_lwe + 1]
-    const u64* bsk;         // [n_lwe][ggsw_len]
-    const u64* ksk;         // [ggsw_len]
-    const u64* consts;      // own verifier data [vk] | dummy verifier data [vk] | dummy proof [proof_words]
-    unsigned first, cnt, n_lwe, N;
-    size_t kn, proof_words, n_pi, ggsw_len, vk_words;
-    // first rows of the sections (the PartialWitness order of vpbs_ivc_create)
-    __host__ __device__ size_t r_acc_init() const { return proof_words; }
-    __host__ __device__ size_t r_counter() const { return proof_words + kn; }
-    __host__ __device__ size_t r_acc() const { return proof_words + kn + 1; }
-    __host__ __device__ size_t r_hashes() const { return proof_words + 2 * kn + 1; }
-    __host__ __device__ size_t r_own_vk() const { return proof_words + 2 * kn + 9; }
-    __host__ __device__ size_t r_cond() const { return proof_words + n_pi; }
-    __host__ __device__ size_t r_ggsw() const { return proof_words + n_pi + 1; }
-    __host__ __device__ size_t r_mask() const { return r_ggsw() + ggsw_len; }
-    __host__ __device__ size_t r_consts() const { return r_mask() + 1; }
-    __host__ __device__ size_t r_dummy_pis() const { return r_consts() + 2 * vk_words + proof_words; }
-    __host__ __device__ size_t n_preset() const { return r_dummy_pis() + n_pi; }
-    __host__ __device__ size_t plain_rows() const { return n_preset() - kn - ggsw_len; }   // all but the accumulator and the GGSW
-};
-
-// every row that is a broadcast or a short gather: one thread per word of those rows (the grid skips the two transposed blocks, which
-// belong to preset_transpose_kernel and are most of the matrix), consecutive threads on consecutive instances of a row
-__global__ void __launch_bounds__(256) preset_rows_kernel(PresetArgs a) {
-    const size_t q = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (q >= a.plain_rows() * a.cnt) return;
-    size_t r = q / a.cnt;   // among the plain rows; below: in the matrix
-    if (r >= a.r_acc()) r += a.kn;
-    if (r >= a.r_ggsw()) r += a.ggsw_len;
-    const unsigned s = a.first + (unsigned)(q % a.cnt);
-    u64 v = 0;
-    if (r < a.r_acc_init()) {
-        v = 0;
-    } else if (r < a.r_counter()) {
-        const size_t k = r - a.r_acc_init();
-        v = k >= a.kn - a.N ? a.testv[k - (a.kn - a.N)] : 0;
-    } else if (r == a.r_counter()) {
-        v = s;
-    } else if (r < a.r_own_vk()) {
-        const size_t h = r - a.r_hashes();
-        v = s == 0 ? 0 : (h < 4 ? a.key_links[(size_t)(s - 1) * 4 + h] : a.lwe_links[(size_t)(s - 1) * 4 + h - 4]);
-    } else if (r < a.r_cond()) {
-        v = a.consts[r - a.r_own_vk()];
-    } else if (r == a.r_cond()) {
-        v = s != 0;
-    } else if (r == a.r_mask()) {
-        v = s == 0 ? a.ct[a.n_lwe] : (s <= a.n_lwe ? a.ct[s - 1] : 0);
-    } else if (r < a.r_dummy_pis()) {
-        v = a.consts[r - a.r_consts()];
-    }
-    a.m[r * a.cnt + (q % a.cnt)] = v;
-}
-
-// The accumulator (blockIdx.z = 0) and the GGSW (1) of cnt consecutive steps: per step a contiguous source row, in the matrix one column.
-// A workgroup turns a tile of 32 steps x 64 words in LDS: rows are read coalesced (64 lanes on 512 contiguous bytes), columns written
-// coalesced (32 lanes on the 32 instances of a matrix row).  A tile row is padded by one word: the 32 lanes of a half-wave then read
-// words 65 apart, i.e. banks 2 (i + k) and 2 (i + k) + 1 mod 64 -- all 64 banks, no conflict.
-constexpr unsigned TILE_I = 32, TILE_K = 64;
-__global__ void __launch_bounds__(256) preset_transpose_kernel(PresetArgs a) {
-    __shared__ u64 tile[TILE_I][TILE_K + 1];
-    const bool ggsw = blockIdx.z == 1;
-    const size_t len = ggsw ? a.ggsw_len : a.kn, r0 = ggsw ? a.r_ggsw() : a.r_acc();
-    const size_t k0 = (size_t)blockIdx.x * TILE_K;
-    const unsigned i0 = blockIdx.y * TILE_I;
-    if (k0 >= len) return;   // the grid is sized for the longer block (uniform per workgroup: before any barrier)
-    for (unsigned ii = threadIdx.x / TILE_K; ii < TILE_I; ii += 256 / TILE_K) {
-        const unsigned k = threadIdx.x % TILE_K, i = i0 + ii;
-        u64 v = 0;
-        if (i < a.cnt && k0 + k < len) {
-            const unsigned s = a.first + i;
-            const u64* src = s == 0 ? nullptr
-                             : ggsw ? (s <= a.n_lwe ? a.bsk + (size_t)(s - 1) * a.ggsw_len : a.ksk)
-                                    : a.accs + (size_t)(s - 1) * a.kn;
-            if (src) v = src[k0 + k];
-        }
-        tile[ii][k] = v;
-    }
-    __syncthreads();
-    for (unsigned k = threadIdx.x / TILE_I; k < TILE_K; k += 256 / TILE_I) {
-        const unsigned ii = threadIdx.x % TILE_I;
-        if (k0 + k < len && i0 + ii < a.cnt) a.m[(r0 + k0 + k) * a.cnt + i0 + ii] = tile[ii][k];
-    }
-}
-
-// both kernels queued on s; the caller orders and waits
-void launch_preset(hipStream_t s, const PresetArgs& a) {
-    const size_t words = a.plain_rows() * a.cnt;
-    hipLaunchKernelGGL(preset_rows_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, s, a);
-    const size_t longer = std::max(a.ggsw_len, a.kn);
-    hipLaunchKernelGGL(preset_transpose_kernel, dim3((unsigned)((longer + TILE_K - 1) / TILE_K), (a.cnt + TILE_I - 1) / TILE_I, 2), dim3(256), 0, s, a);
-}
-
-double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
-void report(char* err, size_t err_len, const std::string& m) {
-    if (err && err_len) {
-        std::strncpy(err, m.c_str(), err_len - 1);
-        err[err_len - 1] = 0;
-    }
-}
-}  // namespace
-}  // namespace vpbs
-
 struct vpbs_pbs_prover {
-    struct Worker {   // one chain in flight: a context, a vpbs_ivc in the device-witness pipeline, the chain's public inputs
-        vpbs_pbs_prover* p = nullptr;
-        vpbs_ctx* ctx = nullptr;
-        vpbs_ivc* ivc = nullptr;
-        u64 *d_accs = nullptr, *d_lwe_links = nullptr, *d_ct = nullptr, *d_testv = nullptr;   // device (the bootstrap context's pool)
-        u64* accs = nullptr;   // pinned host [n_lwe + 2][K N]
-        std::vector<u64> lwe_links;
-        std::vector<uint8_t> proof;
-        size_t index = 0;   // the ciphertext being proven
-    };
-    int device = 0;
-    vpbs_tfhe_params prm{};
-    unsigned n_lwe = 0, total = 0, witness_batch = 0;
-    vpbs::IvcShape shape{};
+    vpbs::ProvePool pool;
     vpbs_ctx* boot_ctx = nullptr;
     vpbs_bootstrapper* boot = nullptr;
-    std::mutex boot_mu;   // one run at a time on the Bootstrapper and its context
-    const u64 *d_bsk = nullptr, *d_ksk = nullptr;
-    u64 *d_key_links = nullptr, *d_consts = nullptr;
-    std::vector<u64*> owned;         // device memory of the bootstrap context's pool
+    vpbs::KeySource keys;            // the one key set
     std::vector<u64> key_links;      // host [n_lwe + 2][4]
-    std::vector<Worker> workers;
-    size_t max_bytes = 0;
     static constexpr size_t BOOT_BATCH = 256;
-    // a run
-    std::mutex run_mu, cb_mu;        // one run at a time; callbacks never two at once
-    vpbs_pbs_run_stats stats{};      // of the last run (vpbs_pbs_prover_last_run)
-    vpbs_pbs_checkpoint_fn ckpt_fn = nullptr;
-    void* ckpt_user = nullptr;
+    std::mutex run_mu;               // one run at a time
 
     ~vpbs_pbs_prover() {
-        for (auto& w : workers) {
-            if (w.accs) vpbs_host_free(w.accs);
-            if (w.ivc) vpbs_ivc_free(w.ivc);
-            if (w.ctx) vpbs_ctx_destroy(w.ctx);
-        }
         if (boot) vpbs_bootstrapper_free(boot);
-        if (boot_ctx) {
-            (void)hipSetDevice(boot_ctx->device);
-            (void)vpbs::stream_sync(boot_ctx->stream);
-            for (u64* d : owned) boot_ctx->release(d);
-            vpbs_ctx_destroy(boot_ctx);
-        }
-    }
-    u64* alloc(size_t words) {
-        u64* d = boot_ctx->alloc_words(std::max<size_t>(1, words));
-        owned.push_back(d);
-        return d;
-    }
-    vpbs::PresetArgs preset_args(const Worker& w, unsigned first, unsigned cnt, u64* d_matrix) const {
-        vpbs::PresetArgs a{};
-        a.m = d_matrix;
-        a.testv = w.d_testv; a.accs = w.d_accs; a.key_links = d_key_links; a.lwe_links = w.d_lwe_links; a.ct = w.d_ct;
-        a.bsk = d_bsk; a.ksk = d_ksk; a.consts = d_consts;
-        a.first = first; a.cnt = cnt; a.n_lwe = n_lwe; a.N = shape.N;
-        a.kn = shape.kn; a.proof_words = shape.proof_words; a.n_pi = shape.n_pi; a.ggsw_len = shape.ggsw_len; a.vk_words = shape.vk_words;
-        return a;
-    }
-    // the chain's public inputs where ivc_prove_pbs_resident wants them: accumulators on the device (Bootstrapper, this worker's buffer) and
-    // on the host (one copy of (n + 2) K N words), the LWE hash chain on both.  Under boot_mu, on the bootstrap context's stream.
-    int prepare_chain(Worker& w, const u64* ct, const u64* testv, std::string& why) {
-        const size_t kn = shape.kn;
-        u64 in[5] = {0, 0, 0, 0, 0}, h[4];   // verify_hash_output's chain: h_s = hash_no_pad(h_{s-1} || mask_s), masks ct[n], ct[0] .. ct[n-1], 0
-        for (unsigned s = 0; s < total; ++s) {
-            in[4] = s == 0 ? ct[n_lwe] : (s <= n_lwe ? ct[s - 1] : 0);
-            vpbs_hash_no_pad(in, 5, h);
-            std::memcpy(in, h, 32);
-            std::memcpy(w.lwe_links.data() + 4 * (size_t)s, h, 32);
-        }
-        std::lock_guard<std::mutex> lk(boot_mu);
-        try {
-            VPBS_HIP(hipSetDevice(device));
-            hipStream_t s = boot_ctx->stream;
-            VPBS_HIP(hipMemcpyAsync(w.d_ct, ct, 8 * (size_t)(n_lwe + 1), hipMemcpyHostToDevice, s));
-            VPBS_HIP(hipMemcpyAsync(w.d_testv, testv, 8 * (size_t)shape.N, hipMemcpyHostToDevice, s));
-            VPBS_HIP(hipMemcpyAsync(w.d_lwe_links, w.lwe_links.data(), 8 * w.lwe_links.size(), hipMemcpyHostToDevice, s));
-            if (vpbs_bootstrapper_run(boot, w.d_ct, 1, w.d_testv, 0, nullptr, nullptr, w.d_accs, 1) != 1)
-                throw DeviceError{VPBS_ERR_DEVICE, std::string("accumulators of the chain: ") + vpbs_last_error(boot_ctx)};
-            VPBS_HIP(hipMemcpyAsync(w.accs, w.d_accs, 8 * (size_t)total * kn, hipMemcpyDeviceToHost, s));
-            VPBS_HIP(vpbs::stream_sync(s));
-            return VPBS_OK;
-        } catch (const DeviceError& e) {
-            (void)vpbs::stream_sync(boot_ctx->stream);
-            why = e.what;
-            return e.status;
-        }
-    }
-    static int fill(void* user, void* stream, unsigned first, unsigned cnt, uint64_t* d_matrix) {
-        auto* w = static_cast<Worker*>(user);
-        vpbs::launch_preset(static_cast<hipStream_t>(stream), w->p->preset_args(*w, first, cnt, d_matrix));
-        return hipGetLastError() == hipSuccess ? VPBS_OK : VPBS_ERR_DEVICE;
-    }
-    static void on_checkpoint(void* user, unsigned done, const uint8_t* bytes, size_t len) {
-        auto* w = static_cast<Worker*>(user);
-        std::lock_guard<std::mutex> lk(w->p->cb_mu);
-        if (w->p->ckpt_fn) w->p->ckpt_fn(w->p->ckpt_user, w->index, done, bytes, len);
+        pool.destroy();
+        if (boot_ctx) vpbs_ctx_destroy(boot_ctx);
     }
 };
 
 namespace vpbs {
 vpbs_bootstrapper* pbs_prover_bootstrapper(vpbs_pbs_prover* p, std::mutex** boot_mu) {
-    *boot_mu = &p->boot_mu;
+    *boot_mu = &p->pool.boot_mu;
     return p->boot;
 }
 }  // namespace vpbs
@@ -271,34 +52,19 @@ int vpbs_pbs_prover_create(int device_ordinal, const vpbs_ivc_circuit* cyclic, c
     if (prm->log_N < 1 || prm->log_N > 11 || prm->K < 2 || prm->ELL < 1 || prm->LOGB < 1) return refuse("unsupported TFHE parameters");
     if (n_lwe == 0) return refuse("n_lwe must be at least 1");
     auto p = std::make_unique<vpbs_pbs_prover>();
-    p->device = device_ordinal;
-    p->prm = *prm;
-    p->n_lwe = n_lwe;
-    p->total = n_lwe + 2;
-    p->witness_batch = witness_batch;
+    ProvePool& pool = p->pool;
+    pool.device = device_ordinal;
+    pool.n_lwe = n_lwe;
+    pool.total = n_lwe + 2;
     const unsigned N = 1u << prm->log_N, K = prm->K;
     const size_t ggsw_len = (size_t)K * prm->ELL * K * N;
     const unsigned log_n_max = std::max(16u, cyclic->circuit->log_n);
     char e[512] = {0};
     int rc = vpbs_ctx_create(device_ordinal, log_n_max, 3, 4, &p->boot_ctx);
     if (rc != VPBS_OK) return report(err, err_len, "the bootstrap context could not be made (no such device?)"), rc;
-    // ---- the chains: what tools/prove_ivc.py builds per chain ----
-    p->workers.resize(chains);
-    for (auto& w : p->workers) {
-        w.p = p.get();
-        rc = vpbs_ctx_create(device_ordinal, log_n_max, 3, 4, &w.ctx);
-        if (rc != VPBS_OK) return report(err, err_len, "a chain's context could not be made"), rc;
-        // chains side by side hide latency: the one-lane Poseidon form down to 2048 nodes (bench.py, tools/prove_ivc.py); the proofs are the same
-        if (chains > 1 && !getenv("VPBS_WIDE_THRESHOLD")) (void)vpbs_ctx_set_option(w.ctx, VPBS_OPT_WIDE_THRESHOLD, 2048);
-        rc = vpbs_ivc_create(w.ctx, cyclic, dummy, N, K, ggsw_len, nullptr, &w.ivc, e, sizeof e);
-        if (rc != VPBS_OK) return report(err, err_len, std::string("vpbs_ivc_create: ") + e), rc;
-        rc = vpbs_ivc_set_device_witness(w.ivc, prm->ELL, prm->LOGB, witness_batch, 0);
-        if (rc != VPBS_OK) return report(err, err_len, std::string("vpbs_ivc_set_device_witness: ") + vpbs_ivc_last_error(w.ivc)), rc;
-        (void)vpbs_ivc_set_checkpoint(w.ivc, 0, nullptr, nullptr);
-    }
-    ivc_shape(p->workers[0].ivc, &p->shape);
-    const IvcShape& sh = p->shape;
-    p->max_bytes = 8 * (sh.proof_words + sh.n_pi) + (1 << 16);
+    pool.boot_ctx = p->boot_ctx;
+    rc = pool.create_chains(cyclic, dummy, prm, chains, witness_batch, log_n_max, err, err_len);
+    if (rc != VPBS_OK) return rc;
     // ---- the resident key set, its hash chain, the Bootstrapper ----
     std::vector<u64> host_keys;   // device keys: downloaded once for the hash chain
     const u64 *h_bsk = bsk, *h_ksk = ksk;
@@ -306,8 +72,8 @@ int vpbs_pbs_prover_create(int device_ordinal, const vpbs_ivc_circuit* cyclic, c
         VPBS_HIP(hipSetDevice(device_ordinal));
         hipStream_t s = p->boot_ctx->stream;
         if (keys_on_device) {
-            p->d_bsk = bsk;
-            p->d_ksk = ksk;
+            p->keys.d_bsk = bsk;
+            p->keys.d_ksk = ksk;
             host_keys.resize((size_t)(n_lwe + 1) * ggsw_len);
             VPBS_HIP(hipMemcpyAsync(host_keys.data(), bsk, 8 * (size_t)n_lwe * ggsw_len, hipMemcpyDeviceToHost, s));
             VPBS_HIP(hipMemcpyAsync(host_keys.data() + (size_t)n_lwe * ggsw_len, ksk, 8 * ggsw_len, hipMemcpyDeviceToHost, s));
@@ -315,47 +81,42 @@ int vpbs_pbs_prover_create(int device_ordinal, const vpbs_ivc_circuit* cyclic, c
             h_bsk = host_keys.data();
             h_ksk = host_keys.data() + (size_t)n_lwe * ggsw_len;
         } else {
-            u64 *d_b = p->alloc((size_t)n_lwe * ggsw_len), *d_k = p->alloc(ggsw_len);
+            u64 *d_b = pool.alloc((size_t)n_lwe * ggsw_len), *d_k = pool.alloc(ggsw_len);
             VPBS_HIP(hipMemcpyAsync(d_b, bsk, 8 * (size_t)n_lwe * ggsw_len, hipMemcpyHostToDevice, s));
             VPBS_HIP(hipMemcpyAsync(d_k, ksk, 8 * ggsw_len, hipMemcpyHostToDevice, s));
-            p->d_bsk = d_b;
-            p->d_ksk = d_k;
+            p->keys.d_bsk = d_b;
+            p->keys.d_ksk = d_k;
         }
         // the key hash chain over [0^ggsw_len, bsk_0 .. bsk_{n-1}, ksk], every link kept
         const std::vector<u64> zero(ggsw_len, 0);
-        std::vector<const u64*> items(p->total);
+        std::vector<const u64*> items(pool.total);
         items[0] = zero.data();
         for (unsigned x = 0; x < n_lwe; ++x) items[1 + x] = h_bsk + (size_t)x * ggsw_len;
         items[n_lwe + 1] = h_ksk;
         const u64 prefix[4] = {0, 0, 0, 0};
-        p->key_links.resize(4 * (size_t)p->total);
-        if (vpbs_hash_chain_links(prefix, items.data(), p->total, ggsw_len, p->key_links.data()) != 0)
+        p->key_links.resize(4 * (size_t)pool.total);
+        if (vpbs_hash_chain_links(prefix, items.data(), pool.total, ggsw_len, p->key_links.data()) != 0)
             throw DeviceError{VPBS_ERR_INVALID, "hash chain of the keys: malformed arguments"};
-        p->d_key_links = p->alloc(p->key_links.size());
-        VPBS_HIP(hipMemcpyAsync(p->d_key_links, p->key_links.data(), 8 * p->key_links.size(), hipMemcpyHostToDevice, s));
-        // the constants of every step: own verifier data | dummy verifier data | the dummy proof
-        std::vector<u64> consts(sh.cyc_vk, sh.cyc_vk + sh.vk_words);
-        consts.insert(consts.end(), sh.dum_vk, sh.dum_vk + sh.vk_words);
-        consts.insert(consts.end(), sh.dummy_proof, sh.dummy_proof + sh.proof_words);
-        p->d_consts = p->alloc(consts.size());
-        VPBS_HIP(hipMemcpyAsync(p->d_consts, consts.data(), 8 * consts.size(), hipMemcpyHostToDevice, s));
-        for (auto& w : p->workers) {
-            w.d_accs = p->alloc((size_t)p->total * sh.kn);
-            w.d_lwe_links = p->alloc(4 * (size_t)p->total);
-            w.d_ct = p->alloc(n_lwe + 1);
-            w.d_testv = p->alloc(N);
-            if (!(w.accs = static_cast<u64*>(vpbs_host_alloc(8 * (size_t)p->total * sh.kn)))) throw DeviceError{VPBS_ERR_OOM, "out of pinned memory"};
-            w.lwe_links.resize(4 * (size_t)p->total);
-            w.proof.resize(p->max_bytes);
-        }
-        VPBS_HIP(vpbs::stream_sync(s));   // the caller's key arrays and the staging vectors may go away
+        u64* d_links = pool.alloc(p->key_links.size());
+        VPBS_HIP(hipMemcpyAsync(d_links, p->key_links.data(), 8 * p->key_links.size(), hipMemcpyHostToDevice, s));
+        p->keys.d_key_links = d_links;
+        p->keys.key_links = p->key_links.data();
+        pool.alloc_buffers();   // waits: the caller's key arrays and the staging vectors may go away
     } catch (const DeviceError& x) {
         (void)vpbs::stream_sync(p->boot_ctx->stream);
         report(err, err_len, x.what);
         return x.status;
     }
-    rc = vpbs_bootstrapper_create(p->boot_ctx, prm, n_lwe, p->d_bsk, p->d_ksk, 1, vpbs_pbs_prover::BOOT_BATCH, &p->boot, e, sizeof e);
+    rc = vpbs_bootstrapper_create(p->boot_ctx, prm, n_lwe, p->keys.d_bsk, p->keys.d_ksk, 1, vpbs_pbs_prover::BOOT_BATCH, &p->boot, e, sizeof e);
     if (rc != VPBS_OK) return report(err, err_len, std::string("vpbs_bootstrapper_create: ") + e), rc;
+    // the key source: one key set for every ciphertext, accumulators from a count-1 run of the Bootstrapper
+    vpbs_pbs_prover* self = p.get();
+    pool.keys_of = [self](size_t) { return self->keys; };
+    pool.accumulators = [self](ProvePool::Worker& w, std::string& why) {
+        if (vpbs_bootstrapper_run(self->boot, w.d_ct, 1, w.d_testv, 0, nullptr, nullptr, w.d_accs, 1) == 1) return true;
+        why = vpbs_last_error(self->boot_ctx);
+        return false;
+    };
     *out = p.release();
     report(err, err_len, "");
     return VPBS_OK;
@@ -365,43 +126,31 @@ void vpbs_pbs_prover_free(vpbs_pbs_prover* p) { delete p; }
 
 int vpbs_pbs_prover_key_hash(const vpbs_pbs_prover* p, uint64_t out[4]) {
     if (!p || !out) return VPBS_ERR_INVALID;
-    std::memcpy(out, p->key_links.data() + 4 * (size_t)(p->total - 1), 32);
+    std::memcpy(out, p->key_links.data() + 4 * (size_t)(p->pool.total - 1), 32);
     return VPBS_OK;
 }
 
 int vpbs_pbs_prover_verifier_data(const vpbs_pbs_prover* p, uint64_t* cyclic_vk, uint64_t* dummy_vk) {
     if (!p) return VPBS_ERR_INVALID;
-    return vpbs_ivc_verifier_data(p->workers[0].ivc, cyclic_vk, dummy_vk);
+    return vpbs_ivc_verifier_data(p->pool.workers[0].ivc, cyclic_vk, dummy_vk);
 }
 
 int vpbs_pbs_prover_set_check_witness(vpbs_pbs_prover* p, int on) {
     if (!p) return VPBS_ERR_INVALID;
     std::lock_guard<std::mutex> run(p->run_mu);
-    for (auto& w : p->workers) {
-        const int rc = vpbs_ivc_set_check_witness(w.ivc, on);
-        if (rc != VPBS_OK) return rc;
-    }
-    return VPBS_OK;
+    return p->pool.set_check_witness(on);
 }
 
 int vpbs_pbs_prover_witness_checks(const vpbs_pbs_prover* p, uint64_t out[2]) {
     if (!p || !out) return VPBS_ERR_INVALID;
-    out[0] = out[1] = 0;
-    for (const auto& w : p->workers) {
-        uint64_t c[2] = {0, 0};
-        (void)vpbs_ivc_witness_checks(w.ivc, c);
-        out[0] += c[0];
-        out[1] += c[1];
-    }
+    p->pool.witness_checks(out);
     return VPBS_OK;
 }
 
 int vpbs_pbs_prover_set_checkpoint(vpbs_pbs_prover* p, unsigned every, vpbs_pbs_checkpoint_fn fn, void* user) {
     if (!p) return VPBS_ERR_INVALID;
     std::lock_guard<std::mutex> run(p->run_mu);
-    p->ckpt_fn = every ? fn : nullptr;
-    p->ckpt_user = user;
-    for (auto& w : p->workers) (void)vpbs_ivc_set_checkpoint(w.ivc, fn ? every : 0, fn ? &vpbs_pbs_prover::on_checkpoint : nullptr, &w);
+    p->pool.set_checkpoint(every, fn, user);
     return VPBS_OK;
 }
 
@@ -416,16 +165,17 @@ long vpbs_pbs_prover_run(vpbs_pbs_prover* p, const uint64_t* cts, size_t count, 
     if (!proof_fn) return refuse("no proof_fn: the proofs have nowhere to go");
     if (count && (!cts || !testv)) return refuse("null cts or testv");
     if (!p) return refuse("null prover");
-    if (steps > p->total) return refuse("steps exceeds n_lwe + 2 = " + std::to_string(p->total));
+    ProvePool& pool = p->pool;
+    if (steps > pool.total) return refuse("steps exceeds n_lwe + 2 = " + std::to_string(pool.total));
     if (count == 0) return 0;
     std::lock_guard<std::mutex> run(p->run_mu);
     const double t_call = now_s();
-    p->stats = vpbs_pbs_run_stats{};
-    const unsigned n_lwe = p->n_lwe, N = p->shape.N;
-    const size_t kn = p->shape.kn, ct_words = n_lwe + 1;
+    pool.stats = vpbs_pbs_run_stats{};
+    const unsigned N = pool.shape.N;
+    const size_t kn = pool.shape.kn, ct_words = pool.n_lwe + 1;
     // ---- every output first: one Bootstrapper launch per BOOT_BATCH ciphertexts ----
     if (out_ct || lwe_out) {
-        std::lock_guard<std::mutex> lk(p->boot_mu);
+        std::lock_guard<std::mutex> lk(pool.boot_mu);
         for (size_t i0 = 0; i0 < count; i0 += vpbs_pbs_prover::BOOT_BATCH) {
             const size_t c = std::min(vpbs_pbs_prover::BOOT_BATCH, count - i0);
             const long rc = vpbs_bootstrapper_run(p->boot, cts + i0 * ct_words, c, testv + (testv_per_ct ? i0 * N : 0), testv_per_ct,
@@ -436,87 +186,39 @@ long vpbs_pbs_prover_run(vpbs_pbs_prover* p, const uint64_t* cts, size_t count, 
             }
         }
     }
-    // ---- the proofs: workers take ciphertext indices from a queue; one that fails reports and takes the next, nobody waits for anybody ----
-    p->stats.outputs_seconds = out_ct || lwe_out ? now_s() - t_call : 0.0;
-    std::mutex q_mu;
-    size_t next = 0;
-    long delivered = 0;
-    double prepare_s = 0;
-    vpbs_ivc_timing sum{};   // over the delivered chains (under cb_mu)
-    auto work = [&](vpbs_pbs_prover::Worker& w) {
-        (void)pthread_setname_np(pthread_self(), "vpbs-chain");
-        for (;;) {
-            {
-                std::lock_guard<std::mutex> lk(q_mu);
-                if (next >= count) return;
-                w.index = next++;
-            }
-            const u64 *ct = cts + w.index * ct_words, *tv = testv + (testv_per_ct ? w.index * N : 0);
-            std::string why;
-            const double t_prepare = now_s();
-            long n = p->prepare_chain(w, ct, tv, why);
-            const double d_prepare = now_s() - t_prepare;
-            vpbs_ivc_timing t{};
-            if (n == VPBS_OK) {
-                const IvcResidentChain chain{w.accs, p->key_links.data(), w.lwe_links.data(), &vpbs_pbs_prover::fill, &w};
-                char e[512] = {0};
-                n = ivc_prove_pbs_resident(w.ivc, tv, ct, n_lwe, &chain, steps, w.proof.data(), w.proof.size(), &t, e, sizeof e);
-                if (n <= 0) why = e;
-            }
-            std::lock_guard<std::mutex> lk(p->cb_mu);
-            if (n > 0) {
-                proof_fn(user, w.index, w.proof.data(), (size_t)n, nullptr);
-                ++delivered;
-                prepare_s += d_prepare;
-                sum.seconds += t.seconds; sum.steps = t.steps; sum.base_proof_ms += t.base_proof_ms; sum.late_witness_ms += t.late_witness_ms;
-                sum.late_rows_upload_ms += t.late_rows_upload_ms; sum.prove_step_ms += t.prove_step_ms; sum.early_witness_ms += t.early_witness_ms;
-                sum.late_ahead_ms += t.late_ahead_ms;
-            } else {
-                proof_fn(user, w.index, nullptr, 0, why.empty() ? "the chain failed" : why.c_str());
-            }
-        }
-    };
-    std::vector<std::thread> threads;
-    const size_t n_threads = std::min(count, p->workers.size());
-    for (size_t t = 0; t < n_threads; ++t) threads.emplace_back(work, std::ref(p->workers[t]));
-    for (auto& t : threads) t.join();
-    p->stats.seconds = now_s() - t_call;
-    p->stats.proofs = (size_t)delivered;
-    if (delivered) {
-        const double d = (double)delivered;
-        p->stats.prepare_chain_ms = 1e3 * prepare_s / d;
-        p->stats.chain = vpbs_ivc_timing{sum.seconds / d, sum.steps, sum.base_proof_ms / d, sum.late_witness_ms / d, sum.late_rows_upload_ms / d,
-                                         sum.prove_step_ms / d, sum.early_witness_ms / d, sum.late_ahead_ms / d};
-    }
-    return delivered;
+    // ---- the proofs: the pool's workers take ciphertext indices from a queue ----
+    pool.stats.outputs_seconds = out_ct || lwe_out ? now_s() - t_call : 0.0;
+    return pool.prove(cts, count, testv, testv_per_ct, steps, t_call, proof_fn, user);
 }
 
 int vpbs_pbs_prover_last_run(const vpbs_pbs_prover* p, vpbs_pbs_run_stats* out) {
     if (!p || !out) return VPBS_ERR_INVALID;
-    *out = p->stats;
+    *out = p->pool.stats;
     return VPBS_OK;
 }
 
 // ---- test entries (test_entries.h) ----
 int vpbs_test_pbs_prover_dummy_proof(const vpbs_pbs_prover* p, uint64_t* out) {
     if (!p || !out) return VPBS_ERR_INVALID;
-    std::memcpy(out, p->shape.dummy_proof, 8 * p->shape.proof_words);   // the vpbs_ivc's own copy, not the device block the kernels read
+    std::memcpy(out, p->pool.shape.dummy_proof, 8 * p->pool.shape.proof_words);   // the vpbs_ivc's own copy, not the device block the kernels read
     return VPBS_OK;
 }
 
 int vpbs_test_pbs_prover_preset_matrix(vpbs_pbs_prover* p, const uint64_t* ct, const uint64_t* testv, unsigned first, unsigned count, uint64_t* out) {
     using namespace vpbs;
-    if (!p || !ct || !testv || !out || count == 0 || first + count > p->total || first + count < first) return VPBS_ERR_INVALID;
+    if (!p || !ct || !testv || !out || count == 0 || first + count > p->pool.total || first + count < first) return VPBS_ERR_INVALID;
     std::lock_guard<std::mutex> run(p->run_mu);
-    vpbs_pbs_prover::Worker& w = p->workers[0];
+    ProvePool& pool = p->pool;
+    ProvePool::Worker& w = pool.workers[0];
+    w.index = 0;
     std::string why;
-    int rc = p->prepare_chain(w, ct, testv, why);
+    int rc = pool.prepare_chain(w, ct, testv, why);
     if (rc != VPBS_OK) return p->boot_ctx->err = why, rc;
-    std::lock_guard<std::mutex> lk(p->boot_mu);
+    std::lock_guard<std::mutex> lk(pool.boot_mu);
     u64* d_m = nullptr;
     try {
-        VPBS_HIP(hipSetDevice(p->device));
-        const PresetArgs a = p->preset_args(w, first, count, nullptr);
+        VPBS_HIP(hipSetDevice(pool.device));
+        const PresetArgs a = pool.preset_args(w, first, count, nullptr);
         const size_t words = a.n_preset() * count;
         d_m = p->boot_ctx->alloc_words(words);
         PresetArgs b = a;
@@ -535,6 +237,6 @@ int vpbs_test_pbs_prover_preset_matrix(vpbs_pbs_prover* p, const uint64_t* ct, c
     return rc;
 }
 
-size_t vpbs_test_pbs_prover_preset_words(const vpbs_pbs_prover* p) { return p ? p->shape.n_preset : 0; }
+size_t vpbs_test_pbs_prover_preset_words(const vpbs_pbs_prover* p) { return p ? p->pool.shape.n_preset : 0; }
 
 }  // extern "C"

@@ -20,6 +20,8 @@
 //           Every index array of every launch is uploaded once, before the first launch; gather_rows_kernel delivers the three outputs in
 //           the caller's instance and gate order; the host waits once.
 //   prove   run on the batch prover's Bootstrapper, then vpbs_pbs_prover_run on the gate inputs (caller's order) with per-gate test vectors.
+//   prove_batch  run_batch on the ring of a ring prover (pbs_prove_ring.hip), then vpbs_ring_prover_run on the gate inputs of every instance,
+//           row b * n_gates + g under the slot of instance b, under the prover's mutex from the evaluation to the last proof.
 //   verify  upload inputs and claimed outputs, lwe_extract_kernel on all outputs, ONE lwe_combine_kernel over all gates in the caller's
 //           order, then vpbs_pbs_verifier_run in chunks.
 #include <algorithm>
@@ -566,6 +568,43 @@ long vpbs_program_prove(vpbs_program* prog, vpbs_pbs_prover* pbs_prover, const u
     if (prog->n_gates == 0) return 0;
     for (unsigned g = 0; g < prog->n_gates; ++g) std::memcpy(tv.data() + (size_t)g * n, testvs + (size_t)prog->given.lut[g] * n, 8 * n);
     return vpbs_pbs_prover_run(pbs_prover, gate_cts.data(), prog->n_gates, tv.data(), 1, steps, nullptr, nullptr, proof_fn, user, err, err_len);
+}
+
+long vpbs_program_prove_batch(vpbs_program* prog, vpbs_ring_prover* ring_prover, const uint64_t* inputs, size_t instances, const uint32_t* key_of,
+                              const uint64_t* testvs, unsigned steps, uint64_t* wires_out, uint64_t* out_cts, vpbs_pbs_proof_fn proof_fn, void* user,
+                              char* err, size_t err_len) {
+    using namespace vpbs;
+    auto refuse = [&](const std::string& m) {
+        report(err, err_len, m);
+        return (long)VPBS_ERR_INVALID;
+    };
+    report(err, err_len, "");
+    if (!ring_prover) return refuse("vpbs_program_prove_batch: null ring prover");
+    if (!prog) return refuse("vpbs_program_prove_batch: null program");
+    if (!proof_fn) return refuse("no proof_fn: the proofs have nowhere to go");
+    vpbs_keyring* ring = vpbs_ring_prover_keyring(ring_prover);
+    KeyringShape sh{};
+    keyring_shape(ring, &sh);
+    if (steps > sh.n_lwe + 2) return refuse("steps exceeds n_lwe + 2 = " + std::to_string(sh.n_lwe + 2));
+    const size_t n = (size_t)1 << sh.prm.log_N, words = sh.n_lwe + 1, n_gates = prog->n_gates;
+    // from the evaluation to the last proof no key set comes or goes: the ring takes them from its prover alone, and the prover waits here
+    std::lock_guard<std::mutex> run(ring_prover_mutex(ring_prover));
+    if (n_gates && instances > 0x7fffffffull / n_gates) return refuse("vpbs_program_prove_batch: instances x gates exceeds 2^31 - 1 rows");
+    std::vector<u64> gate_cts(instances * n_gates * words);
+    // the refusals are run_batch's: checked there before anything is queued, the message in the ring's context
+    const long rc = program_run_batch(prog, ring, inputs, instances, key_of, testvs, wires_out, gate_cts.empty() ? nullptr : gate_cts.data(), out_cts, 0);
+    if (rc < 0) return report(err, err_len, std::string("evaluating the program: ") + vpbs_last_error(sh.ctx)), rc;
+    if (n_gates == 0 || instances == 0) return 0;
+    // row b * n_gates + g: gate g of instance b, with the gate's test vector and the instance's slot
+    std::vector<u64> tv(instances * n_gates * n);
+    std::vector<u32> slot_of(instances * n_gates);
+    for (size_t b = 0; b < instances; ++b)
+        for (size_t g = 0; g < n_gates; ++g) {
+            std::memcpy(tv.data() + (b * n_gates + g) * n, testvs + (size_t)prog->given.lut[g] * n, 8 * n);
+            slot_of[b * n_gates + g] = key_of[b];
+        }
+    return ring_prover_run_locked(ring_prover, gate_cts.data(), instances * n_gates, slot_of.data(), tv.data(), 1, steps, nullptr, nullptr, proof_fn,
+                                  user, err, err_len);
 }
 
 long vpbs_program_verify(vpbs_program* prog, vpbs_pbs_verifier* pbs_verifier, const uint64_t* inputs, const uint64_t* testvs,

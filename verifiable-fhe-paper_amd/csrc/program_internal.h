@@ -1,5 +1,5 @@
-// The seam between the program object (program.hip) and the four objects it drives: the Bootstrapper (pbs_batch.hip), the key ring
-// (pbs_keyring.hip), the batch prover (pbs_prove_batch.hip) and the batch verifier of whole vPBS proofs (verify_pbs_batch.hip).  A program queues one bootstrap launch per
+// The seam between the program object (program.hip) and the five objects it drives: the Bootstrapper (pbs_batch.hip), the key ring
+// (pbs_keyring.hip), the batch provers (pbs_prove_batch.hip, pbs_prove_ring.hip) and the batch verifier of whole vPBS proofs (verify_pbs_batch.hip).  A program queues one bootstrap launch per
 // level behind its own combine kernel and waits once, at the end: it needs the Bootstrapper's launch WITHOUT the wait vpbs_bootstrapper_run
 // ends with, and the shapes of objects whose structs are private to their files.  Library-internal, like ivc_resident.h.
 #pragma once
@@ -50,6 +50,21 @@ bool keyring_check_slots(const vpbs_keyring* r, const uint32_t* key_of, size_t c
 // vpbs::DeviceError for a failed launch; the caller holds the mutex and the device (hipSetDevice).
 void keyring_enqueue(vpbs_keyring* r, const uint64_t* d_cts, size_t count, const uint64_t* d_testv, int testv_per_ct, const uint32_t* d_order,
                      const uint32_t* d_key_of, uint64_t* d_out_ct, uint64_t* d_lwe_out, uint64_t* d_accs_out);
+
+// The device pointers the ring's table holds for `slot` (null for an empty slot or one out of range): what a prover of that slot's
+// bootstraps reads the GGSW rows from.  The caller holds the ring's mutex, or otherwise knows that no add or remove is under way.
+void keyring_slot_keys(const vpbs_keyring* r, unsigned slot, const uint64_t** d_bsk, const uint64_t** d_ksk);
+// vpbs_keyring_add and vpbs_keyring_remove are these with owner = false.  After keyring_set_owned the ring refuses both with a message
+// unless owner is true: the ring of a vpbs_ring_prover (pbs_prove_ring.hip), whose slots carry a key hash chain that the prover keeps.
+void keyring_set_owned(vpbs_keyring* r);
+int keyring_add(vpbs_keyring* r, const uint64_t* bsk, const uint64_t* ksk, int keys_on_device, unsigned* slot_out, bool owner);
+int keyring_remove(vpbs_keyring* r, unsigned slot, bool owner);
+
+// ---- the ring prover (pbs_prove_ring.hip), for vpbs_program_prove_batch ----
+// the mutex that add, remove and run of the ring prover take, and vpbs_ring_prover_run for a caller that holds it
+std::mutex& ring_prover_mutex(vpbs_ring_prover* p);
+long ring_prover_run_locked(vpbs_ring_prover* p, const uint64_t* cts, size_t count, const uint32_t* key_of, const uint64_t* testv, int testv_per_ct,
+                            unsigned steps, uint64_t* out_ct, uint64_t* lwe_out, vpbs_pbs_proof_fn proof_fn, void* user, char* err, size_t err_len);
 
 struct PbsVerifierShape {
     vpbs_ctx* ctx;
