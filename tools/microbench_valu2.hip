@@ -13,6 +13,7 @@
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
+#include <cstring>
 #include <array>
 #include <map>
 #include <vector>
@@ -153,6 +154,94 @@ KERNEL_PRODUCT(k_product_old, PAIR_OLD(FROM_OPS), PAIR_OLD(FROM_B))
 KERNEL_PRODUCT(k_product_chain_mov, PAIR_CHAIN(MOVE_MOV, E_TWO_MOVES, FROM_OPS), PAIR_CHAIN(MOVE_MOV, E_TWO_MOVES, FROM_B))
 KERNEL_PRODUCT(k_product_chain_add, PAIR_CHAIN(MOVE_ADD, E_TWO_MOVES, FROM_OPS), PAIR_CHAIN(MOVE_ADD, E_TWO_MOVES, FROM_B))
 KERNEL_PRODUCT(k_product_chain_shift, PAIR_CHAIN(MOVE_MOV, E_SHIFT, FROM_OPS), PAIR_CHAIN(MOVE_MOV, E_SHIFT, FROM_B))
+// ---- round 8: the carry's correction c (2^32 - 1) behind every reduction as ONE multiply-add (t = c ? 1 : 0;  r = t (2^32 - 1) + r) against
+// the select of 0 / -1 + 64-bit addition it replaces; measured on the whole reduction tail of csrc/gl.h, the whole fold96 of csrc/poseidon.h and
+// the whole product, each as a block whose result is the next block's operand, 32 blocks per loop iteration, in place on fixed registers
+// (v40..v47 scratch as in gl.h, v48..v51 the product's operands; 4 moves in and 4 out per iteration, the same for every form: ~1 %).
+// SEL makes t from the carry in s[80:81] (the tail) or vcc (fold96).
+#define R8_SEL_MINUS1(S) "v_cndmask_b32_e64 v47, 0, -1, " S "\n\t"
+#define R8_SEL_CNDMASK(S) "v_cndmask_b32_e64 v47, 0, 1, " S "\n\t"
+#define R8_SEL_ADDC(S) "v_addc_co_u32_e64 v47, " S ", 0, 0, " S "\n\t"
+#define R8_ADD_OLD(O0, O1, OP) "v_add_co_u32_e32 " O0 ", vcc, v40, v47\n\tv_addc_co_u32_e64 " O1 ", vcc, v41, 0, vcc\n\t"
+#define R8_ADD_MAD(O0, O1, OP) "v_mad_u64_u32 " OP ", vcc, v47, -1, v[40:41]\n\t"
+// the tail: 128-bit value {v[40:41], v44, v45} -> a residue in (O0, O1) = the pair OP.  SUB0: the first word of u - hi_hi (with or without borrow-in)
+#define R8_SUB0_PLAIN "v_sub_co_u32_e32 v40, vcc, v40, v45\n\t"
+#define R8_SUB0_BORROW_IN "v_subb_co_u32_e64 v40, vcc, v40, v45, s[82:83]\n\t"
+#define R8_TAIL(SEL, ADD, SUB0, O0, O1, OP) \
+    "v_mad_u64_u32 v[40:41], s[80:81], v44, -1, v[40:41]\n\t" \
+    SUB0 \
+    "v_subbrev_co_u32_e32 v41, vcc, 0, v41, vcc\n\t" \
+    SEL("s[80:81]") \
+    "s_cbranch_vccz 1f\n\t" \
+    "v_cndmask_b32_e64 v46, 0, -1, vcc\n\t" \
+    "v_sub_co_u32_e32 v40, vcc, v40, v46\n\t" \
+    "v_subbrev_co_u32_e32 v41, vcc, 0, v41, vcc\n" \
+    "1:\n\t" \
+    ADD(O0, O1, OP)
+// fold96: acc_lo = v[40:41] (in and out), hi_lo = v44, hi_hi = v45
+#define R8_FOLD(SEL, ADD) \
+    "v_mad_u64_u32 v[40:41], vcc, v45, -1, v[40:41]\n\t" \
+    "v_add_co_u32_e32 v41, vcc, v41, v44\n\t" \
+    SEL("vcc") \
+    ADD("v40", "v41", "v[40:41]")
+// the product a (v48, v49) x b (v50, v51) chained as in gl.h; CARRY the SGPR pair of the middle word's carry c_M, F1 what makes F's high word
+#define R8_PRODUCT(CARRY, F1) \
+    "v_mad_u64_u32 v[40:41], vcc, v48, v50, 0\n\t" \
+    "v_lshrrev_b64 v[42:43], 32, v[40:41]\n\t" \
+    "v_mad_u64_u32 v[42:43], vcc, v48, v51, v[42:43]\n\t" \
+    "v_mad_u64_u32 v[42:43], " CARRY ", v49, v50, v[42:43]\n\t" \
+    "v_mov_b32 v44, v43\n\t" \
+    F1 \
+    "v_mad_u64_u32 v[44:45], vcc, v49, v51, v[44:45]\n\t" \
+    "v_mov_b32 v41, v42\n\t"
+#define R8_F1_CARRY "v_cndmask_b32_e64 v45, 0, 1, s[80:81]\n\t"
+#define R8_F1_ZERO "v_mov_b32 v45, 0\n\t"
+#define X32(b) X16(X2(b, b), X2(b, b))
+#define KERNEL_R8(name, V0, V1, V2, V3, BLOCK) \
+    __global__ void __launch_bounds__(1024) name(uint32_t* out, Stamp* stamps, uint32_t seed) { \
+        PROLOGUE \
+        asm volatile("v_mov_b32 " V0 ", %0\n\tv_mov_b32 " V1 ", %1\n\tv_mov_b32 " V2 ", %2\n\tv_mov_b32 " V3 ", %3\n\t" \
+                     X32(BLOCK) \
+                     "v_mov_b32 %0, " V0 "\n\tv_mov_b32 %1, " V1 "\n\tv_mov_b32 %2, " V2 "\n\tv_mov_b32 %3, " V3 \
+                     : "+v"(a[0]), "+v"(b[0]), "+v"(c[0]), "+v"(d[0]) \
+                     : : "v40", "v41", "v42", "v43", "v44", "v45", "v46", "v47", "v48", "v49", "v50", "v51", "vcc", "scc", "s80", "s81", "s82", "s83"); \
+        EPILOGUE }
+#define KERNEL_R8_RED(name, BLOCK) KERNEL_R8(name, "v40", "v41", "v44", "v45", BLOCK)
+#define KERNEL_R8_MUL(name, BLOCK) KERNEL_R8(name, "v48", "v49", "v50", "v51", BLOCK)
+KERNEL_R8_RED(k_tail_old, R8_TAIL(R8_SEL_MINUS1, R8_ADD_OLD, R8_SUB0_PLAIN, "v40", "v41", "v[40:41]"))
+KERNEL_R8_RED(k_tail_mad_cndmask, R8_TAIL(R8_SEL_CNDMASK, R8_ADD_MAD, R8_SUB0_PLAIN, "v40", "v41", "v[40:41]"))
+KERNEL_R8_RED(k_tail_mad_addc, R8_TAIL(R8_SEL_ADDC, R8_ADD_MAD, R8_SUB0_PLAIN, "v40", "v41", "v[40:41]"))
+KERNEL_R8_RED(k_fold_old, R8_FOLD(R8_SEL_MINUS1, R8_ADD_OLD))
+KERNEL_R8_RED(k_fold_mad_cndmask, R8_FOLD(R8_SEL_CNDMASK, R8_ADD_MAD))
+KERNEL_R8_RED(k_fold_mad_addc, R8_FOLD(R8_SEL_ADDC, R8_ADD_MAD))
+KERNEL_R8_MUL(k_mul_old, R8_PRODUCT("s[80:81]", R8_F1_CARRY) R8_TAIL(R8_SEL_MINUS1, R8_ADD_OLD, R8_SUB0_PLAIN, "v48", "v49", "v[48:49]"))
+KERNEL_R8_MUL(k_mul_mad_cndmask, R8_PRODUCT("s[80:81]", R8_F1_CARRY) R8_TAIL(R8_SEL_CNDMASK, R8_ADD_MAD, R8_SUB0_PLAIN, "v48", "v49", "v[48:49]"))
+KERNEL_R8_MUL(k_mul_mad_addc, R8_PRODUCT("s[80:81]", R8_F1_CARRY) R8_TAIL(R8_SEL_ADDC, R8_ADD_MAD, R8_SUB0_PLAIN, "v48", "v49", "v[48:49]"))
+// add_a: a (v40, v41, in and out) + b (v44, v45) for any residues; the second correction sits behind its never-taken wave-level branch
+#define R8_ADDA_OLD \
+    "v_add_co_u32_e32 v40, vcc, v40, v44\n\t" \
+    "v_addc_co_u32_e32 v41, vcc, v41, v45, vcc\n\t" \
+    "v_cndmask_b32_e64 v47, 0, -1, vcc\n\t" \
+    "v_add_co_u32_e32 v40, vcc, v40, v47\n\t" \
+    "v_addc_co_u32_e64 v41, vcc, 0, v41, vcc\n\t" \
+    "s_cbranch_vccz 1f\n\t" \
+    "v_cndmask_b32_e64 v47, 0, -1, vcc\n\t" \
+    "v_add_co_u32_e32 v40, vcc, v40, v47\n\t" \
+    "v_addc_co_u32_e64 v41, vcc, 0, v41, vcc\n" \
+    "1:\n\t"
+#define R8_ADDA_MAD \
+    "v_add_co_u32_e32 v42, vcc, v40, v44\n\t" \
+    "v_addc_co_u32_e32 v43, vcc, v41, v45, vcc\n\t" \
+    "v_cndmask_b32_e64 v47, 0, 1, vcc\n\t" \
+    "v_mad_u64_u32 v[40:41], vcc, v47, -1, v[42:43]\n\t" \
+    "s_cbranch_vccz 1f\n\t" \
+    "v_cndmask_b32_e64 v47, 0, 1, vcc\n\t" \
+    "v_mad_u64_u32 v[40:41], vcc, v47, -1, v[40:41]\n" \
+    "1:\n\t"
+KERNEL_R8_RED(k_adda_old, R8_ADDA_OLD)
+KERNEL_R8_RED(k_adda_mad, R8_ADDA_MAD)
+// c_M as the borrow-in of u - hi_hi (weight 2^96 = -1): F = {M.hi, 0}, one more live scalar pair (s[82:83])
+KERNEL_R8_MUL(k_mul_mad_cndmask_cm, R8_PRODUCT("s[82:83]", R8_F1_ZERO) R8_TAIL(R8_SEL_CNDMASK, R8_ADD_MAD, R8_SUB0_BORROW_IN, "v48", "v49", "v[48:49]"))
 typedef void (*kern_t)(uint32_t*, Stamp*, uint32_t);
 struct Entry {
     const char* name;
@@ -161,7 +250,8 @@ struct Entry {
     bool per_block;       // report cycles per chain step (a whole product assembly), not per instruction
 };
 
-int main() {
+int main(int argc, char** argv) {
+    const char* only = argc > 1 ? argv[1] : nullptr;   // rows whose name contains this text (repeated runs of a few rows)
     hipDeviceProp_t prop;
     CHECK(hipGetDeviceProperties(&prop, 0));
     const int cus = prop.multiProcessorCount;
@@ -178,6 +268,13 @@ int main() {
         {"mix: 2 mad_u64_u32 + add_u32", k_mix_mad2_add, 3},
         {"product: old (8 half)", k_product_old, 1, true}, {"product: chained, v_mov (5+4)", k_product_chain_mov, 1, true},
         {"product: chained, v_add (5+4)", k_product_chain_add, 1, true}, {"product: chained, shift (6+2)", k_product_chain_shift, 1, true},
+        // round 8 (32 blocks per loop iteration, as the product rows)
+        {"r8 tail: 0/-1 + add64 (6)", k_tail_old, 1, true}, {"r8 tail: cndmask 0/1 + mad (5)", k_tail_mad_cndmask, 1, true},
+        {"r8 tail: addc 0/1 + mad (5)", k_tail_mad_addc, 1, true}, {"r8 fold96: 0/-1 + add64 (5)", k_fold_old, 1, true},
+        {"r8 fold96: cndmask 0/1+mad (4)", k_fold_mad_cndmask, 1, true}, {"r8 fold96: addc 0/1 + mad (4)", k_fold_mad_addc, 1, true},
+        {"r8 mul_nc: as it was (12+2)", k_mul_old, 1, true}, {"r8 mul_nc: cndmask+mad (11+2)", k_mul_mad_cndmask, 1, true},
+        {"r8 mul_nc: addc + mad (11+2)", k_mul_mad_addc, 1, true}, {"r8 mul_nc: c_M borrow-in(10+3)", k_mul_mad_cndmask_cm, 1, true},
+        {"r8 add_a: 0/-1 + add64 (5)", k_adda_old, 1, true}, {"r8 add_a: cndmask 0/1+mad (4)", k_adda_mad, 1, true},
     };
     const int ws[] = {1, 2, 4, 8};
     const size_t max_threads = (size_t)cus * 2048;
@@ -195,6 +292,7 @@ int main() {
     for (int w : ws) printf("  w=%d per SIMD", w);
     printf("   sclk(GHz)\n");
     for (const Entry& e : es) {
+        if (only && !strstr(e.name, only)) continue;
         printf("%-30s", e.name);
         double ghz = 0;
         for (int w : ws) {

@@ -111,8 +111,9 @@ GL_HD u64 reduce128_nc(u64 lo, u64 hi) {
 //            cycles measured, where adding the partial products afterwards (8 half-rate) took 32.2, two moves for E 26.2 and moves written
 //            as v_add_u32 dst, 0, src 30.4 (tools/microbench_valu2.hip, profiles/r07_microbench_valu2.txt).
 //   reduce : u = hi_lo * (2^32-1) + lo as ONE v_mad_u64_u32 with carry-out c; r = u - hi_hi with borrow b;
-//            r += (c - b) * (2^32 - 1)  -- neither correction can wrap a second time
-// 12 half-rate + 2 full-rate VALU + 1 SALU instead of the 26 VALU hipcc emits for the C form below.
+//            r += (c - b) * (2^32 - 1)  -- neither correction can wrap a second time; the carry's share is one more
+//            v_mad_u64_u32, (c ? 1 : 0) * (2^32 - 1) + r (round 8)
+// 11 half-rate + 2 full-rate VALU + 1 SALU instead of the 26 VALU hipcc emits for the C form below.
 // Scratch registers of the single-product form.  A translation unit whose kernels need few registers of their own (the
 // NTT kernels) defines GL_ASM_SCRATCH_LOW before including this header: the scratch block then sits at v24..v31 instead
 // of v80..v87, so those kernels are not pushed from ~50 to 96 VGPRs (5 -> 8 waves per SIMD).
@@ -165,56 +166,62 @@ GL_HD u64 reduce128_nc(u64 lo, u64 hi) {
 //   u = R4 (2^32 - 1) + P01 as ONE v_mad_u64_u32 with carry-out c;  r = u - R5 with borrow b;  r += (c - b)(2^32 - 1).
 // b needs u < R5 < 2^32, i.e. one product in 2^32: the borrow's correction (r -= 2^32 - 1, applied FIRST so that the carry's correction
 // cannot wrap) sits behind a wave-level branch that is practically never taken, and the common path pays only the carry's correction:
-// 6 VALU where computing both corrections as one signed addend took 8 VALU + 2 SALU (round 5).
+// 5 VALU (6 with the correction as a select of 0 / -1 and a 64-bit addition, rounds 5-7) where computing both corrections as one signed addend
+// took 8 VALU + 2 SALU (round 5).
 #define GL_MOV(DST, SRC) "v_mov_b32 " DST ", " SRC "\n\t"
+// The carry's correction c (2^32 - 1) is ONE multiply-add, r = t (2^32 - 1) + r with t = c ? 1 : 0 (GL_SEL01), where selecting 0 / -1 and
+// adding it as a 64-bit integer took two carry adds (round 8; the same 64-bit sum, so every residue is bit for bit what it was).  The
+// multiply-add writes an aligned pair: the result is ONE 64-bit output operand, %0.  It is the last thing a form writes, after every input has been
+// read, so it is no early-clobber operand: the allocator may put it on a dying input's pair (as early-clobber pairs the results pushed four of
+// the radix-16 NTT kernels from 96 to 98 VGPRs, 5 -> 4 waves per SIMD).
+#define GL_SEL01(DST, CARRY) "v_cndmask_b32_e64 " DST ", 0, 1, " CARRY "\n\t"
+#define GL_ADD_EPS_IF(DST64, T, SRC64) "v_mad_u64_u32 " DST64 ", vcc, " T ", -1, " SRC64
 #define GL_REDUCE_TAIL(UNIQ)                                                          \
     "v_mad_u64_u32 " GL_P01 ", s[80:81], " GL_R4 ", -1, " GL_P01 "\n\t"                \
     "v_sub_co_u32_e32 " GL_R0 ", vcc, " GL_R0 ", " GL_R5 "\n\t"                         \
     "v_subbrev_co_u32_e32 " GL_R1 ", vcc, 0, " GL_R1 ", vcc\n\t"                        \
-    "v_cndmask_b32_e64 " GL_R7 ", 0, -1, s[80:81]\n\t"                                  \
+    GL_SEL01(GL_R7, "s[80:81]")                                                        \
     "s_cbranch_vccz .Lgl_red_" UNIQ "\n\t"                                               \
     "v_cndmask_b32_e64 " GL_R6 ", 0, -1, vcc\n\t"                                       \
     "v_sub_co_u32_e32 " GL_R0 ", vcc, " GL_R0 ", " GL_R6 "\n\t"                         \
     "v_subbrev_co_u32_e32 " GL_R1 ", vcc, 0, " GL_R1 ", vcc\n"                           \
     ".Lgl_red_" UNIQ ":\n\t"                                                             \
-    "v_add_co_u32_e32 %0, vcc, " GL_R0 ", " GL_R7 "\n\t"                                \
-    "v_addc_co_u32_e64 %1, vcc, " GL_R1 ", 0, vcc"
+    GL_ADD_EPS_IF("%0", GL_R7, GL_P01)
 __device__ __forceinline__ u64 mul_nc(u64 a, u64 b) {
-    u32 r0, r1;
-    asm("v_mad_u64_u32 " GL_P01 ", vcc, %2, %4, 0\n\t"                       // P = a0 b0
+    u64 r;
+    asm("v_mad_u64_u32 " GL_P01 ", vcc, %1, %3, 0\n\t"                       // P = a0 b0
         "v_lshrrev_b64 " GL_P23 ", 32, " GL_P01 "\n\t"                        // E = {P.hi, 0}
-        "v_mad_u64_u32 " GL_P23 ", vcc, %2, %5, " GL_P23 "\n\t"              // M = a0 b1 + E
-        "v_mad_u64_u32 " GL_P23 ", s[80:81], %3, %4, " GL_P23 "\n\t"         // M = a1 b0 + M, carry c
+        "v_mad_u64_u32 " GL_P23 ", vcc, %1, %4, " GL_P23 "\n\t"              // M = a0 b1 + E
+        "v_mad_u64_u32 " GL_P23 ", s[80:81], %2, %3, " GL_P23 "\n\t"         // M = a1 b0 + M, carry c
         GL_MOV(GL_R4, GL_R3)                                                  // F = {M.hi, c}
         "v_cndmask_b32_e64 " GL_R5 ", 0, 1, s[80:81]\n\t"
-        "v_mad_u64_u32 " GL_P45 ", vcc, %3, %5, " GL_P45 "\n\t"              // H = a1 b1 + F
+        "v_mad_u64_u32 " GL_P45 ", vcc, %2, %4, " GL_P45 "\n\t"              // H = a1 b1 + F
         GL_MOV(GL_R1, GL_R2)                                                  // low 64 bits = {P.lo, M.lo}
         GL_REDUCE_TAIL("%=")
-        : "=&v"(r0), "=&v"(r1)
+        : "=v"(r)
         : "v"((u32)a), "v"((u32)(a >> 32)), "v"((u32)b), "v"((u32)(b >> 32))
         : GL_R0, GL_R1, GL_R2, GL_R3, GL_R4, GL_R5, GL_R6, GL_R7, "vcc", "scc", "s80", "s81");   // only what the form writes: every named scalar is one the allocator loses
-    return ((u64)r1 << 32) | r0;
+    return r;
 }
 // Two independent products with their instruction streams interleaved (second register set v88..v95 / s[86:91]): used
 // where a single wave has to hide its own dependent-instruction latency (x^3 and x^4 of the S-box in the 16-lane
 // Poseidon).  r = a * b, q = c * d.
 __device__ __forceinline__ void mul2_nc(u64 a, u64 b, u64 c, u64 d, u64& r, u64& q) {
-    u32 r0, r1, q0, q1;
     // both products chained as in mul_nc (2 x (6 half-rate + 2 full-rate) for the assemblies)
-    asm("v_mad_u64_u32 v[80:81], vcc, %4, %6, 0\n\t"
-        "v_mad_u64_u32 v[88:89], vcc, %8, %10, 0\n\t"
+    asm("v_mad_u64_u32 v[80:81], vcc, %2, %4, 0\n\t"
+        "v_mad_u64_u32 v[88:89], vcc, %6, %8, 0\n\t"
         "v_lshrrev_b64 v[82:83], 32, v[80:81]\n\t"
         "v_lshrrev_b64 v[90:91], 32, v[88:89]\n\t"
-        "v_mad_u64_u32 v[82:83], vcc, %4, %7, v[82:83]\n\t"
-        "v_mad_u64_u32 v[90:91], vcc, %8, %11, v[90:91]\n\t"
-        "v_mad_u64_u32 v[82:83], s[80:81], %5, %6, v[82:83]\n\t"
-        "v_mad_u64_u32 v[90:91], s[86:87], %9, %10, v[90:91]\n\t"
+        "v_mad_u64_u32 v[82:83], vcc, %2, %5, v[82:83]\n\t"
+        "v_mad_u64_u32 v[90:91], vcc, %6, %9, v[90:91]\n\t"
+        "v_mad_u64_u32 v[82:83], s[80:81], %3, %4, v[82:83]\n\t"
+        "v_mad_u64_u32 v[90:91], s[86:87], %7, %8, v[90:91]\n\t"
         GL_MOV("v84", "v83")
         "v_cndmask_b32_e64 v85, 0, 1, s[80:81]\n\t"
         GL_MOV("v92", "v91")
         "v_cndmask_b32_e64 v93, 0, 1, s[86:87]\n\t"
-        "v_mad_u64_u32 v[84:85], vcc, %5, %7, v[84:85]\n\t"
-        "v_mad_u64_u32 v[92:93], vcc, %9, %11, v[92:93]\n\t"
+        "v_mad_u64_u32 v[84:85], vcc, %3, %5, v[84:85]\n\t"
+        "v_mad_u64_u32 v[92:93], vcc, %7, %9, v[92:93]\n\t"
         GL_MOV("v81", "v82")
         GL_MOV("v89", "v90")
         // both reductions (GL_REDUCE_TAIL): the two borrows share ONE practically-never-taken branch
@@ -224,8 +231,8 @@ __device__ __forceinline__ void mul2_nc(u64 a, u64 b, u64 c, u64 d, u64& r, u64&
         "v_subbrev_co_u32_e64 v81, s[82:83], 0, v81, vcc\n\t"
         "v_sub_co_u32_e32 v88, vcc, v88, v93\n\t"
         "v_subbrev_co_u32_e64 v89, s[84:85], 0, v89, vcc\n\t"
-        "v_cndmask_b32_e64 v87, 0, -1, s[80:81]\n\t"
-        "v_cndmask_b32_e64 v95, 0, -1, s[86:87]\n\t"
+        GL_SEL01("v87", "s[80:81]")
+        GL_SEL01("v95", "s[86:87]")
         "s_or_b64 s[80:81], s[82:83], s[84:85]\n\t"    // (for SCC only; s[80:81] is dead here)
         "s_cbranch_scc0 .Lgl_red2_%=\n\t"
         "v_cndmask_b32_e64 v86, 0, -1, s[82:83]\n\t"
@@ -235,40 +242,36 @@ __device__ __forceinline__ void mul2_nc(u64 a, u64 b, u64 c, u64 d, u64& r, u64&
         "v_sub_co_u32_e32 v88, vcc, v88, v94\n\t"
         "v_subbrev_co_u32_e32 v89, vcc, 0, v89, vcc\n"
         ".Lgl_red2_%=:\n\t"
-        "v_add_co_u32_e32 %0, vcc, v80, v87\n\t"
-        "v_addc_co_u32_e64 %1, vcc, v81, 0, vcc\n\t"
-        "v_add_co_u32_e32 %2, vcc, v88, v95\n\t"
-        "v_addc_co_u32_e64 %3, vcc, v89, 0, vcc"
-        : "=&v"(r0), "=&v"(r1), "=&v"(q0), "=&v"(q1)
+        GL_ADD_EPS_IF("%0", "v87", "v[80:81]") "\n\t"
+        GL_ADD_EPS_IF("%1", "v95", "v[88:89]")
+        : "=v"(r), "=v"(q)
         : "v"((u32)a), "v"((u32)(a >> 32)), "v"((u32)b), "v"((u32)(b >> 32)), "v"((u32)c), "v"((u32)(c >> 32)), "v"((u32)d),
           "v"((u32)(d >> 32))
         : "v80", "v81", "v82", "v83", "v84", "v85", "v86", "v87", "v88", "v89", "v90", "v91", "v92", "v93", "v94", "v95", "vcc", "scc",
           "s80", "s81", "s82", "s83", "s84", "s85", "s86", "s87");
-    r = ((u64)r1 << 32) | r0;
-    q = ((u64)q1 << 32) | q0;
 }
 // a * b + c * d with ONE reduction: the two 128-bit products are added (the sum can reach 2^129: its top bit k joins hi_hi) and then
 // lo + hi_lo 2^64 + (hi_hi + k 2^32) 2^96 is reduced as in mul_nc.  The subtrahend hi_hi + k 2^32 is below 2^33 instead of 2^32, and
 // the single correction (c - b)(2^32 - 1) still cannot wrap: c = 1 means u < 2^64 - 2^33 + 1, so u + 2^32 - 1 < 2^64; b = 1 without c
 // means the wrapped difference is at least 2^64 - 2^33, so taking 2^32 - 1 away stays positive.  Any u64 residues in, a residue out.
 // Both products are chained as in mul_nc; their low pairs {P.lo, M.lo} need no move here, the 128-bit addition reads the words where they lie.
-// 23 half-rate + 2 full-rate VALU + 1 SALU against 2 x 14 + 8 for two products and a modular addition.
+// 22 half-rate + 2 full-rate VALU + 1 SALU against 2 x 13 + 4 for two products and a modular addition.
 __device__ __forceinline__ u64 dot2_nc(u64 a, u64 b, u64 c, u64 d) {
-    u32 r0, r1;
-    asm("v_mad_u64_u32 " GL_P01 ", vcc, %2, %4, 0\n\t"
-        "v_mad_u64_u32 " GL_Q01 ", vcc, %6, %8, 0\n\t"
+    u64 r;
+    asm("v_mad_u64_u32 " GL_P01 ", vcc, %1, %3, 0\n\t"
+        "v_mad_u64_u32 " GL_Q01 ", vcc, %5, %7, 0\n\t"
         "v_lshrrev_b64 " GL_P23 ", 32, " GL_P01 "\n\t"
         "v_lshrrev_b64 " GL_Q23 ", 32, " GL_Q01 "\n\t"
-        "v_mad_u64_u32 " GL_P23 ", vcc, %2, %5, " GL_P23 "\n\t"
-        "v_mad_u64_u32 " GL_Q23 ", vcc, %6, %9, " GL_Q23 "\n\t"
-        "v_mad_u64_u32 " GL_P23 ", s[80:81], %3, %4, " GL_P23 "\n\t"
-        "v_mad_u64_u32 " GL_Q23 ", s[86:87], %7, %8, " GL_Q23 "\n\t"
+        "v_mad_u64_u32 " GL_P23 ", vcc, %1, %4, " GL_P23 "\n\t"
+        "v_mad_u64_u32 " GL_Q23 ", vcc, %5, %8, " GL_Q23 "\n\t"
+        "v_mad_u64_u32 " GL_P23 ", s[80:81], %2, %3, " GL_P23 "\n\t"
+        "v_mad_u64_u32 " GL_Q23 ", s[86:87], %6, %7, " GL_Q23 "\n\t"
         GL_MOV(GL_R4, GL_R3)
         "v_cndmask_b32_e64 " GL_R5 ", 0, 1, s[80:81]\n\t"
         GL_MOV(GL_Q4, GL_Q3)
         "v_cndmask_b32_e64 " GL_Q5 ", 0, 1, s[86:87]\n\t"
-        "v_mad_u64_u32 " GL_P45 ", vcc, %3, %5, " GL_P45 "\n\t"
-        "v_mad_u64_u32 " GL_Q45 ", vcc, %7, %9, " GL_Q45 "\n\t"
+        "v_mad_u64_u32 " GL_P45 ", vcc, %2, %4, " GL_P45 "\n\t"
+        "v_mad_u64_u32 " GL_Q45 ", vcc, %6, %8, " GL_Q45 "\n\t"
         "v_add_co_u32_e32 " GL_R0 ", vcc, " GL_R0 ", " GL_Q0 "\n\t"
         "v_addc_co_u32_e32 " GL_R1 ", vcc, " GL_R2 ", " GL_Q2 ", vcc\n\t"
         "v_addc_co_u32_e32 " GL_R4 ", vcc, " GL_R4 ", " GL_Q4 ", vcc\n\t"
@@ -278,97 +281,94 @@ __device__ __forceinline__ u64 dot2_nc(u64 a, u64 b, u64 c, u64 d) {
         "v_mad_u64_u32 " GL_P01 ", s[80:81], " GL_R4 ", -1, " GL_P01 "\n\t"
         "v_sub_co_u32_e32 " GL_R0 ", vcc, " GL_R0 ", " GL_R5 "\n\t"
         "v_subb_co_u32_e32 " GL_R1 ", vcc, " GL_R1 ", " GL_R6 ", vcc\n\t"
-        "v_cndmask_b32_e64 " GL_R7 ", 0, -1, s[80:81]\n\t"
+        GL_SEL01(GL_R7, "s[80:81]")
         "s_cbranch_vccz .Lgl_redd_%=\n\t"
         "v_cndmask_b32_e64 " GL_R6 ", 0, -1, vcc\n\t"
         "v_sub_co_u32_e32 " GL_R0 ", vcc, " GL_R0 ", " GL_R6 "\n\t"
         "v_subbrev_co_u32_e32 " GL_R1 ", vcc, 0, " GL_R1 ", vcc\n"
         ".Lgl_redd_%=:\n\t"
-        "v_add_co_u32_e32 %0, vcc, " GL_R0 ", " GL_R7 "\n\t"
-        "v_addc_co_u32_e64 %1, vcc, " GL_R1 ", 0, vcc"
-        : "=&v"(r0), "=&v"(r1)
+        GL_ADD_EPS_IF("%0", GL_R7, GL_P01)
+        : "=v"(r)
         : "v"((u32)a), "v"((u32)(a >> 32)), "v"((u32)b), "v"((u32)(b >> 32)), "v"((u32)c), "v"((u32)(c >> 32)), "v"((u32)d),
           "v"((u32)(d >> 32))
         : GL_R0, GL_R1, GL_R2, GL_R3, GL_R4, GL_R5, GL_R6, GL_R7, GL_Q0, GL_Q1, GL_Q2, GL_Q3, GL_Q4, GL_Q5, "vcc", "scc",
           "s80", "s81", "s86", "s87");
-    return ((u64)r1 << 32) | r0;
+    return r;
 }
-// a * b + c with one reduction (the product plus a 64-bit addend stays below 2^128).  Any residues in, a residue out; 12 half-rate + 3 full-rate VALU.
+// a * b + c with one reduction (the product plus a 64-bit addend stays below 2^128).  Any residues in, a residue out; 11 half-rate + 3 full-rate VALU.
 __device__ __forceinline__ u64 mad_nc(u64 a, u64 b, u64 c) {
-    u32 r0, r1;
+    u64 r;
     // c is the 64-bit addend of the first multiply-add (T = a0 b0 + c, carry kc), and the chain of mul_nc goes on from T: kc weighs 2^64,
     // which is the high word of E = {T.hi, kc} -- a v_cndmask in the place of mul_nc's zero.  a0 b1 + E cannot overflow:
     // E = floor(T / 2^32) <= floor(((2^32 - 1)^2 + 2^64 - 1) / 2^32) = 2^33 - 2, and (2^32 - 1)^2 + 2^33 - 2 = 2^64 - 1;  a1 b1 + F cannot
     // either: it is the top half of a b + c < 2^128.  6 half-rate + 3 full-rate for the assembly where adding kc behind the partial
     // products took 10 half-rate (round 5).
-    asm("v_mad_u64_u32 " GL_P01 ", s[82:83], %2, %4, %6\n\t"                 // T = a0 b0 + c, carry kc
+    asm("v_mad_u64_u32 " GL_P01 ", s[82:83], %1, %3, %5\n\t"                 // T = a0 b0 + c, carry kc
         GL_MOV(GL_R2, GL_R1)                                                  // E = {T.hi, kc}
         "v_cndmask_b32_e64 " GL_R3 ", 0, 1, s[82:83]\n\t"
-        "v_mad_u64_u32 " GL_P23 ", vcc, %2, %5, " GL_P23 "\n\t"              // M = a0 b1 + E
-        "v_mad_u64_u32 " GL_P23 ", s[80:81], %3, %4, " GL_P23 "\n\t"         // M = a1 b0 + M, carry c
+        "v_mad_u64_u32 " GL_P23 ", vcc, %1, %4, " GL_P23 "\n\t"              // M = a0 b1 + E
+        "v_mad_u64_u32 " GL_P23 ", s[80:81], %2, %3, " GL_P23 "\n\t"         // M = a1 b0 + M, carry c
         GL_MOV(GL_R4, GL_R3)                                                  // F = {M.hi, c}
         "v_cndmask_b32_e64 " GL_R5 ", 0, 1, s[80:81]\n\t"
-        "v_mad_u64_u32 " GL_P45 ", vcc, %3, %5, " GL_P45 "\n\t"              // H = a1 b1 + F
+        "v_mad_u64_u32 " GL_P45 ", vcc, %2, %4, " GL_P45 "\n\t"              // H = a1 b1 + F
         GL_MOV(GL_R1, GL_R2)                                                  // low 64 bits = {T.lo, M.lo}
         GL_REDUCE_TAIL("%=")
-        : "=&v"(r0), "=&v"(r1)
+        : "=v"(r)
         : "v"((u32)a), "v"((u32)(a >> 32)), "v"((u32)b), "v"((u32)(b >> 32)), "v"(c)
         : GL_R0, GL_R1, GL_R2, GL_R3, GL_R4, GL_R5, GL_R6, GL_R7, "vcc", "scc", "s80", "s81", "s82", "s83");
-    return ((u64)r1 << 32) | r0;
+    return r;
 }
-// lo + hi_lo 2^64 + hi_hi 2^96 (mod p) -> a u64 residue: the reduction tail of mul_nc on its own (6 VALU), for values that are
+// lo + hi_lo 2^64 + hi_hi 2^96 (mod p) -> a u64 residue: the reduction tail of mul_nc on its own (5 VALU), for values that are
 // 128 bits wide by construction (a field element times a power of two: the shifts inside the radix-16 NTT butterflies)
 __device__ __forceinline__ u64 reduce128_asm(u64 lo, u32 hi_lo, u32 hi_hi) {
-    u32 r0, r1;
-    asm("v_mad_u64_u32 " GL_P01 ", s[80:81], %3, -1, %2\n\t"
-        "v_sub_co_u32_e32 " GL_R0 ", vcc, " GL_R0 ", %4\n\t"
+    u64 r;
+    asm("v_mad_u64_u32 " GL_P01 ", s[80:81], %2, -1, %1\n\t"
+        "v_sub_co_u32_e32 " GL_R0 ", vcc, " GL_R0 ", %3\n\t"
         "v_subbrev_co_u32_e32 " GL_R1 ", vcc, 0, " GL_R1 ", vcc\n\t"
-        "v_cndmask_b32_e64 " GL_R7 ", 0, -1, s[80:81]\n\t"
+        GL_SEL01(GL_R7, "s[80:81]")
         "s_cbranch_vccz .Lgl_red128_%=\n\t"
         "v_cndmask_b32_e64 " GL_R6 ", 0, -1, vcc\n\t"
         "v_sub_co_u32_e32 " GL_R0 ", vcc, " GL_R0 ", " GL_R6 "\n\t"
         "v_subbrev_co_u32_e32 " GL_R1 ", vcc, 0, " GL_R1 ", vcc\n"
         ".Lgl_red128_%=:\n\t"
-        "v_add_co_u32_e32 %0, vcc, " GL_R0 ", " GL_R7 "\n\t"
-        "v_addc_co_u32_e64 %1, vcc, " GL_R1 ", 0, vcc"
-        : "=&v"(r0), "=&v"(r1)
+        GL_ADD_EPS_IF("%0", GL_R7, GL_P01)
+        : "=v"(r)
         : "v"(lo), "v"(hi_lo), "v"(hi_hi)
         : GL_R0, GL_R1, GL_R6, GL_R7, "vcc", "scc", "s80", "s81");
-    return ((u64)r1 << 32) | r0;
+    return r;
 }
 // lo + hi 2^64 (mod p) for hi < 2^32: u = hi (2^32 - 1) + lo as one v_mad_u64_u32, its carry-out selects the single +(2^32 - 1) correction
-// (the wrapped sum is below hi 2^32, so the corrected sum cannot wrap again).  4 VALU.
+// (the wrapped sum is below hi 2^32, so the corrected sum cannot wrap again).  3 VALU.
 __device__ __forceinline__ u64 reduce96_asm(u64 lo, u32 hi) {
-    u32 r0, r1;
-    asm("v_mad_u64_u32 " GL_P01 ", vcc, %3, -1, %2\n\t"
-        "v_cndmask_b32_e64 " GL_R6 ", 0, -1, vcc\n\t"
-        "v_add_co_u32_e32 %0, vcc, " GL_R0 ", " GL_R6 "\n\t"
-        "v_addc_co_u32_e64 %1, vcc, " GL_R1 ", 0, vcc"
-        : "=&v"(r0), "=&v"(r1)
+    u64 r;
+    asm("v_mad_u64_u32 " GL_P01 ", vcc, %2, -1, %1\n\t"
+        GL_SEL01(GL_R6, "vcc")
+        GL_ADD_EPS_IF("%0", GL_R6, GL_P01)
+        : "=v"(r)
         : "v"(lo), "v"(hi)
         : GL_R0, GL_R1, GL_R6, "vcc");
-    return ((u64)r1 << 32) | r0;
+    return r;
 }
 // a + b and a - b for ANY u64 residues, a u64 residue out, always correct: the carry (borrow) of the 64-bit operation selects the correction
 // +-(2^32 - 1); the corrected value can wrap a second time only when both operands sit in the top 2^32 of the u64 range (for random data
-// once in 2^32 operations), and that case is a wave-level branch to a second correction that is practically never taken.  5 VALU each where
+// once in 2^32 operations), and that case is a wave-level branch to a second correction that is practically never taken.  4 VALU (add_a: its corrections are
+// multiply-adds, see GL_SEL01; a subtraction's correction -(2^32 - 1) is no product of a 0 / 1 word and an inline constant) and 5 (sub_a) where
 // the canonical forms cost 6 / 5 and need canonical operands -- which costs every product and shift feeding them a 4-instruction canon.
 __device__ __forceinline__ u64 add_a(u64 a, u64 b) {
-    u32 r0, r1, t;
-    asm("v_add_co_u32_e32 %0, vcc, %3, %5\n\t"
-        "v_addc_co_u32_e32 %1, vcc, %4, %6, vcc\n\t"
-        "v_cndmask_b32_e64 %2, 0, -1, vcc\n\t"
-        "v_add_co_u32_e32 %0, vcc, %0, %2\n\t"
-        "v_addc_co_u32_e64 %1, vcc, 0, %1, vcc\n\t"
+    // the sum is formed in the scratch pair so that both corrections can be multiply-adds into the aligned pair of the result (round 8: 4 VALU)
+    u64 r;
+    asm("v_add_co_u32_e32 " GL_R0 ", vcc, %1, %3\n\t"
+        "v_addc_co_u32_e32 " GL_R1 ", vcc, %2, %4, vcc\n\t"
+        GL_SEL01(GL_R6, "vcc")
+        GL_ADD_EPS_IF("%0", GL_R6, GL_P01) "\n\t"
         "s_cbranch_vccz .Lgl_add_a_%=\n\t"
-        "v_cndmask_b32_e64 %2, 0, -1, vcc\n\t"
-        "v_add_co_u32_e32 %0, vcc, %0, %2\n\t"
-        "v_addc_co_u32_e64 %1, vcc, 0, %1, vcc\n"
+        GL_SEL01(GL_R6, "vcc")
+        GL_ADD_EPS_IF("%0", GL_R6, "%0") "\n"
         ".Lgl_add_a_%=:"
-        : "=&v"(r0), "=&v"(r1), "=&v"(t)
+        : "=v"(r)
         : "v"((u32)a), "v"((u32)(a >> 32)), "v"((u32)b), "v"((u32)(b >> 32))
-        : "vcc");
-    return ((u64)r1 << 32) | r0;
+        : GL_R0, GL_R1, GL_R6, "vcc");
+    return r;
 }
 __device__ __forceinline__ u64 sub_a(u64 a, u64 b) {
     u32 r0, r1, t;
