@@ -820,7 +820,7 @@ int vpbs_verify_pbs(const vpbs_verify_pbs_inputs* in, const uint8_t* proof_bytes
 int vpbs_verify_pbs_prefix(const vpbs_verify_pbs_inputs* in, const uint8_t* bytes, size_t len, unsigned* steps_done, char* why, size_t why_len);
 
 /* ---- batch verifier of whole vPBS proofs on the device (csrc/verify_pbs_batch.hip) ----
- * vpbs_verify_pbs for many last proofs of IVC chains made under ONE key set.  For proof i = bytes[offsets[i] .. offsets[i + 1]) with
+ * vpbs_verify_pbs for many last proofs of IVC chains made under ONE key set (many key sets: vpbs_ring_verifier, below).  For proof i = bytes[offsets[i] .. offsets[i + 1]) with
  * ct[i], out_ct[i] and testv (shared, or testv[i] with testv_per_proof != 0), verdicts[i] equals vpbs_verify_pbs's verdict on the same
  * inputs and the keys whose hash the object holds; reasons[i] (may be NULL) is its first failing check, in its order; where that is
  * VPBS_PBS_PROOF, proof_reasons[i] (may be NULL) is the batch verifier's vpbs_verify_reason (VPBS_VERIFY_OK otherwise).  Words are
@@ -855,6 +855,37 @@ long vpbs_pbs_verifier_run(vpbs_pbs_verifier* v, const uint8_t* bytes, const siz
                            const uint64_t* out_ct /* [count][K][N] */, uint8_t* verdicts /* [count] */, uint8_t* reasons /* [count] or NULL */,
                            uint8_t* proof_reasons /* [count] or NULL */);
 void vpbs_pbs_verifier_free(vpbs_pbs_verifier* v);
+
+/* ---- verifying mixed batches under many key hashes (csrc/verify_pbs_batch.hip) ----
+ * One verifier for all clients: the object holds a table of max_keys key hashes in device memory (32 bytes per slot) and ONE set of the
+ * batch verifier's buffers.  Proof i of a run is checked against the key hash of slot key_of[i] and the test vector testvs[testv_of[i]]:
+ * it gets exactly the verdict, reason and proof reason that a vpbs_pbs_verifier made from that slot's key hash gives it on the same
+ * inputs -- vpbs_verify_pbs's verdict under that client's keys.  The statement stage is the one vpbs_pbs_verifier runs; digest and cap
+ * are shared by all slots.
+ *   create:  shape as for vpbs_pbs_verifier_create; max_keys 1 .. 65535; no slot is filled.
+ *   set_key: fills or replaces slot `slot` (the caller chooses it, so the slots can be those of a vpbs_ring_prover:
+ *            vpbs_ring_prover_key_hash); the 32 bytes go to the table on the context's stream.  VPBS_ERR_INVALID for a null argument or a
+ *            slot at or above max_keys.
+ *   clear_key: empties a slot; VPBS_ERR_INVALID for a slot that is empty or out of range.  count: the number of filled slots.
+ *   run:     key_of [count], a HOST array; testvs [n_testv][N], n_testv <= max_batch; testv_of [count] (host) or NULL -- NULL stands for i
+ *            when n_testv == count, for 0 when n_testv == 1, and is refused otherwise.  Refused before anything is queued, with
+ *            VPBS_ERR_INVALID, a message in err that names the proof and the slot or index, and no output byte written: a key_of entry
+ *            at or above max_keys or naming an empty slot, a testv_of entry at or above n_testv, count or n_testv above max_batch, null
+ *            pointers.  count == 0 returns 0.  Otherwise as vpbs_pbs_verifier_run: returns the number of accepted proofs when the
+ *            verdicts are in host memory; reasons and proof_reasons may be NULL.
+ * set_key, clear_key and run of one object exclude each other (the object's mutex). */
+typedef struct vpbs_ring_verifier vpbs_ring_verifier;
+int vpbs_ring_verifier_create(vpbs_ctx* ctx, const vpbs_verify_pbs_inputs* shape, unsigned max_keys, size_t max_batch, vpbs_ring_verifier** out,
+                              char* err, size_t err_len);
+int vpbs_ring_verifier_set_key(vpbs_ring_verifier* v, unsigned slot, const uint64_t key_hash[4]);
+int vpbs_ring_verifier_clear_key(vpbs_ring_verifier* v, unsigned slot);
+long vpbs_ring_verifier_count(vpbs_ring_verifier* v);
+long vpbs_ring_verifier_run(vpbs_ring_verifier* v, const uint8_t* bytes, const size_t* offsets /* [count + 1] */, size_t count,
+                            const uint32_t* key_of /* [count], HOST array */, const uint64_t* testvs /* [n_testv][N] */, size_t n_testv,
+                            const uint32_t* testv_of /* [count] or NULL */, const uint64_t* ct /* [count][n_lwe + 1] */,
+                            const uint64_t* out_ct /* [count][K][N] */, uint8_t* verdicts /* [count] */, uint8_t* reasons /* [count] or NULL */,
+                            uint8_t* proof_reasons /* [count] or NULL */, char* err, size_t err_len);
+void vpbs_ring_verifier_free(vpbs_ring_verifier* v);
 
 /* ---- kernel-level entry points (host buffers; used by parity tests and by callers outside the prover) ---- */
 int vpbs_k_poseidon_batch(vpbs_ctx* ctx, uint64_t* states /* [n][12] in place */, size_t n);
@@ -1175,15 +1206,29 @@ void vpbs_ring_prover_free(vpbs_ring_prover* p);
  *           gate g of inputs[b] on a vpbs_pbs_prover of the key set in slot key_of[b].  wires_out and out_cts (either may be NULL) carry the
  *           leading instance axis, as in run_batch.  Host pointers.  The refusals are run_batch's (the message in err, prefixed), plus a
  *           null ring prover, no proof_fn and steps > n_lwe + 2; nothing is queued and proof_fn is not called.  The call holds the ring
- *           prover's mutex from the evaluation to the last proof.  Verification stays per client: vpbs_program_verify with a verifier
- *           made from vpbs_ring_prover_key_hash(slot).  Returns the number of proofs delivered or a negative status.
+ *           prover's mutex from the evaluation to the last proof.  Verification: vpbs_program_verify_batch for all instances at once, or
+ *           per client vpbs_program_verify with a verifier made from vpbs_ring_prover_key_hash(slot).  Returns the number of proofs
+ *           delivered or a negative status.
  *   verify: takes the CLAIMED output GLWEs of all gates (out_cts [n_gates][K][N]) and the proofs (bytes, offsets [n_gates + 1], gate order).
  *           The wire table is rebuilt as inputs followed by the extraction (partial_sample_extract) of every claimed output, the inputs of
  *           ALL gates are combined in one launch -- verification has no level order -- and vpbs_pbs_verifier_run checks the proofs, in
  *           chunks of its max_batch, against the recomputed c_g, testvs[gate_lut[g]] and out_cts[g]: gate g gets exactly the verdict and
  *           reasons that call gives proof g on those inputs.  Returns the number of accepted gates; the program is proven iff that is
  *           n_gates.  Consequence: a forged out_cts[g] fails gate g on the output check (VPBS_PBS_OUT_CT) and every consumer of wire
- *           n_inputs + g on its LWE hash check (VPBS_PBS_LWE_HASH), since the consumer's proof was made for another input.  Host pointers. */
+ *           n_inputs + g on its LWE hash check (VPBS_PBS_LWE_HASH), since the consumer's proof was made for another input.  Host pointers.
+ *   verify_batch: verify for `instances` input sets at once on a vpbs_ring_verifier, instance b under the key hash of slot key_of[b]: inputs
+ *           [instances][n_inputs][n_lwe + 1], key_of [instances] (HOST), testvs [n_luts][N], out_cts [instances][n_gates][K][N], proofs with
+ *           offsets [instances * n_gates + 1] and verdicts / reasons / proof_reasons [instances * n_gates], all in row order
+ *           b * n_gates + g.  Row (b, g) gets exactly what vpbs_program_verify gives gate g of instance b with a vpbs_pbs_verifier made
+ *           from the key hash of slot key_of[b].  The claimed outputs of ALL instances are extracted in one launch and the inputs of all
+ *           gates of all instances combined in one launch (the arithmetic of run: canonical on read, the constant in the body only); the
+ *           rows go to the verifier's stages where they lie, in chunks of the ring verifier's max_batch that may straddle instances, the
+ *           test vector of a row taken from testvs through an index, the key hash through key_of: no gate input is downloaded, no test
+ *           vector copied per gate, and the host waits once per chunk, for the result bytes.  Returns the number of accepted rows.
+ *           VPBS_ERR_INVALID with a message in err, nothing queued and no output byte written, for: a null or host-only program, a null
+ *           ring verifier, another device, null pointers with something to read, more than 2^31 - 1 rows (instances x wires), a shape
+ *           without sample extraction, a key_of[b] at or above max_keys or naming an empty slot (the instance and the slot are named).
+ *           The call holds the ring verifier's mutex from its checks to its last wait.  Host pointers. */
 typedef struct {
     unsigned n_inputs, n_gates, n_luts;
     size_t n_terms;
@@ -1212,6 +1257,12 @@ long vpbs_program_prove_batch(vpbs_program* prog, vpbs_ring_prover* ring_prover,
 long vpbs_program_verify(vpbs_program* prog, vpbs_pbs_verifier* pbs_verifier, const uint64_t* inputs, const uint64_t* testvs,
                          const uint64_t* out_cts, const uint8_t* proofs, const size_t* offsets /* [n_gates + 1] */, uint8_t* verdicts /* [n_gates] */,
                          uint8_t* reasons /* [n_gates] or NULL */, uint8_t* proof_reasons /* [n_gates] or NULL */);
+long vpbs_program_verify_batch(vpbs_program* prog, vpbs_ring_verifier* ring_verifier, const uint64_t* inputs /* [instances][n_inputs][n_lwe + 1] */,
+                               size_t instances, const uint32_t* key_of /* [instances], HOST array */, const uint64_t* testvs /* [n_luts][N] */,
+                               const uint64_t* out_cts /* [instances][n_gates][K][N] */, const uint8_t* proofs,
+                               const size_t* offsets /* [instances * n_gates + 1] */, uint8_t* verdicts /* [instances * n_gates] */,
+                               uint8_t* reasons /* [instances * n_gates] or NULL */, uint8_t* proof_reasons /* [instances * n_gates] or NULL */,
+                               char* err, size_t err_len);
 void vpbs_program_free(vpbs_program* prog);
 
 /* ---- memory helpers for hosts that do not link the HIP runtime themselves (a Rust or plain C++ caller) ----

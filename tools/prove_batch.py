@@ -14,12 +14,12 @@ usage: tools/prove_batch.py [--count M] [--chains C] [--witness-batch B] [--step
   --baseline: the same batch the way it was done before PbsProver existed, using only api of that time -- C threads, each with its own
     Context + Ivc.set_device_witness(ELL, LOGB, B) + Ivc.prove_pbs on host keys, outputs from each chain's proof -- so that this file can be
     copied into a build of an older commit and run there.
-  --keys M: the batch spread over M seeded key sets (ciphertext i under key set i mod M) on ONE api.RingProver: every proof is verified by
-    an api.PbsVerifier made from the key hash of its own slot, every output decrypted under its own key.  --keys M --baseline: the same
-    with M api.PbsProver objects, one after the other, each proving the ciphertexts of its key set (it needs nothing newer than
-    api.PbsProver, so this file can be copied into a build of an older commit).  Both print one JSON line with the wall time (seconds),
-    proofs, device_bytes_held_by_the_provers (hipMemGetInfo before the first create and after the last), seconds_until_out_ct_complete and
-    prepare_chain_ms."""
+  --keys M: the batch spread over M seeded key sets (ciphertext i under key set i mod M) on ONE api.RingProver: all proofs are verified in
+    one run of ONE api.RingVerifier whose slot k holds RingProver.key_hash(k), every output decrypted under its own key.  --keys M
+    --baseline: the same with M api.PbsProver objects, one after the other, each proving the ciphertexts of its key set, and M
+    api.PbsVerifier objects (it needs nothing newer than api.PbsProver, so this file can be copied into a build of an older commit).
+    Both print one JSON line with the wall time (seconds), proofs, device_bytes_held_by_the_provers (hipMemGetInfo before the first
+    create and after the last), seconds_until_out_ct_complete and prepare_chain_ms."""
 import argparse
 import json
 import os
@@ -190,7 +190,15 @@ def main_keys(args, N, n_lwe, log_n):
     whole = args.steps in (0, total)
     ncols, cap = [cyc.n_constants + 80, 135, 20, 16], vk[4:].reshape(-1, 4)
     accepted, why = 0, set()
-    for k in range(M):
+    if whole and not args.baseline:   # ONE RingVerifier for all key sets: slot k holds the key hash of the prover's slot k
+        rv = api.RingVerifier(ctx, cap, ncols, vk[:4], log_n, cyc.n_constants, 80, cyc.gates, N, K, n_lwe, K * ELL * K * N, max_keys=M, max_batch=count)
+        for k in range(M):
+            rv.set_key(k, hashes[k])
+        verdicts, reasons, _ = rv.verify(proofs, key_of, testv, cts, out_ct)
+        rv.close()
+        accepted = int(verdicts.sum())
+        why = {api.pbs_reason_text(int(r)) for v, r in zip(verdicts, reasons) if not v}
+    for k in range(M if args.baseline or not whole else 0):
         if not mine[k]:
             continue
         sel = [proofs[i] for i in mine[k]]

@@ -5,7 +5,7 @@ user had to before api.Program existed (the baseline leg: Bootstrapper.run per l
 compared wire by wire.  One JSON line.
 
 usage: tools/run_program.py [--levels L] [--width W] [--fan-in F] [--program FILE.json] [--n8] [--prove] [--baseline] [--runs R] [--seed S]
-                            [--instances B --keys M]
+                            [--instances B --keys M [--verify-per-instance]]
   netlist: W inputs, L layers of W gates; a gate reads F wires of the layer before it with coefficients in {1, p - 1}; gate 0 of every layer
     is the identity of gate 0 of the layer before it (fan-in 1, coefficient 1), so that one output has a known message whatever F is.
   --program: {"n_inputs", "n_luts", "gates": [{"terms": [[src, coef], ..], "const", "lut"}, ..]} instead; lut 0 is the test vector of the
@@ -22,8 +22,10 @@ usage: tools/run_program.py [--levels L] [--width W] [--fan-in F] [--program FIL
     under its own key, and those with a known message are checked.  Prints wall seconds, the HIP-event time of the bootstrap launches and
     the launches queued per leg, and the bytes of the combine and delivery kernels computed from the shapes.
     With --prove the batched leg is followed by ONE api.Program.prove_batch on an api.RingProver that holds the M key sets (host copies
-    from the same seeds): its wires must be the batched leg's, every instance is verified by api.Program.verify on an api.PbsVerifier made
-    from the ring prover's key_hash of that instance's slot, and the decrypted outputs are the proven ones.
+    from the same seeds): its wires must be the batched leg's, ALL instances are verified by one api.Program.verify_batch on an
+    api.RingVerifier whose slot k holds the ring prover's key_hash(k) (verify_seconds), and the decrypted outputs are the proven ones.
+    --verify-per-instance: the proofs are checked a second time by api.Program.verify per instance on the api.PbsVerifier of its key set
+    (verify_per_instance_seconds, verify_per_instance_equal).
   Time: wall seconds per run of a leg (after one warm-up run), per level = / levels; HIP-event milliseconds of the bootstrap launches per
   level (the library's own timers).  Bytes: what each leg moves between host and device per run, computed from the shapes."""
 import argparse
@@ -132,7 +134,8 @@ def run_baseline(ctx, bs, n_inputs, gates, lv, inputs, testvs):
 
 
 def prove_batch(args, ctx, prog, N, n_lwe, log_n, M, inputs, key_of, testvs, batch_wires, out):
-    """--instances B --keys M --prove: Program.prove_batch on a RingProver, Program.verify per instance -> (the proven wires, all accepted)"""
+    """--instances B --keys M --prove: Program.prove_batch on a RingProver, Program.verify_batch on a RingVerifier -> (the proven wires, all
+    accepted)"""
     cyc_path, dum_path = circuit_file.find_cyclic_circuit(N, K, ELL, LOGB, n_lwe, log_n)
     cyc, dum = circuit_file.load(cyc_path), circuit_file.load(dum_path)
     chains = args.chains or (2 if args.n8 else 8)
@@ -148,17 +151,25 @@ def prove_batch(args, ctx, prog, N, n_lwe, log_n, M, inputs, key_of, testvs, bat
     hashes, (vk, _) = [rp.key_hash(k) for k in range(M)], rp.verifier_data()
     rp.close()
     n_gates = prog.n_gates
-    verified, why = 0, set()
-    t = time.perf_counter()
+    shape = (ctx, vk[4:].reshape(-1, 4), [cyc.n_constants + 80, 135, 20, 16], vk[:4], log_n, cyc.n_constants, 80, cyc.gates, N, K, n_lwe, K * ELL * K * N)
+    # ONE RingVerifier, slot k = the ring prover's slot k; all rows (instance, gate) in chunks of its max_batch
+    rv = api.RingVerifier(*shape, max_keys=M, max_batch=max(1, min(len(key_of) * n_gates, 512)))
     for k in range(M):
-        pv = api.PbsVerifier(ctx, vk[4:].reshape(-1, 4), [cyc.n_constants + 80, 135, 20, 16], vk[:4], log_n, cyc.n_constants, 80, cyc.gates, N, K, n_lwe,
-                             K * ELL * K * N, hashes[k], max_batch=max(1, min(n_gates, 64)))
-        for b in [b for b in range(len(key_of)) if key_of[b] == k]:
-            verdicts, reasons, _ = prog.verify(pv, inputs[b], testvs, out_cts[b], proofs[b])
-            verified += int(verdicts.sum())
-            why |= {api.pbs_reason_text(int(r)) for v, r in zip(verdicts, reasons) if not v}
-        pv.close()
+        rv.set_key(k, hashes[k])
+    t = time.perf_counter()
+    verdicts, reasons, _ = prog.verify_batch(rv, inputs, key_of, testvs, out_cts, proofs)
     out["verify_seconds"] = time.perf_counter() - t
+    rv.close()
+    verified = int(verdicts.sum())
+    why = {api.pbs_reason_text(int(r)) for v, r in zip(verdicts.reshape(-1), reasons.reshape(-1)) if not v}
+    if args.verify_per_instance:   # the form before verify_batch: Program.verify per instance on the PbsVerifier of its key set
+        pvs = [api.PbsVerifier(*shape, hashes[k], max_batch=max(1, min(n_gates, 64))) for k in range(M)]
+        t = time.perf_counter()
+        each = [prog.verify(pvs[key_of[b]], inputs[b], testvs, out_cts[b], proofs[b]) for b in range(len(key_of))]
+        out["verify_per_instance_seconds"] = time.perf_counter() - t
+        for pv in pvs:
+            pv.close()
+        out["verify_per_instance_equal"] = bool(all((e[0] == verdicts[b]).all() and (e[1] == reasons[b]).all() for b, e in enumerate(each)))
     out["verified"], out["rejected_because"] = verified, sorted(why)
     out["proven"] = verified == len(key_of) * n_gates
     out["proven_wires_equal"] = bool((wires == batch_wires).all())
@@ -281,6 +292,7 @@ def main():
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--instances", type=int)
     ap.add_argument("--keys", type=int, default=1)
+    ap.add_argument("--verify-per-instance", action="store_true")
     args = ap.parse_args()
     if args.baseline and args.prove:
         raise SystemExit("--baseline evaluates only: it cannot run with --prove")

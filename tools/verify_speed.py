@@ -3,7 +3,13 @@
 host verifier on 16 threads over the same B serialised proofs, five alternating repetitions each: the 2^15 synthetic proof (fri_only:
 its wires satisfy no gate), or with --paper proofs of the exported step circuit at N = 1024 under the full check.
 --pbs --batch B[,B2,..]: whole vPBS proofs at N = 1024, n = 728 (two chains proven, replicated to B) through api.PbsVerifier against 16
-host threads that parse, verify the proof, check the statement and hash the LWE chain (key hash precomputed); one JSON line per B"""
+host threads that parse, verify the proof, check the statement and hash the LWE chain (key hash precomputed); one JSON line per B
+--pbs --keys M --batch B[,B2,..]: the same B proofs as a MIXED batch of M clients (proof i under slot i mod M), three legs: ONE
+api.RingVerifier run of B proofs; M api.PbsVerifier objects of B / M proofs each, one after the other; 16 host threads.  Each device leg runs
+five times in turn with the host leg, while only its own verifier objects exist.  All M
+slots hold the SAME key hash (one key set is generated): fine for timing, because no stage of the verifier exits early and the table is
+read by index either way -- the output says so.  --baseline: without the RingVerifier leg; the rest needs nothing newer than
+api.PbsVerifier, so this file can be copied into a build of an older commit and time that."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch, vpbs_amd
@@ -13,6 +19,7 @@ args = sys.argv[1:]
 device_mode = "--device" in args
 batches = [int(b) for b in args[args.index("--batch") + 1].split(",")] if "--batch" in args else [1]   # --pbs: several, one line each
 batch = batches[0]
+keys_m = int(args[args.index("--keys") + 1]) if "--keys" in args else 0
 log_n = 15
 ctx = vpbs_amd.Context(0, log_n_max=16)
 gates = api.GateSet(bench.GATES)
@@ -142,7 +149,72 @@ if "--pbs" in args:
     key_hash = api.pbs_key_hash(keys["bsk"], keys["ksk"])
     key_hash_ms = 1e3 * (time.perf_counter() - t)
     kn, n_pi = K * N, 2 * K * N + 13 + 64
-    for batch in batches:
+
+    def host_check(pick, k):
+        blob, ct, out_ct = pick[k]
+        p, pi = api.step_proof_from_bytes(blob, pncols, plog_n, cyc.n_constants, max_public_inputs=n_pi)
+        if pi.size != n_pi or pi[:kn - N].any() or not (pi[kn - N:kn] == testv).all() or int(pi[kn]) != n_lwe + 2 or \
+                not (pi[kn + 1:2 * kn + 1] == out_ct).all():
+            return False
+        if not api.verify_step(p, pcap, pncols, pdigest, pi, plog_n, n_constants=cyc.n_constants, n_routed=80, gates=cyc.gates):
+            return False
+        if not (pi[-68:] == vk).all() or not (pi[2 * kn + 1:2 * kn + 5] == key_hash).all():
+            return False
+        lwe_items = np.concatenate([ct[n_lwe:], ct[:n_lwe], np.zeros(1, np.uint64)]).reshape(-1, 1)
+        return api.hash_chain(lwe_items, pi[2 * kn + 5:2 * kn + 9])[1]
+
+    for batch in batches if keys_m else []:
+        # the mixed batch of M clients: see the module text
+        M, ring_leg = keys_m, "--baseline" not in args
+        assert batch % M == 0, "--batch must be a multiple of --keys"
+        shape = (ctx, pcap, pncols, pdigest, plog_n, cyc.n_constants, 80, cyc.gates, N, K, n_lwe, K * ELL * K * N)
+        pick = [made[k % chains] for k in range(batch)]
+        blobs, cts, outs = [p[0] for p in pick], np.stack([p[1] for p in pick]), np.stack([p[2] for p in pick])
+        key_of = np.arange(batch) % M
+        mine = [np.flatnonzero(key_of == k) for k in range(M)]
+        packed = [([blobs[i] for i in mine[k]], cts[mine[k]], outs[mine[k]]) for k in range(M)]
+        ring_ms, per_key_ms, host_ms = [], [], []
+        with ThreadPoolExecutor(max_workers=16) as pool:
+            def host_leg():
+                t = time.perf_counter()
+                okh = list(pool.map(lambda k: host_check(pick, k), range(batch)))
+                host_ms.append((time.perf_counter() - t) * 1e3)
+                assert all(okh)
+            # each device leg in turn with the host leg, and with its own objects alone: every verifier brings a stream of its own for the
+            # LWE chain, and M + 1 of them in one process share the few hardware queues, which is not what a server with ONE verifier sees
+            if ring_leg:
+                rv = api.RingVerifier(*shape, max_keys=M, max_batch=batch)
+                for k in range(M):
+                    rv.set_key(k, key_hash)
+                rv.verify(blobs, key_of, testv, cts, outs)   # warm-up: first launches, pinned staging
+                for _ in range(5):
+                    t = time.perf_counter()
+                    v, r, _ = rv.verify(blobs, key_of, testv, cts, outs)
+                    ring_ms.append((time.perf_counter() - t) * 1e3)
+                    assert v.all(), r
+                    host_leg()
+                rv.close()
+            pvs = [api.PbsVerifier(*shape, key_hash, max_batch=batch // M) for _ in range(M)]
+            per_key = lambda: [pvs[k].verify(b, testv, c, o)[0] for k, (b, c, o) in enumerate(packed)]
+            per_key()
+            for _ in range(5):
+                t = time.perf_counter()
+                vs = per_key()
+                per_key_ms.append((time.perf_counter() - t) * 1e3)
+                assert all(v.all() for v in vs)
+                host_leg()
+            for pv in pvs:
+                pv.close()
+        med = lambda x: sorted(x)[len(x) // 2] if x else None
+        print(json.dumps({"what": "whole vPBS proofs at N = 1024, n = 728 (%d chains proven, replicated) as a mixed batch of %d clients, proof i under "
+                                  "slot i mod %d: one vpbs_ring_verifier_run, %d vpbs_pbs_verifier_run of %d proofs one after the other, 16 host "
+                                  "threads.  All slots hold the same key hash: no stage exits early, so the timing is that of distinct ones"
+                                  % (chains, M, M, M, batch // M),
+                          "batch": batch, "keys": M, "bytes_per_proof": len(blobs[0]), "ring_ms_per_run_wall": med(ring_ms),
+                          "per_key_verifiers_ms_per_run_wall": med(per_key_ms), "host_16_threads_ms": med(host_ms), "ring_runs_ms": ring_ms,
+                          "per_key_verifiers_runs_ms": per_key_ms, "host_runs_ms": host_ms, "proving_s": prove_s}))
+
+    for batch in [] if keys_m else batches:
         pv = api.PbsVerifier(ctx, pcap, pncols, pdigest, plog_n, cyc.n_constants, 80, cyc.gates, N, K, n_lwe, K * ELL * K * N, key_hash,
                              max_batch=batch)
         pick = [made[k % chains] for k in range(batch)]

@@ -308,6 +308,13 @@ SIGNATURES = {
     "vpbs_pbs_verifier_run": (C.c_long, [_vp, C.POINTER(C.c_uint8), C.POINTER(_sz), _sz, U64P, _i, U64P, U64P, C.POINTER(C.c_uint8),
                                          C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]),
     "vpbs_pbs_verifier_free": (None, [_vp]),
+    "vpbs_ring_verifier_create": (_i, [_vp, C.POINTER(VerifyPbsInputsC), _ui, _sz, C.POINTER(_vp), C.c_char_p, _sz]),
+    "vpbs_ring_verifier_set_key": (_i, [_vp, _ui, U64P]),
+    "vpbs_ring_verifier_clear_key": (_i, [_vp, _ui]),
+    "vpbs_ring_verifier_count": (C.c_long, [_vp]),
+    "vpbs_ring_verifier_run": (C.c_long, [_vp, C.POINTER(C.c_uint8), C.POINTER(_sz), _sz, _vp, U64P, _sz, _vp, U64P, U64P, C.POINTER(C.c_uint8),
+                                          C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.c_char_p, _sz]),
+    "vpbs_ring_verifier_free": (None, [_vp]),
     "vpbs_blind_rotate_step": (_i, [_vp, C.POINTER(TfheParamsC), _ui, _vp, _vp, _vp, _i, _i, _i, _vp, _i]),
     "vpbs_pbs_accumulator_chain": (_i, [_vp, C.POINTER(TfheParamsC), _ui, U64P, U64P, U64P, U64P, U64P]),
     "vpbs_host_alloc": (_vp, [_sz]),
@@ -364,6 +371,8 @@ SIGNATURES = {
     "vpbs_program_prove_batch": (C.c_long, [_vp, _vp, U64P, _sz, _vp, U64P, _ui, U64P, U64P, PBS_PROOF_FN, _vp, C.c_char_p, _sz]),
     "vpbs_program_verify": (C.c_long, [_vp, _vp, U64P, U64P, U64P, C.POINTER(C.c_uint8), C.POINTER(_sz), C.POINTER(C.c_uint8),
                                        C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]),
+    "vpbs_program_verify_batch": (C.c_long, [_vp, _vp, U64P, _sz, _vp, U64P, U64P, C.POINTER(C.c_uint8), C.POINTER(_sz), C.POINTER(C.c_uint8),
+                                             C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.c_char_p, _sz]),
     "vpbs_program_free": (None, [_vp]),
     "vpbs_lwe_extract": (_i, [_vp, _ui, _ui, _ui, _vp, _sz, _vp, _i]),
     "vpbs_lwe_decrypt": (_i, [U64P, U64P, _ui, U64P]),
@@ -1243,6 +1252,27 @@ def pbs_key_hash(bsk, ksk):
     return out
 
 
+def _verify_pbs_shape(cs_cap, ncols, circuit_digest, log_n, n_constants, n_routed, gates, N, K, n_lwe, ggsw_len, num_challenges, quotient_degree_factor,
+                      rate_bits, cap_height, compat):
+    """the vpbs_verify_pbs_inputs a device verifier is created from (no testv, ct, out_ct or keys) -> (struct, what it points to)"""
+    v = VerifyInputsC()
+    v.log_n, v.rate_bits, v.cap_height = log_n, rate_bits, cap_height
+    v.n_constants_sigmas, v.n_wires, v.n_zs_partial_products, v.n_quotient = ncols
+    v.num_challenges = num_challenges
+    cap = _u64(cs_cap)
+    v.constants_sigmas_cap = _ptr(cap)
+    for i in range(4):
+        v.circuit_digest[i] = int(circuit_digest[i])
+    v.n_constants, v.n_routed, v.quotient_degree_factor = n_constants, n_routed, quotient_degree_factor
+    v.gates, v.n_gates, v.num_selectors = gates.arr, gates.n, gates.num_selectors
+    if compat is not None:
+        v.compat = C.pointer(compat)
+    p = VerifyPbsInputsC()
+    p.circuit = C.pointer(v)
+    p.N, p.K, p.n_lwe, p.ggsw_len = N, K, n_lwe, ggsw_len
+    return p, (v, cap, gates, compat)
+
+
 class PbsVerifier:
     """vpbs_pbs_verifier: vpbs_verify_pbs for a batch of vPBS proofs (the serialised last proofs of IVC chains) on the device, all under the
     key set whose hash is key_hash (pbs_key_hash).  The parameters mirror verify_pbs; every proof brings its own ct and out_ct."""
@@ -1250,22 +1280,8 @@ class PbsVerifier:
     def __init__(self, ctx, cs_cap, ncols, circuit_digest, log_n, n_constants, n_routed, gates, N, K, n_lwe, ggsw_len, key_hash, max_batch=64,
                  num_challenges=2, quotient_degree_factor=8, rate_bits=3, cap_height=4, compat=None):
         self.ctx, self.max_batch, self.N, self.K, self.n_lwe = ctx, max_batch, N, K, n_lwe
-        v = VerifyInputsC()
-        v.log_n, v.rate_bits, v.cap_height = log_n, rate_bits, cap_height
-        v.n_constants_sigmas, v.n_wires, v.n_zs_partial_products, v.n_quotient = ncols
-        v.num_challenges = num_challenges
-        self._cap = _u64(cs_cap)
-        v.constants_sigmas_cap = _ptr(self._cap)
-        for i in range(4):
-            v.circuit_digest[i] = int(circuit_digest[i])
-        v.n_constants, v.n_routed, v.quotient_degree_factor = n_constants, n_routed, quotient_degree_factor
-        v.gates, v.n_gates, v.num_selectors = gates.arr, gates.n, gates.num_selectors
-        if compat is not None:
-            self._compat = compat
-            v.compat = C.pointer(compat)
-        p = VerifyPbsInputsC()
-        p.circuit = C.pointer(v)
-        p.N, p.K, p.n_lwe, p.ggsw_len = N, K, n_lwe, ggsw_len
+        p, self._keep = _verify_pbs_shape(cs_cap, ncols, circuit_digest, log_n, n_constants, n_routed, gates, N, K, n_lwe, ggsw_len, num_challenges,
+                                          quotient_degree_factor, rate_bits, cap_height, compat)
         kh = _u64(key_hash).reshape(-1)
         h, err = C.c_void_p(), C.create_string_buffer(512)
         rc = lib().vpbs_pbs_verifier_create(ctx.h, C.byref(p), _ptr(kh), max_batch, C.byref(h), err, 512)
@@ -2089,6 +2105,121 @@ class RingProver(PbsProver):
     free = close
 
 
+def ring_verify_args(N, K, n_lwe, max_keys, max_batch, count, key_of, testvs, cts, out_cts, testv_of=None):
+    """shapes of a RingVerifier.verify call, checked without a device: key_of [count] slots below max_keys (any integer dtype; the offending
+    index is named), testvs [N] or [n_testv][N], cts [count][n + 1], out_cts [count][K][N] (or [count][K N]), testv_of [count] indices below
+    n_testv -- or None with n_testv == count (proof i takes testvs[i]) or n_testv == 1 -> (key_of as uint32, testvs [n_testv][N], cts,
+    out_cts [count][K N], testv_of as uint32 or None), contiguous"""
+    if count > max_batch:
+        raise ValueError("RingVerifier.verify: %d proofs exceed max_batch %d" % (count, max_batch))
+    tv, c, o = _u64(testvs), _u64(cts), _u64(out_cts)
+    if tv.ndim == 1:
+        tv = tv.reshape(1, -1)
+    if tv.ndim != 2 or tv.shape[1] != N or tv.shape[0] > max_batch:
+        raise ValueError("RingVerifier.verify: expected testvs [%d] or [n_testv][%d] with n_testv <= max_batch %d, got shape %s" % (N, N, max_batch, tv.shape))
+    if c.shape != (count, n_lwe + 1) or o.size != count * K * N or (count and o.shape[0] != count):
+        raise ValueError("RingVerifier.verify: expected cts [%d][%d] and out_cts [%d][%d][%d], got shapes %s and %s" % (count, n_lwe + 1, count, K, N,
+                                                                                                                     c.shape, o.shape))
+    ko = keyring_key_of(key_of, count, max_keys)
+    n_testv = tv.shape[0]
+    if testv_of is None:
+        if n_testv not in (count, 1):
+            raise ValueError("RingVerifier.verify: without testv_of, testvs must be [%d][N] (one per proof) or one shared vector, got %d" % (count, n_testv))
+        to = None
+    else:
+        to = np.asarray(testv_of)
+        if to.shape == (0,):
+            to = to.astype(np.uint32)
+        if to.dtype.kind not in "iu" or to.shape != (count,):
+            raise ValueError("RingVerifier.verify: expected testv_of [%d] of integers, got %s %s" % (count, to.dtype, to.shape))
+        for i, t in enumerate(to.tolist()):
+            if t < 0 or t >= n_testv:
+                raise ValueError("RingVerifier.verify: testv_of[%d] = %d is not below n_testv %d" % (i, t, n_testv))
+        to = np.ascontiguousarray(to, dtype=np.uint32)
+    return ko, tv, c, np.ascontiguousarray(o.reshape(count, K * N)), to
+
+
+class RingVerifier:
+    """vpbs_ring_verifier: ONE device verifier of whole vPBS proofs for the clients of a key ring.  Slot s holds the key hash of a key set
+    (pbs_key_hash, or RingProver.key_hash(s): the caller chooses the slot, so the slots can be the ring prover's); verify() checks proof i
+    against slot key_of[i] and gives it what a PbsVerifier made from that slot's key hash gives.  The parameters mirror PbsVerifier."""
+
+    def __init__(self, ctx, cs_cap, ncols, circuit_digest, log_n, n_constants, n_routed, gates, N, K, n_lwe, ggsw_len, max_keys, max_batch=512,
+                 num_challenges=2, quotient_degree_factor=8, rate_bits=3, cap_height=4, compat=None):
+        self.ctx, self.max_keys, self.max_batch, self.N, self.K, self.n_lwe = ctx, max_keys, max_batch, N, K, n_lwe
+        p, self._keep = _verify_pbs_shape(cs_cap, ncols, circuit_digest, log_n, n_constants, n_routed, gates, N, K, n_lwe, ggsw_len, num_challenges,
+                                          quotient_degree_factor, rate_bits, cap_height, compat)
+        h, err = C.c_void_p(), C.create_string_buffer(512)
+        rc = lib().vpbs_ring_verifier_create(ctx.h, C.byref(p), max_keys, max_batch, C.byref(h), err, 512)
+        if rc:
+            self.h = None
+            raise VpbsError("vpbs_ring_verifier_create: status %d: %s" % (rc, err.value.decode()))
+        self.h = h
+        ctx._batches.add(self)   # must not outlive its context: Context.close() frees the survivors
+
+    def _status(self, what, rc, text=""):
+        e = VpbsError("%s: status %d%s" % (what, rc, ": " + text if text else ""))
+        e.status = rc
+        return e
+
+    def set_key(self, slot, key_hash):
+        """fills or replaces a slot with a key hash [4]"""
+        kh = np.ascontiguousarray(_u64(key_hash).reshape(-1))
+        if kh.size != 4:
+            raise ValueError("RingVerifier.set_key: a key hash is 4 words, got %d" % kh.size)
+        rc = lib().vpbs_ring_verifier_set_key(self.h, int(slot), _ptr(kh))
+        if rc:
+            raise self._status("vpbs_ring_verifier_set_key", rc, "slot %d of %d" % (slot, self.max_keys))
+
+    def clear_key(self, slot):
+        rc = lib().vpbs_ring_verifier_clear_key(self.h, int(slot))
+        if rc:
+            raise self._status("vpbs_ring_verifier_clear_key", rc, "slot %d is empty or out of range" % slot)
+
+    def count(self):
+        return int(lib().vpbs_ring_verifier_count(self.h))
+
+    def verify_packed(self, buf, offsets, key_of, testvs, cts, out_cts, testv_of=None):
+        """buf, offsets: pack_proofs; the rest as verify"""
+        buf = np.ascontiguousarray(buf, dtype=np.uint8)
+        offs = np.ascontiguousarray(offsets, dtype=np.uint64)
+        count = offs.size - 1
+        ko, tv, c, o, to = ring_verify_args(self.N, self.K, self.n_lwe, self.max_keys, self.max_batch, count, key_of, testvs, cts, out_cts, testv_of)
+        verdicts, reasons, sub = (np.zeros(count, np.uint8) for _ in range(3))
+        u8p = C.POINTER(C.c_uint8)
+        data = buf.ctypes.data_as(u8p) if buf.size else (C.c_uint8 * 1)()
+        keep, keep32 = np.zeros(1, np.uint64), np.zeros(1, np.uint32)   # valid pointers for empty arrays
+        ptr = lambda a: _ptr(a) if a.size else _ptr(keep)
+        p32 = lambda a: None if a is None else (a if a.size else keep32).ctypes.data
+        err = C.create_string_buffer(512)
+        rc = lib().vpbs_ring_verifier_run(self.h, data, offs.ctypes.data_as(C.POINTER(C.c_size_t)), count, p32(ko), ptr(tv.reshape(-1)), tv.shape[0],
+                                          p32(to), ptr(c.reshape(-1)), ptr(o.reshape(-1)), verdicts.ctypes.data_as(u8p), reasons.ctypes.data_as(u8p),
+                                          sub.ctypes.data_as(u8p), err, 512)
+        if rc < 0:
+            raise self._status("vpbs_ring_verifier_run", rc, err.value.decode())
+        return verdicts, reasons, sub
+
+    def verify(self, blobs, key_of, testvs, cts, out_cts, testv_of=None):
+        """blobs: list of serialised vPBS proofs; key_of [count] slots; testvs [N] shared, [count][N], or a table [n_testv][N] addressed by
+        testv_of [count]; cts [count][n + 1]; out_cts [count][K][N] -> (verdicts, reasons, proof_reasons), np.uint8 each.  A key_of entry
+        that names an empty slot raises VpbsError (.status = VPBS_ERR_INVALID) before anything runs."""
+        return self.verify_packed(*pack_proofs(blobs), key_of, testvs, cts, out_cts, testv_of)
+
+    def close(self):
+        if self.h:
+            lib().vpbs_ring_verifier_free(self.h)
+            self.h = None
+            self.ctx._batches.discard(self)
+
+    free = close
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Program:
     """vpbs_program: a netlist of bootstraps on resident keys.  Wire w < n_inputs is input w, wire n_inputs + g the output of gate g; gate g
     bootstraps const * (0, .., 0, 1) + sum coef * wire[src] with test vector testvs[lut].  gates: a list of (terms=[(src, coef), ..], const, lut)
@@ -2240,7 +2371,8 @@ class Program:
         slots, testvs [n_luts][N] -> (proofs[b][g]: bytes, wires [instances][n_inputs + n_gates][n + 1], out_cts
         [instances][n_gates][K][N]).  wires and out_cts are run_batch's on the prover's ring; proof (b, g) is byte for byte
         prove(PbsProver of the key set in slot key_of[b], inputs[b], testvs)[0][g].  on_proof((b, g), bytes); failures: PbsProveError with
-        .failures keyed by b * n_gates + g.  A client verifies its instance with verify() and a PbsVerifier made from key_hash(slot)."""
+        .failures keyed by b * n_gates + g.  verify_batch() checks all instances on one RingVerifier filled from key_hash(slot); a client
+        verifies its own instance with verify() and a PbsVerifier made from key_hash(slot)."""
         if self.ctx is None:
             raise VpbsError("Program.prove_batch: a host-only program (made without a context) cannot be evaluated")
         rp = ring_prover
@@ -2298,6 +2430,37 @@ class Program:
                                        verdicts.ctypes.data_as(u8p), reasons.ctypes.data_as(u8p), sub.ctypes.data_as(u8p))
         if rc < 0:
             raise VpbsError("vpbs_program_verify: status %d: %s" % (rc, lib().vpbs_last_error(v.ctx.h).decode()))
+        return verdicts, reasons, sub
+
+    def verify_batch(self, ring_verifier, inputs, key_of, testvs, out_cts, proofs):
+        """verify for many instances on ONE RingVerifier: inputs [instances][n_inputs][n + 1], key_of [instances] slots, testvs [n_luts][N],
+        out_cts [instances][n_gates][K][N] (claimed), proofs[b][g] as prove_batch returns them -> (verdicts, reasons, proof_reasons), np.uint8
+        [instances][n_gates] each; row (b, g) is verify(PbsVerifier of slot key_of[b]'s key hash, inputs[b], testvs, out_cts[b], proofs[b])[.][g].
+        The rows reach the verifier in chunks of its max_batch that may straddle instances."""
+        if self.ctx is None:
+            raise VpbsError("Program.verify_batch: a host-only program (made without a context) cannot be verified")
+        rv = ring_verifier
+        if rv is None or not rv.h:
+            raise VpbsError("Program.verify_batch: no ring verifier (None, or a closed RingVerifier)")
+        x, ko, tv = program_batch_args(self.n_inputs, rv.n_lwe, rv.N, self.n_luts, rv.max_keys, inputs, key_of, testvs)
+        B, G = x.shape[0], self.n_gates
+        o = _u64(out_cts).reshape(-1)
+        if o.size != B * G * rv.K * rv.N or len(proofs) != B or any(len(row) != G for row in proofs):
+            raise ValueError("Program.verify_batch: expected out_cts [%d][%d][K][N] and proofs [%d][%d]" % (B, G, B, G))
+        buf, offs = pack_proofs([blob for row in proofs for blob in row])
+        buf, offs = np.ascontiguousarray(buf, dtype=np.uint8), np.ascontiguousarray(offs, dtype=np.uint64)
+        verdicts, reasons, sub = (np.zeros((B, G), np.uint8) for _ in range(3))
+        u8p = C.POINTER(C.c_uint8)
+        data = buf.ctypes.data_as(u8p) if buf.size else (C.c_uint8 * 1)()
+        keep, err = np.zeros(1, np.uint64), C.create_string_buffer(512)
+        p = lambda a: _ptr(a if a.size else keep)
+        rc = lib().vpbs_program_verify_batch(self.h, rv.h, p(x.reshape(-1)), B, (ko if ko.size else np.zeros(1, np.uint32)).ctypes.data, p(tv.reshape(-1)),
+                                             p(o), data, offs.ctypes.data_as(C.POINTER(C.c_size_t)), verdicts.ctypes.data_as(u8p),
+                                             reasons.ctypes.data_as(u8p), sub.ctypes.data_as(u8p), err, 512)
+        if rc < 0:
+            e = VpbsError("vpbs_program_verify_batch: status %d: %s" % (rc, err.value.decode()))
+            e.status = rc
+            raise e
         return verdicts, reasons, sub
 
     def close(self):

@@ -24,6 +24,11 @@
 //           row b * n_gates + g under the slot of instance b, under the prover's mutex from the evaluation to the last proof.
 //   verify  upload inputs and claimed outputs, lwe_extract_kernel on all outputs, ONE lwe_combine_kernel over all gates in the caller's
 //           order, then vpbs_pbs_verifier_run in chunks.
+//   verify_batch  verify for all instances on a ring verifier (verify_pbs_batch.hip): upload inputs and claimed outputs of ALL instances, ONE
+//           lwe_extract_kernel, ONE lwe_combine_rows_kernel over the rows (instance, gate) in the caller's order, then per chunk of the ring
+//           verifier's max_batch rows the verifier's core on device pointers into these tables (vpbs::pbs_verify_enqueue) -- the test
+//           vector of a row through testv_of = gate_lut, the key hash through key_of of the row's instance; both index arrays are
+//           uploaded once -- and one wait for the chunk's result bytes.
 #include <algorithm>
 #include <cstring>
 #include <mutex>
@@ -91,6 +96,39 @@ __global__ void __launch_bounds__(256) lwe_combine_batch_kernel(CombineBatchArgs
         for (u64 t = t0; t < t1; ++t) {
             const u32* l = a.loc + 3 * t;
             const size_t row = a.instances * l[0] + inst * l[1] + l[2];
+            s = gl::add(s, gl::mul(a.coef[t], gl::canon(a.wires[row * a.words + j])));
+        }
+        out[j] = s;
+    }
+}
+
+struct CombineRowsArgs {
+    const u64* wires;       // [instances][n_in] input rows, then [instances][n_gates] gate-output rows
+    const u64* first;       // [n_gates + 1], the caller's order
+    const u32* src;         // [n_terms]: wires of the caller's numbering
+    const u64* coef;        // [n_terms]
+    const u64* cst;         // [n_gates]
+    u64* out;               // [instances * n_gates][words]
+    size_t instances;
+    unsigned n_in, n_gates, words;
+};
+
+// lwe_combine_kernel for ALL gates of MANY instances in the caller's order (verification has no level order): one workgroup per row
+// b * n_gates + g, lanes on consecutive words.  Wire w of instance b is row b * n_in + w of the input block for w < n_in, else row
+// b * n_gates + (w - n_in) of the gate block behind it; the term list, the coefficients, the constant and the source rows depend on
+// blockIdx.x alone (wave-uniform).  The same arithmetic in the same order: canonical on read, canonical products and sums, the constant in
+// the body only.
+__global__ void __launch_bounds__(256) lwe_combine_rows_kernel(CombineRowsArgs a) {
+    const size_t b = blockIdx.x / a.n_gates;
+    const unsigned g = blockIdx.x % a.n_gates;
+    const u64 t0 = a.first[g], t1 = a.first[g + 1];
+    const u64 c = a.cst[g];
+    u64* out = a.out + (size_t)blockIdx.x * a.words;
+    for (unsigned j = threadIdx.x; j < a.words; j += 256) {
+        u64 s = j + 1 == a.words ? c : 0;
+        for (u64 t = t0; t < t1; ++t) {
+            const u32 w = a.src[t];
+            const size_t row = w < a.n_in ? b * a.n_in + w : a.instances * a.n_in + b * a.n_gates + (w - a.n_in);
             s = gl::add(s, gl::mul(a.coef[t], gl::canon(a.wires[row * a.words + j])));
         }
         out[j] = s;
@@ -659,6 +697,91 @@ long vpbs_program_verify(vpbs_program* prog, vpbs_pbs_verifier* pbs_verifier, co
                                               verdicts + g0, reasons ? reasons + g0 : nullptr, proof_reasons ? proof_reasons + g0 : nullptr);
         if (rc < 0) return rc;
         accepted += rc;
+    }
+    return accepted;
+}
+
+long vpbs_program_verify_batch(vpbs_program* prog, vpbs_ring_verifier* ring_verifier, const uint64_t* inputs, size_t instances, const uint32_t* key_of,
+                               const uint64_t* testvs, const uint64_t* out_cts, const uint8_t* proofs, const size_t* offsets, uint8_t* verdicts,
+                               uint8_t* reasons, uint8_t* proof_reasons, char* err, size_t err_len) {
+    using namespace vpbs;
+    const std::string who = "vpbs_program_verify_batch";
+    auto refuse = [&](const std::string& m) {
+        report(err, err_len, m);
+        return (long)VPBS_ERR_INVALID;
+    };
+    report(err, err_len, "");
+    if (!ring_verifier) return refuse(who + ": null ring verifier");
+    if (!prog) return refuse(who + ": null program");
+    if (!prog->ctx) return refuse(who + ": a host-only program (made without a context) cannot be verified");
+    std::lock_guard<std::mutex> lock(ring_verifier_mutex(ring_verifier));   // from the check of the slots to the last wait
+    RingVerifierShape sh{};
+    ring_verifier_shape(ring_verifier, &sh);
+    vpbs_ctx* ctx = sh.ctx;
+    const unsigned n_in = prog->n_inputs, n_gates = prog->n_gates, words = sh.n_lwe + 1;
+    const size_t n = sh.N, kn = (size_t)sh.K * n, n_wires = (size_t)n_in + n_gates, B = instances, rows = B * n_gates;
+    if (ctx->device != prog->ctx->device) return refuse(who + ": the program and the ring verifier are on different devices");
+    if (n_wires && B > 0x7fffffffull / n_wires) return refuse(who + ": instances x wires exceeds 2^31 - 1 rows");
+    if (B && !key_of) return refuse(who + ": null key_of");
+    if (rows && ((n_in && !inputs) || !testvs || !out_cts || !proofs || !offsets || !verdicts))
+        return refuse(who + ": null inputs, testvs, out_cts, proofs, offsets or verdicts");
+    unsigned log_n = 0;
+    while (((size_t)1 << log_n) < n) ++log_n;
+    if (((size_t)1 << log_n) != n || sh.K < 2 || sh.n_lwe == 0 || sh.n_lwe > (sh.K - 1) * n)
+        return refuse(who + ": the verifier's shape has no sample extraction (N a power of two, 1 <= n_lwe <= (K - 1) N)");
+    std::string msg;
+    if (!ring_verifier_check_slots(ring_verifier, key_of, B, who.c_str(), "instance", &msg)) return refuse(msg);
+    for (size_t r = 0; r < rows; ++r)
+        if (offsets[r + 1] < offsets[r]) return refuse(who + ": offsets decrease at row " + std::to_string(r));
+    if (rows == 0) return 0;
+    // testv_of | key_of of every row, uploaded once
+    std::vector<u32> idx(2 * rows);   // lives until the last wait
+    for (size_t b = 0; b < B; ++b)
+        for (size_t g = 0; g < n_gates; ++g) {
+            idx[b * n_gates + g] = prog->given.lut[g];
+            idx[rows + b * n_gates + g] = key_of[b];
+        }
+    PbsVerifyCore* core = ring_verifier_core(ring_verifier);
+    long accepted = 0;
+    try {
+        VPBS_HIP(hipSetDevice(ctx->device));
+        hipStream_t s = ctx->stream;
+        Scratch mem(ctx);
+        try {
+            u64* d_wires = mem.words(B * n_wires * words);   // [B][n_in] inputs, then [B][n_gates] extractions
+            u64* d_out = mem.words(rows * kn);
+            u64* d_cts = mem.words(rows * words);
+            u64* d_testvs = mem.words((size_t)prog->n_luts * n);
+            u32* d_idx = reinterpret_cast<u32*>(mem.words(rows));
+            if (n_in) VPBS_HIP(hipMemcpyAsync(d_wires, inputs, 8 * B * n_in * words, hipMemcpyHostToDevice, s));
+            VPBS_HIP(hipMemcpyAsync(d_out, out_cts, 8 * rows * kn, hipMemcpyHostToDevice, s));
+            VPBS_HIP(hipMemcpyAsync(d_testvs, testvs, 8 * (size_t)prog->n_luts * n, hipMemcpyHostToDevice, s));
+            VPBS_HIP(hipMemcpyAsync(d_idx, idx.data(), sizeof(u32) * 2 * rows, hipMemcpyHostToDevice, s));
+            lwe_extract_enqueue(s, d_out, log_n, sh.K, sh.n_lwe, rows, d_wires + B * n_in * words);
+            {
+                vpbs::Timed t(ctx, "lwe_combine");
+                const CombineRowsArgs a{d_wires, prog->d_given.first, prog->d_given.src, prog->d_given.coef, prog->d_given.cst, d_cts, B, n_in, n_gates, words};
+                hipLaunchKernelGGL(lwe_combine_rows_kernel, dim3((unsigned)rows), dim3(256), 0, s, a);
+            }
+            VPBS_HIP(hipGetLastError());
+            for (size_t r0 = 0; r0 < rows; r0 += sh.max_batch) {   // a chunk may straddle instances: every row brings its own indices
+                const size_t c = std::min<size_t>(sh.max_batch, rows - r0);
+                const int rc = pbs_verify_enqueue(core, proofs, offsets + r0, c, d_cts + r0 * words, d_out + r0 * kn, d_testvs, d_idx + r0,
+                                                  ring_verifier_key_table(ring_verifier), d_idx + rows + r0);
+                if (rc) {
+                    (void)vpbs::stream_sync(s);
+                    return report(err, err_len, who + ": malformed offsets"), (long)rc;
+                }
+                accepted += pbs_verify_collect(core, c, verdicts + r0, reasons ? reasons + r0 : nullptr, proof_reasons ? proof_reasons + r0 : nullptr);
+            }
+        } catch (const DeviceError& e) {
+            pbs_verify_abandon(core, e);
+            (void)vpbs::stream_sync(s);
+            throw;
+        }
+    } catch (const DeviceError& e) {
+        report(err, err_len, who + ": " + e.what);
+        return e.status == VPBS_ERR_OOM ? VPBS_ERR_OOM : VPBS_ERR_DEVICE;
     }
     return accepted;
 }

@@ -1,5 +1,6 @@
 // The seam between the program object (program.hip) and the five objects it drives: the Bootstrapper (pbs_batch.hip), the key ring
-// (pbs_keyring.hip), the batch provers (pbs_prove_batch.hip, pbs_prove_ring.hip) and the batch verifier of whole vPBS proofs (verify_pbs_batch.hip).  A program queues one bootstrap launch per
+// (pbs_keyring.hip), the batch provers (pbs_prove_batch.hip, pbs_prove_ring.hip) and the batch verifiers of whole vPBS proofs, one key set or a
+// ring of key hashes (verify_pbs_batch.hip).  A program queues one bootstrap launch per
 // level behind its own combine kernel and waits once, at the end: it needs the Bootstrapper's launch WITHOUT the wait vpbs_bootstrapper_run
 // ends with, and the shapes of objects whose structs are private to their files.  Library-internal, like ivc_resident.h.
 #pragma once
@@ -11,6 +12,7 @@
 #include "../../include/vpbs_prover.h"
 
 namespace vpbs {
+struct DeviceError;
 struct BootstrapperShape {
     vpbs_ctx* ctx;
     vpbs_tfhe_params prm;
@@ -72,4 +74,37 @@ struct PbsVerifierShape {
     size_t max_batch;
 };
 void pbs_verifier_shape(const vpbs_pbs_verifier* v, PbsVerifierShape* out);
+
+// ---- the core of both statement verifiers (verify_pbs_batch.hip), for vpbs_program_verify_batch ----
+// Everything vpbs_pbs_verifier_run queues, on DEVICE pointers: ct [count][n_lwe + 1], out_ct [count][K N], a table of test vectors
+// testvs [..][N] with testv_of [count], a table of key hashes [..][4] with key_of [count] -- proof i is checked against testvs[testv_of[i]]
+// and key_hashes[key_of[i]]; digest and cap are the core's.  Queues the upload of the proof bytes (host memory), vp_lwe_chain (on the core's
+// chain stream up to 64 proofs, on the context's stream above), the batch verifier's stages, the statement and vp_result on the context's
+// stream, and leaves verdicts [count] | reasons [count] | proof reasons [count] in the core's result buffer: no wait after the upload.
+// 1 <= count <= max_batch; the pointers must stay unchanged until pbs_verify_collect has returned.  Returns VPBS_OK, or VPBS_ERR_INVALID
+// for offsets that decrease (nothing of the statement is queued then).  Throws vpbs::DeviceError; the caller holds the device.
+struct PbsVerifyCore;
+int pbs_verify_enqueue(PbsVerifyCore* c, const uint8_t* bytes, const size_t* offsets, size_t count, const uint64_t* d_ct, const uint64_t* d_out_ct,
+                       const uint64_t* d_testvs, const uint32_t* d_testv_of, const uint64_t* d_key_hashes, const uint32_t* d_key_of);
+// the read-back of what pbs_verify_enqueue left, and the one wait: the three bytes per proof into host arrays (reasons, proof_reasons may be
+// null) -> the number of accepted proofs.  Throws vpbs::DeviceError.
+long pbs_verify_collect(PbsVerifyCore* c, size_t count, uint8_t* verdicts, uint8_t* reasons, uint8_t* proof_reasons);
+// after a DeviceError of either: the message into the context, the chain stream drained
+void pbs_verify_abandon(PbsVerifyCore* c, const DeviceError& e);
+
+// ---- the ring verifier (verify_pbs_batch.hip) ----
+struct RingVerifierShape {
+    vpbs_ctx* ctx;
+    unsigned N, K, n_lwe;
+    size_t max_keys, max_batch;
+};
+void ring_verifier_shape(const vpbs_ring_verifier* v, RingVerifierShape* out);
+// the mutex that set_key, clear_key and run take: a caller that queues several chunks holds it from its check of the slots to its last wait
+std::mutex& ring_verifier_mutex(vpbs_ring_verifier* v);
+PbsVerifyCore* ring_verifier_core(vpbs_ring_verifier* v);
+const uint64_t* ring_verifier_key_table(const vpbs_ring_verifier* v);   // device memory, [max_keys][4]
+// Host-side check of key_of [count] against the filled slots (the caller holds the mutex), in the key ring's wording: `who` is the entry
+// point, `what` the thing entry i stands for ("proof", "instance").
+bool ring_verifier_check_slots(const vpbs_ring_verifier* v, const uint32_t* key_of, size_t count, const char* who, const char* what,
+                               std::string* msg);
 }  // namespace vpbs
