@@ -978,6 +978,13 @@ int vpbs_glwe_decrypt(vpbs_ctx* ctx, unsigned log_N, unsigned K, const uint64_t*
  *           pointers, or device pointers when on_device != 0.  Works on the context's stream and returns `count` when the outputs are
  *           where the caller asked for them; VPBS_ERR_INVALID for count > max_batch, null cts / testv or no output; VPBS_ERR_DEVICE for a
  *           failed launch.  One run at a time per object.
+ *   run_from: run with a start step per row.  start [count] is a HOST array in every mode (like key_of of the key ring); NULL start is run.
+ *           Row i with start[i] = 0 is run's row.  With start[i] = k in 1 .. n_lwe + 2 the workgroup takes acc_in[i] ([count][K][N], host or
+ *           device with on_device; taken as is, as an accumulator the kernel itself had stored in slot k - 1 of accs_out) in place of the
+ *           rotated test vector, stores it into slot k - 1 of accs_out (slots below k - 1 of that row are NOT written) and runs steps
+ *           k .. n_lwe + 1; step n_lwe + 1 is the key switch as ever, and k = n_lwe + 2 runs no step: out_ct is acc_in and lwe_out its
+ *           extraction.  acc_in rows with start[i] = 0 are not read; acc_in may be NULL when every start is 0.  A start[i] above n_lwe + 2 is
+ *           refused before anything is queued: VPBS_ERR_INVALID, a message (vpbs_last_error) that names the row, no output word written.
  * Words are canonical field elements.  A word at or above p is NOT reduced first: it goes through the same operations as in
  * vpbs_pbs_accumulator_chain (the mod switch reads the raw word; a coefficient c is negated as p - c in 64 bits), so the outputs equal that
  * call's in that case too.
@@ -990,6 +997,9 @@ int vpbs_bootstrapper_create(vpbs_ctx* ctx, const vpbs_tfhe_params* params, unsi
                              int keys_on_device, size_t max_batch, vpbs_bootstrapper** out, char* err, size_t err_len);
 long vpbs_bootstrapper_run(vpbs_bootstrapper* b, const uint64_t* cts, size_t count, const uint64_t* testv, int testv_per_ct,
                            uint64_t* out_ct, uint64_t* lwe_out, uint64_t* accs_out, int on_device);
+long vpbs_bootstrapper_run_from(vpbs_bootstrapper* b, const uint64_t* cts, size_t count, const uint32_t* start /* [count], HOST */,
+                                const uint64_t* acc_in /* [count][K][N] */, const uint64_t* testv, int testv_per_ct,
+                                uint64_t* out_ct, uint64_t* lwe_out, uint64_t* accs_out, int on_device);
 void vpbs_bootstrapper_free(vpbs_bootstrapper* b);
 int vpbs_lwe_extract(vpbs_ctx* ctx, unsigned log_N, unsigned K, unsigned n_lwe, const uint64_t* glwe, size_t count, uint64_t* lwe_out,
                      int on_device);
@@ -1010,6 +1020,8 @@ int vpbs_lwe_decrypt(const uint64_t* s_lwe, const uint64_t* ct, unsigned n_lwe, 
  *           index at or above max_keys, or an empty slot, returns VPBS_ERR_INVALID with a message (vpbs_last_error) that names the
  *           ciphertext and the slot; nothing is launched and no output word is written.  count == 0 is legal and returns 0; count >
  *           max_batch is VPBS_ERR_INVALID.
+ *   run_from: run with a start step per ciphertext, as vpbs_bootstrapper_run_from (start a HOST array, acc_in [count][K][N], both indexed by
+ *           ciphertext like key_of); the key rows requested ahead begin at the rows of the start step.  key_of is checked first, then start.
  * add, remove and run of one ring exclude each other (a second caller waits); they work on the context's stream and return when done. */
 typedef struct vpbs_keyring vpbs_keyring;
 int vpbs_keyring_create(vpbs_ctx* ctx, const vpbs_tfhe_params* params, unsigned n_lwe, size_t max_keys, size_t max_batch, vpbs_keyring** out,
@@ -1019,6 +1031,9 @@ int vpbs_keyring_remove(vpbs_keyring* ring, unsigned slot);
 size_t vpbs_keyring_count(vpbs_keyring* ring);
 long vpbs_keyring_run(vpbs_keyring* ring, const uint64_t* cts, size_t count, const uint32_t* key_of, const uint64_t* testv, int testv_per_ct,
                       uint64_t* out_ct, uint64_t* lwe_out, uint64_t* accs_out, int on_device);
+long vpbs_keyring_run_from(vpbs_keyring* ring, const uint64_t* cts, size_t count, const uint32_t* key_of, const uint32_t* start,
+                           const uint64_t* acc_in, const uint64_t* testv, int testv_per_ct,
+                           uint64_t* out_ct, uint64_t* lwe_out, uint64_t* accs_out, int on_device);
 void vpbs_keyring_free(vpbs_keyring* ring);
 
 /* ---- the client side in batches: encrypt, lookup-table test vectors, decode with noise statistics (csrc/lwe_client.hip) ----
@@ -1082,6 +1097,19 @@ int vpbs_lwe_decode_batch(vpbs_ctx* ctx, const uint64_t* s_lwe, int key_on_devic
  *           reports proof_fn(user, index, NULL, 0, message); the other chains go on.  steps: 0 = n_lwe + 2, fewer = a prefix (tests).
  *           Returns the number of proofs delivered, or VPBS_ERR_INVALID (null cts / testv with count > 0, no proof_fn, steps > n_lwe + 2;
  *           nothing launched) or the Bootstrapper's status.  One run at a time per object (a second caller waits).
+ *   resume: run, with a checkpoint per row: checkpoints [count] (entries may be NULL, or the array itself), lens [count].  A checkpoint is what
+ *           set_checkpoint's fn received for that ciphertext: the proof after chain steps 0 .. k - 1 (k its counter).  A row without one is
+ *           run's row, so resume with no checkpoint is run, byte for byte.  Before anything is queued every checkpoint is validated on the
+ *           host, the rows spread over the worker threads: the prefix form of vpbs_verify_pbs against the object's own verifier data (the
+ *           LWE hash chain included), then ONE 32-byte compare of its key hash with link k - 1 of the resident key set -- no key chain is
+ *           walked.  A refused checkpoint calls proof_fn(user, i, NULL, 0, "checkpoint: <why>") exactly once ("checkpoint: the key hash
+ *           chain does not match"; "checkpoint: its counter k is beyond the requested s steps"); that row's out_ct and lwe_out are still
+ *           produced, from step 0, and no other row is affected.  Outputs first, as in run: one run_from launch per 256 rows, accepted
+ *           rows entering at their k from the checkpoint's accumulator.  Per chain a count-1 run_from leaves accumulators k - 1 .. n + 1 on
+ *           the device and the chain goes on at step k with the checkpoint's proof as step k's inner proof: the proofs are those of an
+ *           uninterrupted chain, byte for byte.  steps == k delivers the validated checkpoint itself.  set_checkpoint keeps working:
+ *           a resumed chain counts its `every` from k (fn runs after steps k + every, k + 2 every, ..) and `done` counts chain steps,
+ *           not steps of the call.  Returns and last_run as run.
  *   key_hash: the end of the key hash chain -- what vpbs_pbs_verifier_create wants (vpbs_pbs_key_hash, without walking the chain again).
  *   set_check_witness / witness_checks: vpbs_ivc_set_check_witness on every chain; the counters summed over the chains.
  *   set_checkpoint: vpbs_ivc_set_checkpoint on every chain; fn also gets the ciphertext index, and shares proof_fn's serialisation.
@@ -1103,6 +1131,9 @@ int vpbs_pbs_prover_create(int device_ordinal, const vpbs_ivc_circuit* cyclic, c
                            vpbs_pbs_prover** out, char* err, size_t err_len);
 long vpbs_pbs_prover_run(vpbs_pbs_prover* p, const uint64_t* cts, size_t count, const uint64_t* testv, int testv_per_ct, unsigned steps,
                          uint64_t* out_ct, uint64_t* lwe_out, vpbs_pbs_proof_fn proof_fn, void* user, char* err, size_t err_len);
+long vpbs_pbs_prover_resume(vpbs_pbs_prover* p, const uint64_t* cts, size_t count, const uint64_t* testv, int testv_per_ct,
+                            const uint8_t* const* checkpoints /* [count], entries may be NULL */, const size_t* lens, unsigned steps,
+                            uint64_t* out_ct, uint64_t* lwe_out, vpbs_pbs_proof_fn proof_fn, void* user, char* err, size_t err_len);
 int vpbs_pbs_prover_key_hash(const vpbs_pbs_prover* p, uint64_t out[4]);
 int vpbs_pbs_prover_verifier_data(const vpbs_pbs_prover* p, uint64_t* cyclic_vk, uint64_t* dummy_vk);
 int vpbs_pbs_prover_set_check_witness(vpbs_pbs_prover* p, int on);
@@ -1136,6 +1167,8 @@ void vpbs_pbs_prover_free(vpbs_pbs_prover* p);
  *           calls proof_fn zero times and writes no output word.  All outputs come first, in key-ring launches of 256 rows; then the
  *           workers take indices from a queue: per ciphertext a count-1 vpbs_keyring_run under its slot leaves the chain's accumulators on
  *           the device, and the preset matrices are assembled from that slot's resident bsk, ksk and key links.  count == 0 returns 0.
+ *   resume: as vpbs_pbs_prover_resume, plus key_of: a checkpoint's key hash is compared with link k - 1 of the slot key_of[i], so a
+ *           checkpoint presented under another slot is refused with "checkpoint: the key hash chain does not match".
  *   verifier_data, set_check_witness, witness_checks, set_checkpoint, last_run: as on vpbs_pbs_prover.
  * add, remove and run of one object exclude each other for the whole of a run: no slot changes under a chain that is being proven. */
 typedef struct vpbs_ring_prover vpbs_ring_prover;
@@ -1150,6 +1183,9 @@ vpbs_keyring* vpbs_ring_prover_keyring(vpbs_ring_prover* p);
 vpbs_ctx* vpbs_ring_prover_context(vpbs_ring_prover* p);
 long vpbs_ring_prover_run(vpbs_ring_prover* p, const uint64_t* cts, size_t count, const uint32_t* key_of, const uint64_t* testv, int testv_per_ct,
                           unsigned steps, uint64_t* out_ct, uint64_t* lwe_out, vpbs_pbs_proof_fn proof_fn, void* user, char* err, size_t err_len);
+long vpbs_ring_prover_resume(vpbs_ring_prover* p, const uint64_t* cts, size_t count, const uint32_t* key_of, const uint64_t* testv, int testv_per_ct,
+                             const uint8_t* const* checkpoints /* [count], entries may be NULL */, const size_t* lens, unsigned steps,
+                             uint64_t* out_ct, uint64_t* lwe_out, vpbs_pbs_proof_fn proof_fn, void* user, char* err, size_t err_len);
 int vpbs_ring_prover_verifier_data(const vpbs_ring_prover* p, uint64_t* cyclic_vk, uint64_t* dummy_vk);
 int vpbs_ring_prover_set_check_witness(vpbs_ring_prover* p, int on);
 int vpbs_ring_prover_witness_checks(const vpbs_ring_prover* p, uint64_t out[2]);

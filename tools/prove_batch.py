@@ -5,7 +5,7 @@ ALL proofs through api.PbsVerifier built from the prover's key_hash() and all lw
 reference's main.rs:59-64).  One JSON line.
 
 usage: tools/prove_batch.py [--count M] [--chains C] [--witness-batch B] [--steps K] [--n2048 | --n8] [--keys-on-device] [--baseline]
-                            [--keys M [--baseline]]
+                            [--keys M [--baseline]] [--checkpoint DIR:every] [--resume DIR]
   --steps K < n + 2 proves a prefix of every chain (tests); the proofs are then checked by api.verify_pbs_prefix on the host (verify_pbs
     insists on counter = n + 2); the outputs are those of the whole bootstrap either way.
   --n8: the N = 8, n = 6 miniature (degree 2^13); --n2048: N = 2048 (degree 2^17); default: the paper's N = 1024, n = 728 (degree 2^16).
@@ -19,7 +19,13 @@ usage: tools/prove_batch.py [--count M] [--chains C] [--witness-batch B] [--step
     --baseline: the same with M api.PbsProver objects, one after the other, each proving the ciphertexts of its key set, and M
     api.PbsVerifier objects (it needs nothing newer than api.PbsProver, so this file can be copied into a build of an older commit).
     Both print one JSON line with the wall time (seconds), proofs, device_bytes_held_by_the_provers (hipMemGetInfo before the first
-    create and after the last), seconds_until_out_ct_complete and prepare_chain_ms."""
+    create and after the last), seconds_until_out_ct_complete and prepare_chain_ms.
+  --checkpoint DIR:every: every `every` steps of every chain its proof so far goes to DIR/ct<i>_step<k>.bin (on_checkpoint; written under a
+    temporary name and renamed, so a crash never leaves a torn file).  --resume DIR: every ciphertext that has a file there goes on from
+    its highest-numbered one (PbsProver.resume / RingProver.resume); the JSON line reports resumed_from per row (0: from step 0) and, for
+    a checkpoint the prover refused, its message under checkpoints_refused.  Both work with --keys M; neither with --baseline.  Every
+    line carries proofs_sha256, so that a resumed run can be compared with an uninterrupted one."""
+import hashlib
 import argparse
 import json
 import os
@@ -52,6 +58,56 @@ def cpu_seconds():
     return r.ru_utime + r.ru_stime
 
 
+def checkpoint_writer(directory):
+    """on_checkpoint's fn for --checkpoint: directory/ct<i>_step<k>.bin, written under a temporary name and renamed into place"""
+    os.makedirs(directory, exist_ok=True)
+    written = []
+
+    def write(index, done, blob):
+        path = os.path.join(directory, "ct%d_step%d.bin" % (index, done))
+        tmp = path + ".tmp.%d" % os.getpid()
+        with open(tmp, "wb") as f:
+            f.write(blob)
+        os.replace(tmp, path)
+        written.append(path)
+    return write, written
+
+
+def checkpoints_of(directory, count):
+    """--resume: the highest-numbered ct<i>_step<k>.bin of every ciphertext -> (list of bytes or None, list of k or 0)"""
+    best = {}
+    for name in os.listdir(directory):
+        if name.startswith("ct") and name.endswith(".bin") and "_step" in name:
+            i, k = name[2:-4].split("_step")
+            if i.isdigit() and k.isdigit() and int(i) < count and int(k) > best.get(int(i), (0, ""))[0]:
+                best[int(i)] = (int(k), os.path.join(directory, name))
+    blobs = [open(best[i][1], "rb").read() if i in best else None for i in range(count)]
+    return blobs, [best[i][0] if i in best else 0 for i in range(count)]
+
+
+def run_prover(args, prover, prove, resume):
+    """prove(...) or, with --resume, resume(checkpoints, ...) under --checkpoint's writer -> (proofs, out_ct, lwe_out, resume figures)"""
+    written = None
+    if args.checkpoint:
+        directory, every = args.checkpoint.rsplit(":", 1)
+        write, written = checkpoint_writer(directory)
+        prover.on_checkpoint(int(every), write)
+    if args.resume:
+        blobs, ks = checkpoints_of(args.resume, args.count)
+        proofs, out_ct, lwe_out, errors = resume(blobs)
+        refused = {i: e for i, e in enumerate(errors) if e is not None}
+        figures = {"resumed_from": [0 if i in refused else k for i, k in enumerate(ks)], "checkpoints_refused": refused}
+    else:
+        proofs, out_ct, lwe_out = prove()
+        figures = {"resumed_from": [0] * args.count, "checkpoints_refused": {}}
+    figures["checkpoints_written"] = len(written) if written is not None else None
+    return proofs, out_ct, lwe_out, figures
+
+
+def proof_hashes(proofs):
+    return [hashlib.sha256(b).hexdigest() if b is not None else None for b in proofs]
+
+
 def prove_new(args, N, n_lwe, cyc, dum, ctx, keys, cts, testv):
     """-> (proofs, out_ct, lwe_out, key_hash, verifier data, seconds, seconds until out_ct was complete, extra); called inside the CPU clock"""
     t_make = time.perf_counter()
@@ -63,14 +119,16 @@ def prove_new(args, N, n_lwe, cyc, dum, ctx, keys, cts, testv):
     t_make = time.perf_counter() - t_make
     first = []
     t0, c0 = time.perf_counter(), cpu_seconds()
-    proofs, out_ct, lwe_out = prover.prove(cts, testv, steps=args.steps, on_proof=lambda i, b: first.append(time.perf_counter() - t0))
+    on_proof = lambda i, b: first.append(time.perf_counter() - t0)
+    proofs, out_ct, lwe_out, figures = run_prover(args, prover, lambda: prover.prove(cts, testv, steps=args.steps, on_proof=on_proof),
+                                                  lambda blobs: prover.resume(cts, testv, blobs, steps=args.steps, on_proof=on_proof))
     seconds, cpu = time.perf_counter() - t0, cpu_seconds() - c0
     kh, (vk, _) = prover.key_hash(), prover.verifier_data()
     run = prover.last_run()   # the library's own clock: when out_ct / lwe_out were complete, the chains' vpbs_ivc_timing
     prover.close()
     return proofs, out_ct, lwe_out, kh, vk, seconds, run["outputs_seconds"], {
         "cpu_seconds_proving": cpu, "prover_create_s": t_make, "first_proof_after_s": min(first) if first else None, "prepare_chain_ms": run["prepare_chain_ms"],
-        "chain_timing_mean": run["chain"], "early_witness_ms_per_step": run["chain"]["early_witness_ms"]}
+        "chain_timing_mean": run["chain"], "early_witness_ms_per_step": run["chain"]["early_witness_ms"], **figures}
 
 
 def prove_baseline(args, N, n_lwe, log_n, cyc_path, dum_path, keys, cts, testv):
@@ -151,6 +209,7 @@ def main_keys(args, N, n_lwe, log_n):
     cts = np.stack([api.lwe_encrypt(keys[k]["params"], keys[k]["s_lwe"], delta * m % P, nonce=i) for i, (m, k) in enumerate(zip(msgs, key_of))])
     mine = [[i for i in range(count) if key_of[i] == k] for k in range(M)]
     proofs, out_ct, lwe_out = [None] * count, np.zeros((count, K, N), np.uint64), np.zeros((count, n_lwe + 1), np.uint64)
+    figures = {}
     ctx.synchronize()
     load0, free0 = os.getloadavg()[0], device_bytes_free()
     t0 = time.perf_counter()
@@ -179,7 +238,8 @@ def main_keys(args, N, n_lwe, log_n):
         for k in range(M):
             assert rp.add(keys[k]["bsk"], keys[k]["ksk"]) == k
         held, t_made = free0 - device_bytes_free(), time.perf_counter()
-        proofs, out_ct, lwe_out = rp.prove(cts, key_of, testv, steps=args.steps)
+        proofs, out_ct, lwe_out, figures = run_prover(args, rp, lambda: rp.prove(cts, key_of, testv, steps=args.steps),
+                                                      lambda blobs: rp.resume(cts, key_of, testv, blobs, steps=args.steps))
         run = rp.last_run()
         t_out, prepare_ms, n_proofs = run["outputs_seconds"], run["prepare_chain_ms"], run["proofs"]
         hashes, vk = [rp.key_hash(k) for k in range(M)], rp.verifier_data()[0]
@@ -190,11 +250,13 @@ def main_keys(args, N, n_lwe, log_n):
     whole = args.steps in (0, total)
     ncols, cap = [cyc.n_constants + 80, 135, 20, 16], vk[4:].reshape(-1, 4)
     accepted, why = 0, set()
-    if whole and not args.baseline:   # ONE RingVerifier for all key sets: slot k holds the key hash of the prover's slot k
+    live = [i for i in range(count) if proofs[i] is not None]   # a refused checkpoint leaves no proof: not accepted, the exit status is 1
+    mine = [[i for i in m if proofs[i] is not None] for m in mine]
+    if whole and not args.baseline and live:   # ONE RingVerifier for all key sets: slot k holds the key hash of the prover's slot k
         rv = api.RingVerifier(ctx, cap, ncols, vk[:4], log_n, cyc.n_constants, 80, cyc.gates, N, K, n_lwe, K * ELL * K * N, max_keys=M, max_batch=count)
         for k in range(M):
             rv.set_key(k, hashes[k])
-        verdicts, reasons, _ = rv.verify(proofs, key_of, testv, cts, out_ct)
+        verdicts, reasons, _ = rv.verify([proofs[i] for i in live], [key_of[i] for i in live], testv, cts[live], out_ct[live])
         rv.close()
         accepted = int(verdicts.sum())
         why = {api.pbs_reason_text(int(r)) for v, r in zip(verdicts, reasons) if not v}
@@ -215,14 +277,15 @@ def main_keys(args, N, n_lwe, log_n):
             why |= {str(r[-1]) for r in res if not r[0]}
     decrypted = sum(1 for i in range(count) if rounded(api.lwe_decrypt(keys[key_of[i]]["s_lwe"], lwe_out[i]), delta) == msgs[i])
     ctx.close()
-    print(json.dumps({
+    print(json.dumps(dict({
         "what": "%d verifiable bootstraps under %d key sets at N=%d, n=%d (degree 2^%d), %s" % (
             count, M, N, n_lwe, log_n, "one PbsProver per key set, one after the other" if args.baseline else "one RingProver.prove"),
         "count": count, "keys": M, "chains": args.chains, "witness_batch": args.witness_batch, "steps": args.steps or total, "baseline": args.baseline,
         "seconds": t_end - t_made, "seconds_with_create_and_close": t_end - t0, "create_seconds": t_made - t0, "proofs": n_proofs,
         "seconds_per_proof": (t_end - t_made) / max(n_proofs, 1), "device_bytes_held_by_the_provers": held,
         "seconds_until_out_ct_complete": t_out, "prepare_chain_ms": prepare_ms, "accepted": accepted, "rejected_because": sorted(why),
-        "decrypted_correct": decrypted, "host": {"cpus": len(os.sched_getaffinity(0)), "loadavg_before": load0, "loadavg_after": os.getloadavg()[0]}}))
+        "decrypted_correct": decrypted, "proofs_sha256": proof_hashes(proofs),
+        "host": {"cpus": len(os.sched_getaffinity(0)), "loadavg_before": load0, "loadavg_after": os.getloadavg()[0]}}, **figures)))
     return 0 if accepted == count and decrypted == count and n_proofs == count else 1
 
 
@@ -237,7 +300,13 @@ def main():
     ap.add_argument("--keys-on-device", action="store_true")
     ap.add_argument("--baseline", action="store_true")
     ap.add_argument("--keys", type=int, default=0)
+    ap.add_argument("--checkpoint", default="", metavar="DIR:every")
+    ap.add_argument("--resume", default="", metavar="DIR")
     args = ap.parse_args()
+    if args.baseline and (args.checkpoint or args.resume):
+        raise SystemExit("--checkpoint and --resume belong to the batch provers: they cannot run with --baseline")
+    if args.checkpoint and not args.checkpoint.rsplit(":", 1)[-1].isdigit():
+        raise SystemExit("--checkpoint wants DIR:every")
     if args.baseline and args.keys_on_device:
         raise SystemExit("--baseline proves under host keys: it cannot run with --keys-on-device")
     N, n_lwe, log_n = (8, 6, 13) if args.n8 else ((2048, 728, 17) if args.n2048 else (1024, 728, 16))
@@ -269,17 +338,20 @@ def main():
     ncols = [cyc.n_constants + 80, 135, 20, 16]
     cap = vk[4:].reshape(-1, 4)
     t = time.perf_counter()
-    if whole:
+    live = [i for i, b in enumerate(proofs) if b is not None]   # a refused checkpoint leaves no proof: not accepted, the exit status is 1
+    if whole and live:
         pv = api.PbsVerifier(ctx, cap, ncols, vk[:4], log_n, cyc.n_constants, 80, cyc.gates, N, K, n_lwe, K * ELL * K * N, kh,
-                             max_batch=args.count)
-        verdicts, reasons, _ = pv.verify(proofs, testv, cts, out_ct.reshape(args.count, -1))
+                             max_batch=len(live))
+        verdicts, reasons, _ = pv.verify([proofs[i] for i in live], testv, cts[live], out_ct[live].reshape(len(live), -1))
         pv.close()
         accepted = int(verdicts.sum())
         why = sorted({api.pbs_reason_text(int(r)) for v, r in zip(verdicts, reasons) if not v})
+    elif whole:
+        accepted, why = 0, []
     else:   # prefixes: the host's prefix form, which wants host keys
         hk = keys if not args.keys_on_device else ctx.keygen(N, K, ELL, LOGB, n_lwe, SEED, SIGMA_GLWE, SIGMA_LWE)
-        res = [api.verify_pbs_prefix(b, cap, ncols, vk[:4], log_n, cyc.n_constants, 80, cyc.gates, N, K, testv, cts[i], hk["bsk"], hk["ksk"])
-               for i, b in enumerate(proofs)]
+        res = [api.verify_pbs_prefix(proofs[i], cap, ncols, vk[:4], log_n, cyc.n_constants, 80, cyc.gates, N, K, testv, cts[i], hk["bsk"], hk["ksk"])
+               for i in live]
         accepted = sum(1 for r in res if r[0] and r[1] == args.steps)
         why = sorted({str(r[-1]) for r in res if not r[0]})
     t_verify = time.perf_counter() - t
@@ -298,6 +370,7 @@ def main():
         "proofs_per_s": args.count / seconds if whole else None, "ms_per_step": 1e3 * seconds * args.chains / (args.count * (args.steps or total)),
         "seconds_until_out_ct_complete": t_out, "accepted": accepted, "rejected_because": why, "decrypted_correct": decrypted,
         "cpu_seconds_setup_and_proving": cpu, "cpu_seconds_per_proof": extra["cpu_seconds_proving"] / args.count, "verify_s": t_verify,
+        "proofs_sha256": proof_hashes(proofs),
         "host": {"cpus": len(os.sched_getaffinity(0)), "loadavg_before": load0, "loadavg_after": os.getloadavg()[0]}}, **extra)))
     return 0 if accepted == args.count and (decrypted in (None, args.count)) else 1
 

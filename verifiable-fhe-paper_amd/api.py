@@ -332,16 +332,19 @@ SIGNATURES = {
     "vpbs_glwe_decrypt": (_i, [_vp, _ui, _ui, U64P, U64P, U64P]),
     "vpbs_bootstrapper_create": (_i, [_vp, C.POINTER(TfheParamsC), _ui, _vp, _vp, _i, _sz, C.POINTER(_vp), C.c_char_p, _sz]),
     "vpbs_bootstrapper_run": (C.c_long, [_vp, _vp, _sz, _vp, _i, _vp, _vp, _vp, _i]),
+    "vpbs_bootstrapper_run_from": (C.c_long, [_vp, _vp, _sz, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i]),
     "vpbs_bootstrapper_free": (None, [_vp]),
     "vpbs_keyring_create": (_i, [_vp, C.POINTER(TfheParamsC), _ui, _sz, _sz, C.POINTER(_vp), C.c_char_p, _sz]),
     "vpbs_keyring_add": (_i, [_vp, _vp, _vp, _i, C.POINTER(_ui)]),
     "vpbs_keyring_remove": (_i, [_vp, _ui]),
     "vpbs_keyring_count": (_sz, [_vp]),
     "vpbs_keyring_run": (C.c_long, [_vp, _vp, _sz, _vp, _vp, _i, _vp, _vp, _vp, _i]),
+    "vpbs_keyring_run_from": (C.c_long, [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i]),
     "vpbs_keyring_free": (None, [_vp]),
     "vpbs_pbs_prover_create": (_i, [_i, C.POINTER(IvcCircuitC), C.POINTER(IvcCircuitC), C.POINTER(TfheParamsC), _ui, _vp, _vp, _i, _ui, _ui,
                                     C.POINTER(_vp), C.c_char_p, _sz]),
     "vpbs_pbs_prover_run": (C.c_long, [_vp, U64P, _sz, U64P, _i, _ui, U64P, U64P, PBS_PROOF_FN, _vp, C.c_char_p, _sz]),
+    "vpbs_pbs_prover_resume": (C.c_long, [_vp, U64P, _sz, U64P, _i, _vp, _vp, _ui, U64P, U64P, PBS_PROOF_FN, _vp, C.c_char_p, _sz]),
     "vpbs_pbs_prover_key_hash": (_i, [_vp, U64P]),
     "vpbs_pbs_prover_verifier_data": (_i, [_vp, U64P, U64P]),
     "vpbs_pbs_prover_set_check_witness": (_i, [_vp, _i]),
@@ -357,6 +360,7 @@ SIGNATURES = {
     "vpbs_ring_prover_keyring": (_vp, [_vp]),
     "vpbs_ring_prover_context": (_vp, [_vp]),
     "vpbs_ring_prover_run": (C.c_long, [_vp, U64P, _sz, _vp, U64P, _i, _ui, U64P, U64P, PBS_PROOF_FN, _vp, C.c_char_p, _sz]),
+    "vpbs_ring_prover_resume": (C.c_long, [_vp, U64P, _sz, _vp, U64P, _i, _vp, _vp, _ui, U64P, U64P, PBS_PROOF_FN, _vp, C.c_char_p, _sz]),
     "vpbs_ring_prover_verifier_data": (_i, [_vp, U64P, U64P]),
     "vpbs_ring_prover_set_check_witness": (_i, [_vp, _i]),
     "vpbs_ring_prover_witness_checks": (_i, [_vp, U64P]),
@@ -1590,6 +1594,25 @@ class Bootstrapper:
             raise VpbsError("vpbs_bootstrapper_run: status %d: %s" % (rc, lib().vpbs_last_error(self.ctx.h).decode()))
         return (out_ct, lwe_out, accs) if accumulators else (out_ct, lwe_out)
 
+    def run_from(self, cts, start, acc_in, testv, accumulators=False):
+        """run with a start step per row (vpbs_bootstrapper_run_from): start [count] (0: from the test vector, as run; k in 1 .. n + 2: from
+        acc_in[i] [K][N], the accumulator after step k - 1, running steps k .. n + 1); acc_in [count][K][N], or None when every start is 0.
+        accumulators: True for a fresh array, or an array [count][n + 2][K][N] to write into -- slots below k - 1 of a resumed row keep
+        what they held.  A start above n + 2 raises VpbsError with the library's message, which names the row; nothing is launched."""
+        c, st, acc, tv = run_from_args(self.N, self.K, self.n_lwe, cts, start, acc_in, testv, "Bootstrapper.run_from")
+        count = c.shape[0]
+        out_ct, lwe_out = np.zeros((count, self.K, self.N), np.uint64), np.zeros((count, self.n_lwe + 1), np.uint64)
+        accs = _accs_out(accumulators, count, self.n_lwe, self.K, self.N, "Bootstrapper.run_from")
+        keep = np.zeros(1, np.uint64)   # a valid pointer for an empty batch
+        p = lambda a: (a if a.size else keep).ctypes.data
+        rc = lib().vpbs_bootstrapper_run_from(self.h, p(c), count, p(st), None if acc is None else p(acc), p(tv), 1 if tv.ndim == 2 else 0,
+                                              p(out_ct), p(lwe_out), None if accs is None else p(accs), 0)
+        if rc != count:
+            e = VpbsError("vpbs_bootstrapper_run_from: status %d: %s" % (rc, lib().vpbs_last_error(self.ctx.h).decode()))
+            e.status = rc
+            raise e
+        return (out_ct, lwe_out) if accs is None else (out_ct, lwe_out, accs)
+
     def run_device(self, d_cts, count, d_testv, testv_per_ct=False, d_out_ct=None, d_lwe_out=None, d_accs=None):
         """the same on device pointers (integers; None = output not wanted); returns when the outputs are in place"""
         q = lambda x: C.c_void_p(int(x)) if x else None
@@ -1610,6 +1633,81 @@ class Bootstrapper:
             self.close()
         except Exception:
             pass
+
+
+def run_from_args(N, K, n_lwe, cts, start, acc_in, testv, who="run_from"):
+    """shapes of a run_from call, checked without a device: cts [count][n + 1], start [count] non-negative integers (their upper bound is
+    the library's refusal, which names the row), acc_in [count][K][N] or None, testv [N] or [count][N] -> (cts, start as uint32, acc_in,
+    testv), contiguous"""
+    c, tv = _u64(cts), _u64(testv)
+    if c.ndim != 2 or c.shape[1] != n_lwe + 1 or tv.shape not in ((N,), (c.shape[0], N)):
+        raise ValueError("%s: expected cts [count][%d] and testv [%d] or [count][%d]" % (who, n_lwe + 1, N, N))
+    st = np.asarray(start)
+    if st.shape == (0,):
+        st = st.astype(np.uint32)
+    if st.dtype.kind not in "iu" or st.shape != (c.shape[0],):
+        raise ValueError("%s: expected start [%d], one integer step per ciphertext" % (who, c.shape[0]))
+    for i, v in enumerate(st.tolist()):
+        if v < 0 or v > 0xFFFFFFFF:
+            raise ValueError("%s: start[%d] = %d is not a step" % (who, i, v))
+    acc = None
+    if acc_in is not None:
+        acc = _u64(acc_in)
+        if acc.shape != (c.shape[0], K, N):
+            raise ValueError("%s: expected acc_in [%d][%d][%d], got shape %s" % (who, c.shape[0], K, N, acc.shape))
+    elif st.any():
+        raise ValueError("%s: a row with start > 0 needs acc_in" % who)
+    return c, np.ascontiguousarray(st, dtype=np.uint32), acc, tv
+
+
+def _accs_out(accumulators, count, n_lwe, K, N, who):
+    """the accumulators argument of run_from: False / None -> None, True -> a zeroed array, an array -> itself (written in place)"""
+    if accumulators is None or accumulators is False:
+        return None
+    if accumulators is True:
+        return np.zeros((count, n_lwe + 2, K, N), np.uint64)
+    a = accumulators
+    if not isinstance(a, np.ndarray) or a.dtype != np.uint64 or not a.flags["C_CONTIGUOUS"] or a.shape != (count, n_lwe + 2, K, N):
+        raise ValueError("%s: accumulators must be True or a contiguous uint64 array [%d][%d][%d][%d]" % (who, count, n_lwe + 2, K, N))
+    return a
+
+
+def resume_args(N, n_lwe, cts, testv, checkpoints, steps=0, key_of=None, max_keys=None):
+    """shapes of a PbsProver.resume / RingProver.resume call, checked without a device: cts [count][n + 1], testv [N] or [count][N],
+    checkpoints a list of `count` entries, each bytes (non-empty) or None, steps 0 .. n + 2 and, for the ring prover (max_keys given), key_of
+    [count] slots below max_keys -> (cts, testv, checkpoints as a list, key_of as uint32 or None)"""
+    who = "RingProver.resume" if max_keys is not None else "PbsProver.resume"
+    c, tv = _u64(cts), _u64(testv)
+    if c.ndim != 2 or c.shape[1] != n_lwe + 1 or tv.shape not in ((N,), (c.shape[0], N)):
+        raise ValueError("%s: expected cts [count][%d] and testv [%d] or [count][%d]" % (who, n_lwe + 1, N, N))
+    if int(steps) != steps or steps < 0 or steps > n_lwe + 2:
+        raise ValueError("%s: steps must be 0 .. n_lwe + 2 = %d, got %r" % (who, n_lwe + 2, steps))
+    if isinstance(checkpoints, (bytes, bytearray, memoryview)) or not hasattr(checkpoints, "__len__"):
+        raise ValueError("%s: checkpoints must be a list of bytes or None, one entry per ciphertext" % who)
+    cps = list(checkpoints)
+    if len(cps) != c.shape[0]:
+        raise ValueError("%s: expected %d checkpoints, one entry (bytes or None) per ciphertext, got %d" % (who, c.shape[0], len(cps)))
+    for i, b in enumerate(cps):
+        if b is None:
+            continue
+        if not isinstance(b, (bytes, bytearray)):
+            raise ValueError("%s: checkpoints[%d] must be bytes or None, not %s" % (who, i, type(b).__name__))
+        if len(b) == 0:
+            raise ValueError("%s: checkpoints[%d] is empty; pass None for a chain that starts at step 0" % (who, i))
+        cps[i] = bytes(b)
+    ko = keyring_key_of(key_of, c.shape[0], max_keys) if max_keys is not None else None
+    return c, tv, cps, ko
+
+
+def _checkpoint_arrays(cps):
+    """the checkpoints of resume_args as the C ABI wants them: (uint8_t* [count], size_t [count], what keeps the bytes alive)"""
+    count = max(1, len(cps))
+    ptrs, lens = (C.c_void_p * count)(), (C.c_size_t * count)()
+    keep = [C.create_string_buffer(b, len(b)) if b is not None else None for b in cps]
+    for i, k in enumerate(keep):
+        ptrs[i] = C.addressof(k) if k is not None else None
+        lens[i] = len(cps[i]) if k is not None else 0
+    return ptrs, lens, keep
 
 
 def keyring_key_of(key_of, count, max_keys):
@@ -1706,6 +1804,21 @@ class KeyRing:
         if rc != count:
             raise self._fail("vpbs_keyring_run", rc)
         return (out_ct, lwe_out, accs) if accumulators else (out_ct, lwe_out)
+
+    def run_from(self, cts, key_of, start, acc_in, testv, accumulators=False):
+        """Bootstrapper.run_from under the key set of slot key_of[i] (vpbs_keyring_run_from)"""
+        c, st, acc, tv = run_from_args(self.N, self.K, self.n_lwe, cts, start, acc_in, testv, "KeyRing.run_from")
+        count = c.shape[0]
+        ko = keyring_key_of(key_of, count, self.max_keys)
+        out_ct, lwe_out = np.zeros((count, self.K, self.N), np.uint64), np.zeros((count, self.n_lwe + 1), np.uint64)
+        accs = _accs_out(accumulators, count, self.n_lwe, self.K, self.N, "KeyRing.run_from")
+        keep = np.zeros(1, np.uint64)   # a valid pointer for an empty batch
+        p = lambda a: (a if a.size else keep).ctypes.data
+        rc = lib().vpbs_keyring_run_from(self.h, p(c), count, p(ko), p(st), None if acc is None else p(acc), p(tv), 1 if tv.ndim == 2 else 0,
+                                         p(out_ct), p(lwe_out), None if accs is None else p(accs), 0)
+        if rc != count:
+            raise self._fail("vpbs_keyring_run_from", rc)
+        return (out_ct, lwe_out) if accs is None else (out_ct, lwe_out, accs)
 
     def run_device(self, d_cts, count, key_of, d_testv, testv_per_ct=False, d_out_ct=None, d_lwe_out=None, d_accs=None):
         """the same on device pointers (integers; None = output not wanted); key_of stays a host array; returns when the outputs are in place"""
@@ -1825,7 +1938,8 @@ class PbsProver:
     def on_checkpoint(self, every, fn):
         """fn(index, done, bytes) after every chained step `done` of ciphertext `index` that is a multiple of `every` and below the chain's
         last step (Ivc.on_checkpoint with the ciphertext index); never two calls at once.  every = 0 or fn = None turns it off.  An
-        exception raised by fn is kept and re-raised by prove."""
+        exception raised by fn is kept and re-raised by prove.  A chain resumed at step k (resume) counts its `every` from k -- after
+        steps k + every, k + 2 every, .. -- and `done` stays the number of chain steps."""
         self._ckpt_error = None
         if fn is None or not every:
             self._ckpt_cb = None
@@ -1850,14 +1964,31 @@ class PbsProver:
         c, tv = _u64(cts), _u64(testv)
         if c.ndim != 2 or c.shape[1] != self.n_lwe + 1 or tv.shape not in ((self.N,), (c.shape[0], self.N)):
             raise ValueError("PbsProver.prove: expected cts [count][%d] and testv [%d] or [count][%d]" % (self.n_lwe + 1, self.N, self.N))
+        return self._run(c, tv, None, steps, on_proof)[:3]
+
+    def resume(self, cts, testv, checkpoints, steps=0, on_proof=None):
+        """prove, with a checkpoint per ciphertext (vpbs_pbs_prover_resume): checkpoints is a list of bytes (what on_checkpoint's fn received
+        for that ciphertext: the proof after chain steps 0 .. k - 1) or None (an ordinary chain from step 0) -> (proofs, out_ct, lwe_out,
+        errors).  A resumed chain goes on at step k and delivers the proof of the uninterrupted chain, byte for byte; steps = k returns the
+        checkpoint itself.  A checkpoint the prover refuses (it does not verify, belongs to another ciphertext or key set, or lies beyond
+        `steps`) raises nothing: the row is None in proofs and errors[i] is the message ("checkpoint: ..."); errors is None elsewhere, and
+        out_ct / lwe_out are complete for every row.  Chains that fail for another reason raise PbsProveError as in prove."""
+        c, tv, cps, _ = resume_args(self.N, self.n_lwe, cts, testv, checkpoints, steps)
+        return self._run(c, tv, cps, steps, on_proof)
+
+    def _run(self, c, tv, cps, steps, on_proof):
         count = c.shape[0]
         out_ct, lwe_out = np.zeros((count, self.K, self.N), np.uint64), np.zeros((count, self.n_lwe + 1), np.uint64)
-        proofs, failures, raised = [None] * count, [], []
+        proofs, failures, raised, errors = [None] * count, [], [], [None] * count
 
         def trampoline(_user, index, data, n, error):
             try:
                 if not data:
-                    failures.append((int(index), (error or b"").decode()))
+                    text = (error or b"").decode()
+                    if cps is not None and text.startswith("checkpoint: "):
+                        errors[index] = text   # a refused checkpoint: reported, not raised
+                    else:
+                        failures.append((int(index), text))
                     return
                 proofs[index] = C.string_at(data, n)
                 if on_proof is not None and not raised:
@@ -1867,17 +1998,25 @@ class PbsProver:
         cb, err = PBS_PROOF_FN(trampoline), C.create_string_buffer(512)
         keep = np.zeros(1, np.uint64)   # a valid pointer for an empty batch
         p = lambda a: _ptr(a if a.size else keep)
-        n = lib().vpbs_pbs_prover_run(self.h, p(c), count, p(tv), 1 if tv.ndim == 2 else 0, steps, p(out_ct), p(lwe_out), cb, None, err, 512)
+        if cps is None:
+            what = "vpbs_pbs_prover_run"
+            n = lib().vpbs_pbs_prover_run(self.h, p(c), count, p(tv), 1 if tv.ndim == 2 else 0, steps, p(out_ct), p(lwe_out), cb, None, err, 512)
+        else:
+            what = "vpbs_pbs_prover_resume"
+            ptrs, lens, alive = _checkpoint_arrays(cps)
+            n = lib().vpbs_pbs_prover_resume(self.h, p(c), count, p(tv), 1 if tv.ndim == 2 else 0, C.addressof(ptrs), C.addressof(lens), steps,
+                                             p(out_ct), p(lwe_out), cb, None, err, 512)
+            del alive
         if raised:
             raise raised[0]
         e, self._ckpt_error = self._ckpt_error, None
         if e is not None:
             raise e
         if n < 0:
-            raise VpbsError("vpbs_pbs_prover_run: status %d: %s" % (n, err.value.decode()))
+            raise VpbsError("%s: status %d: %s" % (what, n, err.value.decode()))
         if failures:
             raise PbsProveError(dict(failures), proofs, out_ct, lwe_out)
-        return proofs, out_ct, lwe_out
+        return proofs, out_ct, lwe_out, errors
 
     def last_run(self):
         """vpbs_pbs_prover_last_run -> dict: seconds, outputs_seconds (call until out_ct / lwe_out were complete), proofs, prepare_chain_ms
@@ -2052,17 +2191,31 @@ class RingProver(PbsProver):
         names an empty slot raises VpbsError (.status = VPBS_ERR_INVALID) with the ring's message before anything runs.  out_ct / lwe_out:
         arrays to write into instead of fresh ones."""
         c, ko, tv = ring_prove_args(self.N, self.n_lwe, self.max_keys, cts, key_of, testv, steps)
+        return self._run_ring(c, ko, tv, None, steps, on_proof, out_ct, lwe_out)[:3]
+
+    def resume(self, cts, key_of, testv, checkpoints, steps=0, on_proof=None, out_ct=None, lwe_out=None):
+        """PbsProver.resume under the key set of slot key_of[i] (vpbs_ring_prover_resume) -> (proofs, out_ct, lwe_out, errors).  A
+        checkpoint presented under another slot than the one it was made under is refused with "checkpoint: the key hash chain does not
+        match"."""
+        c, tv, cps, ko = resume_args(self.N, self.n_lwe, cts, testv, checkpoints, steps, key_of, self.max_keys)
+        return self._run_ring(c, ko, tv, cps, steps, on_proof, out_ct, lwe_out)
+
+    def _run_ring(self, c, ko, tv, cps, steps, on_proof, out_ct, lwe_out):
         count = c.shape[0]
         out_ct = np.zeros((count, self.K, self.N), np.uint64) if out_ct is None else out_ct
         lwe_out = np.zeros((count, self.n_lwe + 1), np.uint64) if lwe_out is None else lwe_out
         if out_ct.shape != (count, self.K, self.N) or lwe_out.shape != (count, self.n_lwe + 1):
             raise ValueError("RingProver.prove: expected out_ct [count][K][N] and lwe_out [count][n + 1]")
-        proofs, failures, raised = [None] * count, [], []
+        proofs, failures, raised, errors = [None] * count, [], [], [None] * count
 
         def trampoline(_user, index, data, n, error):
             try:
                 if not data:
-                    failures.append((int(index), (error or b"").decode()))
+                    text = (error or b"").decode()
+                    if cps is not None and text.startswith("checkpoint: "):
+                        errors[index] = text   # a refused checkpoint: reported, not raised
+                    else:
+                        failures.append((int(index), text))
                     return
                 proofs[index] = C.string_at(data, n)
                 if on_proof is not None and not raised:
@@ -2072,18 +2225,26 @@ class RingProver(PbsProver):
         cb, err = PBS_PROOF_FN(trampoline), C.create_string_buffer(512)
         keep = np.zeros(1, np.uint64)   # a valid pointer for an empty batch
         p = lambda a: _ptr(a if a.size else keep)
-        n = lib().vpbs_ring_prover_run(self.h, p(c), count, (ko if ko.size else np.zeros(1, np.uint32)).ctypes.data, p(tv), 1 if tv.ndim == 2 else 0,
-                                       steps, p(out_ct), p(lwe_out), cb, None, err, 512)
+        pko = (ko if ko.size else np.zeros(1, np.uint32)).ctypes.data
+        if cps is None:
+            what = "vpbs_ring_prover_run"
+            n = lib().vpbs_ring_prover_run(self.h, p(c), count, pko, p(tv), 1 if tv.ndim == 2 else 0, steps, p(out_ct), p(lwe_out), cb, None, err, 512)
+        else:
+            what = "vpbs_ring_prover_resume"
+            ptrs, lens, alive = _checkpoint_arrays(cps)
+            n = lib().vpbs_ring_prover_resume(self.h, p(c), count, pko, p(tv), 1 if tv.ndim == 2 else 0, C.addressof(ptrs), C.addressof(lens), steps,
+                                              p(out_ct), p(lwe_out), cb, None, err, 512)
+            del alive
         if raised:
             raise raised[0]
         e, self._ckpt_error = self._ckpt_error, None
         if e is not None:
             raise e
         if n < 0:
-            raise self._fail("vpbs_ring_prover_run", n, err)
+            raise self._fail(what, n, err)
         if failures:
             raise PbsProveError(dict(failures), proofs, out_ct, lwe_out)
-        return proofs, out_ct, lwe_out
+        return proofs, out_ct, lwe_out, errors
 
     def last_run(self):
         st = PbsRunStatsC()

@@ -301,10 +301,11 @@ struct vpbs_ivc {
     vpbs_ivc_checkpoint_fn ckpt_fn = nullptr;   // vpbs_ivc_set_checkpoint
     void* ckpt_user = nullptr;
     unsigned ckpt_every = 0;
+    unsigned ckpt_base = 0;   // a resident chain that goes on at step k (ivc_prove_pbs_resident) counts its `every` from k; `done` stays absolute
     std::vector<uint8_t> ckpt_bytes;
     // after chained step `done` of a call that ends at step `last`: the proof serialised exactly as a call with steps = done returns it
     int checkpoint(const vpbs_step_inputs& in, const u64* caps, const u64* openings, const u64* fri, unsigned done, unsigned last) {
-        if (!ckpt_fn || !ckpt_every || done % ckpt_every != 0 || done >= last) return VPBS_OK;
+        if (!ckpt_fn || !ckpt_every || (done - ckpt_base) % ckpt_every != 0 || done >= last) return VPBS_OK;
         if (ckpt_bytes.empty()) ckpt_bytes.resize(8 * (proof_words + n_pi) + (1 << 16));
         const long n = vpbs_step_proof_to_bytes(ctx, &in, cyc.n_const_cols, caps, openings, fri, ckpt_bytes.data(), ckpt_bytes.size());
         if (n <= 0) return VPBS_ERR_INVALID;
@@ -576,8 +577,9 @@ static void preset_matrix_host(u64* m, unsigned first, unsigned cnt, const u64* 
 // from > 0 (vpbs_ivc_resume_pbs): no base proof; step `from` takes the checkpoint's proof words and public inputs, the native accumulator
 // chain starts at step `from` from the checkpoint's accumulator and the hash thread from its two hashes.  Progress below is counted in steps
 // of THIS call: local step j is chain step from + j.
-// res != nullptr (vpbs::ivc_prove_pbs_resident, from = 0, bsk and ksk not read): the chain's public inputs exist already -- accumulators and
-// both hash chains are taken from `res`, and every batch's preset matrix is written on the device by res->fill.
+// res != nullptr (vpbs::ivc_prove_pbs_resident, bsk and ksk not read): the chain's public inputs exist already -- accumulators and both hash
+// chains are taken from `res`, indexed by ABSOLUTE chain step whatever `from` is, and every batch's preset matrix is written on the device by
+// res->fill, called with the absolute first step.
 static long prove_pbs_device_witness(vpbs_ivc* v, const uint64_t* testv, const uint64_t* ct, const uint64_t* bsk, const uint64_t* ksk, unsigned n_lwe,
                                      unsigned from, const u64* from_proof, const u64* from_pis, unsigned steps, uint8_t* proof_out, size_t capacity,
                                      vpbs_ivc_timing* timing, char* err, size_t err_len, const vpbs::IvcResidentChain* res = nullptr) {
@@ -606,7 +608,7 @@ static long prove_pbs_device_witness(vpbs_ivc* v, const uint64_t* testv, const u
         say(std::string("native accumulator chain: ") + vpbs_last_error(ctx));
         return VPBS_ERR_INVALID;
     }
-    const u64* accs = res ? res->accs : own_accs.data();
+    const u64* accs = res ? res->accs + (size_t)from * kn : own_accs.data();   // accs[j]: after chain step from + j (valid from j = -1 for res)
     // pis[j + 1] = public inputs of step from + j (pis[0]: of the base proof, or the checkpoint's): acc_init | counter | accumulator | key
     // hash | LWE hash | verifier data
     std::vector<u64> pis((size_t)(n_run + 1) * n_pi, 0);
@@ -618,7 +620,7 @@ static long prove_pbs_device_witness(vpbs_ivc* v, const uint64_t* testv, const u
         }
         std::memcpy(q, acc_init.data(), 8 * kn);
         q[kn] = from + j;
-        if (j) std::memcpy(q + kn + 1, accs + (size_t)(j - 1) * kn, 8 * kn);
+        if (j) std::memcpy(q + kn + 1, accs + ((size_t)j - 1) * kn, 8 * kn);
         std::memcpy(q + n_pi - cyc.vk.size(), cyc.vk.data(), 8 * cyc.vk.size());
     }
     std::mutex mu;
@@ -644,8 +646,8 @@ static long prove_pbs_device_witness(vpbs_ivc* v, const uint64_t* testv, const u
         if (res) {   // both chains exist: nothing to wait for, nothing to hash
             for (unsigned s = 0; s < n_run; ++s) {
                 u64* q = pis.data() + (size_t)(s + 1) * n_pi + 2 * kn + 1;
-                std::memcpy(q, res->key_links + 4 * (size_t)s, 32);
-                std::memcpy(q + 4, res->lwe_links + 4 * (size_t)s, 32);
+                std::memcpy(q, res->key_links + 4 * (size_t)(from + s), 32);
+                std::memcpy(q + 4, res->lwe_links + 4 * (size_t)(from + s), 32);
             }
             {
                 std::lock_guard<std::mutex> lk(mu);
@@ -711,7 +713,7 @@ static long prove_pbs_device_witness(vpbs_ivc* v, const uint64_t* testv, const u
                         auto* f = static_cast<Fill*>(user);
                         return f->res->fill(f->res->user, stream, f->first, f->cnt, d_matrix);
                     }
-                } fill{res, first, cnt};
+                } fill{res, from + first, cnt};
                 run_rc = vpbs::witness_device_run_filled(v->wdev[b & 1], cnt, &Fill::call, &fill);
             } else {
                 u64* m = v->dw_presets;   // [n_preset][cnt]
@@ -1321,55 +1323,21 @@ long vpbs_ivc_resume_pbs(vpbs_ivc* v, const uint64_t* testv, const uint64_t* ct,
         say("resume is not available for a sharded chain");
         return VPBS_ERR_INVALID;
     }
-    const Side& cyc = v->cyc;
-    const size_t kn = v->kn, n_pi = v->n_pi, cap_words = cyc.cs_cap.size();
-    vpbs_compat compat;
-    vpbs_ctx_get_compat(v->ctx, &compat);
-    vpbs_verify_inputs vi{};   // the cyclic circuit as this object committed it: its own verifier data
-    vi.log_n = cyc.log_n;
-    vi.rate_bits = vpbs_ctx_rate_bits(v->ctx);
-    vi.cap_height = vpbs_ctx_cap_height(v->ctx);
-    vi.n_constants_sigmas = cyc.n_const_cols + cyc.n_routed;
-    vi.n_wires = cyc.n_wires;
-    vi.n_zs_partial_products = 20;
-    vi.n_quotient = 16;
-    vi.num_challenges = 2;
-    vi.constants_sigmas_cap = cyc.cs_cap.data();
-    for (int i = 0; i < 4; ++i) vi.circuit_digest[i] = cyc.vk[i];
-    vi.n_constants = cyc.n_const_cols;
-    vi.n_routed = cyc.n_routed;
-    vi.quotient_degree_factor = 8;
-    vi.gates = cyc.gates.data();
-    vi.n_gates = (unsigned)cyc.gates.size();
-    vi.num_selectors = cyc.num_selectors;
-    vi.compat = &compat;
-    const vpbs_verify_pbs_inputs pin{&vi, v->N, v->K, n_lwe, v->ggsw_len, testv, nullptr, ct, bsk, ksk};
+    const size_t kn = v->kn;
+    const vpbs_verify_pbs_inputs pin{nullptr, v->N, v->K, n_lwe, v->ggsw_len, testv, nullptr, ct, bsk, ksk};   // for the key chain alone
     const double t0 = now();
-    unsigned k = 0;
-    char why[256] = {0};
-    const int ok = vpbs::verify_pbs_prefix_without_keys(&pin, checkpoint, len, &k, why, sizeof why);
-    if (ok != 1) {
-        say(std::string("checkpoint: ") + why);
+    vpbs::IvcCheckpoint cp;
+    std::string why;
+    if (!vpbs::ivc_open_checkpoint(v, testv, ct, n_lwe, checkpoint, len, &cp, &why)) {
+        say("checkpoint: " + why);
         return VPBS_ERR_INVALID;
     }
+    const unsigned k = cp.k;
+    std::vector<u64>&words = cp.proof, &pis = cp.pis;
     const unsigned total = n_lwe + 2;
     if (steps == 0 || steps > total) steps = total;
     if (steps < k) {
         say("checkpoint: its counter " + std::to_string(k) + " is beyond the requested " + std::to_string(steps) + " steps");
-        return VPBS_ERR_INVALID;
-    }
-    // the proof words in target order (caps, openings, FRI) and the public inputs
-    vpbs_step_inputs shape;
-    vpbs_step_sizes sz{};
-    cyc.step_inputs(shape, nullptr, true, nullptr);
-    if (vpbs_step_sizes_get(v->ctx, &shape, &sz) != 0 || sz.cap_words != cap_words || 3 * sz.cap_words + sz.openings_words + sz.fri_words != v->proof_words) {
-        say("checkpoint: the proof shape of this object is not the one its circuit expects");
-        return VPBS_ERR_INVALID;
-    }
-    std::vector<u64> words(v->proof_words), pis(n_pi);
-    u64 *caps = words.data(), *openings = caps + 3 * sz.cap_words, *fri = openings + sz.openings_words;
-    if (vpbs_step_proof_from_bytes(&vi, checkpoint, len, caps, openings, fri, pis.data(), n_pi) != (long)n_pi) {
-        say("checkpoint: the bytes are not a proof of this circuit (shape, canonical field elements, number of public inputs)");
         return VPBS_ERR_INVALID;
     }
     const double t_checks = now() - t0;
@@ -1412,16 +1380,76 @@ void ivc_shape(const vpbs_ivc* v, IvcShape* out) {
     *out = IvcShape{v->N, v->K, v->cyc.log_n, v->kn, v->n_pi, v->cyc.n_preset, v->proof_words, v->ggsw_len, v->cyc.vk.size(),
                     v->cyc.vk.data(), v->dum.vk.data(), v->dummy_proof.data(), v->ctx};
 }
-long ivc_prove_pbs_resident(vpbs_ivc* v, const uint64_t* testv, const uint64_t* ct, unsigned n_lwe, const IvcResidentChain* chain, unsigned steps,
-                            uint8_t* proof_out, size_t capacity, vpbs_ivc_timing* timing, char* err, size_t err_len) {
+bool ivc_open_checkpoint(const vpbs_ivc* v, const uint64_t* testv, const uint64_t* ct, unsigned n_lwe, const uint8_t* bytes, size_t len,
+                         IvcCheckpoint* out, std::string* why) {
+    if (!v || !testv || !ct || !bytes || !out || !why) {
+        if (why) *why = "malformed arguments";
+        return false;
+    }
+    const Side& cyc = v->cyc;
+    const size_t n_pi = v->n_pi, cap_words = cyc.cs_cap.size();
+    vpbs_compat compat;
+    vpbs_ctx_get_compat(v->ctx, &compat);
+    vpbs_verify_inputs vi{};   // the cyclic circuit as this object committed it: its own verifier data
+    vi.log_n = cyc.log_n;
+    vi.rate_bits = vpbs_ctx_rate_bits(v->ctx);
+    vi.cap_height = vpbs_ctx_cap_height(v->ctx);
+    vi.n_constants_sigmas = cyc.n_const_cols + cyc.n_routed;
+    vi.n_wires = cyc.n_wires;
+    vi.n_zs_partial_products = 20;
+    vi.n_quotient = 16;
+    vi.num_challenges = 2;
+    vi.constants_sigmas_cap = cyc.cs_cap.data();
+    for (int i = 0; i < 4; ++i) vi.circuit_digest[i] = cyc.vk[i];
+    vi.n_constants = cyc.n_const_cols;
+    vi.n_routed = cyc.n_routed;
+    vi.quotient_degree_factor = 8;
+    vi.gates = cyc.gates.data();
+    vi.n_gates = (unsigned)cyc.gates.size();
+    vi.num_selectors = cyc.num_selectors;
+    vi.compat = &compat;
+    const vpbs_verify_pbs_inputs pin{&vi, v->N, v->K, n_lwe, v->ggsw_len, testv, nullptr, ct, nullptr, nullptr};   // this form reads no keys
+    char text[256] = {0};
+    if (verify_pbs_prefix_without_keys(&pin, bytes, len, &out->k, text, sizeof text) != 1) {
+        *why = text;
+        return false;
+    }
+    // the proof words in target order (caps, openings, FRI) and the public inputs
+    vpbs_step_inputs shape;
+    vpbs_step_sizes sz{};
+    cyc.step_inputs(shape, nullptr, true, nullptr);
+    if (vpbs_step_sizes_get(v->ctx, &shape, &sz) != 0 || sz.cap_words != cap_words || 3 * sz.cap_words + sz.openings_words + sz.fri_words != v->proof_words) {
+        *why = "the proof shape of this object is not the one its circuit expects";
+        return false;
+    }
+    out->proof.assign(v->proof_words, 0);
+    out->pis.assign(n_pi, 0);
+    u64 *caps = out->proof.data(), *openings = caps + 3 * sz.cap_words, *fri = openings + sz.openings_words;
+    if (vpbs_step_proof_from_bytes(&vi, bytes, len, caps, openings, fri, out->pis.data(), n_pi) != (long)n_pi) {
+        *why = "the bytes are not a proof of this circuit (shape, canonical field elements, number of public inputs)";
+        return false;
+    }
+    return true;
+}
+
+long ivc_prove_pbs_resident(vpbs_ivc* v, const uint64_t* testv, const uint64_t* ct, unsigned n_lwe, const IvcResidentChain* chain, unsigned from,
+                            const uint64_t* from_proof, const uint64_t* from_pis, unsigned steps, uint8_t* proof_out, size_t capacity,
+                            vpbs_ivc_timing* timing, char* err, size_t err_len) {
     if (err && err_len) err[0] = 0;
     if (!v || !testv || !ct || !chain || !chain->accs || !chain->key_links || !chain->lwe_links || !chain->fill || !proof_out || !v->dw_batch ||
-        v->dw_late || v->cyc.comm) {
+        v->dw_late || v->cyc.comm || (from && (!from_proof || !from_pis))) {
         if (err && err_len) std::snprintf(err, err_len, "%s", "malformed arguments (a resident chain needs the device-witness pipeline with the late phase on the host)");
         return VPBS_ERR_INVALID;
     }
     const unsigned total = n_lwe + 2;
     if (steps == 0 || steps > total) steps = total;
-    return prove_pbs_device_witness(v, testv, ct, nullptr, nullptr, n_lwe, 0, nullptr, nullptr, steps, proof_out, capacity, timing, err, err_len, chain);
+    if (from >= steps) {   // nothing to prove: the caller delivers the checkpoint itself
+        if (err && err_len) std::snprintf(err, err_len, "%s", "a resident chain from step `from` needs steps > from");
+        return VPBS_ERR_INVALID;
+    }
+    v->ckpt_base = from;
+    const long n = prove_pbs_device_witness(v, testv, ct, nullptr, nullptr, n_lwe, from, from_proof, from_pis, steps, proof_out, capacity, timing, err, err_len, chain);
+    v->ckpt_base = 0;
+    return n;
 }
 }  // namespace vpbs

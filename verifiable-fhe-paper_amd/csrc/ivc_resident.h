@@ -4,6 +4,8 @@
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include <string>
+#include <vector>
 
 #include "../../include/vpbs_prover.h"
 
@@ -29,8 +31,24 @@ struct IvcResidentChain {
 };
 // vpbs_ivc_prove_pbs in the device-witness pipeline (vpbs_ivc_set_device_witness with batch > 0, late phase on the host) on such a chain: no
 // native accumulator chain, no hashing of keys, no host-built preset matrix.  The same proofs, byte for byte.
-long ivc_prove_pbs_resident(vpbs_ivc* v, const uint64_t* testv, const uint64_t* ct, unsigned n_lwe, const IvcResidentChain* chain, unsigned steps,
-                            uint8_t* proof_out, size_t capacity, vpbs_ivc_timing* timing, char* err, size_t err_len);
+// from > 0: the chain goes on at step `from` (vpbs_ivc_resume_pbs's way: no base proof, from_proof [proof_words] is step `from`'s inner proof
+// and from_pis [n_pi] its predecessor's public inputs -- what ivc_open_checkpoint leaves).  accs, key_links and lwe_links stay indexed by
+// ABSOLUTE chain step (entries below from - 1 are not read), and fill is called with absolute `first`.  from = 0: the proof pointers are not read.
+long ivc_prove_pbs_resident(vpbs_ivc* v, const uint64_t* testv, const uint64_t* ct, unsigned n_lwe, const IvcResidentChain* chain, unsigned from,
+                            const uint64_t* from_proof, const uint64_t* from_pis, unsigned steps, uint8_t* proof_out, size_t capacity,
+                            vpbs_ivc_timing* timing, char* err, size_t err_len);
+
+// A checkpoint opened against the object's own verifier data: the prefix form of vpbs_verify_pbs WITHOUT the key hash chain and without keys
+// (claimed test vector, counter, the proof itself, its verifier data, the LWE hash chain over the first k masks of ct), then the proof words
+// in target order (caps, openings, FRI) and the public inputs [acc_init | counter | accumulator | key hash | LWE hash | verifier data].
+// Host only; reads the object, changes nothing: callers on several threads may share one object.  false with the verifier's text in `why`.
+// The caller still owes the key hash: pis[2 K N + 1 .. + 4] against link k - 1 of the keys.
+struct IvcCheckpoint {
+    unsigned k = 0;
+    std::vector<uint64_t> proof, pis;
+};
+bool ivc_open_checkpoint(const vpbs_ivc* v, const uint64_t* testv, const uint64_t* ct, unsigned n_lwe, const uint8_t* bytes, size_t len,
+                         IvcCheckpoint* out, std::string* why);
 
 // vpbs_witness_device_run on a preset matrix that `fill` leaves on the device: fill(user, stream, d_matrix) is called once, with the
 // object's stream and a matrix of [n_preset][batch] words, before the schedule is queued

@@ -37,10 +37,15 @@ struct PbsBatchArgs {
     u64* lwe_out;         // [count][n_lwe + 1] or null
     u64* accs_out;        // [count][n_lwe + 2][K][N] or null
     unsigned log_n, K, ELL, LOGB, n_lwe;
+    // the start mode, behind everything else: the fields above keep the offsets the kernels without it (FROM = false) were compiled for
+    const uint32_t* start;   // [count] or null: row b enters the chain at step start[b] (0: from the rotated test vector, as without it)
+    const u64* acc_in;       // [count][K][N] or null: the accumulator after step start[b] - 1 of the rows that enter late
 };
 
-// one workgroup per ciphertext
-template <unsigned T>
+// one workgroup per ciphertext.  FROM: the start mode (a.start, a.acc_in) is an instantiation of its own, and its two arguments sit behind
+// the older ones: with FROM = false the kernel compiles to the instructions it had before the start mode existed (moved
+// argument offsets renumber the scalar registers, and the launches that start every row at step 0 lost 0.6 - 0.8 %)
+template <unsigned T, bool FROM>
 __global__ void __launch_bounds__(T) pbs_batch_kernel(PbsBatchArgs a) {
     extern __shared__ __align__(16) u64 lds[];
     const unsigned log_n = a.log_n, n = 1u << log_n, K = a.K, ELL = a.ELL, LOGB = a.LOGB, n_lwe = a.n_lwe;
@@ -54,9 +59,18 @@ __global__ void __launch_bounds__(T) pbs_batch_kernel(PbsBatchArgs a) {
     u64* accs = a.accs_out ? a.accs_out + b * (size_t)(n_lwe + 2) * kn : nullptr;
     const size_t ggsw_words = (size_t)K * ELL * kn;
     const unsigned nl = (64 + LOGB - 1) / LOGB, tb = nl * LOGB;
+    // the step this row enters at: uniform over the workgroup, so the loop bounds below stay scalar and every barrier uniform
+    const unsigned k0 = FROM ? a.start[b] : 0;
 
-    // step 0: acc_init = (0, .., 0, testv) rotated by -body (ivc_based_vpbs.rs:106-111,122)
-    {
+    if (FROM && k0) {   // a resumed row: the accumulator after step k0 - 1, as this kernel had stored it (slots below k0 - 1 are not written)
+        const u64* in = a.acc_in + b * kn;
+        u64* slot = accs ? accs + (size_t)(k0 - 1) * kn : nullptr;
+        for (unsigned idx = threadIdx.x; idx < kn; idx += T) {
+            const u64 v = in[idx];
+            acc[idx] = v;
+            if (slot) slot[idx] = v;
+        }
+    } else {   // step 0: acc_init = (0, .., 0, testv) rotated by -body (ivc_based_vpbs.rs:106-111,122)
         const unsigned shift = pb_mod_switch(gl::neg(ct[n_lwe]), log_n);
         for (unsigned idx = threadIdx.x; idx < kn; idx += T) {
             const unsigned i = idx & (n - 1);
@@ -67,7 +81,7 @@ __global__ void __launch_bounds__(T) pbs_batch_kernel(PbsBatchArgs a) {
     }
     __syncthreads();
 
-    for (unsigned step = 1; step <= n_lwe + 1; ++step) {
+    for (unsigned step = FROM && k0 ? k0 : 1; step <= n_lwe + 1; ++step) {   // k0 = n_lwe + 2: no step, the outputs are acc_in's
         const bool last = step == n_lwe + 1;
         const u64* g = last ? a.ksk : a.bsk + (size_t)(step - 1) * ggsw_words;
         const unsigned shift = last ? 0 : pb_mod_switch(ct[step - 1], log_n);
@@ -152,13 +166,19 @@ void report(char* err, size_t err_len, const std::string& m) {
     }
 }
 
+template <unsigned T, bool FROM>
+void launch_pbs_batch_from(hipStream_t s, const PbsBatchArgs& a, size_t count, size_t lds_bytes) {
+    // a workgroup's dynamic LDS above the default limit is announced once per kernel
+    static const hipError_t announced = hipFuncSetAttribute(reinterpret_cast<const void*>(&pbs_batch_kernel<T, FROM>),
+                                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)PBS_LDS_BUDGET);
+    if (announced != hipSuccess) (void)hipGetLastError();   // the launch below reports what matters
+    hipLaunchKernelGGL((pbs_batch_kernel<T, FROM>), dim3((unsigned)count), dim3(T), lds_bytes, s, a);
+}
+
 template <unsigned T>
 void launch_pbs_batch(hipStream_t s, const PbsBatchArgs& a, size_t count, size_t lds_bytes) {
-    // a workgroup's dynamic LDS above the default limit is announced once per kernel
-    static const hipError_t announced =
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&pbs_batch_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)PBS_LDS_BUDGET);
-    if (announced != hipSuccess) (void)hipGetLastError();   // the launch below reports what matters
-    hipLaunchKernelGGL(pbs_batch_kernel<T>, dim3((unsigned)count), dim3(T), lds_bytes, s, a);
+    if (a.start) launch_pbs_batch_from<T, true>(s, a, count, lds_bytes);
+    else launch_pbs_batch_from<T, false>(s, a, count, lds_bytes);
 }
 }  // namespace
 }  // namespace vpbs
@@ -170,6 +190,7 @@ struct vpbs_bootstrapper {
     size_t max_batch = 0, lds_bytes = 0;
     const u64 *d_bsk = nullptr, *d_ksk = nullptr;
     u64 *d_cts = nullptr, *d_testv = nullptr, *d_out = nullptr, *d_lwe = nullptr;   // staging for host callers
+    uint32_t* d_start = nullptr;   // [max_batch]: the start steps of a run_from (a host array in every mode)
     std::vector<void*> owned;
 
     u64* alloc(size_t words) {
@@ -189,7 +210,7 @@ namespace vpbs {
 void bootstrapper_shape(const vpbs_bootstrapper* b, BootstrapperShape* out) { *out = BootstrapperShape{b->ctx, b->prm, b->n_lwe, b->max_batch}; }
 
 void bootstrapper_enqueue(vpbs_bootstrapper* b, const uint64_t* d_cts, size_t count, const uint64_t* d_testv, int testv_per_ct, uint64_t* d_out_ct,
-                          uint64_t* d_lwe_out, uint64_t* d_accs_out) {
+                          uint64_t* d_lwe_out, uint64_t* d_accs_out, const uint32_t* d_start, const uint64_t* d_acc_in) {
     vpbs_ctx* ctx = b->ctx;
     const unsigned log_n = b->prm.log_N;
     const size_t n = (size_t)1 << log_n;
@@ -199,6 +220,8 @@ void bootstrapper_enqueue(vpbs_bootstrapper* b, const uint64_t* d_cts, size_t co
     a.out_ct = d_out_ct;
     a.lwe_out = d_lwe_out;
     a.accs_out = d_accs_out;
+    a.start = d_start;
+    a.acc_in = d_acc_in;
     a.testv_stride = testv_per_ct ? n : 0;
     a.bsk = b->d_bsk;
     a.ksk = b->d_ksk;
@@ -282,6 +305,7 @@ int vpbs_bootstrapper_create(vpbs_ctx* ctx, const vpbs_tfhe_params* prm, unsigne
         b->d_testv = b->alloc(max_batch * n);
         b->d_out = b->alloc(max_batch * K * n);
         b->d_lwe = b->alloc(max_batch * (n_lwe + 1));
+        b->d_start = reinterpret_cast<uint32_t*>(b->alloc((max_batch * sizeof(uint32_t) + 7) / 8));
         (void)ctx->ring_table(log_n);
         VPBS_HIP(vpbs::stream_sync(ctx->stream));   // the caller's key arrays may go away
     } catch (const DeviceError& e) {
@@ -297,20 +321,56 @@ int vpbs_bootstrapper_create(vpbs_ctx* ctx, const vpbs_tfhe_params* prm, unsigne
 
 void vpbs_bootstrapper_free(vpbs_bootstrapper* b) { delete b; }
 
-long vpbs_bootstrapper_run(vpbs_bootstrapper* b, const uint64_t* cts, size_t count, const uint64_t* testv, int testv_per_ct, uint64_t* out_ct,
-                           uint64_t* lwe_out, uint64_t* accs_out, int on_device) {
-    using namespace vpbs;
+}  // extern "C"
+
+namespace vpbs {
+bool check_start_steps(const uint32_t* start, size_t count, unsigned n_lwe, const uint64_t* acc_in, const char* who, std::string* msg) {
+    for (size_t i = 0; i < count; ++i) {
+        if (start[i] > n_lwe + 2) {
+            *msg = std::string(who) + ": start[" + std::to_string(i) + "] = " + std::to_string(start[i]) + " is beyond n_lwe + 2 = " +
+                   std::to_string(n_lwe + 2) + "; ciphertext " + std::to_string(i) + " has no such step, nothing was launched";
+            return false;
+        }
+        if (start[i] && !acc_in) {
+            *msg = std::string(who) + ": start[" + std::to_string(i) + "] = " + std::to_string(start[i]) + " but acc_in is null; nothing was launched";
+            return false;
+        }
+    }
+    return true;
+}
+
+// the rows of a host acc_in that enter late, in runs of neighbours (rows with start 0 are not read)
+void upload_acc_in(vpbs_ctx* ctx, u64* d_acc_in, const uint64_t* acc_in, const uint32_t* start, size_t count, size_t kn) {
+    for (size_t i = 0; i < count;) {
+        if (!start[i]) {
+            ++i;
+            continue;
+        }
+        size_t j = i + 1;
+        while (j < count && start[j]) ++j;
+        VPBS_HIP(hipMemcpyAsync(d_acc_in + i * kn, acc_in + i * kn, sizeof(u64) * (j - i) * kn, hipMemcpyHostToDevice, ctx->stream));
+        i = j;
+    }
+}
+
+namespace {
+// vpbs_bootstrapper_run (start = null) and vpbs_bootstrapper_run_from
+long bootstrapper_run(vpbs_bootstrapper* b, const uint64_t* cts, size_t count, const uint32_t* start, const uint64_t* acc_in, const uint64_t* testv,
+                      int testv_per_ct, uint64_t* out_ct, uint64_t* lwe_out, uint64_t* accs_out, int on_device) {
     if (!b || !cts || !testv || (!out_ct && !lwe_out && !accs_out) || count > b->max_batch) return VPBS_ERR_INVALID;
-    if (count == 0) return 0;
     vpbs_ctx* ctx = b->ctx;
+    // every start step before anything is queued
+    if (start && !check_start_steps(start, count, b->n_lwe, acc_in, "vpbs_bootstrapper_run_from", &ctx->err)) return VPBS_ERR_INVALID;
+    if (count == 0) return 0;
     const unsigned log_n = b->prm.log_N, K = b->prm.K, n_lwe = b->n_lwe;
     const size_t n = (size_t)1 << log_n, kn = K * n, ct_words = n_lwe + 1;
-    u64* d_accs = nullptr;
+    u64 *d_accs = nullptr, *d_acc_stage = nullptr;
     int rc = VPBS_OK;
     try {
         VPBS_HIP(hipSetDevice(ctx->device));
-        const u64 *d_cts = cts, *d_testv = testv;
+        const u64 *d_cts = cts, *d_testv = testv, *d_acc_in = acc_in;
         u64 *d_out_ct = out_ct, *d_lwe_out = lwe_out, *d_accs_out = accs_out;
+        if (start) VPBS_HIP(hipMemcpyAsync(b->d_start, start, sizeof(uint32_t) * count, hipMemcpyHostToDevice, ctx->stream));
         if (!on_device) {
             VPBS_HIP(hipMemcpyAsync(b->d_cts, cts, sizeof(u64) * count * ct_words, hipMemcpyHostToDevice, ctx->stream));
             VPBS_HIP(hipMemcpyAsync(b->d_testv, testv, sizeof(u64) * (testv_per_ct ? count : 1) * n, hipMemcpyHostToDevice, ctx->stream));
@@ -318,9 +378,17 @@ long vpbs_bootstrapper_run(vpbs_bootstrapper* b, const uint64_t* cts, size_t cou
             d_testv = b->d_testv;
             d_out_ct = out_ct ? b->d_out : nullptr;
             d_lwe_out = lwe_out ? b->d_lwe : nullptr;
-            if (accs_out) d_accs_out = d_accs = ctx->alloc_words(count * (n_lwe + 2) * kn);
+            if (accs_out) {
+                d_accs_out = d_accs = ctx->alloc_words(count * (n_lwe + 2) * kn);
+                // a resumed row leaves the slots below its start as the caller has them
+                if (start) VPBS_HIP(hipMemcpyAsync(d_accs, accs_out, sizeof(u64) * count * (n_lwe + 2) * kn, hipMemcpyHostToDevice, ctx->stream));
+            }
+            if (start && acc_in) {
+                d_acc_in = d_acc_stage = ctx->alloc_words(count * kn);
+                upload_acc_in(ctx, d_acc_stage, acc_in, start, count, kn);
+            }
         }
-        bootstrapper_enqueue(b, d_cts, count, d_testv, testv_per_ct, d_out_ct, d_lwe_out, d_accs_out);
+        bootstrapper_enqueue(b, d_cts, count, d_testv, testv_per_ct, d_out_ct, d_lwe_out, d_accs_out, start ? b->d_start : nullptr, start ? d_acc_in : nullptr);
         if (!on_device) {
             if (out_ct) VPBS_HIP(hipMemcpyAsync(out_ct, b->d_out, sizeof(u64) * count * kn, hipMemcpyDeviceToHost, ctx->stream));
             if (lwe_out) VPBS_HIP(hipMemcpyAsync(lwe_out, b->d_lwe, sizeof(u64) * count * ct_words, hipMemcpyDeviceToHost, ctx->stream));
@@ -332,11 +400,25 @@ long vpbs_bootstrapper_run(vpbs_bootstrapper* b, const uint64_t* cts, size_t cou
         ctx->err = e.what;
         rc = e.status == VPBS_ERR_OOM ? VPBS_ERR_OOM : VPBS_ERR_DEVICE;
     }
-    if (d_accs) {
+    if (d_accs || d_acc_stage) {
         (void)vpbs::stream_sync(ctx->stream);
         ctx->release(d_accs);
+        ctx->release(d_acc_stage);
     }
     return rc == VPBS_OK ? (long)count : rc;
+}
+}  // namespace
+}  // namespace vpbs
+
+extern "C" {
+long vpbs_bootstrapper_run(vpbs_bootstrapper* b, const uint64_t* cts, size_t count, const uint64_t* testv, int testv_per_ct, uint64_t* out_ct,
+                           uint64_t* lwe_out, uint64_t* accs_out, int on_device) {
+    return vpbs::bootstrapper_run(b, cts, count, nullptr, nullptr, testv, testv_per_ct, out_ct, lwe_out, accs_out, on_device);
+}
+
+long vpbs_bootstrapper_run_from(vpbs_bootstrapper* b, const uint64_t* cts, size_t count, const uint32_t* start, const uint64_t* acc_in,
+                                const uint64_t* testv, int testv_per_ct, uint64_t* out_ct, uint64_t* lwe_out, uint64_t* accs_out, int on_device) {
+    return vpbs::bootstrapper_run(b, cts, count, start, acc_in, testv, testv_per_ct, out_ct, lwe_out, accs_out, on_device);
 }
 
 int vpbs_lwe_extract(vpbs_ctx* ctx, unsigned log_N, unsigned K, unsigned n_lwe, const uint64_t* glwe, size_t count, uint64_t* lwe_out,

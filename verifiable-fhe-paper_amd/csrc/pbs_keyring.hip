@@ -42,6 +42,9 @@ struct PbsKeyringArgs {
     u64* lwe_out;            // [count][n_lwe + 1] or null
     u64* accs_out;           // [count][n_lwe + 2][K][N] or null
     unsigned log_n, K, ELL, LOGB, n_lwe;
+    // the start mode, behind everything else: the fields above keep the offsets the kernels without it (FROM = false) were compiled for
+    const uint32_t* start;   // [count] or null: ciphertext c enters the chain at step start[c] (0: from the rotated test vector)
+    const u64* acc_in;       // [count][K][N] or null: the accumulator after step start[c] - 1 of the ciphertexts that enter late
 };
 
 // Request the rows g[p][l][.] at this thread's points into pf: entry trip * ELL + l for the trip-th pair of points.  Branch-free, so that
@@ -61,7 +64,8 @@ __device__ __forceinline__ void kr_prefetch(ulonglong2 (&pf)[PF ? PF : 1], const
 
 // One workgroup per ciphertext.  PF: 16-byte key words a thread holds ahead per input polynomial, chosen by the host as the smallest of
 // 4 and 8 that covers ELL * ceil(K N / (2 T)) (4 at the paper's shape with 1024 threads, 8 with 512); 0: no room, read in the loop.
-template <unsigned T, unsigned PF>
+// FROM: the start mode (a.start, a.acc_in), an instantiation of its own as in pbs_batch_kernel.
+template <unsigned T, unsigned PF, bool FROM>
 __global__ void __launch_bounds__(T) pbs_keyring_kernel(PbsKeyringArgs a) {
     extern __shared__ __align__(16) u64 lds[];
     const unsigned log_n = a.log_n, n = 1u << log_n, K = a.K, ELL = a.ELL, LOGB = a.LOGB, n_lwe = a.n_lwe;
@@ -79,10 +83,21 @@ __global__ void __launch_bounds__(T) pbs_keyring_kernel(PbsKeyringArgs a) {
     const unsigned nl = (64 + LOGB - 1) / LOGB, tb = nl * LOGB;
     constexpr bool ahead = PF != 0;
     ulonglong2 pf[PF ? PF : 1];
+    // the step this ciphertext enters at (pbs_batch_kernel): uniform over the workgroup
+    const unsigned k0 = FROM ? a.start[b] : 0;
+    const unsigned first = FROM && k0 ? k0 : 1;
 
-    // step 0: acc_init = (0, .., 0, testv) rotated by -body (ivc_based_vpbs.rs:106-111,122)
-    if constexpr (ahead) kr_prefetch<T, PF>(pf, key.bsk, kn, ELL);
-    {
+    // the rows of the first step that runs, ahead of the accumulator's load (k0 = n_lwe + 2 runs no step: the rows of ksk, never used)
+    if constexpr (ahead) kr_prefetch<T, PF>(pf, FROM && first > n_lwe ? key.ksk : key.bsk + (size_t)(first - 1) * ggsw_words, kn, ELL);
+    if (FROM && k0) {   // a resumed ciphertext: the accumulator after step k0 - 1 (slots below k0 - 1 are not written)
+        const u64* in = a.acc_in + b * kn;
+        u64* slot = accs ? accs + (size_t)(k0 - 1) * kn : nullptr;
+        for (unsigned idx = threadIdx.x; idx < kn; idx += T) {
+            const u64 v = in[idx];
+            acc[idx] = v;
+            if (slot) slot[idx] = v;
+        }
+    } else {   // step 0: acc_init = (0, .., 0, testv) rotated by -body (ivc_based_vpbs.rs:106-111,122)
         const unsigned shift = pb_mod_switch(gl::neg(ct[n_lwe]), log_n);
         for (unsigned idx = threadIdx.x; idx < kn; idx += T) {
             const unsigned i = idx & (n - 1);
@@ -93,7 +108,7 @@ __global__ void __launch_bounds__(T) pbs_keyring_kernel(PbsKeyringArgs a) {
     }
     __syncthreads();
 
-    for (unsigned step = 1; step <= n_lwe + 1; ++step) {
+    for (unsigned step = first; step <= n_lwe + 1; ++step) {
         const bool last = step == n_lwe + 1;
         const u64* g = last ? key.ksk : key.bsk + (size_t)(step - 1) * ggsw_words;
         const unsigned shift = last ? 0 : pb_mod_switch(ct[step - 1], log_n);
@@ -182,13 +197,19 @@ __global__ void __launch_bounds__(T) pbs_keyring_kernel(PbsKeyringArgs a) {
     }
 }
 
-template <unsigned T, unsigned PF>
-void launch_pbs_keyring_pf(hipStream_t s, const PbsKeyringArgs& a, size_t count, size_t lds_bytes) {
+template <unsigned T, unsigned PF, bool FROM>
+void launch_pbs_keyring_from(hipStream_t s, const PbsKeyringArgs& a, size_t count, size_t lds_bytes) {
     // a workgroup's dynamic LDS above the default limit is announced once per kernel
-    static const hipError_t announced = hipFuncSetAttribute(reinterpret_cast<const void*>(&pbs_keyring_kernel<T, PF>),
+    static const hipError_t announced = hipFuncSetAttribute(reinterpret_cast<const void*>(&pbs_keyring_kernel<T, PF, FROM>),
                                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)PBS_LDS_BUDGET);
     if (announced != hipSuccess) (void)hipGetLastError();   // the launch below reports what matters
-    hipLaunchKernelGGL((pbs_keyring_kernel<T, PF>), dim3((unsigned)count), dim3(T), lds_bytes, s, a);
+    hipLaunchKernelGGL((pbs_keyring_kernel<T, PF, FROM>), dim3((unsigned)count), dim3(T), lds_bytes, s, a);
+}
+
+template <unsigned T, unsigned PF>
+void launch_pbs_keyring_pf(hipStream_t s, const PbsKeyringArgs& a, size_t count, size_t lds_bytes) {
+    if (a.start) launch_pbs_keyring_from<T, PF, true>(s, a, count, lds_bytes);
+    else launch_pbs_keyring_from<T, PF, false>(s, a, count, lds_bytes);
 }
 
 template <unsigned T>
@@ -233,7 +254,7 @@ struct vpbs_keyring {
     std::vector<Slot> slots;
     size_t used = 0;
     vpbs::KeySlot* d_table = nullptr;   // [max_keys]
-    uint32_t* d_index = nullptr;        // order [max_batch] | key_of [max_batch]
+    uint32_t* d_index = nullptr;        // order [max_batch] | key_of [max_batch] | start [max_batch]
     std::vector<uint32_t> h_index, sort_start;
     u64 *d_cts = nullptr, *d_testv = nullptr, *d_out = nullptr, *d_lwe = nullptr;   // staging for host callers
     std::vector<void*> owned;
@@ -274,7 +295,8 @@ bool keyring_check_slots(const vpbs_keyring* r, const uint32_t* key_of, size_t c
 }
 
 void keyring_enqueue(vpbs_keyring* r, const uint64_t* d_cts, size_t count, const uint64_t* d_testv, int testv_per_ct, const uint32_t* d_order,
-                     const uint32_t* d_key_of, uint64_t* d_out_ct, uint64_t* d_lwe_out, uint64_t* d_accs_out) {
+                     const uint32_t* d_key_of, uint64_t* d_out_ct, uint64_t* d_lwe_out, uint64_t* d_accs_out, const uint32_t* d_start,
+                     const uint64_t* d_acc_in) {
     vpbs_ctx* ctx = r->ctx;
     const unsigned log_n = r->prm.log_N;
     const size_t n = (size_t)1 << log_n;
@@ -290,6 +312,8 @@ void keyring_enqueue(vpbs_keyring* r, const uint64_t* d_cts, size_t count, const
     a.out_ct = d_out_ct;
     a.lwe_out = d_lwe_out;
     a.accs_out = d_accs_out;
+    a.start = d_start;
+    a.acc_in = d_acc_in;
     a.log_n = log_n;
     a.K = r->prm.K;
     a.ELL = r->prm.ELL;
@@ -353,7 +377,7 @@ int vpbs_keyring_create(vpbs_ctx* ctx, const vpbs_tfhe_params* prm, unsigned n_l
         VPBS_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
         if (cus > 0) r->cus = (unsigned)cus;
         r->d_table = reinterpret_cast<KeySlot*>(r->alloc((max_keys * sizeof(KeySlot) + 7) / 8));
-        r->d_index = reinterpret_cast<uint32_t*>(r->alloc((2 * max_batch * sizeof(uint32_t) + 7) / 8));
+        r->d_index = reinterpret_cast<uint32_t*>(r->alloc((3 * max_batch * sizeof(uint32_t) + 7) / 8));
         VPBS_HIP(hipMemsetAsync(r->d_table, 0, max_keys * sizeof(KeySlot), ctx->stream));
         r->d_cts = r->alloc(max_batch * (n_lwe + 1));
         r->d_testv = r->alloc(max_batch * n);
@@ -478,18 +502,24 @@ size_t vpbs_keyring_count(vpbs_keyring* r) {
     return r->used;
 }
 
-long vpbs_keyring_run(vpbs_keyring* r, const uint64_t* cts, size_t count, const uint32_t* key_of, const uint64_t* testv, int testv_per_ct,
-                      uint64_t* out_ct, uint64_t* lwe_out, uint64_t* accs_out, int on_device) {
-    using namespace vpbs;
+}  // extern "C"
+
+namespace vpbs {
+namespace {
+// vpbs_keyring_run (start = null) and vpbs_keyring_run_from
+long keyring_run(vpbs_keyring* r, const uint64_t* cts, size_t count, const uint32_t* key_of, const uint32_t* start, const uint64_t* acc_in,
+                 const uint64_t* testv, int testv_per_ct, uint64_t* out_ct, uint64_t* lwe_out, uint64_t* accs_out, int on_device) {
     if (!r) return VPBS_ERR_INVALID;
     std::lock_guard<std::mutex> lock(r->mu);
     vpbs_ctx* ctx = r->ctx;
+    const char* who = start ? "vpbs_keyring_run_from" : "vpbs_keyring_run";
     if (!cts || !testv || (!out_ct && !lwe_out && !accs_out) || count > r->max_batch || (count && !key_of)) {
-        ctx->err = "vpbs_keyring_run: null cts / testv / key_of, no output, or count above max_batch";
+        ctx->err = std::string(who) + ": null cts / testv / key_of, no output, or count above max_batch";
         return VPBS_ERR_INVALID;
     }
-    // every index before anything is queued
-    if (!keyring_check_slots(r, key_of, count, "vpbs_keyring_run", "ciphertext", &ctx->err)) return VPBS_ERR_INVALID;
+    // every index and every start step before anything is queued
+    if (!keyring_check_slots(r, key_of, count, who, "ciphertext", &ctx->err)) return VPBS_ERR_INVALID;
+    if (start && !check_start_steps(start, count, r->n_lwe, acc_in, who, &ctx->err)) return VPBS_ERR_INVALID;
     if (count == 0) return 0;
     const unsigned log_n = r->prm.log_N, K = r->prm.K, n_lwe = r->n_lwe;
     const size_t n = (size_t)1 << log_n, kn = K * n, ct_words = n_lwe + 1;
@@ -497,14 +527,16 @@ long vpbs_keyring_run(vpbs_keyring* r, const uint64_t* cts, size_t count, const 
     uint32_t* h_key_of = h_order + r->max_batch;
     keyring_order(key_of, count, r->max_keys, r->sort_start, h_order);
     std::memcpy(h_key_of, key_of, count * sizeof(uint32_t));
-    u64* d_accs = nullptr;
+    u64 *d_accs = nullptr, *d_acc_stage = nullptr;
+    uint32_t* d_start = r->d_index + 2 * r->max_batch;
     int rc = VPBS_OK;
     try {
         VPBS_HIP(hipSetDevice(ctx->device));
-        const u64 *d_cts = cts, *d_testv = testv;
+        const u64 *d_cts = cts, *d_testv = testv, *d_acc_in = acc_in;
         u64 *d_out_ct = out_ct, *d_lwe_out = lwe_out, *d_accs_out = accs_out;
         VPBS_HIP(hipMemcpyAsync(r->d_index, h_order, sizeof(uint32_t) * count, hipMemcpyHostToDevice, ctx->stream));
         VPBS_HIP(hipMemcpyAsync(r->d_index + r->max_batch, h_key_of, sizeof(uint32_t) * count, hipMemcpyHostToDevice, ctx->stream));
+        if (start) VPBS_HIP(hipMemcpyAsync(d_start, start, sizeof(uint32_t) * count, hipMemcpyHostToDevice, ctx->stream));
         if (!on_device) {
             VPBS_HIP(hipMemcpyAsync(r->d_cts, cts, sizeof(u64) * count * ct_words, hipMemcpyHostToDevice, ctx->stream));
             VPBS_HIP(hipMemcpyAsync(r->d_testv, testv, sizeof(u64) * (testv_per_ct ? count : 1) * n, hipMemcpyHostToDevice, ctx->stream));
@@ -512,9 +544,18 @@ long vpbs_keyring_run(vpbs_keyring* r, const uint64_t* cts, size_t count, const 
             d_testv = r->d_testv;
             d_out_ct = out_ct ? r->d_out : nullptr;
             d_lwe_out = lwe_out ? r->d_lwe : nullptr;
-            if (accs_out) d_accs_out = d_accs = ctx->alloc_words(count * (n_lwe + 2) * kn);
+            if (accs_out) {
+                d_accs_out = d_accs = ctx->alloc_words(count * (n_lwe + 2) * kn);
+                // a resumed row leaves the slots below its start as the caller has them
+                if (start) VPBS_HIP(hipMemcpyAsync(d_accs, accs_out, sizeof(u64) * count * (n_lwe + 2) * kn, hipMemcpyHostToDevice, ctx->stream));
+            }
+            if (start && acc_in) {
+                d_acc_in = d_acc_stage = ctx->alloc_words(count * kn);
+                upload_acc_in(ctx, d_acc_stage, acc_in, start, count, kn);
+            }
         }
-        keyring_enqueue(r, d_cts, count, d_testv, testv_per_ct, r->d_index, r->d_index + r->max_batch, d_out_ct, d_lwe_out, d_accs_out);
+        keyring_enqueue(r, d_cts, count, d_testv, testv_per_ct, r->d_index, r->d_index + r->max_batch, d_out_ct, d_lwe_out, d_accs_out,
+                        start ? d_start : nullptr, start ? d_acc_in : nullptr);
         if (!on_device) {
             if (out_ct) VPBS_HIP(hipMemcpyAsync(out_ct, r->d_out, sizeof(u64) * count * kn, hipMemcpyDeviceToHost, ctx->stream));
             if (lwe_out) VPBS_HIP(hipMemcpyAsync(lwe_out, r->d_lwe, sizeof(u64) * count * ct_words, hipMemcpyDeviceToHost, ctx->stream));
@@ -526,10 +567,24 @@ long vpbs_keyring_run(vpbs_keyring* r, const uint64_t* cts, size_t count, const 
         ctx->err = e.what;
         rc = e.status == VPBS_ERR_OOM ? VPBS_ERR_OOM : VPBS_ERR_DEVICE;
     }
-    if (d_accs) {
+    if (d_accs || d_acc_stage) {
         (void)vpbs::stream_sync(ctx->stream);
         ctx->release(d_accs);
+        ctx->release(d_acc_stage);
     }
     return rc == VPBS_OK ? (long)count : rc;
+}
+}  // namespace
+}  // namespace vpbs
+
+extern "C" {
+long vpbs_keyring_run(vpbs_keyring* r, const uint64_t* cts, size_t count, const uint32_t* key_of, const uint64_t* testv, int testv_per_ct,
+                      uint64_t* out_ct, uint64_t* lwe_out, uint64_t* accs_out, int on_device) {
+    return vpbs::keyring_run(r, cts, count, key_of, nullptr, nullptr, testv, testv_per_ct, out_ct, lwe_out, accs_out, on_device);
+}
+
+long vpbs_keyring_run_from(vpbs_keyring* r, const uint64_t* cts, size_t count, const uint32_t* key_of, const uint32_t* start, const uint64_t* acc_in,
+                           const uint64_t* testv, int testv_per_ct, uint64_t* out_ct, uint64_t* lwe_out, uint64_t* accs_out, int on_device) {
+    return vpbs::keyring_run(r, cts, count, key_of, start, acc_in, testv, testv_per_ct, out_ct, lwe_out, accs_out, on_device);
 }
 }  // extern "C"

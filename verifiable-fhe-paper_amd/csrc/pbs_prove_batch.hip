@@ -112,8 +112,10 @@ int vpbs_pbs_prover_create(int device_ordinal, const vpbs_ivc_circuit* cyclic, c
     // the key source: one key set for every ciphertext, accumulators from a count-1 run of the Bootstrapper
     vpbs_pbs_prover* self = p.get();
     pool.keys_of = [self](size_t) { return self->keys; };
-    pool.accumulators = [self](ProvePool::Worker& w, std::string& why) {
-        if (vpbs_bootstrapper_run(self->boot, w.d_ct, 1, w.d_testv, 0, nullptr, nullptr, w.d_accs, 1) == 1) return true;
+    pool.accumulators = [self](ProvePool::Worker& w, unsigned from, std::string& why) {
+        const uint32_t start = from;
+        if (vpbs_bootstrapper_run_from(self->boot, w.d_ct, 1, from ? &start : nullptr, w.d_acc_in, w.d_testv, 0, nullptr, nullptr, w.d_accs, 1) == 1)
+            return true;
         why = vpbs_last_error(self->boot_ctx);
         return false;
     };
@@ -154,9 +156,14 @@ int vpbs_pbs_prover_set_checkpoint(vpbs_pbs_prover* p, unsigned every, vpbs_pbs_
     return VPBS_OK;
 }
 
-long vpbs_pbs_prover_run(vpbs_pbs_prover* p, const uint64_t* cts, size_t count, const uint64_t* testv, int testv_per_ct, unsigned steps,
-                         uint64_t* out_ct, uint64_t* lwe_out, vpbs_pbs_proof_fn proof_fn, void* user, char* err, size_t err_len) {
-    using namespace vpbs;
+}  // extern "C"
+
+namespace vpbs {
+namespace {
+// vpbs_pbs_prover_run (checkpoints = null) and vpbs_pbs_prover_resume
+long pbs_prover_run(vpbs_pbs_prover* p, const uint64_t* cts, size_t count, const uint64_t* testv, int testv_per_ct, const uint8_t* const* checkpoints,
+                    const size_t* lens, unsigned steps, uint64_t* out_ct, uint64_t* lwe_out, vpbs_pbs_proof_fn proof_fn, void* user, char* err,
+                    size_t err_len) {
     auto refuse = [&](const std::string& m) {
         report(err, err_len, m);
         return (long)VPBS_ERR_INVALID;
@@ -164,6 +171,7 @@ long vpbs_pbs_prover_run(vpbs_pbs_prover* p, const uint64_t* cts, size_t count, 
     report(err, err_len, "");
     if (!proof_fn) return refuse("no proof_fn: the proofs have nowhere to go");
     if (count && (!cts || !testv)) return refuse("null cts or testv");
+    if (count && checkpoints && !lens) return refuse("checkpoints without lens");
     if (!p) return refuse("null prover");
     ProvePool& pool = p->pool;
     if (steps > pool.total) return refuse("steps exceeds n_lwe + 2 = " + std::to_string(pool.total));
@@ -173,22 +181,43 @@ long vpbs_pbs_prover_run(vpbs_pbs_prover* p, const uint64_t* cts, size_t count, 
     pool.stats = vpbs_pbs_run_stats{};
     const unsigned N = pool.shape.N;
     const size_t kn = pool.shape.kn, ct_words = pool.n_lwe + 1;
-    // ---- every output first: one Bootstrapper launch per BOOT_BATCH ciphertexts ----
+    // ---- a resume: every checkpoint validated on the host before anything is queued ----
+    ProvePool::Resume rs;
+    if (checkpoints) pool.open_checkpoints(cts, count, testv, testv_per_ct, checkpoints, lens, steps, rs);
+    // ---- every output first: one Bootstrapper launch per BOOT_BATCH ciphertexts; accepted rows enter at their checkpoint's step ----
     if (out_ct || lwe_out) {
         std::lock_guard<std::mutex> lk(pool.boot_mu);
+        std::vector<uint32_t> start;
+        std::vector<u64> acc_in;
         for (size_t i0 = 0; i0 < count; i0 += vpbs_pbs_prover::BOOT_BATCH) {
             const size_t c = std::min(vpbs_pbs_prover::BOOT_BATCH, count - i0);
-            const long rc = vpbs_bootstrapper_run(p->boot, cts + i0 * ct_words, c, testv + (testv_per_ct ? i0 * N : 0), testv_per_ct,
-                                                  out_ct ? out_ct + i0 * kn : nullptr, lwe_out ? lwe_out + i0 * ct_words : nullptr, nullptr, 0);
+            const bool from = rs.resumed && pool.start_rows(rs, i0, c, start, acc_in);
+            const long rc = vpbs_bootstrapper_run_from(p->boot, cts + i0 * ct_words, c, from ? start.data() : nullptr, from ? acc_in.data() : nullptr,
+                                                       testv + (testv_per_ct ? i0 * N : 0), testv_per_ct, out_ct ? out_ct + i0 * kn : nullptr,
+                                                       lwe_out ? lwe_out + i0 * ct_words : nullptr, nullptr, 0);
             if (rc != (long)c) {
-                report(err, err_len, std::string("vpbs_bootstrapper_run: ") + vpbs_last_error(p->boot_ctx));
+                report(err, err_len, std::string(from ? "vpbs_bootstrapper_run_from: " : "vpbs_bootstrapper_run: ") + vpbs_last_error(p->boot_ctx));
                 return rc < 0 ? rc : (long)VPBS_ERR_DEVICE;
             }
         }
     }
     // ---- the proofs: the pool's workers take ciphertext indices from a queue ----
     pool.stats.outputs_seconds = out_ct || lwe_out ? now_s() - t_call : 0.0;
-    return pool.prove(cts, count, testv, testv_per_ct, steps, t_call, proof_fn, user);
+    return pool.prove(cts, count, testv, testv_per_ct, steps, t_call, proof_fn, user, checkpoints ? &rs : nullptr);
+}
+}  // namespace
+}  // namespace vpbs
+
+extern "C" {
+long vpbs_pbs_prover_run(vpbs_pbs_prover* p, const uint64_t* cts, size_t count, const uint64_t* testv, int testv_per_ct, unsigned steps,
+                         uint64_t* out_ct, uint64_t* lwe_out, vpbs_pbs_proof_fn proof_fn, void* user, char* err, size_t err_len) {
+    return vpbs::pbs_prover_run(p, cts, count, testv, testv_per_ct, nullptr, nullptr, steps, out_ct, lwe_out, proof_fn, user, err, err_len);
+}
+
+long vpbs_pbs_prover_resume(vpbs_pbs_prover* p, const uint64_t* cts, size_t count, const uint64_t* testv, int testv_per_ct,
+                            const uint8_t* const* checkpoints, const size_t* lens, unsigned steps, uint64_t* out_ct, uint64_t* lwe_out,
+                            vpbs_pbs_proof_fn proof_fn, void* user, char* err, size_t err_len) {
+    return vpbs::pbs_prover_run(p, cts, count, testv, testv_per_ct, checkpoints, lens, steps, out_ct, lwe_out, proof_fn, user, err, err_len);
 }
 
 int vpbs_pbs_prover_last_run(const vpbs_pbs_prover* p, vpbs_pbs_run_stats* out) {

@@ -17,6 +17,11 @@
 //
 // -- so neither the 16 384 words of bsk[s] per step nor anything else of the matrix is stored by a host thread or crosses PCIe.
 //
+// A RESUMED chain (vpbs_pbs_prover_resume, vpbs_ring_prover_resume) enters this at step k of its checkpoint: open_checkpoints validates every
+// checkpoint on the host before anything is queued (the key hash against the resident link k - 1: the pool holds every link, so no key
+// chain is walked), the key source leaves accumulators k - 1 .. n + 1 through the kernels' start mode, and ivc_prove_pbs_resident goes on
+// at step k with the checkpoint's proof words and public inputs; the table above is read at rows s >= k only.
+//
 // The pool is parameterised by its key source: which resident key set (device bsk and ksk, the key hash chain on the host and on the
 // device) the chain of ciphertext i is proven under, and a function that leaves that ciphertext's accumulators on the device.  One key set
 // and a Bootstrapper: vpbs_pbs_prover (pbs_prove_batch.hip).  The slot key_of[i] of a key ring: vpbs_ring_prover (pbs_prove_ring.hip).
@@ -158,6 +163,7 @@ struct ProvePool {
         vpbs_ctx* ctx = nullptr;
         vpbs_ivc* ivc = nullptr;
         u64 *d_accs = nullptr, *d_lwe_links = nullptr, *d_ct = nullptr, *d_testv = nullptr;   // device (the bootstrap context's pool)
+        u64* d_acc_in = nullptr;   // device [K N]: a resumed chain's accumulator after step k - 1, from its checkpoint
         u64* accs = nullptr;   // pinned host [n_lwe + 2][K N]
         std::vector<u64> lwe_links;
         std::vector<uint8_t> proof;
@@ -176,13 +182,25 @@ struct ProvePool {
     // ---- the key source (set by the owner before the first chain) ----
     std::function<KeySource(size_t index)> keys_of;   // the key set of ciphertext `index` of the run
     // w.d_ct and w.d_testv are queued on boot_ctx's stream: leave the n + 2 accumulators of that ciphertext in w.d_accs, complete or queued on
-    // the same stream; false with a message otherwise.  Called under boot_mu.
-    std::function<bool(Worker& w, std::string& why)> accumulators;
+    // the same stream; false with a message otherwise.  from > 0 (a resumed chain): w.d_acc_in is queued too and holds the accumulator after
+    // step from - 1; a count-1 run_from leaves slots from - 1 .. n + 1, the slots below keep the worker's previous chain and are read by
+    // nobody (preset_*_kernel for step s >= from reads entry s - 1 >= from - 1 only).  Called under boot_mu.
+    std::function<bool(Worker& w, unsigned from, std::string& why)> accumulators;
     // ---- a run ----
     std::mutex cb_mu;                // callbacks never two at once
     vpbs_pbs_run_stats stats{};      // of the last run
     vpbs_pbs_checkpoint_fn ckpt_fn = nullptr;
     void* ckpt_user = nullptr;
+    // the checkpoints of a resume, row by row: opened[i].k = 0 for a row that starts at step 0 (none given, or refused); refused[i] is the
+    // message of a refused one ("checkpoint: <why>"), empty otherwise
+    struct Resume {
+        const uint8_t* const* bytes = nullptr;
+        const size_t* lens = nullptr;
+        std::vector<IvcCheckpoint> opened;
+        std::vector<std::string> refused;
+        size_t resumed = 0;   // rows accepted
+        const u64* acc_of(size_t i, size_t kn) const { return opened[i].pis.data() + kn + 1; }
+    };
 
     // the chains: what tools/prove_ivc.py builds per chain.  boot_ctx is set; VPBS_OK, or a status with a message
     int create_chains(const vpbs_ivc_circuit* cyclic, const vpbs_ivc_circuit* dummy, const vpbs_tfhe_params* prm, unsigned chains,
@@ -226,6 +244,7 @@ struct ProvePool {
             w.d_lwe_links = alloc(4 * (size_t)total);
             w.d_ct = alloc(n_lwe + 1);
             w.d_testv = alloc(sh.N);
+            w.d_acc_in = alloc(sh.kn);
             if (!(w.accs = static_cast<u64*>(vpbs_host_alloc(8 * (size_t)total * sh.kn)))) throw DeviceError{VPBS_ERR_OOM, "out of pinned memory"};
             w.lwe_links.resize(4 * (size_t)total);
             w.proof.resize(max_bytes);
@@ -258,7 +277,9 @@ struct ProvePool {
     }
     // the chain's public inputs where ivc_prove_pbs_resident wants them: accumulators on the device (the key source, this worker's buffer) and
     // on the host (one copy of (n + 2) K N words), the LWE hash chain on both.  Under boot_mu, on the bootstrap context's stream.
-    int prepare_chain(Worker& w, const u64* ct, const u64* testv, std::string& why) {
+    // from > 0: a resumed chain; acc_from [K N] (host) is the accumulator after step from - 1, and only entries from - 1 .. n + 1 of the
+    // accumulators are made and copied.  The LWE links are walked from 0 all the same (730 permutations).
+    int prepare_chain(Worker& w, const u64* ct, const u64* testv, std::string& why, unsigned from = 0, const u64* acc_from = nullptr) {
         const size_t kn = shape.kn;
         w.keys = keys_of(w.index);
         u64 in[5] = {0, 0, 0, 0, 0}, h[4];   // verify_hash_output's chain: h_s = hash_no_pad(h_{s-1} || mask_s), masks ct[n], ct[0] .. ct[n-1], 0
@@ -275,9 +296,11 @@ struct ProvePool {
             VPBS_HIP(hipMemcpyAsync(w.d_ct, ct, 8 * (size_t)(n_lwe + 1), hipMemcpyHostToDevice, s));
             VPBS_HIP(hipMemcpyAsync(w.d_testv, testv, 8 * (size_t)shape.N, hipMemcpyHostToDevice, s));
             VPBS_HIP(hipMemcpyAsync(w.d_lwe_links, w.lwe_links.data(), 8 * w.lwe_links.size(), hipMemcpyHostToDevice, s));
+            if (from) VPBS_HIP(hipMemcpyAsync(w.d_acc_in, acc_from, 8 * kn, hipMemcpyHostToDevice, s));
             std::string what;
-            if (!accumulators(w, what)) throw DeviceError{VPBS_ERR_DEVICE, "accumulators of the chain: " + what};
-            VPBS_HIP(hipMemcpyAsync(w.accs, w.d_accs, 8 * (size_t)total * kn, hipMemcpyDeviceToHost, s));
+            if (!accumulators(w, from, what)) throw DeviceError{VPBS_ERR_DEVICE, "accumulators of the chain: " + what};
+            const size_t lo = from ? from - 1 : 0;   // the first entry this chain reads
+            VPBS_HIP(hipMemcpyAsync(w.accs + lo * kn, w.d_accs + lo * kn, 8 * ((size_t)total - lo) * kn, hipMemcpyDeviceToHost, s));
             VPBS_HIP(vpbs::stream_sync(s));
             return VPBS_OK;
         } catch (const DeviceError& e) {
@@ -318,10 +341,63 @@ struct ProvePool {
         ckpt_user = user;
         for (auto& w : workers) (void)vpbs_ivc_set_checkpoint(w.ivc, fn ? every : 0, fn ? &ProvePool::on_checkpoint : nullptr, &w);
     }
+    // The checkpoints of a resume, validated on the host before anything is queued, the rows spread over the worker threads (each uses its
+    // own chain's vpbs_ivc, read-only): ivc_open_checkpoint (the prefix form of verify_pbs against the object's own verifier data, LWE hash
+    // chain included), the counter against `steps`, then the key hash against link k - 1 of the row's resident key set -- one 32-byte
+    // compare; no key chain is walked.  keys_of must answer for the run already.
+    void open_checkpoints(const u64* cts, size_t count, const u64* testv, int testv_per_ct, const uint8_t* const* checkpoints, const size_t* lens,
+                          unsigned steps, Resume& rs) {
+        const unsigned last = steps == 0 || steps > total ? total : steps;
+        rs.bytes = checkpoints;
+        rs.lens = lens;
+        rs.opened.assign(count, IvcCheckpoint{});
+        rs.refused.assign(count, std::string());
+        rs.resumed = 0;
+        if (!checkpoints) return;
+        std::vector<size_t> rows;
+        for (size_t i = 0; i < count; ++i)
+            if (checkpoints[i]) rows.push_back(i);
+        const size_t n_threads = std::min(rows.size(), workers.size());
+        auto work = [&](size_t t) {
+            (void)pthread_setname_np(pthread_self(), "vpbs-ckpt");
+            for (size_t r = t; r < rows.size(); r += n_threads) {
+                const size_t i = rows[r];
+                IvcCheckpoint& cp = rs.opened[i];
+                std::string why;
+                if (!ivc_open_checkpoint(workers[t].ivc, testv + (testv_per_ct ? i * shape.N : 0), cts + i * (n_lwe + 1), n_lwe, checkpoints[i],
+                                         lens ? lens[i] : 0, &cp, &why)) {
+                    rs.refused[i] = "checkpoint: " + why;
+                } else if (cp.k > last) {
+                    rs.refused[i] = "checkpoint: its counter " + std::to_string(cp.k) + " is beyond the requested " + std::to_string(last) + " steps";
+                } else if (std::memcmp(cp.pis.data() + 2 * shape.kn + 1, keys_of(i).key_links + 4 * (size_t)(cp.k - 1), 32) != 0) {
+                    rs.refused[i] = "checkpoint: the key hash chain does not match";
+                }
+                if (!rs.refused[i].empty()) cp = IvcCheckpoint{};   // the row starts at step 0 for its outputs and is not proven
+            }
+        };
+        std::vector<std::thread> threads;
+        for (size_t t = 0; t < n_threads; ++t) threads.emplace_back(work, t);
+        for (auto& t : threads) t.join();
+        for (size_t i = 0; i < count; ++i) rs.resumed += rs.opened[i].k != 0;
+    }
+    // start [c] and acc_in [c][K N] of the rows i0 .. i0 + c of a resume for a run_from launch; false when none of them is resumed
+    bool start_rows(const Resume& rs, size_t i0, size_t c, std::vector<uint32_t>& start, std::vector<u64>& acc_in) const {
+        bool any = false;
+        start.assign(c, 0);
+        for (size_t i = 0; i < c; ++i)
+            if ((start[i] = rs.opened[i0 + i].k) != 0) any = true;
+        if (!any) return false;
+        acc_in.resize(c * shape.kn);   // rows that start at 0 are not read
+        for (size_t i = 0; i < c; ++i)
+            if (start[i]) std::memcpy(acc_in.data() + i * shape.kn, rs.acc_of(i0 + i, shape.kn), 8 * shape.kn);
+        return true;
+    }
     // the proofs of a run whose outputs are complete (stats.outputs_seconds is set; t_call: when the owner's run began): workers take
     // ciphertext indices from a queue; one that fails reports and takes the next, nobody waits for anybody.  Returns the proofs delivered.
+    // rs (a resume): a refused row reports its message and is not proven; an accepted one goes on at its checkpoint's step.
     long prove(const u64* cts, size_t count, const u64* testv, int testv_per_ct, unsigned steps, double t_call, vpbs_pbs_proof_fn proof_fn,
-               void* user) {
+               void* user, const Resume* rs = nullptr) {
+        const unsigned last = steps == 0 || steps > total ? total : steps;
         const unsigned N = shape.N;
         const size_t ct_words = n_lwe + 1;
         std::mutex q_mu;
@@ -338,20 +414,36 @@ struct ProvePool {
                     w.index = next++;
                 }
                 const u64 *ct = cts + w.index * ct_words, *tv = testv + (testv_per_ct ? w.index * N : 0);
+                if (rs && !rs->refused[w.index].empty()) {   // exactly once, and nothing queued for the row
+                    std::lock_guard<std::mutex> lk(cb_mu);
+                    proof_fn(user, w.index, nullptr, 0, rs->refused[w.index].c_str());
+                    continue;
+                }
+                const IvcCheckpoint* cp = rs && rs->opened[w.index].k ? &rs->opened[w.index] : nullptr;
+                const unsigned from = cp ? cp->k : 0;
                 std::string why;
-                const double t_prepare = now_s();
-                long n = prepare_chain(w, ct, tv, why);
-                const double d_prepare = now_s() - t_prepare;
+                const uint8_t* bytes = w.proof.data();
+                long n = VPBS_OK;
+                double d_prepare = 0;
                 vpbs_ivc_timing t{};
-                if (n == VPBS_OK) {
-                    const IvcResidentChain chain{w.accs, w.keys.key_links, w.lwe_links.data(), &ProvePool::fill, &w};
-                    char e[512] = {0};
-                    n = ivc_prove_pbs_resident(w.ivc, tv, ct, n_lwe, &chain, steps, w.proof.data(), w.proof.size(), &t, e, sizeof e);
-                    if (n <= 0) why = e;
+                if (cp && from == last) {   // nothing to prove: the validated checkpoint itself
+                    bytes = rs->bytes[w.index];
+                    n = (long)rs->lens[w.index];
+                } else {
+                    const double t_prepare = now_s();
+                    n = prepare_chain(w, ct, tv, why, from, cp ? rs->acc_of(w.index, shape.kn) : nullptr);
+                    d_prepare = now_s() - t_prepare;
+                    if (n == VPBS_OK) {
+                        const IvcResidentChain chain{w.accs, w.keys.key_links, w.lwe_links.data(), &ProvePool::fill, &w};
+                        char e[512] = {0};
+                        n = ivc_prove_pbs_resident(w.ivc, tv, ct, n_lwe, &chain, from, cp ? cp->proof.data() : nullptr, cp ? cp->pis.data() : nullptr,
+                                                   steps, w.proof.data(), w.proof.size(), &t, e, sizeof e);
+                        if (n <= 0) why = e;
+                    }
                 }
                 std::lock_guard<std::mutex> lk(cb_mu);
                 if (n > 0) {
-                    proof_fn(user, w.index, w.proof.data(), (size_t)n, nullptr);
+                    proof_fn(user, w.index, bytes, (size_t)n, nullptr);
                     ++delivered;
                     prepare_s += d_prepare;
                     sum.seconds += t.seconds; sum.steps = t.steps; sum.base_proof_ms += t.base_proof_ms; sum.late_witness_ms += t.late_witness_ms;

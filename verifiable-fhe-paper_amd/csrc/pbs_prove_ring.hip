@@ -48,7 +48,9 @@ namespace vpbs {
 std::mutex& ring_prover_mutex(vpbs_ring_prover* p) { return p->run_mu; }
 
 long ring_prover_run_locked(vpbs_ring_prover* p, const uint64_t* cts, size_t count, const uint32_t* key_of, const uint64_t* testv, int testv_per_ct,
-                            unsigned steps, uint64_t* out_ct, uint64_t* lwe_out, vpbs_pbs_proof_fn proof_fn, void* user, char* err, size_t err_len) {
+                            unsigned steps, uint64_t* out_ct, uint64_t* lwe_out, vpbs_pbs_proof_fn proof_fn, void* user, char* err, size_t err_len,
+                            const uint8_t* const* checkpoints, const size_t* lens) {
+    const char* who = checkpoints ? "vpbs_ring_prover_resume" : "vpbs_ring_prover_run";
     auto refuse = [&](const std::string& m) {
         report(err, err_len, m);
         return (long)VPBS_ERR_INVALID;
@@ -57,29 +59,37 @@ long ring_prover_run_locked(vpbs_ring_prover* p, const uint64_t* cts, size_t cou
     {   // every index before anything is queued
         std::lock_guard<std::mutex> lk(keyring_mutex(p->ring));
         std::string msg;
-        if (!keyring_check_slots(p->ring, key_of, count, "vpbs_ring_prover_run", "ciphertext", &msg)) return refuse(msg);
+        if (!keyring_check_slots(p->ring, key_of, count, who, "ciphertext", &msg)) return refuse(msg);
     }
     const double t_call = now_s();
     pool.stats = vpbs_pbs_run_stats{};
     const unsigned N = pool.shape.N;
     const size_t kn = pool.shape.kn, ct_words = pool.n_lwe + 1;
-    // ---- every output first: one key-ring launch per RING_BATCH ciphertexts ----
+    // ---- a resume: every checkpoint validated on the host before anything is queued, its key hash against the links of the row's slot ----
+    p->key_of = key_of;
+    ProvePool::Resume rs;
+    if (checkpoints) pool.open_checkpoints(cts, count, testv, testv_per_ct, checkpoints, lens, steps, rs);
+    // ---- every output first: one key-ring launch per RING_BATCH ciphertexts; accepted rows enter at their checkpoint's step ----
     if (out_ct || lwe_out) {
         std::lock_guard<std::mutex> lk(pool.boot_mu);
+        std::vector<uint32_t> start;
+        std::vector<u64> acc_in;
         for (size_t i0 = 0; i0 < count; i0 += vpbs_ring_prover::RING_BATCH) {
             const size_t c = std::min(vpbs_ring_prover::RING_BATCH, count - i0);
-            const long rc = vpbs_keyring_run(p->ring, cts + i0 * ct_words, c, key_of + i0, testv + (testv_per_ct ? i0 * N : 0), testv_per_ct,
-                                             out_ct ? out_ct + i0 * kn : nullptr, lwe_out ? lwe_out + i0 * ct_words : nullptr, nullptr, 0);
+            const bool from = rs.resumed && pool.start_rows(rs, i0, c, start, acc_in);
+            const long rc = vpbs_keyring_run_from(p->ring, cts + i0 * ct_words, c, key_of + i0, from ? start.data() : nullptr,
+                                                  from ? acc_in.data() : nullptr, testv + (testv_per_ct ? i0 * N : 0), testv_per_ct,
+                                                  out_ct ? out_ct + i0 * kn : nullptr, lwe_out ? lwe_out + i0 * ct_words : nullptr, nullptr, 0);
             if (rc != (long)c) {
-                report(err, err_len, std::string("vpbs_keyring_run: ") + vpbs_last_error(p->boot_ctx));
+                report(err, err_len, std::string(from ? "vpbs_keyring_run_from: " : "vpbs_keyring_run: ") + vpbs_last_error(p->boot_ctx));
+                p->key_of = nullptr;
                 return rc < 0 ? rc : (long)VPBS_ERR_DEVICE;
             }
         }
     }
     // ---- the proofs: the pool's workers take ciphertext indices from a queue; each chain under the keys and links of its slot ----
     pool.stats.outputs_seconds = out_ct || lwe_out ? now_s() - t_call : 0.0;
-    p->key_of = key_of;
-    const long delivered = pool.prove(cts, count, testv, testv_per_ct, steps, t_call, proof_fn, user);
+    const long delivered = pool.prove(cts, count, testv, testv_per_ct, steps, t_call, proof_fn, user, checkpoints ? &rs : nullptr);
     p->key_of = nullptr;
     return delivered;
 }
@@ -134,9 +144,10 @@ int vpbs_ring_prover_create(int device_ordinal, const vpbs_ivc_circuit* cyclic, 
         const vpbs_ring_prover::Slot& s = self->slots[self->key_of[index]];
         return KeySource{s.d_bsk, s.d_ksk, s.d_links, s.links.data()};
     };
-    pool.accumulators = [self](ProvePool::Worker& w, std::string& why) {
-        const uint32_t slot = self->key_of[w.index];
-        if (vpbs_keyring_run(self->ring, w.d_ct, 1, &slot, w.d_testv, 0, nullptr, nullptr, w.d_accs, 1) == 1) return true;
+    pool.accumulators = [self](ProvePool::Worker& w, unsigned from, std::string& why) {
+        const uint32_t slot = self->key_of[w.index], start = from;
+        if (vpbs_keyring_run_from(self->ring, w.d_ct, 1, &slot, from ? &start : nullptr, w.d_acc_in, w.d_testv, 0, nullptr, nullptr, w.d_accs, 1) == 1)
+            return true;
         why = vpbs_last_error(self->boot_ctx);
         return false;
     };
@@ -258,9 +269,14 @@ int vpbs_ring_prover_set_checkpoint(vpbs_ring_prover* p, unsigned every, vpbs_pb
     return VPBS_OK;
 }
 
-long vpbs_ring_prover_run(vpbs_ring_prover* p, const uint64_t* cts, size_t count, const uint32_t* key_of, const uint64_t* testv, int testv_per_ct,
-                          unsigned steps, uint64_t* out_ct, uint64_t* lwe_out, vpbs_pbs_proof_fn proof_fn, void* user, char* err, size_t err_len) {
-    using namespace vpbs;
+}  // extern "C"
+
+namespace vpbs {
+namespace {
+// vpbs_ring_prover_run (checkpoints = null) and vpbs_ring_prover_resume
+long ring_prover_run(vpbs_ring_prover* p, const uint64_t* cts, size_t count, const uint32_t* key_of, const uint64_t* testv, int testv_per_ct,
+                     const uint8_t* const* checkpoints, const size_t* lens, unsigned steps, uint64_t* out_ct, uint64_t* lwe_out,
+                     vpbs_pbs_proof_fn proof_fn, void* user, char* err, size_t err_len) {
     auto refuse = [&](const std::string& m) {
         report(err, err_len, m);
         return (long)VPBS_ERR_INVALID;
@@ -268,11 +284,26 @@ long vpbs_ring_prover_run(vpbs_ring_prover* p, const uint64_t* cts, size_t count
     report(err, err_len, "");
     if (!proof_fn) return refuse("no proof_fn: the proofs have nowhere to go");
     if (count && (!cts || !testv || !key_of)) return refuse("null cts, testv or key_of");
+    if (count && checkpoints && !lens) return refuse("checkpoints without lens");
     if (!p) return refuse("null prover");
     if (steps > p->pool.total) return refuse("steps exceeds n_lwe + 2 = " + std::to_string(p->pool.total));
     if (count == 0) return 0;
     std::lock_guard<std::mutex> run(p->run_mu);
-    return ring_prover_run_locked(p, cts, count, key_of, testv, testv_per_ct, steps, out_ct, lwe_out, proof_fn, user, err, err_len);
+    return ring_prover_run_locked(p, cts, count, key_of, testv, testv_per_ct, steps, out_ct, lwe_out, proof_fn, user, err, err_len, checkpoints, lens);
+}
+}  // namespace
+}  // namespace vpbs
+
+extern "C" {
+long vpbs_ring_prover_run(vpbs_ring_prover* p, const uint64_t* cts, size_t count, const uint32_t* key_of, const uint64_t* testv, int testv_per_ct,
+                          unsigned steps, uint64_t* out_ct, uint64_t* lwe_out, vpbs_pbs_proof_fn proof_fn, void* user, char* err, size_t err_len) {
+    return vpbs::ring_prover_run(p, cts, count, key_of, testv, testv_per_ct, nullptr, nullptr, steps, out_ct, lwe_out, proof_fn, user, err, err_len);
+}
+
+long vpbs_ring_prover_resume(vpbs_ring_prover* p, const uint64_t* cts, size_t count, const uint32_t* key_of, const uint64_t* testv, int testv_per_ct,
+                             const uint8_t* const* checkpoints, const size_t* lens, unsigned steps, uint64_t* out_ct, uint64_t* lwe_out,
+                             vpbs_pbs_proof_fn proof_fn, void* user, char* err, size_t err_len) {
+    return vpbs::ring_prover_run(p, cts, count, key_of, testv, testv_per_ct, checkpoints, lens, steps, out_ct, lwe_out, proof_fn, user, err, err_len);
 }
 
 int vpbs_ring_prover_last_run(const vpbs_ring_prover* p, vpbs_pbs_run_stats* out) {

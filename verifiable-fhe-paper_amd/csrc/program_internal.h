@@ -22,9 +22,15 @@ struct BootstrapperShape {
 void bootstrapper_shape(const vpbs_bootstrapper* b, BootstrapperShape* out);
 // pbs_batch_kernel for `count` <= max_batch ciphertexts on device pointers, queued on the context's stream: the launch of
 // vpbs_bootstrapper_run(.., on_device = 1) and nothing else -- no copy, no wait.  d_testv: [N], or [count][N] with testv_per_ct.  Any output
-// may be null.  Throws vpbs::DeviceError (context.h) for a failed launch; the caller holds the device (hipSetDevice).
+// may be null.  d_start [count] (device) with d_acc_in [count][K N]: the start mode of vpbs_bootstrapper_run_from, already checked; null: every
+// row from step 0.  Throws vpbs::DeviceError (context.h) for a failed launch; the caller holds the device (hipSetDevice).
 void bootstrapper_enqueue(vpbs_bootstrapper* b, const uint64_t* d_cts, size_t count, const uint64_t* d_testv, int testv_per_ct, uint64_t* d_out_ct,
-                          uint64_t* d_lwe_out, uint64_t* d_accs_out);
+                          uint64_t* d_lwe_out, uint64_t* d_accs_out, const uint32_t* d_start = nullptr, const uint64_t* d_acc_in = nullptr);
+// Host-side check of the start steps of a run_from (both objects): true when every start[i] is at most n_lwe + 2 and acc_in is there for a row
+// that needs it; else false with a message that names the row.  `who` is the entry point.
+bool check_start_steps(const uint32_t* start, size_t count, unsigned n_lwe, const uint64_t* acc_in, const char* who, std::string* msg);
+// the rows of a HOST acc_in [count][kn] with start[i] != 0 into d_acc_in, queued on the context's stream (rows with start 0 are not read)
+void upload_acc_in(vpbs_ctx* ctx, uint64_t* d_acc_in, const uint64_t* acc_in, const uint32_t* start, size_t count, size_t kn);
 // lwe_extract_kernel on device pointers, queued on `stream` (a hipStream_t): GLWEs [count][K][N] -> [count][n_lwe + 1]
 void lwe_extract_enqueue(void* stream, const uint64_t* d_glwe, unsigned log_N, unsigned K, unsigned n_lwe, size_t count, uint64_t* d_lwe_out);
 
@@ -51,7 +57,8 @@ bool keyring_check_slots(const vpbs_keyring* r, const uint32_t* key_of, size_t c
 // has run.  d_testv: [N], or [count][N] with testv_per_ct.  Any output may be null.  Threads per ciphertext by the ring's rule.  Throws
 // vpbs::DeviceError for a failed launch; the caller holds the mutex and the device (hipSetDevice).
 void keyring_enqueue(vpbs_keyring* r, const uint64_t* d_cts, size_t count, const uint64_t* d_testv, int testv_per_ct, const uint32_t* d_order,
-                     const uint32_t* d_key_of, uint64_t* d_out_ct, uint64_t* d_lwe_out, uint64_t* d_accs_out);
+                     const uint32_t* d_key_of, uint64_t* d_out_ct, uint64_t* d_lwe_out, uint64_t* d_accs_out, const uint32_t* d_start = nullptr,
+                     const uint64_t* d_acc_in = nullptr);   // d_start, d_acc_in: as bootstrapper_enqueue, indexed by ciphertext
 
 // The device pointers the ring's table holds for `slot` (null for an empty slot or one out of range): what a prover of that slot's
 // bootstraps reads the GGSW rows from.  The caller holds the ring's mutex, or otherwise knows that no add or remove is under way.
@@ -66,7 +73,8 @@ int keyring_remove(vpbs_keyring* r, unsigned slot, bool owner);
 // the mutex that add, remove and run of the ring prover take, and vpbs_ring_prover_run for a caller that holds it
 std::mutex& ring_prover_mutex(vpbs_ring_prover* p);
 long ring_prover_run_locked(vpbs_ring_prover* p, const uint64_t* cts, size_t count, const uint32_t* key_of, const uint64_t* testv, int testv_per_ct,
-                            unsigned steps, uint64_t* out_ct, uint64_t* lwe_out, vpbs_pbs_proof_fn proof_fn, void* user, char* err, size_t err_len);
+                            unsigned steps, uint64_t* out_ct, uint64_t* lwe_out, vpbs_pbs_proof_fn proof_fn, void* user, char* err, size_t err_len,
+                            const uint8_t* const* checkpoints = nullptr, const size_t* lens = nullptr);   // checkpoints: vpbs_ring_prover_resume
 
 struct PbsVerifierShape {
     vpbs_ctx* ctx;

@@ -284,7 +284,9 @@ int verify_pbs_form(const vpbs_verify_pbs_inputs* in, const uint8_t* proof_bytes
     const bool whole = form == PbsForm::whole;
     // out_ct is part of the statement (the reference asserts it, :440-442): a verdict without it would not bind the proof to the ciphertext
     // the caller holds.  ggsw_len strides the caller's bsk / ksk arrays: it must be a whole number of [K][N] GLWE rows (K * ELL * K * N)
-    if (!in || !in->circuit || !proof_bytes || !in->testv || (whole && !in->out_ct) || !in->ct || !in->ksk || (in->n_lwe && !in->bsk) || in->N == 0 ||
+    // the form without the key chain never reads bsk / ksk: its internal callers (the batch provers' resume) hold no host keys
+    const bool keys_read = form != PbsForm::prefix_without_keys;
+    if (!in || !in->circuit || !proof_bytes || !in->testv || (whole && !in->out_ct) || !in->ct || (keys_read && (!in->ksk || (in->n_lwe && !in->bsk))) || in->N == 0 ||
         in->K == 0 || in->ggsw_len == 0 || in->ggsw_len % ((size_t)in->K * in->K * in->N) != 0) {
         say(whole ? "malformed arguments (testv, out_ct, ct, ksk, bsk are all required; ggsw_len = K * ELL * K * N)"
                   : "malformed arguments (testv, ct, ksk, bsk are all required; ggsw_len = K * ELL * K * N)");
