@@ -1301,6 +1301,53 @@ long vpbs_program_verify_batch(vpbs_program* prog, vpbs_ring_verifier* ring_veri
                                char* err, size_t err_len);
 void vpbs_program_free(vpbs_program* prog);
 
+/* ---- multi-output lookup gates: several tables from one proven bootstrap (csrc/multi_lut.hip, csrc/program.hip) ----
+ * The step circuit mod-switches every word of a ciphertext by itself, to the top log2(2N) bits.  When every word of the input is first
+ * rounded ("snapped") to a multiple of 2^(64 - log2(2N) + log_slots), every rotation is a multiple of s = 2^log_slots and so is their sum:
+ * coefficient j < s of the output GLWE is then the entry testv[rotation + j] of the same s-aligned group, and a test vector that interleaves
+ * s tables yields s results from ONE blind rotation, one key switch and ONE proof.  The snap is a public function of the ciphertext; the
+ * proof is the unchanged proof of the snapped ciphertext with the packed test vector.  The price: the snap multiplies the mod-switch error
+ * by s (DESIGN.md 8.13 has the estimate and the measured decryption failures).
+ * A call that takes a ctx runs on the host when ctx is NULL (every pointer a host array, on_device 0); with a context and on_device != 0 the
+ * word arrays are device pointers, as in vpbs_lwe_extract.
+ *
+ * vpbs_lwe_snap: with L = log_N + 1, t = 64 - L + log_slots and w the word reduced below p: r = (w >> t) + ((w >> (t - 1)) & 1), result
+ *   (r << t) mod 2^64 -- always below p, and 0 when r = 2^(L - log_slots).  log_slots = 0 is the reduced word itself, no rounding.  Then
+ *   mod_switch(snap(w)) = r * s mod 2N, mod_switch(-snap(w)) = -r * s mod 2N (the body's path), and |snap(w) - w| <= 2^(t - 1).
+ *   Refused: log_N outside 1 .. 11, log_slots > log_N, null pointers.
+ * vpbs_lwe_extract_at: row i of lwe_out [rows][n_lwe + 1] is the sample extraction of coefficient index[i] of GLWE src[i] of glwe
+ *   [count][K][N]: over each mask polynomial a, full[c] = a[j - c] for c <= j, else -a[N + j - c] (negation in the field: 0 stays 0); the row
+ *   is the first n_lwe words of full over the K - 1 mask polynomials, then body[j].  index[i] = 0 is word for word vpbs_lwe_extract.
+ *   index and src are HOST arrays in every mode (like key_of of the key ring) and are checked before anything is queued.  Refused, naming
+ *   the row: an index >= N, a src >= count; and what vpbs_lwe_extract refuses.  One workgroup per output row, lanes on consecutive words.
+ * vpbs_lut_testv_multi (host): tables [2^log_slots][p]; with T_j the vector vpbs_lut_testv makes of table j, testv[q s + j] = T_j[q s] for
+ *   every q and j < s.  log_slots = 0 is vpbs_lut_testv.  Refused: what vpbs_lut_testv refuses, log_slots > log_N, and s * 2 p > N (the
+ *   half-block shift N / (2 p) must stay s-aligned); testv is not written then.
+ *
+ * vpbs_program_create_multi: vpbs_program_create with, per gate g, gate_log_slots[g] and gate_outputs[g] = m_g in 1 .. 2^gate_log_slots[g].
+ *   Wires are renumbered: with out_first the prefix sums of m, output j of gate g is wire n_inputs + out_first[g] + j, and a term_src of gate
+ *   g must be below n_inputs + out_first[g].  The gate's input is c_g = snap(combination) with the gate's log_slots, applied to every one of
+ *   the n_lwe + 1 words after the canonical sum: this is what gate_cts_out shows, what is bootstrapped and what the proof is made for.
+ *   Output wire j is vpbs_lwe_extract_at of the gate's output GLWE at coefficient j; testvs[gate_lut[g]] is whatever the caller packed.
+ *   Refused with the gate named: m_g = 0, m_g > 2^gate_log_slots[g] (at creation); 2^gate_log_slots[g] > N (by run, prove and verify,
+ *   against the shape of the object they are given).  All six program calls accept such a program: wires_out has n_inputs + sum m_g rows
+ *   per instance; gate_cts_out, out_cts, the proofs, the verdicts and the reasons stay per gate -- sum m_g results, n_gates proofs.  A forged
+ *   coefficient j of a claimed out_cts[g] fails gate g on the output check and exactly the readers of wire n_inputs + out_first[g] + j on
+ *   the LWE hash check.  Evaluation writes out_ct only from the bootstrap launch and fills the output rows of a chunk with one
+ *   vpbs_lwe_extract_at launch behind it on the same stream; verification extracts all (gate, j) rows in one launch and combines and snaps
+ *   all gates in one launch.  A description in which every gate is (0, 1) gives the object vpbs_program_create gives.
+ * vpbs_program_wires: out_first_out [n_gates + 1] (may be NULL); returns the wire count n_inputs + sum m_g. */
+int vpbs_lwe_snap(vpbs_ctx* ctx, unsigned log_N, unsigned log_slots, const uint64_t* words_in, size_t count_words, uint64_t* words_out,
+                  int on_device);
+int vpbs_lwe_extract_at(vpbs_ctx* ctx, unsigned log_N, unsigned K, unsigned n_lwe, const uint64_t* glwe /* [count][K][N] */, size_t count,
+                        const uint32_t* index /* [rows], HOST */, const uint32_t* src /* [rows], HOST */, size_t rows,
+                        uint64_t* lwe_out /* [rows][n_lwe + 1] */, int on_device);
+int vpbs_lut_testv_multi(unsigned log_N, unsigned p, unsigned log_slots, const uint64_t* tables /* [2^log_slots][p] */, uint64_t delta,
+                         uint64_t* testv);
+int vpbs_program_create_multi(vpbs_ctx* ctx, const vpbs_program_desc* desc, const unsigned* gate_log_slots /* [n_gates] */,
+                              const unsigned* gate_outputs /* [n_gates] */, vpbs_program** out, char* err, size_t err_len);
+long vpbs_program_wires(const vpbs_program* prog, unsigned* out_first_out /* [n_gates + 1] or NULL */);
+
 /* ---- memory helpers for hosts that do not link the HIP runtime themselves (a Rust or plain C++ caller) ----
  * pinned host memory (hipHostMalloc): witness matrices written there reach the device at PCIe speed (70.8 MB in 1.3 ms instead of ~15 ms
  * from pageable memory); device buffers for per-circuit data that is uploaded once (the sigma values of vpbs_step_inputs.sigmas_values with

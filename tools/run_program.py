@@ -5,7 +5,15 @@ user had to before api.Program existed (the baseline leg: Bootstrapper.run per l
 compared wire by wire.  One JSON line.
 
 usage: tools/run_program.py [--levels L] [--width W] [--fan-in F] [--program FILE.json] [--n8] [--prove] [--baseline] [--runs R] [--seed S]
-                            [--instances B --keys M [--verify-per-instance]]
+                            [--instances B --keys M [--verify-per-instance]] [--multi THETA]
+  --multi THETA: multi-output lookup gates.  W inputs, L layers of W lookups of 2^THETA tables over {0, 1} each; a later
+    lookup reads every output of the one before it.  The multi leg makes ONE gate of each lookup (api.Program 5-tuples, api.lut_testv_multi);
+    the single leg makes one gate per table of the same functions on the same inputs -- a plain program that runs unchanged on a build
+    without multi-output gates.  Every wire of the multi leg is compared with the composition snap -> Bootstrapper.run -> extract_at in
+    numpy; every output of both legs is decrypted under its key (api lwe_decode_batch) against the tables and the failures are reported,
+    not judged: they are the price of the snap.  Prints gates, proofs and evaluation seconds of both legs, and with --prove the proving
+    and verifying seconds and the total proof bytes.  Works alone (Program.run / prove / verify) and with --instances B --keys M
+    (run_batch / prove_batch / verify_batch).
   netlist: W inputs, L layers of W gates; a gate reads F wires of the layer before it with coefficients in {1, p - 1}; gate 0 of every layer
     is the identity of gate 0 of the layer before it (fan-in 1, coefficient 1), so that one output has a known message whatever F is.
   --program: {"n_inputs", "n_luts", "gates": [{"terms": [[src, coef], ..], "const", "lut"}, ..]} instead; lut 0 is the test vector of the
@@ -276,6 +284,195 @@ def main_batch(args):
     return 0 if ok else 1
 
 
+TABLES = [[0, 1], [1, 0], [1, 1], [0, 0]]      # over {0, 1}: the identity, its complement, the constants; slot j holds TABLES[j % 4]
+
+
+def multi_netlist(levels, width, s):
+    """-> (gates of the multi-output form, gates of the single-output form, the table behind every wire's message).  W inputs, L layers of W
+    gates with s outputs each; gate g of layer l reads EVERY output of gate g of the layer before it: output (g + l) % s with coefficient 1,
+    every other output once with 1 and once with p - 1 (they cancel word for word), so its message is that one output's.  The single-output
+    form has one gate per (gate, j) with table j alone; both forms number the wire of (gate, j) width + gate * s + j."""
+    multi, single, main = [], [], []
+    theta = s.bit_length() - 1
+    for lv in range(levels):
+        for g in range(width):
+            if lv == 0:
+                terms, j_main = [(g, 1)], None
+            else:
+                first = width + ((lv - 1) * width + g) * s
+                j_main = (g + lv) % s
+                terms = [(first + j_main, 1)] + [(first + j, c) for j in range(s) if j != j_main for c in (1, P - 1)]
+            multi.append((terms, 0, 0, theta, s))
+            single += [(terms, 0, j) for j in range(s)]
+            main.append(j_main)
+    return multi, single, main
+
+
+def multi_messages(levels, width, s, main, msgs):
+    """the message of every wire of one instance: inputs, then TABLES[j % 4][message of the gate's input] for every (gate, j)"""
+    known = [int(m) for m in msgs]
+    for lv in range(levels):
+        for g in range(width):
+            gate = lv * width + g
+            m_in = known[g] if lv == 0 else known[width + ((lv - 1) * width + g) * s + main[gate]]
+            known += [TABLES[j % 4][m_in] for j in range(s)]
+    return known
+
+
+def snap_np(a, log_n, theta):
+    """vpbs_lwe_snap on canonical words, in numpy"""
+    if theta == 0:
+        return a
+    t = np.uint64(64 - (log_n + 1) + theta)
+    r = (a >> t) + ((a >> (t - np.uint64(1))) & np.uint64(1))
+    return np.where((r >> (np.uint64(64) - t)) != 0, np.uint64(0), r << t)
+
+
+def extract_at_np(glwe, n_lwe, j):
+    """vpbs_lwe_extract_at of one GLWE [K][N], in numpy"""
+    neg = lambda a: np.where(a == 0, a, np.uint64(P) - a)
+    full = np.concatenate([np.concatenate([a[j::-1], neg(a[:j:-1])]) for a in glwe[:-1]])
+    return np.concatenate([full[:n_lwe], glwe[-1][j:j + 1]])
+
+
+def compose_multi(bs, n_inputs, gates, levels, width, s, inputs, testvs):
+    """the multi-output program as the composition combine -> snap -> Bootstrapper.run -> extract_at, layer by layer, in numpy -> wires"""
+    words, log_n, theta = inputs.shape[1], bs.N.bit_length() - 1, s.bit_length() - 1
+    wires = np.zeros((n_inputs + len(gates) * s, words), np.uint64)
+    wires[:n_inputs] = inputs % np.uint64(P)
+    for lv in range(levels):
+        todo = list(range(lv * width, (lv + 1) * width))
+        cts = np.zeros((width, words), np.uint64)
+        for t in range(max(len(gates[g][0]) for g in todo)):
+            rows = [k for k, g in enumerate(todo) if len(gates[g][0]) > t]
+            for c in sorted({gates[todo[k]][0][t][1] for k in rows}):
+                sel = [k for k in rows if gates[todo[k]][0][t][1] == c]
+                cts[sel] = addmod(cts[sel], mulmod(wires[[gates[todo[k]][0][t][0] for k in sel]], c))
+        cts = snap_np(cts, log_n, theta)
+        for lo in range(0, width, bs.max_batch):
+            out, _ = bs.run(cts[lo:lo + bs.max_batch], testvs[[gates[g][2] for g in todo[lo:lo + bs.max_batch]]])
+            for k, g in enumerate(todo[lo:lo + bs.max_batch]):
+                for j in range(s):
+                    wires[n_inputs + g * s + j] = extract_at_np(out[k].reshape(bs.K, bs.N), bs.n_lwe, j)
+    wires[:n_inputs] = inputs
+    return wires
+
+
+def main_multi(args):
+    """--multi THETA: gates with 2^THETA tables each against the same functions as single-output gates, on the same inputs; see the module text"""
+    theta, s, p = args.multi, 1 << args.multi, 2
+    N, n_lwe, log_n = (8, 6, 13) if args.n8 else (1024, 728, 16)
+    if s * 2 * p > N:
+        raise SystemExit("--multi %d: 2^theta * 2 p = %d exceeds N = %d" % (theta, s * 2 * p, N))
+    batched = args.instances is not None
+    B, M = (args.instances, max(1, args.keys)) if batched else (1, 1)
+    L, W = args.levels, args.width
+    rng = np.random.default_rng(args.seed)
+    multi, single, main_out = multi_netlist(L, W, s)
+    ctx = vpbs_amd.Context(0, log_n_max=max(16, log_n))
+    host = [ctx.keygen(N, K, ELL, LOGB, n_lwe, SEED + k, SIGMA_GLWE, SIGMA_LWE) for k in range(M)]
+    delta = api.testv(N, p)[1]
+    tables = np.array([TABLES[j % 4] for j in range(s)], np.uint64)
+    tv_multi = api.lut_testv_multi(N, p, tables, delta)[0].reshape(1, N)
+    tv_single = np.stack([api.lut_testv(N, p, t, delta)[0] for t in tables])
+    key_of = np.array([b % M for b in range(B)], np.uint32)
+    msgs = rng.integers(0, 2, size=(B, W))
+    inputs = np.stack([np.stack([api.lwe_encrypt(host[key_of[b]]["params"], host[key_of[b]]["s_lwe"], delta * int(m) % P, nonce=b * W + i)
+                                 for i, m in enumerate(msgs[b])]) for b in range(B)])
+    expected = np.array([multi_messages(L, W, s, main_out, msgs[b]) for b in range(B)], np.uint64)
+    words = n_lwe + 1
+    out = {"what": "%d layers of %d lookups of %d tables each at N=%d, n=%d, %d instance(s) under %d key set(s): one gate per lookup (multi, "
+                   "theta=%d) against one gate per table (single)" % (L, W, s, N, n_lwe, B, M, theta),
+           "theta": theta, "slots": s, "levels": L, "width": W, "instances": B, "keys": M, "runs": args.runs, "outputs": B * L * W * s}
+    max_batch = max(1, args.max_batch)
+    bss = [api.Bootstrapper(ctx, k["bsk"], k["ksk"], K, ELL, LOGB, max_batch=max(1, min(max_batch, L * W * s))) for k in host]
+    ring = None
+    if batched:
+        ring = api.KeyRing(ctx, K, ELL, LOGB, N, n_lwe, max_keys=M, max_batch=max_batch)
+        for k in host:
+            ring.add(k["bsk"], k["ksk"])
+    ok = True
+    prover = shape = hashes = None
+    if args.prove:
+        cyc_path, dum_path = circuit_file.find_cyclic_circuit(N, K, ELL, LOGB, n_lwe, log_n)
+        cyc, dum = circuit_file.load(cyc_path), circuit_file.load(dum_path)
+        chains = args.chains or (2 if args.n8 else 8)
+        api.host_set_late_threads(api.late_threads_for(chains, api.host_cpu_budget()))
+        api.host_set_early_threads(api.early_threads_for(chains))
+        wb = args.witness_batch or (3 if args.n8 else 64)
+        if batched:
+            prover = api.RingProver(0, cyc, dum, K, ELL, LOGB, N, n_lwe, max_keys=M, chains=chains, witness_batch=wb)
+            for k in range(M):
+                assert prover.add(host[k]["bsk"], host[k]["ksk"]) == k
+        else:
+            prover = api.PbsProver(0, cyc, dum, host[0]["bsk"], host[0]["ksk"], K, ELL, LOGB, chains=chains, witness_batch=wb)
+    for name, gates, testvs in (("multi", multi, tv_multi), ("single", single, tv_single)):
+        prog = api.Program(ctx, W, gates, testvs.shape[0])
+        if batched:
+            run = lambda: prog.run_batch(ring, inputs, key_of, testvs, gate_cts=False, out_cts=False)[0]
+        else:
+            run = lambda: prog.run(bss[0], inputs[0], testvs, gate_cts=False, out_cts=False)[0][None]
+        run()                                                            # warm-up
+        secs, wires = [], None
+        for _ in range(args.runs):
+            t = time.perf_counter()
+            wires = run()
+            secs.append(time.perf_counter() - t)
+        leg = out[name] = {"gates": len(gates), "proofs": len(gates) * B, "wires": int(wires.shape[1]), "eval_seconds": secs}
+        if name == "multi":   # every wire against the composition snap -> Bootstrapper.run -> extract_at in numpy
+            want = np.stack([compose_multi(bss[key_of[b]], W, gates, L, W, s, inputs[b], testvs) for b in range(B)])
+            leg["mismatches"] = int((wires != want).any(axis=2).sum())
+            ok = ok and leg["mismatches"] == 0
+        if args.prove:
+            n_gates, rows = len(gates), len(gates) * B
+            t = time.perf_counter()
+            if batched:
+                proofs, p_wires, out_cts = prog.prove_batch(prover, inputs, key_of, testvs)
+            else:
+                proofs, p_wires, out_cts = prog.prove(prover, inputs[0], testvs)
+                proofs, p_wires, out_cts = [proofs], p_wires[None], out_cts[None]
+            leg["prove_seconds"] = time.perf_counter() - t
+            leg["proof_bytes"] = sum(len(blob) for row in proofs for blob in row)
+            if shape is None:
+                hashes = [prover.key_hash(k) for k in range(M)] if batched else [prover.key_hash()]
+                vk = prover.verifier_data()[0]
+                shape = (ctx, vk[4:].reshape(-1, 4), [cyc.n_constants + 80, 135, 20, 16], vk[:4], log_n, cyc.n_constants, 80, cyc.gates, N, K,
+                         n_lwe, K * ELL * K * N)
+            t = time.perf_counter()
+            if batched:
+                rv = api.RingVerifier(*shape, max_keys=M, max_batch=max(1, min(rows, 512)))
+                for k in range(M):
+                    rv.set_key(k, hashes[k])
+                verdicts = prog.verify_batch(rv, inputs, key_of, testvs, out_cts, proofs)[0]
+                rv.close()
+            else:
+                pv = api.PbsVerifier(*shape, hashes[0], max_batch=max(1, min(n_gates, 64)))
+                verdicts = prog.verify(pv, inputs[0], testvs, out_cts[0], proofs[0])[0]
+                pv.close()
+            leg["verify_seconds"] = time.perf_counter() - t
+            leg["verified"] = int(verdicts.sum())
+            leg["proven_wires_equal"] = bool((p_wires == wires).all())
+            ok = ok and leg["verified"] == rows and leg["proven_wires_equal"]
+        prog.close()
+        # every output wire under its own key, through lwe_decode_batch: failures = decoded message != the table's entry
+        stats = api.NoiseStats()
+        for b in range(B):
+            ctx.lwe_decode_batch(host[key_of[b]]["s_lwe"], np.ascontiguousarray(wires[b, W:]), delta, 2 * p, expected=expected[b, W:], stats=stats)
+        leg["decrypted"], leg["decrypt_failures"] = stats.count, stats.failures
+        leg["noise_std_over_delta"] = stats.std() / delta
+        leg["noise_max_over_delta"] = stats.max_abs / delta
+    out["all_equal"] = out["multi"]["mismatches"] == 0
+    if args.prove:
+        prover.close()
+    if ring is not None:
+        ring.close()
+    for bs in bss:
+        bs.close()
+    ctx.close()
+    print(json.dumps(out))
+    return 0 if ok else 1
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--levels", type=int, default=3)
@@ -293,7 +490,12 @@ def main():
     ap.add_argument("--instances", type=int)
     ap.add_argument("--keys", type=int, default=1)
     ap.add_argument("--verify-per-instance", action="store_true")
+    ap.add_argument("--multi", type=int)
     args = ap.parse_args()
+    if args.multi is not None:
+        if args.baseline or args.program:
+            raise SystemExit("--multi builds its own netlist and both legs: it cannot run with --baseline or --program")
+        return main_multi(args)
     if args.baseline and args.prove:
         raise SystemExit("--baseline evaluates only: it cannot run with --prove")
     if args.instances is not None:

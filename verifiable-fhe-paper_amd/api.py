@@ -378,6 +378,11 @@ SIGNATURES = {
     "vpbs_program_verify_batch": (C.c_long, [_vp, _vp, U64P, _sz, _vp, U64P, U64P, C.POINTER(C.c_uint8), C.POINTER(_sz), C.POINTER(C.c_uint8),
                                              C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.c_char_p, _sz]),
     "vpbs_program_free": (None, [_vp]),
+    "vpbs_program_create_multi": (_i, [_vp, C.POINTER(ProgramDescC), C.POINTER(_ui), C.POINTER(_ui), C.POINTER(_vp), C.c_char_p, _sz]),
+    "vpbs_program_wires": (C.c_long, [_vp, C.POINTER(_ui)]),
+    "vpbs_lwe_snap": (_i, [_vp, _ui, _ui, _vp, _sz, _vp, _i]),
+    "vpbs_lwe_extract_at": (_i, [_vp, _ui, _ui, _ui, _vp, _sz, _vp, _vp, _sz, _vp, _i]),
+    "vpbs_lut_testv_multi": (_i, [_ui, _ui, _ui, U64P, _u64, U64P]),
     "vpbs_lwe_extract": (_i, [_vp, _ui, _ui, _ui, _vp, _sz, _vp, _i]),
     "vpbs_lwe_decrypt": (_i, [U64P, U64P, _ui, U64P]),
     "vpbs_lwe_encrypt_batch": (_i, [_vp, C.POINTER(KeygenParamsC), _vp, _i, _vp, _sz, _u64, _vp, _i]),
@@ -1552,6 +1557,75 @@ def lwe_decode_batch(s_lwe, cts, delta, modulus, expected=None, stats=None, want
     return _lwe_decode_batch(None, s_lwe, cts, delta, modulus, expected, None, stats, want, None)
 
 
+def _lwe_snap(ctx, N, log_slots, words, count=None, out_dev_ptr=None):
+    h = ctx.h if ctx is not None else None
+    if out_dev_ptr is not None:
+        rc = lib().vpbs_lwe_snap(h, N.bit_length() - 1, log_slots, C.c_void_p(int(words)), count, C.c_void_p(int(out_dev_ptr)), 1)
+        out = None
+    else:
+        w = _u64(words)
+        out = np.zeros(w.shape, np.uint64)
+        keep = np.zeros(1, np.uint64)
+        rc = lib().vpbs_lwe_snap(h, N.bit_length() - 1, log_slots, (w if w.size else keep).ctypes.data, w.size, (out if w.size else keep).ctypes.data, 0)
+    if rc:
+        raise VpbsError("vpbs_lwe_snap: status %d: %s" % (rc, lib().vpbs_last_error(h).decode() if h else "bad arguments (log_slots <= log_N <= 11)"))
+    return out
+
+
+def _lwe_extract_at(ctx, glwe, n_lwe, index, src, count=None, N=None, K=None, out_dev_ptr=None):
+    h = ctx.h if ctx is not None else None
+    ix, sr = (np.ascontiguousarray(a, dtype=np.uint32).reshape(-1) for a in (index, src))
+    if ix.size != sr.size:
+        raise ValueError("lwe_extract_at: index and src must have one entry per output row")
+    rows = ix.size
+    k32 = np.zeros(1, np.uint32)
+    pi, ps = (ix if rows else k32).ctypes.data, (sr if rows else k32).ctypes.data
+    if out_dev_ptr is not None:
+        rc = lib().vpbs_lwe_extract_at(h, N.bit_length() - 1, K, n_lwe, C.c_void_p(int(glwe)), count, pi, ps, rows, C.c_void_p(int(out_dev_ptr)), 1)
+        out = None
+    else:
+        g = _u64(glwe)
+        g3 = g.reshape((1,) + g.shape) if g.ndim == 2 else g
+        cnt, K_, N_ = g3.shape
+        out = np.zeros((rows, n_lwe + 1), np.uint64)
+        keep = np.zeros(1, np.uint64)
+        rc = lib().vpbs_lwe_extract_at(h, N_.bit_length() - 1, K_, n_lwe, (g3 if g3.size else keep).ctypes.data, cnt, pi, ps, rows,
+                                       (out if out.size else keep).ctypes.data, 0)
+    if rc:
+        raise VpbsError("vpbs_lwe_extract_at: status %d: %s" % (rc, lib().vpbs_last_error(h).decode() if h else
+                                                                "bad arguments (index below N, src below count, 1 <= n_lwe <= (K - 1) N)"))
+    return out
+
+
+def lwe_snap(N, log_slots, words):
+    """vpbs_lwe_snap on the host (null context): every word rounded to a multiple of 2^(64 - log2(2N) + log_slots) -- then the mod switch of
+    every word, and of any sum of them, is a multiple of 2^log_slots.  log_slots = 0 only reduces below p.  -> array of the shape of words"""
+    return _lwe_snap(None, N, log_slots, words)
+
+
+def lwe_extract_at(glwe, n_lwe, index, src):
+    """vpbs_lwe_extract_at on the host (null context): row i = sample extraction of coefficient index[i] of glwe[src[i]] (glwe [count][K][N], or
+    one [K][N]) -> [rows][n_lwe + 1]; index 0 is Context.lwe_extract"""
+    return _lwe_extract_at(None, glwe, n_lwe, index, src)
+
+
+def lut_testv_multi(N, p, tables, delta=None):
+    """vpbs_lut_testv_multi: tables [s][p], s a power of two with s * 2 p <= N, interleaved in groups of s coefficients: coefficient j < s of
+    the bootstrap of a ciphertext snapped with log_slots = log2(s) carries tables[j][m] * delta -> (testv [N], delta)"""
+    t = _u64(tables)
+    if t.ndim != 2 or t.shape[1] != p or t.shape[0] < 1 or t.shape[0] & (t.shape[0] - 1):
+        raise ValueError("lut_testv_multi: expected tables [s][%d] with s a power of two" % p)
+    if delta is None:
+        d = np.zeros(1, np.uint64)
+        if lib().vpbs_testv(N.bit_length() - 1, p, None, _ptr(d)) != 0:
+            raise VpbsError("vpbs_lut_testv_multi: bad arguments")
+        delta = int(d[0])
+    out = np.zeros(N, np.uint64)
+    if lib().vpbs_lut_testv_multi(N.bit_length() - 1, p, t.shape[0].bit_length() - 1, _ptr(t.reshape(-1)), int(delta), _ptr(out)) != 0:
+        raise VpbsError("vpbs_lut_testv_multi: bad arguments (p a power of two, entries below 2 p, s * 2 p <= N)")
+    return out, int(delta)
+
+
 class Bootstrapper:
     """vpbs_bootstrapper: the whole PBS (accumulator chain of verified_pbs + partial_sample_extract) for batches of LWE ciphertexts in one
     launch, under a key set that stays on the device.  bsk [n][K*ELL*K*N], ksk [K*ELL*K*N] (keygen's layout): host arrays, or device
@@ -1734,9 +1808,17 @@ def keyring_run_args(N, n_lwe, max_keys, cts, key_of, testv):
     return c, keyring_key_of(key_of, c.shape[0], max_keys), tv
 
 
-def program_batch_args(n_inputs, n_lwe, N, n_luts, max_keys, inputs, key_of, testvs):
+def program_batch_args(n_inputs, n_lwe, N, n_luts, max_keys, inputs, key_of, testvs, gate_outputs=None):
     """shapes of a Program.run_batch call, checked without a device: inputs [instances][n_inputs][n + 1], key_of [instances] slots below
-    max_keys (any integer dtype; the offending index is named), testvs [n_luts][N] -> (inputs, key_of as uint32, testvs), contiguous"""
+    max_keys (any integer dtype; the offending index is named), testvs [n_luts][N] -> (inputs, key_of as uint32, testvs), contiguous.
+    With gate_outputs [n_gates] (a program with multi-output gates; 1 per plain gate) the shape of wires_out comes fourth:
+    (instances, n_inputs + sum gate_outputs, n + 1)."""
+    if gate_outputs is not None:
+        x, ko, tv = program_batch_args(n_inputs, n_lwe, N, n_luts, max_keys, inputs, key_of, testvs)
+        m = np.asarray(gate_outputs, dtype=np.int64).reshape(-1)
+        if (m < 1).any():
+            raise ValueError("Program.run_batch: gate %d has no output" % int(np.argmax(m < 1)))
+        return x, ko, tv, (x.shape[0], n_inputs + int(m.sum()), n_lwe + 1)
     x, tv = _u64(inputs), _u64(testvs)
     if x.ndim != 3 or x.shape[1:] != (n_inputs, n_lwe + 1):
         raise ValueError("Program.run_batch: expected inputs [instances][%d][%d], got shape %s" % (n_inputs, n_lwe + 1, x.shape))
@@ -2385,7 +2467,11 @@ class Program:
     """vpbs_program: a netlist of bootstraps on resident keys.  Wire w < n_inputs is input w, wire n_inputs + g the output of gate g; gate g
     bootstraps const * (0, .., 0, 1) + sum coef * wire[src] with test vector testvs[lut].  gates: a list of (terms=[(src, coef), ..], const, lut)
     in topological order, or the CSR arrays as a dict {gate_first, term_src, term_coef, gate_const, gate_lut}.  ctx=None gives a host-only
-    object (validated and levelised: levels()); an invalid description raises VpbsError with a message that names the gate."""
+    object (validated and levelised: levels()); an invalid description raises VpbsError with a message that names the gate.
+    Multi-output gates: a gate may be a 5-tuple (terms, const, lut, log_slots, outputs) -- its input is snapped with log_slots (lwe_snap), it
+    has `outputs` <= 2^log_slots output wires (the extractions of coefficients 0 .. outputs - 1 of its output GLWE, lwe_extract_at) and
+    testvs[lut] is a packed test vector (lut_testv_multi); a 3-tuple is (.., 0, 1).  The CSR dict takes gate_log_slots and gate_outputs.
+    Output j of gate g is wire n_inputs + out_first[g] + j (wires()); every per-gate result stays per gate: one proof for all its outputs."""
 
     def __init__(self, ctx, n_inputs, gates, n_luts):
         if isinstance(gates, dict):
@@ -2393,24 +2479,41 @@ class Program:
             src = np.ascontiguousarray(gates["term_src"], dtype=np.uint32).reshape(-1)
             coef, const = _u64(gates["term_coef"]).reshape(-1), _u64(gates["gate_const"]).reshape(-1)
             lut = np.ascontiguousarray(gates["gate_lut"], dtype=np.uint32).reshape(-1)
+            multi = "gate_log_slots" in gates or "gate_outputs" in gates
+            slots = np.ascontiguousarray(gates.get("gate_log_slots", np.zeros(lut.size)), dtype=np.uint32).reshape(-1)
+            outs = np.ascontiguousarray(gates.get("gate_outputs", np.ones(lut.size)), dtype=np.uint32).reshape(-1)
         else:
             gates = [tuple(g) for g in gates]
             first = np.cumsum([0] + [len(g[0]) for g in gates]).astype(np.uint64)
             src = np.array([t[0] for g in gates for t in g[0]], np.uint32)
             coef = np.array([int(t[1]) for g in gates for t in g[0]], np.uint64)
             const, lut = np.array([int(g[1]) for g in gates], np.uint64), np.array([g[2] for g in gates], np.uint32)
-        if src.size != coef.size or const.size != lut.size or first.size != const.size + 1:
-            raise ValueError("Program: expected gate_first [n_gates + 1], term_src / term_coef [n_terms], gate_const / gate_lut [n_gates]")
+            if any(len(g) not in (3, 5) for g in gates):
+                raise ValueError("Program: a gate is (terms, const, lut) or (terms, const, lut, log_slots, outputs)")
+            multi = any(len(g) == 5 for g in gates)
+            slots = np.array([g[3] if len(g) == 5 else 0 for g in gates], np.uint32)
+            outs = np.array([g[4] if len(g) == 5 else 1 for g in gates], np.uint32)
+        if src.size != coef.size or const.size != lut.size or first.size != const.size + 1 or slots.size != lut.size or outs.size != lut.size:
+            raise ValueError("Program: expected gate_first [n_gates + 1], term_src / term_coef [n_terms], gate_const / gate_lut "
+                             "(/ gate_log_slots / gate_outputs) [n_gates]")
         self.ctx, self.n_inputs, self.n_gates, self.n_luts = ctx, n_inputs, int(const.size), n_luts
+        self.gate_log_slots, self.gate_outputs = slots, outs
+        self.n_wires = n_inputs + self.n_gates   # until the object says otherwise
         self.gate_first, self.term_src, self.term_coef, self.gate_const, self.gate_lut = first, src, coef, const, lut
         d = ProgramDescC(n_inputs, self.n_gates, n_luts, src.size, _ptr(first), src.ctypes.data_as(C.POINTER(C.c_uint32)), _ptr(coef), _ptr(const),
                          lut.ctypes.data_as(C.POINTER(C.c_uint32)))
         h, err = C.c_void_p(), C.create_string_buffer(512)
-        rc = lib().vpbs_program_create(ctx.h if ctx is not None else None, C.byref(d), C.byref(h), err, 512)
+        if multi:
+            k32 = np.zeros(1, np.uint32)
+            uip = lambda a: (a if a.size else k32).ctypes.data_as(C.POINTER(C.c_uint))
+            rc = lib().vpbs_program_create_multi(ctx.h if ctx is not None else None, C.byref(d), uip(slots), uip(outs), C.byref(h), err, 512)
+        else:
+            rc = lib().vpbs_program_create(ctx.h if ctx is not None else None, C.byref(d), C.byref(h), err, 512)
         if rc:
             self.h = None
-            raise VpbsError("vpbs_program_create: status %d: %s" % (rc, err.value.decode()))
+            raise VpbsError("vpbs_program_create%s: status %d: %s" % ("_multi" if multi else "", rc, err.value.decode()))
         self.h = h
+        self.n_wires = self.wires()[1]
         if ctx is not None:
             ctx._batches.add(self)   # must not outlive its context: Context.close() frees the survivors
 
@@ -2421,6 +2524,14 @@ class Program:
         if n < 0:
             raise VpbsError("vpbs_program_levels: status %d" % n)
         return out[:self.n_gates], int(n)
+
+    def wires(self):
+        """-> (out_first np.uint32 [n_gates + 1]: output j of gate g is wire n_inputs + out_first[g] + j; the number of wires)"""
+        out = np.zeros(self.n_gates + 1, np.uint32)
+        n = lib().vpbs_program_wires(self.h, out.ctypes.data_as(C.POINTER(C.c_uint)))
+        if n < 0:
+            raise VpbsError("vpbs_program_wires: status %d" % n)
+        return out, int(n)
 
     def _host_args(self, who, n_lwe, N, inputs, testvs):
         x, tv = _u64(inputs).reshape(-1, n_lwe + 1), _u64(testvs).reshape(-1, N)
@@ -2434,7 +2545,7 @@ class Program:
         output is not downloaded (None in its place)."""
         b = bootstrapper
         x, tv = self._host_args("run", b.n_lwe, b.N, inputs, testvs)
-        wires = np.zeros((self.n_inputs + self.n_gates, b.n_lwe + 1), np.uint64)
+        wires = np.zeros((self.n_wires, b.n_lwe + 1), np.uint64)
         cts = np.zeros((self.n_gates, b.n_lwe + 1), np.uint64) if gate_cts else None
         out = np.zeros((self.n_gates, b.K, b.N), np.uint64) if out_cts else None
         keep = np.zeros(1, np.uint64)   # a valid pointer for an empty array
@@ -2469,7 +2580,7 @@ class Program:
         r = ring
         x, ko, tv = program_batch_args(self.n_inputs, r.n_lwe, r.N, self.n_luts, r.max_keys, inputs, key_of, testvs)
         count = x.shape[0]
-        wires = np.zeros((count, self.n_inputs + self.n_gates, r.n_lwe + 1), np.uint64)
+        wires = np.zeros((count, self.n_wires, r.n_lwe + 1), np.uint64)
         cts = np.zeros((count, self.n_gates, r.n_lwe + 1), np.uint64) if gate_cts else None
         out = np.zeros((count, self.n_gates, r.K, r.N), np.uint64) if out_cts else None
         keep = np.zeros(1, np.uint64)   # a valid pointer for an empty array
@@ -2499,7 +2610,7 @@ class Program:
         on_proof(gate, bytes), failures (PbsProveError, with .out_ct = out_cts and .lwe_out = wires) and `steps` as in PbsProver.prove."""
         pp = pbs_prover
         x, tv = self._host_args("prove", pp.n_lwe, pp.N, inputs, testvs)
-        wires, out = np.zeros((self.n_inputs + self.n_gates, pp.n_lwe + 1), np.uint64), np.zeros((self.n_gates, pp.K, pp.N), np.uint64)
+        wires, out = np.zeros((self.n_wires, pp.n_lwe + 1), np.uint64), np.zeros((self.n_gates, pp.K, pp.N), np.uint64)
         proofs, failures, raised = [None] * self.n_gates, [], []
 
         def trampoline(_user, index, data, n, error):
@@ -2541,7 +2652,7 @@ class Program:
             raise VpbsError("Program.prove_batch: no ring prover (None, or a closed RingProver)")
         x, ko, tv = program_batch_args(self.n_inputs, rp.n_lwe, rp.N, self.n_luts, rp.max_keys, inputs, key_of, testvs)
         B, G = x.shape[0], self.n_gates
-        wires, out = np.zeros((B, self.n_inputs + G, rp.n_lwe + 1), np.uint64), np.zeros((B, G, rp.K, rp.N), np.uint64)
+        wires, out = np.zeros((B, self.n_wires, rp.n_lwe + 1), np.uint64), np.zeros((B, G, rp.K, rp.N), np.uint64)
         flat, failures, raised = [None] * (B * G), [], []
 
         def trampoline(_user, index, data, n, error):
@@ -3063,6 +3174,15 @@ class Context:
         out = np.zeros((cnt, n_lwe + 1), np.uint64)
         self._check(lib().vpbs_lwe_extract(self.h, N_.bit_length() - 1, K_, n_lwe, g3.ctypes.data, cnt, out.ctypes.data, 0))
         return out[0] if one else out
+
+    def lwe_snap(self, N, log_slots, words, count=None, out_dev_ptr=None):
+        """vpbs_lwe_snap on the device (see api.lwe_snap).  With out_dev_ptr, words is a device pointer of count words and nothing is returned."""
+        return _lwe_snap(self, N, log_slots, words, count, out_dev_ptr)
+
+    def lwe_extract_at(self, glwe, n_lwe, index, src, count=None, N=None, K=None, out_dev_ptr=None):
+        """vpbs_lwe_extract_at on the device (see api.lwe_extract_at); index and src stay host arrays.  With out_dev_ptr, glwe is a device
+        pointer too (count, N, K given) and nothing is returned."""
+        return _lwe_extract_at(self, glwe, n_lwe, index, src, count, N, K, out_dev_ptr)
 
     def timing_shader_clock(self):
         """-> (MHz sustained under the leaf-hash kernel while timing was on, launches sampled)"""

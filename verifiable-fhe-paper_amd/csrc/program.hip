@@ -29,6 +29,13 @@
 //           verifier's max_batch rows the verifier's core on device pointers into these tables (vpbs::pbs_verify_enqueue) -- the test
 //           vector of a row through testv_of = gate_lut, the key hash through key_of of the row's instance; both index arrays are
 //           uploaded once -- and one wait for the chunk's result bytes.
+//
+// Multi-output gates (vpbs_program_create_multi): gate g has outs[g] output wires and a snap of slots[g].  Everything above
+// holds with "outputs of the level" for "gates of the level" in both wire tables; the gate inputs, the output GLWEs and the proofs stay
+// per gate.  For such a program (multi): the combine kernels run in their SNAP instantiation, the bootstrap launch writes out_ct only,
+// and ONE lwe_extract_at_kernel launch per chunk (multi_lut.hip) fills the chunk's output rows -- contiguous in both tables -- behind it on
+// the same stream; verify and verify_batch extract all (gate, j) rows in one launch.  A description whose every gate is (0, 1) is not
+// multi: it runs exactly the launches listed above.
 #include <algorithm>
 #include <cstring>
 #include <mutex>
@@ -36,6 +43,7 @@
 #include <vector>
 
 #include "context.h"
+#include "multi_lut.h"
 #include "program_internal.h"
 
 using vpbs::DeviceError;
@@ -52,20 +60,26 @@ struct CombineArgs {
     const u64* cst;        // [n_gates]
     u64* out;              // [count][words]: row 0 is gate `gate0`
     unsigned gate0, words; // words = n_lwe + 1
+    const u32* slots;      // SNAP only: [n_gates], log2 of the gate's slots (multi_lut.h); log_n: of the ring
+    unsigned log_n;
 };
 
 // One workgroup per gate, lanes on consecutive words of the ciphertext: every term is one coalesced read of a wire row.  The term list, the
 // coefficients and the constant depend on blockIdx.x alone, so their loads are wave-uniform.  A wire word is reduced before it is used (an
 // input ciphertext may hold words at or above p; bootstrap outputs are canonical); products and sums are canonical in, canonical out.
+// SNAP (programs with multi-output gates): every word of the canonical sum is rounded by the gate's own slots_log before it is stored; the
+// variant without it is the kernel as it was.
+template <bool SNAP>
 __global__ void __launch_bounds__(256) lwe_combine_kernel(CombineArgs a) {
     const unsigned g = a.gate0 + blockIdx.x;
     const u64 t0 = a.first[g], t1 = a.first[g + 1];
     const u64 c = a.cst[g];
     u64* out = a.out + (size_t)blockIdx.x * a.words;
+    const unsigned sl = SNAP ? a.slots[g] : 0;
     for (unsigned j = threadIdx.x; j < a.words; j += 256) {
         u64 s = j + 1 == a.words ? c : 0;
         for (u64 t = t0; t < t1; ++t) s = gl::add(s, gl::mul(a.coef[t], gl::canon(a.wires[(size_t)a.src[t] * a.words + j])));
-        out[j] = s;
+        out[j] = SNAP ? multi_lut::snap(s, a.log_n, sl) : s;
     }
 }
 
@@ -78,12 +92,16 @@ struct CombineBatchArgs {
     u64* out;               // [count][words]: row 0 is row `row0` of the level's block
     size_t instances;
     unsigned row0, gate0, width, words;   // gate0: the level's first permuted gate; width: gates of the level
+    const u32* slots;       // SNAP only, as CombineArgs (permuted order)
+    unsigned log_n;
 };
 
 // lwe_combine_kernel for the rows of one level of MANY instances: one workgroup per (instance, gate) row, lanes on consecutive words.  Row r
 // of the level's block is gate gate0 + r % width of the instance at sorted position r / width; the term list, the coefficients, the
 // constant and the source rows depend on blockIdx.x alone (wave-uniform), and a term is one coalesced read of a wire row.  The same
-// arithmetic in the same order: canonical on read, canonical products and sums, the constant in the body only.
+// arithmetic in the same order: canonical on read, canonical products and sums, the constant in the body only.  A term's block is a level's
+// block of OUTPUT rows (as wide as the level has gates when every gate has one output); SNAP as in lwe_combine_kernel.
+template <bool SNAP>
 __global__ void __launch_bounds__(256) lwe_combine_batch_kernel(CombineBatchArgs a) {
     const unsigned r = a.row0 + blockIdx.x;
     const size_t inst = r / a.width;
@@ -91,6 +109,7 @@ __global__ void __launch_bounds__(256) lwe_combine_batch_kernel(CombineBatchArgs
     const u64 t0 = a.first[g], t1 = a.first[g + 1];
     const u64 c = a.cst[g];
     u64* out = a.out + (size_t)blockIdx.x * a.words;
+    const unsigned sl = SNAP ? a.slots[g] : 0;
     for (unsigned j = threadIdx.x; j < a.words; j += 256) {
         u64 s = j + 1 == a.words ? c : 0;
         for (u64 t = t0; t < t1; ++t) {
@@ -98,12 +117,12 @@ __global__ void __launch_bounds__(256) lwe_combine_batch_kernel(CombineBatchArgs
             const size_t row = a.instances * l[0] + inst * l[1] + l[2];
             s = gl::add(s, gl::mul(a.coef[t], gl::canon(a.wires[row * a.words + j])));
         }
-        out[j] = s;
+        out[j] = SNAP ? multi_lut::snap(s, a.log_n, sl) : s;
     }
 }
 
 struct CombineRowsArgs {
-    const u64* wires;       // [instances][n_in] input rows, then [instances][n_gates] gate-output rows
+    const u64* wires;       // [instances][n_in] input rows, then [instances][n_outs] gate-output rows
     const u64* first;       // [n_gates + 1], the caller's order
     const u32* src;         // [n_terms]: wires of the caller's numbering
     const u64* coef;        // [n_terms]
@@ -111,27 +130,32 @@ struct CombineRowsArgs {
     u64* out;               // [instances * n_gates][words]
     size_t instances;
     unsigned n_in, n_gates, words;
+    unsigned n_outs;        // output wires per instance: n_gates when every gate has one
+    const u32* slots;       // SNAP only, as CombineArgs (the caller's order)
+    unsigned log_n;
 };
 
 // lwe_combine_kernel for ALL gates of MANY instances in the caller's order (verification has no level order): one workgroup per row
 // b * n_gates + g, lanes on consecutive words.  Wire w of instance b is row b * n_in + w of the input block for w < n_in, else row
-// b * n_gates + (w - n_in) of the gate block behind it; the term list, the coefficients, the constant and the source rows depend on
+// b * n_outs + (w - n_in) of the block of gate outputs behind it; the term list, the coefficients, the constant and the source rows depend on
 // blockIdx.x alone (wave-uniform).  The same arithmetic in the same order: canonical on read, canonical products and sums, the constant in
-// the body only.
+// the body only.  SNAP as in lwe_combine_kernel.
+template <bool SNAP>
 __global__ void __launch_bounds__(256) lwe_combine_rows_kernel(CombineRowsArgs a) {
     const size_t b = blockIdx.x / a.n_gates;
     const unsigned g = blockIdx.x % a.n_gates;
     const u64 t0 = a.first[g], t1 = a.first[g + 1];
     const u64 c = a.cst[g];
     u64* out = a.out + (size_t)blockIdx.x * a.words;
+    const unsigned sl = SNAP ? a.slots[g] : 0;
     for (unsigned j = threadIdx.x; j < a.words; j += 256) {
         u64 s = j + 1 == a.words ? c : 0;
         for (u64 t = t0; t < t1; ++t) {
             const u32 w = a.src[t];
-            const size_t row = w < a.n_in ? b * a.n_in + w : a.instances * a.n_in + b * a.n_gates + (w - a.n_in);
+            const size_t row = w < a.n_in ? b * a.n_in + w : a.instances * a.n_in + b * a.n_outs + (w - a.n_in);
             s = gl::add(s, gl::mul(a.coef[t], gl::canon(a.wires[row * a.words + j])));
         }
-        out[j] = s;
+        out[j] = SNAP ? multi_lut::snap(s, a.log_n, sl) : s;
     }
 }
 
@@ -173,6 +197,14 @@ struct vpbs_program {
     vpbs::DeviceCsr d_given, d_perm;   // d_perm.src: rows of the permuted wire table
     u32 *d_wire_pos = nullptr, *d_gate_pos = nullptr;   // caller's wire / gate -> row of the permuted wire table / permuted position
     u32* d_term_loc = nullptr;         // [n_terms][3], permuted term order: where a batched evaluation finds the term's source (run_batch)
+    // multi-output gates (vpbs_program_create_multi): gate g has outs[g] output wires n_inputs + out_first[g] + j, its input is snapped by
+    // slots[g].  multi is false for a description in which every gate is (0, 1): such a program IS one made by vpbs_program_create.
+    bool multi = false;
+    unsigned n_outs = 0;               // sum of outs: n_gates when !multi
+    std::vector<u32> slots, out_first; // [n_gates], [n_gates + 1], caller's order
+    std::vector<u32> pout_first;       // [n_gates + 1]: prefix sums of outs in permuted order (rows of the permuted wire table behind the inputs)
+    u32 *d_given_slots = nullptr, *d_perm_slots = nullptr;   // multi only
+    u32 *d_given_ext = nullptr, *d_perm_ext = nullptr;       // multi only: index [n_outs] | src gate [n_outs] of every output row, both orders
     std::vector<void*> owned;
 
     ~vpbs_program() {
@@ -201,9 +233,21 @@ struct vpbs_program {
 
 namespace vpbs {
 namespace {
-void launch_combine(hipStream_t s, const u64* d_wires, const DeviceCsr& d, unsigned gate0, unsigned count, unsigned words, u64* d_out) {
-    const CombineArgs a{d_wires, d.first, d.src, d.coef, d.cst, d_out, gate0, words};
-    hipLaunchKernelGGL(lwe_combine_kernel, dim3(count), dim3(256), 0, s, a);
+void launch_combine(hipStream_t s, const u64* d_wires, const DeviceCsr& d, unsigned gate0, unsigned count, unsigned words, u64* d_out,
+                    const u32* d_slots = nullptr, unsigned log_n = 0) {
+    const CombineArgs a{d_wires, d.first, d.src, d.coef, d.cst, d_out, gate0, words, d_slots, log_n};
+    if (d_slots) hipLaunchKernelGGL(lwe_combine_kernel<true>, dim3(count), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(lwe_combine_kernel<false>, dim3(count), dim3(256), 0, s, a);
+}
+// a gate's slots against the ring of the object that evaluates or verifies it: false, with the message that names the gate
+bool slots_fit(const vpbs_program* prog, unsigned log_n, std::string* msg) {
+    for (unsigned g = 0; g < prog->n_gates && prog->multi; ++g)
+        if (prog->slots[g] > log_n) {
+            *msg = "gate " + std::to_string(g) + ": 2^gate_log_slots = 2^" + std::to_string(prog->slots[g]) + " exceeds N = " +
+                   std::to_string((size_t)1 << log_n);
+            return false;
+        }
+    return true;
 }
 void launch_gather(hipStream_t s, const u64* d_src, const u32* d_map, size_t words, unsigned rows, u64* d_dst) {
     hipLaunchKernelGGL(gather_rows_kernel, dim3(rows), dim3(256), 0, s, d_src, d_map, words, d_dst);
@@ -234,9 +278,15 @@ long program_run(vpbs_program* prog, vpbs_bootstrapper* b, const u64* inputs, co
     bootstrapper_shape(b, &sh);
     vpbs_ctx* ctx = sh.ctx;
     const unsigned n_in = prog->n_inputs, n_gates = prog->n_gates, words = sh.n_lwe + 1;
-    const size_t n = (size_t)1 << sh.prm.log_N, kn = sh.prm.K * n, n_wires = (size_t)n_in + n_gates;
+    const size_t n = (size_t)1 << sh.prm.log_N, kn = sh.prm.K * n, n_wires = (size_t)n_in + prog->n_outs;
+    const bool multi = prog->multi;
+    const std::vector<u32>& pof = prog->pout_first;
     if (ctx->device != prog->ctx->device) return ctx->err = "the program and the Bootstrapper are on different devices", VPBS_ERR_INVALID;
     if ((n_in && !inputs) || (n_gates && !testvs)) return ctx->err = "null inputs or testvs", VPBS_ERR_INVALID;
+    {
+        std::string msg;
+        if (!slots_fit(prog, sh.prm.log_N, &msg)) return ctx->err = msg, VPBS_ERR_INVALID;
+    }
     int rc = VPBS_OK;
     try {
         VPBS_HIP(hipSetDevice(ctx->device));
@@ -246,7 +296,7 @@ long program_run(vpbs_program* prog, vpbs_bootstrapper* b, const u64* inputs, co
             // the wire table in permuted order: inputs, then the gates level by level
             u64* d_wires = mem.words(n_wires * words);
             u64* d_cts = mem.words((size_t)n_gates * words);
-            u64* d_out = out_cts ? mem.words((size_t)n_gates * kn) : nullptr;
+            u64* d_out = out_cts || multi ? mem.words((size_t)n_gates * kn) : nullptr;   // multi: the wires are extracted from it
             const size_t chunk_max = std::min<size_t>(sh.max_batch, std::max(1u, n_gates));
             u64* d_tv = mem.words(chunk_max * n);
             const u64* d_testvs = testvs;
@@ -265,12 +315,21 @@ long program_run(vpbs_program* prog, vpbs_bootstrapper* b, const u64* inputs, co
                     const unsigned c = (unsigned)std::min<size_t>(sh.max_batch, prog->level_first[lv + 1] - q0);
                     {
                         vpbs::Timed t(ctx, "lwe_combine");
-                        launch_combine(s, d_wires, prog->d_perm, (unsigned)q0, c, words, d_cts + q0 * words);
+                        launch_combine(s, d_wires, prog->d_perm, (unsigned)q0, c, words, d_cts + q0 * words, multi ? prog->d_perm_slots : nullptr,
+                                       sh.prm.log_N);
                     }
                     launch_gather(s, d_testvs, prog->d_perm.lut + q0, n, c, d_tv);
                     VPBS_HIP(hipGetLastError());
-                    bootstrapper_enqueue(b, d_cts + q0 * words, c, d_tv, 1, d_out ? d_out + q0 * kn : nullptr, d_wires + ((size_t)n_in + q0) * words,
-                                         nullptr);
+                    if (!multi) {
+                        bootstrapper_enqueue(b, d_cts + q0 * words, c, d_tv, 1, d_out ? d_out + q0 * kn : nullptr,
+                                             d_wires + ((size_t)n_in + q0) * words, nullptr);
+                        continue;
+                    }
+                    // out_ct only; the chunk's output rows (contiguous in the permuted table) are extracted from it behind the launch
+                    bootstrapper_enqueue(b, d_cts + q0 * words, c, d_tv, 1, d_out + q0 * kn, nullptr, nullptr);
+                    vpbs::Timed t(ctx, "lwe_extract_at");
+                    lwe_extract_at_enqueue(s, d_out, prog->d_perm_ext + pof[q0], prog->d_perm_ext + prog->n_outs + pof[q0], sh.prm.log_N, sh.prm.K,
+                                           sh.n_lwe, pof[q0 + c] - pof[q0], d_wires + ((size_t)n_in + pof[q0]) * words);
                 }
             }
             // back into the caller's order, to where the caller wants it
@@ -283,7 +342,7 @@ long program_run(vpbs_program* prog, vpbs_bootstrapper* b, const u64* inputs, co
             };
             deliver(wires_out, d_wires, prog->d_wire_pos, words, n_wires);
             deliver(gate_cts_out, d_cts, prog->d_gate_pos, words, n_gates);
-            deliver(out_cts, d_out, prog->d_gate_pos, kn, n_gates);
+            deliver(out_cts, out_cts ? d_out : nullptr, prog->d_gate_pos, kn, n_gates);
             VPBS_HIP(vpbs::stream_sync(s));   // the one wait
         } catch (const DeviceError&) {
             (void)vpbs::stream_sync(s);
@@ -313,8 +372,14 @@ long program_run_batch(vpbs_program* prog, vpbs_keyring* ring, const u64* inputs
     if (!prog) return refuse("vpbs_program_run_batch: null program");
     if (!prog->ctx) return refuse("vpbs_program_run_batch: a host-only program (made without a context) cannot be evaluated");
     const unsigned n_in = prog->n_inputs, n_gates = prog->n_gates, words = sh.n_lwe + 1;
-    const size_t n = (size_t)1 << sh.prm.log_N, kn = sh.prm.K * n, n_wires = (size_t)n_in + n_gates, B = instances;
+    const size_t n = (size_t)1 << sh.prm.log_N, kn = sh.prm.K * n, n_outs = prog->n_outs, n_wires = (size_t)n_in + n_outs, B = instances;
+    const bool multi = prog->multi;
+    const std::vector<u32>& pof = prog->pout_first;
     if (ctx->device != prog->ctx->device) return refuse("vpbs_program_run_batch: the program and the ring are on different devices");
+    {
+        std::string fit;
+        if (!slots_fit(prog, sh.prm.log_N, &fit)) return refuse("vpbs_program_run_batch: " + fit);
+    }
     if (B && ((n_in && !inputs) || (n_gates && !testvs) || !key_of)) return refuse("vpbs_program_run_batch: null inputs, testvs or key_of");
     if (n_wires && B > 0x7fffffffull / n_wires) return refuse("vpbs_program_run_batch: instances x wires exceeds 2^31 - 1 rows");
     std::string msg;
@@ -351,9 +416,27 @@ long program_run_batch(vpbs_program* prog, vpbs_keyring* ring, const u64* inputs
     const size_t chunk_max = std::max<size_t>(1, std::min<size_t>(sh.max_batch, B * widest)), rows_g = B * n_gates, rows_w = B * n_wires;
     const bool want_gates = gate_cts_out || out_cts;
     // identity [chunk_max] | key_of of every gate row | gate_lut of every gate row | input rows | caller's wire rows | caller's gate rows
+    // multi: | extraction index of every output row | its gate row -- both in the order of the level-major block of outputs
     const size_t o_key = chunk_max, o_lut = o_key + rows_g, o_in = o_lut + rows_g, o_wire = o_in + B * n_in,
-                 o_gate = o_wire + (wires_out ? rows_w : 0), total = o_gate + (want_gates ? rows_g : 0);
+                 o_gate = o_wire + (wires_out ? rows_w : 0), o_ext = o_gate + (want_gates ? rows_g : 0), total = o_ext + (multi ? 2 * B * n_outs : 0);
     std::vector<u32> idx(total);   // lives until the wait
+    // row of output 0 of gate-row r (instance position r / w, gate lf[lv] + r % w) of level lv among the output rows of the level-major
+    // table; r = B * w gives the end of the level's block
+    auto out_row = [&](unsigned lv, size_t r) {
+        const size_t w = lf[lv + 1] - lf[lv];
+        return B * pof[lf[lv]] + (r / w) * (pof[lf[lv + 1]] - pof[lf[lv]]) + (pof[lf[lv] + r % w] - pof[lf[lv]]);
+    };
+    if (multi)
+        for (unsigned lv = 0; lv < prog->n_levels; ++lv) {
+            const size_t w = lf[lv + 1] - lf[lv];
+            for (size_t r = 0; r < B * w; ++r) {
+                const size_t o = out_row(lv, r), m = pof[lf[lv] + r % w + 1] - pof[lf[lv] + r % w];
+                for (size_t j = 0; j < m; ++j) {
+                    idx[o_ext + o + j] = (u32)j;
+                    idx[o_ext + B * n_outs + o + j] = (u32)(B * lf[lv] + r);
+                }
+            }
+        }
     for (size_t i = 0; i < chunk_max; ++i) idx[i] = (u32)i;
     for (unsigned lv = 0; lv < prog->n_levels; ++lv) {
         const size_t w = lf[lv + 1] - lf[lv], base = B * lf[lv];
@@ -372,7 +455,13 @@ long program_run_batch(vpbs_program* prog, vpbs_keyring* ring, const u64* inputs
     for (size_t b = 0; b < B; ++b) {
         if (wires_out) {
             for (unsigned w = 0; w < n_in; ++w) idx[o_wire + b * n_wires + w] = (u32)((size_t)pos_of[b] * n_in + w);
-            for (unsigned g = 0; g < n_gates; ++g) idx[o_wire + b * n_wires + n_in + g] = (u32)(B * n_in + gate_row(b, g));
+            for (unsigned g = 0; g < n_gates && !multi; ++g) idx[o_wire + b * n_wires + n_in + g] = (u32)(B * n_in + gate_row(b, g));
+            for (unsigned g = 0; g < n_gates && multi; ++g) {   // the gate's outputs lie side by side in its level's block of outputs
+                const unsigned lv = prog->level[g] - 1;
+                const size_t o = out_row(lv, (size_t)pos_of[b] * (lf[lv + 1] - lf[lv]) + (gate_pos[g] - lf[lv]));
+                for (u32 j = prog->out_first[g]; j < prog->out_first[g + 1]; ++j)
+                    idx[o_wire + b * n_wires + n_in + j] = (u32)(B * n_in + o + (j - prog->out_first[g]));
+            }
         }
         if (want_gates)
             for (unsigned g = 0; g < n_gates; ++g) idx[o_gate + b * n_gates + g] = (u32)gate_row(b, g);
@@ -387,7 +476,7 @@ long program_run_batch(vpbs_program* prog, vpbs_keyring* ring, const u64* inputs
             VPBS_HIP(hipMemcpyAsync(d_idx, idx.data(), sizeof(u32) * total, hipMemcpyHostToDevice, s));   // once, before the first launch
             u64* d_wires = mem.words(rows_w * words);
             u64* d_cts = mem.words(rows_g * words);
-            u64* d_out = out_cts ? mem.words(rows_g * kn) : nullptr;
+            u64* d_out = out_cts || multi ? mem.words(rows_g * kn) : nullptr;   // multi: the wires are extracted from it
             u64* d_tv = mem.words(chunk_max * n);
             const u64 *d_testvs = testvs, *d_inputs = inputs;
             if (!on_device) {
@@ -412,14 +501,24 @@ long program_run_batch(vpbs_program* prog, vpbs_keyring* ring, const u64* inputs
                     {
                         vpbs::Timed t(ctx, "lwe_combine");
                         const CombineBatchArgs a{d_wires, prog->d_perm.first, prog->d_term_loc, prog->d_perm.coef, prog->d_perm.cst, cts, B,
-                                                 (unsigned)r0, lf[lv], (unsigned)w, words};
-                        hipLaunchKernelGGL(lwe_combine_batch_kernel, dim3(c), dim3(256), 0, s, a);
+                                                 (unsigned)r0, lf[lv], (unsigned)w, words, multi ? prog->d_perm_slots : nullptr, sh.prm.log_N};
+                        if (multi) hipLaunchKernelGGL(lwe_combine_batch_kernel<true>, dim3(c), dim3(256), 0, s, a);
+                        else hipLaunchKernelGGL(lwe_combine_batch_kernel<false>, dim3(c), dim3(256), 0, s, a);
                     }
                     launch_gather(s, d_testvs, d_idx + o_lut + base + r0, n, c, d_tv);
                     VPBS_HIP(hipGetLastError());
                     // the rows are in slot order already: the identity as `order`, the rows' own slots as `key_of`
-                    keyring_enqueue(ring, cts, c, d_tv, 1, d_idx, d_idx + o_key + base + r0, d_out ? d_out + (base + r0) * kn : nullptr,
-                                    d_wires + (B * n_in + base + r0) * words, nullptr);
+                    if (!multi) {
+                        keyring_enqueue(ring, cts, c, d_tv, 1, d_idx, d_idx + o_key + base + r0, d_out ? d_out + (base + r0) * kn : nullptr,
+                                        d_wires + (B * n_in + base + r0) * words, nullptr);
+                        continue;
+                    }
+                    // out_ct only; the chunk's output rows are a contiguous piece of the level's block of outputs
+                    keyring_enqueue(ring, cts, c, d_tv, 1, d_idx, d_idx + o_key + base + r0, d_out + (base + r0) * kn, nullptr, nullptr);
+                    const size_t o0 = out_row(lv, r0), o1 = out_row(lv, r0 + c);
+                    vpbs::Timed t(ctx, "lwe_extract_at");
+                    lwe_extract_at_enqueue(s, d_out, d_idx + o_ext + o0, d_idx + o_ext + B * n_outs + o0, sh.prm.log_N, sh.prm.K, sh.n_lwe, o1 - o0,
+                                           d_wires + (B * n_in + o0) * words);
                 }
             }
             // back into the caller's instance and gate order, to where the caller wants it
@@ -435,7 +534,7 @@ long program_run_batch(vpbs_program* prog, vpbs_keyring* ring, const u64* inputs
             };
             deliver(wires_out, d_wires, d_idx + o_wire, words, rows_w);
             deliver(gate_cts_out, d_cts, d_idx + o_gate, words, rows_g);
-            deliver(out_cts, d_out, d_idx + o_gate, kn, rows_g);
+            deliver(out_cts, out_cts ? d_out : nullptr, d_idx + o_gate, kn, rows_g);
             VPBS_HIP(vpbs::stream_sync(s));   // the one wait
         } catch (const DeviceError&) {
             (void)vpbs::stream_sync(s);
@@ -447,12 +546,9 @@ long program_run_batch(vpbs_program* prog, vpbs_keyring* ring, const u64* inputs
     }
     return rc == VPBS_OK ? (long)prog->n_levels : rc;
 }
-}  // namespace
-}  // namespace vpbs
-
-extern "C" {
-int vpbs_program_create(vpbs_ctx* ctx, const vpbs_program_desc* desc, vpbs_program** out, char* err, size_t err_len) {
-    using namespace vpbs;
+// vpbs_program_create (slots_in, outs_in null: every gate (0, 1)) and vpbs_program_create_multi
+int program_create(vpbs_ctx* ctx, const vpbs_program_desc* desc, const unsigned* slots_in, const unsigned* outs_in, vpbs_program** out, char* err,
+                   size_t err_len) {
     if (out) *out = nullptr;
     auto refuse = [&](const std::string& m) {
         report(err, err_len, m);
@@ -465,18 +561,29 @@ int vpbs_program_create(vpbs_ctx* ctx, const vpbs_program_desc* desc, vpbs_progr
     if (n_gates && (!desc->gate_first || !desc->gate_const || !desc->gate_lut)) return refuse("null argument");
     if (T && (!desc->term_src || !desc->term_coef || !n_gates)) return refuse("null argument");
     if ((u64)n_in + n_gates > 0x7fffffffull) return refuse("too many wires");
+    const bool described = slots_in || outs_in;
+    if (described && n_gates && (!slots_in || !outs_in)) return refuse("null argument");
     // ---- validity, gate by gate ----
     if (n_gates && desc->gate_first[0] != 0) return refuse("gate 0: gate_first does not start at 0");
+    std::vector<u32> out_first(n_gates + 1, 0);   // output j of gate g is wire n_inputs + out_first[g] + j
+    bool multi = false;
     for (unsigned g = 0; g < n_gates; ++g) {
         const std::string gate = "gate " + std::to_string(g) + ": ";
+        const unsigned sl = described ? slots_in[g] : 0, m = described ? outs_in[g] : 1;
+        if (sl > 16) return refuse(gate + "gate_log_slots " + std::to_string(sl) + " exceeds 16");
+        if (m == 0) return refuse(gate + "gate_outputs is 0");
+        if (m > (1u << sl)) return refuse(gate + "gate_outputs " + std::to_string(m) + " exceeds 2^gate_log_slots = " + std::to_string(1u << sl));
+        if ((u64)n_in + out_first[g] + m > 0x7fffffffull) return refuse(gate + "too many wires");
+        out_first[g + 1] = out_first[g] + m;
+        multi = multi || sl != 0 || m != 1;
         const u64 t0 = desc->gate_first[g], t1 = desc->gate_first[g + 1];
         if (t1 < t0 || t1 > T) return refuse(gate + "gate_first is not monotone within [0, n_terms]");
         if (desc->gate_lut[g] >= desc->n_luts) return refuse(gate + "gate_lut " + std::to_string(desc->gate_lut[g]) + " is not below n_luts");
         if (desc->gate_const[g] >= gl::P) return refuse(gate + "gate_const is not below p");
         for (u64 t = t0; t < t1; ++t) {
-            if (desc->term_src[t] >= (u64)n_in + g)
+            if (desc->term_src[t] >= (u64)n_in + out_first[g])   // out_first[g] = g when every gate has one output
                 return refuse(gate + "term " + std::to_string(t - t0) + " reads wire " + std::to_string(desc->term_src[t]) +
-                              ", which is not below n_inputs + " + std::to_string(g) + " (topological order)");
+                              ", which is not below n_inputs + " + std::to_string(out_first[g]) + " (topological order)");
             if (desc->term_coef[t] >= gl::P) return refuse(gate + "term " + std::to_string(t - t0) + ": term_coef is not below p");
         }
     }
@@ -495,11 +602,19 @@ int vpbs_program_create(vpbs_ctx* ctx, const vpbs_program_desc* desc, vpbs_progr
     G.coef.assign(desc->term_coef, desc->term_coef + T);
     G.cst.assign(desc->gate_const, desc->gate_const + n_gates);
     G.lut.assign(desc->gate_lut, desc->gate_lut + n_gates);
+    const unsigned n_outs = out_first[n_gates];
+    p->multi = multi;
+    p->n_outs = n_outs;
+    p->out_first = out_first;
+    p->slots.assign(n_gates, 0);
+    if (described) std::copy(slots_in, slots_in + n_gates, p->slots.begin());
+    std::vector<u32> gate_of(n_outs);   // output wire - n_inputs -> its gate
+    for (unsigned g = 0; g < n_gates; ++g) std::fill(gate_of.begin() + out_first[g], gate_of.begin() + out_first[g + 1], g);
     p->level.resize(n_gates);
     for (unsigned g = 0; g < n_gates; ++g) {
         unsigned lv = 0;
         for (u64 t = G.first[g]; t < G.first[g + 1]; ++t)
-            if (G.src[t] >= n_in) lv = std::max(lv, p->level[G.src[t] - n_in]);
+            if (G.src[t] >= n_in) lv = std::max(lv, p->level[gate_of[G.src[t] - n_in]]);
         p->level[g] = lv + 1;
         p->n_levels = std::max(p->n_levels, lv + 1);
     }
@@ -507,7 +622,7 @@ int vpbs_program_create(vpbs_ctx* ctx, const vpbs_program_desc* desc, vpbs_progr
     for (unsigned g = 0; g < n_gates; ++g) ++p->level_first[p->level[g]];
     for (unsigned lv = 0; lv < p->n_levels; ++lv) p->level_first[lv + 1] += p->level_first[lv];
     p->order.resize(n_gates);
-    std::vector<u32> gate_pos(n_gates), wire_pos((size_t)n_in + n_gates);
+    std::vector<u32> gate_pos(n_gates), wire_pos((size_t)n_in + n_outs);
     {
         std::vector<u32> next(p->level_first.begin(), p->level_first.end());
         for (unsigned g = 0; g < n_gates; ++g) {
@@ -516,8 +631,13 @@ int vpbs_program_create(vpbs_ctx* ctx, const vpbs_program_desc* desc, vpbs_progr
             gate_pos[g] = q;
         }
     }
+    // the permuted wire table: inputs, then the OUTPUTS of the gates level by level (a gate's outputs side by side)
+    std::vector<u32>& pof = p->pout_first;
+    pof.assign(n_gates + 1, 0);
+    for (unsigned q = 0; q < n_gates; ++q) pof[q + 1] = pof[q] + (out_first[p->order[q] + 1] - out_first[p->order[q]]);
     for (unsigned w = 0; w < n_in; ++w) wire_pos[w] = w;
-    for (unsigned g = 0; g < n_gates; ++g) wire_pos[n_in + g] = n_in + gate_pos[g];
+    for (unsigned g = 0; g < n_gates; ++g)
+        for (u32 j = out_first[g]; j < out_first[g + 1]; ++j) wire_pos[n_in + j] = n_in + pof[gate_pos[g]] + (j - out_first[g]);
     if (ctx) {
         Csr R;   // the permuted description; sources are rows of the permuted wire table
         std::vector<u32> term_loc;   // per term of R: the source's block in a level-major table (first row per instance, width, position)
@@ -531,8 +651,9 @@ int vpbs_program_create(vpbs_ctx* ctx, const vpbs_program_desc* desc, vpbs_progr
                 if (row < n_in) {
                     term_loc.insert(term_loc.end(), {0u, n_in, row});
                 } else {
-                    const unsigned lv = p->level[G.src[t] - n_in] - 1;
-                    term_loc.insert(term_loc.end(), {n_in + p->level_first[lv], p->level_first[lv + 1] - p->level_first[lv], row - n_in - p->level_first[lv]});
+                    const unsigned lv = p->level[gate_of[G.src[t] - n_in]] - 1;
+                    const u32 o0 = pof[p->level_first[lv]], o1 = pof[p->level_first[lv + 1]];   // the level's block of outputs
+                    term_loc.insert(term_loc.end(), {n_in + o0, o1 - o0, row - n_in - o0});
                 }
             }
             R.first.push_back(R.src.size());
@@ -547,6 +668,22 @@ int vpbs_program_create(vpbs_ctx* ctx, const vpbs_program_desc* desc, vpbs_progr
             p->d_wire_pos = p->upload(wire_pos);
             p->d_gate_pos = p->upload(gate_pos);
             p->d_term_loc = p->upload(term_loc);
+            if (multi) {
+                std::vector<u32> perm_slots(n_gates), given_ext(2 * (size_t)n_outs), perm_ext(2 * (size_t)n_outs);
+                for (unsigned q = 0; q < n_gates; ++q) {
+                    const unsigned g = p->order[q];
+                    perm_slots[q] = p->slots[g];
+                    for (u32 j = 0; j < out_first[g + 1] - out_first[g]; ++j) {
+                        given_ext[out_first[g] + j] = perm_ext[pof[q] + j] = j;
+                        given_ext[n_outs + out_first[g] + j] = g;
+                        perm_ext[n_outs + pof[q] + j] = q;
+                    }
+                }
+                p->d_given_slots = p->upload(p->slots);
+                p->d_perm_slots = p->upload(perm_slots);
+                p->d_given_ext = p->upload(given_ext);
+                p->d_perm_ext = p->upload(perm_ext);
+            }
             VPBS_HIP(vpbs::stream_sync(ctx->stream));   // the staging vectors go away
         } catch (const DeviceError& e) {
             (void)vpbs::stream_sync(ctx->stream);
@@ -560,8 +697,33 @@ int vpbs_program_create(vpbs_ctx* ctx, const vpbs_program_desc* desc, vpbs_progr
     report(err, err_len, "");
     return VPBS_OK;
 }
+}  // namespace
+}  // namespace vpbs
+
+extern "C" {
+int vpbs_program_create(vpbs_ctx* ctx, const vpbs_program_desc* desc, vpbs_program** out, char* err, size_t err_len) {
+    return vpbs::program_create(ctx, desc, nullptr, nullptr, out, err, err_len);
+}
+
+int vpbs_program_create_multi(vpbs_ctx* ctx, const vpbs_program_desc* desc, const unsigned* gate_log_slots, const unsigned* gate_outputs,
+                              vpbs_program** out, char* err, size_t err_len) {
+    if (desc && desc->n_gates && (!gate_log_slots || !gate_outputs)) {
+        if (out) *out = nullptr;
+        vpbs::report(err, err_len, "null argument");
+        if (ctx) ctx->err = "null argument";
+        return VPBS_ERR_INVALID;
+    }
+    static const unsigned none = 0;   // a program without gates: the arrays may be null
+    return vpbs::program_create(ctx, desc, gate_log_slots ? gate_log_slots : &none, gate_outputs ? gate_outputs : &none, out, err, err_len);
+}
 
 void vpbs_program_free(vpbs_program* prog) { delete prog; }
+
+long vpbs_program_wires(const vpbs_program* prog, unsigned* out_first_out) {
+    if (!prog) return VPBS_ERR_INVALID;
+    if (out_first_out) std::copy(prog->out_first.begin(), prog->out_first.end(), out_first_out);
+    return (long)prog->n_inputs + (long)prog->n_outs;
+}
 
 long vpbs_program_levels(const vpbs_program* prog, unsigned* levels_out) {
     if (!prog) return VPBS_ERR_INVALID;
@@ -662,21 +824,30 @@ long vpbs_program_verify(vpbs_program* prog, vpbs_pbs_verifier* pbs_verifier, co
     while (((size_t)1 << log_n) < n) ++log_n;
     if (((size_t)1 << log_n) != n || sh.K < 2 || sh.n_lwe == 0 || sh.n_lwe > (sh.K - 1) * n)
         return ctx->err = "the verifier's shape has no sample extraction (N a power of two, 1 <= n_lwe <= (K - 1) N)", VPBS_ERR_INVALID;
+    {
+        std::string msg;
+        if (!slots_fit(prog, log_n, &msg)) return ctx->err = msg, VPBS_ERR_INVALID;
+    }
+    const bool multi = prog->multi;
+    const size_t n_outs = prog->n_outs;
     std::vector<u64> cts((size_t)n_gates * words), tv((size_t)n_gates * n);
     try {
         VPBS_HIP(hipSetDevice(ctx->device));
         hipStream_t s = ctx->stream;
         Scratch mem(ctx);
         try {
-            u64* d_wires = mem.words(((size_t)n_in + n_gates) * words);   // the caller's order: inputs, then the extractions
+            u64* d_wires = mem.words(((size_t)n_in + n_outs) * words);   // the caller's order: inputs, then the extractions
             u64* d_out = mem.words((size_t)n_gates * kn);
             u64* d_cts = mem.words((size_t)n_gates * words);
             if (n_in) VPBS_HIP(hipMemcpyAsync(d_wires, inputs, 8 * (size_t)n_in * words, hipMemcpyHostToDevice, s));
             VPBS_HIP(hipMemcpyAsync(d_out, out_cts, 8 * (size_t)n_gates * kn, hipMemcpyHostToDevice, s));
-            lwe_extract_enqueue(s, d_out, log_n, sh.K, sh.n_lwe, n_gates, d_wires + (size_t)n_in * words);
+            if (!multi) lwe_extract_enqueue(s, d_out, log_n, sh.K, sh.n_lwe, n_gates, d_wires + (size_t)n_in * words);
+            else   // every (gate, j) row in one launch
+                lwe_extract_at_enqueue(s, d_out, prog->d_given_ext, prog->d_given_ext + n_outs, log_n, sh.K, sh.n_lwe, n_outs,
+                                       d_wires + (size_t)n_in * words);
             {
-                vpbs::Timed t(ctx, "lwe_combine");
-                launch_combine(s, d_wires, prog->d_given, 0, n_gates, words, d_cts);   // all gates at once: no level order
+                vpbs::Timed t(ctx, "lwe_combine");   // all gates at once: no level order
+                launch_combine(s, d_wires, prog->d_given, 0, n_gates, words, d_cts, multi ? prog->d_given_slots : nullptr, log_n);
             }
             VPBS_HIP(hipGetLastError());
             VPBS_HIP(hipMemcpyAsync(cts.data(), d_cts, 8 * cts.size(), hipMemcpyDeviceToHost, s));
@@ -719,7 +890,8 @@ long vpbs_program_verify_batch(vpbs_program* prog, vpbs_ring_verifier* ring_veri
     ring_verifier_shape(ring_verifier, &sh);
     vpbs_ctx* ctx = sh.ctx;
     const unsigned n_in = prog->n_inputs, n_gates = prog->n_gates, words = sh.n_lwe + 1;
-    const size_t n = sh.N, kn = (size_t)sh.K * n, n_wires = (size_t)n_in + n_gates, B = instances, rows = B * n_gates;
+    const size_t n = sh.N, kn = (size_t)sh.K * n, n_outs = prog->n_outs, n_wires = (size_t)n_in + n_outs, B = instances, rows = B * n_gates;
+    const bool multi = prog->multi;
     if (ctx->device != prog->ctx->device) return refuse(who + ": the program and the ring verifier are on different devices");
     if (n_wires && B > 0x7fffffffull / n_wires) return refuse(who + ": instances x wires exceeds 2^31 - 1 rows");
     if (B && !key_of) return refuse(who + ": null key_of");
@@ -730,16 +902,22 @@ long vpbs_program_verify_batch(vpbs_program* prog, vpbs_ring_verifier* ring_veri
     if (((size_t)1 << log_n) != n || sh.K < 2 || sh.n_lwe == 0 || sh.n_lwe > (sh.K - 1) * n)
         return refuse(who + ": the verifier's shape has no sample extraction (N a power of two, 1 <= n_lwe <= (K - 1) N)");
     std::string msg;
+    if (!slots_fit(prog, log_n, &msg)) return refuse(who + ": " + msg);
     if (!ring_verifier_check_slots(ring_verifier, key_of, B, who.c_str(), "instance", &msg)) return refuse(msg);
     for (size_t r = 0; r < rows; ++r)
         if (offsets[r + 1] < offsets[r]) return refuse(who + ": offsets decrease at row " + std::to_string(r));
     if (rows == 0) return 0;
-    // testv_of | key_of of every row, uploaded once
-    std::vector<u32> idx(2 * rows);   // lives until the last wait
+    // testv_of | key_of of every row, uploaded once; multi: | extraction index | claimed GLWE of every output row b * n_outs + o
+    const size_t o_ext = 2 * rows, total = o_ext + (multi ? 2 * B * n_outs : 0);
+    std::vector<u32> idx(total);   // lives until the last wait
     for (size_t b = 0; b < B; ++b)
         for (size_t g = 0; g < n_gates; ++g) {
             idx[b * n_gates + g] = prog->given.lut[g];
             idx[rows + b * n_gates + g] = key_of[b];
+            for (u32 o = prog->out_first[g]; multi && o < prog->out_first[g + 1]; ++o) {
+                idx[o_ext + b * n_outs + o] = o - prog->out_first[g];
+                idx[o_ext + B * n_outs + b * n_outs + o] = (u32)(b * n_gates + g);
+            }
         }
     PbsVerifyCore* core = ring_verifier_core(ring_verifier);
     long accepted = 0;
@@ -748,20 +926,25 @@ long vpbs_program_verify_batch(vpbs_program* prog, vpbs_ring_verifier* ring_veri
         hipStream_t s = ctx->stream;
         Scratch mem(ctx);
         try {
-            u64* d_wires = mem.words(B * n_wires * words);   // [B][n_in] inputs, then [B][n_gates] extractions
+            u64* d_wires = mem.words(B * n_wires * words);   // [B][n_in] inputs, then [B][n_outs] extractions
             u64* d_out = mem.words(rows * kn);
             u64* d_cts = mem.words(rows * words);
             u64* d_testvs = mem.words((size_t)prog->n_luts * n);
-            u32* d_idx = reinterpret_cast<u32*>(mem.words(rows));
+            u32* d_idx = reinterpret_cast<u32*>(mem.words((total + 1) / 2));
             if (n_in) VPBS_HIP(hipMemcpyAsync(d_wires, inputs, 8 * B * n_in * words, hipMemcpyHostToDevice, s));
             VPBS_HIP(hipMemcpyAsync(d_out, out_cts, 8 * rows * kn, hipMemcpyHostToDevice, s));
             VPBS_HIP(hipMemcpyAsync(d_testvs, testvs, 8 * (size_t)prog->n_luts * n, hipMemcpyHostToDevice, s));
-            VPBS_HIP(hipMemcpyAsync(d_idx, idx.data(), sizeof(u32) * 2 * rows, hipMemcpyHostToDevice, s));
-            lwe_extract_enqueue(s, d_out, log_n, sh.K, sh.n_lwe, rows, d_wires + B * n_in * words);
+            VPBS_HIP(hipMemcpyAsync(d_idx, idx.data(), sizeof(u32) * total, hipMemcpyHostToDevice, s));
+            if (!multi) lwe_extract_enqueue(s, d_out, log_n, sh.K, sh.n_lwe, rows, d_wires + B * n_in * words);
+            else
+                lwe_extract_at_enqueue(s, d_out, d_idx + o_ext, d_idx + o_ext + B * n_outs, log_n, sh.K, sh.n_lwe, B * n_outs,
+                                       d_wires + B * n_in * words);
             {
                 vpbs::Timed t(ctx, "lwe_combine");
-                const CombineRowsArgs a{d_wires, prog->d_given.first, prog->d_given.src, prog->d_given.coef, prog->d_given.cst, d_cts, B, n_in, n_gates, words};
-                hipLaunchKernelGGL(lwe_combine_rows_kernel, dim3((unsigned)rows), dim3(256), 0, s, a);
+                const CombineRowsArgs a{d_wires, prog->d_given.first, prog->d_given.src, prog->d_given.coef, prog->d_given.cst, d_cts, B, n_in, n_gates,
+                                        words, (unsigned)n_outs, multi ? prog->d_given_slots : nullptr, log_n};
+                if (multi) hipLaunchKernelGGL(lwe_combine_rows_kernel<true>, dim3((unsigned)rows), dim3(256), 0, s, a);
+                else hipLaunchKernelGGL(lwe_combine_rows_kernel<false>, dim3((unsigned)rows), dim3(256), 0, s, a);
             }
             VPBS_HIP(hipGetLastError());
             for (size_t r0 = 0; r0 < rows; r0 += sh.max_batch) {   // a chunk may straddle instances: every row brings its own indices

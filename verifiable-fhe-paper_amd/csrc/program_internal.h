@@ -33,6 +33,10 @@ bool check_start_steps(const uint32_t* start, size_t count, unsigned n_lwe, cons
 void upload_acc_in(vpbs_ctx* ctx, uint64_t* d_acc_in, const uint64_t* acc_in, const uint32_t* start, size_t count, size_t kn);
 // lwe_extract_kernel on device pointers, queued on `stream` (a hipStream_t): GLWEs [count][K][N] -> [count][n_lwe + 1]
 void lwe_extract_enqueue(void* stream, const uint64_t* d_glwe, unsigned log_N, unsigned K, unsigned n_lwe, size_t count, uint64_t* d_lwe_out);
+// lwe_extract_at_kernel (multi_lut.hip) on device pointers, queued on `stream`: row i of d_lwe_out [rows][n_lwe + 1] is the extraction of
+// coefficient d_index[i] of GLWE d_src[i] of d_glwe [..][K][N]; nothing is checked; rows == 0 launches nothing
+void lwe_extract_at_enqueue(void* stream, const uint64_t* d_glwe, const uint32_t* d_index, const uint32_t* d_src, unsigned log_N, unsigned K,
+                            unsigned n_lwe, size_t rows, uint64_t* d_lwe_out);
 
 // the batch prover's own Bootstrapper and the mutex that serialises its runs (vpbs_pbs_prover::boot_mu)
 vpbs_bootstrapper* pbs_prover_bootstrapper(vpbs_pbs_prover* p, std::mutex** boot_mu);
