@@ -206,7 +206,12 @@ typedef struct { /* FriInstanceInfo (oracles are passed separately) */
  *   commit_phase_merkle_caps[n_rounds][2^cap_height][4]
  *   query_round_proofs[q]: initial_trees_proof: per oracle { leaf[ncols_o], siblings[log_lde-cap_height][4] }
  *                          steps[i]: { evals[2 << arity_bits_i], siblings[log(len_i) - cap_height][4] }
- *   final_poly[len][2], pow_witness */
+ *   final_poly[len][2], pow_witness
+ * The parameters are judged as a whole: n_rounds <= 16, arities that never fold below degree 1, every tree of the proof at least as tall as
+ * its cap, log_n + rate_bits <= 24, num_query_rounds <= 128 and n_oracles + n_rounds <= 12.  vpbs_fri_proof_words returns 0 for parameters
+ * that fail (there is no proof to size), and vpbs_fri_prove refuses them with VPBS_ERR_INVALID -- as it does params whose rate_bits or
+ * cap_height are not the context's, and an LDE of 2^24 under cap_height 0 (a tree of 25 levels; 24 can be opened) -- before it queues work,
+ * draws from the challenger or writes to proof_out.  Arity bits above 4 are not covered by the tests. */
 size_t vpbs_fri_proof_words(const vpbs_fri_params* params, unsigned degree_bits, const size_t* ncols, size_t n_oracles);
 /* forced_pow: VPBS_POW_ANY -> smallest valid nonce; otherwise use the given nonce (the reference's rayon find_any
  * may return any valid nonce, so byte parity with a reference proof is conditional on its pow_witness). */

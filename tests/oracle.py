@@ -365,9 +365,17 @@ class ChallengerState:
 
 
 def fri_params(degree_bits, **over):
+    """orc_fri_params_standard with the given fields changed; arity_bits=[...] (a list of at most 16) sets n_rounds and zero-fills the rest"""
     p = FriParams(); lib().orc_fri_params_standard(degree_bits, C.byref(p))
     for k, v in over.items():
-        setattr(p, k, v)
+        if k == "arity_bits":
+            bits = [int(a) for a in v]
+            assert len(bits) <= 16, "the oracle's arity_bits[16] holds 16 rounds"
+            p.n_rounds = len(bits)
+            for i in range(16):
+                p.arity_bits[i] = bits[i] if i < len(bits) else 0
+        else:
+            setattr(p, k, v)
     return p
 
 

@@ -7,6 +7,7 @@ import numpy as np
 
 import oracle as orc
 import pymodel
+from fri_shapes import standard_arities
 from pymodel import P
 
 
@@ -26,12 +27,18 @@ def commit_inputs(inputs, rate_bits=3, cap_height=4):
     }
 
 
+def step_fri_params(log_n, rate_bits=3, cap_height=4, compat=None):
+    """the FRI parameters of a step proof under a FriConfig of this rate and cap height: the rounds follow both (fri_shapes.standard_arities)"""
+    return orc.fri_params(log_n, rate_bits=rate_bits, cap_height=cap_height, arity_bits=standard_arities(log_n, rate_bits, cap_height),
+                          mul_final_by_x=(compat.fri_mul_final_by_x if compat is not None else 0))
+
+
 def prove_step(inputs, circuit_digest, public_inputs, log_n, num_challenges=2, forced_pow=orc.POW_ANY, cs_batch=None,
-               sigmas=None, n_routed=0, n_constants=0, gates=None, compat=None):
+               sigmas=None, n_routed=0, n_constants=0, gates=None, compat=None, rate_bits=3, cap_height=4):
     """sigmas given: the Z / partial-product matrix is computed from the wires and the transcript's betas/gammas
     (all_wires_permutation_partial_products) instead of being read from inputs["zs_partial_products"].
-    compat: an orc.Compat (the switch table, oracle/vpbs_oracle.h); None = the defaults."""
-    rate_bits, cap_height = 3, 4
+    compat: an orc.Compat (the switch table, oracle/vpbs_oracle.h); None = the defaults.
+    rate_bits, cap_height: the FriConfig of every commitment and of the opening proof (the device quotient is stated for rate_bits = 3 only)."""
     cs = cs_batch if cs_batch is not None else orc.Batch(inputs["constants_sigmas"], rate_bits, cap_height, True)
     pi_hash = orc.hash_no_pad(public_inputs)
     wires = orc.Batch(inputs["wires"], rate_bits, cap_height, True)
@@ -62,14 +69,14 @@ def prove_step(inputs, circuit_digest, public_inputs, log_n, num_challenges=2, f
     batches, zeta_next = step_batches(ncols, num_challenges, zeta, log_n)
     openings = np.concatenate([o.eval_ext(zeta) for o in oracles] + [zs.eval_ext(zeta_next)[:num_challenges]])
     ch.observe(openings)
-    params = orc.fri_params(log_n, mul_final_by_x=(compat.fri_mul_final_by_x if compat is not None else 0))
+    params = step_fri_params(log_n, rate_bits, cap_height, compat)
     fri = orc.prove_openings(oracles, batches, ch, params, log_n, forced_pow)
     return {"caps": np.stack([wires.cap(), zs.cap(), quot.cap()]), "openings": openings, "fri": fri,
             "challenger": ch, "challenges": np.array(betas + gammas + alphas + [int(zeta[0]), int(zeta[1])], np.uint64),
             "cs_cap": cs.cap(), "ncols": ncols}
 
 
-def verify_step(proof, cs_cap, ncols, circuit_digest, public_inputs, log_n, num_challenges=2, compat=None):
+def verify_step(proof, cs_cap, ncols, circuit_digest, public_inputs, log_n, num_challenges=2, compat=None, rate_bits=3, cap_height=4):
     """Verifier side of the same transcript + verify_fri_proof (checks a proof without recomputing any commitment)."""
     ch = orc.ChallengerState()
     ch.observe(circuit_digest)
@@ -85,7 +92,7 @@ def verify_step(proof, cs_cap, ncols, circuit_digest, public_inputs, log_n, num_
     openings = [proof["openings"][:total], proof["openings"][total:]]
     ch.observe(proof["openings"])
     caps = [cs_cap, proof["caps"][0], proof["caps"][1], proof["caps"][2]]
-    params = orc.fri_params(log_n, mul_final_by_x=(compat.fri_mul_final_by_x if compat is not None else 0))
+    params = step_fri_params(log_n, rate_bits, cap_height, compat)
     return orc.verify_fri(caps, ncols, batches, openings, ch, params, log_n, proof["fri"])
 
 
@@ -101,7 +108,7 @@ def to_bytes(proof, ncols, n_constants, public_inputs, log_n, num_challenges=2, 
         op[n_cs + n_w + n_z:n_cs + n_w + n_z + n_q], op[n_cs + n_w + n_z + n_q:]
     for part in (cs[:n_constants], cs[n_constants:], w, z[:num_challenges], zn, z[num_challenges:], q):
         put(part)
-    params = orc.fri_params(log_n)
+    params = step_fri_params(log_n, rate_bits, cap_height)
     fri = proof["fri"]
     log_lde = log_n + rate_bits
     pos = 0

@@ -10,7 +10,9 @@ import sys
 import numpy as np
 import pytest
 
+import fri_shapes
 import oracle as orc
+import step_oracle
 import vpbs_amd
 from vpbs_amd import api, sharding, synth
 
@@ -267,6 +269,98 @@ def test_fri_arities_follow_the_supplied_config():
             d -= 4
             rounds += 1
         assert p.n_rounds == rounds
+        assert fri_shapes.standard_arities(log_n) == [4] * rounds == api.standard_arity_bits(log_n)
+    # ... and with the rate and cap height of the caller's configuration: the library (FriParams::standard inside make_proof_shape) agrees
+    # with fri_shapes.standard_arities on every step shape -- it takes a serialised proof of exactly the oracle's length, whose layout
+    # (step_oracle.to_bytes) has the rounds of standard_arities, and refuses one byte less
+    for (log_n, rate, cap_h), rounds in fri_shapes.STEP_SHAPES:
+        assert fri_shapes.standard_arities(log_n, rate, cap_h) == [4] * rounds == api.standard_arity_bits(log_n, rate, cap_h)
+        p, pis, digest = _oracle_step_proof(log_n, rate, cap_h)
+        blob = step_oracle.to_bytes(p, p["ncols"], N_CONSTANTS_STEP, pis, log_n, cap_height=cap_h, rate_bits=rate)
+        back, back_pis = api.step_proof_from_bytes(blob, p["ncols"], log_n, N_CONSTANTS_STEP, rate_bits=rate, cap_height=cap_h)
+        assert back["fri"].size == p["fri"].size and (back_pis == pis).all()
+        with pytest.raises(api.VpbsError):
+            api.step_proof_from_bytes(blob[:-1], p["ncols"], log_n, N_CONSTANTS_STEP, rate_bits=rate, cap_height=cap_h)
+        if rounds != len(fri_shapes.standard_arities(log_n)):   # the standard configuration's rounds would give another length
+            with pytest.raises(api.VpbsError):
+                api.step_proof_from_bytes(blob, p["ncols"], log_n, N_CONSTANTS_STEP)
+
+
+N_CONSTANTS_STEP = 2
+_step_proofs = {}
+
+
+def _oracle_step_proof(log_n, rate, cap_h):
+    """the oracle's step proof of a step shape over synthetic columns (computed once per shape, never changed)"""
+    key = (log_n, rate, cap_h)
+    if key not in _step_proofs:
+        inputs = synth.step_inputs(log_n, cols=fri_shapes.STEP_COLS)
+        pis, digest = synth.field_elements(0xABCD, 11), np.array([11, 22, 33, 44], np.uint64)
+        _step_proofs[key] = (step_oracle.prove_step(inputs, digest, pis, log_n, rate_bits=rate, cap_height=cap_h), pis, digest)
+    return _step_proofs[key]
+
+
+@pytest.mark.parametrize("shape", fri_shapes.FRI_SHAPES, ids=fri_shapes.shape_id)
+def test_fri_proof_words_agree_with_the_oracle_at_every_shape(shape):
+    log_n, rate, cap_h, bits = shape
+    a = api.fri_params(log_n, rate_bits=rate, cap_height=cap_h, arity_bits=bits)
+    b = orc.fri_params(log_n, rate_bits=rate, cap_height=cap_h, arity_bits=bits)
+    assert bytes(a) == bytes(b)   # one struct layout, one meaning of arity_bits=[...]
+    arr = (ctypes.c_size_t * 4)(*fri_shapes.FRI_COLS)
+    words = api.lib().vpbs_fri_proof_words(ctypes.byref(a), log_n, arr, 4)
+    assert words == orc.lib().orc_fri_proof_words(ctypes.byref(b), log_n, arr, 4) and words > 0
+    # closed form: round caps | per query: leaves and paths of the four oracles, then per round the coset and its path | final polynomial | nonce
+    per_q, lg, d = sum(fri_shapes.FRI_COLS) + 4 * 4 * (log_n + rate - cap_h), log_n + rate, log_n
+    for ab in bits:
+        lg, d = lg - ab, d - ab
+        per_q += (2 << ab) + 4 * (lg - cap_h)
+    assert words == len(bits) * (4 << cap_h) + a.num_query_rounds * per_q + (2 << d) + 1
+
+
+def test_fri_proof_words_counts_and_query_rounds_agree_with_the_oracle():
+    for cols in fri_shapes.POLY_COUNTS:
+        a, b = api.fri_params(fri_shapes.POLY_COUNT_LOG_N), orc.fri_params(fri_shapes.POLY_COUNT_LOG_N)
+        arr = (ctypes.c_size_t * 4)(*cols)
+        assert api.lib().vpbs_fri_proof_words(ctypes.byref(a), 6, arr, 4) == orc.lib().orc_fri_proof_words(ctypes.byref(b), 6, arr, 4) > 0
+    for nq in fri_shapes.QUERY_COUNTS:
+        a, b = api.fri_params(6, pow_bits=2, num_query_rounds=nq), orc.fri_params(6, pow_bits=2, num_query_rounds=nq)
+        arr = (ctypes.c_size_t * 4)(*fri_shapes.FRI_COLS)
+        assert api.lib().vpbs_fri_proof_words(ctypes.byref(a), 6, arr, 4) == orc.lib().orc_fri_proof_words(ctypes.byref(b), 6, arr, 4) > 0
+
+
+@pytest.mark.parametrize("name,log_n,over", fri_shapes.REFUSED_SHAPES, ids=[r[0].replace(" ", "_") for r in fri_shapes.REFUSED_SHAPES])
+def test_fri_proof_words_is_zero_for_refused_parameters(name, log_n, over):
+    """parameters that over-fold, outgrow a struct or put a cap above its tree have no word count (the unsigned arithmetic used to wrap into a
+    garbage count, by which the caller sized the proof buffer)"""
+    p = api.fri_params(log_n, **over)
+    arr = (ctypes.c_size_t * 4)(*fri_shapes.FRI_COLS)
+    assert api.lib().vpbs_fri_proof_words(ctypes.byref(p), log_n, arr, 4) == 0
+    ok = api.fri_params(log_n)   # the nearest valid parameters still have one
+    assert api.lib().vpbs_fri_proof_words(ctypes.byref(ok), log_n, arr, 4) > 0
+    if name == "13 trees":       # the count is of trees, not of rounds: the same nine rounds next to three oracles are fine
+        assert api.lib().vpbs_fri_proof_words(ctypes.byref(p), log_n, arr, 3) > 0
+    assert api.lib().vpbs_fri_proof_words(None, log_n, arr, 4) == 0
+
+
+@pytest.mark.parametrize("shape,rounds", fri_shapes.STEP_SHAPES, ids=lambda v: "n%d-r%d-c%d" % v if isinstance(v, tuple) else None)
+def test_host_verifier_on_oracle_step_proofs_at_every_step_shape(shape, rounds):
+    """vpbs_step_proof_from_bytes and vpbs_verify_step (host only) at every (log_n, rate_bits, cap_height): the oracle's proof parses back to
+    the same words and is accepted; five tampered words are rejected"""
+    log_n, rate, cap_h = shape
+    p, pis, digest = _oracle_step_proof(log_n, rate, cap_h)
+    ncols = p["ncols"]
+    blob = step_oracle.to_bytes(p, ncols, N_CONSTANTS_STEP, pis, log_n, cap_height=cap_h, rate_bits=rate)
+    back, back_pis = api.step_proof_from_bytes(blob, ncols, log_n, N_CONSTANTS_STEP, rate_bits=rate, cap_height=cap_h)
+    for key in ("caps", "openings", "fri"):
+        assert (back[key].reshape(-1) == np.asarray(p[key], np.uint64).reshape(-1)).all(), key
+    assert (back_pis == pis).all()
+    assert api.verify_step_fri_only(back, p["cs_cap"], ncols, digest, back_pis, log_n, rate_bits=rate, cap_height=cap_h)
+    n_fri = p["fri"].size
+    for key, pos in (("caps", 5), ("openings", 3), ("fri", 0), ("fri", n_fri // 2), ("fri", n_fri - 2)):
+        bad = {k: back[k].copy() for k in ("caps", "openings", "fri")}
+        flat = bad[key].reshape(-1)
+        flat[pos] = (int(flat[pos]) + 1) % P
+        assert not api.verify_step_fri_only(bad, p["cs_cap"], ncols, digest, back_pis, log_n, rate_bits=rate, cap_height=cap_h), (key, pos)
 
 
 def test_hash_chain_matches_oracle_and_reference_semantics():

@@ -8,6 +8,7 @@ import struct
 import numpy as np
 import pytest
 
+import fri_shapes
 import oracle as orc
 import pymodel
 from pymodel import P
@@ -209,11 +210,13 @@ def test_challenger_matches_model():
             assert ch.get_n(k) == [model.get() for _ in range(k)]
 
 
-def _fri_setup(log_n, cols=(3, 5, 2, 4), rate=3, cap_h=None, **over):
-    params = orc.fri_params(log_n, **over)
+def _fri_setup(log_n, cols=(3, 5, 2, 4), rate=3, cap_h=None, gen=None, **over):
+    """rate / cap_h: the FriConfig of the commitments and of the params (cap_h None: the standard 4); gen: a generator of the case's own"""
+    params = orc.fri_params(log_n, rate_bits=rate, **({} if cap_h is None else {"cap_height": cap_h}), **over)
+    field = rand_field if gen is None else (lambda *shape: gen.integers(0, P, size=shape, dtype=np.uint64))
     oracles = []
     for i, nc in enumerate(cols):
-        oracles.append(orc.Batch(rand_field(nc, 1 << log_n), params.rate_bits, params.cap_height, from_values=(i != 3)))
+        oracles.append(orc.Batch(field(nc, 1 << log_n), params.rate_bits, params.cap_height, from_values=(i != 3)))
     ch = orc.ChallengerState()
     for o in oracles:
         ch.observe(o.cap())
@@ -263,6 +266,83 @@ def test_fri_arity_schedule():
     for d, rounds in ((15, 3), (12, 2), (16, 3)):
         p = orc.fri_params(d)
         assert p.n_rounds == rounds and list(p.arity_bits)[:rounds] == [4] * rounds
+
+
+# ---- FRI off the standard configuration (fri_shapes.py): the reference side of test_gpu_fri_shapes.py, checked against itself.  The
+# oracle's prover folds coefficients, its verifier checks the folds by Lagrange interpolation: two methods, one answer. ----
+def _prove_verify_tamper(log_n, cols, seed, rate=3, cap_h=4, **over):
+    gen = np.random.default_rng(seed)
+    params, oracles, ch, batches, openings = _fri_setup(log_n, cols, rate, cap_h, gen=gen, **over)
+    ch_v = ch.clone()
+    proof = orc.prove_openings(oracles, batches, ch, params, log_n)
+    caps = [o.cap() for o in oracles]; ncols = [o.ncols for o in oracles]
+    ch_v2 = ch_v.clone()
+    assert orc.verify_fri(caps, ncols, batches, openings, ch_v2, params, log_n, proof)
+    assert ch_v2.state_words() == ch.state_words()   # prover and verifier leave the transcript in the same state
+    for pos in [0, proof.size // 2, proof.size - 1] + [int(q) for q in gen.integers(0, proof.size, 20)]:
+        bad = proof.copy(); bad[pos] = (int(bad[pos]) + 1) % P
+        assert not orc.verify_fri(caps, ncols, batches, openings, ch_v.clone(), params, log_n, bad), pos
+    return params, caps, ncols, batches, openings, ch_v, proof
+
+
+@pytest.mark.parametrize("shape", fri_shapes.FRI_SHAPES, ids=fri_shapes.shape_id)
+def test_fri_shapes_prove_then_verify(shape):
+    log_n, rate, cap_h, bits = shape
+    params, *_ = _prove_verify_tamper(log_n, fri_shapes.FRI_COLS, 1000 + fri_shapes.FRI_SHAPES.index(shape), rate, cap_h, arity_bits=bits)
+    assert (params.rate_bits, params.cap_height, params.n_rounds, list(params.arity_bits)) == (rate, cap_h, len(bits), bits + [0] * (16 - len(bits)))
+
+
+@pytest.mark.parametrize("cols", fri_shapes.POLY_COUNTS, ids=lambda c: "%d_polys" % sum(c))
+def test_fri_polynomial_counts_prove_then_verify(cols):
+    _prove_verify_tamper(fri_shapes.POLY_COUNT_LOG_N, cols, 2000 + sum(cols))
+
+
+@pytest.mark.parametrize("nq", fri_shapes.QUERY_COUNTS)
+def test_fri_query_counts_prove_then_verify(nq):
+    _prove_verify_tamper(fri_shapes.QUERY_COUNT_LOG_N, fri_shapes.FRI_COLS, 3000 + nq, pow_bits=fri_shapes.QUERY_COUNT_POW_BITS, num_query_rounds=nq)
+
+
+def test_fri_proof_is_bound_to_its_arity_list():
+    params, caps, ncols, batches, openings, ch_v, proof = _prove_verify_tamper(8, fri_shapes.FRI_COLS, 4000, arity_bits=[3, 2])
+    other = orc.fri_params(8, arity_bits=[2, 3])
+    sizes = (orc.C.c_size_t * 4)(*ncols)
+    words = [orc.lib().orc_fri_proof_words(orc.C.byref(p), 8, sizes, 4) for p in (params, other)]
+    assert words[0] != words[1]   # the two layouts differ in length; the verifier reads only what its own layout names, inside the longer buffer
+    padded = np.concatenate([proof, np.zeros(max(0, words[1] - words[0]), np.uint64)])
+    assert not orc.verify_fri(caps, ncols, batches, openings, ch_v.clone(), other, 8, padded)
+
+
+def test_standard_arities_restate_the_oracles_rule():
+    for log_n in range(1, 22):
+        assert fri_shapes.standard_arities(log_n) == list(orc.fri_params(log_n).arity_bits)[:orc.fri_params(log_n).n_rounds]
+    for (log_n, rate, cap_h), rounds in fri_shapes.STEP_SHAPES:
+        assert fri_shapes.standard_arities(log_n, rate, cap_h) == [4] * rounds
+
+
+@pytest.mark.parametrize("shape,rounds", fri_shapes.STEP_SHAPES, ids=lambda v: "n%d-r%d-c%d" % v if isinstance(v, tuple) else None)
+def test_step_oracle_proves_and_verifies_at_every_step_shape(shape, rounds):
+    import step_oracle
+    from vpbs_amd import synth
+    log_n, rate, cap_h = shape
+    inputs = synth.step_inputs(log_n, cols=fri_shapes.STEP_COLS)
+    pis = synth.field_elements(0xABCD, 11)
+    digest = np.array([11, 22, 33, 44], np.uint64)
+    proof = step_oracle.prove_step(inputs, digest, pis, log_n, rate_bits=rate, cap_height=cap_h)
+    assert proof["caps"].shape == (3, 1 << cap_h, 4) and proof["ncols"] == list(fri_shapes.STEP_COLS.values())
+    assert step_oracle.verify_step(proof, proof["cs_cap"], proof["ncols"], digest, pis, log_n, rate_bits=rate, cap_height=cap_h)
+    if (rate, cap_h) != (3, 4):   # ... and not under the standard configuration
+        bad = dict(proof, fri=proof["fri"].copy())
+        bad["fri"][-2] = (int(bad["fri"][-2]) + 1) % P
+        assert not step_oracle.verify_step(bad, proof["cs_cap"], proof["ncols"], digest, pis, log_n, rate_bits=rate, cap_height=cap_h)
+
+
+def test_step_oracle_defaults_are_the_standard_configuration():
+    """the generalised step_oracle under its defaults: the frozen proofs of test_oracle_reproduces_frozen_step_proofs pin the words; here the
+    parameters themselves"""
+    import step_oracle
+    for log_n in (5, 6, 10, 12, 15, 16):
+        a, b = step_oracle.step_fri_params(log_n), orc.fri_params(log_n)
+        assert bytes(a) == bytes(b)
 
 
 def test_partial_products_match_bigint_model():

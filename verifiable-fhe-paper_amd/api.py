@@ -1357,9 +1357,12 @@ def step_proof_from_bytes(blob, ncols, log_n, n_constants, num_challenges=2, rat
     v.num_challenges, v.n_constants = num_challenges, n_constants
     if compat is not None:
         v.compat = C.pointer(compat)
-    p = fri_params(log_n)
+    # the FRI words of this shape: the rounds follow rate_bits and cap_height, as the parser's own FriParams::standard does
+    p = fri_params(log_n, rate_bits=rate_bits, cap_height=cap_height, arity_bits=standard_arity_bits(log_n, rate_bits, cap_height))
     sizes = (C.c_size_t * 4)(*ncols)
     fri_words = lib().vpbs_fri_proof_words(C.byref(p), log_n, sizes, 4)
+    if fri_words == 0:
+        raise VpbsError("vpbs_step_proof_from_bytes: not a step proof of this shape")
     caps = np.zeros((3, 1 << cap_height, 4), np.uint64)
     openings = np.zeros((sum(ncols) + num_challenges, 2), np.uint64)
     fri = np.zeros(fri_words, np.uint64)
@@ -2751,11 +2754,37 @@ class Program:
             pass
 
 
+ERR_INVALID = -1   # VPBS_ERR_INVALID
+
+
+def set_arity_bits(p, arity_bits):
+    """the reduction rounds of a FriParams from a list: n_rounds = its length, the rest of arity_bits[16] zero.  A list the array cannot hold
+    keeps its length in n_rounds (the library refuses it) and its first 16 entries."""
+    bits = [int(a) for a in arity_bits]
+    p.n_rounds = len(bits)
+    for i in range(len(p.arity_bits)):
+        p.arity_bits[i] = bits[i] if i < len(bits) else 0
+    return p
+
+
+def standard_arity_bits(degree_bits, rate_bits=3, cap_height=4):
+    """FriReductionStrategy::ConstantArityBits(4, 5) under a FriConfig of this rate and cap height (FriParams::standard of the library)"""
+    bits, d = [], degree_bits
+    while d > 5 and d + rate_bits >= cap_height + 4:
+        bits.append(4)
+        d -= 4
+    return bits
+
+
 def fri_params(degree_bits, **over):
+    """vpbs_fri_params_standard with the given fields changed; arity_bits=[...] (a list) sets the reduction rounds"""
     p = FriParams()
     lib().vpbs_fri_params_standard(degree_bits, C.byref(p))
     for k, v in over.items():
-        setattr(p, k, v)
+        if k == "arity_bits":
+            set_arity_bits(p, v)
+        else:
+            setattr(p, k, v)
     return p
 
 
@@ -2847,7 +2876,9 @@ class Context:
 
     def _check(self, rc):
         if rc:
-            raise VpbsError("status %d: %s" % (rc, lib().vpbs_last_error(self.h).decode()))
+            e = VpbsError("status %d: %s" % (rc, lib().vpbs_last_error(self.h).decode()))
+            e.status = rc
+            raise e
 
     def synchronize(self):
         self._check(lib().vpbs_ctx_synchronize(self.h))
@@ -2925,12 +2956,22 @@ class Context:
         return b, cap
 
     # ---- FRI ----
-    def fri_prove(self, oracles, batches, challenger, params, forced_pow=POW_ANY):
-        """batches: [(point(2), [(oracle_index, poly_index), ...]), ...] -> flat FriProof words."""
+    def fri_prove(self, oracles, batches, challenger, params, forced_pow=POW_ANY, proof_out=None):
+        """batches: [(point(2), [(oracle_index, poly_index), ...]), ...] -> flat FriProof words.
+        proof_out: the caller's own buffer (contiguous uint64, at least vpbs_fri_proof_words long) instead of a new one; vpbs_fri_prove is
+        then called with it whatever the parameters are."""
         degree_bits = oracles[0].log_n
         ncols = (C.c_size_t * len(oracles))(*[o.ncols for o in oracles])
-        words = lib().vpbs_fri_proof_words(C.byref(params), degree_bits, ncols, len(oracles))
-        proof = np.zeros(words, np.uint64)
+        if proof_out is None:
+            words = lib().vpbs_fri_proof_words(C.byref(params), degree_bits, ncols, len(oracles))
+            if words == 0:   # parameters the library refuses as a whole: nothing to size a proof by
+                e = VpbsError("status %d: vpbs_fri_proof_words refuses these FRI parameters at degree 2^%d (rounds, arities, cap height, "
+                              "query rounds or tree count)" % (ERR_INVALID, degree_bits))
+                e.status = ERR_INVALID
+                raise e
+            proof = np.zeros(words, np.uint64)
+        else:
+            proof = proof_out
         handles = (C.c_void_p * len(oracles))(*[o.h for o in oracles])
         infos = (FriBatchInfoC * len(batches))()
         keep = []

@@ -635,7 +635,7 @@ struct DevTemp {
 extern "C" {
 
 int vpbs_ctx_create(int device_ordinal, unsigned log_n_max, unsigned rate_bits, unsigned cap_height, vpbs_ctx** out) {
-    if (!out || log_n_max == 0 || log_n_max + rate_bits > 24 || rate_bits > 4) return VPBS_ERR_INVALID;
+    if (!out || log_n_max == 0 || log_n_max + rate_bits > vpbs::MAX_LDE_BITS || rate_bits > 4) return VPBS_ERR_INVALID;
     int count = 0;
     if (hipGetDeviceCount(&count) != hipSuccess || device_ordinal < 0 || device_ordinal >= count) return VPBS_ERR_DEVICE;
     if (hipSetDevice(device_ordinal) != hipSuccess) return VPBS_ERR_DEVICE;
@@ -918,10 +918,9 @@ int vpbs_batch_open(vpbs_batch* b, size_t leaf_index, uint64_t* leaf_out, uint64
         t.digests = b->d_digests;
         t.col_stride = b->lde_len();
         t.leaf_len = b->ncols;
-        t.n_siblings = b->n_levels() - 1;
         t.leaf_lo = 0;
         t.leaf_hi = b->lde_len();
-        for (unsigned k = 0; k < b->n_levels(); ++k) t.level_off[k] = b->level_off[k];
+        VPBS_REQUIRE(vpbs::set_tree_levels(t, b->level_off), vpbs::TOO_MANY_TREE_LEVELS);
         a.record_words = b->ncols + 4 * (size_t)t.n_siblings;
         a.x_index[0] = leaf_index;
         u64* d_out = c->alloc_words(a.record_words);

@@ -167,6 +167,22 @@ struct vpbs_batch {
 };
 
 namespace vpbs {
+// The largest LDE any entry point takes is 2^MAX_LDE_BITS leaves (vpbs_ctx_create: log_n_max + rate_bits <= MAX_LDE_BITS).  A tree has
+// log_leaves - cap_height + 1 levels, the leaves' digests and the cap included, and OpenTree::level_off (kernels.h) holds MAX_TREE_LEVELS of
+// them: every tree of a context with cap_height >= 1, and with cap_height = 0 every tree but the one over the full 2^MAX_LDE_BITS leaves,
+// which has one level more.  That tree can be committed, and its cap read; the calls that open it refuse it (set_tree_levels).
+constexpr unsigned MAX_LDE_BITS = 24;
+constexpr unsigned MAX_TREE_LEVELS = sizeof(OpenTree::level_off) / sizeof(size_t);
+static_assert(MAX_TREE_LEVELS == MAX_LDE_BITS, "OpenTree::level_off is sized by the log_n_max + rate_bits limit of vpbs_ctx_create");
+constexpr const char* TOO_MANY_TREE_LEVELS = "a Merkle tree of more than 24 levels cannot be opened (2^24 leaves under cap_height 0)";
+static_assert(MAX_TREE_LEVELS == 24, "TOO_MANY_TREE_LEVELS names the limit");
+// the one place that fills OpenTree::level_off and n_siblings; false, and nothing written, for a tree the array cannot hold
+template <class Offsets> inline bool set_tree_levels(OpenTree& t, const Offsets& level_off) {
+    if (level_off.empty() || level_off.size() > MAX_TREE_LEVELS) return false;
+    for (size_t k = 0; k < level_off.size(); ++k) t.level_off[k] = level_off[k];
+    t.n_siblings = (u32)level_off.size() - 1;
+    return true;
+}
 // Merkle level layout for a tree with n_leaves leaves and cap height h: returns total words
 size_t merkle_layout(size_t n_leaves, unsigned cap_height, std::vector<size_t>& level_off);
 // commit a device-resident matrix (values or coefficients); returns a new batch

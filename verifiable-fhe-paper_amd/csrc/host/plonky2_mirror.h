@@ -88,6 +88,27 @@ struct FriParams {
         }
         return true;
     }
+    // Everything the prover and the word count assume about the parameters as a whole, asked before anything is sized, queued or written:
+    // NULL, or the reason they are refused.  n_oracles: the initial trees that are opened next to the round trees.
+    const char* why_invalid(size_t n_oracles) const {
+        if (reduction_arity_bits.size() > MAX_ROUNDS) return "more than 16 FRI reduction rounds";
+        unsigned d = degree_bits;
+        for (unsigned a : reduction_arity_bits) {
+            if (a > d) return "the reduction arities exceed the degree of the polynomial";
+            d -= a;
+        }
+        if (lde_bits() > vpbs::MAX_LDE_BITS) return "an LDE above 2^24";
+        if (!caps_fit()) return "a Merkle tree of the proof is shorter than its cap";
+        if (config.num_query_rounds > vpbs::MAX_QUERIES) return "more than 128 query rounds";
+        if (n_oracles + reduction_arity_bits.size() > vpbs::MAX_OPEN_TREES) return "more than 12 trees to open (oracles + reduction rounds)";
+        return nullptr;
+    }
+    // the same for the C struct, whose n_rounds is looked at BEFORE from_c reads arity_bits[0 .. n_rounds)
+    static constexpr size_t MAX_ROUNDS = sizeof(vpbs_fri_params::arity_bits) / sizeof(unsigned);
+    static const char* why_invalid(const vpbs_fri_params& c, unsigned degree_bits, size_t n_oracles) {
+        if (c.n_rounds > MAX_ROUNDS) return "more than 16 FRI reduction rounds";
+        return from_c(c, degree_bits).why_invalid(n_oracles);
+    }
     static FriParams from_c(const vpbs_fri_params& c, unsigned degree_bits) {
         FriParams p;
         p.config = FriConfig{c.rate_bits, c.cap_height, c.pow_bits, c.num_query_rounds};

@@ -20,7 +20,9 @@ using vpbs::u64;
 
 namespace plonky2 {
 
+// 0: parameters that FriParams::why_invalid refuses (the subtractions below are unsigned and would wrap)
 size_t fri_proof_words(const FriParams& p, const std::vector<size_t>& ncols) {
+    if (p.why_invalid(ncols.size())) return 0;
     const unsigned log_lde = p.lde_bits();
     const size_t cap = (size_t)4 << p.config.cap_height;
     size_t w = p.reduction_arity_bits.size() * cap;
@@ -92,9 +94,11 @@ void PolynomialBatch::prove_openings(vpbs_ctx* ctx, const FriInstanceInfo& insta
     hipStream_t s = ctx->stream;
     const unsigned degree_bits = fp.degree_bits, rate_bits = fp.config.rate_bits, cap_h = fp.config.cap_height;
     const size_t n = (size_t)1 << degree_bits;
+    // the parameters as a whole, before anything is queued, drawn from the challenger or written to proof_out
     VPBS_REQUIRE(rate_bits == ctx->rate_bits && cap_h == ctx->cap_height, "FRI params disagree with the context");
-    VPBS_REQUIRE(fp.config.num_query_rounds <= vpbs::MAX_QUERIES, "too many query rounds");
-    VPBS_REQUIRE(oracles.size() + fp.reduction_arity_bits.size() <= vpbs::MAX_OPEN_TREES, "too many trees");
+    if (const char* why = fp.why_invalid(oracles.size())) throw DeviceError{VPBS_ERR_INVALID, std::string("FRI params refused: ") + why};
+    // the initial trees are the tallest of the proof (a limit of the query kernel's argument block, not of the proof's layout)
+    VPBS_REQUIRE(fp.lde_bits() - cap_h + 1 <= vpbs::MAX_TREE_LEVELS, vpbs::TOO_MANY_TREE_LEVELS);
     const bool multi = comm && comm->world > 1;
     for (auto* o : oracles) {
         VPBS_REQUIRE(o && o->log_n == degree_bits && o->ctx == ctx, "oracle does not match degree/context");
@@ -264,13 +268,12 @@ void PolynomialBatch::prove_openings(vpbs_ctx* ctx, const FriInstanceInfo& insta
         t.digests = o->d_digests;
         t.col_stride = o->lde_len();
         t.leaf_len = o->ncols;
-        t.n_siblings = o->n_levels() - 1;
+        VPBS_REQUIRE(vpbs::set_tree_levels(t, o->level_off), vpbs::TOO_MANY_TREE_LEVELS);
         t.index_shift = 0;
         // ownership: a sharded oracle answers for its own leaf range; a replicated one is answered by rank 0 only
         t.leaf_lo = o->leaf_offset();
         t.leaf_hi = o->leaf_offset() + o->lde_len();
         if (multi && o->n_shards == 1 && comm->rank != 0) t.leaf_hi = t.leaf_lo = 0;
-        for (unsigned k = 0; k < o->n_levels(); ++k) t.level_off[k] = o->level_off[k];
         t.out_off = off;
         off += t.leaf_len + 4 * (size_t)t.n_siblings;
     }
@@ -283,12 +286,11 @@ void PolynomialBatch::prove_openings(vpbs_ctx* ctx, const FriInstanceInfo& insta
         t.data1 = ft.values + ft.n_values;
         t.digests = ft.digests;
         t.leaf_len = 2u << ft.arity_bits;
-        t.n_siblings = (unsigned)ft.level_off.size() - 1;
+        VPBS_REQUIRE(vpbs::set_tree_levels(t, ft.level_off), vpbs::TOO_MANY_TREE_LEVELS);
         t.index_shift = total_shift;
         t.arity_bits = ft.arity_bits;
         t.leaf_lo = 0;
         t.leaf_hi = (multi && comm->rank != 0) ? 0 : ft.n_leaves;  // FRI round trees are replicated: rank 0 answers
-        for (size_t k = 0; k < ft.level_off.size(); ++k) t.level_off[k] = ft.level_off[k];
         t.out_off = off;
         off += t.leaf_len + 4 * (size_t)t.n_siblings;
     }
@@ -637,6 +639,7 @@ void vpbs_fri_params_standard(unsigned degree_bits, vpbs_fri_params* out) {
 }
 
 size_t vpbs_fri_proof_words(const vpbs_fri_params* params, unsigned degree_bits, const size_t* ncols, size_t n_oracles) {
+    if (!params || (!ncols && n_oracles) || plonky2::FriParams::why_invalid(*params, degree_bits, n_oracles)) return 0;
     return plonky2::fri_proof_words(plonky2::FriParams::from_c(*params, degree_bits), std::vector<size_t>(ncols, ncols + n_oracles));
 }
 
@@ -647,6 +650,9 @@ int vpbs_fri_prove(vpbs_ctx* ctx, vpbs_batch* const* oracles, size_t n_oracles, 
         VPBS_HIP(hipSetDevice(ctx->device));
         plonky2::Challenger ch(*challenger);
         std::vector<vpbs_batch*> os(oracles, oracles + n_oracles);
+        VPBS_REQUIRE(os[0], "oracle does not match degree/context");
+        if (const char* why = plonky2::FriParams::why_invalid(*params, os[0]->log_n, n_oracles))
+            throw DeviceError{VPBS_ERR_INVALID, std::string("FRI params refused: ") + why};
         plonky2::PolynomialBatch::prove_openings(ctx, instance_from_c(instance), os, ch,
                                                  plonky2::FriParams::from_c(*params, os[0]->log_n), forced_pow, proof_out);
         *challenger = ch.st;
