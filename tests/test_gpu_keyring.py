@@ -103,6 +103,36 @@ def test_bit_exact_against_the_oracle_under_each_ciphertexts_key(ctx, log_n, K, 
     kr.close()
 
 
+@pytest.mark.parametrize("log_n,K,ELL,LOGB,n", [(6, 2, 8, 8, 5), (3, 2, 4, 5, 6), (6, 3, 3, 7, 40), (5, 2, 4, 5, 9)])
+def test_a_ring_of_one_slot_is_the_bootstrapper_word_for_word(ctx, log_n, K, ELL, LOGB, n):
+    """one key set, a batch of 3 (a mask with the edge words, per-ciphertext test vectors): a KeyRing with ONE slot gives every accumulator,
+    out_ct and lwe_out as a Bootstrapper of that key set does, with and without accumulators, through run and through run_from with
+    start = [0, 2, n + 2] and acc_in taken from the first run.  At these shapes the ring holds 8, 4, 4 and 4 key words ahead per thread and
+    the Bootstrapper none: the two kernels share one chain body, and this pins its prefetching paths against the plain one."""
+    k = oracle_keys(log_n, K, ELL, LOGB, n, 311 + log_n + K)
+    N, count = k["ring"].n, 3
+    delta = T.get_delta(4)
+    cts = np.array([T.lwe_encrypt(k["rng"], k["s_lwe"], delta * (i % 2) % P) for i in range(count)], np.uint64)
+    cts[1, 0], cts[1, 1], cts[1, 2] = 0, P - 1, 1 << 63
+    testv = k["rng"].integers(0, P, size=(count, N), dtype=np.uint64)
+    key_of = np.zeros(count, np.uint32)
+    bs = api.Bootstrapper(ctx, k["bsk_flat"], k["ksk_flat"], K, ELL, LOGB, max_batch=count)
+    kr = api.KeyRing(ctx, K, ELL, LOGB, N, n, max_keys=1, max_batch=count)
+    assert kr.add(k["bsk_flat"], k["ksk_flat"]) == 0
+    want = bs.run(cts, testv, accumulators=True)
+    assert want[2].shape == (count, n + 2, K, N) and want[2][:, n + 1].any()
+    for got in (kr.run(cts, key_of, testv, accumulators=True), kr.run(cts, key_of, testv)):
+        assert all((g == w).all() for g, w in zip(got, want)), len(got)
+    start = [0, 2, n + 2]
+    acc_in = np.stack([want[2][i, max(s, 1) - 1] for i, s in enumerate(start)])     # row 0 starts at step 0: its acc_in is not read
+    want_from = bs.run_from(cts, start, acc_in, testv, accumulators=True)
+    assert (want_from[0] == want[0]).all() and (want_from[1] == want[1]).all()     # a resumed chain ends where the whole one does
+    for got in (kr.run_from(cts, key_of, start, acc_in, testv, accumulators=True), kr.run_from(cts, key_of, start, acc_in, testv)):
+        assert all((g == w).all() for g, w in zip(got, want_from)), len(got)
+    kr.close()
+    bs.close()
+
+
 def test_word_for_word_the_one_key_bootstrapper_at_the_papers_parameters(ctx, paper, monkeypatch):
     """three noisy key sets, a batch of 6 in mixed order: every out_ct and lwe_out row is Bootstrapper(key k).run's of that row, the
     outputs decrypt under their own keys, and 256, 512 and 1024 threads per ciphertext change no word"""

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
+#include <cstring>
 #include <map>
 #include <string>
 #include <tuple>
@@ -36,6 +37,14 @@ struct DeviceError {
     do {                                                                \
         if (!(cond)) throw ::vpbs::DeviceError{VPBS_ERR_INVALID, msg};  \
     } while (0)
+
+// a message into the caller's buffer of an entry point that takes (err, err_len): truncated, always terminated; a null buffer takes nothing
+inline void report(char* err, size_t err_len, const std::string& m) {
+    if (err && err_len) {
+        std::strncpy(err, m.c_str(), err_len - 1);
+        err[err_len - 1] = 0;
+    }
+}
 }  // namespace vpbs
 
 namespace vpbs {

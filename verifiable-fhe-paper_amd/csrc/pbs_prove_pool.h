@@ -143,13 +143,6 @@ void launch_preset(hipStream_t s, const PresetArgs& a) {
 
 double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
-void report(char* err, size_t err_len, const std::string& m) {
-    if (err && err_len) {
-        std::strncpy(err, m.c_str(), err_len - 1);
-        err[err_len - 1] = 0;
-    }
-}
-
 // the resident key set a chain is proven under
 struct KeySource {
     const u64 *d_bsk = nullptr, *d_ksk = nullptr;   // device: [n_lwe][ggsw_len], [ggsw_len]

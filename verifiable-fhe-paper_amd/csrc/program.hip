@@ -168,13 +168,6 @@ __global__ void __launch_bounds__(256) gather_rows_kernel(const u64* __restrict_
     for (size_t j = threadIdx.x; j < words; j += 256) d[j] = s[j];
 }
 
-void report(char* err, size_t err_len, const std::string& m) {
-    if (err && err_len) {
-        std::strncpy(err, m.c_str(), err_len - 1);
-        err[err_len - 1] = 0;
-    }
-}
-
 struct Csr {   // a description in one gate order
     std::vector<u64> first, coef, cst;
     std::vector<u32> src, lut;

@@ -3,6 +3,9 @@
 // ring of key hashes (verify_pbs_batch.hip).  A program queues one bootstrap launch per
 // level behind its own combine kernel and waits once, at the end: it needs the Bootstrapper's launch WITHOUT the wait vpbs_bootstrapper_run
 // ends with, and the shapes of objects whose structs are private to their files.  Library-internal, like ivc_resident.h.
+// The chain that the Bootstrapper's and the ring's kernels walk is one device function, pb_chain (pbs_chain.h); what the two objects share on
+// the host -- shape, staging, thread rule, launch ladder, the run behind vpbs_*_run -- is pbs_chain_host.h.  The two enqueue functions below
+// fill the object's own argument struct and go through that ladder.
 #pragma once
 #include <cstddef>
 #include <cstdint>

@@ -41,6 +41,7 @@
 
 namespace {
 using vpbs::DeviceError;
+using vpbs::report;
 using gl::Ext;
 using u32 = uint32_t;
 using u64 = uint64_t;
@@ -394,13 +395,6 @@ __global__ __launch_bounds__(256) void vb_result(const u32* __restrict__ flags, 
                                                : VPBS_VERIFY_OK;
     out[i] = reason == VPBS_VERIFY_OK ? 1 : 0;
     out[count + i] = reason;
-}
-
-void report(char* err, size_t err_len, const std::string& m) {
-    if (err && err_len) {
-        std::strncpy(err, m.c_str(), err_len - 1);
-        err[err_len - 1] = 0;
-    }
 }
 
 // walk_step_proof, recorded once: for every word of the unified order its byte offset in a serialised proof, and the offset and expected

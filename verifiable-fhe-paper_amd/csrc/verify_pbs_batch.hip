@@ -35,6 +35,7 @@
 
 namespace {
 using vpbs::DeviceError;
+using vpbs::report;
 using u32 = uint32_t;
 using u64 = uint64_t;
 
@@ -120,13 +121,6 @@ __global__ __launch_bounds__(256) void vp_result(const u32* __restrict__ flags, 
     out[i] = reason == VPBS_PBS_OK ? 1 : 0;
     out[count + i] = reason;
     out[2 * (u64)count + i] = reason == VPBS_PBS_PROOF ? pr : VPBS_VERIFY_OK;
-}
-
-void report(char* err, size_t err_len, const std::string& m) {
-    if (err && err_len) {
-        std::strncpy(err, m.c_str(), err_len - 1);
-        err[err_len - 1] = 0;
-    }
 }
 }  // namespace
 

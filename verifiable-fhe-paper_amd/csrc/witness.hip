@@ -14,13 +14,6 @@ namespace vpbs {
 namespace {
 constexpr u32 NO_ROW = 0xFFFFFFFFu, NONE = 0xFFFFFFFFu;
 
-void report(char* err, size_t err_len, const std::string& m) {
-    if (err && err_len) {
-        std::strncpy(err, m.c_str(), err_len - 1);
-        err[err_len - 1] = 0;
-    }
-}
-
 // plan creation: generators "run" on readiness flags only (every read returns 1, which no generator rejects)
 struct FlagRow {
     std::vector<uint8_t>& ready;

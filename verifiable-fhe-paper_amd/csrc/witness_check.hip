@@ -49,6 +49,7 @@ template <> struct Fld<H64> {
 
 namespace {
 using vpbs::DeviceError;
+using vpbs::report;
 using u32 = uint32_t;
 using u64 = uint64_t;
 constexpr u64 NO_VIOLATION = ~0ull;
@@ -110,13 +111,6 @@ __global__ __launch_bounds__(256) void check_copies(const u32* __restrict__ copi
     const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_copies) return;
     if (wires[copies[2 * i]] != wires[copies[2 * i + 1]]) atomicMin(key, (unsigned long long)(COPY_BIT | i));
-}
-
-void report(char* err, size_t err_len, const std::string& m) {
-    if (err && err_len) {
-        std::strncpy(err, m.c_str(), err_len - 1);
-        err[err_len - 1] = 0;
-    }
 }
 }  // namespace
 
