@@ -1353,6 +1353,92 @@ int vpbs_program_create_multi(vpbs_ctx* ctx, const vpbs_program_desc* desc, cons
                               const unsigned* gate_outputs /* [n_gates] */, vpbs_program** out, char* err, size_t err_len);
 long vpbs_program_wires(const vpbs_program* prog, unsigned* out_first_out /* [n_gates + 1] or NULL */);
 
+/* ---- aggregation: the vPBS proofs of a batch folded into ONE proof (csrc/aggregate.hip) ----
+ * Statement.  Leaf i is the vPBS proof of (testvs[testv_of[i]], cts[i], out_cts[i], key_hashes[key_of[i]]); its statement s_i is
+ * hash_no_pad of the proof's public inputs, n_pi = 2 K N + 77 words:
+ *     acc_init [K N] (K - 1 zero polynomials, then the test vector) | counter = n_lwe + 2 | accumulator [K N] = out_ct | key hash [4] |
+ *     LWE hash [4] (the chain of vpbs_verify_pbs over ct) | vk_0 [68] (the cyclic circuit's digest [4], then its cap [16][4])
+ * Tree: 1 <= count <= 2^levels leaves, d = max(1, ceil(log2 count)); the leaf list is padded to 2^d by repeating the last leaf; a node's
+ * statement is hash_no_pad(s_left || s_right); the root is the level-d statement.  The level-l circuit A_l (l >= 1) verifies two proofs
+ * of level l - 1 under vk_{l-1}, which it takes from its own public inputs root [4] | vk_0 [68] | .. | vk_{l-1} [68]; no verifier data
+ * are constants of a circuit.  The aggregate proof is the ProofWithPublicInputs bytes of the level-d node: whoever fixes vk_d fixes, through
+ * the public inputs, every vk below it.
+ * Words: testvs, out_cts and key_hashes enter raw -- a word at or above p can match no proof (VPBS_AGG_ROOT); words of cts are reduced, as
+ * in vpbs_hash_chain.  testv_of NULL: leaf i takes testvs[i] when n_testv == count, testvs[0] when n_testv == 1; key_of NULL: slot 0.
+ *
+ * vpbs_aggregate_root (host): the root of the statement -> out; VPBS_OK, VPBS_ERR_INVALID (count == 0, N or K == 0, null pointers, an
+ *   index at or above n_testv / n_keys), or 1 when a raw word is at or above p (out is not written: no proof has that statement).
+ * vpbs_verify_aggregate (host): 1 = accepted, 0 = rejected, < 0 = malformed arguments (those of vpbs_aggregate_root; count > 2^levels).
+ *   Checks, in this order, with *reason (may be NULL) and `why` = vpbs_aggregate_reason_text(reason):
+ *     VPBS_AGG_MALFORMED      the bytes do not parse at level d's shape, or their public-input count is not 4 + 68 d
+ *     VPBS_AGG_VERIFIER_DATA  the vk list in the public inputs differs from vks[0 .. d - 1]
+ *     VPBS_AGG_PROOF          vpbs_verify_step under vks[d]
+ *     VPBS_AGG_ROOT           the root computed from the statement differs from the public inputs' (or a raw word is at or above p)
+ * shape: level_shapes[l - 1] describes A_l as for vpbs_verify_step (degree, column counts, gates; its cap, digest and public inputs are not
+ * read: they come from vks [levels + 1][68] and from the bytes). */
+typedef enum {
+    VPBS_AGG_OK = 0,
+    VPBS_AGG_MALFORMED = 1,
+    VPBS_AGG_VERIFIER_DATA = 2,
+    VPBS_AGG_PROOF = 3,
+    VPBS_AGG_ROOT = 4
+} vpbs_aggregate_reason;
+typedef struct {
+    unsigned N, K, n_lwe;
+    unsigned levels;                          /* the circuits A_1 .. A_levels: up to 2^levels leaves */
+    const vpbs_verify_inputs* level_shapes;   /* [levels] */
+    const uint64_t* vks;                      /* [levels + 1][68]: vk_0 (the cyclic circuit's) .. vk_levels */
+} vpbs_aggregate_shape;
+const char* vpbs_aggregate_reason_text(int reason);   /* "" for VPBS_AGG_OK; NULL for an unknown code */
+int vpbs_aggregate_root(unsigned N, unsigned K, unsigned n_lwe, const uint64_t* vk0 /* [68] */, size_t count, const uint64_t* testvs /* [n_testv][N] */,
+                        size_t n_testv, const uint32_t* testv_of /* [count] or NULL */, const uint64_t* cts /* [count][n_lwe + 1] */,
+                        const uint64_t* out_cts /* [count][K][N] */, const uint64_t* key_hashes /* [n_keys][4] */, size_t n_keys,
+                        const uint32_t* key_of /* [count] or NULL */, uint64_t out[4]);
+int vpbs_verify_aggregate(const vpbs_aggregate_shape* shape, size_t count, const uint64_t* testvs, size_t n_testv, const uint32_t* testv_of,
+                          const uint64_t* cts, const uint64_t* out_cts, const uint64_t* key_hashes, size_t n_keys, const uint32_t* key_of,
+                          const uint8_t* bytes, size_t len, int* reason, char* why, size_t why_len);
+/* The prover side.  create: `leaf` describes the cyclic step circuit as for vpbs_verify_step (shape, gates, cap and digest = vk_0; public
+ * inputs not read), leaf_n_pi = 2 K N + 77; levels[l - 1] is A_l as data, in the form of vpbs_ivc_create: preset_pos in the order slot 0 proof
+ * [proof_words] | slot 0 public inputs | slot 1 proof | slot 1 public inputs | vk_0 .. vk_{l-1}, pi_pos / n_pi = 4 + 68 l its public-input
+ * targets, proof_words the words of one INNER proof.  It commits every level's constants and sigmas, derives vk_1 .. vk_levels (no
+ * commitment arrives with the circuits) and compiles the witness plans; the context must have rate_bits 3 and cap_height 4.
+ * verifier_data: out [levels + 1][68].
+ * run: proofs bytes[offsets[i] .. offsets[i + 1]), 1 <= count <= 2^levels.  Every leaf is parsed and verified on the host (up to 16
+ * threads) and its last 68 public inputs compared with vk_0 BEFORE anything is proven: a bad leaf returns VPBS_ERR_INVALID with err =
+ * "leaf i: ..." for the first bad index and stats->nodes = 0 -- a proof that would not verify in circuit never reaches witness generation.
+ * Then level by level: the node's witness on the host (the next node's on a second thread while this one is being proven), the wires
+ * uploaded, vpbs_prove_step; nodes with the same two children (padding) are proven once.  count = 1 aggregates the leaf with itself.
+ * Returns the number of bytes written to out (the root node's ProofWithPublicInputs bytes), or < 0.  One run at a time per object. */
+typedef struct {
+    double seconds, check_leaves_ms, witness_ms, prove_ms;   /* witness_ms, prove_ms: sums over the nodes */
+    unsigned nodes, depth;
+} vpbs_aggregate_stats;
+typedef struct vpbs_aggregator vpbs_aggregator;
+int vpbs_aggregator_create(vpbs_ctx* ctx, const vpbs_verify_inputs* leaf, size_t leaf_n_pi, const vpbs_ivc_circuit* levels, unsigned n_levels,
+                           vpbs_aggregator** out, char* err, size_t err_len);
+int vpbs_aggregator_verifier_data(const vpbs_aggregator* a, uint64_t* out /* [levels + 1][68] */);
+long vpbs_aggregator_run(vpbs_aggregator* a, const uint8_t* bytes, const size_t* offsets /* [count + 1] */, size_t count, uint8_t* out,
+                         size_t capacity, vpbs_aggregate_stats* stats, char* err, size_t err_len);
+int vpbs_aggregator_last_run(const vpbs_aggregator* a, vpbs_aggregate_stats* out);
+void vpbs_aggregator_free(vpbs_aggregator* a);
+/* vpbs_verify_aggregate on the device: the leaf statements (one 16-lane group per leaf absorbs the n_pi words as it generates them from
+ * the statement's parts -- the public-input vector is never materialised), the LWE chains, the fold (one launch per level), the root proof
+ * through the batch verifier's stages with a batch of one, and a one-lane kernel that orders the reasons as the host does.  The word arrays
+ * (testvs, cts, out_cts, key_hashes) are device pointers when on_device != 0; testv_of and key_of are HOST arrays in every mode and are
+ * checked before anything is queued; count, n_testv and n_keys are at most max_leaves.  run returns 1 = accepted, 0 = rejected, < 0 =
+ * malformed arguments or a device failure (err); *reason (may be NULL) is the host's.  One run at a time per object. */
+typedef struct vpbs_aggregate_verifier vpbs_aggregate_verifier;
+int vpbs_aggregate_verifier_create(vpbs_ctx* ctx, const vpbs_aggregate_shape* shape, size_t max_leaves, vpbs_aggregate_verifier** out, char* err,
+                                   size_t err_len);
+int vpbs_aggregate_verifier_run(vpbs_aggregate_verifier* v, const uint8_t* bytes, size_t len, size_t count, const uint64_t* testvs, size_t n_testv,
+                                const uint32_t* testv_of, const uint64_t* cts, const uint64_t* out_cts, const uint64_t* key_hashes, size_t n_keys,
+                                const uint32_t* key_of, int on_device, int* reason, char* err, size_t err_len);
+/* the statement stages alone: vpbs_aggregate_root computed on the device (same return values; out is a host array) */
+int vpbs_aggregate_verifier_root(vpbs_aggregate_verifier* v, size_t count, const uint64_t* testvs, size_t n_testv, const uint32_t* testv_of,
+                                 const uint64_t* cts, const uint64_t* out_cts, const uint64_t* key_hashes, size_t n_keys, const uint32_t* key_of,
+                                 int on_device, uint64_t out[4], char* err, size_t err_len);
+void vpbs_aggregate_verifier_free(vpbs_aggregate_verifier* v);
+
 /* ---- memory helpers for hosts that do not link the HIP runtime themselves (a Rust or plain C++ caller) ----
  * pinned host memory (hipHostMalloc): witness matrices written there reach the device at PCIe speed (70.8 MB in 1.3 ms instead of ~15 ms
  * from pageable memory); device buffers for per-circuit data that is uploaded once (the sigma values of vpbs_step_inputs.sigmas_values with

@@ -5,7 +5,8 @@ builder.build(): gates, gate per row, constants columns, copy c
 PartialWitness sets, the public-input targets; plus one sample PartialWitness and the public inputs it must produce.
 Format: little-endian u64 words, see examples/prove_step_circuit.cpp (the reader).
 usage: tools/export_step_circuit.py OUT.bin [N K ELL LOGB n_lwe]     (default 8 2 4 5 6)
-       tools/export_step_circuit.py --cyclic OUT.bin DUMMY.bin N K ELL LOGB n_lwe log_n"""
+       tools/export_step_circuit.py --cyclic OUT.bin DUMMY.bin N K ELL LOGB n_lwe log_n
+       tools/export_step_circuit.py --aggregate N K ELL LOGB n_lwe log_n LEVEL1.bin [LEVEL2.bin ...]"""
 import os
 import sys
 
@@ -17,7 +18,7 @@ import step_circuit as sc  # noqa: E402
 from vpbs_amd import api  # noqa: E402
 
 MAGIC = 0x5354455043495243  # "STEPCIRC"
-KIND_STEP, KIND_CYCLIC, KIND_DUMMY = 0, 1, 2
+KIND_STEP, KIND_CYCLIC, KIND_DUMMY, KIND_AGGREGATE = 0, 1, 2, 3
 
 
 def write_circuit(path, built, preset_pos, values, pis, trailer):
@@ -73,8 +74,29 @@ def export_cyclic(path, dummy_path, N, K, ELL, LOGB, n_lwe, log_n):
     return cy, dm
 
 
+def export_aggregate(paths, N, K, ELL, LOGB, n_lwe, log_n):
+    """the aggregation circuits A_1 .. A_len(paths) (circuitgen/aggregate_circuit.py) over proofs of the cyclic circuit of degree 2^log_n.
+    Only the cyclic circuit's SHAPE enters (degree, number of public inputs): no verifier data, so nothing of it is built here.
+    PartialWitness order: slot 0 proof | slot 0 public inputs | slot 1 proof | slot 1 public inputs | vk_0 .. vk_{l-1}; the trailer's
+    proof_words are those of one inner proof.  No sample witness (it would need proofs)."""
+    import aggregate_circuit as ag
+    import cyclic_circuit as cyc
+    shape, out = cyc.Shape(api, log_n, cyc.cyclic_n_pi(N, K)), []
+    for level, path in enumerate(paths, 1):
+        a = ag.AggregateCircuit(api, shape, level)
+        b = a.built
+        write_circuit(path, b, a.positions, np.zeros(len(a.positions), np.uint64), np.zeros(len(b.public_inputs), np.uint64),
+                      [N, K, ELL, LOGB, n_lwe, b.used_rows, KIND_AGGREGATE, shape.proof_words, level])
+        out.append(a)
+        shape = a.shape
+    return out
+
+
 if __name__ == "__main__":
-    if sys.argv[1] == "--cyclic":   # --cyclic OUT.bin DUMMY.bin N K ELL LOGB n_lwe log_n
+    if sys.argv[1] == "--aggregate":   # --aggregate N K ELL LOGB n_lwe log_n LEVEL1.bin ...
+        for a, path in zip(export_aggregate(sys.argv[8:], *[int(x) for x in sys.argv[2:8]]), sys.argv[8:]):
+            print("wrote %s: level %d, %d gate rows, degree 2^%d, %d public inputs" % (path, a.level, a.built.used_rows, a.built.log_n, a.shape.n_pi))
+    elif sys.argv[1] == "--cyclic":   # --cyclic OUT.bin DUMMY.bin N K ELL LOGB n_lwe log_n
         a = [int(x) for x in sys.argv[4:10]]
         cy, dm = export_cyclic(sys.argv[2], sys.argv[3], *a)
         print("wrote %s: %d gate rows, degree 2^%d, %d public inputs; %s: dummy circuit" % (sys.argv[2], cy.built.used_rows, cy.built.log_n,

@@ -5,7 +5,7 @@ ALL proofs through api.PbsVerifier built from the prover's key_hash() and all lw
 reference's main.rs:59-64).  One JSON line.
 
 usage: tools/prove_batch.py [--count M] [--chains C] [--witness-batch B] [--steps K] [--n2048 | --n8] [--keys-on-device] [--baseline]
-                            [--keys M [--baseline]] [--checkpoint DIR:every] [--resume DIR]
+                            [--keys M [--baseline]] [--checkpoint DIR:every] [--resume DIR] [--aggregate]
   --steps K < n + 2 proves a prefix of every chain (tests); the proofs are then checked by api.verify_pbs_prefix on the host (verify_pbs
     insists on counter = n + 2); the outputs are those of the whole bootstrap either way.
   --n8: the N = 8, n = 6 miniature (degree 2^13); --n2048: N = 2048 (degree 2^17); default: the paper's N = 1024, n = 728 (degree 2^16).
@@ -24,7 +24,11 @@ usage: tools/prove_batch.py [--count M] [--chains C] [--witness-batch B] [--step
     temporary name and renamed, so a crash never leaves a torn file).  --resume DIR: every ciphertext that has a file there goes on from
     its highest-numbered one (PbsProver.resume / RingProver.resume); the JSON line reports resumed_from per row (0: from step 0) and, for
     a checkpoint the prover refused, its message under checkpoints_refused.  Both work with --keys M; neither with --baseline.  Every
-    line carries proofs_sha256, so that a resumed run can be compared with an uninterrupted one."""
+    line carries proofs_sha256, so that a resumed run can be compared with an uninterrupted one.
+  --aggregate: after the proofs and their verification, ONE api.Aggregator folds all proofs into one proof (the level circuits are located
+    as data: tools/export_circuits.py --aggregate N K ELL LOGB n_lwe log_n levels makes them), which api.verify_aggregate (host) and
+    api.AggregateVerifier (device) check against the statement of the whole batch; the JSON line gains "aggregate": bytes, depth, nodes and
+    the times.  With --keys M too; not with --steps or --baseline, and only when every proof exists."""
 import hashlib
 import argparse
 import json
@@ -191,6 +195,40 @@ def prove_baseline(args, N, n_lwe, log_n, cyc_path, dum_path, keys, cts, testv):
                                                                         "early_witness_ms_per_step": mean["early_witness_ms"]}
 
 
+def aggregate_section(ctx, N, n_lwe, log_n, cyc, vk, proofs, testv, cts, out_ct, key_hashes, key_of, leaves_seconds):
+    """--aggregate: fold `proofs` into one proof and verify it on the host and on the device -> the "aggregate" entry of the JSON line"""
+    count = len(proofs)
+    depth = api.aggregate_depth(count)
+    levels = [circuit_file.load(p) for p in circuit_file.find_aggregate_circuits(N, K, ELL, LOGB, n_lwe, log_n, depth)]
+    t = time.perf_counter()
+    agg = api.Aggregator(ctx, cyc, vk, levels)
+    t_create = time.perf_counter() - t
+    t = time.perf_counter()
+    blob = agg.aggregate(proofs)
+    t_run = time.perf_counter() - t
+    run, vks = agg.last_run(), agg.verifier_data()
+    agg.close()
+    shape = api.AggregateShape(N, K, n_lwe, vks, levels)
+    statement = (np.asarray(testv, np.uint64).reshape(1, N), cts, np.asarray(out_ct, np.uint64).reshape(count, K * N), np.stack(key_hashes), key_of)
+    t = time.perf_counter()
+    host = api.verify_aggregate(shape, blob, count, *statement)
+    t_host = time.perf_counter() - t
+    av = api.AggregateVerifier(ctx, shape, max_leaves=count)
+    device = av.verify(blob, count, *statement)     # the first run pays for the staging buffers
+    t = time.perf_counter()
+    device = av.verify(blob, count, *statement)
+    t_device = time.perf_counter() - t
+    av.close()
+    leaf_bytes = sum(len(b) for b in proofs)
+    return {"count": count, "depth": depth, "nodes": run["nodes"], "level_degree_bits": [d.log_n for d in levels], "bytes": len(blob),
+            "leaf_bytes_total": leaf_bytes, "bytes_ratio": len(blob) / leaf_bytes, "sha256": hashlib.sha256(blob).hexdigest(),
+            "create_seconds": t_create, "aggregate_seconds": t_run, "check_leaves_ms_16_host_threads": run["check_leaves_ms"],
+            "node_witness_ms": run["witness_ms"] / max(run["nodes"], 1), "node_prove_ms": run["prove_ms"] / max(run["nodes"], 1),
+            "aggregate_seconds_over_leaves_seconds": t_run / leaves_seconds if leaves_seconds else None,
+            "verify_host_ms": 1e3 * t_host, "verify_device_ms": 1e3 * t_device, "host": [bool(host[0]), api.aggregate_reason_text(host[1])],
+            "device": [bool(device[0]), api.aggregate_reason_text(device[1])], "accepted": bool(host[0] and device[0])}
+
+
 def device_bytes_free():
     free, _ = torch.cuda.mem_get_info(0)   # hipMemGetInfo
     return int(free)
@@ -256,7 +294,9 @@ def main_keys(args, N, n_lwe, log_n):
         rv = api.RingVerifier(ctx, cap, ncols, vk[:4], log_n, cyc.n_constants, 80, cyc.gates, N, K, n_lwe, K * ELL * K * N, max_keys=M, max_batch=count)
         for k in range(M):
             rv.set_key(k, hashes[k])
+        t_rv = time.perf_counter()
         verdicts, reasons, _ = rv.verify([proofs[i] for i in live], [key_of[i] for i in live], testv, cts[live], out_ct[live])
+        figures["ring_verifier_ms"] = 1e3 * (time.perf_counter() - t_rv)
         rv.close()
         accepted = int(verdicts.sum())
         why = {api.pbs_reason_text(int(r)) for v, r in zip(verdicts, reasons) if not v}
@@ -276,6 +316,10 @@ def main_keys(args, N, n_lwe, log_n):
             accepted += sum(1 for r in res if r[0] and r[1] == args.steps)
             why |= {str(r[-1]) for r in res if not r[0]}
     decrypted = sum(1 for i in range(count) if rounded(api.lwe_decrypt(keys[key_of[i]]["s_lwe"], lwe_out[i]), delta) == msgs[i])
+    aggregated = True
+    if args.aggregate and len(live) == count:
+        figures["aggregate"] = aggregate_section(ctx, N, n_lwe, log_n, cyc, vk, proofs, testv, cts, out_ct, hashes, key_of, t_end - t_made)
+        aggregated = figures["aggregate"]["accepted"]
     ctx.close()
     print(json.dumps(dict({
         "what": "%d verifiable bootstraps under %d key sets at N=%d, n=%d (degree 2^%d), %s" % (
@@ -286,7 +330,7 @@ def main_keys(args, N, n_lwe, log_n):
         "seconds_until_out_ct_complete": t_out, "prepare_chain_ms": prepare_ms, "accepted": accepted, "rejected_because": sorted(why),
         "decrypted_correct": decrypted, "proofs_sha256": proof_hashes(proofs),
         "host": {"cpus": len(os.sched_getaffinity(0)), "loadavg_before": load0, "loadavg_after": os.getloadavg()[0]}}, **figures)))
-    return 0 if accepted == count and decrypted == count and n_proofs == count else 1
+    return 0 if accepted == count and decrypted == count and n_proofs == count and aggregated else 1
 
 
 def main():
@@ -302,7 +346,10 @@ def main():
     ap.add_argument("--keys", type=int, default=0)
     ap.add_argument("--checkpoint", default="", metavar="DIR:every")
     ap.add_argument("--resume", default="", metavar="DIR")
+    ap.add_argument("--aggregate", action="store_true")
     args = ap.parse_args()
+    if args.aggregate and (args.baseline or args.steps):
+        raise SystemExit("--aggregate folds whole vPBS proofs of the batch provers: it cannot run with --baseline or --steps")
     if args.baseline and (args.checkpoint or args.resume):
         raise SystemExit("--checkpoint and --resume belong to the batch provers: they cannot run with --baseline")
     if args.checkpoint and not args.checkpoint.rsplit(":", 1)[-1].isdigit():
@@ -358,6 +405,10 @@ def main():
     decrypted = None
     if lwe_out is not None:
         decrypted = sum(1 for m, want in zip(api.lwe_decrypt(keys["s_lwe"], lwe_out), msgs) if rounded(m, delta) == want)
+    aggregated = True
+    if args.aggregate and len(live) == args.count:
+        extra["aggregate"] = aggregate_section(ctx, N, n_lwe, log_n, cyc, vk, proofs, testv, cts, out_ct, [kh], None, seconds)
+        aggregated = extra["aggregate"]["accepted"]
     if args.keys_on_device:
         ctx.device_free(keys["d_bsk"])
         ctx.device_free(keys["d_ksk"])
@@ -372,7 +423,7 @@ def main():
         "cpu_seconds_setup_and_proving": cpu, "cpu_seconds_per_proof": extra["cpu_seconds_proving"] / args.count, "verify_s": t_verify,
         "proofs_sha256": proof_hashes(proofs),
         "host": {"cpus": len(os.sched_getaffinity(0)), "loadavg_before": load0, "loadavg_after": os.getloadavg()[0]}}, **extra)))
-    return 0 if accepted == args.count and (decrypted in (None, args.count)) else 1
+    return 0 if accepted == args.count and (decrypted in (None, args.count)) and aggregated else 1
 
 
 if __name__ == "__main__":

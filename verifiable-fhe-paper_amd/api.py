@@ -398,6 +398,19 @@ SIGNATURES = {
     "vpbs_timing_enable": (_i, [_vp, _i]),
     "vpbs_timing_report": (_i, [_vp, C.c_char_p, _sz]),
     "vpbs_timing_shader_clock": (_i, [_vp, C.POINTER(C.c_double), C.POINTER(_ui)]),
+    "vpbs_aggregate_reason_text": (C.c_char_p, [_i]),
+    "vpbs_aggregate_root": (_i, [_ui, _ui, _ui, U64P, _sz, U64P, _sz, _vp, U64P, U64P, U64P, _sz, _vp, U64P]),
+    "vpbs_verify_aggregate": (_i, [_vp, _sz, U64P, _sz, _vp, U64P, U64P, U64P, _sz, _vp, C.POINTER(C.c_uint8), _sz, C.POINTER(_i), C.c_char_p, _sz]),
+    "vpbs_aggregator_create": (_i, [_vp, _vp, _sz, _vp, _ui, C.POINTER(_vp), C.c_char_p, _sz]),
+    "vpbs_aggregator_verifier_data": (_i, [_vp, U64P]),
+    "vpbs_aggregator_run": (C.c_long, [_vp, C.POINTER(C.c_uint8), C.POINTER(_sz), _sz, C.POINTER(C.c_uint8), _sz, _vp, C.c_char_p, _sz]),
+    "vpbs_aggregator_last_run": (_i, [_vp, _vp]),
+    "vpbs_aggregator_free": (None, [_vp]),
+    "vpbs_aggregate_verifier_create": (_i, [_vp, _vp, _sz, C.POINTER(_vp), C.c_char_p, _sz]),
+    "vpbs_aggregate_verifier_run": (_i, [_vp, C.POINTER(C.c_uint8), _sz, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _sz, _vp, _i, C.POINTER(_i),
+                                         C.c_char_p, _sz]),
+    "vpbs_aggregate_verifier_root": (_i, [_vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _sz, _vp, _i, U64P, C.c_char_p, _sz]),
+    "vpbs_aggregate_verifier_free": (None, [_vp]),
 }
 
 # test entries (csrc/test_entries.h): exported for the suite, not part of the C ABI
@@ -2454,6 +2467,279 @@ class RingVerifier:
     def close(self):
         if self.h:
             lib().vpbs_ring_verifier_free(self.h)
+            self.h = None
+            self.ctx._batches.discard(self)
+
+    free = close
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# ---- aggregation: the vPBS proofs of a batch folded into one proof (csrc/aggregate.hip) ----
+AGG_OK, AGG_MALFORMED, AGG_VERIFIER_DATA, AGG_PROOF, AGG_ROOT = range(5)   # vpbs_aggregate_reason, in vpbs_verify_aggregate's order
+AGG_VK_WORDS = 68
+
+
+class AggregateShapeC(C.Structure):
+    _fields_ = [("N", C.c_uint), ("K", C.c_uint), ("n_lwe", C.c_uint), ("levels", C.c_uint), ("level_shapes", C.POINTER(VerifyInputsC)),
+                ("vks", U64P)]
+
+
+class AggregateStatsC(C.Structure):
+    _fields_ = [("seconds", C.c_double), ("check_leaves_ms", C.c_double), ("witness_ms", C.c_double), ("prove_ms", C.c_double),
+                ("nodes", C.c_uint), ("depth", C.c_uint)]
+
+
+def aggregate_reason_text(reason):
+    """vpbs_aggregate_reason_text: the `why` vpbs_verify_aggregate writes when that check fails ("" for AGG_OK)"""
+    t = lib().vpbs_aggregate_reason_text(int(reason))
+    if t is None:
+        raise ValueError("no aggregate verifier reason %r" % (reason,))
+    return t.decode()
+
+
+def aggregate_depth(count):
+    """d = max(1, ceil(log2 count)): the level whose circuit proves the root over `count` leaves"""
+    if count < 1:
+        raise ValueError("aggregate_depth: count must be at least 1")
+    return max(1, (int(count) - 1).bit_length())
+
+
+def _circuit_shape(v, d):
+    """fills a VerifyInputsC from a circuit (circuit_file.CircuitDescription, or what a circuit builder's build() returns): degree, column
+    counts, gates; cap, digest and public inputs stay empty"""
+    n_constants = getattr(d, "n_constants", None)
+    if n_constants is None:
+        n_constants = d.constants.shape[0]
+    n_routed, n_wires = getattr(d, "n_routed", 80), getattr(d, "n_wires", 135)
+    v.log_n, v.rate_bits, v.cap_height = d.log_n, 3, 4
+    v.n_constants_sigmas, v.n_wires, v.n_zs_partial_products, v.n_quotient = n_constants + n_routed, n_wires, 20, 16
+    v.num_challenges = 2
+    v.n_constants, v.n_routed, v.quotient_degree_factor = n_constants, n_routed, 8
+    v.gates, v.n_gates, v.num_selectors = d.gates.arr, d.gates.n, d.gates.num_selectors
+
+
+class AggregateShape:
+    """vpbs_aggregate_shape: what a verifier of aggregates holds -- the ring (N, K, n_lwe), the level circuits A_1 .. A_levels (each an
+    object with log_n, gates and n_constants or constants: a loaded circuit file or a built circuit) and vks [levels + 1][68]: vk_0 of the
+    cyclic step circuit, then vk_l of A_l (Aggregator.verifier_data())."""
+
+    def __init__(self, N, K, n_lwe, vks, level_circuits):
+        self.N, self.K, self.n_lwe, self.levels = N, K, n_lwe, len(level_circuits)
+        self.vks = np.ascontiguousarray(_u64(vks).reshape(-1, AGG_VK_WORDS))
+        if self.levels < 1 or self.vks.shape[0] != self.levels + 1:
+            raise ValueError("AggregateShape: %d level circuits need vks [%d][68], got %s" % (self.levels, self.levels + 1, self.vks.shape))
+        self._shapes = (VerifyInputsC * self.levels)()
+        self._keep = list(level_circuits)
+        for v, d in zip(self._shapes, level_circuits):
+            _circuit_shape(v, d)
+        self.c = AggregateShapeC(N, K, n_lwe, self.levels, self._shapes, _ptr(self.vks))
+
+
+def _aggregate_args(who, N, K, n_lwe, testvs, cts, out_cts, key_hashes, key_of, testv_of):
+    """the statement arrays of an aggregate, shapes checked -> (count, testvs [n_testv][N], cts [count][n + 1], out_cts [count][K N],
+    key_hashes [n_keys][4], key_of uint32 [count] or None, testv_of uint32 [count] or None)"""
+    tv, c, o, kh = _u64(testvs), _u64(cts), _u64(out_cts), _u64(key_hashes)
+    if tv.ndim == 1:
+        tv = tv.reshape(1, -1)
+    if kh.ndim == 1:
+        kh = kh.reshape(1, -1)
+    c = c.reshape(-1, n_lwe + 1)
+    count = c.shape[0]
+    if tv.ndim != 2 or tv.shape[1] != N or kh.ndim != 2 or kh.shape[1] != 4 or o.size != count * K * N:
+        raise ValueError("%s: expected testvs [n_testv][%d], cts [count][%d], out_cts [count][%d][%d] and key_hashes [n_keys][4]; got %s, %s, %s, %s" %
+                         (who, N, n_lwe + 1, K, N, tv.shape, c.shape, o.shape, kh.shape))
+
+    def index(a, name):
+        if a is None:
+            return None
+        a = np.asarray(a)
+        if a.size and a.dtype.kind not in "iu" or a.shape != (count,):
+            raise ValueError("%s: expected %s [%d] of integers, got %s %s" % (who, name, count, a.dtype, a.shape))
+        if a.size and (int(a.min()) < 0 or int(a.max()) >= 1 << 32):
+            raise ValueError("%s: %s holds an entry that is no uint32" % (who, name))
+        return np.ascontiguousarray(a, dtype=np.uint32)
+    return (count, np.ascontiguousarray(tv), np.ascontiguousarray(c), np.ascontiguousarray(o.reshape(count, K * N)), np.ascontiguousarray(kh),
+            index(key_of, "key_of"), index(testv_of, "testv_of"))
+
+
+def _aggregate_ptrs(tv, c, o, kh, ko, to):
+    keep = np.zeros(1, np.uint64)   # a valid pointer for an empty array
+    p = lambda a: (a if a.size else keep).ctypes.data
+    p32 = lambda a: None if a is None else (a if a.size else keep).ctypes.data
+    return (keep, C.cast(p(tv), U64P), tv.shape[0], p32(to), C.cast(p(c), U64P), C.cast(p(o), U64P), C.cast(p(kh), U64P), kh.shape[0], p32(ko))
+
+
+def aggregate_root(N, K, n_lwe, vk0, testvs, cts, out_cts, key_hashes, key_of=None, testv_of=None):
+    """vpbs_aggregate_root (host): the root of the aggregate's statement over the leaves (testvs[testv_of[i]], cts[i], out_cts[i],
+    key_hashes[key_of[i]]) under the cyclic circuit's verifier data vk0 [68] -> [4].  VpbsError for no leaves, an index out of range, or a
+    raw word of testvs / out_cts / key_hashes / vk0 at or above p (no proof has such a statement)."""
+    count, tv, c, o, kh, ko, to = _aggregate_args("aggregate_root", N, K, n_lwe, testvs, cts, out_cts, key_hashes, key_of, testv_of)
+    vk = _u64(vk0).reshape(-1)
+    if vk.size != AGG_VK_WORDS:
+        raise ValueError("aggregate_root: vk0 is 68 words (digest, cap), got %d" % vk.size)
+    keep, ptv, n_tv, pto, pc, po, pkh, n_kh, pko = _aggregate_ptrs(tv, c, o, kh, ko, to)
+    out = np.zeros(4, np.uint64)
+    rc = lib().vpbs_aggregate_root(N, K, n_lwe, _ptr(vk), count, ptv, n_tv, pto, pc, po, pkh, n_kh, pko, _ptr(out))
+    if rc == 1:
+        raise VpbsError("vpbs_aggregate_root: a word of the statement is not a field element (at or above p): no proof has this statement")
+    if rc:
+        raise VpbsError("vpbs_aggregate_root: malformed arguments (count = %d; indices below n_testv = %d and n_keys = %d)" % (count, n_tv, n_kh))
+    return out
+
+
+def verify_aggregate(shape, blob, count, testvs, cts, out_cts, key_hashes, key_of=None, testv_of=None):
+    """vpbs_verify_aggregate (host): ONE proof for `count` bootstraps -> (accepted, reason), reason one of AGG_* in the order of the checks
+    (aggregate_reason_text).  shape: an AggregateShape; the statement arrays as aggregate_root; count must be their number of leaves."""
+    n, tv, c, o, kh, ko, to = _aggregate_args("verify_aggregate", shape.N, shape.K, shape.n_lwe, testvs, cts, out_cts, key_hashes, key_of, testv_of)
+    if n != count:
+        raise ValueError("verify_aggregate: count = %d but the statement has %d leaves" % (count, n))
+    keep, ptv, n_tv, pto, pc, po, pkh, n_kh, pko = _aggregate_ptrs(tv, c, o, kh, ko, to)
+    buf = (C.c_uint8 * max(1, len(blob))).from_buffer_copy(bytes(blob) or b"\0")
+    why, reason = C.create_string_buffer(256), C.c_int(0)
+    rc = lib().vpbs_verify_aggregate(C.byref(shape.c), count, ptv, n_tv, pto, pc, po, pkh, n_kh, pko, buf, len(blob), C.byref(reason), why, 256)
+    if rc < 0:
+        raise VpbsError("vpbs_verify_aggregate: " + why.value.decode())
+    return rc == 1, int(reason.value)
+
+
+class Aggregator:
+    """vpbs_aggregator: folds serialised vPBS proofs into one proof.  leaf: the cyclic step circuit (a loaded circuit file) with its
+    verifier data leaf_vk [68] (digest, cap: PbsProver / RingProver.verifier_data()[0]); level_circuits: A_1 .. A_levels as loaded circuit
+    files (circuit_file.find_aggregate_circuits) -- up to 2^levels leaves."""
+
+    def __init__(self, ctx, leaf, leaf_vk, level_circuits):
+        self.ctx, self.levels = ctx, len(level_circuits)
+        self._vk0 = _u64(leaf_vk).reshape(-1).copy()
+        if self._vk0.size != AGG_VK_WORDS:
+            raise ValueError("Aggregator: leaf_vk is 68 words (digest, cap), got %d" % self._vk0.size)
+        v = VerifyInputsC()
+        _circuit_shape(v, leaf)
+        v.constants_sigmas_cap = C.cast(self._vk0[4:].ctypes.data, U64P)
+        for i in range(4):
+            v.circuit_digest[i] = int(self._vk0[i])
+        self._keep = [leaf, v]
+        arr = (IvcCircuitC * self.levels)()
+        for c, d in zip(arr, level_circuits):
+            pre = np.ascontiguousarray(d.preset_flat, dtype=np.uint32)
+            pi = np.ascontiguousarray(d.pi_flat, dtype=np.uint32)
+            self._keep += [pre, pi, d]
+            c.circuit = C.pointer(d.circuit.c)
+            c.preset_pos, c.n_preset = pre.ctypes.data_as(U32P), pre.size
+            c.pi_pos, c.n_pi = pi.ctypes.data_as(U32P), pi.size
+            c.proof_words = d.meta["proof_words"]
+        self.h, err = C.c_void_p(), C.create_string_buffer(512)
+        rc = lib().vpbs_aggregator_create(ctx.h, C.byref(v), len(leaf.pi_pos), arr, self.levels, C.byref(self.h), err, 512)
+        if rc:
+            self.h = None
+            raise VpbsError("status %d: %s" % (rc, err.value.decode()))
+        top = level_circuits[-1]
+        self.max_bytes = 8 * (top.circuit.n_wires * 64 + (1 << 17)) + 8 * len(top.pi_pos)
+        ctx._batches.add(self)   # must not outlive its context: Context.close() frees the survivors
+
+    def verifier_data(self):
+        """-> [levels + 1][68]: vk_0 (the cyclic circuit's) .. vk_levels, what an AggregateShape takes"""
+        out = np.zeros((self.levels + 1, AGG_VK_WORDS), np.uint64)
+        lib().vpbs_aggregator_verifier_data(self.h, _ptr(out))
+        return out
+
+    def aggregate(self, blobs):
+        """serialised vPBS proofs (1 .. 2^levels of them) -> the aggregate proof's bytes.  A leaf that does not parse, does not verify or
+        carries other verifier data raises VpbsError("... leaf i: ...") before anything is proven (last_run()["nodes"] == 0)."""
+        buf, offs = pack_proofs(blobs)
+        out = np.zeros(self.max_bytes, np.uint8)
+        u8p = C.POINTER(C.c_uint8)
+        data = buf.ctypes.data_as(u8p) if buf.size else (C.c_uint8 * 1)()
+        err = C.create_string_buffer(512)
+        n = lib().vpbs_aggregator_run(self.h, data, offs.ctypes.data_as(C.POINTER(C.c_size_t)), len(blobs), out.ctypes.data_as(u8p), out.size, None,
+                                      err, 512)
+        if n < 0:
+            e = VpbsError("status %d: %s" % (n, err.value.decode()))
+            e.status = n
+            raise e
+        return out[:n].tobytes()
+
+    def last_run(self):
+        s = AggregateStatsC()
+        lib().vpbs_aggregator_last_run(self.h, C.byref(s))
+        return {k: getattr(s, k) for k, _ in AggregateStatsC._fields_}
+
+    def close(self):
+        if self.h:
+            lib().vpbs_aggregator_free(self.h)
+            self.h = None
+            self.ctx._batches.discard(self)
+
+    free = close
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class AggregateVerifier:
+    """vpbs_aggregate_verifier: verify_aggregate on the device -- leaf statements, LWE chains and the fold as kernels, the root proof through
+    the batch verifier's stages -> the host's verdict and reason.  With on_device=True testvs, cts, out_cts and key_hashes are device pointers
+    (ints) and n_testv / n_keys say how many rows the tables have; key_of and testv_of are host arrays in every mode."""
+
+    def __init__(self, ctx, shape, max_leaves):
+        self.ctx, self.shape, self.max_leaves = ctx, shape, max_leaves
+        self.h, err = C.c_void_p(), C.create_string_buffer(512)
+        rc = lib().vpbs_aggregate_verifier_create(ctx.h, C.byref(shape.c), max_leaves, C.byref(self.h), err, 512)
+        if rc:
+            self.h = None
+            raise VpbsError("status %d: %s" % (rc, err.value.decode()))
+        ctx._batches.add(self)   # must not outlive its context: Context.close() frees the survivors
+
+    def _statement(self, who, count, testvs, cts, out_cts, key_hashes, key_of, testv_of, on_device, n_testv, n_keys):
+        s = self.shape
+        if not on_device:
+            n, tv, c, o, kh, ko, to = _aggregate_args(who, s.N, s.K, s.n_lwe, testvs, cts, out_cts, key_hashes, key_of, testv_of)
+            if count is not None and n != count:
+                raise ValueError("%s: count = %d but the statement has %d leaves" % (who, count, n))
+            keep, ptv, n_tv, pto, pc, po, pkh, n_kh, pko = _aggregate_ptrs(tv, c, o, kh, ko, to)
+            return (keep, tv, c, o, kh, ko, to), n, (C.cast(ptv, C.c_void_p), n_tv, pto, C.cast(pc, C.c_void_p), C.cast(po, C.c_void_p),
+                                                     C.cast(pkh, C.c_void_p), n_kh, pko, 0)
+        if count is None or n_testv is None or n_keys is None:
+            raise ValueError("%s: device pointers need count, n_testv and n_keys" % who)
+        idx = lambda a: None if a is None else np.ascontiguousarray(np.asarray(a), dtype=np.uint32)
+        ko, to = idx(key_of), idx(testv_of)
+        for a in (ko, to):
+            if a is not None and a.shape != (count,):
+                raise ValueError("%s: key_of and testv_of are host arrays of %d entries" % (who, count))
+        p32 = lambda a: None if a is None else a.ctypes.data
+        return (ko, to), count, (int(testvs), n_testv, p32(to), int(cts), int(out_cts), int(key_hashes), n_keys, p32(ko), 1)
+
+    def root(self, testvs, cts, out_cts, key_hashes, key_of=None, testv_of=None, on_device=False, count=None, n_testv=None, n_keys=None):
+        """aggregate_root computed on the device -> [4]"""
+        keep, count, a = self._statement("AggregateVerifier.root", count, testvs, cts, out_cts, key_hashes, key_of, testv_of, on_device, n_testv, n_keys)
+        out, err = np.zeros(4, np.uint64), C.create_string_buffer(512)
+        rc = lib().vpbs_aggregate_verifier_root(self.h, count, *a, _ptr(out), err, 512)
+        if rc == 1:
+            raise VpbsError("vpbs_aggregate_verifier_root: a word of the statement is not a field element (at or above p)")
+        if rc:
+            raise VpbsError("status %d: %s" % (rc, err.value.decode()))
+        return out
+
+    def verify(self, blob, count, testvs, cts, out_cts, key_hashes, key_of=None, testv_of=None, on_device=False, n_testv=None, n_keys=None):
+        """-> (verdict, reason): verify_aggregate's, for the same arguments"""
+        keep, count, a = self._statement("AggregateVerifier.verify", count, testvs, cts, out_cts, key_hashes, key_of, testv_of, on_device, n_testv, n_keys)
+        buf = (C.c_uint8 * max(1, len(blob))).from_buffer_copy(bytes(blob) or b"\0")
+        err, reason = C.create_string_buffer(512), C.c_int(0)
+        rc = lib().vpbs_aggregate_verifier_run(self.h, buf, len(blob), count, *a, C.byref(reason), err, 512)
+        if rc < 0:
+            raise VpbsError("status %d: %s" % (rc, err.value.decode()))
+        return rc == 1, int(reason.value)
+
+    def close(self):
+        if self.h:
+            lib().vpbs_aggregate_verifier_free(self.h)
             self.h = None
             self.ctx._batches.discard(self)
 

@@ -8,7 +8,8 @@ builder: find_* locate exported files and raise when one is missing (tools/expor
 File: header {magic, log_n, n_wires, n_routed, n_gates, n_constants_cols, n_copies, n_generators, generator_words, n_preset, n_public_inputs};
 gates [n_gates][kind, p0, p1, p2]; row_gate [n]; constants [cols][n]; copies [n_copies][2]; generators {kind, p0, n_in, n_out, in.., out..}*;
 preset positions; public-input positions; sample preset values; expected public inputs; optional trailer {N, K, ELL, LOGB, n_lwe, used_rows
-[, kind, proof_words]} (kind 1: the cyclic step circuit, 2: its dummy circuit -- no sample witness in those files).
+[, kind, proof_words [, level]]} (kind 1: the cyclic step circuit, 2: its dummy circuit, 3: the aggregation circuit of `level`, whose
+proof_words are those of ONE inner proof -- no sample witness in those files).
 Positions are column * n + row."""
 import os
 
@@ -60,6 +61,8 @@ class CircuitDescription:
             self.meta = dict(zip(("N", "K", "ELL", "LOGB", "n_lwe", "used_rows"), (int(x) for x in take(6))))
         if words.size - pos >= 2:       # cyclic / dummy circuits: kind (1 / 2) and the number of proof words among the presets
             self.meta.update(zip(("kind", "proof_words"), (int(x) for x in take(2))))
+        if words.size - pos >= 1:       # aggregation circuits: the level
+            self.meta["level"] = int(take(1)[0])
         self.preset_pos = [(int(x) // n, int(x) % n) for x in self.preset_flat]
         self.pi_pos = [(int(x) // n, int(x) % n) for x in self.pi_flat]
         self.circuit = api.Circuit(self.gates, self.log_n, row_gate, self.constants, copies, self.n_wires, self.n_routed, gens)
@@ -114,3 +117,17 @@ def find_cyclic_circuit(N=1024, K=2, ELL=4, LOGB=5, n_lwe=728, log_n=16):
     if not (os.path.exists(path) and os.path.exists(dummy)):
         raise _missing("cyclic step circuit", [path, dummy], "--cyclic %d %d %d %d %d %d" % (N, K, ELL, LOGB, n_lwe, log_n))
     return path, dummy
+
+
+def aggregate_circuit_paths(N, K, ELL, LOGB, n_lwe, log_n, levels):
+    """the files of the aggregation circuits A_1 .. A_levels over vPBS proofs of the cyclic circuit at these parameters"""
+    stem = "N%d_K%d_ELL%d_LOGB%d_n%d_deg%d" % (N, K, ELL, LOGB, n_lwe, log_n)
+    return [os.path.join(DIR, "aggregate_%s_level%d.bin" % (stem, l)) for l in range(1, levels + 1)]
+
+
+def find_aggregate_circuits(N=1024, K=2, ELL=4, LOGB=5, n_lwe=728, log_n=16, levels=3):
+    """paths of A_1 .. A_levels (up to 2^levels leaves); FileNotFoundError when they have not been exported"""
+    paths = aggregate_circuit_paths(N, K, ELL, LOGB, n_lwe, log_n, levels)
+    if not all(os.path.exists(p) for p in paths):
+        raise _missing("aggregation circuits", paths, "--aggregate %d %d %d %d %d %d %d" % (N, K, ELL, LOGB, n_lwe, log_n, levels))
+    return paths

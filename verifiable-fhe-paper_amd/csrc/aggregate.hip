@@ -1,0 +1,838 @@
+// Aggregation of the vPBS proofs of a batch into ONE proof (include/vpbs_prover.h).
+//   statement  : leaf i = hash_no_pad of the public inputs its vPBS proof must carry; a binary tree of hash_no_pad(left || right) over the
+//                leaves, padded to 2^d with the last leaf (vpbs_aggregate_root on the host; ag_leaf + ag_fold on the device)
+//   prover     : vpbs_aggregator -- the level circuits A_1 .. A_levels arrive as data; every leaf is verified before anything is proven;
+//                then level by level witness plan (host) -> upload -> vpbs_prove_step, the next node's witness on a second thread
+//   verifiers  : vpbs_verify_aggregate (host) and vpbs_aggregate_verifier (device): parse at level d's shape, the vk list, the proof, the root
+// The prover part is host code against the library's own C ABI, as ivc.hip is.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <chrono>
+#include <cstring>
+#include <mutex>
+#include <string>
+#include <thread>
+#include <vector>
+
+#include "gl.h"
+#include "poseidon.h"
+#include "context.h"
+#include "verify_batch.h"
+#include "program_internal.h"
+
+namespace {
+using vpbs::DeviceError;
+using vpbs::report;
+using u32 = uint32_t;
+using u64 = uint64_t;
+
+constexpr size_t VK = 68;                 // verifier data: circuit digest [4], constants / sigmas cap [16][4]
+constexpr unsigned MAX_LEVELS = 20;
+constexpr unsigned HOST_THREADS = 16;     // the most host threads a call here uses
+
+double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+unsigned depth_of(size_t count) {   // max(1, ceil(log2 count))
+    unsigned d = 1;
+    while (((size_t)1 << d) < count) ++d;
+    return d;
+}
+
+// ================= the statement on the host =================
+struct Statement {
+    unsigned N, K, n_lwe;
+    const u64* vk0;
+    size_t count;
+    const u64* testvs;
+    size_t n_testv;
+    const u32* testv_of;
+    const u64* cts;
+    const u64* out_cts;
+    const u64* key_hashes;
+    size_t n_keys;
+    const u32* key_of;
+    size_t kn() const { return (size_t)K * N; }
+    size_t n_pi() const { return 2 * kn() + 9 + VK; }
+    size_t tv(size_t i) const { return testv_of ? testv_of[i] : (n_testv == 1 ? 0 : i); }
+    size_t key(size_t i) const { return key_of ? key_of[i] : 0; }
+};
+
+// what every entry point refuses of a statement, before it reads a word of it
+bool statement_ok(const Statement& s, const char* who, std::string* msg) {
+    auto no = [&](const std::string& m) {
+        *msg = std::string(who) + ": " + m;
+        return false;
+    };
+    if (s.count == 0) return no("count is 0: there is nothing to aggregate");
+    if (s.N == 0 || s.K == 0 || s.kn() > (1u << 20) || s.n_lwe > (1u << 24)) return no("N, K or n_lwe out of range");
+    if (!s.vk0 || !s.testvs || !s.cts || !s.out_cts || !s.key_hashes) return no("null vk0, testvs, cts, out_cts or key_hashes");
+    if (s.n_testv == 0 || s.n_keys == 0) return no("no test vector or no key hash");
+    if (!s.testv_of && s.n_testv != s.count && s.n_testv != 1)
+        return no("testv_of is null and n_testv " + std::to_string(s.n_testv) + " is neither count " + std::to_string(s.count) + " nor 1");
+    for (size_t i = 0; i < s.count; ++i) {
+        if (s.testv_of && s.testv_of[i] >= s.n_testv)
+            return no("testv_of[" + std::to_string(i) + "] = " + std::to_string(s.testv_of[i]) + " is not below n_testv " + std::to_string(s.n_testv));
+        if (s.key_of && s.key_of[i] >= s.n_keys)
+            return no("key_of[" + std::to_string(i) + "] = " + std::to_string(s.key_of[i]) + " is not below n_keys " + std::to_string(s.n_keys));
+    }
+    return true;
+}
+
+// s_i on the host: the public inputs laid out once per leaf, then the sponge.  false: a raw word at or above p (no proof has that statement)
+bool leaf_statement_host(const Statement& s, size_t i, std::vector<u64>& pis, u64 out[4]) {
+    const size_t kn = s.kn(), N = s.N;
+    pis.assign(s.n_pi(), 0);
+    std::memcpy(pis.data() + kn - N, s.testvs + s.tv(i) * N, 8 * N);
+    pis[kn] = (u64)s.n_lwe + 2;
+    std::memcpy(pis.data() + kn + 1, s.out_cts + i * kn, 8 * kn);
+    std::memcpy(pis.data() + 2 * kn + 1, s.key_hashes + 4 * s.key(i), 32);
+    const u64* ct = s.cts + i * ((size_t)s.n_lwe + 1);
+    std::vector<u64> masks((size_t)s.n_lwe + 2, 0);   // [ct[n], ct[0] .. ct[n-1], 0]: vpbs_verify_pbs's LWE chain
+    masks[0] = ct[s.n_lwe];
+    for (unsigned k = 0; k < s.n_lwe; ++k) masks[k + 1] = ct[k];
+    vpbs_hash_chain(masks.data(), masks.size(), 1, nullptr, pis.data() + 2 * kn + 5);
+    std::memcpy(pis.data() + 2 * kn + 9, s.vk0, 8 * VK);
+    for (size_t j = 0; j < pis.size(); ++j)
+        if (pis[j] >= gl::P) return false;
+    poseidon::hash_no_pad_host(pis.data(), pis.size(), out);
+    return true;
+}
+
+// the root over the leaves; false: some raw word is at or above p
+bool root_host(const Statement& s, u64 out[4]) {
+    const size_t count = s.count;
+    const unsigned d = depth_of(count);
+    std::vector<u64> level(4 * ((size_t)1 << d));
+    std::vector<uint8_t> ok(count, 1);
+    const unsigned hw = std::max(1u, std::min(HOST_THREADS, std::thread::hardware_concurrency()));
+    const unsigned threads = (unsigned)std::min<size_t>(hw, (count + 3) / 4);
+    auto work = [&](unsigned t) {
+        std::vector<u64> pis;
+        for (size_t i = t; i < count; i += threads) ok[i] = leaf_statement_host(s, i, pis, level.data() + 4 * i) ? 1 : 0;
+    };
+    if (threads <= 1) {
+        work(0);
+    } else {
+        std::vector<std::thread> pool;
+        for (unsigned t = 0; t < threads; ++t) pool.emplace_back(work, t);
+        for (auto& t : pool) t.join();
+    }
+    for (size_t i = 0; i < count; ++i)
+        if (!ok[i]) return false;
+    for (size_t i = count; i < ((size_t)1 << d); ++i) std::memcpy(level.data() + 4 * i, level.data() + 4 * (count - 1), 32);   // the padding
+    for (size_t n = (size_t)1 << d; n > 1; n /= 2)
+        for (size_t k = 0; k < n / 2; ++k) {
+            u64 h[4];
+            poseidon::hash_no_pad_host(level.data() + 8 * k, 8, h);
+            std::memcpy(level.data() + 4 * k, h, 32);
+        }
+    std::memcpy(out, level.data(), 32);
+    return true;
+}
+
+bool shape_ok(const vpbs_aggregate_shape* sh) {
+    return sh && sh->level_shapes && sh->vks && sh->levels >= 1 && sh->levels <= MAX_LEVELS;
+}
+
+// A_l's verify inputs: the caller's shape with cap and digest taken from vks[l]
+vpbs_verify_inputs level_inputs(const vpbs_aggregate_shape& sh, unsigned l) {
+    vpbs_verify_inputs v = sh.level_shapes[l - 1];
+    const u64* vk = sh.vks + VK * l;
+    std::memcpy(v.circuit_digest, vk, 32);
+    v.constants_sigmas_cap = vk + 4;
+    v.public_inputs = nullptr;
+    v.n_public_inputs = 0;
+    v.fri_only = 0;
+    return v;
+}
+
+size_t openings_words(const vpbs_verify_inputs& c) {
+    return 2 * ((size_t)c.n_constants_sigmas + c.n_wires + c.n_zs_partial_products + c.n_quotient + c.num_challenges);
+}
+
+// ================= the statement on the device =================
+struct AggShape {
+    u32 N, kn, n_lwe, n_pi;
+};
+
+// Leaf statements: one leaf per 16-lane block, lane l < 12 owns sponge element l (the permute_wide layout of vp_lwe_chain).  Block b of
+// the sponge overwrites the rate lanes l < 8 with public inputs 8 b + l, generated here from the statement's parts; n_pi = 2 K N + 77 is no
+// multiple of 8, so the last block is partial and its upper rate lanes keep the old state.  A raw word at or above p sets *flag (the
+// leaf's own result is then meaningless: no proof has that statement).  Bounds: testv_of[i] < n_testv, key_of[i] < n_keys (checked on the
+// host), j - 2 kn - 9 < 68.
+__global__ __launch_bounds__(16) void ag_leaf(const u64* __restrict__ testvs, const u32* __restrict__ testv_of, const u64* __restrict__ out_ct,
+                                              const u64* __restrict__ key_hashes, const u32* __restrict__ key_of, const u64* __restrict__ lwe,
+                                              const u64* __restrict__ vk0, AggShape S, u64* __restrict__ stmt, u32* __restrict__ flag) {
+    __shared__ u64 sh[poseidon::WIDE_LDS_WORDS];
+    const unsigned l = threadIdx.x;
+    const u32 i = blockIdx.x;
+    const u64* tv = testvs + (u64)testv_of[i] * S.N;
+    const u64* oc = out_ct + (u64)i * S.kn;
+    const u64* kh = key_hashes + (u64)key_of[i] * 4;
+    const u64* lw = lwe + (u64)i * 4;
+    auto word = [&](u32 j) -> u64 {
+        if (j < S.kn - S.N) return 0;
+        if (j < S.kn) return tv[j - (S.kn - S.N)];
+        if (j == S.kn) return (u64)S.n_lwe + 2;
+        if (j <= 2 * S.kn) return oc[j - S.kn - 1];
+        if (j < 2 * S.kn + 5) return kh[j - 2 * S.kn - 1];
+        if (j < 2 * S.kn + 9) return lw[j - 2 * S.kn - 5];
+        return vk0[j - 2 * S.kn - 9];
+    };
+    const bool rate = l < 8;
+    u64 x = 0;
+    bool bad = false;
+    u64 next = rate && l < S.n_pi ? word(l) : 0;   // block b + 1 is loaded while block b runs: the loads are off the dependent chain
+    for (u32 off = 0; off < S.n_pi; off += 8) {
+        const bool mine = rate && off + l < S.n_pi;
+        const u64 w = next;
+        const u32 jn = off + 8 + l;
+        next = rate && jn < S.n_pi ? word(jn) : 0;
+        if (mine) {
+            bad = bad || w >= gl::P;
+            x = gl::canon(w);
+        }
+        x = poseidon::permute_wide(x, sh, l);
+    }
+    if (l < 4) stmt[(u64)i * 4 + l] = x;
+    if (bad) atomicOr(flag, 1u);
+}
+
+// One level of the tree: node k = hash_no_pad(in[2k] || in[2k + 1]), one permutation of [left, right, 0 0 0 0], one node per 16-lane block.
+// Entries at or past n_in read entry n_in - 1: at the leaves that IS the padding rule (n_in = count); above them n_in is the whole level.
+__global__ __launch_bounds__(16) void ag_fold(const u64* __restrict__ in, u32 n_in, u64* __restrict__ out) {
+    __shared__ u64 sh[poseidon::WIDE_LDS_WORDS];
+    const unsigned l = threadIdx.x;
+    const u32 k = blockIdx.x;
+    const u32 a = min(2 * k, n_in - 1), b = min(2 * k + 1, n_in - 1);
+    u64 x = 0;
+    if (l < 4) x = in[(u64)a * 4 + l];
+    else if (l < 8) x = in[(u64)b * 4 + l - 4];
+    x = poseidon::permute_wide(x, sh, l);
+    if (l < 4) out[(u64)k * 4 + l] = x;
+}
+
+// the first failing check in vpbs_verify_aggregate's order -> out: verdict | reason.  pis: the root proof's public inputs as the batch
+// verifier parsed them (n_expected = 4 + 68 d words are inside its slot whatever the bytes were)
+__global__ void ag_result(const uint8_t* __restrict__ proof_reason, const u32* __restrict__ n_pi, const u64* __restrict__ pis,
+                          const u64* __restrict__ vks, const u64* __restrict__ root, const u32* __restrict__ flag, u32 n_expected,
+                          uint8_t* __restrict__ out) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const uint8_t pr = proof_reason[0];
+    uint8_t reason = VPBS_AGG_OK;
+    if (pr == VPBS_VERIFY_MALFORMED || n_pi[0] != n_expected) {
+        reason = VPBS_AGG_MALFORMED;
+    } else {
+        bool vk_bad = false, root_bad = *flag != 0;
+        for (u32 j = 4; j < n_expected; ++j) vk_bad = vk_bad || pis[j] != vks[j - 4];
+        for (u32 j = 0; j < 4; ++j) root_bad = root_bad || pis[j] != root[j];
+        reason = vk_bad ? VPBS_AGG_VERIFIER_DATA : pr != VPBS_VERIFY_OK ? VPBS_AGG_PROOF : root_bad ? VPBS_AGG_ROOT : VPBS_AGG_OK;
+    }
+    out[0] = reason == VPBS_AGG_OK ? 1 : 0;
+    out[1] = reason;
+}
+}  // namespace
+
+struct vpbs_aggregate_verifier {
+    vpbs_ctx* ctx = nullptr;
+    unsigned N = 0, K = 0, n_lwe = 0, levels = 0;
+    size_t max_leaves = 0;
+    std::vector<vpbs_proof_verifier*> proofs;   // [levels]: the batch verifier of A_l's proofs, a batch of one
+    std::vector<void*> owned;
+    u64 *d_vks = nullptr, *d_in = nullptr, *d_lwe = nullptr, *d_stmt = nullptr, *d_nodes[2] = {nullptr, nullptr};
+    u32* d_flag = nullptr;
+    uint8_t* d_out = nullptr;
+    u64* h_in = nullptr;      // pinned: cts | out_cts | testvs | key_hashes | testv_of, key_of
+    u64* h_out = nullptr;     // pinned: root [4] | flag | verdict, reason
+    std::mutex mu;
+    size_t kn() const { return (size_t)K * N; }
+    size_t in_words() const { return max_leaves * ((size_t)n_lwe + 1 + kn() + N + 4 + 1); }
+    void* alloc(size_t bytes) {
+        void* d = ctx->alloc_bytes(std::max<size_t>(8, bytes));
+        owned.push_back(d);
+        return d;
+    }
+    ~vpbs_aggregate_verifier() {
+        if (!ctx) return;
+        (void)hipSetDevice(ctx->device);
+        (void)vpbs::stream_sync(ctx->stream);
+        for (void* p : owned) ctx->release(p);
+        if (h_in) (void)hipHostFree(h_in);
+        if (h_out) (void)hipHostFree(h_out);
+        for (auto* p : proofs) vpbs_proof_verifier_free(p);
+    }
+};
+
+namespace {
+// the statement stages queued on the context's stream: after them d_nodes[*top] holds the root and d_flag the raw-word flag
+void statement_enqueue(vpbs_aggregate_verifier* v, const Statement& s, int on_device, const u64** d_root) {
+    vpbs_ctx* ctx = v->ctx;
+    hipStream_t st = ctx->stream;
+    const size_t count = s.count, kn = v->kn();
+    const size_t n_ct = count * ((size_t)s.n_lwe + 1), n_out = count * kn, n_tv = s.n_testv * (size_t)s.N, n_kh = 4 * s.n_keys;
+    // the index arrays always come from the host; the word arrays only when they are host arrays
+    size_t at = 0;
+    const u64 *d_ct = s.cts, *d_oc = s.out_cts, *d_tv = s.testvs, *d_kh = s.key_hashes;
+    if (!on_device) {
+        std::memcpy(v->h_in, s.cts, 8 * n_ct);
+        std::memcpy(v->h_in + n_ct, s.out_cts, 8 * n_out);
+        std::memcpy(v->h_in + n_ct + n_out, s.testvs, 8 * n_tv);
+        std::memcpy(v->h_in + n_ct + n_out + n_tv, s.key_hashes, 8 * n_kh);
+        at = n_ct + n_out + n_tv + n_kh;
+        d_ct = v->d_in;
+        d_oc = v->d_in + n_ct;
+        d_tv = v->d_in + n_ct + n_out;
+        d_kh = v->d_in + n_ct + n_out + n_tv;
+    }
+    u32* idx = reinterpret_cast<u32*>(v->h_in + at);
+    for (size_t i = 0; i < count; ++i) {
+        idx[i] = (u32)s.tv(i);
+        idx[count + i] = (u32)s.key(i);
+    }
+    VPBS_HIP(hipMemcpyAsync(v->d_in, v->h_in, 8 * (at + count), hipMemcpyHostToDevice, st));
+    const u32* d_idx = reinterpret_cast<const u32*>(v->d_in + at);
+    VPBS_HIP(hipMemsetAsync(v->d_flag, 0, 4, st));
+    vpbs::lwe_chain_enqueue(st, d_ct, s.n_lwe, count, v->d_lwe);
+    const AggShape S{s.N, (u32)kn, s.n_lwe, (u32)s.n_pi()};
+    {
+        vpbs::Timed t(ctx, "ag_leaf");
+        ag_leaf<<<(u32)count, 16, 0, st>>>(d_tv, d_idx, d_oc, d_kh, d_idx + count, v->d_lwe, v->d_vks, S, v->d_stmt, v->d_flag);
+    }
+    VPBS_HIP(hipGetLastError());
+    const unsigned d = depth_of(count);
+    const u64* in = v->d_stmt;
+    u32 n_in = (u32)count;
+    {
+        vpbs::Timed t(ctx, "ag_fold");
+        for (unsigned l = 1; l <= d; ++l) {
+            const u32 nodes = 1u << (d - l);
+            u64* out = v->d_nodes[l & 1];
+            ag_fold<<<nodes, 16, 0, st>>>(in, n_in, out);
+            in = out;
+            n_in = nodes;
+        }
+    }
+    VPBS_HIP(hipGetLastError());
+    *d_root = in;
+}
+
+bool verifier_args_ok(vpbs_aggregate_verifier* v, const Statement& s, const char* who, std::string* msg) {
+    if (!statement_ok(s, who, msg)) return false;
+    if (s.count > v->max_leaves || s.n_testv > v->max_leaves || s.n_keys > v->max_leaves) {
+        *msg = std::string(who) + ": count, n_testv or n_keys exceeds max_leaves " + std::to_string(v->max_leaves);
+        return false;
+    }
+    if (depth_of(s.count) > v->levels) {
+        *msg = std::string(who) + ": count " + std::to_string(s.count) + " exceeds 2^levels = " + std::to_string((size_t)1 << v->levels);
+        return false;
+    }
+    return true;
+}
+}  // namespace
+
+// ================= the prover =================
+namespace {
+struct Level {   // one circuit A_l on the context
+    vpbs_ctx* ctx = nullptr;
+    unsigned log_n = 0, n_wires = 0, n_routed = 0, n_const_cols = 0, num_selectors = 0;
+    size_t n = 0, n_pi = 0, n_preset = 0, inner_words = 0, inner_pi = 0;
+    std::vector<vpbs_gate> gates;
+    std::vector<uint32_t> pi_pos;
+    std::vector<u64> vk;
+    u64* d_sigma = nullptr;
+    vpbs_batch* cs = nullptr;
+    vpbs_witness_plan* plan = nullptr;
+    vpbs_step_sizes sz{};
+    size_t proof_words() const { return 3 * sz.cap_words + sz.openings_words + sz.fri_words; }
+
+    void step_inputs(vpbs_step_inputs& in, const u64* d_wires, const u64* pis) const {
+        in = vpbs_step_inputs{};
+        in.log_n = log_n; in.n_wires = n_wires; in.n_zs_partial_products = 20; in.n_quotient = 16; in.num_challenges = 2;
+        in.inputs_on_device = 1;
+        in.wires_values = d_wires;
+        in.constants_sigmas = cs;
+        for (int i = 0; i < 4; ++i) in.circuit_digest[i] = vk[i];
+        in.public_inputs = pis; in.n_public_inputs = n_pi;
+        in.forced_pow = VPBS_POW_ANY;
+        in.sigmas_values = d_sigma; in.sigmas_on_device = 1;
+        in.n_routed = n_routed; in.quotient_degree_factor = 8; in.n_constants = n_const_cols;
+        in.gates = gates.data(); in.n_gates = (unsigned)gates.size(); in.num_selectors = num_selectors;
+    }
+    int init(vpbs_ctx* c, const vpbs_ivc_circuit& d, std::string& err) {
+        ctx = c;
+        const vpbs_circuit& k = *d.circuit;
+        log_n = k.log_n; n_wires = k.n_wires; n_routed = k.n_routed; n_const_cols = k.n_constants_cols; num_selectors = k.num_selectors;
+        n = (size_t)1 << log_n;
+        gates.assign(k.gates, k.gates + k.n_gates);
+        pi_pos.assign(d.pi_pos, d.pi_pos + d.n_pi);
+        n_pi = d.n_pi;
+        n_preset = d.n_preset;
+        inner_words = d.proof_words;
+        std::vector<u64> csv((size_t)(n_const_cols + n_routed) * n);
+        std::memcpy(csv.data(), k.constants, 8 * (size_t)n_const_cols * n);
+        u64* sigma = csv.data() + (size_t)n_const_cols * n;
+        if (vpbs_sigma_values(&k, sigma) != 0) return err = "sigma polynomials: malformed copy constraints", VPBS_ERR_INVALID;
+        std::vector<u64> cap(VK - 4);
+        int rc = vpbs_commit_values(ctx, csv.data(), n_const_cols + n_routed, log_n, &cs, cap.data());
+        if (rc != 0) return err = std::string("constants / sigmas commitment: ") + vpbs_last_error(ctx), rc;
+        vk.assign(4, 0);
+        vpbs_compat compat;
+        vpbs_ctx_get_compat(ctx, &compat);
+        vpbs_circuit_digest(&compat, cap.data(), cap.size(), log_n, vk.data());
+        vk.insert(vk.end(), cap.begin(), cap.end());
+        rc = vpbs_device_alloc(ctx, (size_t)n_routed * n, &d_sigma);
+        if (rc == 0) rc = vpbs_device_upload(ctx, d_sigma, sigma, (size_t)n_routed * n);
+        if (rc != 0) return err = std::string("sigma values to the device: ") + vpbs_last_error(ctx), rc;
+        char e[256] = {0};
+        rc = vpbs_witness_plan_create(&k, d.preset_pos, d.n_preset, &plan, e, sizeof e);
+        if (rc != 0) return err = std::string("witness plan: ") + e, rc;
+        vpbs_step_inputs in;
+        step_inputs(in, nullptr, nullptr);
+        if (vpbs_step_sizes_get(ctx, &in, &sz) != 0) return err = "no step proof of this shape", VPBS_ERR_INVALID;
+        return VPBS_OK;
+    }
+    void release() {
+        if (plan) vpbs_witness_plan_free(plan);
+        if (cs) vpbs_batch_free(cs);
+        if (d_sigma) vpbs_device_free(ctx, d_sigma);
+        plan = nullptr; cs = nullptr; d_sigma = nullptr;
+    }
+};
+
+struct Proof {   // a leaf or a node: the flat proof words (caps, openings, FRI) and the public inputs
+    std::vector<u64> flat, pis;
+};
+}  // namespace
+
+struct vpbs_aggregator {
+    vpbs_ctx* ctx = nullptr;
+    vpbs_verify_inputs leaf{};
+    std::vector<vpbs_gate> leaf_gates;
+    std::vector<u64> vk0;
+    size_t leaf_n_pi = 0, leaf_words = 0;
+    std::vector<Level> levels;
+    u64 *bufs[2] = {nullptr, nullptr}, *d_wires = nullptr;
+    size_t wire_words = 0;
+    vpbs_aggregate_stats last{};
+    std::mutex mu;
+    ~vpbs_aggregator() {
+        for (auto b : bufs)
+            if (b) vpbs_host_free(b);
+        if (d_wires) vpbs_device_free(ctx, d_wires);
+        for (auto& l : levels) l.release();
+    }
+};
+
+extern "C" {
+
+const char* vpbs_aggregate_reason_text(int reason) {
+    switch (reason) {
+        case VPBS_AGG_OK: return "";
+        case VPBS_AGG_MALFORMED: return "the bytes are not an aggregate proof of this depth (shape, canonical field elements, number of public inputs)";
+        case VPBS_AGG_VERIFIER_DATA: return "the aggregate carries other verifier data than the expected circuits'";
+        case VPBS_AGG_PROOF: return "the aggregate proof does not verify";
+        case VPBS_AGG_ROOT: return "the aggregate's root is not the root of this statement";
+        default: return nullptr;
+    }
+}
+
+int vpbs_aggregate_root(unsigned N, unsigned K, unsigned n_lwe, const uint64_t* vk0, size_t count, const uint64_t* testvs, size_t n_testv,
+                        const uint32_t* testv_of, const uint64_t* cts, const uint64_t* out_cts, const uint64_t* key_hashes, size_t n_keys,
+                        const uint32_t* key_of, uint64_t out[4]) {
+    const Statement s{N, K, n_lwe, vk0, count, testvs, n_testv, testv_of, cts, out_cts, key_hashes, n_keys, key_of};
+    std::string msg;
+    if (!out || !statement_ok(s, "vpbs_aggregate_root", &msg)) return VPBS_ERR_INVALID;
+    u64 root[4];
+    if (!root_host(s, root)) return 1;
+    std::memcpy(out, root, 32);
+    return VPBS_OK;
+}
+
+int vpbs_verify_aggregate(const vpbs_aggregate_shape* shape, size_t count, const uint64_t* testvs, size_t n_testv, const uint32_t* testv_of,
+                          const uint64_t* cts, const uint64_t* out_cts, const uint64_t* key_hashes, size_t n_keys, const uint32_t* key_of,
+                          const uint8_t* bytes, size_t len, int* reason, char* why, size_t why_len) {
+    auto verdict = [&](int r) {
+        if (reason) *reason = r;
+        report(why, why_len, vpbs_aggregate_reason_text(r));
+        return r == VPBS_AGG_OK ? 1 : 0;
+    };
+    if (reason) *reason = VPBS_AGG_MALFORMED;
+    if (!shape_ok(shape) || !bytes) return report(why, why_len, "vpbs_verify_aggregate: null or malformed shape, or null bytes"), VPBS_ERR_INVALID;
+    const Statement s{shape->N, shape->K, shape->n_lwe, shape->vks, count, testvs, n_testv, testv_of, cts, out_cts, key_hashes, n_keys, key_of};
+    std::string msg;
+    if (!statement_ok(s, "vpbs_verify_aggregate", &msg)) return report(why, why_len, msg), VPBS_ERR_INVALID;
+    const unsigned d = depth_of(count);
+    if (d > shape->levels)
+        return report(why, why_len, "vpbs_verify_aggregate: count " + std::to_string(count) + " exceeds 2^levels = " +
+                                        std::to_string((size_t)1 << shape->levels)), VPBS_ERR_INVALID;
+    vpbs_verify_inputs c = level_inputs(*shape, d);
+    if (c.cap_height != 4) return report(why, why_len, "vpbs_verify_aggregate: the level circuits have cap_height 4"), VPBS_ERR_INVALID;
+    const size_t n_pi = 4 + VK * d, cap_words = (size_t)4 << c.cap_height;
+    std::vector<u64> caps(3 * cap_words), openings(openings_words(c)), fri(len / 8 + 8), pis(n_pi);
+    if (vpbs_step_proof_from_bytes(&c, bytes, len, caps.data(), openings.data(), fri.data(), pis.data(), n_pi) != (long)n_pi)
+        return verdict(VPBS_AGG_MALFORMED);
+    if (std::memcmp(pis.data() + 4, shape->vks, 8 * VK * d) != 0) return verdict(VPBS_AGG_VERIFIER_DATA);
+    c.public_inputs = pis.data();
+    c.n_public_inputs = n_pi;
+    const int ok = vpbs_verify_step(&c, caps.data(), openings.data(), fri.data());
+    if (ok < 0) return report(why, why_len, "vpbs_verify_aggregate: malformed circuit description"), ok;
+    if (ok != 1) return verdict(VPBS_AGG_PROOF);
+    u64 root[4];
+    if (!root_host(s, root) || std::memcmp(root, pis.data(), 32) != 0) return verdict(VPBS_AGG_ROOT);
+    return verdict(VPBS_AGG_OK);
+}
+
+int vpbs_aggregator_create(vpbs_ctx* ctx, const vpbs_verify_inputs* leaf, size_t leaf_n_pi, const vpbs_ivc_circuit* levels, unsigned n_levels,
+                           vpbs_aggregator** out, char* err, size_t err_len) {
+    if (out) *out = nullptr;
+    report(err, err_len, "");
+    auto refuse = [&](const std::string& m) {
+        report(err, err_len, "vpbs_aggregator_create: " + m);
+        return VPBS_ERR_INVALID;
+    };
+    if (!ctx || !leaf || !levels || !out || !leaf->constants_sigmas_cap || n_levels == 0 || n_levels > MAX_LEVELS || leaf_n_pi < VK)
+        return refuse("malformed arguments");
+    if (vpbs_ctx_rate_bits(ctx) != 3 || vpbs_ctx_cap_height(ctx) != 4 || leaf->rate_bits != 3 || leaf->cap_height != 4)
+        return refuse("aggregation needs a context and proofs with rate_bits = 3 and cap_height = 4 (standard_recursion_config)");
+    for (unsigned l = 0; l < n_levels; ++l)
+        if (!levels[l].circuit || !levels[l].preset_pos || !levels[l].pi_pos) return refuse("level " + std::to_string(l + 1) + ": null circuit, preset_pos or pi_pos");
+    auto* a = new vpbs_aggregator();
+    a->ctx = ctx;
+    a->leaf = *leaf;
+    a->leaf.fri_only = 0;
+    a->leaf.public_inputs = nullptr;
+    a->leaf.n_public_inputs = 0;
+    a->leaf.compat = nullptr;
+    if (leaf->gates) {
+        a->leaf_gates.assign(leaf->gates, leaf->gates + leaf->n_gates);
+        a->leaf.gates = a->leaf_gates.data();
+    }
+    a->vk0.assign(leaf->circuit_digest, leaf->circuit_digest + 4);
+    a->vk0.insert(a->vk0.end(), leaf->constants_sigmas_cap, leaf->constants_sigmas_cap + VK - 4);
+    a->leaf.constants_sigmas_cap = a->vk0.data() + 4;
+    a->leaf_n_pi = leaf_n_pi;
+    a->levels.resize(n_levels);
+    std::string msg;
+    int rc = VPBS_OK;
+    size_t inner_words = 0, inner_pi = leaf_n_pi;
+    for (unsigned l = 1; l <= n_levels && rc == 0; ++l) {
+        Level& L = a->levels[l - 1];
+        const vpbs_ivc_circuit& d = levels[l - 1];
+        if (d.n_pi != 4 + VK * l || d.n_preset != 2 * (d.proof_words + inner_pi) + VK * l || (l > 1 && d.proof_words != inner_words)) {
+            msg = "level " + std::to_string(l) + ": not the aggregation circuit of this level (public inputs / PartialWitness layout / inner proof words)";
+            rc = VPBS_ERR_INVALID;
+            break;
+        }
+        rc = L.init(ctx, d, msg);
+        if (rc != 0) msg = "level " + std::to_string(l) + ": " + msg;
+        L.inner_pi = inner_pi;
+        inner_words = L.proof_words();
+        inner_pi = L.n_pi;
+        a->wire_words = std::max(a->wire_words, (size_t)L.n_wires * L.n);
+    }
+    if (rc == 0) {
+        a->leaf_words = a->levels[0].inner_words;
+        const size_t lw = 3 * ((size_t)4 << 4) + openings_words(a->leaf);
+        if (a->leaf_words <= lw) {
+            msg = "level 1: the inner proof is shorter than the leaf circuit's caps and openings";
+            rc = VPBS_ERR_INVALID;
+        }
+    }
+    if (rc == 0) {
+        for (auto& b : a->bufs)
+            if (!(b = static_cast<u64*>(vpbs_host_alloc(8 * a->wire_words)))) rc = VPBS_ERR_OOM;
+        if (rc == 0) rc = vpbs_device_alloc(ctx, a->wire_words, &a->d_wires);
+        if (rc != 0) msg = "wire matrices: out of (pinned or device) memory";
+    }
+    if (rc != 0) {
+        report(err, err_len, "vpbs_aggregator_create: " + msg);
+        delete a;
+        return rc;
+    }
+    *out = a;
+    return VPBS_OK;
+}
+
+int vpbs_aggregator_verifier_data(const vpbs_aggregator* a, uint64_t* out) {
+    if (!a || !out) return VPBS_ERR_INVALID;
+    std::memcpy(out, a->vk0.data(), 8 * VK);
+    for (size_t l = 0; l < a->levels.size(); ++l) std::memcpy(out + VK * (l + 1), a->levels[l].vk.data(), 8 * VK);
+    return VPBS_OK;
+}
+
+int vpbs_aggregator_last_run(const vpbs_aggregator* a, vpbs_aggregate_stats* out) {
+    if (!a || !out) return VPBS_ERR_INVALID;
+    *out = a->last;
+    return VPBS_OK;
+}
+
+void vpbs_aggregator_free(vpbs_aggregator* a) { delete a; }
+
+long vpbs_aggregator_run(vpbs_aggregator* a, const uint8_t* bytes, const size_t* offsets, size_t count, uint8_t* out, size_t capacity,
+                         vpbs_aggregate_stats* stats, char* err, size_t err_len) {
+    report(err, err_len, "");
+    if (stats) *stats = vpbs_aggregate_stats{};
+    auto fail = [&](long rc, const std::string& m) {
+        report(err, err_len, "vpbs_aggregator_run: " + m);
+        if (stats && a) *stats = a->last;
+        return rc;
+    };
+    if (!a) return fail(VPBS_ERR_INVALID, "null aggregator");
+    std::lock_guard<std::mutex> lock(a->mu);
+    a->last = vpbs_aggregate_stats{};
+    if (!bytes || !offsets || !out) return fail(VPBS_ERR_INVALID, "null bytes, offsets or out");
+    if (count == 0) return fail(VPBS_ERR_INVALID, "count is 0: there is nothing to aggregate");
+    const unsigned d = depth_of(count);
+    if (d > a->levels.size())
+        return fail(VPBS_ERR_INVALID, "count " + std::to_string(count) + " exceeds 2^levels = " + std::to_string((size_t)1 << a->levels.size()));
+    for (size_t i = 0; i < count; ++i)
+        if (offsets[i + 1] < offsets[i]) return fail(VPBS_ERR_INVALID, "offsets decrease at leaf " + std::to_string(i));
+    const double t_start = now();
+    a->last.depth = d;
+    // ---- every leaf is parsed, verified and compared with vk_0 before anything is proven ----
+    std::vector<Proof> cur(count);
+    std::vector<std::string> why(count);
+    {
+        const size_t cap3 = 3 * ((size_t)4 << 4), op = openings_words(a->leaf), fri_words = a->leaf_words - cap3 - op;
+        const unsigned hw = std::max(1u, std::min(HOST_THREADS, std::thread::hardware_concurrency()));
+        const unsigned threads = (unsigned)std::min<size_t>(hw, count);
+        auto work = [&](unsigned t) {
+            for (size_t i = t; i < count; i += threads) {
+                Proof& p = cur[i];
+                const size_t len = offsets[i + 1] - offsets[i];
+                p.pis.assign(a->leaf_n_pi, 0);
+                std::vector<u64> fri(std::max(fri_words, len / 8 + 8));
+                p.flat.assign(a->leaf_words, 0);
+                const long n = vpbs_step_proof_from_bytes(&a->leaf, bytes + offsets[i], len, p.flat.data(), p.flat.data() + cap3, fri.data(), p.pis.data(),
+                                                          a->leaf_n_pi);
+                // a proof of the leaf shape has exactly leaf_words words: the parser accepts no other length of FRI section
+                if (n != (long)a->leaf_n_pi || 8 * (a->leaf_words + a->leaf_n_pi) > len) {
+                    why[i] = "the bytes are not a vPBS proof of the leaf circuit (shape, canonical field elements, number of public inputs)";
+                    continue;
+                }
+                std::memcpy(p.flat.data() + cap3 + op, fri.data(), 8 * fri_words);
+                if (std::memcmp(p.pis.data() + a->leaf_n_pi - VK, a->vk0.data(), 8 * VK) != 0) {
+                    why[i] = "the proof carries other verifier data than vk_0";
+                    continue;
+                }
+                vpbs_verify_inputs v = a->leaf;
+                v.public_inputs = p.pis.data();
+                v.n_public_inputs = a->leaf_n_pi;
+                if (vpbs_verify_step(&v, p.flat.data(), p.flat.data() + cap3, fri.data()) != 1) why[i] = "the proof does not verify";
+            }
+        };
+        if (threads <= 1) {
+            work(0);
+        } else {
+            std::vector<std::thread> pool;
+            for (unsigned t = 0; t < threads; ++t) pool.emplace_back(work, t);
+            for (auto& t : pool) t.join();
+        }
+        a->last.check_leaves_ms = 1e3 * (now() - t_start);
+        for (size_t i = 0; i < count; ++i)
+            if (!why[i].empty()) {
+                a->last.seconds = now() - t_start;
+                return fail(VPBS_ERR_INVALID, "leaf " + std::to_string(i) + ": " + why[i] + "; nothing was proven");
+            }
+    }
+    // ---- level by level.  ids: which proof of `cur` stands at each position of the padded level (equal ids: the same proof) ----
+    std::vector<size_t> ids((size_t)1 << d);
+    for (size_t i = 0; i < ids.size(); ++i) ids[i] = std::min(i, count - 1);
+    std::vector<u64> vks((a->levels.size() + 1) * VK);
+    vpbs_aggregator_verifier_data(a, vks.data());
+    vpbs_step_inputs in{};
+    std::vector<u64> caps, openings, fri;
+    for (unsigned l = 1; l <= d; ++l) {
+        const Level& L = a->levels[l - 1];
+        // the distinct nodes of this level, in order: a node whose children are those of its left neighbour is that neighbour
+        std::vector<std::pair<size_t, size_t>> jobs;
+        std::vector<size_t> next_ids(ids.size() / 2);
+        for (size_t k = 0; k < next_ids.size(); ++k) {
+            const std::pair<size_t, size_t> ch{ids[2 * k], ids[2 * k + 1]};
+            if (jobs.empty() || jobs.back() != ch) jobs.push_back(ch);
+            next_ids[k] = jobs.size() - 1;
+        }
+        std::vector<Proof> next(jobs.size());
+        std::string werr[2];
+        double wms[2] = {0, 0};
+        auto witness = [&](size_t j) {   // the node's PartialWitness in the circuit's order, then the plan
+            const double t0 = now();
+            const Proof &x = cur[jobs[j].first], &y = cur[jobs[j].second];
+            std::vector<u64> vals;
+            vals.reserve(L.n_preset);
+            vals.insert(vals.end(), x.flat.begin(), x.flat.end());
+            vals.insert(vals.end(), x.pis.begin(), x.pis.end());
+            vals.insert(vals.end(), y.flat.begin(), y.flat.end());
+            vals.insert(vals.end(), y.pis.begin(), y.pis.end());
+            vals.insert(vals.end(), vks.begin(), vks.begin() + VK * l);
+            char e[256] = {0};
+            werr[j & 1].clear();
+            if (vals.size() != L.n_preset) werr[j & 1] = "the children do not have the circuit's shape";
+            else if (vpbs_witness_plan_run(L.plan, vals.data(), 8, a->bufs[j & 1], e, sizeof e) != 0) werr[j & 1] = std::string("witness: ") + e;
+            wms[j & 1] = 1e3 * (now() - t0);
+        };
+        witness(0);
+        for (size_t j = 0; j < jobs.size(); ++j) {
+            const std::string at = "level " + std::to_string(l) + ", node " + std::to_string(j) + ": ";
+            a->last.witness_ms += wms[j & 1];
+            if (!werr[j & 1].empty()) {
+                a->last.seconds = now() - t_start;
+                return fail(VPBS_ERR_INVALID, at + werr[j & 1]);
+            }
+            const u64* wires = a->bufs[j & 1];
+            Proof& p = next[j];
+            p.pis.resize(L.n_pi);
+            for (size_t i = 0; i < L.n_pi; ++i) p.pis[i] = wires[L.pi_pos[i]];
+            int rc = vpbs_device_upload(a->ctx, a->d_wires, wires, (size_t)L.n_wires * L.n);
+            std::thread ahead;   // the next node's witness while this one is being proven (the other buffer)
+            if (j + 1 < jobs.size()) ahead = std::thread(witness, j + 1);
+            const double t0 = now();
+            p.flat.assign(L.proof_words(), 0);
+            L.step_inputs(in, a->d_wires, p.pis.data());
+            u64 *cp = p.flat.data(), *opn = cp + 3 * L.sz.cap_words, *fr = opn + L.sz.openings_words;
+            if (rc == 0) rc = vpbs_prove_step(a->ctx, &in, cp, opn, fr, nullptr, nullptr);
+            a->last.prove_ms += 1e3 * (now() - t0);
+            if (ahead.joinable()) ahead.join();
+            if (rc != 0) {
+                a->last.seconds = now() - t_start;
+                return fail(rc, at + "proof: " + vpbs_last_error(a->ctx));
+            }
+            ++a->last.nodes;
+        }
+        cur.swap(next);
+        ids.swap(next_ids);
+    }
+    // ---- the root node's proof, serialised ----
+    const Level& L = a->levels[d - 1];
+    const Proof& p = cur[0];
+    L.step_inputs(in, a->d_wires, p.pis.data());
+    const u64 *cp = p.flat.data(), *opn = cp + 3 * L.sz.cap_words, *fr = opn + L.sz.openings_words;
+    const long n = vpbs_step_proof_to_bytes(a->ctx, &in, L.n_const_cols, cp, opn, fr, out, capacity);
+    a->last.seconds = now() - t_start;
+    if (n <= 0) return fail(VPBS_ERR_INVALID, "the output buffer is too small for the aggregate proof");
+    if (stats) *stats = a->last;
+    return n;
+}
+
+int vpbs_aggregate_verifier_create(vpbs_ctx* ctx, const vpbs_aggregate_shape* shape, size_t max_leaves, vpbs_aggregate_verifier** out, char* err,
+                                   size_t err_len) {
+    if (out) *out = nullptr;
+    report(err, err_len, "");
+    auto refuse = [&](const char* m) {
+        report(err, err_len, std::string("vpbs_aggregate_verifier_create: ") + m);
+        return VPBS_ERR_INVALID;
+    };
+    if (!ctx || !out || !shape_ok(shape)) return refuse("null or malformed arguments");
+    if (shape->N == 0 || shape->K == 0 || (size_t)shape->K * shape->N > (1u << 20) || shape->n_lwe > (1u << 24)) return refuse("N, K or n_lwe out of range");
+    if (max_leaves == 0 || max_leaves > (1u << 20)) return refuse("max_leaves must be 1 .. 2^20");
+    for (unsigned l = 1; l <= shape->levels; ++l)
+        if (shape->level_shapes[l - 1].cap_height != 4) return refuse("the level circuits have cap_height 4");
+    auto* v = new vpbs_aggregate_verifier;
+    v->N = shape->N; v->K = shape->K; v->n_lwe = shape->n_lwe;
+    v->max_leaves = max_leaves;
+    // only the levels max_leaves can reach get a batch verifier
+    v->levels = std::min(shape->levels, depth_of(max_leaves));
+    for (unsigned l = 1; l <= v->levels; ++l) {
+        const vpbs_verify_inputs c = level_inputs(*shape, l);
+        vpbs_proof_verifier* p = nullptr;
+        const int rc = vpbs_proof_verifier_create(ctx, &c, 1, 4 + VK * l, &p, err, err_len);
+        if (rc) {
+            delete v;
+            return rc;
+        }
+        v->proofs.push_back(p);
+    }
+    v->ctx = ctx;
+    try {
+        VPBS_HIP(hipSetDevice(ctx->device));
+        const size_t pad = (size_t)1 << depth_of(max_leaves);
+        v->d_vks = static_cast<u64*>(v->alloc(8 * VK * (v->levels + 1)));
+        v->d_in = static_cast<u64*>(v->alloc(8 * v->in_words()));
+        v->d_lwe = static_cast<u64*>(v->alloc(32 * max_leaves));
+        v->d_stmt = static_cast<u64*>(v->alloc(32 * max_leaves));
+        for (auto& n : v->d_nodes) n = static_cast<u64*>(v->alloc(32 * std::max<size_t>(1, pad / 2)));
+        v->d_flag = static_cast<u32*>(v->alloc(4));
+        v->d_out = static_cast<uint8_t*>(v->alloc(8));
+        VPBS_HIP(hipHostMalloc((void**)&v->h_in, 8 * v->in_words(), hipHostMallocDefault));
+        VPBS_HIP(hipHostMalloc((void**)&v->h_out, 64, hipHostMallocDefault));
+        VPBS_HIP(hipMemcpyAsync(v->d_vks, shape->vks, 8 * VK * (v->levels + 1), hipMemcpyHostToDevice, ctx->stream));
+        VPBS_HIP(vpbs::stream_sync(ctx->stream));
+    } catch (const DeviceError& e) {
+        report(err, err_len, e.what);
+        ctx->err = e.what;
+        delete v;
+        return e.status;
+    }
+    *out = v;
+    return VPBS_OK;
+}
+
+int vpbs_aggregate_verifier_root(vpbs_aggregate_verifier* v, size_t count, const uint64_t* testvs, size_t n_testv, const uint32_t* testv_of,
+                                 const uint64_t* cts, const uint64_t* out_cts, const uint64_t* key_hashes, size_t n_keys, const uint32_t* key_of,
+                                 int on_device, uint64_t out[4], char* err, size_t err_len) {
+    report(err, err_len, "");
+    if (!v || !out) return report(err, err_len, "vpbs_aggregate_verifier_root: null argument"), VPBS_ERR_INVALID;
+    std::lock_guard<std::mutex> lock(v->mu);
+    u64 vk0_unused = 0;   // the host checks need a non-null vk0; the device holds the real one
+    const Statement s{v->N, v->K, v->n_lwe, &vk0_unused, count, testvs, n_testv, testv_of, cts, out_cts, key_hashes, n_keys, key_of};
+    std::string msg;
+    if (!verifier_args_ok(v, s, "vpbs_aggregate_verifier_root", &msg)) return report(err, err_len, msg), VPBS_ERR_INVALID;
+    try {
+        VPBS_HIP(hipSetDevice(v->ctx->device));
+        const u64* d_root = nullptr;
+        statement_enqueue(v, s, on_device, &d_root);
+        VPBS_HIP(hipMemcpyAsync(v->h_out, d_root, 32, hipMemcpyDeviceToHost, v->ctx->stream));
+        VPBS_HIP(hipMemcpyAsync(v->h_out + 4, v->d_flag, 4, hipMemcpyDeviceToHost, v->ctx->stream));
+        VPBS_HIP(vpbs::stream_sync(v->ctx->stream));
+    } catch (const DeviceError& e) {
+        v->ctx->err = e.what;
+        return report(err, err_len, "vpbs_aggregate_verifier_root: " + e.what), e.status;
+    }
+    if ((u32)v->h_out[4] != 0) return 1;
+    std::memcpy(out, v->h_out, 32);
+    return VPBS_OK;
+}
+
+int vpbs_aggregate_verifier_run(vpbs_aggregate_verifier* v, const uint8_t* bytes, size_t len, size_t count, const uint64_t* testvs, size_t n_testv,
+                                const uint32_t* testv_of, const uint64_t* cts, const uint64_t* out_cts, const uint64_t* key_hashes, size_t n_keys,
+                                const uint32_t* key_of, int on_device, int* reason, char* err, size_t err_len) {
+    report(err, err_len, "");
+    if (reason) *reason = VPBS_AGG_MALFORMED;
+    if (!v || !bytes) return report(err, err_len, "vpbs_aggregate_verifier_run: null argument"), VPBS_ERR_INVALID;
+    std::lock_guard<std::mutex> lock(v->mu);
+    u64 vk0_unused = 0;
+    const Statement s{v->N, v->K, v->n_lwe, &vk0_unused, count, testvs, n_testv, testv_of, cts, out_cts, key_hashes, n_keys, key_of};
+    std::string msg;
+    if (!verifier_args_ok(v, s, "vpbs_aggregate_verifier_run", &msg)) return report(err, err_len, msg), VPBS_ERR_INVALID;
+    const unsigned d = depth_of(count);
+    try {
+        VPBS_HIP(hipSetDevice(v->ctx->device));
+        hipStream_t st = v->ctx->stream;
+        const u64* d_root = nullptr;
+        statement_enqueue(v, s, on_device, &d_root);
+        const size_t offsets[2] = {0, len};
+        vpbs::ProofBatchView pv{};
+        const int rc = vpbs::proof_verifier_enqueue(v->proofs[d - 1], bytes, offsets, 1, &pv);
+        if (rc) {
+            (void)vpbs::stream_sync(st);
+            return report(err, err_len, "vpbs_aggregate_verifier_run: the batch verifier refused the bytes"), rc;
+        }
+        const u32 n_expected = (u32)(4 + VK * d);
+        VPBS_REQUIRE(pv.max_pi >= n_expected, "the batch verifier's slot is smaller than the aggregate's public inputs");
+        ag_result<<<1, 64, 0, st>>>(pv.reasons, pv.n_pi, pv.words + pv.n_fixed, v->d_vks, d_root, v->d_flag, n_expected, v->d_out);
+        VPBS_HIP(hipGetLastError());
+        VPBS_HIP(hipMemcpyAsync(v->h_out, v->d_out, 2, hipMemcpyDeviceToHost, st));
+        VPBS_HIP(vpbs::stream_sync(st));
+    } catch (const DeviceError& e) {
+        v->ctx->err = e.what;
+        return report(err, err_len, "vpbs_aggregate_verifier_run: " + e.what), e.status;
+    }
+    const uint8_t* o = reinterpret_cast<const uint8_t*>(v->h_out);
+    if (reason) *reason = o[1];
+    return o[0];
+}
+
+void vpbs_aggregate_verifier_free(vpbs_aggregate_verifier* v) { delete v; }
+
+}  // extern "C"

@@ -107,6 +107,10 @@ long pbs_verify_collect(PbsVerifyCore* c, size_t count, uint8_t* verdicts, uint8
 // after a DeviceError of either: the message into the context, the chain stream drained
 void pbs_verify_abandon(PbsVerifyCore* c, const DeviceError& e);
 
+// vp_lwe_chain alone, queued on `stream` (a hipStream_t), for the aggregate verifier (aggregate.hip): the ends [count][4] of the LWE hash
+// chains of d_ct [count][n_lwe + 1], one 16-lane group per ciphertext.  Throws vpbs::DeviceError for a failed launch.
+void lwe_chain_enqueue(void* stream, const uint64_t* d_ct, unsigned n_lwe, size_t count, uint64_t* d_out);
+
 // ---- the ring verifier (verify_pbs_batch.hip) ----
 struct RingVerifierShape {
     vpbs_ctx* ctx;
