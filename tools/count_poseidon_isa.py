@@ -2,7 +2,13 @@
 """Dynamic VALU-instruction count of the product Poseidon permutation on gfx950 (the number quoted in DESIGN.md / bench.py).
 
 Compiles a one-permutation-per-lane kernel to ISA, counts VALU instructions per loop body and multiplies by the trip
-counts (4 + 4 full rounds, 7 fused partial groups, 1 plain partial round).  Needs hipcc only (no GPU).
+counts (4 + 3 full rounds in loops, 6 fused partial groups of three; the closing group of four, the last round's S-boxes and
+the last MDS layer stand outside the loops).  Needs hipcc only (no GPU).
+
+Two forms are counted: the whole permutation (poseidon::permute, all twelve rows of the last MDS layer) and the HASHING
+permutation, the one a sponge runs between two full blocks (the path poseidon::permute_sponge takes there: the head and
+rows 8..11 of the last layer only; practically every permutation of a step proof) -- the same harness, so the
+difference is the eight skipped rows.
 
 Besides the plain sum (what bench.py's constant and the SQ_INSTS_VALU counter mean) the count is split by issue rate, as measured by
 tools/microbench_valu2.hip (profiles/r07_microbench_valu2.txt, one SIMD with 4 waves): FULL-rate instructions take ~2.5 cycles per wave64
@@ -25,11 +31,16 @@ __global__ void __launch_bounds__(256) permute_batch_kernel(u64* states, size_t 
     u64 s[12];
 #pragma unroll
     for (int k = 0; k < 12; ++k) s[k] = states[12 * i + k];
-    poseidon::permute(s);
+    PERMUTE;
 #pragma unroll
     for (int k = 0; k < 12; ++k) states[12 * i + k] = s[k];
 }
 '''
+# (the hashing form canonicalises and stores its eight unwritten words too: the harness is for counting, and equal but for the rows)
+FORMS = (("whole permutation", "poseidon::permute(s)"),
+         ("hashing permutation", "poseidon::permute_head(s); poseidon::last_rows<8, 4>(s, poseidon::head_halves(s)); "
+                                 "for (int k = 0; k < 12; ++k) s[k] = gl::canon(s[k])"))
+TRIPS = (4, 6, 3)
 
 
 FULL_RATE = re.compile(r"^\s+v_(mov_b32|add_u32|sub_u32|subrev_u32|xor_b32|and_b32|or_b32|not_b32|lshlrev_b32|lshrrev_b32|ashrrev_i32)(_e32)?\s")
@@ -42,10 +53,10 @@ def count(seg):
     return len(valu), sum(1 for x in valu if FULL_RATE.match(x))
 
 
-def main():
+def measure(name, call):
     with tempfile.TemporaryDirectory() as d:
         src, out = os.path.join(d, "t.hip"), os.path.join(d, "t.s")
-        open(src, "w").write(SRC)
+        open(src, "w").write(SRC.replace("PERMUTE", call))
         subprocess.check_call(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-I", CSRC, "-S", "--cuda-device-only", src, "-o", out],
                               stderr=subprocess.DEVNULL)
         # -S does not ASSEMBLE inline asm: an operand the assembler rejects (gfx950: VGPR pairs must be 64-bit aligned) only shows with -c
@@ -82,14 +93,26 @@ def main():
     total_static, total_full = count(body)
     print("static VALU instructions:", total_static, " loop bodies:", [n for n, _ in loops])
     if len(loops) == 3:
-        (full_a, fa), (group, fg), (full_b, fb) = loops
-        rest = total_static - full_a - group - full_b   # first constant layer, the plain partial round, canonicalisation, load/store
-        dyn = 4 * full_a + 7 * group + 4 * full_b + rest
-        print("dynamic VALU instructions per permutation ~ %d  (4 x %d + 7 x %d + 4 x %d + %d)" % (dyn, full_a, group, full_b, rest))
-        full = 4 * fa + 7 * fg + 4 * fb + (total_full - fa - fg - fb)
+        in_loops = sum(n for n, _ in loops)
+        rest = total_static - in_loops   # first constant layer, the plain partial round, the last round, canonicalisation, load/store
+        dyn = sum(k * n for k, (n, _) in zip(TRIPS, loops)) + rest
+        prefix = "" if name == "whole permutation" else name + ": "
+        print("%sdynamic VALU instructions per permutation ~ %d  (%s + %d)" % (prefix, dyn, " + ".join("%d x %d" % (k, n) for k, (n, _) in zip(TRIPS, loops)), rest))
+        full = sum(k * f for k, (_, f) in zip(TRIPS, loops)) + (total_full - sum(f for _, f in loops))
         half = dyn - full
-        print("by issue rate: %d half-rate + %d full-rate;  cycle-weighted ~ %d SIMD cycles per wave64 permutation (%.1f / %.1f cycles)"
-              % (half, full, round(half * HALF_CYCLES + full * FULL_CYCLES), HALF_CYCLES, FULL_CYCLES))
+        print("%sby issue rate: %d half-rate + %d full-rate;  cycle-weighted ~ %d SIMD cycles per wave64 permutation (%.1f / %.1f cycles)"
+              % (prefix, half, full, round(half * HALF_CYCLES + full * FULL_CYCLES), HALF_CYCLES, FULL_CYCLES))
+        return dyn
+    return None
+
+
+def main():
+    counts = {}
+    for name, call in FORMS:
+        print("--", name, "--")
+        counts[name] = measure(name, call)
+    if all(counts.values()):
+        print("the hashing permutation runs %d VALU instructions fewer than the whole one" % (counts["whole permutation"] - counts["hashing permutation"]))
 
 
 if __name__ == "__main__":

@@ -3,7 +3,8 @@
 // H::two_to_one), hash/hashing.rs `hash_n_to_m_no_pad` (overwrite-mode sponge, rate 8) and fri/prover.rs
 // `fri_proof_of_work`, reached from prove() at /root/reference/src/vtfhe/ivc_based_vpbs.rs:302,333,364
 // (SURVEY.md 8a rows a5/a6/a11).  One lane = one leaf / node / nonce: the column-major, leaf-ordered LDE makes every
-// absorb a fully coalesced 512-B wave read.  Integer-VALU bound (~12.7k instructions per permutation); no MFMA.
+// absorb a fully coalesced 512-B wave read.  Integer-VALU bound (~12.2k instructions per permutation: a
+// sponge computes only the rows of the last MDS layer that it reads, poseidon::permute_sponge); no MFMA.
 #include <cstdlib>
 
 #include <algorithm>
@@ -42,17 +43,22 @@ leaf_hash_kernel(const u64* __restrict__ lde, unsigned ncols, size_t n_leaves, s
         // wave ever waits on HBM in front of a permutation
         u64 nxt[8];
 #pragma unroll
-        for (int k = 0; k < 8; ++k) nxt[k] = (unsigned)k < ncols ? lde[(size_t)k * col_stride + j] : 0;
-        for (unsigned c0 = 0; c0 < ncols; c0 += 8) {
-#pragma unroll
-            for (int k = 0; k < 8; ++k)
-                if (c0 + k < ncols) s[k] = nxt[k];
+        for (int k = 0; k < 8; ++k)
+            if ((unsigned)k < ncols) s[k] = lde[(size_t)k * col_stride + j];
+        for (unsigned c0 = 0;; c0 += 8) {
             if (c0 + 8 < ncols) {
 #pragma unroll
                 for (int k = 0; k < 8; ++k)
                     if (c0 + 8 + k < ncols) nxt[k] = lde[(size_t)(c0 + 8 + k) * col_stride + j];
             }
-            poseidon::permute_residues(s);   // the capacity goes on as residues; only the digest is made canonical
+            // the capacity goes on as residues; only the digest is made canonical.  Of the last MDS layer only the rows that are read: the
+            // digest's after the last block, the capacity's where a whole block overwrites the rest (poseidon::permute_sponge)
+            const bool more = poseidon::permute_sponge(s, ncols - c0, [&](unsigned n) {
+#pragma unroll
+                for (int k = 0; k < 8; ++k)
+                    if ((unsigned)k < n) s[k] = nxt[k];
+            });
+            if (!more) break;
         }
 #pragma unroll
         for (int k = 0; k < 4; ++k) s[k] = gl::canon(s[k]);
@@ -77,14 +83,21 @@ fri_leaf_hash_kernel(const u64* __restrict__ v0, const u64* __restrict__ v1, siz
 #pragma unroll
     for (int i = 0; i < 12; ++i) s[i] = 0;
     if (2 * arity <= 4) {
-        for (unsigned m = 0; m < arity; ++m) { s[2 * m] = v0[base + m]; s[2 * m + 1] = v1[base + m]; }
+#pragma unroll
+        for (int m = 0; m < 2; ++m)
+            if ((unsigned)m < arity) { s[2 * m] = v0[base + m]; s[2 * m + 1] = v1[base + m]; }
     } else {
         // leaf = [v_0.c0, v_0.c1, v_1.c0, ...]; one absorb block = 4 extension values
-        for (unsigned m0 = 0; m0 < arity; m0 += 4) {
 #pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (m0 + k < arity) { s[2 * k] = v0[base + m0 + k]; s[2 * k + 1] = v1[base + m0 + k]; }
-            poseidon::permute_residues(s);
+        for (int k = 0; k < 4; ++k)
+            if ((unsigned)k < arity) { s[2 * k] = v0[base + k]; s[2 * k + 1] = v1[base + k]; }
+        for (unsigned m0 = 0;; m0 += 4) {
+            const bool more = poseidon::permute_sponge(s, 2 * (arity - m0), [&](unsigned n) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (2 * (unsigned)k < n) { s[2 * k] = v0[base + m0 + 4 + k]; s[2 * k + 1] = v1[base + m0 + 4 + k]; }
+            });
+            if (!more) break;
         }
 #pragma unroll
         for (int k = 0; k < 4; ++k) s[k] = gl::canon(s[k]);
@@ -101,9 +114,9 @@ merkle_level_kernel(const u64* __restrict__ children, u64* __restrict__ parents,
     const ulonglong2* c = reinterpret_cast<const ulonglong2*>(children + 8 * i);
     const ulonglong2 a = c[0], b = c[1], e = c[2], f = c[3];
     u64 s[12] = {a.x, a.y, b.x, b.y, e.x, e.y, f.x, f.y, 0, 0, 0, 0};
-    poseidon::permute_residues(s);
+    poseidon::permute_digest(s);   // the digest's four rows of the last layer; the other eight words are never computed
 #pragma unroll
-    for (int k = 0; k < 4; ++k) s[k] = gl::canon(s[k]);   // the digest; the other eight words are dropped
+    for (int k = 0; k < 4; ++k) s[k] = gl::canon(s[k]);
     ulonglong2* d = reinterpret_cast<ulonglong2*>(parents + 4 * i);
     d[0] = make_ulonglong2(s[0], s[1]);
     d[1] = make_ulonglong2(s[2], s[3]);
@@ -196,11 +209,16 @@ hash_rows_kernel(const u64* __restrict__ rows, size_t n, unsigned len, u64* __re
     u64 s[12];
 #pragma unroll
     for (int k = 0; k < 12; ++k) s[k] = 0;
-    for (unsigned c0 = 0; c0 < len; c0 += 8) {
 #pragma unroll
-        for (int k = 0; k < 8; ++k)
-            if (c0 + k < len) s[k] = row[c0 + k];
-        poseidon::permute_residues(s);
+    for (int k = 0; k < 8; ++k)
+        if ((unsigned)k < len) s[k] = row[k];
+    for (unsigned c0 = 0;; c0 += 8) {
+        const bool more = poseidon::permute_sponge(s, len - c0, [&](unsigned n) {
+#pragma unroll
+            for (int k = 0; k < 8; ++k)
+                if ((unsigned)k < n) s[k] = row[c0 + 8 + k];
+        });
+        if (!more) break;
     }
 #pragma unroll
     for (int k = 0; k < 4; ++k) out[4 * i + k] = gl::canon(s[k]);
