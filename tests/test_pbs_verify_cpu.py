@@ -24,6 +24,19 @@ def test_key_hash_is_the_hash_chain_over_zero_bsk_ksk():
         api.pbs_key_hash(np.zeros((1, 0), np.uint64), np.zeros(0, np.uint64))
 
 
+@pytest.mark.parametrize("n_lwe", [0, 1, 6])
+@pytest.mark.parametrize("ggsw_len", [64, 65])
+def test_key_hash_is_the_last_link_of_the_public_walker(n_lwe, ggsw_len):
+    """the key-links function the batch provers and vpbs_pbs_key_hash share (vpbs::key_hash_links) against vpbs_hash_chain_links over the
+    same items from a zero prefix, at item lengths on both sides of a sponge block (64 = 8 blocks of rate 8, 65 = one element more)"""
+    rng = np.random.default_rng(1000 * n_lwe + ggsw_len)
+    bsk = rng.integers(0, P, size=(n_lwe, ggsw_len), dtype=np.uint64)
+    ksk = rng.integers(0, P, size=ggsw_len, dtype=np.uint64)
+    links = api.hash_chain_links(np.zeros(4, np.uint64), np.vstack([np.zeros((1, ggsw_len), np.uint64), bsk, ksk.reshape(1, ggsw_len)]))
+    assert links.shape == (n_lwe + 2, 4)
+    assert api.pbs_key_hash(bsk, ksk).tolist() == links[-1].tolist()
+
+
 def test_reason_codes_and_texts():
     assert [api.PBS_OK, api.PBS_MALFORMED, api.PBS_TESTV_MASK, api.PBS_TESTV, api.PBS_COUNTER, api.PBS_OUT_CT, api.PBS_PROOF,
             api.PBS_VERIFIER_DATA, api.PBS_KEY_HASH, api.PBS_LWE_HASH] == list(range(10))

@@ -1053,6 +1053,19 @@ class ProofVerifier:
             pass
 
 
+def _ivc_circuit(d, proof_words, keep):
+    """IvcCircuitC of a circuit_file.CircuitDescription; `keep` takes what its pointers refer to and must outlive the call that reads it"""
+    c = IvcCircuitC()
+    pre = np.ascontiguousarray(d.preset_flat, dtype=np.uint32)
+    pi = np.ascontiguousarray(d.pi_flat, dtype=np.uint32)
+    keep.extend([pre, pi, d])
+    c.circuit = C.pointer(d.circuit.c)
+    c.preset_pos, c.n_preset = pre.ctypes.data_as(U32P), pre.size
+    c.pi_pos, c.n_pi = pi.ctypes.data_as(U32P), pi.size
+    c.proof_words = proof_words
+    return c
+
+
 class Ivc:
     """vpbs_ivc: one verifiable PBS as one call -- the IVC chain of verified_pbs (ivc_based_vpbs.rs:159-386) driven inside the library.
     cyclic / dummy: circuit_file.CircuitDescription of the exported cyclic step circuit and its dummy circuit."""
@@ -1060,18 +1073,7 @@ class Ivc:
     def __init__(self, ctx, cyclic, dummy, N, K, ggsw_len, comm=None):
         """comm: a CommC (sharding.make_comm / make_comm_rccl) -> every step proof coset-sharded over the ranks; every rank builds its own Ivc"""
         self.ctx, self._keep = ctx, [comm]
-
-        def side(d, proof_words):
-            c = IvcCircuitC()
-            pre = np.ascontiguousarray(d.preset_flat, dtype=np.uint32)
-            pi = np.ascontiguousarray(d.pi_flat, dtype=np.uint32)
-            self._keep += [pre, pi, d]
-            c.circuit = C.pointer(d.circuit.c)
-            c.preset_pos, c.n_preset = pre.ctypes.data_as(U32P), pre.size
-            c.pi_pos, c.n_pi = pi.ctypes.data_as(U32P), pi.size
-            c.proof_words = proof_words
-            return c
-        cy, du = side(cyclic, cyclic.meta["proof_words"]), side(dummy, 0)
+        cy, du = _ivc_circuit(cyclic, cyclic.meta["proof_words"], self._keep), _ivc_circuit(dummy, 0, self._keep)
         self.h, err = C.c_void_p(), C.create_string_buffer(512)
         if lib().vpbs_ivc_create(ctx.h, C.byref(cy), C.byref(du), N, K, ggsw_len, C.byref(comm) if comm is not None else None, C.byref(self.h),
                                  err, 512):
@@ -1965,12 +1967,145 @@ class PbsProveError(VpbsError):
         self.failures, self.proofs, self.out_ct, self.lwe_out = failures, proofs, out_ct, lwe_out
 
 
-class PbsProver:
+class _BatchProver:
+    """What PbsProver and RingProver share: the handle of a C object whose entry points are named <_prefix>_*, with the chains' settings,
+    the checkpoint callback, the run behind prove and resume, and the statistics of the last run."""
+    _prefix = None
+
+    def _entry(self, name):
+        return getattr(lib(), "%s_%s" % (self._prefix, name))
+
+    def _fail(self, what, rc, err):
+        e = VpbsError("%s: status %d: %s" % (what, rc, err.value.decode()))
+        e.status = rc
+        return e
+
+    def _create(self, cyclic, dummy, N, K, ELL, LOGB, create):
+        """create(cyclic, dummy, prm, handle, err): the call of the C constructor with these five filled in -> its status"""
+        keep = []
+        cy, du = _ivc_circuit(cyclic, cyclic.meta["proof_words"], keep), _ivc_circuit(dummy, 0, keep)
+        prm = TfheParamsC(N.bit_length() - 1, K, ELL, LOGB)
+        self.h, err = C.c_void_p(), C.create_string_buffer(512)
+        rc = create(C.byref(cy), C.byref(du), C.byref(prm), C.byref(self.h), err)
+        if rc:
+            self.h = None
+            raise self._fail(self._prefix + "_create", rc, err)
+        self.vk_words = 4 + (4 << 4)
+        self._proof_words = cyclic.meta["proof_words"]
+        self._ckpt_cb = self._ckpt_error = None
+
+    def verifier_data(self):
+        """-> (cyclic circuit: digest [4] + cap, dummy circuit: the same)"""
+        a, b = np.zeros(self.vk_words, np.uint64), np.zeros(self.vk_words, np.uint64)
+        self._entry("verifier_data")(self.h, _ptr(a), _ptr(b))
+        return a, b
+
+    def set_check_witness(self, on=True):
+        """every witness of later chains checked on the device before it is proven (Ivc.set_check_witness on every chain); resets the counters"""
+        rc = self._entry("set_check_witness")(self.h, 1 if on else 0)
+        if rc != 0:
+            raise VpbsError("%s_set_check_witness: status %d" % (self._prefix, rc))
+
+    def witness_checks(self):
+        """-> (witnesses checked, violations found), summed over the chains, since the last set_check_witness"""
+        out = np.zeros(2, np.uint64)
+        self._entry("witness_checks")(self.h, _ptr(out))
+        return int(out[0]), int(out[1])
+
+    def on_checkpoint(self, every, fn):
+        """fn(index, done, bytes) after every chained step `done` of ciphertext `index` that is a multiple of `every` and below the chain's
+        last step (Ivc.on_checkpoint with the ciphertext index); never two calls at once.  every = 0 or fn = None turns it off.  An
+        exception raised by fn is kept and re-raised by prove.  A chain resumed at step k (resume) counts its `every` from k -- after
+        steps k + every, k + 2 every, .. -- and `done` stays the number of chain steps."""
+        self._ckpt_error = None
+        if fn is None or not every:
+            self._ckpt_cb = None
+            self._entry("set_checkpoint")(self.h, 0, C.cast(None, PBS_CHECKPOINT_FN), None)
+            return
+
+        def trampoline(_user, index, done, data, n):
+            try:
+                if self._ckpt_error is None:
+                    fn(int(index), int(done), C.string_at(data, n))
+            except BaseException as e:   # noqa: BLE001 -- must not unwind through the C frames
+                self._ckpt_error = e
+        self._ckpt_cb = PBS_CHECKPOINT_FN(trampoline)
+        self._entry("set_checkpoint")(self.h, every, self._ckpt_cb, None)
+
+    def _run(self, c, tv, cps, steps, on_proof, key_of=None, out_ct=None, lwe_out=None):
+        """<_prefix>_run, or _resume with the checkpoints cps; key_of: the ring prover's slots -> (proofs, out_ct, lwe_out, errors)"""
+        count = c.shape[0]
+        out_ct = np.zeros((count, self.K, self.N), np.uint64) if out_ct is None else out_ct
+        lwe_out = np.zeros((count, self.n_lwe + 1), np.uint64) if lwe_out is None else lwe_out
+        if out_ct.shape != (count, self.K, self.N) or lwe_out.shape != (count, self.n_lwe + 1):
+            raise ValueError("%s.prove: expected out_ct [count][K][N] and lwe_out [count][n + 1]" % type(self).__name__)
+        proofs, failures, raised, errors = [None] * count, [], [], [None] * count
+
+        def trampoline(_user, index, data, n, error):
+            try:
+                if not data:
+                    text = (error or b"").decode()
+                    if cps is not None and text.startswith("checkpoint: "):
+                        errors[index] = text   # a refused checkpoint: reported, not raised
+                    else:
+                        failures.append((int(index), text))
+                    return
+                proofs[index] = C.string_at(data, n)
+                if on_proof is not None and not raised:
+                    on_proof(int(index), proofs[index])
+            except BaseException as e:   # noqa: BLE001 -- must not unwind through the C frames
+                raised.append(e)
+        cb, err = PBS_PROOF_FN(trampoline), C.create_string_buffer(512)
+        keep = np.zeros(1, np.uint64)   # a valid pointer for an empty batch
+        p = lambda a: _ptr(a if a.size else keep)
+        args = [self.h, p(c), count] + ([] if key_of is None else [(key_of if key_of.size else np.zeros(1, np.uint32)).ctypes.data])
+        args += [p(tv), 1 if tv.ndim == 2 else 0]
+        what = self._prefix + "_run"
+        if cps is not None:
+            what = self._prefix + "_resume"
+            ptrs, lens, alive = _checkpoint_arrays(cps)
+            args += [C.addressof(ptrs), C.addressof(lens)]
+        n = getattr(lib(), what)(*args, steps, p(out_ct), p(lwe_out), cb, None, err, 512)
+        if raised:
+            raise raised[0]
+        e, self._ckpt_error = self._ckpt_error, None
+        if e is not None:
+            raise e
+        if n < 0:
+            raise self._fail(what, n, err)
+        if failures:
+            raise PbsProveError(dict(failures), proofs, out_ct, lwe_out)
+        return proofs, out_ct, lwe_out, errors
+
+    def last_run(self):
+        """<_prefix>_last_run -> dict: seconds, outputs_seconds (call until out_ct / lwe_out were complete), proofs, prepare_chain_ms
+        (per chain: waiting for its public inputs) and chain = the mean vpbs_ivc_timing of the delivered chains"""
+        st = PbsRunStatsC()
+        self._entry("last_run")(self.h, C.byref(st))
+        return {"seconds": st.seconds, "outputs_seconds": st.outputs_seconds, "proofs": st.proofs, "prepare_chain_ms": st.prepare_chain_ms,
+                "chain": {f: getattr(st.chain, f) for f, _ in IvcTimingC._fields_}}
+
+    def close(self):
+        if self.h:
+            self._entry("free")(self.h)
+            self.h = None
+
+    free = close
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class PbsProver(_BatchProver):
     """vpbs_pbs_prover: the bootstraps of a batch of LWE ciphertexts AND their vPBS proofs under one key set that stays on the device.
     cyclic / dummy: circuit_file.CircuitDescription of the exported cyclic step circuit and its dummy circuit.  bsk [n][K*ELL*K*N], ksk
     [K*ELL*K*N] (keygen's layout): host arrays, or device pointers (integers) with keys_on_device=True and n_lwe given -- they must stay
     allocated while the object lives.  `chains` IVC chains run side by side, each in the device-witness pipeline with `witness_batch` steps
     per batch."""
+    _prefix = "vpbs_pbs_prover"
 
     def __init__(self, device, cyclic, dummy, bsk, ksk, K, ELL, LOGB, chains=8, witness_batch=64, keys_on_device=False, N=None, n_lwe=None):
         ggsw_words = lambda N: K * ELL * K * N
@@ -1985,73 +2120,14 @@ class PbsProver:
                 raise ValueError("PbsProver: expected bsk [n][K*ELL*K*N] and ksk [K*ELL*K*N]")
             pb, pk = C.c_void_p(b.ctypes.data), C.c_void_p(k.ctypes.data)
         self.N, self.K, self.ELL, self.LOGB, self.n_lwe, self.chains = N, K, ELL, LOGB, n_lwe, chains
-        keep = []
-
-        def side(d, proof_words):
-            c = IvcCircuitC()
-            pre = np.ascontiguousarray(d.preset_flat, dtype=np.uint32)
-            pi = np.ascontiguousarray(d.pi_flat, dtype=np.uint32)
-            keep.extend([pre, pi, d])
-            c.circuit = C.pointer(d.circuit.c)
-            c.preset_pos, c.n_preset = pre.ctypes.data_as(U32P), pre.size
-            c.pi_pos, c.n_pi = pi.ctypes.data_as(U32P), pi.size
-            c.proof_words = proof_words
-            return c
-        cy, du = side(cyclic, cyclic.meta["proof_words"]), side(dummy, 0)
-        prm = TfheParamsC(N.bit_length() - 1, K, ELL, LOGB)
-        self.h, err = C.c_void_p(), C.create_string_buffer(512)
-        rc = lib().vpbs_pbs_prover_create(device, C.byref(cy), C.byref(du), C.byref(prm), n_lwe, pb, pk, 1 if keys_on_device else 0, chains,
-                                          witness_batch, C.byref(self.h), err, 512)
-        if rc:
-            self.h = None
-            raise VpbsError("vpbs_pbs_prover_create: status %d: %s" % (rc, err.value.decode()))
-        self.vk_words = 4 + (4 << 4)
-        self._proof_words = cyclic.meta["proof_words"]
-        self._ckpt_cb = self._ckpt_error = None
+        self._create(cyclic, dummy, N, K, ELL, LOGB, lambda cy, du, prm, h, err: lib().vpbs_pbs_prover_create(
+            device, cy, du, prm, n_lwe, pb, pk, 1 if keys_on_device else 0, chains, witness_batch, h, err, 512))
 
     def key_hash(self):
         """the end of the key hash chain walked at creation: what PbsVerifier takes (= pbs_key_hash(bsk, ksk))"""
         out = np.zeros(4, np.uint64)
         lib().vpbs_pbs_prover_key_hash(self.h, _ptr(out))
         return out
-
-    def verifier_data(self):
-        """-> (cyclic circuit: digest [4] + cap, dummy circuit: the same)"""
-        a, b = np.zeros(self.vk_words, np.uint64), np.zeros(self.vk_words, np.uint64)
-        lib().vpbs_pbs_prover_verifier_data(self.h, _ptr(a), _ptr(b))
-        return a, b
-
-    def set_check_witness(self, on=True):
-        """every witness of later chains checked on the device before it is proven (Ivc.set_check_witness on every chain); resets the counters"""
-        rc = lib().vpbs_pbs_prover_set_check_witness(self.h, 1 if on else 0)
-        if rc != 0:
-            raise VpbsError("vpbs_pbs_prover_set_check_witness: status %d" % rc)
-
-    def witness_checks(self):
-        """-> (witnesses checked, violations found), summed over the chains, since the last set_check_witness"""
-        out = np.zeros(2, np.uint64)
-        lib().vpbs_pbs_prover_witness_checks(self.h, _ptr(out))
-        return int(out[0]), int(out[1])
-
-    def on_checkpoint(self, every, fn):
-        """fn(index, done, bytes) after every chained step `done` of ciphertext `index` that is a multiple of `every` and below the chain's
-        last step (Ivc.on_checkpoint with the ciphertext index); never two calls at once.  every = 0 or fn = None turns it off.  An
-        exception raised by fn is kept and re-raised by prove.  A chain resumed at step k (resume) counts its `every` from k -- after
-        steps k + every, k + 2 every, .. -- and `done` stays the number of chain steps."""
-        self._ckpt_error = None
-        if fn is None or not every:
-            self._ckpt_cb = None
-            lib().vpbs_pbs_prover_set_checkpoint(self.h, 0, C.cast(None, PBS_CHECKPOINT_FN), None)
-            return
-
-        def trampoline(_user, index, done, data, n):
-            try:
-                if self._ckpt_error is None:
-                    fn(int(index), int(done), C.string_at(data, n))
-            except BaseException as e:   # noqa: BLE001 -- must not unwind through the C frames
-                self._ckpt_error = e
-        self._ckpt_cb = PBS_CHECKPOINT_FN(trampoline)
-        lib().vpbs_pbs_prover_set_checkpoint(self.h, every, self._ckpt_cb, None)
 
     def prove(self, cts, testv, steps=0, on_proof=None):
         """cts [count][n + 1]; testv [N] shared or [count][N] -> (proofs: list of bytes in the order of cts, out_ct [count][K][N], lwe_out
@@ -2074,56 +2150,6 @@ class PbsProver:
         c, tv, cps, _ = resume_args(self.N, self.n_lwe, cts, testv, checkpoints, steps)
         return self._run(c, tv, cps, steps, on_proof)
 
-    def _run(self, c, tv, cps, steps, on_proof):
-        count = c.shape[0]
-        out_ct, lwe_out = np.zeros((count, self.K, self.N), np.uint64), np.zeros((count, self.n_lwe + 1), np.uint64)
-        proofs, failures, raised, errors = [None] * count, [], [], [None] * count
-
-        def trampoline(_user, index, data, n, error):
-            try:
-                if not data:
-                    text = (error or b"").decode()
-                    if cps is not None and text.startswith("checkpoint: "):
-                        errors[index] = text   # a refused checkpoint: reported, not raised
-                    else:
-                        failures.append((int(index), text))
-                    return
-                proofs[index] = C.string_at(data, n)
-                if on_proof is not None and not raised:
-                    on_proof(int(index), proofs[index])
-            except BaseException as e:   # noqa: BLE001 -- must not unwind through the C frames
-                raised.append(e)
-        cb, err = PBS_PROOF_FN(trampoline), C.create_string_buffer(512)
-        keep = np.zeros(1, np.uint64)   # a valid pointer for an empty batch
-        p = lambda a: _ptr(a if a.size else keep)
-        if cps is None:
-            what = "vpbs_pbs_prover_run"
-            n = lib().vpbs_pbs_prover_run(self.h, p(c), count, p(tv), 1 if tv.ndim == 2 else 0, steps, p(out_ct), p(lwe_out), cb, None, err, 512)
-        else:
-            what = "vpbs_pbs_prover_resume"
-            ptrs, lens, alive = _checkpoint_arrays(cps)
-            n = lib().vpbs_pbs_prover_resume(self.h, p(c), count, p(tv), 1 if tv.ndim == 2 else 0, C.addressof(ptrs), C.addressof(lens), steps,
-                                             p(out_ct), p(lwe_out), cb, None, err, 512)
-            del alive
-        if raised:
-            raise raised[0]
-        e, self._ckpt_error = self._ckpt_error, None
-        if e is not None:
-            raise e
-        if n < 0:
-            raise VpbsError("%s: status %d: %s" % (what, n, err.value.decode()))
-        if failures:
-            raise PbsProveError(dict(failures), proofs, out_ct, lwe_out)
-        return proofs, out_ct, lwe_out, errors
-
-    def last_run(self):
-        """vpbs_pbs_prover_last_run -> dict: seconds, outputs_seconds (call until out_ct / lwe_out were complete), proofs, prepare_chain_ms
-        (per chain: waiting for its public inputs) and chain = the mean vpbs_ivc_timing of the delivered chains"""
-        st = PbsRunStatsC()
-        lib().vpbs_pbs_prover_last_run(self.h, C.byref(st))
-        return {"seconds": st.seconds, "outputs_seconds": st.outputs_seconds, "proofs": st.proofs, "prepare_chain_ms": st.prepare_chain_ms,
-                "chain": {f: getattr(st.chain, f) for f, _ in IvcTimingC._fields_}}
-
     def dummy_proof_for_tests(self):
         """vpbs_test_pbs_prover_dummy_proof: the dummy proof [proof_words] as the object's vpbs_ivc holds it on the host"""
         out = np.zeros(self._proof_words, np.uint64)
@@ -2140,19 +2166,6 @@ class PbsProver:
         if rc != 0:
             raise VpbsError("vpbs_test_pbs_prover_preset_matrix: status %d" % rc)
         return out
-
-    def close(self):
-        if self.h:
-            lib().vpbs_pbs_prover_free(self.h)
-            self.h = None
-
-    free = close
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def ring_prove_args(N, n_lwe, max_keys, cts, key_of, testv, steps=0):
@@ -2173,51 +2186,24 @@ class _RingContext:
         self.h, self._batches = h, set()
 
 
-class RingProver(PbsProver):
+class RingProver(_BatchProver):
     """vpbs_ring_prover: ONE prover for all clients of a key ring.  The object owns a KeyRing of max_keys slots, `chains` IVC chains in the
     device-witness pipeline and the key hash chain of every slot; prove() bootstraps and proves ciphertext i under the key set of slot
     key_of[i], and its proof is byte for byte what a PbsProver of that key set gives.  cyclic / dummy, chains, witness_batch: as PbsProver.
     .keyring is a KeyRing view of the owned ring (KeyRing.run and Program.run_batch evaluate on the same resident keys; it is not closed
     by the caller, and its add / remove are refused: key sets come and go through this object, which keeps their key links)."""
+    _prefix = "vpbs_ring_prover"
 
     def __init__(self, device, cyclic, dummy, K, ELL, LOGB, N, n_lwe, max_keys, chains=8, witness_batch=64):
         self.N, self.K, self.ELL, self.LOGB, self.n_lwe, self.chains, self.max_keys = N, K, ELL, LOGB, n_lwe, chains, max_keys
-        keep = []
-
-        def side(d, proof_words):
-            c = IvcCircuitC()
-            pre = np.ascontiguousarray(d.preset_flat, dtype=np.uint32)
-            pi = np.ascontiguousarray(d.pi_flat, dtype=np.uint32)
-            keep.extend([pre, pi, d])
-            c.circuit = C.pointer(d.circuit.c)
-            c.preset_pos, c.n_preset = pre.ctypes.data_as(U32P), pre.size
-            c.pi_pos, c.n_pi = pi.ctypes.data_as(U32P), pi.size
-            c.proof_words = proof_words
-            return c
-        cy, du = side(cyclic, cyclic.meta["proof_words"]), side(dummy, 0)
-        prm = TfheParamsC(N.bit_length() - 1, K, ELL, LOGB)
-        self.h, err = C.c_void_p(), C.create_string_buffer(512)
-        rc = lib().vpbs_ring_prover_create(device, C.byref(cy), C.byref(du), C.byref(prm), n_lwe, max_keys, chains, witness_batch,
-                                           C.byref(self.h), err, 512)
-        if rc:
-            self.h = None
-            e = VpbsError("vpbs_ring_prover_create: status %d: %s" % (rc, err.value.decode()))
-            e.status = rc
-            raise e
-        self.vk_words = 4 + (4 << 4)
-        self._proof_words = cyclic.meta["proof_words"]
-        self._ckpt_cb = self._ckpt_error = None
+        self._create(cyclic, dummy, N, K, ELL, LOGB, lambda cy, du, prm, h, err: lib().vpbs_ring_prover_create(
+            device, cy, du, prm, n_lwe, max_keys, chains, witness_batch, h, err, 512))
         ring = KeyRing.__new__(KeyRing)   # a view: the handle is the prover's, and goes with it
         ring.ctx = _RingContext(C.c_void_p(lib().vpbs_ring_prover_context(self.h)))
         ring.N, ring.K, ring.ELL, ring.LOGB, ring.n_lwe, ring.max_keys, ring.max_batch = N, K, ELL, LOGB, n_lwe, max_keys, 256
         ring.h = C.c_void_p(lib().vpbs_ring_prover_keyring(self.h))
         ring.close = ring.free = lambda: None
         self.keyring = ring
-
-    def _fail(self, what, rc, err):
-        e = VpbsError("%s: status %d: %s" % (what, rc, err.value.decode()))
-        e.status = rc
-        return e
 
     def add(self, bsk, ksk, keys_on_device=False):
         """KeyRing.add on the owned ring, and the key hash chain of the key set walked once, on the host.  Returns the slot."""
@@ -2251,115 +2237,25 @@ class RingProver(PbsProver):
             raise e
         return out
 
-    def verifier_data(self):
-        a, b = np.zeros(self.vk_words, np.uint64), np.zeros(self.vk_words, np.uint64)
-        lib().vpbs_ring_prover_verifier_data(self.h, _ptr(a), _ptr(b))
-        return a, b
-
-    def set_check_witness(self, on=True):
-        rc = lib().vpbs_ring_prover_set_check_witness(self.h, 1 if on else 0)
-        if rc != 0:
-            raise VpbsError("vpbs_ring_prover_set_check_witness: status %d" % rc)
-
-    def witness_checks(self):
-        out = np.zeros(2, np.uint64)
-        lib().vpbs_ring_prover_witness_checks(self.h, _ptr(out))
-        return int(out[0]), int(out[1])
-
-    def on_checkpoint(self, every, fn):
-        """as PbsProver.on_checkpoint"""
-        self._ckpt_error = None
-        if fn is None or not every:
-            self._ckpt_cb = None
-            lib().vpbs_ring_prover_set_checkpoint(self.h, 0, C.cast(None, PBS_CHECKPOINT_FN), None)
-            return
-
-        def trampoline(_user, index, done, data, n):
-            try:
-                if self._ckpt_error is None:
-                    fn(int(index), int(done), C.string_at(data, n))
-            except BaseException as e:   # noqa: BLE001 -- must not unwind through the C frames
-                self._ckpt_error = e
-        self._ckpt_cb = PBS_CHECKPOINT_FN(trampoline)
-        lib().vpbs_ring_prover_set_checkpoint(self.h, every, self._ckpt_cb, None)
-
     def prove(self, cts, key_of, testv, steps=0, on_proof=None, out_ct=None, lwe_out=None):
         """cts [count][n + 1]; key_of [count] slots; testv [N] shared or [count][N] -> (proofs: list of bytes in the order of cts, out_ct
         [count][K][N], lwe_out [count][n + 1]); on_proof, failures (PbsProveError) and `steps` as in PbsProver.prove.  A key_of entry that
         names an empty slot raises VpbsError (.status = VPBS_ERR_INVALID) with the ring's message before anything runs.  out_ct / lwe_out:
         arrays to write into instead of fresh ones."""
         c, ko, tv = ring_prove_args(self.N, self.n_lwe, self.max_keys, cts, key_of, testv, steps)
-        return self._run_ring(c, ko, tv, None, steps, on_proof, out_ct, lwe_out)[:3]
+        return self._run(c, tv, None, steps, on_proof, ko, out_ct, lwe_out)[:3]
 
     def resume(self, cts, key_of, testv, checkpoints, steps=0, on_proof=None, out_ct=None, lwe_out=None):
         """PbsProver.resume under the key set of slot key_of[i] (vpbs_ring_prover_resume) -> (proofs, out_ct, lwe_out, errors).  A
         checkpoint presented under another slot than the one it was made under is refused with "checkpoint: the key hash chain does not
         match"."""
         c, tv, cps, ko = resume_args(self.N, self.n_lwe, cts, testv, checkpoints, steps, key_of, self.max_keys)
-        return self._run_ring(c, ko, tv, cps, steps, on_proof, out_ct, lwe_out)
-
-    def _run_ring(self, c, ko, tv, cps, steps, on_proof, out_ct, lwe_out):
-        count = c.shape[0]
-        out_ct = np.zeros((count, self.K, self.N), np.uint64) if out_ct is None else out_ct
-        lwe_out = np.zeros((count, self.n_lwe + 1), np.uint64) if lwe_out is None else lwe_out
-        if out_ct.shape != (count, self.K, self.N) or lwe_out.shape != (count, self.n_lwe + 1):
-            raise ValueError("RingProver.prove: expected out_ct [count][K][N] and lwe_out [count][n + 1]")
-        proofs, failures, raised, errors = [None] * count, [], [], [None] * count
-
-        def trampoline(_user, index, data, n, error):
-            try:
-                if not data:
-                    text = (error or b"").decode()
-                    if cps is not None and text.startswith("checkpoint: "):
-                        errors[index] = text   # a refused checkpoint: reported, not raised
-                    else:
-                        failures.append((int(index), text))
-                    return
-                proofs[index] = C.string_at(data, n)
-                if on_proof is not None and not raised:
-                    on_proof(int(index), proofs[index])
-            except BaseException as e:   # noqa: BLE001 -- must not unwind through the C frames
-                raised.append(e)
-        cb, err = PBS_PROOF_FN(trampoline), C.create_string_buffer(512)
-        keep = np.zeros(1, np.uint64)   # a valid pointer for an empty batch
-        p = lambda a: _ptr(a if a.size else keep)
-        pko = (ko if ko.size else np.zeros(1, np.uint32)).ctypes.data
-        if cps is None:
-            what = "vpbs_ring_prover_run"
-            n = lib().vpbs_ring_prover_run(self.h, p(c), count, pko, p(tv), 1 if tv.ndim == 2 else 0, steps, p(out_ct), p(lwe_out), cb, None, err, 512)
-        else:
-            what = "vpbs_ring_prover_resume"
-            ptrs, lens, alive = _checkpoint_arrays(cps)
-            n = lib().vpbs_ring_prover_resume(self.h, p(c), count, pko, p(tv), 1 if tv.ndim == 2 else 0, C.addressof(ptrs), C.addressof(lens), steps,
-                                              p(out_ct), p(lwe_out), cb, None, err, 512)
-            del alive
-        if raised:
-            raise raised[0]
-        e, self._ckpt_error = self._ckpt_error, None
-        if e is not None:
-            raise e
-        if n < 0:
-            raise self._fail(what, n, err)
-        if failures:
-            raise PbsProveError(dict(failures), proofs, out_ct, lwe_out)
-        return proofs, out_ct, lwe_out, errors
-
-    def last_run(self):
-        st = PbsRunStatsC()
-        lib().vpbs_ring_prover_last_run(self.h, C.byref(st))
-        return {"seconds": st.seconds, "outputs_seconds": st.outputs_seconds, "proofs": st.proofs, "prepare_chain_ms": st.prepare_chain_ms,
-                "chain": {f: getattr(st.chain, f) for f, _ in IvcTimingC._fields_}}
-
-    def dummy_proof_for_tests(self):
-        raise NotImplementedError("a test entry of PbsProver")
-
-    preset_matrix = dummy_proof_for_tests
+        return self._run(c, tv, cps, steps, on_proof, ko, out_ct, lwe_out)
 
     def close(self):
         if self.h:
-            self.keyring.h = None
-            lib().vpbs_ring_prover_free(self.h)
-            self.h = None
+            self.keyring.h = None   # the view first: its handle goes with the prover's
+        super().close()
 
     free = close
 

@@ -387,6 +387,25 @@ void hash_links_shared(const u64 prefix[4], const u64* const* items, size_t n_li
 #endif
     sponge_scalar(job);
 }
+
+void key_hash_links(const u64* bsk, const u64* ksk, int keys_on_device, unsigned n_lwe, size_t ggsw_len, u64* links) {
+    std::vector<u64> host_keys;   // device keys: downloaded once, for this
+    if (keys_on_device) {
+        host_keys.resize(((size_t)n_lwe + 1) * ggsw_len);
+        if (n_lwe) VPBS_HIP(hipMemcpy(host_keys.data(), bsk, 8 * (size_t)n_lwe * ggsw_len, hipMemcpyDeviceToHost));
+        VPBS_HIP(hipMemcpy(host_keys.data() + (size_t)n_lwe * ggsw_len, ksk, 8 * ggsw_len, hipMemcpyDeviceToHost));
+        bsk = host_keys.data();
+        ksk = host_keys.data() + (size_t)n_lwe * ggsw_len;
+    }
+    const size_t total = (size_t)n_lwe + 2;
+    const std::vector<u64> zero(ggsw_len, 0);
+    std::vector<const u64*> items(total);
+    items[0] = zero.data();
+    for (unsigned x = 0; x < n_lwe; ++x) items[1 + x] = bsk + (size_t)x * ggsw_len;
+    items[total - 1] = ksk;
+    const u64 prefix[4] = {0, 0, 0, 0};
+    hash_links_shared(prefix, items.data(), total, ggsw_len, links);
+}
 }  // namespace vpbs
 
 extern "C" int vpbs_host_set_blocking_sync(int on) {

@@ -58,6 +58,11 @@ void stream_sync_forget(hipStream_t s);   // before hipStreamDestroy: the stream
 int sync_word_mode();                     // 1: waits read a word the device writes (default); 0: they go through the runtime
 // out[k] = hash_no_pad(h_{k-1} || items[k]), h_{-1} = prefix; concurrent callers with long items share the lanes of the eight-lane host Poseidon
 void hash_links_shared(const u64 prefix[4], const u64* const* items, size_t n_links, size_t item_len, u64* out);
+// The key hash chain of ONE key set, every link kept: links [n_lwe + 2][4] over the items [0^ggsw_len, bsk_0 .. bsk_{n-1}, ksk] from a zero
+// prefix, as vpbs_verify_pbs hashes them, without materialising the items (bsk [n_lwe][ggsw_len] may be null for n_lwe = 0).  The last link
+// is the key hash.  keys_on_device: bsk and ksk are device pointers and are downloaded once for this, with blocking copies on no stream of
+// the library's (the caller holds the device); throws DeviceError for a failed copy.  Walked through hash_links_shared.
+void key_hash_links(const u64* bsk, const u64* ksk, int keys_on_device, unsigned n_lwe, size_t ggsw_len, u64* links);
 void blocking_sync_budget_changed();      // the process's CPU budget was set: AUTO decides again
 }  // namespace vpbs
 

@@ -1,5 +1,6 @@
 // The seam between the program object (program.hip) and the five objects it drives: the Bootstrapper (pbs_batch.hip), the key ring
-// (pbs_keyring.hip), the batch provers (pbs_prove_batch.hip, pbs_prove_ring.hip) and the batch verifiers of whole vPBS proofs, one key set or a
+// (pbs_keyring.hip), the batch provers (pbs_prove_batch.hip, pbs_prove_ring.hip: two key sources of one worker pool, pbs_prove_pool.h, which
+// holds the run both share) and the batch verifiers of whole vPBS proofs, one key set or a
 // ring of key hashes (verify_pbs_batch.hip).  A program queues one bootstrap launch per
 // level behind its own combine kernel and waits once, at the end: it needs the Bootstrapper's launch WITHOUT the wait vpbs_bootstrapper_run
 // ends with, and the shapes of objects whose structs are private to their files.  Library-internal, like ivc_resident.h.
@@ -77,7 +78,8 @@ int keyring_add(vpbs_keyring* r, const uint64_t* bsk, const uint64_t* ksk, int k
 int keyring_remove(vpbs_keyring* r, unsigned slot, bool owner);
 
 // ---- the ring prover (pbs_prove_ring.hip), for vpbs_program_prove_batch ----
-// the mutex that add, remove and run of the ring prover take, and vpbs_ring_prover_run for a caller that holds it
+// the mutex that add, remove and run of the ring prover take, and vpbs_ring_prover_run for a caller that holds it and has made the
+// refusals of vpbs::ProvePool::check_run itself (count > 0): the check of the slots, then the pool's run
 std::mutex& ring_prover_mutex(vpbs_ring_prover* p);
 long ring_prover_run_locked(vpbs_ring_prover* p, const uint64_t* cts, size_t count, const uint32_t* key_of, const uint64_t* testv, int testv_per_ct,
                             unsigned steps, uint64_t* out_ct, uint64_t* lwe_out, vpbs_pbs_proof_fn proof_fn, void* user, char* err, size_t err_len,

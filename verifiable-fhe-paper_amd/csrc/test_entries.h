@@ -13,7 +13,7 @@ extern "C" {
 int vpbs_test_ivc_preset_matrix(size_t proof_words, size_t n_pi, size_t ggsw_len, size_t vk_words, unsigned n_lwe, unsigned first, unsigned count,
                                 const uint64_t* pis, const uint64_t* ct, const uint64_t* bsk, const uint64_t* ksk, const uint64_t* cyclic_vk,
                                 const uint64_t* dummy_vk, const uint64_t* dummy_proof, uint64_t* out);
-// The same matrix for the chain of one ciphertext, assembled on the device by the kernels of pbs_prove_batch.hip and copied to the host;
+// The same matrix for the chain of one ciphertext, assembled on the device by the kernels of pbs_prove_pool.hip and copied to the host;
 // preset_words: n_preset; dummy_proof: the [proof_words] dummy proof the object's vpbs_ivc holds on the host (the yardstick's constant).
 int vpbs_test_pbs_prover_preset_matrix(vpbs_pbs_prover* p, const uint64_t* ct, const uint64_t* testv, unsigned first, unsigned count, uint64_t* out);
 size_t vpbs_test_pbs_prover_preset_words(const vpbs_pbs_prover* p);

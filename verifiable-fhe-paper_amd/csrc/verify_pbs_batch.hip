@@ -376,17 +376,9 @@ bool ring_verifier_check_slots(const vpbs_ring_verifier* v, const uint32_t* key_
 extern "C" {
 int vpbs_pbs_key_hash(const uint64_t* bsk, const uint64_t* ksk, unsigned n_lwe, size_t ggsw_len, uint64_t out[4]) {
     if (!ksk || !out || ggsw_len == 0 || (n_lwe && !bsk)) return VPBS_ERR_INVALID;
-    // [dummy GGSW (zeros), bsk_0 .. bsk_{n-1}, ksk] as vpbs_verify_pbs hashes them, without materialising the items
-    const size_t steps = (size_t)n_lwe + 2;
-    const std::vector<u64> zero(ggsw_len, 0);
-    std::vector<const u64*> items(steps);
-    items[0] = zero.data();
-    for (unsigned k = 0; k < n_lwe; ++k) items[k + 1] = bsk + (size_t)k * ggsw_len;
-    items[steps - 1] = ksk;
-    std::vector<u64> links(4 * steps);
-    const u64 h0[4] = {0, 0, 0, 0};
-    vpbs::hash_links_shared(h0, items.data(), steps, ggsw_len, links.data());
-    std::memcpy(out, links.data() + 4 * (steps - 1), 32);
+    std::vector<u64> links(4 * ((size_t)n_lwe + 2));   // the last link of the chain the batch provers keep whole
+    vpbs::key_hash_links(bsk, ksk, 0, n_lwe, ggsw_len, links.data());
+    std::memcpy(out, links.data() + 4 * ((size_t)n_lwe + 1), 32);
     return VPBS_OK;
 }
 
