@@ -7,11 +7,20 @@
 //            constants/sigmas commitments and verifier data of the cyclic and the dummy circuit (CircuitBuilder::build's prover data),
 //            compiled witness plans, the split of the cyclic plan (the previous proof's words are the late part), three pinned + three
 //            device wire matrices
-//   prove  : base proof of the dummy circuit (cyclic_base_proof, :292-299), then per step
-//              thread E  vpbs_witness_plan_run_early   everything that does not need the previous proof; yields the step's public inputs
-//              thread U  vpbs_device_upload_bg         that matrix to the device while the previous step is being proven
-//              caller    vpbs_witness_plan_run_late -> vpbs_device_upload_rows -> vpbs_prove_step
-//            and the last proof serialised (ProofWithPublicInputs::to_bytes)
+//   prove  : ONE loop (ChainRun) on the calling thread: base proof of the dummy circuit (cyclic_base_proof, :292-299), then per step the
+//            late witness phase (the previous proof's words: vpbs_witness_plan_run_late_packed), the scatter of its values into the
+//            step's device matrix, vpbs_prove_step, the step hook and the checkpoint; the last proof serialised
+//            (ProofWithPublicInputs::to_bytes).  Who STAGES a step -- its device matrix with the early wires, its public inputs, its late
+//            state -- is a StepSource, and there are two:
+//              host pipeline (prove_pbs_host, the default)
+//                thread E  vpbs_witness_plan_run_early   everything that does not need the previous proof; yields the step's public inputs
+//                thread U  vpbs_device_upload_bg         that matrix to the device while the previous step is being proven
+//              device pipeline (prove_pbs_device_witness, vpbs_ivc_set_device_witness)
+//                the public inputs of ALL steps natively (accumulator chain; thread H walks the two hash chains), then
+//                thread B  vpbs_witness_device_run       the early phases of a batch of steps on one of two device objects
+//                thread S  vpbs_witness_device_wires     a step's wires into a device matrix, its late state seeded from the device
+//                (late phase on the device: no thread S, the loop runs vpbs_witness_device_run_late itself; resident chain: the public
+//                inputs are given, ivc_resident.h)
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -20,6 +29,8 @@
 #include <cstdlib>
 #include <cstring>
 #include <deque>
+#include <functional>
+#include <memory>
 #include <mutex>
 #include <pthread.h>
 #include <string>
@@ -55,6 +66,21 @@ double thread_cpu() {
     timespec ts;
     return clock_gettime(CLOCK_THREAD_CPUTIME_ID, &ts) == 0 ? ts.tv_sec + 1e-9 * ts.tv_nsec : 0.0;
 }
+// the message of an entry point into the caller's buffer (none: dropped)
+void report(char* err, size_t err_len, const std::string& m) {
+    if (err && err_len) {
+        std::strncpy(err, m.c_str(), err_len - 1);
+        err[err_len - 1] = 0;
+    }
+}
+// steps = 0, or more than the chain has: the whole chain of n + 2 steps
+unsigned clamp_steps(unsigned steps, unsigned n_lwe) { return steps == 0 || steps > n_lwe + 2 ? n_lwe + 2 : steps; }
+// the one owner of a late state (vpbs_witness_plan_run_early / vpbs_witness_state_from_late_inputs make it, run_late consumes it): a
+// failure on the way must not leak tens of MB of slot values
+struct StateFree {
+    void operator()(vpbs_witness_state* s) const { vpbs_witness_state_free(s); }
+};
+using State = std::unique_ptr<vpbs_witness_state, StateFree>;
 
 struct Side {   // one circuit on the context
     vpbs_ctx* ctx = nullptr;
@@ -303,11 +329,15 @@ struct vpbs_ivc {
     unsigned ckpt_every = 0;
     unsigned ckpt_base = 0;   // a resident chain that goes on at step k (ivc_prove_pbs_resident) counts its `every` from k; `done` stays absolute
     std::vector<uint8_t> ckpt_bytes;
+    // a step proof of the cyclic circuit as ProofWithPublicInputs::to_bytes writes it: what a call returns and what a checkpoint is
+    long to_bytes(const vpbs_step_inputs& in, const u64* caps, const u64* openings, const u64* fri, uint8_t* out, size_t capacity) const {
+        return vpbs_step_proof_to_bytes(ctx, &in, cyc.n_const_cols, caps, openings, fri, out, capacity);
+    }
     // after chained step `done` of a call that ends at step `last`: the proof serialised exactly as a call with steps = done returns it
     int checkpoint(const vpbs_step_inputs& in, const u64* caps, const u64* openings, const u64* fri, unsigned done, unsigned last) {
         if (!ckpt_fn || !ckpt_every || (done - ckpt_base) % ckpt_every != 0 || done >= last) return VPBS_OK;
         if (ckpt_bytes.empty()) ckpt_bytes.resize(8 * (proof_words + n_pi) + (1 << 16));
-        const long n = vpbs_step_proof_to_bytes(ctx, &in, cyc.n_const_cols, caps, openings, fri, ckpt_bytes.data(), ckpt_bytes.size());
+        const long n = to_bytes(in, caps, openings, fri, ckpt_bytes.data(), ckpt_bytes.size());
         if (n <= 0) return VPBS_ERR_INVALID;
         ckpt_fn(ckpt_user, done, ckpt_bytes.data(), (size_t)n);
         return VPBS_OK;
@@ -347,16 +377,266 @@ struct vpbs_ivc {
     }
 };
 
+namespace {
+// One call's arguments, as vpbs_ivc_prove_pbs, vpbs_ivc_resume_pbs and vpbs::ivc_prove_pbs_resident pass them on.  from > 0: a resume --
+// no base proof, step `from` takes from_proof [proof_words] as its inner proof and from_pis [n_pi] as its predecessor's public inputs.
+struct ChainArgs {
+    vpbs_ivc* v;
+    const u64 *testv, *ct, *bsk, *ksk;
+    unsigned n_lwe, from;
+    const u64 *from_proof, *from_pis;
+    unsigned steps;
+    uint8_t* proof_out;
+    size_t capacity;
+    vpbs_ivc_timing* timing;
+    char* err;
+    size_t err_len;
+};
+// One step as a pipeline hands it to the loop: the early wires are in device matrix `buf`, `pis` are the step's public inputs, `state` is
+// what the late phase goes on from (none: the late phase runs on the device) and `values` the PartialWitness values that phase reads -- only
+// the previous proof's words, at the front.  The host pipeline builds an array per step (own_*); the device pipeline's steps read the loop's.
+struct Staged {
+    int buf = -1;   // -1: no step
+    const u64* pis = nullptr;
+    u64* values = nullptr;
+    State state;
+    std::vector<u64> own_values, own_pis;
+};
+// What a pipeline is to the loop.  j counts the steps of THIS call: local step j is chain step from + j.
+struct StepSource {
+    // blocks until step j is staged and its public inputs are complete; fills `step` unless try_take has (buf >= 0).  false: the run failed
+    std::function<bool(unsigned j, Staged& step)> take;
+    // step j if it is staged by now: asked from inside the previous step's proof (on_section), so it never waits
+    std::function<bool(unsigned j, Staged& step)> try_take;
+    // step j is proven: its device matrix is free again
+    std::function<void(unsigned j, const Staged& step)> release;
+    // late phase on the device only: on_section of the proof of step j (DevHook)
+    std::function<void(unsigned j, vpbs_step_inputs& in)> arm_device_late;
+    // device pipeline only: what take waited for {the staged wires, the hash chain} in seconds, and with them the VPBS_TRACE_IVC line
+    const double* waits = nullptr;
+};
+// The frame of one chain run: what both pipelines own -- arguments, error reporting, the producer threads and the lock they share with the
+// loop, the proof buffer, the LateAhead worker, the timers -- and the chain itself, stated once: base(), step() per step, tail().
+struct ChainRun : ChainArgs {
+    Side &cyc, &dum;
+    vpbs_ctx* const ctx;
+    const size_t proof_words, ggsw_len;
+    const unsigned n_run;
+    const std::vector<u64> zero_ggsw;
+    std::mutex mu;
+    std::condition_variable cv;
+    std::atomic<bool> failed{false};   // every wait predicate names it
+    std::string thread_err;
+    std::vector<std::thread> producers;
+    // the clock: from here in the device pipeline (its native accumulator chain counts); the host pipeline restarts it at the base proof
+    double t0 = now();
+    double t_base = 0, t_early = 0, t_late = 0, t_rows = 0, t_prove = 0;   // t_early: the pipeline's (thread E, thread B)
+    double c_late = 0, c_rows = 0, c_prove = 0, lap_t = 0, lap_c = 0;      // CPU time of THIS thread in the same sections (VPBS_TRACE_IVC)
+    // the previous proof, in the flat order of the proof targets.  A whole PartialWitness array with the proof at its front: the late phase
+    // reads the late presets only, so the prover writes straight into what the device pipeline's steps read (Staged::values)
+    std::vector<u64> proof;
+    u64 *const caps, *openings = nullptr, *fri = nullptr;
+    vpbs_step_inputs in;
+    char e[256] = {0};
+    // The next step's late stages 1 and 2 run on a worker while this step's FRI stage is on the device (LateAhead): the prover reports its
+    // sections (on_section, on this thread); the first report that finds the next step staged takes it.  The steps are declared before the
+    // worker: the worker is joined before the state it may be working on goes away.
+    Staged cur, next;
+    LateAhead ahead;
+    const StepSource* src = nullptr;
+    unsigned j = 0;   // the step being proven
+
+    explicit ChainRun(const ChainArgs& a)
+        : ChainArgs(a), cyc(a.v->cyc), dum(a.v->dum), ctx(a.v->ctx), proof_words(a.v->proof_words), ggsw_len(a.v->ggsw_len), n_run(a.steps - a.from),
+          zero_ggsw(a.v->ggsw_len, 0), proof(a.v->cyc.n_preset, 0), caps(proof.data()) {}
+    void say(const std::string& m) { report(err, err_len, m); }
+    // GGSW and mask of chain step s: nothing in the base step, a bootstrapping key and its mask, then the key-switching key
+    const u64* ggsw_of(unsigned s) const { return s == 0 ? zero_ggsw.data() : (s <= n_lwe ? bsk + (size_t)(s - 1) * ggsw_len : ksk); }
+    u64 mask_of(unsigned s) const { return s == 0 ? ct[n_lwe] : (s <= n_lwe ? ct[s - 1] : (u64)0); }
+    void fail(const std::string& m) {
+        {   // the flag changes under the lock: a waiter that has just evaluated its predicate cannot miss the notification
+            std::lock_guard<std::mutex> lk(mu);
+            if (thread_err.empty()) thread_err = m;
+            failed = true;
+        }
+        cv.notify_all();
+    }
+    void spawn(const char* name, std::function<void()> body) {
+        producers.emplace_back([name, body] {
+            name_thread(name);
+            body();
+        });
+    }
+    void join() {
+        for (auto& t : producers)
+            if (t.joinable()) t.join();
+    }
+    // fails, joins every producer and reports the FIRST error of the run
+    long stop(const std::string& m, int rc) {
+        fail(m);
+        join();
+        std::string first;
+        {
+            std::lock_guard<std::mutex> lk(mu);
+            first = thread_err;
+        }
+        say(first);
+        return rc;
+    }
+    // a rank of a SHARDED chain that cannot start a step's proof (its witness failed) takes part in that step's collectives on the failing
+    // side: the other ranks' proofs of the step return VPBS_ERR_PEER and the chain ends on every rank instead of hanging on the others
+    void abandon_step(int why) {
+        if (!cyc.comm) return;
+        vpbs_step_inputs shape;
+        cyc.step_inputs(shape, nullptr, true, nullptr);
+        (void)vpbs_prove_step_sharded_fail(ctx, &shape, cyc.comm, why);
+    }
+    long stop_step(const std::string& m, int why) {
+        abandon_step(why);
+        return stop(m, why);
+    }
+    void lap(double& wall, double& cpu) {   // the section since the last lap
+        const double t = now(), c = thread_cpu();
+        wall += t - lap_t;
+        cpu += c - lap_c;
+        lap_t = t;
+        lap_c = c;
+    }
+
+    // cyclic_base_proof (:292-299): a proof of the dummy circuit carrying the initial accumulator and the cyclic verifier data -- or, on a
+    // resume, the checkpoint's proof words.  0, or what stop() returned
+    long base(const u64* base_pis) {
+        vpbs_step_sizes sz{};
+        if (!from && vpbs_witness_plan_run(dum.plan, base_pis, 0, v->base_wires, e, sizeof e) != 0)
+            return stop(std::string("dummy witness: ") + e, VPBS_ERR_INVALID);
+        dum.step_inputs(in, v->base_wires, false, base_pis);
+        if (vpbs_step_sizes_get(ctx, &in, &sz) != 0 || 3 * sz.cap_words + sz.openings_words + sz.fri_words != proof_words)
+            return stop("the proof of this shape does not have the number of words the cyclic circuit expects", VPBS_ERR_INVALID);
+        openings = caps + 3 * sz.cap_words;
+        fri = openings + sz.openings_words;
+        if (from) {
+            std::memcpy(proof.data(), from_proof, 8 * proof_words);   // the checkpoint's proof is the inner proof of step `from`
+        } else {
+            const int rc = dum.prove(in, caps, openings, fri);
+            if (rc != 0) return stop(std::string("base proof: ") + vpbs_last_error(ctx), rc);
+            t_base = now() - t0;
+            if (v->step_fn) v->step_fn(v->step_user, 0);
+        }
+        if (v->staged && !v->dw_late) {
+            ahead.ranges = v->ahead_layout.ranges;
+            ahead.packed = v->late_vals;
+            ahead.start(cyc.plan);
+        }
+        return 0;
+    }
+    // on_section of a step's proof with the late phase on the host: the sections of the proof in progress that are final
+    static void section(void* user, int sec) {
+        auto* r = static_cast<ChainRun*>(user);
+        if (r->next.buf < 0) {
+            if (!r->src->try_take(r->j + 1, r->next)) return;   // the next step is not staged yet: its late phase runs whole, after the proof
+            r->ahead.begin(r->next.state.get(), r->next.values, r->proof.data());
+        }
+        r->ahead.post((unsigned)sec);
+    }
+    // local step j: late phase, scatter, proof; then the buffer goes back, the step hook runs and the checkpoint is taken.  0, or what stop() returned
+    long step(unsigned local, const StepSource& source) {
+        j = local;
+        src = &source;
+        const unsigned s = from + j;
+        cur = std::move(next);
+        next = Staged{};
+        if (!source.take(j, cur)) return stop_step("", VPBS_ERR_INVALID);
+        const std::string late_failed = "late witness phase of step " + std::to_string(s) + " (the previous proof does not verify in circuit): ";
+        u64* d_wires = v->d_bufs[cur.buf];
+        int rc;
+        lap_t = now();
+        lap_c = thread_cpu();
+        if (v->dw_late) {
+            // the late phase on the device object that holds the step's early values, then ALL its wires into the prover's matrix
+            const unsigned o = (j / v->dw_batch) & 1, i = j % v->dw_batch;
+            rc = vpbs_witness_device_run_late(v->wdev[o], i, proof.data());
+            if (rc != 0) return stop_step(late_failed + vpbs_last_error(v->wctx[o]), rc);
+            lap(t_late, c_late);
+            rc = vpbs_witness_device_wires(v->wdev[o], i, d_wires);
+            if (rc != 0) return stop_step(std::string("gathering the wires: ") + vpbs_last_error(v->wctx[o]), rc);
+        } else {
+            if (ahead.active()) {   // stages that ran ahead on this step's state: wait for the last of them (usually long finished)
+                std::string msg;
+                if (!ahead.drain(msg)) return stop_step(late_failed + msg, VPBS_ERR_INVALID);
+            }
+            if (cur.values != proof.data()) std::memcpy(cur.values, proof.data(), 8 * proof_words);   // else the prover wrote them there
+            rc = vpbs_witness_plan_run_late_packed(cyc.plan, cur.state.release(), cur.values, v->late_vals, e, sizeof e);   // consumes the state, also when it fails
+            if (rc != 0) return stop_step(late_failed + e, rc);
+            lap(t_late, c_late);
+            // queued, not waited for: the proof is ordered behind it on the context's stream, and the packed buffer is next written a whole
+            // proof (several waits on this stream) later -- by the late stages of the NEXT step, which start at this proof's first section
+            rc = vpbs::device_scatter(ctx, d_wires, v->d_late_pos, v->late_vals, v->late_count, v->d_late_stage, false);
+            if (rc != 0) return stop_step(std::string("upload of the late wires: ") + vpbs_last_error(ctx), rc);
+        }
+        lap(t_rows, c_rows);
+        cyc.step_inputs(in, d_wires, true, cur.pis);
+        if (v->staged && s + 1 < steps) {
+            static const bool dev_ahead = !std::getenv("VPBS_DEVICE_LATE_AHEAD") || std::atoi(std::getenv("VPBS_DEVICE_LATE_AHEAD")) != 0;   // A-B switch
+            if (!v->dw_late) {
+                in.on_section = &ChainRun::section;
+                in.on_section_user = this;
+            } else if (dev_ahead) {
+                source.arm_device_late(j, in);
+            }
+        }
+        rc = cyc.prove(in, caps, openings, fri);
+        if (rc != 0) {   // a sharded chain's collectives carried it already
+            if (ahead.active()) {   // the worker may be inside a stage of the next step's state: let it finish before that state is freed
+                std::string ignored;
+                (void)ahead.drain(ignored);
+            }
+            return stop("step " + std::to_string(s) + ": " + vpbs_last_error(ctx), rc);
+        }
+        lap(t_prove, c_prove);
+        source.release(j, cur);
+        if (v->step_fn) v->step_fn(v->step_user, s + 1);
+        if (v->checkpoint(in, caps, openings, fri, s + 1, steps) != 0) return stop("checkpoint after step " + std::to_string(s) + ": the proof does not serialise", VPBS_ERR_INVALID);
+        return 0;
+    }
+    // the last proof serialised (ProofWithPublicInputs::to_bytes) and the timing of the run
+    long tail(const StepSource& source) {
+        join();
+        const double seconds = now() - t0;
+        if (source.waits && std::getenv("VPBS_TRACE_IVC"))
+            std::fprintf(stderr, "[ivc device witness] per step: waited %.2f ms for the staged wires, %.2f ms for the hash chain; late %.2f, scatter %.2f, "
+                         "prove %.2f, device batch run %.2f ms; CPU time of the proving thread: late %.2f, scatter %.2f, prove %.2f ms (blocking waits: %d)\n",
+                         1e3 * source.waits[0] / n_run, 1e3 * source.waits[1] / n_run, 1e3 * t_late / n_run, 1e3 * t_rows / n_run, 1e3 * t_prove / n_run,
+                         1e3 * t_early / n_run, 1e3 * c_late / n_run, 1e3 * c_rows / n_run, 1e3 * c_prove / n_run, vpbs_host_blocking_sync());
+        const long n_bytes = v->to_bytes(in, caps, openings, fri, proof_out, capacity);
+        if (n_bytes <= 0) {
+            say("the output buffer is too small for the proof");
+            return VPBS_ERR_INVALID;
+        }
+        if (timing) {
+            timing->seconds = seconds;
+            timing->steps = n_run;
+            timing->base_proof_ms = 1e3 * t_base;
+            timing->late_witness_ms = 1e3 * t_late / n_run;
+            timing->late_rows_upload_ms = 1e3 * t_rows / n_run;
+            timing->prove_step_ms = 1e3 * t_prove / n_run;
+            timing->early_witness_ms = 1e3 * t_early / n_run;
+            timing->late_ahead_ms = 1e3 * ahead.busy_s / n_run;
+        }
+        return n_bytes;
+    }
+    long run(const u64* base_pis, const StepSource& source) {
+        long rc = base(base_pis);
+        for (unsigned k = 0; rc == 0 && k < n_run; ++k) rc = step(k, source);
+        return rc == 0 ? tail(source) : rc;
+    }
+};
+}  // namespace
+
 extern "C" {
 
 int vpbs_ivc_create(vpbs_ctx* ctx, const vpbs_ivc_circuit* cyclic, const vpbs_ivc_circuit* dummy, unsigned N, unsigned K, size_t ggsw_len,
                     const vpbs_comm* comm, vpbs_ivc** out, char* err, size_t err_len) {
-    auto say = [&](const std::string& m) {
-        if (err && err_len) {
-            std::strncpy(err, m.c_str(), err_len - 1);
-            err[err_len - 1] = 0;
-        }
-    };
+    auto say = [&](const std::string& m) { report(err, err_len, m); };
     say("");
     if (!ctx || !cyclic || !dummy || !out || !cyclic->circuit || !dummy->circuit || !cyclic->preset_pos || !dummy->preset_pos || !cyclic->pi_pos ||
         N == 0 || K == 0) {
@@ -572,40 +852,34 @@ static void preset_matrix_host(u64* m, unsigned first, unsigned cnt, const u64* 
 // INPUTS, and those are known without proving anything: the accumulators from the native chain (vpbs_pbs_accumulator_chain), the two chain
 // hashes from the native sponge (one host thread walks them ahead of the batches), counter and verifier data.  So the early phases of
 // `dw_batch` consecutive steps run on the device at once (thread B), a stager thread gathers an instance's wires into the device matrix
-// the prover will read and fetches the early values the late phase needs (thread S), and the caller is left with the late phase (the
-// in-circuit verifier's rows), the scatter of its values and the proof.
+// the prover will read and fetches the early values the late phase needs (thread S), and the loop (ChainRun, which this function only
+// feeds with staged steps) is left with the late phase (the in-circuit verifier's rows), the scatter of its values and the proof.
 // from > 0 (vpbs_ivc_resume_pbs): no base proof; step `from` takes the checkpoint's proof words and public inputs, the native accumulator
 // chain starts at step `from` from the checkpoint's accumulator and the hash thread from its two hashes.  Progress below is counted in steps
 // of THIS call: local step j is chain step from + j.
 // res != nullptr (vpbs::ivc_prove_pbs_resident, bsk and ksk not read): the chain's public inputs exist already -- accumulators and both hash
 // chains are taken from `res`, indexed by ABSOLUTE chain step whatever `from` is, and every batch's preset matrix is written on the device by
 // res->fill, called with the absolute first step.
-static long prove_pbs_device_witness(vpbs_ivc* v, const uint64_t* testv, const uint64_t* ct, const uint64_t* bsk, const uint64_t* ksk, unsigned n_lwe,
-                                     unsigned from, const u64* from_proof, const u64* from_pis, unsigned steps, uint8_t* proof_out, size_t capacity,
-                                     vpbs_ivc_timing* timing, char* err, size_t err_len, const vpbs::IvcResidentChain* res = nullptr) {
-    auto say = [&](const std::string& m) {
-        if (err && err_len) {
-            std::strncpy(err, m.c_str(), err_len - 1);
-            err[err_len - 1] = 0;
-        }
-    };
+static long prove_pbs_device_witness(const ChainArgs& a, const vpbs::IvcResidentChain* res = nullptr) {
+    ChainRun run(a);   // the clock starts here
+    vpbs_ivc* v = a.v;
     Side &cyc = v->cyc, &dum = v->dum;
-    vpbs_ctx* ctx = v->ctx;
-    const size_t kn = v->kn, n_pi = v->n_pi, proof_words = v->proof_words, ggsw_len = v->ggsw_len, n_preset = cyc.n_preset;
-    const unsigned B = v->dw_batch, total = n_lwe + 2, n_run = steps - from;
-    const std::vector<u64> zero_ggsw(ggsw_len, 0);
-    auto ggsw_of = [&](unsigned s) { return s == 0 ? zero_ggsw.data() : (s <= n_lwe ? bsk + (size_t)(s - 1) * ggsw_len : ksk); };
-    auto mask_of = [&](unsigned s) { return s == 0 ? ct[n_lwe] : (s <= n_lwe ? ct[s - 1] : (u64)0); };
-    const double t0 = now();
+    const size_t kn = v->kn, n_pi = v->n_pi, ggsw_len = v->ggsw_len;
+    const unsigned B = v->dw_batch, from = a.from, n_lwe = a.n_lwe, total = n_lwe + 2, n_run = run.n_run;
+    constexpr unsigned NBUF = vpbs_ivc::NBUF;
+    std::mutex& mu = run.mu;
+    std::condition_variable& cv = run.cv;
+    std::atomic<bool>& failed = run.failed;
+    auto fail = [&](const std::string& m) { run.fail(m); };
     // ---- the chain's public inputs, natively ----
     // accs[j] = the accumulator after chain step from + j (step `from` reads acc_init, or the checkpoint's accumulator)
     std::vector<u64> acc_init(kn, 0), own_accs(res ? 0 : (size_t)(total - from) * kn);
-    std::memcpy(acc_init.data() + kn - v->N, testv, 8 * (size_t)v->N);
+    std::memcpy(acc_init.data() + kn - v->N, a.testv, 8 * (size_t)v->N);
     unsigned log_N = 0;
     while ((1u << log_N) < v->N) ++log_N;
     const vpbs_tfhe_params tp{log_N, v->K, v->ELL, v->LOGB};
-    if (!res && vpbs::pbs_accumulator_chain_from(ctx, &tp, n_lwe, from, from ? from_pis + kn + 1 : acc_init.data(), ct, bsk, ksk, own_accs.data()) != 0) {
-        say(std::string("native accumulator chain: ") + vpbs_last_error(ctx));
+    if (!res && vpbs::pbs_accumulator_chain_from(v->ctx, &tp, n_lwe, from, from ? a.from_pis + kn + 1 : acc_init.data(), a.ct, a.bsk, a.ksk, own_accs.data()) != 0) {
+        run.say(std::string("native accumulator chain: ") + vpbs_last_error(v->ctx));
         return VPBS_ERR_INVALID;
     }
     const u64* accs = res ? res->accs + (size_t)from * kn : own_accs.data();   // accs[j]: after chain step from + j (valid from j = -1 for res)
@@ -615,7 +889,7 @@ static long prove_pbs_device_witness(vpbs_ivc* v, const uint64_t* testv, const u
     for (unsigned j = 0; j <= n_run; ++j) {
         u64* q = pis.data() + (size_t)j * n_pi;
         if (j == 0 && from) {
-            std::memcpy(q, from_pis, 8 * n_pi);
+            std::memcpy(q, a.from_pis, 8 * n_pi);
             continue;
         }
         std::memcpy(q, acc_init.data(), 8 * kn);
@@ -623,26 +897,12 @@ static long prove_pbs_device_witness(vpbs_ivc* v, const uint64_t* testv, const u
         if (j) std::memcpy(q + kn + 1, accs + ((size_t)j - 1) * kn, 8 * kn);
         std::memcpy(q + n_pi - cyc.vk.size(), cyc.vk.data(), 8 * cyc.vk.size());
     }
-    std::mutex mu;
-    std::condition_variable cv;
-    std::atomic<bool> failed{false};
-    std::string thread_err;
-    auto fail = [&](const std::string& m) {
-        {   // the flag changes under the lock: a waiter that has just evaluated its predicate cannot miss the notification
-            std::lock_guard<std::mutex> lk(mu);
-            if (thread_err.empty()) thread_err = m;
-            failed = true;
-        }
-        cv.notify_all();
-    };
     unsigned hashed = 0;        // steps whose chain hashes are in pis (guarded by mu; these four count the steps of this call: local j)
     unsigned batches_run = 0;   // batches whose early phases are on the device
     unsigned staged = 0;        // steps gathered and read back
-    unsigned consumed = 0;      // steps the caller has finished with (their device matrix is free again)
-    double t_early = 0;
+    unsigned consumed = 0;      // steps the loop has finished with (their device matrix is free again)
     // thread H: the two hash chains of verify_hash_output (:64-78), h_s = hash_no_pad(h_{s-1} || item_s), one permutation after the other
-    std::thread hasher([&] {
-        name_thread("vpbs-hash");
+    run.spawn("vpbs-hash", [&] {
         if (res) {   // both chains exist: nothing to wait for, nothing to hash
             for (unsigned s = 0; s < n_run; ++s) {
                 u64* q = pis.data() + (size_t)(s + 1) * n_pi + 2 * kn + 1;
@@ -672,13 +932,13 @@ static long prove_pbs_device_witness(vpbs_ivc* v, const uint64_t* testv, const u
                 if (failed) return;
             }
             const unsigned cnt = std::min(SEG, n_run - s0);
-            for (unsigned i = 0; i < cnt; ++i) items[i] = ggsw_of(from + s0 + i);
+            for (unsigned i = 0; i < cnt; ++i) items[i] = run.ggsw_of(from + s0 + i);
             if (vpbs_hash_chain_links(hb, items, cnt, ggsw_len, links) != 0) return fail("hash chain of the bootstrapping key: malformed arguments");
             std::memcpy(hb, links + 4 * (cnt - 1), 32);
             for (unsigned i = 0; i < cnt; ++i) {
                 const unsigned s = s0 + i;
                 std::memcpy(in2.data(), hl, 32);
-                in2[4] = mask_of(from + s);
+                in2[4] = run.mask_of(from + s);
                 vpbs_hash_no_pad(in2.data(), 5, hl);
                 u64* q = pis.data() + (size_t)(s + 1) * n_pi + 2 * kn + 1;
                 std::memcpy(q, links + 4 * i, 32);
@@ -693,8 +953,7 @@ static long prove_pbs_device_witness(vpbs_ivc* v, const uint64_t* testv, const u
     });
     // thread B: batch b = steps [b B, (b + 1) B) on device object b & 1, once their public inputs exist and the object's previous batch is consumed
     const unsigned n_batches = (n_run + B - 1) / B;
-    std::thread batcher([&] {
-        name_thread("vpbs-batcher");
+    run.spawn("vpbs-batcher", [&] {
         for (unsigned b = 0; b < n_batches && !failed; ++b) {
             const unsigned first = b * B, cnt = std::min(B, n_run - first);
             {
@@ -717,13 +976,13 @@ static long prove_pbs_device_witness(vpbs_ivc* v, const uint64_t* testv, const u
                 run_rc = vpbs::witness_device_run_filled(v->wdev[b & 1], cnt, &Fill::call, &fill);
             } else {
                 u64* m = v->dw_presets;   // [n_preset][cnt]
-                preset_matrix_host(m, from + first, cnt, pis.data() + (size_t)first * n_pi, proof_words, n_pi, ggsw_len, n_lwe, ct, bsk, ksk,
+                preset_matrix_host(m, from + first, cnt, pis.data() + (size_t)first * n_pi, v->proof_words, n_pi, ggsw_len, n_lwe, a.ct, a.bsk, a.ksk,
                                    cyc.vk.data(), dum.vk.data(), cyc.vk.size(), v->dummy_proof.data());
                 run_rc = vpbs_witness_device_run(v->wdev[b & 1], m, cnt);
             }
             if (run_rc != 0)
                 return fail("early witness phases of steps " + std::to_string(from + first) + ".. on the device: " + vpbs_last_error(v->wctx[b & 1]));
-            t_early += now() - t;
+            run.t_early += now() - t;
             {
                 std::lock_guard<std::mutex> lk(mu);
                 batches_run = b + 1;
@@ -733,22 +992,15 @@ static long prove_pbs_device_witness(vpbs_ivc* v, const uint64_t* testv, const u
     });
     // thread S: per step, the instance's wires into one of the device matrices, the late phase's inputs to the host and the late phase's
     // state seeded with them (allocation and first touch of its pages happen here, ahead of the chain)
-    std::vector<std::vector<u64>> late_in(vpbs_ivc::NBUF, std::vector<u64>(v->late_in_count));
-    struct States {   // owned here until the caller takes one; whatever is left at the end is freed
-        vpbs_witness_state* st[vpbs_ivc::NBUF] = {nullptr, nullptr, nullptr};
-        ~States() {
-            for (auto* x : st)
-                if (x) vpbs_witness_state_free(x);
-        }
-    } states;
-    std::thread stager([&] {
-        name_thread("vpbs-stager");
-        if (v->dw_late) return;   // the caller runs the late phase on the device object itself and gathers afterwards
+    std::vector<std::vector<u64>> late_in(NBUF, std::vector<u64>(v->late_in_count));
+    State states[NBUF];   // owned here until the loop takes one; whatever is left at the end is freed
+    run.spawn("vpbs-stager", [&] {
+        if (v->dw_late) return;   // the loop runs the late phase on the device object itself and gathers afterwards
         for (unsigned j = 0; j < n_run && !failed; ++j) {
-            const unsigned b = j / B, k = j % vpbs_ivc::NBUF;
+            const unsigned b = j / B, k = j % NBUF;
             {
                 std::unique_lock<std::mutex> lk(mu);
-                cv.wait(lk, [&] { return failed || (batches_run > b && j < consumed + vpbs_ivc::NBUF); });
+                cv.wait(lk, [&] { return failed || (batches_run > b && j < consumed + NBUF); });
                 if (failed) return;
             }
             if (vpbs_witness_device_wires(v->wdev[b & 1], j % B, v->d_bufs[k]) != 0 ||
@@ -759,86 +1011,15 @@ static long prove_pbs_device_witness(vpbs_ivc* v, const uint64_t* testv, const u
                 return fail("late witness phase of step " + std::to_string(from + j) + ": the early values read back from the device are malformed");
             {
                 std::lock_guard<std::mutex> lk(mu);
-                states.st[k] = st;
+                states[k].reset(st);
                 staged = j + 1;
             }
             cv.notify_all();
         }
     });
-    auto stop = [&](const std::string& m, int rc) {
-        fail(m);
-        hasher.join();
-        batcher.join();
-        stager.join();
-        std::string first;
-        {
-            std::lock_guard<std::mutex> lk(mu);
-            first = thread_err;
-        }
-        say(first);
-        return (long)rc;
-    };
-    // cyclic_base_proof (:292-299)
-    char e[256] = {0};
-    vpbs_step_inputs in;
-    vpbs_step_sizes sz{};
-    if (!from && vpbs_witness_plan_run(dum.plan, pis.data(), 0, v->base_wires, e, sizeof e) != 0)
-        return stop(std::string("dummy witness: ") + e, VPBS_ERR_INVALID);
-    dum.step_inputs(in, v->base_wires, false, pis.data());
-    if (vpbs_step_sizes_get(ctx, &in, &sz) != 0 || 3 * sz.cap_words + sz.openings_words + sz.fri_words != proof_words)
-        return stop("the proof of this shape does not have the number of words the cyclic circuit expects", VPBS_ERR_INVALID);
-    std::vector<u64> values(n_preset, 0);   // run_late reads the late presets only: the previous proof's words, at the front
-    u64 *caps = values.data(), *openings = caps + 3 * sz.cap_words, *fri = openings + sz.openings_words;
-    int rc = VPBS_OK;
-    if (from) {
-        std::memcpy(values.data(), from_proof, 8 * proof_words);   // the checkpoint's proof is the inner proof of step `from`
-    } else {
-        rc = dum.prove(in, caps, openings, fri);
-        if (rc != 0) return stop(std::string("base proof: ") + vpbs_last_error(ctx), rc);
-    }
-    const double t_base = from ? 0.0 : now() - t0;
-    if (v->step_fn && !from) v->step_fn(v->step_user, 0);
-    double t_late = 0, t_rows = 0, t_prove = 0, t_wait_staged = 0, t_wait_hashed = 0;
-    double c_late = 0, c_rows = 0, c_prove = 0;   // CPU time of THIS thread in the same sections (VPBS_TRACE_IVC)
-    // late stages 1 and 2 of the next step while this step's FRI stage runs (LateAhead); here the prover writes the proof straight into
-    // `values`, the array the late phase reads its presets from
-    vpbs_witness_state* next_state = nullptr;   // taken from `states` by the hook; declared before the worker (joined first)
-    struct NextGuard {
-        vpbs_witness_state*& p;
-        ~NextGuard() {
-            if (p) vpbs_witness_state_free(p);
-        }
-    } next_guard{next_state};
-    LateAhead ahead;
-    if (v->staged && !v->dw_late) {
-        ahead.ranges = v->ahead_layout.ranges;
-        ahead.packed = v->late_vals;
-        ahead.start(cyc.plan);
-    }
-    struct Hook {
-        LateAhead* ahead;
-        std::mutex* mu;
-        const unsigned* staged;
-        States* states;
-        vpbs_witness_state** next_state;
-        u64* values;
-        unsigned step = 0;   // the step being proven
-        static void section(void* user, int sec) {
-            auto* h = static_cast<Hook*>(user);
-            if (!*h->next_state) {
-                std::lock_guard<std::mutex> lk(*h->mu);
-                if (*h->staged <= h->step + 1) return;   // the next step is not staged yet: its late phase runs whole, after the proof
-                const unsigned k = (h->step + 1) % vpbs_ivc::NBUF;
-                *h->next_state = h->states->st[k];
-                h->states->st[k] = nullptr;
-                h->ahead->begin(*h->next_state, h->values, h->values);
-            }
-            h->ahead->post((unsigned)sec);
-        }
-    } hook{&ahead, &mu, &staged, &states, &next_state, values.data()};
-    // The same idea with the late phase on the DEVICE (round 6): the stages of the next step's late phase are queued on its witness object's
-    // stream as the sections of the proof in progress become final (the prover writes them straight into `values`); when the proof returns only
-    // the last stage -- the query rounds: 33 of the 162 dependency levels -- is left to queue and wait for.
+    // The LateAhead idea with the late phase on the DEVICE (round 6): the stages of the next step's late phase are queued on its witness object's
+    // stream as the sections of the proof in progress become final (the prover writes them straight into the loop's proof buffer); when the
+    // proof returns only the last stage -- the query rounds: 33 of the 162 dependency levels -- is left to queue and wait for.
     struct DevHook {
         vpbs_ivc* v;
         std::mutex* mu;
@@ -860,228 +1041,103 @@ static long prove_pbs_device_witness(vpbs_ivc* v, const uint64_t* testv, const u
                 ++h->queued;
             }
         }
-    } dev_hook{v, &mu, &batches_run, B, values.data()};
-    // a rank of a SHARDED chain that cannot start a step's proof takes part in the step's collectives on the failing side (see the host pipeline)
-    auto stop_step = [&](const std::string& m, int why) {
-        if (cyc.comm) {
-            vpbs_step_inputs shape;
-            cyc.step_inputs(shape, nullptr, true, nullptr);
-            (void)vpbs_prove_step_sharded_fail(ctx, &shape, cyc.comm, why);
-        }
-        return stop(m, why);
+    } dev_hook{v, &mu, &batches_run, B, run.proof.data()};
+    double waits[2] = {0, 0};
+    auto hand_over = [&](unsigned j, Staged& step) {   // mu held, step j staged
+        step.buf = j % NBUF;
+        step.pis = pis.data() + (size_t)(j + 1) * n_pi;
+        step.values = run.proof.data();
+        step.state = std::move(states[j % NBUF]);   // none with the late phase on the device
     };
-    for (unsigned j = 0; j < n_run; ++j) {
-        const unsigned s = from + j, k = j % vpbs_ivc::NBUF;
-        {
-            const double tw = now();
-            std::unique_lock<std::mutex> lk(mu);
-            const unsigned b = j / B;
-            cv.wait(lk, [&] { return failed || (v->dw_late ? batches_run > b : staged > j); });
-            const double tw2 = now();
-            t_wait_staged += tw2 - tw;
-            cv.wait(lk, [&] { return failed || hashed > j; });   // its own public inputs are complete
-            t_wait_hashed += now() - tw2;
-            if (failed) {
-                lk.unlock();
-                return stop_step("", VPBS_ERR_INVALID);
-            }
-        }
-        double t = now();
-        double c0 = thread_cpu();
-        if (v->dw_late) {
-            // the late phase on the device object that holds the step's early values, then ALL its wires into the prover's matrix
-            vpbs_witness_device* dev = v->wdev[(j / B) & 1];
-            rc = vpbs_witness_device_run_late(dev, j % B, values.data());
-            if (rc != 0)
-                return stop_step("late witness phase of step " + std::to_string(s) + " (the previous proof does not verify in circuit): " +
-                            vpbs_last_error(v->wctx[(j / B) & 1]), rc);
-            t_late += now() - t;
-            t = now();
-            rc = vpbs_witness_device_wires(dev, j % B, v->d_bufs[k]);
-            if (rc != 0) return stop_step(std::string("gathering the wires: ") + vpbs_last_error(v->wctx[(j / B) & 1]), rc);
-            t_rows += now() - t;
-        } else {
-            vpbs_witness_state* st = next_state;
-            next_state = nullptr;
-            if (st) {   // stages ran ahead on it: wait for the last of them
-                std::string msg;
-                if (!ahead.drain(msg)) {
-                    vpbs_witness_state_free(st);
-                    return stop_step("late witness phase of step " + std::to_string(s) + " (the previous proof does not verify in circuit): " + msg, VPBS_ERR_INVALID);
-                }
-            } else {
-                std::lock_guard<std::mutex> lk(mu);
-                st = states.st[k];
-                states.st[k] = nullptr;
-            }
-            rc = vpbs_witness_plan_run_late_packed(cyc.plan, st, values.data(), v->late_vals, e, sizeof e);
-            if (rc != 0) return stop_step("late witness phase of step " + std::to_string(s) + " (the previous proof does not verify in circuit): " + e, rc);
-            t_late += now() - t;
-            t = now();
-            c_late += thread_cpu() - c0;
-            c0 = thread_cpu();
-            // queued, not waited for: the proof is ordered behind it on the context's stream, and the packed buffer is next written a whole
-            // proof (several waits on this stream) later -- by the late stages of the NEXT step, which start at this proof's first section
-            rc = vpbs::device_scatter(ctx, v->d_bufs[k], v->d_late_pos, v->late_vals, v->late_count, v->d_late_stage, false);
-            if (rc != 0) return stop_step(std::string("upload of the late wires: ") + vpbs_last_error(ctx), rc);
-            t_rows += now() - t;
-            c_rows += thread_cpu() - c0;
-        }
-        t = now();
-        c0 = thread_cpu();
-        cyc.step_inputs(in, v->d_bufs[k], true, pis.data() + (size_t)(j + 1) * n_pi);
-        if (v->staged && !v->dw_late && s + 1 < steps) {
-            hook.step = j;
-            in.on_section = &Hook::section;
-            in.on_section_user = &hook;
-        }
-        static const bool dev_ahead = !std::getenv("VPBS_DEVICE_LATE_AHEAD") || std::atoi(std::getenv("VPBS_DEVICE_LATE_AHEAD")) != 0;   // A-B switch
-        if (v->staged && v->dw_late && dev_ahead && s + 1 < steps) {
-            dev_hook.step = j;
-            dev_hook.queued = 0;
-            in.on_section = &DevHook::section;
-            in.on_section_user = &dev_hook;
-        }
-        rc = cyc.prove(in, caps, openings, fri);
-        if (rc != 0) {
-            if (ahead.active()) {   // the worker may be inside a stage of the next step's state
-                std::string ignored;
-                (void)ahead.drain(ignored);
-            }
-            return stop("step " + std::to_string(s) + ": " + vpbs_last_error(ctx), rc);
-        }
-        t_prove += now() - t;
-        c_prove += thread_cpu() - c0;
+    StepSource src;
+    src.waits = waits;
+    src.take = [&](unsigned j, Staged& step) {
+        const double tw = now();
+        std::unique_lock<std::mutex> lk(mu);
+        cv.wait(lk, [&] { return failed || (v->dw_late ? batches_run > j / B : staged > j); });
+        const double tw2 = now();
+        waits[0] += tw2 - tw;
+        cv.wait(lk, [&] { return failed || hashed > j; });   // its own public inputs are complete
+        waits[1] += now() - tw2;
+        if (failed) return false;
+        if (step.buf < 0) hand_over(j, step);
+        return true;
+    };
+    src.try_take = [&](unsigned j, Staged& step) {
+        std::lock_guard<std::mutex> lk(mu);
+        if (staged <= j) return false;
+        hand_over(j, step);
+        return true;
+    };
+    src.release = [&](unsigned j, const Staged&) {
         {
             std::lock_guard<std::mutex> lk(mu);
             consumed = j + 1;
         }
         cv.notify_all();
-        if (v->step_fn) v->step_fn(v->step_user, s + 1);
-        if (v->checkpoint(in, caps, openings, fri, s + 1, steps) != 0) return stop("checkpoint after step " + std::to_string(s) + ": the proof does not serialise", VPBS_ERR_INVALID);
-    }
-    hasher.join();
-    batcher.join();
-    stager.join();
-    const double seconds = now() - t0;
-    if (std::getenv("VPBS_TRACE_IVC"))
-        std::fprintf(stderr, "[ivc device witness] per step: waited %.2f ms for the staged wires, %.2f ms for the hash chain; late %.2f, scatter %.2f, "
-                     "prove %.2f, device batch run %.2f ms; CPU time of the proving thread: late %.2f, scatter %.2f, prove %.2f ms (blocking waits: %d)\n",
-                     1e3 * t_wait_staged / n_run, 1e3 * t_wait_hashed / n_run, 1e3 * t_late / n_run,
-                     1e3 * t_rows / n_run, 1e3 * t_prove / n_run, 1e3 * t_early / n_run, 1e3 * c_late / n_run, 1e3 * c_rows / n_run, 1e3 * c_prove / n_run,
-                     vpbs_host_blocking_sync());
-    const long n_bytes = vpbs_step_proof_to_bytes(ctx, &in, cyc.n_const_cols, caps, openings, fri, proof_out, capacity);
-    if (n_bytes <= 0) {
-        say("the output buffer is too small for the proof");
-        return VPBS_ERR_INVALID;
-    }
-    if (timing) {
-        timing->seconds = seconds;
-        timing->steps = n_run;
-        timing->base_proof_ms = 1e3 * t_base;
-        timing->late_witness_ms = 1e3 * t_late / n_run;
-        timing->late_rows_upload_ms = 1e3 * t_rows / n_run;
-        timing->prove_step_ms = 1e3 * t_prove / n_run;
-        timing->early_witness_ms = 1e3 * t_early / n_run;
-        timing->late_ahead_ms = 1e3 * ahead.busy_s / n_run;
-    }
-    return n_bytes;
+    };
+    src.arm_device_late = [&](unsigned j, vpbs_step_inputs& in) {
+        dev_hook.step = j;
+        dev_hook.queued = 0;
+        in.on_section = &DevHook::section;
+        in.on_section_user = &dev_hook;
+    };
+    return run.run(pis.data(), src);
 }
 
-// The host pipeline (the default): early phase on thread E, upload on thread U, late phase + proof on the caller.  from > 0
+// The host pipeline (the default): early phase on thread E, upload on thread U, late phase + proof in the loop (ChainRun).  from > 0
 // (vpbs_ivc_resume_pbs): no base proof; step `from` takes the checkpoint's proof words and public inputs.
-static long prove_pbs_host(vpbs_ivc* v, const uint64_t* testv, const uint64_t* ct, const uint64_t* bsk, const uint64_t* ksk, unsigned n_lwe,
-                           unsigned from, const u64* from_proof, const u64* from_pis, unsigned steps, uint8_t* proof_out, size_t capacity,
-                           vpbs_ivc_timing* timing, char* err, size_t err_len) {
-    auto say = [&](const std::string& m) {
-        if (err && err_len) {
-            std::strncpy(err, m.c_str(), err_len - 1);
-            err[err_len - 1] = 0;
-        }
-    };
+static long prove_pbs_host(const ChainArgs& a) {
+    ChainRun run(a);
+    vpbs_ivc* v = a.v;
     Side &cyc = v->cyc, &dum = v->dum;
-    vpbs_ctx* ctx = v->ctx;
-    const size_t kn = v->kn, n_pi = v->n_pi, proof_words = v->proof_words, ggsw_len = v->ggsw_len;
-    const unsigned n_run = steps - from;
-    const std::vector<u64> zero_ggsw(ggsw_len, 0);
-    auto ggsw_of = [&](unsigned s) { return s == 0 ? zero_ggsw.data() : (s <= n_lwe ? bsk + (size_t)(s - 1) * ggsw_len : ksk); };
-    auto mask_of = [&](unsigned s) { return s == 0 ? ct[n_lwe] : (s <= n_lwe ? ct[s - 1] : (u64)0); };
+    const size_t kn = v->kn, n_pi = v->n_pi;
+    std::mutex& mu = run.mu;
+    std::condition_variable& cv = run.cv;
+    std::atomic<bool>& failed = run.failed;
     // public inputs of the base proof: acc_init = (0, .., 0, testv) | counter 0 | accumulator 0 | hashes 0 | the cyclic circuit's verifier data
     std::vector<u64> base_pis(n_pi, 0);
-    std::memcpy(base_pis.data() + kn - v->N, testv, 8 * (size_t)v->N);
+    std::memcpy(base_pis.data() + kn - v->N, a.testv, 8 * (size_t)v->N);
     std::memcpy(base_pis.data() + n_pi - cyc.vk.size(), cyc.vk.data(), 8 * cyc.vk.size());
-
-    struct Ready {   // owns the early phase's state until run_late consumes it (a failure on the way must not leak tens of MB of slot values)
-        int buf = -1;
-        vpbs_witness_state* state = nullptr;
-        std::vector<u64> values, pis;
-        Ready() = default;
-        Ready(int b, std::vector<u64>&& v) : buf(b), values(std::move(v)) {}
-        Ready(Ready&& o) noexcept : buf(o.buf), state(o.state), values(std::move(o.values)), pis(std::move(o.pis)) { o.state = nullptr; }
-        Ready& operator=(Ready&& o) noexcept {
-            if (this != &o) {
-                drop();
-                buf = o.buf; state = o.state; values = std::move(o.values); pis = std::move(o.pis);
-                o.state = nullptr;
-            }
-            return *this;
-        }
-        Ready(const Ready&) = delete;
-        Ready& operator=(const Ready&) = delete;
-        void drop() {
-            if (state) vpbs_witness_state_free(state);
-            state = nullptr;
-        }
-        ~Ready() { drop(); }
-    };
-    std::mutex mu;
-    std::condition_variable cv;
     std::deque<int> free_bufs{0, 1, 2};
-    std::deque<Ready> generated, ready;   // early thread -> uploader -> caller
-    std::atomic<bool> failed{false};
-    std::string thread_err;
-    double t_early = 0;
-    auto fail = [&](const std::string& m) {
-        {   // the flag changes under the lock: a waiter that has just evaluated its predicate cannot miss the notification
-            std::lock_guard<std::mutex> lk(mu);
-            if (thread_err.empty()) thread_err = m;
-            failed = true;
-        }
-        cv.notify_all();
-    };
-    std::thread early([&] {
-        name_thread("vpbs-early");
-        std::vector<u64> pis_prev = from ? std::vector<u64>(from_pis, from_pis + n_pi) : base_pis;
+    std::deque<Staged> generated, ready;   // early thread -> uploader -> the loop; whatever nobody consumed is freed at the end
+    run.spawn("vpbs-early", [&] {
+        std::vector<u64> pis_prev = a.from ? std::vector<u64>(a.from_pis, a.from_pis + n_pi) : base_pis;
         char e2[256];
-        for (unsigned s = from; s < steps && !failed; ++s) {
-            int b;
+        for (unsigned s = a.from; s < a.steps && !failed; ++s) {
+            Staged r;
             {
                 std::unique_lock<std::mutex> lk(mu);
                 cv.wait(lk, [&] { return !free_bufs.empty() || failed; });
                 if (failed) return;
-                b = free_bufs.front();
+                r.buf = free_bufs.front();
                 free_bufs.pop_front();
             }
             const double t = now();
-            Ready r(b, std::vector<u64>(proof_words, 0));
-            r.values.reserve(cyc.n_preset);
-            r.values.insert(r.values.end(), pis_prev.begin(), pis_prev.end());
-            r.values.push_back(s == 0 ? 0 : 1);   // condition: false only in the base step
-            r.values.insert(r.values.end(), ggsw_of(s), ggsw_of(s) + ggsw_len);
-            r.values.push_back(mask_of(s));
-            r.values.insert(r.values.end(), cyc.vk.begin(), cyc.vk.end());
-            r.values.insert(r.values.end(), dum.vk.begin(), dum.vk.end());
-            r.values.insert(r.values.end(), v->dummy_proof.begin(), v->dummy_proof.end());
-            r.values.insert(r.values.end(), n_pi, 0);   // the dummy proof's public inputs
+            std::vector<u64>& vals = r.own_values;
+            vals.reserve(cyc.n_preset);
+            vals.assign(v->proof_words, 0);
+            vals.insert(vals.end(), pis_prev.begin(), pis_prev.end());
+            vals.push_back(s == 0 ? 0 : 1);   // condition: false only in the base step
+            vals.insert(vals.end(), run.ggsw_of(s), run.ggsw_of(s) + v->ggsw_len);
+            vals.push_back(run.mask_of(s));
+            vals.insert(vals.end(), cyc.vk.begin(), cyc.vk.end());
+            vals.insert(vals.end(), dum.vk.begin(), dum.vk.end());
+            vals.insert(vals.end(), v->dummy_proof.begin(), v->dummy_proof.end());
+            vals.insert(vals.end(), n_pi, 0);   // the dummy proof's public inputs
+            r.values = vals.data();
             // a matrix this plan has filled before only gets its value-carrying positions rewritten
-            const auto run_early = v->filled[b] ? vpbs_witness_plan_run_early_recycled : vpbs_witness_plan_run_early;
-            if (run_early(cyc.plan, r.values.data(), 0, v->bufs[b], &r.state, e2, sizeof e2) != 0)
-                return fail("early witness phase of step " + std::to_string(s) + ": " + e2);
-            v->filled[b] = true;
-            r.pis.resize(n_pi);
-            for (size_t i = 0; i < n_pi; ++i) r.pis[i] = v->bufs[b][cyc.pi_pos[i]];   // public inputs never depend on the inner proof's words
-            pis_prev = r.pis;
-            t_early += now() - t;
+            const auto run_early = v->filled[r.buf] ? vpbs_witness_plan_run_early_recycled : vpbs_witness_plan_run_early;
+            vpbs_witness_state* st = nullptr;
+            const int rc = run_early(cyc.plan, r.values, 0, v->bufs[r.buf], &st, e2, sizeof e2);
+            r.state.reset(st);
+            if (rc != 0) return run.fail("early witness phase of step " + std::to_string(s) + ": " + e2);
+            v->filled[r.buf] = true;
+            r.own_pis.resize(n_pi);
+            for (size_t i = 0; i < n_pi; ++i) r.own_pis[i] = v->bufs[r.buf][cyc.pi_pos[i]];   // public inputs never depend on the inner proof's words
+            r.pis = r.own_pis.data();
+            pis_prev = r.own_pis;
+            run.t_early += now() - t;
             {
                 std::lock_guard<std::mutex> lk(mu);
                 generated.push_back(std::move(r));
@@ -1089,10 +1145,9 @@ static long prove_pbs_host(vpbs_ivc* v, const uint64_t* testv, const uint64_t* c
             cv.notify_all();
         }
     });
-    std::thread uploader([&] {
-        name_thread("vpbs-upload");
-        for (unsigned s = from; s < steps; ++s) {
-            Ready r;
+    run.spawn("vpbs-upload", [&] {
+        for (unsigned s = a.from; s < a.steps; ++s) {
+            Staged r;
             {
                 std::unique_lock<std::mutex> lk(mu);
                 cv.wait(lk, [&] { return !generated.empty() || failed; });
@@ -1100,8 +1155,8 @@ static long prove_pbs_host(vpbs_ivc* v, const uint64_t* testv, const uint64_t* c
                 r = std::move(generated.front());
                 generated.pop_front();
             }
-            if (vpbs_device_upload_bg(ctx, v->d_bufs[r.buf], v->bufs[r.buf], v->wire_words) != 0)
-                return fail("upload of the early wires of step " + std::to_string(s));
+            if (vpbs_device_upload_bg(v->ctx, v->d_bufs[r.buf], v->bufs[r.buf], v->wire_words) != 0)
+                return run.fail("upload of the early wires of step " + std::to_string(s));
             {
                 std::lock_guard<std::mutex> lk(mu);
                 ready.push_back(std::move(r));
@@ -1109,177 +1164,45 @@ static long prove_pbs_host(vpbs_ivc* v, const uint64_t* testv, const uint64_t* c
             cv.notify_all();
         }
     });
-    auto stop = [&](const std::string& m, int rc) {
-        fail(m);
-        early.join();
-        uploader.join();
-        generated.clear();   // ~Ready frees the states nobody consumed
-        ready.clear();
-        std::string first;
+    auto take_ready = [&](Staged& step) {   // mu held, ready not empty
+        step = std::move(ready.front());
+        ready.pop_front();
+    };
+    StepSource src;
+    src.take = [&](unsigned, Staged& step) {
+        if (step.buf >= 0) return true;
+        std::unique_lock<std::mutex> lk(mu);
+        cv.wait(lk, [&] { return !ready.empty() || failed; });
+        if (failed) return false;
+        take_ready(step);
+        return true;
+    };
+    src.try_take = [&](unsigned, Staged& step) {
+        std::lock_guard<std::mutex> lk(mu);
+        if (ready.empty()) return false;   // its early phase is still running
+        take_ready(step);
+        return true;
+    };
+    src.release = [&](unsigned, const Staged& step) {
         {
             std::lock_guard<std::mutex> lk(mu);
-            first = thread_err;
-        }
-        say(first);
-        return (long)rc;
-    };
-
-    // cyclic_base_proof (:292-299): a proof of the dummy circuit carrying the initial accumulator and the cyclic verifier data
-    const double t0 = now();
-    char e[256] = {0};
-    vpbs_step_inputs in;
-    vpbs_step_sizes sz{};
-    if (!from && vpbs_witness_plan_run(dum.plan, base_pis.data(), 0, v->base_wires, e, sizeof e) != 0)
-        return stop(std::string("dummy witness: ") + e, VPBS_ERR_INVALID);
-    dum.step_inputs(in, v->base_wires, false, base_pis.data());
-    if (vpbs_step_sizes_get(ctx, &in, &sz) != 0 || 3 * sz.cap_words + sz.openings_words + sz.fri_words != proof_words)
-        return stop("the proof of this shape does not have the number of words the cyclic circuit expects", VPBS_ERR_INVALID);
-    std::vector<u64> proof(proof_words), pis;
-    u64 *caps = proof.data(), *openings = caps + 3 * sz.cap_words, *fri = openings + sz.openings_words;   // the flat order of the proof targets
-    int rc = VPBS_OK;
-    if (from) {
-        std::copy(from_proof, from_proof + proof_words, proof.begin());   // the checkpoint's proof is the inner proof of step `from`
-    } else {
-        rc = dum.prove(in, caps, openings, fri);
-        if (rc != 0) return stop(std::string("base proof: ") + vpbs_last_error(ctx), rc);
-    }
-    const double t_base = from ? 0.0 : now() - t0;
-    if (v->step_fn && !from) v->step_fn(v->step_user, 0);
-    double t_late = 0, t_rows = 0, t_prove = 0;
-    // the next step's late stages 1 and 2 run on a worker while this step's FRI stage is on the device (LateAhead): the prover reports its
-    // sections (on_section, on this thread); the first report that finds the next step's early phase finished and uploaded takes it
-    Ready next;   // declared before the worker: the worker is joined before the state it may be working on goes away
-    bool have_next = false;
-    LateAhead ahead;
-    if (v->staged) {
-        ahead.ranges = v->ahead_layout.ranges;
-        ahead.packed = v->late_vals;
-        ahead.start(cyc.plan);
-    }
-    struct Hook {
-        LateAhead* ahead;
-        std::mutex* mu;
-        std::deque<Ready>* ready;
-        Ready* next;
-        bool* have_next;
-        const u64* proof;
-        static void section(void* user, int sec) {
-            auto* h = static_cast<Hook*>(user);
-            if (!*h->have_next) {
-                std::lock_guard<std::mutex> lk(*h->mu);
-                if (h->ready->empty()) return;   // its early phase is still running: this step's late phase runs whole, after the proof
-                *h->next = std::move(h->ready->front());
-                h->ready->pop_front();
-                *h->have_next = true;
-                h->ahead->begin(h->next->state, h->next->values.data(), h->proof);
-            }
-            h->ahead->post((unsigned)sec);
-        }
-    } hook{&ahead, &mu, &ready, &next, &have_next, proof.data()};
-    // a rank of a SHARDED chain that cannot start a step's proof (its witness failed) takes part in that step's collectives on the failing
-    // side: the other ranks' proofs of the step return VPBS_ERR_PEER and the chain ends on every rank instead of hanging on the others
-    auto abandon_step = [&](int why) {
-        if (!cyc.comm) return;
-        vpbs_step_inputs shape;
-        cyc.step_inputs(shape, nullptr, true, nullptr);
-        (void)vpbs_prove_step_sharded_fail(ctx, &shape, cyc.comm, why);
-    };
-    for (unsigned s = from; s < steps; ++s) {
-        Ready r;
-        if (have_next) {
-            r = std::move(next);
-            have_next = false;
-        } else {
-            std::unique_lock<std::mutex> lk(mu);
-            cv.wait(lk, [&] { return !ready.empty() || failed; });
-            if (failed) {
-                lk.unlock();
-                abandon_step(VPBS_ERR_INVALID);
-                return stop("", VPBS_ERR_INVALID);
-            }
-            r = std::move(ready.front());
-            ready.pop_front();
-        }
-        double t = now();
-        if (ahead.active()) {   // stages that ran ahead on this step's state: wait for the last of them (usually long finished)
-            std::string msg;
-            if (!ahead.drain(msg)) {
-                abandon_step(VPBS_ERR_INVALID);
-                return stop("late witness phase of step " + std::to_string(s) + " (the previous proof does not verify in circuit): " + msg, VPBS_ERR_INVALID);
-            }
-        }
-        std::copy(proof.begin(), proof.end(), r.values.begin());
-        vpbs_witness_state* st = r.state;
-        r.state = nullptr;
-        rc = vpbs_witness_plan_run_late_packed(cyc.plan, st, r.values.data(), v->late_vals, e, sizeof e);   // consumes the state, also when it fails
-        if (rc != 0) {
-            abandon_step(rc);
-            return stop("late witness phase of step " + std::to_string(s) + " (the previous proof does not verify in circuit): " + e, rc);
-        }
-        t_late += now() - t;
-        t = now();
-        rc = vpbs::device_scatter(ctx, v->d_bufs[r.buf], v->d_late_pos, v->late_vals, v->late_count, v->d_late_stage, false);   // queued ahead of the proof (see the device pipeline's loop)
-        if (rc != 0) {
-            abandon_step(rc);
-            return stop(std::string("upload of the late wires: ") + vpbs_last_error(ctx), rc);
-        }
-        t_rows += now() - t;
-        t = now();
-        pis = std::move(r.pis);
-        cyc.step_inputs(in, v->d_bufs[r.buf], true, pis.data());
-        if (v->staged && s + 1 < steps) {
-            in.on_section = &Hook::section;
-            in.on_section_user = &hook;
-        }
-        rc = cyc.prove(in, caps, openings, fri);
-        if (rc != 0) {
-            if (ahead.active()) {   // the worker may be inside a stage of the next step's state: let it finish before that state is freed
-                std::string ignored;
-                (void)ahead.drain(ignored);
-            }
-            return stop("step " + std::to_string(s) + ": " + vpbs_last_error(ctx), rc);
-        }
-        t_prove += now() - t;
-        {
-            std::lock_guard<std::mutex> lk(mu);
-            free_bufs.push_back(r.buf);
+            free_bufs.push_back(step.buf);
         }
         cv.notify_all();
-        if (v->step_fn) v->step_fn(v->step_user, s + 1);
-        if (v->checkpoint(in, caps, openings, fri, s + 1, steps) != 0) return stop("checkpoint after step " + std::to_string(s) + ": the proof does not serialise", VPBS_ERR_INVALID);
-    }
-    early.join();
-    uploader.join();
-    const double seconds = now() - t0;
-    const long n_bytes = vpbs_step_proof_to_bytes(ctx, &in, cyc.n_const_cols, caps, openings, fri, proof_out, capacity);
-    if (n_bytes <= 0) {
-        say("the output buffer is too small for the proof");
-        return VPBS_ERR_INVALID;
-    }
-    if (timing) {
-        timing->seconds = seconds;
-        timing->steps = n_run;
-        timing->base_proof_ms = 1e3 * t_base;
-        timing->late_witness_ms = 1e3 * t_late / n_run;
-        timing->late_rows_upload_ms = 1e3 * t_rows / n_run;
-        timing->prove_step_ms = 1e3 * t_prove / n_run;
-        timing->early_witness_ms = 1e3 * t_early / n_run;
-        timing->late_ahead_ms = 1e3 * ahead.busy_s / n_run;
-    }
-    return n_bytes;
+    };
+    run.t0 = now();
+    return run.run(base_pis.data(), src);
 }
 
 long vpbs_ivc_prove_pbs(vpbs_ivc* v, const uint64_t* testv, const uint64_t* ct, const uint64_t* bsk, const uint64_t* ksk, unsigned n_lwe,
                         unsigned steps, uint8_t* proof_out, size_t capacity, vpbs_ivc_timing* timing, char* err, size_t err_len) {
-    if (err && err_len) err[0] = 0;
+    report(err, err_len, "");
     if (!v || !testv || !ct || !ksk || (n_lwe && !bsk) || !proof_out) {
-        if (err && err_len) std::snprintf(err, err_len, "%s", "malformed arguments");
+        report(err, err_len, "malformed arguments");
         return VPBS_ERR_INVALID;
     }
-    const unsigned total = n_lwe + 2;
-    if (steps == 0 || steps > total) steps = total;
-    if (v->dw_batch) return prove_pbs_device_witness(v, testv, ct, bsk, ksk, n_lwe, 0, nullptr, nullptr, steps, proof_out, capacity, timing, err, err_len);
-    return prove_pbs_host(v, testv, ct, bsk, ksk, n_lwe, 0, nullptr, nullptr, steps, proof_out, capacity, timing, err, err_len);
+    const ChainArgs a{v, testv, ct, bsk, ksk, n_lwe, 0, nullptr, nullptr, clamp_steps(steps, n_lwe), proof_out, capacity, timing, err, err_len};
+    return v->dw_batch ? prove_pbs_device_witness(a) : prove_pbs_host(a);
 }
 
 int vpbs_test_ivc_preset_matrix(size_t proof_words, size_t n_pi, size_t ggsw_len, size_t vk_words, unsigned n_lwe, unsigned first, unsigned count,
@@ -1308,12 +1231,7 @@ int vpbs_ivc_set_checkpoint(vpbs_ivc* v, unsigned every, vpbs_ivc_checkpoint_fn 
 long vpbs_ivc_resume_pbs(vpbs_ivc* v, const uint64_t* testv, const uint64_t* ct, const uint64_t* bsk, const uint64_t* ksk, unsigned n_lwe,
                          const uint8_t* checkpoint, size_t len, unsigned steps, uint8_t* proof_out, size_t capacity, vpbs_ivc_timing* timing,
                          char* err, size_t err_len) {
-    auto say = [&](const std::string& m) {
-        if (err && err_len) {
-            std::strncpy(err, m.c_str(), err_len - 1);
-            err[err_len - 1] = 0;
-        }
-    };
+    auto say = [&](const std::string& m) { report(err, err_len, m); };
     say("");
     if (!v || !testv || !ct || !ksk || (n_lwe && !bsk) || !proof_out || !checkpoint) {
         say("malformed arguments");
@@ -1334,8 +1252,7 @@ long vpbs_ivc_resume_pbs(vpbs_ivc* v, const uint64_t* testv, const uint64_t* ct,
     }
     const unsigned k = cp.k;
     std::vector<u64>&words = cp.proof, &pis = cp.pis;
-    const unsigned total = n_lwe + 2;
-    if (steps == 0 || steps > total) steps = total;
+    steps = clamp_steps(steps, n_lwe);
     if (steps < k) {
         say("checkpoint: its counter " + std::to_string(k) + " is beyond the requested " + std::to_string(steps) + " steps");
         return VPBS_ERR_INVALID;
@@ -1356,10 +1273,9 @@ long vpbs_ivc_resume_pbs(vpbs_ivc* v, const uint64_t* testv, const uint64_t* ct,
         if (n_bytes > 0) std::memcpy(proof_out, checkpoint, len);
         else say("the output buffer is too small for the proof");
         if (timing) *timing = vpbs_ivc_timing{};
-    } else if (v->dw_batch) {
-        n_bytes = prove_pbs_device_witness(v, testv, ct, bsk, ksk, n_lwe, k, words.data(), pis.data(), steps, proof_out, capacity, timing, err, err_len);
     } else {
-        n_bytes = prove_pbs_host(v, testv, ct, bsk, ksk, n_lwe, k, words.data(), pis.data(), steps, proof_out, capacity, timing, err, err_len);
+        const ChainArgs a{v, testv, ct, bsk, ksk, n_lwe, k, words.data(), pis.data(), steps, proof_out, capacity, timing, err, err_len};
+        n_bytes = v->dw_batch ? prove_pbs_device_witness(a) : prove_pbs_host(a);
     }
     key_chain.join();
     if (std::getenv("VPBS_TRACE_IVC"))
@@ -1435,20 +1351,19 @@ bool ivc_open_checkpoint(const vpbs_ivc* v, const uint64_t* testv, const uint64_
 long ivc_prove_pbs_resident(vpbs_ivc* v, const uint64_t* testv, const uint64_t* ct, unsigned n_lwe, const IvcResidentChain* chain, unsigned from,
                             const uint64_t* from_proof, const uint64_t* from_pis, unsigned steps, uint8_t* proof_out, size_t capacity,
                             vpbs_ivc_timing* timing, char* err, size_t err_len) {
-    if (err && err_len) err[0] = 0;
+    report(err, err_len, "");
     if (!v || !testv || !ct || !chain || !chain->accs || !chain->key_links || !chain->lwe_links || !chain->fill || !proof_out || !v->dw_batch ||
         v->dw_late || v->cyc.comm || (from && (!from_proof || !from_pis))) {
-        if (err && err_len) std::snprintf(err, err_len, "%s", "malformed arguments (a resident chain needs the device-witness pipeline with the late phase on the host)");
+        report(err, err_len, "malformed arguments (a resident chain needs the device-witness pipeline with the late phase on the host)");
         return VPBS_ERR_INVALID;
     }
-    const unsigned total = n_lwe + 2;
-    if (steps == 0 || steps > total) steps = total;
+    steps = clamp_steps(steps, n_lwe);
     if (from >= steps) {   // nothing to prove: the caller delivers the checkpoint itself
-        if (err && err_len) std::snprintf(err, err_len, "%s", "a resident chain from step `from` needs steps > from");
+        report(err, err_len, "a resident chain from step `from` needs steps > from");
         return VPBS_ERR_INVALID;
     }
     v->ckpt_base = from;
-    const long n = prove_pbs_device_witness(v, testv, ct, nullptr, nullptr, n_lwe, from, from_proof, from_pis, steps, proof_out, capacity, timing, err, err_len, chain);
+    const long n = prove_pbs_device_witness({v, testv, ct, nullptr, nullptr, n_lwe, from, from_proof, from_pis, steps, proof_out, capacity, timing, err, err_len}, chain);
     v->ckpt_base = 0;
     return n;
 }
