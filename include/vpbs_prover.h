@@ -1438,6 +1438,87 @@ int vpbs_aggregate_verifier_root(vpbs_aggregate_verifier* v, size_t count, const
                                  const uint64_t* cts, const uint64_t* out_cts, const uint64_t* key_hashes, size_t n_keys, const uint32_t* key_of,
                                  int on_device, uint64_t out[4], char* err, size_t err_len);
 void vpbs_aggregate_verifier_free(vpbs_aggregate_verifier* v);
+/* MANY aggregates in one device run.  A run of vpbs_aggregate_verifier_run is one latency-bound chain of n_lwe + 2 links
+ * and then ceil((2 K N + 77) / 8) sponge blocks on a 16-lane group, whatever the leaf count: the chain depends on neither the number of
+ * leaves nor the number of trees, so many aggregates fit in the time of one.
+ * create_many: vpbs_aggregate_verifier_create whose per-level proof verifiers take batches of max_aggregates (1 .. 2^16); create is the
+ *   case max_aggregates = 1, and run / root work on such an object as before.
+ * run_many: aggregate a is bytes[offsets[a] .. offsets[a + 1]) and its tree owns the leaves leaf_first[a] .. leaf_first[a + 1] of the per-leaf
+ *   arrays (leaf_first [n_agg + 1], a HOST array, starts at 0 and increases); testv_of and key_of are per leaf and HOST arrays, the word arrays
+ *   device pointers when on_device != 0, as in run.  Aggregate a gets in verdicts[a] / reasons[a] (reasons may be NULL) exactly the verdict
+ *   and reason vpbs_verify_aggregate gives it on its slice of the statement.  Returns the number accepted.  Stages, on the context's stream:
+ *   one leaf-pair launch over all leaves (one leaf per two 16-lane groups of a wave: one walks the LWE chain while the other absorbs the
+ *   public-input blocks that hold no LWE-hash word, then takes the chain's end through LDS), one segmented fold launch per level over the
+ *   trees that have that level, per depth present ONE batch of root proofs through that level's proof verifier and a result kernel, one
+ *   lane per aggregate; the raw-word flag is per tree; the host waits once.
+ * roots_many: the statement stages alone: out [n_agg][4] and raw_bad [n_agg], 1 where a raw word of the tree's statement is at or above p
+ *   (its root is then meaningless).  VPBS_OK or < 0.
+ * Refused by name (VPBS_ERR_INVALID, err) before anything is queued: n_agg = 0 or above max_aggregates, an empty tree, a tree above
+ *   2^levels leaves, a leaf count, n_testv or n_keys above max_leaves, offsets that decrease, an index at or above n_testv / n_keys. */
+int vpbs_aggregate_verifier_create_many(vpbs_ctx* ctx, const vpbs_aggregate_shape* shape, size_t max_leaves, size_t max_aggregates,
+                                        vpbs_aggregate_verifier** out, char* err, size_t err_len);
+long vpbs_aggregate_verifier_run_many(vpbs_aggregate_verifier* v, const uint8_t* bytes, const size_t* offsets /* [n_agg + 1] */, size_t n_agg,
+                                      const size_t* leaf_first /* [n_agg + 1], HOST */, const uint64_t* testvs, size_t n_testv,
+                                      const uint32_t* testv_of, const uint64_t* cts, const uint64_t* out_cts, const uint64_t* key_hashes,
+                                      size_t n_keys, const uint32_t* key_of, int on_device, uint8_t* verdicts /* [n_agg] */,
+                                      uint8_t* reasons /* [n_agg] or NULL */, char* err, size_t err_len);
+int vpbs_aggregate_verifier_roots_many(vpbs_aggregate_verifier* v, size_t n_agg, const size_t* leaf_first /* [n_agg + 1], HOST */,
+                                       const uint64_t* testvs, size_t n_testv, const uint32_t* testv_of, const uint64_t* cts,
+                                       const uint64_t* out_cts, const uint64_t* key_hashes, size_t n_keys, const uint32_t* key_of, int on_device,
+                                       uint64_t* out /* [n_agg][4] */, uint8_t* raw_bad /* [n_agg] */, char* err, size_t err_len);
+
+/* ---- one proof per program instance: the gates of a program as the leaves of ONE aggregate (csrc/program.hip) ----
+ * Statement.  A program instance has inputs [n_inputs][n_lwe + 1], testvs [n_luts][N], the claimed outputs out_cts [n_gates][K][N] and one
+ * key hash.  Its aggregate has one leaf per gate, in gate order: leaf g is the vPBS statement (testvs[gate_lut[g]], c_g, out_cts[g], the key
+ * hash), where c_g is what vpbs_program_verify recomputes -- the wire table is the inputs followed by the extraction at coefficient j of
+ * every claimed output (vpbs_lwe_extract for plain gates, vpbs_lwe_extract_at per output wire of a multi-output gate), then the gate's
+ * combination (canonical on read, canonical products and sums, the constant in the body word only) and the snap of its log_slots.  Tree,
+ * padding and root are vpbs_aggregate_root's; n_gates is at most 2^levels.  Circuits, provers and the proof format are unchanged.
+ * Host, no device needed (a host-only program will do):
+ *   gate_inputs: cts_out [instances][n_gates][n_lwe + 1], word for word what the device path of verify / verify_batch combines.  Refused
+ *     with a message in err: N no power of two or n_lwe outside 1 .. (K - 1) N, a gate whose 2^gate_log_slots exceeds N, null pointers.
+ *   aggregate_root: vpbs_aggregate_root over those c_g with testv_of = gate_lut; the same return values (1: a raw word at or above p).
+ *   verify_aggregate: the client's check without a GPU: vpbs_verify_aggregate on that statement; 1 / 0 / < 0, its reasons in its order.
+ * Prover (compositions; the bytes are exactly the composition's):
+ *   prove_aggregate: vpbs_program_prove with steps = 0, then vpbs_aggregator_run over the proofs in gate order -> the aggregate in out
+ *     (capacity bytes); returns its length.  proof_fn (may be NULL) still sees every gate's proof; stats may be NULL.
+ *   prove_aggregate_batch: vpbs_program_prove_batch, then ONE aggregate PER INSTANCE, delivered through agg_fn in instance order: aggregate b
+ *     is byte for byte what prove_aggregate gives on a vpbs_pbs_prover of the key set in slot key_of[b].  Returns the number delivered.
+ *   Both refuse, before anything is proven and without calling a callback, a program of more than 2^levels gates of the aggregator (the
+ *   message names n_gates and 2^levels) or of none, and whatever prove / prove_batch refuse.  A gate whose chain fails ends the call with
+ *   that gate named; nothing is aggregated then.  Aggregation runs after the last proof.
+ * Device verifier:
+ *   verify_aggregate_batch: `instances` program instances, instance b under key_hashes[key_of[b]] with aggregate bytes[offsets[b] ..
+ *     offsets[b + 1]), on an aggregate verifier made with create_many.  The claimed outputs of all instances are extracted in one launch and
+ *     the gate inputs of all instances combined in one launch (the kernels of verify_batch); the tables go to run_many where they lie, as
+ *     device pointers, with testv_of = gate_lut per instance and the instance's key index per row: no gate input is downloaded.  Chunked
+ *     by the verifier's max_aggregates / max_leaves, one wait per chunk.  verdicts[b] / reasons[b] are exactly what the host's
+ *     verify_aggregate gives instance b with key_hashes[key_of[b]].  Returns the number accepted. */
+typedef void (*vpbs_aggregate_fn)(size_t instance, const uint8_t* bytes, size_t len, void* user);
+int vpbs_program_gate_inputs(const vpbs_program* prog, unsigned N, unsigned K, unsigned n_lwe, const uint64_t* inputs /* [instances][n_inputs][n_lwe + 1] */,
+                             size_t instances, const uint64_t* out_cts /* [instances][n_gates][K][N] */,
+                             uint64_t* cts_out /* [instances][n_gates][n_lwe + 1] */, char* err, size_t err_len);
+int vpbs_program_aggregate_root(const vpbs_program* prog, unsigned N, unsigned K, unsigned n_lwe, const uint64_t* vk0 /* [68] */,
+                                const uint64_t* inputs, const uint64_t* testvs, const uint64_t* out_cts, const uint64_t* key_hash /* [4] */,
+                                uint64_t out[4], char* err, size_t err_len);
+int vpbs_program_verify_aggregate(const vpbs_program* prog, const vpbs_aggregate_shape* shape, const uint64_t* inputs, const uint64_t* testvs,
+                                  const uint64_t* out_cts, const uint64_t* key_hash /* [4] */, const uint8_t* bytes, size_t len, int* reason,
+                                  char* why, size_t why_len);
+long vpbs_program_prove_aggregate(vpbs_program* prog, vpbs_pbs_prover* pbs_prover, vpbs_aggregator* aggregator, const uint64_t* inputs,
+                                  const uint64_t* testvs, uint64_t* wires_out, uint64_t* out_cts, uint8_t* out, size_t capacity,
+                                  vpbs_aggregate_stats* stats, vpbs_pbs_proof_fn proof_fn /* may be NULL */, void* user, char* err, size_t err_len);
+long vpbs_program_prove_aggregate_batch(vpbs_program* prog, vpbs_ring_prover* ring_prover, vpbs_aggregator* aggregator,
+                                        const uint64_t* inputs /* [instances][n_inputs][n_lwe + 1] */, size_t instances,
+                                        const uint32_t* key_of /* [instances], HOST array */, const uint64_t* testvs, uint64_t* wires_out,
+                                        uint64_t* out_cts, vpbs_aggregate_fn agg_fn, vpbs_pbs_proof_fn proof_fn /* may be NULL */, void* user,
+                                        char* err, size_t err_len);
+long vpbs_program_verify_aggregate_batch(vpbs_program* prog, vpbs_aggregate_verifier* agg_verifier,
+                                         const uint64_t* inputs /* [instances][n_inputs][n_lwe + 1] */, size_t instances,
+                                         const uint32_t* key_of /* [instances], HOST array */, const uint64_t* key_hashes /* [n_keys][4] */,
+                                         size_t n_keys, const uint64_t* testvs /* [n_luts][N] */,
+                                         const uint64_t* out_cts /* [instances][n_gates][K][N] */, const uint8_t* bytes,
+                                         const size_t* offsets /* [instances + 1] */, uint8_t* verdicts /* [instances] */,
+                                         uint8_t* reasons /* [instances] or NULL */, char* err, size_t err_len);
 
 /* ---- memory helpers for hosts that do not link the HIP runtime themselves (a Rust or plain C++ caller) ----
  * pinned host memory (hipHostMalloc): witness matrices written there reach the device at PCIe speed (70.8 MB in 1.3 ms instead of ~15 ms

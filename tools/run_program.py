@@ -5,7 +5,12 @@ user had to before api.Program existed (the baseline leg: Bootstrapper.run per l
 compared wire by wire.  One JSON line.
 
 usage: tools/run_program.py [--levels L] [--width W] [--fan-in F] [--program FILE.json] [--n8] [--prove] [--baseline] [--runs R] [--seed S]
-                            [--instances B --keys M [--verify-per-instance]] [--multi THETA]
+                            [--instances B --keys M [--verify-per-instance]] [--multi THETA] [--aggregate]
+  --aggregate (with --prove, alone or with --instances B --keys M): ONE proof per program instance.  The gate proofs of
+    every instance are folded by an api.Aggregator (api.Program.prove_aggregate / prove_aggregate_batch; the level circuits are located as
+    data: tools/export_circuits.py --aggregate N K ELL LOGB n_lwe log_n levels makes them, and the program may have at most 2^levels gates);
+    every aggregate is verified on the host (api.program_verify_aggregate, the client's check) and all of them in one device run
+    (api.Program.verify_aggregate_batch); the JSON line gains "aggregate": bytes, depth, both verdict lists and the bytes a client receives.
   --multi THETA: multi-output lookup gates.  W inputs, L layers of W lookups of 2^THETA tables over {0, 1} each; a later
     lookup reads every output of the one before it.  The multi leg makes ONE gate of each lookup (api.Program 5-tuples, api.lut_testv_multi);
     the single leg makes one gate per table of the same functions on the same inputs -- a plain program that runs unchanged on a build
@@ -141,6 +146,34 @@ def run_baseline(ctx, bs, n_inputs, gates, lv, inputs, testvs):
     return wires, event_ms
 
 
+def aggregate_setup(ctx, prog, N, n_lwe, log_n, cyc, vk, max_aggregates):
+    """--aggregate: the Aggregator over the level circuits the program's gate count needs (located as data: tools/export_circuits.py
+    --aggregate makes them), the verifiers' shape and the device verifier -> (aggregator, shape, device verifier)"""
+    depth = api.aggregate_depth(max(prog.n_gates, 1))
+    levels = [circuit_file.load(p) for p in circuit_file.find_aggregate_circuits(N, K, ELL, LOGB, n_lwe, log_n, depth)]
+    agg = api.Aggregator(ctx, cyc, vk, levels)
+    shape = api.AggregateShape(N, K, n_lwe, agg.verifier_data(), levels)
+    return agg, shape, api.AggregateVerifier(ctx, shape, max_leaves=max_aggregates * prog.n_gates, max_aggregates=max_aggregates)
+
+
+def aggregate_report(prog, shape, av, blobs, inputs, key_of, hashes, testvs, out_cts, proof_bytes, seconds):
+    """every instance's aggregate on the host (api.program_verify_aggregate, the client's check) and all of them in one device run
+    (Program.verify_aggregate_batch) -> the "aggregate" entry of the JSON line; bytes a client receives either way"""
+    t = time.perf_counter()
+    host = [api.program_verify_aggregate(prog, shape, blobs[b], inputs[b], testvs, out_cts[b], hashes[key_of[b]]) for b in range(len(blobs))]
+    t_host = time.perf_counter() - t
+    t = time.perf_counter()
+    verdicts, reasons = prog.verify_aggregate_batch(av, inputs, key_of, np.stack(hashes), testvs, out_cts, blobs)
+    t_device = time.perf_counter() - t
+    device = [(bool(v), int(r)) for v, r in zip(verdicts, reasons)]
+    outputs = out_cts[0].nbytes
+    return {"instances": len(blobs), "gates": prog.n_gates, "depth": api.aggregate_depth(prog.n_gates), "bytes": [len(b) for b in blobs],
+            "prove_and_aggregate_seconds": seconds, "verify_host_ms": 1e3 * t_host, "verify_device_ms": 1e3 * t_device,
+            "host": [[ok, api.aggregate_reason_text(r)] for ok, r in host], "device": [[ok, api.aggregate_reason_text(r)] for ok, r in device],
+            "client_bytes_aggregate": len(blobs[0]) + outputs, "client_bytes_per_gate_proofs": proof_bytes + outputs,
+            "accepted": bool(all(ok for ok, _ in host) and device == [(ok, r) for ok, r in host])}
+
+
 def prove_batch(args, ctx, prog, N, n_lwe, log_n, M, inputs, key_of, testvs, batch_wires, out):
     """--instances B --keys M --prove: Program.prove_batch on a RingProver, Program.verify_batch on a RingVerifier -> (the proven wires, all
     accepted)"""
@@ -157,6 +190,17 @@ def prove_batch(args, ctx, prog, N, n_lwe, log_n, M, inputs, key_of, testvs, bat
     proofs, wires, out_cts = prog.prove_batch(rp, inputs, key_of, testvs)
     out["prove_seconds"] = time.perf_counter() - t
     hashes, (vk, _) = [rp.key_hash(k) for k in range(M)], rp.verifier_data()
+    aggregated = True
+    if args.aggregate:   # one aggregate per instance: proven again, now folded, and checked on the host and on the device
+        agg, ashape, av = aggregate_setup(ctx, prog, N, n_lwe, log_n, cyc, vk, max(1, min(len(key_of), 64)))
+        t = time.perf_counter()
+        blobs, _, agg_out = prog.prove_aggregate_batch(rp, agg, inputs, key_of, testvs)
+        out["aggregate"] = aggregate_report(prog, ashape, av, blobs, inputs, key_of, hashes, testvs, agg_out, sum(len(p) for p in proofs[0]),
+                                            time.perf_counter() - t)
+        out["aggregate"]["out_cts_equal"] = bool((agg_out == out_cts).all())
+        aggregated = out["aggregate"]["accepted"] and out["aggregate"]["out_cts_equal"]
+        av.close()
+        agg.close()
     rp.close()
     n_gates = prog.n_gates
     shape = (ctx, vk[4:].reshape(-1, 4), [cyc.n_constants + 80, 135, 20, 16], vk[:4], log_n, cyc.n_constants, 80, cyc.gates, N, K, n_lwe, K * ELL * K * N)
@@ -179,7 +223,7 @@ def prove_batch(args, ctx, prog, N, n_lwe, log_n, M, inputs, key_of, testvs, bat
             pv.close()
         out["verify_per_instance_equal"] = bool(all((e[0] == verdicts[b]).all() and (e[1] == reasons[b]).all() for b, e in enumerate(each)))
     out["verified"], out["rejected_because"] = verified, sorted(why)
-    out["proven"] = verified == len(key_of) * n_gates
+    out["proven"] = verified == len(key_of) * n_gates and aggregated
     out["proven_wires_equal"] = bool((wires == batch_wires).all())
     return wires, out["proven"] and out["proven_wires_equal"]
 
@@ -491,7 +535,10 @@ def main():
     ap.add_argument("--keys", type=int, default=1)
     ap.add_argument("--verify-per-instance", action="store_true")
     ap.add_argument("--multi", type=int)
+    ap.add_argument("--aggregate", action="store_true")
     args = ap.parse_args()
+    if args.aggregate and (not args.prove or args.multi is not None):
+        raise SystemExit("--aggregate folds the gate proofs of --prove into one proof per instance: it needs --prove and cannot run with --multi")
     if args.multi is not None:
         if args.baseline or args.program:
             raise SystemExit("--multi builds its own netlist and both legs: it cannot run with --baseline or --program")
@@ -566,6 +613,17 @@ def main():
             proofs, p_wires, out_cts = prog.prove(prover, inputs, testvs)
             out["prove_seconds"] = time.perf_counter() - t
             kh, (vk, _) = prover.key_hash(), prover.verifier_data()
+            aggregated = True
+            if args.aggregate:
+                agg, ashape, av = aggregate_setup(ctx, prog, N, n_lwe, log_n, cyc, vk, 1)
+                t = time.perf_counter()
+                blob, _, agg_out = prog.prove_aggregate(prover, agg, inputs, testvs)
+                out["aggregate"] = aggregate_report(prog, ashape, av, [blob], inputs[None], [0], [kh], testvs, agg_out[None], sum(len(p) for p in proofs),
+                                                    time.perf_counter() - t)
+                out["aggregate"]["out_cts_equal"] = bool((agg_out == out_cts).all())
+                aggregated = out["aggregate"]["accepted"] and out["aggregate"]["out_cts_equal"]
+                av.close()
+                agg.close()
             prover.close()
             pv = api.PbsVerifier(ctx, vk[4:].reshape(-1, 4), [cyc.n_constants + 80, 135, 20, 16], vk[:4], log_n, cyc.n_constants, 80, cyc.gates, N, K,
                                  n_lwe, K * ELL * K * N, kh, max_batch=max(1, min(n_gates, 64)))
@@ -574,7 +632,7 @@ def main():
             out["verify_seconds"] = time.perf_counter() - t
             pv.close()
             out["verified"] = int(verdicts.sum())
-            out["proven"] = out["verified"] == n_gates
+            out["proven"] = out["verified"] == n_gates and aggregated
             out["rejected_because"] = sorted({api.pbs_reason_text(int(r)) for v, r in zip(verdicts, reasons) if not v})
             out["all_equal"] = bool(out["all_equal"] and (p_wires == base_wires).all())
             ok = out["all_equal"] and out["proven"]

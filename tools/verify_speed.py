@@ -9,7 +9,12 @@ api.RingVerifier run of B proofs; M api.PbsVerifier objects of B / M proofs each
 five times in turn with the host leg, while only its own verifier objects exist.  All M
 slots hold the SAME key hash (one key set is generated): fine for timing, because no stage of the verifier exits early and the table is
 read by index either way -- the output says so.  --baseline: without the RingVerifier leg; the rest needs nothing newer than
-api.PbsVerifier, so this file can be copied into a build of an older commit and time that."""
+api.PbsVerifier, so this file can be copied into a build of an older commit and time that.
+--aggregate --batch B[,B2,..] [--n8]: MANY aggregates in one device run.  Eight vPBS proofs are made and folded into one
+real aggregate, which is replicated B times (the verifier does not deduplicate): ONE api.AggregateVerifier.verify_many of B aggregates
+against B single device runs (AggregateVerifier.verify) and against B api.verify_aggregate calls over 16 host threads, the three legs in
+turn, five times after a warm-up; one JSON line per B.  The level circuits are located as data (tools/export_circuits.py --aggregate);
+--n8: the N = 8, n = 6 miniature.  Nothing else of this file runs in this mode."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch, vpbs_amd
@@ -20,6 +25,62 @@ device_mode = "--device" in args
 batches = [int(b) for b in args[args.index("--batch") + 1].split(",")] if "--batch" in args else [1]   # --pbs: several, one line each
 batch = batches[0]
 keys_m = int(args[args.index("--keys") + 1]) if "--keys" in args else 0
+
+
+def aggregate_batches():
+    """--aggregate: see the module text"""
+    import json
+    from concurrent.futures import ThreadPoolExecutor
+    from vpbs_amd import circuit_file
+    K, ELL, LOGB, leaves, n8 = 2, 4, 5, 8, "--n8" in args
+    N, n_lwe, deg = (8, 6, 13) if n8 else (1024, 728, 16)
+    c = vpbs_amd.Context(0, log_n_max=16)
+    cyc, dum = (circuit_file.load(p) for p in circuit_file.find_cyclic_circuit(N, K, ELL, LOGB, n_lwe, deg))
+    levels = [circuit_file.load(p) for p in circuit_file.find_aggregate_circuits(N, K, ELL, LOGB, n_lwe, deg, 3)]
+    keys = c.keygen(N, K, ELL, LOGB, n_lwe, 0x5EED0728, 4.99027217501041e-8, 1.17021618159313e-5)
+    prover = api.PbsProver(0, cyc, dum, keys["bsk"], keys["ksk"], K, ELL, LOGB, chains=2 if n8 else 8, witness_batch=3 if n8 else 64)
+    tv, delta = api.testv(N, 2)
+    cts = np.stack([api.lwe_encrypt(keys["params"], keys["s_lwe"], delta * (i % 2) % api.P, nonce=i) for i in range(leaves)])
+    proofs, out_ct, _ = prover.prove(cts, tv)
+    kh, (vk0, _) = prover.key_hash(), prover.verifier_data()
+    prover.close()
+    agg = api.Aggregator(c, cyc, vk0, levels)
+    blob = agg.aggregate(proofs)
+    shape = api.AggregateShape(N, K, n_lwe, agg.verifier_data(), levels)
+    agg.close()
+    out_ct = out_ct.reshape(leaves, K * N)
+    one = (tv, cts, out_ct, kh)
+    spread = lambda ms: {"median": sorted(ms)[len(ms) // 2], "min": min(ms), "max": max(ms)}
+    with ThreadPoolExecutor(max_workers=16) as pool:
+        for B in batches:
+            av = api.AggregateVerifier(c, shape, max_leaves=B * leaves, max_aggregates=B)
+            many = (tv, np.tile(cts, (B, 1)), np.tile(out_ct, (B, 1)), kh)
+            host_one = lambda _: api.verify_aggregate(shape, blob, leaves, *one)
+            verdicts, _ = av.verify_many([blob] * B, [leaves] * B, *many)          # and the warm-up of all three legs
+            assert verdicts.all() and av.verify(blob, leaves, *one) == (True, api.AGG_OK) and all(ok for ok, _ in pool.map(host_one, range(B)))
+            ms = {"many": [], "single": [], "host": []}
+            for _ in range(5):
+                t = time.perf_counter()
+                av.verify_many([blob] * B, [leaves] * B, *many)
+                ms["many"].append(1e3 * (time.perf_counter() - t))
+                t = time.perf_counter()
+                for _ in range(B):
+                    av.verify(blob, leaves, *one)
+                ms["single"].append(1e3 * (time.perf_counter() - t))
+                t = time.perf_counter()
+                list(pool.map(host_one, range(B)))
+                ms["host"].append(1e3 * (time.perf_counter() - t))
+            av.close()
+            print(json.dumps({"what": "B copies of one real aggregate of 8 leaves, N=%d n=%d: one verify_many against B single device runs and B "
+                                      "host verifications on 16 threads" % (N, n_lwe), "batch": B, "aggregate_bytes": len(blob),
+                              "leaf_bytes_total": sum(len(p) for p in proofs), "verify_many_ms": spread(ms["many"]),
+                              "single_runs_ms": spread(ms["single"]), "host_16_threads_ms": spread(ms["host"])}))
+    c.close()
+
+
+if "--aggregate" in args:
+    aggregate_batches()
+    sys.exit(0)
 log_n = 15
 ctx = vpbs_amd.Context(0, log_n_max=16)
 gates = api.GateSet(bench.GATES)

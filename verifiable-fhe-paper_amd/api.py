@@ -170,6 +170,7 @@ ALLGATHER_DEV_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_size_t)
 IVC_STEP_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_uint)
 IVC_CHECKPOINT_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_uint, C.POINTER(C.c_uint8), C.c_size_t)
 PBS_PROOF_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint8), C.c_size_t, C.c_char_p)
+AGGREGATE_FN = C.CFUNCTYPE(None, C.c_size_t, C.POINTER(C.c_uint8), C.c_size_t, C.c_void_p)   # vpbs_aggregate_fn
 PBS_CHECKPOINT_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_size_t, C.c_uint, C.POINTER(C.c_uint8), C.c_size_t)
 
 
@@ -411,6 +412,20 @@ SIGNATURES = {
                                          C.c_char_p, _sz]),
     "vpbs_aggregate_verifier_root": (_i, [_vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _sz, _vp, _i, U64P, C.c_char_p, _sz]),
     "vpbs_aggregate_verifier_free": (None, [_vp]),
+    "vpbs_aggregate_verifier_create_many": (_i, [_vp, _vp, _sz, _sz, C.POINTER(_vp), C.c_char_p, _sz]),
+    "vpbs_aggregate_verifier_run_many": (C.c_long, [_vp, C.POINTER(C.c_uint8), C.POINTER(_sz), _sz, C.POINTER(_sz), _vp, _sz, _vp, _vp, _vp, _vp, _sz,
+                                                    _vp, _i, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.c_char_p, _sz]),
+    "vpbs_aggregate_verifier_roots_many": (_i, [_vp, _sz, C.POINTER(_sz), _vp, _sz, _vp, _vp, _vp, _vp, _sz, _vp, _i, U64P, C.POINTER(C.c_uint8),
+                                                C.c_char_p, _sz]),
+    "vpbs_program_gate_inputs": (_i, [_vp, _ui, _ui, _ui, U64P, _sz, U64P, U64P, C.c_char_p, _sz]),
+    "vpbs_program_aggregate_root": (_i, [_vp, _ui, _ui, _ui, U64P, U64P, U64P, U64P, U64P, U64P, C.c_char_p, _sz]),
+    "vpbs_program_verify_aggregate": (_i, [_vp, _vp, U64P, U64P, U64P, U64P, C.POINTER(C.c_uint8), _sz, C.POINTER(_i), C.c_char_p, _sz]),
+    "vpbs_program_prove_aggregate": (C.c_long, [_vp, _vp, _vp, U64P, U64P, U64P, U64P, C.POINTER(C.c_uint8), _sz, _vp, PBS_PROOF_FN, _vp, C.c_char_p,
+                                                _sz]),
+    "vpbs_program_prove_aggregate_batch": (C.c_long, [_vp, _vp, _vp, U64P, _sz, _vp, U64P, U64P, U64P, AGGREGATE_FN, PBS_PROOF_FN, _vp, C.c_char_p,
+                                                      _sz]),
+    "vpbs_program_verify_aggregate_batch": (C.c_long, [_vp, _vp, U64P, _sz, _vp, U64P, _sz, U64P, U64P, C.POINTER(C.c_uint8), C.POINTER(_sz),
+                                                       C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.c_char_p, _sz]),
 }
 
 # test entries (csrc/test_entries.h): exported for the suite, not part of the C ABI
@@ -2503,6 +2518,100 @@ def verify_aggregate(shape, blob, count, testvs, cts, out_cts, key_hashes, key_o
     return rc == 1, int(reason.value)
 
 
+# ---- one proof per program instance: the gates of a program as the leaves of one aggregate (csrc/program.hip) ----
+def program_aggregate_args(who, n_inputs, n_gates, n_luts, N, K, n_lwe, inputs, out_cts, testvs=None, key_hash=None, instances=None):
+    """shapes of a program statement, checked without a device: inputs [n_inputs][n + 1] and out_cts [n_gates][K][N] -- with a leading
+    instance axis when `instances` is not None (True: taken from inputs) -- testvs [n_luts][N] and key_hash [4] where given
+    -> (inputs, out_cts, testvs or None, key_hash or None), contiguous uint64"""
+    x, o = _u64(inputs), _u64(out_cts)
+    lead = () if instances is None else (x.shape[0] if instances is True and x.ndim == 3 else instances,)
+    if x.shape != lead + (n_inputs, n_lwe + 1):
+        raise ValueError("%s: expected inputs %s, got shape %s" % (who, "".join("[%d]" % d for d in lead + (n_inputs, n_lwe + 1)), x.shape))
+    if o.size != int(np.prod(lead + (n_gates, K, N))) or (instances is not None and o.shape[:1] != lead):
+        raise ValueError("%s: expected out_cts %s, got shape %s" % (who, "".join("[%d]" % d for d in lead + (n_gates, K, N)), o.shape))
+    tv = kh = None
+    if testvs is not None:
+        tv = _u64(testvs)
+        if tv.shape != (n_luts, N):
+            raise ValueError("%s: expected testvs [%d][%d], got shape %s" % (who, n_luts, N, tv.shape))
+    if key_hash is not None:
+        kh = _u64(key_hash).reshape(-1)
+        if kh.size != 4:
+            raise ValueError("%s: a key hash is 4 words, got %d" % (who, kh.size))
+    c = np.ascontiguousarray
+    return c(x), c(o.reshape(lead + (n_gates, K * N))), None if tv is None else c(tv), None if kh is None else c(kh)
+
+
+def _keep_ptr(a):
+    return _ptr(a if a.size else np.zeros(1, np.uint64))
+
+
+def program_gate_inputs(prog, N, K, n_lwe, inputs, out_cts):
+    """vpbs_program_gate_inputs (host; a host-only Program will do): the gate inputs c_g a verifier recomputes from the program inputs and the
+    CLAIMED outputs -- the extraction of every claimed output, the gate's combination, its snap -> [n_gates][n + 1], or
+    [instances][n_gates][n + 1] for inputs [instances][n_inputs][n + 1] and out_cts [instances][n_gates][K][N]"""
+    batched = _u64(inputs).ndim == 3
+    x, o, _, _ = program_aggregate_args("program_gate_inputs", prog.n_inputs, prog.n_gates, prog.n_luts, N, K, n_lwe, inputs, out_cts,
+                                        instances=True if batched else None)
+    B = x.shape[0] if batched else 1
+    out = np.zeros(((B,) if batched else ()) + (prog.n_gates, n_lwe + 1), np.uint64)
+    err = C.create_string_buffer(512)
+    rc = lib().vpbs_program_gate_inputs(prog.h, N, K, n_lwe, _keep_ptr(x.reshape(-1)), B, _keep_ptr(o.reshape(-1)), _keep_ptr(out.reshape(-1)), err, 512)
+    if rc:
+        raise VpbsError("status %d: %s" % (rc, err.value.decode()))
+    return out
+
+
+def program_aggregate_root(prog, N, K, n_lwe, vk0, inputs, testvs, out_cts, key_hash):
+    """vpbs_program_aggregate_root (host): the root of the aggregate of one program instance -- one leaf per gate, in gate order: leaf g is
+    (testvs[gate_lut[g]], c_g of program_gate_inputs, out_cts[g], key_hash) -> [4]; aggregate_root's errors"""
+    x, o, tv, kh = program_aggregate_args("program_aggregate_root", prog.n_inputs, prog.n_gates, prog.n_luts, N, K, n_lwe, inputs, out_cts, testvs,
+                                          key_hash)
+    vk = _u64(vk0).reshape(-1)
+    if vk.size != AGG_VK_WORDS:
+        raise ValueError("program_aggregate_root: vk0 is 68 words (digest, cap), got %d" % vk.size)
+    out, err = np.zeros(4, np.uint64), C.create_string_buffer(512)
+    rc = lib().vpbs_program_aggregate_root(prog.h, N, K, n_lwe, _ptr(vk), _keep_ptr(x.reshape(-1)), _keep_ptr(tv.reshape(-1)), _keep_ptr(o.reshape(-1)),
+                                           _ptr(kh), _ptr(out), err, 512)
+    if rc == 1:
+        raise VpbsError("vpbs_program_aggregate_root: a word of the statement is not a field element (at or above p): no proof has this statement")
+    if rc:
+        raise VpbsError("status %d: %s" % (rc, err.value.decode()))
+    return out
+
+
+def program_verify_aggregate(prog, shape, blob, inputs, testvs, out_cts, key_hash):
+    """vpbs_program_verify_aggregate (host): the client's check of ONE proof for its program instance, without a GPU -> (accepted, reason),
+    verify_aggregate's reasons in its order.  shape: an AggregateShape; prog may be host-only."""
+    x, o, tv, kh = program_aggregate_args("program_verify_aggregate", prog.n_inputs, prog.n_gates, prog.n_luts, shape.N, shape.K, shape.n_lwe, inputs,
+                                          out_cts, testvs, key_hash)
+    buf = (C.c_uint8 * max(1, len(blob))).from_buffer_copy(bytes(blob) or b"\0")
+    why, reason = C.create_string_buffer(512), C.c_int(0)
+    rc = lib().vpbs_program_verify_aggregate(prog.h, C.byref(shape.c), _keep_ptr(x.reshape(-1)), _keep_ptr(tv.reshape(-1)), _keep_ptr(o.reshape(-1)),
+                                             _ptr(kh), buf, len(blob), C.byref(reason), why, 512)
+    if rc < 0:
+        raise VpbsError("status %d: %s" % (rc, why.value.decode()))
+    return rc == 1, int(reason.value)
+
+
+def aggregate_many_args(counts, max_leaves=None, max_aggregates=None, levels=None):
+    """the trees of a many-run, checked without a device: counts [n_agg] leaf counts, each 1 .. 2^levels, n_agg <= max_aggregates, their sum
+    <= max_leaves (a limit that is None is not checked) -> leaf_first [n_agg + 1] as the C ABI wants it (size_t)"""
+    c = np.asarray(counts)
+    if c.ndim != 1 or c.size == 0 or c.dtype.kind not in "iu":
+        raise ValueError("aggregate_many_args: counts is a non-empty list of integers, one leaf count per aggregate")
+    for a, n in enumerate(c.tolist()):
+        if n < 1:
+            raise ValueError("aggregate_many_args: tree %d is empty" % a)
+        if levels is not None and n > 1 << levels:
+            raise ValueError("aggregate_many_args: tree %d: %d leaves exceed 2^levels = %d" % (a, n, 1 << levels))
+    if max_aggregates is not None and c.size > max_aggregates:
+        raise ValueError("aggregate_many_args: %d aggregates exceed max_aggregates %d" % (c.size, max_aggregates))
+    if max_leaves is not None and int(c.sum()) > max_leaves:
+        raise ValueError("aggregate_many_args: %d leaves exceed max_leaves %d" % (int(c.sum()), max_leaves))
+    return np.concatenate([[0], np.cumsum(c)]).astype(np.uint64)
+
+
 class Aggregator:
     """vpbs_aggregator: folds serialised vPBS proofs into one proof.  leaf: the cyclic step circuit (a loaded circuit file) with its
     verifier data leaf_vk [68] (digest, cap: PbsProver / RingProver.verifier_data()[0]); level_circuits: A_1 .. A_levels as loaded circuit
@@ -2582,12 +2691,14 @@ class Aggregator:
 class AggregateVerifier:
     """vpbs_aggregate_verifier: verify_aggregate on the device -- leaf statements, LWE chains and the fold as kernels, the root proof through
     the batch verifier's stages -> the host's verdict and reason.  With on_device=True testvs, cts, out_cts and key_hashes are device pointers
-    (ints) and n_testv / n_keys say how many rows the tables have; key_of and testv_of are host arrays in every mode."""
+    (ints) and n_testv / n_keys say how many rows the tables have; key_of and testv_of are host arrays in every mode.
+    max_aggregates > 1 (vpbs_aggregate_verifier_create_many): verify_many / roots_many take up to that many aggregates -- max_leaves leaves
+    in all -- in ONE device run, whose latency-bound chain is as long as that of one aggregate."""
 
-    def __init__(self, ctx, shape, max_leaves):
-        self.ctx, self.shape, self.max_leaves = ctx, shape, max_leaves
+    def __init__(self, ctx, shape, max_leaves, max_aggregates=1):
+        self.ctx, self.shape, self.max_leaves, self.max_aggregates = ctx, shape, max_leaves, max_aggregates
         self.h, err = C.c_void_p(), C.create_string_buffer(512)
-        rc = lib().vpbs_aggregate_verifier_create(ctx.h, C.byref(shape.c), max_leaves, C.byref(self.h), err, 512)
+        rc = lib().vpbs_aggregate_verifier_create_many(ctx.h, C.byref(shape.c), max_leaves, max_aggregates, C.byref(self.h), err, 512)
         if rc:
             self.h = None
             raise VpbsError("status %d: %s" % (rc, err.value.decode()))
@@ -2632,6 +2743,40 @@ class AggregateVerifier:
         if rc < 0:
             raise VpbsError("status %d: %s" % (rc, err.value.decode()))
         return rc == 1, int(reason.value)
+
+    def _many(self, who, counts, testvs, cts, out_cts, key_hashes, key_of, testv_of, on_device, n_testv, n_keys):
+        first = aggregate_many_args(counts, self.max_leaves, self.max_aggregates, min(self.shape.levels, aggregate_depth(self.max_leaves)))
+        keep, total, a = self._statement(who, int(first[-1]), testvs, cts, out_cts, key_hashes, key_of, testv_of, on_device, n_testv, n_keys)
+        return (keep, first), first.size - 1, first.ctypes.data_as(C.POINTER(C.c_size_t)), a
+
+    def roots_many(self, counts, testvs, cts, out_cts, key_hashes, key_of=None, testv_of=None, on_device=False, n_testv=None, n_keys=None):
+        """the statement stages of many trees in one run: tree a owns the next counts[a] leaves of the per-leaf arrays -> (roots
+        [n_agg][4], raw_bad uint8 [n_agg]: 1 where a raw word of that tree's statement is at or above p and its root means nothing)"""
+        keep, n_agg, first, a = self._many("AggregateVerifier.roots_many", counts, testvs, cts, out_cts, key_hashes, key_of, testv_of, on_device,
+                                           n_testv, n_keys)
+        out, bad, err = np.zeros((n_agg, 4), np.uint64), np.zeros(n_agg, np.uint8), C.create_string_buffer(512)
+        rc = lib().vpbs_aggregate_verifier_roots_many(self.h, n_agg, first, *a, _ptr(out.reshape(-1)), bad.ctypes.data_as(C.POINTER(C.c_uint8)), err, 512)
+        if rc:
+            raise VpbsError("status %d: %s" % (rc, err.value.decode()))
+        return out, bad
+
+    def verify_many(self, blobs, counts, testvs, cts, out_cts, key_hashes, key_of=None, testv_of=None, on_device=False, n_testv=None, n_keys=None):
+        """many aggregates in one run: blobs[a] over the next counts[a] leaves -> (verdicts, reasons), np.uint8 [n_agg] each; entry a is
+        verify_aggregate's (and verify's) verdict and reason for that blob on its slice of the statement"""
+        if len(blobs) != len(counts):
+            raise ValueError("AggregateVerifier.verify_many: %d blobs for %d leaf counts" % (len(blobs), len(counts)))
+        keep, n_agg, first, a = self._many("AggregateVerifier.verify_many", counts, testvs, cts, out_cts, key_hashes, key_of, testv_of, on_device,
+                                           n_testv, n_keys)
+        buf, offs = pack_proofs(blobs)
+        buf, offs = np.ascontiguousarray(buf, dtype=np.uint8), np.ascontiguousarray(offs, dtype=np.uint64)
+        u8p = C.POINTER(C.c_uint8)
+        data = buf.ctypes.data_as(u8p) if buf.size else (C.c_uint8 * 1)()
+        verdicts, reasons, err = np.zeros(n_agg, np.uint8), np.zeros(n_agg, np.uint8), C.create_string_buffer(512)
+        rc = lib().vpbs_aggregate_verifier_run_many(self.h, data, offs.ctypes.data_as(C.POINTER(C.c_size_t)), n_agg, first, *a,
+                                                    verdicts.ctypes.data_as(u8p), reasons.ctypes.data_as(u8p), err, 512)
+        if rc < 0:
+            raise VpbsError("status %d: %s" % (rc, err.value.decode()))
+        return verdicts, reasons
 
     def close(self):
         if self.h:
@@ -2919,6 +3064,109 @@ class Program:
             e.status = rc
             raise e
         return verdicts, reasons, sub
+
+    def prove_aggregate(self, pbs_prover, aggregator, inputs, testvs, on_proof=None):
+        """ONE proof for the program instance: prove(), then Aggregator.aggregate over the gate proofs in gate order -> (blob, wires,
+        out_cts); the bytes are that composition's.  on_proof(gate, bytes) still sees every gate proof.  A program of more than
+        2^levels gates (or none) is refused before anything is proven: VpbsError, on_proof never called."""
+        pp = pbs_prover
+        x, tv = self._host_args("prove_aggregate", pp.n_lwe, pp.N, inputs, testvs)
+        wires, out = np.zeros((self.n_wires, pp.n_lwe + 1), np.uint64), np.zeros((self.n_gates, pp.K, pp.N), np.uint64)
+        raised = []
+
+        def trampoline(_user, index, data, n, error):
+            try:
+                if data and on_proof is not None and not raised:
+                    on_proof(int(index), C.string_at(data, n))
+            except BaseException as e:   # noqa: BLE001 -- must not unwind through the C frames
+                raised.append(e)
+        cb, err = PBS_PROOF_FN(trampoline), C.create_string_buffer(512)
+        blob = np.zeros(aggregator.max_bytes, np.uint8)
+        n = lib().vpbs_program_prove_aggregate(self.h, pp.h, aggregator.h, _keep_ptr(x.reshape(-1)), _keep_ptr(tv.reshape(-1)), _ptr(wires.reshape(-1)),
+                                               _ptr(out.reshape(-1)), blob.ctypes.data_as(C.POINTER(C.c_uint8)), blob.size, None, cb, None, err, 512)
+        if raised:
+            raise raised[0]
+        e, pp._ckpt_error = pp._ckpt_error, None
+        if e is not None:
+            raise e
+        if n < 0:
+            e = VpbsError("vpbs_program_prove_aggregate: status %d: %s" % (n, err.value.decode()))
+            e.status = n
+            raise e
+        return blob[:n].tobytes(), wires, out
+
+    def prove_aggregate_batch(self, ring_prover, aggregator, inputs, key_of, testvs, on_aggregate=None):
+        """one aggregate PER INSTANCE on a RingProver: prove_batch(), then instance by instance Aggregator.aggregate over its gate proofs
+        -> (blobs [instances], wires, out_cts); blobs[b] is byte for byte prove_aggregate on a PbsProver of the key set in slot
+        key_of[b], and a client verifies its own with program_verify_aggregate.  on_aggregate(b, bytes) as they are made."""
+        if self.ctx is None:
+            raise VpbsError("Program.prove_aggregate_batch: a host-only program (made without a context) cannot be evaluated")
+        rp = ring_prover
+        if rp is None or not rp.h:
+            raise VpbsError("Program.prove_aggregate_batch: no ring prover (None, or a closed RingProver)")
+        x, ko, tv = program_batch_args(self.n_inputs, rp.n_lwe, rp.N, self.n_luts, rp.max_keys, inputs, key_of, testvs)
+        B, G = x.shape[0], self.n_gates
+        wires, out = np.zeros((B, self.n_wires, rp.n_lwe + 1), np.uint64), np.zeros((B, G, rp.K, rp.N), np.uint64)
+        blobs, raised = [None] * B, []
+
+        def trampoline(instance, data, n, _user):
+            try:
+                blobs[instance] = C.string_at(data, n)
+                if on_aggregate is not None and not raised:
+                    on_aggregate(int(instance), blobs[instance])
+            except BaseException as e:   # noqa: BLE001 -- must not unwind through the C frames
+                raised.append(e)
+        cb, none, err = AGGREGATE_FN(trampoline), PBS_PROOF_FN(), C.create_string_buffer(512)
+        n = lib().vpbs_program_prove_aggregate_batch(self.h, rp.h, aggregator.h, _keep_ptr(x.reshape(-1)), B,
+                                                     (ko if ko.size else np.zeros(1, np.uint32)).ctypes.data, _keep_ptr(tv.reshape(-1)),
+                                                     _keep_ptr(wires.reshape(-1)), _keep_ptr(out.reshape(-1)), cb, none, None, err, 512)
+        if raised:
+            raise raised[0]
+        e, rp._ckpt_error = rp._ckpt_error, None
+        if e is not None:
+            raise e
+        if n < 0:
+            e = VpbsError("vpbs_program_prove_aggregate_batch: status %d: %s" % (n, err.value.decode()))
+            e.status = n
+            raise e
+        return blobs, wires, out
+
+    def verify_aggregate_batch(self, agg_verifier, inputs, key_of, key_hashes, testvs, out_cts, blobs):
+        """the aggregates of many instances on ONE AggregateVerifier (made with max_aggregates > 1 to take several per run): inputs
+        [instances][n_inputs][n + 1], key_of [instances] indices into key_hashes [n_keys][4], testvs [n_luts][N], out_cts
+        [instances][n_gates][K][N] (claimed), blobs [instances] -> (verdicts, reasons), np.uint8 [instances]; entry b is
+        program_verify_aggregate(blobs[b], inputs[b], testvs, out_cts[b], key_hashes[key_of[b]]).  The gate inputs are recomputed on the
+        device and stay there."""
+        if self.ctx is None:
+            raise VpbsError("Program.verify_aggregate_batch: a host-only program (made without a context) cannot be verified on the device")
+        av = agg_verifier
+        if av is None or not av.h:
+            raise VpbsError("Program.verify_aggregate_batch: no aggregate verifier (None, or a closed AggregateVerifier)")
+        s = av.shape
+        kh = _u64(key_hashes)
+        kh = np.ascontiguousarray(kh.reshape(1, -1) if kh.ndim == 1 else kh)
+        if kh.ndim != 2 or kh.shape[1] != 4:
+            raise ValueError("Program.verify_aggregate_batch: expected key_hashes [n_keys][4], got shape %s" % (kh.shape,))
+        x, ko, tv = program_batch_args(self.n_inputs, s.n_lwe, s.N, self.n_luts, kh.shape[0], inputs, key_of, testvs)
+        B = x.shape[0]
+        _, o, _, _ = program_aggregate_args("Program.verify_aggregate_batch", self.n_inputs, self.n_gates, self.n_luts, s.N, s.K, s.n_lwe, x, out_cts,
+                                            instances=B)
+        if len(blobs) != B:
+            raise ValueError("Program.verify_aggregate_batch: %d blobs for %d instances" % (len(blobs), B))
+        buf, offs = pack_proofs(blobs)
+        buf, offs = np.ascontiguousarray(buf, dtype=np.uint8), np.ascontiguousarray(offs, dtype=np.uint64)
+        u8p = C.POINTER(C.c_uint8)
+        data = buf.ctypes.data_as(u8p) if buf.size else (C.c_uint8 * 1)()
+        verdicts, reasons, err = np.zeros(B, np.uint8), np.zeros(B, np.uint8), C.create_string_buffer(512)
+        rc = lib().vpbs_program_verify_aggregate_batch(self.h, av.h, _keep_ptr(x.reshape(-1)), B, (ko if ko.size else np.zeros(1, np.uint32)).ctypes.data,
+                                                       _ptr(kh.reshape(-1)), kh.shape[0], _keep_ptr(tv.reshape(-1)), _keep_ptr(o.reshape(-1)), data,
+                                                       offs.ctypes.data_as(C.POINTER(C.c_size_t)), verdicts.ctypes.data_as(u8p),
+                                                       reasons.ctypes.data_as(u8p), err, 512)
+        if rc < 0:
+            e = VpbsError("vpbs_program_verify_aggregate_batch: status %d: %s" % (rc, err.value.decode()))
+            e.status = rc
+            raise e
+        return verdicts, reasons
 
     def close(self):
         if self.h:

@@ -4,6 +4,9 @@
 //   prover     : vpbs_aggregator -- the level circuits A_1 .. A_levels arrive as data; every leaf is verified before anything is proven;
 //                then level by level witness plan (host) -> upload -> vpbs_prove_step, the next node's witness on a second thread
 //   verifiers  : vpbs_verify_aggregate (host) and vpbs_aggregate_verifier (device): parse at level d's shape, the vk list, the proof, the root
+//   many-run   : vpbs_aggregate_verifier_run_many / _roots_many -- many trees in ONE run: ag_leaf_pair over all leaves (the
+//                LWE chain and the public-input sponge of a leaf side by side in one wave), ag_fold_many per level over the trees that have
+//                it, per depth ONE batch of root proofs and ag_result_many; the single-run entry points and their kernels are unchanged
 // The prover part is host code against the library's own C ABI, as ivc.hip is.
 #include <hip/hip_runtime.h>
 
@@ -232,6 +235,134 @@ __global__ void ag_result(const uint8_t* __restrict__ proof_reason, const u32* _
     out[0] = reason == VPBS_AGG_OK ? 1 : 0;
     out[1] = reason;
 }
+
+// ================= many aggregates in one run =================
+// Leaf pair: ag_leaf o vp_lwe_chain for one leaf in ONE wave of two 16-lane groups, each with its own 48-word LDS window.  Group A (lanes
+// 0 .. 15) walks the LWE chain exactly as vp_lwe_chain; group B (lanes 16 .. 31) absorbs the leaf's public-input blocks exactly as ag_leaf,
+// first the F = (2 K N + 5) div 8 blocks that hold no LWE-hash word.  Both groups call permute_wide in the same iterations -- every lane of the
+// wave must -- and a group with nothing left permutes a value it discards.  After max(n_lwe + 2, F) iterations A leaves its four words in LDS
+// behind a wavefront fence (the LDS operations of a wave execute in order) and B absorbs the remaining blocks, at most ten.  Critical path:
+// max(n_lwe + 2, F) + ceil(n_pi / 8) - F permutations instead of (n_lwe + 2) + ceil(n_pi / 8).  A raw word at or above p sets the flag of
+// the leaf's TREE.  Bounds: blockIdx.x < the leaf count; testv_of[i] < n_testv, key_of[i] < n_keys and tree_of[i] < n_agg are checked on the
+// host; j - 2 kn - 9 < 68.
+__global__ __launch_bounds__(32) void ag_leaf_pair(const u64* __restrict__ testvs, const u32* __restrict__ testv_of, const u64* __restrict__ out_ct,
+                                                   const u64* __restrict__ key_hashes, const u32* __restrict__ key_of, const u64* __restrict__ cts,
+                                                   const u64* __restrict__ vk0, const u32* __restrict__ tree_of, AggShape S, u64* __restrict__ stmt,
+                                                   u32* __restrict__ flags) {
+    __shared__ u64 sh[2 * poseidon::WIDE_LDS_WORDS + 4];
+    const unsigned l = threadIdx.x & 15, g = threadIdx.x >> 4;
+    u64* win = sh + g * poseidon::WIDE_LDS_WORDS;
+    u64* hand = sh + 2 * poseidon::WIDE_LDS_WORDS;   // the end of the LWE chain, from A to B
+    const u32 i = blockIdx.x;
+    const u64* c = cts + (u64)i * (S.n_lwe + 1);
+    const u64* tv = testvs + (u64)testv_of[i] * S.N;
+    const u64* oc = out_ct + (u64)i * S.kn;
+    const u64* kh = key_hashes + (u64)key_of[i] * 4;
+    auto word = [&](u32 j) -> u64 {
+        if (j < S.kn - S.N) return 0;
+        if (j < S.kn) return tv[j - (S.kn - S.N)];
+        if (j == S.kn) return (u64)S.n_lwe + 2;
+        if (j <= 2 * S.kn) return oc[j - S.kn - 1];
+        if (j < 2 * S.kn + 5) return kh[j - 2 * S.kn - 1];
+        if (j < 2 * S.kn + 9) return hand[j - 2 * S.kn - 5];
+        return vk0[j - 2 * S.kn - 9];
+    };
+    const u32 links = S.n_lwe + 2, F = (2 * S.kn + 5) / 8, both = max(links, F);
+    const bool rate = g == 1 && l < 8;
+    u64 x = 0;
+    bool bad = false;
+    // the next item / block is loaded while this one runs: the loads are off the dependent chain.  Words below 8 F never come from `hand`.
+    u64 next = g == 0 ? c[S.n_lwe] : (rate && l < 8 * F ? word(l) : 0);
+    for (u32 it = 0; it < both; ++it) {
+        const u64 cur = next;
+        u64 in = x;
+        if (g == 0) {
+            next = it < S.n_lwe ? c[it] : 0;
+            if (l == 4) in = gl::canon(cur);
+            else if (l > 4) in = 0;
+        } else {
+            const u32 jn = 8 * (it + 1) + l;
+            next = rate && jn < 8 * F ? word(jn) : 0;
+            if (rate && it < F) {
+                bad = bad || cur >= gl::P;
+                in = gl::canon(cur);
+            }
+        }
+        const u64 y = poseidon::permute_wide(in, win, l);
+        if (it < (g == 0 ? links : F)) x = y;
+    }
+    if (g == 0 && l < 4) hand[l] = x;
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    next = rate && 8 * F + l < S.n_pi ? word(8 * F + l) : 0;
+    for (u32 off = 8 * F; off < S.n_pi; off += 8) {
+        const bool mine = rate && off + l < S.n_pi;
+        const u64 w = next;
+        const u32 jn = off + 8 + l;
+        next = rate && jn < S.n_pi ? word(jn) : 0;
+        u64 in = x;
+        if (mine) {
+            bad = bad || w >= gl::P;
+            in = gl::canon(w);
+        }
+        const u64 y = poseidon::permute_wide(in, win, l);
+        if (g == 1) x = y;
+    }
+    if (g == 1 && l < 4) stmt[(u64)i * 4 + l] = x;
+    if (bad) atomicOr(&flags[tree_of[i]], 1u);
+}
+
+// what the segmented fold knows of one tree at one level: its entries of the level below (n_in of them from in_first: the tree's own leaf
+// count at level 1, the whole level above that), where its nodes start in this level, and whether this level is the tree's depth
+struct FoldTree {
+    u32 in_first, n_in, out_first, root;
+};
+
+// One level of ALL trees that still have that level: ag_fold per node, one node per 16-lane block; node_tree[node] names the node's tree.
+// The padding rule is ag_fold's index clamp by the tree's own n_in, so a one-leaf tree folds its leaf with itself.  The node of a tree's own
+// depth also lands in roots[tree].  Bounds: blockIdx.x < the level's node count, node_tree[..] < n_agg, in_first + n_in within the level below
+// (the host builds the tables from the checked leaf counts).
+__global__ __launch_bounds__(16) void ag_fold_many(const u64* __restrict__ in, const u32* __restrict__ node_tree, const FoldTree* __restrict__ tab,
+                                                   u64* __restrict__ out, u64* __restrict__ roots) {
+    __shared__ u64 sh[poseidon::WIDE_LDS_WORDS];
+    const unsigned l = threadIdx.x;
+    const u32 node = blockIdx.x, t = node_tree[node];
+    const FoldTree T = tab[t];
+    const u32 k = node - T.out_first;
+    const u32 a = T.in_first + min(2 * k, T.n_in - 1), b = T.in_first + min(2 * k + 1, T.n_in - 1);
+    u64 x = 0;
+    if (l < 4) x = in[(u64)a * 4 + l];
+    else if (l < 8) x = in[(u64)b * 4 + l - 4];
+    x = poseidon::permute_wide(x, sh, l);
+    if (l < 4) {
+        out[(u64)node * 4 + l] = x;
+        if (T.root) roots[(u64)t * 4 + l] = x;
+    }
+}
+
+// ag_result for the n aggregates of one depth, one lane each: proof i of the depth's batch is aggregate agg_of[i]; its own root, its own
+// tree's flag, n_expected = 4 + 68 d; the same order of checks -> out[2 a] = verdict, out[2 a + 1] = reason
+__global__ __launch_bounds__(64) void ag_result_many(const uint8_t* __restrict__ proof_reason, const u32* __restrict__ n_pi,
+                                                     const u64* __restrict__ words, u32 W, u32 n_fixed, const u64* __restrict__ vks,
+                                                     const u64* __restrict__ roots, const u32* __restrict__ flags, const u32* __restrict__ agg_of,
+                                                     u32 n, u32 n_expected, uint8_t* __restrict__ out) {
+    const u32 i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    const u32 a = agg_of[i];
+    const u64* pis = words + (u64)i * W + n_fixed;
+    const u64* root = roots + (u64)a * 4;
+    const uint8_t pr = proof_reason[i];
+    uint8_t reason = VPBS_AGG_OK;
+    if (pr == VPBS_VERIFY_MALFORMED || n_pi[i] != n_expected) {
+        reason = VPBS_AGG_MALFORMED;
+    } else {
+        bool vk_bad = false, root_bad = flags[a] != 0;
+        for (u32 j = 4; j < n_expected; ++j) vk_bad = vk_bad || pis[j] != vks[j - 4];
+        for (u32 j = 0; j < 4; ++j) root_bad = root_bad || pis[j] != root[j];
+        reason = vk_bad ? VPBS_AGG_VERIFIER_DATA : pr != VPBS_VERIFY_OK ? VPBS_AGG_PROOF : root_bad ? VPBS_AGG_ROOT : VPBS_AGG_OK;
+    }
+    out[2 * a] = reason == VPBS_AGG_OK ? 1 : 0;
+    out[2 * a + 1] = reason;
+}
 }  // namespace
 
 struct vpbs_aggregate_verifier {
@@ -245,6 +376,16 @@ struct vpbs_aggregate_verifier {
     uint8_t* d_out = nullptr;
     u64* h_in = nullptr;      // pinned: cts | out_cts | testvs | key_hashes | testv_of, key_of
     u64* h_out = nullptr;     // pinned: root [4] | flag | verdict, reason
+    // many aggregates in one run (create_many): the proof verifiers take batches of max_aggregates
+    size_t max_aggregates = 1;
+    u64 *d_mnodes[2] = {nullptr, nullptr}, *d_roots = nullptr;   // a level of all trees [max_leaves][4], twice; roots [max_aggregates][4]
+    u32 *d_mflags = nullptr, *d_midx = nullptr;                  // raw-word flag per tree; the index tables of a run (many_idx_words)
+    uint8_t* d_mout = nullptr;                                   // verdict, reason per aggregate
+    u32* h_midx = nullptr;    // pinned: d_midx's image
+    u64* h_mout = nullptr;    // pinned: roots [max_aggregates][4] | flags or verdict, reason [max_aggregates]
+    // testv_of, key_of, tree_of per leaf | node_tree of every level (fewer than 2 max_leaves nodes in all) | FoldTree per tree and level |
+    // agg_of per aggregate
+    size_t many_idx_words() const { return 5 * max_leaves + (4 * (size_t)levels + 1) * max_aggregates + 16; }
     std::mutex mu;
     size_t kn() const { return (size_t)K * N; }
     size_t in_words() const { return max_leaves * ((size_t)n_lwe + 1 + kn() + N + 4 + 1); }
@@ -260,6 +401,8 @@ struct vpbs_aggregate_verifier {
         for (void* p : owned) ctx->release(p);
         if (h_in) (void)hipHostFree(h_in);
         if (h_out) (void)hipHostFree(h_out);
+        if (h_midx) (void)hipHostFree(h_midx);
+        if (h_mout) (void)hipHostFree(h_mout);
         for (auto* p : proofs) vpbs_proof_verifier_free(p);
     }
 };
@@ -293,7 +436,10 @@ void statement_enqueue(vpbs_aggregate_verifier* v, const Statement& s, int on_de
     VPBS_HIP(hipMemcpyAsync(v->d_in, v->h_in, 8 * (at + count), hipMemcpyHostToDevice, st));
     const u32* d_idx = reinterpret_cast<const u32*>(v->d_in + at);
     VPBS_HIP(hipMemsetAsync(v->d_flag, 0, 4, st));
-    vpbs::lwe_chain_enqueue(st, d_ct, s.n_lwe, count, v->d_lwe);
+    {
+        vpbs::Timed t(ctx, "vp_lwe_chain");
+        vpbs::lwe_chain_enqueue(st, d_ct, s.n_lwe, count, v->d_lwe);
+    }
     const AggShape S{s.N, (u32)kn, s.n_lwe, (u32)s.n_pi()};
     {
         vpbs::Timed t(ctx, "ag_leaf");
@@ -717,12 +863,18 @@ long vpbs_aggregator_run(vpbs_aggregator* a, const uint8_t* bytes, const size_t*
 
 int vpbs_aggregate_verifier_create(vpbs_ctx* ctx, const vpbs_aggregate_shape* shape, size_t max_leaves, vpbs_aggregate_verifier** out, char* err,
                                    size_t err_len) {
+    return vpbs_aggregate_verifier_create_many(ctx, shape, max_leaves, 1, out, err, err_len);
+}
+
+int vpbs_aggregate_verifier_create_many(vpbs_ctx* ctx, const vpbs_aggregate_shape* shape, size_t max_leaves, size_t max_aggregates,
+                                        vpbs_aggregate_verifier** out, char* err, size_t err_len) {
     if (out) *out = nullptr;
     report(err, err_len, "");
     auto refuse = [&](const char* m) {
         report(err, err_len, std::string("vpbs_aggregate_verifier_create: ") + m);
         return VPBS_ERR_INVALID;
     };
+    if (max_aggregates == 0 || max_aggregates > (1u << 16)) return refuse("max_aggregates must be 1 .. 2^16");
     if (!ctx || !out || !shape_ok(shape)) return refuse("null or malformed arguments");
     if (shape->N == 0 || shape->K == 0 || (size_t)shape->K * shape->N > (1u << 20) || shape->n_lwe > (1u << 24)) return refuse("N, K or n_lwe out of range");
     if (max_leaves == 0 || max_leaves > (1u << 20)) return refuse("max_leaves must be 1 .. 2^20");
@@ -731,12 +883,13 @@ int vpbs_aggregate_verifier_create(vpbs_ctx* ctx, const vpbs_aggregate_shape* sh
     auto* v = new vpbs_aggregate_verifier;
     v->N = shape->N; v->K = shape->K; v->n_lwe = shape->n_lwe;
     v->max_leaves = max_leaves;
+    v->max_aggregates = max_aggregates;
     // only the levels max_leaves can reach get a batch verifier
     v->levels = std::min(shape->levels, depth_of(max_leaves));
     for (unsigned l = 1; l <= v->levels; ++l) {
         const vpbs_verify_inputs c = level_inputs(*shape, l);
         vpbs_proof_verifier* p = nullptr;
-        const int rc = vpbs_proof_verifier_create(ctx, &c, 1, 4 + VK * l, &p, err, err_len);
+        const int rc = vpbs_proof_verifier_create(ctx, &c, max_aggregates, 4 + VK * l, &p, err, err_len);
         if (rc) {
             delete v;
             return rc;
@@ -756,6 +909,13 @@ int vpbs_aggregate_verifier_create(vpbs_ctx* ctx, const vpbs_aggregate_shape* sh
         v->d_out = static_cast<uint8_t*>(v->alloc(8));
         VPBS_HIP(hipHostMalloc((void**)&v->h_in, 8 * v->in_words(), hipHostMallocDefault));
         VPBS_HIP(hipHostMalloc((void**)&v->h_out, 64, hipHostMallocDefault));
+        for (auto& n : v->d_mnodes) n = static_cast<u64*>(v->alloc(32 * max_leaves));
+        v->d_roots = static_cast<u64*>(v->alloc(32 * max_aggregates));
+        v->d_mflags = static_cast<u32*>(v->alloc(4 * max_aggregates));
+        v->d_midx = static_cast<u32*>(v->alloc(4 * v->many_idx_words()));
+        v->d_mout = static_cast<uint8_t*>(v->alloc(2 * max_aggregates));
+        VPBS_HIP(hipHostMalloc((void**)&v->h_midx, 4 * v->many_idx_words(), hipHostMallocDefault));
+        VPBS_HIP(hipHostMalloc((void**)&v->h_mout, 40 * max_aggregates, hipHostMallocDefault));
         VPBS_HIP(hipMemcpyAsync(v->d_vks, shape->vks, 8 * VK * (v->levels + 1), hipMemcpyHostToDevice, ctx->stream));
         VPBS_HIP(vpbs::stream_sync(ctx->stream));
     } catch (const DeviceError& e) {
@@ -835,4 +995,231 @@ int vpbs_aggregate_verifier_run(vpbs_aggregate_verifier* v, const uint8_t* bytes
 
 void vpbs_aggregate_verifier_free(vpbs_aggregate_verifier* v) { delete v; }
 
+}  // extern "C"
+
+// ================= many aggregates in one run =================
+namespace {
+// What run_many and roots_many refuse, by name, before anything is queued; s.count is the total leaf count.  depth: of every tree.
+bool many_args_ok(vpbs_aggregate_verifier* v, const Statement& s, size_t n_agg, const size_t* leaf_first, const char* who, std::vector<unsigned>* depth,
+                  std::string* msg) {
+    auto no = [&](const std::string& m) {
+        *msg = std::string(who) + ": " + m;
+        return false;
+    };
+    if (n_agg == 0) return no("n_agg is 0: there is nothing to verify");
+    if (!leaf_first) return no("null leaf_first");
+    if (n_agg > v->max_aggregates) return no("n_agg " + std::to_string(n_agg) + " exceeds max_aggregates " + std::to_string(v->max_aggregates));
+    if (leaf_first[0] != 0) return no("leaf_first[0] must be 0");
+    depth->assign(n_agg, 0);
+    for (size_t a = 0; a < n_agg; ++a) {
+        if (leaf_first[a + 1] <= leaf_first[a]) return no("tree " + std::to_string(a) + " is empty (leaf_first must increase)");
+        const size_t count = leaf_first[a + 1] - leaf_first[a];
+        if (count > ((size_t)1 << v->levels))
+            return no("tree " + std::to_string(a) + ": " + std::to_string(count) + " leaves exceed 2^levels = " + std::to_string((size_t)1 << v->levels));
+        (*depth)[a] = depth_of(count);
+    }
+    if (leaf_first[n_agg] != s.count) return no("leaf_first ends at " + std::to_string(leaf_first[n_agg]) + ", not at the leaf count");
+    if (s.count > v->max_leaves || s.n_testv > v->max_leaves || s.n_keys > v->max_leaves)
+        return no("the leaf count " + std::to_string(s.count) + ", n_testv or n_keys exceeds max_leaves " + std::to_string(v->max_leaves));
+    return statement_ok(s, who, msg);
+}
+
+// The statement stages of all trees, queued on the context's stream: ag_leaf_pair over all leaves, then one ag_fold_many per level over the
+// trees that have that level.  After them d_roots [n_agg][4] holds the roots and d_mflags [n_agg] the raw-word flags.  *agg_idx: where the
+// caller may put further u32 tables in h_midx / d_midx (the upload of h_midx is the caller's, before its first launch that reads them; the
+// tables of this function are uploaded here).
+void many_statement_enqueue(vpbs_aggregate_verifier* v, const Statement& s, size_t n_agg, const size_t* leaf_first, const std::vector<unsigned>& depth,
+                            int on_device, size_t extra_idx, size_t* agg_idx) {
+    vpbs_ctx* ctx = v->ctx;
+    hipStream_t st = ctx->stream;
+    const size_t total = s.count, kn = v->kn();
+    const size_t n_ct = total * ((size_t)s.n_lwe + 1), n_out = total * kn, n_tv = s.n_testv * (size_t)s.N, n_kh = 4 * s.n_keys;
+    const u64 *d_ct = s.cts, *d_oc = s.out_cts, *d_tv = s.testvs, *d_kh = s.key_hashes;
+    if (!on_device) {
+        std::memcpy(v->h_in, s.cts, 8 * n_ct);
+        std::memcpy(v->h_in + n_ct, s.out_cts, 8 * n_out);
+        std::memcpy(v->h_in + n_ct + n_out, s.testvs, 8 * n_tv);
+        std::memcpy(v->h_in + n_ct + n_out + n_tv, s.key_hashes, 8 * n_kh);
+        VPBS_HIP(hipMemcpyAsync(v->d_in, v->h_in, 8 * (n_ct + n_out + n_tv + n_kh), hipMemcpyHostToDevice, st));
+        d_ct = v->d_in;
+        d_oc = v->d_in + n_ct;
+        d_tv = v->d_in + n_ct + n_out;
+        d_kh = v->d_in + n_ct + n_out + n_tv;
+    }
+    // ---- the index tables, computed once per run ----
+    u32* idx = v->h_midx;
+    unsigned max_d = 0;
+    for (size_t a = 0; a < n_agg; ++a) {
+        max_d = std::max(max_d, depth[a]);
+        for (size_t i = leaf_first[a]; i < leaf_first[a + 1]; ++i) {
+            idx[i] = (u32)s.tv(i);
+            idx[total + i] = (u32)s.key(i);
+            idx[2 * total + i] = (u32)a;
+        }
+    }
+    size_t at = 3 * total;
+    std::vector<size_t> o_tree(max_d + 1), o_tab(max_d + 1), nodes(max_d + 1, 0);
+    std::vector<u32> prev_first(n_agg), prev_n(n_agg);   // the tree's entries in the level below
+    for (size_t a = 0; a < n_agg; ++a) {
+        prev_first[a] = (u32)leaf_first[a];
+        prev_n[a] = (u32)(leaf_first[a + 1] - leaf_first[a]);
+    }
+    for (unsigned l = 1; l <= max_d; ++l) {
+        o_tree[l] = at;
+        u32 node = 0;
+        std::vector<FoldTree> tab(n_agg, FoldTree{0, 1, 0, 0});
+        for (size_t a = 0; a < n_agg; ++a) {
+            if (depth[a] < l) continue;
+            const u32 mine = 1u << (depth[a] - l);
+            tab[a] = FoldTree{prev_first[a], prev_n[a], node, depth[a] == l ? 1u : 0u};
+            for (u32 k = 0; k < mine; ++k) idx[at + node + k] = (u32)a;
+            prev_first[a] = node;
+            prev_n[a] = mine;
+            node += mine;
+        }
+        nodes[l] = node;
+        at += node;
+        o_tab[l] = at;
+        std::memcpy(idx + at, tab.data(), sizeof(FoldTree) * n_agg);
+        at += 4 * n_agg;
+    }
+    *agg_idx = at;
+    VPBS_REQUIRE(at + extra_idx <= v->many_idx_words(), "the index tables of the run exceed their buffer");
+    VPBS_HIP(hipMemcpyAsync(v->d_midx, v->h_midx, 4 * at, hipMemcpyHostToDevice, st));
+    VPBS_HIP(hipMemsetAsync(v->d_mflags, 0, 4 * n_agg, st));
+    const AggShape S{s.N, (u32)kn, s.n_lwe, (u32)s.n_pi()};
+    {
+        vpbs::Timed t(ctx, "ag_leaf_pair");
+        ag_leaf_pair<<<(u32)total, 32, 0, st>>>(d_tv, v->d_midx, d_oc, d_kh, v->d_midx + total, d_ct, v->d_vks, v->d_midx + 2 * total, S, v->d_stmt,
+                                                v->d_mflags);
+    }
+    VPBS_HIP(hipGetLastError());
+    {
+        vpbs::Timed t(ctx, "ag_fold_many");
+        const u64* in = v->d_stmt;
+        for (unsigned l = 1; l <= max_d; ++l) {
+            u64* out = v->d_mnodes[l & 1];
+            ag_fold_many<<<(u32)nodes[l], 16, 0, st>>>(in, v->d_midx + o_tree[l], reinterpret_cast<const FoldTree*>(v->d_midx + o_tab[l]), out, v->d_roots);
+            in = out;
+        }
+    }
+    VPBS_HIP(hipGetLastError());
+}
+}  // namespace
+
+namespace vpbs {
+unsigned aggregator_levels(const vpbs_aggregator* a) { return (unsigned)a->levels.size(); }
+size_t aggregator_max_bytes(const vpbs_aggregator* a) {
+    size_t most = 0;
+    for (const Level& L : a->levels) most = std::max(most, 8 * ((size_t)L.n_wires * 64 + ((size_t)1 << 17)) + 8 * L.n_pi);
+    return most;
+}
+void aggregate_verifier_shape(const vpbs_aggregate_verifier* v, AggregateVerifierShape* out) {
+    *out = AggregateVerifierShape{v->ctx, v->N, v->K, v->n_lwe, v->levels, v->max_leaves, v->max_aggregates};
+}
+}  // namespace vpbs
+
+extern "C" {
+int vpbs_aggregate_verifier_roots_many(vpbs_aggregate_verifier* v, size_t n_agg, const size_t* leaf_first, const uint64_t* testvs, size_t n_testv,
+                                       const uint32_t* testv_of, const uint64_t* cts, const uint64_t* out_cts, const uint64_t* key_hashes,
+                                       size_t n_keys, const uint32_t* key_of, int on_device, uint64_t* out, uint8_t* raw_bad, char* err,
+                                       size_t err_len) {
+    report(err, err_len, "");
+    const char* who = "vpbs_aggregate_verifier_roots_many";
+    if (!v || !out || !raw_bad) return report(err, err_len, std::string(who) + ": null argument"), VPBS_ERR_INVALID;
+    std::lock_guard<std::mutex> lock(v->mu);
+    u64 vk0_unused = 0;   // the host checks need a non-null vk0; the device holds the real one
+    const Statement s{v->N, v->K, v->n_lwe, &vk0_unused, leaf_first && n_agg ? leaf_first[n_agg] : 0, testvs, n_testv, testv_of, cts, out_cts,
+                      key_hashes, n_keys, key_of};
+    std::string msg;
+    std::vector<unsigned> depth;
+    if (!many_args_ok(v, s, n_agg, leaf_first, who, &depth, &msg)) return report(err, err_len, msg), VPBS_ERR_INVALID;
+    try {
+        VPBS_HIP(hipSetDevice(v->ctx->device));
+        hipStream_t st = v->ctx->stream;
+        size_t at = 0;
+        many_statement_enqueue(v, s, n_agg, leaf_first, depth, on_device, 0, &at);
+        VPBS_HIP(hipMemcpyAsync(v->h_mout, v->d_roots, 32 * n_agg, hipMemcpyDeviceToHost, st));
+        VPBS_HIP(hipMemcpyAsync(v->h_mout + 4 * n_agg, v->d_mflags, 4 * n_agg, hipMemcpyDeviceToHost, st));
+        VPBS_HIP(vpbs::stream_sync(st));   // the one wait
+    } catch (const DeviceError& e) {
+        v->ctx->err = e.what;
+        return report(err, err_len, std::string(who) + ": " + e.what), e.status;
+    }
+    std::memcpy(out, v->h_mout, 32 * n_agg);
+    const u32* flags = reinterpret_cast<const u32*>(v->h_mout + 4 * n_agg);
+    for (size_t a = 0; a < n_agg; ++a) raw_bad[a] = flags[a] ? 1 : 0;
+    return VPBS_OK;
+}
+
+long vpbs_aggregate_verifier_run_many(vpbs_aggregate_verifier* v, const uint8_t* bytes, const size_t* offsets, size_t n_agg, const size_t* leaf_first,
+                                      const uint64_t* testvs, size_t n_testv, const uint32_t* testv_of, const uint64_t* cts, const uint64_t* out_cts,
+                                      const uint64_t* key_hashes, size_t n_keys, const uint32_t* key_of, int on_device, uint8_t* verdicts,
+                                      uint8_t* reasons, char* err, size_t err_len) {
+    report(err, err_len, "");
+    const char* who = "vpbs_aggregate_verifier_run_many";
+    if (!v || !bytes || !offsets || !verdicts) return report(err, err_len, std::string(who) + ": null argument"), VPBS_ERR_INVALID;
+    std::lock_guard<std::mutex> lock(v->mu);
+    u64 vk0_unused = 0;
+    const Statement s{v->N, v->K, v->n_lwe, &vk0_unused, leaf_first && n_agg ? leaf_first[n_agg] : 0, testvs, n_testv, testv_of, cts, out_cts,
+                      key_hashes, n_keys, key_of};
+    std::string msg;
+    std::vector<unsigned> depth;
+    if (!many_args_ok(v, s, n_agg, leaf_first, who, &depth, &msg)) return report(err, err_len, msg), VPBS_ERR_INVALID;
+    for (size_t a = 0; a < n_agg; ++a)
+        if (offsets[a + 1] < offsets[a]) return report(err, err_len, std::string(who) + ": offsets decrease at aggregate " + std::to_string(a)), VPBS_ERR_INVALID;
+    try {
+        VPBS_HIP(hipSetDevice(v->ctx->device));
+        hipStream_t st = v->ctx->stream;
+        size_t at = 0;
+        many_statement_enqueue(v, s, n_agg, leaf_first, depth, on_device, n_agg, &at);
+        // agg_of: the aggregates grouped by depth, each depth ONE batch of its level's proof verifier
+        std::vector<std::vector<u32>> of_depth(v->levels + 1);
+        for (size_t a = 0; a < n_agg; ++a) of_depth[depth[a]].push_back((u32)a);
+        u32* agg_of = v->h_midx + at;
+        size_t k = 0;
+        for (unsigned d = 1; d <= v->levels; ++d)
+            for (u32 a : of_depth[d]) agg_of[k++] = a;
+        VPBS_HIP(hipMemcpyAsync(v->d_midx + at, agg_of, 4 * n_agg, hipMemcpyHostToDevice, st));
+        std::vector<uint8_t> packed;
+        std::vector<size_t> offs;
+        size_t first = 0;
+        for (unsigned d = 1; d <= v->levels; ++d) {
+            const std::vector<u32>& mine = of_depth[d];
+            if (mine.empty()) continue;
+            packed.clear();
+            offs.assign(1, 0);
+            for (u32 a : mine) {
+                packed.insert(packed.end(), bytes + offsets[a], bytes + offsets[a + 1]);
+                offs.push_back(packed.size());
+            }
+            if (packed.empty()) packed.push_back(0);   // a valid pointer for a batch of empty blobs
+            vpbs::ProofBatchView pv{};
+            const int rc = vpbs::proof_verifier_enqueue(v->proofs[d - 1], packed.data(), offs.data(), mine.size(), &pv);
+            if (rc) {
+                (void)vpbs::stream_sync(st);
+                return report(err, err_len, std::string(who) + ": the batch verifier refused the bytes"), (long)rc;
+            }
+            const u32 n_expected = (u32)(4 + VK * d), n = (u32)mine.size();
+            VPBS_REQUIRE(pv.max_pi >= n_expected, "the batch verifier's slot is smaller than the aggregate's public inputs");
+            ag_result_many<<<(n + 63) / 64, 64, 0, st>>>(pv.reasons, pv.n_pi, pv.words, pv.W, pv.n_fixed, v->d_vks, v->d_roots, v->d_mflags,
+                                                         v->d_midx + at + first, n, n_expected, v->d_mout);
+            VPBS_HIP(hipGetLastError());
+            first += mine.size();
+        }
+        VPBS_HIP(hipMemcpyAsync(v->h_mout, v->d_mout, 2 * n_agg, hipMemcpyDeviceToHost, st));
+        VPBS_HIP(vpbs::stream_sync(st));   // the one wait
+    } catch (const DeviceError& e) {
+        v->ctx->err = e.what;
+        return report(err, err_len, std::string(who) + ": " + e.what), (long)e.status;
+    }
+    const uint8_t* o = reinterpret_cast<const uint8_t*>(v->h_mout);
+    long accepted = 0;
+    for (size_t a = 0; a < n_agg; ++a) {
+        verdicts[a] = o[2 * a];
+        if (reasons) reasons[a] = o[2 * a + 1];
+        accepted += o[2 * a];
+    }
+    return accepted;
+}
 }  // extern "C"

@@ -29,6 +29,14 @@
 //           verifier's max_batch rows the verifier's core on device pointers into these tables (vpbs::pbs_verify_enqueue) -- the test
 //           vector of a row through testv_of = gate_lut, the key hash through key_of of the row's instance; both index arrays are
 //           uploaded once -- and one wait for the chunk's result bytes.
+//   One proof per program instance: the gates of an instance are the leaves of ONE aggregate (aggregate.hip), in gate order.
+//   gate_inputs, aggregate_root, verify_aggregate   the statement on the HOST (a host-only program will do): the wire table from the claimed
+//           outputs (multi_lut::extract_at_word), lwe_combine_kernel's arithmetic and the snap in plain C++, then vpbs_aggregate_root /
+//           vpbs_verify_aggregate over those gate inputs with testv_of = gate_lut.
+//   prove_aggregate, prove_aggregate_batch   prove / prove_batch with the proofs kept, then vpbs_aggregator_run per instance, after the last proof.
+//   verify_aggregate_batch   verify_batch's upload, ONE extraction launch and ONE lwe_combine_rows_kernel over all instances, then the tables
+//           where they lie to vpbs_aggregate_verifier_run_many (device pointers; testv_of = gate_lut tiled, the key index per row), in chunks
+//           of the verifier's max_aggregates / max_leaves on the same stream, one wait per chunk.
 //
 // Multi-output gates (vpbs_program_create_multi): gate g has outs[g] output wires and a snap of slots[g].  Everything above
 // holds with "outputs of the level" for "gates of the level" in both wire tables; the gate inputs, the output GLWEs and the proofs stay
@@ -242,6 +250,54 @@ bool slots_fit(const vpbs_program* prog, unsigned log_n, std::string* msg) {
         }
     return true;
 }
+// the shape refusal of verify / verify_batch, for a shape that arrives as numbers: N a power of two, 1 <= n_lwe <= (K - 1) N
+bool extraction_shape(unsigned N, unsigned K, unsigned n_lwe, unsigned* log_n) {
+    unsigned l = 0;
+    while (l < 16 && (1u << l) < N) ++l;
+    *log_n = l;
+    return N != 0 && (1u << l) == N && K >= 2 && K <= (1u << 20) / N && n_lwe != 0 && n_lwe <= (size_t)(K - 1) * N;
+}
+
+// The gate inputs a verifier recomputes, on the host, word for word what verify / verify_batch leave in d_cts: per instance the wire table is
+// the inputs followed by the extraction at coefficient j of every claimed output (multi_lut::extract_at_word; j = 0 is lwe_extract_kernel's
+// row), then lwe_combine_kernel's arithmetic per gate -- canonical on read, canonical products and sums, the constant in the body word only
+// -- and, for a program with multi-output gates, the snap of the gate's log_slots.  The shape has been checked (extraction_shape, slots_fit).
+void gate_inputs_host(const vpbs_program* prog, unsigned log_n, unsigned K, unsigned n_lwe, const u64* inputs, size_t instances, const u64* out_cts,
+                      u64* cts_out) {
+    const unsigned n_in = prog->n_inputs, n_gates = prog->n_gates;
+    const size_t n = (size_t)1 << log_n, kn = K * n, words = (size_t)n_lwe + 1;
+    const Csr& G = prog->given;
+    std::vector<u64> wires(((size_t)n_in + prog->n_outs) * words);
+    for (size_t b = 0; b < instances; ++b) {
+        if (n_in) std::memcpy(wires.data(), inputs + b * n_in * words, 8 * n_in * words);
+        for (unsigned g = 0; g < n_gates; ++g) {
+            const u64* ct = out_cts + (b * n_gates + g) * kn;
+            for (u32 o = prog->out_first[g]; o < prog->out_first[g + 1]; ++o) {
+                u64* row = wires.data() + ((size_t)n_in + o) * words;
+                for (unsigned c = 0; c <= n_lwe; ++c) row[c] = multi_lut::extract_at_word(ct, log_n, K, n_lwe, o - prog->out_first[g], c);
+            }
+        }
+        for (unsigned g = 0; g < n_gates; ++g) {
+            u64* out = cts_out + (b * n_gates + g) * words;
+            for (size_t j = 0; j < words; ++j) {
+                u64 s = j + 1 == words ? G.cst[g] : 0;
+                for (u64 t = G.first[g]; t < G.first[g + 1]; ++t) s = gl::add(s, gl::mul(G.coef[t], gl::canon(wires[(size_t)G.src[t] * words + j])));
+                out[j] = prog->multi ? multi_lut::snap(s, log_n, prog->slots[g]) : s;
+            }
+        }
+    }
+}
+
+// what the three host statement functions refuse of (prog, N, K, n_lwe): false with the message, `who` in front
+bool statement_shape_ok(const vpbs_program* prog, unsigned N, unsigned K, unsigned n_lwe, const std::string& who, unsigned* log_n, std::string* msg) {
+    if (!prog) return *msg = who + ": null program", false;
+    if (!extraction_shape(N, K, n_lwe, log_n))
+        return *msg = who + ": the shape has no sample extraction (N a power of two, 1 <= n_lwe <= (K - 1) N)", false;
+    std::string fit;
+    if (!slots_fit(prog, *log_n, &fit)) return *msg = who + ": " + fit, false;
+    return true;
+}
+
 void launch_gather(hipStream_t s, const u64* d_src, const u32* d_map, size_t words, unsigned rows, u64* d_dst) {
     hipLaunchKernelGGL(gather_rows_kernel, dim3(rows), dim3(256), 0, s, d_src, d_map, words, d_dst);
 }
@@ -952,6 +1008,264 @@ long vpbs_program_verify_batch(vpbs_program* prog, vpbs_ring_verifier* ring_veri
             }
         } catch (const DeviceError& e) {
             pbs_verify_abandon(core, e);
+            (void)vpbs::stream_sync(s);
+            throw;
+        }
+    } catch (const DeviceError& e) {
+        report(err, err_len, who + ": " + e.what);
+        return e.status == VPBS_ERR_OOM ? VPBS_ERR_OOM : VPBS_ERR_DEVICE;
+    }
+    return accepted;
+}
+
+// ---- one proof per program instance ----
+int vpbs_program_gate_inputs(const vpbs_program* prog, unsigned N, unsigned K, unsigned n_lwe, const uint64_t* inputs, size_t instances,
+                             const uint64_t* out_cts, uint64_t* cts_out, char* err, size_t err_len) {
+    using namespace vpbs;
+    const std::string who = "vpbs_program_gate_inputs";
+    report(err, err_len, "");
+    unsigned log_n = 0;
+    std::string msg;
+    if (!statement_shape_ok(prog, N, K, n_lwe, who, &log_n, &msg)) return report(err, err_len, msg), VPBS_ERR_INVALID;
+    if (instances && prog->n_gates && ((prog->n_inputs && !inputs) || !out_cts || !cts_out))
+        return report(err, err_len, who + ": null inputs, out_cts or cts_out"), VPBS_ERR_INVALID;
+    gate_inputs_host(prog, log_n, K, n_lwe, inputs, instances, out_cts, cts_out);
+    return VPBS_OK;
+}
+
+int vpbs_program_aggregate_root(const vpbs_program* prog, unsigned N, unsigned K, unsigned n_lwe, const uint64_t* vk0, const uint64_t* inputs,
+                                const uint64_t* testvs, const uint64_t* out_cts, const uint64_t* key_hash, uint64_t out[4], char* err, size_t err_len) {
+    using namespace vpbs;
+    const std::string who = "vpbs_program_aggregate_root";
+    report(err, err_len, "");
+    unsigned log_n = 0;
+    std::string msg;
+    if (!statement_shape_ok(prog, N, K, n_lwe, who, &log_n, &msg)) return report(err, err_len, msg), VPBS_ERR_INVALID;
+    if (prog->n_gates == 0) return report(err, err_len, who + ": the program has no gates: there is nothing to aggregate"), VPBS_ERR_INVALID;
+    if (!vk0 || (prog->n_inputs && !inputs) || !testvs || !out_cts || !key_hash || !out)
+        return report(err, err_len, who + ": null vk0, inputs, testvs, out_cts, key_hash or out"), VPBS_ERR_INVALID;
+    std::vector<u64> cts((size_t)prog->n_gates * (n_lwe + 1));
+    gate_inputs_host(prog, log_n, K, n_lwe, inputs, 1, out_cts, cts.data());
+    const int rc = vpbs_aggregate_root(N, K, n_lwe, vk0, prog->n_gates, testvs, prog->n_luts, prog->given.lut.data(), cts.data(), out_cts, key_hash, 1,
+                                       nullptr, out);
+    if (rc < 0) report(err, err_len, who + ": vpbs_aggregate_root refused the statement");
+    return rc;
+}
+
+int vpbs_program_verify_aggregate(const vpbs_program* prog, const vpbs_aggregate_shape* shape, const uint64_t* inputs, const uint64_t* testvs,
+                                  const uint64_t* out_cts, const uint64_t* key_hash, const uint8_t* bytes, size_t len, int* reason, char* why,
+                                  size_t why_len) {
+    using namespace vpbs;
+    const std::string who = "vpbs_program_verify_aggregate";
+    report(why, why_len, "");
+    if (reason) *reason = VPBS_AGG_MALFORMED;
+    if (!shape) return report(why, why_len, who + ": null shape"), VPBS_ERR_INVALID;
+    unsigned log_n = 0;
+    std::string msg;
+    if (!statement_shape_ok(prog, shape->N, shape->K, shape->n_lwe, who, &log_n, &msg)) return report(why, why_len, msg), VPBS_ERR_INVALID;
+    if (prog->n_gates == 0) return report(why, why_len, who + ": the program has no gates: there is nothing to aggregate"), VPBS_ERR_INVALID;
+    if (shape->levels < 32 && prog->n_gates > ((size_t)1 << shape->levels))
+        return report(why, why_len, who + ": n_gates " + std::to_string(prog->n_gates) + " exceeds 2^levels = " +
+                                        std::to_string((size_t)1 << shape->levels)), VPBS_ERR_INVALID;
+    if ((prog->n_inputs && !inputs) || !testvs || !out_cts || !key_hash || !bytes)
+        return report(why, why_len, who + ": null inputs, testvs, out_cts, key_hash or bytes"), VPBS_ERR_INVALID;
+    std::vector<u64> cts((size_t)prog->n_gates * (shape->n_lwe + 1));
+    gate_inputs_host(prog, log_n, shape->K, shape->n_lwe, inputs, 1, out_cts, cts.data());
+    return vpbs_verify_aggregate(shape, prog->n_gates, testvs, prog->n_luts, prog->given.lut.data(), cts.data(), out_cts, key_hash, 1, nullptr, bytes,
+                                 len, reason, why, why_len);
+}
+
+}  // extern "C"
+
+namespace {
+// the proofs of a prove / prove_batch run, kept for the aggregator, and the caller's own proof_fn behind them
+struct ProofSink {
+    std::vector<std::vector<uint8_t>> proofs;
+    std::vector<uint8_t> have;
+    std::string failure;   // the first failing row, named
+    vpbs_pbs_proof_fn fn;
+    void* user;
+    static void take(void* self, size_t index, const uint8_t* bytes, size_t len, const char* error) {
+        auto* s = static_cast<ProofSink*>(self);
+        if (index < s->proofs.size()) {
+            if (bytes) {
+                s->proofs[index].assign(bytes, bytes + len);
+                s->have[index] = 1;
+            } else if (s->failure.empty()) {
+                s->failure = std::to_string(index) + ": " + (error ? error : "no proof");
+            }
+        }
+        if (s->fn) s->fn(s->user, index, bytes, len, error);
+    }
+    // the proofs [first, first + count) in one buffer with offsets, as vpbs_aggregator_run takes them
+    void pack(size_t first, size_t count, std::vector<uint8_t>* bytes, std::vector<size_t>* offsets) const {
+        bytes->clear();
+        offsets->assign(1, 0);
+        for (size_t i = first; i < first + count; ++i) {
+            bytes->insert(bytes->end(), proofs[i].begin(), proofs[i].end());
+            offsets->push_back(bytes->size());
+        }
+    }
+};
+// the refusal both aggregate provers make before anything is proven: "" when the program fits the aggregator
+std::string gates_fit(const vpbs_program* prog, const vpbs_aggregator* aggregator) {
+    const unsigned levels = vpbs::aggregator_levels(aggregator);
+    if (prog->n_gates == 0) return "the program has no gates: there is nothing to aggregate";
+    if (prog->n_gates > ((size_t)1 << levels))
+        return "n_gates " + std::to_string(prog->n_gates) + " exceeds 2^levels = " + std::to_string((size_t)1 << levels) + " of the aggregator";
+    return "";
+}
+}  // namespace
+
+extern "C" {
+long vpbs_program_prove_aggregate(vpbs_program* prog, vpbs_pbs_prover* pbs_prover, vpbs_aggregator* aggregator, const uint64_t* inputs,
+                                  const uint64_t* testvs, uint64_t* wires_out, uint64_t* out_cts, uint8_t* out, size_t capacity,
+                                  vpbs_aggregate_stats* stats, vpbs_pbs_proof_fn proof_fn, void* user, char* err, size_t err_len) {
+    using namespace vpbs;
+    const std::string who = "vpbs_program_prove_aggregate: ";
+    auto refuse = [&](const std::string& m) {
+        report(err, err_len, who + m);
+        return (long)VPBS_ERR_INVALID;
+    };
+    report(err, err_len, "");
+    if (stats) *stats = vpbs_aggregate_stats{};
+    if (!prog || !pbs_prover || !aggregator || !out) return refuse("null program, prover, aggregator or out");
+    const std::string fit = gates_fit(prog, aggregator);
+    if (!fit.empty()) return refuse(fit);
+    ProofSink sink{std::vector<std::vector<uint8_t>>(prog->n_gates), std::vector<uint8_t>(prog->n_gates, 0), "", proof_fn, user};
+    const long n = vpbs_program_prove(prog, pbs_prover, inputs, testvs, 0, wires_out, out_cts, &ProofSink::take, &sink, err, err_len);
+    if (n < 0) return n;
+    if (!sink.failure.empty() || (size_t)n != prog->n_gates) return refuse((sink.failure.empty() ? "proofs are missing" : "gate " + sink.failure) + "; nothing was aggregated");
+    std::vector<uint8_t> bytes;
+    std::vector<size_t> offsets;
+    sink.pack(0, prog->n_gates, &bytes, &offsets);
+    return vpbs_aggregator_run(aggregator, bytes.data(), offsets.data(), prog->n_gates, out, capacity, stats, err, err_len);
+}
+
+long vpbs_program_prove_aggregate_batch(vpbs_program* prog, vpbs_ring_prover* ring_prover, vpbs_aggregator* aggregator, const uint64_t* inputs,
+                                        size_t instances, const uint32_t* key_of, const uint64_t* testvs, uint64_t* wires_out, uint64_t* out_cts,
+                                        vpbs_aggregate_fn agg_fn, vpbs_pbs_proof_fn proof_fn, void* user, char* err, size_t err_len) {
+    using namespace vpbs;
+    const std::string who = "vpbs_program_prove_aggregate_batch: ";
+    auto refuse = [&](const std::string& m) {
+        report(err, err_len, who + m);
+        return (long)VPBS_ERR_INVALID;
+    };
+    report(err, err_len, "");
+    if (!prog || !ring_prover || !aggregator) return refuse("null program, ring prover or aggregator");
+    if (!agg_fn) return refuse("no agg_fn: the aggregates have nowhere to go");
+    const std::string fit = gates_fit(prog, aggregator);
+    if (!fit.empty()) return refuse(fit);
+    const size_t G = prog->n_gates;
+    if (instances > 0x7fffffffull / G) return refuse("instances x gates exceeds 2^31 - 1 rows");
+    ProofSink sink{std::vector<std::vector<uint8_t>>(instances * G), std::vector<uint8_t>(instances * G, 0), "", proof_fn, user};
+    const long n = vpbs_program_prove_batch(prog, ring_prover, inputs, instances, key_of, testvs, 0, wires_out, out_cts, &ProofSink::take, &sink, err,
+                                            err_len);
+    if (n < 0) return n;
+    if (!sink.failure.empty() || (size_t)n != instances * G)
+        return refuse((sink.failure.empty() ? "proofs are missing" : "row " + sink.failure + " (row b * n_gates + g)") + "; nothing was aggregated");
+    std::vector<uint8_t> bytes, agg(aggregator_max_bytes(aggregator));
+    std::vector<size_t> offsets;
+    for (size_t b = 0; b < instances; ++b) {
+        sink.pack(b * G, G, &bytes, &offsets);
+        const long len = vpbs_aggregator_run(aggregator, bytes.data(), offsets.data(), G, agg.data(), agg.size(), nullptr, err, err_len);
+        if (len < 0) return len;
+        agg_fn(b, agg.data(), (size_t)len, user);
+    }
+    return (long)instances;
+}
+
+long vpbs_program_verify_aggregate_batch(vpbs_program* prog, vpbs_aggregate_verifier* agg_verifier, const uint64_t* inputs, size_t instances,
+                                         const uint32_t* key_of, const uint64_t* key_hashes, size_t n_keys, const uint64_t* testvs,
+                                         const uint64_t* out_cts, const uint8_t* bytes, const size_t* offsets, uint8_t* verdicts, uint8_t* reasons,
+                                         char* err, size_t err_len) {
+    using namespace vpbs;
+    const std::string who = "vpbs_program_verify_aggregate_batch";
+    auto refuse = [&](const std::string& m) {
+        report(err, err_len, m);
+        return (long)VPBS_ERR_INVALID;
+    };
+    report(err, err_len, "");
+    if (!agg_verifier) return refuse(who + ": null aggregate verifier");
+    if (!prog) return refuse(who + ": null program");
+    if (!prog->ctx) return refuse(who + ": a host-only program (made without a context) cannot be verified on the device");
+    AggregateVerifierShape sh{};
+    aggregate_verifier_shape(agg_verifier, &sh);
+    vpbs_ctx* ctx = sh.ctx;
+    const unsigned n_in = prog->n_inputs, n_gates = prog->n_gates, words = sh.n_lwe + 1;
+    const size_t n = sh.N, kn = (size_t)sh.K * n, n_outs = prog->n_outs, n_wires = (size_t)n_in + n_outs, B = instances, rows = B * n_gates;
+    const bool multi = prog->multi;
+    if (ctx->device != prog->ctx->device) return refuse(who + ": the program and the aggregate verifier are on different devices");
+    unsigned log_n = 0;
+    std::string msg;
+    if (!statement_shape_ok(prog, sh.N, sh.K, sh.n_lwe, who, &log_n, &msg)) return refuse(msg);
+    if (n_gates == 0) return refuse(who + ": the program has no gates: there is nothing to aggregate");
+    if (n_gates > ((size_t)1 << sh.levels) || n_gates > sh.max_leaves)
+        return refuse(who + ": n_gates " + std::to_string(n_gates) + " exceeds 2^levels = " + std::to_string((size_t)1 << sh.levels) +
+                      " or max_leaves " + std::to_string(sh.max_leaves) + " of the aggregate verifier");
+    if (n_wires && B > 0x7fffffffull / n_wires) return refuse(who + ": instances x wires exceeds 2^31 - 1 rows");
+    if (B && (!key_of || !key_hashes || (n_in && !inputs) || !testvs || !out_cts || !bytes || !offsets || !verdicts))
+        return refuse(who + ": null key_of, key_hashes, inputs, testvs, out_cts, bytes, offsets or verdicts");
+    for (size_t b = 0; b < B; ++b) {
+        if (key_of[b] >= n_keys)
+            return refuse(who + ": key_of[" + std::to_string(b) + "] = " + std::to_string(key_of[b]) + " is not below n_keys " + std::to_string(n_keys));
+        if (offsets[b + 1] < offsets[b]) return refuse(who + ": offsets decrease at instance " + std::to_string(b));
+    }
+    if (B == 0) return 0;
+    // instances per run of the verifier; testv_of = gate_lut tiled, key_of of the row's instance, the trees' first leaves: host arrays
+    const size_t per = std::min(sh.max_aggregates, sh.max_leaves / n_gates);
+    std::vector<u32> lut_of(per * n_gates), key_row(rows);
+    std::vector<size_t> leaf_first(per + 1);
+    for (size_t b = 0; b < per; ++b) std::copy(prog->given.lut.begin(), prog->given.lut.end(), lut_of.begin() + b * n_gates);
+    for (size_t b = 0; b <= per; ++b) leaf_first[b] = b * n_gates;
+    for (size_t b = 0; b < B; ++b) std::fill(key_row.begin() + b * n_gates, key_row.begin() + (b + 1) * n_gates, key_of[b]);
+    std::vector<u32> ext;   // multi: extraction index | claimed GLWE of every output row b * n_outs + o (as verify_batch)
+    if (multi) {
+        ext.resize(2 * B * n_outs);
+        for (size_t b = 0; b < B; ++b)
+            for (size_t g = 0; g < n_gates; ++g)
+                for (u32 o = prog->out_first[g]; o < prog->out_first[g + 1]; ++o) {
+                    ext[b * n_outs + o] = o - prog->out_first[g];
+                    ext[B * n_outs + b * n_outs + o] = (u32)(b * n_gates + g);
+                }
+    }
+    long accepted = 0;
+    try {
+        VPBS_HIP(hipSetDevice(ctx->device));
+        hipStream_t s = ctx->stream;
+        Scratch mem(ctx);
+        try {
+            u64* d_wires = mem.words(B * n_wires * words);   // [B][n_in] inputs, then [B][n_outs] extractions
+            u64* d_out = mem.words(rows * kn);
+            u64* d_cts = mem.words(rows * words);
+            u64* d_testvs = mem.words((size_t)prog->n_luts * n);
+            u64* d_khs = mem.words(4 * n_keys);
+            u32* d_ext = multi ? reinterpret_cast<u32*>(mem.words(B * n_outs)) : nullptr;
+            if (n_in) VPBS_HIP(hipMemcpyAsync(d_wires, inputs, 8 * B * n_in * words, hipMemcpyHostToDevice, s));
+            VPBS_HIP(hipMemcpyAsync(d_out, out_cts, 8 * rows * kn, hipMemcpyHostToDevice, s));
+            VPBS_HIP(hipMemcpyAsync(d_testvs, testvs, 8 * (size_t)prog->n_luts * n, hipMemcpyHostToDevice, s));
+            VPBS_HIP(hipMemcpyAsync(d_khs, key_hashes, 32 * n_keys, hipMemcpyHostToDevice, s));
+            if (multi) VPBS_HIP(hipMemcpyAsync(d_ext, ext.data(), sizeof(u32) * ext.size(), hipMemcpyHostToDevice, s));
+            if (!multi) lwe_extract_enqueue(s, d_out, log_n, sh.K, sh.n_lwe, rows, d_wires + B * n_in * words);
+            else lwe_extract_at_enqueue(s, d_out, d_ext, d_ext + B * n_outs, log_n, sh.K, sh.n_lwe, B * n_outs, d_wires + B * n_in * words);
+            {
+                vpbs::Timed t(ctx, "lwe_combine");
+                const CombineRowsArgs a{d_wires, prog->d_given.first, prog->d_given.src, prog->d_given.coef, prog->d_given.cst, d_cts, B, n_in, n_gates,
+                                        words, (unsigned)n_outs, multi ? prog->d_given_slots : nullptr, log_n};
+                if (multi) hipLaunchKernelGGL(lwe_combine_rows_kernel<true>, dim3((unsigned)rows), dim3(256), 0, s, a);
+                else hipLaunchKernelGGL(lwe_combine_rows_kernel<false>, dim3((unsigned)rows), dim3(256), 0, s, a);
+            }
+            VPBS_HIP(hipGetLastError());
+            // the verifier's stages follow on the same stream: the tables stay where they are
+            for (size_t b0 = 0; b0 < B; b0 += per) {
+                const size_t c = std::min(per, B - b0), r0 = b0 * n_gates;
+                const long rc = vpbs_aggregate_verifier_run_many(agg_verifier, bytes, offsets + b0, c, leaf_first.data(), d_testvs, prog->n_luts,
+                                                                 lut_of.data(), d_cts + r0 * words, d_out + r0 * kn, d_khs, n_keys, key_row.data() + r0, 1,
+                                                                 verdicts + b0, reasons ? reasons + b0 : nullptr, err, err_len);
+                if (rc < 0) return rc;
+                accepted += rc;
+            }
+        } catch (const DeviceError&) {
             (void)vpbs::stream_sync(s);
             throw;
         }

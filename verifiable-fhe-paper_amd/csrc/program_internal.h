@@ -113,6 +113,16 @@ void pbs_verify_abandon(PbsVerifyCore* c, const DeviceError& e);
 // chains of d_ct [count][n_lwe + 1], one 16-lane group per ciphertext.  Throws vpbs::DeviceError for a failed launch.
 void lwe_chain_enqueue(void* stream, const uint64_t* d_ct, unsigned n_lwe, size_t count, uint64_t* d_out);
 
+// ---- aggregation (aggregate.hip), for the program calls that end in one aggregate per instance ----
+unsigned aggregator_levels(const vpbs_aggregator* a);     // up to 2^levels leaves
+size_t aggregator_max_bytes(const vpbs_aggregator* a);    // a capacity that holds the aggregate proof of every level
+struct AggregateVerifierShape {
+    vpbs_ctx* ctx;
+    unsigned N, K, n_lwe, levels;   // levels: those the verifier has a batch verifier for
+    size_t max_leaves, max_aggregates;
+};
+void aggregate_verifier_shape(const vpbs_aggregate_verifier* v, AggregateVerifierShape* out);
+
 // ---- the ring verifier (verify_pbs_batch.hip) ----
 struct RingVerifierShape {
     vpbs_ctx* ctx;
