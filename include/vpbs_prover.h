@@ -1421,6 +1421,39 @@ long vpbs_aggregator_run(vpbs_aggregator* a, const uint8_t* bytes, const size_t*
                          size_t capacity, vpbs_aggregate_stats* stats, char* err, size_t err_len);
 int vpbs_aggregator_last_run(const vpbs_aggregator* a, vpbs_aggregate_stats* out);
 void vpbs_aggregator_free(vpbs_aggregator* a);
+/* The node witnesses of a tree level in ONE device batch.  The default is the host path above and stays it.
+ * set_device_witness: max_nodes = 0 selects the host path (the state after create); max_nodes >= 1 makes, per level circuit A_l, one
+ *   vpbs_witness_device of the level's own FULL plan (vpbs_witness_device_create: level launch by level launch, no kernel waits for another
+ *   workgroup) with max_batch = max_nodes.  A level circuit with a generator that has no device form, or an allocation that fails: VPBS_ERR_INVALID
+ *   with the device object's own message, and the aggregator stays on the host path.
+ *   A level of a run then takes its distinct nodes (vpbs_aggregate_level_jobs) in chunks of at most max_nodes; per chunk every DISTINCT child
+ *   proof is uploaded once as one row flat | pis (pinned memory, the context's stream), ag_presets_kernel assembles the preset matrix
+ *   [n_preset][batch] on the device, the plan runs for the chunk, and per node the public inputs are read back, the wires gathered into the
+ *   device matrix and proven there: no wire matrix crosses PCIe.  Every output is byte for byte the host path's.  A value error of a chunk ends
+ *   the run with "level l: witness: <device message>" and nothing written to out.  Leaves are verified before anything is queued, as on the
+ *   host path.  On this path vpbs_aggregate_stats.witness_ms is the host wall time spent waiting for the batches.
+ * device_stats: of the last run {nodes whose witness came from the device, witness batches run, device-witness microseconds (HIP events
+ *   around the batches), microseconds of reading public inputs and gathering wires}; all 0 after a run on the host path.
+ * level_jobs (host only; the one statement of the padding rule, which run and run_many both use): the distinct nodes of `level` (1 ..) over
+ *   the trees of counts[n_trees] leaves, tree by tree in order.  Tree t of depth d = max(1, ceil(log2 count)) has m_0 = count entries at level
+ *   0 and m_l = min(2^(d - l), m_{l-1} div 2 + 1) distinct nodes at level l <= d -- a padding node whose children are those of its left
+ *   neighbour is that neighbour -- and none above d.  Node k of the tree stands on entries min(2 k, m - 1) and min(2 k + 1, m - 1) of its m =
+ *   m_{l-1} entries below.  tree[j], left[j], right[j] (each may be NULL when capacity is 0): the node's tree and its children as indices
+ *   into the list this function returns for level - 1 (level 1: into the leaves of all trees, concatenated).  Returns the number of nodes
+ *   (only the first `capacity` are written), or VPBS_ERR_INVALID: null counts, n_trees = 0, level = 0, an empty tree, 2^32 leaves or more.
+ * run_many: MANY trees in one run; tree t aggregates its counts[t] consecutive leaves, fn(user, t, proof, len) is called in tree order
+ *   with an aggregate that is byte for byte vpbs_aggregator_run's on those leaves.  Refused before anything is queued: n_trees = 0, an
+ *   empty tree, a tree above 2^levels, offsets that decrease.  ALL leaves of all trees are checked first: a bad one is named "tree t, leaf i:
+ *   ...", nothing is proven and no callback is made.  On the host path the trees are then aggregated one after the other; on the device path
+ *   the level-l nodes of ALL trees that have a level l form the chunks, and a tree of depth d has its root after level d while deeper trees
+ *   go on.  vpbs_aggregator_last_run then holds the sums over the trees (depth: the largest).  Returns n_trees, or < 0. */
+int vpbs_aggregator_set_device_witness(vpbs_aggregator* a, unsigned max_nodes, char* err, size_t err_len);
+int vpbs_aggregator_device_stats(const vpbs_aggregator* a, uint64_t out[4]);
+int vpbs_aggregate_level_jobs(const size_t* counts, size_t n_trees, unsigned level, uint32_t* tree, uint32_t* left, uint32_t* right,
+                              size_t capacity);
+typedef void (*vpbs_aggregate_tree_fn)(void* user, size_t tree, const uint8_t* proof, size_t len);
+long vpbs_aggregator_run_many(vpbs_aggregator* a, const uint8_t* bytes, const size_t* offsets /* [sum of counts + 1] */, const size_t* counts,
+                              size_t n_trees, vpbs_aggregate_tree_fn fn, void* user, char* err, size_t err_len);
 /* vpbs_verify_aggregate on the device: the leaf statements (one 16-lane group per leaf absorbs the n_pi words as it generates them from
  * the statement's parts -- the public-input vector is never materialised), the LWE chains, the fold (one launch per level), the root proof
  * through the batch verifier's stages with a batch of one, and a one-lane kernel that orders the reasons as the host does.  The word arrays
@@ -1484,6 +1517,9 @@ int vpbs_aggregate_verifier_roots_many(vpbs_aggregate_verifier* v, size_t n_agg,
  *     (capacity bytes); returns its length.  proof_fn (may be NULL) still sees every gate's proof; stats may be NULL.
  *   prove_aggregate_batch: vpbs_program_prove_batch, then ONE aggregate PER INSTANCE, delivered through agg_fn in instance order: aggregate b
  *     is byte for byte what prove_aggregate gives on a vpbs_pbs_prover of the key set in slot key_of[b].  Returns the number delivered.
+ *     With the aggregator's device witness on (vpbs_aggregator_set_device_witness) all instances go to ONE vpbs_aggregator_run_many -- the
+ *     level-l nodes of all instances in the same device batches; agg_fn still sees the same bytes in instance order.  With it off: one
+ *     vpbs_aggregator_run per instance, one after the other.
  *   Both refuse, before anything is proven and without calling a callback, a program of more than 2^levels gates of the aggregator (the
  *   message names n_gates and 2^levels) or of none, and whatever prove / prove_batch refuse.  A gate whose chain fails ends the call with
  *   that gate named; nothing is aggregated then.  Aggregation runs after the last proof.

@@ -5,7 +5,7 @@ ALL proofs through api.PbsVerifier built from the prover's key_hash() and all lw
 reference's main.rs:59-64).  One JSON line.
 
 usage: tools/prove_batch.py [--count M] [--chains C] [--witness-batch B] [--steps K] [--n2048 | --n8] [--keys-on-device] [--baseline]
-                            [--keys M [--baseline]] [--checkpoint DIR:every] [--resume DIR] [--aggregate]
+                            [--keys M [--baseline]] [--checkpoint DIR:every] [--resume DIR] [--aggregate [--aggregate-device [MAX_NODES]]]
   --steps K < n + 2 proves a prefix of every chain (tests); the proofs are then checked by api.verify_pbs_prefix on the host (verify_pbs
     insists on counter = n + 2); the outputs are those of the whole bootstrap either way.
   --n8: the N = 8, n = 6 miniature (degree 2^13); --n2048: N = 2048 (degree 2^17); default: the paper's N = 1024, n = 728 (degree 2^16).
@@ -28,7 +28,9 @@ usage: tools/prove_batch.py [--count M] [--chains C] [--witness-batch B] [--step
   --aggregate: after the proofs and their verification, ONE api.Aggregator folds all proofs into one proof (the level circuits are located
     as data: tools/export_circuits.py --aggregate N K ELL LOGB n_lwe log_n levels makes them), which api.verify_aggregate (host) and
     api.AggregateVerifier (device) check against the statement of the whole batch; the JSON line gains "aggregate": bytes, depth, nodes and
-    the times.  With --keys M too; not with --steps or --baseline, and only when every proof exists."""
+    the times.  With --keys M too; not with --steps or --baseline, and only when every proof exists.
+    --aggregate-device [MAX_NODES] (default 32): the aggregator's device witness -- the node witnesses of a tree level in
+    device batches of at most MAX_NODES; the same bytes.  "aggregate" shows the aggregator's "device_stats" beside its "last_run" either way."""
 import hashlib
 import argparse
 import json
@@ -195,18 +197,21 @@ def prove_baseline(args, N, n_lwe, log_n, cyc_path, dum_path, keys, cts, testv):
                                                                         "early_witness_ms_per_step": mean["early_witness_ms"]}
 
 
-def aggregate_section(ctx, N, n_lwe, log_n, cyc, vk, proofs, testv, cts, out_ct, key_hashes, key_of, leaves_seconds):
-    """--aggregate: fold `proofs` into one proof and verify it on the host and on the device -> the "aggregate" entry of the JSON line"""
+def aggregate_section(ctx, N, n_lwe, log_n, cyc, vk, proofs, testv, cts, out_ct, key_hashes, key_of, leaves_seconds, device_nodes=None):
+    """--aggregate: fold `proofs` into one proof and verify it on the host and on the device -> the "aggregate" entry of the JSON line;
+    device_nodes (--aggregate-device): the node witnesses of a level in device batches of at most that many (Aggregator.set_device_witness)"""
     count = len(proofs)
     depth = api.aggregate_depth(count)
     levels = [circuit_file.load(p) for p in circuit_file.find_aggregate_circuits(N, K, ELL, LOGB, n_lwe, log_n, depth)]
     t = time.perf_counter()
     agg = api.Aggregator(ctx, cyc, vk, levels)
+    if device_nodes:
+        agg.set_device_witness(device_nodes)
     t_create = time.perf_counter() - t
     t = time.perf_counter()
     blob = agg.aggregate(proofs)
     t_run = time.perf_counter() - t
-    run, vks = agg.last_run(), agg.verifier_data()
+    run, vks, device_stats = agg.last_run(), agg.verifier_data(), agg.device_stats()
     agg.close()
     shape = api.AggregateShape(N, K, n_lwe, vks, levels)
     statement = (np.asarray(testv, np.uint64).reshape(1, N), cts, np.asarray(out_ct, np.uint64).reshape(count, K * N), np.stack(key_hashes), key_of)
@@ -220,7 +225,8 @@ def aggregate_section(ctx, N, n_lwe, log_n, cyc, vk, proofs, testv, cts, out_ct,
     t_device = time.perf_counter() - t
     av.close()
     leaf_bytes = sum(len(b) for b in proofs)
-    return {"count": count, "depth": depth, "nodes": run["nodes"], "level_degree_bits": [d.log_n for d in levels], "bytes": len(blob),
+    return {"count": count, "depth": depth, "nodes": run["nodes"], "last_run": run, "device_stats": device_stats,
+            "level_degree_bits": [d.log_n for d in levels], "bytes": len(blob),
             "leaf_bytes_total": leaf_bytes, "bytes_ratio": len(blob) / leaf_bytes, "sha256": hashlib.sha256(blob).hexdigest(),
             "create_seconds": t_create, "aggregate_seconds": t_run, "check_leaves_ms_16_host_threads": run["check_leaves_ms"],
             "node_witness_ms": run["witness_ms"] / max(run["nodes"], 1), "node_prove_ms": run["prove_ms"] / max(run["nodes"], 1),
@@ -318,7 +324,8 @@ def main_keys(args, N, n_lwe, log_n):
     decrypted = sum(1 for i in range(count) if rounded(api.lwe_decrypt(keys[key_of[i]]["s_lwe"], lwe_out[i]), delta) == msgs[i])
     aggregated = True
     if args.aggregate and len(live) == count:
-        figures["aggregate"] = aggregate_section(ctx, N, n_lwe, log_n, cyc, vk, proofs, testv, cts, out_ct, hashes, key_of, t_end - t_made)
+        figures["aggregate"] = aggregate_section(ctx, N, n_lwe, log_n, cyc, vk, proofs, testv, cts, out_ct, hashes, key_of, t_end - t_made,
+                                               args.aggregate_device)
         aggregated = figures["aggregate"]["accepted"]
     ctx.close()
     print(json.dumps(dict({
@@ -347,7 +354,10 @@ def main():
     ap.add_argument("--checkpoint", default="", metavar="DIR:every")
     ap.add_argument("--resume", default="", metavar="DIR")
     ap.add_argument("--aggregate", action="store_true")
+    ap.add_argument("--aggregate-device", type=int, nargs="?", const=32, default=None, metavar="MAX_NODES")
     args = ap.parse_args()
+    if args.aggregate_device is not None and (not args.aggregate or args.aggregate_device < 1):
+        raise SystemExit("--aggregate-device [max_nodes] (at least 1; default 32) is a switch of --aggregate")
     if args.aggregate and (args.baseline or args.steps):
         raise SystemExit("--aggregate folds whole vPBS proofs of the batch provers: it cannot run with --baseline or --steps")
     if args.baseline and (args.checkpoint or args.resume):
@@ -407,7 +417,7 @@ def main():
         decrypted = sum(1 for m, want in zip(api.lwe_decrypt(keys["s_lwe"], lwe_out), msgs) if rounded(m, delta) == want)
     aggregated = True
     if args.aggregate and len(live) == args.count:
-        extra["aggregate"] = aggregate_section(ctx, N, n_lwe, log_n, cyc, vk, proofs, testv, cts, out_ct, [kh], None, seconds)
+        extra["aggregate"] = aggregate_section(ctx, N, n_lwe, log_n, cyc, vk, proofs, testv, cts, out_ct, [kh], None, seconds, args.aggregate_device)
         aggregated = extra["aggregate"]["accepted"]
     if args.keys_on_device:
         ctx.device_free(keys["d_bsk"])

@@ -5,12 +5,15 @@ user had to before api.Program existed (the baseline leg: Bootstrapper.run per l
 compared wire by wire.  One JSON line.
 
 usage: tools/run_program.py [--levels L] [--width W] [--fan-in F] [--program FILE.json] [--n8] [--prove] [--baseline] [--runs R] [--seed S]
-                            [--instances B --keys M [--verify-per-instance]] [--multi THETA] [--aggregate]
+                            [--instances B --keys M [--verify-per-instance]] [--multi THETA] [--aggregate [--aggregate-device [MAX_NODES]]]
   --aggregate (with --prove, alone or with --instances B --keys M): ONE proof per program instance.  The gate proofs of
     every instance are folded by an api.Aggregator (api.Program.prove_aggregate / prove_aggregate_batch; the level circuits are located as
     data: tools/export_circuits.py --aggregate N K ELL LOGB n_lwe log_n levels makes them, and the program may have at most 2^levels gates);
     every aggregate is verified on the host (api.program_verify_aggregate, the client's check) and all of them in one device run
     (api.Program.verify_aggregate_batch); the JSON line gains "aggregate": bytes, depth, both verdict lists and the bytes a client receives.
+    --aggregate-device [MAX_NODES] (default 32): the aggregator's device witness -- with --instances, the level-l nodes of ALL
+    instances in the same device batches of at most MAX_NODES, in ONE run of the aggregator; the same bytes.  "aggregate" shows the aggregator's
+    "device_stats" beside its "last_run" either way.
   --multi THETA: multi-output lookup gates.  W inputs, L layers of W lookups of 2^THETA tables over {0, 1} each; a later
     lookup reads every output of the one before it.  The multi leg makes ONE gate of each lookup (api.Program 5-tuples, api.lut_testv_multi);
     the single leg makes one gate per table of the same functions on the same inputs -- a plain program that runs unchanged on a build
@@ -146,12 +149,15 @@ def run_baseline(ctx, bs, n_inputs, gates, lv, inputs, testvs):
     return wires, event_ms
 
 
-def aggregate_setup(ctx, prog, N, n_lwe, log_n, cyc, vk, max_aggregates):
+def aggregate_setup(ctx, prog, N, n_lwe, log_n, cyc, vk, max_aggregates, device_nodes=None):
     """--aggregate: the Aggregator over the level circuits the program's gate count needs (located as data: tools/export_circuits.py
-    --aggregate makes them), the verifiers' shape and the device verifier -> (aggregator, shape, device verifier)"""
+    --aggregate makes them), the verifiers' shape and the device verifier -> (aggregator, shape, device verifier); device_nodes
+    (--aggregate-device): its node witnesses in device batches of at most that many (Aggregator.set_device_witness)"""
     depth = api.aggregate_depth(max(prog.n_gates, 1))
     levels = [circuit_file.load(p) for p in circuit_file.find_aggregate_circuits(N, K, ELL, LOGB, n_lwe, log_n, depth)]
     agg = api.Aggregator(ctx, cyc, vk, levels)
+    if device_nodes:
+        agg.set_device_witness(device_nodes)
     shape = api.AggregateShape(N, K, n_lwe, agg.verifier_data(), levels)
     return agg, shape, api.AggregateVerifier(ctx, shape, max_leaves=max_aggregates * prog.n_gates, max_aggregates=max_aggregates)
 
@@ -192,12 +198,13 @@ def prove_batch(args, ctx, prog, N, n_lwe, log_n, M, inputs, key_of, testvs, bat
     hashes, (vk, _) = [rp.key_hash(k) for k in range(M)], rp.verifier_data()
     aggregated = True
     if args.aggregate:   # one aggregate per instance: proven again, now folded, and checked on the host and on the device
-        agg, ashape, av = aggregate_setup(ctx, prog, N, n_lwe, log_n, cyc, vk, max(1, min(len(key_of), 64)))
+        agg, ashape, av = aggregate_setup(ctx, prog, N, n_lwe, log_n, cyc, vk, max(1, min(len(key_of), 64)), args.aggregate_device)
         t = time.perf_counter()
         blobs, _, agg_out = prog.prove_aggregate_batch(rp, agg, inputs, key_of, testvs)
         out["aggregate"] = aggregate_report(prog, ashape, av, blobs, inputs, key_of, hashes, testvs, agg_out, sum(len(p) for p in proofs[0]),
                                             time.perf_counter() - t)
         out["aggregate"]["out_cts_equal"] = bool((agg_out == out_cts).all())
+        out["aggregate"].update(last_run=agg.last_run(), device_stats=agg.device_stats())
         aggregated = out["aggregate"]["accepted"] and out["aggregate"]["out_cts_equal"]
         av.close()
         agg.close()
@@ -536,7 +543,10 @@ def main():
     ap.add_argument("--verify-per-instance", action="store_true")
     ap.add_argument("--multi", type=int)
     ap.add_argument("--aggregate", action="store_true")
+    ap.add_argument("--aggregate-device", type=int, nargs="?", const=32, default=None, metavar="MAX_NODES")
     args = ap.parse_args()
+    if args.aggregate_device is not None and (not args.aggregate or args.aggregate_device < 1):
+        raise SystemExit("--aggregate-device [max_nodes] (at least 1; default 32) is a switch of --prove --aggregate")
     if args.aggregate and (not args.prove or args.multi is not None):
         raise SystemExit("--aggregate folds the gate proofs of --prove into one proof per instance: it needs --prove and cannot run with --multi")
     if args.multi is not None:
@@ -615,12 +625,13 @@ def main():
             kh, (vk, _) = prover.key_hash(), prover.verifier_data()
             aggregated = True
             if args.aggregate:
-                agg, ashape, av = aggregate_setup(ctx, prog, N, n_lwe, log_n, cyc, vk, 1)
+                agg, ashape, av = aggregate_setup(ctx, prog, N, n_lwe, log_n, cyc, vk, 1, args.aggregate_device)
                 t = time.perf_counter()
                 blob, _, agg_out = prog.prove_aggregate(prover, agg, inputs, testvs)
                 out["aggregate"] = aggregate_report(prog, ashape, av, [blob], inputs[None], [0], [kh], testvs, agg_out[None], sum(len(p) for p in proofs),
                                                     time.perf_counter() - t)
                 out["aggregate"]["out_cts_equal"] = bool((agg_out == out_cts).all())
+                out["aggregate"].update(last_run=agg.last_run(), device_stats=agg.device_stats())
                 aggregated = out["aggregate"]["accepted"] and out["aggregate"]["out_cts_equal"]
                 av.close()
                 agg.close()

@@ -171,6 +171,7 @@ IVC_STEP_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_uint)
 IVC_CHECKPOINT_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_uint, C.POINTER(C.c_uint8), C.c_size_t)
 PBS_PROOF_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint8), C.c_size_t, C.c_char_p)
 AGGREGATE_FN = C.CFUNCTYPE(None, C.c_size_t, C.POINTER(C.c_uint8), C.c_size_t, C.c_void_p)   # vpbs_aggregate_fn
+AGGREGATE_TREE_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint8), C.c_size_t)   # vpbs_aggregate_tree_fn
 PBS_CHECKPOINT_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_size_t, C.c_uint, C.POINTER(C.c_uint8), C.c_size_t)
 
 
@@ -407,6 +408,10 @@ SIGNATURES = {
     "vpbs_aggregator_run": (C.c_long, [_vp, C.POINTER(C.c_uint8), C.POINTER(_sz), _sz, C.POINTER(C.c_uint8), _sz, _vp, C.c_char_p, _sz]),
     "vpbs_aggregator_last_run": (_i, [_vp, _vp]),
     "vpbs_aggregator_free": (None, [_vp]),
+    "vpbs_aggregator_set_device_witness": (_i, [_vp, _ui, C.c_char_p, _sz]),
+    "vpbs_aggregator_device_stats": (_i, [_vp, U64P]),
+    "vpbs_aggregate_level_jobs": (_i, [C.POINTER(_sz), _sz, _ui, _vp, _vp, _vp, _sz]),
+    "vpbs_aggregator_run_many": (C.c_long, [_vp, C.POINTER(C.c_uint8), C.POINTER(_sz), C.POINTER(_sz), _sz, AGGREGATE_TREE_FN, _vp, C.c_char_p, _sz]),
     "vpbs_aggregate_verifier_create": (_i, [_vp, _vp, _sz, C.POINTER(_vp), C.c_char_p, _sz]),
     "vpbs_aggregate_verifier_run": (_i, [_vp, C.POINTER(C.c_uint8), _sz, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _sz, _vp, _i, C.POINTER(_i),
                                          C.c_char_p, _sz]),
@@ -434,6 +439,7 @@ INTERNAL_SIGNATURES = {
     "vpbs_test_pbs_prover_preset_matrix": (_i, [_vp, U64P, U64P, _ui, _ui, U64P]),
     "vpbs_test_pbs_prover_preset_words": (_sz, [_vp]),
     "vpbs_test_pbs_prover_dummy_proof": (_i, [_vp, U64P]),
+    "vpbs_test_aggregator_preset_matrix": (_i, [_vp, _ui, U64P, _sz, _vp, _ui, U64P]),
 }
 
 _lib = None
@@ -2612,6 +2618,23 @@ def aggregate_many_args(counts, max_leaves=None, max_aggregates=None, levels=Non
     return np.concatenate([[0], np.cumsum(c)]).astype(np.uint64)
 
 
+def aggregate_level_jobs(counts, level):
+    """vpbs_aggregate_level_jobs (host only): the distinct nodes of `level` over trees of counts[t] leaves, tree by tree -> (tree, left,
+    right), np.uint32 [nodes] each; left / right index the list of level - 1 (level 1: the leaves of all trees, concatenated).  The padding
+    rule of Aggregator.aggregate and aggregate_many, stated once."""
+    aggregate_many_args(counts)
+    if int(level) < 1:
+        raise ValueError("aggregate_level_jobs: level is at least 1, got %r" % (level,))
+    c = np.asarray(counts).astype(np.uint64)
+    cp = c.ctypes.data_as(C.POINTER(C.c_size_t))
+    n = lib().vpbs_aggregate_level_jobs(cp, c.size, int(level), None, None, None, 0)
+    if n < 0:
+        raise VpbsError("vpbs_aggregate_level_jobs: status %d" % n)
+    tree, left, right = (np.zeros(max(n, 1), np.uint32) for _ in range(3))
+    lib().vpbs_aggregate_level_jobs(cp, c.size, int(level), tree.ctypes.data, left.ctypes.data, right.ctypes.data, n)
+    return tree[:n], left[:n], right[:n]
+
+
 class Aggregator:
     """vpbs_aggregator: folds serialised vPBS proofs into one proof.  leaf: the cyclic step circuit (a loaded circuit file) with its
     verifier data leaf_vk [68] (digest, cap: PbsProver / RingProver.verifier_data()[0]); level_circuits: A_1 .. A_levels as loaded circuit
@@ -2672,6 +2695,66 @@ class Aggregator:
         s = AggregateStatsC()
         lib().vpbs_aggregator_last_run(self.h, C.byref(s))
         return {k: getattr(s, k) for k, _ in AggregateStatsC._fields_}
+
+    def set_device_witness(self, max_nodes):
+        """vpbs_aggregator_set_device_witness: max_nodes >= 1 -- the node witnesses of a tree level in device batches of at most max_nodes
+        (the same bytes as the host path); 0 -- back to the host path, the default.  A level circuit without a device form, or memory that is
+        not there, raises VpbsError and leaves the host path on."""
+        if int(max_nodes) < 0:
+            raise ValueError("Aggregator.set_device_witness: max_nodes is 0 (the host path) or a batch size, got %r" % (max_nodes,))
+        err = C.create_string_buffer(512)
+        rc = lib().vpbs_aggregator_set_device_witness(self.h, int(max_nodes), err, 512)
+        if rc:
+            raise VpbsError("status %d: %s" % (rc, err.value.decode()))
+
+    def device_stats(self):
+        """vpbs_aggregator_device_stats of the last run: nodes whose witness came from the device, witness batches, device-witness
+        microseconds (HIP events around the batches), microseconds of reading public inputs and gathering wires"""
+        out = np.zeros(4, np.uint64)
+        lib().vpbs_aggregator_device_stats(self.h, _ptr(out))
+        return dict(zip(("nodes", "batches", "witness_us", "gather_us"), (int(v) for v in out)))
+
+    def aggregate_many(self, blob_lists, on_aggregate=None):
+        """vpbs_aggregator_run_many: one list of serialised vPBS proofs per tree -> the aggregates, in tree order; aggregate t is byte for
+        byte aggregate(blob_lists[t]).  All leaves are checked first: a bad one raises VpbsError("... tree t, leaf i: ...") before anything is
+        proven.  With the device witness on, the level-l nodes of ALL trees share the device batches.  on_aggregate(t, bytes) as they are made."""
+        counts = [len(b) for b in blob_lists]
+        aggregate_many_args(counts, levels=self.levels)
+        buf, offs = pack_proofs([b for blobs in blob_lists for b in blobs])
+        cnt = np.asarray(counts, np.uint64)
+        out, raised = [None] * len(counts), []
+
+        def take(_, tree, data, n):
+            try:
+                out[tree] = C.string_at(data, n)
+                if on_aggregate is not None and not raised:
+                    on_aggregate(int(tree), out[tree])
+            except BaseException as e:   # never through the C frames
+                raised.append(e)
+        cb = AGGREGATE_TREE_FN(take)
+        err = C.create_string_buffer(512)
+        data = buf.ctypes.data_as(C.POINTER(C.c_uint8)) if buf.size else (C.c_uint8 * 1)()
+        n = lib().vpbs_aggregator_run_many(self.h, data, offs.ctypes.data_as(C.POINTER(C.c_size_t)),
+                                           cnt.ctypes.data_as(C.POINTER(C.c_size_t)), len(counts), cb, None, err, 512)
+        if raised:
+            raise raised[0]
+        if n < 0:
+            e = VpbsError("status %d: %s" % (n, err.value.decode()))
+            e.status = n
+            raise e
+        return out
+
+    def test_preset_matrix(self, level, rows, pairs):
+        """vpbs_test_aggregator_preset_matrix (a test entry): rows [n_rows][row_words] child proofs flat | pis, pairs [batch][2] -> the preset
+        matrix [n_preset][batch] of that chunk of level-`level` nodes as the device path assembles it"""
+        r = np.ascontiguousarray(rows, dtype=np.uint64)
+        pr = np.ascontiguousarray(pairs, dtype=np.uint32).reshape(-1, 2)
+        n_preset = 2 * r.shape[1] + AGG_VK_WORDS * level
+        out = np.zeros((n_preset, pr.shape[0]), np.uint64)
+        rc = lib().vpbs_test_aggregator_preset_matrix(self.h, level, _ptr(r.reshape(-1)), r.shape[0], pr.ctypes.data, pr.shape[0], _ptr(out.reshape(-1)))
+        if rc:
+            raise VpbsError("vpbs_test_aggregator_preset_matrix: status %d" % rc)
+        return out
 
     def close(self):
         if self.h:
@@ -3098,7 +3181,8 @@ class Program:
     def prove_aggregate_batch(self, ring_prover, aggregator, inputs, key_of, testvs, on_aggregate=None):
         """one aggregate PER INSTANCE on a RingProver: prove_batch(), then instance by instance Aggregator.aggregate over its gate proofs
         -> (blobs [instances], wires, out_cts); blobs[b] is byte for byte prove_aggregate on a PbsProver of the key set in slot
-        key_of[b], and a client verifies its own with program_verify_aggregate.  on_aggregate(b, bytes) as they are made."""
+        key_of[b], and a client verifies its own with program_verify_aggregate.  on_aggregate(b, bytes) as they are made.  With the
+        aggregator's device witness on (Aggregator.set_device_witness) all instances are ONE run of the aggregator (aggregate_many's)."""
         if self.ctx is None:
             raise VpbsError("Program.prove_aggregate_batch: a host-only program (made without a context) cannot be evaluated")
         rp = ring_prover

@@ -7,12 +7,16 @@
 //   many-run   : vpbs_aggregate_verifier_run_many / _roots_many -- many trees in ONE run: ag_leaf_pair over all leaves (the
 //                LWE chain and the public-input sponge of a leaf side by side in one wave), ag_fold_many per level over the trees that have
 //                it, per depth ONE batch of root proofs and ag_result_many; the single-run entry points and their kernels are unchanged
+//   device witness : vpbs_aggregator_set_device_witness -- the distinct nodes of a level (of ALL trees of a run_many) in
+//                chunks: child proofs uploaded once each, ag_presets_kernel, the level's full plan on a vpbs_witness_device, per node gather + proof
 // The prover part is host code against the library's own C ABI, as ivc.hip is.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <chrono>
 #include <cstring>
+#include <functional>
+#include <iterator>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -23,6 +27,8 @@
 #include "context.h"
 #include "verify_batch.h"
 #include "program_internal.h"
+#include "ivc_resident.h"
+#include "test_entries.h"
 
 namespace {
 using vpbs::DeviceError;
@@ -40,6 +46,36 @@ unsigned depth_of(size_t count) {   // max(1, ceil(log2 count))
     unsigned d = 1;
     while (((size_t)1 << d) < count) ++d;
     return d;
+}
+
+// ================= which nodes a level has (host only) =================
+// The one statement of the padding rule (vpbs_aggregate_level_jobs in the header).  A tree of `count` leaves and depth d has m_0 = count
+// entries at level 0; the 2^(d - l + 1) positions of level l - 1 stand on entry min(position, m_{l-1} - 1), so node k of level l has the
+// children (min(2 k, m - 1), min(2 k + 1, m - 1)), and a node whose children are those of its left neighbour is that neighbour:
+// m_l = min(2^(d - l), m_{l-1} div 2 + 1).
+size_t distinct_nodes(size_t count, unsigned d, unsigned level) {
+    size_t m = count;
+    for (unsigned l = 1; l <= level; ++l) m = std::min((size_t)1 << (d - l), m / 2 + 1);
+    return m;
+}
+
+// the distinct nodes of `level` over all trees, children as indices into the list of level - 1 -> their number (the first `capacity` written)
+size_t level_jobs(const size_t* counts, size_t n_trees, unsigned level, u32* tree, u32* left, u32* right, size_t capacity) {
+    size_t below = 0, n = 0;
+    for (size_t t = 0; t < n_trees; ++t) {
+        const unsigned d = depth_of(counts[t]);
+        if (level - 1 > d) continue;   // the tree ended below level - 1
+        const size_t m = distinct_nodes(counts[t], d, level - 1);
+        const size_t mine = level <= d ? distinct_nodes(counts[t], d, level) : 0;
+        for (size_t k = 0; k < mine; ++k, ++n)
+            if (n < capacity) {
+                tree[n] = (u32)t;
+                left[n] = (u32)(below + std::min(2 * k, m - 1));
+                right[n] = (u32)(below + std::min(2 * k + 1, m - 1));
+            }
+        below += m;
+    }
+    return n;
 }
 
 // ================= the statement on the host =================
@@ -363,6 +399,53 @@ __global__ __launch_bounds__(64) void ag_result_many(const uint8_t* __restrict__
     out[2 * a] = reason == VPBS_AGG_OK ? 1 : 0;
     out[2 * a + 1] = reason;
 }
+
+// ================= the preset matrix of a chunk of nodes, on the device =================
+// rows [n_rows][row_words]: the distinct child proofs of the chunk, each flat | pis; tab [batch][2]: the (left row, right row) of every node;
+// vks: vk_0 .. vk_{l-1} as the level takes them.  The matrix is [2 row_words + vk_words][batch], instances innermost, in the order
+// vpbs_aggregator_create documents: slot 0 proof | slot 0 public inputs | slot 1 proof | slot 1 public inputs | vk_0 .. vk_{l-1}.
+struct PresetJob {
+    const u64* rows;
+    const u32* tab;
+    const u64* vks;
+    u32 row_words, vk_words, batch;
+};
+
+// blockIdx.z = slot 0 / 1: per node a contiguous child row, in the matrix one column.  A workgroup turns a tile of 32 nodes x 64 words in
+// LDS, as preset_transpose_kernel (pbs_prove_pool.hip) does for the chains: the rows are read coalesced (64 lanes on 512 contiguous bytes),
+// the columns written coalesced (32 lanes on the 32 instances of a matrix row); a tile row is padded by one word, so the 32 lanes of a half-wave
+// read words 65 apart -- all 64 banks, no conflict.  blockIdx.z = 2: the vk rows, every word broadcast over its row, consecutive lanes on
+// consecutive instances.  Bounds: tab[..] < n_rows (the host builds both from the same list), k0 + k < row_words and i < batch are tested.
+constexpr unsigned AG_TILE_I = 32, AG_TILE_K = 64;
+__global__ void __launch_bounds__(256) ag_presets_kernel(PresetJob j, u64* __restrict__ m) {
+    __shared__ u64 tile[AG_TILE_I][AG_TILE_K + 1];
+    if (blockIdx.z == 2) {
+        const size_t words = (size_t)j.vk_words * j.batch, stride = (size_t)gridDim.x * gridDim.y * 256;
+        for (size_t q = ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 256 + threadIdx.x; q < words; q += stride)
+            m[2 * (size_t)j.row_words * j.batch + q] = j.vks[q / j.batch];
+        return;
+    }
+    const u32 slot = blockIdx.z, k0 = blockIdx.x * AG_TILE_K, i0 = blockIdx.y * AG_TILE_I;
+    for (unsigned ii = threadIdx.x / AG_TILE_K; ii < AG_TILE_I; ii += 256 / AG_TILE_K) {
+        const unsigned k = threadIdx.x % AG_TILE_K, i = i0 + ii;
+        u64 v = 0;
+        if (i < j.batch && k0 + k < j.row_words) v = j.rows[(size_t)j.tab[2 * i + slot] * j.row_words + k0 + k];
+        tile[ii][k] = v;
+    }
+    __syncthreads();
+    for (unsigned k = threadIdx.x / AG_TILE_I; k < AG_TILE_K; k += 256 / AG_TILE_I) {
+        const unsigned ii = threadIdx.x % AG_TILE_I;
+        if (k0 + k < j.row_words && i0 + ii < j.batch) m[((size_t)slot * j.row_words + k0 + k) * j.batch + i0 + ii] = tile[ii][k];
+    }
+}
+
+// the fill of vpbs::witness_device_run_filled: user is the chunk's PresetJob
+int presets_fill(void* user, void* stream, uint64_t* d_matrix) {
+    const PresetJob& j = *static_cast<const PresetJob*>(user);
+    hipLaunchKernelGGL(ag_presets_kernel, dim3((j.row_words + AG_TILE_K - 1) / AG_TILE_K, (j.batch + AG_TILE_I - 1) / AG_TILE_I, 3), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), j, d_matrix);
+    return hipGetLastError() == hipSuccess ? VPBS_OK : VPBS_ERR_DEVICE;
+}
 }  // namespace
 
 struct vpbs_aggregate_verifier {
@@ -489,6 +572,7 @@ struct Level {   // one circuit A_l on the context
     u64* d_sigma = nullptr;
     vpbs_batch* cs = nullptr;
     vpbs_witness_plan* plan = nullptr;
+    vpbs_witness_device* wd = nullptr;   // the plan on the device, for batches of nodes (vpbs_aggregator_set_device_witness)
     vpbs_step_sizes sz{};
     size_t proof_words() const { return 3 * sz.cap_words + sz.openings_words + sz.fri_words; }
 
@@ -539,6 +623,8 @@ struct Level {   // one circuit A_l on the context
         return VPBS_OK;
     }
     void release() {
+        if (wd) vpbs_witness_device_free(wd);   // before the plan it replays
+        wd = nullptr;
         if (plan) vpbs_witness_plan_free(plan);
         if (cs) vpbs_batch_free(cs);
         if (d_sigma) vpbs_device_free(ctx, d_sigma);
@@ -561,14 +647,155 @@ struct vpbs_aggregator {
     u64 *bufs[2] = {nullptr, nullptr}, *d_wires = nullptr;
     size_t wire_words = 0;
     vpbs_aggregate_stats last{};
+    // the device witness: at most max_nodes nodes per batch (0: the host path); the child rows of a chunk and behind them its
+    // (left row, right row) table, pinned and on the device; vk_0 .. vk_{levels-1} resident; the last run's figures
+    unsigned max_nodes = 0;
+    size_t row_words_max = 0;
+    u64 *h_rows = nullptr, *d_rows = nullptr, *d_vks = nullptr;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    uint64_t dev_stats[4] = {0, 0, 0, 0};
     std::mutex mu;
+    void device_witness_off() {
+        for (auto& l : levels)
+            if (l.wd) {
+                vpbs_witness_device_free(l.wd);
+                l.wd = nullptr;
+            }
+        if (h_rows) (void)hipHostFree(h_rows);
+        if (d_rows) vpbs_device_free(ctx, d_rows);
+        if (d_vks) vpbs_device_free(ctx, d_vks);
+        for (auto& e : ev)
+            if (e) (void)hipEventDestroy(e);
+        h_rows = d_rows = d_vks = nullptr;
+        ev[0] = ev[1] = nullptr;
+        max_nodes = 0;
+    }
     ~vpbs_aggregator() {
+        device_witness_off();
         for (auto b : bufs)
             if (b) vpbs_host_free(b);
         if (d_wires) vpbs_device_free(ctx, d_wires);
         for (auto& l : levels) l.release();
     }
 };
+
+namespace {
+void check_leaves(const vpbs_aggregator* a, const uint8_t* bytes, const size_t* offsets, size_t count, std::vector<Proof>& cur,
+                  std::vector<std::string>& why);
+long tree_host(vpbs_aggregator* a, std::vector<Proof>& cur, size_t count, uint8_t* out, size_t capacity, std::string& msg);
+
+// a root node's proof, serialised -> the number of bytes, or < 0 with msg
+long root_bytes(vpbs_aggregator* a, const Level& L, const Proof& p, uint8_t* out, size_t capacity, std::string& msg) {
+    vpbs_step_inputs in{};
+    L.step_inputs(in, a->d_wires, p.pis.data());
+    const u64 *cp = p.flat.data(), *opn = cp + 3 * L.sz.cap_words, *fr = opn + L.sz.openings_words;
+    const long n = vpbs_step_proof_to_bytes(a->ctx, &in, L.n_const_cols, cp, opn, fr, out, capacity);
+    if (n > 0) return n;
+    msg = "the output buffer is too small for the aggregate proof";
+    return VPBS_ERR_INVALID;
+}
+
+// the child rows of a chunk and its (left row, right row) table, staged in h_rows and queued for d_rows on the context's stream -> the job
+// ag_presets_kernel takes.  ids: the DISTINCT children of the chunk, ascending; pairs [batch][2]: every node's children, as entries of ids.
+PresetJob presets_upload(vpbs_aggregator* a, const Level& L, unsigned l, const std::vector<const Proof*>& rows, const u32* pairs, unsigned batch) {
+    const size_t row_words = L.inner_words + L.inner_pi;
+    for (size_t r = 0; r < rows.size(); ++r) {
+        std::memcpy(a->h_rows + r * row_words, rows[r]->flat.data(), 8 * L.inner_words);
+        std::memcpy(a->h_rows + r * row_words + L.inner_words, rows[r]->pis.data(), 8 * L.inner_pi);
+    }
+    std::memcpy(a->h_rows + rows.size() * row_words, pairs, 8 * (size_t)batch);
+    VPBS_HIP(hipMemcpyAsync(a->d_rows, a->h_rows, 8 * (rows.size() * row_words + batch), hipMemcpyHostToDevice, a->ctx->stream));
+    return PresetJob{a->d_rows, reinterpret_cast<const u32*>(a->d_rows + rows.size() * row_words), a->d_vks, (u32)row_words, (u32)(VK * l), batch};
+}
+
+// ---- the trees of a run on the device path, level by level over ALL of them: the checked leaves of all trees in `cur`, concatenated.  A tree's
+// root goes to `root` after the level of its depth (a negative return ends the run).  VPBS_OK, or < 0 with msg ----
+using RootFn = std::function<long(size_t tree, const Level& L, const Proof& p)>;
+long trees_device(vpbs_aggregator* a, std::vector<Proof>& cur, const size_t* counts, size_t n_trees, const RootFn& root, std::string& msg) {
+    vpbs_ctx* ctx = a->ctx;
+    unsigned deepest = 0;
+    for (size_t t = 0; t < n_trees; ++t) deepest = std::max(deepest, depth_of(counts[t]));
+    vpbs_step_inputs in{};
+    try {
+        VPBS_HIP(hipSetDevice(ctx->device));
+        for (unsigned l = 1; l <= deepest; ++l) {
+            const Level& L = a->levels[l - 1];
+            const std::string at = "level " + std::to_string(l) + ": ";
+            std::vector<u32> tree(level_jobs(counts, n_trees, l, nullptr, nullptr, nullptr, 0)), left(tree.size()), right(tree.size());
+            level_jobs(counts, n_trees, l, tree.data(), left.data(), right.data(), tree.size());
+            std::vector<Proof> next(tree.size());
+            for (size_t first = 0; first < tree.size(); first += a->max_nodes) {
+                const unsigned batch = (unsigned)std::min<size_t>(a->max_nodes, tree.size() - first);
+                // 1. every distinct child of the chunk once; 2. + 3. the preset matrix and the plan behind the upload, on the context's stream
+                const double t0 = now();
+                std::vector<u32> ids;
+                for (unsigned j = 0; j < batch; ++j) {
+                    ids.push_back(left[first + j]);
+                    ids.push_back(right[first + j]);
+                }
+                std::sort(ids.begin(), ids.end());
+                ids.erase(std::unique(ids.begin(), ids.end()), ids.end());
+                std::vector<const Proof*> rows;
+                for (u32 id : ids) {
+                    if (cur[id].flat.size() != L.inner_words || cur[id].pis.size() != L.inner_pi) return msg = at + "the children do not have the circuit's shape", VPBS_ERR_INVALID;
+                    rows.push_back(&cur[id]);
+                }
+                std::vector<u32> pairs(2 * (size_t)batch);
+                for (unsigned j = 0; j < batch; ++j) {
+                    pairs[2 * j] = (u32)(std::lower_bound(ids.begin(), ids.end(), left[first + j]) - ids.begin());
+                    pairs[2 * j + 1] = (u32)(std::lower_bound(ids.begin(), ids.end(), right[first + j]) - ids.begin());
+                }
+                VPBS_HIP(hipEventRecord(a->ev[0], ctx->stream));
+                PresetJob job = presets_upload(a, L, l, rows, pairs.data(), batch);
+                const int wrc = vpbs::witness_device_run_filled(L.wd, batch, presets_fill, &job);
+                const std::string werr = wrc != 0 ? vpbs_last_error(ctx) : "";
+                VPBS_HIP(hipEventRecord(a->ev[1], ctx->stream));
+                VPBS_HIP(hipEventSynchronize(a->ev[1]));
+                float ms = 0;
+                VPBS_HIP(hipEventElapsedTime(&ms, a->ev[0], a->ev[1]));
+                a->last.witness_ms += 1e3 * (now() - t0);
+                ++a->dev_stats[1];
+                a->dev_stats[2] += (uint64_t)(1e3 * ms);
+                if (wrc != 0) return msg = at + "witness: " + werr, (long)wrc;
+                // 4. node by node: the public inputs, the wires into the device matrix, the proof
+                for (unsigned j = 0; j < batch; ++j) {
+                    const size_t node = first + j;
+                    const std::string at_node = "level " + std::to_string(l) + ", node " + std::to_string(node) + ": ";
+                    Proof& p = next[node];
+                    p.pis.resize(L.n_pi);
+                    const double tg = now();
+                    int rc = vpbs_witness_device_read(L.wd, j, L.pi_pos.data(), L.n_pi, p.pis.data());
+                    if (rc == 0) rc = vpbs_witness_device_wires(L.wd, j, a->d_wires);
+                    const double tp = now();
+                    a->dev_stats[3] += (uint64_t)(1e6 * (tp - tg));
+                    if (rc != 0) return msg = at_node + "gather: " + vpbs_last_error(ctx), (long)rc;
+                    p.flat.assign(L.proof_words(), 0);
+                    L.step_inputs(in, a->d_wires, p.pis.data());
+                    u64 *cp = p.flat.data(), *opn = cp + 3 * L.sz.cap_words, *fr = opn + L.sz.openings_words;
+                    rc = vpbs_prove_step(ctx, &in, cp, opn, fr, nullptr, nullptr);
+                    a->last.prove_ms += 1e3 * (now() - tp);
+                    if (rc != 0) return msg = at_node + "proof: " + vpbs_last_error(ctx), (long)rc;
+                    ++a->last.nodes;
+                    ++a->dev_stats[0];
+                }
+            }
+            // a tree whose depth this level is has exactly one node here: its root
+            for (size_t node = 0; node < tree.size(); ++node)
+                if (depth_of(counts[tree[node]]) == l) {
+                    const long rc = root(tree[node], L, next[node]);
+                    if (rc < 0) return rc;
+                }
+            cur.swap(next);
+        }
+    } catch (const DeviceError& e) {
+        (void)vpbs::stream_sync(ctx->stream);
+        ctx->err = e.what;
+        msg = e.what;
+        return e.status;
+    }
+    return VPBS_OK;
+}
+}  // namespace
 
 extern "C" {
 
@@ -727,6 +954,7 @@ long vpbs_aggregator_run(vpbs_aggregator* a, const uint8_t* bytes, const size_t*
     if (!a) return fail(VPBS_ERR_INVALID, "null aggregator");
     std::lock_guard<std::mutex> lock(a->mu);
     a->last = vpbs_aggregate_stats{};
+    std::memset(a->dev_stats, 0, sizeof a->dev_stats);
     if (!bytes || !offsets || !out) return fail(VPBS_ERR_INVALID, "null bytes, offsets or out");
     if (count == 0) return fail(VPBS_ERR_INVALID, "count is 0: there is nothing to aggregate");
     const unsigned d = depth_of(count);
@@ -736,9 +964,37 @@ long vpbs_aggregator_run(vpbs_aggregator* a, const uint8_t* bytes, const size_t*
         if (offsets[i + 1] < offsets[i]) return fail(VPBS_ERR_INVALID, "offsets decrease at leaf " + std::to_string(i));
     const double t_start = now();
     a->last.depth = d;
-    // ---- every leaf is parsed, verified and compared with vk_0 before anything is proven ----
-    std::vector<Proof> cur(count);
-    std::vector<std::string> why(count);
+    std::vector<Proof> cur;
+    std::vector<std::string> why;
+    check_leaves(a, bytes, offsets, count, cur, why);
+    a->last.check_leaves_ms = 1e3 * (now() - t_start);
+    for (size_t i = 0; i < count; ++i)
+        if (!why[i].empty()) {
+            a->last.seconds = now() - t_start;
+            return fail(VPBS_ERR_INVALID, "leaf " + std::to_string(i) + ": " + why[i] + "; nothing was proven");
+        }
+    std::string msg;
+    long n = 0;
+    if (a->max_nodes) {   // the device witness: this tree's levels in chunks; the root's bytes only once every level is through
+        long written = 0;
+        n = trees_device(a, cur, &count, 1, [&](size_t, const Level& L, const Proof& p) { return written = root_bytes(a, L, p, out, capacity, msg); }, msg);
+        if (n == VPBS_OK) n = written;
+    } else {
+        n = tree_host(a, cur, count, out, capacity, msg);
+    }
+    a->last.seconds = now() - t_start;
+    if (n < 0) return fail(n, msg);
+    if (stats) *stats = a->last;
+    return n;
+}
+}  // extern "C"
+
+namespace {
+// ---- every leaf is parsed, verified and compared with vk_0 before anything is proven: cur[i] the leaf, why[i] "" or what is wrong with it ----
+void check_leaves(const vpbs_aggregator* a, const uint8_t* bytes, const size_t* offsets, size_t count, std::vector<Proof>& cur,
+                  std::vector<std::string>& why) {
+    cur.assign(count, Proof{});
+    why.assign(count, "");
     {
         const size_t cap3 = 3 * ((size_t)4 << 4), op = openings_words(a->leaf), fri_words = a->leaf_words - cap3 - op;
         const unsigned hw = std::max(1u, std::min(HOST_THREADS, std::thread::hardware_concurrency()));
@@ -775,30 +1031,26 @@ long vpbs_aggregator_run(vpbs_aggregator* a, const uint8_t* bytes, const size_t*
             for (unsigned t = 0; t < threads; ++t) pool.emplace_back(work, t);
             for (auto& t : pool) t.join();
         }
-        a->last.check_leaves_ms = 1e3 * (now() - t_start);
-        for (size_t i = 0; i < count; ++i)
-            if (!why[i].empty()) {
-                a->last.seconds = now() - t_start;
-                return fail(VPBS_ERR_INVALID, "leaf " + std::to_string(i) + ": " + why[i] + "; nothing was proven");
-            }
     }
-    // ---- level by level.  ids: which proof of `cur` stands at each position of the padded level (equal ids: the same proof) ----
-    std::vector<size_t> ids((size_t)1 << d);
-    for (size_t i = 0; i < ids.size(); ++i) ids[i] = std::min(i, count - 1);
+}
+
+// ---- one tree on the host path, level by level: the checked leaves in `cur` -> the aggregate's bytes in out; their number, or < 0 with msg ----
+long tree_host(vpbs_aggregator* a, std::vector<Proof>& cur, size_t count, uint8_t* out, size_t capacity, std::string& msg) {
+    auto fail = [&](long rc, const std::string& m) {
+        msg = m;
+        return rc;
+    };
+    const unsigned d = depth_of(count);
     std::vector<u64> vks((a->levels.size() + 1) * VK);
     vpbs_aggregator_verifier_data(a, vks.data());
     vpbs_step_inputs in{};
-    std::vector<u64> caps, openings, fri;
     for (unsigned l = 1; l <= d; ++l) {
         const Level& L = a->levels[l - 1];
-        // the distinct nodes of this level, in order: a node whose children are those of its left neighbour is that neighbour
+        // the distinct nodes of this level, in order, and which proofs of `cur` they stand on
+        std::vector<u32> tree(level_jobs(&count, 1, l, nullptr, nullptr, nullptr, 0)), jl(tree.size()), jr(tree.size());
+        level_jobs(&count, 1, l, tree.data(), jl.data(), jr.data(), tree.size());
         std::vector<std::pair<size_t, size_t>> jobs;
-        std::vector<size_t> next_ids(ids.size() / 2);
-        for (size_t k = 0; k < next_ids.size(); ++k) {
-            const std::pair<size_t, size_t> ch{ids[2 * k], ids[2 * k + 1]};
-            if (jobs.empty() || jobs.back() != ch) jobs.push_back(ch);
-            next_ids[k] = jobs.size() - 1;
-        }
+        for (size_t j = 0; j < tree.size(); ++j) jobs.push_back({jl[j], jr[j]});
         std::vector<Proof> next(jobs.size());
         std::string werr[2];
         double wms[2] = {0, 0};
@@ -822,10 +1074,7 @@ long vpbs_aggregator_run(vpbs_aggregator* a, const uint8_t* bytes, const size_t*
         for (size_t j = 0; j < jobs.size(); ++j) {
             const std::string at = "level " + std::to_string(l) + ", node " + std::to_string(j) + ": ";
             a->last.witness_ms += wms[j & 1];
-            if (!werr[j & 1].empty()) {
-                a->last.seconds = now() - t_start;
-                return fail(VPBS_ERR_INVALID, at + werr[j & 1]);
-            }
+            if (!werr[j & 1].empty()) return fail(VPBS_ERR_INVALID, at + werr[j & 1]);
             const u64* wires = a->bufs[j & 1];
             Proof& p = next[j];
             p.pis.resize(L.n_pi);
@@ -840,25 +1089,184 @@ long vpbs_aggregator_run(vpbs_aggregator* a, const uint8_t* bytes, const size_t*
             if (rc == 0) rc = vpbs_prove_step(a->ctx, &in, cp, opn, fr, nullptr, nullptr);
             a->last.prove_ms += 1e3 * (now() - t0);
             if (ahead.joinable()) ahead.join();
-            if (rc != 0) {
-                a->last.seconds = now() - t_start;
-                return fail(rc, at + "proof: " + vpbs_last_error(a->ctx));
-            }
+            if (rc != 0) return fail(rc, at + "proof: " + vpbs_last_error(a->ctx));
             ++a->last.nodes;
         }
         cur.swap(next);
-        ids.swap(next_ids);
     }
-    // ---- the root node's proof, serialised ----
-    const Level& L = a->levels[d - 1];
-    const Proof& p = cur[0];
-    L.step_inputs(in, a->d_wires, p.pis.data());
-    const u64 *cp = p.flat.data(), *opn = cp + 3 * L.sz.cap_words, *fr = opn + L.sz.openings_words;
-    const long n = vpbs_step_proof_to_bytes(a->ctx, &in, L.n_const_cols, cp, opn, fr, out, capacity);
+    return root_bytes(a, a->levels[d - 1], cur[0], out, capacity, msg);
+}
+}  // namespace
+
+extern "C" {
+
+int vpbs_aggregate_level_jobs(const size_t* counts, size_t n_trees, unsigned level, uint32_t* tree, uint32_t* left, uint32_t* right,
+                              size_t capacity) {
+    if (!counts || n_trees == 0 || level == 0 || (capacity && (!tree || !left || !right))) return VPBS_ERR_INVALID;
+    size_t leaves = 0;
+    for (size_t t = 0; t < n_trees; ++t) {
+        if (counts[t] == 0 || counts[t] > 0xffffffffull - leaves) return VPBS_ERR_INVALID;
+        leaves += counts[t];
+    }
+    const size_t n = level_jobs(counts, n_trees, level, tree, left, right, capacity);
+    return n > 0x7fffffffull ? VPBS_ERR_INVALID : (int)n;
+}
+
+int vpbs_aggregator_set_device_witness(vpbs_aggregator* a, unsigned max_nodes, char* err, size_t err_len) {
+    report(err, err_len, "");
+    auto refuse = [&](const std::string& m) {
+        report(err, err_len, "vpbs_aggregator_set_device_witness: " + m);
+        return VPBS_ERR_INVALID;
+    };
+    if (!a) return refuse("null aggregator");
+    if (max_nodes > (1u << 16)) return refuse("max_nodes must be 0 .. 2^16");
+    std::lock_guard<std::mutex> lock(a->mu);
+    a->device_witness_off();
+    if (max_nodes == 0) return VPBS_OK;
+    vpbs_ctx* ctx = a->ctx;
+    std::string why;
+    for (size_t l = 0; l < a->levels.size() && why.empty(); ++l) {
+        Level& L = a->levels[l];
+        if (vpbs_witness_device_create(ctx, L.plan, max_nodes, &L.wd) != 0) why = "level " + std::to_string(l + 1) + ": " + vpbs_last_error(ctx);
+        a->row_words_max = std::max(a->row_words_max, L.inner_words + L.inner_pi);
+    }
+    if (why.empty()) {
+        try {
+            VPBS_HIP(hipSetDevice(ctx->device));
+            // at most 2 max_nodes distinct children per chunk, and one word per node for its pair of rows
+            const size_t words = (2 * a->row_words_max + 1) * (size_t)max_nodes;
+            VPBS_HIP(hipHostMalloc(reinterpret_cast<void**>(&a->h_rows), 8 * words, hipHostMallocDefault));
+            for (auto& e : a->ev) VPBS_HIP(hipEventCreate(&e));
+            std::vector<u64> vks((a->levels.size() + 1) * VK);
+            vpbs_aggregator_verifier_data(a, vks.data());
+            if (vpbs_device_alloc(ctx, words, &a->d_rows) != 0 || vpbs_device_alloc(ctx, vks.size(), &a->d_vks) != 0 ||
+                vpbs_device_upload(ctx, a->d_vks, vks.data(), vks.size()) != 0)
+                why = std::string("child rows and verifier data on the device: ") + vpbs_last_error(ctx);
+        } catch (const DeviceError& e) {
+            why = e.what;
+        }
+    }
+    if (!why.empty()) {
+        a->device_witness_off();
+        return refuse(why + "; the aggregator stays on the host path");
+    }
+    a->max_nodes = max_nodes;
+    return VPBS_OK;
+}
+
+int vpbs_aggregator_device_stats(const vpbs_aggregator* a, uint64_t out[4]) {
+    if (!a || !out) return VPBS_ERR_INVALID;
+    std::memcpy(out, a->dev_stats, sizeof a->dev_stats);
+    return VPBS_OK;
+}
+
+long vpbs_aggregator_run_many(vpbs_aggregator* a, const uint8_t* bytes, const size_t* offsets, const size_t* counts, size_t n_trees,
+                              vpbs_aggregate_tree_fn fn, void* user, char* err, size_t err_len) {
+    report(err, err_len, "");
+    auto fail = [&](long rc, const std::string& m) {
+        report(err, err_len, "vpbs_aggregator_run_many: " + m);
+        return rc;
+    };
+    if (!a) return fail(VPBS_ERR_INVALID, "null aggregator");
+    std::lock_guard<std::mutex> lock(a->mu);
+    a->last = vpbs_aggregate_stats{};
+    std::memset(a->dev_stats, 0, sizeof a->dev_stats);
+    if (n_trees == 0) return fail(VPBS_ERR_INVALID, "n_trees is 0: there is nothing to aggregate");
+    if (!bytes || !offsets || !counts || !fn) return fail(VPBS_ERR_INVALID, "null bytes, offsets, counts or fn");
+    size_t total = 0;
+    std::vector<size_t> first(n_trees + 1, 0);
+    for (size_t t = 0; t < n_trees; ++t) {
+        if (counts[t] == 0) return fail(VPBS_ERR_INVALID, "tree " + std::to_string(t) + " is empty");
+        if (counts[t] > ((size_t)1 << a->levels.size()))
+            return fail(VPBS_ERR_INVALID, "tree " + std::to_string(t) + ": count " + std::to_string(counts[t]) + " exceeds 2^levels = " +
+                                              std::to_string((size_t)1 << a->levels.size()));
+        if (counts[t] > 0xffffffffull - total) return fail(VPBS_ERR_INVALID, "2^32 leaves or more");
+        total += counts[t];
+        first[t + 1] = total;
+        a->last.depth = std::max(a->last.depth, depth_of(counts[t]));
+    }
+    for (size_t i = 0; i < total; ++i)
+        if (offsets[i + 1] < offsets[i]) return fail(VPBS_ERR_INVALID, "offsets decrease at leaf " + std::to_string(i));
+    const double t_start = now();
+    // ---- ALL leaves of all trees before anything is proven ----
+    std::vector<Proof> cur;
+    std::vector<std::string> why;
+    check_leaves(a, bytes, offsets, total, cur, why);
+    a->last.check_leaves_ms = 1e3 * (now() - t_start);
+    for (size_t t = 0; t < n_trees; ++t)
+        for (size_t i = first[t]; i < first[t + 1]; ++i)
+            if (!why[i].empty()) {
+                a->last.seconds = now() - t_start;
+                return fail(VPBS_ERR_INVALID, "tree " + std::to_string(t) + ", leaf " + std::to_string(i - first[t]) + ": " + why[i] + "; nothing was proven");
+            }
+    std::string msg;
+    std::vector<uint8_t> agg(vpbs::aggregator_max_bytes(a));
+    long rc = VPBS_OK;
+    if (a->max_nodes) {
+        // a root is serialised when its level is through and handed on once every tree before it has been
+        std::vector<std::vector<uint8_t>> done(n_trees);
+        std::vector<uint8_t> ready(n_trees, 0);
+        size_t handed = 0;
+        rc = trees_device(a, cur, counts, n_trees, [&](size_t t, const Level& L, const Proof& p) {
+            const long n = root_bytes(a, L, p, agg.data(), agg.size(), msg);
+            if (n < 0) return n;
+            done[t].assign(agg.begin(), agg.begin() + n);
+            ready[t] = 1;
+            for (; handed < n_trees && ready[handed]; ++handed) {
+                fn(user, handed, done[handed].data(), done[handed].size());
+                std::vector<uint8_t>().swap(done[handed]);
+            }
+            return n;
+        }, msg);
+    } else {
+        for (size_t t = 0; t < n_trees && rc >= 0; ++t) {
+            std::vector<Proof> leaves(std::make_move_iterator(cur.begin() + first[t]), std::make_move_iterator(cur.begin() + first[t + 1]));
+            rc = tree_host(a, leaves, counts[t], agg.data(), agg.size(), msg);
+            if (rc >= 0) fn(user, t, agg.data(), (size_t)rc);
+            else msg = "tree " + std::to_string(t) + ": " + msg;
+        }
+    }
     a->last.seconds = now() - t_start;
-    if (n <= 0) return fail(VPBS_ERR_INVALID, "the output buffer is too small for the aggregate proof");
-    if (stats) *stats = a->last;
-    return n;
+    if (rc < 0) return fail(rc, msg);
+    return (long)n_trees;
+}
+
+// test_entries.h: the preset matrix of a chunk as the device path assembles it, copied to the host
+int vpbs_test_aggregator_preset_matrix(vpbs_aggregator* a, unsigned level, const uint64_t* rows, size_t n_rows, const uint32_t* pairs, unsigned batch,
+                                       uint64_t* out) {
+    if (!a || !rows || !pairs || !out || level == 0 || level > a->levels.size() || n_rows == 0 || batch == 0) return VPBS_ERR_INVALID;
+    std::lock_guard<std::mutex> lock(a->mu);
+    if (batch > a->max_nodes || n_rows > 2 * (size_t)batch) return VPBS_ERR_INVALID;
+    for (unsigned j = 0; j < 2 * batch; ++j)
+        if (pairs[j] >= n_rows) return VPBS_ERR_INVALID;
+    const Level& L = a->levels[level - 1];
+    const size_t row_words = L.inner_words + L.inner_pi;
+    vpbs_ctx* ctx = a->ctx;
+    std::vector<Proof> held(n_rows);
+    std::vector<const Proof*> ptrs;
+    for (size_t r = 0; r < n_rows; ++r) {
+        held[r].flat.assign(rows + r * row_words, rows + r * row_words + L.inner_words);
+        held[r].pis.assign(rows + r * row_words + L.inner_words, rows + (r + 1) * row_words);
+        ptrs.push_back(&held[r]);
+    }
+    u64* d_m = nullptr;
+    int rc = VPBS_OK;
+    try {
+        VPBS_HIP(hipSetDevice(ctx->device));
+        const size_t words = L.n_preset * batch;
+        d_m = ctx->alloc_words(words);
+        VPBS_HIP(hipMemsetAsync(d_m, 0xA5, 8 * words, ctx->stream));   // a word the kernel leaves out shows
+        PresetJob job = presets_upload(a, L, level, ptrs, pairs, batch);
+        rc = presets_fill(&job, ctx->stream, d_m);
+        VPBS_HIP(hipMemcpyAsync(out, d_m, 8 * words, hipMemcpyDeviceToHost, ctx->stream));
+        VPBS_HIP(vpbs::stream_sync(ctx->stream));
+    } catch (const DeviceError& e) {
+        (void)vpbs::stream_sync(ctx->stream);
+        ctx->err = e.what;
+        rc = e.status;
+    }
+    if (d_m) ctx->release(d_m);
+    return rc;
 }
 
 int vpbs_aggregate_verifier_create(vpbs_ctx* ctx, const vpbs_aggregate_shape* shape, size_t max_leaves, vpbs_aggregate_verifier** out, char* err,
@@ -1109,6 +1517,7 @@ void many_statement_enqueue(vpbs_aggregate_verifier* v, const Statement& s, size
 
 namespace vpbs {
 unsigned aggregator_levels(const vpbs_aggregator* a) { return (unsigned)a->levels.size(); }
+unsigned aggregator_device_witness(const vpbs_aggregator* a) { return a->max_nodes; }
 size_t aggregator_max_bytes(const vpbs_aggregator* a) {
     size_t most = 0;
     for (const Level& L : a->levels) most = std::max(most, 8 * ((size_t)L.n_wires * 64 + ((size_t)1 << 17)) + 8 * L.n_pi);

@@ -1166,6 +1166,20 @@ long vpbs_program_prove_aggregate_batch(vpbs_program* prog, vpbs_ring_prover* ri
         return refuse((sink.failure.empty() ? "proofs are missing" : "row " + sink.failure + " (row b * n_gates + g)") + "; nothing was aggregated");
     std::vector<uint8_t> bytes, agg(aggregator_max_bytes(aggregator));
     std::vector<size_t> offsets;
+    if (aggregator_device_witness(aggregator) && instances) {   // ONE run: the level-l nodes of all instances in the same device batches
+        sink.pack(0, instances * G, &bytes, &offsets);
+        const std::vector<size_t> counts(instances, G);
+        struct Hand {
+            vpbs_aggregate_fn fn;
+            void* user;
+        } hand{agg_fn, user};
+        const long done = vpbs_aggregator_run_many(aggregator, bytes.data(), offsets.data(), counts.data(), instances,
+                                                   [](void* h, size_t tree, const uint8_t* proof, size_t len) {
+                                                       auto* x = static_cast<Hand*>(h);
+                                                       x->fn(tree, proof, len, x->user);
+                                                   }, &hand, err, err_len);
+        return done < 0 ? done : (long)instances;
+    }
     for (size_t b = 0; b < instances; ++b) {
         sink.pack(b * G, G, &bytes, &offsets);
         const long len = vpbs_aggregator_run(aggregator, bytes.data(), offsets.data(), G, agg.data(), agg.size(), nullptr, err, err_len);

@@ -115,6 +115,7 @@ void lwe_chain_enqueue(void* stream, const uint64_t* d_ct, unsigned n_lwe, size_
 
 // ---- aggregation (aggregate.hip), for the program calls that end in one aggregate per instance ----
 unsigned aggregator_levels(const vpbs_aggregator* a);     // up to 2^levels leaves
+unsigned aggregator_device_witness(const vpbs_aggregator* a);   // max_nodes of vpbs_aggregator_set_device_witness (0: the host path)
 size_t aggregator_max_bytes(const vpbs_aggregator* a);    // a capacity that holds the aggregate proof of every level
 struct AggregateVerifierShape {
     vpbs_ctx* ctx;

@@ -23,6 +23,13 @@ int vpbs_test_pbs_prover_dummy_proof(const vpbs_pbs_prover* p, uint64_t* out);
 // caps | openings | fri in a serialised proof, lenb_off / lenb_val [*n_lenb] the offset and value of every Merkle-path length byte.  Returns
 // the bytes up to and including the PoW witness.  Host only.  VPBS_ERR_INVALID for a null pointer, a shape vpbs_step_proof_from_bytes
 // refuses or a capacity below the count (the counts are still written).  Tests bind it themselves: it has no entry in api.py.
+// The preset matrix of a chunk of level-`level` nodes as the aggregator's device path assembles it (aggregate.hip: the upload of the child rows
+// and ag_presets_kernel), copied to the host: rows [n_rows][row_words] the distinct child proofs, each flat | pis (row_words = the level's
+// inner proof words + inner public inputs); pairs [batch][2] every node's (left row, right row); out [n_preset][batch], instances innermost.
+// The aggregator's device witness must be on with max_nodes >= batch.  VPBS_ERR_INVALID for null pointers, a level the aggregator does not
+// have, batch = 0 or above max_nodes, n_rows = 0 or above 2 batch, a pair entry at or above n_rows.
+int vpbs_test_aggregator_preset_matrix(vpbs_aggregator* a, unsigned level, const uint64_t* rows, size_t n_rows, const uint32_t* pairs, unsigned batch,
+                                       uint64_t* out);
 long vpbs_test_proof_byte_tables(const vpbs_verify_inputs* in, size_t src_capacity, size_t lenb_capacity, uint32_t* src, uint32_t* lenb_off,
                                  uint8_t* lenb_val, size_t* n_src, size_t* n_lenb);
 }
