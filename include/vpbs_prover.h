@@ -1085,6 +1085,45 @@ int vpbs_lwe_decode_batch(vpbs_ctx* ctx, const uint64_t* s_lwe, int key_on_devic
                           uint64_t modulus, const uint64_t* expected /* [count] or NULL */, uint64_t* phase_out, uint64_t* msg_out,
                           uint64_t* err_out, vpbs_noise_stats* stats /* accumulated into, may be NULL */, int on_device /* vpbs_decode_where */);
 
+/* ---- seeded keys and ciphertexts: a client's own secrets, expanded on the device (csrc/keygen.hip, csrc/key_seeded.hip, csrc/lwe_client.hip) ----
+ * The SPLIT generator (csrc/keygen_streams.h): the streams of kind BSK_MASK, KSK_MASK and LWE_MASK are keyed by a public mask_seed, all other
+ * kinds (the secrets, the noise) by params->seed; tags, draw, field and noise are vpbs_keygen's.  With mask_seed == params->seed it IS
+ * vpbs_keygen's generator.  K - 1 of the K polynomials of every GLWE of a key, and n_lwe of the n_lwe + 1 words of a ciphertext, are masks that
+ * mask_seed (and the nonce) determine, so a client ships the rest -- the BODIES -- and the server rebuilds the full layouts word for word.
+ * mix64 is NOT a cryptographic generator: these calls separate what is public from what is private, they do not make the noise stream fit
+ * for production.  Refusals are VPBS_ERR_INVALID before anything is queued, with a message in vpbs_last_error that names the first offending
+ * index, and no output word written.  Device pointers of keys and bodies must be 16-byte aligned.
+ *
+ * vpbs_keygen_seeded: vpbs_keygen under the split generator, handing out bodies only.  bsk_bodies [n_lwe][K][ELL][N] and ksk_bodies [K][ELL][N]
+ *   are the LAST polynomial (r = K - 1) of every GLWE of bsk / ksk, NTT domain, in the order of the full layout: 1 / K of the key set; device
+ *   pointers when bodies_on_device != 0.  s_lwe_in [n_lwe] and s_glwe_in [K - 1][N] are both NULL -- the secrets come from the seed, exactly as
+ *   in vpbs_keygen -- or both given: then they ARE the secrets, and s_to is the partial key laid out from s_lwe_in
+ *   (s_to[x / N][x % N] = s_lwe_in[x], zeros elsewhere).  A secret word that is neither 0 nor 1 is refused: the message names the array and
+ *   the (flat) index.  The three secret outputs and either bodies pointer may be NULL.
+ * vpbs_key_expand: the full keys in vpbs_keygen's layout from mask_seed and the bodies: the mask polynomials regenerated as vpbs_keygen
+ *   generates them (drawn in the coefficient domain, then the forward negacyclic transform), the bodies copied in.  One launch per key writes
+ *   it once.  Either pair (bsk_bodies, bsk) or (ksk_bodies, ksk) may be NULL; host arrays, or device pointers by bodies_on_device /
+ *   keys_on_device (e.g. for vpbs_bootstrapper_create or vpbs_pbs_prover_create with keys_on_device).  A context is required.
+ * vpbs_lwe_encrypt_seeded_batch: bodies_out[i] is the body word (word n_lwe) of vpbs_lwe_encrypt_batch's row i under the split generator; the
+ *   pointers, the NULL context (host form) and the refusals are vpbs_lwe_encrypt_batch's.
+ * vpbs_lwe_expand_batch: row i of cts_out [count][n_lwe + 1] is field(draw(stream(mask_seed, tag(LWE_MASK, nonce0 + i, 0, 0)), j)) for
+ *   j < n_lwe, followed by bodies[i] copied unchanged; bodies and cts_out are device pointers when on_device != 0; a NULL ctx is the host
+ *   form.  Refused: nonce0 + count above 2^24, null pointers, n_lwe of 0 or at least 2^24.
+ * vpbs_keyring_add_seeded: vpbs_keyring_add of the key set that vpbs_key_expand gives, expanded into memory the RING owns (remove frees it
+ *   exactly as it frees what add uploaded); *slot by add's rule; refused on the ring of a vpbs_ring_prover, as add is.
+ * vpbs_ring_prover_add_seeded: the same on the prover's owned ring, then the key hash chain walked exactly as vpbs_ring_prover_add walks it
+ *   for device-only keys: one download, then the host walk. */
+int vpbs_keygen_seeded(vpbs_ctx* ctx, const vpbs_keygen_params* params, uint64_t mask_seed, const uint64_t* s_lwe_in, const uint64_t* s_glwe_in,
+                       uint64_t* s_lwe, uint64_t* s_glwe, uint64_t* s_to, uint64_t* bsk_bodies, uint64_t* ksk_bodies, int bodies_on_device);
+int vpbs_key_expand(vpbs_ctx* ctx, const vpbs_tfhe_params* tfhe_params, unsigned n_lwe, uint64_t mask_seed, const uint64_t* bsk_bodies,
+                    const uint64_t* ksk_bodies, int bodies_on_device, uint64_t* bsk, uint64_t* ksk, int keys_on_device);
+int vpbs_lwe_encrypt_seeded_batch(vpbs_ctx* ctx, const vpbs_keygen_params* params, uint64_t mask_seed, const uint64_t* s_lwe, int key_on_device,
+                                  const uint64_t* messages, size_t count, uint64_t nonce0, uint64_t* bodies_out, int on_device);
+int vpbs_lwe_expand_batch(vpbs_ctx* ctx, unsigned n_lwe, uint64_t mask_seed, uint64_t nonce0, const uint64_t* bodies, size_t count,
+                          uint64_t* cts_out, int on_device);
+int vpbs_keyring_add_seeded(vpbs_keyring* ring, uint64_t mask_seed, const uint64_t* bsk_bodies, const uint64_t* ksk_bodies, int bodies_on_device,
+                            unsigned* slot);
+
 /* ---- proving the bootstraps of a batch under one resident key set (csrc/pbs_prove_batch.hip) ----
  * One object owns a key set in device memory and turns a batch of LWE ciphertexts into their bootstrapped outputs AND their vPBS proofs.
  *   create: `chains` vpbs_ivc objects, each on a context of its own, in the device-witness pipeline with `witness_batch` steps per batch
@@ -1182,6 +1221,9 @@ int vpbs_ring_prover_create(int device_ordinal, const vpbs_ivc_circuit* cyclic, 
                             size_t err_len);
 int vpbs_ring_prover_add(vpbs_ring_prover* p, const uint64_t* bsk, const uint64_t* ksk, int keys_on_device, unsigned* slot, char* err,
                          size_t err_len);
+/* vpbs_ring_prover_add of a seeded key set (see vpbs_keyring_add_seeded above) */
+int vpbs_ring_prover_add_seeded(vpbs_ring_prover* p, uint64_t mask_seed, const uint64_t* bsk_bodies, const uint64_t* ksk_bodies,
+                                int bodies_on_device, unsigned* slot, char* err, size_t err_len);
 int vpbs_ring_prover_remove(vpbs_ring_prover* p, unsigned slot, char* err, size_t err_len);
 int vpbs_ring_prover_key_hash(vpbs_ring_prover* p, unsigned slot, uint64_t out[4]);
 vpbs_keyring* vpbs_ring_prover_keyring(vpbs_ring_prover* p);

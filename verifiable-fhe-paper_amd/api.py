@@ -390,6 +390,12 @@ SIGNATURES = {
     "vpbs_lwe_encrypt_batch": (_i, [_vp, C.POINTER(KeygenParamsC), _vp, _i, _vp, _sz, _u64, _vp, _i]),
     "vpbs_lut_testv": (_i, [_ui, _ui, U64P, _u64, U64P]),
     "vpbs_lwe_decode_batch": (_i, [_vp, _vp, _i, _vp, _sz, _ui, _u64, _u64, _vp, _vp, _vp, _vp, C.POINTER(NoiseStatsC), _i]),
+    "vpbs_keygen_seeded": (_i, [_vp, C.POINTER(KeygenParamsC), _u64, _vp, _vp, U64P, U64P, U64P, _vp, _vp, _i]),
+    "vpbs_key_expand": (_i, [_vp, C.POINTER(TfheParamsC), _ui, _u64, _vp, _vp, _i, _vp, _vp, _i]),
+    "vpbs_lwe_encrypt_seeded_batch": (_i, [_vp, C.POINTER(KeygenParamsC), _u64, _vp, _i, _vp, _sz, _u64, _vp, _i]),
+    "vpbs_lwe_expand_batch": (_i, [_vp, _ui, _u64, _u64, _vp, _sz, _vp, _i]),
+    "vpbs_keyring_add_seeded": (_i, [_vp, _u64, _vp, _vp, _i, C.POINTER(_ui)]),
+    "vpbs_ring_prover_add_seeded": (_i, [_vp, _u64, _vp, _vp, _i, C.POINTER(_ui), C.c_char_p, _sz]),
     "vpbs_k_poseidon_batch": (_i, [_vp, U64P, _sz]),
     "vpbs_k_hash_rows": (_i, [_vp, U64P, _sz, _ui, U64P]),
     "vpbs_k_intt": (_i, [_vp, U64P, _ui, _ui, U64P]),
@@ -1497,7 +1503,9 @@ def _is_dev(x):
     return isinstance(x, (int, np.integer))
 
 
-def _lwe_encrypt_batch(ctx, params, s_lwe, messages, nonce0, out_dev_ptr, count):
+def _lwe_encrypt_batch(ctx, params, s_lwe, messages, nonce0, out_dev_ptr, count, mask_seed=None):
+    """vpbs_lwe_encrypt_batch, or with mask_seed vpbs_lwe_encrypt_seeded_batch: the same arguments, [count] bodies instead of [count][n + 1] rows"""
+    name = "vpbs_lwe_encrypt_batch" if mask_seed is None else "vpbs_lwe_encrypt_seeded_batch"
     h = ctx.h if ctx is not None else None
     n = int(params.n_lwe)
     key = None if _is_dev(s_lwe) else _u64(s_lwe).reshape(-1)
@@ -1512,13 +1520,17 @@ def _lwe_encrypt_batch(ctx, params, s_lwe, messages, nonce0, out_dev_ptr, count)
     tmp, out = None, None
     try:
         if out_dev_ptr is None:
-            out = np.zeros((count, n + 1), np.uint64)
+            out = np.zeros((count, n + 1) if mask_seed is None else count, np.uint64)
             pm, po, on_device = (msgs if count else keep).ctypes.data, (out if count else keep).ctypes.data, 0
         else:
             if msgs is not None:
                 tmp = ctx.device_upload_new(msgs if count else keep)
             pm, po, on_device = (tmp if msgs is not None else int(messages)), int(out_dev_ptr), 1
-        rc = lib().vpbs_lwe_encrypt_batch(h, C.byref(params), pkey, 1 if key is None else 0, pm, count, int(nonce0), po, on_device)
+        if mask_seed is None:
+            rc = lib().vpbs_lwe_encrypt_batch(h, C.byref(params), pkey, 1 if key is None else 0, pm, count, int(nonce0), po, on_device)
+        else:
+            rc = lib().vpbs_lwe_encrypt_seeded_batch(h, C.byref(params), int(mask_seed), pkey, 1 if key is None else 0, pm, count, int(nonce0), po,
+                                                     on_device)
     finally:
         if tmp is not None:
             ctx.device_free(tmp)
@@ -1529,8 +1541,62 @@ def _lwe_encrypt_batch(ctx, params, s_lwe, messages, nonce0, out_dev_ptr, count)
             bad = np.nonzero(msgs >= np.uint64(P))[0]
             text = ("message %d is not below p" % bad[0] if bad.size else
                     "nonce0 + count exceeds 2^24" if int(nonce0) + count > 1 << 24 else "bad arguments")
-        raise VpbsError("vpbs_lwe_encrypt_batch: status %d: %s" % (rc, text))
+        raise VpbsError("%s: status %d: %s" % (name, rc, text))
     return out
+
+
+def _lwe_expand_batch(ctx, n_lwe, mask_seed, bodies, nonce0, out_dev_ptr, count):
+    h = ctx.h if ctx is not None else None
+    b = None if _is_dev(bodies) else _u64(bodies).reshape(-1)
+    if b is None and (count is None or out_dev_ptr is None):
+        raise ValueError("lwe_expand_batch: bodies on the device need count and out_dev_ptr")
+    count = b.size if b is not None else int(count)
+    keep = np.zeros(1, np.uint64)   # a valid pointer for an empty batch
+    tmp, out = None, None
+    try:
+        if out_dev_ptr is None:
+            out = np.zeros((count, int(n_lwe) + 1), np.uint64)
+            pb, po, on_device = (b if count else keep).ctypes.data, (out if out.size else keep).ctypes.data, 0
+        else:
+            if b is not None:
+                tmp = ctx.device_upload_new(b if count else keep)
+            pb, po, on_device = (tmp if b is not None else int(bodies)), int(out_dev_ptr), 1
+        rc = lib().vpbs_lwe_expand_batch(h, int(n_lwe), int(mask_seed), int(nonce0), pb, count, po, on_device)
+    finally:
+        if tmp is not None:
+            ctx.device_free(tmp)
+    if rc:
+        text = (lib().vpbs_last_error(h).decode() if h else
+                "nonce0 + count exceeds 2^24" if int(nonce0) + count > 1 << 24 else "n_lwe must be 1 .. 2^24 - 1, or a null pointer")
+        raise VpbsError("vpbs_lwe_expand_batch: status %d: %s" % (rc, text))
+    return out
+
+
+def seeded_key_shapes(N, K, ELL, n_lwe):
+    """words of one key set (bsk and ksk together) as vpbs_keygen_seeded ships it and as vpbs_key_expand rebuilds it -> (bodies words, full
+    words): the bodies are the last of the K polynomials of every GLWE, 1 / K of the key set"""
+    glwes = (n_lwe + 1) * K * ELL
+    return glwes * N, glwes * K * N
+
+
+def key_expand_args(N, K, ELL, n_lwe, bsk_bodies, ksk_bodies):
+    """shapes of the host form of Context.key_expand / KeyRing.add_seeded / RingProver.add_seeded, checked without a device: bsk_bodies
+    [n_lwe][K*ELL*N], ksk_bodies [K*ELL*N] (keygen_seeded's layout; either may be None) -> (bsk_bodies, ksk_bodies), contiguous uint64"""
+    g = K * ELL * N
+    b = None if bsk_bodies is None else _u64(bsk_bodies)
+    k = None if ksk_bodies is None else _u64(ksk_bodies).reshape(-1)
+    if (b is not None and b.shape != (n_lwe, g)) or (k is not None and k.size != g):
+        raise ValueError("key_expand: expected bsk_bodies [%d][%d] and ksk_bodies [%d]" % (n_lwe, g, g))
+    return b, k
+
+
+def _seeded_add_args(obj, bsk_bodies, ksk_bodies, bodies_on_device):
+    if bodies_on_device:
+        return C.c_void_p(int(bsk_bodies)), C.c_void_p(int(ksk_bodies)), None
+    b, k = key_expand_args(obj.N, obj.K, obj.ELL, obj.n_lwe, bsk_bodies, ksk_bodies)
+    if b is None or k is None:
+        raise ValueError("add_seeded: both bsk_bodies and ksk_bodies are needed")
+    return C.c_void_p(b.ctypes.data), C.c_void_p(k.ctypes.data), (b, k)
 
 
 DECODE_OUTPUTS = ("phase", "msg", "err")
@@ -1589,6 +1655,18 @@ def _lwe_decode_batch(ctx, s_lwe, cts, delta, modulus, expected, count, stats, w
 def lwe_encrypt_batch(params, s_lwe, messages, nonce0=0):
     """vpbs_lwe_encrypt_batch on the host (null context): row i = lwe_encrypt(params, s_lwe, messages[i], nonce0 + i) -> cts [count][n + 1]"""
     return _lwe_encrypt_batch(None, params, s_lwe, messages, nonce0, None, None)
+
+
+def lwe_encrypt_seeded_batch(params, mask_seed, s_lwe, messages, nonce0=0):
+    """vpbs_lwe_encrypt_seeded_batch on the host (null context): bodies [count], the last word of lwe_encrypt_batch's rows when the mask
+    streams are keyed by mask_seed and the noise by params.seed (mask_seed == params.seed: of lwe_encrypt_batch's rows themselves)"""
+    return _lwe_encrypt_batch(None, params, s_lwe, messages, nonce0, None, None, mask_seed=mask_seed)
+
+
+def lwe_expand_batch(n_lwe, mask_seed, bodies, nonce0=0):
+    """vpbs_lwe_expand_batch on the host (null context): row i = the n_lwe mask words of nonce nonce0 + i under mask_seed, then bodies[i]
+    -> cts [count][n + 1]"""
+    return _lwe_expand_batch(None, n_lwe, mask_seed, bodies, nonce0, None, None)
 
 
 def lwe_decode_batch(s_lwe, cts, delta, modulus, expected=None, stats=None, want=("msg",)):
@@ -1901,6 +1979,17 @@ class KeyRing:
         rc = lib().vpbs_keyring_add(self.h, pb, pk, 1 if keys_on_device else 0, C.byref(slot))
         if rc:
             raise self._fail("vpbs_keyring_add", rc)
+        return slot.value
+
+    def add_seeded(self, mask_seed, bsk_bodies, ksk_bodies, bodies_on_device=False):
+        """vpbs_keyring_add_seeded: the key set of Context.key_expand(mask_seed, bodies), expanded on the device into memory the ring owns
+        (remove frees it).  bsk_bodies [n][K*ELL*N], ksk_bodies [K*ELL*N] (keygen_seeded's layout, 1 / K of the key set), or device pointers
+        (integers) with bodies_on_device=True -- they are read during the call only.  Returns the slot: the lowest free number."""
+        pb, pk, _keep = _seeded_add_args(self, bsk_bodies, ksk_bodies, bodies_on_device)
+        slot = C.c_uint()
+        rc = lib().vpbs_keyring_add_seeded(self.h, int(mask_seed), pb, pk, 1 if bodies_on_device else 0, C.byref(slot))
+        if rc:
+            raise self._fail("vpbs_keyring_add_seeded", rc)
         return slot.value
 
     def remove(self, slot):
@@ -2240,6 +2329,16 @@ class RingProver(_BatchProver):
         rc = lib().vpbs_ring_prover_add(self.h, pb, pk, 1 if keys_on_device else 0, C.byref(slot), err, 512)
         if rc:
             raise self._fail("vpbs_ring_prover_add", rc, err)
+        return slot.value
+
+    def add_seeded(self, mask_seed, bsk_bodies, ksk_bodies, bodies_on_device=False):
+        """KeyRing.add_seeded on the owned ring, and the key hash chain of the expanded key set: one download, then the host walk, as add
+        does for keys that are on the device only.  Returns the slot."""
+        pb, pk, _keep = _seeded_add_args(self, bsk_bodies, ksk_bodies, bodies_on_device)
+        slot, err = C.c_uint(), C.create_string_buffer(512)
+        rc = lib().vpbs_ring_prover_add_seeded(self.h, int(mask_seed), pb, pk, 1 if bodies_on_device else 0, C.byref(slot), err, 512)
+        if rc:
+            raise self._fail("vpbs_ring_prover_add_seeded", rc, err)
         return slot.value
 
     def remove(self, slot):
@@ -3690,6 +3789,97 @@ class Context:
         self._check(lib().vpbs_device_alloc(self.h, g, C.byref(d_ksk)))
         self._check(lib().vpbs_keygen(self.h, C.byref(prm), _ptr(s_lwe), _ptr(s_glwe), _ptr(s_to), d_bsk, d_ksk, 1))
         return {"params": prm, "s_lwe": s_lwe, "s_glwe": s_glwe, "s_to": s_to, "d_bsk": d_bsk.value, "d_ksk": d_ksk.value}
+
+    def keygen_seeded(self, N, K, ELL, LOGB, n_lwe, seed, mask_seed, sigma_glwe=0.0, sigma_lwe=0.0, s_lwe=None, s_glwe=None, on_device=False):
+        """vpbs_keygen_seeded: keygen under the split generator -- the mask streams from the public mask_seed, the secrets and the noise
+        from the private seed -- handing out only the last polynomial of every GLWE: 1 / K of the key set.  s_lwe [n] and s_glwe [K-1][N]
+        (both or neither) are the caller's OWN binary secrets; without them the secrets are those of keygen(seed).  -> dict(params,
+        mask_seed, s_lwe, s_glwe, s_to host arrays; bsk_bodies [n][K*ELL*N], ksk_bodies [K*ELL*N] host arrays, or with on_device=True
+        d_bsk_bodies, d_ksk_bodies device pointers to be released with device_free).  With mask_seed == seed the bodies are those of
+        keygen's bsk / ksk.  mix64 is not a cryptographic generator: keys for benchmarking and integration, not for production."""
+        prm = KeygenParamsC(N.bit_length() - 1, K, ELL, LOGB, n_lwe, seed, sigma_glwe, sigma_lwe)
+        if (s_lwe is None) != (s_glwe is None):
+            raise ValueError("keygen_seeded: s_lwe and s_glwe are given together or not at all")
+        own = s_lwe is not None
+        if own:
+            sl_in, sg_in = _u64(s_lwe).reshape(-1), _u64(s_glwe).reshape(-1)
+            if sl_in.size != n_lwe or sg_in.size != (K - 1) * N:
+                raise ValueError("keygen_seeded: expected s_lwe [%d] and s_glwe [%d][%d]" % (n_lwe, K - 1, N))
+        o_lwe, o_glwe, o_to = np.zeros(n_lwe, np.uint64), np.zeros((K - 1, N), np.uint64), np.zeros((K, N), np.uint64)
+        g = K * ELL * N
+        out = {"params": prm, "mask_seed": mask_seed, "s_lwe": o_lwe, "s_glwe": o_glwe, "s_to": o_to}
+        if on_device:
+            d_b, d_k = C.c_void_p(), C.c_void_p()
+            self._check(lib().vpbs_device_alloc(self.h, n_lwe * g, C.byref(d_b)))
+            self._check(lib().vpbs_device_alloc(self.h, g, C.byref(d_k)))
+            pb, pk = d_b, d_k
+        else:
+            out["bsk_bodies"], out["ksk_bodies"] = np.zeros((n_lwe, g), np.uint64), np.zeros(g, np.uint64)
+            pb, pk = out["bsk_bodies"].ctypes.data, out["ksk_bodies"].ctypes.data
+        rc = lib().vpbs_keygen_seeded(self.h, C.byref(prm), int(mask_seed), sl_in.ctypes.data if own else None, sg_in.ctypes.data if own else None,
+                                      _ptr(o_lwe), _ptr(o_glwe), _ptr(o_to), pb, pk, 1 if on_device else 0)
+        if rc and on_device:
+            self.device_free(d_b.value)
+            self.device_free(d_k.value)
+        self._check(rc)
+        if on_device:
+            out["d_bsk_bodies"], out["d_ksk_bodies"] = d_b.value, d_k.value
+        return out
+
+    def key_expand(self, N, K, ELL, n_lwe, mask_seed, bsk_bodies, ksk_bodies, on_device=False, d_bsk=None, d_ksk=None):
+        """vpbs_key_expand: the full keys in keygen's layout from mask_seed and the bodies of keygen_seeded, word for word; the mask
+        polynomials are regenerated and transformed on the device, the bodies copied in.  Host-array form: bsk_bodies [n][K*ELL*N] and
+        ksk_bodies [K*ELL*N] (either may be None).  Device-pointer form: integers (None to skip one).  -> dict(bsk [n][K*ELL*K*N], ksk
+        [K*ELL*K*N]) host arrays, or with on_device=True dict(d_bsk, d_ksk) device pointers for Bootstrapper / PbsProver / KeyRing.add with
+        keys_on_device=True, to be released with device_free; or, with d_bsk / d_ksk (16-byte aligned device pointers of the caller's), the
+        keys written there and nothing returned."""
+        prm = TfheParamsC(N.bit_length() - 1, K, ELL, 0)   # the gadget base plays no part in the masks
+        g = K * ELL * K * N
+        bodies_dev = _is_dev(bsk_bodies) or _is_dev(ksk_bodies)
+        if bodies_dev:
+            pb, pk = (None if x is None else C.c_void_p(int(x)) for x in (bsk_bodies, ksk_bodies))
+        else:
+            b, k = key_expand_args(N, K, ELL, n_lwe, bsk_bodies, ksk_bodies)
+            pb, pk = (None if x is None else C.c_void_p(x.ctypes.data) for x in (b, k))
+        want_b, want_k = bsk_bodies is not None, ksk_bodies is not None
+        if d_bsk is not None or d_ksk is not None:   # the caller's device buffers
+            if (d_bsk is not None) != want_b or (d_ksk is not None) != want_k:
+                raise ValueError("key_expand: d_bsk goes with bsk_bodies and d_ksk with ksk_bodies")
+            rc = lib().vpbs_key_expand(self.h, C.byref(prm), n_lwe, int(mask_seed), pb, pk, 1 if bodies_dev else 0,
+                                       C.c_void_p(int(d_bsk)) if want_b else None, C.c_void_p(int(d_ksk)) if want_k else None, 1)
+            self._check(rc)
+            return None
+        if on_device:
+            d_b, d_k = C.c_void_p(), C.c_void_p()
+            if want_b:
+                self._check(lib().vpbs_device_alloc(self.h, n_lwe * g, C.byref(d_b)))
+            if want_k:
+                self._check(lib().vpbs_device_alloc(self.h, g, C.byref(d_k)))
+            ob, ok = (d_b if want_b else None), (d_k if want_k else None)
+        else:
+            bsk = np.zeros((n_lwe, g), np.uint64) if want_b else None
+            ksk = np.zeros(g, np.uint64) if want_k else None
+            ob, ok = (C.c_void_p(bsk.ctypes.data) if want_b else None), (C.c_void_p(ksk.ctypes.data) if want_k else None)
+        rc = lib().vpbs_key_expand(self.h, C.byref(prm), n_lwe, int(mask_seed), pb, pk, 1 if bodies_dev else 0, ob, ok, 1 if on_device else 0)
+        if rc and on_device:
+            for d in (d_b, d_k):
+                if d.value:
+                    self.device_free(d.value)
+        self._check(rc)
+        if on_device:
+            return {"d_bsk": d_b.value, "d_ksk": d_k.value}
+        return {"bsk": bsk, "ksk": ksk}
+
+    def lwe_encrypt_seeded_batch(self, params, mask_seed, s_lwe, messages, nonce0=0, out_dev_ptr=None, count=None):
+        """vpbs_lwe_encrypt_seeded_batch on the device: bodies [count], the last word of lwe_encrypt_batch's rows under the split generator
+        (mask streams from mask_seed, noise from params.seed).  s_lwe, messages, out_dev_ptr and count as in lwe_encrypt_batch."""
+        return _lwe_encrypt_batch(self, params, s_lwe, messages, nonce0, out_dev_ptr, count, mask_seed=mask_seed)
+
+    def lwe_expand_batch(self, n_lwe, mask_seed, bodies, nonce0=0, out_dev_ptr=None, count=None):
+        """vpbs_lwe_expand_batch on the device: row i = the n_lwe mask words of nonce nonce0 + i under mask_seed, then bodies[i].  bodies is a
+        host array or a device pointer (an integer; then count and out_dev_ptr are needed).  Without out_dev_ptr the rows come back,
+        [count][n + 1]; with it they are left at that device pointer -- for KeyRing.run_device and the like -- and nothing is returned."""
+        return _lwe_expand_batch(self, n_lwe, mask_seed, bodies, nonce0, out_dev_ptr, count)
 
     def device_free(self, d_ptr):
         lib().vpbs_device_free(self.h, C.c_void_p(int(d_ptr)))

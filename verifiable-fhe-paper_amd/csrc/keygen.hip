@@ -15,6 +15,13 @@
 //                  support +-6 sigma, integer arithmetic only, hence identical on every host and device (a libm Box-Muller would not be).
 // The GLWE encryptions are generated directly in the NTT domain the circuit consumes:  ntt(a), ntt(a s + e + m) = ntt(a) . ntt(s) + ntt(e + m)
 // -- the same field elements as the reference's encrypt-then-ntt_forward order (exact arithmetic), one transform per polynomial instead of three.
+//
+// vpbs_keygen_seeded is the same generation under the SPLIT generator (keygen_streams.h): the mask streams from a public mask_seed, the
+// secrets -- the seed's, or the caller's own -- and the noise from the private seed, and only the last polynomial of every GLWE handed
+// out: 1 / K of a key set.  vpbs_key_expand (csrc/key_seeded.hip) rebuilds the full keys from mask_seed and those bodies on the device;
+// vpbs_lwe_encrypt_seeded_batch / vpbs_lwe_expand_batch (csrc/lwe_client.hip) do the same for ciphertexts.  mix64 is not a cryptographic
+// generator: the split separates what is public from what is private, it does not make the noise stream fit for production.
+#include <string>
 #include <vector>
 
 #include "context.h"
@@ -26,7 +33,7 @@ namespace keygen {
 // every coefficient of every GLWE of a batch of GGSW encryptions, coefficient domain, straight into the output buffer
 // out: [n_ggsw][K][ELL][K][N];  msg: [K][N] (the polynomial GLEV p encrypts before the bit / gadget scaling);  bits: [n_ggsw] or null (= 1)
 struct GgswJob {
-    u64 seed, m_sigma;
+    u64 seed, mask_seed, m_sigma;   // the split generator (keygen_streams.h); vpbs_keygen: mask_seed = seed
     u64 kind_mask, kind_noise;
     unsigned log_n, K, ELL, n_ggsw;
     u64 scale[16];  // B^(first_limb + l), l < ELL
@@ -45,10 +52,10 @@ __global__ void __launch_bounds__(256) ggsw_fill_kernel(GgswJob j, const u64* __
     const unsigned g = (unsigned)(rest / j.K);
     const u64 pl = (u64)p * j.ELL + l;
     if (r + 1 < j.K) {  // mask polynomial r
-        out[idx] = field(draw(stream(j.seed, tag(j.kind_mask, g, pl, r)), i));
+        out[idx] = field(draw(split_stream(j.seed, j.mask_seed, j.kind_mask, g, pl, r), i));
         return;
     }
-    const u64 e = noise(stream(j.seed, tag(j.kind_noise, g, pl, 0)), i, j.m_sigma);
+    const u64 e = noise(split_stream(j.seed, j.mask_seed, j.kind_noise, g, pl, 0), i, j.m_sigma);
     const u64 bit = bits ? bits[g] : 1;
     const u64 m = bit ? gl::mul(j.scale[l], msg[(size_t)p * n + i]) : 0;
     out[idx] = gl::add(e, m);
@@ -62,6 +69,13 @@ __global__ void __launch_bounds__(256) ggsw_body_kernel(unsigned log_n, unsigned
     u64 acc = ct[(size_t)(K - 1) * n + i];
     for (unsigned r = 0; r + 1 < K; ++r) acc = gl::add(acc, gl::mul(ct[(size_t)r * n + i], key_hat[(size_t)r * n + i]));
     ct[(size_t)(K - 1) * n + i] = acc;
+}
+// bodies [n_glwe][N] = the last polynomial of every GLWE of full [n_glwe][K][N] (vpbs_keygen_seeded); one thread per pair of words
+__global__ void __launch_bounds__(256) ggsw_bodies_kernel(unsigned log_n, unsigned K, size_t n_glwe, const u64* __restrict__ full, u64* __restrict__ bodies) {
+    const size_t half = (size_t)1 << (log_n - 1), idx = blockIdx.x * (size_t)256 + threadIdx.x;
+    if (idx >= n_glwe * half) return;
+    const size_t glwe = idx >> (log_n - 1), i = idx & (half - 1);
+    reinterpret_cast<ulonglong2*>(bodies)[idx] = reinterpret_cast<const ulonglong2*>(full + (glwe * K + (K - 1)) * 2 * half)[i];
 }
 __global__ void __launch_bounds__(256) pointwise_mac_kernel(size_t n, unsigned terms, const u64* __restrict__ a, const u64* __restrict__ b, u64* __restrict__ out) {
     const size_t i = blockIdx.x * (size_t)256 + threadIdx.x;
@@ -98,21 +112,17 @@ void host_keys(const vpbs_keygen_params* k, std::vector<u64>& s_to, std::vector<
     for (unsigned j = 0; j + 1 < k->K; ++j)
         for (size_t i = 0; i < n; ++i) s_glwe[j * n + i] = binary_coeff(k->seed, S_GLWE, j, i);
 }
-}  // namespace
-
-extern "C" {
-
-int vpbs_keygen(vpbs_ctx* c, const vpbs_keygen_params* k, uint64_t* s_lwe, uint64_t* s_glwe_out, uint64_t* s_to_out, uint64_t* bsk, uint64_t* ksk,
-                int keys_on_device) {
-    if (!c || !params_ok(k)) return VPBS_ERR_INVALID;
+// The secrets to the caller, then the GGSWs of the key set under the split generator (keygen_streams.h): bsk / ksk in the full layout
+// (vpbs_keygen, where mask_seed is the seed itself), or -- bodies_only -- the last polynomial of every GLWE alone, [n_ggsw][K][ELL][N], which
+// is all of a key that a mask_seed does not determine (vpbs_keygen_seeded).  Host or device outputs.
+int keys_from(vpbs_ctx* c, const vpbs_keygen_params* k, u64 mask_seed, const std::vector<u64>& s_to, const std::vector<u64>& s_glwe, uint64_t* s_lwe,
+              uint64_t* s_glwe_out, uint64_t* s_to_out, uint64_t* bsk, uint64_t* ksk, int keys_on_device, bool bodies_only) {
     try {
         using namespace vpbs;
         using namespace vpbs::keygen;
         VPBS_HIP(hipSetDevice(c->device));
         const unsigned log_n = k->log_N, K = k->K, ELL = k->ELL;
         const size_t n = (size_t)1 << log_n, ggsw_words = (size_t)K * ELL * K * n;
-        std::vector<u64> s_to, s_glwe;
-        host_keys(k, s_to, s_glwe);
         if (s_lwe) std::copy(s_to.begin(), s_to.begin() + k->n_lwe, s_lwe);   // flatten_partial_key: the leading n coefficients
         if (s_glwe_out) std::copy(s_glwe.begin(), s_glwe.end(), s_glwe_out);
         if (s_to_out) std::copy(s_to.begin(), s_to.end(), s_to_out);
@@ -128,6 +138,7 @@ int vpbs_keygen(vpbs_ctx* c, const vpbs_keygen_params* k, uint64_t* s_lwe, uint6
         VPBS_HIP(hipMemcpyAsync(d_bits.p, s_to.data(), sizeof(u64) * k->n_lwe, hipMemcpyHostToDevice, c->stream));
         GgswJob job{};
         job.seed = k->seed;
+        job.mask_seed = mask_seed;
         job.log_n = log_n;
         job.K = K;
         job.ELL = ELL;
@@ -138,24 +149,33 @@ int vpbs_keygen(vpbs_ctx* c, const vpbs_keygen_params* k, uint64_t* s_lwe, uint6
             job.kind_mask = kind_mask;
             job.kind_noise = kind_noise;
             job.m_sigma = sigma_to_int(sigma);
-            const size_t words = (size_t)n_ggsw * ggsw_words;
-            u64* d_out = keys_on_device ? out : c->alloc_words(words);
+            const size_t words = (size_t)n_ggsw * ggsw_words, n_glwe = (size_t)n_ggsw * K * ELL;
+            // d_out: the full GGSWs; d_res: what the caller gets, the same or the compact bodies gathered from it
+            const bool own_out = !keys_on_device || bodies_only, own_res = bodies_only && !keys_on_device;
+            u64* d_out = own_out ? c->alloc_words(words) : out;
+            u64* d_res = d_out;
             try {
+                if (bodies_only) d_res = own_res ? c->alloc_words(n_glwe * n) : out;
                 VPBS_HIP(hipMemcpyAsync(d_key.p, key.data(), sizeof(u64) * (K - 1) * n, hipMemcpyHostToDevice, c->stream));
                 launch_negacyclic(c->stream, d_key.p, tab, K - 1, log_n, false, ninv);
                 hipLaunchKernelGGL(ggsw_fill_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, c->stream, job, d_msg.p, d_bits_or_null, d_out);
                 launch_negacyclic(c->stream, d_out, tab, (unsigned)(words / n), log_n, false, ninv);
-                const size_t n_glwe = (size_t)n_ggsw * K * ELL;
                 hipLaunchKernelGGL(ggsw_body_kernel, dim3((unsigned)((n_glwe * n + 255) / 256)), dim3(256), 0, c->stream, log_n, K, n_glwe, d_key.p, d_out);
+                if (bodies_only)
+                    hipLaunchKernelGGL(ggsw_bodies_kernel, dim3((unsigned)((n_glwe * (n / 2) + 255) / 256)), dim3(256), 0, c->stream, log_n, K, n_glwe, d_out,
+                                       d_res);
                 VPBS_HIP(hipGetLastError());
-                if (!keys_on_device) VPBS_HIP(hipMemcpyAsync(out, d_out, sizeof(u64) * words, hipMemcpyDeviceToHost, c->stream));
+                if (!keys_on_device)
+                    VPBS_HIP(hipMemcpyAsync(out, d_res, sizeof(u64) * (bodies_only ? n_glwe * n : words), hipMemcpyDeviceToHost, c->stream));
                 VPBS_HIP(vpbs::stream_sync(c->stream));
             } catch (...) {
                 (void)vpbs::stream_sync(c->stream);
-                if (!keys_on_device) c->release(d_out);
+                if (own_res && d_res != d_out) c->release(d_res);
+                if (own_out) c->release(d_out);
                 throw;
             }
-            if (!keys_on_device) c->release(d_out);
+            if (own_res) c->release(d_res);
+            if (own_out) c->release(d_out);
         };
         // compute_bsk: GGSW i encrypts the constant s_lwe[i] under s_glwe with sigma_glwe
         if (bsk) run(k->n_lwe, s_glwe, d_bits.p, BSK_MASK, BSK_NOISE, k->sigma_glwe, bsk);
@@ -166,6 +186,44 @@ int vpbs_keygen(vpbs_ctx* c, const vpbs_keygen_params* k, uint64_t* s_lwe, uint6
         c->err = e.what;
         return e.status;
     }
+}
+}  // namespace
+
+extern "C" {
+
+int vpbs_keygen(vpbs_ctx* c, const vpbs_keygen_params* k, uint64_t* s_lwe, uint64_t* s_glwe_out, uint64_t* s_to_out, uint64_t* bsk, uint64_t* ksk,
+                int keys_on_device) {
+    if (!c || !params_ok(k)) return VPBS_ERR_INVALID;
+    std::vector<u64> s_to, s_glwe;
+    host_keys(k, s_to, s_glwe);
+    return keys_from(c, k, k->seed, s_to, s_glwe, s_lwe, s_glwe_out, s_to_out, bsk, ksk, keys_on_device, false);
+}
+
+int vpbs_keygen_seeded(vpbs_ctx* c, const vpbs_keygen_params* k, uint64_t mask_seed, const uint64_t* s_lwe_in, const uint64_t* s_glwe_in,
+                       uint64_t* s_lwe, uint64_t* s_glwe_out, uint64_t* s_to_out, uint64_t* bsk_bodies, uint64_t* ksk_bodies, int bodies_on_device) {
+    if (!c) return VPBS_ERR_INVALID;
+    auto refuse = [&](const std::string& what) {
+        c->err = "vpbs_keygen_seeded: " + what;
+        return VPBS_ERR_INVALID;
+    };
+    if (!params_ok(k)) return refuse("unsupported parameters");
+    if (!s_lwe_in != !s_glwe_in) return refuse("s_lwe_in and s_glwe_in are both NULL (the secrets come from the seed) or both given");
+    if (bodies_on_device && ((((uintptr_t)bsk_bodies) | ((uintptr_t)ksk_bodies)) & 15)) return refuse("device pointers must be 16-byte aligned");
+    const size_t n = (size_t)1 << k->log_N;
+    std::vector<u64> s_to, s_glwe;
+    if (!s_lwe_in) {
+        host_keys(k, s_to, s_glwe);
+    } else {
+        // the caller's own secrets: binary words, checked before any output word is written
+        for (size_t x = 0; x < k->n_lwe; ++x)
+            if (s_lwe_in[x] > 1) return refuse("s_lwe_in[" + std::to_string(x) + "] = " + std::to_string(s_lwe_in[x]) + " is neither 0 nor 1");
+        for (size_t x = 0; x < (size_t)(k->K - 1) * n; ++x)
+            if (s_glwe_in[x] > 1) return refuse("s_glwe_in[" + std::to_string(x) + "] = " + std::to_string(s_glwe_in[x]) + " is neither 0 nor 1");
+        s_to.assign((size_t)k->K * n, 0);   // Glwe::partial_key's layout of the caller's LWE key
+        std::copy(s_lwe_in, s_lwe_in + k->n_lwe, s_to.begin());
+        s_glwe.assign(s_glwe_in, s_glwe_in + (size_t)(k->K - 1) * n);
+    }
+    return keys_from(c, k, mask_seed, s_to, s_glwe, s_lwe, s_glwe_out, s_to_out, bsk_bodies, ksk_bodies, bodies_on_device, true);
 }
 
 int vpbs_lwe_encrypt(const vpbs_keygen_params* k, const uint64_t* s_lwe, uint64_t message, uint64_t nonce, uint64_t* ct) {

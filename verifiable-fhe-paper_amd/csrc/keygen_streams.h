@@ -20,6 +20,12 @@ GL_HD u64 mix64(u64 z) {
 GL_HD u64 tag(u64 kind, u64 a, u64 b, u64 c) { return (kind << 56) | (a << 32) | (b << 16) | c; }
 GL_HD u64 stream(u64 seed, u64 t) { return mix64(seed + G * (t + 1)); }
 GL_HD u64 draw(u64 stream_key, u64 i) { return mix64(stream_key + G * (i + 1)); }
+// The SPLIT generator of the seeded calls (vpbs_keygen_seeded, vpbs_key_expand, vpbs_lwe_encrypt_seeded_batch, vpbs_lwe_expand_batch), stated
+// once: the streams of the three MASK kinds are keyed by a public mask_seed, the streams of every other kind (the secrets, the noise) by the
+// private seed.  Tags, draw, field and noise are the ones above and below; with mask_seed == seed this is the one-seed generator.
+// mix64 is NOT a cryptographic generator: the split says who may know which seed, it does not make the noise stream fit for production.
+GL_HD bool is_mask_kind(u64 kind) { return kind == BSK_MASK || kind == KSK_MASK || kind == LWE_MASK; }
+GL_HD u64 split_stream(u64 seed, u64 mask_seed, u64 kind, u64 a, u64 b, u64 c) { return stream(is_mask_kind(kind) ? mask_seed : seed, tag(kind, a, b, c)); }
 GL_HD u64 field(u64 u) { return u >= gl::P ? u - gl::P : u; }
 GL_HD u64 noise(u64 stream_key, u64 i, u64 m_sigma) {
     u64 s = 0;

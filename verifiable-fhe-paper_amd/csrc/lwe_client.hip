@@ -11,6 +11,9 @@
 //   decode:  8 (n + 1) bytes read per row, each word once; the key again from L2.  Statistics: lane 0 of a wave keeps limb sums in registers
 //            over its rows, the workgroup combines them in LDS (ds atomics), and 76 global vector atomics per workgroup -- at most, zero words
 //            are skipped -- add them to the launch's tally.  No workgroup waits for another; the host folds the tally into the caller's struct.
+//   seeded:  vpbs_lwe_encrypt_seeded_batch is encrypt without the row -- 8 bytes written per ciphertext, its body -- and vpbs_lwe_expand_batch
+//            writes the row back from a public mask_seed, the nonce and that body: 8 (n + 1) bytes written, 8 read, one mix64 per word.  The
+//            split generator of keygen_streams.h; mix64 is not a cryptographic generator.
 #include <algorithm>
 #include <string>
 #include <vector>
@@ -144,6 +147,46 @@ __global__ void __launch_bounds__(THREADS) lwe_encrypt_batch_kernel(EncryptJob j
     }
 }
 
+// ---- seeded ciphertexts (the split generator of keygen_streams.h): the client keeps the body word, the server rebuilds the mask ----
+struct SeededJob {
+    u64 seed, mask_seed, m_sigma, nonce0;
+    unsigned n_lwe;
+    size_t count;
+};
+// the body word of one seeded ciphertext on the host, and of lwe_encrypt_seeded_kernel's lane 0 up to the inner product
+GL_HD u64 seeded_body_tail(const SeededJob& j, size_t c, u64 m) {
+    return gl::add(m, keygen::noise(keygen::split_stream(j.seed, j.mask_seed, keygen::LWE_NOISE, j.nonce0 + c, 0, 0), 0, j.m_sigma));
+}
+// bodies[c] = word n_lwe of lwe_encrypt_batch_kernel's row c under the split generator; the mask is drawn, used and never stored
+__global__ void __launch_bounds__(THREADS) lwe_encrypt_seeded_kernel(SeededJob j, const u64* __restrict__ s_lwe, const u64* __restrict__ messages,
+                                                                     u64* __restrict__ bodies, unsigned long long* __restrict__ first_bad) {
+    using namespace keygen;
+    const unsigned lane = threadIdx.x % WAVE, wave = threadIdx.x / WAVE;
+    for (size_t c = (size_t)blockIdx.x * WAVES + wave; c < j.count; c += (size_t)gridDim.x * WAVES) {
+        const u64 m = messages[c];
+        if (m >= gl::P) {   // the same for every lane of the wave
+            if (lane == 0) atomicMin(first_bad, (unsigned long long)c);
+            continue;
+        }
+        const u64 km = split_stream(j.seed, j.mask_seed, LWE_MASK, j.nonce0 + c, 0, 0);
+        u64 acc = 0;
+        for (unsigned i = lane; i < j.n_lwe; i += WAVE) acc = gl::add(acc, gl::mul(field(draw(km, i)), gl::canon(s_lwe[i])));
+        acc = wave_sum(acc);
+        if (lane == 0) bodies[c] = gl::add(acc, seeded_body_tail(j, c, m));
+    }
+}
+// row c = the n_lwe mask words of nonce nonce0 + c under mask_seed, then bodies[c] unchanged; lane l writes words l, l + 64, ..
+__global__ void __launch_bounds__(THREADS) lwe_expand_kernel(u64 mask_seed, u64 nonce0, unsigned n_lwe, size_t count, const u64* __restrict__ bodies,
+                                                             u64* __restrict__ cts) {
+    using namespace keygen;
+    const unsigned lane = threadIdx.x % WAVE, wave = threadIdx.x / WAVE;
+    for (size_t c = (size_t)blockIdx.x * WAVES + wave; c < count; c += (size_t)gridDim.x * WAVES) {
+        const u64 km = stream(mask_seed, tag(LWE_MASK, nonce0 + c, 0, 0));
+        u64* row = cts + c * ((size_t)n_lwe + 1);
+        for (unsigned i = lane; i <= n_lwe; i += WAVE) row[i] = i < n_lwe ? field(draw(km, i)) : bodies[c];
+    }
+}
+
 struct DecodeJob {
     u64 delta, modulus;
     unsigned n_lwe;
@@ -274,6 +317,95 @@ int vpbs_lwe_encrypt_batch(vpbs_ctx* c, const vpbs_keygen_params* k, const uint6
         if (!on_device) VPBS_HIP(hipMemcpyAsync(cts_out, d_out, sizeof(u64) * count * ct_words, hipMemcpyDeviceToHost, c->stream));
         VPBS_HIP(vpbs::stream_sync(c->stream));
         if (bad != ~(u64)0) return bad_message((size_t)bad);
+        return VPBS_OK;
+    } catch (const DeviceError& e) {
+        c->err = e.what;
+        return e.status;
+    }
+}
+
+int vpbs_lwe_encrypt_seeded_batch(vpbs_ctx* c, const vpbs_keygen_params* k, uint64_t mask_seed, const uint64_t* s_lwe, int key_on_device,
+                                  const uint64_t* messages, size_t count, uint64_t nonce0, uint64_t* bodies_out, int on_device) {
+    using namespace vpbs;
+    using namespace vpbs::lwe_client;
+    const char* who = "vpbs_lwe_encrypt_seeded_batch: ";
+    // the refusals of vpbs_lwe_encrypt_batch
+    if (!keygen::params_ok(k)) return refuse(c, std::string(who) + "unsupported parameters");
+    if (!s_lwe || (count && (!messages || !bodies_out))) return refuse(c, std::string(who) + "null pointer");
+    if (!c && (key_on_device || on_device)) return refuse(c, std::string(who) + "device pointers need a context");
+    if (nonce0 > ((u64)1 << 24) || count > ((u64)1 << 24) - nonce0)
+        return refuse(c, std::string(who) + "nonce0 + count exceeds 2^24: ciphertext " +
+                             std::to_string(((u64)1 << 24) - std::min<u64>(nonce0, (u64)1 << 24)) + " is the first without a nonce");
+    if (count == 0) return VPBS_OK;
+    auto bad_message = [&](size_t i) { return refuse(c, std::string(who) + "message " + std::to_string(i) + " is not below p"); };
+    if (!on_device)
+        for (size_t i = 0; i < count; ++i)
+            if (messages[i] >= gl::P) return bad_message(i);
+    const SeededJob job{k->seed, mask_seed, keygen::sigma_to_int(k->sigma_lwe), nonce0, k->n_lwe, count};
+    if (!c) {
+        for (size_t i = 0; i < count; ++i) {
+            const u64 km = keygen::split_stream(job.seed, job.mask_seed, keygen::LWE_MASK, nonce0 + i, 0, 0);
+            u64 body = seeded_body_tail(job, i, messages[i]);
+            for (unsigned x = 0; x < k->n_lwe; ++x)
+                if (s_lwe[x]) body = gl::add(body, gl::mul(keygen::field(keygen::draw(km, x)), s_lwe[x] % gl::P));
+            bodies_out[i] = body;
+        }
+        return VPBS_OK;
+    }
+    try {
+        VPBS_HIP(hipSetDevice(c->device));
+        Scratch tmp(c);
+        const u64* d_key = key_on_device ? s_lwe : tmp.upload(s_lwe, k->n_lwe);
+        const u64* d_msg = on_device ? messages : tmp.upload(messages, count);
+        u64* d_out = on_device ? bodies_out : tmp.words(count);
+        u64* d_bad = tmp.words(1);
+        VPBS_HIP(hipMemsetAsync(d_bad, 0xFF, sizeof(u64), c->stream));
+        hipLaunchKernelGGL(lwe_encrypt_seeded_kernel, dim3(blocks_for(count)), dim3(THREADS), 0, c->stream, job, d_key, d_msg, d_out,
+                           (unsigned long long*)d_bad);
+        VPBS_HIP(hipGetLastError());
+        u64 bad = 0;
+        VPBS_HIP(hipMemcpyAsync(&bad, d_bad, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+        if (!on_device) VPBS_HIP(hipMemcpyAsync(bodies_out, d_out, sizeof(u64) * count, hipMemcpyDeviceToHost, c->stream));
+        VPBS_HIP(vpbs::stream_sync(c->stream));
+        if (bad != ~(u64)0) return bad_message((size_t)bad);
+        return VPBS_OK;
+    } catch (const DeviceError& e) {
+        c->err = e.what;
+        return e.status;
+    }
+}
+
+int vpbs_lwe_expand_batch(vpbs_ctx* c, unsigned n_lwe, uint64_t mask_seed, uint64_t nonce0, const uint64_t* bodies, size_t count, uint64_t* cts_out,
+                          int on_device) {
+    using namespace vpbs;
+    using namespace vpbs::lwe_client;
+    const char* who = "vpbs_lwe_expand_batch: ";
+    if (n_lwe < 1 || n_lwe >= (1u << 24)) return refuse(c, std::string(who) + "n_lwe must be 1 .. 2^24 - 1");
+    if (count && (!bodies || !cts_out)) return refuse(c, std::string(who) + "null pointer");
+    if (!c && on_device) return refuse(c, std::string(who) + "device pointers need a context");
+    if (nonce0 > ((u64)1 << 24) || count > ((u64)1 << 24) - nonce0)
+        return refuse(c, std::string(who) + "nonce0 + count exceeds 2^24: ciphertext " +
+                             std::to_string(((u64)1 << 24) - std::min<u64>(nonce0, (u64)1 << 24)) + " is the first without a nonce");
+    if (count == 0) return VPBS_OK;
+    const size_t ct_words = (size_t)n_lwe + 1;
+    if (!c) {
+        for (size_t i = 0; i < count; ++i) {
+            const u64 km = keygen::stream(mask_seed, keygen::tag(keygen::LWE_MASK, nonce0 + i, 0, 0));
+            u64* row = cts_out + i * ct_words;
+            for (unsigned x = 0; x < n_lwe; ++x) row[x] = keygen::field(keygen::draw(km, x));
+            row[n_lwe] = bodies[i];
+        }
+        return VPBS_OK;
+    }
+    try {
+        VPBS_HIP(hipSetDevice(c->device));
+        Scratch tmp(c);
+        const u64* d_bodies = on_device ? bodies : tmp.upload(bodies, count);
+        u64* d_out = on_device ? cts_out : tmp.words(count * ct_words);
+        hipLaunchKernelGGL(lwe_expand_kernel, dim3(blocks_for(count)), dim3(THREADS), 0, c->stream, mask_seed, nonce0, n_lwe, count, d_bodies, d_out);
+        VPBS_HIP(hipGetLastError());
+        if (!on_device) VPBS_HIP(hipMemcpyAsync(cts_out, d_out, sizeof(u64) * count * ct_words, hipMemcpyDeviceToHost, c->stream));
+        VPBS_HIP(vpbs::stream_sync(c->stream));
         return VPBS_OK;
     } catch (const DeviceError& e) {
         c->err = e.what;

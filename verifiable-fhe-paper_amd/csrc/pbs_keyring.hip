@@ -191,6 +191,11 @@ int vpbs_keyring_add(vpbs_keyring* r, const uint64_t* bsk, const uint64_t* ksk, 
     return vpbs::keyring_add(r, bsk, ksk, keys_on_device, slot_out, false);
 }
 
+int vpbs_keyring_add_seeded(vpbs_keyring* r, uint64_t mask_seed, const uint64_t* bsk_bodies, const uint64_t* ksk_bodies, int bodies_on_device,
+                            unsigned* slot_out) {
+    return vpbs::keyring_add_seeded(r, mask_seed, bsk_bodies, ksk_bodies, bodies_on_device, slot_out, false);
+}
+
 int vpbs_keyring_remove(vpbs_keyring* r, unsigned slot) { return vpbs::keyring_remove(r, slot, false); }
 }  // extern "C"
 
@@ -243,6 +248,48 @@ int keyring_add(vpbs_keyring* r, const uint64_t* bsk, const uint64_t* ksk, int k
         fresh.ksk = entry.ksk;
         VPBS_HIP(hipMemcpyAsync(r->d_table + s, &entry, sizeof entry, hipMemcpyHostToDevice, ctx->stream));
         VPBS_HIP(vpbs::stream_sync(ctx->stream));   // the caller's key arrays, and `entry`, may go away
+    } catch (const DeviceError& e) {
+        ctx->err = e.what;
+        (void)vpbs::stream_sync(ctx->stream);
+        ctx->release(fresh.own_bsk);
+        ctx->release(fresh.own_ksk);
+        return e.status;
+    }
+    r->slots[s] = fresh;
+    ++r->used;
+    *slot_out = (unsigned)s;
+    return VPBS_OK;
+}
+
+int keyring_add_seeded(vpbs_keyring* r, uint64_t mask_seed, const uint64_t* bsk_bodies, const uint64_t* ksk_bodies, int bodies_on_device,
+                       unsigned* slot_out, bool owner) {
+    if (!r || !bsk_bodies || !ksk_bodies || !slot_out) return VPBS_ERR_INVALID;
+    std::lock_guard<std::mutex> lock(r->mu);
+    vpbs_ctx* ctx = r->ctx;
+    if (refuse_owned(r, owner, "vpbs_keyring_add_seeded")) return VPBS_ERR_INVALID;
+    size_t s = 0;
+    while (s < r->max_keys && r->slots[s].used) ++s;
+    if (s == r->max_keys) {
+        ctx->err = "vpbs_keyring_add_seeded: all " + std::to_string(r->max_keys) + " slots of the ring are taken (max_keys)";
+        return VPBS_ERR_INVALID;
+    }
+    if (bodies_on_device && ((((uintptr_t)bsk_bodies) | ((uintptr_t)ksk_bodies)) & 15)) {
+        ctx->err = "vpbs_keyring_add_seeded: device pointers must be 16-byte aligned";
+        return VPBS_ERR_INVALID;
+    }
+    vpbs_keyring::Slot fresh;
+    fresh.used = true;
+    try {
+        VPBS_HIP(hipSetDevice(ctx->device));
+        // the slot owns the expanded key set exactly as it owns an uploaded one
+        fresh.own_bsk = ctx->alloc_words((size_t)r->n_lwe * r->ggsw_words);
+        fresh.own_ksk = ctx->alloc_words(r->ggsw_words);
+        key_expand_device(ctx, r->prm, r->n_lwe, mask_seed, bsk_bodies, ksk_bodies, bodies_on_device, fresh.own_bsk, fresh.own_ksk);
+        fresh.bsk = fresh.own_bsk;
+        fresh.ksk = fresh.own_ksk;
+        const KeySlot entry{fresh.bsk, fresh.ksk};
+        VPBS_HIP(hipMemcpyAsync(r->d_table + s, &entry, sizeof entry, hipMemcpyHostToDevice, ctx->stream));
+        VPBS_HIP(vpbs::stream_sync(ctx->stream));
     } catch (const DeviceError& e) {
         ctx->err = e.what;
         (void)vpbs::stream_sync(ctx->stream);

@@ -153,6 +153,42 @@ int vpbs_ring_prover_add(vpbs_ring_prover* p, const uint64_t* bsk, const uint64_
     return VPBS_OK;
 }
 
+int vpbs_ring_prover_add_seeded(vpbs_ring_prover* p, uint64_t mask_seed, const uint64_t* bsk_bodies, const uint64_t* ksk_bodies, int bodies_on_device,
+                                unsigned* slot_out, char* err, size_t err_len) {
+    using namespace vpbs;
+    report(err, err_len, "");
+    if (!p || !bsk_bodies || !ksk_bodies || !slot_out) return report(err, err_len, "null argument"), VPBS_ERR_INVALID;
+    vpbs_ctx* ctx = p->pool.boot_ctx;
+    vpbs_ring_prover::Slot fresh;
+    fresh.links.resize(4 * (size_t)p->pool.total);
+    // ---- the slot first: the keys exist only once the ring has expanded them; then their hash chain as add walks it for device-only keys ----
+    std::lock_guard<std::mutex> run(p->run_mu);
+    unsigned slot = 0;
+    int rc = keyring_add_seeded(p->ring, mask_seed, bsk_bodies, ksk_bodies, bodies_on_device, &slot, true);
+    if (rc != VPBS_OK) return report(err, err_len, vpbs_last_error(ctx)), rc;
+    try {
+        VPBS_HIP(hipSetDevice(p->pool.device));
+        keyring_slot_keys(p->ring, slot, &fresh.d_bsk, &fresh.d_ksk);   // no add or remove is under way: run_mu
+        key_hash_links(fresh.d_bsk, fresh.d_ksk, 1, p->pool.n_lwe, p->pool.shape.ggsw_len, fresh.links.data());
+        std::lock_guard<std::mutex> lk(keyring_mutex(p->ring));   // the context's pool is the ring's too
+        fresh.d_links = ctx->alloc_words(fresh.links.size());
+        VPBS_HIP(hipMemcpyAsync(fresh.d_links, fresh.links.data(), 8 * fresh.links.size(), hipMemcpyHostToDevice, ctx->stream));
+        VPBS_HIP(vpbs::stream_sync(ctx->stream));
+    } catch (const DeviceError& x) {
+        (void)vpbs::stream_sync(ctx->stream);
+        {
+            std::lock_guard<std::mutex> lk(keyring_mutex(p->ring));
+            ctx->release(fresh.d_links);
+        }
+        (void)keyring_remove(p->ring, slot, true);
+        report(err, err_len, x.what);
+        return x.status;
+    }
+    p->slots[slot] = std::move(fresh);
+    *slot_out = slot;
+    return VPBS_OK;
+}
+
 int vpbs_ring_prover_remove(vpbs_ring_prover* p, unsigned slot, char* err, size_t err_len) {
     using namespace vpbs;
     report(err, err_len, "");

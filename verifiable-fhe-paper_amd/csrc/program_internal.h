@@ -76,6 +76,20 @@ void keyring_slot_keys(const vpbs_keyring* r, unsigned slot, const uint64_t** d_
 void keyring_set_owned(vpbs_keyring* r);
 int keyring_add(vpbs_keyring* r, const uint64_t* bsk, const uint64_t* ksk, int keys_on_device, unsigned* slot_out, bool owner);
 int keyring_remove(vpbs_keyring* r, unsigned slot, bool owner);
+// vpbs_keyring_add_seeded is this with owner = false: the key set expanded from mask_seed and its bodies (key_expand_device) into memory the
+// ring owns, which keyring_remove frees as it frees what keyring_add uploaded; the slot number by keyring_add's rule
+int keyring_add_seeded(vpbs_keyring* r, uint64_t mask_seed, const uint64_t* bsk_bodies, const uint64_t* ksk_bodies, int bodies_on_device,
+                       unsigned* slot_out, bool owner);
+
+// ---- seeded key sets (key_seeded.hip) ----
+// the shapes vpbs_key_expand takes; false with the reason in *why
+bool key_expand_shape_ok(const vpbs_tfhe_params* prm, unsigned n_lwe, std::string* why);
+// The full keys in vpbs_keygen's layout at the DEVICE pointers d_bsk [n_lwe][K][ELL][K][N] and d_ksk [K][ELL][K][N] (16-byte aligned): the mask
+// polynomials from mask_seed, the last polynomial of every GLWE from bsk_bodies [n_lwe][K][ELL][N] / ksk_bodies [K][ELL][N] (host arrays,
+// uploaded for the call, or 16-byte aligned device pointers).  A pair (bodies, output) with a null member is skipped.  On the context's
+// stream; returns after the wait.  Throws vpbs::DeviceError; the caller holds the device and whatever guards the context's pool.
+void key_expand_device(vpbs_ctx* c, const vpbs_tfhe_params& prm, unsigned n_lwe, uint64_t mask_seed, const uint64_t* bsk_bodies,
+                       const uint64_t* ksk_bodies, int bodies_on_device, uint64_t* d_bsk, uint64_t* d_ksk);
 
 // ---- the ring prover (pbs_prove_ring.hip), for vpbs_program_prove_batch ----
 // the mutex that add, remove and run of the ring prover take, and vpbs_ring_prover_run for a caller that holds it and has made the
