@@ -1606,8 +1606,9 @@ void* vpbs_host_alloc(size_t bytes);
 void vpbs_host_free(void* p);
 int vpbs_device_alloc(vpbs_ctx* ctx, size_t words, uint64_t** out);
 int vpbs_device_upload(vpbs_ctx* ctx, uint64_t* d_dst, const uint64_t* host_src, size_t words); /* returns after the copy has completed */
-/* The same copy on the context's upload stream, for a second host thread: it may run while another call (vpbs_prove_step ...) is in
- * progress on the context, touches none of the context's state and reports failures by return code only (vpbs_last_error is not set).
+/* The same copy on the upload stream of the context's DEVICE (one stream, shared by the contexts there, made by the first call and gone with
+ * the last context), for a second host thread: it may run while another call (vpbs_prove_step ...) is in progress on the context, touches
+ * none of the context's state and reports failures by return code only (vpbs_last_error is not set).  Returns after its own copy has completed.
  * An IVC host uploads the early-phase wires of the NEXT step with it while the current step is being proven. */
 int vpbs_device_upload_bg(vpbs_ctx* ctx, uint64_t* d_dst, const uint64_t* host_src, size_t words);
 /* Rows [row_lo, row_hi) of every column of a column-major [n_cols][n] matrix (one strided copy; the late phase of a split witness plan

@@ -446,6 +446,7 @@ INTERNAL_SIGNATURES = {
     "vpbs_test_pbs_prover_preset_words": (_sz, [_vp]),
     "vpbs_test_pbs_prover_dummy_proof": (_i, [_vp, U64P]),
     "vpbs_test_aggregator_preset_matrix": (_i, [_vp, _ui, U64P, _sz, _vp, _ui, U64P]),
+    "vpbs_test_stream_counts": (_i, [_i, C.POINTER(_ui)]),
 }
 
 _lib = None
@@ -3942,8 +3943,8 @@ class Context:
         return out.value
 
     def upload_bg(self, d_dst, host, words):
-        """vpbs_device_upload_bg: host (pinned) -> device pointer on the context's upload stream; callable from a second thread while a
-        prover call runs on the context"""
+        """vpbs_device_upload_bg: host (pinned) -> device pointer on the upload stream the contexts of a device share; callable from a
+        second thread while a prover call runs on the context"""
         if lib().vpbs_device_upload_bg(self.h, C.c_void_p(int(d_dst)), C.c_void_p(int(host)), int(words)):
             raise VpbsError("vpbs_device_upload_bg failed")
 

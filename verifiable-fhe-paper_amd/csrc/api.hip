@@ -14,6 +14,7 @@
 #include "context.h"
 #include "poseidon.h"
 #include "host/poseidon_x8.h"
+#include "test_entries.h"
 
 using vpbs::DeviceError;
 using vpbs::u64;
@@ -182,15 +183,30 @@ static bool launch_class_error(hipError_t e) {
             return false;
     }
 }
-hipError_t stream_sync(hipStream_t s) {
+// The wait of stream_sync; `copy` (may be null): a host->device copy queued on the stream in front of the marker, under the lock that makes
+// sequence number and marker one step -- so on a stream several threads use, nobody's copy gets between another thread's copy and its marker
+namespace {
+struct CopyAhead {
+    void* dst;
+    const void* src;
+    size_t bytes;
+    hipError_t queue(hipStream_t s) const { return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s); }
+};
+}  // namespace
+static hipError_t stream_sync_behind(hipStream_t s, const CopyAhead* copy) {
     struct Waiter {
         int n;
         Waiter() : n(g_sync_waiters.fetch_add(1, std::memory_order_relaxed) + 1) {}
         ~Waiter() { g_sync_waiters.fetch_sub(1, std::memory_order_relaxed); }
     } waiter;
     const bool block = this_wait_sleeps(waiter.n);
-    if (sync_word_mode()) {
-        if (SyncWord* w = sync_word_of(s)) {
+    SyncWord* const word_of_s = sync_word_mode() ? sync_word_of(s) : nullptr;   // decided once per wait
+    if (copy && !word_of_s) {   // the waits below go through the runtime: they cover whatever is on the stream
+        if (const hipError_t e = copy->queue(s); e != hipSuccess) return e;
+        copy = nullptr;
+    }
+    if (word_of_s) {
+        if (SyncWord* w = word_of_s) {
             // A launch that failed earlier on this thread (bad configuration, out of resources) left its error pending and the buffers it should
             // have written untouched: the wait reports it instead of waiting for work that was never queued -- and it must not CONSUME the
             // thread's error state either (hipGetLastError here once hid such failures from the checks at the end of the stages: ADVICE r04).
@@ -203,6 +219,8 @@ hipError_t stream_sync(hipStream_t s) {
             hipError_t launched;
             {
                 std::lock_guard<std::mutex> lk(w->mu);
+                if (copy)
+                    if (const hipError_t e = copy->queue(s); e != hipSuccess) return e;
                 seq = ++w->seq;
                 u64* word = w->dev;
                 void* args[] = {&word, &seq};
@@ -244,6 +262,60 @@ hipError_t stream_sync(hipStream_t s) {
         if (i < 64) continue;
         nap(0);
     }
+}
+hipError_t stream_sync(hipStream_t s) { return stream_sync_behind(s, nullptr); }
+hipError_t stream_upload_sync(hipStream_t s, void* d_dst, const void* host_src, size_t bytes) {
+    const CopyAhead copy{d_dst, host_src, bytes};
+    return stream_sync_behind(s, &copy);
+}
+
+// ---- the streams the library holds on a device ----
+// A context creates ONE stream, its prover stream, so contexts created one after another take consecutive hardware queues of the runtime
+// (Host side).  The host->device copies of vpbs_device_upload_bg go through one stream per DEVICE, made by the first such call of
+// any context there and destroyed when the last context on the device closes: most contexts never upload, and the ones that do wait for their
+// own copy only (stream_upload_sync).  It has the lowest priority the device offers -- the runtime keeps its hardware queues per priority, and
+// a marker behind a 70 MB copy must not sit in a queue in front of a prover's kernels.
+namespace {
+struct DeviceStreams {
+    unsigned contexts = 0;          // open contexts = prover streams
+    unsigned gate_lanes = 0;        // gate-lane streams of those contexts (vpbs_ctx::ensure_gate_lanes)
+    hipStream_t upload = nullptr;
+};
+std::mutex g_device_streams_mu;
+std::map<int, DeviceStreams> g_device_streams;
+}  // namespace
+void device_streams_note(int device, int contexts, int gate_lanes) {
+    hipStream_t last = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(g_device_streams_mu);
+        DeviceStreams& d = g_device_streams[device];
+        d.contexts += contexts;
+        d.gate_lanes += gate_lanes;
+        if (d.contexts == 0) std::swap(last, d.upload);
+    }
+    if (last) {   // nobody is left who could upload through it (the caller has selected the device)
+        (void)stream_sync(last);
+        stream_sync_forget(last);
+        (void)hipStreamDestroy(last);
+    }
+}
+// the device's upload stream, created on first use; the calling thread has selected the device and holds an open context on it
+static hipStream_t device_upload_stream(int device) {
+    std::lock_guard<std::mutex> lk(g_device_streams_mu);
+    DeviceStreams& d = g_device_streams[device];
+    if (!d.upload) {
+        int least = 0, greatest = 0;
+        if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess ||
+            hipStreamCreateWithPriority(&d.upload, hipStreamNonBlocking, least) != hipSuccess)
+            d.upload = nullptr;
+    }
+    return d.upload;
+}
+void device_stream_counts(int device, unsigned out[2]) {
+    std::lock_guard<std::mutex> lk(g_device_streams_mu);
+    auto it = g_device_streams.find(device);
+    out[0] = it == g_device_streams.end() ? 0 : it->second.contexts;
+    out[1] = it == g_device_streams.end() ? 0 : it->second.gate_lanes + (it->second.upload ? 1 : 0);
 }
 }  // namespace vpbs
 
@@ -455,7 +527,10 @@ void vpbs_ctx::d2h_sync(void* dst, const void* d_src, size_t bytes) {
 }
 void vpbs_ctx::ensure_gate_lanes() {
     if (gate_fork) return;
-    for (auto& st : gate_streams) VPBS_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+    for (auto& st : gate_streams) {
+        VPBS_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+        vpbs::device_streams_note(device, 0, 1);
+    }
     VPBS_HIP(hipEventCreateWithFlags(&gate_fork, hipEventDisableTiming));
     for (auto& e : gate_join) VPBS_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
 }
@@ -663,12 +738,12 @@ int vpbs_ctx_create(int device_ordinal, unsigned log_n_max, unsigned rate_bits, 
     c->log_n_max = log_n_max;
     c->rate_bits = rate_bits;
     c->cap_height = cap_height;
-    if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipStreamCreateWithFlags(&c->upload_stream, hipStreamNonBlocking) != hipSuccess) {
-        if (c->stream) (void)hipStreamDestroy(c->stream);
+    // the prover stream and nothing else: contexts created one after another take consecutive hardware queues
+    if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
         delete c;
         return VPBS_ERR_DEVICE;
     }
+    vpbs::device_streams_note(device_ordinal, 1, 0);
     *out = c;
     return VPBS_OK;
 }
@@ -687,19 +762,20 @@ void vpbs_ctx_destroy(vpbs_ctx* c) {
     for (auto e : c->event_pool) (void)hipEventDestroy(e);
     for (auto& kv : c->free_blocks) (void)hipFree(kv.second);
     if (c->pinned) (void)hipHostFree(c->pinned);
+    int lanes = 0;
     for (auto st : c->gate_streams)
         if (st) {
             vpbs::stream_sync_forget(st);
             (void)hipStreamDestroy(st);
+            ++lanes;
         }
     if (c->gate_fork) (void)hipEventDestroy(c->gate_fork);
     for (auto e : c->gate_join)
         if (e) (void)hipEventDestroy(e);
-    (void)vpbs::stream_sync(c->upload_stream);
-    vpbs::stream_sync_forget(c->upload_stream);
     vpbs::stream_sync_forget(c->stream);
-    (void)hipStreamDestroy(c->upload_stream);
     (void)hipStreamDestroy(c->stream);
+    // the device's upload stream is other contexts' as well: it is neither waited on nor destroyed here unless this context is the last
+    vpbs::device_streams_note(c->device, -1, -lanes);
     delete c;
 }
 
@@ -1167,11 +1243,18 @@ int vpbs_device_upload(vpbs_ctx* c, uint64_t* d_dst, const uint64_t* host_src, s
     });
 }
 int vpbs_device_upload_bg(vpbs_ctx* c, uint64_t* d_dst, const uint64_t* host_src, size_t words) {
-    // nothing of the context is touched except its (immutable) device ordinal and upload stream: safe beside a running prover call
+    // nothing of the context is touched except its (immutable) device ordinal: safe beside a running prover call.  The copy goes through the
+    // device's one upload stream, which the contexts there share: queued together with its marker, waited for outside the stream's lock
     if (!c || !d_dst || !host_src) return VPBS_ERR_INVALID;
     if (hipSetDevice(c->device) != hipSuccess) return VPBS_ERR_DEVICE;
-    if (hipMemcpyAsync(d_dst, host_src, sizeof(u64) * words, hipMemcpyHostToDevice, c->upload_stream) != hipSuccess) return VPBS_ERR_DEVICE;
-    return vpbs::stream_sync(c->upload_stream) == hipSuccess ? VPBS_OK : VPBS_ERR_DEVICE;
+    hipStream_t up = vpbs::device_upload_stream(c->device);
+    if (!up) return VPBS_ERR_DEVICE;
+    return vpbs::stream_upload_sync(up, d_dst, host_src, sizeof(u64) * words) == hipSuccess ? VPBS_OK : VPBS_ERR_DEVICE;
+}
+int vpbs_test_stream_counts(int device, unsigned out[2]) {
+    if (!out || device < 0) return VPBS_ERR_INVALID;
+    vpbs::device_stream_counts(device, out);
+    return VPBS_OK;
 }
 int vpbs_device_upload_rows(vpbs_ctx* c, uint64_t* d_dst, const uint64_t* host_src, unsigned n_cols, size_t n, size_t row_lo, size_t row_hi) {
     if (!c || !d_dst || !host_src || row_lo > row_hi || row_hi > n) return VPBS_ERR_INVALID;

@@ -56,6 +56,13 @@ int blocking_sync_mode();                 // 0 spin, 1 block
 hipError_t stream_sync(hipStream_t s);    // drop-in for hipStreamSynchronize
 void stream_sync_forget(hipStream_t s);   // before hipStreamDestroy: the stream's completion word (api.hip) is freed
 int sync_word_mode();                     // 1: waits read a word the device writes (default); 0: they go through the runtime
+// host->device copy on `s` and the wait for it; copy and marker are queued as one step, so a caller on a stream that several threads share
+// waits for its own copy and for what was queued before it, never for a copy another thread queued behind it
+hipError_t stream_upload_sync(hipStream_t s, void* d_dst, const void* host_src, size_t bytes);
+// The streams the library holds per device (api.hip): a context's prover stream is counted from vpbs_ctx_create to vpbs_ctx_destroy, its
+// gate-lane streams as they come and go; the last context to close takes the device's upload stream with it (the caller has selected the device).
+void device_streams_note(int device, int contexts, int gate_lanes);
+void device_stream_counts(int device, unsigned out[2]);   // {prover streams, auxiliary streams: upload stream + gate lanes}
 // out[k] = hash_no_pad(h_{k-1} || items[k]), h_{-1} = prefix; concurrent callers with long items share the lanes of the eight-lane host Poseidon
 void hash_links_shared(const u64 prefix[4], const u64* const* items, size_t n_links, size_t item_len, u64* out);
 // The key hash chain of ONE key set, every link kept: links [n_lwe + 2][4] over the items [0^ggsw_len, bsk_0 .. bsk_{n-1}, ksk] from a zero
@@ -68,8 +75,7 @@ void blocking_sync_budget_changed();      // the process's CPU budget was set: A
 
 struct vpbs_ctx {
     int device = 0;
-    hipStream_t stream = nullptr;
-    hipStream_t upload_stream = nullptr;   // vpbs_device_upload_bg: host->device copies next to the work on `stream`
+    hipStream_t stream = nullptr;   // the one stream a context creates; vpbs_device_upload_bg goes through the device's shared upload stream (api.hip)
     unsigned log_n_max = 0, rate_bits = 3, cap_height = 4;
     vpbs::Tuning tune = vpbs::Tuning::from_env();   // vpbs_ctx_set_option
     vpbs_compat compat{0, 1, 1, 1};   // vpbs_compat_default: plonky2 0.2.0 as restated (include/vpbs_prover.h, the switch table)

@@ -30,6 +30,10 @@ int vpbs_test_pbs_prover_dummy_proof(const vpbs_pbs_prover* p, uint64_t* out);
 // have, batch = 0 or above max_nodes, n_rows = 0 or above 2 batch, a pair entry at or above n_rows.
 int vpbs_test_aggregator_preset_matrix(vpbs_aggregator* a, unsigned level, const uint64_t* rows, size_t n_rows, const uint32_t* pairs, unsigned batch,
                                        uint64_t* out);
+// The streams the library holds on a device right now: out[0] the prover streams (one per open context, the witness contexts of a device
+// pipeline included), out[1] the auxiliary ones (the device's shared upload stream once a vpbs_device_upload_bg has made it, and the gate-lane
+// streams of contexts that ran with three gate lanes).  Touches no device.  VPBS_ERR_INVALID for a null pointer or a negative ordinal.
+int vpbs_test_stream_counts(int device, unsigned out[2]);
 long vpbs_test_proof_byte_tables(const vpbs_verify_inputs* in, size_t src_capacity, size_t lenb_capacity, uint32_t* src, uint32_t* lenb_off,
                                  uint8_t* lenb_val, size_t* n_src, size_t* n_lenb);
 }
