@@ -20,6 +20,10 @@ NAMES = ["vpbs_program_gate_inputs", "vpbs_program_aggregate_root", "vpbs_progra
 FOUR = [([(0, 1)], 0, 0, 1, 2), ([(1, 1), (0, P - 1)], 7, 1, 2, 3), ([(3, 1), (6, P - 1)], 0, 0), ([(2, 1), (4, 3)], 0, 1, 1, 1)]
 # plain gates only (lwe_extract's rows), every input read, a gate without terms
 PLAIN = [([(0, 1), (1, 2)], 0, 0), ([], 5, 1), ([(2, P - 1), (3, 1)], 9, 1)]
+# the last gate reads an input together with outputs of two different levels (gate 0: level 1, gate 1: level 2): plain, and with the
+# outputs of multi-output gates that are not their gate's first
+DEEP = [([(0, 1)], 0, 0), ([(2, 1), (1, 2)], 3, 1), ([(0, P - 1), (2, 5), (3, 1)], 1, 0)]
+DEEP_MULTI = [([(0, 1)], 0, 0, 1, 2), ([(3, 1), (1, 2)], 3, 1, 2, 3), ([(1, P - 1), (3, 5), (6, 1)], 1, 0, 1, 1)]
 
 
 def test_library_exports_the_entry_points_and_api_binds_them():
@@ -49,9 +53,11 @@ def want_gate_inputs(gates, n_inputs, inputs, out_cts, n, log_n):
     return M.gate_inputs(n_inputs, gates, wires, n + 1, log_n)
 
 
-@pytest.mark.parametrize("gates,log_n,K,n", [(FOUR, 3, 2, 6), (FOUR, 3, 3, 12), (PLAIN, 3, 2, 6), (PLAIN, 2, 3, 5)])
+@pytest.mark.parametrize("gates,log_n,K,n", [(FOUR, 3, 2, 6), (FOUR, 3, 3, 12), (PLAIN, 3, 2, 6), (PLAIN, 2, 3, 5), (DEEP, 2, 3, 5),
+                                             (DEEP_MULTI, 3, 2, 6)])
 def test_gate_inputs_against_the_restatement(gates, log_n, K, n):
-    """(3, 3, 12) and (2, 3, 5): the extraction crosses a polynomial; input words p - 1, p and 2^64 - 1; two instances; a host-only program"""
+    """(3, 3, 12) and (2, 3, 5): the extraction crosses a polynomial; input words p - 1, p and 2^64 - 1; two instances; a host-only program;
+    DEEP and DEEP_MULTI: one gate reads an input and outputs of two levels"""
     N = 1 << log_n
     prog = api.Program(None, 2, gates, 2)
     inputs, out_cts, _ = statement(70 + K + n, gates, 2, log_n, K, n)

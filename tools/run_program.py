@@ -41,10 +41,12 @@ usage: tools/run_program.py [--levels L] [--width W] [--fan-in F] [--program FIL
     from the same seeds): its wires must be the batched leg's, ALL instances are verified by one api.Program.verify_batch on an
     api.RingVerifier whose slot k holds the ring prover's key_hash(k) (verify_seconds), and the decrypted outputs are the proven ones.
     --verify-per-instance: the proofs are checked a second time by api.Program.verify per instance on the api.PbsVerifier of its key set
-    (verify_per_instance_seconds, verify_per_instance_equal).
+    (verify_per_instance_seconds, verify_per_instance_equal).  With --runs R > 1 both forms are called R more times after that first call
+    (verify_again, verify_per_instance_again: seconds per call, event time and launches of their combine kernel).
   Time: wall seconds per run of a leg (after one warm-up run), per level = / levels; HIP-event milliseconds of the bootstrap launches per
   level (the library's own timers).  Bytes: what each leg moves between host and device per run, computed from the shapes."""
 import argparse
+import hashlib
 import json
 import os
 import statistics
@@ -195,6 +197,7 @@ def prove_batch(args, ctx, prog, N, n_lwe, log_n, M, inputs, key_of, testvs, bat
     t = time.perf_counter()
     proofs, wires, out_cts = prog.prove_batch(rp, inputs, key_of, testvs)
     out["prove_seconds"] = time.perf_counter() - t
+    out["proofs_sha256"] = hashlib.sha256(b"".join(blob for row in proofs for blob in row)).hexdigest()   # to compare two builds on one seed
     hashes, (vk, _) = [rp.key_hash(k) for k in range(M)], rp.verifier_data()
     aggregated = True
     if args.aggregate:   # one aggregate per instance: proven again, now folded, and checked on the host and on the device
@@ -218,6 +221,17 @@ def prove_batch(args, ctx, prog, N, n_lwe, log_n, M, inputs, key_of, testvs, bat
     t = time.perf_counter()
     verdicts, reasons, _ = prog.verify_batch(rv, inputs, key_of, testvs, out_cts, proofs)
     out["verify_seconds"] = time.perf_counter() - t
+
+    def again(call):   # --runs R > 1: R more calls after that first one -> (seconds of each, event ms and launches of their combine kernel)
+        secs = []
+        ctx.timing_report()
+        for _ in range(args.runs if args.runs > 1 else 0):
+            t0 = time.perf_counter()
+            call()
+            secs.append(time.perf_counter() - t0)
+        rep = ctx.timing_report().get("lwe_combine", {})
+        return {"seconds": secs, "combine_event_ms": rep.get("ms", 0.0), "combine_launches": rep.get("count", 0)}
+    out["verify_again"] = again(lambda: prog.verify_batch(rv, inputs, key_of, testvs, out_cts, proofs))
     rv.close()
     verified = int(verdicts.sum())
     why = {api.pbs_reason_text(int(r)) for v, r in zip(verdicts.reshape(-1), reasons.reshape(-1)) if not v}
@@ -226,6 +240,7 @@ def prove_batch(args, ctx, prog, N, n_lwe, log_n, M, inputs, key_of, testvs, bat
         t = time.perf_counter()
         each = [prog.verify(pvs[key_of[b]], inputs[b], testvs, out_cts[b], proofs[b]) for b in range(len(key_of))]
         out["verify_per_instance_seconds"] = time.perf_counter() - t
+        out["verify_per_instance_again"] = again(lambda: [prog.verify(pvs[key_of[b]], inputs[b], testvs, out_cts[b], proofs[b]) for b in range(len(key_of))])
         for pv in pvs:
             pv.close()
         out["verify_per_instance_equal"] = bool(all((e[0] == verdicts[b]).all() and (e[1] == reasons[b]).all() for b, e in enumerate(each)))
@@ -287,7 +302,9 @@ def main_batch(args):
                             keys_on_device=True) for k in keys]
     per_instance = lambda: np.stack([prog.run(bss[key_of[b]], inputs[b], testvs, gate_cts=False, out_cts=False)[0] for b in range(B)]) \
         if B else np.zeros((0, n_inputs + n_gates, words), np.uint64)
-    base_wires, _, out["baseline"] = leg(per_instance, "pbs_batch")
+    base_wires, base_rep, out["baseline"] = leg(per_instance, "pbs_batch")
+    out["baseline"].update({"combine_event_ms": base_rep.get("lwe_combine", {}).get("ms", 0.0),   # of the last run, as the batched leg's
+                            "combine_launches": base_rep.get("lwe_combine", {}).get("count", 0)})
     for bs in bss:
         bs.close()
     wires, ok = base_wires, True
@@ -312,6 +329,7 @@ def main_batch(args):
                              "d2h_bytes": 8 * B * (n_inputs + n_gates) * words})
         out["batch_over_baseline"] = statistics.median(out["batch"]["seconds"]) / statistics.median(out["baseline"]["seconds"])
         out["all_equal"] = bool(wires.shape == base_wires.shape and (wires == base_wires).all())
+        out["wires_sha256"] = hashlib.sha256(np.ascontiguousarray(wires).tobytes()).hexdigest()
         ok = out["all_equal"] and (not args.prove or proven)
     prog.close()
     # ---- every program output (the wires of the last level), under its own key ----

@@ -2649,7 +2649,13 @@ def program_aggregate_args(who, n_inputs, n_gates, n_luts, N, K, n_lwe, inputs, 
 
 
 def _keep_ptr(a):
-    return _ptr(a if a.size else np.zeros(1, np.uint64))
+    """a uint64 array as a pointer -- a valid one for an empty array too; None stays None"""
+    return None if a is None else _ptr(a if a.size else np.zeros(1, np.uint64))
+
+
+def _keep_u32(a):
+    """the same for a uint32 array, as a void pointer"""
+    return (a if a.size else np.zeros(1, np.uint32)).ctypes.data_as(C.c_void_p)
 
 
 def program_gate_inputs(prog, N, K, n_lwe, inputs, out_cts):
@@ -3061,8 +3067,7 @@ class Program:
         wires = np.zeros((self.n_wires, b.n_lwe + 1), np.uint64)
         cts = np.zeros((self.n_gates, b.n_lwe + 1), np.uint64) if gate_cts else None
         out = np.zeros((self.n_gates, b.K, b.N), np.uint64) if out_cts else None
-        keep = np.zeros(1, np.uint64)   # a valid pointer for an empty array
-        p = lambda a: None if a is None else (a if a.size else keep).ctypes.data
+        p = _keep_ptr
         rc = lib().vpbs_program_run(self.h, b.h, p(x), p(tv), p(wires), p(cts), p(out), 0)
         if rc < 0:
             raise VpbsError("vpbs_program_run: status %d: %s" % (rc, lib().vpbs_last_error(b.ctx.h).decode()))
@@ -3096,9 +3101,8 @@ class Program:
         wires = np.zeros((count, self.n_wires, r.n_lwe + 1), np.uint64)
         cts = np.zeros((count, self.n_gates, r.n_lwe + 1), np.uint64) if gate_cts else None
         out = np.zeros((count, self.n_gates, r.K, r.N), np.uint64) if out_cts else None
-        keep = np.zeros(1, np.uint64)   # a valid pointer for an empty array
-        p = lambda a: None if a is None else (a if a.size else keep).ctypes.data
-        rc = lib().vpbs_program_run_batch(self.h, r.h, p(x), count, p(ko), p(tv), p(wires), p(cts), p(out), 0)
+        p = _keep_ptr
+        rc = lib().vpbs_program_run_batch(self.h, r.h, p(x), count, _keep_u32(ko), p(tv), p(wires), p(cts), p(out), 0)
         if rc < 0:
             raise self._batch_fail(r, rc)
         return wires, cts, out
@@ -3112,11 +3116,47 @@ class Program:
             raise VpbsError("Program.run_batch_device: no ring (None, or a closed KeyRing)")
         ko = keyring_key_of(key_of, instances, ring.max_keys)
         q = lambda x: C.c_void_p(int(x)) if x else None
-        rc = lib().vpbs_program_run_batch(self.h, ring.h, q(d_inputs), instances, (ko if ko.size else np.zeros(1, np.uint32)).ctypes.data,
-                                          q(d_testvs), q(d_wires), q(d_gate_cts), q(d_out_cts), 1)
+        rc = lib().vpbs_program_run_batch(self.h, ring.h, q(d_inputs), instances, _keep_u32(ko), q(d_testvs), q(d_wires), q(d_gate_cts), q(d_out_cts), 1)
         if rc < 0:
             raise self._batch_fail(ring, rc)
         return rc
+
+    @staticmethod
+    def _gate_proof_fn(on_proof, raised, proofs=None, failures=None, index=int):
+        """the PBS_PROOF_FN of a proving call: proof i into proofs[i] and a failing row into failures (where kept), on_proof(index(i), bytes)
+        until a callback raises -- the exception goes into `raised`, never through the C frames"""
+        def trampoline(_user, i, data, n, error):
+            try:
+                if not data:
+                    if failures is not None:
+                        failures.append((int(i), (error or b"").decode()))
+                    return
+                if proofs is None and on_proof is None:
+                    return
+                blob = C.string_at(data, n)
+                if proofs is not None:
+                    proofs[i] = blob
+                if on_proof is not None and not raised:
+                    on_proof(index(int(i)), blob)
+            except BaseException as e:   # noqa: BLE001 -- must not unwind through the C frames
+                raised.append(e)
+        return PBS_PROOF_FN(trampoline)
+
+    @staticmethod
+    def _proving_done(name, prover, n, err, raised, failed=None):
+        """after a proving call: the callback's exception, the checkpoint callback's, a negative status (VpbsError with .status), failing
+        rows (failed = (failures, proofs, out_cts, wires) -> PbsProveError)"""
+        if raised:
+            raise raised[0]
+        e, prover._ckpt_error = prover._ckpt_error, None
+        if e is not None:
+            raise e
+        if n < 0:
+            e = VpbsError("%s: status %d: %s" % (name, n, err.value.decode()))
+            e.status = n
+            raise e
+        if failed is not None and failed[0]:
+            raise PbsProveError(dict(failed[0]), *failed[1:])
 
     def prove(self, pbs_prover, inputs, testvs, steps=0, on_proof=None):
         """-> (proofs: list of bytes in the caller's gate order, wires, out_cts).  Proof g is PbsProver.prove(gate_cts[g], testvs[lut_g])[0];
@@ -3125,30 +3165,9 @@ class Program:
         x, tv = self._host_args("prove", pp.n_lwe, pp.N, inputs, testvs)
         wires, out = np.zeros((self.n_wires, pp.n_lwe + 1), np.uint64), np.zeros((self.n_gates, pp.K, pp.N), np.uint64)
         proofs, failures, raised = [None] * self.n_gates, [], []
-
-        def trampoline(_user, index, data, n, error):
-            try:
-                if not data:
-                    failures.append((int(index), (error or b"").decode()))
-                    return
-                proofs[index] = C.string_at(data, n)
-                if on_proof is not None and not raised:
-                    on_proof(int(index), proofs[index])
-            except BaseException as e:   # noqa: BLE001 -- must not unwind through the C frames
-                raised.append(e)
-        cb, err = PBS_PROOF_FN(trampoline), C.create_string_buffer(512)
-        keep = np.zeros(1, np.uint64)
-        p = lambda a: _ptr(a if a.size else keep)
-        n = lib().vpbs_program_prove(self.h, pp.h, p(x.reshape(-1)), p(tv.reshape(-1)), steps, p(wires.reshape(-1)), p(out.reshape(-1)), cb, None, err, 512)
-        if raised:
-            raise raised[0]
-        e, pp._ckpt_error = pp._ckpt_error, None
-        if e is not None:
-            raise e
-        if n < 0:
-            raise VpbsError("vpbs_program_prove: status %d: %s" % (n, err.value.decode()))
-        if failures:
-            raise PbsProveError(dict(failures), proofs, out, wires)
+        cb, err, p = self._gate_proof_fn(on_proof, raised, proofs, failures), C.create_string_buffer(512), _keep_ptr
+        n = lib().vpbs_program_prove(self.h, pp.h, p(x), p(tv), steps, p(wires), p(out), cb, None, err, 512)
+        self._proving_done("vpbs_program_prove", pp, n, err, raised, (failures, proofs, out, wires))
         return proofs, wires, out
 
     def prove_batch(self, ring_prover, inputs, key_of, testvs, steps=0, on_proof=None):
@@ -3167,34 +3186,22 @@ class Program:
         B, G = x.shape[0], self.n_gates
         wires, out = np.zeros((B, self.n_wires, rp.n_lwe + 1), np.uint64), np.zeros((B, G, rp.K, rp.N), np.uint64)
         flat, failures, raised = [None] * (B * G), [], []
-
-        def trampoline(_user, index, data, n, error):
-            try:
-                if not data:
-                    failures.append((int(index), (error or b"").decode()))
-                    return
-                flat[index] = C.string_at(data, n)
-                if on_proof is not None and not raised:
-                    on_proof(divmod(int(index), G), flat[index])
-            except BaseException as e:   # noqa: BLE001 -- must not unwind through the C frames
-                raised.append(e)
-        cb, err = PBS_PROOF_FN(trampoline), C.create_string_buffer(512)
-        keep = np.zeros(1, np.uint64)
-        p = lambda a: _ptr(a if a.size else keep)
-        n = lib().vpbs_program_prove_batch(self.h, rp.h, p(x.reshape(-1)), B, (ko if ko.size else np.zeros(1, np.uint32)).ctypes.data, p(tv.reshape(-1)),
-                                           steps, p(wires.reshape(-1)), p(out.reshape(-1)), cb, None, err, 512)
-        if raised:
-            raise raised[0]
-        e, rp._ckpt_error = rp._ckpt_error, None
-        if e is not None:
-            raise e
-        if n < 0:
-            e = VpbsError("vpbs_program_prove_batch: status %d: %s" % (n, err.value.decode()))
-            e.status = n
-            raise e
-        if failures:
-            raise PbsProveError(dict(failures), flat, out, wires)
+        cb = self._gate_proof_fn(on_proof, raised, flat, failures, index=lambda i: divmod(i, G))
+        err, p = C.create_string_buffer(512), _keep_ptr
+        n = lib().vpbs_program_prove_batch(self.h, rp.h, p(x), B, _keep_u32(ko), p(tv), steps, p(wires), p(out), cb, None, err, 512)
+        self._proving_done("vpbs_program_prove_batch", rp, n, err, raised, (failures, flat, out, wires))
         return [flat[b * G:(b + 1) * G] for b in range(B)], wires, out
+
+    @staticmethod
+    def _packed(blobs, shape, outputs):
+        """the proofs of a verifying call in one buffer -> (bytes pointer, offsets pointer, `outputs` np.uint8 arrays of `shape` for the
+        verdicts and reasons, their pointers)"""
+        buf, offs = pack_proofs(blobs)
+        buf, offs = np.ascontiguousarray(buf, dtype=np.uint8), np.ascontiguousarray(offs, dtype=np.uint64)
+        u8p = C.POINTER(C.c_uint8)
+        data = buf.ctypes.data_as(u8p) if buf.size else (C.c_uint8 * 1)()
+        outs = tuple(np.zeros(shape, np.uint8) for _ in range(outputs))
+        return data, offs.ctypes.data_as(C.POINTER(C.c_size_t)), outs, [o.ctypes.data_as(u8p) for o in outs]
 
     def verify(self, pbs_verifier, inputs, testvs, out_cts, proofs):
         """out_cts [n_gates][K][N]: the claimed output GLWEs; proofs: list of bytes in gate order -> (verdicts, reasons, proof_reasons),
@@ -3204,18 +3211,12 @@ class Program:
         o = _u64(out_cts).reshape(-1)
         if o.size != self.n_gates * v.K * v.N or len(proofs) != self.n_gates:
             raise ValueError("Program.verify: expected out_cts [%d][K][N] and %d proofs" % (self.n_gates, self.n_gates))
-        buf, offs = pack_proofs(proofs)
-        buf, offs = np.ascontiguousarray(buf, dtype=np.uint8), np.ascontiguousarray(offs, dtype=np.uint64)
-        verdicts, reasons, sub = (np.zeros(self.n_gates, np.uint8) for _ in range(3))
-        u8p = C.POINTER(C.c_uint8)
-        data = buf.ctypes.data_as(u8p) if buf.size else (C.c_uint8 * 1)()
-        keep = np.zeros(1, np.uint64)
-        p = lambda a: _ptr(a if a.size else keep)
-        rc = lib().vpbs_program_verify(self.h, v.h, p(x.reshape(-1)), p(tv.reshape(-1)), p(o), data, offs.ctypes.data_as(C.POINTER(C.c_size_t)),
-                                       verdicts.ctypes.data_as(u8p), reasons.ctypes.data_as(u8p), sub.ctypes.data_as(u8p))
+        data, offs, results, ptrs = self._packed(proofs, self.n_gates, 3)
+        p = _keep_ptr
+        rc = lib().vpbs_program_verify(self.h, v.h, p(x), p(tv), p(o), data, offs, *ptrs)
         if rc < 0:
             raise VpbsError("vpbs_program_verify: status %d: %s" % (rc, lib().vpbs_last_error(v.ctx.h).decode()))
-        return verdicts, reasons, sub
+        return results
 
     def verify_batch(self, ring_verifier, inputs, key_of, testvs, out_cts, proofs):
         """verify for many instances on ONE RingVerifier: inputs [instances][n_inputs][n + 1], key_of [instances] slots, testvs [n_luts][N],
@@ -3232,21 +3233,14 @@ class Program:
         o = _u64(out_cts).reshape(-1)
         if o.size != B * G * rv.K * rv.N or len(proofs) != B or any(len(row) != G for row in proofs):
             raise ValueError("Program.verify_batch: expected out_cts [%d][%d][K][N] and proofs [%d][%d]" % (B, G, B, G))
-        buf, offs = pack_proofs([blob for row in proofs for blob in row])
-        buf, offs = np.ascontiguousarray(buf, dtype=np.uint8), np.ascontiguousarray(offs, dtype=np.uint64)
-        verdicts, reasons, sub = (np.zeros((B, G), np.uint8) for _ in range(3))
-        u8p = C.POINTER(C.c_uint8)
-        data = buf.ctypes.data_as(u8p) if buf.size else (C.c_uint8 * 1)()
-        keep, err = np.zeros(1, np.uint64), C.create_string_buffer(512)
-        p = lambda a: _ptr(a if a.size else keep)
-        rc = lib().vpbs_program_verify_batch(self.h, rv.h, p(x.reshape(-1)), B, (ko if ko.size else np.zeros(1, np.uint32)).ctypes.data, p(tv.reshape(-1)),
-                                             p(o), data, offs.ctypes.data_as(C.POINTER(C.c_size_t)), verdicts.ctypes.data_as(u8p),
-                                             reasons.ctypes.data_as(u8p), sub.ctypes.data_as(u8p), err, 512)
+        data, offs, results, ptrs = self._packed([blob for row in proofs for blob in row], (B, G), 3)
+        err, p = C.create_string_buffer(512), _keep_ptr
+        rc = lib().vpbs_program_verify_batch(self.h, rv.h, p(x), B, _keep_u32(ko), p(tv), p(o), data, offs, *ptrs, err, 512)
         if rc < 0:
             e = VpbsError("vpbs_program_verify_batch: status %d: %s" % (rc, err.value.decode()))
             e.status = rc
             raise e
-        return verdicts, reasons, sub
+        return results
 
     def prove_aggregate(self, pbs_prover, aggregator, inputs, testvs, on_proof=None):
         """ONE proof for the program instance: prove(), then Aggregator.aggregate over the gate proofs in gate order -> (blob, wires,
@@ -3256,26 +3250,11 @@ class Program:
         x, tv = self._host_args("prove_aggregate", pp.n_lwe, pp.N, inputs, testvs)
         wires, out = np.zeros((self.n_wires, pp.n_lwe + 1), np.uint64), np.zeros((self.n_gates, pp.K, pp.N), np.uint64)
         raised = []
-
-        def trampoline(_user, index, data, n, error):
-            try:
-                if data and on_proof is not None and not raised:
-                    on_proof(int(index), C.string_at(data, n))
-            except BaseException as e:   # noqa: BLE001 -- must not unwind through the C frames
-                raised.append(e)
-        cb, err = PBS_PROOF_FN(trampoline), C.create_string_buffer(512)
+        cb, err, p = self._gate_proof_fn(on_proof, raised), C.create_string_buffer(512), _keep_ptr
         blob = np.zeros(aggregator.max_bytes, np.uint8)
-        n = lib().vpbs_program_prove_aggregate(self.h, pp.h, aggregator.h, _keep_ptr(x.reshape(-1)), _keep_ptr(tv.reshape(-1)), _ptr(wires.reshape(-1)),
-                                               _ptr(out.reshape(-1)), blob.ctypes.data_as(C.POINTER(C.c_uint8)), blob.size, None, cb, None, err, 512)
-        if raised:
-            raise raised[0]
-        e, pp._ckpt_error = pp._ckpt_error, None
-        if e is not None:
-            raise e
-        if n < 0:
-            e = VpbsError("vpbs_program_prove_aggregate: status %d: %s" % (n, err.value.decode()))
-            e.status = n
-            raise e
+        n = lib().vpbs_program_prove_aggregate(self.h, pp.h, aggregator.h, p(x), p(tv), p(wires), p(out), blob.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                               blob.size, None, cb, None, err, 512)
+        self._proving_done("vpbs_program_prove_aggregate", pp, n, err, raised)
         return blob[:n].tobytes(), wires, out
 
     def prove_aggregate_batch(self, ring_prover, aggregator, inputs, key_of, testvs, on_aggregate=None):
@@ -3300,19 +3279,9 @@ class Program:
                     on_aggregate(int(instance), blobs[instance])
             except BaseException as e:   # noqa: BLE001 -- must not unwind through the C frames
                 raised.append(e)
-        cb, none, err = AGGREGATE_FN(trampoline), PBS_PROOF_FN(), C.create_string_buffer(512)
-        n = lib().vpbs_program_prove_aggregate_batch(self.h, rp.h, aggregator.h, _keep_ptr(x.reshape(-1)), B,
-                                                     (ko if ko.size else np.zeros(1, np.uint32)).ctypes.data, _keep_ptr(tv.reshape(-1)),
-                                                     _keep_ptr(wires.reshape(-1)), _keep_ptr(out.reshape(-1)), cb, none, None, err, 512)
-        if raised:
-            raise raised[0]
-        e, rp._ckpt_error = rp._ckpt_error, None
-        if e is not None:
-            raise e
-        if n < 0:
-            e = VpbsError("vpbs_program_prove_aggregate_batch: status %d: %s" % (n, err.value.decode()))
-            e.status = n
-            raise e
+        cb, none, err, p = AGGREGATE_FN(trampoline), PBS_PROOF_FN(), C.create_string_buffer(512), _keep_ptr
+        n = lib().vpbs_program_prove_aggregate_batch(self.h, rp.h, aggregator.h, p(x), B, _keep_u32(ko), p(tv), p(wires), p(out), cb, none, None, err, 512)
+        self._proving_done("vpbs_program_prove_aggregate_batch", rp, n, err, raised)
         return blobs, wires, out
 
     def verify_aggregate_batch(self, agg_verifier, inputs, key_of, key_hashes, testvs, out_cts, blobs):
@@ -3337,20 +3306,14 @@ class Program:
                                             instances=B)
         if len(blobs) != B:
             raise ValueError("Program.verify_aggregate_batch: %d blobs for %d instances" % (len(blobs), B))
-        buf, offs = pack_proofs(blobs)
-        buf, offs = np.ascontiguousarray(buf, dtype=np.uint8), np.ascontiguousarray(offs, dtype=np.uint64)
-        u8p = C.POINTER(C.c_uint8)
-        data = buf.ctypes.data_as(u8p) if buf.size else (C.c_uint8 * 1)()
-        verdicts, reasons, err = np.zeros(B, np.uint8), np.zeros(B, np.uint8), C.create_string_buffer(512)
-        rc = lib().vpbs_program_verify_aggregate_batch(self.h, av.h, _keep_ptr(x.reshape(-1)), B, (ko if ko.size else np.zeros(1, np.uint32)).ctypes.data,
-                                                       _ptr(kh.reshape(-1)), kh.shape[0], _keep_ptr(tv.reshape(-1)), _keep_ptr(o.reshape(-1)), data,
-                                                       offs.ctypes.data_as(C.POINTER(C.c_size_t)), verdicts.ctypes.data_as(u8p),
-                                                       reasons.ctypes.data_as(u8p), err, 512)
+        data, offs, results, ptrs = self._packed(blobs, B, 2)
+        err, p = C.create_string_buffer(512), _keep_ptr
+        rc = lib().vpbs_program_verify_aggregate_batch(self.h, av.h, p(x), B, _keep_u32(ko), p(kh), kh.shape[0], p(tv), p(o), data, offs, *ptrs, err, 512)
         if rc < 0:
             e = VpbsError("vpbs_program_verify_aggregate_batch: status %d: %s" % (rc, err.value.decode()))
             e.status = rc
             raise e
-        return verdicts, reasons
+        return results
 
     def close(self):
         if self.h:

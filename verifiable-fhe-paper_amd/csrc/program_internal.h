@@ -1,9 +1,10 @@
 // The seam between the program object (program.hip) and the five objects it drives: the Bootstrapper (pbs_batch.hip), the key ring
 // (pbs_keyring.hip), the batch provers (pbs_prove_batch.hip, pbs_prove_ring.hip: two key sources of one worker pool, pbs_prove_pool.h, which
 // holds the run both share) and the batch verifiers of whole vPBS proofs, one key set or a
-// ring of key hashes (verify_pbs_batch.hip).  A program queues one bootstrap launch per
-// level behind its own combine kernel and waits once, at the end: it needs the Bootstrapper's launch WITHOUT the wait vpbs_bootstrapper_run
-// ends with, and the shapes of objects whose structs are private to their files.  Library-internal, like ivc_resident.h.
+// ring of key hashes (verify_pbs_batch.hip).  A program's ONE level walk queues one bootstrap launch per
+// level behind its own combine kernel and waits once, at the end: it needs the launch of the Bootstrapper or of the key ring WITHOUT the
+// wait their run ends with, and the shapes of objects whose structs are private to their files.  Its ONE proof check hands rows in
+// device memory to the core that both statement verifiers hold, with the verifier's own key table.  Library-internal, like ivc_resident.h.
 // The chain that the Bootstrapper's and the ring's kernels walk is one device function, pb_chain (pbs_chain.h); what the two objects share on
 // the host -- shape, staging, thread rule, launch ladder, the run behind vpbs_*_run -- is pbs_chain_host.h.  The two enqueue functions below
 // fill the object's own argument struct and go through that ladder.
@@ -106,7 +107,7 @@ struct PbsVerifierShape {
 };
 void pbs_verifier_shape(const vpbs_pbs_verifier* v, PbsVerifierShape* out);
 
-// ---- the core of both statement verifiers (verify_pbs_batch.hip), for vpbs_program_verify_batch ----
+// ---- the core of both statement verifiers (verify_pbs_batch.hip), for vpbs_program_verify and vpbs_program_verify_batch ----
 // Everything vpbs_pbs_verifier_run queues, on DEVICE pointers: ct [count][n_lwe + 1], out_ct [count][K N], a table of test vectors
 // testvs [..][N] with testv_of [count], a table of key hashes [..][4] with key_of [count] -- proof i is checked against testvs[testv_of[i]]
 // and key_hashes[key_of[i]]; digest and cap are the core's.  Queues the upload of the proof bytes (host memory), vp_lwe_chain (on the core's
@@ -122,6 +123,9 @@ int pbs_verify_enqueue(PbsVerifyCore* c, const uint8_t* bytes, const size_t* off
 long pbs_verify_collect(PbsVerifyCore* c, size_t count, uint8_t* verdicts, uint8_t* reasons, uint8_t* proof_reasons);
 // after a DeviceError of either: the message into the context, the chain stream drained
 void pbs_verify_abandon(PbsVerifyCore* c, const DeviceError& e);
+// the core of a vpbs_pbs_verifier and its key table of one entry (device memory, [1][4]), for vpbs_program_verify
+PbsVerifyCore* pbs_verifier_core(vpbs_pbs_verifier* v);
+const uint64_t* pbs_verifier_key_table(const vpbs_pbs_verifier* v);
 
 // vp_lwe_chain alone, queued on `stream` (a hipStream_t), for the aggregate verifier (aggregate.hip): the ends [count][4] of the LWE hash
 // chains of d_ct [count][n_lwe + 1], one 16-lane group per ciphertext.  Throws vpbs::DeviceError for a failed launch.

@@ -355,6 +355,8 @@ void ring_verifier_shape(const vpbs_ring_verifier* v, RingVerifierShape* out) {
     const PbsShape& P = v->core.P;
     *out = RingVerifierShape{v->core.ctx, P.N, P.kn / P.N, P.n_lwe, v->max_keys, v->core.max_batch};
 }
+PbsVerifyCore* pbs_verifier_core(vpbs_pbs_verifier* v) { return &v->core; }
+const uint64_t* pbs_verifier_key_table(const vpbs_pbs_verifier* v) { return v->d_key; }
 std::mutex& ring_verifier_mutex(vpbs_ring_verifier* v) { return v->mu; }
 PbsVerifyCore* ring_verifier_core(vpbs_ring_verifier* v) { return &v->core; }
 const uint64_t* ring_verifier_key_table(const vpbs_ring_verifier* v) { return v->d_keys; }
