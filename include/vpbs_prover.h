@@ -1496,12 +1496,14 @@ int vpbs_aggregate_level_jobs(const size_t* counts, size_t n_trees, unsigned lev
 typedef void (*vpbs_aggregate_tree_fn)(void* user, size_t tree, const uint8_t* proof, size_t len);
 long vpbs_aggregator_run_many(vpbs_aggregator* a, const uint8_t* bytes, const size_t* offsets /* [sum of counts + 1] */, const size_t* counts,
                               size_t n_trees, vpbs_aggregate_tree_fn fn, void* user, char* err, size_t err_len);
-/* vpbs_verify_aggregate on the device: the leaf statements (one 16-lane group per leaf absorbs the n_pi words as it generates them from
- * the statement's parts -- the public-input vector is never materialised), the LWE chains, the fold (one launch per level), the root proof
- * through the batch verifier's stages with a batch of one, and a one-lane kernel that orders the reasons as the host does.  The word arrays
- * (testvs, cts, out_cts, key_hashes) are device pointers when on_device != 0; testv_of and key_of are HOST arrays in every mode and are
- * checked before anything is queued; count, n_testv and n_keys are at most max_leaves.  run returns 1 = accepted, 0 = rejected, < 0 =
- * malformed arguments or a device failure (err); *reason (may be NULL) is the host's.  One run at a time per object. */
+/* vpbs_verify_aggregate on the device.  run and root are run_many and roots_many (below) with ONE tree that owns all `count` leaves, behind
+ * their own refusals: the same stages -- the leaf-pair launch over the leaves (per leaf one wave of two 16-lane groups: the LWE chain beside
+ * the sponge over the n_pi public inputs, which are generated from the statement's parts and never materialised), one fold launch per level,
+ * the root proof through the batch verifier's stages with a batch of one, and the result kernel, which orders the reasons as the host does --
+ * and one wait.  The word arrays (testvs, cts, out_cts, key_hashes) are device pointers when on_device != 0; testv_of and key_of are HOST
+ * arrays in every mode and are checked before anything is queued; count, n_testv and n_keys are at most max_leaves.  run returns 1 =
+ * accepted, 0 = rejected, < 0 = malformed arguments or a device failure (err); *reason (may be NULL) is the host's.  One run at a time per
+ * object. */
 typedef struct vpbs_aggregate_verifier vpbs_aggregate_verifier;
 int vpbs_aggregate_verifier_create(vpbs_ctx* ctx, const vpbs_aggregate_shape* shape, size_t max_leaves, vpbs_aggregate_verifier** out, char* err,
                                    size_t err_len);
@@ -1513,11 +1515,11 @@ int vpbs_aggregate_verifier_root(vpbs_aggregate_verifier* v, size_t count, const
                                  const uint64_t* cts, const uint64_t* out_cts, const uint64_t* key_hashes, size_t n_keys, const uint32_t* key_of,
                                  int on_device, uint64_t out[4], char* err, size_t err_len);
 void vpbs_aggregate_verifier_free(vpbs_aggregate_verifier* v);
-/* MANY aggregates in one device run.  A run of vpbs_aggregate_verifier_run is one latency-bound chain of n_lwe + 2 links
- * and then ceil((2 K N + 77) / 8) sponge blocks on a 16-lane group, whatever the leaf count: the chain depends on neither the number of
- * leaves nor the number of trees, so many aggregates fit in the time of one.
+/* MANY aggregates in one device run.  The statement of a leaf is one latency-bound chain: n_lwe + 2 links beside the sponge
+ * blocks that need no LWE hash, then the at most ten blocks left, on one wave, whatever the leaf count: the chain depends on neither the
+ * number of leaves nor the number of trees, so many aggregates fit in the time of one.
  * create_many: vpbs_aggregate_verifier_create whose per-level proof verifiers take batches of max_aggregates (1 .. 2^16); create is the
- *   case max_aggregates = 1, and run / root work on such an object as before.
+ *   case max_aggregates = 1, and run / root work on every such object.
  * run_many: aggregate a is bytes[offsets[a] .. offsets[a + 1]) and its tree owns the leaves leaf_first[a] .. leaf_first[a + 1] of the per-leaf
  *   arrays (leaf_first [n_agg + 1], a HOST array, starts at 0 and increases); testv_of and key_of are per leaf and HOST arrays, the word arrays
  *   device pointers when on_device != 0, as in run.  Aggregate a gets in verdicts[a] / reasons[a] (reasons may be NULL) exactly the verdict

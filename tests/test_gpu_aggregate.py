@@ -210,6 +210,39 @@ def test_the_device_root_alone(world):
         W.av.root(testvs, cts, out_cts, key_hashes, [0, 4, 0, 0, 0], testv_of)
 
 
+def bound_statement(count):
+    """a random statement of `count` leaves, seeded by count alone (no proofs): min(count, 3) test vectors and min(count, 4) key hashes,
+    so that n_testv and n_keys fit a verifier of max_leaves = count, with repeats and out of order"""
+    rng = np.random.default_rng(100 + count)
+    f = lambda *shape: rng.integers(0, P, size=shape, dtype=np.uint64)
+    n_tv, n_kh = min(count, 3), min(count, 4)
+    return (f(n_tv, N), f(count, N_LWE + 1), f(count, KN), f(n_kh, 4), rng.integers(0, n_kh, size=count), rng.integers(0, n_tv, size=count))
+
+
+@pytest.mark.parametrize("max_leaves, count", [(8, 6), (8, 7), (8, 8), (5, 5), (1, 1)])
+def test_the_single_root_at_the_bounds_of_the_run_buffers(world, max_leaves, count):
+    """AggregateVerifier.root runs the statement of many trees with one tree; its level buffers hold max_leaves entries and its index tables
+    5 max_leaves + (4 levels + 1) max_aggregates words.  Against api.aggregate_root under the verifier's vk_0, max_aggregates = 1: counts 6
+    (level 1 stands on the leaf pairs (4, 5) and (5, 5)), 7 and 8 (a full tree at exactly max_leaves) under max_leaves = 8; count 5 under
+    max_leaves = 5 (no power of two: 4 level-1 nodes in a buffer of 5); count 1 under max_leaves = 1 (the leaf folded with itself, a verifier
+    of one level).  And a raw out_cts word equal to p in a full tree is refused as the host refuses it."""
+    W = world
+    av = W.av if max_leaves == 8 else api.AggregateVerifier(W.ctx, W.shape, max_leaves=max_leaves)
+    try:
+        assert (av.max_leaves, av.max_aggregates) == (max_leaves, 1)
+        st = bound_statement(count)
+        assert (av.root(*st) == api.aggregate_root(N, K, N_LWE, W.vk0, *st)).all()
+        if count == 8:
+            bad = (st[0], st[1], with_word(st[2], (7, KN - 1), P), *st[3:])
+            with pytest.raises(api.VpbsError, match="not a field element"):
+                api.aggregate_root(N, K, N_LWE, W.vk0, *bad)
+            with pytest.raises(api.VpbsError, match="not a field element"):
+                av.root(*bad)
+    finally:
+        if av is not W.av:
+            av.close()
+
+
 def with_word(a, at, value):
     a = np.array(a, np.uint64).copy()
     a[at] = np.uint64(value)

@@ -1,14 +1,15 @@
 #!/usr/bin/env python3
 """The statement side of an aggregate alone: the root over G leaf statements on the host (api.aggregate_root, up to 16
-threads) against the device (api.AggregateVerifier.root: vp_lwe_chain, ag_leaf, ag_fold), random statements, no proofs.  One JSON line.
+threads) against the device (api.AggregateVerifier.root: ag_leaf_pair, ag_fold_many), random statements, no proofs.  One JSON line.
 
 usage: tools/aggregate_root_speed.py [--n8] [--leaves 64,256,1024] [--runs 5]
        tools/aggregate_root_speed.py --many 1,8,64 [--tree-leaves 8,64] [--runs 5] [--n8] [--shape-circuits-n8]
   the level circuits give the verifier its shape only and are located as data (tools/export_circuits.py --aggregate ... levels makes them)
   --many T[,T2,..]: MANY trees in one run.  For every T and every L of --tree-leaves: T trees of L leaves, random statements;
-    api.AggregateVerifier.roots_many (one run) against T calls of AggregateVerifier.root (the single run) and against api.aggregate_root per
-    tree on up to 16 host threads -- the three legs in turn, median and range of --runs after a warm-up -- and, from the library's HIP-event
-    timers, the leaf-pair kernel against vp_lwe_chain + ag_leaf for the same leaves (one run of each with timing on).
+    api.AggregateVerifier.roots_many (one run) against T calls of AggregateVerifier.root (the same stages with one tree per call: what T
+    runs cost, and with T = 1 what the single entry's wrapper costs) and against api.aggregate_root per tree on up to 16 host threads -- the
+    three legs in turn, median and range of --runs after a warm-up -- and, from the library's HIP-event timers, the leaf-pair kernel of
+    the one run (--runs runs with timing on).
   --shape-circuits-n8: size the proof verifiers by the level circuits of the N = 8, n = 6 set (no proof is read by this tool; a level beyond
     the exported ones reuses the last one's shape) while the statement keeps the paper's parameters."""
 import argparse
@@ -67,22 +68,16 @@ def many(args, N, n_lwe, log_n):
                     t = time.perf_counter()
                     list(pool.map(host_root, range(T)))
                     ms["host"].append(1e3 * (time.perf_counter() - t))
-                # the kernels, by the library's HIP-event timers: `runs` runs of each form with timing on
+                # the leaf kernel, by the library's HIP-event timers: `runs` runs with timing on
                 ctx.timing_enable(1)
-                pair, two = [], []
+                pair = []
                 for _ in range(args.runs):
                     ctx.timing_report()
                     av.roots_many([L] * T, *st)
-                    rep = ctx.timing_report()
-                    pair.append(rep.get("ag_leaf_pair", {}).get("ms", 0.0))
-                    for a in range(T):
-                        av.root(*one(a))
-                    rep = ctx.timing_report()
-                    two.append(rep.get("vp_lwe_chain", {}).get("ms", 0.0) + rep.get("ag_leaf", {}).get("ms", 0.0))
+                    pair.append(ctx.timing_report().get("ag_leaf_pair", {}).get("ms", 0.0))
                 ctx.timing_enable(0)
                 rows.append({"trees": T, "leaves_per_tree": L, "roots_many_ms": spread(ms["many"]), "single_runs_ms": spread(ms["single"]),
-                             "host_16_threads_ms": spread(ms["host"]), "ag_leaf_pair_event_ms": spread(pair),
-                             "vp_lwe_chain_plus_ag_leaf_event_ms": spread(two), "single_launches": 2 * T})
+                             "host_16_threads_ms": spread(ms["host"]), "ag_leaf_pair_event_ms": spread(pair)})
     av.close()
     ctx.close()
     print(json.dumps({"what": "roots of T trees of L leaves: one many-run against T single device runs and against the host on up to 16 threads, "

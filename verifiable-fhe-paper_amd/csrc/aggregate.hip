@@ -1,12 +1,14 @@
 // Aggregation of the vPBS proofs of a batch into ONE proof (include/vpbs_prover.h).
 //   statement  : leaf i = hash_no_pad of the public inputs its vPBS proof must carry; a binary tree of hash_no_pad(left || right) over the
-//                leaves, padded to 2^d with the last leaf (vpbs_aggregate_root on the host; ag_leaf + ag_fold on the device)
+//                leaves, padded to 2^d with the last leaf (vpbs_aggregate_root on the host; ag_leaf_pair + ag_fold_many on the device)
 //   prover     : vpbs_aggregator -- the level circuits A_1 .. A_levels arrive as data; every leaf is verified before anything is proven;
-//                then level by level witness plan (host) -> upload -> vpbs_prove_step, the next node's witness on a second thread
+//                then level by level witness plan (host) -> upload -> vpbs_prove_step, the next node's witness on a second thread.
+//                vpbs_aggregator_run is vpbs_aggregator_run_many with one tree: one run body, one proof per node in prove_node
 //   verifiers  : vpbs_verify_aggregate (host) and vpbs_aggregate_verifier (device): parse at level d's shape, the vk list, the proof, the root
-//   many-run   : vpbs_aggregate_verifier_run_many / _roots_many -- many trees in ONE run: ag_leaf_pair over all leaves (the
-//                LWE chain and the public-input sponge of a leaf side by side in one wave), ag_fold_many per level over the trees that have
-//                it, per depth ONE batch of root proofs and ag_result_many; the single-run entry points and their kernels are unchanged
+//   device statement : ONE, for many trees in one run: ag_leaf_pair over all leaves (the LWE chain and the public-input
+//                sponge of a leaf side by side in one wave), ag_fold_many per level over the trees that have it, per depth ONE batch of root
+//                proofs and ag_result_many, one lane per aggregate.  vpbs_aggregate_verifier_run / _root are _run_many / _roots_many with
+//                one tree, behind their own refusals
 //   device witness : vpbs_aggregator_set_device_witness -- the distinct nodes of a level (of ALL trees of a run_many) in
 //                chunks: child proofs uploaded once each, ag_presets_kernel, the level's full plan on a vpbs_witness_device, per node gather + proof
 // The prover part is host code against the library's own C ABI, as ivc.hip is.
@@ -46,6 +48,18 @@ unsigned depth_of(size_t count) {   // max(1, ceil(log2 count))
     unsigned d = 1;
     while (((size_t)1 << d) < count) ++d;
     return d;
+}
+
+// work(t, threads) for every t < threads = min(HOST_THREADS, the hardware's, most), each on a host thread of its own: worker t takes the
+// items t, t + threads, ..
+template <class Work>
+void strided(size_t most, Work work) {
+    const unsigned hw = std::max(1u, std::min(HOST_THREADS, std::thread::hardware_concurrency()));
+    const unsigned threads = (unsigned)std::min<size_t>(hw, most);
+    if (threads <= 1) return work(0u, 1u);
+    std::vector<std::thread> pool;
+    for (unsigned t = 0; t < threads; ++t) pool.emplace_back(work, t, threads);
+    for (auto& t : pool) t.join();
 }
 
 // ================= which nodes a level has (host only) =================
@@ -144,19 +158,10 @@ bool root_host(const Statement& s, u64 out[4]) {
     const unsigned d = depth_of(count);
     std::vector<u64> level(4 * ((size_t)1 << d));
     std::vector<uint8_t> ok(count, 1);
-    const unsigned hw = std::max(1u, std::min(HOST_THREADS, std::thread::hardware_concurrency()));
-    const unsigned threads = (unsigned)std::min<size_t>(hw, (count + 3) / 4);
-    auto work = [&](unsigned t) {
+    strided((count + 3) / 4, [&](unsigned t, unsigned threads) {
         std::vector<u64> pis;
         for (size_t i = t; i < count; i += threads) ok[i] = leaf_statement_host(s, i, pis, level.data() + 4 * i) ? 1 : 0;
-    };
-    if (threads <= 1) {
-        work(0);
-    } else {
-        std::vector<std::thread> pool;
-        for (unsigned t = 0; t < threads; ++t) pool.emplace_back(work, t);
-        for (auto& t : pool) t.join();
-    }
+    });
     for (size_t i = 0; i < count; ++i)
         if (!ok[i]) return false;
     for (size_t i = count; i < ((size_t)1 << d); ++i) std::memcpy(level.data() + 4 * i, level.data() + 4 * (count - 1), 32);   // the padding
@@ -190,97 +195,25 @@ size_t openings_words(const vpbs_verify_inputs& c) {
     return 2 * ((size_t)c.n_constants_sigmas + c.n_wires + c.n_zs_partial_products + c.n_quotient + c.num_challenges);
 }
 
-// ================= the statement on the device =================
+// ================= the statement on the device: the trees of a run, one or many =================
 struct AggShape {
     u32 N, kn, n_lwe, n_pi;
 };
 
-// Leaf statements: one leaf per 16-lane block, lane l < 12 owns sponge element l (the permute_wide layout of vp_lwe_chain).  Block b of
-// the sponge overwrites the rate lanes l < 8 with public inputs 8 b + l, generated here from the statement's parts; n_pi = 2 K N + 77 is no
-// multiple of 8, so the last block is partial and its upper rate lanes keep the old state.  A raw word at or above p sets *flag (the
-// leaf's own result is then meaningless: no proof has that statement).  Bounds: testv_of[i] < n_testv, key_of[i] < n_keys (checked on the
-// host), j - 2 kn - 9 < 68.
-__global__ __launch_bounds__(16) void ag_leaf(const u64* __restrict__ testvs, const u32* __restrict__ testv_of, const u64* __restrict__ out_ct,
-                                              const u64* __restrict__ key_hashes, const u32* __restrict__ key_of, const u64* __restrict__ lwe,
-                                              const u64* __restrict__ vk0, AggShape S, u64* __restrict__ stmt, u32* __restrict__ flag) {
-    __shared__ u64 sh[poseidon::WIDE_LDS_WORDS];
-    const unsigned l = threadIdx.x;
-    const u32 i = blockIdx.x;
-    const u64* tv = testvs + (u64)testv_of[i] * S.N;
-    const u64* oc = out_ct + (u64)i * S.kn;
-    const u64* kh = key_hashes + (u64)key_of[i] * 4;
-    const u64* lw = lwe + (u64)i * 4;
-    auto word = [&](u32 j) -> u64 {
-        if (j < S.kn - S.N) return 0;
-        if (j < S.kn) return tv[j - (S.kn - S.N)];
-        if (j == S.kn) return (u64)S.n_lwe + 2;
-        if (j <= 2 * S.kn) return oc[j - S.kn - 1];
-        if (j < 2 * S.kn + 5) return kh[j - 2 * S.kn - 1];
-        if (j < 2 * S.kn + 9) return lw[j - 2 * S.kn - 5];
-        return vk0[j - 2 * S.kn - 9];
-    };
-    const bool rate = l < 8;
-    u64 x = 0;
-    bool bad = false;
-    u64 next = rate && l < S.n_pi ? word(l) : 0;   // block b + 1 is loaded while block b runs: the loads are off the dependent chain
-    for (u32 off = 0; off < S.n_pi; off += 8) {
-        const bool mine = rate && off + l < S.n_pi;
-        const u64 w = next;
-        const u32 jn = off + 8 + l;
-        next = rate && jn < S.n_pi ? word(jn) : 0;
-        if (mine) {
-            bad = bad || w >= gl::P;
-            x = gl::canon(w);
-        }
-        x = poseidon::permute_wide(x, sh, l);
-    }
-    if (l < 4) stmt[(u64)i * 4 + l] = x;
-    if (bad) atomicOr(flag, 1u);
-}
-
-// One level of the tree: node k = hash_no_pad(in[2k] || in[2k + 1]), one permutation of [left, right, 0 0 0 0], one node per 16-lane block.
-// Entries at or past n_in read entry n_in - 1: at the leaves that IS the padding rule (n_in = count); above them n_in is the whole level.
-__global__ __launch_bounds__(16) void ag_fold(const u64* __restrict__ in, u32 n_in, u64* __restrict__ out) {
-    __shared__ u64 sh[poseidon::WIDE_LDS_WORDS];
-    const unsigned l = threadIdx.x;
-    const u32 k = blockIdx.x;
-    const u32 a = min(2 * k, n_in - 1), b = min(2 * k + 1, n_in - 1);
-    u64 x = 0;
-    if (l < 4) x = in[(u64)a * 4 + l];
-    else if (l < 8) x = in[(u64)b * 4 + l - 4];
-    x = poseidon::permute_wide(x, sh, l);
-    if (l < 4) out[(u64)k * 4 + l] = x;
-}
-
-// the first failing check in vpbs_verify_aggregate's order -> out: verdict | reason.  pis: the root proof's public inputs as the batch
-// verifier parsed them (n_expected = 4 + 68 d words are inside its slot whatever the bytes were)
-__global__ void ag_result(const uint8_t* __restrict__ proof_reason, const u32* __restrict__ n_pi, const u64* __restrict__ pis,
-                          const u64* __restrict__ vks, const u64* __restrict__ root, const u32* __restrict__ flag, u32 n_expected,
-                          uint8_t* __restrict__ out) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    const uint8_t pr = proof_reason[0];
-    uint8_t reason = VPBS_AGG_OK;
-    if (pr == VPBS_VERIFY_MALFORMED || n_pi[0] != n_expected) {
-        reason = VPBS_AGG_MALFORMED;
-    } else {
-        bool vk_bad = false, root_bad = *flag != 0;
-        for (u32 j = 4; j < n_expected; ++j) vk_bad = vk_bad || pis[j] != vks[j - 4];
-        for (u32 j = 0; j < 4; ++j) root_bad = root_bad || pis[j] != root[j];
-        reason = vk_bad ? VPBS_AGG_VERIFIER_DATA : pr != VPBS_VERIFY_OK ? VPBS_AGG_PROOF : root_bad ? VPBS_AGG_ROOT : VPBS_AGG_OK;
-    }
-    out[0] = reason == VPBS_AGG_OK ? 1 : 0;
-    out[1] = reason;
-}
-
-// ================= many aggregates in one run =================
-// Leaf pair: ag_leaf o vp_lwe_chain for one leaf in ONE wave of two 16-lane groups, each with its own 48-word LDS window.  Group A (lanes
-// 0 .. 15) walks the LWE chain exactly as vp_lwe_chain; group B (lanes 16 .. 31) absorbs the leaf's public-input blocks exactly as ag_leaf,
-// first the F = (2 K N + 5) div 8 blocks that hold no LWE-hash word.  Both groups call permute_wide in the same iterations -- every lane of the
-// wave must -- and a group with nothing left permutes a value it discards.  After max(n_lwe + 2, F) iterations A leaves its four words in LDS
-// behind a wavefront fence (the LDS operations of a wave execute in order) and B absorbs the remaining blocks, at most ten.  Critical path:
-// max(n_lwe + 2, F) + ceil(n_pi / 8) - F permutations instead of (n_lwe + 2) + ceil(n_pi / 8).  A raw word at or above p sets the flag of
-// the leaf's TREE.  Bounds: blockIdx.x < the leaf count; testv_of[i] < n_testv, key_of[i] < n_keys and tree_of[i] < n_agg are checked on the
-// host; j - 2 kn - 9 < 68.
+// Leaf statements: one leaf per wave of two 16-lane groups, each with its own 48-word LDS window.  In a group lane l < 12 owns sponge
+// element l (the permute_wide layout of vp_lwe_chain) and lanes 12 .. 15 only take part in the permutation.
+//   Group A (lanes 0 .. 15) walks the leaf's LWE chain exactly as vp_lwe_chain: n_lwe + 2 links over [ct[n], ct[0] .. ct[n-1], 0], a link
+//     puts the reduced item in element 4, zero in elements 5 .. 11 and permutes.
+//   Group B (lanes 16 .. 31) is the sponge over the leaf's n_pi = 2 K N + 77 public inputs, generated here from the statement's parts (the
+//     vector is never materialised).  The sponge is in overwrite mode: block b replaces the rate lanes l < 8 by public inputs 8 b + l; n_pi
+//     is no multiple of 8, so the last block is partial and its upper rate lanes keep the old state.  B absorbs first the F = (2 K N + 5)
+//     div 8 blocks that hold no LWE-hash word.
+// Both groups call permute_wide in the same iterations -- every lane of the wave must -- and a group with nothing left permutes a value it
+// discards.  After max(n_lwe + 2, F) iterations A leaves its four words in LDS behind a wavefront fence (the LDS operations of a wave execute
+// in order) and B absorbs the remaining blocks, at most ten.  Critical path: max(n_lwe + 2, F) + ceil(n_pi / 8) - F permutations, where the
+// chain and the sponge one after the other would take (n_lwe + 2) + ceil(n_pi / 8).  A raw word at or above p sets the flag of the leaf's
+// TREE (the leaf's own result is then meaningless: no proof has that statement).  Bounds: blockIdx.x < the leaf count; testv_of[i] <
+// n_testv, key_of[i] < n_keys and tree_of[i] < n_agg are checked on the host; j - 2 kn - 9 < 68.
 __global__ __launch_bounds__(32) void ag_leaf_pair(const u64* __restrict__ testvs, const u32* __restrict__ testv_of, const u64* __restrict__ out_ct,
                                                    const u64* __restrict__ key_hashes, const u32* __restrict__ key_of, const u64* __restrict__ cts,
                                                    const u64* __restrict__ vk0, const u32* __restrict__ tree_of, AggShape S, u64* __restrict__ stmt,
@@ -353,10 +286,12 @@ struct FoldTree {
     u32 in_first, n_in, out_first, root;
 };
 
-// One level of ALL trees that still have that level: ag_fold per node, one node per 16-lane block; node_tree[node] names the node's tree.
-// The padding rule is ag_fold's index clamp by the tree's own n_in, so a one-leaf tree folds its leaf with itself.  The node of a tree's own
-// depth also lands in roots[tree].  Bounds: blockIdx.x < the level's node count, node_tree[..] < n_agg, in_first + n_in within the level below
-// (the host builds the tables from the checked leaf counts).
+// One level of ALL trees that still have that level, one node per 16-lane block: node k of a tree = hash_no_pad(in[2k] || in[2k + 1]), one
+// permutation of [left, right, 0 0 0 0]; node_tree[node] names the node's tree.  A tree's entries at or past its n_in read its entry
+// n_in - 1: at the leaves (n_in = the tree's own count) that index clamp IS the padding rule, so a one-leaf tree folds its leaf with itself;
+// above them n_in is the tree's whole level and nothing is clamped.  The node of a tree's own depth also lands in roots[tree].  Bounds:
+// blockIdx.x < the level's node count, node_tree[..] < n_agg, in_first + n_in within the level below (the host builds the tables from the
+// checked leaf counts).
 __global__ __launch_bounds__(16) void ag_fold_many(const u64* __restrict__ in, const u32* __restrict__ node_tree, const FoldTree* __restrict__ tab,
                                                    u64* __restrict__ out, u64* __restrict__ roots) {
     __shared__ u64 sh[poseidon::WIDE_LDS_WORDS];
@@ -375,8 +310,11 @@ __global__ __launch_bounds__(16) void ag_fold_many(const u64* __restrict__ in, c
     }
 }
 
-// ag_result for the n aggregates of one depth, one lane each: proof i of the depth's batch is aggregate agg_of[i]; its own root, its own
-// tree's flag, n_expected = 4 + 68 d; the same order of checks -> out[2 a] = verdict, out[2 a + 1] = reason
+// The verdicts of the n aggregates of one depth d, one lane each: proof i of the depth's batch is aggregate a = agg_of[i].  The first failing
+// check in vpbs_verify_aggregate's order -- MALFORMED (the batch verifier could not parse the bytes, or they do not carry n_expected = 4 + 68 d
+// public inputs), VERIFIER_DATA (public inputs 4 .. against vks), PROOF (the batch verifier's verdict), ROOT (public inputs 0 .. 3 against
+// the tree's own root, or the tree's raw-word flag) -> out[2 a] = verdict, out[2 a + 1] = reason.  The public inputs are read as the batch
+// verifier parsed them: n_expected words are inside its slot whatever the bytes were (the host checks max_pi).
 __global__ __launch_bounds__(64) void ag_result_many(const uint8_t* __restrict__ proof_reason, const u32* __restrict__ n_pi,
                                                      const u64* __restrict__ words, u32 W, u32 n_fixed, const u64* __restrict__ vks,
                                                      const u64* __restrict__ roots, const u32* __restrict__ flags, const u32* __restrict__ agg_of,
@@ -452,26 +390,25 @@ struct vpbs_aggregate_verifier {
     vpbs_ctx* ctx = nullptr;
     unsigned N = 0, K = 0, n_lwe = 0, levels = 0;
     size_t max_leaves = 0;
-    std::vector<vpbs_proof_verifier*> proofs;   // [levels]: the batch verifier of A_l's proofs, a batch of one
+    size_t max_aggregates = 1;                  // the trees of one run at most (create: 1)
+    std::vector<vpbs_proof_verifier*> proofs;   // [levels]: the batch verifier of A_l's proofs, batches of max_aggregates
     std::vector<void*> owned;
-    u64 *d_vks = nullptr, *d_in = nullptr, *d_lwe = nullptr, *d_stmt = nullptr, *d_nodes[2] = {nullptr, nullptr};
-    u32* d_flag = nullptr;
-    uint8_t* d_out = nullptr;
-    u64* h_in = nullptr;      // pinned: cts | out_cts | testvs | key_hashes | testv_of, key_of
-    u64* h_out = nullptr;     // pinned: root [4] | flag | verdict, reason
-    // many aggregates in one run (create_many): the proof verifiers take batches of max_aggregates
-    size_t max_aggregates = 1;
-    u64 *d_mnodes[2] = {nullptr, nullptr}, *d_roots = nullptr;   // a level of all trees [max_leaves][4], twice; roots [max_aggregates][4]
+    u64 *d_vks = nullptr, *d_in = nullptr, *d_stmt = nullptr;    // vk_0 .. vk_levels; h_in's image; the leaf statements [max_leaves][4]
+    u64* h_in = nullptr;      // pinned: cts | out_cts | testvs | key_hashes
+    // A level of all trees [max_leaves][4], twice; roots [max_aggregates][4].  A level never has more nodes than there are leaves: a tree
+    // of count >= 2 leaves and depth d has 2^(d - 1) < count nodes at level 1 and fewer above, a tree of one leaf has one node.
+    u64 *d_mnodes[2] = {nullptr, nullptr}, *d_roots = nullptr;
     u32 *d_mflags = nullptr, *d_midx = nullptr;                  // raw-word flag per tree; the index tables of a run (many_idx_words)
     uint8_t* d_mout = nullptr;                                   // verdict, reason per aggregate
     u32* h_midx = nullptr;    // pinned: d_midx's image
     u64* h_mout = nullptr;    // pinned: roots [max_aggregates][4] | flags or verdict, reason [max_aggregates]
-    // testv_of, key_of, tree_of per leaf | node_tree of every level (fewer than 2 max_leaves nodes in all) | FoldTree per tree and level |
-    // agg_of per aggregate
+    // testv_of, key_of, tree_of per leaf | node_tree of every level (a tree of count leaves has 2^d - 1 < 2 count nodes over its levels:
+    // fewer than 2 max_leaves in all) | FoldTree per tree and level | agg_of per aggregate
     size_t many_idx_words() const { return 5 * max_leaves + (4 * (size_t)levels + 1) * max_aggregates + 16; }
     std::mutex mu;
     size_t kn() const { return (size_t)K * N; }
-    size_t in_words() const { return max_leaves * ((size_t)n_lwe + 1 + kn() + N + 4 + 1); }
+    // the leaf count, n_testv and n_keys of a run are at most max_leaves each
+    size_t in_words() const { return max_leaves * ((size_t)n_lwe + 1 + kn() + N + 4); }
     void* alloc(size_t bytes) {
         void* d = ctx->alloc_bytes(std::max<size_t>(8, bytes));
         owned.push_back(d);
@@ -483,82 +420,11 @@ struct vpbs_aggregate_verifier {
         (void)vpbs::stream_sync(ctx->stream);
         for (void* p : owned) ctx->release(p);
         if (h_in) (void)hipHostFree(h_in);
-        if (h_out) (void)hipHostFree(h_out);
         if (h_midx) (void)hipHostFree(h_midx);
         if (h_mout) (void)hipHostFree(h_mout);
         for (auto* p : proofs) vpbs_proof_verifier_free(p);
     }
 };
-
-namespace {
-// the statement stages queued on the context's stream: after them d_nodes[*top] holds the root and d_flag the raw-word flag
-void statement_enqueue(vpbs_aggregate_verifier* v, const Statement& s, int on_device, const u64** d_root) {
-    vpbs_ctx* ctx = v->ctx;
-    hipStream_t st = ctx->stream;
-    const size_t count = s.count, kn = v->kn();
-    const size_t n_ct = count * ((size_t)s.n_lwe + 1), n_out = count * kn, n_tv = s.n_testv * (size_t)s.N, n_kh = 4 * s.n_keys;
-    // the index arrays always come from the host; the word arrays only when they are host arrays
-    size_t at = 0;
-    const u64 *d_ct = s.cts, *d_oc = s.out_cts, *d_tv = s.testvs, *d_kh = s.key_hashes;
-    if (!on_device) {
-        std::memcpy(v->h_in, s.cts, 8 * n_ct);
-        std::memcpy(v->h_in + n_ct, s.out_cts, 8 * n_out);
-        std::memcpy(v->h_in + n_ct + n_out, s.testvs, 8 * n_tv);
-        std::memcpy(v->h_in + n_ct + n_out + n_tv, s.key_hashes, 8 * n_kh);
-        at = n_ct + n_out + n_tv + n_kh;
-        d_ct = v->d_in;
-        d_oc = v->d_in + n_ct;
-        d_tv = v->d_in + n_ct + n_out;
-        d_kh = v->d_in + n_ct + n_out + n_tv;
-    }
-    u32* idx = reinterpret_cast<u32*>(v->h_in + at);
-    for (size_t i = 0; i < count; ++i) {
-        idx[i] = (u32)s.tv(i);
-        idx[count + i] = (u32)s.key(i);
-    }
-    VPBS_HIP(hipMemcpyAsync(v->d_in, v->h_in, 8 * (at + count), hipMemcpyHostToDevice, st));
-    const u32* d_idx = reinterpret_cast<const u32*>(v->d_in + at);
-    VPBS_HIP(hipMemsetAsync(v->d_flag, 0, 4, st));
-    {
-        vpbs::Timed t(ctx, "vp_lwe_chain");
-        vpbs::lwe_chain_enqueue(st, d_ct, s.n_lwe, count, v->d_lwe);
-    }
-    const AggShape S{s.N, (u32)kn, s.n_lwe, (u32)s.n_pi()};
-    {
-        vpbs::Timed t(ctx, "ag_leaf");
-        ag_leaf<<<(u32)count, 16, 0, st>>>(d_tv, d_idx, d_oc, d_kh, d_idx + count, v->d_lwe, v->d_vks, S, v->d_stmt, v->d_flag);
-    }
-    VPBS_HIP(hipGetLastError());
-    const unsigned d = depth_of(count);
-    const u64* in = v->d_stmt;
-    u32 n_in = (u32)count;
-    {
-        vpbs::Timed t(ctx, "ag_fold");
-        for (unsigned l = 1; l <= d; ++l) {
-            const u32 nodes = 1u << (d - l);
-            u64* out = v->d_nodes[l & 1];
-            ag_fold<<<nodes, 16, 0, st>>>(in, n_in, out);
-            in = out;
-            n_in = nodes;
-        }
-    }
-    VPBS_HIP(hipGetLastError());
-    *d_root = in;
-}
-
-bool verifier_args_ok(vpbs_aggregate_verifier* v, const Statement& s, const char* who, std::string* msg) {
-    if (!statement_ok(s, who, msg)) return false;
-    if (s.count > v->max_leaves || s.n_testv > v->max_leaves || s.n_keys > v->max_leaves) {
-        *msg = std::string(who) + ": count, n_testv or n_keys exceeds max_leaves " + std::to_string(v->max_leaves);
-        return false;
-    }
-    if (depth_of(s.count) > v->levels) {
-        *msg = std::string(who) + ": count " + std::to_string(s.count) + " exceeds 2^levels = " + std::to_string((size_t)1 << v->levels);
-        return false;
-    }
-    return true;
-}
-}  // namespace
 
 // ================= the prover =================
 namespace {
@@ -680,9 +546,38 @@ struct vpbs_aggregator {
 };
 
 namespace {
+// ---- every leaf is parsed, verified and compared with vk_0 before anything is proven: cur[i] the leaf, why[i] "" or what is wrong with it ----
 void check_leaves(const vpbs_aggregator* a, const uint8_t* bytes, const size_t* offsets, size_t count, std::vector<Proof>& cur,
-                  std::vector<std::string>& why);
-long tree_host(vpbs_aggregator* a, std::vector<Proof>& cur, size_t count, uint8_t* out, size_t capacity, std::string& msg);
+                  std::vector<std::string>& why) {
+    cur.assign(count, Proof{});
+    why.assign(count, "");
+    const size_t cap3 = 3 * ((size_t)4 << 4), op = openings_words(a->leaf), fri_words = a->leaf_words - cap3 - op;
+    strided(count, [&](unsigned t, unsigned threads) {
+        for (size_t i = t; i < count; i += threads) {
+            Proof& p = cur[i];
+            const size_t len = offsets[i + 1] - offsets[i];
+            p.pis.assign(a->leaf_n_pi, 0);
+            std::vector<u64> fri(std::max(fri_words, len / 8 + 8));
+            p.flat.assign(a->leaf_words, 0);
+            const long n = vpbs_step_proof_from_bytes(&a->leaf, bytes + offsets[i], len, p.flat.data(), p.flat.data() + cap3, fri.data(), p.pis.data(),
+                                                      a->leaf_n_pi);
+            // a proof of the leaf shape has exactly leaf_words words: the parser accepts no other length of FRI section
+            if (n != (long)a->leaf_n_pi || 8 * (a->leaf_words + a->leaf_n_pi) > len) {
+                why[i] = "the bytes are not a vPBS proof of the leaf circuit (shape, canonical field elements, number of public inputs)";
+                continue;
+            }
+            std::memcpy(p.flat.data() + cap3 + op, fri.data(), 8 * fri_words);
+            if (std::memcmp(p.pis.data() + a->leaf_n_pi - VK, a->vk0.data(), 8 * VK) != 0) {
+                why[i] = "the proof carries other verifier data than vk_0";
+                continue;
+            }
+            vpbs_verify_inputs v = a->leaf;
+            v.public_inputs = p.pis.data();
+            v.n_public_inputs = a->leaf_n_pi;
+            if (vpbs_verify_step(&v, p.flat.data(), p.flat.data() + cap3, fri.data()) != 1) why[i] = "the proof does not verify";
+        }
+    });
+}
 
 // a root node's proof, serialised -> the number of bytes, or < 0 with msg
 long root_bytes(vpbs_aggregator* a, const Level& L, const Proof& p, uint8_t* out, size_t capacity, std::string& msg) {
@@ -693,6 +588,76 @@ long root_bytes(vpbs_aggregator* a, const Level& L, const Proof& p, uint8_t* out
     if (n > 0) return n;
     msg = "the output buffer is too small for the aggregate proof";
     return VPBS_ERR_INVALID;
+}
+
+// One node's proof, on either path: its wires are in a->d_wires and p.pis is filled -> p.flat.  The time goes to last.prove_ms; a proven
+// node is counted.  VPBS_OK, or the prover's status with msg.
+int prove_node(vpbs_aggregator* a, const Level& L, Proof& p, std::string& msg) {
+    const double t0 = now();
+    vpbs_step_inputs in{};
+    p.flat.assign(L.proof_words(), 0);
+    L.step_inputs(in, a->d_wires, p.pis.data());
+    u64 *cp = p.flat.data(), *opn = cp + 3 * L.sz.cap_words, *fr = opn + L.sz.openings_words;
+    const int rc = vpbs_prove_step(a->ctx, &in, cp, opn, fr, nullptr, nullptr);
+    a->last.prove_ms += 1e3 * (now() - t0);
+    if (rc != 0) return msg = std::string("proof: ") + vpbs_last_error(a->ctx), rc;
+    ++a->last.nodes;
+    return VPBS_OK;
+}
+
+// where a tree's root goes once the level of its depth is through: the number of bytes it serialised, or < 0 (with the run's msg set), which ends the run
+using RootFn = std::function<long(size_t tree, const Level& L, const Proof& p)>;
+
+// ---- tree `t` on the host path, level by level: its checked leaves in `cur` -> its root to `root`; what that returns, or < 0 with msg ----
+long tree_host(vpbs_aggregator* a, std::vector<Proof>& cur, size_t count, size_t t, const RootFn& root, std::string& msg) {
+    const unsigned d = depth_of(count);
+    std::vector<u64> vks((a->levels.size() + 1) * VK);
+    vpbs_aggregator_verifier_data(a, vks.data());
+    for (unsigned l = 1; l <= d; ++l) {
+        const Level& L = a->levels[l - 1];
+        // the distinct nodes of this level, in order, and which proofs of `cur` they stand on
+        std::vector<u32> tree(level_jobs(&count, 1, l, nullptr, nullptr, nullptr, 0)), left(tree.size()), right(tree.size());
+        level_jobs(&count, 1, l, tree.data(), left.data(), right.data(), tree.size());
+        std::vector<Proof> next(tree.size());
+        std::string werr[2];
+        double wms[2] = {0, 0};
+        auto witness = [&](size_t j) {   // the node's PartialWitness in the circuit's order, then the plan
+            const double t0 = now();
+            const Proof &x = cur[left[j]], &y = cur[right[j]];
+            std::vector<u64> vals;
+            vals.reserve(L.n_preset);
+            vals.insert(vals.end(), x.flat.begin(), x.flat.end());
+            vals.insert(vals.end(), x.pis.begin(), x.pis.end());
+            vals.insert(vals.end(), y.flat.begin(), y.flat.end());
+            vals.insert(vals.end(), y.pis.begin(), y.pis.end());
+            vals.insert(vals.end(), vks.begin(), vks.begin() + VK * l);
+            char e[256] = {0};
+            werr[j & 1].clear();
+            if (vals.size() != L.n_preset) werr[j & 1] = "the children do not have the circuit's shape";
+            else if (vpbs_witness_plan_run(L.plan, vals.data(), 8, a->bufs[j & 1], e, sizeof e) != 0) werr[j & 1] = std::string("witness: ") + e;
+            wms[j & 1] = 1e3 * (now() - t0);
+        };
+        witness(0);
+        for (size_t j = 0; j < next.size(); ++j) {
+            const std::string at = "level " + std::to_string(l) + ", node " + std::to_string(j) + ": ";
+            a->last.witness_ms += wms[j & 1];
+            if (!werr[j & 1].empty()) return msg = at + werr[j & 1], VPBS_ERR_INVALID;
+            const u64* wires = a->bufs[j & 1];
+            Proof& p = next[j];
+            p.pis.resize(L.n_pi);
+            for (size_t i = 0; i < L.n_pi; ++i) p.pis[i] = wires[L.pi_pos[i]];
+            std::string why;
+            int rc = vpbs_device_upload(a->ctx, a->d_wires, wires, (size_t)L.n_wires * L.n);
+            if (rc != 0) why = std::string("proof: ") + vpbs_last_error(a->ctx);
+            std::thread ahead;   // the next node's witness while this one is being proven (the other buffer)
+            if (j + 1 < next.size()) ahead = std::thread(witness, j + 1);
+            if (rc == 0) rc = prove_node(a, L, p, why);
+            if (ahead.joinable()) ahead.join();
+            if (rc != 0) return msg = at + why, (long)rc;
+        }
+        cur.swap(next);
+    }
+    return root(t, a->levels[d - 1], cur[0]);
 }
 
 // the child rows of a chunk and its (left row, right row) table, staged in h_rows and queued for d_rows on the context's stream -> the job
@@ -709,13 +674,11 @@ PresetJob presets_upload(vpbs_aggregator* a, const Level& L, unsigned l, const s
 }
 
 // ---- the trees of a run on the device path, level by level over ALL of them: the checked leaves of all trees in `cur`, concatenated.  A tree's
-// root goes to `root` after the level of its depth (a negative return ends the run).  VPBS_OK, or < 0 with msg ----
-using RootFn = std::function<long(size_t tree, const Level& L, const Proof& p)>;
+// root goes to `root` after the level of its depth.  VPBS_OK, or < 0 with msg ----
 long trees_device(vpbs_aggregator* a, std::vector<Proof>& cur, const size_t* counts, size_t n_trees, const RootFn& root, std::string& msg) {
     vpbs_ctx* ctx = a->ctx;
     unsigned deepest = 0;
     for (size_t t = 0; t < n_trees; ++t) deepest = std::max(deepest, depth_of(counts[t]));
-    vpbs_step_inputs in{};
     try {
         VPBS_HIP(hipSetDevice(ctx->device));
         for (unsigned l = 1; l <= deepest; ++l) {
@@ -766,16 +729,11 @@ long trees_device(vpbs_aggregator* a, std::vector<Proof>& cur, const size_t* cou
                     const double tg = now();
                     int rc = vpbs_witness_device_read(L.wd, j, L.pi_pos.data(), L.n_pi, p.pis.data());
                     if (rc == 0) rc = vpbs_witness_device_wires(L.wd, j, a->d_wires);
-                    const double tp = now();
-                    a->dev_stats[3] += (uint64_t)(1e6 * (tp - tg));
+                    a->dev_stats[3] += (uint64_t)(1e6 * (now() - tg));
                     if (rc != 0) return msg = at_node + "gather: " + vpbs_last_error(ctx), (long)rc;
-                    p.flat.assign(L.proof_words(), 0);
-                    L.step_inputs(in, a->d_wires, p.pis.data());
-                    u64 *cp = p.flat.data(), *opn = cp + 3 * L.sz.cap_words, *fr = opn + L.sz.openings_words;
-                    rc = vpbs_prove_step(ctx, &in, cp, opn, fr, nullptr, nullptr);
-                    a->last.prove_ms += 1e3 * (now() - tp);
-                    if (rc != 0) return msg = at_node + "proof: " + vpbs_last_error(ctx), (long)rc;
-                    ++a->last.nodes;
+                    std::string why;
+                    rc = prove_node(a, L, p, why);
+                    if (rc != 0) return msg = at_node + why, (long)rc;
                     ++a->dev_stats[0];
                 }
             }
@@ -794,6 +752,50 @@ long trees_device(vpbs_aggregator* a, std::vector<Proof>& cur, const size_t* cou
         return e.status;
     }
     return VPBS_OK;
+}
+
+// a run starts from zeroed figures, whatever it goes on to refuse
+void reset_stats(vpbs_aggregator* a) {
+    a->last = vpbs_aggregate_stats{};
+    std::memset(a->dev_stats, 0, sizeof a->dev_stats);
+}
+
+// ---- The body of vpbs_aggregator_run (one tree) and _run_many, under the aggregator's lock, after reset_stats and the wrapper's own
+// refusals (1 <= counts[t] <= 2^levels, fewer than 2^32 leaves, no null pointer).  `many`: trees are named -- a bad leaf is "tree t, leaf
+// i", not "leaf i", and what fails in tree t on the host path starts "tree t: ".  root takes the roots.  VPBS_OK, or < 0 with msg ----
+long run_body(vpbs_aggregator* a, const uint8_t* bytes, const size_t* offsets, const size_t* counts, size_t n_trees, bool many, const RootFn& root,
+              std::string& msg) {
+    const auto tree = [](size_t t) { return "tree " + std::to_string(t); };
+    std::vector<size_t> first(n_trees + 1, 0);
+    for (size_t t = 0; t < n_trees; ++t) first[t + 1] = first[t] + counts[t];
+    const size_t total = first[n_trees];
+    for (size_t i = 0; i < total; ++i)
+        if (offsets[i + 1] < offsets[i]) return msg = "offsets decrease at leaf " + std::to_string(i), VPBS_ERR_INVALID;
+    const double t_start = now();
+    for (size_t t = 0; t < n_trees; ++t) a->last.depth = std::max(a->last.depth, depth_of(counts[t]));
+    // ---- ALL leaves of all trees before anything is proven ----
+    std::vector<Proof> cur;
+    std::vector<std::string> why;
+    check_leaves(a, bytes, offsets, total, cur, why);
+    a->last.check_leaves_ms = 1e3 * (now() - t_start);
+    long rc = VPBS_OK;
+    for (size_t t = 0; t < n_trees && rc == VPBS_OK; ++t)
+        for (size_t i = first[t]; i < first[t + 1] && rc == VPBS_OK; ++i)
+            if (!why[i].empty()) {
+                msg = (many ? tree(t) + ", leaf " : "leaf ") + std::to_string(i - first[t]) + ": " + why[i] + "; nothing was proven";
+                rc = VPBS_ERR_INVALID;
+            }
+    if (rc == VPBS_OK && a->max_nodes) {   // the device witness: the levels of all trees in chunks
+        rc = trees_device(a, cur, counts, n_trees, root, msg);
+    } else if (rc == VPBS_OK) {            // the host path: the trees one after the other
+        for (size_t t = 0; t < n_trees && rc >= 0; ++t) {
+            std::vector<Proof> leaves(std::make_move_iterator(cur.begin() + first[t]), std::make_move_iterator(cur.begin() + first[t + 1]));
+            rc = tree_host(a, leaves, counts[t], t, root, msg);
+            if (rc < 0 && many) msg = tree(t) + ": " + msg;
+        }
+    }
+    a->last.seconds = now() - t_start;
+    return rc < 0 ? rc : VPBS_OK;
 }
 }  // namespace
 
@@ -953,152 +955,19 @@ long vpbs_aggregator_run(vpbs_aggregator* a, const uint8_t* bytes, const size_t*
     };
     if (!a) return fail(VPBS_ERR_INVALID, "null aggregator");
     std::lock_guard<std::mutex> lock(a->mu);
-    a->last = vpbs_aggregate_stats{};
-    std::memset(a->dev_stats, 0, sizeof a->dev_stats);
+    reset_stats(a);
     if (!bytes || !offsets || !out) return fail(VPBS_ERR_INVALID, "null bytes, offsets or out");
     if (count == 0) return fail(VPBS_ERR_INVALID, "count is 0: there is nothing to aggregate");
-    const unsigned d = depth_of(count);
-    if (d > a->levels.size())
+    if (depth_of(count) > a->levels.size())
         return fail(VPBS_ERR_INVALID, "count " + std::to_string(count) + " exceeds 2^levels = " + std::to_string((size_t)1 << a->levels.size()));
-    for (size_t i = 0; i < count; ++i)
-        if (offsets[i + 1] < offsets[i]) return fail(VPBS_ERR_INVALID, "offsets decrease at leaf " + std::to_string(i));
-    const double t_start = now();
-    a->last.depth = d;
-    std::vector<Proof> cur;
-    std::vector<std::string> why;
-    check_leaves(a, bytes, offsets, count, cur, why);
-    a->last.check_leaves_ms = 1e3 * (now() - t_start);
-    for (size_t i = 0; i < count; ++i)
-        if (!why[i].empty()) {
-            a->last.seconds = now() - t_start;
-            return fail(VPBS_ERR_INVALID, "leaf " + std::to_string(i) + ": " + why[i] + "; nothing was proven");
-        }
     std::string msg;
-    long n = 0;
-    if (a->max_nodes) {   // the device witness: this tree's levels in chunks; the root's bytes only once every level is through
-        long written = 0;
-        n = trees_device(a, cur, &count, 1, [&](size_t, const Level& L, const Proof& p) { return written = root_bytes(a, L, p, out, capacity, msg); }, msg);
-        if (n == VPBS_OK) n = written;
-    } else {
-        n = tree_host(a, cur, count, out, capacity, msg);
-    }
-    a->last.seconds = now() - t_start;
-    if (n < 0) return fail(n, msg);
+    long written = 0;   // the one root's bytes go straight into out
+    const long rc = run_body(a, bytes, offsets, &count, 1, false,
+                             [&](size_t, const Level& L, const Proof& p) { return written = root_bytes(a, L, p, out, capacity, msg); }, msg);
+    if (rc < 0) return fail(rc, msg);
     if (stats) *stats = a->last;
-    return n;
+    return written;
 }
-}  // extern "C"
-
-namespace {
-// ---- every leaf is parsed, verified and compared with vk_0 before anything is proven: cur[i] the leaf, why[i] "" or what is wrong with it ----
-void check_leaves(const vpbs_aggregator* a, const uint8_t* bytes, const size_t* offsets, size_t count, std::vector<Proof>& cur,
-                  std::vector<std::string>& why) {
-    cur.assign(count, Proof{});
-    why.assign(count, "");
-    {
-        const size_t cap3 = 3 * ((size_t)4 << 4), op = openings_words(a->leaf), fri_words = a->leaf_words - cap3 - op;
-        const unsigned hw = std::max(1u, std::min(HOST_THREADS, std::thread::hardware_concurrency()));
-        const unsigned threads = (unsigned)std::min<size_t>(hw, count);
-        auto work = [&](unsigned t) {
-            for (size_t i = t; i < count; i += threads) {
-                Proof& p = cur[i];
-                const size_t len = offsets[i + 1] - offsets[i];
-                p.pis.assign(a->leaf_n_pi, 0);
-                std::vector<u64> fri(std::max(fri_words, len / 8 + 8));
-                p.flat.assign(a->leaf_words, 0);
-                const long n = vpbs_step_proof_from_bytes(&a->leaf, bytes + offsets[i], len, p.flat.data(), p.flat.data() + cap3, fri.data(), p.pis.data(),
-                                                          a->leaf_n_pi);
-                // a proof of the leaf shape has exactly leaf_words words: the parser accepts no other length of FRI section
-                if (n != (long)a->leaf_n_pi || 8 * (a->leaf_words + a->leaf_n_pi) > len) {
-                    why[i] = "the bytes are not a vPBS proof of the leaf circuit (shape, canonical field elements, number of public inputs)";
-                    continue;
-                }
-                std::memcpy(p.flat.data() + cap3 + op, fri.data(), 8 * fri_words);
-                if (std::memcmp(p.pis.data() + a->leaf_n_pi - VK, a->vk0.data(), 8 * VK) != 0) {
-                    why[i] = "the proof carries other verifier data than vk_0";
-                    continue;
-                }
-                vpbs_verify_inputs v = a->leaf;
-                v.public_inputs = p.pis.data();
-                v.n_public_inputs = a->leaf_n_pi;
-                if (vpbs_verify_step(&v, p.flat.data(), p.flat.data() + cap3, fri.data()) != 1) why[i] = "the proof does not verify";
-            }
-        };
-        if (threads <= 1) {
-            work(0);
-        } else {
-            std::vector<std::thread> pool;
-            for (unsigned t = 0; t < threads; ++t) pool.emplace_back(work, t);
-            for (auto& t : pool) t.join();
-        }
-    }
-}
-
-// ---- one tree on the host path, level by level: the checked leaves in `cur` -> the aggregate's bytes in out; their number, or < 0 with msg ----
-long tree_host(vpbs_aggregator* a, std::vector<Proof>& cur, size_t count, uint8_t* out, size_t capacity, std::string& msg) {
-    auto fail = [&](long rc, const std::string& m) {
-        msg = m;
-        return rc;
-    };
-    const unsigned d = depth_of(count);
-    std::vector<u64> vks((a->levels.size() + 1) * VK);
-    vpbs_aggregator_verifier_data(a, vks.data());
-    vpbs_step_inputs in{};
-    for (unsigned l = 1; l <= d; ++l) {
-        const Level& L = a->levels[l - 1];
-        // the distinct nodes of this level, in order, and which proofs of `cur` they stand on
-        std::vector<u32> tree(level_jobs(&count, 1, l, nullptr, nullptr, nullptr, 0)), jl(tree.size()), jr(tree.size());
-        level_jobs(&count, 1, l, tree.data(), jl.data(), jr.data(), tree.size());
-        std::vector<std::pair<size_t, size_t>> jobs;
-        for (size_t j = 0; j < tree.size(); ++j) jobs.push_back({jl[j], jr[j]});
-        std::vector<Proof> next(jobs.size());
-        std::string werr[2];
-        double wms[2] = {0, 0};
-        auto witness = [&](size_t j) {   // the node's PartialWitness in the circuit's order, then the plan
-            const double t0 = now();
-            const Proof &x = cur[jobs[j].first], &y = cur[jobs[j].second];
-            std::vector<u64> vals;
-            vals.reserve(L.n_preset);
-            vals.insert(vals.end(), x.flat.begin(), x.flat.end());
-            vals.insert(vals.end(), x.pis.begin(), x.pis.end());
-            vals.insert(vals.end(), y.flat.begin(), y.flat.end());
-            vals.insert(vals.end(), y.pis.begin(), y.pis.end());
-            vals.insert(vals.end(), vks.begin(), vks.begin() + VK * l);
-            char e[256] = {0};
-            werr[j & 1].clear();
-            if (vals.size() != L.n_preset) werr[j & 1] = "the children do not have the circuit's shape";
-            else if (vpbs_witness_plan_run(L.plan, vals.data(), 8, a->bufs[j & 1], e, sizeof e) != 0) werr[j & 1] = std::string("witness: ") + e;
-            wms[j & 1] = 1e3 * (now() - t0);
-        };
-        witness(0);
-        for (size_t j = 0; j < jobs.size(); ++j) {
-            const std::string at = "level " + std::to_string(l) + ", node " + std::to_string(j) + ": ";
-            a->last.witness_ms += wms[j & 1];
-            if (!werr[j & 1].empty()) return fail(VPBS_ERR_INVALID, at + werr[j & 1]);
-            const u64* wires = a->bufs[j & 1];
-            Proof& p = next[j];
-            p.pis.resize(L.n_pi);
-            for (size_t i = 0; i < L.n_pi; ++i) p.pis[i] = wires[L.pi_pos[i]];
-            int rc = vpbs_device_upload(a->ctx, a->d_wires, wires, (size_t)L.n_wires * L.n);
-            std::thread ahead;   // the next node's witness while this one is being proven (the other buffer)
-            if (j + 1 < jobs.size()) ahead = std::thread(witness, j + 1);
-            const double t0 = now();
-            p.flat.assign(L.proof_words(), 0);
-            L.step_inputs(in, a->d_wires, p.pis.data());
-            u64 *cp = p.flat.data(), *opn = cp + 3 * L.sz.cap_words, *fr = opn + L.sz.openings_words;
-            if (rc == 0) rc = vpbs_prove_step(a->ctx, &in, cp, opn, fr, nullptr, nullptr);
-            a->last.prove_ms += 1e3 * (now() - t0);
-            if (ahead.joinable()) ahead.join();
-            if (rc != 0) return fail(rc, at + "proof: " + vpbs_last_error(a->ctx));
-            ++a->last.nodes;
-        }
-        cur.swap(next);
-    }
-    return root_bytes(a, a->levels[d - 1], cur[0], out, capacity, msg);
-}
-}  // namespace
-
-extern "C" {
 
 int vpbs_aggregate_level_jobs(const size_t* counts, size_t n_trees, unsigned level, uint32_t* tree, uint32_t* left, uint32_t* right,
                               size_t capacity) {
@@ -1169,12 +1038,10 @@ long vpbs_aggregator_run_many(vpbs_aggregator* a, const uint8_t* bytes, const si
     };
     if (!a) return fail(VPBS_ERR_INVALID, "null aggregator");
     std::lock_guard<std::mutex> lock(a->mu);
-    a->last = vpbs_aggregate_stats{};
-    std::memset(a->dev_stats, 0, sizeof a->dev_stats);
+    reset_stats(a);
     if (n_trees == 0) return fail(VPBS_ERR_INVALID, "n_trees is 0: there is nothing to aggregate");
     if (!bytes || !offsets || !counts || !fn) return fail(VPBS_ERR_INVALID, "null bytes, offsets, counts or fn");
     size_t total = 0;
-    std::vector<size_t> first(n_trees + 1, 0);
     for (size_t t = 0; t < n_trees; ++t) {
         if (counts[t] == 0) return fail(VPBS_ERR_INVALID, "tree " + std::to_string(t) + " is empty");
         if (counts[t] > ((size_t)1 << a->levels.size()))
@@ -1182,51 +1049,31 @@ long vpbs_aggregator_run_many(vpbs_aggregator* a, const uint8_t* bytes, const si
                                               std::to_string((size_t)1 << a->levels.size()));
         if (counts[t] > 0xffffffffull - total) return fail(VPBS_ERR_INVALID, "2^32 leaves or more");
         total += counts[t];
-        first[t + 1] = total;
-        a->last.depth = std::max(a->last.depth, depth_of(counts[t]));
+        a->last.depth = std::max(a->last.depth, depth_of(counts[t]));   // a refused call reports the depths it saw
     }
-    for (size_t i = 0; i < total; ++i)
-        if (offsets[i + 1] < offsets[i]) return fail(VPBS_ERR_INVALID, "offsets decrease at leaf " + std::to_string(i));
-    const double t_start = now();
-    // ---- ALL leaves of all trees before anything is proven ----
-    std::vector<Proof> cur;
-    std::vector<std::string> why;
-    check_leaves(a, bytes, offsets, total, cur, why);
-    a->last.check_leaves_ms = 1e3 * (now() - t_start);
-    for (size_t t = 0; t < n_trees; ++t)
-        for (size_t i = first[t]; i < first[t + 1]; ++i)
-            if (!why[i].empty()) {
-                a->last.seconds = now() - t_start;
-                return fail(VPBS_ERR_INVALID, "tree " + std::to_string(t) + ", leaf " + std::to_string(i - first[t]) + ": " + why[i] + "; nothing was proven");
-            }
     std::string msg;
+    // A root is serialised when its tree is through.  The tree whose turn it is goes to fn at once -- on the host path, where the trees come
+    // in order, every one; on the device path a shallow tree is through first and is kept until every tree before it has been handed on.
     std::vector<uint8_t> agg(vpbs::aggregator_max_bytes(a));
-    long rc = VPBS_OK;
-    if (a->max_nodes) {
-        // a root is serialised when its level is through and handed on once every tree before it has been
-        std::vector<std::vector<uint8_t>> done(n_trees);
-        std::vector<uint8_t> ready(n_trees, 0);
-        size_t handed = 0;
-        rc = trees_device(a, cur, counts, n_trees, [&](size_t t, const Level& L, const Proof& p) {
-            const long n = root_bytes(a, L, p, agg.data(), agg.size(), msg);
-            if (n < 0) return n;
-            done[t].assign(agg.begin(), agg.begin() + n);
+    std::vector<std::vector<uint8_t>> kept(n_trees);
+    std::vector<uint8_t> ready(n_trees, 0);
+    size_t handed = 0;
+    auto root = [&](size_t t, const Level& L, const Proof& p) {
+        const long n = root_bytes(a, L, p, agg.data(), agg.size(), msg);
+        if (n < 0) return n;
+        if (t != handed) {
+            kept[t].assign(agg.begin(), agg.begin() + n);
             ready[t] = 1;
-            for (; handed < n_trees && ready[handed]; ++handed) {
-                fn(user, handed, done[handed].data(), done[handed].size());
-                std::vector<uint8_t>().swap(done[handed]);
-            }
             return n;
-        }, msg);
-    } else {
-        for (size_t t = 0; t < n_trees && rc >= 0; ++t) {
-            std::vector<Proof> leaves(std::make_move_iterator(cur.begin() + first[t]), std::make_move_iterator(cur.begin() + first[t + 1]));
-            rc = tree_host(a, leaves, counts[t], agg.data(), agg.size(), msg);
-            if (rc >= 0) fn(user, t, agg.data(), (size_t)rc);
-            else msg = "tree " + std::to_string(t) + ": " + msg;
         }
-    }
-    a->last.seconds = now() - t_start;
+        fn(user, handed++, agg.data(), (size_t)n);
+        for (; handed < n_trees && ready[handed]; ++handed) {
+            fn(user, handed, kept[handed].data(), kept[handed].size());
+            std::vector<uint8_t>().swap(kept[handed]);
+        }
+        return n;
+    };
+    const long rc = run_body(a, bytes, offsets, counts, n_trees, true, root, msg);
     if (rc < 0) return fail(rc, msg);
     return (long)n_trees;
 }
@@ -1307,16 +1154,10 @@ int vpbs_aggregate_verifier_create_many(vpbs_ctx* ctx, const vpbs_aggregate_shap
     v->ctx = ctx;
     try {
         VPBS_HIP(hipSetDevice(ctx->device));
-        const size_t pad = (size_t)1 << depth_of(max_leaves);
         v->d_vks = static_cast<u64*>(v->alloc(8 * VK * (v->levels + 1)));
         v->d_in = static_cast<u64*>(v->alloc(8 * v->in_words()));
-        v->d_lwe = static_cast<u64*>(v->alloc(32 * max_leaves));
         v->d_stmt = static_cast<u64*>(v->alloc(32 * max_leaves));
-        for (auto& n : v->d_nodes) n = static_cast<u64*>(v->alloc(32 * std::max<size_t>(1, pad / 2)));
-        v->d_flag = static_cast<u32*>(v->alloc(4));
-        v->d_out = static_cast<uint8_t*>(v->alloc(8));
         VPBS_HIP(hipHostMalloc((void**)&v->h_in, 8 * v->in_words(), hipHostMallocDefault));
-        VPBS_HIP(hipHostMalloc((void**)&v->h_out, 64, hipHostMallocDefault));
         for (auto& n : v->d_mnodes) n = static_cast<u64*>(v->alloc(32 * max_leaves));
         v->d_roots = static_cast<u64*>(v->alloc(32 * max_aggregates));
         v->d_mflags = static_cast<u32*>(v->alloc(4 * max_aggregates));
@@ -1336,77 +1177,26 @@ int vpbs_aggregate_verifier_create_many(vpbs_ctx* ctx, const vpbs_aggregate_shap
     return VPBS_OK;
 }
 
-int vpbs_aggregate_verifier_root(vpbs_aggregate_verifier* v, size_t count, const uint64_t* testvs, size_t n_testv, const uint32_t* testv_of,
-                                 const uint64_t* cts, const uint64_t* out_cts, const uint64_t* key_hashes, size_t n_keys, const uint32_t* key_of,
-                                 int on_device, uint64_t out[4], char* err, size_t err_len) {
-    report(err, err_len, "");
-    if (!v || !out) return report(err, err_len, "vpbs_aggregate_verifier_root: null argument"), VPBS_ERR_INVALID;
-    std::lock_guard<std::mutex> lock(v->mu);
-    u64 vk0_unused = 0;   // the host checks need a non-null vk0; the device holds the real one
-    const Statement s{v->N, v->K, v->n_lwe, &vk0_unused, count, testvs, n_testv, testv_of, cts, out_cts, key_hashes, n_keys, key_of};
-    std::string msg;
-    if (!verifier_args_ok(v, s, "vpbs_aggregate_verifier_root", &msg)) return report(err, err_len, msg), VPBS_ERR_INVALID;
-    try {
-        VPBS_HIP(hipSetDevice(v->ctx->device));
-        const u64* d_root = nullptr;
-        statement_enqueue(v, s, on_device, &d_root);
-        VPBS_HIP(hipMemcpyAsync(v->h_out, d_root, 32, hipMemcpyDeviceToHost, v->ctx->stream));
-        VPBS_HIP(hipMemcpyAsync(v->h_out + 4, v->d_flag, 4, hipMemcpyDeviceToHost, v->ctx->stream));
-        VPBS_HIP(vpbs::stream_sync(v->ctx->stream));
-    } catch (const DeviceError& e) {
-        v->ctx->err = e.what;
-        return report(err, err_len, "vpbs_aggregate_verifier_root: " + e.what), e.status;
-    }
-    if ((u32)v->h_out[4] != 0) return 1;
-    std::memcpy(out, v->h_out, 32);
-    return VPBS_OK;
-}
-
-int vpbs_aggregate_verifier_run(vpbs_aggregate_verifier* v, const uint8_t* bytes, size_t len, size_t count, const uint64_t* testvs, size_t n_testv,
-                                const uint32_t* testv_of, const uint64_t* cts, const uint64_t* out_cts, const uint64_t* key_hashes, size_t n_keys,
-                                const uint32_t* key_of, int on_device, int* reason, char* err, size_t err_len) {
-    report(err, err_len, "");
-    if (reason) *reason = VPBS_AGG_MALFORMED;
-    if (!v || !bytes) return report(err, err_len, "vpbs_aggregate_verifier_run: null argument"), VPBS_ERR_INVALID;
-    std::lock_guard<std::mutex> lock(v->mu);
-    u64 vk0_unused = 0;
-    const Statement s{v->N, v->K, v->n_lwe, &vk0_unused, count, testvs, n_testv, testv_of, cts, out_cts, key_hashes, n_keys, key_of};
-    std::string msg;
-    if (!verifier_args_ok(v, s, "vpbs_aggregate_verifier_run", &msg)) return report(err, err_len, msg), VPBS_ERR_INVALID;
-    const unsigned d = depth_of(count);
-    try {
-        VPBS_HIP(hipSetDevice(v->ctx->device));
-        hipStream_t st = v->ctx->stream;
-        const u64* d_root = nullptr;
-        statement_enqueue(v, s, on_device, &d_root);
-        const size_t offsets[2] = {0, len};
-        vpbs::ProofBatchView pv{};
-        const int rc = vpbs::proof_verifier_enqueue(v->proofs[d - 1], bytes, offsets, 1, &pv);
-        if (rc) {
-            (void)vpbs::stream_sync(st);
-            return report(err, err_len, "vpbs_aggregate_verifier_run: the batch verifier refused the bytes"), rc;
-        }
-        const u32 n_expected = (u32)(4 + VK * d);
-        VPBS_REQUIRE(pv.max_pi >= n_expected, "the batch verifier's slot is smaller than the aggregate's public inputs");
-        ag_result<<<1, 64, 0, st>>>(pv.reasons, pv.n_pi, pv.words + pv.n_fixed, v->d_vks, d_root, v->d_flag, n_expected, v->d_out);
-        VPBS_HIP(hipGetLastError());
-        VPBS_HIP(hipMemcpyAsync(v->h_out, v->d_out, 2, hipMemcpyDeviceToHost, st));
-        VPBS_HIP(vpbs::stream_sync(st));
-    } catch (const DeviceError& e) {
-        v->ctx->err = e.what;
-        return report(err, err_len, "vpbs_aggregate_verifier_run: " + e.what), e.status;
-    }
-    const uint8_t* o = reinterpret_cast<const uint8_t*>(v->h_out);
-    if (reason) *reason = o[1];
-    return o[0];
-}
-
 void vpbs_aggregate_verifier_free(vpbs_aggregate_verifier* v) { delete v; }
 
 }  // extern "C"
 
-// ================= many aggregates in one run =================
+// ================= the device verifier's runs: the trees of a run, one or many =================
 namespace {
+// what run and root refuse, by name, before anything is queued
+bool verifier_args_ok(vpbs_aggregate_verifier* v, const Statement& s, const char* who, std::string* msg) {
+    if (!statement_ok(s, who, msg)) return false;
+    if (s.count > v->max_leaves || s.n_testv > v->max_leaves || s.n_keys > v->max_leaves) {
+        *msg = std::string(who) + ": count, n_testv or n_keys exceeds max_leaves " + std::to_string(v->max_leaves);
+        return false;
+    }
+    if (depth_of(s.count) > v->levels) {
+        *msg = std::string(who) + ": count " + std::to_string(s.count) + " exceeds 2^levels = " + std::to_string((size_t)1 << v->levels);
+        return false;
+    }
+    return true;
+}
+
 // What run_many and roots_many refuse, by name, before anything is queued; s.count is the total leaf count.  depth: of every tree.
 bool many_args_ok(vpbs_aggregate_verifier* v, const Statement& s, size_t n_agg, const size_t* leaf_first, const char* who, std::vector<unsigned>* depth,
                   std::string* msg) {
@@ -1513,36 +1303,13 @@ void many_statement_enqueue(vpbs_aggregate_verifier* v, const Statement& s, size
     }
     VPBS_HIP(hipGetLastError());
 }
-}  // namespace
 
-namespace vpbs {
-unsigned aggregator_levels(const vpbs_aggregator* a) { return (unsigned)a->levels.size(); }
-unsigned aggregator_device_witness(const vpbs_aggregator* a) { return a->max_nodes; }
-size_t aggregator_max_bytes(const vpbs_aggregator* a) {
-    size_t most = 0;
-    for (const Level& L : a->levels) most = std::max(most, 8 * ((size_t)L.n_wires * 64 + ((size_t)1 << 17)) + 8 * L.n_pi);
-    return most;
-}
-void aggregate_verifier_shape(const vpbs_aggregate_verifier* v, AggregateVerifierShape* out) {
-    *out = AggregateVerifierShape{v->ctx, v->N, v->K, v->n_lwe, v->levels, v->max_leaves, v->max_aggregates};
-}
-}  // namespace vpbs
+// ---- The two cores of the four entry points, under the verifier's lock: s, n_agg, leaf_first and depth are through the entry point's own
+// refusals, `who` names it in what a core reports.  Everything from the statement stages to the one wait, and the read-back. ----
 
-extern "C" {
-int vpbs_aggregate_verifier_roots_many(vpbs_aggregate_verifier* v, size_t n_agg, const size_t* leaf_first, const uint64_t* testvs, size_t n_testv,
-                                       const uint32_t* testv_of, const uint64_t* cts, const uint64_t* out_cts, const uint64_t* key_hashes,
-                                       size_t n_keys, const uint32_t* key_of, int on_device, uint64_t* out, uint8_t* raw_bad, char* err,
-                                       size_t err_len) {
-    report(err, err_len, "");
-    const char* who = "vpbs_aggregate_verifier_roots_many";
-    if (!v || !out || !raw_bad) return report(err, err_len, std::string(who) + ": null argument"), VPBS_ERR_INVALID;
-    std::lock_guard<std::mutex> lock(v->mu);
-    u64 vk0_unused = 0;   // the host checks need a non-null vk0; the device holds the real one
-    const Statement s{v->N, v->K, v->n_lwe, &vk0_unused, leaf_first && n_agg ? leaf_first[n_agg] : 0, testvs, n_testv, testv_of, cts, out_cts,
-                      key_hashes, n_keys, key_of};
-    std::string msg;
-    std::vector<unsigned> depth;
-    if (!many_args_ok(v, s, n_agg, leaf_first, who, &depth, &msg)) return report(err, err_len, msg), VPBS_ERR_INVALID;
+// the statement stages alone -> out [n_agg][4] and raw_bad [n_agg]; VPBS_OK, or < 0 with err
+int roots_core(vpbs_aggregate_verifier* v, const Statement& s, size_t n_agg, const size_t* leaf_first, const std::vector<unsigned>& depth,
+               int on_device, const char* who, uint64_t* out, uint8_t* raw_bad, char* err, size_t err_len) {
     try {
         VPBS_HIP(hipSetDevice(v->ctx->device));
         hipStream_t st = v->ctx->stream;
@@ -1561,22 +1328,10 @@ int vpbs_aggregate_verifier_roots_many(vpbs_aggregate_verifier* v, size_t n_agg,
     return VPBS_OK;
 }
 
-long vpbs_aggregate_verifier_run_many(vpbs_aggregate_verifier* v, const uint8_t* bytes, const size_t* offsets, size_t n_agg, const size_t* leaf_first,
-                                      const uint64_t* testvs, size_t n_testv, const uint32_t* testv_of, const uint64_t* cts, const uint64_t* out_cts,
-                                      const uint64_t* key_hashes, size_t n_keys, const uint32_t* key_of, int on_device, uint8_t* verdicts,
-                                      uint8_t* reasons, char* err, size_t err_len) {
-    report(err, err_len, "");
-    const char* who = "vpbs_aggregate_verifier_run_many";
-    if (!v || !bytes || !offsets || !verdicts) return report(err, err_len, std::string(who) + ": null argument"), VPBS_ERR_INVALID;
-    std::lock_guard<std::mutex> lock(v->mu);
-    u64 vk0_unused = 0;
-    const Statement s{v->N, v->K, v->n_lwe, &vk0_unused, leaf_first && n_agg ? leaf_first[n_agg] : 0, testvs, n_testv, testv_of, cts, out_cts,
-                      key_hashes, n_keys, key_of};
-    std::string msg;
-    std::vector<unsigned> depth;
-    if (!many_args_ok(v, s, n_agg, leaf_first, who, &depth, &msg)) return report(err, err_len, msg), VPBS_ERR_INVALID;
-    for (size_t a = 0; a < n_agg; ++a)
-        if (offsets[a + 1] < offsets[a]) return report(err, err_len, std::string(who) + ": offsets decrease at aggregate " + std::to_string(a)), VPBS_ERR_INVALID;
+// aggregate a = bytes[offsets[a] .. offsets[a + 1]) against tree a -> verdicts [n_agg], reasons [n_agg] (may be null); the number accepted,
+// or < 0 with err
+long run_core(vpbs_aggregate_verifier* v, const Statement& s, const uint8_t* bytes, const size_t* offsets, size_t n_agg, const size_t* leaf_first,
+              const std::vector<unsigned>& depth, int on_device, const char* who, uint8_t* verdicts, uint8_t* reasons, char* err, size_t err_len) {
     try {
         VPBS_HIP(hipSetDevice(v->ctx->device));
         hipStream_t st = v->ctx->stream;
@@ -1630,5 +1385,96 @@ long vpbs_aggregate_verifier_run_many(vpbs_aggregate_verifier* v, const uint8_t*
         accepted += o[2 * a];
     }
     return accepted;
+}
+
+const u64 VK0_ON_DEVICE = 0;   // the host checks of a Statement need a non-null vk0; the device holds the real one
+}  // namespace
+
+namespace vpbs {
+unsigned aggregator_levels(const vpbs_aggregator* a) { return (unsigned)a->levels.size(); }
+unsigned aggregator_device_witness(const vpbs_aggregator* a) { return a->max_nodes; }
+size_t aggregator_max_bytes(const vpbs_aggregator* a) {
+    size_t most = 0;
+    for (const Level& L : a->levels) most = std::max(most, 8 * ((size_t)L.n_wires * 64 + ((size_t)1 << 17)) + 8 * L.n_pi);
+    return most;
+}
+void aggregate_verifier_shape(const vpbs_aggregate_verifier* v, AggregateVerifierShape* out) {
+    *out = AggregateVerifierShape{v->ctx, v->N, v->K, v->n_lwe, v->levels, v->max_leaves, v->max_aggregates};
+}
+}  // namespace vpbs
+
+extern "C" {
+int vpbs_aggregate_verifier_roots_many(vpbs_aggregate_verifier* v, size_t n_agg, const size_t* leaf_first, const uint64_t* testvs, size_t n_testv,
+                                       const uint32_t* testv_of, const uint64_t* cts, const uint64_t* out_cts, const uint64_t* key_hashes,
+                                       size_t n_keys, const uint32_t* key_of, int on_device, uint64_t* out, uint8_t* raw_bad, char* err,
+                                       size_t err_len) {
+    report(err, err_len, "");
+    const char* who = "vpbs_aggregate_verifier_roots_many";
+    if (!v || !out || !raw_bad) return report(err, err_len, std::string(who) + ": null argument"), VPBS_ERR_INVALID;
+    std::lock_guard<std::mutex> lock(v->mu);
+    const Statement s{v->N, v->K, v->n_lwe, &VK0_ON_DEVICE, leaf_first && n_agg ? leaf_first[n_agg] : 0, testvs, n_testv, testv_of, cts, out_cts,
+                      key_hashes, n_keys, key_of};
+    std::string msg;
+    std::vector<unsigned> depth;
+    if (!many_args_ok(v, s, n_agg, leaf_first, who, &depth, &msg)) return report(err, err_len, msg), VPBS_ERR_INVALID;
+    return roots_core(v, s, n_agg, leaf_first, depth, on_device, who, out, raw_bad, err, err_len);
+}
+
+long vpbs_aggregate_verifier_run_many(vpbs_aggregate_verifier* v, const uint8_t* bytes, const size_t* offsets, size_t n_agg, const size_t* leaf_first,
+                                      const uint64_t* testvs, size_t n_testv, const uint32_t* testv_of, const uint64_t* cts, const uint64_t* out_cts,
+                                      const uint64_t* key_hashes, size_t n_keys, const uint32_t* key_of, int on_device, uint8_t* verdicts,
+                                      uint8_t* reasons, char* err, size_t err_len) {
+    report(err, err_len, "");
+    const char* who = "vpbs_aggregate_verifier_run_many";
+    if (!v || !bytes || !offsets || !verdicts) return report(err, err_len, std::string(who) + ": null argument"), VPBS_ERR_INVALID;
+    std::lock_guard<std::mutex> lock(v->mu);
+    const Statement s{v->N, v->K, v->n_lwe, &VK0_ON_DEVICE, leaf_first && n_agg ? leaf_first[n_agg] : 0, testvs, n_testv, testv_of, cts, out_cts,
+                      key_hashes, n_keys, key_of};
+    std::string msg;
+    std::vector<unsigned> depth;
+    if (!many_args_ok(v, s, n_agg, leaf_first, who, &depth, &msg)) return report(err, err_len, msg), VPBS_ERR_INVALID;
+    for (size_t a = 0; a < n_agg; ++a)
+        if (offsets[a + 1] < offsets[a]) return report(err, err_len, std::string(who) + ": offsets decrease at aggregate " + std::to_string(a)), VPBS_ERR_INVALID;
+    return run_core(v, s, bytes, offsets, n_agg, leaf_first, depth, on_device, who, verdicts, reasons, err, err_len);
+}
+
+// ---- one tree: the same cores behind the single entry points' own refusals ----
+int vpbs_aggregate_verifier_root(vpbs_aggregate_verifier* v, size_t count, const uint64_t* testvs, size_t n_testv, const uint32_t* testv_of,
+                                 const uint64_t* cts, const uint64_t* out_cts, const uint64_t* key_hashes, size_t n_keys, const uint32_t* key_of,
+                                 int on_device, uint64_t out[4], char* err, size_t err_len) {
+    report(err, err_len, "");
+    const char* who = "vpbs_aggregate_verifier_root";
+    if (!v || !out) return report(err, err_len, std::string(who) + ": null argument"), VPBS_ERR_INVALID;
+    std::lock_guard<std::mutex> lock(v->mu);
+    const Statement s{v->N, v->K, v->n_lwe, &VK0_ON_DEVICE, count, testvs, n_testv, testv_of, cts, out_cts, key_hashes, n_keys, key_of};
+    std::string msg;
+    if (!verifier_args_ok(v, s, who, &msg)) return report(err, err_len, msg), VPBS_ERR_INVALID;
+    const size_t leaf_first[2] = {0, count};
+    u64 root[4];
+    uint8_t raw_bad = 0;
+    const int rc = roots_core(v, s, 1, leaf_first, {depth_of(count)}, on_device, who, root, &raw_bad, err, err_len);
+    if (rc != VPBS_OK) return rc;
+    if (raw_bad) return 1;
+    std::memcpy(out, root, 32);
+    return VPBS_OK;
+}
+
+int vpbs_aggregate_verifier_run(vpbs_aggregate_verifier* v, const uint8_t* bytes, size_t len, size_t count, const uint64_t* testvs, size_t n_testv,
+                                const uint32_t* testv_of, const uint64_t* cts, const uint64_t* out_cts, const uint64_t* key_hashes, size_t n_keys,
+                                const uint32_t* key_of, int on_device, int* reason, char* err, size_t err_len) {
+    report(err, err_len, "");
+    const char* who = "vpbs_aggregate_verifier_run";
+    if (reason) *reason = VPBS_AGG_MALFORMED;
+    if (!v || !bytes) return report(err, err_len, std::string(who) + ": null argument"), VPBS_ERR_INVALID;
+    std::lock_guard<std::mutex> lock(v->mu);
+    const Statement s{v->N, v->K, v->n_lwe, &VK0_ON_DEVICE, count, testvs, n_testv, testv_of, cts, out_cts, key_hashes, n_keys, key_of};
+    std::string msg;
+    if (!verifier_args_ok(v, s, who, &msg)) return report(err, err_len, msg), VPBS_ERR_INVALID;
+    const size_t leaf_first[2] = {0, count}, offsets[2] = {0, len};
+    uint8_t verdict = 0, why = VPBS_AGG_MALFORMED;
+    const long rc = run_core(v, s, bytes, offsets, 1, leaf_first, {depth_of(count)}, on_device, who, &verdict, &why, err, err_len);
+    if (rc < 0) return (int)rc;
+    if (reason) *reason = why;
+    return verdict;
 }
 }  // extern "C"

@@ -127,10 +127,6 @@ void pbs_verify_abandon(PbsVerifyCore* c, const DeviceError& e);
 PbsVerifyCore* pbs_verifier_core(vpbs_pbs_verifier* v);
 const uint64_t* pbs_verifier_key_table(const vpbs_pbs_verifier* v);
 
-// vp_lwe_chain alone, queued on `stream` (a hipStream_t), for the aggregate verifier (aggregate.hip): the ends [count][4] of the LWE hash
-// chains of d_ct [count][n_lwe + 1], one 16-lane group per ciphertext.  Throws vpbs::DeviceError for a failed launch.
-void lwe_chain_enqueue(void* stream, const uint64_t* d_ct, unsigned n_lwe, size_t count, uint64_t* d_out);
-
 // ---- aggregation (aggregate.hip), for the program calls that end in one aggregate per instance ----
 unsigned aggregator_levels(const vpbs_aggregator* a);     // up to 2^levels leaves
 unsigned aggregator_device_witness(const vpbs_aggregator* a);   // max_nodes of vpbs_aggregator_set_device_witness (0: the host path)

@@ -125,12 +125,6 @@ __global__ __launch_bounds__(256) void vp_result(const u32* __restrict__ flags, 
 }  // namespace
 
 namespace vpbs {
-void lwe_chain_enqueue(void* stream, const uint64_t* d_ct, unsigned n_lwe, size_t count, uint64_t* d_out) {
-    if (count == 0) return;
-    vp_lwe_chain<<<(u32)count, 16, 0, static_cast<hipStream_t>(stream)>>>(d_ct, n_lwe, d_out);
-    VPBS_HIP(hipGetLastError());
-}
-
 // What both objects are built on: the batch verifier of the proofs, the statement's shared words, the per-run buffers of max_batch proofs
 // and the staging area of an object that takes host arrays.
 struct PbsVerifyCore {
