@@ -15,10 +15,17 @@ P = 0xFFFFFFFF00000001
 POW_ANY = 0xFFFFFFFFFFFFFFFF
 U64P = C.POINTER(C.c_uint64)
 U32P = C.POINTER(C.c_uint32)
+U8P = C.POINTER(C.c_uint8)
+SZP = C.POINTER(C.c_size_t)
 
 
 class VpbsError(RuntimeError):
-    pass
+    """status=: the library's status code, kept as .status where the caller is meant to tell the failures apart"""
+
+    def __init__(self, *args, status=None):
+        super().__init__(*args)
+        if status is not None:
+            self.status = status
 
 
 ERR_WITNESS = -6   # VPBS_ERR_WITNESS
@@ -182,271 +189,271 @@ class CommC(C.Structure):
 
 
 # every symbol include/vpbs_prover.h declares: name -> (restype, argtypes)
-_vp, _sz, _ui, _u64, _i = C.c_void_p, C.c_size_t, C.c_uint, C.c_uint64, C.c_int
+_VP, _SZ, _UI, _U64, _I = C.c_void_p, C.c_size_t, C.c_uint, C.c_uint64, C.c_int
 SIGNATURES = {
-    "vpbs_ctx_create": (_i, [_i, _ui, _ui, _ui, C.POINTER(_vp)]),
-    "vpbs_ctx_destroy": (None, [_vp]),
-    "vpbs_last_error": (C.c_char_p, [_vp]),
-    "vpbs_ctx_synchronize": (_i, [_vp]),
-    "vpbs_k_poseidon_host": (_i, [U64P, _sz]),
-    "vpbs_k_clock_probe": (_i, [_vp, C.POINTER(C.c_double)]),
-    "vpbs_ctx_set_gate_lanes": (_i, [_vp, _ui]),
-    "vpbs_ctx_stream": (_vp, [_vp]),
+    "vpbs_ctx_create": (_I, [_I, _UI, _UI, _UI, C.POINTER(_VP)]),
+    "vpbs_ctx_destroy": (None, [_VP]),
+    "vpbs_last_error": (C.c_char_p, [_VP]),
+    "vpbs_ctx_synchronize": (_I, [_VP]),
+    "vpbs_k_poseidon_host": (_I, [U64P, _SZ]),
+    "vpbs_k_clock_probe": (_I, [_VP, C.POINTER(C.c_double)]),
+    "vpbs_ctx_set_gate_lanes": (_I, [_VP, _UI]),
+    "vpbs_ctx_stream": (_VP, [_VP]),
     "vpbs_compat_default": (None, [C.POINTER(CompatC)]),
-    "vpbs_ctx_set_compat": (_i, [_vp, C.POINTER(CompatC)]),
-    "vpbs_ctx_get_compat": (_i, [_vp, C.POINTER(CompatC)]),
-    "vpbs_ctx_set_option": (_i, [_vp, _i, _u64]),
-    "vpbs_ctx_get_option": (_i, [_vp, _i, U64P]),
-    "vpbs_host_set_poseidon_x8": (_i, [_i]),
-    "vpbs_host_set_cpu_budget": (_i, [_ui]),
-    "vpbs_host_cpu_budget": (_ui, []),
-    "vpbs_hash_pad": (None, [U64P, _sz, U64P]),
-    "vpbs_circuit_digest": (_i, [C.POINTER(CompatC), U64P, _sz, _ui, U64P]),
-    "vpbs_ctx_rate_bits": (_ui, [_vp]),
-    "vpbs_ctx_cap_height": (_ui, [_vp]),
-    "vpbs_commit_values": (_i, [_vp, U64P, _ui, _ui, C.POINTER(_vp), U64P]),
-    "vpbs_commit_coeffs": (_i, [_vp, U64P, _ui, _ui, C.POINTER(_vp), U64P]),
-    "vpbs_commit_values_dev": (_i, [_vp, _vp, _ui, _ui, C.POINTER(_vp), U64P]),
-    "vpbs_commit_coeffs_dev": (_i, [_vp, _vp, _ui, _ui, C.POINTER(_vp), U64P]),
-    "vpbs_commit_sharded_dev": (_i, [_vp, _vp, _i, _ui, _ui, _ui, _ui, C.POINTER(_vp), U64P]),
-    "vpbs_batch_free": (None, [_vp]),
-    "vpbs_batch_ncols": (_ui, [_vp]),
-    "vpbs_batch_log_n": (_ui, [_vp]),
-    "vpbs_batch_cap": (_i, [_vp, U64P]),
-    "vpbs_batch_coeffs": (_i, [_vp, U64P]),
-    "vpbs_batch_lde_rows": (_i, [_vp, _sz, _sz, _sz, U64P]),
-    "vpbs_batch_eval_ext": (_i, [_vp, U64P, U64P]),
-    "vpbs_batch_open": (_i, [_vp, _sz, U64P, U64P]),
+    "vpbs_ctx_set_compat": (_I, [_VP, C.POINTER(CompatC)]),
+    "vpbs_ctx_get_compat": (_I, [_VP, C.POINTER(CompatC)]),
+    "vpbs_ctx_set_option": (_I, [_VP, _I, _U64]),
+    "vpbs_ctx_get_option": (_I, [_VP, _I, U64P]),
+    "vpbs_host_set_poseidon_x8": (_I, [_I]),
+    "vpbs_host_set_cpu_budget": (_I, [_UI]),
+    "vpbs_host_cpu_budget": (_UI, []),
+    "vpbs_hash_pad": (None, [U64P, _SZ, U64P]),
+    "vpbs_circuit_digest": (_I, [C.POINTER(CompatC), U64P, _SZ, _UI, U64P]),
+    "vpbs_ctx_rate_bits": (_UI, [_VP]),
+    "vpbs_ctx_cap_height": (_UI, [_VP]),
+    "vpbs_commit_values": (_I, [_VP, U64P, _UI, _UI, C.POINTER(_VP), U64P]),
+    "vpbs_commit_coeffs": (_I, [_VP, U64P, _UI, _UI, C.POINTER(_VP), U64P]),
+    "vpbs_commit_values_dev": (_I, [_VP, _VP, _UI, _UI, C.POINTER(_VP), U64P]),
+    "vpbs_commit_coeffs_dev": (_I, [_VP, _VP, _UI, _UI, C.POINTER(_VP), U64P]),
+    "vpbs_commit_sharded_dev": (_I, [_VP, _VP, _I, _UI, _UI, _UI, _UI, C.POINTER(_VP), U64P]),
+    "vpbs_batch_free": (None, [_VP]),
+    "vpbs_batch_ncols": (_UI, [_VP]),
+    "vpbs_batch_log_n": (_UI, [_VP]),
+    "vpbs_batch_cap": (_I, [_VP, U64P]),
+    "vpbs_batch_coeffs": (_I, [_VP, U64P]),
+    "vpbs_batch_lde_rows": (_I, [_VP, _SZ, _SZ, _SZ, U64P]),
+    "vpbs_batch_eval_ext": (_I, [_VP, U64P, U64P]),
+    "vpbs_batch_open": (_I, [_VP, _SZ, U64P, U64P]),
     "vpbs_challenger_init": (None, [C.POINTER(ChallengerStateC)]),
-    "vpbs_challenger_observe": (None, [C.POINTER(ChallengerStateC), U64P, _sz]),
-    "vpbs_challenger_get": (_u64, [C.POINTER(ChallengerStateC)]),
-    "vpbs_hash_no_pad": (None, [U64P, _sz, U64P]),
-    "vpbs_hash_chain": (_i, [U64P, _sz, _sz, U64P, U64P]),
-    "vpbs_hash_chain_links": (_i, [U64P, C.POINTER(U64P), _sz, _sz, U64P]),
-    "vpbs_fri_params_standard": (None, [_ui, C.POINTER(FriParams)]),
-    "vpbs_fri_proof_words": (_sz, [C.POINTER(FriParams), _ui, C.POINTER(_sz), _sz]),
-    "vpbs_fri_prove": (_i, [_vp, C.POINTER(_vp), _sz, C.POINTER(FriInstanceC), C.POINTER(FriParams),
-                            C.POINTER(ChallengerStateC), _u64, U64P]),
-    "vpbs_step_sizes_get": (_i, [_vp, C.POINTER(StepInputsC), C.POINTER(StepSizesC)]),
-    "vpbs_prove_step": (_i, [_vp, C.POINTER(StepInputsC), U64P, U64P, U64P, C.POINTER(ChallengerStateC), U64P]),
-    "vpbs_prove_step_sharded": (_i, [_vp, C.POINTER(StepInputsC), C.POINTER(CommC), U64P, U64P, U64P, C.POINTER(ChallengerStateC), U64P]),
-    "vpbs_rccl_available": (_i, []),
-    "vpbs_rccl_unique_id": (_i, [C.POINTER(C.c_uint8)]),
-    "vpbs_comm_rccl_create": (_i, [_vp, C.POINTER(C.c_uint8), _ui, _ui, _sz, C.POINTER(CommC)]),
+    "vpbs_challenger_observe": (None, [C.POINTER(ChallengerStateC), U64P, _SZ]),
+    "vpbs_challenger_get": (_U64, [C.POINTER(ChallengerStateC)]),
+    "vpbs_hash_no_pad": (None, [U64P, _SZ, U64P]),
+    "vpbs_hash_chain": (_I, [U64P, _SZ, _SZ, U64P, U64P]),
+    "vpbs_hash_chain_links": (_I, [U64P, C.POINTER(U64P), _SZ, _SZ, U64P]),
+    "vpbs_fri_params_standard": (None, [_UI, C.POINTER(FriParams)]),
+    "vpbs_fri_proof_words": (_SZ, [C.POINTER(FriParams), _UI, C.POINTER(_SZ), _SZ]),
+    "vpbs_fri_prove": (_I, [_VP, C.POINTER(_VP), _SZ, C.POINTER(FriInstanceC), C.POINTER(FriParams),
+                            C.POINTER(ChallengerStateC), _U64, U64P]),
+    "vpbs_step_sizes_get": (_I, [_VP, C.POINTER(StepInputsC), C.POINTER(StepSizesC)]),
+    "vpbs_prove_step": (_I, [_VP, C.POINTER(StepInputsC), U64P, U64P, U64P, C.POINTER(ChallengerStateC), U64P]),
+    "vpbs_prove_step_sharded": (_I, [_VP, C.POINTER(StepInputsC), C.POINTER(CommC), U64P, U64P, U64P, C.POINTER(ChallengerStateC), U64P]),
+    "vpbs_rccl_available": (_I, []),
+    "vpbs_rccl_unique_id": (_I, [C.POINTER(C.c_uint8)]),
+    "vpbs_comm_rccl_create": (_I, [_VP, C.POINTER(C.c_uint8), _UI, _UI, _SZ, C.POINTER(CommC)]),
     "vpbs_comm_rccl_destroy": (None, [C.POINTER(CommC)]),
-    "vpbs_step_proof_to_bytes": (C.c_long, [_vp, C.POINTER(StepInputsC), _ui, U64P, U64P, U64P, C.POINTER(C.c_uint8), _sz]),
-    "vpbs_partial_products": (_i, [_vp, _vp, _vp, _i, _ui, _ui, U64P, U64P, _ui, _ui, _vp]),
-    "vpbs_quotient_permutation": (_i, [_vp, _vp, _ui, _vp, _vp, _ui, U64P, U64P, U64P, _ui, _ui, _vp, _vp, _i]),
-    "vpbs_gate_default_params": (_i, [C.POINTER(GateC)]),
-    "vpbs_gates_layout": (_i, [C.POINTER(GateC), _ui, _ui, C.POINTER(_ui), C.POINTER(_ui)]),
-    "vpbs_gate_id": (_i, [C.POINTER(GateC), C.c_char_p, _sz]),
-    "vpbs_gate_terms": (_i, [_vp, _vp, _vp, C.POINTER(GateC), _ui, _ui, U64P, U64P, _ui, _vp]),
-    "vpbs_gate_terms_at": (_i, [C.POINTER(GateC), _ui, _ui, U64P, _ui, U64P, _ui, U64P, U64P, _ui, U64P]),
-    "vpbs_gate_fill_row": (_i, [C.POINTER(GateC), U64P, U64P]),
-    "vpbs_selector_columns": (_i, [C.POINTER(CircuitC), U64P]),
-    "vpbs_sigma_values": (_i, [C.POINTER(CircuitC), U64P]),
-    "vpbs_generate_witness": (_i, [C.POINTER(CircuitC), U32P, U64P, _sz, U64P, C.c_char_p, _sz]),
-    "vpbs_witness_plan_create": (_i, [C.POINTER(CircuitC), U32P, _sz, C.POINTER(C.c_void_p), C.c_char_p, _sz]),
-    "vpbs_witness_plan_run": (_i, [C.c_void_p, U64P, C.c_uint, U64P, C.c_char_p, _sz]),
-    "vpbs_step_proof_from_bytes": (C.c_long, [C.POINTER(VerifyInputsC), C.POINTER(C.c_uint8), _sz, U64P, U64P, U64P, U64P, _sz]),
+    "vpbs_step_proof_to_bytes": (C.c_long, [_VP, C.POINTER(StepInputsC), _UI, U64P, U64P, U64P, C.POINTER(C.c_uint8), _SZ]),
+    "vpbs_partial_products": (_I, [_VP, _VP, _VP, _I, _UI, _UI, U64P, U64P, _UI, _UI, _VP]),
+    "vpbs_quotient_permutation": (_I, [_VP, _VP, _UI, _VP, _VP, _UI, U64P, U64P, U64P, _UI, _UI, _VP, _VP, _I]),
+    "vpbs_gate_default_params": (_I, [C.POINTER(GateC)]),
+    "vpbs_gates_layout": (_I, [C.POINTER(GateC), _UI, _UI, C.POINTER(_UI), C.POINTER(_UI)]),
+    "vpbs_gate_id": (_I, [C.POINTER(GateC), C.c_char_p, _SZ]),
+    "vpbs_gate_terms": (_I, [_VP, _VP, _VP, C.POINTER(GateC), _UI, _UI, U64P, U64P, _UI, _VP]),
+    "vpbs_gate_terms_at": (_I, [C.POINTER(GateC), _UI, _UI, U64P, _UI, U64P, _UI, U64P, U64P, _UI, U64P]),
+    "vpbs_gate_fill_row": (_I, [C.POINTER(GateC), U64P, U64P]),
+    "vpbs_selector_columns": (_I, [C.POINTER(CircuitC), U64P]),
+    "vpbs_sigma_values": (_I, [C.POINTER(CircuitC), U64P]),
+    "vpbs_generate_witness": (_I, [C.POINTER(CircuitC), U32P, U64P, _SZ, U64P, C.c_char_p, _SZ]),
+    "vpbs_witness_plan_create": (_I, [C.POINTER(CircuitC), U32P, _SZ, C.POINTER(C.c_void_p), C.c_char_p, _SZ]),
+    "vpbs_witness_plan_run": (_I, [C.c_void_p, U64P, C.c_uint, U64P, C.c_char_p, _SZ]),
+    "vpbs_step_proof_from_bytes": (C.c_long, [C.POINTER(VerifyInputsC), C.POINTER(C.c_uint8), _SZ, U64P, U64P, U64P, U64P, _SZ]),
     "vpbs_witness_plan_free": (None, [C.c_void_p]),
-    "vpbs_witness_plan_split": (_i, [C.c_void_p, C.POINTER(C.c_uint8), C.c_char_p, _sz]),
-    "vpbs_witness_plan_run_early": (_i, [C.c_void_p, U64P, C.c_uint, U64P, C.POINTER(C.c_void_p), C.c_char_p, _sz]),
-    "vpbs_witness_plan_run_early_recycled": (_i, [C.c_void_p, U64P, C.c_uint, U64P, C.POINTER(C.c_void_p), C.c_char_p, _sz]),
-    "vpbs_witness_plan_run_late": (_i, [C.c_void_p, C.c_void_p, U64P, U64P, C.c_char_p, _sz]),
+    "vpbs_witness_plan_split": (_I, [C.c_void_p, C.POINTER(C.c_uint8), C.c_char_p, _SZ]),
+    "vpbs_witness_plan_run_early": (_I, [C.c_void_p, U64P, C.c_uint, U64P, C.POINTER(C.c_void_p), C.c_char_p, _SZ]),
+    "vpbs_witness_plan_run_early_recycled": (_I, [C.c_void_p, U64P, C.c_uint, U64P, C.POINTER(C.c_void_p), C.c_char_p, _SZ]),
+    "vpbs_witness_plan_run_late": (_I, [C.c_void_p, C.c_void_p, U64P, U64P, C.c_char_p, _SZ]),
     "vpbs_witness_state_free": (None, [C.c_void_p]),
-    "vpbs_witness_plan_run_late_packed": (_i, [C.c_void_p, C.c_void_p, U64P, U64P, C.c_char_p, _sz]),
-    "vpbs_witness_plan_late_count": (_sz, [C.c_void_p]),
-    "vpbs_witness_plan_late_stages": (_ui, [C.c_void_p]),
-    "vpbs_witness_plan_run_late_stage": (_i, [C.c_void_p, C.c_void_p, _ui, U64P, U64P, C.c_char_p, _sz]),
-    "vpbs_witness_plan_late_input_count": (_sz, [C.c_void_p]),
-    "vpbs_witness_plan_late_input_positions": (_i, [C.c_void_p, U32P]),
-    "vpbs_witness_state_from_late_inputs": (_i, [C.c_void_p, U64P, C.POINTER(C.c_void_p)]),
-    "vpbs_witness_plan_late_positions": (_i, [C.c_void_p, U32P]),
-    "vpbs_witness_plan_stats": (_i, [C.c_void_p, U64P]),
-    "vpbs_witness_device_create": (_i, [C.c_void_p, C.c_void_p, C.c_uint, C.POINTER(C.c_void_p)]),
-    "vpbs_witness_device_create_early": (_i, [C.c_void_p, C.c_void_p, C.c_uint, C.POINTER(C.c_void_p)]),
-    "vpbs_witness_device_read_late_inputs": (_i, [C.c_void_p, C.c_uint, U64P]),
-    "vpbs_witness_device_run": (_i, [C.c_void_p, U64P, C.c_uint]),
-    "vpbs_witness_device_wires": (_i, [C.c_void_p, C.c_uint, C.c_void_p]),
-    "vpbs_witness_device_read": (_i, [C.c_void_p, C.c_uint, U32P, _sz, U64P]),
+    "vpbs_witness_plan_run_late_packed": (_I, [C.c_void_p, C.c_void_p, U64P, U64P, C.c_char_p, _SZ]),
+    "vpbs_witness_plan_late_count": (_SZ, [C.c_void_p]),
+    "vpbs_witness_plan_late_stages": (_UI, [C.c_void_p]),
+    "vpbs_witness_plan_run_late_stage": (_I, [C.c_void_p, C.c_void_p, _UI, U64P, U64P, C.c_char_p, _SZ]),
+    "vpbs_witness_plan_late_input_count": (_SZ, [C.c_void_p]),
+    "vpbs_witness_plan_late_input_positions": (_I, [C.c_void_p, U32P]),
+    "vpbs_witness_state_from_late_inputs": (_I, [C.c_void_p, U64P, C.POINTER(C.c_void_p)]),
+    "vpbs_witness_plan_late_positions": (_I, [C.c_void_p, U32P]),
+    "vpbs_witness_plan_stats": (_I, [C.c_void_p, U64P]),
+    "vpbs_witness_device_create": (_I, [C.c_void_p, C.c_void_p, C.c_uint, C.POINTER(C.c_void_p)]),
+    "vpbs_witness_device_create_early": (_I, [C.c_void_p, C.c_void_p, C.c_uint, C.POINTER(C.c_void_p)]),
+    "vpbs_witness_device_read_late_inputs": (_I, [C.c_void_p, C.c_uint, U64P]),
+    "vpbs_witness_device_run": (_I, [C.c_void_p, U64P, C.c_uint]),
+    "vpbs_witness_device_wires": (_I, [C.c_void_p, C.c_uint, C.c_void_p]),
+    "vpbs_witness_device_read": (_I, [C.c_void_p, C.c_uint, U32P, _SZ, U64P]),
     "vpbs_witness_device_free": (None, [C.c_void_p]),
-    "vpbs_check_witness": (_i, [C.POINTER(CircuitC), U64P, U64P, C.c_char_p, _sz]),
-    "vpbs_verify_step": (_i, [C.POINTER(VerifyInputsC), U64P, U64P, U64P]),
-    "vpbs_proof_verifier_create": (_i, [_vp, C.POINTER(VerifyInputsC), _sz, _sz, C.POINTER(_vp), C.c_char_p, _sz]),
-    "vpbs_proof_verifier_run": (C.c_long, [_vp, C.POINTER(C.c_uint8), C.POINTER(_sz), _sz, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]),
-    "vpbs_proof_verifier_free": (None, [_vp]),
-    "vpbs_ivc_create": (_i, [_vp, C.POINTER(IvcCircuitC), C.POINTER(IvcCircuitC), _ui, _ui, _sz, C.POINTER(CommC), C.POINTER(_vp), C.c_char_p, _sz]),
-    "vpbs_ivc_free": (None, [_vp]),
-    "vpbs_ivc_verifier_data": (_i, [_vp, U64P, U64P]),
-    "vpbs_ivc_set_step_callback": (_i, [_vp, IVC_STEP_FN, _vp]),
-    "vpbs_ivc_set_device_witness": (_i, [_vp, _ui, _ui, _ui, _i]),
-    "vpbs_ivc_last_error": (C.c_char_p, [_vp]),
-    "vpbs_prove_step_sharded_fail": (_i, [_vp, C.POINTER(StepInputsC), C.POINTER(CommC), _i]),
-    "vpbs_comm_allgather_checked": (_i, [C.POINTER(CommC), U64P, _sz, U64P, _i]),
-    "vpbs_host_set_late_threads": (_i, [_ui]),
-    "vpbs_host_set_early_threads": (_i, [_ui]),
-    "vpbs_host_set_blocking_sync": (_i, [_i]),
-    "vpbs_host_blocking_sync": (_i, []),
-    "vpbs_host_set_sync_word": (_i, [_i]),
-    "vpbs_witness_device_has_late": (_i, [_vp]),
-    "vpbs_witness_device_run_late": (_i, [C.c_void_p, C.c_uint, U64P]),
-    "vpbs_ctx_device": (_i, [_vp]),
-    "vpbs_witness_checker_create": (_i, [_vp, C.POINTER(CircuitC), C.POINTER(_vp), C.c_char_p, _sz]),
-    "vpbs_witness_checker_free": (None, [_vp]),
-    "vpbs_witness_checker_run": (_i, [_vp, _vp, _i, U64P, C.c_char_p, _sz]),
-    "vpbs_prove_step_checked": (_i, [_vp, _vp, C.POINTER(StepInputsC), U64P, U64P, U64P, C.POINTER(ChallengerStateC), U64P]),
-    "vpbs_ivc_set_check_witness": (_i, [_vp, _i]),
-    "vpbs_ivc_witness_checks": (_i, [_vp, U64P]),
-    "vpbs_ivc_prove_pbs": (C.c_long, [_vp, U64P, U64P, U64P, U64P, _ui, _ui, C.POINTER(C.c_uint8), _sz, C.POINTER(IvcTimingC), C.c_char_p, _sz]),
-    "vpbs_verify_pbs": (_i, [C.POINTER(VerifyPbsInputsC), C.POINTER(C.c_uint8), _sz, C.c_char_p, _sz]),
-    "vpbs_verify_pbs_prefix": (_i, [C.POINTER(VerifyPbsInputsC), C.POINTER(C.c_uint8), _sz, C.POINTER(_ui), C.c_char_p, _sz]),
-    "vpbs_ivc_set_checkpoint": (_i, [_vp, _ui, IVC_CHECKPOINT_FN, _vp]),
-    "vpbs_ivc_resume_pbs": (C.c_long, [_vp, U64P, U64P, U64P, U64P, _ui, C.POINTER(C.c_uint8), _sz, _ui, C.POINTER(C.c_uint8), _sz,
-                                       C.POINTER(IvcTimingC), C.c_char_p, _sz]),
-    "vpbs_pbs_key_hash": (_i, [U64P, U64P, _ui, _sz, U64P]),
-    "vpbs_pbs_reason_text": (C.c_char_p, [_i]),
-    "vpbs_pbs_verifier_create": (_i, [_vp, C.POINTER(VerifyPbsInputsC), U64P, _sz, C.POINTER(_vp), C.c_char_p, _sz]),
-    "vpbs_pbs_verifier_run": (C.c_long, [_vp, C.POINTER(C.c_uint8), C.POINTER(_sz), _sz, U64P, _i, U64P, U64P, C.POINTER(C.c_uint8),
+    "vpbs_check_witness": (_I, [C.POINTER(CircuitC), U64P, U64P, C.c_char_p, _SZ]),
+    "vpbs_verify_step": (_I, [C.POINTER(VerifyInputsC), U64P, U64P, U64P]),
+    "vpbs_proof_verifier_create": (_I, [_VP, C.POINTER(VerifyInputsC), _SZ, _SZ, C.POINTER(_VP), C.c_char_p, _SZ]),
+    "vpbs_proof_verifier_run": (C.c_long, [_VP, C.POINTER(C.c_uint8), C.POINTER(_SZ), _SZ, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]),
+    "vpbs_proof_verifier_free": (None, [_VP]),
+    "vpbs_ivc_create": (_I, [_VP, C.POINTER(IvcCircuitC), C.POINTER(IvcCircuitC), _UI, _UI, _SZ, C.POINTER(CommC), C.POINTER(_VP), C.c_char_p, _SZ]),
+    "vpbs_ivc_free": (None, [_VP]),
+    "vpbs_ivc_verifier_data": (_I, [_VP, U64P, U64P]),
+    "vpbs_ivc_set_step_callback": (_I, [_VP, IVC_STEP_FN, _VP]),
+    "vpbs_ivc_set_device_witness": (_I, [_VP, _UI, _UI, _UI, _I]),
+    "vpbs_ivc_last_error": (C.c_char_p, [_VP]),
+    "vpbs_prove_step_sharded_fail": (_I, [_VP, C.POINTER(StepInputsC), C.POINTER(CommC), _I]),
+    "vpbs_comm_allgather_checked": (_I, [C.POINTER(CommC), U64P, _SZ, U64P, _I]),
+    "vpbs_host_set_late_threads": (_I, [_UI]),
+    "vpbs_host_set_early_threads": (_I, [_UI]),
+    "vpbs_host_set_blocking_sync": (_I, [_I]),
+    "vpbs_host_blocking_sync": (_I, []),
+    "vpbs_host_set_sync_word": (_I, [_I]),
+    "vpbs_witness_device_has_late": (_I, [_VP]),
+    "vpbs_witness_device_run_late": (_I, [C.c_void_p, C.c_uint, U64P]),
+    "vpbs_ctx_device": (_I, [_VP]),
+    "vpbs_witness_checker_create": (_I, [_VP, C.POINTER(CircuitC), C.POINTER(_VP), C.c_char_p, _SZ]),
+    "vpbs_witness_checker_free": (None, [_VP]),
+    "vpbs_witness_checker_run": (_I, [_VP, _VP, _I, U64P, C.c_char_p, _SZ]),
+    "vpbs_prove_step_checked": (_I, [_VP, _VP, C.POINTER(StepInputsC), U64P, U64P, U64P, C.POINTER(ChallengerStateC), U64P]),
+    "vpbs_ivc_set_check_witness": (_I, [_VP, _I]),
+    "vpbs_ivc_witness_checks": (_I, [_VP, U64P]),
+    "vpbs_ivc_prove_pbs": (C.c_long, [_VP, U64P, U64P, U64P, U64P, _UI, _UI, C.POINTER(C.c_uint8), _SZ, C.POINTER(IvcTimingC), C.c_char_p, _SZ]),
+    "vpbs_verify_pbs": (_I, [C.POINTER(VerifyPbsInputsC), C.POINTER(C.c_uint8), _SZ, C.c_char_p, _SZ]),
+    "vpbs_verify_pbs_prefix": (_I, [C.POINTER(VerifyPbsInputsC), C.POINTER(C.c_uint8), _SZ, C.POINTER(_UI), C.c_char_p, _SZ]),
+    "vpbs_ivc_set_checkpoint": (_I, [_VP, _UI, IVC_CHECKPOINT_FN, _VP]),
+    "vpbs_ivc_resume_pbs": (C.c_long, [_VP, U64P, U64P, U64P, U64P, _UI, C.POINTER(C.c_uint8), _SZ, _UI, C.POINTER(C.c_uint8), _SZ,
+                                       C.POINTER(IvcTimingC), C.c_char_p, _SZ]),
+    "vpbs_pbs_key_hash": (_I, [U64P, U64P, _UI, _SZ, U64P]),
+    "vpbs_pbs_reason_text": (C.c_char_p, [_I]),
+    "vpbs_pbs_verifier_create": (_I, [_VP, C.POINTER(VerifyPbsInputsC), U64P, _SZ, C.POINTER(_VP), C.c_char_p, _SZ]),
+    "vpbs_pbs_verifier_run": (C.c_long, [_VP, C.POINTER(C.c_uint8), C.POINTER(_SZ), _SZ, U64P, _I, U64P, U64P, C.POINTER(C.c_uint8),
                                          C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]),
-    "vpbs_pbs_verifier_free": (None, [_vp]),
-    "vpbs_ring_verifier_create": (_i, [_vp, C.POINTER(VerifyPbsInputsC), _ui, _sz, C.POINTER(_vp), C.c_char_p, _sz]),
-    "vpbs_ring_verifier_set_key": (_i, [_vp, _ui, U64P]),
-    "vpbs_ring_verifier_clear_key": (_i, [_vp, _ui]),
-    "vpbs_ring_verifier_count": (C.c_long, [_vp]),
-    "vpbs_ring_verifier_run": (C.c_long, [_vp, C.POINTER(C.c_uint8), C.POINTER(_sz), _sz, _vp, U64P, _sz, _vp, U64P, U64P, C.POINTER(C.c_uint8),
-                                          C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.c_char_p, _sz]),
-    "vpbs_ring_verifier_free": (None, [_vp]),
-    "vpbs_blind_rotate_step": (_i, [_vp, C.POINTER(TfheParamsC), _ui, _vp, _vp, _vp, _i, _i, _i, _vp, _i]),
-    "vpbs_pbs_accumulator_chain": (_i, [_vp, C.POINTER(TfheParamsC), _ui, U64P, U64P, U64P, U64P, U64P]),
-    "vpbs_host_alloc": (_vp, [_sz]),
-    "vpbs_host_free": (None, [_vp]),
-    "vpbs_device_alloc": (_i, [_vp, _sz, C.POINTER(_vp)]),
-    "vpbs_device_upload": (_i, [_vp, _vp, U64P, _sz]),
-    "vpbs_device_upload_bg": (_i, [_vp, _vp, _vp, _sz]),
-    "vpbs_device_upload_rows": (_i, [_vp, _vp, _vp, _ui, _sz, _sz, _sz]),
-    "vpbs_witness_plan_late_rows": (_i, [_vp, C.POINTER(_sz)]),
-    "vpbs_device_scatter": (_i, [_vp, _vp, _vp, _vp, _sz, _vp]),
-    "vpbs_device_free": (None, [_vp, _vp]),
-    "vpbs_keygen": (_i, [_vp, C.POINTER(KeygenParamsC), U64P, U64P, U64P, _vp, _vp, _i]),
-    "vpbs_lwe_encrypt": (_i, [C.POINTER(KeygenParamsC), U64P, _u64, _u64, U64P]),
-    "vpbs_testv": (_i, [_ui, _ui, U64P, U64P]),
-    "vpbs_glwe_decrypt": (_i, [_vp, _ui, _ui, U64P, U64P, U64P]),
-    "vpbs_bootstrapper_create": (_i, [_vp, C.POINTER(TfheParamsC), _ui, _vp, _vp, _i, _sz, C.POINTER(_vp), C.c_char_p, _sz]),
-    "vpbs_bootstrapper_run": (C.c_long, [_vp, _vp, _sz, _vp, _i, _vp, _vp, _vp, _i]),
-    "vpbs_bootstrapper_run_from": (C.c_long, [_vp, _vp, _sz, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i]),
-    "vpbs_bootstrapper_free": (None, [_vp]),
-    "vpbs_keyring_create": (_i, [_vp, C.POINTER(TfheParamsC), _ui, _sz, _sz, C.POINTER(_vp), C.c_char_p, _sz]),
-    "vpbs_keyring_add": (_i, [_vp, _vp, _vp, _i, C.POINTER(_ui)]),
-    "vpbs_keyring_remove": (_i, [_vp, _ui]),
-    "vpbs_keyring_count": (_sz, [_vp]),
-    "vpbs_keyring_run": (C.c_long, [_vp, _vp, _sz, _vp, _vp, _i, _vp, _vp, _vp, _i]),
-    "vpbs_keyring_run_from": (C.c_long, [_vp, _vp, _sz, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i]),
-    "vpbs_keyring_free": (None, [_vp]),
-    "vpbs_pbs_prover_create": (_i, [_i, C.POINTER(IvcCircuitC), C.POINTER(IvcCircuitC), C.POINTER(TfheParamsC), _ui, _vp, _vp, _i, _ui, _ui,
-                                    C.POINTER(_vp), C.c_char_p, _sz]),
-    "vpbs_pbs_prover_run": (C.c_long, [_vp, U64P, _sz, U64P, _i, _ui, U64P, U64P, PBS_PROOF_FN, _vp, C.c_char_p, _sz]),
-    "vpbs_pbs_prover_resume": (C.c_long, [_vp, U64P, _sz, U64P, _i, _vp, _vp, _ui, U64P, U64P, PBS_PROOF_FN, _vp, C.c_char_p, _sz]),
-    "vpbs_pbs_prover_key_hash": (_i, [_vp, U64P]),
-    "vpbs_pbs_prover_verifier_data": (_i, [_vp, U64P, U64P]),
-    "vpbs_pbs_prover_set_check_witness": (_i, [_vp, _i]),
-    "vpbs_pbs_prover_witness_checks": (_i, [_vp, U64P]),
-    "vpbs_pbs_prover_set_checkpoint": (_i, [_vp, _ui, PBS_CHECKPOINT_FN, _vp]),
-    "vpbs_pbs_prover_last_run": (_i, [_vp, C.POINTER(PbsRunStatsC)]),
-    "vpbs_pbs_prover_free": (None, [_vp]),
-    "vpbs_ring_prover_create": (_i, [_i, C.POINTER(IvcCircuitC), C.POINTER(IvcCircuitC), C.POINTER(TfheParamsC), _ui, _sz, _ui, _ui, C.POINTER(_vp),
-                                     C.c_char_p, _sz]),
-    "vpbs_ring_prover_add": (_i, [_vp, _vp, _vp, _i, C.POINTER(_ui), C.c_char_p, _sz]),
-    "vpbs_ring_prover_remove": (_i, [_vp, _ui, C.c_char_p, _sz]),
-    "vpbs_ring_prover_key_hash": (_i, [_vp, _ui, U64P]),
-    "vpbs_ring_prover_keyring": (_vp, [_vp]),
-    "vpbs_ring_prover_context": (_vp, [_vp]),
-    "vpbs_ring_prover_run": (C.c_long, [_vp, U64P, _sz, _vp, U64P, _i, _ui, U64P, U64P, PBS_PROOF_FN, _vp, C.c_char_p, _sz]),
-    "vpbs_ring_prover_resume": (C.c_long, [_vp, U64P, _sz, _vp, U64P, _i, _vp, _vp, _ui, U64P, U64P, PBS_PROOF_FN, _vp, C.c_char_p, _sz]),
-    "vpbs_ring_prover_verifier_data": (_i, [_vp, U64P, U64P]),
-    "vpbs_ring_prover_set_check_witness": (_i, [_vp, _i]),
-    "vpbs_ring_prover_witness_checks": (_i, [_vp, U64P]),
-    "vpbs_ring_prover_set_checkpoint": (_i, [_vp, _ui, PBS_CHECKPOINT_FN, _vp]),
-    "vpbs_ring_prover_last_run": (_i, [_vp, C.POINTER(PbsRunStatsC)]),
-    "vpbs_ring_prover_free": (None, [_vp]),
-    "vpbs_program_create": (_i, [_vp, C.POINTER(ProgramDescC), C.POINTER(_vp), C.c_char_p, _sz]),
-    "vpbs_program_levels": (C.c_long, [_vp, C.POINTER(_ui)]),
-    "vpbs_program_run": (C.c_long, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i]),
-    "vpbs_program_run_batch": (C.c_long, [_vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _i]),
-    "vpbs_program_prove": (C.c_long, [_vp, _vp, U64P, U64P, _ui, U64P, U64P, PBS_PROOF_FN, _vp, C.c_char_p, _sz]),
-    "vpbs_program_prove_batch": (C.c_long, [_vp, _vp, U64P, _sz, _vp, U64P, _ui, U64P, U64P, PBS_PROOF_FN, _vp, C.c_char_p, _sz]),
-    "vpbs_program_verify": (C.c_long, [_vp, _vp, U64P, U64P, U64P, C.POINTER(C.c_uint8), C.POINTER(_sz), C.POINTER(C.c_uint8),
+    "vpbs_pbs_verifier_free": (None, [_VP]),
+    "vpbs_ring_verifier_create": (_I, [_VP, C.POINTER(VerifyPbsInputsC), _UI, _SZ, C.POINTER(_VP), C.c_char_p, _SZ]),
+    "vpbs_ring_verifier_set_key": (_I, [_VP, _UI, U64P]),
+    "vpbs_ring_verifier_clear_key": (_I, [_VP, _UI]),
+    "vpbs_ring_verifier_count": (C.c_long, [_VP]),
+    "vpbs_ring_verifier_run": (C.c_long, [_VP, C.POINTER(C.c_uint8), C.POINTER(_SZ), _SZ, _VP, U64P, _SZ, _VP, U64P, U64P, C.POINTER(C.c_uint8),
+                                          C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.c_char_p, _SZ]),
+    "vpbs_ring_verifier_free": (None, [_VP]),
+    "vpbs_blind_rotate_step": (_I, [_VP, C.POINTER(TfheParamsC), _UI, _VP, _VP, _VP, _I, _I, _I, _VP, _I]),
+    "vpbs_pbs_accumulator_chain": (_I, [_VP, C.POINTER(TfheParamsC), _UI, U64P, U64P, U64P, U64P, U64P]),
+    "vpbs_host_alloc": (_VP, [_SZ]),
+    "vpbs_host_free": (None, [_VP]),
+    "vpbs_device_alloc": (_I, [_VP, _SZ, C.POINTER(_VP)]),
+    "vpbs_device_upload": (_I, [_VP, _VP, U64P, _SZ]),
+    "vpbs_device_upload_bg": (_I, [_VP, _VP, _VP, _SZ]),
+    "vpbs_device_upload_rows": (_I, [_VP, _VP, _VP, _UI, _SZ, _SZ, _SZ]),
+    "vpbs_witness_plan_late_rows": (_I, [_VP, C.POINTER(_SZ)]),
+    "vpbs_device_scatter": (_I, [_VP, _VP, _VP, _VP, _SZ, _VP]),
+    "vpbs_device_free": (None, [_VP, _VP]),
+    "vpbs_keygen": (_I, [_VP, C.POINTER(KeygenParamsC), U64P, U64P, U64P, _VP, _VP, _I]),
+    "vpbs_lwe_encrypt": (_I, [C.POINTER(KeygenParamsC), U64P, _U64, _U64, U64P]),
+    "vpbs_testv": (_I, [_UI, _UI, U64P, U64P]),
+    "vpbs_glwe_decrypt": (_I, [_VP, _UI, _UI, U64P, U64P, U64P]),
+    "vpbs_bootstrapper_create": (_I, [_VP, C.POINTER(TfheParamsC), _UI, _VP, _VP, _I, _SZ, C.POINTER(_VP), C.c_char_p, _SZ]),
+    "vpbs_bootstrapper_run": (C.c_long, [_VP, _VP, _SZ, _VP, _I, _VP, _VP, _VP, _I]),
+    "vpbs_bootstrapper_run_from": (C.c_long, [_VP, _VP, _SZ, _VP, _VP, _VP, _I, _VP, _VP, _VP, _I]),
+    "vpbs_bootstrapper_free": (None, [_VP]),
+    "vpbs_keyring_create": (_I, [_VP, C.POINTER(TfheParamsC), _UI, _SZ, _SZ, C.POINTER(_VP), C.c_char_p, _SZ]),
+    "vpbs_keyring_add": (_I, [_VP, _VP, _VP, _I, C.POINTER(_UI)]),
+    "vpbs_keyring_remove": (_I, [_VP, _UI]),
+    "vpbs_keyring_count": (_SZ, [_VP]),
+    "vpbs_keyring_run": (C.c_long, [_VP, _VP, _SZ, _VP, _VP, _I, _VP, _VP, _VP, _I]),
+    "vpbs_keyring_run_from": (C.c_long, [_VP, _VP, _SZ, _VP, _VP, _VP, _VP, _I, _VP, _VP, _VP, _I]),
+    "vpbs_keyring_free": (None, [_VP]),
+    "vpbs_pbs_prover_create": (_I, [_I, C.POINTER(IvcCircuitC), C.POINTER(IvcCircuitC), C.POINTER(TfheParamsC), _UI, _VP, _VP, _I, _UI, _UI,
+                                    C.POINTER(_VP), C.c_char_p, _SZ]),
+    "vpbs_pbs_prover_run": (C.c_long, [_VP, U64P, _SZ, U64P, _I, _UI, U64P, U64P, PBS_PROOF_FN, _VP, C.c_char_p, _SZ]),
+    "vpbs_pbs_prover_resume": (C.c_long, [_VP, U64P, _SZ, U64P, _I, _VP, _VP, _UI, U64P, U64P, PBS_PROOF_FN, _VP, C.c_char_p, _SZ]),
+    "vpbs_pbs_prover_key_hash": (_I, [_VP, U64P]),
+    "vpbs_pbs_prover_verifier_data": (_I, [_VP, U64P, U64P]),
+    "vpbs_pbs_prover_set_check_witness": (_I, [_VP, _I]),
+    "vpbs_pbs_prover_witness_checks": (_I, [_VP, U64P]),
+    "vpbs_pbs_prover_set_checkpoint": (_I, [_VP, _UI, PBS_CHECKPOINT_FN, _VP]),
+    "vpbs_pbs_prover_last_run": (_I, [_VP, C.POINTER(PbsRunStatsC)]),
+    "vpbs_pbs_prover_free": (None, [_VP]),
+    "vpbs_ring_prover_create": (_I, [_I, C.POINTER(IvcCircuitC), C.POINTER(IvcCircuitC), C.POINTER(TfheParamsC), _UI, _SZ, _UI, _UI, C.POINTER(_VP),
+                                     C.c_char_p, _SZ]),
+    "vpbs_ring_prover_add": (_I, [_VP, _VP, _VP, _I, C.POINTER(_UI), C.c_char_p, _SZ]),
+    "vpbs_ring_prover_remove": (_I, [_VP, _UI, C.c_char_p, _SZ]),
+    "vpbs_ring_prover_key_hash": (_I, [_VP, _UI, U64P]),
+    "vpbs_ring_prover_keyring": (_VP, [_VP]),
+    "vpbs_ring_prover_context": (_VP, [_VP]),
+    "vpbs_ring_prover_run": (C.c_long, [_VP, U64P, _SZ, _VP, U64P, _I, _UI, U64P, U64P, PBS_PROOF_FN, _VP, C.c_char_p, _SZ]),
+    "vpbs_ring_prover_resume": (C.c_long, [_VP, U64P, _SZ, _VP, U64P, _I, _VP, _VP, _UI, U64P, U64P, PBS_PROOF_FN, _VP, C.c_char_p, _SZ]),
+    "vpbs_ring_prover_verifier_data": (_I, [_VP, U64P, U64P]),
+    "vpbs_ring_prover_set_check_witness": (_I, [_VP, _I]),
+    "vpbs_ring_prover_witness_checks": (_I, [_VP, U64P]),
+    "vpbs_ring_prover_set_checkpoint": (_I, [_VP, _UI, PBS_CHECKPOINT_FN, _VP]),
+    "vpbs_ring_prover_last_run": (_I, [_VP, C.POINTER(PbsRunStatsC)]),
+    "vpbs_ring_prover_free": (None, [_VP]),
+    "vpbs_program_create": (_I, [_VP, C.POINTER(ProgramDescC), C.POINTER(_VP), C.c_char_p, _SZ]),
+    "vpbs_program_levels": (C.c_long, [_VP, C.POINTER(_UI)]),
+    "vpbs_program_run": (C.c_long, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _I]),
+    "vpbs_program_run_batch": (C.c_long, [_VP, _VP, _VP, _SZ, _VP, _VP, _VP, _VP, _VP, _I]),
+    "vpbs_program_prove": (C.c_long, [_VP, _VP, U64P, U64P, _UI, U64P, U64P, PBS_PROOF_FN, _VP, C.c_char_p, _SZ]),
+    "vpbs_program_prove_batch": (C.c_long, [_VP, _VP, U64P, _SZ, _VP, U64P, _UI, U64P, U64P, PBS_PROOF_FN, _VP, C.c_char_p, _SZ]),
+    "vpbs_program_verify": (C.c_long, [_VP, _VP, U64P, U64P, U64P, C.POINTER(C.c_uint8), C.POINTER(_SZ), C.POINTER(C.c_uint8),
                                        C.POINTER(C.c_uint8), C.POINTER(C.c_uint8)]),
-    "vpbs_program_verify_batch": (C.c_long, [_vp, _vp, U64P, _sz, _vp, U64P, U64P, C.POINTER(C.c_uint8), C.POINTER(_sz), C.POINTER(C.c_uint8),
-                                             C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.c_char_p, _sz]),
-    "vpbs_program_free": (None, [_vp]),
-    "vpbs_program_create_multi": (_i, [_vp, C.POINTER(ProgramDescC), C.POINTER(_ui), C.POINTER(_ui), C.POINTER(_vp), C.c_char_p, _sz]),
-    "vpbs_program_wires": (C.c_long, [_vp, C.POINTER(_ui)]),
-    "vpbs_lwe_snap": (_i, [_vp, _ui, _ui, _vp, _sz, _vp, _i]),
-    "vpbs_lwe_extract_at": (_i, [_vp, _ui, _ui, _ui, _vp, _sz, _vp, _vp, _sz, _vp, _i]),
-    "vpbs_lut_testv_multi": (_i, [_ui, _ui, _ui, U64P, _u64, U64P]),
-    "vpbs_lwe_extract": (_i, [_vp, _ui, _ui, _ui, _vp, _sz, _vp, _i]),
-    "vpbs_lwe_decrypt": (_i, [U64P, U64P, _ui, U64P]),
-    "vpbs_lwe_encrypt_batch": (_i, [_vp, C.POINTER(KeygenParamsC), _vp, _i, _vp, _sz, _u64, _vp, _i]),
-    "vpbs_lut_testv": (_i, [_ui, _ui, U64P, _u64, U64P]),
-    "vpbs_lwe_decode_batch": (_i, [_vp, _vp, _i, _vp, _sz, _ui, _u64, _u64, _vp, _vp, _vp, _vp, C.POINTER(NoiseStatsC), _i]),
-    "vpbs_keygen_seeded": (_i, [_vp, C.POINTER(KeygenParamsC), _u64, _vp, _vp, U64P, U64P, U64P, _vp, _vp, _i]),
-    "vpbs_key_expand": (_i, [_vp, C.POINTER(TfheParamsC), _ui, _u64, _vp, _vp, _i, _vp, _vp, _i]),
-    "vpbs_lwe_encrypt_seeded_batch": (_i, [_vp, C.POINTER(KeygenParamsC), _u64, _vp, _i, _vp, _sz, _u64, _vp, _i]),
-    "vpbs_lwe_expand_batch": (_i, [_vp, _ui, _u64, _u64, _vp, _sz, _vp, _i]),
-    "vpbs_keyring_add_seeded": (_i, [_vp, _u64, _vp, _vp, _i, C.POINTER(_ui)]),
-    "vpbs_ring_prover_add_seeded": (_i, [_vp, _u64, _vp, _vp, _i, C.POINTER(_ui), C.c_char_p, _sz]),
-    "vpbs_k_poseidon_batch": (_i, [_vp, U64P, _sz]),
-    "vpbs_k_hash_rows": (_i, [_vp, U64P, _sz, _ui, U64P]),
-    "vpbs_k_intt": (_i, [_vp, U64P, _ui, _ui, U64P]),
-    "vpbs_k_coset_lde": (_i, [_vp, U64P, _ui, _ui, _ui, _u64, U64P]),
-    "vpbs_k_merkle_cap": (_i, [_vp, U64P, _sz, _ui, _ui, U64P]),
-    "vpbs_k_negacyclic_ntt": (_i, [_vp, U64P, _ui, _ui, _i]),
-    "vpbs_ntt_params": (_i, [_ui, U64P, U64P, U64P]),
-    "vpbs_timing_enable": (_i, [_vp, _i]),
-    "vpbs_timing_report": (_i, [_vp, C.c_char_p, _sz]),
-    "vpbs_timing_shader_clock": (_i, [_vp, C.POINTER(C.c_double), C.POINTER(_ui)]),
-    "vpbs_aggregate_reason_text": (C.c_char_p, [_i]),
-    "vpbs_aggregate_root": (_i, [_ui, _ui, _ui, U64P, _sz, U64P, _sz, _vp, U64P, U64P, U64P, _sz, _vp, U64P]),
-    "vpbs_verify_aggregate": (_i, [_vp, _sz, U64P, _sz, _vp, U64P, U64P, U64P, _sz, _vp, C.POINTER(C.c_uint8), _sz, C.POINTER(_i), C.c_char_p, _sz]),
-    "vpbs_aggregator_create": (_i, [_vp, _vp, _sz, _vp, _ui, C.POINTER(_vp), C.c_char_p, _sz]),
-    "vpbs_aggregator_verifier_data": (_i, [_vp, U64P]),
-    "vpbs_aggregator_run": (C.c_long, [_vp, C.POINTER(C.c_uint8), C.POINTER(_sz), _sz, C.POINTER(C.c_uint8), _sz, _vp, C.c_char_p, _sz]),
-    "vpbs_aggregator_last_run": (_i, [_vp, _vp]),
-    "vpbs_aggregator_free": (None, [_vp]),
-    "vpbs_aggregator_set_device_witness": (_i, [_vp, _ui, C.c_char_p, _sz]),
-    "vpbs_aggregator_device_stats": (_i, [_vp, U64P]),
-    "vpbs_aggregate_level_jobs": (_i, [C.POINTER(_sz), _sz, _ui, _vp, _vp, _vp, _sz]),
-    "vpbs_aggregator_run_many": (C.c_long, [_vp, C.POINTER(C.c_uint8), C.POINTER(_sz), C.POINTER(_sz), _sz, AGGREGATE_TREE_FN, _vp, C.c_char_p, _sz]),
-    "vpbs_aggregate_verifier_create": (_i, [_vp, _vp, _sz, C.POINTER(_vp), C.c_char_p, _sz]),
-    "vpbs_aggregate_verifier_run": (_i, [_vp, C.POINTER(C.c_uint8), _sz, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _sz, _vp, _i, C.POINTER(_i),
-                                         C.c_char_p, _sz]),
-    "vpbs_aggregate_verifier_root": (_i, [_vp, _sz, _vp, _sz, _vp, _vp, _vp, _vp, _sz, _vp, _i, U64P, C.c_char_p, _sz]),
-    "vpbs_aggregate_verifier_free": (None, [_vp]),
-    "vpbs_aggregate_verifier_create_many": (_i, [_vp, _vp, _sz, _sz, C.POINTER(_vp), C.c_char_p, _sz]),
-    "vpbs_aggregate_verifier_run_many": (C.c_long, [_vp, C.POINTER(C.c_uint8), C.POINTER(_sz), _sz, C.POINTER(_sz), _vp, _sz, _vp, _vp, _vp, _vp, _sz,
-                                                    _vp, _i, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.c_char_p, _sz]),
-    "vpbs_aggregate_verifier_roots_many": (_i, [_vp, _sz, C.POINTER(_sz), _vp, _sz, _vp, _vp, _vp, _vp, _sz, _vp, _i, U64P, C.POINTER(C.c_uint8),
-                                                C.c_char_p, _sz]),
-    "vpbs_program_gate_inputs": (_i, [_vp, _ui, _ui, _ui, U64P, _sz, U64P, U64P, C.c_char_p, _sz]),
-    "vpbs_program_aggregate_root": (_i, [_vp, _ui, _ui, _ui, U64P, U64P, U64P, U64P, U64P, U64P, C.c_char_p, _sz]),
-    "vpbs_program_verify_aggregate": (_i, [_vp, _vp, U64P, U64P, U64P, U64P, C.POINTER(C.c_uint8), _sz, C.POINTER(_i), C.c_char_p, _sz]),
-    "vpbs_program_prove_aggregate": (C.c_long, [_vp, _vp, _vp, U64P, U64P, U64P, U64P, C.POINTER(C.c_uint8), _sz, _vp, PBS_PROOF_FN, _vp, C.c_char_p,
-                                                _sz]),
-    "vpbs_program_prove_aggregate_batch": (C.c_long, [_vp, _vp, _vp, U64P, _sz, _vp, U64P, U64P, U64P, AGGREGATE_FN, PBS_PROOF_FN, _vp, C.c_char_p,
-                                                      _sz]),
-    "vpbs_program_verify_aggregate_batch": (C.c_long, [_vp, _vp, U64P, _sz, _vp, U64P, _sz, U64P, U64P, C.POINTER(C.c_uint8), C.POINTER(_sz),
-                                                       C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.c_char_p, _sz]),
+    "vpbs_program_verify_batch": (C.c_long, [_VP, _VP, U64P, _SZ, _VP, U64P, U64P, C.POINTER(C.c_uint8), C.POINTER(_SZ), C.POINTER(C.c_uint8),
+                                             C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.c_char_p, _SZ]),
+    "vpbs_program_free": (None, [_VP]),
+    "vpbs_program_create_multi": (_I, [_VP, C.POINTER(ProgramDescC), C.POINTER(_UI), C.POINTER(_UI), C.POINTER(_VP), C.c_char_p, _SZ]),
+    "vpbs_program_wires": (C.c_long, [_VP, C.POINTER(_UI)]),
+    "vpbs_lwe_snap": (_I, [_VP, _UI, _UI, _VP, _SZ, _VP, _I]),
+    "vpbs_lwe_extract_at": (_I, [_VP, _UI, _UI, _UI, _VP, _SZ, _VP, _VP, _SZ, _VP, _I]),
+    "vpbs_lut_testv_multi": (_I, [_UI, _UI, _UI, U64P, _U64, U64P]),
+    "vpbs_lwe_extract": (_I, [_VP, _UI, _UI, _UI, _VP, _SZ, _VP, _I]),
+    "vpbs_lwe_decrypt": (_I, [U64P, U64P, _UI, U64P]),
+    "vpbs_lwe_encrypt_batch": (_I, [_VP, C.POINTER(KeygenParamsC), _VP, _I, _VP, _SZ, _U64, _VP, _I]),
+    "vpbs_lut_testv": (_I, [_UI, _UI, U64P, _U64, U64P]),
+    "vpbs_lwe_decode_batch": (_I, [_VP, _VP, _I, _VP, _SZ, _UI, _U64, _U64, _VP, _VP, _VP, _VP, C.POINTER(NoiseStatsC), _I]),
+    "vpbs_keygen_seeded": (_I, [_VP, C.POINTER(KeygenParamsC), _U64, _VP, _VP, U64P, U64P, U64P, _VP, _VP, _I]),
+    "vpbs_key_expand": (_I, [_VP, C.POINTER(TfheParamsC), _UI, _U64, _VP, _VP, _I, _VP, _VP, _I]),
+    "vpbs_lwe_encrypt_seeded_batch": (_I, [_VP, C.POINTER(KeygenParamsC), _U64, _VP, _I, _VP, _SZ, _U64, _VP, _I]),
+    "vpbs_lwe_expand_batch": (_I, [_VP, _UI, _U64, _U64, _VP, _SZ, _VP, _I]),
+    "vpbs_keyring_add_seeded": (_I, [_VP, _U64, _VP, _VP, _I, C.POINTER(_UI)]),
+    "vpbs_ring_prover_add_seeded": (_I, [_VP, _U64, _VP, _VP, _I, C.POINTER(_UI), C.c_char_p, _SZ]),
+    "vpbs_k_poseidon_batch": (_I, [_VP, U64P, _SZ]),
+    "vpbs_k_hash_rows": (_I, [_VP, U64P, _SZ, _UI, U64P]),
+    "vpbs_k_intt": (_I, [_VP, U64P, _UI, _UI, U64P]),
+    "vpbs_k_coset_lde": (_I, [_VP, U64P, _UI, _UI, _UI, _U64, U64P]),
+    "vpbs_k_merkle_cap": (_I, [_VP, U64P, _SZ, _UI, _UI, U64P]),
+    "vpbs_k_negacyclic_ntt": (_I, [_VP, U64P, _UI, _UI, _I]),
+    "vpbs_ntt_params": (_I, [_UI, U64P, U64P, U64P]),
+    "vpbs_timing_enable": (_I, [_VP, _I]),
+    "vpbs_timing_report": (_I, [_VP, C.c_char_p, _SZ]),
+    "vpbs_timing_shader_clock": (_I, [_VP, C.POINTER(C.c_double), C.POINTER(_UI)]),
+    "vpbs_aggregate_reason_text": (C.c_char_p, [_I]),
+    "vpbs_aggregate_root": (_I, [_UI, _UI, _UI, U64P, _SZ, U64P, _SZ, _VP, U64P, U64P, U64P, _SZ, _VP, U64P]),
+    "vpbs_verify_aggregate": (_I, [_VP, _SZ, U64P, _SZ, _VP, U64P, U64P, U64P, _SZ, _VP, C.POINTER(C.c_uint8), _SZ, C.POINTER(_I), C.c_char_p, _SZ]),
+    "vpbs_aggregator_create": (_I, [_VP, _VP, _SZ, _VP, _UI, C.POINTER(_VP), C.c_char_p, _SZ]),
+    "vpbs_aggregator_verifier_data": (_I, [_VP, U64P]),
+    "vpbs_aggregator_run": (C.c_long, [_VP, C.POINTER(C.c_uint8), C.POINTER(_SZ), _SZ, C.POINTER(C.c_uint8), _SZ, _VP, C.c_char_p, _SZ]),
+    "vpbs_aggregator_last_run": (_I, [_VP, _VP]),
+    "vpbs_aggregator_free": (None, [_VP]),
+    "vpbs_aggregator_set_device_witness": (_I, [_VP, _UI, C.c_char_p, _SZ]),
+    "vpbs_aggregator_device_stats": (_I, [_VP, U64P]),
+    "vpbs_aggregate_level_jobs": (_I, [C.POINTER(_SZ), _SZ, _UI, _VP, _VP, _VP, _SZ]),
+    "vpbs_aggregator_run_many": (C.c_long, [_VP, C.POINTER(C.c_uint8), C.POINTER(_SZ), C.POINTER(_SZ), _SZ, AGGREGATE_TREE_FN, _VP, C.c_char_p, _SZ]),
+    "vpbs_aggregate_verifier_create": (_I, [_VP, _VP, _SZ, C.POINTER(_VP), C.c_char_p, _SZ]),
+    "vpbs_aggregate_verifier_run": (_I, [_VP, C.POINTER(C.c_uint8), _SZ, _SZ, _VP, _SZ, _VP, _VP, _VP, _VP, _SZ, _VP, _I, C.POINTER(_I),
+                                         C.c_char_p, _SZ]),
+    "vpbs_aggregate_verifier_root": (_I, [_VP, _SZ, _VP, _SZ, _VP, _VP, _VP, _VP, _SZ, _VP, _I, U64P, C.c_char_p, _SZ]),
+    "vpbs_aggregate_verifier_free": (None, [_VP]),
+    "vpbs_aggregate_verifier_create_many": (_I, [_VP, _VP, _SZ, _SZ, C.POINTER(_VP), C.c_char_p, _SZ]),
+    "vpbs_aggregate_verifier_run_many": (C.c_long, [_VP, C.POINTER(C.c_uint8), C.POINTER(_SZ), _SZ, C.POINTER(_SZ), _VP, _SZ, _VP, _VP, _VP, _VP, _SZ,
+                                                    _VP, _I, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.c_char_p, _SZ]),
+    "vpbs_aggregate_verifier_roots_many": (_I, [_VP, _SZ, C.POINTER(_SZ), _VP, _SZ, _VP, _VP, _VP, _VP, _SZ, _VP, _I, U64P, C.POINTER(C.c_uint8),
+                                                C.c_char_p, _SZ]),
+    "vpbs_program_gate_inputs": (_I, [_VP, _UI, _UI, _UI, U64P, _SZ, U64P, U64P, C.c_char_p, _SZ]),
+    "vpbs_program_aggregate_root": (_I, [_VP, _UI, _UI, _UI, U64P, U64P, U64P, U64P, U64P, U64P, C.c_char_p, _SZ]),
+    "vpbs_program_verify_aggregate": (_I, [_VP, _VP, U64P, U64P, U64P, U64P, C.POINTER(C.c_uint8), _SZ, C.POINTER(_I), C.c_char_p, _SZ]),
+    "vpbs_program_prove_aggregate": (C.c_long, [_VP, _VP, _VP, U64P, U64P, U64P, U64P, C.POINTER(C.c_uint8), _SZ, _VP, PBS_PROOF_FN, _VP, C.c_char_p,
+                                                _SZ]),
+    "vpbs_program_prove_aggregate_batch": (C.c_long, [_VP, _VP, _VP, U64P, _SZ, _VP, U64P, U64P, U64P, AGGREGATE_FN, PBS_PROOF_FN, _VP, C.c_char_p,
+                                                      _SZ]),
+    "vpbs_program_verify_aggregate_batch": (C.c_long, [_VP, _VP, U64P, _SZ, _VP, U64P, _SZ, U64P, U64P, C.POINTER(C.c_uint8), C.POINTER(_SZ),
+                                                       C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.c_char_p, _SZ]),
 }
 
 # test entries (csrc/test_entries.h): exported for the suite, not part of the C ABI
 INTERNAL_SIGNATURES = {
-    "vpbs_test_ivc_preset_matrix": (_i, [_sz, _sz, _sz, _sz, _ui, _ui, _ui, U64P, U64P, U64P, U64P, U64P, U64P, U64P, U64P]),
-    "vpbs_test_pbs_prover_preset_matrix": (_i, [_vp, U64P, U64P, _ui, _ui, U64P]),
-    "vpbs_test_pbs_prover_preset_words": (_sz, [_vp]),
-    "vpbs_test_pbs_prover_dummy_proof": (_i, [_vp, U64P]),
-    "vpbs_test_aggregator_preset_matrix": (_i, [_vp, _ui, U64P, _sz, _vp, _ui, U64P]),
-    "vpbs_test_stream_counts": (_i, [_i, C.POINTER(_ui)]),
+    "vpbs_test_ivc_preset_matrix": (_I, [_SZ, _SZ, _SZ, _SZ, _UI, _UI, _UI, U64P, U64P, U64P, U64P, U64P, U64P, U64P, U64P]),
+    "vpbs_test_pbs_prover_preset_matrix": (_I, [_VP, U64P, U64P, _UI, _UI, U64P]),
+    "vpbs_test_pbs_prover_preset_words": (_SZ, [_VP]),
+    "vpbs_test_pbs_prover_dummy_proof": (_I, [_VP, U64P]),
+    "vpbs_test_aggregator_preset_matrix": (_I, [_VP, _UI, U64P, _SZ, _VP, _UI, U64P]),
+    "vpbs_test_stream_counts": (_I, [_I, C.POINTER(_UI)]),
 }
 
 _lib = None
@@ -484,13 +491,109 @@ def lib():
     return _lib
 
 
+def _u64(x):
+    return np.ascontiguousarray(np.asarray(x, dtype=np.uint64))
+
+
+# ---- the pointer vocabulary: every array or device address reaches the library through one of these four ----
 def _ptr(a):
+    """a contiguous uint64 array that is known not to be empty -> U64P"""
     assert a.dtype == np.uint64 and a.flags["C_CONTIGUOUS"]
     return a.ctypes.data_as(U64P)
 
 
-def _u64(x):
-    return np.ascontiguousarray(np.asarray(x, dtype=np.uint64))
+def _keep_ptr(a):
+    """a uint64 array -> U64P, a valid pointer for an empty array too (the pointer keeps what it points to alive); None stays None"""
+    return None if a is None else _ptr(a if a.size else np.zeros(1, np.uint64))
+
+
+def _keep_u32(a):
+    """the same for a uint32 array -> U32P"""
+    if a is None:
+        return None
+    assert a.dtype == np.uint32 and a.flags["C_CONTIGUOUS"]
+    return (a if a.size else np.zeros(1, np.uint32)).ctypes.data_as(U32P)
+
+
+def _dev(x):
+    """a device address (an integer) -> c_void_p; None or 0 -> None"""
+    return C.c_void_p(int(x)) if x else None
+
+
+def _cts_testv(who, N, n_lwe, cts, testv):
+    """the shapes every bootstrapping call checks: cts [count][n + 1] and testv [N] shared or [count][N] -> (cts, testv), contiguous uint64"""
+    c, tv = _u64(cts), _u64(testv)
+    if c.ndim != 2 or c.shape[1] != n_lwe + 1 or tv.shape not in ((N,), (c.shape[0], N)):
+        raise ValueError("%s: expected cts [count][%d] and testv [%d] or [count][%d]" % (who, n_lwe + 1, N, N))
+    return c, tv
+
+
+def _packed(proofs, offsets=None, shape=None, outputs=0):
+    """the serialised proofs of one call -- a list of them, or with `offsets` the (buf, offsets) of pack_proofs -- as the C ABI takes them
+    -> (count, bytes pointer, size_t offsets pointer, `outputs` np.uint8 arrays of `shape` ([count] unless given) for the verdicts and
+    reasons, their pointers)"""
+    buf, offs = pack_proofs(proofs) if offsets is None else (proofs, offsets)
+    buf, offs = np.ascontiguousarray(buf, dtype=np.uint8), np.ascontiguousarray(offs, dtype=np.uint64)
+    count = offs.size - 1
+    outs = tuple(np.zeros(max(count, 0) if shape is None else shape, np.uint8) for _ in range(outputs))
+    data = buf.ctypes.data_as(U8P) if buf.size else (C.c_uint8 * 1)()
+    return count, data, offs.ctypes.data_as(SZP), outs, [o.ctypes.data_as(U8P) for o in outs]
+
+
+class _Handle:
+    """The lifecycle of every object that wraps a C handle whose entry points are named <_prefix>_*: h is the handle (None once freed),
+    ctx the Context it lives on (None for an object without one).  An object on a context registers with it (_created): it must not
+    outlive the context, so Context.close() closes the survivors first -- in any order: no destructor of the library reaches into another
+    registered object, only into the context and into what the object itself made.  Closing again, or after the context, does nothing."""
+    _prefix = None
+    _owns = True   # False: a view of a handle that another object frees (RingProver.keyring) -- close() only forgets it
+    h = ctx = None
+
+    def _entry(self, name):
+        return getattr(lib(), "%s_%s" % (self._prefix, name))
+
+    @staticmethod
+    def _fail(what, rc, text=None):
+        """the VpbsError of a failed call, with .status: "<what>: status <rc>: <text>" (no what, no text: that part is left out)"""
+        return VpbsError("%sstatus %d%s" % (what + ": " if what else "", rc, "" if text is None else ": " + text), status=rc)
+
+    def _construct(self, ctx, *args, entry="create", what=None, status=False):
+        """<_prefix>_<entry>(*args, &handle, err, 512), then _created(ctx).  A status other than 0 raises VpbsError "<what>: status <rc>:
+        <the library's message>" (what: the entry point unless given; status: with .status)"""
+        h, err = C.c_void_p(), C.create_string_buffer(512)
+        rc = self._entry(entry)(*args, C.byref(h), err, 512)
+        if rc:
+            e = self._fail("%s_%s" % (self._prefix, entry) if what is None else what, rc, err.value.decode())
+            raise e if status else VpbsError(str(e))
+        self.h = h
+        self._created(ctx)
+
+    def _created(self, ctx):
+        self.ctx = ctx
+        if ctx is not None:
+            ctx._batches.add(self)
+
+    def _release(self):
+        """<_prefix>_free(h); a subclass lets go first of what goes with the handle (RingProver: its view)"""
+        self._entry("free")(self.h)
+
+    def close(self):
+        if self.h:
+            try:
+                if self._owns:
+                    self._release()
+            finally:
+                self.h = None
+                if self.ctx is not None:
+                    self.ctx._batches.discard(self)
+
+    free = close
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class ChallengerState:
@@ -722,8 +825,9 @@ class Circuit:
         return WitnessPlan(self, positions)
 
 
-class WitnessPlan:
+class WitnessPlan(_Handle):
     """vpbs_witness_plan: the compiled witness generator of one circuit (create once, run per PartialWitness)."""
+    _prefix = "vpbs_witness_plan"
 
     def __init__(self, circuit, positions):
         self.circuit = circuit
@@ -836,29 +940,14 @@ class WitnessPlan:
             raise VpbsError("vpbs_witness_plan_stats failed")
         return dict(zip(("slots", "generators", "levels", "positions"), (int(x) for x in out)))
 
-    def free(self):
-        if self.h:
-            lib().vpbs_witness_plan_free(self.h)
-            self.h = None
 
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
-
-
-class WitnessChecker:
+class WitnessChecker(_Handle):
     """vpbs_witness_checker: vpbs_check_witness on the device (same verdict, same message); the circuit's tables are uploaded once."""
+    _prefix = "vpbs_witness_checker"
 
     def __init__(self, ctx, circuit):
-        self.ctx, self.circuit = ctx, circuit
-        h, err = C.c_void_p(), C.create_string_buffer(512)
-        rc = lib().vpbs_witness_checker_create(ctx.h, C.byref(circuit.c), C.byref(h), err, 512)
-        if rc:
-            raise VpbsError("vpbs_witness_checker_create: status %d: %s" % (rc, err.value.decode()))
-        self.h = h
-        ctx._batches.add(self)   # like a batch, a checker must not outlive its context: Context.close() frees the survivors
+        self.circuit = circuit
+        self._construct(ctx, ctx.h, C.byref(circuit.c))
 
     def check(self, wires, pi_hash):
         """wires: a host matrix [n_wires][n] or a device pointer (int) to one -> (ok, message of the first violation)"""
@@ -875,27 +964,18 @@ class WitnessChecker:
             raise VpbsError("vpbs_witness_checker_run: status %d: %s" % (rc, err.value.decode()))
         return rc == 1, err.value.decode()
 
-    def free(self):
-        if self.h:
-            lib().vpbs_witness_checker_free(self.h)
-            self.h = None
 
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
-
-
-class WitnessDevice:
+class WitnessDevice(_Handle):
     """vpbs_witness_device: the plan's schedule replayed on the device for a batch of PartialWitnesses (create once per circuit)."""
+    _prefix = "vpbs_witness_device"
 
     def __init__(self, ctx, plan, max_batch, early=False):
         """early: the early phase of a split plan alone (vpbs_witness_device_create_early); the late presets' rows of `values` are ignored"""
-        self.ctx, self.plan, self.max_batch = ctx, plan, max_batch
+        self.plan, self.max_batch = plan, max_batch   # the plan is kept: the device object replays it
         h = C.c_void_p()
-        ctx._check((lib().vpbs_witness_device_create_early if early else lib().vpbs_witness_device_create)(ctx.h, plan.h, max_batch, C.byref(h)))
+        ctx._check(self._entry("create_early" if early else "create")(ctx.h, plan.h, max_batch, C.byref(h)))
         self.h = h
+        self._created(ctx)
 
     def run_late(self, instance, values):
         """the late phase of one instance of the last batch on top of its early values (values: [n_preset], the late entries are read)"""
@@ -927,17 +1007,6 @@ class WitnessDevice:
         out = np.zeros(pos.size, np.uint64)
         self.ctx._check(lib().vpbs_witness_device_read(self.h, instance, pos.ctypes.data_as(U32P), pos.size, _ptr(out)))
         return out
-
-    def free(self):
-        if self.h:
-            lib().vpbs_witness_device_free(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
 
 
 def hash_chain(items, claimed=None):
@@ -1011,11 +1080,12 @@ def pack_proofs(blobs):
     return buf, offsets
 
 
-class ProofVerifier:
+class ProofVerifier(_Handle):
     """vpbs_proof_verifier: vpbs_step_proof_from_bytes + vpbs_verify_step for a batch of serialised step proofs on the device, with the host's
     verdict for every one of them.  The parameters mirror verify_step (each proof carries its own public inputs); max_public_inputs is the
     parser's public_inputs_capacity.  Every proof slot on the device holds the proof's words and max_public_inputs more, max_batch slots:
     size both to the proofs at hand (the defaults, 256 proofs of up to 8192 public inputs, take ~200 MB for a paper-size step proof)."""
+    _prefix = "vpbs_proof_verifier"
 
     def __init__(self, ctx, cs_cap, ncols, circuit_digest, log_n, num_challenges=2, check_permutation=True, n_constants=0, n_routed=0,
                  quotient_degree_factor=8, gates=None, compat=None, rate_bits=3, cap_height=4, max_batch=256, max_public_inputs=1 << 13,
@@ -1023,7 +1093,7 @@ class ProofVerifier:
         if check_permutation and n_routed == 0:
             raise ValueError("ProofVerifier: the full check needs n_constants / n_routed (and the gates); check_permutation=False for "
                              "transcript + FRI only")
-        self.ctx, self.max_batch = ctx, max_batch
+        self.max_batch = max_batch
         v = VerifyInputsC()
         v.log_n, v.rate_bits, v.cap_height = log_n, rate_bits, cap_height
         v.n_constants_sigmas, v.n_wires, v.n_zs_partial_products, v.n_quotient = ncols
@@ -1041,44 +1111,19 @@ class ProofVerifier:
         if compat is not None:
             self._compat = compat
             v.compat = C.pointer(compat)
-        h, err = C.c_void_p(), C.create_string_buffer(512)
-        rc = lib().vpbs_proof_verifier_create(ctx.h, C.byref(v), max_batch, max_public_inputs, C.byref(h), err, 512)
-        if rc:
-            raise VpbsError("vpbs_proof_verifier_create: status %d: %s" % (rc, err.value.decode()))
-        self.h = h
-        ctx._batches.add(self)   # must not outlive its context: Context.close() frees the survivors
+        self._construct(ctx, ctx.h, C.byref(v), max_batch, max_public_inputs)
 
     def verify_packed(self, buf, offsets):
         """buf: uint8 buffer, offsets: [count + 1] (pack_proofs) -> (verdicts, reasons), np.uint8 each"""
-        buf = np.ascontiguousarray(buf, dtype=np.uint8)
-        offs = np.ascontiguousarray(offsets, dtype=np.uint64)
-        count = offs.size - 1
-        verdicts, reasons = np.zeros(max(count, 0), np.uint8), np.zeros(max(count, 0), np.uint8)
-        u8p = C.POINTER(C.c_uint8)
-        data = buf.ctypes.data_as(u8p) if buf.size else (C.c_uint8 * 1)()
-        rc = lib().vpbs_proof_verifier_run(self.h, data, offs.ctypes.data_as(C.POINTER(C.c_size_t)), count, verdicts.ctypes.data_as(u8p),
-                                           reasons.ctypes.data_as(u8p))
+        count, data, offs, results, ptrs = _packed(buf, offsets, outputs=2)
+        rc = lib().vpbs_proof_verifier_run(self.h, data, offs, count, *ptrs)
         if rc < 0:
             raise VpbsError("vpbs_proof_verifier_run: status %d" % rc)
-        return verdicts, reasons
+        return results
 
     def verify(self, blobs):
         """list of ProofWithPublicInputs byte strings -> (verdicts, reasons), np.uint8 each"""
         return self.verify_packed(*pack_proofs(blobs))
-
-    def close(self):
-        if self.h:
-            lib().vpbs_proof_verifier_free(self.h)
-            self.h = None
-            self.ctx._batches.discard(self)
-
-    free = close
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def _ivc_circuit(d, proof_words, keep):
@@ -1094,18 +1139,21 @@ def _ivc_circuit(d, proof_words, keep):
     return c
 
 
-class Ivc:
+class Ivc(_Handle):
     """vpbs_ivc: one verifiable PBS as one call -- the IVC chain of verified_pbs (ivc_based_vpbs.rs:159-386) driven inside the library.
     cyclic / dummy: circuit_file.CircuitDescription of the exported cyclic step circuit and its dummy circuit."""
+    _prefix = "vpbs_ivc"
 
     def __init__(self, ctx, cyclic, dummy, N, K, ggsw_len, comm=None):
         """comm: a CommC (sharding.make_comm / make_comm_rccl) -> every step proof coset-sharded over the ranks; every rank builds its own Ivc"""
-        self.ctx, self._keep = ctx, [comm]
+        self._keep = [comm]
         cy, du = _ivc_circuit(cyclic, cyclic.meta["proof_words"], self._keep), _ivc_circuit(dummy, 0, self._keep)
-        self.h, err = C.c_void_p(), C.create_string_buffer(512)
-        if lib().vpbs_ivc_create(ctx.h, C.byref(cy), C.byref(du), N, K, ggsw_len, C.byref(comm) if comm is not None else None, C.byref(self.h),
+        h, err = C.c_void_p(), C.create_string_buffer(512)
+        if lib().vpbs_ivc_create(ctx.h, C.byref(cy), C.byref(du), N, K, ggsw_len, C.byref(comm) if comm is not None else None, C.byref(h),
                                  err, 512):
             raise VpbsError("vpbs_ivc_create: " + err.value.decode())
+        self.h = h
+        self._created(ctx)
         self.vk_words = 4 + (4 << 4)
         self.max_bytes = 8 * (cyclic.meta["proof_words"] + len(cyclic.pi_pos)) + (1 << 16)
 
@@ -1206,11 +1254,6 @@ class Ivc:
         if n < 0:
             raise VpbsError("vpbs_ivc_resume_pbs: " + err.value.decode())
         return bytes(buf[:n]), {f: getattr(t, f) for f, _ in IvcTimingC._fields_}
-
-    def free(self):
-        if self.h:
-            lib().vpbs_ivc_free(self.h)
-            self.h = None
 
 
 def verify_pbs(blob, cs_cap, ncols, circuit_digest, log_n, n_constants, n_routed, gates, N, K, testv, ct, bsk, ksk, out_ct, num_challenges=2,
@@ -1325,64 +1368,54 @@ def _verify_pbs_shape(cs_cap, ncols, circuit_digest, log_n, n_constants, n_route
     return p, (v, cap, gates, compat)
 
 
-class PbsVerifier:
+class _PbsVerify(_Handle):
+    """What PbsVerifier and RingVerifier share: the creation from _verify_pbs_shape and the run over packed proofs.  A subclass gives
+    _statement(count, ...): its own arguments checked and turned into what <_prefix>_run takes between the proofs and the verdicts."""
+    _run_err = False   # <_prefix>_run ends in (err, err_len) and its failures carry .status
+
+    def _create(self, ctx, shape, N, K, n_lwe, max_batch, *create_args):
+        """shape: _verify_pbs_shape's leading arguments; create_args: what <_prefix>_create takes between the shape and max_batch"""
+        self.max_batch, self.N, self.K, self.n_lwe = max_batch, N, K, n_lwe
+        p, self._keep = _verify_pbs_shape(*shape)
+        self._construct(ctx, ctx.h, C.byref(p), *create_args, max_batch)
+
+    def _verify(self, buf, offsets, *statement):
+        count, data, offs, results, ptrs = _packed(buf, offsets, outputs=3)
+        args = self._statement(count, *statement)
+        what, err = self._prefix + "_run", C.create_string_buffer(512)
+        rc = self._entry("run")(self.h, data, offs, count, *args, *ptrs, *((err, 512) if self._run_err else ()))
+        if rc < 0:
+            raise self._fail(what, rc, err.value.decode() or None) if self._run_err else VpbsError("%s: status %d" % (what, rc))
+        return results
+
+
+class PbsVerifier(_PbsVerify):
     """vpbs_pbs_verifier: vpbs_verify_pbs for a batch of vPBS proofs (the serialised last proofs of IVC chains) on the device, all under the
     key set whose hash is key_hash (pbs_key_hash).  The parameters mirror verify_pbs; every proof brings its own ct and out_ct."""
+    _prefix = "vpbs_pbs_verifier"
 
     def __init__(self, ctx, cs_cap, ncols, circuit_digest, log_n, n_constants, n_routed, gates, N, K, n_lwe, ggsw_len, key_hash, max_batch=64,
                  num_challenges=2, quotient_degree_factor=8, rate_bits=3, cap_height=4, compat=None):
-        self.ctx, self.max_batch, self.N, self.K, self.n_lwe = ctx, max_batch, N, K, n_lwe
-        p, self._keep = _verify_pbs_shape(cs_cap, ncols, circuit_digest, log_n, n_constants, n_routed, gates, N, K, n_lwe, ggsw_len, num_challenges,
-                                          quotient_degree_factor, rate_bits, cap_height, compat)
-        kh = _u64(key_hash).reshape(-1)
-        h, err = C.c_void_p(), C.create_string_buffer(512)
-        rc = lib().vpbs_pbs_verifier_create(ctx.h, C.byref(p), _ptr(kh), max_batch, C.byref(h), err, 512)
-        if rc:
-            raise VpbsError("vpbs_pbs_verifier_create: status %d: %s" % (rc, err.value.decode()))
-        self.h = h
-        ctx._batches.add(self)   # must not outlive its context: Context.close() frees the survivors
+        shape = (cs_cap, ncols, circuit_digest, log_n, n_constants, n_routed, gates, N, K, n_lwe, ggsw_len, num_challenges, quotient_degree_factor,
+                 rate_bits, cap_height, compat)
+        self._create(ctx, shape, N, K, n_lwe, max_batch, _ptr(_u64(key_hash).reshape(-1)))
+
+    def _statement(self, count, testv, cts, out_cts):
+        tv = _u64(testv)
+        per_proof = tv.ndim == 2
+        tv, c, o = tv.reshape(-1), _u64(cts).reshape(-1), _u64(out_cts).reshape(-1)
+        if c.size != count * (self.n_lwe + 1) or o.size != count * self.K * self.N or tv.size != (count if per_proof else 1) * self.N:
+            raise ValueError("PbsVerifier.verify: expected testv [N] or [%d][N], cts [%d][n + 1] and out_cts [%d][K][N]" % (count, count, count))
+        return _keep_ptr(tv), 1 if per_proof else 0, _keep_ptr(c), _keep_ptr(o)
 
     def verify_packed(self, buf, offsets, testv, cts, out_cts):
         """buf, offsets: pack_proofs; testv: [N] shared or [count][N]; cts: [count][n + 1]; out_cts: [count][K][N]
         -> (verdicts, reasons, proof_reasons), np.uint8 each"""
-        buf = np.ascontiguousarray(buf, dtype=np.uint8)
-        offs = np.ascontiguousarray(offsets, dtype=np.uint64)
-        count = offs.size - 1
-        tv = _u64(testv)
-        per_proof = tv.ndim == 2
-        tv = tv.reshape(-1)
-        c = _u64(cts).reshape(-1)
-        o = _u64(out_cts).reshape(-1)
-        if c.size != count * (self.n_lwe + 1) or o.size != count * self.K * self.N or tv.size != (count if per_proof else 1) * self.N:
-            raise ValueError("PbsVerifier.verify: expected testv [N] or [%d][N], cts [%d][n + 1] and out_cts [%d][K][N]" % (count, count, count))
-        verdicts, reasons, sub = (np.zeros(max(count, 0), np.uint8) for _ in range(3))
-        u8p = C.POINTER(C.c_uint8)
-        data = buf.ctypes.data_as(u8p) if buf.size else (C.c_uint8 * 1)()
-        keep = np.zeros(1, np.uint64)   # a valid pointer for empty arrays
-        ptr = lambda a: _ptr(a) if a.size else _ptr(keep)
-        rc = lib().vpbs_pbs_verifier_run(self.h, data, offs.ctypes.data_as(C.POINTER(C.c_size_t)), count, ptr(tv), 1 if per_proof else 0,
-                                         ptr(c), ptr(o), verdicts.ctypes.data_as(u8p), reasons.ctypes.data_as(u8p), sub.ctypes.data_as(u8p))
-        if rc < 0:
-            raise VpbsError("vpbs_pbs_verifier_run: status %d" % rc)
-        return verdicts, reasons, sub
+        return self._verify(buf, offsets, testv, cts, out_cts)
 
     def verify(self, blobs, testv, cts, out_cts):
         """list of serialised vPBS proofs -> (verdicts, reasons, proof_reasons), np.uint8 each"""
         return self.verify_packed(*pack_proofs(blobs), testv, cts, out_cts)
-
-    def close(self):
-        if self.h:
-            lib().vpbs_pbs_verifier_free(self.h)
-            self.h = None
-            self.ctx._batches.discard(self)
-
-    free = close
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def verify_step_fri_only(proof, cs_cap, ncols, circuit_digest, public_inputs, log_n, num_challenges=2, rate_bits=3, cap_height=4):
@@ -1522,7 +1555,7 @@ def _lwe_encrypt_batch(ctx, params, s_lwe, messages, nonce0, out_dev_ptr, count,
     try:
         if out_dev_ptr is None:
             out = np.zeros((count, n + 1) if mask_seed is None else count, np.uint64)
-            pm, po, on_device = (msgs if count else keep).ctypes.data, (out if count else keep).ctypes.data, 0
+            pm, po, on_device = _keep_ptr(msgs), _keep_ptr(out), 0
         else:
             if msgs is not None:
                 tmp = ctx.device_upload_new(msgs if count else keep)
@@ -1557,7 +1590,7 @@ def _lwe_expand_batch(ctx, n_lwe, mask_seed, bodies, nonce0, out_dev_ptr, count)
     try:
         if out_dev_ptr is None:
             out = np.zeros((count, int(n_lwe) + 1), np.uint64)
-            pb, po, on_device = (b if count else keep).ctypes.data, (out if out.size else keep).ctypes.data, 0
+            pb, po, on_device = _keep_ptr(b), _keep_ptr(out), 0
         else:
             if b is not None:
                 tmp = ctx.device_upload_new(b if count else keep)
@@ -1624,11 +1657,10 @@ def _lwe_decode_batch(ctx, s_lwe, cts, delta, modulus, expected, count, stats, w
     if exp is not None and exp.size != count:
         raise ValueError("lwe_decode_batch: expected must have count = %d entries" % count)
     keep = np.zeros(1, np.uint64)
-    host = lambda a: (a if a.size else keep).ctypes.data
     tmp, outs = None, {}
     try:
         if rows is not None:
-            where, pc, pe = 0, host(rows), (None if expected is None else host(exp))
+            where, pc, pe = 0, _keep_ptr(rows), _keep_ptr(exp)
         else:
             where, pc = (1 if isinstance(want, dict) else 2), int(cts)
             if exp is not None:
@@ -1638,7 +1670,7 @@ def _lwe_decode_batch(ctx, s_lwe, cts, delta, modulus, expected, count, stats, w
             po = [int(want[w]) if w in want else None for w in DECODE_OUTPUTS]
         else:
             outs = {w: np.zeros(count, np.uint64) for w in want}
-            po = [host(outs[w]) if w in outs else None for w in DECODE_OUTPUTS]
+            po = [_keep_ptr(outs.get(w)) for w in DECODE_OUTPUTS]
         rc = lib().vpbs_lwe_decode_batch(h, int(s_lwe) if key is None else key.ctypes.data, 1 if key is None else 0, pc, count, n, int(delta),
                                          int(modulus), pe, po[0], po[1], po[2], C.byref(stats.c) if stats is not None else None, where)
     finally:
@@ -1678,13 +1710,12 @@ def lwe_decode_batch(s_lwe, cts, delta, modulus, expected=None, stats=None, want
 def _lwe_snap(ctx, N, log_slots, words, count=None, out_dev_ptr=None):
     h = ctx.h if ctx is not None else None
     if out_dev_ptr is not None:
-        rc = lib().vpbs_lwe_snap(h, N.bit_length() - 1, log_slots, C.c_void_p(int(words)), count, C.c_void_p(int(out_dev_ptr)), 1)
+        rc = lib().vpbs_lwe_snap(h, N.bit_length() - 1, log_slots, _dev(words), count, _dev(out_dev_ptr), 1)
         out = None
     else:
         w = _u64(words)
         out = np.zeros(w.shape, np.uint64)
-        keep = np.zeros(1, np.uint64)
-        rc = lib().vpbs_lwe_snap(h, N.bit_length() - 1, log_slots, (w if w.size else keep).ctypes.data, w.size, (out if w.size else keep).ctypes.data, 0)
+        rc = lib().vpbs_lwe_snap(h, N.bit_length() - 1, log_slots, _keep_ptr(w), w.size, _keep_ptr(out), 0)
     if rc:
         raise VpbsError("vpbs_lwe_snap: status %d: %s" % (rc, lib().vpbs_last_error(h).decode() if h else "bad arguments (log_slots <= log_N <= 11)"))
     return out
@@ -1696,8 +1727,7 @@ def _lwe_extract_at(ctx, glwe, n_lwe, index, src, count=None, N=None, K=None, ou
     if ix.size != sr.size:
         raise ValueError("lwe_extract_at: index and src must have one entry per output row")
     rows = ix.size
-    k32 = np.zeros(1, np.uint32)
-    pi, ps = (ix if rows else k32).ctypes.data, (sr if rows else k32).ctypes.data
+    pi, ps = _keep_u32(ix), _keep_u32(sr)
     if out_dev_ptr is not None:
         rc = lib().vpbs_lwe_extract_at(h, N.bit_length() - 1, K, n_lwe, C.c_void_p(int(glwe)), count, pi, ps, rows, C.c_void_p(int(out_dev_ptr)), 1)
         out = None
@@ -1706,9 +1736,7 @@ def _lwe_extract_at(ctx, glwe, n_lwe, index, src, count=None, N=None, K=None, ou
         g3 = g.reshape((1,) + g.shape) if g.ndim == 2 else g
         cnt, K_, N_ = g3.shape
         out = np.zeros((rows, n_lwe + 1), np.uint64)
-        keep = np.zeros(1, np.uint64)
-        rc = lib().vpbs_lwe_extract_at(h, N_.bit_length() - 1, K_, n_lwe, (g3 if g3.size else keep).ctypes.data, cnt, pi, ps, rows,
-                                       (out if out.size else keep).ctypes.data, 0)
+        rc = lib().vpbs_lwe_extract_at(h, N_.bit_length() - 1, K_, n_lwe, _keep_ptr(g3), cnt, pi, ps, rows, _keep_ptr(out), 0)
     if rc:
         raise VpbsError("vpbs_lwe_extract_at: status %d: %s" % (rc, lib().vpbs_last_error(h).decode() if h else
                                                                 "bad arguments (index below N, src below count, 1 <= n_lwe <= (K - 1) N)"))
@@ -1744,96 +1772,107 @@ def lut_testv_multi(N, p, tables, delta=None):
     return out, int(delta)
 
 
-class Bootstrapper:
+def _key_args(who, bsk, ksk, K, ELL, N, n_lwe, keys_on_device):
+    """the key set of a bootstrapping object: bsk [n][K*ELL*K*N] and ksk [K*ELL*K*N] as host arrays (keygen's layout), or device
+    pointers (integers) with keys_on_device -> (bsk pointer, ksk pointer, N, n_lwe, what the pointers refer to).  N and n_lwe are the
+    shape the keys must have; None: the shape is read off the host arrays, and device keys are refused."""
+    if keys_on_device:
+        if N is None or n_lwe is None:
+            raise ValueError("%s: device keys need N and n_lwe" % who)
+        return C.c_void_p(int(bsk)), C.c_void_p(int(ksk)), N, n_lwe, None
+    b, k = _u64(bsk), _u64(ksk).reshape(-1)
+    if N is None or n_lwe is None:
+        n_lwe, N = b.shape[0], k.size // (K * ELL * K)
+        want = "bsk [n][K*ELL*K*N] and ksk [K*ELL*K*N]"
+    else:
+        want = "bsk [%d][%d] and ksk [%d]" % (n_lwe, K * ELL * K * N, K * ELL * K * N)
+    if b.shape != (n_lwe, K * ELL * K * N) or k.size != K * ELL * K * N:
+        raise ValueError("%s: expected %s" % (who, want))
+    return C.c_void_p(b.ctypes.data), C.c_void_p(k.ctypes.data), N, n_lwe, (b, k)
+
+
+class _ChainRun(_Handle):
+    """The run methods of Bootstrapper and KeyRing: one body each for run, run_from and run_device; key_of (the ring's slots) is
+    checked and passed on only by the ring (_ring).  The object has N, K, n_lwe and, for key_of, max_keys."""
+    _ring = False
+
+    def _run_fail(self, name, rc, status=True):
+        e = self._fail("%s_%s" % (self._prefix, name), rc, lib().vpbs_last_error(self.ctx.h).decode())
+        return e if status else VpbsError(str(e))
+
+    def _outputs(self, count):
+        return np.zeros((count, self.K, self.N), np.uint64), np.zeros((count, self.n_lwe + 1), np.uint64)
+
+    def _run(self, cts, testv, accumulators, key_of=None):
+        ring, who = self._ring, type(self).__name__ + ".run"
+        c, tv = _cts_testv(who, self.N, self.n_lwe, cts, testv)
+        count = c.shape[0]
+        ko = [_keep_u32(keyring_key_of(key_of, count, self.max_keys))] if ring else []
+        out_ct, lwe_out = self._outputs(count)
+        accs = np.zeros((count, self.n_lwe + 2, self.K, self.N), np.uint64) if accumulators else None
+        rc = self._entry("run")(self.h, _keep_ptr(c), count, *ko, _keep_ptr(tv), 1 if tv.ndim == 2 else 0, _keep_ptr(out_ct), _keep_ptr(lwe_out),
+                                _keep_ptr(accs), 0)
+        if rc != count:
+            raise self._run_fail("run", rc, status=ring)
+        return (out_ct, lwe_out, accs) if accumulators else (out_ct, lwe_out)
+
+    def _run_from(self, cts, start, acc_in, testv, accumulators, key_of=None):
+        who = type(self).__name__ + ".run_from"
+        c, st, acc, tv = run_from_args(self.N, self.K, self.n_lwe, cts, start, acc_in, testv, who)
+        count = c.shape[0]
+        ko = [_keep_u32(keyring_key_of(key_of, count, self.max_keys))] if self._ring else []
+        out_ct, lwe_out = self._outputs(count)
+        accs = _accs_out(accumulators, count, self.n_lwe, self.K, self.N, who)
+        rc = self._entry("run_from")(self.h, _keep_ptr(c), count, *ko, _keep_u32(st), _keep_ptr(acc), _keep_ptr(tv), 1 if tv.ndim == 2 else 0,
+                                     _keep_ptr(out_ct), _keep_ptr(lwe_out), _keep_ptr(accs), 0)
+        if rc != count:
+            raise self._run_fail("run_from", rc)
+        return (out_ct, lwe_out) if accs is None else (out_ct, lwe_out, accs)
+
+    def _run_device(self, d_cts, count, d_testv, testv_per_ct, d_out_ct, d_lwe_out, d_accs, key_of=None):
+        ko = [_keep_u32(keyring_key_of(key_of, count, self.max_keys))] if self._ring else []
+        rc = self._entry("run")(self.h, _dev(d_cts), count, *ko, _dev(d_testv), 1 if testv_per_ct else 0, _dev(d_out_ct), _dev(d_lwe_out),
+                                _dev(d_accs), 1)
+        if rc != count:
+            raise self._run_fail("run", rc, status=self._ring)
+
+
+class Bootstrapper(_ChainRun):
     """vpbs_bootstrapper: the whole PBS (accumulator chain of verified_pbs + partial_sample_extract) for batches of LWE ciphertexts in one
     launch, under a key set that stays on the device.  bsk [n][K*ELL*K*N], ksk [K*ELL*K*N] (keygen's layout): host arrays, or device
     pointers (integers) with keys_on_device=True, N and n_lwe given -- they must stay allocated while the object lives."""
+    _prefix = "vpbs_bootstrapper"
 
     def __init__(self, ctx, bsk, ksk, K, ELL, LOGB, max_batch=64, N=None, n_lwe=None, keys_on_device=False):
-        if keys_on_device:
-            if N is None or n_lwe is None:
-                raise ValueError("Bootstrapper: device keys need N and n_lwe")
-            pb, pk = C.c_void_p(int(bsk)), C.c_void_p(int(ksk))
-        else:
-            b, k = _u64(bsk), _u64(ksk).reshape(-1)
-            n_lwe, N = b.shape[0], k.size // (K * ELL * K)
-            if b.shape != (n_lwe, K * ELL * K * N) or k.size != K * ELL * K * N:
-                raise ValueError("Bootstrapper: expected bsk [n][K*ELL*K*N] and ksk [K*ELL*K*N]")
-            pb, pk = C.c_void_p(b.ctypes.data), C.c_void_p(k.ctypes.data)
-        self.ctx, self.N, self.K, self.ELL, self.LOGB, self.n_lwe, self.max_batch = ctx, N, K, ELL, LOGB, n_lwe, max_batch
+        if not keys_on_device:
+            N = n_lwe = None   # host keys say their own shape
+        pb, pk, N, n_lwe, _keep = _key_args("Bootstrapper", bsk, ksk, K, ELL, N, n_lwe, keys_on_device)
+        self.N, self.K, self.ELL, self.LOGB, self.n_lwe, self.max_batch = N, K, ELL, LOGB, n_lwe, max_batch
         prm = TfheParamsC(N.bit_length() - 1, K, ELL, LOGB)
-        h, err = C.c_void_p(), C.create_string_buffer(512)
-        rc = lib().vpbs_bootstrapper_create(ctx.h, C.byref(prm), n_lwe, pb, pk, 1 if keys_on_device else 0, max_batch, C.byref(h), err, 512)
-        if rc:
-            raise VpbsError("vpbs_bootstrapper_create: status %d: %s" % (rc, err.value.decode()))
-        self.h = h
-        ctx._batches.add(self)   # must not outlive its context: Context.close() frees the survivors
+        self._construct(ctx, ctx.h, C.byref(prm), n_lwe, pb, pk, 1 if keys_on_device else 0, max_batch)
 
     def run(self, cts, testv, accumulators=False):
         """cts [count][n + 1]; testv [N] shared or [count][N] -> (out_ct [count][K][N], lwe_out [count][n + 1]) and, with accumulators=True,
         every intermediate accumulator [count][n + 2][K][N] (Context.pbs_accumulator_chain for each ciphertext)"""
-        c, tv = _u64(cts), _u64(testv)
-        if c.ndim != 2 or c.shape[1] != self.n_lwe + 1 or tv.shape not in ((self.N,), (c.shape[0], self.N)):
-            raise ValueError("Bootstrapper.run: expected cts [count][%d] and testv [%d] or [count][%d]" % (self.n_lwe + 1, self.N, self.N))
-        count = c.shape[0]
-        out_ct, lwe_out = np.zeros((count, self.K, self.N), np.uint64), np.zeros((count, self.n_lwe + 1), np.uint64)
-        accs = np.zeros((count, self.n_lwe + 2, self.K, self.N), np.uint64) if accumulators else None
-        keep = np.zeros(1, np.uint64)   # a valid pointer for an empty batch
-        p = lambda a: (a if a.size else keep).ctypes.data
-        rc = lib().vpbs_bootstrapper_run(self.h, p(c), count, p(tv), 1 if tv.ndim == 2 else 0, p(out_ct), p(lwe_out),
-                                         p(accs) if accumulators else None, 0)
-        if rc != count:
-            raise VpbsError("vpbs_bootstrapper_run: status %d: %s" % (rc, lib().vpbs_last_error(self.ctx.h).decode()))
-        return (out_ct, lwe_out, accs) if accumulators else (out_ct, lwe_out)
+        return self._run(cts, testv, accumulators)
 
     def run_from(self, cts, start, acc_in, testv, accumulators=False):
         """run with a start step per row (vpbs_bootstrapper_run_from): start [count] (0: from the test vector, as run; k in 1 .. n + 2: from
         acc_in[i] [K][N], the accumulator after step k - 1, running steps k .. n + 1); acc_in [count][K][N], or None when every start is 0.
         accumulators: True for a fresh array, or an array [count][n + 2][K][N] to write into -- slots below k - 1 of a resumed row keep
         what they held.  A start above n + 2 raises VpbsError with the library's message, which names the row; nothing is launched."""
-        c, st, acc, tv = run_from_args(self.N, self.K, self.n_lwe, cts, start, acc_in, testv, "Bootstrapper.run_from")
-        count = c.shape[0]
-        out_ct, lwe_out = np.zeros((count, self.K, self.N), np.uint64), np.zeros((count, self.n_lwe + 1), np.uint64)
-        accs = _accs_out(accumulators, count, self.n_lwe, self.K, self.N, "Bootstrapper.run_from")
-        keep = np.zeros(1, np.uint64)   # a valid pointer for an empty batch
-        p = lambda a: (a if a.size else keep).ctypes.data
-        rc = lib().vpbs_bootstrapper_run_from(self.h, p(c), count, p(st), None if acc is None else p(acc), p(tv), 1 if tv.ndim == 2 else 0,
-                                              p(out_ct), p(lwe_out), None if accs is None else p(accs), 0)
-        if rc != count:
-            e = VpbsError("vpbs_bootstrapper_run_from: status %d: %s" % (rc, lib().vpbs_last_error(self.ctx.h).decode()))
-            e.status = rc
-            raise e
-        return (out_ct, lwe_out) if accs is None else (out_ct, lwe_out, accs)
+        return self._run_from(cts, start, acc_in, testv, accumulators)
 
     def run_device(self, d_cts, count, d_testv, testv_per_ct=False, d_out_ct=None, d_lwe_out=None, d_accs=None):
         """the same on device pointers (integers; None = output not wanted); returns when the outputs are in place"""
-        q = lambda x: C.c_void_p(int(x)) if x else None
-        rc = lib().vpbs_bootstrapper_run(self.h, q(d_cts), count, q(d_testv), 1 if testv_per_ct else 0, q(d_out_ct), q(d_lwe_out), q(d_accs), 1)
-        if rc != count:
-            raise VpbsError("vpbs_bootstrapper_run: status %d: %s" % (rc, lib().vpbs_last_error(self.ctx.h).decode()))
-
-    def close(self):
-        if self.h:
-            lib().vpbs_bootstrapper_free(self.h)
-            self.h = None
-            self.ctx._batches.discard(self)
-
-    free = close
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._run_device(d_cts, count, d_testv, testv_per_ct, d_out_ct, d_lwe_out, d_accs)
 
 
 def run_from_args(N, K, n_lwe, cts, start, acc_in, testv, who="run_from"):
     """shapes of a run_from call, checked without a device: cts [count][n + 1], start [count] non-negative integers (their upper bound is
     the library's refusal, which names the row), acc_in [count][K][N] or None, testv [N] or [count][N] -> (cts, start as uint32, acc_in,
     testv), contiguous"""
-    c, tv = _u64(cts), _u64(testv)
-    if c.ndim != 2 or c.shape[1] != n_lwe + 1 or tv.shape not in ((N,), (c.shape[0], N)):
-        raise ValueError("%s: expected cts [count][%d] and testv [%d] or [count][%d]" % (who, n_lwe + 1, N, N))
+    c, tv = _cts_testv(who, N, n_lwe, cts, testv)
     st = np.asarray(start)
     if st.shape == (0,):
         st = st.astype(np.uint32)
@@ -1869,9 +1908,7 @@ def resume_args(N, n_lwe, cts, testv, checkpoints, steps=0, key_of=None, max_key
     checkpoints a list of `count` entries, each bytes (non-empty) or None, steps 0 .. n + 2 and, for the ring prover (max_keys given), key_of
     [count] slots below max_keys -> (cts, testv, checkpoints as a list, key_of as uint32 or None)"""
     who = "RingProver.resume" if max_keys is not None else "PbsProver.resume"
-    c, tv = _u64(cts), _u64(testv)
-    if c.ndim != 2 or c.shape[1] != n_lwe + 1 or tv.shape not in ((N,), (c.shape[0], N)):
-        raise ValueError("%s: expected cts [count][%d] and testv [%d] or [count][%d]" % (who, n_lwe + 1, N, N))
+    c, tv = _cts_testv(who, N, n_lwe, cts, testv)
     if int(steps) != steps or steps < 0 or steps > n_lwe + 2:
         raise ValueError("%s: steps must be 0 .. n_lwe + 2 = %d, got %r" % (who, n_lwe + 2, steps))
     if isinstance(checkpoints, (bytes, bytearray, memoryview)) or not hasattr(checkpoints, "__len__"):
@@ -1920,9 +1957,7 @@ def keyring_key_of(key_of, count, max_keys):
 
 def keyring_run_args(N, n_lwe, max_keys, cts, key_of, testv):
     """shapes of a KeyRing.run call, checked without a device: cts [count][n + 1], key_of [count], testv [N] or [count][N]"""
-    c, tv = _u64(cts), _u64(testv)
-    if c.ndim != 2 or c.shape[1] != n_lwe + 1 or tv.shape not in ((N,), (c.shape[0], N)):
-        raise ValueError("KeyRing.run: expected cts [count][%d] and testv [%d] or [count][%d]" % (n_lwe + 1, N, N))
+    c, tv = _cts_testv("KeyRing.run", N, n_lwe, cts, testv)
     return c, keyring_key_of(key_of, c.shape[0], max_keys), tv
 
 
@@ -1945,58 +1980,59 @@ def program_batch_args(n_inputs, n_lwe, N, n_luts, max_keys, inputs, key_of, tes
     return x, keyring_key_of(key_of, x.shape[0], max_keys), tv
 
 
-class KeyRing:
-    """vpbs_keyring: up to max_keys key sets of one shape resident on the device, and the whole PBS of a MIXED batch -- ciphertext i under
-    the key set of slot key_of[i] -- in one launch.  Row i of every output is what Bootstrapper(key set key_of[i]).run gives for it."""
+class _KeySlots:
+    """The slots of a key ring as KeyRing and RingProver fill them: add, add_seeded, remove.  The object is a _Handle with N, K, ELL and
+    n_lwe; _slot_err says whether its entries end in (err, err_len) -- the ring prover's do; the ring's leave the text with the context."""
+    _slot_err = False
 
-    def __init__(self, ctx, K, ELL, LOGB, N, n_lwe, max_keys, max_batch=64):
-        self.ctx, self.N, self.K, self.ELL, self.LOGB, self.n_lwe = ctx, N, K, ELL, LOGB, n_lwe
-        self.max_keys, self.max_batch = max_keys, max_batch
-        prm = TfheParamsC(N.bit_length() - 1, K, ELL, LOGB)
-        h, err = C.c_void_p(), C.create_string_buffer(512)
-        rc = lib().vpbs_keyring_create(ctx.h, C.byref(prm), n_lwe, max_keys, max_batch, C.byref(h), err, 512)
+    def _slot_call(self, name, *args):
+        err = C.create_string_buffer(512)
+        rc = self._entry(name)(self.h, *args, *((err, 512) if self._slot_err else ()))
         if rc:
-            raise VpbsError("vpbs_keyring_create: status %d: %s" % (rc, err.value.decode()))
-        self.h = h
-        ctx._batches.add(self)   # must not outlive its context: Context.close() frees the survivors
-
-    def _fail(self, what, rc):
-        e = VpbsError("%s: status %d: %s" % (what, rc, lib().vpbs_last_error(self.ctx.h).decode()))
-        e.status = rc
-        return e
+            raise self._fail("%s_%s" % (self._prefix, name), rc, (err.value if self._slot_err else lib().vpbs_last_error(self.ctx.h)).decode())
 
     def add(self, bsk, ksk, keys_on_device=False):
         """bsk [n][K*ELL*K*N], ksk [K*ELL*K*N] (keygen's layout) uploaded once, or device pointers (integers) adopted with
-        keys_on_device=True -- they must stay allocated until the slot is removed.  Returns the slot: the lowest free number."""
-        g = self.K * self.ELL * self.K * self.N
-        if keys_on_device:
-            pb, pk = C.c_void_p(int(bsk)), C.c_void_p(int(ksk))
-        else:
-            b, k = _u64(bsk), _u64(ksk).reshape(-1)
-            if b.shape != (self.n_lwe, g) or k.size != g:
-                raise ValueError("KeyRing.add: expected bsk [%d][%d] and ksk [%d]" % (self.n_lwe, g, g))
-            pb, pk = C.c_void_p(b.ctypes.data), C.c_void_p(k.ctypes.data)
+        keys_on_device=True -- they must stay allocated until the slot is removed.  Returns the slot: the lowest free number.  The ring
+        prover also walks the key hash chain of the key set once, on the host."""
+        pb, pk, _, _, _keep = _key_args(type(self).__name__ + ".add", bsk, ksk, self.K, self.ELL, self.N, self.n_lwe, keys_on_device)
         slot = C.c_uint()
-        rc = lib().vpbs_keyring_add(self.h, pb, pk, 1 if keys_on_device else 0, C.byref(slot))
-        if rc:
-            raise self._fail("vpbs_keyring_add", rc)
+        self._slot_call("add", pb, pk, 1 if keys_on_device else 0, C.byref(slot))
         return slot.value
 
     def add_seeded(self, mask_seed, bsk_bodies, ksk_bodies, bodies_on_device=False):
-        """vpbs_keyring_add_seeded: the key set of Context.key_expand(mask_seed, bodies), expanded on the device into memory the ring owns
+        """<_prefix>_add_seeded: the key set of Context.key_expand(mask_seed, bodies), expanded on the device into memory the ring owns
         (remove frees it).  bsk_bodies [n][K*ELL*N], ksk_bodies [K*ELL*N] (keygen_seeded's layout, 1 / K of the key set), or device pointers
-        (integers) with bodies_on_device=True -- they are read during the call only.  Returns the slot: the lowest free number."""
+        (integers) with bodies_on_device=True -- they are read during the call only.  Returns the slot: the lowest free number.  The ring
+        prover downloads the expanded key set once for its key hash chain, as add does for keys that are on the device only."""
         pb, pk, _keep = _seeded_add_args(self, bsk_bodies, ksk_bodies, bodies_on_device)
         slot = C.c_uint()
-        rc = lib().vpbs_keyring_add_seeded(self.h, int(mask_seed), pb, pk, 1 if bodies_on_device else 0, C.byref(slot))
-        if rc:
-            raise self._fail("vpbs_keyring_add_seeded", rc)
+        self._slot_call("add_seeded", int(mask_seed), pb, pk, 1 if bodies_on_device else 0, C.byref(slot))
         return slot.value
 
     def remove(self, slot):
-        rc = lib().vpbs_keyring_remove(self.h, int(slot))
-        if rc:
-            raise self._fail("vpbs_keyring_remove", rc)
+        self._slot_call("remove", int(slot))
+
+
+class KeyRing(_KeySlots, _ChainRun):
+    """vpbs_keyring: up to max_keys key sets of one shape resident on the device, and the whole PBS of a MIXED batch -- ciphertext i under
+    the key set of slot key_of[i] -- in one launch.  Row i of every output is what Bootstrapper(key set key_of[i]).run gives for it."""
+    _prefix = "vpbs_keyring"
+    _ring = True
+
+    def __init__(self, ctx, K, ELL, LOGB, N, n_lwe, max_keys, max_batch=64):
+        self.N, self.K, self.ELL, self.LOGB, self.n_lwe = N, K, ELL, LOGB, n_lwe
+        self.max_keys, self.max_batch = max_keys, max_batch
+        prm = TfheParamsC(N.bit_length() - 1, K, ELL, LOGB)
+        self._construct(ctx, ctx.h, C.byref(prm), n_lwe, max_keys, max_batch)
+
+    @classmethod
+    def _view(cls, h, ctx, N, K, ELL, LOGB, n_lwe, max_keys, max_batch):
+        """a KeyRing on a handle that another object owns and frees (RingProver.keyring): close() forgets the handle, nothing more"""
+        ring = cls.__new__(cls)
+        ring.h, ring.ctx, ring._owns = h, ctx, False
+        ring.N, ring.K, ring.ELL, ring.LOGB, ring.n_lwe, ring.max_keys, ring.max_batch = N, K, ELL, LOGB, n_lwe, max_keys, max_batch
+        return ring
 
     def count(self):
         return lib().vpbs_keyring_count(self.h)
@@ -2004,55 +2040,15 @@ class KeyRing:
     def run(self, cts, key_of, testv, accumulators=False):
         """cts [count][n + 1]; key_of [count] slots; testv [N] shared or [count][N] -> (out_ct [count][K][N], lwe_out [count][n + 1]) and,
         with accumulators=True, every intermediate accumulator [count][n + 2][K][N]"""
-        c, ko, tv = keyring_run_args(self.N, self.n_lwe, self.max_keys, cts, key_of, testv)
-        count = c.shape[0]
-        out_ct, lwe_out = np.zeros((count, self.K, self.N), np.uint64), np.zeros((count, self.n_lwe + 1), np.uint64)
-        accs = np.zeros((count, self.n_lwe + 2, self.K, self.N), np.uint64) if accumulators else None
-        keep = np.zeros(1, np.uint64)   # a valid pointer for an empty batch
-        p = lambda a: (a if a.size else keep).ctypes.data
-        rc = lib().vpbs_keyring_run(self.h, p(c), count, p(ko), p(tv), 1 if tv.ndim == 2 else 0, p(out_ct), p(lwe_out),
-                                    p(accs) if accumulators else None, 0)
-        if rc != count:
-            raise self._fail("vpbs_keyring_run", rc)
-        return (out_ct, lwe_out, accs) if accumulators else (out_ct, lwe_out)
+        return self._run(cts, testv, accumulators, key_of)
 
     def run_from(self, cts, key_of, start, acc_in, testv, accumulators=False):
         """Bootstrapper.run_from under the key set of slot key_of[i] (vpbs_keyring_run_from)"""
-        c, st, acc, tv = run_from_args(self.N, self.K, self.n_lwe, cts, start, acc_in, testv, "KeyRing.run_from")
-        count = c.shape[0]
-        ko = keyring_key_of(key_of, count, self.max_keys)
-        out_ct, lwe_out = np.zeros((count, self.K, self.N), np.uint64), np.zeros((count, self.n_lwe + 1), np.uint64)
-        accs = _accs_out(accumulators, count, self.n_lwe, self.K, self.N, "KeyRing.run_from")
-        keep = np.zeros(1, np.uint64)   # a valid pointer for an empty batch
-        p = lambda a: (a if a.size else keep).ctypes.data
-        rc = lib().vpbs_keyring_run_from(self.h, p(c), count, p(ko), p(st), None if acc is None else p(acc), p(tv), 1 if tv.ndim == 2 else 0,
-                                         p(out_ct), p(lwe_out), None if accs is None else p(accs), 0)
-        if rc != count:
-            raise self._fail("vpbs_keyring_run_from", rc)
-        return (out_ct, lwe_out) if accs is None else (out_ct, lwe_out, accs)
+        return self._run_from(cts, start, acc_in, testv, accumulators, key_of)
 
     def run_device(self, d_cts, count, key_of, d_testv, testv_per_ct=False, d_out_ct=None, d_lwe_out=None, d_accs=None):
         """the same on device pointers (integers; None = output not wanted); key_of stays a host array; returns when the outputs are in place"""
-        ko = keyring_key_of(key_of, count, self.max_keys)
-        q = lambda x: C.c_void_p(int(x)) if x else None
-        rc = lib().vpbs_keyring_run(self.h, q(d_cts), count, (ko if ko.size else np.zeros(1, np.uint32)).ctypes.data, q(d_testv),
-                                    1 if testv_per_ct else 0, q(d_out_ct), q(d_lwe_out), q(d_accs), 1)
-        if rc != count:
-            raise self._fail("vpbs_keyring_run", rc)
-
-    def close(self):
-        if self.h:
-            lib().vpbs_keyring_free(self.h)
-            self.h = None
-            self.ctx._batches.discard(self)
-
-    free = close
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._run_device(d_cts, count, d_testv, testv_per_ct, d_out_ct, d_lwe_out, d_accs, key_of)
 
 
 def ivc_preset_matrix_for_tests(proof_words, n_lwe, first, pis, ct, bsk, ksk, cyclic_vk, dummy_vk, dummy_proof):
@@ -2078,29 +2074,16 @@ class PbsProveError(VpbsError):
         self.failures, self.proofs, self.out_ct, self.lwe_out = failures, proofs, out_ct, lwe_out
 
 
-class _BatchProver:
-    """What PbsProver and RingProver share: the handle of a C object whose entry points are named <_prefix>_*, with the chains' settings,
-    the checkpoint callback, the run behind prove and resume, and the statistics of the last run."""
-    _prefix = None
+class _BatchProver(_Handle):
+    """What PbsProver and RingProver share: the chains' settings, the checkpoint callback, the run behind prove and resume, and the
+    statistics of the last run.  The object lives on a device, not on a Context of the caller's."""
 
-    def _entry(self, name):
-        return getattr(lib(), "%s_%s" % (self._prefix, name))
-
-    def _fail(self, what, rc, err):
-        e = VpbsError("%s: status %d: %s" % (what, rc, err.value.decode()))
-        e.status = rc
-        return e
-
-    def _create(self, cyclic, dummy, N, K, ELL, LOGB, create):
-        """create(cyclic, dummy, prm, handle, err): the call of the C constructor with these five filled in -> its status"""
+    def _create(self, device, cyclic, dummy, N, K, ELL, LOGB, *create_args):
+        """create_args: what <_prefix>_create takes behind (device, cyclic, dummy, TFHE parameters)"""
         keep = []
         cy, du = _ivc_circuit(cyclic, cyclic.meta["proof_words"], keep), _ivc_circuit(dummy, 0, keep)
         prm = TfheParamsC(N.bit_length() - 1, K, ELL, LOGB)
-        self.h, err = C.c_void_p(), C.create_string_buffer(512)
-        rc = create(C.byref(cy), C.byref(du), C.byref(prm), C.byref(self.h), err)
-        if rc:
-            self.h = None
-            raise self._fail(self._prefix + "_create", rc, err)
+        self._construct(None, device, C.byref(cy), C.byref(du), C.byref(prm), *create_args, status=True)
         self.vk_words = 4 + (4 << 4)
         self._proof_words = cyclic.meta["proof_words"]
         self._ckpt_cb = self._ckpt_error = None
@@ -2167,23 +2150,21 @@ class _BatchProver:
             except BaseException as e:   # noqa: BLE001 -- must not unwind through the C frames
                 raised.append(e)
         cb, err = PBS_PROOF_FN(trampoline), C.create_string_buffer(512)
-        keep = np.zeros(1, np.uint64)   # a valid pointer for an empty batch
-        p = lambda a: _ptr(a if a.size else keep)
-        args = [self.h, p(c), count] + ([] if key_of is None else [(key_of if key_of.size else np.zeros(1, np.uint32)).ctypes.data])
-        args += [p(tv), 1 if tv.ndim == 2 else 0]
+        args = [self.h, _keep_ptr(c), count] + ([] if key_of is None else [_keep_u32(key_of)])
+        args += [_keep_ptr(tv), 1 if tv.ndim == 2 else 0]
         what = self._prefix + "_run"
         if cps is not None:
             what = self._prefix + "_resume"
             ptrs, lens, alive = _checkpoint_arrays(cps)
             args += [C.addressof(ptrs), C.addressof(lens)]
-        n = getattr(lib(), what)(*args, steps, p(out_ct), p(lwe_out), cb, None, err, 512)
+        n = getattr(lib(), what)(*args, steps, _keep_ptr(out_ct), _keep_ptr(lwe_out), cb, None, err, 512)
         if raised:
             raise raised[0]
         e, self._ckpt_error = self._ckpt_error, None
         if e is not None:
             raise e
         if n < 0:
-            raise self._fail(what, n, err)
+            raise self._fail(what, n, err.value.decode())
         if failures:
             raise PbsProveError(dict(failures), proofs, out_ct, lwe_out)
         return proofs, out_ct, lwe_out, errors
@@ -2196,19 +2177,6 @@ class _BatchProver:
         return {"seconds": st.seconds, "outputs_seconds": st.outputs_seconds, "proofs": st.proofs, "prepare_chain_ms": st.prepare_chain_ms,
                 "chain": {f: getattr(st.chain, f) for f, _ in IvcTimingC._fields_}}
 
-    def close(self):
-        if self.h:
-            self._entry("free")(self.h)
-            self.h = None
-
-    free = close
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 class PbsProver(_BatchProver):
     """vpbs_pbs_prover: the bootstraps of a batch of LWE ciphertexts AND their vPBS proofs under one key set that stays on the device.
@@ -2219,20 +2187,11 @@ class PbsProver(_BatchProver):
     _prefix = "vpbs_pbs_prover"
 
     def __init__(self, device, cyclic, dummy, bsk, ksk, K, ELL, LOGB, chains=8, witness_batch=64, keys_on_device=False, N=None, n_lwe=None):
-        ggsw_words = lambda N: K * ELL * K * N
-        if keys_on_device:
-            if N is None or n_lwe is None:
-                raise ValueError("PbsProver: device keys need N and n_lwe")
-            pb, pk = C.c_void_p(int(bsk)), C.c_void_p(int(ksk))
-        else:
-            b, k = _u64(bsk), _u64(ksk).reshape(-1)
-            n_lwe, N = b.shape[0], k.size // (K * ELL * K)
-            if b.shape != (n_lwe, ggsw_words(N)) or k.size != ggsw_words(N):
-                raise ValueError("PbsProver: expected bsk [n][K*ELL*K*N] and ksk [K*ELL*K*N]")
-            pb, pk = C.c_void_p(b.ctypes.data), C.c_void_p(k.ctypes.data)
+        if not keys_on_device:
+            N = n_lwe = None   # host keys say their own shape
+        pb, pk, N, n_lwe, _keep = _key_args("PbsProver", bsk, ksk, K, ELL, N, n_lwe, keys_on_device)
         self.N, self.K, self.ELL, self.LOGB, self.n_lwe, self.chains = N, K, ELL, LOGB, n_lwe, chains
-        self._create(cyclic, dummy, N, K, ELL, LOGB, lambda cy, du, prm, h, err: lib().vpbs_pbs_prover_create(
-            device, cy, du, prm, n_lwe, pb, pk, 1 if keys_on_device else 0, chains, witness_batch, h, err, 512))
+        self._create(device, cyclic, dummy, N, K, ELL, LOGB, n_lwe, pb, pk, 1 if keys_on_device else 0, chains, witness_batch)
 
     def key_hash(self):
         """the end of the key hash chain walked at creation: what PbsVerifier takes (= pbs_key_hash(bsk, ksk))"""
@@ -2246,9 +2205,7 @@ class PbsProver(_BatchProver):
         it raises is re-raised here after the run has drained.  A chain that fails does not stop the others: after the run PbsProveError is
         raised, naming the failed indices, with .failures {index: message} and .proofs (None at the failed indices), .out_ct, .lwe_out --
         everything the chains that succeeded delivered."""
-        c, tv = _u64(cts), _u64(testv)
-        if c.ndim != 2 or c.shape[1] != self.n_lwe + 1 or tv.shape not in ((self.N,), (c.shape[0], self.N)):
-            raise ValueError("PbsProver.prove: expected cts [count][%d] and testv [%d] or [count][%d]" % (self.n_lwe + 1, self.N, self.N))
+        c, tv = _cts_testv("PbsProver.prove", self.N, self.n_lwe, cts, testv)
         return self._run(c, tv, None, steps, on_proof)[:3]
 
     def resume(self, cts, testv, checkpoints, steps=0, on_proof=None):
@@ -2282,9 +2239,7 @@ class PbsProver(_BatchProver):
 def ring_prove_args(N, n_lwe, max_keys, cts, key_of, testv, steps=0):
     """shapes of a RingProver.prove call, checked without a device: cts [count][n + 1], key_of [count] slots below max_keys (any integer
     dtype; the offending index is named), testv [N] or [count][N], steps 0 .. n + 2 -> (cts, key_of as uint32, testv), contiguous"""
-    c, tv = _u64(cts), _u64(testv)
-    if c.ndim != 2 or c.shape[1] != n_lwe + 1 or tv.shape not in ((N,), (c.shape[0], N)):
-        raise ValueError("RingProver.prove: expected cts [count][%d] and testv [%d] or [count][%d]" % (n_lwe + 1, N, N))
+    c, tv = _cts_testv("RingProver.prove", N, n_lwe, cts, testv)
     if int(steps) != steps or steps < 0 or steps > n_lwe + 2:
         raise ValueError("RingProver.prove: steps must be 0 .. n_lwe + 2 = %d, got %r" % (n_lwe + 2, steps))
     return c, keyring_key_of(key_of, c.shape[0], max_keys), tv
@@ -2297,65 +2252,28 @@ class _RingContext:
         self.h, self._batches = h, set()
 
 
-class RingProver(_BatchProver):
+class RingProver(_KeySlots, _BatchProver):
     """vpbs_ring_prover: ONE prover for all clients of a key ring.  The object owns a KeyRing of max_keys slots, `chains` IVC chains in the
     device-witness pipeline and the key hash chain of every slot; prove() bootstraps and proves ciphertext i under the key set of slot
     key_of[i], and its proof is byte for byte what a PbsProver of that key set gives.  cyclic / dummy, chains, witness_batch: as PbsProver.
     .keyring is a KeyRing view of the owned ring (KeyRing.run and Program.run_batch evaluate on the same resident keys; it is not closed
     by the caller, and its add / remove are refused: key sets come and go through this object, which keeps their key links)."""
     _prefix = "vpbs_ring_prover"
+    _slot_err = True
+    keyring = None
 
     def __init__(self, device, cyclic, dummy, K, ELL, LOGB, N, n_lwe, max_keys, chains=8, witness_batch=64):
         self.N, self.K, self.ELL, self.LOGB, self.n_lwe, self.chains, self.max_keys = N, K, ELL, LOGB, n_lwe, chains, max_keys
-        self._create(cyclic, dummy, N, K, ELL, LOGB, lambda cy, du, prm, h, err: lib().vpbs_ring_prover_create(
-            device, cy, du, prm, n_lwe, max_keys, chains, witness_batch, h, err, 512))
-        ring = KeyRing.__new__(KeyRing)   # a view: the handle is the prover's, and goes with it
-        ring.ctx = _RingContext(C.c_void_p(lib().vpbs_ring_prover_context(self.h)))
-        ring.N, ring.K, ring.ELL, ring.LOGB, ring.n_lwe, ring.max_keys, ring.max_batch = N, K, ELL, LOGB, n_lwe, max_keys, 256
-        ring.h = C.c_void_p(lib().vpbs_ring_prover_keyring(self.h))
-        ring.close = ring.free = lambda: None
-        self.keyring = ring
-
-    def add(self, bsk, ksk, keys_on_device=False):
-        """KeyRing.add on the owned ring, and the key hash chain of the key set walked once, on the host.  Returns the slot."""
-        g = self.K * self.ELL * self.K * self.N
-        if keys_on_device:
-            pb, pk = C.c_void_p(int(bsk)), C.c_void_p(int(ksk))
-        else:
-            b, k = _u64(bsk), _u64(ksk).reshape(-1)
-            if b.shape != (self.n_lwe, g) or k.size != g:
-                raise ValueError("RingProver.add: expected bsk [%d][%d] and ksk [%d]" % (self.n_lwe, g, g))
-            pb, pk = C.c_void_p(b.ctypes.data), C.c_void_p(k.ctypes.data)
-        slot, err = C.c_uint(), C.create_string_buffer(512)
-        rc = lib().vpbs_ring_prover_add(self.h, pb, pk, 1 if keys_on_device else 0, C.byref(slot), err, 512)
-        if rc:
-            raise self._fail("vpbs_ring_prover_add", rc, err)
-        return slot.value
-
-    def add_seeded(self, mask_seed, bsk_bodies, ksk_bodies, bodies_on_device=False):
-        """KeyRing.add_seeded on the owned ring, and the key hash chain of the expanded key set: one download, then the host walk, as add
-        does for keys that are on the device only.  Returns the slot."""
-        pb, pk, _keep = _seeded_add_args(self, bsk_bodies, ksk_bodies, bodies_on_device)
-        slot, err = C.c_uint(), C.create_string_buffer(512)
-        rc = lib().vpbs_ring_prover_add_seeded(self.h, int(mask_seed), pb, pk, 1 if bodies_on_device else 0, C.byref(slot), err, 512)
-        if rc:
-            raise self._fail("vpbs_ring_prover_add_seeded", rc, err)
-        return slot.value
-
-    def remove(self, slot):
-        err = C.create_string_buffer(512)
-        rc = lib().vpbs_ring_prover_remove(self.h, int(slot), err, 512)
-        if rc:
-            raise self._fail("vpbs_ring_prover_remove", rc, err)
+        self._create(device, cyclic, dummy, N, K, ELL, LOGB, n_lwe, max_keys, chains, witness_batch)
+        self.keyring = KeyRing._view(C.c_void_p(lib().vpbs_ring_prover_keyring(self.h)), _RingContext(C.c_void_p(lib().vpbs_ring_prover_context(self.h))),
+                                     N, K, ELL, LOGB, n_lwe, max_keys, 256)
 
     def key_hash(self, slot):
         """the end of the slot's key hash chain: what the PbsVerifier of that client takes (= pbs_key_hash(bsk, ksk))"""
         out = np.zeros(4, np.uint64)
         rc = lib().vpbs_ring_prover_key_hash(self.h, int(slot), _ptr(out))
         if rc:
-            e = VpbsError("vpbs_ring_prover_key_hash: status %d: slot %d holds no key set" % (rc, slot))
-            e.status = rc
-            raise e
+            raise self._fail("vpbs_ring_prover_key_hash", rc, "slot %d holds no key set" % slot)
         return out
 
     def prove(self, cts, key_of, testv, steps=0, on_proof=None, out_ct=None, lwe_out=None):
@@ -2373,12 +2291,10 @@ class RingProver(_BatchProver):
         c, tv, cps, ko = resume_args(self.N, self.n_lwe, cts, testv, checkpoints, steps, key_of, self.max_keys)
         return self._run(c, tv, cps, steps, on_proof, ko, out_ct, lwe_out)
 
-    def close(self):
-        if self.h:
-            self.keyring.h = None   # the view first: its handle goes with the prover's
-        super().close()
-
-    free = close
+    def _release(self):
+        if self.keyring is not None:
+            self.keyring.close()   # the view first: its handle goes with the prover's
+        super()._release()
 
 
 def ring_verify_args(N, K, n_lwe, max_keys, max_batch, count, key_of, testvs, cts, out_cts, testv_of=None):
@@ -2415,28 +2331,19 @@ def ring_verify_args(N, K, n_lwe, max_keys, max_batch, count, key_of, testvs, ct
     return ko, tv, c, np.ascontiguousarray(o.reshape(count, K * N)), to
 
 
-class RingVerifier:
+class RingVerifier(_PbsVerify):
     """vpbs_ring_verifier: ONE device verifier of whole vPBS proofs for the clients of a key ring.  Slot s holds the key hash of a key set
     (pbs_key_hash, or RingProver.key_hash(s): the caller chooses the slot, so the slots can be the ring prover's); verify() checks proof i
     against slot key_of[i] and gives it what a PbsVerifier made from that slot's key hash gives.  The parameters mirror PbsVerifier."""
+    _prefix = "vpbs_ring_verifier"
+    _run_err = True
 
     def __init__(self, ctx, cs_cap, ncols, circuit_digest, log_n, n_constants, n_routed, gates, N, K, n_lwe, ggsw_len, max_keys, max_batch=512,
                  num_challenges=2, quotient_degree_factor=8, rate_bits=3, cap_height=4, compat=None):
-        self.ctx, self.max_keys, self.max_batch, self.N, self.K, self.n_lwe = ctx, max_keys, max_batch, N, K, n_lwe
-        p, self._keep = _verify_pbs_shape(cs_cap, ncols, circuit_digest, log_n, n_constants, n_routed, gates, N, K, n_lwe, ggsw_len, num_challenges,
-                                          quotient_degree_factor, rate_bits, cap_height, compat)
-        h, err = C.c_void_p(), C.create_string_buffer(512)
-        rc = lib().vpbs_ring_verifier_create(ctx.h, C.byref(p), max_keys, max_batch, C.byref(h), err, 512)
-        if rc:
-            self.h = None
-            raise VpbsError("vpbs_ring_verifier_create: status %d: %s" % (rc, err.value.decode()))
-        self.h = h
-        ctx._batches.add(self)   # must not outlive its context: Context.close() frees the survivors
-
-    def _status(self, what, rc, text=""):
-        e = VpbsError("%s: status %d%s" % (what, rc, ": " + text if text else ""))
-        e.status = rc
-        return e
+        self.max_keys = max_keys
+        shape = (cs_cap, ncols, circuit_digest, log_n, n_constants, n_routed, gates, N, K, n_lwe, ggsw_len, num_challenges, quotient_degree_factor,
+                 rate_bits, cap_height, compat)
+        self._create(ctx, shape, N, K, n_lwe, max_batch, max_keys)
 
     def set_key(self, slot, key_hash):
         """fills or replaces a slot with a key hash [4]"""
@@ -2445,55 +2352,29 @@ class RingVerifier:
             raise ValueError("RingVerifier.set_key: a key hash is 4 words, got %d" % kh.size)
         rc = lib().vpbs_ring_verifier_set_key(self.h, int(slot), _ptr(kh))
         if rc:
-            raise self._status("vpbs_ring_verifier_set_key", rc, "slot %d of %d" % (slot, self.max_keys))
+            raise self._fail("vpbs_ring_verifier_set_key", rc, "slot %d of %d" % (slot, self.max_keys))
 
     def clear_key(self, slot):
         rc = lib().vpbs_ring_verifier_clear_key(self.h, int(slot))
         if rc:
-            raise self._status("vpbs_ring_verifier_clear_key", rc, "slot %d is empty or out of range" % slot)
+            raise self._fail("vpbs_ring_verifier_clear_key", rc, "slot %d is empty or out of range" % slot)
 
     def count(self):
         return int(lib().vpbs_ring_verifier_count(self.h))
 
+    def _statement(self, count, key_of, testvs, cts, out_cts, testv_of):
+        ko, tv, c, o, to = ring_verify_args(self.N, self.K, self.n_lwe, self.max_keys, self.max_batch, count, key_of, testvs, cts, out_cts, testv_of)
+        return _keep_u32(ko), _keep_ptr(tv.reshape(-1)), tv.shape[0], _keep_u32(to), _keep_ptr(c.reshape(-1)), _keep_ptr(o.reshape(-1))
+
     def verify_packed(self, buf, offsets, key_of, testvs, cts, out_cts, testv_of=None):
         """buf, offsets: pack_proofs; the rest as verify"""
-        buf = np.ascontiguousarray(buf, dtype=np.uint8)
-        offs = np.ascontiguousarray(offsets, dtype=np.uint64)
-        count = offs.size - 1
-        ko, tv, c, o, to = ring_verify_args(self.N, self.K, self.n_lwe, self.max_keys, self.max_batch, count, key_of, testvs, cts, out_cts, testv_of)
-        verdicts, reasons, sub = (np.zeros(count, np.uint8) for _ in range(3))
-        u8p = C.POINTER(C.c_uint8)
-        data = buf.ctypes.data_as(u8p) if buf.size else (C.c_uint8 * 1)()
-        keep, keep32 = np.zeros(1, np.uint64), np.zeros(1, np.uint32)   # valid pointers for empty arrays
-        ptr = lambda a: _ptr(a) if a.size else _ptr(keep)
-        p32 = lambda a: None if a is None else (a if a.size else keep32).ctypes.data
-        err = C.create_string_buffer(512)
-        rc = lib().vpbs_ring_verifier_run(self.h, data, offs.ctypes.data_as(C.POINTER(C.c_size_t)), count, p32(ko), ptr(tv.reshape(-1)), tv.shape[0],
-                                          p32(to), ptr(c.reshape(-1)), ptr(o.reshape(-1)), verdicts.ctypes.data_as(u8p), reasons.ctypes.data_as(u8p),
-                                          sub.ctypes.data_as(u8p), err, 512)
-        if rc < 0:
-            raise self._status("vpbs_ring_verifier_run", rc, err.value.decode())
-        return verdicts, reasons, sub
+        return self._verify(buf, offsets, key_of, testvs, cts, out_cts, testv_of)
 
     def verify(self, blobs, key_of, testvs, cts, out_cts, testv_of=None):
         """blobs: list of serialised vPBS proofs; key_of [count] slots; testvs [N] shared, [count][N], or a table [n_testv][N] addressed by
         testv_of [count]; cts [count][n + 1]; out_cts [count][K][N] -> (verdicts, reasons, proof_reasons), np.uint8 each.  A key_of entry
         that names an empty slot raises VpbsError (.status = VPBS_ERR_INVALID) before anything runs."""
         return self.verify_packed(*pack_proofs(blobs), key_of, testvs, cts, out_cts, testv_of)
-
-    def close(self):
-        if self.h:
-            lib().vpbs_ring_verifier_free(self.h)
-            self.h = None
-            self.ctx._batches.discard(self)
-
-    free = close
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 # ---- aggregation: the vPBS proofs of a batch folded into one proof (csrc/aggregate.hip, DESIGN.md 8.14) ----
@@ -2585,10 +2466,8 @@ def _aggregate_args(who, N, K, n_lwe, testvs, cts, out_cts, key_hashes, key_of, 
 
 
 def _aggregate_ptrs(tv, c, o, kh, ko, to):
-    keep = np.zeros(1, np.uint64)   # a valid pointer for an empty array
-    p = lambda a: (a if a.size else keep).ctypes.data
-    p32 = lambda a: None if a is None else (a if a.size else keep).ctypes.data
-    return (keep, C.cast(p(tv), U64P), tv.shape[0], p32(to), C.cast(p(c), U64P), C.cast(p(o), U64P), C.cast(p(kh), U64P), kh.shape[0], p32(ko))
+    """the statement arrays of _aggregate_args in the order every aggregate entry point takes them"""
+    return (_keep_ptr(tv), tv.shape[0], _keep_u32(to), _keep_ptr(c), _keep_ptr(o), _keep_ptr(kh), kh.shape[0], _keep_u32(ko))
 
 
 def aggregate_root(N, K, n_lwe, vk0, testvs, cts, out_cts, key_hashes, key_of=None, testv_of=None):
@@ -2599,13 +2478,13 @@ def aggregate_root(N, K, n_lwe, vk0, testvs, cts, out_cts, key_hashes, key_of=No
     vk = _u64(vk0).reshape(-1)
     if vk.size != AGG_VK_WORDS:
         raise ValueError("aggregate_root: vk0 is 68 words (digest, cap), got %d" % vk.size)
-    keep, ptv, n_tv, pto, pc, po, pkh, n_kh, pko = _aggregate_ptrs(tv, c, o, kh, ko, to)
     out = np.zeros(4, np.uint64)
-    rc = lib().vpbs_aggregate_root(N, K, n_lwe, _ptr(vk), count, ptv, n_tv, pto, pc, po, pkh, n_kh, pko, _ptr(out))
+    rc = lib().vpbs_aggregate_root(N, K, n_lwe, _ptr(vk), count, *_aggregate_ptrs(tv, c, o, kh, ko, to), _ptr(out))
     if rc == 1:
         raise VpbsError("vpbs_aggregate_root: a word of the statement is not a field element (at or above p): no proof has this statement")
     if rc:
-        raise VpbsError("vpbs_aggregate_root: malformed arguments (count = %d; indices below n_testv = %d and n_keys = %d)" % (count, n_tv, n_kh))
+        raise VpbsError("vpbs_aggregate_root: malformed arguments (count = %d; indices below n_testv = %d and n_keys = %d)" %
+                        (count, tv.shape[0], kh.shape[0]))
     return out
 
 
@@ -2615,10 +2494,9 @@ def verify_aggregate(shape, blob, count, testvs, cts, out_cts, key_hashes, key_o
     n, tv, c, o, kh, ko, to = _aggregate_args("verify_aggregate", shape.N, shape.K, shape.n_lwe, testvs, cts, out_cts, key_hashes, key_of, testv_of)
     if n != count:
         raise ValueError("verify_aggregate: count = %d but the statement has %d leaves" % (count, n))
-    keep, ptv, n_tv, pto, pc, po, pkh, n_kh, pko = _aggregate_ptrs(tv, c, o, kh, ko, to)
     buf = (C.c_uint8 * max(1, len(blob))).from_buffer_copy(bytes(blob) or b"\0")
     why, reason = C.create_string_buffer(256), C.c_int(0)
-    rc = lib().vpbs_verify_aggregate(C.byref(shape.c), count, ptv, n_tv, pto, pc, po, pkh, n_kh, pko, buf, len(blob), C.byref(reason), why, 256)
+    rc = lib().vpbs_verify_aggregate(C.byref(shape.c), count, *_aggregate_ptrs(tv, c, o, kh, ko, to), buf, len(blob), C.byref(reason), why, 256)
     if rc < 0:
         raise VpbsError("vpbs_verify_aggregate: " + why.value.decode())
     return rc == 1, int(reason.value)
@@ -2646,16 +2524,6 @@ def program_aggregate_args(who, n_inputs, n_gates, n_luts, N, K, n_lwe, inputs, 
             raise ValueError("%s: a key hash is 4 words, got %d" % (who, kh.size))
     c = np.ascontiguousarray
     return c(x), c(o.reshape(lead + (n_gates, K * N))), None if tv is None else c(tv), None if kh is None else c(kh)
-
-
-def _keep_ptr(a):
-    """a uint64 array as a pointer -- a valid one for an empty array too; None stays None"""
-    return None if a is None else _ptr(a if a.size else np.zeros(1, np.uint64))
-
-
-def _keep_u32(a):
-    """the same for a uint32 array, as a void pointer"""
-    return (a if a.size else np.zeros(1, np.uint32)).ctypes.data_as(C.c_void_p)
 
 
 def program_gate_inputs(prog, N, K, n_lwe, inputs, out_cts):
@@ -2741,13 +2609,14 @@ def aggregate_level_jobs(counts, level):
     return tree[:n], left[:n], right[:n]
 
 
-class Aggregator:
+class Aggregator(_Handle):
     """vpbs_aggregator: folds serialised vPBS proofs into one proof.  leaf: the cyclic step circuit (a loaded circuit file) with its
     verifier data leaf_vk [68] (digest, cap: PbsProver / RingProver.verifier_data()[0]); level_circuits: A_1 .. A_levels as loaded circuit
     files (circuit_file.find_aggregate_circuits) -- up to 2^levels leaves."""
+    _prefix = "vpbs_aggregator"
 
     def __init__(self, ctx, leaf, leaf_vk, level_circuits):
-        self.ctx, self.levels = ctx, len(level_circuits)
+        self.levels = len(level_circuits)
         self._vk0 = _u64(leaf_vk).reshape(-1).copy()
         if self._vk0.size != AGG_VK_WORDS:
             raise ValueError("Aggregator: leaf_vk is 68 words (digest, cap), got %d" % self._vk0.size)
@@ -2757,23 +2626,10 @@ class Aggregator:
         for i in range(4):
             v.circuit_digest[i] = int(self._vk0[i])
         self._keep = [leaf, v]
-        arr = (IvcCircuitC * self.levels)()
-        for c, d in zip(arr, level_circuits):
-            pre = np.ascontiguousarray(d.preset_flat, dtype=np.uint32)
-            pi = np.ascontiguousarray(d.pi_flat, dtype=np.uint32)
-            self._keep += [pre, pi, d]
-            c.circuit = C.pointer(d.circuit.c)
-            c.preset_pos, c.n_preset = pre.ctypes.data_as(U32P), pre.size
-            c.pi_pos, c.n_pi = pi.ctypes.data_as(U32P), pi.size
-            c.proof_words = d.meta["proof_words"]
-        self.h, err = C.c_void_p(), C.create_string_buffer(512)
-        rc = lib().vpbs_aggregator_create(ctx.h, C.byref(v), len(leaf.pi_pos), arr, self.levels, C.byref(self.h), err, 512)
-        if rc:
-            self.h = None
-            raise VpbsError("status %d: %s" % (rc, err.value.decode()))
+        arr = (IvcCircuitC * self.levels)(*[_ivc_circuit(d, d.meta["proof_words"], self._keep) for d in level_circuits])
+        self._construct(ctx, ctx.h, C.byref(v), len(leaf.pi_pos), arr, self.levels, what="")
         top = level_circuits[-1]
         self.max_bytes = 8 * (top.circuit.n_wires * 64 + (1 << 17)) + 8 * len(top.pi_pos)
-        ctx._batches.add(self)   # must not outlive its context: Context.close() frees the survivors
 
     def verifier_data(self):
         """-> [levels + 1][68]: vk_0 (the cyclic circuit's) .. vk_levels, what an AggregateShape takes"""
@@ -2784,17 +2640,11 @@ class Aggregator:
     def aggregate(self, blobs):
         """serialised vPBS proofs (1 .. 2^levels of them) -> the aggregate proof's bytes.  A leaf that does not parse, does not verify or
         carries other verifier data raises VpbsError("... leaf i: ...") before anything is proven (last_run()["nodes"] == 0)."""
-        buf, offs = pack_proofs(blobs)
-        out = np.zeros(self.max_bytes, np.uint8)
-        u8p = C.POINTER(C.c_uint8)
-        data = buf.ctypes.data_as(u8p) if buf.size else (C.c_uint8 * 1)()
-        err = C.create_string_buffer(512)
-        n = lib().vpbs_aggregator_run(self.h, data, offs.ctypes.data_as(C.POINTER(C.c_size_t)), len(blobs), out.ctypes.data_as(u8p), out.size, None,
-                                      err, 512)
+        count, data, offs, _, _ = _packed(blobs)
+        out, err = np.zeros(self.max_bytes, np.uint8), C.create_string_buffer(512)
+        n = lib().vpbs_aggregator_run(self.h, data, offs, count, out.ctypes.data_as(U8P), out.size, None, err, 512)
         if n < 0:
-            e = VpbsError("status %d: %s" % (n, err.value.decode()))
-            e.status = n
-            raise e
+            raise self._fail("", n, err.value.decode())
         return out[:n].tobytes()
 
     def last_run(self):
@@ -2826,7 +2676,7 @@ class Aggregator:
         proven.  With the device witness on, the level-l nodes of ALL trees share the device batches.  on_aggregate(t, bytes) as they are made."""
         counts = [len(b) for b in blob_lists]
         aggregate_many_args(counts, levels=self.levels)
-        buf, offs = pack_proofs([b for blobs in blob_lists for b in blobs])
+        _, data, offs, _, _ = _packed([b for blobs in blob_lists for b in blobs])
         cnt = np.asarray(counts, np.uint64)
         out, raised = [None] * len(counts), []
 
@@ -2839,15 +2689,11 @@ class Aggregator:
                 raised.append(e)
         cb = AGGREGATE_TREE_FN(take)
         err = C.create_string_buffer(512)
-        data = buf.ctypes.data_as(C.POINTER(C.c_uint8)) if buf.size else (C.c_uint8 * 1)()
-        n = lib().vpbs_aggregator_run_many(self.h, data, offs.ctypes.data_as(C.POINTER(C.c_size_t)),
-                                           cnt.ctypes.data_as(C.POINTER(C.c_size_t)), len(counts), cb, None, err, 512)
+        n = lib().vpbs_aggregator_run_many(self.h, data, offs, cnt.ctypes.data_as(SZP), len(counts), cb, None, err, 512)
         if raised:
             raise raised[0]
         if n < 0:
-            e = VpbsError("status %d: %s" % (n, err.value.decode()))
-            e.status = n
-            raise e
+            raise self._fail("", n, err.value.decode())
         return out
 
     def test_preset_matrix(self, level, rows, pairs):
@@ -2862,59 +2708,38 @@ class Aggregator:
             raise VpbsError("vpbs_test_aggregator_preset_matrix: status %d" % rc)
         return out
 
-    def close(self):
-        if self.h:
-            lib().vpbs_aggregator_free(self.h)
-            self.h = None
-            self.ctx._batches.discard(self)
 
-    free = close
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class AggregateVerifier:
+class AggregateVerifier(_Handle):
     """vpbs_aggregate_verifier: verify_aggregate on the device -- leaf statements, LWE chains and the fold as kernels, the root proof through
     the batch verifier's stages -> the host's verdict and reason.  With on_device=True testvs, cts, out_cts and key_hashes are device pointers
     (ints) and n_testv / n_keys say how many rows the tables have; key_of and testv_of are host arrays in every mode.
     max_aggregates > 1 (vpbs_aggregate_verifier_create_many): verify_many / roots_many take up to that many aggregates -- max_leaves leaves
     in all -- in ONE device run, whose latency-bound chain is as long as that of one aggregate."""
+    _prefix = "vpbs_aggregate_verifier"
 
     def __init__(self, ctx, shape, max_leaves, max_aggregates=1):
-        self.ctx, self.shape, self.max_leaves, self.max_aggregates = ctx, shape, max_leaves, max_aggregates
-        self.h, err = C.c_void_p(), C.create_string_buffer(512)
-        rc = lib().vpbs_aggregate_verifier_create_many(ctx.h, C.byref(shape.c), max_leaves, max_aggregates, C.byref(self.h), err, 512)
-        if rc:
-            self.h = None
-            raise VpbsError("status %d: %s" % (rc, err.value.decode()))
-        ctx._batches.add(self)   # must not outlive its context: Context.close() frees the survivors
+        self.shape, self.max_leaves, self.max_aggregates = shape, max_leaves, max_aggregates
+        self._construct(ctx, ctx.h, C.byref(shape.c), max_leaves, max_aggregates, entry="create_many", what="")
 
     def _statement(self, who, count, testvs, cts, out_cts, key_hashes, key_of, testv_of, on_device, n_testv, n_keys):
+        """-> (the number of leaves, the statement as every entry point of the verifier takes it)"""
         s = self.shape
         if not on_device:
             n, tv, c, o, kh, ko, to = _aggregate_args(who, s.N, s.K, s.n_lwe, testvs, cts, out_cts, key_hashes, key_of, testv_of)
             if count is not None and n != count:
                 raise ValueError("%s: count = %d but the statement has %d leaves" % (who, count, n))
-            keep, ptv, n_tv, pto, pc, po, pkh, n_kh, pko = _aggregate_ptrs(tv, c, o, kh, ko, to)
-            return (keep, tv, c, o, kh, ko, to), n, (C.cast(ptv, C.c_void_p), n_tv, pto, C.cast(pc, C.c_void_p), C.cast(po, C.c_void_p),
-                                                     C.cast(pkh, C.c_void_p), n_kh, pko, 0)
+            return n, _aggregate_ptrs(tv, c, o, kh, ko, to) + (0,)
         if count is None or n_testv is None or n_keys is None:
             raise ValueError("%s: device pointers need count, n_testv and n_keys" % who)
-        idx = lambda a: None if a is None else np.ascontiguousarray(np.asarray(a), dtype=np.uint32)
-        ko, to = idx(key_of), idx(testv_of)
+        ko, to = (None if a is None else np.ascontiguousarray(np.asarray(a), dtype=np.uint32) for a in (key_of, testv_of))
         for a in (ko, to):
             if a is not None and a.shape != (count,):
                 raise ValueError("%s: key_of and testv_of are host arrays of %d entries" % (who, count))
-        p32 = lambda a: None if a is None else a.ctypes.data
-        return (ko, to), count, (int(testvs), n_testv, p32(to), int(cts), int(out_cts), int(key_hashes), n_keys, p32(ko), 1)
+        return count, (int(testvs), n_testv, _keep_u32(to), int(cts), int(out_cts), int(key_hashes), n_keys, _keep_u32(ko), 1)
 
     def root(self, testvs, cts, out_cts, key_hashes, key_of=None, testv_of=None, on_device=False, count=None, n_testv=None, n_keys=None):
         """aggregate_root computed on the device -> [4]"""
-        keep, count, a = self._statement("AggregateVerifier.root", count, testvs, cts, out_cts, key_hashes, key_of, testv_of, on_device, n_testv, n_keys)
+        count, a = self._statement("AggregateVerifier.root", count, testvs, cts, out_cts, key_hashes, key_of, testv_of, on_device, n_testv, n_keys)
         out, err = np.zeros(4, np.uint64), C.create_string_buffer(512)
         rc = lib().vpbs_aggregate_verifier_root(self.h, count, *a, _ptr(out), err, 512)
         if rc == 1:
@@ -2925,7 +2750,7 @@ class AggregateVerifier:
 
     def verify(self, blob, count, testvs, cts, out_cts, key_hashes, key_of=None, testv_of=None, on_device=False, n_testv=None, n_keys=None):
         """-> (verdict, reason): verify_aggregate's, for the same arguments"""
-        keep, count, a = self._statement("AggregateVerifier.verify", count, testvs, cts, out_cts, key_hashes, key_of, testv_of, on_device, n_testv, n_keys)
+        count, a = self._statement("AggregateVerifier.verify", count, testvs, cts, out_cts, key_hashes, key_of, testv_of, on_device, n_testv, n_keys)
         buf = (C.c_uint8 * max(1, len(blob))).from_buffer_copy(bytes(blob) or b"\0")
         err, reason = C.create_string_buffer(512), C.c_int(0)
         rc = lib().vpbs_aggregate_verifier_run(self.h, buf, len(blob), count, *a, C.byref(reason), err, 512)
@@ -2935,16 +2760,16 @@ class AggregateVerifier:
 
     def _many(self, who, counts, testvs, cts, out_cts, key_hashes, key_of, testv_of, on_device, n_testv, n_keys):
         first = aggregate_many_args(counts, self.max_leaves, self.max_aggregates, min(self.shape.levels, aggregate_depth(self.max_leaves)))
-        keep, total, a = self._statement(who, int(first[-1]), testvs, cts, out_cts, key_hashes, key_of, testv_of, on_device, n_testv, n_keys)
-        return (keep, first), first.size - 1, first.ctypes.data_as(C.POINTER(C.c_size_t)), a
+        _, a = self._statement(who, int(first[-1]), testvs, cts, out_cts, key_hashes, key_of, testv_of, on_device, n_testv, n_keys)
+        return first.size - 1, first.ctypes.data_as(SZP), a
 
     def roots_many(self, counts, testvs, cts, out_cts, key_hashes, key_of=None, testv_of=None, on_device=False, n_testv=None, n_keys=None):
         """the statement stages of many trees in one run: tree a owns the next counts[a] leaves of the per-leaf arrays -> (roots
         [n_agg][4], raw_bad uint8 [n_agg]: 1 where a raw word of that tree's statement is at or above p and its root means nothing)"""
-        keep, n_agg, first, a = self._many("AggregateVerifier.roots_many", counts, testvs, cts, out_cts, key_hashes, key_of, testv_of, on_device,
+        n_agg, first, a = self._many("AggregateVerifier.roots_many", counts, testvs, cts, out_cts, key_hashes, key_of, testv_of, on_device,
                                            n_testv, n_keys)
         out, bad, err = np.zeros((n_agg, 4), np.uint64), np.zeros(n_agg, np.uint8), C.create_string_buffer(512)
-        rc = lib().vpbs_aggregate_verifier_roots_many(self.h, n_agg, first, *a, _ptr(out.reshape(-1)), bad.ctypes.data_as(C.POINTER(C.c_uint8)), err, 512)
+        rc = lib().vpbs_aggregate_verifier_roots_many(self.h, n_agg, first, *a, _ptr(out.reshape(-1)), bad.ctypes.data_as(U8P), err, 512)
         if rc:
             raise VpbsError("status %d: %s" % (rc, err.value.decode()))
         return out, bad
@@ -2954,35 +2779,17 @@ class AggregateVerifier:
         verify_aggregate's (and verify's) verdict and reason for that blob on its slice of the statement"""
         if len(blobs) != len(counts):
             raise ValueError("AggregateVerifier.verify_many: %d blobs for %d leaf counts" % (len(blobs), len(counts)))
-        keep, n_agg, first, a = self._many("AggregateVerifier.verify_many", counts, testvs, cts, out_cts, key_hashes, key_of, testv_of, on_device,
+        n_agg, first, a = self._many("AggregateVerifier.verify_many", counts, testvs, cts, out_cts, key_hashes, key_of, testv_of, on_device,
                                            n_testv, n_keys)
-        buf, offs = pack_proofs(blobs)
-        buf, offs = np.ascontiguousarray(buf, dtype=np.uint8), np.ascontiguousarray(offs, dtype=np.uint64)
-        u8p = C.POINTER(C.c_uint8)
-        data = buf.ctypes.data_as(u8p) if buf.size else (C.c_uint8 * 1)()
-        verdicts, reasons, err = np.zeros(n_agg, np.uint8), np.zeros(n_agg, np.uint8), C.create_string_buffer(512)
-        rc = lib().vpbs_aggregate_verifier_run_many(self.h, data, offs.ctypes.data_as(C.POINTER(C.c_size_t)), n_agg, first, *a,
-                                                    verdicts.ctypes.data_as(u8p), reasons.ctypes.data_as(u8p), err, 512)
+        _, data, offs, results, ptrs = _packed(blobs, outputs=2)
+        err = C.create_string_buffer(512)
+        rc = lib().vpbs_aggregate_verifier_run_many(self.h, data, offs, n_agg, first, *a, *ptrs, err, 512)
         if rc < 0:
             raise VpbsError("status %d: %s" % (rc, err.value.decode()))
-        return verdicts, reasons
-
-    def close(self):
-        if self.h:
-            lib().vpbs_aggregate_verifier_free(self.h)
-            self.h = None
-            self.ctx._batches.discard(self)
-
-    free = close
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return results
 
 
-class Program:
+class Program(_Handle):
     """vpbs_program: a netlist of bootstraps on resident keys.  Wire w < n_inputs is input w, wire n_inputs + g the output of gate g; gate g
     bootstraps const * (0, .., 0, 1) + sum coef * wire[src] with test vector testvs[lut].  gates: a list of (terms=[(src, coef), ..], const, lut)
     in topological order, or the CSR arrays as a dict {gate_first, term_src, term_coef, gate_const, gate_lut}.  ctx=None gives a host-only
@@ -2991,6 +2798,7 @@ class Program:
     has `outputs` <= 2^log_slots output wires (the extractions of coefficients 0 .. outputs - 1 of its output GLWE, lwe_extract_at) and
     testvs[lut] is a packed test vector (lut_testv_multi); a 3-tuple is (.., 0, 1).  The CSR dict takes gate_log_slots and gate_outputs.
     Output j of gate g is wire n_inputs + out_first[g] + j (wires()); every per-gate result stays per gate: one proof for all its outputs."""
+    _prefix = "vpbs_program"
 
     def __init__(self, ctx, n_inputs, gates, n_luts):
         if isinstance(gates, dict):
@@ -3015,26 +2823,17 @@ class Program:
         if src.size != coef.size or const.size != lut.size or first.size != const.size + 1 or slots.size != lut.size or outs.size != lut.size:
             raise ValueError("Program: expected gate_first [n_gates + 1], term_src / term_coef [n_terms], gate_const / gate_lut "
                              "(/ gate_log_slots / gate_outputs) [n_gates]")
-        self.ctx, self.n_inputs, self.n_gates, self.n_luts = ctx, n_inputs, int(const.size), n_luts
+        self.n_inputs, self.n_gates, self.n_luts = n_inputs, int(const.size), n_luts
         self.gate_log_slots, self.gate_outputs = slots, outs
         self.n_wires = n_inputs + self.n_gates   # until the object says otherwise
         self.gate_first, self.term_src, self.term_coef, self.gate_const, self.gate_lut = first, src, coef, const, lut
         d = ProgramDescC(n_inputs, self.n_gates, n_luts, src.size, _ptr(first), src.ctypes.data_as(C.POINTER(C.c_uint32)), _ptr(coef), _ptr(const),
                          lut.ctypes.data_as(C.POINTER(C.c_uint32)))
-        h, err = C.c_void_p(), C.create_string_buffer(512)
         if multi:
-            k32 = np.zeros(1, np.uint32)
-            uip = lambda a: (a if a.size else k32).ctypes.data_as(C.POINTER(C.c_uint))
-            rc = lib().vpbs_program_create_multi(ctx.h if ctx is not None else None, C.byref(d), uip(slots), uip(outs), C.byref(h), err, 512)
+            self._construct(ctx, ctx.h if ctx is not None else None, C.byref(d), _keep_u32(slots), _keep_u32(outs), entry="create_multi")
         else:
-            rc = lib().vpbs_program_create(ctx.h if ctx is not None else None, C.byref(d), C.byref(h), err, 512)
-        if rc:
-            self.h = None
-            raise VpbsError("vpbs_program_create%s: status %d: %s" % ("_multi" if multi else "", rc, err.value.decode()))
-        self.h = h
+            self._construct(ctx, ctx.h if ctx is not None else None, C.byref(d))
         self.n_wires = self.wires()[1]
-        if ctx is not None:
-            ctx._batches.add(self)   # must not outlive its context: Context.close() frees the survivors
 
     def levels(self):
         """-> (level of every gate in the caller's order, np.uint32 [n_gates]; number of levels)"""
@@ -3075,16 +2874,13 @@ class Program:
 
     def run_device(self, bootstrapper, d_inputs, d_testvs, d_wires=None, d_gate_cts=None, d_out_cts=None):
         """the same on device pointers (integers; None = output not wanted); returns the number of levels when the outputs are in place"""
-        q = lambda x: C.c_void_p(int(x)) if x else None
-        rc = lib().vpbs_program_run(self.h, bootstrapper.h, q(d_inputs), q(d_testvs), q(d_wires), q(d_gate_cts), q(d_out_cts), 1)
+        rc = lib().vpbs_program_run(self.h, bootstrapper.h, _dev(d_inputs), _dev(d_testvs), _dev(d_wires), _dev(d_gate_cts), _dev(d_out_cts), 1)
         if rc < 0:
             raise VpbsError("vpbs_program_run: status %d: %s" % (rc, lib().vpbs_last_error(bootstrapper.ctx.h).decode()))
         return rc
 
     def _batch_fail(self, ring, rc):
-        e = VpbsError("vpbs_program_run_batch: status %d: %s" % (rc, lib().vpbs_last_error(ring.ctx.h).decode()))
-        e.status = rc
-        return e
+        return self._fail("vpbs_program_run_batch", rc, lib().vpbs_last_error(ring.ctx.h).decode())
 
     def run_batch(self, ring, inputs, key_of, testvs, gate_cts=True, out_cts=True):
         """ONE program for many input sets on a KeyRing: inputs [instances][n_inputs][n + 1], key_of [instances] slots, testvs [n_luts][N]
@@ -3115,8 +2911,8 @@ class Program:
         if ring is None or not ring.h:
             raise VpbsError("Program.run_batch_device: no ring (None, or a closed KeyRing)")
         ko = keyring_key_of(key_of, instances, ring.max_keys)
-        q = lambda x: C.c_void_p(int(x)) if x else None
-        rc = lib().vpbs_program_run_batch(self.h, ring.h, q(d_inputs), instances, _keep_u32(ko), q(d_testvs), q(d_wires), q(d_gate_cts), q(d_out_cts), 1)
+        rc = lib().vpbs_program_run_batch(self.h, ring.h, _dev(d_inputs), instances, _keep_u32(ko), _dev(d_testvs), _dev(d_wires), _dev(d_gate_cts),
+                                          _dev(d_out_cts), 1)
         if rc < 0:
             raise self._batch_fail(ring, rc)
         return rc
@@ -3152,9 +2948,7 @@ class Program:
         if e is not None:
             raise e
         if n < 0:
-            e = VpbsError("%s: status %d: %s" % (name, n, err.value.decode()))
-            e.status = n
-            raise e
+            raise _Handle._fail(name, n, err.value.decode())
         if failed is not None and failed[0]:
             raise PbsProveError(dict(failed[0]), *failed[1:])
 
@@ -3192,17 +2986,6 @@ class Program:
         self._proving_done("vpbs_program_prove_batch", rp, n, err, raised, (failures, flat, out, wires))
         return [flat[b * G:(b + 1) * G] for b in range(B)], wires, out
 
-    @staticmethod
-    def _packed(blobs, shape, outputs):
-        """the proofs of a verifying call in one buffer -> (bytes pointer, offsets pointer, `outputs` np.uint8 arrays of `shape` for the
-        verdicts and reasons, their pointers)"""
-        buf, offs = pack_proofs(blobs)
-        buf, offs = np.ascontiguousarray(buf, dtype=np.uint8), np.ascontiguousarray(offs, dtype=np.uint64)
-        u8p = C.POINTER(C.c_uint8)
-        data = buf.ctypes.data_as(u8p) if buf.size else (C.c_uint8 * 1)()
-        outs = tuple(np.zeros(shape, np.uint8) for _ in range(outputs))
-        return data, offs.ctypes.data_as(C.POINTER(C.c_size_t)), outs, [o.ctypes.data_as(u8p) for o in outs]
-
     def verify(self, pbs_verifier, inputs, testvs, out_cts, proofs):
         """out_cts [n_gates][K][N]: the claimed output GLWEs; proofs: list of bytes in gate order -> (verdicts, reasons, proof_reasons),
         np.uint8 [n_gates] each.  The program is proven iff every verdict is 1."""
@@ -3211,7 +2994,7 @@ class Program:
         o = _u64(out_cts).reshape(-1)
         if o.size != self.n_gates * v.K * v.N or len(proofs) != self.n_gates:
             raise ValueError("Program.verify: expected out_cts [%d][K][N] and %d proofs" % (self.n_gates, self.n_gates))
-        data, offs, results, ptrs = self._packed(proofs, self.n_gates, 3)
+        _, data, offs, results, ptrs = _packed(proofs, shape=self.n_gates, outputs=3)
         p = _keep_ptr
         rc = lib().vpbs_program_verify(self.h, v.h, p(x), p(tv), p(o), data, offs, *ptrs)
         if rc < 0:
@@ -3233,13 +3016,11 @@ class Program:
         o = _u64(out_cts).reshape(-1)
         if o.size != B * G * rv.K * rv.N or len(proofs) != B or any(len(row) != G for row in proofs):
             raise ValueError("Program.verify_batch: expected out_cts [%d][%d][K][N] and proofs [%d][%d]" % (B, G, B, G))
-        data, offs, results, ptrs = self._packed([blob for row in proofs for blob in row], (B, G), 3)
+        _, data, offs, results, ptrs = _packed([blob for row in proofs for blob in row], shape=(B, G), outputs=3)
         err, p = C.create_string_buffer(512), _keep_ptr
         rc = lib().vpbs_program_verify_batch(self.h, rv.h, p(x), B, _keep_u32(ko), p(tv), p(o), data, offs, *ptrs, err, 512)
         if rc < 0:
-            e = VpbsError("vpbs_program_verify_batch: status %d: %s" % (rc, err.value.decode()))
-            e.status = rc
-            raise e
+            raise self._fail("vpbs_program_verify_batch", rc, err.value.decode())
         return results
 
     def prove_aggregate(self, pbs_prover, aggregator, inputs, testvs, on_proof=None):
@@ -3252,7 +3033,7 @@ class Program:
         raised = []
         cb, err, p = self._gate_proof_fn(on_proof, raised), C.create_string_buffer(512), _keep_ptr
         blob = np.zeros(aggregator.max_bytes, np.uint8)
-        n = lib().vpbs_program_prove_aggregate(self.h, pp.h, aggregator.h, p(x), p(tv), p(wires), p(out), blob.ctypes.data_as(C.POINTER(C.c_uint8)),
+        n = lib().vpbs_program_prove_aggregate(self.h, pp.h, aggregator.h, p(x), p(tv), p(wires), p(out), blob.ctypes.data_as(U8P),
                                                blob.size, None, cb, None, err, 512)
         self._proving_done("vpbs_program_prove_aggregate", pp, n, err, raised)
         return blob[:n].tobytes(), wires, out
@@ -3306,29 +3087,12 @@ class Program:
                                             instances=B)
         if len(blobs) != B:
             raise ValueError("Program.verify_aggregate_batch: %d blobs for %d instances" % (len(blobs), B))
-        data, offs, results, ptrs = self._packed(blobs, B, 2)
+        _, data, offs, results, ptrs = _packed(blobs, shape=B, outputs=2)
         err, p = C.create_string_buffer(512), _keep_ptr
         rc = lib().vpbs_program_verify_aggregate_batch(self.h, av.h, p(x), B, _keep_u32(ko), p(kh), kh.shape[0], p(tv), p(o), data, offs, *ptrs, err, 512)
         if rc < 0:
-            e = VpbsError("vpbs_program_verify_aggregate_batch: status %d: %s" % (rc, err.value.decode()))
-            e.status = rc
-            raise e
+            raise self._fail("vpbs_program_verify_aggregate_batch", rc, err.value.decode())
         return results
-
-    def close(self):
-        if self.h:
-            lib().vpbs_program_free(self.h)
-            self.h = None
-            if self.ctx is not None:
-                self.ctx._batches.discard(self)
-
-    free = close
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 ERR_INVALID = -1   # VPBS_ERR_INVALID
@@ -3374,28 +3138,18 @@ def ntt_params(log_n):
     return roots, inv, int(ninv[0])
 
 
-class Batch:
-    """Device-resident PolynomialBatch handle (fri/oracle.rs)."""
+class Batch(_Handle):
+    """Device-resident PolynomialBatch handle (fri/oracle.rs).  A batch must not outlive its context (Context.close() frees the
+    survivors); one that did is only forgotten: vpbs_batch_free reaches into the context."""
+    _prefix = "vpbs_batch"
+    _owns = property(lambda self: bool(self.ctx.h))
 
     def __init__(self, ctx, handle):
-        self.ctx, self.h = ctx, handle
+        self.h = handle
         self.ncols = lib().vpbs_batch_ncols(handle)
         self.log_n = lib().vpbs_batch_log_n(handle)
         self.n = 1 << self.log_n
-        ctx._batches.add(self)
-
-    def free(self):
-        """vpbs_batch_free; a batch must not outlive its context (Context.close() frees the survivors)."""
-        if self.h and self.ctx.h:
-            lib().vpbs_batch_free(self.h)
-        self.h = None
-        self.ctx._batches.discard(self)
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
+        self._created(ctx)
 
     def cap(self):
         out = np.zeros((1 << self.ctx.cap_height, 4), np.uint64)
@@ -3440,8 +3194,8 @@ class Context:
 
     def close(self):
         if self.h:
-            for b in list(self._batches):
-                b.free()
+            for b in list(self._batches):   # every _Handle made on this context that is still open
+                b.close()
             lib().vpbs_ctx_destroy(self.h)
             self.h = None
 
@@ -3453,9 +3207,7 @@ class Context:
 
     def _check(self, rc):
         if rc:
-            e = VpbsError("status %d: %s" % (rc, lib().vpbs_last_error(self.h).decode()))
-            e.status = rc
-            raise e
+            raise _Handle._fail("", rc, lib().vpbs_last_error(self.h).decode())
 
     def synchronize(self):
         self._check(lib().vpbs_ctx_synchronize(self.h))
@@ -3542,10 +3294,8 @@ class Context:
         if proof_out is None:
             words = lib().vpbs_fri_proof_words(C.byref(params), degree_bits, ncols, len(oracles))
             if words == 0:   # parameters the library refuses as a whole: nothing to size a proof by
-                e = VpbsError("status %d: vpbs_fri_proof_words refuses these FRI parameters at degree 2^%d (rounds, arities, cap height, "
-                              "query rounds or tree count)" % (ERR_INVALID, degree_bits))
-                e.status = ERR_INVALID
-                raise e
+                raise _Handle._fail("", ERR_INVALID, "vpbs_fri_proof_words refuses these FRI parameters at degree 2^%d (rounds, arities, cap "
+                                    "height, query rounds or tree count)" % degree_bits)
             proof = np.zeros(words, np.uint64)
         else:
             proof = proof_out
