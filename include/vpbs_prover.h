@@ -1084,6 +1084,26 @@ int vpbs_lut_testv(unsigned log_N, unsigned p, const uint64_t* table, uint64_t d
 int vpbs_lwe_decode_batch(vpbs_ctx* ctx, const uint64_t* s_lwe, int key_on_device, const uint64_t* cts, size_t count, unsigned n_lwe, uint64_t delta,
                           uint64_t modulus, const uint64_t* expected /* [count] or NULL */, uint64_t* phase_out, uint64_t* msg_out,
                           uint64_t* err_out, vpbs_noise_stats* stats /* accumulated into, may be NULL */, int on_device /* vpbs_decode_where */);
+/* vpbs_lwe_rotation_batch: what a bootstrap of each row will look up, from the row and the LWE key alone (csrc/rotation.h).  The
+ * bootstrap never rounds the phase: it rounds every word by itself and rotates the test vector by the sum.  With L = log_N + 1, s_lwe [n_lwe]
+ * words that are 0 or 1, snap the function of vpbs_lwe_snap and ms(w) = (w >> (64 - L)) + ((w >> (64 - L - 1)) & 1):
+ *   w_i  = snap(cts[row][i], log_N, log_slots)                 (log_slots 0: the reduced word; snapped rows are fixed points, pass them with 0)
+ *   R    = (ms(-w_n) + sum over i < n_lwe with s_i = 1 of ms(w_i)) mod 2N,  mu = (2N - R) mod 2N                          -> rot_out
+ *   PREDICTION CONTRACT: with noise-free keys and an exact decomposition, coefficient j of the phase of the bootstrap's output GLWE under
+ *   test vector testv is E(mu + j), indices mod 2N: E(x) = testv[x] for x < N, -testv[x - N] otherwise.
+ *   With the p of vpbs_lut_testv, block = N / p, h = block / 2:
+ *   idx  = ((mu + h) / block) mod 2p: the table position the bootstrap reads, [p, 2p) the negated half                        -> idx_out
+ *   ref  = expected_i mod 2p when expected is given, else idx
+ *   dev  = (mu - ref * block) mod 2N, centred into [-N, N), a two's-complement word                                           -> dev_out
+ *   failure: expected given and idx != ref
+ * Pointers, on_device (vpbs_decode_where) and stats (ADDED to, with err := dev) are vpbs_lwe_decode_batch's; ctx NULL runs on the host.  Refused
+ * with nothing launched: null s_lwe / cts (as in vpbs_lwe_decode_batch, a null cts with count == 0 is an empty batch and returns 0), n_lwe 0 or >= 2^24, log_N outside 1 .. 16, log_slots > log_N, p 0, not a power of two or above N,
+ * more than 2^31 rows, device flags without a context, and a key word that is neither 0 nor 1 after reduction: the message names the first
+ * such index (a key on the device is checked there, by the launch itself; outputs may then have been written, stats is left as it was). */
+int vpbs_lwe_rotation_batch(vpbs_ctx* ctx, const uint64_t* s_lwe, int key_on_device, const uint64_t* cts, size_t count, unsigned n_lwe,
+                            unsigned log_N, unsigned log_slots, unsigned p, const uint64_t* expected /* [count] or NULL */,
+                            uint64_t* rot_out /* mu */, uint64_t* idx_out, uint64_t* dev_out /* any may be NULL */,
+                            vpbs_noise_stats* stats /* added to; err := dev */, int on_device /* vpbs_decode_where */);
 
 /* ---- seeded keys and ciphertexts: a client's own secrets, expanded on the device (csrc/keygen.hip, csrc/key_seeded.hip, csrc/lwe_client.hip) ----
  * The SPLIT generator (csrc/keygen_streams.h): the streams of kind BSK_MASK, KSK_MASK and LWE_MASK are keyed by a public mask_seed, all other

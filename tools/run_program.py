@@ -5,7 +5,7 @@ user had to before api.Program existed (the baseline leg: Bootstrapper.run per l
 compared wire by wire.  One JSON line.
 
 usage: tools/run_program.py [--levels L] [--width W] [--fan-in F] [--program FILE.json] [--n8] [--prove] [--baseline] [--runs R] [--seed S]
-                            [--instances B --keys M [--verify-per-instance]] [--multi THETA] [--aggregate [--aggregate-device [MAX_NODES]]]
+                            [--instances B --keys M [--verify-per-instance]] [--multi THETA [--margins]] [--aggregate [--aggregate-device [MAX_NODES]]]
   --aggregate (with --prove, alone or with --instances B --keys M): ONE proof per program instance.  The gate proofs of
     every instance are folded by an api.Aggregator (api.Program.prove_aggregate / prove_aggregate_batch; the level circuits are located as
     data: tools/export_circuits.py --aggregate N K ELL LOGB n_lwe log_n levels makes them, and the program may have at most 2^levels gates);
@@ -21,7 +21,9 @@ usage: tools/run_program.py [--levels L] [--width W] [--fan-in F] [--program FIL
     numpy; every output of both legs is decrypted under its key (api lwe_decode_batch) against the tables and the failures are reported,
     not judged: they are the price of the snap.  Prints gates, proofs and evaluation seconds of both legs, and with --prove the proving
     and verifying seconds and the total proof bytes.  Works alone (Program.run / prove / verify) and with --instances B --keys M
-    (run_batch / prove_batch / verify_batch).
+    (run_batch / prove_batch / verify_batch).  --margins (with --multi): api.Program.margins of each leg's gate inputs against the message
+    every gate reads, per level -- count, failures, the deviation in positions and NoiseStats.tail_log2 at N / (2p) - 2^THETA -- in
+    "margins", beside the decryption failures.
   netlist: W inputs, L layers of W gates; a gate reads F wires of the layer before it with coefficients in {1, p - 1}; gate 0 of every layer
     is the identity of gate 0 of the layer before it (fan-in 1, coefficient 1), so that one output has a known message whatever F is.
   --program: {"n_inputs", "n_luts", "gates": [{"terms": [[src, coef], ..], "const", "lut"}, ..]} instead; lut 0 is the test vector of the
@@ -522,6 +524,22 @@ def main_multi(args):
             leg["verified"] = int(verdicts.sum())
             leg["proven_wires_equal"] = bool((p_wires == wires).all())
             ok = ok and leg["verified"] == rows and leg["proven_wires_equal"]
+        if args.margins:   # what every gate's bootstrap looks up (Program.margins), per level, beside the decryption failures below
+            slots = s if name == "multi" else 1
+            bound = N // (2 * p) - slots
+            per_level = None
+            for b in range(B):
+                known = expected[b]
+                m_in = [int(known[g]) if lv == 0 else int(known[W + ((lv - 1) * W + g) * s + main_out[lv * W + g]])
+                        for lv in range(L) for g in range(W) for _ in range(s // slots)]
+                if batched:
+                    cts = prog.run_batch(ring, inputs[b:b + 1], key_of[b:b + 1], testvs, out_cts=False)[1][0]
+                else:
+                    cts = prog.run(bss[0], inputs[0], testvs, out_cts=False)[1]
+                per_level = prog.margins(ctx, host[key_of[b]]["s_lwe"], cts, [p] * testvs.shape[0], expected=m_in, N=N, stats=per_level)[3]
+            leg["margins"] = [{"level": lv + 1, "count": st.count, "failures": st.failures, "std_positions": st.std(),
+                               "mean_positions": st.mean(), "max_abs_positions": st.max_abs, "margin_positions": bound,
+                               "tail_log2_at_margin": st.tail_log2(bound)} for lv, st in enumerate(per_level)]
         prog.close()
         # every output wire under its own key, through lwe_decode_batch: failures = decoded message != the table's entry
         stats = api.NoiseStats()
@@ -560,6 +578,7 @@ def main():
     ap.add_argument("--keys", type=int, default=1)
     ap.add_argument("--verify-per-instance", action="store_true")
     ap.add_argument("--multi", type=int)
+    ap.add_argument("--margins", action="store_true")
     ap.add_argument("--aggregate", action="store_true")
     ap.add_argument("--aggregate-device", type=int, nargs="?", const=32, default=None, metavar="MAX_NODES")
     args = ap.parse_args()
@@ -567,6 +586,8 @@ def main():
         raise SystemExit("--aggregate-device [max_nodes] (at least 1; default 32) is a switch of --prove --aggregate")
     if args.aggregate and (not args.prove or args.multi is not None):
         raise SystemExit("--aggregate folds the gate proofs of --prove into one proof per instance: it needs --prove and cannot run with --multi")
+    if args.margins and args.multi is None:
+        raise SystemExit("--margins reports the rotation margins of the --multi legs: it needs --multi THETA")
     if args.multi is not None:
         if args.baseline or args.program:
             raise SystemExit("--multi builds its own netlist and both legs: it cannot run with --baseline or --program")

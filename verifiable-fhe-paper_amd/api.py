@@ -397,6 +397,7 @@ SIGNATURES = {
     "vpbs_lwe_encrypt_batch": (_I, [_VP, C.POINTER(KeygenParamsC), _VP, _I, _VP, _SZ, _U64, _VP, _I]),
     "vpbs_lut_testv": (_I, [_UI, _UI, U64P, _U64, U64P]),
     "vpbs_lwe_decode_batch": (_I, [_VP, _VP, _I, _VP, _SZ, _UI, _U64, _U64, _VP, _VP, _VP, _VP, C.POINTER(NoiseStatsC), _I]),
+    "vpbs_lwe_rotation_batch": (_I, [_VP, _VP, _I, _VP, _SZ, _UI, _UI, _UI, _UI, _VP, _VP, _VP, _VP, C.POINTER(NoiseStatsC), _I]),
     "vpbs_keygen_seeded": (_I, [_VP, C.POINTER(KeygenParamsC), _U64, _VP, _VP, U64P, U64P, U64P, _VP, _VP, _I]),
     "vpbs_key_expand": (_I, [_VP, C.POINTER(TfheParamsC), _UI, _U64, _VP, _VP, _I, _VP, _VP, _I]),
     "vpbs_lwe_encrypt_seeded_batch": (_I, [_VP, C.POINTER(KeygenParamsC), _U64, _VP, _I, _VP, _SZ, _U64, _VP, _I]),
@@ -1528,6 +1529,30 @@ class NoiseStats:
             return 0.0
         return math.sqrt(Fraction(self.count * self.sum_sq - self.sum_signed ** 2, self.count ** 2))
 
+    @staticmethod
+    def _ln_erfc(x):
+        """ln erfc(x); beyond x = 25, where erfc nears the smallest doubles, its asymptotic series (next term below 1e-11 there)"""
+        if x < 25.0:
+            return math.log(math.erfc(x))
+        y = 1.0 / (2.0 * x * x)
+        return -x * x - math.log(x * math.sqrt(math.pi)) + math.log1p(-y + 3.0 * y * y - 15.0 * y ** 3 + 105.0 * y ** 4)
+
+    def tail_log2(self, bound):
+        """log2 of P(|X| > bound) for X Gaussian with the exact mean and variance of this struct: a MODEL of the tail, not a measurement of
+        it.  What the struct holds decides how far the model can be trusted: a sum of bounded roundings (the rotation error of
+        lwe_rotation_batch at sigma 0: n + 1 terms, each within half a step) has LIGHTER tails than a Gaussian of its variance, so there
+        the figure is pessimistic; the ciphertext's own noise (lwe_decode_batch's err, and its share of dev) IS Gaussian, so there it is
+        the tail.  Stable for large arguments (erfc's asymptotic series in logarithms): finite wherever the variance is not zero.  With
+        zero variance: 0.0 if |mean| > bound, else -inf."""
+        if not self.count:
+            raise ValueError("NoiseStats.tail_log2: an empty struct")
+        m, s, b = self.mean(), self.std(), float(bound)
+        if s == 0.0:
+            return 0.0 if abs(m) > b else -math.inf
+        hi, lo = self._ln_erfc((b - m) / (s * math.sqrt(2.0))), self._ln_erfc((b + m) / (s * math.sqrt(2.0)))
+        top = max(hi, lo)
+        return (top + math.log(math.exp(hi - top) + math.exp(lo - top)) - math.log(2.0)) / math.log(2.0)
+
     def as_dict(self):
         return {"count": self.count, "failures": self.failures, "max_abs": self.max_abs, "sum_abs": self.sum_abs, "sum_sq": self.sum_sq,
                 "sum_signed": self.sum_signed, "hist": self.hist}
@@ -1634,28 +1659,32 @@ def _seeded_add_args(obj, bsk_bodies, ksk_bodies, bodies_on_device):
 
 
 DECODE_OUTPUTS = ("phase", "msg", "err")
+ROTATION_OUTPUTS = ("rot", "idx", "dev")
 
 
-def _lwe_decode_batch(ctx, s_lwe, cts, delta, modulus, expected, count, stats, want, n_lwe):
+def _lwe_rows_batch(who, names, call, host_text, ctx, s_lwe, cts, expected, count, stats, want, n_lwe):
+    """the body of the two calls that turn rows [count][n + 1] into three words per row and a tally (vpbs_lwe_decode_batch,
+    vpbs_lwe_rotation_batch): names are the three outputs (the last one signed), call(h, key pointer, key_on_device, cts, count, n, expected,
+    the three output pointers, stats, where) the entry point; host_text(key) words the refusal of a call without a context"""
     h = ctx.h if ctx is not None else None
     key = None if _is_dev(s_lwe) else _u64(s_lwe).reshape(-1)
     n = key.size if key is not None else n_lwe
     if n is None:
-        raise ValueError("lwe_decode_batch: a key on the device needs n_lwe")
-    if any(w not in DECODE_OUTPUTS for w in want):
-        raise ValueError("lwe_decode_batch: want names any of %r" % (DECODE_OUTPUTS,))
+        raise ValueError("%s: a key on the device needs n_lwe" % who)
+    if any(w not in names for w in want):
+        raise ValueError("%s: want names any of %r" % (who, names))
     rows = None if _is_dev(cts) else _u64(cts)
     if rows is not None:
         if rows.ndim != 2 or rows.shape[1] != n + 1 or (count is not None and count != rows.shape[0]):
-            raise ValueError("lwe_decode_batch: expected cts [count][%d]" % (n + 1))
+            raise ValueError("%s: expected cts [count][%d]" % (who, n + 1))
         count = rows.shape[0]
     elif count is None:
-        raise ValueError("lwe_decode_batch: ciphertexts on the device need count")
+        raise ValueError("%s: ciphertexts on the device need count" % who)
     if isinstance(want, dict) and rows is not None:
-        raise ValueError("lwe_decode_batch: device outputs need device ciphertexts")
+        raise ValueError("%s: device outputs need device ciphertexts" % who)
     exp = None if expected is None or _is_dev(expected) else _u64(expected).reshape(-1)
     if exp is not None and exp.size != count:
-        raise ValueError("lwe_decode_batch: expected must have count = %d entries" % count)
+        raise ValueError("%s: expected must have count = %d entries" % (who, count))
     keep = np.zeros(1, np.uint64)
     tmp, outs = None, {}
     try:
@@ -1667,22 +1696,44 @@ def _lwe_decode_batch(ctx, s_lwe, cts, delta, modulus, expected, count, stats, w
                 tmp = ctx.device_upload_new(exp if count else keep)
             pe = None if expected is None else tmp if exp is not None else int(expected)
         if where == 1:
-            po = [int(want[w]) if w in want else None for w in DECODE_OUTPUTS]
+            po = [int(want[w]) if w in want else None for w in names]
         else:
             outs = {w: np.zeros(count, np.uint64) for w in want}
-            po = [_keep_ptr(outs.get(w)) for w in DECODE_OUTPUTS]
-        rc = lib().vpbs_lwe_decode_batch(h, int(s_lwe) if key is None else key.ctypes.data, 1 if key is None else 0, pc, count, n, int(delta),
-                                         int(modulus), pe, po[0], po[1], po[2], C.byref(stats.c) if stats is not None else None, where)
+            po = [_keep_ptr(outs.get(w)) for w in names]
+        rc = call(h, int(s_lwe) if key is None else key.ctypes.data, 1 if key is None else 0, pc, count, n, pe, po,
+                  C.byref(stats.c) if stats is not None else None, where)
     finally:
         if tmp is not None:
             ctx.device_free(tmp)
     if rc:
-        raise VpbsError("vpbs_lwe_decode_batch: status %d: %s" % (rc, lib().vpbs_last_error(h).decode() if h else "bad arguments"))
+        raise VpbsError("vpbs_%s: status %d: %s" % (who, rc, lib().vpbs_last_error(h).decode() if h else host_text(key)))
     if where == 1:
         return None
-    if "err" in outs:
-        outs["err"] = outs["err"].view(np.int64)
+    if names[2] in outs:
+        outs[names[2]] = outs[names[2]].view(np.int64)
     return outs
+
+
+def _lwe_decode_batch(ctx, s_lwe, cts, delta, modulus, expected, count, stats, want, n_lwe):
+    def call(h, pkey, key_dev, pc, count, n, pe, po, pstats, where):
+        return lib().vpbs_lwe_decode_batch(h, pkey, key_dev, pc, count, n, int(delta), int(modulus), pe, po[0], po[1], po[2], pstats, where)
+    return _lwe_rows_batch("lwe_decode_batch", DECODE_OUTPUTS, call, lambda key: "bad arguments", ctx, s_lwe, cts, expected, count, stats, want,
+                           n_lwe)
+
+
+def _lwe_rotation_batch(ctx, s_lwe, cts, N, p, log_slots, expected, count, stats, want, n_lwe):
+    N = int(N)
+    if N < 2 or N & (N - 1):
+        raise ValueError("lwe_rotation_batch: N must be a power of two, 2 .. 2^16")
+
+    def call(h, pkey, key_dev, pc, count, n, pe, po, pstats, where):
+        return lib().vpbs_lwe_rotation_batch(h, pkey, key_dev, pc, count, n, N.bit_length() - 1, int(log_slots), int(p), pe, po[0], po[1], po[2],
+                                             pstats, where)
+
+    def host_text(key):   # no context to hold the text: name the first offending index here
+        bad = np.nonzero(key % np.uint64(P) > 1)[0] if key is not None else ()
+        return "key word %d is neither 0 nor 1" % bad[0] if len(bad) else "bad arguments"
+    return _lwe_rows_batch("lwe_rotation_batch", ROTATION_OUTPUTS, call, host_text, ctx, s_lwe, cts, expected, count, stats, want, n_lwe)
 
 
 def lwe_encrypt_batch(params, s_lwe, messages, nonce0=0):
@@ -1705,6 +1756,23 @@ def lwe_expand_batch(n_lwe, mask_seed, bodies, nonce0=0):
 def lwe_decode_batch(s_lwe, cts, delta, modulus, expected=None, stats=None, want=("msg",)):
     """vpbs_lwe_decode_batch on the host (null context); see Context.lwe_decode_batch"""
     return _lwe_decode_batch(None, s_lwe, cts, delta, modulus, expected, None, stats, want, None)
+
+
+def lwe_rotation_batch(s_lwe, cts, N, p, log_slots=0, expected=None, stats=None, want=("idx",)):
+    """vpbs_lwe_rotation_batch on the host (null context); see Context.lwe_rotation_batch"""
+    return _lwe_rotation_batch(None, s_lwe, cts, N, p, log_slots, expected, None, stats, want, None)
+
+
+def lut_expect(testv, mu, j=0):
+    """the prediction contract of vpbs_lwe_rotation_batch, stated once: E(mu + j), the phase of coefficient j of the output GLWE of a
+    bootstrap with rotation mu ("rot") under test vector testv [N] when the keys are noise-free and the decomposition exact; indices mod 2N,
+    E(x) = testv[x] for x < N and -testv[x - N] otherwise.  mu a number -> int, an array -> np.uint64 array"""
+    tv = _u64(testv).reshape(-1)
+    n = tv.size
+    x = (np.asarray(mu).astype(np.int64) + int(j)) % (2 * n)
+    v = tv[x % n] % np.uint64(P)
+    out = np.where(x >= n, (np.uint64(P) - v) % np.uint64(P), v)
+    return int(out) if out.ndim == 0 else out
 
 
 def _lwe_snap(ctx, N, log_slots, words, count=None, out_dev_ptr=None):
@@ -2872,6 +2940,42 @@ class Program(_Handle):
             raise VpbsError("vpbs_program_run: status %d: %s" % (rc, lib().vpbs_last_error(b.ctx.h).decode()))
         return wires, cts, out
 
+    def margins(self, ctx, s_lwe, gate_cts, p_of_lut, expected=None, *, N, n_lwe=None, stats=None):
+        """lwe_rotation_batch over the gate inputs of a run: gate_cts [n_gates][n + 1] as run() returns them (a host array, or a device
+        pointer as run_device() fills it), p_of_lut [n_luts] the p of every test vector, expected [n_gates] table positions or None ->
+        (mu, idx, dev, stats_per_level): three arrays [n_gates] in the caller's gate order (dev int64) and one NoiseStats per level of
+        levels().  The rows are already snapped, so every call passes log_slots 0; one call per level and p over host rows, per run of
+        consecutive gates of one level and p over a device pointer.  ctx None: on the host (host arrays only).  N: the ring size of the
+        bootstraps, which the program itself does not know; n_lwe: for a key on the device; stats: the list of an earlier call, added to
+        (a survey over many instances)."""
+        p_of_lut = [int(v) for v in p_of_lut]
+        if len(p_of_lut) != self.n_luts:
+            raise ValueError("Program.margins: p_of_lut must have n_luts = %d entries" % self.n_luts)
+        level, n_levels = self.levels()
+        dev_rows = _is_dev(gate_cts)
+        n = int(n_lwe) if _is_dev(s_lwe) else _u64(s_lwe).size
+        rows = None if dev_rows else _u64(gate_cts).reshape(self.n_gates, n + 1)
+        exp = None if expected is None else _u64(expected).reshape(-1)
+        if exp is not None and exp.size != self.n_gates:
+            raise ValueError("Program.margins: expected must have n_gates = %d entries" % self.n_gates)
+        p_of_gate = np.array([p_of_lut[l] for l in self.gate_lut], np.int64)
+        out = {w: np.zeros(self.n_gates, np.uint64) for w in ROTATION_OUTPUTS}
+        stats = [NoiseStats() for _ in range(n_levels)] if stats is None else stats
+        if len(stats) != n_levels:
+            raise ValueError("Program.margins: stats must hold one NoiseStats per level, %d" % n_levels)
+        for lv in range(1, n_levels + 1):
+            for p in sorted(set(p_of_gate[level == lv].tolist())):
+                pick = np.nonzero((level == lv) & (p_of_gate == p))[0]
+                # a device pointer: runs of consecutive gates; host rows: the whole group, gathered
+                groups = np.split(pick, np.nonzero(np.diff(pick) != 1)[0] + 1) if dev_rows else [pick]
+                for g in groups:
+                    cts = int(gate_cts) + 8 * (n + 1) * int(g[0]) if dev_rows else rows[g]
+                    got = _lwe_rotation_batch(ctx, s_lwe, cts, N, p, 0, None if exp is None else exp[g], g.size if dev_rows else None,
+                                              stats[lv - 1], ROTATION_OUTPUTS, n)
+                    for w in ROTATION_OUTPUTS:
+                        out[w][g] = got[w].view(np.uint64)
+        return out["rot"], out["idx"], out["dev"].view(np.int64), stats
+
     def run_device(self, bootstrapper, d_inputs, d_testvs, d_wires=None, d_gate_cts=None, d_out_cts=None):
         """the same on device pointers (integers; None = output not wanted); returns the number of levels when the outputs are in place"""
         rc = lib().vpbs_program_run(self.h, bootstrapper.h, _dev(d_inputs), _dev(d_testvs), _dev(d_wires), _dev(d_gate_cts), _dev(d_out_cts), 1)
@@ -3619,6 +3723,16 @@ class Context:
         or, for device ciphertexts, a dict name -> device pointer, filled in place (returns None).  stats: a NoiseStats that is ADDED to;
         expected makes err relative to expected * delta and counts msg != expected mod modulus as a failure."""
         return _lwe_decode_batch(self, s_lwe, cts_or_dev_ptr, delta, modulus, expected, count, stats, want, n_lwe)
+
+    def lwe_rotation_batch(self, s_lwe, cts_or_dev_ptr, N, p, log_slots=0, expected=None, count=None, stats=None, want=("idx",), n_lwe=None):
+        """vpbs_lwe_rotation_batch on the device: what a bootstrap of each row will look up, without running it.  The arguments
+        are lwe_decode_batch's, with the ring size N, the p of lut_testv and the gate's log_slots (0 for rows that are already snapped) in
+        the place of delta and modulus.  want: names among "rot" (mu: coefficient j of the output's phase is lut_expect(testv, mu, j)),
+        "idx" (the table position read; [p, 2p) is the negated half), "dev" (int64: positions between mu and the centre of the block of
+        expected, or of idx) -> dict of host arrays [count]; or, for device ciphertexts, a dict name -> device pointer, filled in place
+        (returns None).  stats: a NoiseStats that is ADDED to, over dev; expected counts idx != expected mod 2p as a failure.  The key's
+        words must be 0 or 1."""
+        return _lwe_rotation_batch(self, s_lwe, cts_or_dev_ptr, N, p, log_slots, expected, count, stats, want, n_lwe)
 
     def lwe_extract(self, glwe, n_lwe, count=None, N=None, K=None, out_dev_ptr=None):
         """vpbs_lwe_extract: Glwe::partial_sample_extract(n_lwe) of GLWEs [count][K][N] (or one [K][N]) -> [count][n_lwe + 1] (or [n_lwe + 1]).

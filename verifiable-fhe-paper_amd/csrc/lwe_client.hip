@@ -11,6 +11,8 @@
 //   decode:  8 (n + 1) bytes read per row, each word once; the key again from L2.  Statistics: lane 0 of a wave keeps limb sums in registers
 //            over its rows, the workgroup combines them in LDS (ds atomics), and 76 global vector atomics per workgroup -- at most, zero words
 //            are skipped -- add them to the launch's tally.  No workgroup waits for another; the host folds the tally into the caller's struct.
+//   rotation: vpbs_lwe_rotation_batch is decode's shape and traffic with the chain's own rounding in the place of the inner
+//            product: every word snapped and mod-switched by itself (rotation.h), the lane sums in u32, the same tally.
 //   seeded:  vpbs_lwe_encrypt_seeded_batch is encrypt without the row -- 8 bytes written per ciphertext, its body -- and vpbs_lwe_expand_batch
 //            writes the row back from a public mask_seed, the nonce and that body: 8 (n + 1) bytes written, 8 read, one mix64 per word.  The
 //            split generator of keygen_streams.h; mix64 is not a cryptographic generator.
@@ -21,6 +23,7 @@
 #include "context.h"
 #include "kernels.h"
 #include "keygen_streams.h"
+#include "rotation.h"
 
 namespace vpbs {
 namespace lwe_client {
@@ -187,6 +190,33 @@ __global__ void __launch_bounds__(THREADS) lwe_expand_kernel(u64 mask_seed, u64 
     }
 }
 
+// ---- the tally of a launch, shared by the decode and the rotation kernel: lane 0 of a wave keeps the sums over its rows in registers
+// (tally_add) and the histogram bin in LDS; the workgroup combines in LDS and adds its nonzero words to the launch's tally ----
+__device__ __forceinline__ void tally_open(unsigned long long* lds) {
+    for (unsigned i = threadIdx.x; i < T_WORDS; i += THREADS) lds[i] = 0;
+    __syncthreads();
+}
+__device__ __forceinline__ void tally_row(u64* mine, unsigned long long* lds, const Decoded& d) {
+    tally_add(mine, d);
+    atomicAdd(&lds[T_HIST + bit_length(d.abs)], 1ull);
+}
+__device__ __forceinline__ void tally_close(const u64* mine, unsigned long long* lds, unsigned long long* __restrict__ tally, unsigned lane) {
+    if (lane == 0) {
+#pragma unroll
+        for (unsigned i = 0; i < T_HIST; ++i) {
+            if (i == T_MAX) atomicMax(&lds[i], (unsigned long long)mine[i]);
+            else if (mine[i]) atomicAdd(&lds[i], (unsigned long long)mine[i]);
+        }
+    }
+    __syncthreads();
+    for (unsigned i = threadIdx.x; i < T_WORDS; i += THREADS) {
+        const unsigned long long v = lds[i];
+        if (!v) continue;
+        if (i == T_MAX) atomicMax(&tally[i], v);
+        else atomicAdd(&tally[i], v);
+    }
+}
+
 struct DecodeJob {
     u64 delta, modulus;
     unsigned n_lwe;
@@ -198,10 +228,7 @@ __global__ void __launch_bounds__(THREADS) lwe_decode_batch_kernel(DecodeJob j, 
                                                                    unsigned long long* __restrict__ tally) {
     __shared__ unsigned long long lds[T_WORDS];
     const unsigned lane = threadIdx.x % WAVE, wave = threadIdx.x / WAVE;
-    if (tally) {
-        for (unsigned i = threadIdx.x; i < T_WORDS; i += THREADS) lds[i] = 0;
-        __syncthreads();
-    }
+    if (tally) tally_open(lds);
     u64 mine[T_HIST] = {};   // lane 0's sums over the rows of this wave
     for (size_t c = (size_t)blockIdx.x * WAVES + wave; c < j.count; c += (size_t)gridDim.x * WAVES) {
         const u64* row = cts + c * ((size_t)j.n_lwe + 1);
@@ -220,27 +247,65 @@ __global__ void __launch_bounds__(THREADS) lwe_decode_batch_kernel(DecodeJob j, 
             if (phase_out) phase_out[c] = phase;
             if (msg_out) msg_out[c] = d.msg;
             if (err_out) err_out[c] = d.err;
-            if (tally) {
-                tally_add(mine, d);
-                atomicAdd(&lds[T_HIST + bit_length(d.abs)], 1ull);
+            if (tally) tally_row(mine, lds, d);
+        }
+    }
+    if (tally) tally_close(mine, lds, tally, lane);
+}
+
+// ---- rotation margins (rotation.h states the definitions): the decode kernel's shape with integer lane sums ----
+// a margin in the tally's terms: msg = idx, err = dev
+GL_HD Decoded as_decoded(const rotation::Margin& m) {
+    Decoded d;
+    d.msg = m.idx;
+    d.abs = m.abs;
+    d.neg = m.neg;
+    d.err = m.neg ? (u64)0 - m.abs : m.abs;
+    d.fail = m.fail;
+    return d;
+}
+struct RotationJob {
+    unsigned n_lwe, log_n, log_slots, p;
+    size_t count;
+};
+// One wave per row, every row word read once, the key from L2.  A lane adds the rotations of its words -- the body's, and a mask word's when
+// its key bit is 1 -- in u32 (2N divides 2^32); five xor shuffles give every lane the sum; lane 0 writes mu, idx and dev and tallies.  A key
+// word that is neither 0 nor 1 after reduction leaves the lowest such index in *first_bad (the same words for every row).
+__global__ void __launch_bounds__(THREADS) lwe_rotation_batch_kernel(RotationJob j, const u64* __restrict__ s_lwe, const u64* __restrict__ cts,
+                                                                     const u64* __restrict__ expected, u64* __restrict__ rot_out,
+                                                                     u64* __restrict__ idx_out, u64* __restrict__ dev_out,
+                                                                     unsigned long long* __restrict__ tally,
+                                                                     unsigned long long* __restrict__ first_bad) {
+    __shared__ unsigned long long lds[T_WORDS];
+    const unsigned lane = threadIdx.x % WAVE, wave = threadIdx.x / WAVE;
+    if (tally) tally_open(lds);
+    u64 mine[T_HIST] = {};   // lane 0's sums over the rows of this wave
+    for (size_t c = (size_t)blockIdx.x * WAVES + wave; c < j.count; c += (size_t)gridDim.x * WAVES) {
+        const u64* row = cts + c * ((size_t)j.n_lwe + 1);
+        unsigned acc = 0;
+#pragma unroll 4
+        for (unsigned i = lane; i <= j.n_lwe; i += WAVE) {
+            const u64 w = row[i];
+            if (i < j.n_lwe) {
+                const u64 s = gl::canon(s_lwe[i]);
+                if (s > 1) atomicMin(first_bad, (unsigned long long)i);
+                acc += s == 1 ? rotation::word_rotation(w, j.log_n, j.log_slots, false) : 0u;
+            } else {
+                acc += rotation::word_rotation(w, j.log_n, j.log_slots, true);   // one lane of the wave
             }
         }
-    }
-    if (!tally) return;
-    if (lane == 0) {
 #pragma unroll
-        for (unsigned i = 0; i < T_HIST; ++i) {
-            if (i == T_MAX) atomicMax(&lds[i], (unsigned long long)mine[i]);
-            else if (mine[i]) atomicAdd(&lds[i], (unsigned long long)mine[i]);
+        for (int m = WAVE / 2; m >= 1; m >>= 1) acc += (unsigned)__shfl_xor((int)acc, m, WAVE);
+        if (lane == 0) {
+            const rotation::Margin m = rotation::margin(acc, j.log_n, j.p, expected != nullptr, expected ? expected[c] : 0);
+            const Decoded d = as_decoded(m);
+            if (rot_out) rot_out[c] = m.mu;
+            if (idx_out) idx_out[c] = m.idx;
+            if (dev_out) dev_out[c] = d.err;
+            if (tally) tally_row(mine, lds, d);
         }
     }
-    __syncthreads();
-    for (unsigned i = threadIdx.x; i < T_WORDS; i += THREADS) {
-        const unsigned long long v = lds[i];
-        if (!v) continue;
-        if (i == T_MAX) atomicMax(&tally[i], v);
-        else atomicAdd(&tally[i], v);
-    }
+    if (tally) tally_close(mine, lds, tally, lane);
 }
 
 unsigned blocks_for(size_t count) { return (unsigned)std::min<size_t>((count + WAVES - 1) / WAVES, MAX_BLOCKS); }
@@ -478,6 +543,81 @@ int vpbs_lwe_decode_batch(vpbs_ctx* c, const uint64_t* s_lwe, int key_on_device,
             for (unsigned o = 0; o < 3; ++o)
                 if (host_out[o]) VPBS_HIP(hipMemcpyAsync(host_out[o], d_out[o], sizeof(u64) * count, hipMemcpyDeviceToHost, c->stream));
         VPBS_HIP(vpbs::stream_sync(c->stream));
+        if (stats) fold(t, stats);
+        return VPBS_OK;
+    } catch (const DeviceError& e) {
+        c->err = e.what;
+        return e.status;
+    }
+}
+
+int vpbs_lwe_rotation_batch(vpbs_ctx* c, const uint64_t* s_lwe, int key_on_device, const uint64_t* cts, size_t count, unsigned n_lwe, unsigned log_N,
+                            unsigned log_slots, unsigned p, const uint64_t* expected, uint64_t* rot_out, uint64_t* idx_out, uint64_t* dev_out,
+                            vpbs_noise_stats* stats, int on_device) {
+    using namespace vpbs;
+    using namespace vpbs::lwe_client;
+    const char* who = "vpbs_lwe_rotation_batch: ";
+    if (!s_lwe || (count && !cts)) return refuse(c, std::string(who) + "null pointer");
+    if (n_lwe < 1 || n_lwe >= (1u << 24)) return refuse(c, std::string(who) + "n_lwe must be 1 .. 2^24 - 1");
+    if (log_N < 1 || log_N > 16) return refuse(c, std::string(who) + "log_N must be 1 .. 16");
+    if (log_slots > log_N) return refuse(c, std::string(who) + "log_slots exceeds log_N");
+    if (p < 1 || (p & (p - 1)) || p > (1u << log_N)) return refuse(c, std::string(who) + "p must be a power of two, 1 .. N");
+    if (on_device < 0 || on_device > VPBS_DECODE_OUTPUTS_TO_HOST) return refuse(c, std::string(who) + "on_device must be 0, 1 or 2");
+    if (!c && (key_on_device || on_device)) return refuse(c, std::string(who) + "device pointers need a context");
+    if (count > MAX_COUNT) return refuse(c, std::string(who) + "more than 2^31 ciphertexts in one call");
+    auto bad_key = [&](size_t i) { return refuse(c, std::string(who) + "key word " + std::to_string(i) + " is neither 0 nor 1"); };
+    if (!key_on_device)
+        for (unsigned i = 0; i < n_lwe; ++i)
+            if (gl::canon(s_lwe[i]) > 1) return bad_key(i);
+    if (count == 0) return VPBS_OK;
+    const size_t ct_words = (size_t)n_lwe + 1;
+    if (!c) {
+        u64 t[T_WORDS] = {};
+        for (size_t r = 0; r < count; ++r) {
+            const u64* row = cts + r * ct_words;
+            unsigned acc = rotation::word_rotation(row[n_lwe], log_N, log_slots, true);
+            for (unsigned i = 0; i < n_lwe; ++i)
+                if (gl::canon(s_lwe[i])) acc += rotation::word_rotation(row[i], log_N, log_slots, false);
+            const rotation::Margin m = rotation::margin(acc, log_N, p, expected != nullptr, expected ? expected[r] : 0);
+            const Decoded d = as_decoded(m);
+            if (rot_out) rot_out[r] = m.mu;
+            if (idx_out) idx_out[r] = m.idx;
+            if (dev_out) dev_out[r] = d.err;
+            tally_add(t, d);
+            t[T_HIST + bit_length(d.abs)] += 1;
+        }
+        if (stats) fold(t, stats);
+        return VPBS_OK;
+    }
+    try {
+        VPBS_HIP(hipSetDevice(c->device));
+        Scratch tmp(c);
+        const bool in_dev = on_device != 0, out_dev = on_device == 1;
+        const u64* d_key = key_on_device ? s_lwe : tmp.upload(s_lwe, n_lwe);
+        const u64* d_cts = in_dev ? cts : tmp.upload(cts, count * ct_words);
+        const u64* d_exp = !expected ? nullptr : in_dev ? expected : tmp.upload(expected, count);
+        u64* host_out[3] = {rot_out, idx_out, dev_out};
+        u64* d_out[3];
+        for (unsigned o = 0; o < 3; ++o) d_out[o] = !host_out[o] ? nullptr : out_dev ? host_out[o] : tmp.words(count);
+        u64* d_tally = nullptr;
+        if (stats) {
+            d_tally = tmp.words(T_WORDS);
+            VPBS_HIP(hipMemsetAsync(d_tally, 0, sizeof(u64) * T_WORDS, c->stream));
+        }
+        u64* d_bad = tmp.words(1);
+        VPBS_HIP(hipMemsetAsync(d_bad, 0xFF, sizeof(u64), c->stream));
+        const RotationJob job{n_lwe, log_N, log_slots, p, count};
+        hipLaunchKernelGGL(lwe_rotation_batch_kernel, dim3(blocks_for(count)), dim3(THREADS), 0, c->stream, job, d_key, d_cts, d_exp, d_out[0],
+                           d_out[1], d_out[2], (unsigned long long*)d_tally, (unsigned long long*)d_bad);
+        VPBS_HIP(hipGetLastError());
+        u64 t[T_WORDS] = {}, bad = 0;
+        VPBS_HIP(hipMemcpyAsync(&bad, d_bad, sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+        if (stats) VPBS_HIP(hipMemcpyAsync(t, d_tally, sizeof(u64) * T_WORDS, hipMemcpyDeviceToHost, c->stream));
+        if (!out_dev)
+            for (unsigned o = 0; o < 3; ++o)
+                if (host_out[o]) VPBS_HIP(hipMemcpyAsync(host_out[o], d_out[o], sizeof(u64) * count, hipMemcpyDeviceToHost, c->stream));
+        VPBS_HIP(vpbs::stream_sync(c->stream));
+        if (bad != ~(u64)0) return bad_key((size_t)bad);   // a key on the device: found there; the struct is left as it was
         if (stats) fold(t, stats);
         return VPBS_OK;
     } catch (const DeviceError& e) {

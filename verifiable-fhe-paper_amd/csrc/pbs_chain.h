@@ -14,8 +14,9 @@ using gl::u64;
 
 constexpr size_t PBS_LDS_BUDGET = 160 * 1024;   // what one workgroup may declare on gfx950
 
-// rotation amount in [0, 2N]: top log2(2N) bits of the mask, rounded with the next bit (mod.rs:85-106); as tfhe.hip
-__device__ __forceinline__ unsigned pb_mod_switch(u64 mask, unsigned log_n_ring) {
+// rotation amount in [0, 2N]: top log2(2N) bits of the mask, rounded with the next bit (mod.rs:85-106); as tfhe.hip.  Host and device:
+// rotation.h predicts the chain's rotation from this very function (the kernels inline it to the instructions they had as a device function)
+GL_HD unsigned pb_mod_switch(u64 mask, unsigned log_n_ring) {
     const unsigned log2n = log_n_ring + 1;
     return (unsigned)(mask >> (64 - log2n)) + (unsigned)((mask >> (64 - log2n - 1)) & 1);
 }
